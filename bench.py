@@ -1,11 +1,19 @@
 """bench.py -- throughput of the Klatt hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg1|cfg3|cfg4] [--mode 0]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg1|cfg3|cfg4] [--mode 0] [--dump-outputs DIR] [--full]
 
 A step is one pass of the synthesis kernel over one batch of synthetic frame streams that is already resident in
 HBM (frames in, int16 PCM out, both in HBM).  The headline workload is BASELINE.json configs[2], the largest
 single-GPU configuration: 65 536 IPA utterances from sampleIpa.txt through the frame producer (1.5e9 samples per
-step); the other configurations are selectable and cfg1 (configs[1]) is measured as an extra key.
+step); the other configurations are selectable.
+
+A plain run sets the batch up, warms up, times the K steps and prints the result line (headline, HBM / VALU rooflines
+of the timed kernel).  --full adds everything else as extra keys: the repeated and page-locked set calls, the batch
+handed over as IPA text, MODE_FAST, the same batch without tracks / rotated / jittered / unsorted, the all-different
+and distinct batches, cfg1 (configs[1]) and its recipe at 65 536 utterances, the pipeline, single-stream and
+live-handle extras, configs[0] on the CPU, the CPU baseline and, at N > 1, configs[3] / [4] at their node sizes
+(--no-extras / --no-cpu-baseline leave parts of it out).  --dump-outputs DIR writes what the last timed step computed
+for a fixed, seeded sample of the utterances (dump_outputs below) as DIR/<name>.npy.
 
 N > 1: one process per GPU.  Under `torch.distributed.run` the ranks come from the environment; a plain
 `python bench.py --gpus N` starts its own N rank processes (the parent never touches the GPU, relays rank 0's JSON
@@ -50,13 +58,22 @@ def parse(argv=None):
     ap.add_argument("--utterances", type=int, default=0, help="override the batch size per GPU")
     ap.add_argument("--mode", type=int, default=0, help="arithmetic mode (include/speechPlayer_batch.h)")
     ap.add_argument("--layout", type=int, default=-1, help="-1: engine's choice, 1: stage-parallel workgroups, 0: one wavefront per 64 utterances")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (extra keys, CPU baseline; see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-extras", "--no-large-batch", dest="no_extras", action="store_true",
-                    help="skip the extra measurements (MODE_FAST, cfg1, cfg1 recipe at 65536 utterances)")
+                    help="with --full: leave out the extra measurements (other modes, batches and configurations)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall time to spend on the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's PCM (a fixed, seeded sample of the utterances) as DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="everything but the GPU: ranks, rendezvous (gloo), shard dealing, workload build, reductions; value is null")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dump-outputs needs the GPU run (--dry-run computes no PCM)")
+    return args
 
 
 def engine_source_digest():
@@ -362,6 +379,36 @@ def cpu_baseline(batch, target_seconds):
                       "1 thread: %.3g samples/s" % (n, batch.n_utt, reps, done, cores, dt, one_core)}
 
 
+DUMP_UTTERANCES = 256          # cfg2: ~6 M samples, 24 MB as float32
+DUMP_BYTES = 48 << 20          # what the samples of a dump may take at most (the whole PCM of cfg2 is 3 GB)
+
+
+def dump_outputs(bp, outdir, first, prefix=""):
+    """What a caller of the timed path receives, as the last timed step left it on the device: the PCM and the last index
+    marks of a fixed, seeded sample of the batch's utterances (the same ones on every run with the same arguments), read
+    through speechPlayer_batch_read / _getLastIndex.  Written as float32 / float64 .npy files under `outdir`:
+      pcm          the sampled utterances' int16 samples, concatenated (exact in float32)
+      pcm_offsets  where each sampled utterance starts in `pcm`, and the total at the end
+      utterances   the sampled utterances' indices in the node's batch
+      last_index   speechPlayer_batch_getLastIndex of each sampled utterance"""
+    import numpy as np
+    n = bp.nUtterances
+    pick = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_UTTERANCES), replace=False))
+    pcm, offsets, kept = [], [0], []
+    for u in pick:
+        x = bp.read(int(u))
+        if (offsets[-1] + len(x)) * 4 > DUMP_BYTES:
+            break
+        pcm.append(x); offsets.append(offsets[-1] + len(x)); kept.append(int(u))
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"pcm": np.concatenate(pcm).astype(np.float32) if pcm else np.zeros(0, np.float32),
+              "pcm_offsets": np.asarray(offsets, dtype=np.float64),
+              "utterances": np.asarray(kept, dtype=np.float64) + first,
+              "last_index": np.asarray([bp.getLastIndex(u) for u in kept], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, prefix + name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # N > 1 without a launcher: the parent starts the ranks itself
 # ------------------------------------------------------------------------------------------------------------------
@@ -470,7 +517,9 @@ def main():
     t_build = time.perf_counter() - t_build
     samples = int(batch.sample_counts().sum())
     bp = None
-    t_set = t_set_again = 0.0
+    extras = args.full and not args.no_extras     # a plain run measures the headline alone (parse: --full)
+    t_set = 0.0
+    t_set_again = None
     t_set_pinned = None
     compact = None
     if not dry:
@@ -480,14 +529,14 @@ def main():
                          batch["isnull"], batch["seeds"])
         t_set = time.perf_counter() - t_set       # classification, lane packing, track planning, uploads: outside the timed region
         assert bp.totalSamples == samples
-        # the same call again: what a batch costs a player that has set one before (device buffers allocated, the host's per-frame
-        # scratch sized and touched) -- the first call above also pays the allocations
-        t_set_again = time.perf_counter()
-        bp.setUtterances(batch["frame_start"], batch["frames"], batch["min"], batch["fade"], batch["index"],
-                         batch["isnull"], batch["seeds"])
-        t_set_again = time.perf_counter() - t_set_again
-        t_set_pinned = None
-        if world == 1 and not args.no_extras:
+        if args.full:
+            # the same call again: what a batch costs a player that has set one before (device buffers allocated, the host's per-frame
+            # scratch sized and touched) -- the first call above also pays the allocations
+            t_set_again = time.perf_counter()
+            bp.setUtterances(batch["frame_start"], batch["frames"], batch["min"], batch["fade"], batch["index"],
+                             batch["isnull"], batch["seeds"])
+            t_set_again = time.perf_counter() - t_set_again
+        if world == 1 and extras:
             # and with the frames in page-locked memory the library handed out (speechPlayer_hostAlloc): one DMA, classified and hashed on the device
             from nvspeechplayer_amd import host_array
             try:
@@ -501,7 +550,7 @@ def main():
                     bp.setUtterances(batch["frame_start"], fr, batch["min"], batch["fade"], batch["index"], batch["isnull"], batch["seeds"])
                     t_set_pinned = time.perf_counter() - t_set_pinned
                 del fr
-        if world == 1 and not args.no_extras and args.workload in ("cfg2", "cfg4"):
+        if world == 1 and extras and args.workload in ("cfg2", "cfg4"):
             # the same batch handed over as IPA text (speechPlayer_batch_setIpa / _setIpaVoices): the producer builds the distinct frame lists
             # as 32-byte records, the device expands them, utterances share their list's frames -- "build" is numpy writing the arguments
             try:
@@ -545,12 +594,14 @@ def main():
     elapsed, total_samples = reduce_throughput(elapsed, samples, dist, device=red_dev)   # max / sum over ranks
     info = bp.kernelInfo() if not dry else {}
     alg_bytes = batch.algorithmic_bytes()
+    if args.dump_outputs:      # before any extra launches something else on this player
+        dump_outputs(bp, args.dump_outputs, shard["first_utterance"], "rank%d_" % rank if world > 1 else "")
 
     # N > 1: BASELINE's node-wide configurations at their node sizes, as extra keys: configs[3] (world x 125 000 utterances cut to
     # 0.5 s: 10^6 at N = 8) and configs[4] (world x 32 voice variants x 16 384 utterances: 256 x 16 384 at N = 8).  Same deal (contiguous
     # shards of near-equal sample count), same barriers and reductions, 5 launches each.  --dry-run: the deal alone (closed-form lengths).
     node_extras = {}
-    if world > 1 and not args.utterances and not args.no_extras:
+    if world > 1 and not args.utterances and extras:
         from nvspeechplayer_amd.sharding import shard_bounds
         if bp is not None:
             bp.close(); bp = None
@@ -622,7 +673,7 @@ def main():
                        "shard_bounds": shard["bounds"], "process_group": None if dist is None else dist.get_backend(),
                        "world_size": 1 if dist is None else dist.get_world_size(),
                        "rccl_ranks": dist.get_world_size() if (dist is not None and dist.get_backend() == "nccl") else None,
-                       "host": {"build_batch_s": round(t_build, 3), "set_utterances_s": round(t_set, 3), "set_utterances_again_s": round(t_set_again, 3),
+                       "host": {"build_batch_s": round(t_build, 3), "set_utterances_s": round(t_set, 3), "set_utterances_again_s": None if t_set_again is None else round(t_set_again, 3),
                                 "set_utterances_page_locked_frames_s": None if t_set_pinned is None else round(t_set_pinned, 3),
                                 "from_ipa": compact,
                                 "note": "outside the timed region: the frame producer (build) and speechPlayer_batch_setUtterances (classification, "
@@ -646,7 +697,7 @@ def main():
                     "note": "declared bound: HBM (2 B per sample + 388 B per frame). What binds is f64 VALU issue with two barrier-coupled waves per SIMD: "
                             "see `valu` (ONE figure: issue cycles of the VALU instructions executed / issue cycles the 1024 SIMDs had at the held clock) "
                             "and DESIGN.md section 4, Roofline.  The headline leans on the benchmark's duplicates (8 sentences x 64 pitches share 105 tracks): "
-                            "`headline_without_tracks` and `general_case` on this line are the same sample count without that help"}
+                            "`headline_without_tracks` and `general_case` (--full) are the same sample count without that help"}
             # HBM bytes and VALU instructions per launch come from the PMC passes of tools/profile.sh (bench.py cannot run rocprofv3 on
             # itself); the file names the engine sources it was collected from, and is ignored when they have changed since
             try:
@@ -674,7 +725,7 @@ def main():
             except Exception:
                 pass
             out["roofline"] = roof
-            if world == 1 and args.mode == 0 and not args.no_extras:
+            if world == 1 and args.mode == 0 and extras:
                 # same batch in MODE_FAST (fused multiply-adds; held to <= 1 LSB and <= 5 one-LSB differences per million samples against the
                 # oracle, not bit-exact: the tracked stages measured 0 differences on the test corpus, the direct stages' pole recurrences 36 in
                 # 8.5 M samples of 350 000-sample fades)
@@ -684,7 +735,7 @@ def main():
                 bp.setOption("mode", 0)
                 out["mode_fast"] = {"value": samples / (fast_ms * 1e-3), "unit": "samples/s", "kernel_ms": fast_ms,
                                     "roofline_frac": alg_bytes / (fast_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
-            if world == 1 and args.mode == 0 and not args.no_extras and info.get("tracked"):
+            if world == 1 and args.mode == 0 and extras and info.get("tracked"):
                 # the same batch without tracks (every stage interpolates and evaluates exp/cos itself, as in round 1), and with every
                 # utterance's frame list rotated by a random amount -- same lengths, ~24 different timings per sentence in random
                 # order: the lane packing puts equally timed utterances side by side again
@@ -734,7 +785,7 @@ def main():
                 out["general_case"] = dict({k: v for k, v in out["all_different"].items() if k != "legacy"},
                                            what="nothing shared, nothing aligned (workloads.all_different: every frame's duration, fade and formants scaled by factors of its own): "
                                                 "the direct stages, two workgroups per CU; mode_fast: pole recurrences instead of polynomials")
-            if world == 1 and not args.utterances and not args.no_extras:
+            if world == 1 and not args.utterances and extras:
                 # the other single-GPU configuration (BASELINE configs[1], 4096 steady vowels) and its recipe at 65 536 utterances
                 bp.close()
                 for key, wl, n, reps in (("cfg1", "cfg1", 4096, 400), ("cfg1_recipe_at_batch_65536", "cfg1", 65536, 60)):
@@ -750,7 +801,7 @@ def main():
                                 "roofline_frac": xb.algorithmic_bytes() / (x_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "kernel": kernel_name(xi)}
                     bp.close()
                 bp = None
-            if world == 1 and not args.utterances and not args.no_extras and args.workload == "cfg2":
+            if world == 1 and not args.utterances and extras and args.workload == "cfg2":
                 # what the timed region leaves out, taken in: sustained throughput over eight distinct batches, host work overlapped
                 batch_keep = batch
                 # (sixteen batches: the first one's setUtterances has nothing to hide behind, and eight batches made that ramp a fifth of the figure)
@@ -767,13 +818,13 @@ def main():
                 out["pipeline"]["with_pcm_to_host"] = extra(copy_out=True, n_batches=8, players=6, workers=4)
                 out["pipeline"]["pageable_host_buffers"] = dict(extra(pinned=False, **same), with_pcm_to_host=extra(n_batches=8, players=6, workers=4, copy_out=True, pinned=False))
                 batch = batch_keep
-            if world == 1 and not args.no_extras:
+            if world == 1 and extras:
                 for key, fn in (("single_stream", single_stream_extra), ("live_handles", live_handles_extra), ("cfg0_cpu", cfg0_cpu_extra)):
                     try:
                         out[key] = fn()
                     except Exception as e:      # noqa: BLE001
                         out[key] = {"value": None, "error": "%s: %s" % (type(e).__name__, e)}
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and args.full and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(batch, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if bp is not None:

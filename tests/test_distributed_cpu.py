@@ -83,10 +83,10 @@ def test_bench_starts_its_own_ranks(tmp_path):
         halves = [int(counts[:b[1]].sum()), int(counts[b[1]:].sum())]
         assert abs(halves[0] - halves[1]) <= 2 * int(counts.max())                                # balanced by samples, not by count
         assert c["samples_per_gpu"] == halves[0]
-    # without --utterances the N > 1 run also carries BASELINE's node-wide configurations at their node sizes as extra keys
+    # without --utterances the N > 1 run with --full also carries BASELINE's node-wide configurations at their node sizes as extra keys
     # (--dry-run: the deal alone, from the closed-form lengths)
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "0"],
-                                  env=env, cwd=str(tmp_path), timeout=280)
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "0",
+                                   "--full"], env=env, cwd=str(tmp_path), timeout=280)
     d = json.loads([l for l in out.decode().splitlines() if l.startswith("{")][0])
     assert d["config"]["node_utterances"] == 2 * 65536 and d["config"]["rccl_ranks"] is None      # gloo here; RCCL reports its ranks
     for key, per_gpu, wl in (("cfg3_node", 125000, "cfg3"), ("cfg4_node", 32 * 16384, "cfg4")):
@@ -112,8 +112,8 @@ def test_bench_eight_ranks_dry_run(tmp_path):
     from nvspeechplayer_amd import workloads
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     before = resource.getrusage(resource.RUSAGE_CHILDREN).ru_maxrss
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dry-run", "--steps", "2", "--warmup", "0"],
-                                  env=env, cwd=str(tmp_path), timeout=850)
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dry-run", "--steps", "2", "--warmup", "0",
+                                   "--full"], env=env, cwd=str(tmp_path), timeout=850)
     peak_kb = resource.getrusage(resource.RUSAGE_CHILDREN).ru_maxrss      # the largest of the processes waited for: bench.py's ranks among them
     lines = [l for l in out.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1, out

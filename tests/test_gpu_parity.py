@@ -1063,6 +1063,42 @@ def test_bench_rccl_branch_at_world_size_one(tmp_path):
     assert c["host"]["set_utterances_s"] > 0 and c["host"]["first_launch_end_to_end_samples_per_s"] > 0
 
 
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` line is the headline alone (the extras come with --full), and --dump-outputs writes what the last timed
+    step computed for a seeded sample of the utterances: float32 / float64 .npy files, the same on a second run, the PCM and the
+    index marks the oracle gives for those utterances."""
+    import json
+    import subprocess
+    import sys
+    from nvspeechplayer_amd import workloads
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    names = ("pcm", "pcm_offsets", "utterances", "last_index")
+    dumps = []
+    for k in range(2):
+        outdir = tmp_path / ("dump%d" % k)
+        out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg3", "--utterances", "4000", "--steps", "3",
+                                       "--warmup", "1", "--dump-outputs", str(outdir)], env=env, cwd=str(tmp_path), timeout=600)
+        lines = [l for l in out.decode().splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 1e9 and d["dtype"] == "f64"
+        assert not set(d) & {"mode_fast", "tracks_off", "cfg1", "pipeline", "single_stream", "live_handles", "cfg0_cpu", "cpu_baseline"}
+        dumps.append({n: np.load(str(outdir / (n + ".npy"))) for n in names})
+    a, b = dumps
+    for n in names:
+        assert a[n].dtype in (np.float32, np.float64) and np.array_equal(a[n], b[n]), n
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    utt, off = a["utterances"].astype(np.int64), a["pcm_offsets"].astype(np.int64)
+    assert len(utt) == 256 and (np.diff(utt) > 0).all() and len(off) == 257 and off[-1] == len(a["pcm"])
+    batch = workloads.make("cfg3", 4000)
+    for j, u in enumerate(utt):
+        one = batch.slice(int(u), 1)
+        exp, _, _ = oracle.batch_synthesize(batch["sr"], one)
+        compare(a["pcm"][off[j]:off[j + 1]].astype(np.int16), exp, "utterance %d" % u)
+        assert a["last_index"][j] == int(oracle.batch_last_index(batch["sr"], one)[0])
+
+
 def test_error_codes_and_digest(ref):
     """speechPlayer_lastErrorCode: non-zero after a failed call, back to 0 after the next successful one; and the device-side
     digest against the same formula in numpy, per utterance, on a ragged batch (lengths 0, 1, 7, 8, 9, ... samples)."""

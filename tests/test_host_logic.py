@@ -66,7 +66,9 @@ def test_failures_carry_an_error_code():
         assert not L.speechPlayer_initialize(22050)
         assert _native.last_error_code() == 2 and "no HIP device" in _native.last_error()
         assert not L.speechPlayer_batch_create(22050, -1) and _native.last_error_code() == 2
-    assert L.speechPlayer_voiceCount() == 4
+    n = L.speechPlayer_voiceCount()          # the 4 presets, then the voices earlier tests of this process defined (speechPlayer_voiceDefine)
+    assert L.speechPlayer_voicePresetCount() == 4 and n >= 4
+    assert all(L.speechPlayer_voiceName(i) for i in range(n)) and L.speechPlayer_voiceName(n) is None
     assert L.speechPlayer_ipa_frames(b"h", 1.0, 100.0, 0.5, 0, None, None, None, None, None, 0) == 1     # host-only producer: no GPU needed
 
 

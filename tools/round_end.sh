@@ -6,33 +6,35 @@
 #   c: the probes (tracks, mixed, steady, direct stages with a kernel trace of the all-different batch; compact forms, sparse wavefronts),
 #      the live-handle bench
 #   d: the N > 1 path on the one GPU this box has: bench.py --gpus 2 with the node-sized extras (two ranks share the device, gloo)
-# Everything lands under gpurun_out/; the summaries are then copied into profiles/ (see profiles/README.md).
+# a, b and d write under $OUT (default: build/round_end/); the summaries are then copied into profiles/ (see profiles/README.md).
 R=r6
 mkdir -p gpurun_out
+export OUT=$(realpath -m "${OUT:-build/round_end}")
+mkdir -p "$OUT"
 # (A/B variant libraries and their objects are scratch: they would travel with every snapshot -- 131 MB at the end of round 4)
 rm -f nvspeechplayer_amd/build_tmp/libspeechPlayer_*.o nvspeechplayer_amd/lib/variants/*.so
 case "${1:-a}" in
 a)
-timeout -k 10 1100 python -m pytest tests -m gpu -x -q > gpurun_out/${R}_gputests.log 2>&1; tail -3 gpurun_out/${R}_gputests.log
-rm -f gpurun_out/${R}_pmc.json
-PMC_KEY=cfg2 PMC_JSON=$PWD/gpurun_out/${R}_pmc.json timeout -k 10 600 bash tools/profile.sh gpurun_out/prof_${R}_cfg2 --workload cfg2 > gpurun_out/prof_${R}_cfg2.log 2>&1
-timeout -k 10 600 bash tools/profile.sh gpurun_out/prof_${R}_cfg2_fast --workload cfg2 --mode 1 > gpurun_out/prof_${R}_cfg2_fast.log 2>&1
-PMC_KEY=cfg1 PMC_JSON=$PWD/gpurun_out/${R}_pmc.json timeout -k 10 600 bash tools/profile.sh gpurun_out/prof_${R}_cfg1 --workload cfg1 > gpurun_out/prof_${R}_cfg1.log 2>&1
-tail -30 gpurun_out/prof_${R}_cfg2/summary.txt; tail -12 gpurun_out/prof_${R}_cfg2_fast/summary.txt; tail -12 gpurun_out/prof_${R}_cfg1/summary.txt
+timeout -k 10 1100 python -m pytest tests -m gpu -x -q > $OUT/${R}_gputests.log 2>&1; tail -3 $OUT/${R}_gputests.log
+rm -f $OUT/${R}_pmc.json
+PMC_KEY=cfg2 PMC_JSON=$OUT/${R}_pmc.json timeout -k 10 600 bash tools/profile.sh $OUT/prof_${R}_cfg2 --workload cfg2 > $OUT/prof_${R}_cfg2.log 2>&1
+timeout -k 10 600 bash tools/profile.sh $OUT/prof_${R}_cfg2_fast --workload cfg2 --mode 1 > $OUT/prof_${R}_cfg2_fast.log 2>&1
+PMC_KEY=cfg1 PMC_JSON=$OUT/${R}_pmc.json timeout -k 10 600 bash tools/profile.sh $OUT/prof_${R}_cfg1 --workload cfg1 > $OUT/prof_${R}_cfg1.log 2>&1
+tail -30 $OUT/prof_${R}_cfg2/summary.txt; tail -12 $OUT/prof_${R}_cfg2_fast/summary.txt; tail -12 $OUT/prof_${R}_cfg1/summary.txt
 ;;
 b)
-[ -f gpurun_out/${R}_pmc.json ] && cp gpurun_out/${R}_pmc.json profiles/${R}_pmc.json
-timeout -k 10 500 python bench.py > gpurun_out/${R}_bench.json 2> gpurun_out/${R}_bench.err; echo bench rc=$?
-timeout -k 10 500 python bench.py --steps 20 --warmup 5 > gpurun_out/${R}_bench_steps20.json 2> gpurun_out/${R}_bench_steps20.err; echo bench rc=$?
-timeout -k 10 400 python bench.py --mode 1 --steps 30 --no-extras --no-cpu-baseline > gpurun_out/${R}_bench_fast.json 2> /dev/null
-timeout -k 10 400 python bench.py --workload cfg1 --steps 50 --no-extras --no-cpu-baseline > gpurun_out/${R}_bench_cfg1.json 2> /dev/null
-timeout -k 10 400 python bench.py --workload cfg3 --steps 30 --no-extras --no-cpu-baseline > gpurun_out/${R}_bench_cfg3.json 2> /dev/null
-timeout -k 10 600 python bench.py --workload cfg4 --steps 5 --warmup 1 --no-extras --no-cpu-baseline > gpurun_out/${R}_bench_cfg4.json 2> /dev/null
+[ -f $OUT/${R}_pmc.json ] && cp $OUT/${R}_pmc.json profiles/${R}_pmc.json
+timeout -k 10 500 python bench.py --full > $OUT/${R}_bench.json 2> $OUT/${R}_bench.err; echo bench rc=$?
+timeout -k 10 500 python bench.py --full --steps 20 --warmup 5 > $OUT/${R}_bench_steps20.json 2> $OUT/${R}_bench_steps20.err; echo bench rc=$?
+timeout -k 10 400 python bench.py --mode 1 --steps 30 --no-extras --no-cpu-baseline > $OUT/${R}_bench_fast.json 2> /dev/null
+timeout -k 10 400 python bench.py --workload cfg1 --steps 50 --no-extras --no-cpu-baseline > $OUT/${R}_bench_cfg1.json 2> /dev/null
+timeout -k 10 400 python bench.py --workload cfg3 --steps 30 --no-extras --no-cpu-baseline > $OUT/${R}_bench_cfg3.json 2> /dev/null
+timeout -k 10 600 python bench.py --workload cfg4 --steps 5 --warmup 1 --no-extras --no-cpu-baseline > $OUT/${R}_bench_cfg4.json 2> /dev/null
 python - <<'PY'
-import json
+import json, os
 for f in ("r6_bench", "r6_bench_steps20", "r6_bench_fast", "r6_bench_cfg1", "r6_bench_cfg3", "r6_bench_cfg4"):
     try:
-        d = json.loads([l for l in open("gpurun_out/%s.json" % f) if l.startswith("{")][-1])
+        d = json.loads([l for l in open(os.path.join(os.environ["OUT"], "%s.json" % f)) if l.startswith("{")][-1])
     except Exception as e:
         print(f, "no line:", e); continue
     print(f, "%.4g samples/s" % d["value"], "%.3f ms" % d["ms_per_step"], "frac %.4f" % d["roofline"]["frac"], d["roofline"].get("valu", {}).get("frac"))
@@ -46,8 +48,8 @@ for f in ("r6_bench", "r6_bench_steps20", "r6_bench_fast", "r6_bench_cfg1", "r6_
 PY
 ;;
 d)
-timeout -k 10 900 python bench.py --gpus 2 --steps 5 --warmup 1 > gpurun_out/${R}_bench_2ranks_one_gpu.json 2> gpurun_out/${R}_bench_2ranks_one_gpu.err; echo rc=$?
-tail -c 3000 gpurun_out/${R}_bench_2ranks_one_gpu.json
+timeout -k 10 900 python bench.py --full --gpus 2 --steps 5 --warmup 1 > $OUT/${R}_bench_2ranks_one_gpu.json 2> $OUT/${R}_bench_2ranks_one_gpu.err; echo rc=$?
+tail -c 3000 $OUT/${R}_bench_2ranks_one_gpu.json
 ;;
 c)
 timeout -k 10 300 python tools/steady_probe.py > gpurun_out/${R}_steady_probe.txt 2>&1
