@@ -95,6 +95,47 @@ int speechPlayer_batch_setUtterancesShared(speechPlayer_batch_t batch, long long
 int speechPlayer_batch_setRecords(speechPlayer_batch_t batch, long long nShapes, const speechPlayer_frame_t* shapes,
 	long long nLists, const long long* listStart, const speechPlayer_frameRecord_t* records,
 	long long nUtterances, const unsigned int* listOf, const unsigned int* noiseSeed);
+/*
+ * The batch of speechPlayer_batch_setUtterances with the 47-double frames in DEVICE memory (a tensor a model or tensor ops computed):
+ * same lengths, PCM, index marks, speechPlayer_batch_frames readback and plan.  Only the frames' place differs.
+ *   deviceFrames[frameStart[nUtterances]]  device memory of the batch's device (hipMalloc'd, e.g. a torch tensor), 8-byte aligned; the
+ *                              call copies it device to device into the batch's own buffer: once it returns the caller may free or
+ *                              overwrite it.  frameStart, the durations, userIndex, isNull and noiseSeed stay HOST arrays (the host
+ *                              plans with them: 16 bytes per frame against 376).
+ *   readyStream                a hipStream_t on which the frames are being produced: the engine records an event there and its copy
+ *                              waits for it on the device -- the caller's stream is never synchronised from the host.  NULL: the
+ *                              caller guarantees the frames are ready (so frames produced on the NULL stream itself must be handed
+ *                              over with a stream that waits for it: BatchPlayer.setUtterancesTensor does so).
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT, the previous batch left in place: a host pointer (page-locked memory included), memory of
+ * another device, managed memory, a pointer the HIP runtime does not know, one not 8-byte aligned, and frames that run past the end of
+ * their allocation.  The frames are looked at on the device (klatt_frame_facts: 24 bytes per frame come back); for the track planner
+ * one frame per distinct shape is gathered there and downloaded.
+ */
+int speechPlayer_batch_setUtterancesDevice(speechPlayer_batch_t batch, long long nUtterances, const long long* frameStart,
+	const speechPlayer_frame_t* deviceFrames, const unsigned int* minFrameDuration, const unsigned int* fadeDuration,
+	const int* userIndex, const unsigned char* isNull, const unsigned int* noiseSeed, void* readyStream);
+/*
+ * The PCM of chosen utterances into CALLER-OWNED device memory, typed and ordered on the caller's stream.
+ *   utterances[nUtterances]    host array of utterance numbers, any order, repeats allowed; NULL: every utterance in order
+ *                              (nUtterances is then ignored)
+ *   deviceOut                  device memory of the batch's device, aligned to the element size (16-byte alignment takes the vector
+ *                              stores), holding the return value's number of elements
+ *   format                     0 int16; 1 float32 = sample / 32767 (as speechPlayer_batch_readFloat)
+ *   rowStride                  > 0: row i (utterance utterances[i]) starts at element i * rowStride, the elements past the utterance's
+ *                              end are 0 -- a rowStride below the longest chosen utterance is refused; 0: the utterances back to back
+ *                              in the order given
+ *   stream                     a hipStream_t of the batch's device (NULL: the null stream)
+ * Returns the number of elements written (0 writes nothing and needs no buffer), -1 on error.  Ordering by events, no host waits: the
+ * export runs on `stream` after the batch's last synthesis launch (all its streams), and the batch's next launch waits on the device
+ * for the export before it overwrites the pool (a set call leaves the pool alone, unless it must grow it: then it waits for the
+ * exports on the host before it frees the old one).  On return the work is queued, nothing has been synchronised (with more than sixteen
+ * exports of one batch in flight the seventeenth waits for the first).  The batch must have been synthesised since it was set.
+ */
+long long speechPlayer_batch_exportPcm(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
+	void* deviceOut, int format, long long rowStride, void* stream);
+/* The HIP device the batch is bound to (-1: no batch). */
+int speechPlayer_batch_device(speechPlayer_batch_t batch);
+
 /* The frames of utterance u as they are resident in HBM (downloaded; after any of the set calls): what each speechPlayer_queueFrame
  * call of that utterance would have been given.  Returns the utterance's number of frames; fills the arrays (each may be NULL)
  * when it is <= capacity.  fadeDuration comes back as the engine uses it (>= 1: reference src/speechPlayer.cpp:36). */
@@ -103,6 +144,8 @@ long long speechPlayer_batch_frames(speechPlayer_batch_t batch, long long uttera
 
 /* Number of samples utterance u produces: sum over its frames of max(M, F+1)+1. */
 long long speechPlayer_batch_utteranceSamples(speechPlayer_batch_t batch, long long utterance);
+/* The same for every utterance at once: returns the number of utterances, and fills lengths[] when it is <= capacity. */
+long long speechPlayer_batch_lengths(speechPlayer_batch_t batch, long long* lengths, long long capacity);
 long long speechPlayer_batch_totalSamples(speechPlayer_batch_t batch);
 long long speechPlayer_batch_totalFrames(speechPlayer_batch_t batch);
 int speechPlayer_batch_sampleRate(speechPlayer_batch_t batch);

@@ -51,6 +51,7 @@ EXPORTS = [
     "speechPlayer_node_time", "speechPlayer_planTracks", "speechPlayer_planDirect", "speechPlayer_frameFacts", "speechPlayer_planTracksFacts",
     "speechPlayer_batch_setUtterancesShared", "speechPlayer_batch_setRecords", "speechPlayer_batch_frames", "speechPlayer_batch_setIpaVoices",
     "speechPlayer_ipa_records", "speechPlayer_records_view", "speechPlayer_records_free", "speechPlayer_voiceIndex", "speechPlayer_voiceDefine", "speechPlayer_voicePresetCount",
+    "speechPlayer_batch_setUtterancesDevice", "speechPlayer_batch_exportPcm", "speechPlayer_batch_device", "speechPlayer_batch_lengths",
 ]
 
 
@@ -293,6 +294,14 @@ def load():
     L.speechPlayer_planDirect.argtypes = [i64, vp, vp, vp, vp, vp]
     L.speechPlayer_planTracksFacts.restype = i64
     L.speechPlayer_planTracksFacts.argtypes = [i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.speechPlayer_batch_setUtterancesDevice.restype = i32
+    L.speechPlayer_batch_setUtterancesDevice.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.speechPlayer_batch_exportPcm.restype = i64
+    L.speechPlayer_batch_exportPcm.argtypes = [vp, vp, i64, vp, i32, i64, vp]
+    L.speechPlayer_batch_device.restype = i32
+    L.speechPlayer_batch_device.argtypes = [vp]
+    L.speechPlayer_batch_lengths.restype = i64
+    L.speechPlayer_batch_lengths.argtypes = [vp, vp, i64]
     L.speechPlayer_batch_setUtterancesShared.restype = i32
     L.speechPlayer_batch_setUtterancesShared.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp]
     L.speechPlayer_batch_setRecords.restype = i32

@@ -171,6 +171,105 @@ __global__ void __launch_bounds__(256) pcm_digest(const int16_t* __restrict__ pc
     }
 }
 
+// speechPlayer_batch_exportPcm: chosen utterances of the pool into a caller's device buffer, as int16 or as float (/ 32767, the
+// scaling of pcm_to_float), in rows of `rowStride` elements zero-padded past each utterance's end (rowStride > 0) or back to back
+// (rowStride == 0: row r starts at dstStart[r]; chunkRow[c] is the row that holds element c * kExportChunk, so that the bisection for a
+// thread's row runs over the few rows of its chunk -- over all 65 536 rows of configs[2] it was 16 dependent loads per 8 elements, and
+// the kernel ran at a third of its bandwidth).  A thread owns 8 OUTPUT elements, so its store is one aligned 16-byte (int16) or two
+// 16-byte (float) stores whatever the row stride, when the buffer is 16-byte aligned (vecStore).  Inside a row the source is misaligned
+// against the destination by the same even number of bytes for every thread of the row: the two aligned 16-byte loads and the shift
+// of pcm_compact.  8 elements that straddle rows or an utterance's end go element by element.  HBM-bound: 2 B read, 2 or 4 B written.
+struct ExportRow { long long src, len; };      // pool offset (a multiple of kTile) and samples of a row's utterance
+constexpr int kExportChunkLog2 = 15;
+template <bool FLOAT>
+__global__ void __launch_bounds__(256) pcm_export(const int16_t* __restrict__ pool, void* __restrict__ out, const ExportRow* __restrict__ rows,
+                                                  const long long* __restrict__ dstStart, const long long* __restrict__ chunkRow, long long nRows,
+                                                  long long rowStride, long long total, int vecStore)
+{
+    const long long n8 = (total + 7) / 8;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n8; t += stride) {
+        const long long p = t * 8;
+        long long r, c0, width;          // p's row, its column there, the row's width
+        if (rowStride > 0) {
+            r = p / rowStride; c0 = p - r * rowStride; width = rowStride;
+        } else {
+            const long long c = p >> kExportChunkLog2;
+            long long lo = chunkRow[c], hi = chunkRow[c + 1] + 1;      // the last row whose start is <= p
+            while (hi - lo > 1) { const long long mid = (lo + hi) >> 1; if (dstStart[mid] <= p) lo = mid; else hi = mid; }
+            r = lo; c0 = p - dstStart[r]; width = dstStart[r + 1] - dstStart[r];
+        }
+        uint32_t s16[8];
+        const ExportRow row = rows[r];
+        if (p + 8 <= total && c0 + 8 <= width && c0 + 8 <= row.len) {
+            const long long src = row.src + c0;
+            const int k = (int)(src & 7) * 2;
+            const uint4* a = reinterpret_cast<const uint4*>(pool + (src - (src & 7)));
+            const uint4 v0 = a[0];
+            uint32_t x[8] = {v0.x, v0.y, v0.z, v0.w, 0u, 0u, 0u, 0u};
+            if (k) { const uint4 v1 = a[1]; x[4] = v1.x; x[5] = v1.y; x[6] = v1.z; x[7] = v1.w; }
+            const int dw = k >> 2, half = k & 2;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t a0 = 0, a1 = 0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) if (dw == q) { a0 = x[j + q]; a1 = x[j + q + 1 < 8 ? j + q + 1 : 7]; }
+                const uint32_t w = half ? (a0 >> 16) | (a1 << 16) : a0;
+                s16[2 * j] = w & 0xFFFFu; s16[2 * j + 1] = w >> 16;
+            }
+        } else if (p + 8 <= total && c0 + 8 <= width && c0 >= row.len) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) s16[i] = 0u;       // padding
+        } else {
+            // across rows, across an utterance's end, or past the end of the output: element by element
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const long long q = p + i;
+                uint32_t v = 0;
+                if (q < total) {
+                    long long rr, c;
+                    if (rowStride > 0) { rr = q / rowStride; c = q - rr * rowStride; }
+                    else { while (q >= dstStart[r + 1]) ++r; rr = r; c = q - dstStart[r]; }     // (rows of zero samples are stepped over)
+                    const ExportRow e = rows[rr];
+                    if (c < e.len) v = (uint16_t)pool[e.src + c];
+                }
+                s16[i] = v;
+            }
+        }
+        if (FLOAT) {
+            float f[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) f[i] = (float)(int16_t)s16[i] / 32767.0f;
+            float* o = static_cast<float*>(out) + p;
+            if (vecStore && p + 8 <= total) {
+                reinterpret_cast<float4*>(o)[0] = make_float4(f[0], f[1], f[2], f[3]);
+                reinterpret_cast<float4*>(o)[1] = make_float4(f[4], f[5], f[6], f[7]);
+            } else {
+                for (int i = 0; i < 8 && p + i < total; ++i) o[i] = f[i];
+            }
+        } else {
+            int16_t* o = static_cast<int16_t*>(out) + p;
+            if (vecStore && p + 8 <= total) {
+                reinterpret_cast<uint4*>(o)[0] = make_uint4(s16[0] | (s16[1] << 16), s16[2] | (s16[3] << 16), s16[4] | (s16[5] << 16), s16[6] | (s16[7] << 16));
+            } else {
+                for (int i = 0; i < 8 && p + i < total; ++i) o[i] = (int16_t)s16[i];
+            }
+        }
+    }
+}
+
+// Frames given in device memory (speechPlayer_batch_setUtterancesDevice): the rows of the frames that stand for the batch's distinct
+// shapes, gathered for the one download the track planner needs (FrameSource).
+__global__ void __launch_bounds__(256) klatt_gather_frames(const double* __restrict__ frames, const long long* __restrict__ idx, long long nRows, double* __restrict__ out)
+{
+    const long long n = nRows * kNumParams;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
+        const long long r = e / kNumParams;
+        out[e] = frames[idx[r] * kNumParams + (e - r * kNumParams)];
+    }
+}
+
 namespace {
 
 thread_local std::string g_lastError;
@@ -515,7 +614,35 @@ struct Batch {
     hipEvent_t denseReady = nullptr, copyDone = nullptr;
     bool copyPending = false;                  // a speechPlayer_batch_readAllAsync copy is in flight (speechPlayer_batch_readWait)
     bool floatFresh = false;
+    // speechPlayer_batch_setUtterancesDevice: the caller's frames are ready on its stream when inputReady (recorded there) has passed;
+    // the distinct shapes' rows the track planner reads (FrameSource) are gathered into dShapeRows and downloaded
+    hipEvent_t inputReady = nullptr;
+    DeviceBuffer<long long> dShapeIdx;
+    DeviceBuffer<double> dShapeRows;
+    // speechPlayer_batch_exportPcm runs on the CALLER's stream: behind pcmReady (recorded on `stream`, which every launch joins its side
+    // streams into), with its rows staged through one of kExportSlots page-locked / device buffer pairs; a slot is reused once its `done`
+    // (recorded behind its kernel) has passed, and every launch and set call makes `stream` wait for the slots' last exports
+    hipEvent_t pcmReady = nullptr;
+    struct ExportSlot { PinnedBlock host; DeviceBuffer<unsigned char> dev; hipEvent_t done = nullptr; bool used = false; };
+    static constexpr int kExportSlots = 16;
+    ExportSlot exportSlot[kExportSlots];
+    unsigned exportNext = 0;
 };
+
+// The batch's own streams wait (on the device) for the exports that still read its pool.
+int wait_exports(Batch* b)
+{
+    for (auto& s : b->exportSlot)
+        if (s.used) HIP_TRY(hipStreamWaitEvent(b->stream, s.done, 0));
+    return 0;
+}
+// ... and the host, before the pool or a slot is freed.
+int sync_exports(Batch* b)
+{
+    for (auto& s : b->exportSlot)
+        if (s.used) { HIP_TRY(hipEventSynchronize(s.done)); s.used = false; }
+    return 0;
+}
 
 // How many of the quiet, nasal-free utterances (the head of `order`) the lane-pipelined kernel takes.
 // layout 2 forces it; "auto" takes it where it measured faster than the stage-parallel kernel.
@@ -563,12 +690,19 @@ inline unsigned long long hash_shape(const double* v)
 }
 
 // where a frame's parameter values are on the host: in the caller's frames, or -- records -- in the row of the shape table a record names
-// (the planner reads parameters 1..45 only: a record's own pitches are not among them)
+// (the planner reads parameters 1..45 only: a record's own pitches are not among them), or -- frames that stay in device memory
+// (speechPlayer_batch_setUtterancesDevice) -- in the row rowOf[k] of a table that holds ONE frame per distinct (masked) shape hash,
+// downloaded for the planner: equal hashes stand for equal values, as the planner assumes anyway, and klatt_verify_shared checks it
 struct FrameSource {
     const speechPlayer_frame_t* frames;
     const speechPlayer_frameRecord_t* records;
     const speechPlayer_frame_t* shapes;
-    const double* values(long long k) const { return reinterpret_cast<const double*>(records ? shapes + records[k].shape : frames + k); }
+    const uint32_t* rowOf = nullptr;
+    const double* values(long long k) const
+    {
+        if (rowOf) return reinterpret_cast<const double*>(shapes + rowOf[k]);
+        return reinterpret_cast<const double*>(records ? shapes + records[k].shape : frames + k);
+    }
 };
 unsigned long long g_planHashMask[2] = {~0ull, ~0ull};      // speechPlayer_setGlobalOption("plan_hash_bits")
 struct TrackPlan {
@@ -1060,6 +1194,7 @@ int batch_launch(Batch* b)
     KernelArgs a = base_args(b->sampleRate);
     a.frames = b->dFrames.ptr; a.meta = b->dMeta.ptr; a.utt = b->dUtt.ptr;
     a.pcm = b->dPcm.ptr; a.result = b->dResult.ptr; a.state = nullptr; a.control = nullptr;
+    if (wait_exports(b)) return -1;      // (the pool is overwritten: exports queued on other streams read it first)
     b->resultsFresh = false;
     b->floatFresh = false;
     b->launched = true;
@@ -1934,7 +2069,10 @@ speechPlayer_batch_t speechPlayer_batch_create(int sampleRate, int device)
               hipEventCreateWithFlags(&b->forkEvent, hipEventDisableTiming) == hipSuccess &&
               hipStreamCreateWithFlags(&b->copyStream, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreateWithFlags(&b->denseReady, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&b->copyDone, hipEventDisableTiming) == hipSuccess;
+              hipEventCreateWithFlags(&b->copyDone, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&b->inputReady, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&b->pcmReady, hipEventDisableTiming) == hipSuccess;
+    for (auto& s : b->exportSlot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
     { const char* e = getenv("SPEECHPLAYER_TRACKS"); if (e) b->tracks = atoi(e) ? 1 : 0; }
     { const char* e = getenv("SPEECHPLAYER_DIRECT"); if (e) b->direct = std::min(2, std::max(0, atoi(e))); }
     { const char* e = getenv("SPEECHPLAYER_DIRECT_LEAN"); if (e) b->directLean = std::min(1, std::max(-1, atoi(e))); }
@@ -1955,6 +2093,14 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch)
     Batch* b = static_cast<Batch*>(batch);
     if (!b) return;
     (void)hipSetDevice(b->device);
+    (void)sync_exports(b);      // (exports on the callers' streams may still read the pool)
+    for (auto& s : b->exportSlot) {
+        if (s.done) (void)hipEventDestroy(s.done);
+        s.host.release(); s.dev.release();
+    }
+    if (b->inputReady) (void)hipEventDestroy(b->inputReady);
+    if (b->pcmReady) (void)hipEventDestroy(b->pcmReady);
+    b->dShapeIdx.release(); b->dShapeRows.release();
     if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
     for (int i = 0; i < 6; ++i) {
         if (b->side[i]) { (void)hipStreamSynchronize(b->side[i]); (void)hipStreamDestroy(b->side[i]); }
@@ -2014,6 +2160,8 @@ struct SetInput {
     long long nUtt = 0;
     const unsigned int* listOf = nullptr;
     const unsigned int* seeds = nullptr;
+    const double* deviceFrames = nullptr;   // speechPlayer_batch_setUtterancesDevice: the frames in device memory of the batch's device
+    hipStream_t readyStream = nullptr;      // ... ready there once this stream's work queued so far is done (nullptr: ready now)
     bool noTracks = false;       // the second attempt of a batch whose shared shapes failed their verification
 };
 static_assert(sizeof(speechPlayer_frameRecord_t) == sizeof(FrameRecord), "record layout");
@@ -2050,6 +2198,53 @@ int speechPlayer_batch_setUtterances(speechPlayer_batch_t batch, long long nUtte
     return batch_set_guarded("setUtterances", batch, in);
 }
 
+// Is [p, p + bytes) device memory of `device`, inside one allocation, aligned to `align`?  (A kernel never runs on a pointer the
+// runtime does not report as device memory: host memory, page-locked or not, managed memory and unknown pointers are refused.)
+static bool device_range(const void* p, size_t bytes, int device, size_t align, const char* what)
+{
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: %p is not memory the HIP runtime knows (host memory?)", what, p);
+        return false;
+    }
+    if (a.type != hipMemoryTypeDevice) { set_error("%s: %p is not device memory (memory type %d)", what, p, (int)a.type); return false; }
+    if (a.device != device) { set_error("%s: %p is memory of device %d, the batch's is %d", what, p, a.device, device); return false; }
+    if (reinterpret_cast<uintptr_t>(p) % align) { set_error("%s: %p is not %zu-byte aligned", what, p, align); return false; }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: the allocation that holds %p is unknown to the HIP runtime", what, p);
+        return false;
+    }
+    if ((size_t)(static_cast<const char*>(p) - static_cast<const char*>(base)) + bytes > size) {
+        set_error("%s: %zu bytes from %p run past the end of their allocation (%zu bytes from %p)", what, bytes, p, size, base);
+        return false;
+    }
+    return true;
+}
+
+int speechPlayer_batch_setUtterancesDevice(speechPlayer_batch_t batch, long long nUtterances, const long long* frameStart,
+                                           const speechPlayer_frame_t* deviceFrames, const unsigned int* minFrameDuration,
+                                           const unsigned int* fadeDuration, const int* userIndex, const unsigned char* isNull,
+                                           const unsigned int* noiseSeed, void* readyStream)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b || nUtterances < 0 || !frameStart) { set_error("setUtterancesDevice: bad arguments"); return -1; }
+    if (hipSetDevice(b->device) != hipSuccess) { set_error_code(SPEECHPLAYER_ERR_HIP); set_error("setUtterancesDevice: cannot select device %d", b->device); return -1; }
+    const long long nF = frameStart[nUtterances];
+    if (nF < 0 || nF > (1ll << 48)) { set_error("setUtterancesDevice: frameStart[%lld] = %lld", nUtterances, nF); return -1; }
+    if (nF > 0 && !deviceFrames) { set_error("setUtterancesDevice: no frames"); return -1; }
+    if (nF > 0 && !device_range(deviceFrames, (size_t)nF * sizeof(speechPlayer_frame_t), b->device, 8, "setUtterancesDevice")) return -1;
+    SetInput in;
+    in.nLists = nUtterances; in.listStart = frameStart; in.minDur = minFrameDuration; in.fadeDur = fadeDuration;
+    in.userIndex = userIndex; in.isNull = isNull; in.nUtt = nUtterances; in.seeds = noiseSeed;
+    in.deviceFrames = reinterpret_cast<const double*>(deviceFrames); in.readyStream = static_cast<hipStream_t>(readyStream);
+    return batch_set_guarded("setUtterancesDevice", batch, in);
+}
+
 int speechPlayer_batch_setUtterancesShared(speechPlayer_batch_t batch, long long nLists, const long long* listStart,
                                            const speechPlayer_frame_t* frames, const unsigned int* minFrameDuration, const unsigned int* fadeDuration,
                                            const int* userIndex, const unsigned char* isNull, long long nUtterances, const unsigned int* listOf,
@@ -2075,12 +2270,72 @@ int speechPlayer_batch_setRecords(speechPlayer_batch_t batch, long long nShapes,
     return batch_set_guarded("setRecords", batch, in);
 }
 
+// Frames in device memory (speechPlayer_batch_setUtterancesDevice) and the track planner, which reads the values of a frame whose
+// (masked) shape hash it has not seen yet (FrameSource::values): one frame per distinct hash among the frames it may read -- the
+// non-silent frames of the lists that may be tracked --, the first in frame order, stands for all frames of that hash; rowOf[k] names
+// frame k's.  Their rows are gathered on the device (klatt_gather_frames) and downloaded: a few hundred rows for speech, instead of
+// the frames.  Host threads over parts of the lists, each with a map of its own; the maps are merged in frame order.
+static int device_shape_table(Batch* b, long long nL, const long long* listStart, const FrameMeta* meta, const FrameFacts* facts,
+                              const unsigned char* eligible, RawVector<uint32_t>& rowOf, std::vector<long long>& rep, std::vector<double>& rows)
+{
+    struct Key { unsigned long long a, b; bool operator==(const Key& o) const { return a == o.a && b == o.b; } };
+    struct KeyHash { size_t operator()(const Key& k) const { return (size_t)(k.a ^ (k.b * 0x9E3779B97F4A7C15ull)); } };
+    struct Part { std::unordered_map<Key, uint32_t, KeyHash> id; std::vector<long long> first; std::vector<Key> keys; };
+    const long long nF = listStart[nL];
+    rowOf.resize((size_t)nF);
+    const unsigned nT = (unsigned)std::max<long long>(1, std::min<long long>(host_threads(), nF / 65536 + 1));
+    std::vector<long long> cut(nT + 1, nL);
+    cut[0] = 0;
+    for (unsigned t = 1; t < nT; ++t) cut[t] = std::lower_bound(listStart, listStart + nL, nF * (long long)t / nT) - listStart;
+    std::vector<Part> part(nT);
+    auto each_frame = [&](unsigned t, auto fn) {
+        for (long long l = cut[t]; l < cut[t + 1]; ++l)
+            if (eligible[l])
+                for (long long k = listStart[l]; k < listStart[l + 1]; ++k)
+                    if (!(meta[k].flags & FRAME_NULL)) fn(k);
+    };
+    run_parts(nT, [&](unsigned t) {
+        Part& p = part[t];
+        each_frame(t, [&](long long k) {
+            const Key key{facts[k].h0 & g_planHashMask[0], facts[k].h1 & g_planHashMask[1]};
+            auto it = p.id.find(key);
+            if (it == p.id.end()) { it = p.id.emplace(key, (uint32_t)p.first.size()).first; p.first.push_back(k); p.keys.push_back(key); }
+            rowOf[k] = it->second;
+        });
+    });
+    std::unordered_map<Key, uint32_t, KeyHash> global;
+    std::vector<std::vector<uint32_t>> remap(nT);
+    rep.clear();
+    for (unsigned t = 0; t < nT; ++t) {
+        const Part& p = part[t];
+        remap[t].resize(p.first.size());
+        for (size_t i = 0; i < p.first.size(); ++i) {
+            auto it = global.find(p.keys[i]);
+            if (it == global.end()) { it = global.emplace(p.keys[i], (uint32_t)rep.size()).first; rep.push_back(p.first[i]); }
+            remap[t][i] = it->second;
+        }
+    }
+    run_parts(nT, [&](unsigned t) { each_frame(t, [&](long long k) { rowOf[k] = remap[t][rowOf[k]]; }); });
+    const size_t nRows = rep.size();
+    rows.assign(nRows * kNumParams, 0.0);
+    if (nRows == 0) return 0;
+    if (b->dShapeIdx.reserve(nRows) || b->dShapeRows.reserve(nRows * kNumParams)) return -1;
+    HIP_TRY(hipMemcpyAsync(b->dShapeIdx.ptr, rep.data(), nRows * sizeof(long long), hipMemcpyHostToDevice, b->copyStream));
+    const unsigned grid = (unsigned)std::min<long long>(((long long)nRows * kNumParams + 255) / 256, 1 << 16);
+    hipLaunchKernelGGL(klatt_gather_frames, dim3(grid), dim3(256), 0, b->copyStream, b->dFrames.ptr, b->dShapeIdx.ptr, (long long)nRows, b->dShapeRows.ptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rows.data(), b->dShapeRows.ptr, nRows * kNumParams * sizeof(double), hipMemcpyDeviceToHost, b->copyStream));
+    HIP_TRY(hipStreamSynchronize(b->copyStream));
+    return 0;
+}
+
 static int batch_set(Batch* b, const SetInput& in)
 {
     const long long nL = in.nLists, nU = in.nUtt;
     const long long* const listStart = in.listStart;
     const unsigned int* const listOf = in.listOf;
     const bool byRecords = in.records != nullptr;
+    const bool byDevice = in.deviceFrames != nullptr;
     if (!b || nL < 0 || nU < 0 || !listStart) { set_error("set: bad arguments"); return -1; }
     if (nU >= 0xFFFFFFFFll || nL >= 0xFFFFFFFFll) { set_error("set: too many utterances"); return -1; }
     if (!listOf && nU != nL) { set_error("set: %lld utterances for %lld lists and no listOf", nU, nL); return -1; }
@@ -2095,7 +2350,7 @@ static int batch_set(Batch* b, const SetInput& in)
     for (long long l = 0; l < nL; ++l)
         if (listStart[l + 1] < listStart[l]) { set_error("set: frameStart not monotone at %lld", l); return -1; }
     const long long nF = listStart[nL];
-    if (nF > 0 && !byRecords && (!in.frames || !in.minDur || !in.fadeDur)) { set_error("set: bad frame arrays"); return -1; }
+    if (nF > 0 && !byRecords && ((!in.frames && !byDevice) || !in.minDur || !in.fadeDur)) { set_error("set: bad frame arrays"); return -1; }
     if (listOf) {
         std::atomic<long long> bad{-1};
         parallel_ranges(nU, 1 << 16, [&](long long a, long long e) {
@@ -2191,6 +2446,17 @@ static int batch_set(Batch* b, const SetInput& in)
             HIP_TRY(hipGetLastError());
         }
         earlyStarted = true;
+    } else if (byDevice && nF > 0) {
+        // frames in device memory: copied device to device on the copy stream, behind what the caller's stream has queued so far
+        if (in.readyStream) {
+            HIP_TRY(hipEventRecord(b->inputReady, in.readyStream));
+            HIP_TRY(hipStreamWaitEvent(b->copyStream, b->inputReady, 0));
+        }
+        if (b->dFrames.reserve((size_t)nF * kNumParams)) { batch_clear(b); return -1; }
+        batch_clear(b);
+        copyGuard.armed = true;
+        HIP_TRY(hipMemcpyAsync(b->dFrames.ptr, in.deviceFrames, (size_t)nF * kNumParams * sizeof(double), hipMemcpyDeviceToDevice, b->copyStream));
+        earlyStarted = true;
     } else if (nF > 0 && (framesPinned || (size_t)nF * kNumParams * sizeof(double) >= (32u << 20))) {
         if (b->dFrames.reserve((size_t)nF * kNumParams)) { batch_clear(b); return -1; }
         batch_clear(b);
@@ -2216,7 +2482,7 @@ static int batch_set(Batch* b, const SetInput& in)
     // host's threads, while the staging thread copies them.
     const double maxBwDirect = 690.0 * b->sampleRate / M_PI, maxFDirect = 9900.0 * b->sampleRate / (2.0 * M_PI);
     const FrameFacts* facts = nullptr;
-    const bool factsOnDevice = framesPinned && earlyStarted;
+    const bool factsOnDevice = (framesPinned || byDevice) && earlyStarted;
     if (byRecords) {
         std::vector<uint32_t> shapeFl((size_t)in.nShapes);
         for (long long s = 0; s < in.nShapes; ++s) shapeFl[(size_t)s] = shape_flags(reinterpret_cast<const double*>(in.shapes + s), maxFDirect, maxBwDirect);
@@ -2332,9 +2598,31 @@ static int batch_set(Batch* b, const SetInput& in)
             if ((flagsL[l] & UTT_NEEDS_NOISE) && weight[l]) eligible[l] = shapeL[l];
     }
     lap("eligibility");
-    const FrameSource source{in.frames, in.records, in.shapes};
+    FrameSource source{in.frames, in.records, in.shapes};
+    RawVector<uint32_t> rowOf;
+    std::vector<long long> shapeRep;
+    std::vector<double> shapeRows;
+    if (wantTracks && nF > 0 && byDevice) {
+        if (device_shape_table(b, nL, listStart, meta.data(), facts, eligible.data(), rowOf, shapeRep, shapeRows)) return -1;
+        source.shapes = reinterpret_cast<const speechPlayer_frame_t*>(shapeRows.data());
+        source.rowOf = rowOf.data();
+        lap("shape table");
+    }
     if (wantTracks && nF > 0) {
         plan_tracks(nL, listStart, source, facts, meta.data(), eligible.data(), b->trackBudgetMB, plan);
+        if (source.rowOf && !plan.rep.empty()) {
+            // every frame the planner took values for stands for the table's row: each is compared with the row's frame (klatt_verify_shared)
+            parallel_ranges(nL, 4096, [&](long long la, long long le) {
+                for (long long l = la; l < le; ++l) {
+                    if (!eligible[l]) continue;
+                    for (long long k = listStart[l]; k < listStart[l + 1]; ++k) {
+                        if (meta[k].flags & FRAME_NULL) continue;
+                        const long long r = shapeRep[rowOf[k]];
+                        plan.rep[k] = r == k ? 0xFFFFFFFFu : (uint32_t)r;
+                    }
+                }
+            });
+        }
         lap("tracks planned");
         // MODE_FAST, lanes that fade at unrelated times, tracks far beyond the caches (every fading lane streams through a track of its
         // own: the jittered batch's 445 MB): the lean direct stages, whose pole recurrences compute what the tracks would deliver, are
@@ -2553,6 +2841,7 @@ static int batch_set(Batch* b, const SetInput& in)
     unsigned long long mismatchAt = ~0ull;
 
     auto upload = [&]() -> int {
+        if ((size_t)pool > b->dPcm.cap && sync_exports(b)) return -1;      // (a new pool: the old one is freed once no export reads it)
         if (b->dFrames.reserve(std::max<size_t>((size_t)nF * kNumParams, 1)) || b->dMeta.reserve(std::max<size_t>(nF, 1)) ||
             b->dUtt.reserve(std::max<size_t>(nU, 1)) || b->dOrder.reserve(std::max<size_t>(nSlotsAll, 1)) ||
             b->dResult.reserve(std::max<size_t>(nU, 1)) || b->dPcm.reserve(std::max<size_t>(pool, 1)))
@@ -2674,6 +2963,15 @@ long long speechPlayer_batch_utteranceSamples(speechPlayer_batch_t batch, long l
     Batch* b = static_cast<Batch*>(batch);
     if (!b || u < 0 || u >= b->nUtt) return -1;
     return b->lens[u];
+}
+long long speechPlayer_batch_lengths(speechPlayer_batch_t batch, long long* lengths, long long capacity)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("batch_lengths: no batch"); return -1; }
+    if (lengths && b->nUtt <= capacity)
+        for (long long u = 0; u < b->nUtt; ++u) lengths[u] = b->lens[(size_t)u];
+    return b->nUtt;
 }
 long long speechPlayer_batch_totalSamples(speechPlayer_batch_t batch) { return batch ? static_cast<Batch*>(batch)->totalSamples : -1; }
 long long speechPlayer_batch_totalFrames(speechPlayer_batch_t batch) { return batch ? static_cast<Batch*>(batch)->nFramesSpoken : -1; }
@@ -2949,6 +3247,89 @@ long long speechPlayer_batch_deviceOffset(speechPlayer_batch_t batch, long long 
     Batch* b = static_cast<Batch*>(batch);
     if (!b || u < 0 || u > b->nUtt) return -1;
     return b->outStart[u];
+}
+
+int speechPlayer_batch_device(speechPlayer_batch_t batch)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("batch_device: no batch"); return -1; }
+    return b->device;
+}
+
+// The chosen utterances' PCM into the caller's device memory on the caller's stream (pcm_export), ordered by events only: behind the
+// batch's last synthesis launch (pcmReady on `stream`, which every launch joins its side streams into), and ahead of the batch's next
+// launch or set call (wait_exports).  The rows' descriptors are staged through a page-locked slot; nothing waits on the host unless
+// all kExportSlots slots still hold exports in flight.
+long long speechPlayer_batch_exportPcm(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, void* deviceOut,
+                                       int format, long long rowStride, void* stream)
+{
+    begin_call();
+    if (refuse_timing_only("speechPlayer_batch_exportPcm")) return -1;
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("exportPcm: no batch"); return -1; }
+    if (format != 0 && format != 1) { set_error("exportPcm: format %d (0 int16, 1 float32)", format); return -1; }
+    if (rowStride < 0) { set_error("exportPcm: rowStride %lld", rowStride); return -1; }
+    const long long n = utterances ? nUtterances : b->nUtt;
+    if (n < 0) { set_error("exportPcm: %lld utterances", n); return -1; }
+    const bool packed = rowStride == 0;
+    std::vector<ExportRow> rows((size_t)n);
+    std::vector<long long> dst(packed ? (size_t)n + 1 : 0), chunkRow;
+    long long maxLen = 0, total = 0;
+    for (long long i = 0; i < n; ++i) {
+        const long long u = utterances ? utterances[i] : i;
+        if (u < 0 || u >= b->nUtt) { set_error("exportPcm: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, u, b->nUtt); return -1; }
+        rows[(size_t)i] = ExportRow{b->outStart[(size_t)u], (long long)b->lens[(size_t)u]};
+        if (packed) dst[(size_t)i] = total;
+        total += b->lens[(size_t)u];
+        maxLen = std::max<long long>(maxLen, b->lens[(size_t)u]);
+    }
+    if (packed) {
+        dst[(size_t)n] = total;
+        const long long nChunks = (total >> kExportChunkLog2) + 1;
+        chunkRow.resize((size_t)nChunks + 1);
+        long long r = 0;
+        for (long long c = 0; c < nChunks; ++c) {
+            while (r + 1 < n && dst[(size_t)r + 1] <= (c << kExportChunkLog2)) ++r;
+            chunkRow[(size_t)c] = r;
+        }
+        chunkRow[(size_t)nChunks] = std::max<long long>(n - 1, 0);
+    }
+    if (!packed && rowStride < maxLen) { set_error("exportPcm: rowStride %lld is below the longest chosen utterance (%lld samples)", rowStride, maxLen); return -1; }
+    if (!packed && n > (1ll << 50) / rowStride) { set_error("exportPcm: %lld rows of %lld elements", n, rowStride); return -1; }
+    const long long elements = packed ? total : n * rowStride;
+    if (elements == 0) return 0;
+    if (!b->launched) { set_error("exportPcm: the batch has not been synthesised since it was set"); return -1; }
+    const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
+    HIP_TRY(hipSetDevice(b->device));
+    if (!deviceOut) { set_error("exportPcm: no output buffer"); return -1; }
+    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportPcm")) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Batch::ExportSlot& slot = b->exportSlot[b->exportNext++ % Batch::kExportSlots];
+    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
+    const size_t rowBytes = (size_t)n * sizeof(ExportRow), dstBytes = dst.size() * sizeof(long long);
+    const size_t bytes = rowBytes + dstBytes + chunkRow.size() * sizeof(long long);
+    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
+    memcpy(slot.host.ptr, rows.data(), rowBytes);
+    if (packed) {
+        memcpy(static_cast<char*>(slot.host.ptr) + rowBytes, dst.data(), dstBytes);
+        memcpy(static_cast<char*>(slot.host.ptr) + rowBytes + dstBytes, chunkRow.data(), chunkRow.size() * sizeof(long long));
+    }
+    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(b->pcmReady, b->stream));
+    HIP_TRY(hipStreamWaitEvent(st, b->pcmReady, 0));
+    const ExportRow* dRows = reinterpret_cast<const ExportRow*>(slot.dev.ptr);
+    const long long* dDst = packed ? reinterpret_cast<const long long*>(slot.dev.ptr + rowBytes) : nullptr;
+    const long long* dChunk = packed ? reinterpret_cast<const long long*>(slot.dev.ptr + rowBytes + dstBytes) : nullptr;
+    const long long n8 = (elements + 7) / 8;
+    const unsigned grid = (unsigned)std::min<long long>((n8 + 255) / 256, 8ll * b->cus);
+    const int vec = reinterpret_cast<uintptr_t>(deviceOut) % 16 == 0;
+    if (format) hipLaunchKernelGGL(pcm_export<true>, dim3(grid), dim3(256), 0, st, b->dPcm.ptr, deviceOut, dRows, dDst, dChunk, n, rowStride, elements, vec);
+    else hipLaunchKernelGGL(pcm_export<false>, dim3(grid), dim3(256), 0, st, b->dPcm.ptr, deviceOut, dRows, dDst, dChunk, n, rowStride, elements, vec);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(slot.done, st));
+    slot.used = true;
+    return elements;
 }
 
 int speechPlayer_batch_time(speechPlayer_batch_t batch, int launches, float* msPerLaunch)

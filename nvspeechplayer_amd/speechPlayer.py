@@ -240,6 +240,36 @@ def host_array(shape, dtype):
     return np.frombuffer(raw, dtype=dt, count=n).reshape(shape)
 
 
+def _host_array(a, dtype):
+    """A numpy array of `a` (numpy, sequence or torch tensor; a CUDA tensor is copied to the host, which synchronises)."""
+    if hasattr(a, "detach") and hasattr(a, "cpu"):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def check_frames_tensor(frames, frameStart, device):
+    """The argument checks of BatchPlayer.setUtterancesTensor, before any library call: `frames` must be a contiguous torch.float64
+    tensor [F, 47] with F = frameStart[-1], on CUDA device `device`.  Nothing is converted.  Raises TypeError (not a tensor, another
+    dtype, not a CUDA tensor) or ValueError (shape, layout, frameStart, another device).  Returns frameStart as an int64 array."""
+    import torch
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError("frames must be a torch tensor, not %s" % type(frames).__name__)
+    if frames.dtype != torch.float64:
+        raise TypeError("frames must be torch.float64 (the frame's 47 doubles), not %s" % frames.dtype)
+    if frames.dim() != 2 or frames.shape[1] != 47:
+        raise ValueError("frames must have the shape [F, 47], not %s" % list(frames.shape))
+    if not frames.is_contiguous():
+        raise ValueError("frames must be contiguous")
+    fs = _host_array(frameStart, np.int64)
+    if fs.ndim != 1 or len(fs) < 1 or fs[0] != 0 or fs[-1] != frames.shape[0] or (np.diff(fs) < 0).any():
+        raise ValueError("frameStart must run from 0 to F = %d without decreasing" % frames.shape[0])
+    if not frames.is_cuda:
+        raise TypeError("frames must be a CUDA tensor (device memory), not a %s tensor" % frames.device.type)
+    if frames.device.index != device:
+        raise ValueError("frames are on cuda:%d, the batch on cuda:%d" % (frames.device.index, device))
+    return fs
+
+
 class BatchPlayer(object):
     """N independent utterances per launch (include/speechPlayer_batch.h)."""
 
@@ -277,6 +307,92 @@ class BatchPlayer(object):
         p = lambda a: None if a is None else a.ctypes.data
         self._check(self._dll.speechPlayer_batch_setUtterances(self._h, n_utt, p(fs), p(fr), p(m), p(f), p(ix), p(nu), p(sd)))
         self.nUtterances = n_utt
+
+    @property
+    def nUtterances(self):
+        return self._n_utt
+
+    @nUtterances.setter
+    def nUtterances(self, n):      # (every set call assigns it: the lengths cached for pcmTensor belong to the batch before)
+        self._n_utt, self._lens = n, None
+
+    def _lengths(self):
+        """Every utterance's sample count, in one call (speechPlayer_batch_lengths), kept until the next set call."""
+        if self._lens is None:
+            lens = np.zeros(max(self.nUtterances, 1), dtype=np.int64)
+            n = self._check(self._dll.speechPlayer_batch_lengths(self._h, lens.ctypes.data, len(lens)))
+            self._lens = lens[:n]
+        return self._lens
+
+    @property
+    def device(self):
+        """The HIP (= torch CUDA) device index the batch is bound to."""
+        return self._check(self._dll.speechPlayer_batch_device(self._h))
+
+    def setUtterancesTensor(self, frameStart, frames, minSamples, fadeSamples, userIndex=None, isNull=None, noiseSeed=None):
+        """setUtterances with the frames in a torch tensor on the batch's device (speechPlayer_batch_setUtterancesDevice): `frames` a
+        contiguous torch.float64 CUDA tensor [F, 47]; nothing is converted (check_frames_tensor says what is refused).  The engine copies
+        it device to device behind the work queued so far on torch's current stream (the default stream too: the NULL stream, which the C
+        entry reads as "ready now", is waited for by a stream of the player's own) -- no host synchronisation of it -- and the
+        tensor may be freed or overwritten once the call returns.  The other arguments are numpy arrays, sequences or tensors; a CUDA
+        tensor among them is copied to the host, which synchronises."""
+        import torch
+        dev = self.device
+        fs = check_frames_tensor(frames, frameStart, dev)
+        m = _host_array(minSamples, np.uint32)
+        f = _host_array(fadeSamples, np.uint32)
+        n_frames = int(fs[-1])
+        if len(m) != n_frames or len(f) != n_frames:
+            raise ValueError("minSamples and fadeSamples need %d entries" % n_frames)
+        ix = None if userIndex is None else _host_array(userIndex, np.int32)
+        nu = None if isNull is None else _host_array(isNull, np.uint8)
+        sd = None if noiseSeed is None else _host_array(noiseSeed, np.uint32)
+        if (ix is not None and len(ix) != n_frames) or (nu is not None and len(nu) != n_frames) or (sd is not None and len(sd) != len(fs) - 1):
+            raise ValueError("userIndex / isNull need %d entries, noiseSeed %d" % (n_frames, len(fs) - 1))
+        cur = torch.cuda.current_stream(dev)
+        stream = cur.cuda_stream
+        if not stream:
+            # torch's default stream is the NULL stream, which the engine reads as "ready now": a stream of our own that waits for it on
+            # the device carries the order instead
+            if getattr(self, "_ready", None) is None:
+                self._ready = torch.cuda.Stream(dev)
+            self._ready.wait_stream(cur)
+            stream = self._ready.cuda_stream
+        p = lambda a: None if a is None else a.ctypes.data
+        self._check(self._dll.speechPlayer_batch_setUtterancesDevice(self._h, len(fs) - 1, p(fs), frames.data_ptr() if n_frames else None,
+                                                                     p(m), p(f), p(ix), p(nu), p(sd), stream))
+        self.nUtterances = len(fs) - 1
+
+    def pcmTensor(self, utterances=None, dtype=None, padded=True):
+        """The PCM as a torch tensor on the batch's device (speechPlayer_batch_exportPcm), filled on torch's current stream behind the
+        synthesis without a host wait: -> (pcm, lengths).  utterances: indices in any order, repeats allowed (None: all, in order);
+        dtype torch.float32 (default: sample / 32767, as readFloat) or torch.int16.  padded: pcm is [n, longest], zero past each
+        utterance's end, and lengths the n lengths; else pcm is the utterances back to back and lengths the n + 1 offsets (int64 CPU tensors)."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.int16):
+            raise TypeError("pcmTensor: dtype must be torch.float32 or torch.int16, not %s" % dtype)
+        sel = None if utterances is None else _host_array(utterances, np.int64).reshape(-1)
+        n = self.nUtterances if sel is None else len(sel)
+        idx = np.arange(n) if sel is None else sel
+        if n and (idx.min() < 0 or idx.max() >= self.nUtterances):
+            raise ValueError("pcmTensor: utterance numbers must lie in [0, %d)" % self.nUtterances)
+        lens = self._lengths()[idx]
+        dev = self.device
+        if padded:
+            width = int(lens.max()) if n else 0
+            out = torch.empty((n, width), dtype=dtype, device="cuda:%d" % dev)
+            stride = width
+        else:
+            offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+            out = torch.empty(int(offsets[-1]), dtype=dtype, device="cuda:%d" % dev)
+            stride = 0
+        if out.numel():
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            got = self._check(self._dll.speechPlayer_batch_exportPcm(self._h, None if sel is None else sel.ctypes.data, n, out.data_ptr(),
+                                                                     1 if dtype == torch.float32 else 0, stride, stream))
+            assert got == out.numel(), (got, out.numel())
+        return out, torch.from_numpy(lens if padded else offsets)
 
     def setUtterancesShared(self, listStart, frames, minSamples, fadeSamples, listOf, userIndex=None, isNull=None, noiseSeed=None):
         """Frame lists that utterances share (speechPlayer_batch_setUtterancesShared): `listStart`/frames/... describe the lists as
