@@ -24,7 +24,7 @@
 //
 // Arithmetic is IEEE double.  This translation unit is compiled with -ffp-contract=off.
 // MODE_EXACT rounds every multiply and add of the signal path separately, as the reference binary does;
-// MODE_FAST fuses the resonators' multiply-adds.  Both evaluate exp/cos with klatt_math.h (<= 1 ulp).
+// MODE_FAST fuses the resonators' multiply-adds.  Both evaluate exp/cos with klatt_math.h (exp <= 1 ulp, cos <= 1.5 ulp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -385,7 +385,7 @@ __device__ __forceinline__ RadCos coefficient_parts(double f, double bw, double 
     const double ex = negPiOverSr * bw;
     const double th = twoPiOverSr * -f;
     double rad, cs;
-    // exp and cos: the straight-line versions of klatt_math.h (<= 1 ulp, like a libm); arguments outside their
+    // exp and cos: the straight-line versions of klatt_math.h (exp <= 1 ulp, cos <= 1.5 ulp); arguments outside their
     // validated range take the device library.  Same code in both arithmetic modes.
     // Wave-uniform short cut (klatt_math.h): when no active lane's argument needs a range reduction the kernels
     // alone return the same bits as fast_exp / fast_cos.  (Separate decisions for exp and cos, and a third

@@ -2,9 +2,15 @@
 //
 // Reference src/speechWaveGenerator.cpp:116,118 call libm exp and cos once per resonator on
 // every sample of a fade.  These are straight-line fused-multiply-add versions (about 20 and
-// 30 instructions instead of the library's ~70 each), accurate to better than 1 ulp over the
-// argument ranges a frame can produce; tests/test_host_logic.py measures them against libm
-// on the host (this header compiles for both).
+// 30 instructions instead of the library's ~70 each).  Measured against mpmath at 128 bits on
+// the arguments a frame forms at 8 to 48 kHz (tests/test_device_math.py): fast_exp is within
+// 1 ulp for |x| <= 700 (worst seen 0.96); fast_cos and fast_sin are within 1.5 ulp (worst seen
+// 1.37, most often in quadrants -3, -1 and +1) wherever |result| >= 2^-30, and within
+// 1.5 ulp + 2^-90 absolute everywhere for |t| <= 1e4 -- near the zeros the two-part pi/2 of the
+// reduction dominates (<= 4.2e-28 seen: hundreds of ulp relative).  4 to 31 % of the results
+// differ from glibc's in the last bit, depending on the class.  The device returns the host's
+// bits on every argument (the same test, on the GPU); tests/test_host_logic.py checks the
+// header against libm on the host too.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -20,7 +26,7 @@ namespace klatt {
 // the step becomes `v_mov_b64 tmp, C; v_fmac_f64 tmp, p, x` -- the two-address form wants the addend in the destination, and C,
 // kept in a VGPR pair for the whole kernel, must survive: two issue slots per step and two dozen constants' worth of VGPRs in
 // every kernel that evaluates coefficients (klatt_direct.h has the count: 130 of ~230 instructions per sample and stage).  Same
-// operation, same operands: the same bits.
+// operation, same operands: the same bits (tests/test_device_math.py compares them with the host's and the compiler's own FMAs').
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(KLATT_NO_SCALAR_CONSTANTS)
 __device__ __forceinline__ double horner(double p, double x, double c)
 {
@@ -109,8 +115,8 @@ KLATT_HD double cos_kernel(double z)
     return __builtin_fma(z, __builtin_fma(z, c, -0.5), 1.0);
 }
 
-// cos(t), |t| <= 1e4.  t = n pi/2 + r, |r| <= pi/4 (two-part pi/2 with FMA), then the sine or
-// cosine kernel in r by quadrant (truncation < 3e-18).
+// cos(t), |t| <= 1e4 (the bounds in the header above).  t = n pi/2 + r, |r| <= pi/4 (two-part pi/2 with
+// FMA), then the sine or cosine kernel in r by quadrant (truncation < 3e-18).
 KLATT_HD double fast_cos(double t)
 {
     const double n = __builtin_rint(mul_const(t, kTwoOverPi));
@@ -124,7 +130,7 @@ KLATT_HD double fast_cos(double t)
     return (q == 1 || q == 2) ? -v : v;
 }
 
-// sin(t), |t| <= 1e4: the same reduction as fast_cos.  (Used by klatt_seeds.h, once per fade: the start of MODE_FAST's coefficient
+// sin(t), |t| <= 1e4, the same bounds: the same reduction as fast_cos.  (Used by klatt_seeds.h, once per fade: the start of MODE_FAST's coefficient
 // recurrences; nothing on the MODE_EXACT path calls it.)
 KLATT_HD double fast_sin(double t)
 {

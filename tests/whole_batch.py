@@ -3,9 +3,9 @@ packing, the track sharing and the six groups of a real batch unchecked in the o
 
 The engine's PCM stays in HBM: speechPlayer_batch_digest gives 8 bytes per utterance.  The oracle synthesises the same utterances on
 the host's cores, piece by piece (the whole of configs[2] is 3 GB of PCM), tests/native/pcm_digest.c computes the same digest of the
-oracle's PCM, and the two arrays are compared.  MODE_EXACT's exp / cos are within 1 ulp of glibc's, so a sample on a truncation
-boundary may differ by one LSB (tests/test_gpu_parity.py, compare): an utterance whose digests differ is read back and held to that
-bar, and the number of such utterances is bounded.  Test infrastructure: loads the oracle.
+oracle's PCM, and the two arrays are compared.  MODE_EXACT's exp / cos differ from glibc's in the last bit on up to 31 % of their
+arguments (tests/test_device_math.py), so a sample on a truncation boundary may differ by one LSB (tests/test_gpu_parity.py,
+compare): an utterance whose digests differ is read back and held to that bar, and the number of such utterances is bounded.  Test infrastructure: loads the oracle.
 """
 import ctypes
 import os
