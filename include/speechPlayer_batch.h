@@ -287,10 +287,54 @@ int speechPlayer_node_time(speechPlayer_node_t node, int launches, float* msPerL
  * creation saves a sort.
  */
 int speechPlayer_synthesizeMany(speechPlayer_handle_t* handles, int nHandles, unsigned int sampleCount, sample** sampleBufs, int* produced);
-/* The same with the PCM left in HBM: handle i's samples start at *devicePcm + i * *rowStride (device memory, valid until the next
- * live call on that device).  For consumers on the GPU and for measuring the engine without the PCIe copy of the PCM. */
+/* The same with the PCM left in HBM: handle i's samples start at *devicePcm + i * *rowStride.  The pointer is the engine's own pull
+ * buffer: it dies at the next live call on that device (the next pull overwrites it) and at "live_trim" (which frees it).
+ * speechPlayer_synthesizeManyExport below is the caller-owned form.  For measuring the engine without the PCIe copy of the PCM. */
 int speechPlayer_synthesizeManyDevice(speechPlayer_handle_t* handles, int nHandles, unsigned int sampleCount, const sample** devicePcm,
 	long long* rowStride, int* produced);
+/*
+ * speechPlayer_synthesizeMany with handle i's samples written to CALLER-OWNED device memory of the handles' device: row i at element
+ * i * rowStride, format 0 int16 / 1 float32 (= sample / 32767, the bits of speechPlayer_batch_exportPcm), elements produced[i] ..
+ * rowStride-1 zero; rowStride 0 means sampleCount, and a rowStride below sampleCount is refused.  deviceOut is aligned to the element
+ * size (16-byte alignment takes the vector stores).  The pull is unchanged: host-synchronous, produced[] and the index marks are there on
+ * return.  The rows are written on `stream` (a hipStream_t of that device; NULL: the null stream) behind an event recorded after the
+ * pull, with no host wait; the next live call on the device waits for them on the device before it overwrites the pull buffer, and
+ * "live_trim" waits for them before it frees it.  Refused with SPEECHPLAYER_ERR_ARGUMENT before anything is pulled: what
+ * speechPlayer_synthesizeMany refuses, an unknown format, a rowStride below sampleCount, and deviceOut that is not device memory of the
+ * handles' device, not aligned, or too small.  0, or -1.
+ */
+int speechPlayer_synthesizeManyExport(speechPlayer_handle_t* handles, int nHandles, unsigned int sampleCount, void* deviceOut,
+	int format, long long rowStride, void* stream, int* produced);
+/*
+ * Queue frames into many live handles in one call.  Exactly: for every i, for k = frameStart[i] .. frameStart[i+1]-1 in order,
+ *   speechPlayer_queueFrame(handles[i], isNull && isNull[k] ? NULL : &frames[k], minFrameDuration[k], fadeDuration[k],
+ *                           userIndex ? userIndex[k] : -1, purge && purge[i] && k == frameStart[i]).
+ * userIndex, isNull and purge may be NULL (frames too, when every frame is NULL); a row whose isNull is set is never read.  The handles
+ * may live on different devices.  All or nothing: the call checks everything before it queues anything, and refuses an invalid handle,
+ * a handle listed twice, a frameStart that does not run from 0 without decreasing, and a purge[i] set on a handle given no frames --
+ * SPEECHPLAYER_ERR_ARGUMENT, no handle's queue changed.  speechPlayer_queueFrame is this call with one handle and one frame.  0, or -1
+ * (SPEECHPLAYER_ERR_ARGUMENT / _HIP).
+ */
+int speechPlayer_queueFramesMany(const speechPlayer_handle_t* handles, int nHandles, const long long* frameStart,
+	const speechPlayer_frame_t* frames, const unsigned int* minFrameDuration, const unsigned int* fadeDuration,
+	const int* userIndex, const unsigned char* isNull, const unsigned char* purge);
+/*
+ * The same with the 47-double frames in DEVICE memory of the handles' device (a torch tensor); every other array stays on the host.
+ *   deviceFrames[frameStart[nHandles]]  8-byte aligned device memory; read before the call returns: then the caller may free or
+ *                              overwrite it.  A frame that fits in its handle's ring (256 frames) is placed there by a kernel
+ *                              (live_place): 16 bytes of meta, a row number and a target cross the link instead of the 400-byte log entry.
+ *                              Frames beyond a ring wait on the host as in speechPlayer_queueFrame: only their rows are gathered on the
+ *                              device and downloaded.
+ *   readyStream                as in speechPlayer_batch_setUtterancesDevice: a hipStream_t on which the frames are being produced (the
+ *                              engine's stream waits for an event recorded there); NULL: the frames are ready.
+ * Refused besides, with nothing queued: handles on different devices, and frames that are not device memory of the handles' device
+ * (host memory, page-locked or not, included), not 8-byte aligned, or running past the end of their allocation.
+ */
+int speechPlayer_queueFramesManyDevice(const speechPlayer_handle_t* handles, int nHandles, const long long* frameStart,
+	const speechPlayer_frame_t* deviceFrames, const unsigned int* minFrameDuration, const unsigned int* fadeDuration,
+	const int* userIndex, const unsigned char* isNull, const unsigned char* purge, void* readyStream);
+/* The HIP device a live handle's state lives on (-1: not a handle). */
+int speechPlayer_handleDevice(speechPlayer_handle_t handle);
 /* Kernel time in milliseconds of the last live call on HIP device `device` (HIP events on its stream). */
 float speechPlayer_lastLiveKernelMs(int device);
 /* Kernel launches that call took: 1, unless a handle had more frames queued than the 256 its device-side ring holds and the

@@ -52,6 +52,7 @@ EXPORTS = [
     "speechPlayer_batch_setUtterancesShared", "speechPlayer_batch_setRecords", "speechPlayer_batch_frames", "speechPlayer_batch_setIpaVoices",
     "speechPlayer_ipa_records", "speechPlayer_records_view", "speechPlayer_records_free", "speechPlayer_voiceIndex", "speechPlayer_voiceDefine", "speechPlayer_voicePresetCount",
     "speechPlayer_batch_setUtterancesDevice", "speechPlayer_batch_exportPcm", "speechPlayer_batch_device", "speechPlayer_batch_lengths",
+    "speechPlayer_queueFramesMany", "speechPlayer_queueFramesManyDevice", "speechPlayer_synthesizeManyExport", "speechPlayer_handleDevice",
 ]
 
 
@@ -171,6 +172,14 @@ def load():
     L.speechPlayer_synthesizeMany.argtypes = [vp, i32, u32, vp, vp]
     L.speechPlayer_synthesizeManyDevice.restype = i32
     L.speechPlayer_synthesizeManyDevice.argtypes = [vp, i32, u32, vp, vp, vp]
+    L.speechPlayer_synthesizeManyExport.restype = i32
+    L.speechPlayer_synthesizeManyExport.argtypes = [vp, i32, u32, vp, i32, i64, vp, vp]
+    L.speechPlayer_queueFramesMany.restype = i32
+    L.speechPlayer_queueFramesMany.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.speechPlayer_queueFramesManyDevice.restype = i32
+    L.speechPlayer_queueFramesManyDevice.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.speechPlayer_handleDevice.restype = i32
+    L.speechPlayer_handleDevice.argtypes = [vp]
     L.speechPlayer_lastLiveKernelMs.restype = ctypes.c_float
     L.speechPlayer_lastLiveKernelMs.argtypes = [i32]
     L.speechPlayer_lastLiveLaunches.restype = i32

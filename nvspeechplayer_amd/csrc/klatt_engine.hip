@@ -1352,6 +1352,29 @@ __global__ void __launch_bounds__(256) live_scatter(const LogEntry* __restrict__
     else if (j == (uint32_t)kNumParams) ringMeta[at] = log[e].meta;
 }
 
+// speechPlayer_queueFramesManyDevice: a frame in the caller's device memory into the ring position the host assigned it -- the log's
+// entry without its 376 bytes of values, which the kernel reads from the caller's row instead (row -1: a NULL frame, zeros as
+// log_append writes them; such a row is never read).
+struct LivePlace {           // 32 B
+    FrameMeta meta;
+    long long row;           // the frame's row of the caller's array, or -1
+    uint32_t target;         // slot * kRing + ring position
+    uint32_t pad;
+};
+static_assert(sizeof(LivePlace) == 32, "LivePlace layout");
+
+__global__ void __launch_bounds__(256) live_place(const double* __restrict__ frames, const LivePlace* __restrict__ place, long long n,
+                                                  double* __restrict__ ringFrames, FrameMeta* __restrict__ ringMeta)
+{
+    const uint32_t j = threadIdx.x & 63u;
+    const long long step = (long long)gridDim.x * 4;
+    for (long long e = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); e < n; e += step) {     // one wavefront per frame
+        const LivePlace p = place[e];
+        if (j < (uint32_t)kNumParams) ringFrames[(size_t)p.target * kNumParams + j] = p.row < 0 ? 0.0 : frames[p.row * kNumParams + j];
+        else if (j == (uint32_t)kNumParams) ringMeta[p.target] = p.meta;
+    }
+}
+
 inline uint32_t frame_span(const FrameMeta& m)      // samples from this frame's dequeue to the next one's, the closed form of speechPlayer_batch_setUtterances
 {
     const unsigned long long v = std::max<unsigned long long>(m.minSamples, (unsigned long long)m.fadeSamples + 1) + 1;
@@ -1442,6 +1465,24 @@ struct LiveContext {
     hipEvent_t kernelStart = nullptr, kernelStop = nullptr;
     float lastKernelMs = 0.0f;           // the last call's kernel time (speechPlayer_lastLiveKernelMs)
     int lastLaunches = 0;
+    int cus = 256;                       // the device's CUs (pcm_export's grid)
+    // speechPlayer_queueFramesManyDevice: ring frames placed by live_place from the caller's memory, the rows of frames that go to the
+    // host queues gathered (klatt_gather_frames) and downloaded; `stream` first waits for inputReady, recorded on the caller's stream
+    hipEvent_t inputReady = nullptr;
+    PinnedBuffer<LivePlace> hPlace;
+    DeviceBuffer<LivePlace> dPlace;
+    PinnedBuffer<long long> hGatherIdx;
+    DeviceBuffer<long long> dGatherIdx;
+    PinnedBuffer<double> hGatherRows;
+    DeviceBuffer<double> dGatherRows;
+    // speechPlayer_synthesizeManyExport: pcm_export on the caller's stream behind pullDone, its rows staged through one of kExportSlots
+    // page-locked / device buffer pairs; the next pull waits for the exports on the device before it overwrites dPcm / dPcmJoin, the
+    // host waits for them before either is freed (live_wait_exports)
+    hipEvent_t pullDone = nullptr;
+    struct ExportSlot { PinnedBlock host; DeviceBuffer<unsigned char> dev; hipEvent_t done = nullptr; bool used = false, pending = false; };
+    static constexpr int kExportSlots = 16;
+    ExportSlot exportSlot[kExportSlots];
+    unsigned exportNext = 0;
 };
 std::mutex g_liveMutex;
 std::vector<LiveContext*> g_live;   // per device
@@ -1457,12 +1498,27 @@ int g_liveTrim = 0;                 // speechPlayer_setGlobalOption("live_trim")
 
 // c->mu held.  No handle lives on this device: give its arena (state blocks, rings) and the pull buffers back.  The next
 // speechPlayer_initialize starts a new arena of 64 slots.
+// c->mu held.  Exports of earlier pulls (speechPlayer_synthesizeManyExport) may still read dPcm / dPcmJoin on their callers' streams:
+// before the buffers are overwritten `stream` waits for them on the device; before they are freed (freeing) the host waits.
+int live_wait_exports(LiveContext* c, bool freeing)
+{
+    for (auto& e : c->exportSlot) {
+        if (!e.used) continue;
+        if (freeing) { HIP_TRY(hipEventSynchronize(e.done)); e.used = e.pending = false; }
+        else if (e.pending) { HIP_TRY(hipStreamWaitEvent(c->stream, e.done, 0)); e.pending = false; }
+    }
+    return 0;
+}
+
 void arena_trim(LiveContext* c)
 {
     if (c->slots == 0 || c->freeSlots.size() != (size_t)c->nextSlot) return;
     (void)hipStreamSynchronize(c->stream);
+    (void)live_wait_exports(c, true);
     c->dState.release(); c->dRingFrames.release(); c->dRingMeta.release();
     c->dPcm.release(); c->dPcmJoin.release(); c->dCtl.release(); c->dResult.release(); c->dOrder.release();
+    c->dPlace.release(); c->dGatherIdx.release(); c->dGatherRows.release();
+    for (auto& e : c->exportSlot) e.dev.release();
     c->orderFilled = 0;
     c->slots = 0; c->nextSlot = 0;
     c->freeSlots.clear();
@@ -1474,9 +1530,15 @@ LiveContext* live_context(int device)
     if ((int)g_live.size() <= device) g_live.resize(device + 1, nullptr);
     if (!g_live[device]) {
         LiveContext* c = new LiveContext;
-        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreate(&c->kernelStart) != hipSuccess || hipEventCreate(&c->kernelStop) != hipSuccess ||
-            c->hLog.reserve(kLogEntries) || c->dLog.reserve(kLogEntries)) {
+        bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
+                  hipEventCreate(&c->kernelStart) == hipSuccess && hipEventCreate(&c->kernelStop) == hipSuccess &&
+                  hipEventCreateWithFlags(&c->inputReady, hipEventDisableTiming) == hipSuccess &&
+                  hipEventCreateWithFlags(&c->pullDone, hipEventDisableTiming) == hipSuccess &&
+                  !c->hLog.reserve(kLogEntries) && !c->dLog.reserve(kLogEntries);
+        for (auto& e : c->exportSlot) ok = ok && hipEventCreateWithFlags(&e.done, hipEventDisableTiming) == hipSuccess;
+        hipDeviceProp_t prop;
+        if (ok && hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->cus = prop.multiProcessorCount;
+        if (!ok) {
             set_error("cannot create the live-handle context of device %d", device);
             delete c;
             return nullptr;
@@ -1541,6 +1603,15 @@ int log_send(LiveContext* c)
     return 0;
 }
 
+// s->mu held.  The handle's next ring position for a frame (the caller has checked ring_takes): its target in the arena.
+uint32_t ring_claim(Stream* s, const FrameMeta& meta)
+{
+    const uint32_t pos = (s->ringHead + s->ringCount) & (kRing - 1);
+    s->span[pos] = frame_span(meta);
+    s->ringCount++;
+    return s->slot * kRing + pos;
+}
+
 // s->mu held.  One frame into the handle's ring, by way of the log.  The caller has checked ringCount < kRing.
 int log_append(LiveContext* c, Stream* s, const double* p, const FrameMeta& meta, bool holdsContext)
 {
@@ -1555,17 +1626,14 @@ int log_append(LiveContext* c, Stream* s, const double* p, const FrameMeta& meta
             c->logTail = c->logSent = 0;
         }
     }
-    const uint32_t pos = (s->ringHead + s->ringCount) & (kRing - 1);
     LogEntry& e = c->hLog.ptr[c->logTail];
     if (p) memcpy(e.p, p, sizeof e.p); else memset(e.p, 0, sizeof e.p);
     e.meta = meta;
-    e.target = s->slot * kRing + pos;
+    e.target = ring_claim(s, meta);
     e.pad = 0;
     if (s->logEpoch != c->logEpoch) { s->logIdx.clear(); s->logEpoch = c->logEpoch; }
     s->logIdx.push_back((uint32_t)c->logTail);
     c->logTail++;
-    s->span[pos] = frame_span(meta);
-    s->ringCount++;
     return 0;
 }
 
@@ -1580,6 +1648,57 @@ void ring_drop(LiveContext* c, Stream* s)
     s->ringCount = 0;
 }
 
+// s->mu held.  A purge request (reference src/frame.cpp:103-112): what the handle queued is forgotten, in the ring and on the host;
+// the state half of the purge runs in the kernel before the next sample.
+void stream_purge(LiveContext* c, Stream* s)
+{
+    ring_drop(c, s);
+    s->overflow.clear(); s->overHead = 0;
+    s->purgePending = true;
+}
+
+// s->mu held.  A queued frame goes into the handle's ring while the ring has room and nothing waits on the host, else into the
+// handle's host queue, from where the next pulls refill the ring (copied: the caller may reuse its frame, reference src/frame.cpp:97).
+bool ring_takes(const Stream* s) { return s->overHead == s->overflow.size() && s->ringCount < kRing; }
+void overflow_push(Stream* s, const double* p, const FrameMeta& meta)
+{
+    PendingFrame f;
+    memset(&f, 0, sizeof f);
+    f.meta = meta;
+    if (p) memcpy(f.p, p, sizeof f.p);
+    s->overflow.push_back(f);
+}
+
+// speechPlayer_synthesizeManyExport: where a pull's rows go (caller-owned device memory the entry point has checked).
+struct LiveExport { void* out; int format; long long rowStride; hipStream_t stream; };
+
+// c->mu held, the pull just done (it is host-synchronous).  Row i of the pull -- produced[i] samples at pcm + i * padded: the pull
+// buffer, or the joined rows of a pull in pieces -- into the caller's row i on the caller's stream (pcm_export), behind pullDone; the
+// rows' descriptors are staged through one of kExportSlots page-locked / device buffer pairs, as speechPlayer_batch_exportPcm stages them.
+int live_export(LiveContext* c, const int16_t* pcm, size_t padded, const int* produced, int n, const LiveExport& x)
+{
+    LiveContext::ExportSlot& slot = c->exportSlot[c->exportNext++ % LiveContext::kExportSlots];
+    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = slot.pending = false; }
+    const size_t bytes = (size_t)n * sizeof(ExportRow);
+    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
+    ExportRow* rows = static_cast<ExportRow*>(slot.host.ptr);
+    for (int i = 0; i < n; ++i) rows[i] = ExportRow{(long long)i * (long long)padded, (long long)produced[i]};
+    HIP_TRY(hipEventRecord(c->pullDone, c->stream));
+    HIP_TRY(hipStreamWaitEvent(x.stream, c->pullDone, 0));
+    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, x.stream));
+    const long long elements = (long long)n * x.rowStride, n8 = (elements + 7) / 8;
+    const unsigned grid = (unsigned)std::min<long long>((n8 + 255) / 256, 8ll * c->cus);
+    const int vec = reinterpret_cast<uintptr_t>(x.out) % 16 == 0;
+    const ExportRow* dRows = reinterpret_cast<const ExportRow*>(slot.dev.ptr);
+    const long long* none = nullptr;       // (rows of rowStride elements: no packed-row index)
+    if (x.format) hipLaunchKernelGGL(pcm_export<true>, dim3(grid), dim3(256), 0, x.stream, pcm, x.out, dRows, none, none, (long long)n, x.rowStride, elements, vec);
+    else hipLaunchKernelGGL(pcm_export<false>, dim3(grid), dim3(256), 0, x.stream, pcm, x.out, dRows, none, none, (long long)n, x.rowStride, elements, vec);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(slot.done, x.stream));
+    slot.used = slot.pending = true;
+    return 0;
+}
+
 // Advance n live streams by up to `count` samples each (one stream per wavefront lane; one launch, unless some handle has
 // more frames queued than its ring holds AND the ring's frames end before `count` samples: then the call proceeds in pieces,
 // refilling the rings in between -- a pull is the same as several shorter pulls, reference src/speechPlayer.cpp:39-42).
@@ -1589,8 +1708,9 @@ void ring_drop(LiveContext* c, Stream* s)
 unsigned long long g_streamStamps[32];
 extern "C" __attribute__((visibility("default"))) void speechPlayer_debugStreamStamps(unsigned long long* out) { for (int k = 0; k < 32; ++k) { out[k] = g_streamStamps[k]; g_streamStamps[k] = 0; } }
 #endif
+// exportTo: the rows also go into caller-owned device memory (live_export).
 int streams_synthesize(Stream* const* ss, int n, unsigned int count, sample* const* outs, int* produced,
-                       const int16_t** devicePcm = nullptr, long long* deviceStride = nullptr)
+                       const int16_t** devicePcm = nullptr, long long* deviceStride = nullptr, const LiveExport* exportTo = nullptr)
 {
     for (int i = 0; i < n; ++i) produced[i] = 0;
     if (count == 0 || n <= 0) return 0;
@@ -1609,6 +1729,7 @@ int streams_synthesize(Stream* const* ss, int n, unsigned int count, sample* con
     std::lock_guard<std::mutex> g(c->mu);
     HIP_TRY(hipSetDevice(device));
     const size_t padded = ((size_t)count + kTile - 1) / kTile * kTile;
+    if (live_wait_exports(c, padded * n > c->dPcm.cap)) return -1;
     // A LONE handle -- the reference's own use (one stream pulled 8192 samples at a time, nvdaAddon/synthDrivers/nvSpeechPlayer/__init__.py:62-81)
     // -- is advanced in ALL 64 lanes of its wavefront: every lane is given the same control entry (same state block, same ring, same PCM
     // row) and computes the same samples; they store the same values to the same places.  A wavefront with one active lane runs the same
@@ -1737,7 +1858,7 @@ int streams_synthesize(Stream* const* ss, int n, unsigned int count, sample* con
 #endif
         HIP_TRY(hipMemcpyAsync(c->hResult.ptr, c->dResult.ptr, (size_t)(replicate ? nCtl : n) * sizeof(UttResult), hipMemcpyDeviceToHost, c->stream));
         if (piece < count || joined) {       // a call in pieces: this piece's columns into the joined rows
-            if (c->dPcmJoin.reserve(padded * n)) return -1;
+            if ((padded * n > c->dPcmJoin.cap && live_wait_exports(c, true)) || c->dPcmJoin.reserve(padded * n)) return -1;
             HIP_TRY(hipMemcpy2DAsync(c->dPcmJoin.ptr + at, padded * sizeof(int16_t), c->dPcm.ptr, padded * sizeof(int16_t), (size_t)piece * sizeof(int16_t), n,
                                      hipMemcpyDeviceToDevice, c->stream));
             joined = true;
@@ -1773,6 +1894,7 @@ int streams_synthesize(Stream* const* ss, int n, unsigned int count, sample* con
         produced[i] = (int)c->done[i];
         if (c->done[i]) { lastWithData = i; any = true; }
     }
+    if (exportTo && live_export(c, pcm, padded, produced, n, *exportTo)) return -1;
     if (any && outs) {
         if (n == 1) {
             HIP_TRY(hipMemcpy(outs[0], pcm, (size_t)c->done[0] * sizeof(int16_t), hipMemcpyDeviceToHost));
@@ -1823,6 +1945,24 @@ int streams_synthesize(Stream* const* ss, int n, unsigned int count, sample* con
     return 0;
 }
 
+// One bulk queue call (speechPlayer_queueFramesMany, _queueFramesManyDevice; speechPlayer_queueFrame is the host call with one handle
+// and one frame): handle i is given frames frameStart[i] .. frameStart[i+1]-1 in order, the first of them after a purge when purge[i]
+// is set (queue_frames).
+struct QueueCall {
+    const char* what = "";
+    const speechPlayer_handle_t* handles = nullptr;
+    int n = 0;
+    const long long* frameStart = nullptr;
+    const void* frames = nullptr;        // [nFrames][47] doubles in host memory (nullptr: every frame is NULL), or in device memory (onDevice)
+    bool onDevice = false;
+    const unsigned int* minDur = nullptr;
+    const unsigned int* fadeDur = nullptr;
+    const int* userIndex = nullptr;      // nullptr: -1
+    const unsigned char* isNull = nullptr;
+    const unsigned char* purge = nullptr;
+    hipStream_t readyStream = nullptr;   // onDevice: the frames are ready once the work queued there so far has run (nullptr: now)
+};
+
 }  // namespace
 
 // ==========================================================================================
@@ -1858,42 +1998,19 @@ speechPlayer_handle_t speechPlayer_initialize(int sampleRate)
     return reinterpret_cast<speechPlayer_handle_t>(g_streams.size());
 }
 
+static int queue_frames(const QueueCall& q);
+
+// The bulk call with one handle and one frame: one queue path (queue_frames).
 void speechPlayer_queueFrame(speechPlayer_handle_t playerHandle, speechPlayer_frame_t* framePtr, unsigned int minFrameDuration,
                              unsigned int fadeDuration, int userIndex, bool purgeQueue)
 {
     begin_call();
-    Stream* s = lookup(playerHandle);
-    if (!s) { set_error("speechPlayer_queueFrame: invalid handle"); return; }
-    FrameMeta meta;
-    meta.minSamples = minFrameDuration;
-    meta.fadeSamples = std::max(fadeDuration, 1u);       // reference src/speechPlayer.cpp:36
-    meta.userIndex = userIndex;
-    meta.flags = framePtr ? 0u : FRAME_NULL;
-    LiveContext* const c = s->context;
-    std::lock_guard<std::mutex> g(s->mu);
-    if (purgeQueue) {                                    // reference src/frame.cpp:103-112; the state half of
-        ring_drop(c, s);                                 // the purge runs in the kernel before the next sample
-        s->overflow.clear(); s->overHead = 0;
-        s->purgePending = true;
-    }
-    // copied: the caller may reuse its frame (reference src/frame.cpp:97) -- into the pinned log while the handle's ring has
-    // room, else into the handle's host queue, from where the next pulls refill the ring
-    if (s->overHead == s->overflow.size() && s->ringCount < kRing) {
-        if (log_append(c, s, reinterpret_cast<const double*>(framePtr), meta, false)) return;
-        bool eager;
-        { std::lock_guard<std::mutex> lg(c->logMu); eager = c->logTail - c->logSent >= kLogEager; }
-        if (eager && c->mu.try_lock()) {                 // no pull is running: the log need not wait for the next one
-            std::lock_guard<std::mutex> lg(c->logMu);
-            if (hipSetDevice(s->device) == hipSuccess) (void)log_send(c);
-            c->mu.unlock();
-        }
-    } else {
-        PendingFrame f;
-        memset(&f, 0, sizeof f);
-        f.meta = meta;
-        if (framePtr) memcpy(f.p, framePtr, sizeof f.p);
-        s->overflow.push_back(f);
-    }
+    static const long long one[2] = {0, 1};
+    const unsigned char isNull = framePtr ? 0 : 1, purge = purgeQueue ? 1 : 0;
+    QueueCall q;
+    q.what = "speechPlayer_queueFrame"; q.handles = &playerHandle; q.n = 1; q.frameStart = one; q.frames = framePtr;
+    q.minDur = &minFrameDuration; q.fadeDur = &fadeDuration; q.userIndex = &userIndex; q.isNull = &isNull; q.purge = &purge;
+    (void)queue_frames(q);
 }
 
 int speechPlayer_synthesize(speechPlayer_handle_t playerHandle, unsigned int sampleCount, sample* sampleBuf)
@@ -1992,13 +2109,13 @@ int speechPlayer_setGlobalOption(const char* name, int value)
 // Equivalent to calling speechPlayer_synthesize(handles[i], sampleCount, sampleBufs[i]) for every i;
 // produced[i] receives each call's return value.  Handles must be distinct and share a sample rate.
 static int synthesize_many(speechPlayer_handle_t* handles, int nHandles, unsigned int sampleCount, sample** sampleBufs, int* produced,
-                           const int16_t** devicePcm, long long* deviceStride);
+                           const int16_t** devicePcm, long long* deviceStride, const char* what, const LiveExport* exportTo);
 
 int speechPlayer_synthesizeMany(speechPlayer_handle_t* handles, int nHandles, unsigned int sampleCount, sample** sampleBufs, int* produced)
 {
     begin_call();
     if (nHandles > 0 && !sampleBufs) { set_error("speechPlayer_synthesizeMany: bad arguments"); return -1; }
-    return synthesize_many(handles, nHandles, sampleCount, sampleBufs, produced, nullptr, nullptr);
+    return synthesize_many(handles, nHandles, sampleCount, sampleBufs, produced, nullptr, nullptr, "speechPlayer_synthesizeMany", nullptr);
 }
 
 // The same with the PCM left in HBM: handle i's samples start at *devicePcm + i * *rowStride (valid until the next live call
@@ -2009,9 +2126,43 @@ int speechPlayer_synthesizeManyDevice(speechPlayer_handle_t* handles, int nHandl
     begin_call();
     if (!devicePcm || !rowStride) { set_error("speechPlayer_synthesizeManyDevice: bad arguments"); return -1; }
     const int16_t* p = nullptr;
-    const int rc = synthesize_many(handles, nHandles, sampleCount, nullptr, produced, &p, rowStride);
+    const int rc = synthesize_many(handles, nHandles, sampleCount, nullptr, produced, &p, rowStride, "speechPlayer_synthesizeMany", nullptr);
     *devicePcm = reinterpret_cast<const sample*>(p);
     return rc;
+}
+
+static bool device_range(const void* p, size_t bytes, int device, size_t align, const char* what);
+
+// The same with the rows written to caller-owned device memory on the caller's stream (live_export).
+int speechPlayer_synthesizeManyExport(speechPlayer_handle_t* handles, int nHandles, unsigned int sampleCount, void* deviceOut, int format,
+                                      long long rowStride, void* stream, int* produced)
+{
+    begin_call();
+    const char* what = "speechPlayer_synthesizeManyExport";
+    if (refuse_timing_only(what)) return -1;
+    if (format != 0 && format != 1) { set_error("%s: format %d (0 int16, 1 float32)", what, format); return -1; }
+    if (rowStride == 0) rowStride = sampleCount;
+    if (rowStride < (long long)sampleCount) { set_error("%s: rowStride %lld is below sampleCount %u", what, rowStride, sampleCount); return -1; }
+    if (nHandles > 0 && rowStride > (1ll << 50) / nHandles) { set_error("%s: %d rows of %lld elements", what, nHandles, rowStride); return -1; }
+    const LiveExport x{deviceOut, format, rowStride, static_cast<hipStream_t>(stream)};
+    const int rc = synthesize_many(handles, nHandles, sampleCount, nullptr, produced, nullptr, nullptr, what, &x);
+    if (rc == 0 && sampleCount == 0 && nHandles > 0 && rowStride > 0)       // nothing pulled (no pull buffer): the rows are zeros
+        HIP_TRY(hipMemsetAsync(deviceOut, 0, (size_t)nHandles * rowStride * (format ? sizeof(float) : sizeof(int16_t)), x.stream));
+    return rc;
+}
+
+// The export's memory: device memory of the handles' device, aligned to the element, holding their rows.
+static int live_export_check(const std::vector<Stream*>& ss, const LiveExport& x, const char* what)
+{
+    const int device = ss[0]->device;
+    for (size_t i = 1; i < ss.size(); ++i)
+        if (ss[i]->device != device) { set_error("%s: handles on devices %d and %d", what, device, ss[i]->device); return -1; }
+    const long long elements = (long long)ss.size() * x.rowStride;
+    if (elements == 0) return 0;
+    if (!x.out) { set_error("%s: no output buffer", what); return -1; }
+    if (hipSetDevice(device) != hipSuccess) { set_error_code(SPEECHPLAYER_ERR_HIP); set_error("%s: cannot select device %d", what, device); return -1; }
+    const size_t elSize = x.format ? sizeof(float) : sizeof(int16_t);
+    return device_range(x.out, (size_t)elements * elSize, device, elSize, what) ? 0 : -1;
 }
 
 // Duration in milliseconds of the last live-handle launch on `device` (HIP events around the kernel on its stream).
@@ -2028,29 +2179,222 @@ int speechPlayer_lastLiveLaunches(int device)
     return (device >= 0 && device < (int)g_live.size() && g_live[device]) ? g_live[device]->lastLaunches : -1;
 }
 
-static int synthesize_many(speechPlayer_handle_t* handles, int nHandles, unsigned int sampleCount, sample** sampleBufs, int* produced,
-                           const int16_t** devicePcm, long long* deviceStride)
+// Look the handles up (ss, in the call's order) and sort them into the lock order (order: ascending creation; no deadlock between
+// concurrent calls); an invalid handle and a handle listed twice are errors.
+static int lookup_handles(const speechPlayer_handle_t* handles, int n, std::vector<Stream*>& ss, std::vector<Stream*>& order, const char* what)
 {
-    if (nHandles < 0 || (nHandles > 0 && (!handles || !produced))) { set_error("speechPlayer_synthesizeMany: bad arguments"); return -1; }
-    std::vector<Stream*> ss((size_t)nHandles);
+    ss.resize((size_t)n);
     bool ascending = true;
     {
         std::lock_guard<std::mutex> g(g_tableMutex);
-        for (int i = 0; i < nHandles; ++i) {
+        for (int i = 0; i < n; ++i) {
             ss[i] = lookup_locked(handles[i]);
-            if (!ss[i]) { set_error("speechPlayer_synthesizeMany: invalid handle at %d", i); return -1; }
+            if (!ss[i]) { set_error("%s: invalid handle at %d", what, i); return -1; }
             if (i && ss[i]->id <= ss[i - 1]->id) ascending = false;
         }
     }
-    // lock in handle order (no deadlock between concurrent calls); duplicates are an error
-    std::vector<Stream*> order(ss);
+    order = ss;
     if (!ascending) std::sort(order.begin(), order.end(), [](Stream* x, Stream* y) { return x->id < y->id; });
     for (size_t i = 1; i < order.size(); ++i)
-        if (order[i] == order[i - 1]) { set_error("speechPlayer_synthesizeMany: handle listed twice"); return -1; }
+        if (order[i] == order[i - 1]) { set_error("%s: handle listed twice", what); return -1; }
+    return 0;
+}
+
+static int synthesize_many(speechPlayer_handle_t* handles, int nHandles, unsigned int sampleCount, sample** sampleBufs, int* produced,
+                           const int16_t** devicePcm, long long* deviceStride, const char* what, const LiveExport* exportTo)
+{
+    if (nHandles < 0 || (nHandles > 0 && (!handles || !produced))) { set_error("%s: bad arguments", what); return -1; }
+    std::vector<Stream*> ss, order;
+    if (lookup_handles(handles, nHandles, ss, order, what)) return -1;
+    if (exportTo && nHandles > 0 && live_export_check(ss, *exportTo, what)) return -1;
     for (Stream* s : order) s->mu.lock();
-    const int rc = streams_synthesize(ss.data(), nHandles, sampleCount, sampleBufs, produced, devicePcm, deviceStride);
+    const int rc = streams_synthesize(ss.data(), nHandles, sampleCount, sampleBufs, produced, devicePcm, deviceStride, exportTo);
     for (Stream* s : order) s->mu.unlock();
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// Bulk queueing: speechPlayer_queueFramesMany, _queueFramesManyDevice (and speechPlayer_queueFrame, the host call with one frame)
+// ------------------------------------------------------------------------------------------
+// Everything is checked before anything is queued: a refused call changes no handle.
+static int queue_check(const QueueCall& q, std::vector<Stream*>& ss, std::vector<Stream*>& order)
+{
+    if (q.n < 0 || (q.n > 0 && (!q.handles || !q.frameStart))) { set_error("%s: bad arguments", q.what); return -1; }
+    if (q.n == 0) return 0;
+    if (q.frameStart[0] != 0) { set_error("%s: frameStart[0] = %lld (frameStart runs from 0)", q.what, q.frameStart[0]); return -1; }
+    for (int i = 0; i < q.n; ++i) {
+        if (q.frameStart[i + 1] < q.frameStart[i]) {
+            set_error("%s: frameStart decreases at %d (%lld -> %lld)", q.what, i + 1, q.frameStart[i], q.frameStart[i + 1]);
+            return -1;
+        }
+        if (q.purge && q.purge[i] && q.frameStart[i + 1] == q.frameStart[i]) { set_error("%s: purge[%d] is set on a handle given no frames", q.what, i); return -1; }
+    }
+    const long long nF = q.frameStart[q.n];
+    if (nF > (1ll << 48)) { set_error("%s: frameStart[%d] = %lld", q.what, q.n, nF); return -1; }
+    if (nF > 0 && (!q.minDur || !q.fadeDur)) { set_error("%s: no durations", q.what); return -1; }
+    if (nF > 0 && !q.frames) {           // (host frames may be absent when every frame is NULL)
+        long long k = 0;
+        if (!q.onDevice && q.isNull) while (k < nF && q.isNull[k]) ++k;
+        if (k < nF) { set_error("%s: no frames", q.what); return -1; }
+    }
+    if (lookup_handles(q.handles, q.n, ss, order, q.what)) return -1;
+    if (q.onDevice && nF > 0) {
+        const int device = ss[0]->device;
+        for (int i = 1; i < q.n; ++i)
+            if (ss[i]->device != device) { set_error("%s: handles on devices %d and %d", q.what, device, ss[i]->device); return -1; }
+        if (hipSetDevice(device) != hipSuccess) { set_error_code(SPEECHPLAYER_ERR_HIP); set_error("%s: cannot select device %d", q.what, device); return -1; }
+        if (!device_range(q.frames, (size_t)nF * sizeof(speechPlayer_frame_t), device, 8, q.what)) return -1;
+    }
+    return 0;
+}
+
+static FrameMeta queue_meta(const QueueCall& q, long long k)
+{
+    FrameMeta m;
+    m.minSamples = q.minDur[k];
+    m.fadeSamples = std::max(q.fadeDur[k], 1u);          // reference src/speechPlayer.cpp:36
+    m.userIndex = q.userIndex ? q.userIndex[k] : -1;
+    m.flags = (!q.frames || (q.isNull && q.isNull[k])) ? FRAME_NULL : 0u;
+    return m;
+}
+
+// The handles' mutexes held.  Every frame into its ring by way of the pinned log, or into the host queue (ring_takes).
+static int queue_host(const QueueCall& q, Stream* const* ss)
+{
+    const double* frames = static_cast<const double*>(q.frames);
+    for (int i = 0; i < q.n; ++i) {
+        const long long k0 = q.frameStart[i], k1 = q.frameStart[i + 1];
+        if (k0 == k1) continue;
+        Stream* s = ss[i];
+        LiveContext* const c = s->context;
+        if (q.purge && q.purge[i]) stream_purge(c, s);
+        bool logged = false;
+        for (long long k = k0; k < k1; ++k) {
+            const FrameMeta meta = queue_meta(q, k);
+            const double* p = (meta.flags & FRAME_NULL) ? nullptr : frames + k * kNumParams;
+            if (!ring_takes(s)) { overflow_push(s, p, meta); continue; }
+            if (log_append(c, s, p, meta, false)) return -1;
+            logged = true;
+        }
+        if (!logged) continue;
+        bool eager;
+        { std::lock_guard<std::mutex> lg(c->logMu); eager = c->logTail - c->logSent >= kLogEager; }
+        if (eager && c->mu.try_lock()) {                 // no pull is running: the log need not wait for the next one
+            std::lock_guard<std::mutex> lg(c->logMu);
+            if (hipSetDevice(s->device) == hipSuccess) (void)log_send(c);
+            c->mu.unlock();
+        }
+    }
+    return 0;
+}
+
+// The handles' mutexes held; one device.  The same choice per frame as queue_host.  A ring frame is placed by live_place from the
+// caller's memory (the log is sent first: one stream carries every frame in queue order); the rows of host-queue frames are gathered
+// on the device (klatt_gather_frames) and downloaded.  Returns once the caller's memory has been read.
+static int queue_device(const QueueCall& q, Stream* const* ss)
+{
+    const double* frames = static_cast<const double*>(q.frames);
+    const int device = ss[0]->device;
+    LiveContext* const c = ss[0]->context;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(device));
+    const long long nF = q.frameStart[q.n];
+    const size_t placeCap = (size_t)std::min<long long>(nF, (long long)q.n * kRing);      // a call fills a ring at most once
+    if (c->hPlace.reserve(placeCap) || c->dPlace.reserve(c->hPlace.cap) || c->hGatherIdx.reserve((size_t)nF) || c->dGatherIdx.reserve(c->hGatherIdx.cap))
+        return -1;
+    if (q.readyStream) {
+        HIP_TRY(hipEventRecord(c->inputReady, q.readyStream));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->inputReady, 0));
+    }
+    {
+        std::lock_guard<std::mutex> lg(c->logMu);
+        if (log_send(c)) return -1;
+    }
+    struct Fill { Stream* s; size_t at; };               // a host-queue frame whose values the download brings
+    std::vector<Fill> fill;
+    size_t nPlace = 0, nGather = 0;
+    for (int i = 0; i < q.n; ++i) {
+        const long long k0 = q.frameStart[i], k1 = q.frameStart[i + 1];
+        if (k0 == k1) continue;
+        Stream* s = ss[i];
+        if (q.purge && q.purge[i]) stream_purge(c, s);
+        for (long long k = k0; k < k1; ++k) {
+            const FrameMeta meta = queue_meta(q, k);
+            const bool null = (meta.flags & FRAME_NULL) != 0;
+            if (ring_takes(s)) {
+                LivePlace& p = c->hPlace.ptr[nPlace++];
+                p.meta = meta; p.row = null ? -1 : k; p.pad = 0;
+                p.target = ring_claim(s, meta);
+            } else {
+                overflow_push(s, nullptr, meta);
+                if (!null) { c->hGatherIdx.ptr[nGather++] = k; fill.push_back(Fill{s, s->overflow.size() - 1}); }
+            }
+        }
+    }
+    if (nGather && (c->hGatherRows.reserve(nGather * kNumParams) || c->dGatherRows.reserve(c->hGatherRows.cap))) return -1;
+    if (nPlace) {
+        HIP_TRY(hipMemcpyAsync(c->dPlace.ptr, c->hPlace.ptr, nPlace * sizeof(LivePlace), hipMemcpyHostToDevice, c->stream));
+        const unsigned grid = (unsigned)std::min<size_t>((nPlace + 3) / 4, (size_t)1 << 20);
+        hipLaunchKernelGGL(live_place, dim3(grid), dim3(256), 0, c->stream, frames, c->dPlace.ptr, (long long)nPlace, c->dRingFrames.ptr, c->dRingMeta.ptr);
+        HIP_TRY(hipGetLastError());
+    }
+    if (nGather) {
+        HIP_TRY(hipMemcpyAsync(c->dGatherIdx.ptr, c->hGatherIdx.ptr, nGather * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+        const unsigned grid = (unsigned)std::min<size_t>((nGather * kNumParams + 255) / 256, (size_t)1 << 16);
+        hipLaunchKernelGGL(klatt_gather_frames, dim3(grid), dim3(256), 0, c->stream, frames, c->dGatherIdx.ptr, (long long)nGather, c->dGatherRows.ptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->hGatherRows.ptr, c->dGatherRows.ptr, nGather * kNumParams * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));            // the caller's memory has been read
+    {
+        std::lock_guard<std::mutex> lg(c->logMu);        // everything sent has arrived: an empty log starts over
+        if (c->logSent == c->logTail) c->logSent = c->logTail = 0;
+    }
+    for (size_t j = 0; j < nGather; ++j) memcpy(fill[j].s->overflow[fill[j].at].p, c->hGatherRows.ptr + j * kNumParams, kNumParams * sizeof(double));
+    return 0;
+}
+
+static int queue_frames(const QueueCall& q)
+{
+    std::vector<Stream*> ss, order;
+    if (queue_check(q, ss, order)) return -1;
+    if (q.n == 0 || q.frameStart[q.n] == 0) return 0;
+    for (Stream* s : order) s->mu.lock();
+    const int rc = q.onDevice ? queue_device(q, ss.data()) : queue_host(q, ss.data());
+    for (Stream* s : order) s->mu.unlock();
+    return rc;
+}
+
+int speechPlayer_queueFramesMany(const speechPlayer_handle_t* handles, int nHandles, const long long* frameStart, const speechPlayer_frame_t* frames,
+                                 const unsigned int* minFrameDuration, const unsigned int* fadeDuration, const int* userIndex,
+                                 const unsigned char* isNull, const unsigned char* purge)
+{
+    begin_call();
+    QueueCall q;
+    q.what = "speechPlayer_queueFramesMany"; q.handles = handles; q.n = nHandles; q.frameStart = frameStart; q.frames = frames;
+    q.minDur = minFrameDuration; q.fadeDur = fadeDuration; q.userIndex = userIndex; q.isNull = isNull; q.purge = purge;
+    return queue_frames(q);
+}
+
+int speechPlayer_queueFramesManyDevice(const speechPlayer_handle_t* handles, int nHandles, const long long* frameStart,
+                                       const speechPlayer_frame_t* deviceFrames, const unsigned int* minFrameDuration,
+                                       const unsigned int* fadeDuration, const int* userIndex, const unsigned char* isNull,
+                                       const unsigned char* purge, void* readyStream)
+{
+    begin_call();
+    QueueCall q;
+    q.what = "speechPlayer_queueFramesManyDevice"; q.handles = handles; q.n = nHandles; q.frameStart = frameStart; q.frames = deviceFrames;
+    q.onDevice = true; q.minDur = minFrameDuration; q.fadeDur = fadeDuration; q.userIndex = userIndex; q.isNull = isNull; q.purge = purge;
+    q.readyStream = static_cast<hipStream_t>(readyStream);
+    return queue_frames(q);
+}
+
+int speechPlayer_handleDevice(speechPlayer_handle_t handle)
+{
+    begin_call();
+    Stream* s = lookup(handle);
+    if (!s) { set_error("speechPlayer_handleDevice: invalid handle"); return -1; }
+    return s->device;
 }
 
 // ==========================================================================================

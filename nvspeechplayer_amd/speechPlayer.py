@@ -169,8 +169,64 @@ class LiveGroup(object):
         self._out = None
         self._rows = None
 
+    @property
+    def device(self):
+        """The HIP (= torch CUDA) device of the group's handles (speechPlayer_handleDevice)."""
+        d = self._dll.speechPlayer_handleDevice(self._handles[0])
+        if d < 0:
+            raise RuntimeError("speechPlayer_handleDevice failed: %s" % _native.last_error())
+        return d
+
+    def queue(self, frameStart, frames, minSamples, fadeSamples, userIndex=None, isNull=None, purge=None):
+        """Frames into every player in one call (speechPlayer_queueFramesMany): players[i] is given frames frameStart[i] ..
+        frameStart[i+1]-1 in order, as that many queueFrameSamples calls (durations in samples), the first of them with purgeQueue when
+        purge[i] is set; a frame whose isNull is set is never read.  frames [F, 47] and the other arguments are numpy arrays, sequences or
+        CPU tensors (check_live_queue says what is refused)."""
+        fs, m, f, ix, nu, pg, fr = check_live_queue(len(self.players), frameStart, minSamples, fadeSamples, userIndex, isNull, purge, frames=frames)
+        p = lambda a: None if a is None else a.ctypes.data
+        if self._dll.speechPlayer_queueFramesMany(self._handles, len(self.players), p(fs), p(fr), p(m), p(f), p(ix), p(nu), p(pg)) != 0:
+            raise RuntimeError("speechPlayer_queueFramesMany failed: %s" % _native.last_error())
+
+    def queueTensor(self, frameStart, frames, minSamples, fadeSamples, userIndex=None, isNull=None, purge=None):
+        """queue with `frames` a contiguous torch.float64 CUDA tensor [F, 47] on the group's device (speechPlayer_queueFramesManyDevice);
+        nothing is converted (check_frames_tensor, check_live_queue).  Ordered behind the work queued so far on torch's current stream, as
+        BatchPlayer.setUtterancesTensor is: no host synchronisation of that stream.  The frames that fit in the players' rings are placed
+        by a kernel; only the rows of frames beyond come to the host.  The tensor may be freed or overwritten once the call returns."""
+        dev = self.device
+        fs = check_frames_tensor(frames, frameStart, dev)
+        fs, m, f, ix, nu, pg, _ = check_live_queue(len(self.players), fs, minSamples, fadeSamples, userIndex, isNull, purge)
+        p = lambda a: None if a is None else a.ctypes.data
+        rc = self._dll.speechPlayer_queueFramesManyDevice(self._handles, len(self.players), p(fs), frames.data_ptr() if fs[-1] else None,
+                                                          p(m), p(f), p(ix), p(nu), p(pg), _ready_stream(self, dev))
+        if rc != 0:
+            raise RuntimeError("speechPlayer_queueFramesManyDevice failed: %s" % _native.last_error())
+
+    def pullTensor(self, numSamples, dtype=None, out=None):
+        """pull with the samples left on the device, in a tensor the caller owns (speechPlayer_synthesizeManyExport): -> (pcm, produced).
+        pcm [n, numSamples] on the group's device, row i = players[i]'s samples, zero past produced[i]; dtype torch.float32 (default:
+        sample / 32767, as BatchPlayer.pcmTensor) or torch.int16.  The pull itself is pull()'s (host-synchronous); the rows are written on
+        torch's current stream behind it, with no host wait.  out: a contiguous int16 or float32 CUDA tensor [n, >= numSamples] to fill
+        instead (its dtype counts; pcm is then out[:, :numSamples] and the columns beyond are zeros).  produced is a view, overwritten by
+        the next pull."""
+        import torch
+        n = len(self.players)
+        dev = self.device
+        if out is None:
+            dtype = torch.float32 if dtype is None else dtype
+            if dtype not in (torch.float32, torch.int16):
+                raise TypeError("pullTensor: dtype must be torch.float32 or torch.int16, not %s" % dtype)
+            out = torch.empty((n, numSamples), dtype=dtype, device="cuda:%d" % dev)
+        fmt = check_pcm_out(out, n, numSamples, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self._dll.speechPlayer_synthesizeManyExport(self._handles, n, numSamples, out.data_ptr() if out.numel() else None, fmt,
+                                                         out.shape[1], stream, self._produced)
+        if rc != 0:
+            raise RuntimeError("speechPlayer_synthesizeManyExport failed: %s" % _native.last_error())
+        return out[:, :numSamples], self.produced
+
     def pullDevice(self, numSamples):
-        """-> (device pointer, row stride in samples, produced[n]); the PCM stays in HBM (speechPlayer_synthesizeManyDevice)."""
+        """-> (device pointer, row stride in samples, produced[n]); the PCM stays in HBM (speechPlayer_synthesizeManyDevice).  The pointer
+        is the engine's pull buffer, valid until the next live call on the device (pullTensor: memory of the caller's)."""
         rc = self._dll.speechPlayer_synthesizeManyDevice(self._handles, len(self.players), numSamples, byref(self._ptr), byref(self._stride),
                                                          self._produced)
         if rc != 0:
@@ -270,6 +326,72 @@ def check_frames_tensor(frames, frameStart, device):
     return fs
 
 
+def check_live_queue(n, frameStart, minSamples, fadeSamples, userIndex=None, isNull=None, purge=None, frames=None):
+    """The argument checks of LiveGroup.queue / queueTensor that need no GPU, before any library call: frameStart has n + 1 entries and
+    runs from 0 without decreasing (F = frameStart[-1] frames); minSamples and fadeSamples have F entries, userIndex and isNull F (or are
+    None), purge n (or is None) and is set only on rows that have frames; `frames` (host frames; None: not checked here) is [F, 47].
+    Raises ValueError.  Returns the C arrays (frameStart int64, min uint32, fade uint32, userIndex int32, isNull uint8, purge uint8,
+    frames float64 [F, 47]; None for what was None)."""
+    fs = _host_array(frameStart, np.int64).reshape(-1)
+    if len(fs) != n + 1 or fs[0] != 0 or (np.diff(fs) < 0).any():
+        raise ValueError("frameStart must have %d entries and run from 0 without decreasing" % (n + 1))
+    F = int(fs[-1])
+    m = _host_array(minSamples, np.uint32).reshape(-1)
+    f = _host_array(fadeSamples, np.uint32).reshape(-1)
+    if len(m) != F or len(f) != F:
+        raise ValueError("minSamples and fadeSamples need %d entries, not %d and %d" % (F, len(m), len(f)))
+    ix = None if userIndex is None else _host_array(userIndex, np.int32).reshape(-1)
+    nu = None if isNull is None else _host_array(isNull, np.uint8).reshape(-1)
+    if (ix is not None and len(ix) != F) or (nu is not None and len(nu) != F):
+        raise ValueError("userIndex and isNull need %d entries" % F)
+    pg = None if purge is None else _host_array(purge, np.uint8).reshape(-1)
+    if pg is not None:
+        if len(pg) != n:
+            raise ValueError("purge needs %d entries, not %d" % (n, len(pg)))
+        empty = np.flatnonzero((pg != 0) & (fs[1:] == fs[:-1]))
+        if len(empty):
+            raise ValueError("purge is set on row %d, which has no frames" % empty[0])
+    fr = None
+    if frames is not None:
+        fr = _host_array(frames, np.float64)
+        if fr.shape != (F, 47):
+            raise ValueError("frames must have the shape [%d, 47], not %s" % (F, list(fr.shape)))
+    return fs, m, f, ix, nu, pg, fr
+
+
+def check_pcm_out(out, n, numSamples, device):
+    """The argument checks of LiveGroup.pullTensor's `out`, before any library call: a contiguous torch.int16 or torch.float32 tensor
+    [n, >= numSamples] on CUDA device `device`.  Raises TypeError (not a tensor, another dtype, not a CUDA tensor) or ValueError (shape,
+    layout, another device).  Returns the export format (0 int16, 1 float32)."""
+    import torch
+    if not isinstance(out, torch.Tensor):
+        raise TypeError("out must be a torch tensor, not %s" % type(out).__name__)
+    if out.dtype not in (torch.int16, torch.float32):
+        raise TypeError("out must be torch.int16 or torch.float32, not %s" % out.dtype)
+    if out.dim() != 2 or out.shape[0] != n or out.shape[1] < numSamples:
+        raise ValueError("out must have the shape [%d, >= %d], not %s" % (n, numSamples, list(out.shape)))
+    if not out.is_contiguous():
+        raise ValueError("out must be contiguous")
+    if not out.is_cuda:
+        raise TypeError("out must be a CUDA tensor (device memory), not a %s tensor" % out.device.type)
+    if out.device.index != device:
+        raise ValueError("out is on cuda:%d, the players on cuda:%d" % (out.device.index, device))
+    return 1 if out.dtype == torch.float32 else 0
+
+
+def _ready_stream(owner, dev):
+    """The hipStream_t a device-frames call is ordered behind: torch's current stream on `dev`.  torch's default stream is the NULL stream,
+    which the engine reads as "ready now": a stream of `owner`'s own that waits for it on the device carries the order instead."""
+    import torch
+    cur = torch.cuda.current_stream(dev)
+    if cur.cuda_stream:
+        return cur.cuda_stream
+    if getattr(owner, "_ready", None) is None:
+        owner._ready = torch.cuda.Stream(dev)
+    owner._ready.wait_stream(cur)
+    return owner._ready.cuda_stream
+
+
 class BatchPlayer(object):
     """N independent utterances per launch (include/speechPlayer_batch.h)."""
 
@@ -336,7 +458,6 @@ class BatchPlayer(object):
         entry reads as "ready now", is waited for by a stream of the player's own) -- no host synchronisation of it -- and the
         tensor may be freed or overwritten once the call returns.  The other arguments are numpy arrays, sequences or tensors; a CUDA
         tensor among them is copied to the host, which synchronises."""
-        import torch
         dev = self.device
         fs = check_frames_tensor(frames, frameStart, dev)
         m = _host_array(minSamples, np.uint32)
@@ -349,18 +470,9 @@ class BatchPlayer(object):
         sd = None if noiseSeed is None else _host_array(noiseSeed, np.uint32)
         if (ix is not None and len(ix) != n_frames) or (nu is not None and len(nu) != n_frames) or (sd is not None and len(sd) != len(fs) - 1):
             raise ValueError("userIndex / isNull need %d entries, noiseSeed %d" % (n_frames, len(fs) - 1))
-        cur = torch.cuda.current_stream(dev)
-        stream = cur.cuda_stream
-        if not stream:
-            # torch's default stream is the NULL stream, which the engine reads as "ready now": a stream of our own that waits for it on
-            # the device carries the order instead
-            if getattr(self, "_ready", None) is None:
-                self._ready = torch.cuda.Stream(dev)
-            self._ready.wait_stream(cur)
-            stream = self._ready.cuda_stream
         p = lambda a: None if a is None else a.ctypes.data
         self._check(self._dll.speechPlayer_batch_setUtterancesDevice(self._h, len(fs) - 1, p(fs), frames.data_ptr() if n_frames else None,
-                                                                     p(m), p(f), p(ix), p(nu), p(sd), stream))
+                                                                     p(m), p(f), p(ix), p(nu), p(sd), _ready_stream(self, dev)))
         self.nUtterances = len(fs) - 1
 
     def pcmTensor(self, utterances=None, dtype=None, padded=True):
