@@ -31,7 +31,7 @@ struct FrameFacts {          // 24 B per frame
 constexpr uint32_t FACT_NOISE = 1u;        // a noise gain is non-zero, or the parallel bank's coefficients may not be finite
 constexpr uint32_t FACT_NONFINITE = 2u;    // some parameter is NaN or infinite
 constexpr uint32_t FACT_NASAL = 4u;        // the nasal pair is coupled in, or could not be skipped safely
-constexpr uint32_t FACT_UNBOUNDED = 8u;    // a frequency or bandwidth outside the range of klatt_math.h (the direct stages)
+constexpr uint32_t FACT_UNBOUNDED = 8u;    // a frequency or bandwidth outside the range of klatt_math.h, or a negative bandwidth (the direct stages)
 
 __host__ __device__ inline bool fact_finite(double v)
 {
@@ -89,9 +89,14 @@ __host__ __device__ inline uint32_t shape_flags(const double* p, double maxF, do
         fl |= 4u;
     // the direct stages evaluate exp / cos with klatt_math.h alone, whose range is |arg| <= 700 / 1e4: frequencies (parameters 7..14,
     // 25..30) and bandwidths (15..22, 31..36) bounded accordingly
+    // -- and no bandwidth negative.  In MODE_FAST the direct stages advance a fading gain by constant increments (klatt_direct.h), so a
+    // gain that a fade takes to 0 -- the preFormantGain of a silence -- ends a few 1e-17 beside it, where the reference lands on 0
+    // exactly.  Behind stable filters that is nothing; a pole pair that GROWS (bandwidth < 0: r > 1) amplifies it without bound (found
+    // by tests/test_gpu_reference.py: parallel bandwidth -3.2e5 after a silence, one sample of +32000 for -32000).  Such a list keeps
+    // the stages with the frame state machine, which interpolate as the reference does.
     bool inRange = true;
-    for (int i = 7; i <= 14; ++i) inRange = inRange && (fact_abs(p[i]) <= maxF) && (fact_abs(p[i + 8]) <= maxBw);
-    for (int i = 25; i <= 30; ++i) inRange = inRange && (fact_abs(p[i]) <= maxF) && (fact_abs(p[i + 6]) <= maxBw);
+    for (int i = 7; i <= 14; ++i) inRange = inRange && (fact_abs(p[i]) <= maxF) && (p[i + 8] >= 0.0) && (p[i + 8] <= maxBw);
+    for (int i = 25; i <= 30; ++i) inRange = inRange && (fact_abs(p[i]) <= maxF) && (p[i + 6] >= 0.0) && (p[i + 6] <= maxBw);
     if (!inRange) fl |= 8u;                                                      // FACT_UNBOUNDED
     return fl;
 }

@@ -19,14 +19,14 @@
  *   src/speechWaveGenerator.cpp:197-214 (mix, gain, clip, int16 store)
  *   src/speechPlayer.cpp:25-53          (C-ABI shim, fade clamp >= 1)
  *
- * PARITY UNPINNED in the sense of this build's rules: the reference holds no tests, golden vectors or fixtures
- * for this path, and the reference cannot be compiled here without a stand-in <windows.h>
- * (not allowed), so neither of the accepted pins exists.  What there is:
  * Pinning: tests/test_oracle_pin.py checks this file against the known-answer
  * values SURVEY.md section 8(c) recorded from the compiled reference (cfg0 SHA-1,
  * first samples, min/max; the eight sampleIpa.txt lines' lengths and SHA-1
- * prefixes under glibc rand() after srand(1)).  The reference itself needs
- * <windows.h> and MSVC extensions, so it is not built here.
+ * prefixes under glibc rand() after srand(1)).  tests/test_reference_pin.py
+ * compares it call by call with the reference itself, compiled in place by this
+ * directory's Makefile (target `ref`: a stand-in <windows.h>, clang++ for the MSVC
+ * extensions), on every scenario, the random batches and 800 fuzzed call
+ * sequences; tests/golden/reference.json records what that library answered.
  *
  * Noise: the reference draws from libc rand().  ORACLE_NOISE_LIBC reproduces that
  * (used only for the pin above).  ORACLE_NOISE_COUNTER is the engine's defined

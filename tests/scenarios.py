@@ -202,13 +202,20 @@ def build_scenarios(ref):
         ops = [q(fv, ms(180, sr), ms(40, sr)), q(vowel_frame(ref, "s", 120.0), ms(90, sr), ms(30, sr)),
                q(vowel_frame(ref, "m", 100.0, 90.0), ms(120, sr), ms(50, sr)), q(None, ms(40, sr), ms(40, sr)), ("drain",)]
         sc.append(Scenario("vowel_fric_nasal_%dk" % (sr // 1000), ops, sr=sr, seed=seed + 1, batchable=True))
+
+    # a pole pair that GROWS right after a silence (found by tests/test_gpu_reference.py; queue calls 1 .. 4 of fuzz_sequence(36, extreme)
+    # at 8 kHz): a frame, a silence of 1842 samples, a 2-sample frame with a parallel bandwidth of -3.2e5 Hz (r = e^127 per sample),
+    # a frame that fades back.  The silence's fade takes preFormantGain to exactly 0 (frame.cpp:61, utils.h:22), so what the growing
+    # pair amplifies to full scale is the filters' own ring-down; a gain that ends 1e-17 beside 0 shows as samples of the other sign
+    fz36 = fuzz_sequence(36, True)
+    ops = [op[:5] + (False,) for op in fz36.ops if op[0] == "q"][1:5] + [("drain",)]
+    sc.append(Scenario("growing_pole_after_silence", ops, sr=fz36.sr, seed=fz36.seed, batchable=True))
     return sc
 
 
-def play_oracle(scn):
-    """-> (list of int16 arrays, one per synth/drain op; list of lastIndex after each such op)"""
-    from tests import oracle
-    p = oracle.OraclePlayer(scn.sr, noise=oracle.NOISE_COUNTER, seed=scn.seed)
+def play(scn, p):
+    """Play a scenario on a player with the oracle's call surface (tests/oracle.py, tests/reference.py) and close it.
+    -> (list of int16 arrays, one per synth/drain op; list of lastIndex after each such op)"""
     pcm, marks = [], []
     for op in scn.ops:
         if op[0] == "q":
@@ -221,8 +228,53 @@ def play_oracle(scn):
     return pcm, marks
 
 
+def play_oracle(scn):
+    from tests import oracle
+    return play(scn, oracle.OraclePlayer(scn.sr, noise=oracle.NOISE_COUNTER, seed=scn.seed))
+
+
+def random_batch(rng, n_utt, quiet_fraction=0.3, wild=False, nasal_fraction=0.4):
+    """Ragged random utterances: random formants / bandwidths / gains / pitches, random durations
+    (including fade > frame, fade 0, 1-sample frames), NULL frames anywhere, optional NaN holds."""
+    frames, mins, fades, nul, start, seeds = [], [], [], [], [0], []
+    for u in range(n_utt):
+        n = int(rng.integers(1, 9))
+        quiet = rng.random() < quiet_fraction
+        prev_real = False
+        for k in range(n):
+            f = np.zeros(47)
+            f[0] = rng.uniform(40, 400); f[46] = f[0] * rng.uniform(0.6, 1.6)
+            if rng.random() < 0.3:
+                f[1] = rng.uniform(0, 0.2); f[2] = rng.uniform(0, 8)
+            f[5] = rng.uniform(0, 1)
+            if not quiet:
+                f[3] = rng.uniform(0, 0.5) * (rng.random() < 0.5); f[4] = rng.uniform(0, 1)
+                f[6] = rng.uniform(0, 1) * (rng.random() < 0.5); f[24] = rng.uniform(0, 1) * (rng.random() < 0.6)
+            f[7:13] = np.sort(rng.uniform(150, 5500, 6)); f[13] = rng.uniform(0, 600) * (rng.random() < 0.5); f[14] = rng.uniform(200, 500)
+            f[15:23] = rng.uniform(30, 1000, 8); f[23] = rng.uniform(0, 1) * (rng.random() < nasal_fraction)
+            f[25:31] = np.sort(rng.uniform(150, 5500, 6)); f[31:37] = rng.uniform(30, 1000, 6); f[37:43] = rng.uniform(0, 1, 6)
+            f[43] = rng.uniform(0, 1); f[44] = rng.uniform(0, 1.5); f[45] = rng.uniform(0.2, 2.5)
+            is_null = rng.random() < 0.2
+            if wild and prev_real and not is_null and rng.random() < 0.3:
+                f[rng.integers(1, 46, size=3)] = np.nan          # "hold" semantics (utils.h:21); only where a value exists to hold
+            prev_real = not is_null
+            frames.append(f); nul.append(is_null)
+            mode = rng.integers(0, 5)
+            if mode == 0: m, fd = int(rng.integers(0, 4)), int(rng.integers(0, 4))
+            elif mode == 1: m, fd = int(rng.integers(1, 300)), int(rng.integers(300, 900))       # fade longer than the frame
+            else: m, fd = int(rng.integers(50, 2500)), int(rng.integers(0, 700))
+            if not is_null and m == 0 and not (wild and rng.random() < 0.25):
+                m = 1                                           # M = 0 on a real frame divides by zero (frame.cpp:98: an infinite or NaN pitch,
+                                                                # samples of 32000): in the wild batches only, and there on one such frame in four
+            mins.append(m); fades.append(fd)
+        start.append(start[-1] + n); seeds.append(int(rng.integers(0, 2 ** 32)))
+    return dict(frames=np.array(frames), min=np.array(mins, np.uint32), fade=np.array(fades, np.uint32),
+                index=np.full(len(mins), -1, np.int32), isnull=np.array(nul, np.uint8), frame_start=np.array(start, np.int64),
+                seeds=np.array(seeds, np.uint32))
+
+
 STORED_PCM = ("cfg0_a_1s", "stream_chunks", "purge_resume", "vowelchart_pairs", "hannah_vibrato", "nan_hold",
-              "duration_edges", "ipa_l0_16k", "ipa_l1_44k", "ipa_l3_8k", "vowel_fric_nasal_44k", "vowel_fric_nasal_8k")
+              "duration_edges", "ipa_l0_16k", "ipa_l1_44k", "ipa_l3_8k", "vowel_fric_nasal_44k", "vowel_fric_nasal_8k", "growing_pole_after_silence")
 
 
 def write_expected_pcm(ref_path, outdir):
@@ -241,3 +293,230 @@ def write_expected_pcm(ref_path, outdir):
         json.dump(table, f, indent=1, sort_keys=True)
     np.savez_compressed(os.path.join(outdir, "expected_pcm.npz"), **store)
     print("expected.json: %d scenarios; expected_pcm.npz: %d stored" % (len(table), len(store)))
+
+
+# ---- fuzzed call sequences (tests/test_reference_pin.py, tests/test_gpu_reference.py) --------------------------------------------
+# either side of every hand-over size the kernels use
+FUZZ_PULLS = (1, 2, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 100, 500, 1000, 4096, 8192)
+FUZZ_RATES = (8000, 11025, 16000, 22050, 44100, 48000)
+N0_EDGE = (0.0, -0.0, 5e-324, -5e-324, 1e-310, 2.2250738585072014e-308)     # the anti-resonator's `f != 0` (speechWaveGenerator.cpp:120)
+EXTREME_KINDS = ("neg_cascade_bw", "neg_parallel_bw", "inf", "n0_zero", "gain", "beyond_nyquist", "n0_edge")
+PURGE_KINDS = ("fade_first", "fade_last", "frame_end", "drained", "boundary_in_fade")
+N_FUZZ = 400        # sequences of each variant the CPU pin plays (seeds 0 .. N_FUZZ-1)
+
+
+def fuzz_sequence(seed, extreme=False, n_utt=40):
+    """One seeded call sequence against the five entry points, as a Scenario (its .kinds: the extreme kinds it holds).
+    Frames as random_batch(wild=True) draws them, each queued with a random user index and, one time in five, with purge; after it,
+    one time in two, ONE synthesize(n) with n from FUZZ_PULLS, and one time in ten a drain -- so frames pile up in the queue, are
+    purged out of it, and are queued onto drained handles.  One sample rate per sequence.  extreme: a real frame additionally gets,
+    one time in ten each, a negative cascade bandwidth, a negative parallel bandwidth down to -3e6 (exp overflows: infinite
+    coefficients), +-inf in any parameter, N0 frequency 0 with caNP 1, an output gain up to 1e6 (clipping), a formant beyond the
+    Nyquist frequency up to 1e5 Hz, an N0 frequency from N0_EDGE with caNP > 0."""
+    rng = np.random.default_rng([int(bool(extreme)), int(seed)])
+    sr = int(rng.choice(FUZZ_RATES))
+    # (one sequence in four has no noise source at all and every second of those no nasal branch either: what the batch planner
+    # calls quiet and nasal-free, each with kernels of its own)
+    b = random_batch(rng, n_utt, wild=True, quiet_fraction=1.0 if seed % 4 == 3 else 0.3, nasal_fraction=0.0 if seed % 8 == 7 else 0.4)
+    ops, kinds = [], set()
+    for k in range(len(b["min"])):
+        fr = None if b["isnull"][k] else b["frames"][k].copy()
+        if extreme and fr is not None:
+            hit = rng.random(len(EXTREME_KINDS)) < 0.1
+            u = rng.random(len(EXTREME_KINDS))
+            j = rng.integers(0, 1 << 30, len(EXTREME_KINDS))
+            if hit[0]: fr[15 + j[0] % 8] = -300.0 * u[0]
+            if hit[1]: fr[31 + j[1] % 6] = -(10.0 ** (2.0 + u[1] * (np.log10(3e6) - 2.0)))
+            if hit[2]: fr[j[2] % 47] = np.inf if u[2] < 0.5 else -np.inf
+            if hit[3]: fr[13] = 0.0; fr[CANP] = 1.0
+            if hit[4]: fr[OUTGAIN] = 10.0 ** (1.0 + 5.0 * u[4])
+            if hit[5]: fr[(7, 25)[j[5] % 2] + (j[5] >> 1) % 6] = sr / 2.0 + u[5] * (1e5 - sr / 2.0)
+            if hit[6]: fr[13] = N0_EDGE[j[6] % len(N0_EDGE)]; fr[CANP] = 0.1 + 0.9 * u[6]
+            kinds.update(name for name, h in zip(EXTREME_KINDS, hit) if h)
+        ops.append(q(fr, b["min"][k], b["fade"][k], index=int(rng.integers(-1, 1000)), purge=rng.random() < 0.2))
+        if rng.random() < 0.5:
+            ops.append(("s", int(rng.choice(FUZZ_PULLS))))
+        if rng.random() < 0.1:
+            ops.append(("drain",))
+    ops.append(("drain",))
+    scn = Scenario("fuzz_%s_%04d" % ("extreme" if extreme else "plain", seed), ops, sr=sr, seed=int(rng.integers(0, 2 ** 32)))
+    scn.kinds = kinds
+    return scn
+
+
+def without_purges(scn):
+    """(frames, min, fade, index, isnull) of a sequence's queue calls, the purges dropped: one utterance of a batch."""
+    return Scenario(scn.name, [op[:5] + (False,) for op in scn.ops if op[0] == "q"], sr=scn.sr, seed=scn.seed, batchable=True).frames()
+
+
+def trace_sequence(scn):
+    """The frame state machine of frame.cpp:41-115 alone -- its sample counter, no parameters -- over a sequence's calls.
+    -> (calls, kinds): the length of every synthesize / drain op, and how many purges arrived
+      fade_first        right after the sample that took a request out of the queue, before the first interpolated sample of its fade
+      fade_last         right after the last interpolated sample of a fade (counter == fade): the next sample would have ended it
+      frame_end         in steady state on an event sample: right after the sample that ended a fade, or with the frame's time just
+                        up (counter == min: the next sample takes a request), samples having been pulled since the last purge
+      drained           on a handle whose last pull came back short and that has nothing queued
+      boundary_in_fade  (counted per pull, not per purge) a pull that ends inside the fade of a frame that was queued with purge
+    The calls are checked against the oracle's and the reference's (tests/test_reference_pin.py), so the counts stand on the same
+    arithmetic as the PCM."""
+    has_new = False; counter = 0; old_min = 0; new_min = new_fade = 0
+    queue = []; drained = True; produced = 0; just_ended = False
+    new_is_purge = False; pulled = False
+    kinds = dict.fromkeys(PURGE_KINDS, 0)
+    calls = []
+
+    def advance(n):
+        nonlocal pulled, has_new, counter, old_min, new_min, new_fade, drained, produced, just_ended, new_is_purge
+        done = 0
+        while done < n:
+            if has_new:
+                k = min(n - done, new_fade + 1 - counter)          # the sample with counter == fade + 1 ends the fade
+                counter += k; done += k
+                just_ended = False
+                if counter > new_fade:
+                    has_new = False; old_min = new_min; just_ended = True
+            elif counter < old_min:
+                k = min(n - done, old_min - counter)
+                counter += k; done += k; just_ended = False
+            else:
+                counter += 1
+                just_ended = False
+                if not queue:
+                    drained = True
+                    break
+                new_min, new_fade, new_is_purge = queue.pop(0)
+                has_new = True; drained = False; counter = 0; done += 1
+        produced += done
+        pulled = pulled or done > 0
+        return done
+
+    for op in scn.ops:
+        if op[0] == "q":
+            m, f, purge = op[2], max(op[3], 1), op[5]
+            if purge:
+                if has_new and counter == 0:
+                    kinds["fade_first"] += 1
+                elif has_new and counter == new_fade:
+                    kinds["fade_last"] += 1
+                elif not has_new and not drained and pulled and (counter == old_min or just_ended):
+                    kinds["frame_end"] += 1
+                elif drained and not queue and produced:
+                    kinds["drained"] += 1
+                del queue[:]
+                counter = old_min
+                has_new = False; just_ended = False; pulled = False
+            queue.append((m, f, purge))
+        elif op[0] == "s":
+            got = advance(op[1])
+            calls.append(got)
+            if got == op[1] and has_new and new_is_purge and 1 <= counter < new_fade:
+                kinds["boundary_in_fade"] += 1
+        else:
+            total = 0
+            while True:
+                got = advance(8192)
+                total += got
+                if got < 8192:
+                    break
+                if has_new and new_is_purge and 1 <= counter < new_fade:
+                    kinds["boundary_in_fade"] += 1
+            calls.append(total)
+    return calls, kinds
+
+
+FREQ_BW = tuple(range(7, 23)) + tuple(range(25, 37))
+
+
+def nudged(scn):
+    """The sequence with every non-zero frequency and bandwidth one place up (zeros stay: `f != 0` is a branch)."""
+    ops = []
+    for op in scn.ops:
+        if op[0] == "q" and op[1] is not None:
+            fr = op[1].copy()
+            v = fr[list(FREQ_BW)]
+            fr[list(FREQ_BW)] = np.where(v != 0, np.nextafter(v, np.inf), v)
+            op = op[:1] + (fr,) + op[2:]
+        ops.append(op)
+    return Scenario(scn.name, ops, sr=scn.sr, seed=scn.seed)
+
+
+def admitted(scn, player):
+    """Whether the device's last-place differences in exp / cos can be held to the parity bar on this sequence: decided on the CPU
+    alone.  The sequence is played twice on `player` (oracle.OraclePlayer or reference.RefPlayer), the second time nudged();
+    a filter that is unstable or cancels nearly completely amplifies that last place into the PCM, a sound one does not.
+    -> (admitted, pcm per call, marks) of the sequence as it stands."""
+    pcm, marks = play(scn, player(scn.sr, seed=scn.seed))
+    pcm2, _ = play(nudged(scn), player(scn.sr, seed=scn.seed))
+    return all(np.array_equal(a, b) for a, b in zip(pcm, pcm2)), pcm, marks
+
+
+def sequence_digest(pcm, marks):
+    """ONE SHA-1 over PCM bytes, call lengths and marks in order."""
+    h = hashlib.sha1()
+    for x, m in zip(pcm, marks):
+        h.update(np.ascontiguousarray(x, dtype="<i2").tobytes())
+        h.update(np.array([len(x), m], dtype="<i8").tobytes())
+    return h.hexdigest()
+
+
+def input_digest(scns):
+    """SHA-1 of the generated frames and calls of a list of sequences: what the recorded outputs belong to."""
+    h = hashlib.sha1()
+    for scn in scns:
+        h.update(np.array([scn.sr, scn.seed, len(scn.ops)], dtype="<i8").tobytes())
+        for op in scn.ops:
+            if op[0] == "q":
+                h.update(b"n" if op[1] is None else np.ascontiguousarray(op[1], dtype="<f8").tobytes())
+                h.update(np.array([op[2], op[3], op[4], op[5]], dtype="<i8").tobytes())
+            else:
+                h.update(np.array([-1 if op[0] == "drain" else op[1]], dtype="<i8").tobytes())
+    return h.hexdigest()
+
+
+REFERENCE_BATCHES = ((1, False), (2, True), (11, False), (12, True), (21, False), (22, True))    # the GPU parity tests' random_batch seeds
+
+
+def batch_scenarios(seed, wild, n_utt=1500):
+    """random_batch(seed) utterance by utterance, as drain-only scenarios."""
+    b = random_batch(np.random.default_rng(seed), n_utt, wild=wild)
+    out = []
+    for u in range(n_utt):
+        ops = [q(None if b["isnull"][k] else b["frames"][k], b["min"][k], b["fade"][k], b["index"][k])
+               for k in range(b["frame_start"][u], b["frame_start"][u + 1])]
+        out.append(Scenario("batch%d_%04d" % (seed, u), ops + [("drain",)], seed=int(b["seeds"][u])))
+    return out
+
+
+def group_digest(results):
+    """One SHA-1 over the sequence digests of a group, in order."""
+    return hashlib.sha1("".join(results).encode()).hexdigest()
+
+
+def reference_table(player_of, ref=None, progress=None):
+    """What `player_of(sr, seed)` answers on everything tests/golden/reference.json records, in that file's layout."""
+    table = {"numpy": np.__version__, "scenarios": {}, "fuzz": {}, "batches": {}}
+    for scn in build_scenarios(ref or Ref()):
+        pcm, marks = play(scn, player_of(scn.sr, scn.seed))
+        flat = np.concatenate(pcm) if pcm else np.zeros(0, np.int16)
+        table["scenarios"][scn.name] = {"sha1": hashlib.sha1(flat.tobytes()).hexdigest(), "calls": [int(len(x)) for x in pcm],
+                                        "marks": [int(m) for m in marks]}
+    samples = sum(sum(v["calls"]) for v in table["scenarios"].values())
+    for extreme in (False, True):
+        scns = [fuzz_sequence(s, extreme) for s in range(N_FUZZ)]
+        out = []
+        for scn in scns:
+            pcm, marks = play(scn, player_of(scn.sr, scn.seed))
+            out.append(sequence_digest(pcm, marks)); samples += sum(len(x) for x in pcm)
+        table["fuzz"]["extreme" if extreme else "plain"] = {"input": input_digest(scns), "sha1": out}
+        if progress:
+            progress("fuzz %s: %d samples so far" % ("extreme" if extreme else "plain", samples))
+    for seed, wild in REFERENCE_BATCHES:
+        scns = batch_scenarios(seed, wild)
+        out = []
+        for scn in scns:
+            pcm, marks = play(scn, player_of(scn.sr, scn.seed))
+            out.append(sequence_digest(pcm, marks)); samples += sum(len(x) for x in pcm)
+        table["batches"]["%d" % seed] = {"wild": bool(wild), "input": input_digest(scns), "sha1": group_digest(out)}
+    table["samples"] = int(samples)
+    return table

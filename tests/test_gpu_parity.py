@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from tests import oracle, scenarios
+from tests.scenarios import random_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -296,46 +297,6 @@ def test_full_size_cfg1_properties():
     print("cfg1: %d utterances against the oracle, %d with one-LSB differences" % (n, differ))
     assert n == 4096
     bp.close()
-
-
-def random_batch(rng, n_utt, quiet_fraction=0.3, wild=False, nasal_fraction=0.4):
-    """Ragged random utterances: random formants / bandwidths / gains / pitches, random durations
-    (including fade > frame, fade 0, 1-sample frames), NULL frames anywhere, optional NaN holds."""
-    frames, mins, fades, nul, start, seeds = [], [], [], [], [0], []
-    for u in range(n_utt):
-        n = int(rng.integers(1, 9))
-        quiet = rng.random() < quiet_fraction
-        prev_real = False
-        for k in range(n):
-            f = np.zeros(47)
-            f[0] = rng.uniform(40, 400); f[46] = f[0] * rng.uniform(0.6, 1.6)
-            if rng.random() < 0.3:
-                f[1] = rng.uniform(0, 0.2); f[2] = rng.uniform(0, 8)
-            f[5] = rng.uniform(0, 1)
-            if not quiet:
-                f[3] = rng.uniform(0, 0.5) * (rng.random() < 0.5); f[4] = rng.uniform(0, 1)
-                f[6] = rng.uniform(0, 1) * (rng.random() < 0.5); f[24] = rng.uniform(0, 1) * (rng.random() < 0.6)
-            f[7:13] = np.sort(rng.uniform(150, 5500, 6)); f[13] = rng.uniform(0, 600) * (rng.random() < 0.5); f[14] = rng.uniform(200, 500)
-            f[15:23] = rng.uniform(30, 1000, 8); f[23] = rng.uniform(0, 1) * (rng.random() < nasal_fraction)
-            f[25:31] = np.sort(rng.uniform(150, 5500, 6)); f[31:37] = rng.uniform(30, 1000, 6); f[37:43] = rng.uniform(0, 1, 6)
-            f[43] = rng.uniform(0, 1); f[44] = rng.uniform(0, 1.5); f[45] = rng.uniform(0.2, 2.5)
-            is_null = rng.random() < 0.2
-            if wild and prev_real and not is_null and rng.random() < 0.3:
-                f[rng.integers(1, 46, size=3)] = np.nan          # "hold" semantics (utils.h:21); only where a value exists to hold
-            prev_real = not is_null
-            frames.append(f); nul.append(is_null)
-            mode = rng.integers(0, 5)
-            if mode == 0: m, fd = int(rng.integers(0, 4)), int(rng.integers(0, 4))
-            elif mode == 1: m, fd = int(rng.integers(1, 300)), int(rng.integers(300, 900))       # fade longer than the frame
-            else: m, fd = int(rng.integers(50, 2500)), int(rng.integers(0, 700))
-            if not is_null and m == 0 and not (wild and rng.random() < 0.25):
-                m = 1                                           # M = 0 on a real frame divides by zero (frame.cpp:98: an infinite or NaN pitch,
-                                                                # samples of 32000): in the wild batches only, and there on one such frame in four
-            mins.append(m); fades.append(fd)
-        start.append(start[-1] + n); seeds.append(int(rng.integers(0, 2 ** 32)))
-    return dict(frames=np.array(frames), min=np.array(mins, np.uint32), fade=np.array(fades, np.uint32),
-                index=np.full(len(mins), -1, np.int32), isnull=np.array(nul, np.uint8), frame_start=np.array(start, np.int64),
-                seeds=np.array(seeds, np.uint32))
 
 
 @pytest.mark.parametrize("layout", [1, 0])

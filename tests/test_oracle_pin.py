@@ -7,6 +7,10 @@ rand() after srand(1)): the cfg0 PCM (SHA-1, first samples, extrema, call
 lengths) and, for the eight sampleIpa.txt lines synthesised in one process in
 order, the sample counts and SHA-1 prefixes.  The frame streams fed here come
 from the reference's own frame producer (tests/golden/ref_frames.npz).
+
+These nine answers are plain speech.  tests/test_reference_pin.py compiles the reference itself (oracle/Makefile, target
+`ref`), gets the same nine answers out of that build, and compares the oracle with it call by call on everything else --
+purge, chunked pulls, index marks, NaN hold, zero-length frames, vibrato, other sample rates, overflowing coefficients.
 """
 import ctypes
 import hashlib

@@ -238,7 +238,7 @@ def expected_flags(f, sr=22050):
         nasal = (f[:, 23] != 0) | ~(f[:, 21] >= 1) | ~(f[:, 22] >= 0) | ~(f[:, 21] <= 1e6) | ~(f[:, 22] <= 1e6) | ~(np.abs(f[:, 13]) <= 1e6) | \
                 ~(np.abs(f[:, 14]) <= 1e6) | ~(np.abs(f[:, 5]) <= 1e30) | ~(np.abs(f[:, 44]) <= 1e30) | ~(np.abs(f[:, 0]) <= 1e30) | ~(np.abs(f[:, 46]) <= 1e30)
         freq = np.concatenate([f[:, 7:15], f[:, 25:31]], axis=1); bw = np.concatenate([f[:, 15:23], f[:, 31:37]], axis=1)
-        unbounded = (~(np.abs(freq) <= max_f)).any(axis=1) | (~(np.abs(bw) <= max_bw)).any(axis=1)
+        unbounded = (~(np.abs(freq) <= max_f)).any(axis=1) | (~(bw >= 0)).any(axis=1) | (~(bw <= max_bw)).any(axis=1)
     return noise * 1 + nonfinite * 2 + nasal * 4 + unbounded * 8
 
 
