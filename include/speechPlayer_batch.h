@@ -133,6 +133,52 @@ int speechPlayer_batch_setUtterancesDevice(speechPlayer_batch_t batch, long long
  */
 long long speechPlayer_batch_exportPcm(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
 	void* deviceOut, int format, long long rowStride, void* stream);
+/*
+ * The timeline of a batch and its per-sample parameter tracks: what was spoken when, and the frame the synthesiser used on a given
+ * sample -- the reference's getCurrentFrame() (src/frame.cpp:121-126), which a handle's caller can follow between pulls
+ * (speechPlayer_getLastIndex) and a batch's caller could not.  For utterance u of a set batch, of length L, and sample t in 0 .. L-1:
+ *   track(u, c, t), c in 0 .. 46 (the order of speechPlayer_frame_t): field c of the frame getCurrentFrame() returned for sample t of a
+ *       fresh handle that had the utterance's frames queued, the reference's quirks included: sample 0 and every sample on which a request
+ *       is dequeued see the frame of the sample before (all zeros at t = 0); a NaN target holds (src/utils.h:20-23) and the hold after such
+ *       a fade keeps the value of the fade's last sample; a NULL request fades to the previous request's values with preFormantGain 0 and
+ *       the pitch frozen; voicePitch glides by one addition per hold sample (src/frame.cpp:77), and a real frame with minFrameDuration 0
+ *       makes it infinite or NaN (src/frame.cpp:98)
+ *   SPEECHPLAYER_TRACK_MARK   what speechPlayer_getLastIndex answers after sample t has been generated
+ *   SPEECHPLAYER_TRACK_FRAME  the number, within the utterance, of the request most recently dequeued (0 at t = 0)
+ * Request k is dequeued on sample S_k = sum_{i<k} (max(M_i, F_i + 1) + 1), F_i = max(fadeDuration_i, 1); S_n = L.  The tracks are a function
+ * of the batch as set: they do not depend on the mode, the layout, the planner's choices or on whether the batch has been synthesised.
+ */
+#define SPEECHPLAYER_TRACK_MARK  47
+#define SPEECHPLAYER_TRACK_FRAME 48
+/* Host only, touches no device (like speechPlayer_planDirect): firstSample[frameStart[nUtterances]] = S_k of every request,
+ * length[nUtterances] = L_u (either may be NULL).  Returns the number of frames, -1 on bad arguments. */
+long long speechPlayer_planTimeline(long long nUtterances, const long long* frameStart, const unsigned int* minFrameDuration,
+	const unsigned int* fadeDuration, long long* firstSample, long long* length);
+/* The same for utterance u of a set batch (any of the set calls, shared lists and records included), with its marks: returns the
+ * utterance's number of frames n; fills firstSample[n + 1] and userIndex[n] (each may be NULL) when n <= capacity. */
+long long speechPlayer_batch_timeline(speechPlayer_batch_t batch, long long utterance, long long* firstSample, int* userIndex,
+	long long capacity);
+/* Tracks of chosen utterances into caller-owned device memory on the caller's stream.  Step j of an utterance is sample
+ * phase + j * hop; an utterance has ceil((L - phase) / hop) steps (0 when L <= phase).  Element (i, j, q) =
+ * track(utterances[i], columns[q], phase + j * hop).
+ *   columns[nColumns]   0 .. 48, any order, repeats allowed
+ *   format              0 float64 (the value itself), 1 float32 (the value rounded to nearest; marks beyond 2^24 lose bits)
+ *   rowStride           > 0: row i starts at element i * rowStride * nColumns, steps past the utterance's end are 0; below the
+ *                       largest step count it is refused; 0: the utterances back to back
+ * utterances / nUtterances / deviceOut / stream as in speechPlayer_batch_exportPcm (deviceOut aligned to the element size; 16-byte
+ * alignment takes the vector stores).  Returns the elements written (0 writes nothing and needs no buffer), -1 on error.
+ * Ordering by events, no host waits: the export needs no synthesis launch -- it is valid as soon as the set call has returned (what
+ * that call left queued on the device is waited for by an event) and does not wait for a running launch; the NEXT set call, which
+ * replaces the frames the export reads, waits for the exports in flight: on the device where the buffers are reused, on the host where
+ * one is freed or where pageable frames are copied outside the streams' order.  With more than sixteen exports of one batch in flight
+ * the seventeenth waits for the first.  voicePitch (column 0) is carried through a table of 8 bytes per (frame list, step); an export
+ * whose table would exceed option "pitch_table_mb" (default 256) proceeds in pieces of utterances, and exports that ask for column 0
+ * follow one another on the device.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: no batch, a column outside 0 .. 48, nColumns <= 0, hop <= 0, phase < 0, an
+ * unknown format, an utterance number outside the batch, a rowStride below the largest step count, an output that is not device memory
+ * of the batch's device, misaligned or too small. */
+long long speechPlayer_batch_exportTracks(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
+	const int* columns, int nColumns, long long hop, long long phase, void* deviceOut, int format, long long rowStride, void* stream);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

@@ -53,6 +53,7 @@ EXPORTS = [
     "speechPlayer_ipa_records", "speechPlayer_records_view", "speechPlayer_records_free", "speechPlayer_voiceIndex", "speechPlayer_voiceDefine", "speechPlayer_voicePresetCount",
     "speechPlayer_batch_setUtterancesDevice", "speechPlayer_batch_exportPcm", "speechPlayer_batch_device", "speechPlayer_batch_lengths",
     "speechPlayer_queueFramesMany", "speechPlayer_queueFramesManyDevice", "speechPlayer_synthesizeManyExport", "speechPlayer_handleDevice",
+    "speechPlayer_planTimeline", "speechPlayer_batch_timeline", "speechPlayer_batch_exportTracks",
 ]
 
 
@@ -305,6 +306,12 @@ def load():
     L.speechPlayer_planTracksFacts.argtypes = [i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
     L.speechPlayer_batch_setUtterancesDevice.restype = i32
     L.speechPlayer_batch_setUtterancesDevice.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.speechPlayer_planTimeline.restype = i64
+    L.speechPlayer_planTimeline.argtypes = [i64, vp, vp, vp, vp, vp]
+    L.speechPlayer_batch_timeline.restype = i64
+    L.speechPlayer_batch_timeline.argtypes = [vp, i64, vp, vp, i64]
+    L.speechPlayer_batch_exportTracks.restype = i64
+    L.speechPlayer_batch_exportTracks.argtypes = [vp, vp, i64, vp, i32, i64, i64, vp, i32, i64, vp]
     L.speechPlayer_batch_exportPcm.restype = i64
     L.speechPlayer_batch_exportPcm.argtypes = [vp, vp, i64, vp, i32, i64, vp]
     L.speechPlayer_batch_device.restype = i32

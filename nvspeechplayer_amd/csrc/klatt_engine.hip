@@ -15,6 +15,7 @@
 #include "klatt_tracks.h"
 #include "klatt_direct.h"
 #include "klatt_plan.h"
+#include "klatt_timeline.h"
 
 #include <algorithm>
 #include <cmath>
@@ -627,6 +628,20 @@ struct Batch {
     static constexpr int kExportSlots = 16;
     ExportSlot exportSlot[kExportSlots];
     unsigned exportNext = 0;
+    // speechPlayer_batch_exportTracks (klatt_timeline.h) reads the frames, the meta words and the list table of the batch AS SET, on the
+    // caller's stream: behind setDone / setCopied (recorded by the set call on its two streams), and ahead of the NEXT set call, which
+    // waits for the slots' last exports before it overwrites what they read (settle_track_exports).  The per-request records are built
+    // once per set call, by the first export (timelineReady: recorded behind klatt_timeline_requests on that export's stream); the
+    // voicePitch table is shared by the exports that ask for column 0, which follow one another on the device (pitchDone).
+    std::vector<uint32_t> uttList;             // [nUtt] the list an utterance speaks
+    DeviceBuffer<long long> dListStart;        // [nLists + 1]
+    DeviceBuffer<TimelineReq> dTimeline;       // [nFrames]
+    DeviceBuffer<double> dPitch;
+    hipEvent_t setDone = nullptr, setCopied = nullptr, timelineReady = nullptr, pitchDone = nullptr;
+    bool timelineFresh = false, pitchUsed = false;
+    long long pitchBudgetMB = 256;             // option "pitch_table_mb": an export whose voicePitch table would be larger proceeds in pieces
+    ExportSlot trackSlot[kExportSlots];
+    unsigned trackNext = 0;
 };
 
 // The batch's own streams wait (on the device) for the exports that still read its pool.
@@ -641,6 +656,18 @@ int sync_exports(Batch* b)
 {
     for (auto& s : b->exportSlot)
         if (s.used) { HIP_TRY(hipEventSynchronize(s.done)); s.used = false; }
+    return 0;
+}
+
+// A set call replaces what the track exports read.  Where the buffers are reused its two streams wait for the exports in flight on the
+// device; where one is freed (it must grow), or where the frames are copied outside the streams' order, the host waits.
+int settle_track_exports(Batch* b, bool onHost)
+{
+    for (auto& s : b->trackSlot) {
+        if (!s.used) continue;
+        if (onHost) { HIP_TRY(hipEventSynchronize(s.done)); s.used = false; }
+        else { HIP_TRY(hipStreamWaitEvent(b->stream, s.done, 0)); HIP_TRY(hipStreamWaitEvent(b->copyStream, s.done, 0)); }
+    }
     return 0;
 }
 
@@ -2417,6 +2444,8 @@ speechPlayer_batch_t speechPlayer_batch_create(int sampleRate, int device)
               hipEventCreateWithFlags(&b->inputReady, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&b->pcmReady, hipEventDisableTiming) == hipSuccess;
     for (auto& s : b->exportSlot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
+    for (auto& s : b->trackSlot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
+    for (hipEvent_t* e : {&b->setDone, &b->setCopied, &b->timelineReady, &b->pitchDone}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     { const char* e = getenv("SPEECHPLAYER_TRACKS"); if (e) b->tracks = atoi(e) ? 1 : 0; }
     { const char* e = getenv("SPEECHPLAYER_DIRECT"); if (e) b->direct = std::min(2, std::max(0, atoi(e))); }
     { const char* e = getenv("SPEECHPLAYER_DIRECT_LEAN"); if (e) b->directLean = std::min(1, std::max(-1, atoi(e))); }
@@ -2442,6 +2471,13 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch)
         if (s.done) (void)hipEventDestroy(s.done);
         s.host.release(); s.dev.release();
     }
+    (void)settle_track_exports(b, true);
+    for (auto& s : b->trackSlot) {
+        if (s.done) (void)hipEventDestroy(s.done);
+        s.host.release(); s.dev.release();
+    }
+    for (hipEvent_t e : {b->setDone, b->setCopied, b->timelineReady, b->pitchDone}) if (e) (void)hipEventDestroy(e);
+    b->dListStart.release(); b->dTimeline.release(); b->dPitch.release();
     if (b->inputReady) (void)hipEventDestroy(b->inputReady);
     if (b->pcmReady) (void)hipEventDestroy(b->pcmReady);
     b->dShapeIdx.release(); b->dShapeRows.release();
@@ -2483,6 +2519,8 @@ int speechPlayer_batch_setOption(speechPlayer_batch_t batch, const char* name, i
     if (!strcmp(name, "direct")) { b->direct = value < 0 ? 0 : (value > 2 ? 2 : value); return 0; }
     // direct_lean: the direct stages two workgroups to a CU (1), one (0), or the engine's choice (-1, default); same PCM in MODE_EXACT
     if (!strcmp(name, "direct_lean")) { b->directLean = value < 0 ? -1 : (value ? 1 : 0); return 0; }
+    // pitch_table_mb: read by speechPlayer_batch_exportTracks (the voicePitch table of an export; a larger one proceeds in pieces)
+    if (!strcmp(name, "pitch_table_mb")) { b->pitchBudgetMB = value < 1 ? 1 : value; return 0; }
     set_error("unknown option %s", name);
     return -1;
 }
@@ -2515,7 +2553,7 @@ static void batch_clear(Batch* b)
     b->nUtt = 0; b->nFrames = 0; b->nFramesSpoken = 0; b->nLists = 0; b->nSlots = 0; b->nQuiet = 0; b->nNoNasal = 0; b->nNoNasalUtt = 0; b->totalSamples = 0; b->poolSamples = 0;
     b->nTracked = 0; b->nTrackedUtt = 0; b->nJobs = 0; b->trackEntries = 0; b->nDirect = 0; b->nDirectUtt = 0; b->nDirectFrames = 0;
     b->lens.clear(); b->outStart.assign(1, 0); b->results.clear(); b->resultsFresh = false; b->floatFresh = false;
-    b->uttFrameStart.clear(); b->uttFrames.clear();
+    b->uttFrameStart.clear(); b->uttFrames.clear(); b->uttList.clear(); b->timelineFresh = false;
 }
 
 static int batch_set(Batch* b, const SetInput& in);
@@ -2770,13 +2808,19 @@ static int batch_set(Batch* b, const SetInput& in)
     // of a batch of full frames, 0.6 GB for BASELINE configs[2] -- start on their way now: on a thread of their own from pageable memory
     // (such a copy keeps its caller until it is done), as one asynchronous DMA from page-locked memory (speechPlayer_hostAlloc); records
     // travel the same way (32 bytes per frame) with their shape table, and klatt_expand_frames builds frames and meta words behind them.
+    // the track exports in flight read the frames, meta words and list table this call replaces
+    const bool framesPinned = !byRecords && nF > 0 && is_pinned(in.frames);
+    {
+        const bool grows = (size_t)nF * kNumParams > b->dFrames.cap || (size_t)nF > b->dMeta.cap || (size_t)nL + 1 > b->dListStart.cap;
+        const bool unordered = !byRecords && !byDevice && !framesPinned;      // pageable frames: copied by a thread of their own, or staged by the runtime
+        if (settle_track_exports(b, grows || unordered)) return -1;
+    }
     int earlyRc = 0;
     std::string earlyErr;
     std::thread early;
     bool earlyStarted = false;
     // while a DMA reads the caller's arrays no exit may leave it running: every return below passes this guard
     struct CopyGuard { Batch* b; bool armed = false; ~CopyGuard() { if (armed) (void)hipStreamSynchronize(b->copyStream); } } copyGuard{b};
-    const bool framesPinned = !byRecords && nF > 0 && is_pinned(in.frames);
     if (byRecords) {
         if (b->dFrames.reserve(std::max<size_t>((size_t)nF * kNumParams, 1)) || b->dMeta.reserve(std::max<size_t>((size_t)nF, 1)) ||
             b->dRecords.reserve(std::max<size_t>((size_t)nF, 1)) || b->dShapeTable.reserve(std::max<size_t>((size_t)in.nShapes * kNumParams, 1))) { batch_clear(b); return -1; }
@@ -3188,8 +3232,9 @@ static int batch_set(Batch* b, const SetInput& in)
         if ((size_t)pool > b->dPcm.cap && sync_exports(b)) return -1;      // (a new pool: the old one is freed once no export reads it)
         if (b->dFrames.reserve(std::max<size_t>((size_t)nF * kNumParams, 1)) || b->dMeta.reserve(std::max<size_t>(nF, 1)) ||
             b->dUtt.reserve(std::max<size_t>(nU, 1)) || b->dOrder.reserve(std::max<size_t>(nSlotsAll, 1)) ||
-            b->dResult.reserve(std::max<size_t>(nU, 1)) || b->dPcm.reserve(std::max<size_t>(pool, 1)))
+            b->dResult.reserve(std::max<size_t>(nU, 1)) || b->dPcm.reserve(std::max<size_t>(pool, 1)) || b->dListStart.reserve((size_t)nL + 1))
             return -1;
+        HIP_TRY(hipMemcpyAsync(b->dListStart.ptr, listStart, ((size_t)nL + 1) * sizeof(long long), hipMemcpyHostToDevice, b->stream));
         if (nTrackedUtt > 0) {
             if (b->dFlatRef.reserve((size_t)nF) || b->dJobs.reserve(jobs.size()) || b->dShapes.reserve(plan.shapes.size()) ||
                 b->dTrack.reserve((size_t)trackEntries + kTrackPad)) return -1;
@@ -3272,6 +3317,12 @@ static int batch_set(Batch* b, const SetInput& in)
     b->totalSamples = total; b->poolSamples = pool;
     b->lens.swap(lens); b->outStart.swap(outStart); b->denseStart.swap(denseStart);
     b->uttFrameStart.swap(uttFrameStart); b->uttFrames.swap(uttFrames);
+    b->uttList.resize((size_t)nU);
+    for (long long u = 0; u < nU; ++u) b->uttList[(size_t)u] = (uint32_t)list_of(u);
+    b->timelineFresh = false;
+    // (what this call left queued on its two streams, if anything: the track exports wait for it on the device)
+    HIP_TRY(hipEventRecord(b->setDone, b->stream));
+    HIP_TRY(hipEventRecord(b->setCopied, b->copyStream));
     b->results.clear();
     b->resultsFresh = false;
     b->floatFresh = false;
@@ -4251,6 +4302,218 @@ long long speechPlayer_planDirect(long long nUtterances, const long long* frameS
         if (flags) flags[k] = jobs[(size_t)k].flags;
     }
     return nF;
+}
+
+// Host-only view of a batch's timeline (tests, tools, callers that plan before they set; touches no device): the sample every request
+// is dequeued on and every utterance's length, from the durations alone (reference src/frame.cpp:41-80 with src/speechPlayer.cpp:36).
+long long speechPlayer_planTimeline(long long nUtterances, const long long* frameStart, const unsigned int* minFrameDuration,
+                                    const unsigned int* fadeDuration, long long* firstSample, long long* length)
+{
+    begin_call();
+    if (nUtterances < 0 || !frameStart || frameStart[0] != 0) { set_error("planTimeline: bad arguments"); return -1; }
+    for (long long u = 0; u < nUtterances; ++u)
+        if (frameStart[u + 1] < frameStart[u]) { set_error("planTimeline: frameStart not monotone at %lld", u); return -1; }
+    const long long nF = frameStart[nUtterances];
+    if (nF > 0 && (!minFrameDuration || !fadeDuration)) { set_error("planTimeline: no durations"); return -1; }
+    for (long long u = 0; u < nUtterances; ++u) {
+        long long S = 0;
+        for (long long k = frameStart[u]; k < frameStart[u + 1]; ++k) {
+            if (firstSample) firstSample[k] = S;
+            FrameMeta m;
+            m.minSamples = minFrameDuration[k]; m.fadeSamples = std::max(fadeDuration[k], 1u);
+            S += timeline_span(m);
+        }
+        if (length) length[u] = S;
+    }
+    return nF;
+}
+
+long long speechPlayer_batch_timeline(speechPlayer_batch_t batch, long long u, long long* firstSample, int* userIndex, long long capacity)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b || u < 0 || u >= b->nUtt) { set_error("batch_timeline: no such utterance"); return -1; }
+    HIP_TRY(hipSetDevice(b->device));
+    const long long n = b->uttFrames[(size_t)u], k0 = b->uttFrameStart[(size_t)u];
+    if (n > capacity || (!firstSample && !userIndex)) return n;
+    std::vector<FrameMeta> m((size_t)n);
+    if (n) HIP_TRY(hipMemcpy(m.data(), b->dMeta.ptr + k0, (size_t)n * sizeof(FrameMeta), hipMemcpyDeviceToHost));
+    long long S = 0;
+    for (long long k = 0; k < n; ++k) {
+        if (firstSample) firstSample[k] = S;
+        if (userIndex) userIndex[k] = m[(size_t)k].userIndex;
+        S += timeline_span(m[(size_t)k]);
+    }
+    if (firstSample) firstSample[n] = S;
+    return n;
+}
+
+// The tracks of chosen utterances into the caller's device memory on the caller's stream (klatt_timeline.h), ordered by events only:
+// behind the set call's own device work (setDone, setCopied), behind the per-request records (built by the first export after a set call)
+// and ahead of the next set call (settle_track_exports).  Rows, columns and list descriptors of all pieces are staged through one
+// page-locked slot; nothing waits on the host unless all slots hold exports in flight or a buffer of the batch must grow.
+long long speechPlayer_batch_exportTracks(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const int* columns,
+                                          int nColumns, long long hop, long long phase, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("exportTracks: no batch"); return -1; }
+    if (format != 0 && format != 1) { set_error("exportTracks: format %d (0 float64, 1 float32)", format); return -1; }
+    if (!columns || nColumns <= 0) { set_error("exportTracks: %d columns", nColumns); return -1; }
+    if (hop <= 0 || phase < 0) { set_error("exportTracks: hop %lld, phase %lld", hop, phase); return -1; }
+    if (rowStride < 0) { set_error("exportTracks: rowStride %lld", rowStride); return -1; }
+    bool needPitch = false;
+    for (int q = 0; q < nColumns; ++q) {
+        if (columns[q] < 0 || columns[q] >= kTrackColumns) { set_error("exportTracks: columns[%d] = %d (0 .. %d)", q, columns[q], kTrackColumns - 1); return -1; }
+        needPitch = needPitch || columns[q] == 0;
+    }
+    const long long n = utterances ? nUtterances : b->nUtt;
+    if (n < 0) { set_error("exportTracks: %lld utterances", n); return -1; }
+    if (b->nFrames >= 0xFFFFFFFFll) { set_error("exportTracks: too many frames"); return -1; }
+    // no utterance is longer than 2^32 samples: a larger hop or phase means the same
+    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
+    const bool packed = rowStride == 0;
+    std::vector<TimelineRow> rows((size_t)n);
+    long long maxSteps = 0, totalSteps = 0;
+    for (long long i = 0; i < n; ++i) {
+        const long long u = utterances ? utterances[i] : i;
+        if (u < 0 || u >= b->nUtt) { set_error("exportTracks: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, u, b->nUtt); return -1; }
+        const long long L = b->lens[(size_t)u];
+        TimelineRow& r = rows[(size_t)i];
+        r.frame0 = b->uttFrameStart[(size_t)u]; r.nFrames = b->uttFrames[(size_t)u]; r.slot = 0;
+        r.steps = L > phase ? (L - phase + hop - 1) / hop : 0;
+        maxSteps = std::max(maxSteps, r.steps);
+        totalSteps += r.steps;
+    }
+    if (!packed && rowStride < maxSteps) { set_error("exportTracks: rowStride %lld is below the largest step count (%lld)", rowStride, maxSteps); return -1; }
+    if (!packed && n > 0 && n > (1ll << 50) / rowStride / nColumns) { set_error("exportTracks: %lld rows of %lld steps of %d columns", n, rowStride, nColumns); return -1; }
+    if (packed && totalSteps > (1ll << 50) / nColumns) { set_error("exportTracks: %lld steps of %d columns", totalSteps, nColumns); return -1; }
+    const long long elements = (packed ? totalSteps : n * rowStride) * nColumns;
+    if (elements == 0) return 0;
+    const size_t elSize = format ? sizeof(float) : sizeof(double);
+    HIP_TRY(hipSetDevice(b->device));
+    if (!deviceOut) { set_error("exportTracks: no output buffer"); return -1; }
+    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportTracks")) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    // the pieces: runs of rows whose distinct lists fit the voicePitch table (one piece when column 0 is not asked for)
+    struct Piece { long long r0, r1, nLists, rowsOff, startOff, chunkOff, listOff, nChunks; };
+    std::vector<Piece> pieces;
+    std::vector<TimelineList> lists;      // of all pieces, one after the other
+    long long slotsPerPiece = 0;
+    if (needPitch && maxSteps > 0) {
+        slotsPerPiece = std::max<long long>(1, (b->pitchBudgetMB << 20) / (maxSteps * (long long)sizeof(double)));
+        std::vector<long long> stamp((size_t)b->nLists, -1);     // the piece that last gave the list a slot
+        std::vector<uint32_t> slotOf((size_t)b->nLists, 0);
+        Piece pc{0, 0, 0, 0, 0, 0, 0, 0};
+        for (long long i = 0; i < n; ++i) {
+            const long long u = utterances ? utterances[i] : i;
+            const uint32_t l = b->uttList[(size_t)u];
+            const long long id = (long long)pieces.size();
+            if (stamp[l] != id) {
+                if (pc.nLists == slotsPerPiece) {
+                    pc.r1 = i; pieces.push_back(pc);
+                    pc = Piece{i, i, 0, 0, 0, 0, 0, 0};
+                }
+                stamp[l] = (long long)pieces.size();
+                slotOf[l] = (uint32_t)pc.nLists++;
+                lists.push_back(TimelineList{rows[(size_t)i].frame0, (long long)rows[(size_t)i].nFrames});
+            }
+            rows[(size_t)i].slot = slotOf[l];
+        }
+        pc.r1 = n; pieces.push_back(pc);
+    } else {
+        pieces.push_back(Piece{0, n, 0, 0, 0, 0, 0, 0});
+    }
+    // the staging block: columns | rows | per piece: step starts and chunk rows (packed), lists
+    std::vector<long long> words;      // step starts and chunk rows of all pieces
+    for (Piece& pc : pieces) {
+        if (!packed) continue;
+        pc.startOff = (long long)words.size();
+        long long acc = 0;
+        for (long long i = pc.r0; i < pc.r1; ++i) { words.push_back(acc); acc += rows[(size_t)i].steps; }
+        words.push_back(acc);
+        const long long nr = pc.r1 - pc.r0;
+        pc.nChunks = (acc >> kTimelineChunkLog2) + 1;
+        pc.chunkOff = (long long)words.size();
+        long long r = 0;
+        for (long long c = 0; c < pc.nChunks; ++c) {
+            while (r + 1 < nr && words[(size_t)(pc.startOff + r + 1)] <= (c << kTimelineChunkLog2)) ++r;
+            words.push_back(r);
+        }
+        words.push_back(std::max<long long>(nr - 1, 0));
+    }
+    const size_t colBytes = ((size_t)nColumns * sizeof(int) + 15) / 16 * 16, rowBytes = (size_t)n * sizeof(TimelineRow);
+    const size_t wordBytes = words.size() * sizeof(long long), listBytes = lists.size() * sizeof(TimelineList);
+    const size_t rowsAt = colBytes, wordsAt = (rowsAt + rowBytes + 15) / 16 * 16, listsAt = wordsAt + wordBytes, bytes = listsAt + listBytes;
+
+    // (every allocation first: once a kernel is queued the slot's event must come to stand behind it)
+    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
+    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
+    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
+    long long pitchStride = 0;
+    if (needPitch && maxSteps > 0) {
+        long long most = 0;
+        for (const Piece& pc : pieces) most = std::max(most, pc.nLists);
+        pitchStride = maxSteps;
+        if ((size_t)(most * pitchStride) > b->dPitch.cap && settle_track_exports(b, true)) return -1;
+        if (b->dPitch.reserve((size_t)(most * pitchStride))) return -1;
+    }
+    if (!b->timelineFresh) {
+        if ((size_t)b->nFrames > b->dTimeline.cap && settle_track_exports(b, true)) return -1;
+        if (b->dTimeline.reserve(std::max<size_t>((size_t)b->nFrames, 1))) return -1;
+    }
+    if (b->timelineFresh) HIP_TRY(hipStreamWaitEvent(st, b->timelineReady, 0));
+    else {
+        // the records of every list of the batch, once per set call
+        HIP_TRY(hipStreamWaitEvent(st, b->setDone, 0));
+        HIP_TRY(hipStreamWaitEvent(st, b->setCopied, 0));
+        const unsigned grid = (unsigned)std::min<long long>((b->nLists + 255) / 256, 4ll * b->cus);
+        hipLaunchKernelGGL(klatt_timeline_requests, dim3(std::max(grid, 1u)), dim3(256), 0, st, b->dMeta.ptr, b->dListStart.ptr, b->nLists, b->dTimeline.ptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(b->timelineReady, st));
+        b->timelineFresh = true;
+    }
+    if (pitchStride > 0 && b->pitchUsed) HIP_TRY(hipStreamWaitEvent(st, b->pitchDone, 0));      // (the table's previous export, whichever stream it ran on)
+    char* h = static_cast<char*>(slot.host.ptr);
+    memcpy(h, columns, (size_t)nColumns * sizeof(int));
+    memcpy(h + rowsAt, rows.data(), rowBytes);
+    if (wordBytes) memcpy(h + wordsAt, words.data(), wordBytes);
+    if (listBytes) memcpy(h + listsAt, lists.data(), listBytes);
+    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
+    const int* dCols = reinterpret_cast<const int*>(slot.dev.ptr);
+    const TimelineRow* dRows = reinterpret_cast<const TimelineRow*>(slot.dev.ptr + rowsAt);
+    const long long* dWords = reinterpret_cast<const long long*>(slot.dev.ptr + wordsAt);
+    const TimelineList* dLists = reinterpret_cast<const TimelineList*>(slot.dev.ptr + listsAt);
+    long long listAt = 0, elementAt = 0;
+    for (const Piece& pc : pieces) {
+        const long long nr = pc.r1 - pc.r0;
+        const long long pieceElements = (packed ? words[(size_t)(pc.startOff + nr)] : nr * rowStride) * nColumns;
+        if (pc.nLists > 0) {
+            hipLaunchKernelGGL(klatt_timeline_pitch, dim3((unsigned)((pc.nLists + 63) / 64)), dim3(64), 0, st, b->dFrames.ptr, b->dMeta.ptr,
+                               dLists + listAt, pc.nLists, hop, phase, pitchStride, b->dPitch.ptr);
+            HIP_TRY(hipGetLastError());
+            listAt += pc.nLists;
+        }
+        if (pieceElements > 0) {
+            char* out = static_cast<char*>(deviceOut) + (size_t)elementAt * elSize;
+            const long long nLane = (pieceElements * (long long)elSize + 15) / 16;
+            const unsigned grid = (unsigned)std::min<long long>((nLane + 255) / 256, 8ll * b->cus);
+            const int vec = reinterpret_cast<uintptr_t>(out) % 16 == 0;
+            const long long* dStart = packed ? dWords + pc.startOff : nullptr;
+            const long long* dChunk = packed ? dWords + pc.chunkOff : nullptr;
+            if (format) hipLaunchKernelGGL(klatt_timeline_dense<true>, dim3(grid), dim3(256), 0, st, b->dFrames.ptr, b->dTimeline.ptr, dRows + pc.r0, dStart, dChunk,
+                                           nr, rowStride, dCols, nColumns, hop, phase, b->dPitch.ptr, pitchStride, (void*)out, pieceElements, vec);
+            else hipLaunchKernelGGL(klatt_timeline_dense<false>, dim3(grid), dim3(256), 0, st, b->dFrames.ptr, b->dTimeline.ptr, dRows + pc.r0, dStart, dChunk,
+                                    nr, rowStride, dCols, nColumns, hop, phase, b->dPitch.ptr, pitchStride, (void*)out, pieceElements, vec);
+            HIP_TRY(hipGetLastError());
+            elementAt += pieceElements;
+        }
+    }
+    HIP_TRY(hipEventRecord(slot.done, st));
+    slot.used = true;
+    if (needPitch && maxSteps > 0) { HIP_TRY(hipEventRecord(b->pitchDone, st)); b->pitchUsed = true; }
+    return elements;
 }
 
 }  // extern "C"

@@ -379,6 +379,41 @@ def check_pcm_out(out, n, numSamples, device):
     return 1 if out.dtype == torch.float32 else 0
 
 
+TRACK_MARK, TRACK_FRAME = 47, 48      # SPEECHPLAYER_TRACK_MARK / _FRAME: the columns of trackTensor beyond the frame's 47 parameters
+TRACK_COLUMNS = FRAME_FIELDS + ["mark", "frame"]
+
+
+def check_track_request(columns, hop, phase, dtype):
+    """The argument checks of BatchPlayer.trackTensor that need no GPU, before any library call: `columns` a non-empty sequence of
+    column numbers 0 .. 48 or names (FRAME_FIELDS, "mark", "frame"; a single number or name stands for one column), hop >= 1,
+    phase >= 0, dtype None / torch.float32 / torch.float64.  Raises KeyError (unknown name), ValueError (number, hop, phase, no columns)
+    or TypeError (dtype).  Returns (columns as an int32 array, hop, phase, the export format: 0 float64, 1 float32)."""
+    import torch
+    if isinstance(columns, (str, int, np.integer)):
+        columns = [columns]
+    cols = []
+    for c in columns:
+        if isinstance(c, str):
+            if c not in TRACK_COLUMNS:
+                raise KeyError("trackTensor: no column named %r (FRAME_FIELDS, 'mark', 'frame')" % c)
+            c = TRACK_COLUMNS.index(c)
+        c = int(c)
+        if not 0 <= c < len(TRACK_COLUMNS):
+            raise ValueError("trackTensor: column %d is not in 0 .. %d" % (c, len(TRACK_COLUMNS) - 1))
+        cols.append(c)
+    if not cols:
+        raise ValueError("trackTensor: no columns")
+    hop, phase = int(hop), int(phase)
+    if hop < 1:
+        raise ValueError("trackTensor: hop must be at least 1, not %d" % hop)
+    if phase < 0:
+        raise ValueError("trackTensor: phase must not be negative (%d)" % phase)
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError("trackTensor: dtype must be torch.float32 or torch.float64, not %s" % dtype)
+    return np.asarray(cols, dtype=np.int32), hop, phase, 1 if dtype == torch.float32 else 0
+
+
 def _ready_stream(owner, dev):
     """The hipStream_t a device-frames call is ordered behind: torch's current stream on `dev`.  torch's default stream is the NULL stream,
     which the engine reads as "ready now": a stream of `owner`'s own that waits for it on the device carries the order instead."""
@@ -505,6 +540,55 @@ class BatchPlayer(object):
                                                                      1 if dtype == torch.float32 else 0, stride, stream))
             assert got == out.numel(), (got, out.numel())
         return out, torch.from_numpy(lens if padded else offsets)
+
+    def timeline(self, u):
+        """When utterance u's requests are dequeued (speechPlayer_batch_timeline): -> (firstSample int64 [n + 1], userIndex int32 [n]);
+        request k takes effect on sample firstSample[k], firstSample[n] is the utterance's length."""
+        n = self._check(self._dll.speechPlayer_batch_timeline(self._h, u, None, None, 0))
+        first = np.zeros(n + 1, np.int64); ix = np.zeros(n, np.int32)
+        self._check(self._dll.speechPlayer_batch_timeline(self._h, u, first.ctypes.data, ix.ctypes.data, n))
+        return first, ix
+
+    def marks(self, u):
+        """The index marks of utterance u: -> (sample int64 [m], index int32 [m]) of the requests that carry one; getLastIndex answers
+        index[i] once sample[i] + 1 samples have been produced."""
+        first, ix = self.timeline(u)
+        keep = ix != -1
+        return first[:-1][keep], ix[keep]
+
+    def trackTensor(self, columns, hop=1, phase=0, utterances=None, dtype=None, padded=True):
+        """Per-sample parameter tracks and timelines as a torch tensor on the batch's device (speechPlayer_batch_exportTracks), filled on
+        torch's current stream without a host wait and without a synthesis launch: -> (tracks, steps).  Step j of an utterance is its
+        sample phase + j * hop; element [.., j, q] is column columns[q] of the frame the synthesiser used on that sample (columns by
+        number or by name: FRAME_FIELDS, "mark" = getLastIndex after that sample, "frame" = the request in effect).  utterances:
+        indices in any order, repeats allowed (None: all, in order); dtype torch.float32 (default) or torch.float64 (the values
+        themselves).  padded: tracks is [n, most steps, len(columns)], zero past each utterance's end, and steps the n step counts;
+        else tracks is [total steps, len(columns)] and steps the n + 1 offsets (int64 CPU tensors)."""
+        import torch
+        cols, hop, phase, fmt = check_track_request(columns, hop, phase, dtype)
+        sel = None if utterances is None else _host_array(utterances, np.int64).reshape(-1)
+        n = self.nUtterances if sel is None else len(sel)
+        idx = np.arange(n) if sel is None else sel
+        if n and (idx.min() < 0 or idx.max() >= self.nUtterances):
+            raise ValueError("trackTensor: utterance numbers must lie in [0, %d)" % self.nUtterances)
+        lens = self._lengths()[idx]
+        steps = np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
+        dev = self.device
+        tdtype = torch.float32 if fmt else torch.float64
+        if padded:
+            width = int(steps.max()) if n else 0
+            out = torch.empty((n, width, len(cols)), dtype=tdtype, device="cuda:%d" % dev)
+            stride = width
+        else:
+            offsets = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
+            out = torch.empty((int(offsets[-1]), len(cols)), dtype=tdtype, device="cuda:%d" % dev)
+            stride = 0
+        if out.numel():
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            got = self._check(self._dll.speechPlayer_batch_exportTracks(self._h, None if sel is None else sel.ctypes.data, n, cols.ctypes.data, len(cols),
+                                                                        hop, phase, out.data_ptr(), fmt, stride, stream))
+            assert got == out.numel(), (got, out.numel())
+        return out, torch.from_numpy(steps if padded else offsets)
 
     def setUtterancesShared(self, listStart, frames, minSamples, fadeSamples, listOf, userIndex=None, isNull=None, noiseSeed=None):
         """Frame lists that utterances share (speechPlayer_batch_setUtterancesShared): `listStart`/frames/... describe the lists as
