@@ -458,6 +458,82 @@ speechPlayer_records_t speechPlayer_ipa_records(int sampleRate, long long nTexts
 int speechPlayer_records_view(speechPlayer_records_t records, speechPlayer_recordsView_t* view);
 void speechPlayer_records_free(speechPlayer_records_t records);
 /*
+ * Phoneme alignment: which phoneme is sounding when.  Beside every record the producer keeps a 16-byte LABEL -- what its lexer knew
+ * about the frame -- and a batch set from IPA text carries the labels of its lists to the device, where two exports turn them into
+ * framewise labels and a segment table on the caller's stream (klatt_align.h).
+ *   phoneme     row of speechPlayer_ipa_phoneme; an inserted pre-stop gap: speechPlayer_ipa_phonemeCount() (SPEECHPLAYER_LABEL "gap" id),
+ *               a silence frame (the trailing silence, speechPlayer_batch_setText's pause): count + 1.  Never negative.  A post-stop
+ *               aspiration carries the row it is a copy of (/h/) and SPEECHPLAYER_LABEL_PUFF.
+ *   flags       SPEECHPLAYER_LABEL_* below: the stress in bits 0-1, then the producer's prosodic bits
+ *   unit        index within the utterance of the text symbol the frame belongs to: a gap belongs to the stop after it, an aspiration
+ *               to the stop before it, silence is a unit of its own; non-decreasing along a list
+ *   textOffset  byte offset in the caller's UTF-8 string at which the symbol begins (after a tie bar that joins two symbols into one
+ *               table row: the first of them); -1 for inserted frames and silence.  speechPlayer_batch_setText: always -1 (the IPA
+ *               of a clause is eSpeak's, not the caller's string; units count on through the clauses of a text).
+ */
+typedef struct {
+	int phoneme;
+	unsigned int flags;
+	int unit;
+	int textOffset;
+} speechPlayer_frameLabel_t;
+enum {
+	SPEECHPLAYER_LABEL_STRESS_MASK    = 3,     /* 0 none, 1 primary, 2 secondary (set on the syllable's head) */
+	SPEECHPLAYER_LABEL_TIED_TO        = 4,     /* a tie bar follows the symbol */
+	SPEECHPLAYER_LABEL_TIED_FROM      = 8,     /* a tie bar precedes it */
+	SPEECHPLAYER_LABEL_LONG           = 16,    /* a length mark follows it */
+	SPEECHPLAYER_LABEL_WORD_START     = 32,
+	SPEECHPLAYER_LABEL_SYLLABLE_START = 64,
+	SPEECHPLAYER_LABEL_GAP            = 128,   /* the frame is an inserted pre-stop gap; in a unit table: the unit has one */
+	SPEECHPLAYER_LABEL_PUFF           = 256    /* ... an inserted post-stop aspiration */
+};
+/* One utterance's labels, host only (no GPU): the arguments of speechPlayer_ipa_frames that decide the frame list, and the same n
+ * frames.  Any array may be NULL; filled when n <= capacity.  Returns n; -1 on an allocation failure. */
+long long speechPlayer_ipa_labels(const char* ipaUtf8, int* phoneme, unsigned int* flags, int* unit, int* textOffset, long long capacity);
+/* The labels of a records object: *labels is parallel to its view's `records` array (owned by the object).  0, or -1. */
+int speechPlayer_records_labels(speechPlayer_records_t records, const speechPlayer_frameLabel_t** labels, long long* nLabels);
+/* speechPlayer_batch_setRecords with labels[listStart[nLists]] attached (NULL: none -- the call is then speechPlayer_batch_setRecords).
+ * speechPlayer_batch_setIpa, _setIpaVoices and _setText attach theirs; a batch set any other way has none, and any set call without
+ * labels drops them.  Refused (the previous batch stays): a list whose units do not count from 0 and rise by at most one from frame to
+ * frame, a negative phoneme id. */
+int speechPlayer_batch_setRecordsLabelled(speechPlayer_batch_t batch, long long nShapes, const speechPlayer_frame_t* shapes,
+	long long nLists, const long long* listStart, const speechPlayer_frameRecord_t* records, const speechPlayer_frameLabel_t* labels,
+	long long nUtterances, const unsigned int* listOf, const unsigned int* noiseSeed);
+int speechPlayer_batch_hasLabels(speechPlayer_batch_t batch);     /* 1, 0; -1: no batch */
+/*
+ * speechPlayer_batch_exportAlignment: framewise labels of chosen utterances (any order, repeats; NULL: all) at the steps
+ * phase + j * hop, as [row][step][column] of int64 (format 0) or int32 (format 1) in the caller's device memory, on the caller's
+ * stream, with the contract of speechPlayer_batch_exportTracks (no synthesis launch, ordered by events, the next set call waits on the
+ * device).  rowStride > 0: every row has rowStride steps, `pad` past the utterance's end; 0: the rows back to back.  `capacity`: elements
+ * deviceOut holds.  Columns:
+ */
+#define SPEECHPLAYER_ALIGN_PHONEME     0   /* the label's phoneme id */
+#define SPEECHPLAYER_ALIGN_STRESS      1   /* flags & 3 */
+#define SPEECHPLAYER_ALIGN_FLAGS       2
+#define SPEECHPLAYER_ALIGN_UNIT        3
+#define SPEECHPLAYER_ALIGN_TEXT_OFFSET 4
+#define SPEECHPLAYER_ALIGN_FRAME       5   /* the request in effect: SPEECHPLAYER_TRACK_FRAME */
+#define SPEECHPLAYER_ALIGN_POSITION    6   /* samples since the unit began */
+#define SPEECHPLAYER_ALIGN_REMAINING   7   /* samples until the next unit begins (the utterance's end for the last) */
+#define SPEECHPLAYER_ALIGN_COLUMNS     8
+/* The request in effect on sample t is the last one dequeued on or before t (the utterance's last sample belongs to its last request).
+ * Returns the number of elements written, -1 and nothing written when refused (SPEECHPLAYER_ERR_ARGUMENT): no batch, no labels on this
+ * batch, a column outside 0 .. 7, nColumns <= 0, hop < 1, phase < 0, an utterance outside the batch, rowStride below the largest step
+ * count, capacity below the elements needed, deviceOut not device memory of the batch's device. */
+long long speechPlayer_batch_exportAlignment(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
+	const int* columns, int nColumns, long long hop, long long phase, void* deviceOut, int format, long long rowStride, long long pad,
+	long long capacity, void* stream);
+/* speechPlayer_batch_exportUnits: the segment table, [row][unit][7] of int64 -- phoneme (that of the unit's frame that is neither gap
+ * nor aspiration), flags (ORed over the unit's frames), textOffset, firstSample, samples, firstStep, steps: the steps phase + j * hop
+ * that fall inside the unit (a row's `steps` sum to its step count).  byFrame != 0: one entry per frame instead of per unit (gaps and
+ * aspirations are entries of their own).  rowStride > 0: rowStride entries per row, `pad` in every column past the row's count; 0: back
+ * to back.  Same contract and refusals as above. */
+#define SPEECHPLAYER_UNIT_COLUMNS 7
+long long speechPlayer_batch_exportUnits(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, long long hop,
+	long long phase, int byFrame, void* deviceOut, long long rowStride, long long pad, long long capacity, void* stream);
+/* Units (byFrame: frames) per chosen utterance, to size the output (host only).  Returns the number of utterances; -1 when refused. */
+long long speechPlayer_batch_unitCounts(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int byFrame, long long* counts);
+/*
  * Optional text front-end: what the NVDA driver does before the frame producer (reference
  * nvdaAddon/synthDrivers/nvSpeechPlayer/__init__.py:189-234), with eSpeak NG loaded at run time (dlopen of libespeak-ng.so.1, or of
  * $SPEECHPLAYER_ESPEAK_LIB) -- the library links against nothing of it.  PARITY UNPINNED: eSpeak NG is absent from the reference tree

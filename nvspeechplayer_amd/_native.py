@@ -24,7 +24,8 @@ OBJ_DIR = os.path.join(PKG_DIR, "build_tmp")
 # kernels within 1 % (tools/ab_probe.py, profiles/r2_ab_noisy_variants.txt; max-ilp: +1.5 %, machine LICM off: +5 %).
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
                "-mllvm", "-amdgpu-sched-strategy=max-memory-clause"]
-CXX_FLAGS = ["-O2", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall", "-Wextra"]
+# SPEECHPLAYER_LABELLED_SET: the producer hands text batches to speechPlayer_batch_setRecordsLabelled (frame_producer.cpp, set_records_labelled)
+CXX_FLAGS = ["-O2", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall", "-Wextra", "-DSPEECHPLAYER_LABELLED_SET"]
 LINK_FLAGS = ["-shared", "-fPIC", "--offload-arch=gfx950", "-Wl,-rpath,/opt/rocm/lib"]
 
 EXPORTS = [
@@ -54,6 +55,8 @@ EXPORTS = [
     "speechPlayer_batch_setUtterancesDevice", "speechPlayer_batch_exportPcm", "speechPlayer_batch_device", "speechPlayer_batch_lengths",
     "speechPlayer_queueFramesMany", "speechPlayer_queueFramesManyDevice", "speechPlayer_synthesizeManyExport", "speechPlayer_handleDevice",
     "speechPlayer_planTimeline", "speechPlayer_batch_timeline", "speechPlayer_batch_exportTracks",
+    "speechPlayer_ipa_labels", "speechPlayer_records_labels", "speechPlayer_batch_setRecordsLabelled", "speechPlayer_batch_hasLabels",
+    "speechPlayer_batch_exportAlignment", "speechPlayer_batch_exportUnits", "speechPlayer_batch_unitCounts",
 ]
 
 
@@ -338,6 +341,20 @@ def load():
     L.speechPlayer_voiceIndex.argtypes = [ctypes.c_char_p]
     L.speechPlayer_voiceDefine.restype = i32
     L.speechPlayer_voiceDefine.argtypes = [ctypes.c_char_p, i32, vp, vp, vp]
+    L.speechPlayer_ipa_labels.restype = i64
+    L.speechPlayer_ipa_labels.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, i64]
+    L.speechPlayer_records_labels.restype = i32
+    L.speechPlayer_records_labels.argtypes = [vp, vp, vp]
+    L.speechPlayer_batch_setRecordsLabelled.restype = i32
+    L.speechPlayer_batch_setRecordsLabelled.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, vp, vp]
+    L.speechPlayer_batch_hasLabels.restype = i32
+    L.speechPlayer_batch_hasLabels.argtypes = [vp]
+    L.speechPlayer_batch_exportAlignment.restype = i64
+    L.speechPlayer_batch_exportAlignment.argtypes = [vp, vp, i64, vp, i32, i64, i64, vp, i32, i64, i64, i64, vp]
+    L.speechPlayer_batch_exportUnits.restype = i64
+    L.speechPlayer_batch_exportUnits.argtypes = [vp, vp, i64, i64, i64, i32, vp, i64, i64, i64, vp]
+    L.speechPlayer_batch_unitCounts.restype = i64
+    L.speechPlayer_batch_unitCounts.argtypes = [vp, vp, i64, i32, vp]
     _lib = L
     return L
 

@@ -105,6 +105,7 @@ struct Segment {
     uint8_t cls;
     uint8_t stress;      // 0, 1 primary, 2 secondary; meaningful on syllable heads
     uint16_t pros;       // S_* bits
+    int textOffset;      // byte offset of the symbol in the text; -1 for an inserted segment
     double duration, fade;
 };
 struct Utterance { std::vector<Segment> seg; };
@@ -152,12 +153,15 @@ private:
     std::unordered_map<uint64_t, int> byKey_;
 };
 
-void decode_utf8(const char* text, std::vector<uint32_t>& out)
+// `offsets` (parallel to `out`): the byte at which every code point begins
+void decode_utf8(const char* text, std::vector<uint32_t>& out, std::vector<int>& offsets)
 {
-    out.clear();
-    const unsigned char* p = reinterpret_cast<const unsigned char*>(text ? text : "");
+    out.clear(); offsets.clear();
+    const unsigned char* const p0 = reinterpret_cast<const unsigned char*>(text ? text : "");
+    const unsigned char* p = p0;
     while (*p) {
         uint32_t c = *p;
+        offsets.push_back((int)(p - p0));
         int extra = c < 0x80 ? 0 : (c >> 5) == 6 ? 1 : (c >> 4) == 14 ? 2 : (c >> 3) == 30 ? 3 : -1;
         if (extra < 0) { out.push_back(0xFFFD); ++p; continue; }       // stray byte: an unknown symbol
         if (extra) c &= 0x3F >> extra;
@@ -171,7 +175,7 @@ void decode_utf8(const char* text, std::vector<uint32_t>& out)
 Segment make_segment(int row)
 {
     Segment s;
-    s.row = row; s.comp = row; s.cls = row < 0 ? 0 : kPhonemeRows[row].cls; s.stress = 0; s.pros = 0;
+    s.row = row; s.comp = row; s.cls = row < 0 ? 0 : kPhonemeRows[row].cls; s.stress = 0; s.pros = 0; s.textOffset = -1;
     s.duration = s.fade = 0.0;
     return s;
 }
@@ -180,7 +184,7 @@ Segment make_segment(int row)
 // one row when the table has the pair, else it marks its neighbours as tied; a length mark prefers the lengthened row.
 // Between a voiceless stop and a voiced continuant goes a short aspiration (/h/); before a stop or affricate that
 // does not carry the stress mark itself goes a gap.
-void lex(const std::vector<uint32_t>& cp, Utterance& u)
+void lex(const std::vector<uint32_t>& cp, const std::vector<int>& offsets, Utterance& u)
 {
     u.seg.clear();
     const SymbolIndex& sym = symbols();
@@ -203,10 +207,12 @@ void lex(const std::vector<uint32_t>& cp, Utterance& u)
             step = 2;
         }
         if (row < 0) row = sym.find(&c, 1);
+        const int symbolAt = offsets[pos];
         pos += step;
         if (c == ' ') { wordBoundary = true; continue; }
         if (row < 0) continue;                                          // a symbol the table does not know
         Segment s = make_segment(row);
+        s.textOffset = symbolAt;
         if (tieBefore) s.pros |= S_TIED_FROM; else if (tieAfter) s.pros |= S_TIED_TO;
         if (longMark) s.pros |= S_LONG;
         const int stress = waitingStress;
@@ -256,6 +262,27 @@ void colour(Utterance& u, Composites& comps)
         if (from < 0 || u.seg[from].row < 0) continue;                  // (a gap has no fields to give)
         s.comp = comps.combine(s.comp, u.seg[from].comp);
     }
+}
+
+// What the lexer knew about every segment, as labels (include/speechPlayer_batch.h, speechPlayer_frameLabel_t): out[seg.size()], and one
+// more for the silence behind the utterance when `tail`.  The S_* bits sit above the two stress bits.
+static_assert((S_TIED_TO << 2) == SPEECHPLAYER_LABEL_TIED_TO && (S_TIED_FROM << 2) == SPEECHPLAYER_LABEL_TIED_FROM && (S_LONG << 2) == SPEECHPLAYER_LABEL_LONG &&
+              (S_WORD_START << 2) == SPEECHPLAYER_LABEL_WORD_START && (S_SYLLABLE_START << 2) == SPEECHPLAYER_LABEL_SYLLABLE_START &&
+              (S_GAP << 2) == SPEECHPLAYER_LABEL_GAP && (S_PUFF << 2) == SPEECHPLAYER_LABEL_PUFF, "label flags");
+void label_segments(const Utterance& u, bool tail, speechPlayer_frameLabel_t* out)
+{
+    int symbols = 0;                       // text symbols seen so far: the unit of the next one
+    const size_t n = u.seg.size();
+    for (size_t k = 0; k < n; ++k) {
+        const Segment& s = u.seg[k];
+        speechPlayer_frameLabel_t& l = out[k];
+        l.flags = (uint32_t)(s.stress & 3) | (uint32_t)s.pros << 2;
+        l.textOffset = s.textOffset;
+        if (s.pros & S_GAP) { l.phoneme = kNumPhonemes; l.unit = symbols; }                   // belongs to the stop after it
+        else if (s.pros & S_PUFF) { l.phoneme = s.row; l.unit = symbols > 0 ? symbols - 1 : 0; }   // ... to the stop before it
+        else { l.phoneme = s.row; l.unit = symbols++; }
+    }
+    if (tail) out[n] = speechPlayer_frameLabel_t{kNumPhonemes + 1, 0u, symbols, -1};
 }
 
 // Duration and fade in milliseconds, by class.  The tempo of a syllable depends on its head's stress.
@@ -459,6 +486,23 @@ void speechPlayer_internal_parallel(long long n, long long grain, void (*fn)(voi
 }
 
 namespace {
+// A batch with its labels to the engine.  SPEECHPLAYER_LABELLED_SET is defined by every build that links the engine's
+// speechPlayer_batch_setRecordsLabelled (the library: _native.py; tests/native/fuzz_labels.cpp stubs it); a build of the producer
+// alone without it (tests/native/fuzz_producer.cpp stubs the engine's older entry points only) hands the records over without labels.
+int set_records_labelled(speechPlayer_batch_t batch, long long nShapes, const speechPlayer_frame_t* shapes, long long nLists, const long long* listStart,
+                         const speechPlayer_frameRecord_t* records, const speechPlayer_frameLabel_t* labels, long long nUtterances,
+                         const unsigned int* listOf, const unsigned int* noiseSeed)
+{
+#ifdef SPEECHPLAYER_LABELLED_SET
+    return speechPlayer_batch_setRecordsLabelled(batch, nShapes, shapes, nLists, listStart, records, labels, nUtterances, listOf, noiseSeed);
+#else
+    (void)labels;
+    return speechPlayer_batch_setRecords(batch, nShapes, shapes, nLists, listStart, records, nUtterances, listOf, noiseSeed);
+#endif
+}
+}
+
+namespace {
 
 template <class F>
 void parallel_for(long long n, long long grain, F body)
@@ -491,6 +535,7 @@ struct Compact {
     std::vector<speechPlayer_frame_t> shapes;
     std::vector<long long> listStart;
     std::vector<speechPlayer_frameRecord_t> records;
+    std::vector<speechPlayer_frameLabel_t> labels;   // per record: what the lexer knew about the frame
     std::vector<uint32_t> listOf;
     std::vector<double> durationMs, fadeMs;          // per record (keepMs)
     long long frames_of(long long u) const { const uint32_t l = listOf[(size_t)u]; return listStart[l + 1] - listStart[l]; }
@@ -564,10 +609,11 @@ int build_compact(const PackArgs& a, bool sizeOnly, bool keepMs, Compact& out)
     std::vector<Timed> timed(textPtr.size());
     parallel_for((long long)textPtr.size(), 64, [&](long long ta, long long te) {
         std::vector<uint32_t> cp;
+        std::vector<int> cpAt;
         for (long long t = ta; t < te; ++t) {
             Timed& x = timed[(size_t)t];
-            decode_utf8(textPtr[(size_t)t], cp);
-            lex(cp, x.u);
+            decode_utf8(textPtr[(size_t)t], cp, cpAt);
+            lex(cp, cpAt, x.u);
             colour(x.u, comps);
             time_segments(x.u, a.speed);
             const size_t ns = x.u.seg.size();
@@ -603,6 +649,7 @@ int build_compact(const PackArgs& a, bool sizeOnly, bool keepMs, Compact& out)
     // ---- the records, list by list ----
     const size_t nRec = (size_t)out.listStart[nLists];
     out.records.resize(nRec);
+    out.labels.resize(nRec);
     if (keepMs) { out.durationMs.assign(nRec, 0.0); out.fadeMs.assign(nRec, 0.0); }
     const unsigned int tailSamples = tail ? ms_to_samples(a.tailMs, a.sampleRate) : 0u;
     parallel_for((long long)nLists, 16, [&](long long la, long long le) {
@@ -620,6 +667,7 @@ int build_compact(const PackArgs& a, bool sizeOnly, bool keepMs, Compact& out)
                 apply_spans(x.u, spans, basePitch, a.inflection, pt);
             }
             speechPlayer_frameRecord_t* r = out.records.data() + out.listStart[(size_t)l];
+            label_segments(x.u, tail, out.labels.data() + out.listStart[(size_t)l]);
             for (size_t k = 0; k < ns; ++k) {
                 const Segment& s = x.u.seg[k];
                 r[k].minFrameDuration = x.minSamples[k]; r[k].fadeDuration = x.fadeSamples[k]; r[k].userIndex = -1;
@@ -780,6 +828,28 @@ long long speechPlayer_ipa_frames(const char* ipaUtf8, double speed, double base
     });
 }
 
+long long speechPlayer_ipa_labels(const char* ipaUtf8, int* phoneme, unsigned int* flags, int* unit, int* textOffset, long long capacity)
+{
+    return producer_call<long long>("speechPlayer_ipa_labels", -1, [&]() -> long long {
+        std::vector<uint32_t> cp;
+        std::vector<int> cpAt;
+        Utterance u;
+        decode_utf8(ipaUtf8, cp, cpAt);
+        lex(cp, cpAt, u);
+        const long long n = (long long)u.seg.size();
+        if (n > capacity) return n;
+        std::vector<speechPlayer_frameLabel_t> l((size_t)n);
+        label_segments(u, false, l.data());
+        for (long long k = 0; k < n; ++k) {
+            if (phoneme) phoneme[k] = l[(size_t)k].phoneme;
+            if (flags) flags[k] = l[(size_t)k].flags;
+            if (unit) unit[k] = l[(size_t)k].unit;
+            if (textOffset) textOffset[k] = l[(size_t)k].textOffset;
+        }
+        return n;
+    });
+}
+
 static int check_pack_args(long long nTexts, const char* const* ipaUtf8, const char* clauseTypes, const int* voiceOf, const char* voiceName, int* voiceAll)
 {
     if (nTexts < 0 || (nTexts > 0 && !ipaUtf8)) return -1;
@@ -854,6 +924,15 @@ int speechPlayer_records_view(speechPlayer_records_t records, speechPlayer_recor
     return 0;
 }
 
+int speechPlayer_records_labels(speechPlayer_records_t records, const speechPlayer_frameLabel_t** labels, long long* nLabels)
+{
+    if (!records || !labels) return -1;
+    const Compact& c = static_cast<speechPlayer_recordsObject*>(records)->c;
+    *labels = c.labels.data();
+    if (nLabels) *nLabels = (long long)c.labels.size();
+    return 0;
+}
+
 void speechPlayer_records_free(speechPlayer_records_t records) { delete static_cast<speechPlayer_recordsObject*>(records); }
 
 static int set_ipa(const char* what, speechPlayer_batch_t batch, long long nTexts, const char* const* ipaUtf8, double speed,
@@ -871,8 +950,8 @@ static int set_ipa(const char* what, speechPlayer_batch_t batch, long long nText
         a.clauseTypes = clauseTypes; a.voiceOf = voiceOf; a.tailMs = trailingSilenceMs;
         Compact c;
         if (build_compact(a, false, false, c)) { set_producer_error((std::string(what) + ": voice index out of range").c_str()); return -1; }
-        return speechPlayer_batch_setRecords(batch, (long long)c.shapes.size(), c.shapes.data(), (long long)c.listStart.size() - 1, c.listStart.data(),
-                                             c.records.data(), nTexts, c.listOf.data(), noiseSeed);
+        return set_records_labelled(batch, (long long)c.shapes.size(), c.shapes.data(), (long long)c.listStart.size() - 1, c.listStart.data(),
+                                                     c.records.data(), c.labels.data(), nTexts, c.listOf.data(), noiseSeed);
     });
 }
 
@@ -1193,12 +1272,23 @@ int speechPlayer_batch_setText(speechPlayer_batch_t batch, long long nTexts, con
         // queueFrame(None, endPause / rate, max(10, 10 / rate))
         std::vector<long long> start((size_t)nTexts + 1, 0);
         std::vector<speechPlayer_frameRecord_t> recs;
+        std::vector<speechPlayer_frameLabel_t> labels;     // the clauses' labels: units count on through the text, no text offsets (the IPA is eSpeak's)
         for (long long i = 0; i < nTexts; ++i) {
             start[(size_t)i] = (long long)recs.size();
+            int unit0 = 0;
             for (size_t k = firstItem[(size_t)i]; k < firstItem[(size_t)i + 1]; ++k) {
                 const uint32_t l = c.listOf[k];
                 recs.insert(recs.end(), c.records.begin() + c.listStart[l], c.records.begin() + c.listStart[l + 1]);
+                int last = unit0 - 1;
+                for (long long f = c.listStart[l]; f < c.listStart[l + 1]; ++f) {
+                    speechPlayer_frameLabel_t lb = c.labels[(size_t)f];
+                    lb.unit += unit0; lb.textOffset = -1;
+                    last = std::max(last, lb.unit);
+                    labels.push_back(lb);
+                }
+                unit0 = last + 1;
             }
+            labels.push_back(speechPlayer_frameLabel_t{kNumPhonemes + 1, 0u, unit0, -1});
             speechPlayer_frameRecord_t t;
             t.shape = SPEECHPLAYER_RECORD_SILENCE; t.voicePitch = 0.0; t.endVoicePitch = 0.0; t.userIndex = -1;
             t.minFrameDuration = ms_to_samples(endPauseOf[(size_t)i], rate);
@@ -1206,7 +1296,8 @@ int speechPlayer_batch_setText(speechPlayer_batch_t batch, long long nTexts, con
             recs.push_back(t);
         }
         start[(size_t)nTexts] = (long long)recs.size();
-        return speechPlayer_batch_setRecords(batch, (long long)c.shapes.size(), c.shapes.data(), nTexts, start.data(), recs.data(), nTexts, nullptr, noiseSeed);
+        return set_records_labelled(batch, (long long)c.shapes.size(), c.shapes.data(), nTexts, start.data(), recs.data(), labels.data(),
+                                                     nTexts, nullptr, noiseSeed);
     });
 }
 

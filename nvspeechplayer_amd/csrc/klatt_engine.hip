@@ -16,6 +16,7 @@
 #include "klatt_direct.h"
 #include "klatt_plan.h"
 #include "klatt_timeline.h"
+#include "klatt_align.h"
 
 #include <algorithm>
 #include <cmath>
@@ -642,6 +643,13 @@ struct Batch {
     long long pitchBudgetMB = 256;             // option "pitch_table_mb": an export whose voicePitch table would be larger proceeds in pieces
     ExportSlot trackSlot[kExportSlots];
     unsigned trackNext = 0;
+    // speechPlayer_batch_exportAlignment / _exportUnits (klatt_align.h): the labels of a batch set with labels (one per list frame) and
+    // unitFirst[] (list l's entries from listStart[l] + l), uploaded on the copy stream by the set call -- ahead of setCopied; their
+    // exports share the track exports' slots and order.
+    DeviceBuffer<FrameLabel> dLabels;
+    DeviceBuffer<uint32_t> dUnitFirst;
+    std::vector<uint32_t> listUnits;           // [nLists] units of a list
+    bool hasLabels = false;
 };
 
 // The batch's own streams wait (on the device) for the exports that still read its pool.
@@ -2477,7 +2485,7 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch)
         s.host.release(); s.dev.release();
     }
     for (hipEvent_t e : {b->setDone, b->setCopied, b->timelineReady, b->pitchDone}) if (e) (void)hipEventDestroy(e);
-    b->dListStart.release(); b->dTimeline.release(); b->dPitch.release();
+    b->dListStart.release(); b->dTimeline.release(); b->dPitch.release(); b->dLabels.release(); b->dUnitFirst.release();
     if (b->inputReady) (void)hipEventDestroy(b->inputReady);
     if (b->pcmReady) (void)hipEventDestroy(b->pcmReady);
     b->dShapeIdx.release(); b->dShapeRows.release();
@@ -2544,9 +2552,13 @@ struct SetInput {
     const unsigned int* seeds = nullptr;
     const double* deviceFrames = nullptr;   // speechPlayer_batch_setUtterancesDevice: the frames in device memory of the batch's device
     hipStream_t readyStream = nullptr;      // ... ready there once this stream's work queued so far is done (nullptr: ready now)
+    const speechPlayer_frameLabel_t* labels = nullptr;      // speechPlayer_batch_setRecordsLabelled: one per list frame
     bool noTracks = false;       // the second attempt of a batch whose shared shapes failed their verification
 };
 static_assert(sizeof(speechPlayer_frameRecord_t) == sizeof(FrameRecord), "record layout");
+static_assert(sizeof(speechPlayer_frameLabel_t) == sizeof(FrameLabel), "label layout");
+static_assert(SPEECHPLAYER_LABEL_GAP == kLabelGap && SPEECHPLAYER_LABEL_PUFF == kLabelPuff && SPEECHPLAYER_ALIGN_COLUMNS == kAlignColumns &&
+              SPEECHPLAYER_UNIT_COLUMNS == kUnitColumns, "alignment constants");
 
 static void batch_clear(Batch* b)
 {
@@ -2554,6 +2566,7 @@ static void batch_clear(Batch* b)
     b->nTracked = 0; b->nTrackedUtt = 0; b->nJobs = 0; b->trackEntries = 0; b->nDirect = 0; b->nDirectUtt = 0; b->nDirectFrames = 0;
     b->lens.clear(); b->outStart.assign(1, 0); b->results.clear(); b->resultsFresh = false; b->floatFresh = false;
     b->uttFrameStart.clear(); b->uttFrames.clear(); b->uttList.clear(); b->timelineFresh = false;
+    b->hasLabels = false; b->listUnits.clear();
 }
 
 static int batch_set(Batch* b, const SetInput& in);
@@ -2652,6 +2665,24 @@ int speechPlayer_batch_setRecords(speechPlayer_batch_t batch, long long nShapes,
     return batch_set_guarded("setRecords", batch, in);
 }
 
+int speechPlayer_batch_setRecordsLabelled(speechPlayer_batch_t batch, long long nShapes, const speechPlayer_frame_t* shapes,
+                                          long long nLists, const long long* listStart, const speechPlayer_frameRecord_t* records,
+                                          const speechPlayer_frameLabel_t* labels, long long nUtterances, const unsigned int* listOf,
+                                          const unsigned int* noiseSeed)
+{
+    if (!labels) return speechPlayer_batch_setRecords(batch, nShapes, shapes, nLists, listStart, records, nUtterances, listOf, noiseSeed);
+    SetInput in;
+    in.nLists = nLists; in.listStart = listStart; in.records = records; in.nShapes = nShapes; in.shapes = shapes;
+    in.nUtt = nUtterances; in.listOf = listOf; in.seeds = noiseSeed; in.labels = labels;
+    if (nShapes < 0 || (nShapes > 0 && !shapes)) { begin_call(); set_error("setRecordsLabelled: bad shape table"); return -1; }
+    if (!records && nLists > 0 && listStart && listStart[nLists] > 0) { begin_call(); set_error("setRecordsLabelled: no records"); return -1; }
+    static const speechPlayer_frameRecord_t none = {0.0, 0.0, SPEECHPLAYER_RECORD_SILENCE, 0u, 0u, -1};
+    if (!in.records) in.records = &none;
+    return batch_set_guarded("setRecordsLabelled", batch, in);
+}
+
+int speechPlayer_batch_hasLabels(speechPlayer_batch_t batch) { return batch ? (static_cast<Batch*>(batch)->hasLabels ? 1 : 0) : -1; }
+
 // Frames in device memory (speechPlayer_batch_setUtterancesDevice) and the track planner, which reads the values of a frame whose
 // (masked) shape hash it has not seen yet (FrameSource::values): one frame per distinct hash among the frames it may read -- the
 // non-silent frames of the lists that may be tracked --, the first in frame order, stands for all frames of that hash; rowOf[k] names
@@ -2748,6 +2779,31 @@ static int batch_set(Batch* b, const SetInput& in)
         });
         if (bad.load() >= 0) { set_error("setRecords: record %lld names shape %u of %lld", bad.load(), in.records[bad.load()].shape, in.nShapes); return -1; }
     }
+    // labels: the units of a list count from 0 and rise by at most one from frame to frame; unitFirst[] (klatt_align.h) from them
+    std::vector<uint32_t> unitFirst, listUnits;
+    if (in.labels) {
+        if (nF >= 0xFFFFFFFFll) { set_error("setRecordsLabelled: too many frames"); return -1; }
+        unitFirst.resize((size_t)(nF + nL)); listUnits.assign((size_t)nL, 0);
+        std::atomic<long long> bad{-1};
+        parallel_ranges(nL, 256, [&](long long la, long long le) {
+            for (long long l = la; l < le; ++l) {
+                uint32_t* uf = unitFirst.data() + listStart[l] + l;
+                int units = 0;
+                for (long long k = listStart[l]; k < listStart[l + 1]; ++k) {
+                    const int u = in.labels[k].unit;
+                    if (in.labels[k].phoneme < 0 || (u != units && !(units > 0 && u == units - 1))) { long long none = -1; bad.compare_exchange_strong(none, k); break; }
+                    if (u == units) uf[units++] = (uint32_t)(k - listStart[l]);
+                }
+                uf[units] = (uint32_t)(listStart[l + 1] - listStart[l]);
+                listUnits[(size_t)l] = (uint32_t)units;
+            }
+        });
+        if (bad.load() >= 0) {
+            set_error("setRecordsLabelled: label %lld (phoneme %d, unit %d): the units of a list count from 0 and rise by at most one, ids are not negative",
+                      bad.load(), in.labels[bad.load()].phoneme, in.labels[bad.load()].unit);
+            return -1;
+        }
+    }
     auto list_of = [&](long long u) -> long long { return listOf ? (long long)listOf[u] : u; };
     // everything below is built in locals and committed to the Batch only after the uploads succeeded: a call that fails
     // validation leaves the previous batch in place, one that fails while uploading leaves an empty batch
@@ -2811,7 +2867,8 @@ static int batch_set(Batch* b, const SetInput& in)
     // the track exports in flight read the frames, meta words and list table this call replaces
     const bool framesPinned = !byRecords && nF > 0 && is_pinned(in.frames);
     {
-        const bool grows = (size_t)nF * kNumParams > b->dFrames.cap || (size_t)nF > b->dMeta.cap || (size_t)nL + 1 > b->dListStart.cap;
+        const bool grows = (size_t)nF * kNumParams > b->dFrames.cap || (size_t)nF > b->dMeta.cap || (size_t)nL + 1 > b->dListStart.cap ||
+                           (in.labels && ((size_t)nF > b->dLabels.cap || (size_t)(nF + nL) > b->dUnitFirst.cap));
         const bool unordered = !byRecords && !byDevice && !framesPinned;      // pageable frames: copied by a thread of their own, or staged by the runtime
         if (settle_track_exports(b, grows || unordered)) return -1;
     }
@@ -3268,6 +3325,13 @@ static int batch_set(Batch* b, const SetInput& in)
             HIP_TRY(hipMemcpyAsync(b->dRep.ptr, plan.rep.data(), (size_t)nF * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
             HIP_TRY(hipMemsetAsync(b->dMismatch.ptr, 0xFF, sizeof(unsigned long long), b->stream));
         }
+        if (in.labels) {
+            // the labels and unitFirst[] (klatt_align.h) on the copy stream, ahead of setCopied; the wait below covers the arrays they leave
+            if (b->dLabels.reserve(std::max<size_t>((size_t)nF, 1)) || b->dUnitFirst.reserve(std::max<size_t>((size_t)(nF + nL), 1))) return -1;
+            copyGuard.armed = true;
+            if (nF) HIP_TRY(hipMemcpyAsync(b->dLabels.ptr, in.labels, (size_t)nF * sizeof(FrameLabel), hipMemcpyHostToDevice, b->copyStream));
+            if (nF + nL) HIP_TRY(hipMemcpyAsync(b->dUnitFirst.ptr, unitFirst.data(), (size_t)(nF + nL) * sizeof(uint32_t), hipMemcpyHostToDevice, b->copyStream));
+        }
         HIP_TRY(hipStreamSynchronize(b->stream));
         if (copyGuard.armed) { HIP_TRY(hipStreamSynchronize(b->copyStream)); copyGuard.armed = false; }
         if (early.joinable()) early.join();
@@ -3308,6 +3372,8 @@ static int batch_set(Batch* b, const SetInput& in)
         }
         return rc;
     }
+    b->hasLabels = in.labels != nullptr;
+    b->listUnits.swap(listUnits);
     b->nUtt = nU; b->nFrames = nF; b->nFramesSpoken = spoken; b->nLists = nL; b->nSlots = nSlotsAll;
     b->nNoNasalUtt = nNoNasal;
     b->nQuiet = nQuietSlots; b->nNoNasal = nNoNasalSlots;      // (slots: the groups' utterances and the replicas that complete their sparse last wavefronts)
@@ -4348,6 +4414,22 @@ long long speechPlayer_batch_timeline(speechPlayer_batch_t batch, long long u, l
     return n;
 }
 
+// The per-request records behind the set call on stream `st`: built by the first export after a set call, waited for by the others.
+static int timeline_on_stream(Batch* b, hipStream_t st)
+{
+    if (b->timelineFresh) { HIP_TRY(hipStreamWaitEvent(st, b->timelineReady, 0)); return 0; }
+    if ((size_t)b->nFrames > b->dTimeline.cap && settle_track_exports(b, true)) return -1;
+    if (b->dTimeline.reserve(std::max<size_t>((size_t)b->nFrames, 1))) return -1;
+    HIP_TRY(hipStreamWaitEvent(st, b->setDone, 0));
+    HIP_TRY(hipStreamWaitEvent(st, b->setCopied, 0));
+    const unsigned grid = (unsigned)std::min<long long>((b->nLists + 255) / 256, 4ll * b->cus);
+    hipLaunchKernelGGL(klatt_timeline_requests, dim3(std::max(grid, 1u)), dim3(256), 0, st, b->dMeta.ptr, b->dListStart.ptr, b->nLists, b->dTimeline.ptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(b->timelineReady, st));
+    b->timelineFresh = true;
+    return 0;
+}
+
 // The tracks of chosen utterances into the caller's device memory on the caller's stream (klatt_timeline.h), ordered by events only:
 // behind the set call's own device work (setDone, setCopied), behind the per-request records (built by the first export after a set call)
 // and ahead of the next set call (settle_track_exports).  Rows, columns and list descriptors of all pieces are staged through one
@@ -4459,21 +4541,7 @@ long long speechPlayer_batch_exportTracks(speechPlayer_batch_t batch, const long
         if ((size_t)(most * pitchStride) > b->dPitch.cap && settle_track_exports(b, true)) return -1;
         if (b->dPitch.reserve((size_t)(most * pitchStride))) return -1;
     }
-    if (!b->timelineFresh) {
-        if ((size_t)b->nFrames > b->dTimeline.cap && settle_track_exports(b, true)) return -1;
-        if (b->dTimeline.reserve(std::max<size_t>((size_t)b->nFrames, 1))) return -1;
-    }
-    if (b->timelineFresh) HIP_TRY(hipStreamWaitEvent(st, b->timelineReady, 0));
-    else {
-        // the records of every list of the batch, once per set call
-        HIP_TRY(hipStreamWaitEvent(st, b->setDone, 0));
-        HIP_TRY(hipStreamWaitEvent(st, b->setCopied, 0));
-        const unsigned grid = (unsigned)std::min<long long>((b->nLists + 255) / 256, 4ll * b->cus);
-        hipLaunchKernelGGL(klatt_timeline_requests, dim3(std::max(grid, 1u)), dim3(256), 0, st, b->dMeta.ptr, b->dListStart.ptr, b->nLists, b->dTimeline.ptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(b->timelineReady, st));
-        b->timelineFresh = true;
-    }
+    if (timeline_on_stream(b, st)) return -1;
     if (pitchStride > 0 && b->pitchUsed) HIP_TRY(hipStreamWaitEvent(st, b->pitchDone, 0));      // (the table's previous export, whichever stream it ran on)
     char* h = static_cast<char*>(slot.host.ptr);
     memcpy(h, columns, (size_t)nColumns * sizeof(int));
@@ -4514,6 +4582,195 @@ long long speechPlayer_batch_exportTracks(speechPlayer_batch_t batch, const long
     slot.used = true;
     if (needPitch && maxSteps > 0) { HIP_TRY(hipEventRecord(b->pitchDone, st)); b->pitchUsed = true; }
     return elements;
+}
+
+
+// ---- phoneme alignment (klatt_align.h) ----------------------------------------------------------------------------------------------
+// The rows of an alignment export: count = steps (kind 0), units (1) or frames (2) of every chosen utterance.  0, or -1 with the message set.
+static int align_rows(Batch* b, const char* what, const long long* utterances, long long n, int kind, long long hop, long long phase,
+                      std::vector<AlignRow>& rows, long long* most, long long* total)
+{
+    if (!b->hasLabels) { set_error("%s: the batch has no labels (set it with setIpa, setIpaVoices, setText or setRecordsLabelled)", what); return -1; }
+    if (n < 0) { set_error("%s: %lld utterances", what, n); return -1; }
+    if (b->nFrames >= 0xFFFFFFFFll) { set_error("%s: too many frames", what); return -1; }
+    rows.resize((size_t)n);
+    *most = 0; *total = 0;
+    for (long long i = 0; i < n; ++i) {
+        const long long u = utterances ? utterances[i] : i;
+        if (u < 0 || u >= b->nUtt) { set_error("%s: utterances[%lld] = %lld is not an utterance of the batch (%lld)", what, i, u, b->nUtt); return -1; }
+        const long long L = b->lens[(size_t)u];
+        const uint32_t l = b->uttList[(size_t)u];
+        AlignRow& r = rows[(size_t)i];
+        r.frame0 = b->uttFrameStart[(size_t)u]; r.unit0 = r.frame0 + (long long)l;
+        r.nFrames = b->uttFrames[(size_t)u]; r.nUnits = b->listUnits[l]; r.length = (uint32_t)L; r.pad = 0;
+        r.count = kind == 0 ? align_steps_below(L, hop, phase) : kind == 1 ? (long long)r.nUnits : (long long)r.nFrames;
+        *most = std::max(*most, r.count);
+        *total += r.count;
+    }
+    return 0;
+}
+
+long long speechPlayer_batch_unitCounts(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int byFrame, long long* counts)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("unitCounts: no batch"); return -1; }
+    const long long n = utterances ? nUtterances : b->nUtt;
+    std::vector<AlignRow> rows;
+    long long most, total;
+    try {
+        if (align_rows(b, "unitCounts", utterances, n, byFrame ? 2 : 1, 1, 0, rows, &most, &total)) return -1;
+    } catch (const std::exception& e) { set_error("unitCounts: %s", e.what()); return -1; }
+    for (long long i = 0; counts && i < n; ++i) counts[i] = rows[(size_t)i].count;
+    return n;
+}
+
+static long long export_alignment(Batch* b, const long long* utterances, long long nUtterances, const int* columns, int nColumns, long long hop,
+                                  long long phase, void* deviceOut, int format, long long rowStride, long long pad, long long capacity, void* stream)
+{
+    if (format != 0 && format != 1) { set_error("exportAlignment: format %d (0 int64, 1 int32)", format); return -1; }
+    if (!columns || nColumns <= 0) { set_error("exportAlignment: %d columns", nColumns); return -1; }
+    if (hop <= 0 || phase < 0) { set_error("exportAlignment: hop %lld, phase %lld", hop, phase); return -1; }
+    if (rowStride < 0) { set_error("exportAlignment: rowStride %lld", rowStride); return -1; }
+    int needSpan = 0;
+    for (int q = 0; q < nColumns; ++q) {
+        if (columns[q] < 0 || columns[q] >= kAlignColumns) { set_error("exportAlignment: columns[%d] = %d (0 .. %d)", q, columns[q], kAlignColumns - 1); return -1; }
+        needSpan |= columns[q] == kAlignPosition || columns[q] == kAlignRemaining;
+    }
+    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);      // (no utterance is longer than 2^32 samples)
+    const long long n = utterances ? nUtterances : b->nUtt;
+    const bool packed = rowStride == 0;
+    std::vector<AlignRow> rows;
+    long long maxSteps = 0, totalSteps = 0;
+    if (align_rows(b, "exportAlignment", utterances, n, 0, hop, phase, rows, &maxSteps, &totalSteps)) return -1;
+    if (!packed && rowStride < maxSteps) { set_error("exportAlignment: rowStride %lld is below the largest step count (%lld)", rowStride, maxSteps); return -1; }
+    if (!packed && n > 0 && n > (1ll << 50) / rowStride / nColumns) { set_error("exportAlignment: %lld rows of %lld steps of %d columns", n, rowStride, nColumns); return -1; }
+    if (packed && totalSteps > (1ll << 50) / nColumns) { set_error("exportAlignment: %lld steps of %d columns", totalSteps, nColumns); return -1; }
+    const long long elements = (packed ? totalSteps : n * rowStride) * nColumns;
+    if (elements > capacity) { set_error("exportAlignment: the output takes %lld elements, capacity is %lld", elements, capacity); return -1; }
+    if (elements == 0) return 0;
+    const size_t elSize = format ? sizeof(int) : sizeof(long long);
+    HIP_TRY(hipSetDevice(b->device));
+    if (!deviceOut) { set_error("exportAlignment: no output buffer"); return -1; }
+    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportAlignment")) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // the staging block: columns | rows | step starts and chunk rows (packed)
+    std::vector<long long> words;
+    long long chunkOff = 0;
+    if (packed) {
+        long long acc = 0;
+        for (long long i = 0; i < n; ++i) { words.push_back(acc); acc += rows[(size_t)i].count; }
+        words.push_back(acc);
+        const long long nChunks = (acc >> kTimelineChunkLog2) + 1;
+        chunkOff = (long long)words.size();
+        long long r = 0;
+        for (long long c = 0; c < nChunks; ++c) {
+            while (r + 1 < n && words[(size_t)(r + 1)] <= (c << kTimelineChunkLog2)) ++r;
+            words.push_back(r);
+        }
+        words.push_back(std::max<long long>(n - 1, 0));
+    }
+    const size_t colBytes = ((size_t)nColumns * sizeof(int) + 15) / 16 * 16, rowBytes = (size_t)n * sizeof(AlignRow);
+    const size_t wordBytes = words.size() * sizeof(long long);
+    const size_t rowsAt = colBytes, wordsAt = (rowsAt + rowBytes + 15) / 16 * 16, bytes = wordsAt + wordBytes;
+    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
+    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
+    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
+    if (timeline_on_stream(b, st)) return -1;
+    char* h = static_cast<char*>(slot.host.ptr);
+    memcpy(h, columns, (size_t)nColumns * sizeof(int));
+    memcpy(h + rowsAt, rows.data(), rowBytes);
+    if (wordBytes) memcpy(h + wordsAt, words.data(), wordBytes);
+    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
+    const int* dCols = reinterpret_cast<const int*>(slot.dev.ptr);
+    const AlignRow* dRows = reinterpret_cast<const AlignRow*>(slot.dev.ptr + rowsAt);
+    const long long* dWords = reinterpret_cast<const long long*>(slot.dev.ptr + wordsAt);
+    const long long nLane = (elements * (long long)elSize + 15) / 16;
+    const unsigned grid = (unsigned)std::min<long long>((nLane + 255) / 256, 8ll * b->cus);
+    const int vec = reinterpret_cast<uintptr_t>(deviceOut) % 16 == 0;
+    const long long* dStart = packed ? dWords : nullptr;
+    const long long* dChunk = packed ? dWords + chunkOff : nullptr;
+    if (format) hipLaunchKernelGGL(klatt_align_dense<true>, dim3(grid), dim3(256), 0, st, b->dTimeline.ptr, b->dLabels.ptr, b->dUnitFirst.ptr, dRows, dStart, dChunk,
+                                   n, rowStride, dCols, nColumns, hop, phase, pad, needSpan, deviceOut, elements, vec);
+    else hipLaunchKernelGGL(klatt_align_dense<false>, dim3(grid), dim3(256), 0, st, b->dTimeline.ptr, b->dLabels.ptr, b->dUnitFirst.ptr, dRows, dStart, dChunk,
+                            n, rowStride, dCols, nColumns, hop, phase, pad, needSpan, deviceOut, elements, vec);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(slot.done, st));
+    slot.used = true;
+    return elements;
+}
+
+// Framewise labels of chosen utterances into the caller's device memory on the caller's stream: ordered as speechPlayer_batch_exportTracks
+// is (behind the set call and the per-request records, ahead of the next set call), staged through the same page-locked slots.
+long long speechPlayer_batch_exportAlignment(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const int* columns,
+                                             int nColumns, long long hop, long long phase, void* deviceOut, int format, long long rowStride,
+                                             long long pad, long long capacity, void* stream)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("exportAlignment: no batch"); return -1; }
+    try {
+        return export_alignment(b, utterances, nUtterances, columns, nColumns, hop, phase, deviceOut, format, rowStride, pad, capacity, stream);
+    } catch (const std::exception& e) { set_error("exportAlignment: %s", e.what()); return -1; }
+}
+
+static long long export_units(Batch* b, const long long* utterances, long long nUtterances, long long hop, long long phase, int byFrame,
+                              void* deviceOut, long long rowStride, long long pad, long long capacity, void* stream)
+{
+    if (hop <= 0 || phase < 0) { set_error("exportUnits: hop %lld, phase %lld", hop, phase); return -1; }
+    if (rowStride < 0) { set_error("exportUnits: rowStride %lld", rowStride); return -1; }
+    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
+    const long long n = utterances ? nUtterances : b->nUtt;
+    const bool packed = rowStride == 0;
+    std::vector<AlignRow> rows;
+    long long most = 0, totalEntries = 0;
+    if (align_rows(b, "exportUnits", utterances, n, byFrame ? 2 : 1, hop, phase, rows, &most, &totalEntries)) return -1;
+    if (!packed && rowStride < most) { set_error("exportUnits: rowStride %lld is below the largest count (%lld)", rowStride, most); return -1; }
+    if (!packed && n > 0 && n > (1ll << 50) / rowStride) { set_error("exportUnits: %lld rows of %lld entries", n, rowStride); return -1; }
+    const long long entries = packed ? totalEntries : n * rowStride;
+    const long long elements = entries * kUnitColumns;
+    if (elements > capacity) { set_error("exportUnits: the output takes %lld elements, capacity is %lld", elements, capacity); return -1; }
+    if (elements == 0) return 0;
+    HIP_TRY(hipSetDevice(b->device));
+    if (!deviceOut) { set_error("exportUnits: no output buffer"); return -1; }
+    if (!device_range(deviceOut, (size_t)elements * sizeof(long long), b->device, sizeof(long long), "exportUnits")) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    std::vector<long long> words;
+    if (packed) {
+        long long acc = 0;
+        for (long long i = 0; i < n; ++i) { words.push_back(acc); acc += rows[(size_t)i].count; }
+        words.push_back(acc);
+    }
+    const size_t rowBytes = (size_t)n * sizeof(AlignRow), wordBytes = words.size() * sizeof(long long);
+    const size_t wordsAt = (rowBytes + 15) / 16 * 16, bytes = wordsAt + wordBytes;
+    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
+    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
+    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
+    if (timeline_on_stream(b, st)) return -1;
+    char* h = static_cast<char*>(slot.host.ptr);
+    memcpy(h, rows.data(), rowBytes);
+    if (wordBytes) memcpy(h + wordsAt, words.data(), wordBytes);
+    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
+    const AlignRow* dRows = reinterpret_cast<const AlignRow*>(slot.dev.ptr);
+    const long long* dStart = packed ? reinterpret_cast<const long long*>(slot.dev.ptr + wordsAt) : nullptr;
+    const unsigned grid = (unsigned)std::min<long long>((entries + 255) / 256, 8ll * b->cus);
+    hipLaunchKernelGGL(klatt_align_units, dim3(grid), dim3(256), 0, st, b->dTimeline.ptr, b->dLabels.ptr, b->dUnitFirst.ptr, dRows, dStart, n, rowStride,
+                       hop, phase, byFrame ? 1 : 0, pad, static_cast<long long*>(deviceOut), entries);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(slot.done, st));
+    slot.used = true;
+    return elements;
+}
+
+long long speechPlayer_batch_exportUnits(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, long long hop, long long phase,
+                                         int byFrame, void* deviceOut, long long rowStride, long long pad, long long capacity, void* stream)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("exportUnits: no batch"); return -1; }
+    try {
+        return export_units(b, utterances, nUtterances, hop, phase, byFrame, deviceOut, rowStride, pad, capacity, stream);
+    } catch (const std::exception& e) { set_error("exportUnits: %s", e.what()); return -1; }
 }
 
 }  // extern "C"

@@ -184,6 +184,42 @@ def frames_for_batch(texts, sampleRate=22050, speed=1, basePitch=100, inflection
     return dict(frame_start=start, frames=frames, min=m, fade=f, isnull=nul)
 
 
+# what the producer's lexer knew about a frame (include/speechPlayer_batch.h, speechPlayer_frameLabel_t): 16 bytes
+LABEL_DTYPE = np.dtype([("phoneme", "<i4"), ("flags", "<u4"), ("unit", "<i4"), ("textOffset", "<i4")])
+LABEL_STRESS_MASK, LABEL_TIED_TO, LABEL_TIED_FROM, LABEL_LONG, LABEL_WORD_START, LABEL_SYLLABLE_START, LABEL_GAP, LABEL_PUFF = 3, 4, 8, 16, 32, 64, 128, 256
+
+
+def labels(ipaText):
+    """One utterance's labels, frame for frame what generateFramesAndTiming yields (speechPlayer_ipa_labels; no GPU): a structured array of
+    LABEL_DTYPE -- phoneme (index into phonemeSymbols()), flags (LABEL_*: stress in bits 0-1), unit (the text symbol the frame belongs to)
+    and textOffset (the symbol's byte offset in ipaText.encode("utf8"); -1 for inserted gaps and aspirations)."""
+    L = _native.load()
+    text = ipaText.encode("utf8")
+    n = L.speechPlayer_ipa_labels(text, None, None, None, None, -1)
+    if n < 0:
+        raise RuntimeError("speechPlayer_ipa_labels: %s" % _native.last_error())
+    cols = [np.zeros(max(n, 1), dt) for dt in (np.int32, np.uint32, np.int32, np.int32)]
+    got = L.speechPlayer_ipa_labels(text, *[c.ctypes.data for c in cols], n)
+    assert got == n
+    out = np.zeros(n, LABEL_DTYPE)
+    for name, c in zip(LABEL_DTYPE.names, cols):
+        out[name] = c[:n]
+    return out
+
+
+def phonemeSymbols():
+    """id -> symbol for the `phoneme` label: the phoneme table's symbols in table order, then "<gap>" (an inserted pre-stop gap) and
+    "<sil>" (a silence frame)."""
+    L = _native.load()
+    out = []
+    for i in range(L.speechPlayer_ipa_phonemeCount()):
+        sym = ctypes.create_string_buffer(16)
+        if L.speechPlayer_ipa_phoneme(i, sym, 16, None, None, None) != 0:
+            raise RuntimeError("phoneme table entry %d" % i)
+        out.append(sym.value.decode("utf8"))
+    return out + ["<gap>", "<sil>"]
+
+
 class _RecordsView(ctypes.Structure):
     _fields_ = [("nShapes", ctypes.c_longlong), ("shapes", ctypes.c_void_p), ("nLists", ctypes.c_longlong), ("listStart", ctypes.c_void_p),
                 ("nRecords", ctypes.c_longlong), ("records", ctypes.c_void_p), ("nUtterances", ctypes.c_longlong), ("listOf", ctypes.c_void_p)]
@@ -208,8 +244,11 @@ def records_for_batch(texts, sampleRate=22050, speed=1, basePitch=100, inflectio
         v = _RecordsView()
         assert L.speechPlayer_records_view(h, ctypes.byref(v)) == 0
         grab = lambda ptr, count, dt: np.frombuffer(ctypes.string_at(ptr, count * np.dtype(dt).itemsize), dtype=dt).copy() if count else np.zeros(0, dt)
+        lab, n_lab = ctypes.c_void_p(), ctypes.c_longlong(0)
+        assert L.speechPlayer_records_labels(h, ctypes.byref(lab), ctypes.byref(n_lab)) == 0 and n_lab.value == v.nRecords
         return dict(shapes=grab(v.shapes, v.nShapes * 47, np.float64).reshape(-1, 47), list_start=grab(v.listStart, v.nLists + 1, np.int64),
-                    records=grab(v.records, v.nRecords, RECORD_DTYPE), list_of=grab(v.listOf, v.nUtterances, np.uint32))
+                    records=grab(v.records, v.nRecords, RECORD_DTYPE), list_of=grab(v.listOf, v.nUtterances, np.uint32),
+                    labels=grab(lab.value, n_lab.value, LABEL_DTYPE))
     finally:
         L.speechPlayer_records_free(h)
 

@@ -414,6 +414,40 @@ def check_track_request(columns, hop, phase, dtype):
     return np.asarray(cols, dtype=np.int32), hop, phase, 1 if dtype == torch.float32 else 0
 
 
+ALIGN_COLUMNS = ["phoneme", "stress", "flags", "unit", "textOffset", "frame", "position", "remaining"]      # SPEECHPLAYER_ALIGN_*
+UNIT_COLUMNS = ["phoneme", "flags", "textOffset", "firstSample", "samples", "firstStep", "steps"]              # speechPlayer_batch_exportUnits
+
+
+def check_alignment_request(columns, hop, phase, dtype):
+    """The argument checks of BatchPlayer.alignmentTensor that need no GPU: `columns` a non-empty sequence of column numbers 0 .. 7 or
+    names (ALIGN_COLUMNS; a single one stands for one column), hop >= 1, phase >= 0, dtype torch.int64 / torch.int32.  Raises KeyError,
+    ValueError or TypeError as check_track_request does.  Returns (columns as an int32 array, hop, phase, the export format: 0 int64, 1 int32)."""
+    import torch
+    if isinstance(columns, (str, int, np.integer)):
+        columns = [columns]
+    cols = []
+    for c in columns:
+        if isinstance(c, str):
+            if c not in ALIGN_COLUMNS:
+                raise KeyError("alignmentTensor: no column named %r (%s)" % (c, ", ".join(ALIGN_COLUMNS)))
+            c = ALIGN_COLUMNS.index(c)
+        c = int(c)
+        if not 0 <= c < len(ALIGN_COLUMNS):
+            raise ValueError("alignmentTensor: column %d is not in 0 .. %d" % (c, len(ALIGN_COLUMNS) - 1))
+        cols.append(c)
+    if not cols:
+        raise ValueError("alignmentTensor: no columns")
+    hop, phase = int(hop), int(phase)
+    if hop < 1:
+        raise ValueError("alignmentTensor: hop must be at least 1, not %d" % hop)
+    if phase < 0:
+        raise ValueError("alignmentTensor: phase must not be negative (%d)" % phase)
+    dtype = torch.int64 if dtype is None else dtype
+    if dtype not in (torch.int64, torch.int32):
+        raise TypeError("alignmentTensor: dtype must be torch.int64 or torch.int32, not %s" % dtype)
+    return np.asarray(cols, dtype=np.int32), hop, phase, 1 if dtype == torch.int32 else 0
+
+
 def _ready_stream(owner, dev):
     """The hipStream_t a device-frames call is ordered behind: torch's current stream on `dev`.  torch's default stream is the NULL stream,
     which the engine reads as "ready now": a stream of `owner`'s own that waits for it on the device carries the order instead."""
@@ -590,6 +624,89 @@ class BatchPlayer(object):
             assert got == out.numel(), (got, out.numel())
         return out, torch.from_numpy(steps if padded else offsets)
 
+    @property
+    def hasLabels(self):
+        """True when the batch carries phoneme labels: set by setIpa, setText or setRecords(..., labels=...); any other set call drops them."""
+        return self._check(self._dll.speechPlayer_batch_hasLabels(self._h)) == 1
+
+    def _selection(self, what, utterances):
+        sel = None if utterances is None else _host_array(utterances, np.int64).reshape(-1)
+        n = self.nUtterances if sel is None else len(sel)
+        idx = np.arange(n) if sel is None else sel
+        if n and (idx.min() < 0 or idx.max() >= self.nUtterances):
+            raise ValueError("%s: utterance numbers must lie in [0, %d)" % (what, self.nUtterances))
+        return sel, n, idx
+
+    def alignmentTensor(self, columns, hop=1, phase=0, utterances=None, dtype=None, padded=True, pad=-1):
+        """Framewise phoneme labels of a batch set from IPA text, as a torch tensor on the batch's device
+        (speechPlayer_batch_exportAlignment), filled on torch's current stream without a host wait and without a synthesis launch:
+        -> (labels, steps).  Step j of an utterance is its sample phase + j * hop; element [.., j, q] is column columns[q] (by number or
+        by name, ALIGN_COLUMNS) of the frame in effect on that sample: "phoneme" (index into ipa.phonemeSymbols()), "stress", "flags"
+        (ipa.LABEL_*), "unit", "textOffset", "frame" (as trackTensor's), "position" (samples since the unit began) and "remaining" (until
+        the next begins).  utterances: indices in any order, repeats allowed (None: all); dtype torch.int64 (default) or torch.int32.
+        padded: labels is [n, most steps, len(columns)], `pad` past each utterance's end, and steps the n step counts; else labels is
+        [total steps, len(columns)] and steps the n + 1 offsets (int64 CPU tensors).  RuntimeError when the batch has no labels."""
+        import torch
+        cols, hop, phase, fmt = check_alignment_request(columns, hop, phase, dtype)
+        sel, n, idx = self._selection("alignmentTensor", utterances)
+        lens = self._lengths()[idx]
+        steps = np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
+        dev = self.device
+        tdtype = torch.int32 if fmt else torch.int64
+        if padded:
+            width = int(steps.max()) if n else 0
+            out = torch.empty((n, width, len(cols)), dtype=tdtype, device="cuda:%d" % dev)
+            stride = width
+        else:
+            offsets = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
+            out = torch.empty((int(offsets[-1]), len(cols)), dtype=tdtype, device="cuda:%d" % dev)
+            stride = 0
+        if out.numel() or not self.hasLabels:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            got = self._check(self._dll.speechPlayer_batch_exportAlignment(self._h, None if sel is None else sel.ctypes.data, n, cols.ctypes.data, len(cols),
+                                                                           hop, phase, out.data_ptr() if out.numel() else None, fmt, stride, int(pad),
+                                                                           out.numel(), stream))
+            assert got == out.numel(), (got, out.numel())
+        return out, torch.from_numpy(steps if padded else offsets)
+
+    def unitCounts(self, utterances=None, by="unit"):
+        """Units (by="frame": frames) of the chosen utterances (speechPlayer_batch_unitCounts): an int64 array."""
+        if by not in ("unit", "frame"):
+            raise ValueError("by must be 'unit' or 'frame', not %r" % (by,))
+        sel, n, _ = self._selection("unitCounts", utterances)
+        counts = np.zeros(max(n, 1), np.int64)
+        self._check(self._dll.speechPlayer_batch_unitCounts(self._h, None if sel is None else sel.ctypes.data, n, int(by == "frame"), counts.ctypes.data))
+        return counts[:n]
+
+    def unitTensor(self, hop=1, phase=0, utterances=None, by="unit", padded=True, pad=-1):
+        """The segment table of a batch set from IPA text (speechPlayer_batch_exportUnits), an int64 torch tensor on the batch's device
+        filled on torch's current stream: -> (units, counts).  One entry per text symbol of an utterance (by="unit": an inserted gap counts
+        to the stop after it, an aspiration to the stop before it, silence is an entry of its own) or per frame (by="frame"), with the columns
+        UNIT_COLUMNS: phoneme, flags (ORed over the unit; LABEL_GAP / LABEL_PUFF: it has one), textOffset, firstSample, samples, and firstStep,
+        steps: the steps phase + j * hop inside the entry (a row's steps sum to alignmentTensor's step count: duration targets at that hop).
+        padded: units is [n, most entries, 7], `pad` past each row's count, and counts the n counts; else [total entries, 7] and the n + 1 offsets."""
+        import torch
+        hop, phase = int(hop), int(phase)
+        if hop < 1 or phase < 0:
+            raise ValueError("unitTensor: hop must be at least 1 and phase not negative (%d, %d)" % (hop, phase))
+        sel, n, _ = self._selection("unitTensor", utterances)
+        counts = self.unitCounts(utterances, by)
+        dev = self.device
+        if padded:
+            width = int(counts.max()) if n else 0
+            out = torch.empty((n, width, len(UNIT_COLUMNS)), dtype=torch.int64, device="cuda:%d" % dev)
+            stride = width
+        else:
+            offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            out = torch.empty((int(offsets[-1]), len(UNIT_COLUMNS)), dtype=torch.int64, device="cuda:%d" % dev)
+            stride = 0
+        if out.numel():
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            got = self._check(self._dll.speechPlayer_batch_exportUnits(self._h, None if sel is None else sel.ctypes.data, n, hop, phase, int(by == "frame"),
+                                                                       out.data_ptr(), stride, int(pad), out.numel(), stream))
+            assert got == out.numel(), (got, out.numel())
+        return out, torch.from_numpy(counts if padded else offsets)
+
     def setUtterancesShared(self, listStart, frames, minSamples, fadeSamples, listOf, userIndex=None, isNull=None, noiseSeed=None):
         """Frame lists that utterances share (speechPlayer_batch_setUtterancesShared): `listStart`/frames/... describe the lists as
         setUtterances describes utterances; utterance u speaks list listOf[u] with noise seed noiseSeed[u]."""
@@ -606,10 +723,12 @@ class BatchPlayer(object):
         self._check(self._dll.speechPlayer_batch_setUtterancesShared(self._h, len(ls) - 1, p(ls), p(fr), p(m), p(f), p(ix), p(nu), len(lo), p(lo), p(sd)))
         self.nUtterances = len(lo)
 
-    def setRecords(self, shapes, listStart, records, listOf=None, noiseSeed=None):
+    def setRecords(self, shapes, listStart, records, listOf=None, noiseSeed=None, labels=None):
         """The batch in compact form (speechPlayer_batch_setRecords): `shapes` [nShapes, 47] f64, `records` a structured array of
-        nvspeechplayer_amd.ipa.RECORD_DTYPE (32 bytes per frame), lists and listOf as in setUtterancesShared (None: utterance u = list u)."""
-        from .ipa import RECORD_DTYPE
+        nvspeechplayer_amd.ipa.RECORD_DTYPE (32 bytes per frame), lists and listOf as in setUtterancesShared (None: utterance u = list u).
+        labels: a structured array of ipa.LABEL_DTYPE parallel to records (speechPlayer_batch_setRecordsLabelled): the batch then carries
+        phoneme labels (alignmentTensor, unitTensor)."""
+        from .ipa import LABEL_DTYPE, RECORD_DTYPE
         sh = np.ascontiguousarray(shapes, dtype=np.float64).reshape(-1, 47)
         ls = np.ascontiguousarray(listStart, dtype=np.int64)
         rc = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
@@ -618,7 +737,14 @@ class BatchPlayer(object):
         n_utt = len(ls) - 1 if lo is None else len(lo)
         sd = None if noiseSeed is None else np.ascontiguousarray(noiseSeed, dtype=np.uint32)
         p = lambda a: None if a is None else a.ctypes.data
-        self._check(self._dll.speechPlayer_batch_setRecords(self._h, len(sh), p(sh), len(ls) - 1, p(ls), p(rc), n_utt, p(lo), p(sd)))
+        if labels is None:
+            self._check(self._dll.speechPlayer_batch_setRecords(self._h, len(sh), p(sh), len(ls) - 1, p(ls), p(rc), n_utt, p(lo), p(sd)))
+        else:
+            lb = np.ascontiguousarray(labels, dtype=LABEL_DTYPE)
+            if len(lb) != len(rc):
+                raise ValueError("setRecords: %d labels for %d records" % (len(lb), len(rc)))
+            lb = lb if len(lb) else np.zeros(1, LABEL_DTYPE)
+            self._check(self._dll.speechPlayer_batch_setRecordsLabelled(self._h, len(sh), p(sh), len(ls) - 1, p(ls), p(rc), p(lb), n_utt, p(lo), p(sd)))
         self.nUtterances = n_utt
 
     def frames(self, u):

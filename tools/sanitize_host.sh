@@ -11,7 +11,7 @@ OUT=${TMPDIR:-/tmp}/speechplayer_asan
 mkdir -p "$OUT"
 /opt/rocm/bin/hipcc -O1 -g --offload-arch=gfx950 -ffp-contract=off -fPIC -std=c++17 -Xarch_host -fsanitize=address,undefined \
     -Xarch_host -fno-omit-frame-pointer -c nvspeechplayer_amd/csrc/klatt_engine.hip -o "$OUT/klatt_engine.o"
-/opt/rocm/lib/llvm/bin/clang++ -O1 -g -fPIC -std=c++17 -fsanitize=address,undefined -c nvspeechplayer_amd/csrc/frame_producer.cpp -o "$OUT/frame_producer.o"
+/opt/rocm/lib/llvm/bin/clang++ -O1 -g -fPIC -std=c++17 -fsanitize=address,undefined -DSPEECHPLAYER_LABELLED_SET -c nvspeechplayer_amd/csrc/frame_producer.cpp -o "$OUT/frame_producer.o"
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -fsanitize=address,undefined -shared-libsan -Wl,-rpath,/opt/rocm/lib \
     -o "$OUT/libspeechPlayer_asan.so" "$OUT/klatt_engine.o" "$OUT/frame_producer.o"
 RT=$(ls /opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so | head -1)
