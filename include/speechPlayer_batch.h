@@ -179,6 +179,68 @@ long long speechPlayer_batch_timeline(speechPlayer_batch_t batch, long long utte
  * of the batch's device, misaligned or too small. */
 long long speechPlayer_batch_exportTracks(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
 	const int* columns, int nColumns, long long hop, long long phase, void* deviceOut, int format, long long rowStride, void* stream);
+/*
+ * The glottal source of a batch: what the voice source did on every sample -- the fundamental after vibrato, the glottal phase, whether
+ * the glottis is open, and the sample on which every glottal cycle begins (the pitch marks).  The synthesiser computes these from two
+ * running sums that it rounds once per sample (FrequencyGenerator, reference src/speechWaveGenerator.cpp:46-60, :72-77) and keeps none
+ * of them; re-adding the exported tracks elsewhere gives another phase and, now and then, a pitch mark on another sample.
+ * For utterance u of a set batch, of length L, at sample rate sr, let cur(t) be the frame speechPlayer_batch_exportTracks defines for
+ * sample t (its quirks included: sample 0 and every dequeue sample see the frame of the sample before, NaN holds, NULL requests, the
+ * voicePitch glide).  With V(-1) = P(-1) = 0 and C(-1) = 0, for t = 0 .. L-1, every operation rounded separately in binary64, in this order:
+ *   frac(x)  = x - trunc(x)                           (fmod(x, 1) except for the sign of a zero; NaN for a non-finite x)
+ *   V(t)     = frac(vibratoSpeed(t) / sr + V(t-1))    (the vibrato phase advances at zero depth too)
+ *   vib(t)   = sin(V(t) * 6.283185307179586) * 0.06 * vibratoPitchOffset(t) + 1
+ *   hz(t)    = voicePitch(t) * vib(t)
+ *   x(t)     = hz(t) / sr + P(t-1)
+ *   P(t)     = frac(x(t))
+ *   epoch(t) = x(t) is finite and |x(t)| >= 1
+ *   C(t)     = C(t-1) + epoch(t)
+ * -- what the source stage of every synthesis kernel does with cur(t), by the same device functions on the same operands in the same
+ * order, so the exported phase is the phase behind the PCM.  The phases advance on every sample, through silence as well.  The result
+ * is a function of the utterance's frame list alone: not of its noise seed, the mode, the layout, the planner's choices or of whether the
+ * batch has been synthesised; utterances that share a list share their source.
+ * Framewise columns of speechPlayer_batch_exportSource, at the steps phase + j * hop:
+ */
+#define SPEECHPLAYER_SOURCE_F0            0   /* hz(t) */
+#define SPEECHPLAYER_SOURCE_PHASE         1   /* P(t) */
+#define SPEECHPLAYER_SOURCE_VIBRATO_PHASE 2   /* V(t) */
+#define SPEECHPLAYER_SOURCE_CYCLE         3   /* C(t) */
+#define SPEECHPLAYER_SOURCE_OPEN          4   /* 1 if P(t) >= glottalOpenQuotient(t), else 0 (a NaN compares false) */
+#define SPEECHPLAYER_SOURCE_WAVE          5   /* (P(t) * 2 - 1) * voiceAmplitude(t): the reference's glottal wave before turbulence and
+                                                 aspiration (src/speechWaveGenerator.cpp:81-83) */
+#define SPEECHPLAYER_SOURCE_COLUMNS       6
+/*
+ * The epoch table has one entry per sample with epoch(t), in time order, four float64 values each:
+ *   sample    t
+ *   instant   t - P(t) / (hz(t) / sr), both plain IEEE divisions, t as a double: the sub-sample time of the wrap
+ *   f0        hz(t)
+ *   gain      voiceAmplitude(t) * preFormantGain(t); zero: the cycle is inaudible (a caller who wants voiced pitch marks filters on it)
+ */
+#define SPEECHPLAYER_EPOCH_COLUMNS 4
+/* The source columns of chosen utterances into caller-owned device memory on the caller's stream.  Arguments, formats (0 float64,
+ * 1 float32 rounded to nearest), packing, return value, refusals and event ordering are exactly those of speechPlayer_batch_exportTracks,
+ * with columns 0 .. 5: valid as soon as the set call has returned, no synthesis launch, no host wait; the next set call waits for the
+ * exports in flight and the seventeenth export in flight waits for the first.  One wavefront walks each distinct frame list the rows
+ * speak -- one lane from option "source_lane_lists" (default 12288) lists up; the same bits -- and leaves 48 bytes per (list, step) in
+ * a table; an export whose table would exceed option "source_table_mb" (default 256) proceeds in pieces of utterances, and exports
+ * that use the table follow one another on the device. */
+long long speechPlayer_batch_exportSource(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
+	const int* columns, int nColumns, long long hop, long long phase, void* deviceOut, int format, long long rowStride, void* stream);
+/* Epochs of every chosen utterance (utterances NULL: all) into counts[] (may be NULL).  The first call after a set call runs a counting
+ * walk over the batch's lists on the engine's own stream and waits for it on the host (it downloads the counts); they are kept until
+ * the next set call.  Returns the number of utterances, -1 when refused (no batch, an utterance number outside the batch). */
+long long speechPlayer_batch_epochCounts(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, long long* counts);
+/* The epoch table of chosen utterances, float64 [row][epoch][4], into caller-owned device memory on the caller's stream.
+ *   rowStride   > 0: rowStride entries per row, `pad` in every column past the row's count; below the largest count it is refused;
+ *               0: the rows back to back
+ *   capacity    elements (doubles) deviceOut can take; fewer than the export needs is refused
+ * Contract as speechPlayer_batch_exportUnits: returns the elements written (0 writes nothing and needs no buffer), -1 on error; ordered
+ * by events like speechPlayer_batch_exportSource, except that the first call after a set call waits on the host for the counts
+ * (speechPlayer_batch_epochCounts).  Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: no batch, an utterance number outside the
+ * batch, rowStride < 0 or below the largest count, capacity below the elements needed, an output that is not device memory of the batch's
+ * device, misaligned or too small. */
+long long speechPlayer_batch_exportEpochs(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
+	void* deviceOut, long long rowStride, double pad, long long capacity, void* stream);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

@@ -57,6 +57,7 @@ EXPORTS = [
     "speechPlayer_planTimeline", "speechPlayer_batch_timeline", "speechPlayer_batch_exportTracks",
     "speechPlayer_ipa_labels", "speechPlayer_records_labels", "speechPlayer_batch_setRecordsLabelled", "speechPlayer_batch_hasLabels",
     "speechPlayer_batch_exportAlignment", "speechPlayer_batch_exportUnits", "speechPlayer_batch_unitCounts",
+    "speechPlayer_batch_exportSource", "speechPlayer_batch_epochCounts", "speechPlayer_batch_exportEpochs",
 ]
 
 
@@ -355,6 +356,12 @@ def load():
     L.speechPlayer_batch_exportUnits.argtypes = [vp, vp, i64, i64, i64, i32, vp, i64, i64, i64, vp]
     L.speechPlayer_batch_unitCounts.restype = i64
     L.speechPlayer_batch_unitCounts.argtypes = [vp, vp, i64, i32, vp]
+    L.speechPlayer_batch_exportSource.restype = i64
+    L.speechPlayer_batch_exportSource.argtypes = [vp, vp, i64, vp, i32, i64, i64, vp, i32, i64, vp]
+    L.speechPlayer_batch_epochCounts.restype = i64
+    L.speechPlayer_batch_epochCounts.argtypes = [vp, vp, i64, vp]
+    L.speechPlayer_batch_exportEpochs.restype = i64
+    L.speechPlayer_batch_exportEpochs.argtypes = [vp, vp, i64, vp, i64, f64, i64, vp]
     _lib = L
     return L
 

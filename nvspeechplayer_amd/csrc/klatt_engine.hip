@@ -17,6 +17,7 @@
 #include "klatt_plan.h"
 #include "klatt_timeline.h"
 #include "klatt_align.h"
+#include "klatt_source.h"
 
 #include <algorithm>
 #include <cmath>
@@ -650,6 +651,17 @@ struct Batch {
     DeviceBuffer<uint32_t> dUnitFirst;
     std::vector<uint32_t> listUnits;           // [nLists] units of a list
     bool hasLabels = false;
+    // speechPlayer_batch_exportSource / _epochCounts / _exportEpochs (klatt_source.h): the walks read what the track exports read and share
+    // their slots and order.  The step table and the epoch table are shared by the exports that use them, which follow one another on the
+    // device (sourceDone); the per-list epoch counts are those of the batch as set, kept until the next set call.
+    DeviceBuffer<double> dSource;              // [slot][step][6]
+    DeviceBuffer<double> dEpochs;              // [epoch][4], list after list
+    DeviceBuffer<long long> dEpochCount;       // [nLists] what the counting walk leaves
+    std::vector<long long> epochCount;         // [nLists]
+    hipEvent_t sourceDone = nullptr;
+    bool sourceUsed = false, epochFresh = false;
+    long long sourceBudgetMB = 256;            // option "source_table_mb": an export whose step table would be larger proceeds in pieces
+    long long sourceLaneLists = 12288;         // option "source_lane_lists": a walk over this many lists or more runs one lane per list
 };
 
 // The batch's own streams wait (on the device) for the exports that still read its pool.
@@ -2453,7 +2465,7 @@ speechPlayer_batch_t speechPlayer_batch_create(int sampleRate, int device)
               hipEventCreateWithFlags(&b->pcmReady, hipEventDisableTiming) == hipSuccess;
     for (auto& s : b->exportSlot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
     for (auto& s : b->trackSlot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
-    for (hipEvent_t* e : {&b->setDone, &b->setCopied, &b->timelineReady, &b->pitchDone}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    for (hipEvent_t* e : {&b->setDone, &b->setCopied, &b->timelineReady, &b->pitchDone, &b->sourceDone}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     { const char* e = getenv("SPEECHPLAYER_TRACKS"); if (e) b->tracks = atoi(e) ? 1 : 0; }
     { const char* e = getenv("SPEECHPLAYER_DIRECT"); if (e) b->direct = std::min(2, std::max(0, atoi(e))); }
     { const char* e = getenv("SPEECHPLAYER_DIRECT_LEAN"); if (e) b->directLean = std::min(1, std::max(-1, atoi(e))); }
@@ -2484,8 +2496,9 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch)
         if (s.done) (void)hipEventDestroy(s.done);
         s.host.release(); s.dev.release();
     }
-    for (hipEvent_t e : {b->setDone, b->setCopied, b->timelineReady, b->pitchDone}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {b->setDone, b->setCopied, b->timelineReady, b->pitchDone, b->sourceDone}) if (e) (void)hipEventDestroy(e);
     b->dListStart.release(); b->dTimeline.release(); b->dPitch.release(); b->dLabels.release(); b->dUnitFirst.release();
+    b->dSource.release(); b->dEpochs.release(); b->dEpochCount.release();
     if (b->inputReady) (void)hipEventDestroy(b->inputReady);
     if (b->pcmReady) (void)hipEventDestroy(b->pcmReady);
     b->dShapeIdx.release(); b->dShapeRows.release();
@@ -2529,6 +2542,10 @@ int speechPlayer_batch_setOption(speechPlayer_batch_t batch, const char* name, i
     if (!strcmp(name, "direct_lean")) { b->directLean = value < 0 ? -1 : (value ? 1 : 0); return 0; }
     // pitch_table_mb: read by speechPlayer_batch_exportTracks (the voicePitch table of an export; a larger one proceeds in pieces)
     if (!strcmp(name, "pitch_table_mb")) { b->pitchBudgetMB = value < 1 ? 1 : value; return 0; }
+    // source_table_mb: read by speechPlayer_batch_exportSource (the step table of an export; a larger one proceeds in pieces)
+    if (!strcmp(name, "source_table_mb")) { b->sourceBudgetMB = value < 1 ? 1 : value; return 0; }
+    // source_lane_lists: a source walk over at least this many frame lists runs one lane per list instead of one wavefront (same bits)
+    if (!strcmp(name, "source_lane_lists")) { b->sourceLaneLists = value < 1 ? 1 : value; return 0; }
     set_error("unknown option %s", name);
     return -1;
 }
@@ -2565,7 +2582,7 @@ static void batch_clear(Batch* b)
     b->nUtt = 0; b->nFrames = 0; b->nFramesSpoken = 0; b->nLists = 0; b->nSlots = 0; b->nQuiet = 0; b->nNoNasal = 0; b->nNoNasalUtt = 0; b->totalSamples = 0; b->poolSamples = 0;
     b->nTracked = 0; b->nTrackedUtt = 0; b->nJobs = 0; b->trackEntries = 0; b->nDirect = 0; b->nDirectUtt = 0; b->nDirectFrames = 0;
     b->lens.clear(); b->outStart.assign(1, 0); b->results.clear(); b->resultsFresh = false; b->floatFresh = false;
-    b->uttFrameStart.clear(); b->uttFrames.clear(); b->uttList.clear(); b->timelineFresh = false;
+    b->uttFrameStart.clear(); b->uttFrames.clear(); b->uttList.clear(); b->timelineFresh = false; b->epochFresh = false;
     b->hasLabels = false; b->listUnits.clear();
 }
 
@@ -3385,7 +3402,7 @@ static int batch_set(Batch* b, const SetInput& in)
     b->uttFrameStart.swap(uttFrameStart); b->uttFrames.swap(uttFrames);
     b->uttList.resize((size_t)nU);
     for (long long u = 0; u < nU; ++u) b->uttList[(size_t)u] = (uint32_t)list_of(u);
-    b->timelineFresh = false;
+    b->timelineFresh = false; b->epochFresh = false;
     // (what this call left queued on its two streams, if anything: the track exports wait for it on the device)
     HIP_TRY(hipEventRecord(b->setDone, b->stream));
     HIP_TRY(hipEventRecord(b->setCopied, b->copyStream));
@@ -4771,6 +4788,310 @@ long long speechPlayer_batch_exportUnits(speechPlayer_batch_t batch, const long 
     try {
         return export_units(b, utterances, nUtterances, hop, phase, byFrame, deviceOut, rowStride, pad, capacity, stream);
     } catch (const std::exception& e) { set_error("exportUnits: %s", e.what()); return -1; }
+}
+
+// ---- the glottal source (klatt_source.h) ----------------------------------------------------------------------------------------------
+// The source columns of chosen utterances into the caller's device memory on the caller's stream: arguments, packing, refusals and event
+// order are speechPlayer_batch_exportTracks'.  Every export walks the distinct lists its rows speak (klatt_source_walk) into the step
+// table, in pieces of rows whose lists fit option "source_table_mb", and klatt_source_dense deals the table out to the rows.
+// One walk over nLists lists (klatt_source.h): a wavefront per list, or a lane per list where there are enough of them to fill the
+// device that way (option "source_lane_lists"; profiles/source_export.txt).
+static void launch_source_walk(Batch* b, int what, hipStream_t st, const SourceList* dLists, long long nLists, long long hop, long long phase,
+                               long long tableStride, double* table, long long* counts, double* epochs)
+{
+    const double srF = (double)b->sampleRate, invSr = 1.0 / (double)b->sampleRate;      // (KernelArgs' sampleRateF and invSampleRate)
+    if (nLists >= b->sourceLaneLists) {
+        const auto fn = what == kSourceColumns ? klatt_source_lanes<kSourceColumns> : what == kSourceCount ? klatt_source_lanes<kSourceCount> : klatt_source_lanes<kSourceEpochs>;
+        hipLaunchKernelGGL(fn, dim3((unsigned)((nLists + 63) / 64)), dim3(64), 0, st, b->dFrames.ptr, b->dMeta.ptr, b->dTimeline.ptr,
+                           dLists, nLists, srF, invSr, hop, phase, tableStride, table, counts, epochs);
+    } else {
+        const auto fn = what == kSourceColumns ? klatt_source_walk<kSourceColumns> : what == kSourceCount ? klatt_source_walk<kSourceCount> : klatt_source_walk<kSourceEpochs>;
+        hipLaunchKernelGGL(fn, dim3((unsigned)nLists), dim3(64), 0, st, b->dFrames.ptr, b->dMeta.ptr, b->dTimeline.ptr,
+                           dLists, srF, invSr, hop, phase, tableStride, table, counts, epochs);
+    }
+}
+
+static long long export_source(Batch* b, const long long* utterances, long long nUtterances, const int* columns, int nColumns, long long hop,
+                               long long phase, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    if (format != 0 && format != 1) { set_error("exportSource: format %d (0 float64, 1 float32)", format); return -1; }
+    if (!columns || nColumns <= 0) { set_error("exportSource: %d columns", nColumns); return -1; }
+    if (hop <= 0 || phase < 0) { set_error("exportSource: hop %lld, phase %lld", hop, phase); return -1; }
+    if (rowStride < 0) { set_error("exportSource: rowStride %lld", rowStride); return -1; }
+    for (int q = 0; q < nColumns; ++q)
+        if (columns[q] < 0 || columns[q] >= kSourceCols) { set_error("exportSource: columns[%d] = %d (0 .. %d)", q, columns[q], kSourceCols - 1); return -1; }
+    const long long n = utterances ? nUtterances : b->nUtt;
+    if (n < 0) { set_error("exportSource: %lld utterances", n); return -1; }
+    if (b->nFrames >= 0xFFFFFFFFll) { set_error("exportSource: too many frames"); return -1; }
+    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);      // (no utterance is longer than 2^32 samples)
+    const bool packed = rowStride == 0;
+    std::vector<TimelineRow> rows((size_t)n);
+    long long maxSteps = 0, totalSteps = 0;
+    for (long long i = 0; i < n; ++i) {
+        const long long u = utterances ? utterances[i] : i;
+        if (u < 0 || u >= b->nUtt) { set_error("exportSource: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, u, b->nUtt); return -1; }
+        const long long L = b->lens[(size_t)u];
+        TimelineRow& r = rows[(size_t)i];
+        r.frame0 = b->uttFrameStart[(size_t)u]; r.nFrames = b->uttFrames[(size_t)u]; r.slot = 0;
+        r.steps = L > phase ? (L - phase + hop - 1) / hop : 0;
+        maxSteps = std::max(maxSteps, r.steps);
+        totalSteps += r.steps;
+    }
+    if (!packed && rowStride < maxSteps) { set_error("exportSource: rowStride %lld is below the largest step count (%lld)", rowStride, maxSteps); return -1; }
+    if (!packed && n > 0 && n > (1ll << 50) / rowStride / nColumns) { set_error("exportSource: %lld rows of %lld steps of %d columns", n, rowStride, nColumns); return -1; }
+    if (packed && totalSteps > (1ll << 50) / nColumns) { set_error("exportSource: %lld steps of %d columns", totalSteps, nColumns); return -1; }
+    const long long elements = (packed ? totalSteps : n * rowStride) * nColumns;
+    if (elements == 0) return 0;
+    const size_t elSize = format ? sizeof(float) : sizeof(double);
+    HIP_TRY(hipSetDevice(b->device));
+    if (!deviceOut) { set_error("exportSource: no output buffer"); return -1; }
+    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportSource")) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    // the pieces: runs of rows whose distinct lists (those with steps) fit the step table
+    struct Piece { long long r0, r1, nLists, startOff, chunkOff, nChunks; };
+    std::vector<Piece> pieces;
+    std::vector<SourceList> lists;      // of all pieces, one after the other
+    const long long tableStride = std::max<long long>(maxSteps, 1);
+    const long long slotsPerPiece = std::max<long long>(1, (b->sourceBudgetMB << 20) / (tableStride * kSourceCols * (long long)sizeof(double)));
+    {
+        std::vector<long long> stamp((size_t)b->nLists, -1);     // the piece that last gave the list a slot
+        std::vector<uint32_t> slotOf((size_t)b->nLists, 0);
+        Piece pc{0, 0, 0, 0, 0, 0};
+        for (long long i = 0; i < n; ++i) {
+            if (rows[(size_t)i].steps == 0) continue;
+            const long long u = utterances ? utterances[i] : i;
+            const uint32_t l = b->uttList[(size_t)u];
+            if (stamp[l] != (long long)pieces.size()) {
+                if (pc.nLists == slotsPerPiece) {
+                    pc.r1 = i; pieces.push_back(pc);
+                    pc = Piece{i, i, 0, 0, 0, 0};
+                }
+                stamp[l] = (long long)pieces.size();
+                slotOf[l] = (uint32_t)pc.nLists++;
+                lists.push_back(SourceList{rows[(size_t)i].frame0, (long long)rows[(size_t)i].nFrames, (long long)b->lens[(size_t)u], 0, 0});
+            }
+            rows[(size_t)i].slot = slotOf[l];
+        }
+        pc.r1 = n; pieces.push_back(pc);
+    }
+    // the staging block: columns | rows | per piece: step starts and chunk rows (packed) | lists
+    std::vector<long long> words;
+    for (Piece& pc : pieces) {
+        if (!packed) continue;
+        pc.startOff = (long long)words.size();
+        long long acc = 0;
+        for (long long i = pc.r0; i < pc.r1; ++i) { words.push_back(acc); acc += rows[(size_t)i].steps; }
+        words.push_back(acc);
+        const long long nr = pc.r1 - pc.r0;
+        pc.nChunks = (acc >> kTimelineChunkLog2) + 1;
+        pc.chunkOff = (long long)words.size();
+        long long r = 0;
+        for (long long c = 0; c < pc.nChunks; ++c) {
+            while (r + 1 < nr && words[(size_t)(pc.startOff + r + 1)] <= (c << kTimelineChunkLog2)) ++r;
+            words.push_back(r);
+        }
+        words.push_back(std::max<long long>(nr - 1, 0));
+    }
+    const size_t colBytes = ((size_t)nColumns * sizeof(int) + 15) / 16 * 16, rowBytes = (size_t)n * sizeof(TimelineRow);
+    const size_t wordBytes = words.size() * sizeof(long long), listBytes = lists.size() * sizeof(SourceList);
+    const size_t rowsAt = colBytes, wordsAt = (rowsAt + rowBytes + 15) / 16 * 16, listsAt = wordsAt + wordBytes, bytes = listsAt + listBytes;
+
+    // (every allocation first: once a kernel is queued the slot's event must come to stand behind it)
+    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
+    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
+    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
+    long long most = 0;
+    for (const Piece& pc : pieces) most = std::max(most, pc.nLists);
+    const size_t tableDoubles = (size_t)(most * tableStride) * kSourceCols;
+    if (tableDoubles > b->dSource.cap && settle_track_exports(b, true)) return -1;
+    if (b->dSource.reserve(std::max<size_t>(tableDoubles, 1))) return -1;
+    if (timeline_on_stream(b, st)) return -1;
+    if (b->sourceUsed) HIP_TRY(hipStreamWaitEvent(st, b->sourceDone, 0));      // (the table's previous export, whichever stream it ran on)
+    char* h = static_cast<char*>(slot.host.ptr);
+    memcpy(h, columns, (size_t)nColumns * sizeof(int));
+    memcpy(h + rowsAt, rows.data(), rowBytes);
+    if (wordBytes) memcpy(h + wordsAt, words.data(), wordBytes);
+    if (listBytes) memcpy(h + listsAt, lists.data(), listBytes);
+    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
+    const int* dCols = reinterpret_cast<const int*>(slot.dev.ptr);
+    const TimelineRow* dRows = reinterpret_cast<const TimelineRow*>(slot.dev.ptr + rowsAt);
+    const long long* dWords = reinterpret_cast<const long long*>(slot.dev.ptr + wordsAt);
+    const SourceList* dLists = reinterpret_cast<const SourceList*>(slot.dev.ptr + listsAt);
+    long long listAt = 0, elementAt = 0;
+    for (const Piece& pc : pieces) {
+        const long long nr = pc.r1 - pc.r0;
+        const long long pieceElements = (packed ? words[(size_t)(pc.startOff + nr)] : nr * rowStride) * nColumns;
+        if (pc.nLists > 0) {
+            launch_source_walk(b, kSourceColumns, st, dLists + listAt, pc.nLists, hop, phase, tableStride, b->dSource.ptr, nullptr, nullptr);
+            HIP_TRY(hipGetLastError());
+            listAt += pc.nLists;
+        }
+        if (pieceElements > 0) {
+            char* out = static_cast<char*>(deviceOut) + (size_t)elementAt * elSize;
+            const long long nLane = (pieceElements * (long long)elSize + 15) / 16;
+            const unsigned grid = (unsigned)std::min<long long>((nLane + 255) / 256, 8ll * b->cus);
+            const int vec = reinterpret_cast<uintptr_t>(out) % 16 == 0;
+            const long long* dStart = packed ? dWords + pc.startOff : nullptr;
+            const long long* dChunk = packed ? dWords + pc.chunkOff : nullptr;
+            if (format) hipLaunchKernelGGL(klatt_source_dense<true>, dim3(grid), dim3(256), 0, st, b->dSource.ptr, tableStride, dRows + pc.r0, dStart, dChunk,
+                                           nr, rowStride, dCols, nColumns, (void*)out, pieceElements, vec);
+            else hipLaunchKernelGGL(klatt_source_dense<false>, dim3(grid), dim3(256), 0, st, b->dSource.ptr, tableStride, dRows + pc.r0, dStart, dChunk,
+                                    nr, rowStride, dCols, nColumns, (void*)out, pieceElements, vec);
+            HIP_TRY(hipGetLastError());
+            elementAt += pieceElements;
+        }
+    }
+    HIP_TRY(hipEventRecord(slot.done, st));
+    slot.used = true;
+    HIP_TRY(hipEventRecord(b->sourceDone, st));
+    b->sourceUsed = true;
+    return elements;
+}
+
+long long speechPlayer_batch_exportSource(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const int* columns,
+                                          int nColumns, long long hop, long long phase, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("exportSource: no batch"); return -1; }
+    try {
+        return export_source(b, utterances, nUtterances, columns, nColumns, hop, phase, deviceOut, format, rowStride, stream);
+    } catch (const std::exception& e) { set_error("exportSource: %s", e.what()); return -1; }
+}
+
+// The epochs of every list of the batch as set: one counting walk on the batch's own stream, downloaded, kept until the next set call.
+static int epoch_counts(Batch* b)
+{
+    if (b->epochFresh) return 0;
+    if (b->nFrames >= 0xFFFFFFFFll || b->nLists > 0x7FFFFFFFll) { set_error("epochCounts: too many frames"); return -1; }
+    b->epochCount.assign((size_t)b->nLists, 0);
+    if (b->nLists == 0) { b->epochFresh = true; return 0; }
+    HIP_TRY(hipSetDevice(b->device));
+    std::vector<SourceList> lists((size_t)b->nLists, SourceList{0, 0, 0, 0, 0});      // (a list no utterance speaks has no samples)
+    for (long long u = 0; u < b->nUtt; ++u)
+        lists[b->uttList[(size_t)u]] = SourceList{b->uttFrameStart[(size_t)u], (long long)b->uttFrames[(size_t)u], (long long)b->lens[(size_t)u], 0, 0};
+    const size_t bytes = lists.size() * sizeof(SourceList);
+    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
+    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
+    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
+    if ((size_t)b->nLists > b->dEpochCount.cap && settle_track_exports(b, true)) return -1;
+    if (b->dEpochCount.reserve((size_t)b->nLists)) return -1;
+    if (timeline_on_stream(b, b->stream)) return -1;
+    memcpy(slot.host.ptr, lists.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, b->stream));
+    launch_source_walk(b, kSourceCount, b->stream, reinterpret_cast<const SourceList*>(slot.dev.ptr), b->nLists, 1, 0, 0, nullptr, b->dEpochCount.ptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->epochCount.data(), b->dEpochCount.ptr, (size_t)b->nLists * sizeof(long long), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    b->epochFresh = true;
+    return 0;
+}
+
+long long speechPlayer_batch_epochCounts(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, long long* counts)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("epochCounts: no batch"); return -1; }
+    const long long n = utterances ? nUtterances : b->nUtt;
+    if (n < 0) { set_error("epochCounts: %lld utterances", n); return -1; }
+    for (long long i = 0; utterances && i < n; ++i)
+        if (utterances[i] < 0 || utterances[i] >= b->nUtt) { set_error("epochCounts: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, utterances[i], b->nUtt); return -1; }
+    try {
+        if (epoch_counts(b)) return -1;
+    } catch (const std::exception& e) { set_error("epochCounts: %s", e.what()); return -1; }
+    for (long long i = 0; counts && i < n; ++i) counts[i] = b->epochCount[b->uttList[(size_t)(utterances ? utterances[i] : i)]];
+    return n;
+}
+
+// The epoch table of chosen utterances into the caller's device memory on the caller's stream, ordered as the other exports are.  The
+// counts come from epoch_counts (the first call after a set call waits for the counting walk); the writing walk takes the distinct
+// lists with epochs that the rows speak, and klatt_source_deal copies their tables to the rows.
+static long long export_epochs(Batch* b, const long long* utterances, long long nUtterances, void* deviceOut, long long rowStride, double pad,
+                               long long capacity, void* stream)
+{
+    if (rowStride < 0) { set_error("exportEpochs: rowStride %lld", rowStride); return -1; }
+    const long long n = utterances ? nUtterances : b->nUtt;
+    if (n < 0) { set_error("exportEpochs: %lld utterances", n); return -1; }
+    for (long long i = 0; utterances && i < n; ++i)
+        if (utterances[i] < 0 || utterances[i] >= b->nUtt) { set_error("exportEpochs: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, utterances[i], b->nUtt); return -1; }
+    if (epoch_counts(b)) return -1;
+    const bool packed = rowStride == 0;
+    std::vector<EpochRow> rows((size_t)n);
+    std::vector<SourceList> lists;
+    std::vector<long long> slotOf((size_t)b->nLists, -1);
+    long long most = 0, total = 0, tableEntries = 0;
+    for (long long i = 0; i < n; ++i) {
+        const long long u = utterances ? utterances[i] : i;
+        const uint32_t l = b->uttList[(size_t)u];
+        const long long count = b->epochCount[l];
+        if (count > 0 && slotOf[l] < 0) {
+            slotOf[l] = (long long)lists.size();
+            lists.push_back(SourceList{b->uttFrameStart[(size_t)u], (long long)b->uttFrames[(size_t)u], (long long)b->lens[(size_t)u], tableEntries, count});
+            tableEntries += count;
+        }
+        rows[(size_t)i] = EpochRow{count > 0 ? lists[(size_t)slotOf[l]].out : 0, count};
+        most = std::max(most, count);
+        total += count;
+    }
+    if (!packed && rowStride < most) { set_error("exportEpochs: rowStride %lld is below the largest count (%lld)", rowStride, most); return -1; }
+    if (!packed && n > 0 && n > (1ll << 50) / rowStride) { set_error("exportEpochs: %lld rows of %lld entries", n, rowStride); return -1; }
+    const long long entries = packed ? total : n * rowStride;
+    const long long elements = entries * kEpochCols;
+    if (elements > capacity) { set_error("exportEpochs: the output takes %lld elements, capacity is %lld", elements, capacity); return -1; }
+    if (elements == 0) return 0;
+    HIP_TRY(hipSetDevice(b->device));
+    if (!deviceOut) { set_error("exportEpochs: no output buffer"); return -1; }
+    if (!device_range(deviceOut, (size_t)elements * sizeof(double), b->device, sizeof(double), "exportEpochs")) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    std::vector<long long> words;
+    if (packed) {
+        long long acc = 0;
+        for (long long i = 0; i < n; ++i) { words.push_back(acc); acc += rows[(size_t)i].count; }
+        words.push_back(acc);
+    }
+    const size_t rowBytes = (size_t)n * sizeof(EpochRow), wordBytes = words.size() * sizeof(long long), listBytes = lists.size() * sizeof(SourceList);
+    const size_t wordsAt = rowBytes, listsAt = wordsAt + wordBytes, bytes = listsAt + listBytes;
+    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
+    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
+    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
+    const size_t tableDoubles = (size_t)tableEntries * kEpochCols;
+    if (tableDoubles > b->dEpochs.cap && settle_track_exports(b, true)) return -1;
+    if (b->dEpochs.reserve(std::max<size_t>(tableDoubles, 1))) return -1;
+    if (timeline_on_stream(b, st)) return -1;
+    if (b->sourceUsed) HIP_TRY(hipStreamWaitEvent(st, b->sourceDone, 0));
+    char* h = static_cast<char*>(slot.host.ptr);
+    memcpy(h, rows.data(), rowBytes);
+    if (wordBytes) memcpy(h + wordsAt, words.data(), wordBytes);
+    if (listBytes) memcpy(h + listsAt, lists.data(), listBytes);
+    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
+    const EpochRow* dRows = reinterpret_cast<const EpochRow*>(slot.dev.ptr);
+    const long long* dStart = packed ? reinterpret_cast<const long long*>(slot.dev.ptr + wordsAt) : nullptr;
+    if (!lists.empty()) {
+        launch_source_walk(b, kSourceEpochs, st, reinterpret_cast<const SourceList*>(slot.dev.ptr + listsAt), (long long)lists.size(), 1, 0, 0, nullptr, nullptr,
+                                          b->dEpochs.ptr);
+        HIP_TRY(hipGetLastError());
+    }
+    const unsigned grid = (unsigned)std::min<long long>((entries + 255) / 256, 8ll * b->cus);
+    hipLaunchKernelGGL(klatt_source_deal, dim3(grid), dim3(256), 0, st, b->dEpochs.ptr, dRows, dStart, n, rowStride, pad, static_cast<double*>(deviceOut), entries,
+                       reinterpret_cast<uintptr_t>(deviceOut) % 16 == 0 ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(slot.done, st));
+    slot.used = true;
+    HIP_TRY(hipEventRecord(b->sourceDone, st));
+    b->sourceUsed = true;
+    return elements;
+}
+
+long long speechPlayer_batch_exportEpochs(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, void* deviceOut,
+                                          long long rowStride, double pad, long long capacity, void* stream)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("exportEpochs: no batch"); return -1; }
+    try {
+        return export_epochs(b, utterances, nUtterances, deviceOut, rowStride, pad, capacity, stream);
+    } catch (const std::exception& e) { set_error("exportEpochs: %s", e.what()); return -1; }
 }
 
 }  // extern "C"

@@ -448,6 +448,50 @@ def check_alignment_request(columns, hop, phase, dtype):
     return np.asarray(cols, dtype=np.int32), hop, phase, 1 if dtype == torch.int32 else 0
 
 
+SOURCE_COLUMNS = ["f0", "phase", "vibratoPhase", "cycle", "open", "wave"]      # SPEECHPLAYER_SOURCE_*
+EPOCH_COLUMNS = ["sample", "instant", "f0", "gain"]                             # speechPlayer_batch_exportEpochs
+
+
+def check_source_request(columns, hop, phase, dtype):
+    """The argument checks of BatchPlayer.sourceTensor that need no GPU: `columns` a non-empty sequence of column numbers 0 .. 5 or
+    names (SOURCE_COLUMNS; a single one stands for one column), hop >= 1, phase >= 0, dtype None / torch.float32 / torch.float64.  Raises
+    KeyError, ValueError or TypeError as check_track_request does.  Returns (columns as an int32 array, hop, phase, the export format:
+    0 float64, 1 float32)."""
+    import torch
+    if isinstance(columns, (str, int, np.integer)):
+        columns = [columns]
+    cols = []
+    for c in columns:
+        if isinstance(c, str):
+            if c not in SOURCE_COLUMNS:
+                raise KeyError("sourceTensor: no column named %r (%s)" % (c, ", ".join(SOURCE_COLUMNS)))
+            c = SOURCE_COLUMNS.index(c)
+        c = int(c)
+        if not 0 <= c < len(SOURCE_COLUMNS):
+            raise ValueError("sourceTensor: column %d is not in 0 .. %d" % (c, len(SOURCE_COLUMNS) - 1))
+        cols.append(c)
+    if not cols:
+        raise ValueError("sourceTensor: no columns")
+    hop, phase = int(hop), int(phase)
+    if hop < 1:
+        raise ValueError("sourceTensor: hop must be at least 1, not %d" % hop)
+    if phase < 0:
+        raise ValueError("sourceTensor: phase must not be negative (%d)" % phase)
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError("sourceTensor: dtype must be torch.float32 or torch.float64, not %s" % dtype)
+    return np.asarray(cols, dtype=np.int32), hop, phase, 1 if dtype == torch.float32 else 0
+
+
+def check_option_value(name, value):
+    """speechPlayer_batch_setOption takes a C int: a value outside its range would wrap without a word (2 ** 40 arrives as 0).  Returns
+    int(value), or raises ValueError."""
+    value = int(value)
+    if not -2 ** 31 <= value < 2 ** 31:
+        raise ValueError("setOption(%r): %d does not fit the option's C int (-2**31 .. 2**31 - 1)" % (name, value))
+    return value
+
+
 def _ready_stream(owner, dev):
     """The hipStream_t a device-frames call is ordered behind: torch's current stream on `dev`.  torch's default stream is the NULL stream,
     which the engine reads as "ready now": a stream of `owner`'s own that waits for it on the device carries the order instead."""
@@ -483,7 +527,7 @@ class BatchPlayer(object):
         return rc
 
     def setOption(self, name, value):
-        self._check(self._dll.speechPlayer_batch_setOption(self._h, name.encode(), int(value)))
+        self._check(self._dll.speechPlayer_batch_setOption(self._h, name.encode(), check_option_value(name, value)))
 
     def setUtterances(self, frameStart, frames, minSamples, fadeSamples, userIndex=None, isNull=None, noiseSeed=None):
         fs = np.ascontiguousarray(frameStart, dtype=np.int64)
@@ -704,6 +748,73 @@ class BatchPlayer(object):
             stream = torch.cuda.current_stream(dev).cuda_stream
             got = self._check(self._dll.speechPlayer_batch_exportUnits(self._h, None if sel is None else sel.ctypes.data, n, hop, phase, int(by == "frame"),
                                                                        out.data_ptr(), stride, int(pad), out.numel(), stream))
+            assert got == out.numel(), (got, out.numel())
+        return out, torch.from_numpy(counts if padded else offsets)
+
+    def sourceTensor(self, columns, hop=1, phase=0, utterances=None, dtype=None, padded=True):
+        """The glottal source as a torch tensor on the batch's device (speechPlayer_batch_exportSource), filled on torch's current stream
+        without a host wait and without a synthesis launch: -> (source, steps).  Step j of an utterance is its sample phase + j * hop;
+        element [.., j, q] is column columns[q] (by number or by name, SOURCE_COLUMNS) on that sample: "f0" (the fundamental after
+        vibrato, Hz), "phase" (the glottal phase in [0, 1)), "vibratoPhase", "cycle" (glottal cycles begun so far), "open" (1 while the
+        glottis is open) and "wave" (the glottal wave before noise) -- the values behind the PCM, not a re-derivation.  utterances,
+        dtype and padded as trackTensor's: source is [n, most steps, len(columns)], zero past each utterance's end, and steps the n step
+        counts; or [total steps, len(columns)] and the n + 1 offsets (int64 CPU tensors)."""
+        import torch
+        cols, hop, phase, fmt = check_source_request(columns, hop, phase, dtype)
+        sel, n, idx = self._selection("sourceTensor", utterances)
+        lens = self._lengths()[idx]
+        steps = np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
+        dev = self.device
+        tdtype = torch.float32 if fmt else torch.float64
+        if padded:
+            width = int(steps.max()) if n else 0
+            out = torch.empty((n, width, len(cols)), dtype=tdtype, device="cuda:%d" % dev)
+            stride = width
+        else:
+            offsets = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
+            out = torch.empty((int(offsets[-1]), len(cols)), dtype=tdtype, device="cuda:%d" % dev)
+            stride = 0
+        if out.numel():
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            got = self._check(self._dll.speechPlayer_batch_exportSource(self._h, None if sel is None else sel.ctypes.data, n, cols.ctypes.data, len(cols),
+                                                                        hop, phase, out.data_ptr(), fmt, stride, stream))
+            assert got == out.numel(), (got, out.numel())
+        return out, torch.from_numpy(steps if padded else offsets)
+
+    def epochCounts(self, utterances=None):
+        """Glottal cycles begun (pitch marks) in each of the chosen utterances (speechPlayer_batch_epochCounts): an int64 array.  The first
+        call after a set call waits for a counting walk on the device."""
+        sel, n, _ = self._selection("epochCounts", utterances)
+        if n == 0:
+            return np.zeros(0, np.int64)
+        counts = np.zeros(n, np.int64)
+        self._check(self._dll.speechPlayer_batch_epochCounts(self._h, None if sel is None else sel.ctypes.data, n, counts.ctypes.data))
+        return counts[:n]
+
+    def epochTensor(self, utterances=None, padded=True, pad=-1.0):
+        """The pitch marks of the chosen utterances (speechPlayer_batch_exportEpochs), a float64 torch tensor on the batch's device filled on
+        torch's current stream: -> (epochs, counts).  One entry per sample on which the glottal phase wraps, in time order, with the columns
+        EPOCH_COLUMNS: sample, instant (the sub-sample time of the wrap), f0 and gain (voiceAmplitude * preFormantGain: zero means the
+        cycle is inaudible).  padded: epochs is [n, most entries, 4], `pad` past each row's count, and counts the n counts; else
+        [total entries, 4] and the n + 1 offsets (int64 CPU tensors).  The first call after a set call is not free of host waits: the
+        counts come from a walk over EVERY list of the batch on the engine's own stream (however few utterances are chosen), which
+        queues behind a synthesize(wait=False) in flight and is waited for on the host; later calls are ordered by events alone."""
+        import torch
+        sel, n, _ = self._selection("epochTensor", utterances)
+        counts = self.epochCounts(utterances)
+        dev = self.device
+        if padded:
+            width = int(counts.max()) if n else 0
+            out = torch.empty((n, width, len(EPOCH_COLUMNS)), dtype=torch.float64, device="cuda:%d" % dev)
+            stride = width
+        else:
+            offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            out = torch.empty((int(offsets[-1]), len(EPOCH_COLUMNS)), dtype=torch.float64, device="cuda:%d" % dev)
+            stride = 0
+        if out.numel():
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            got = self._check(self._dll.speechPlayer_batch_exportEpochs(self._h, None if sel is None else sel.ctypes.data, n, out.data_ptr(), stride,
+                                                                        float(pad), out.numel(), stream))
             assert got == out.numel(), (got, out.numel())
         return out, torch.from_numpy(counts if padded else offsets)
 
