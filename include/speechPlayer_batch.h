@@ -241,6 +241,61 @@ long long speechPlayer_batch_epochCounts(speechPlayer_batch_t batch, const long 
  * device, misaligned or too small. */
 long long speechPlayer_batch_exportEpochs(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
 	void* deviceOut, long long rowStride, double pad, long long capacity, void* stream);
+/*
+ * The vocal-tract frequency response of a batch: the spectral envelope -- the frequency response of the filter network that the track
+ * values configure on each sample, the cascade branch (N0, NP, r6 .. r1) and the parallel branch (p1 .. p6 with parallelBypass; reference
+ * src/speechWaveGenerator.cpp:139-182).  For utterance u of a set batch at sample rate sr let cur(t) be the frame
+ * speechPlayer_batch_exportTracks defines for sample t, its quirks included.  For a frequency f (Hz, any finite double):
+ *   w = 6.283185307179586 * f / sr;   c1 = cos w, s1 = sin w, c2 = cos 2w, s2 = sin 2w (the C library's, made once per bin on the host);
+ *   z1 = c1 - i s1, z2 = c2 - i s2
+ *   (a, b, c)_r = coefficient_finish(coefficient_parts(cf, cb), anti, cf) of each of the 14 resonators from cur(t): the functions the
+ *       synthesis kernels call (exp and cos of klatt_math.h inside their validated range)
+ * and, every operation a separately rounded binary64 operation, complex products written out in real arithmetic
+ * ((x y).re = x.re y.re - x.im y.im, (x y).im = x.re y.im + x.im y.re; sums and products from left to right):
+ *   pole resonator   H_r = 0 when a_r == 0: its output is identically zero from a fresh state -- the all-zero frame of sample 0 and of
+ *                    silence phonemes (f = bw = 0 gives a = 0 exactly).  Otherwise, with D = 1 - b_r z1 - c_r z2, i.e.
+ *                    D.re = 1 - b c1 - c c2, D.im = b s1 + c s2:   q = a / (D.re D.re + D.im D.im) by IEEE division,
+ *                    H_r = (q D.re, -(q D.im)).  A pole on a bin gives +-inf or NaN, and that is the answer.
+ *   anti-resonator   H_N0 = a + b z1 + c z2 = (a + b c1 + c c2, -(b s1 + c s2)): always the FIR form; with cfN0 == 0 the coefficients are
+ *                    the non-inverted ones (src/speechWaveGenerator.cpp:120, :133)
+ *   cascade          T = H_N0 H_NP;  X = ((1 + (T.re - 1) caNP) 0.5, (T.im caNP) 0.5);  C = X H_6 H_5 H_4 H_3 H_2 H_1, the factors applied
+ *                    in that order (:148-156)
+ *   parallel         S = sum_{k = 1 .. 6} ((H_pk.re - 1) pa_k, H_pk.im pa_k), from zero;
+ *                    P = ((S.re + (1 - S.re) parallelBypass) 0.5, (S.im + (0 - S.im) parallelBypass) 0.5)      (:171-179)
+ *   gain != 0        both multiplied, component by component, by g = preFormantGain(t) * outputGain(t)
+ * It is the frozen-time response of cur(t): the network with the coefficients of that one sample held for ever.  It does not depend on
+ * voicePitch, the noise seed, the mode, the layout, the planner's choices or on whether the batch has been synthesised; utterances that
+ * share a frame list share it.  Non-finite parameters propagate by IEEE arithmetic and give unspecified values, never a fault.
+ * Kinds, in any order, repeats allowed:
+ */
+#define SPEECHPLAYER_RESPONSE_CASCADE_RE   0
+#define SPEECHPLAYER_RESPONSE_CASCADE_IM   1
+#define SPEECHPLAYER_RESPONSE_CASCADE_MAG  2   /* sqrt(re * re + im * im) */
+#define SPEECHPLAYER_RESPONSE_CASCADE_DB   3   /* 20 * log10(MAG): -inf at 0 */
+#define SPEECHPLAYER_RESPONSE_PARALLEL_RE  4
+#define SPEECHPLAYER_RESPONSE_PARALLEL_IM  5
+#define SPEECHPLAYER_RESPONSE_PARALLEL_MAG 6
+#define SPEECHPLAYER_RESPONSE_PARALLEL_DB  7
+#define SPEECHPLAYER_RESPONSE_KINDS        8
+/* Host only, touches no device (like speechPlayer_planTimeline): the response of nFrames plain frames at sampleRate, by the definition
+ * above with cur = the frame, out[frame][kind][bin] float64 -- the product's own CPU statement of the definition (a voice designer plots
+ * one phoneme with it; the device path is held to it, bit for bit but for log10).  frequencies[nFrequencies]: 1 .. 4096 finite values.
+ * Returns the elements written (0 for nFrames == 0), -1 on bad arguments. */
+long long speechPlayer_frameResponse(const speechPlayer_frame_t* frames, long long nFrames, int sampleRate, const double* frequencies,
+	int nFrequencies, const int* kinds, int nKinds, int gain, double* out);
+/* The response of chosen utterances into caller-owned device memory on the caller's stream: element (i, j, q, k) of [row][step][kind][bin]
+ * is kind kinds[q] of utterance utterances[i] at sample phase + j * hop and frequency frequencies[k].  frequencies is a HOST array,
+ * 1 <= nFrequencies <= 4096; the library computes the four twiddles per bin on the host, so that the device and
+ * speechPlayer_frameResponse use the same bits, and uploads them in the export's stream order.  Steps, rowStride (in steps, zeros past
+ * the end), packing, format (0 float64, 1 float32 rounded to nearest), return value, device-memory checks, event ordering and the
+ * sixteen-in-flight rule are exactly those of speechPlayer_batch_exportTracks: valid as soon as the set call has returned, no synthesis
+ * launch, no host wait; the next set call waits for the exports in flight.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: no batch, a kind outside 0 .. 7, nKinds <= 0, nFrequencies outside
+ * 1 .. 4096, a NULL or non-finite frequency, hop <= 0, phase < 0, an unknown format, an utterance number outside the batch, a rowStride
+ * below the largest step count, an output that is not device memory of the batch's device, misaligned or too small. */
+long long speechPlayer_batch_exportResponse(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
+	const double* frequencies, int nFrequencies, const int* kinds, int nKinds, int gain, long long hop, long long phase,
+	void* deviceOut, int format, long long rowStride, void* stream);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

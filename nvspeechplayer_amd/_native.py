@@ -58,6 +58,7 @@ EXPORTS = [
     "speechPlayer_ipa_labels", "speechPlayer_records_labels", "speechPlayer_batch_setRecordsLabelled", "speechPlayer_batch_hasLabels",
     "speechPlayer_batch_exportAlignment", "speechPlayer_batch_exportUnits", "speechPlayer_batch_unitCounts",
     "speechPlayer_batch_exportSource", "speechPlayer_batch_epochCounts", "speechPlayer_batch_exportEpochs",
+    "speechPlayer_frameResponse", "speechPlayer_batch_exportResponse",
 ]
 
 
@@ -362,6 +363,10 @@ def load():
     L.speechPlayer_batch_epochCounts.argtypes = [vp, vp, i64, vp]
     L.speechPlayer_batch_exportEpochs.restype = i64
     L.speechPlayer_batch_exportEpochs.argtypes = [vp, vp, i64, vp, i64, f64, i64, vp]
+    L.speechPlayer_frameResponse.restype = i64
+    L.speechPlayer_frameResponse.argtypes = [vp, i64, i32, vp, i32, vp, i32, i32, vp]
+    L.speechPlayer_batch_exportResponse.restype = i64
+    L.speechPlayer_batch_exportResponse.argtypes = [vp, vp, i64, vp, i32, vp, i32, i32, i64, i64, vp, i32, i64, vp]
     _lib = L
     return L
 

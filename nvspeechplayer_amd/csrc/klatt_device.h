@@ -406,8 +406,8 @@ __device__ __forceinline__ RadCos coefficient_parts(double f, double bw, double 
     RadCos o; o.rad = rad; o.cs = cs;
     return o;
 }
-// the coefficients from the two parts (reference src/speechWaveGenerator.cpp:117-126)
-__device__ __forceinline__ Coef coefficient_finish(double rad, double cs, bool anti, double f)
+// the coefficients from the two parts (reference src/speechWaveGenerator.cpp:117-126); the host states the response with it too (klatt_response.h)
+__host__ __device__ __forceinline__ Coef coefficient_finish(double rad, double cs, bool anti, double f)
 {
     double cc = -(rad * rad);
     double bb = rad * cs * 2.0;

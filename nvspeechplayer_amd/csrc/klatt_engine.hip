@@ -18,6 +18,7 @@
 #include "klatt_timeline.h"
 #include "klatt_align.h"
 #include "klatt_source.h"
+#include "klatt_response.h"
 
 #include <algorithm>
 #include <cmath>
@@ -5092,6 +5093,172 @@ long long speechPlayer_batch_exportEpochs(speechPlayer_batch_t batch, const long
     try {
         return export_epochs(b, utterances, nUtterances, deviceOut, rowStride, pad, capacity, stream);
     } catch (const std::exception& e) { set_error("exportEpochs: %s", e.what()); return -1; }
+}
+
+// ---- vocal-tract frequency response (klatt_response.h) ---------------------------------------------------------------------------------
+// The arguments both entry points share.  0, or -1 with the message set.
+static int response_request(const char* what, const double* frequencies, int nFrequencies, const int* kinds, int nKinds)
+{
+    if (nFrequencies < 1 || nFrequencies > kRespMaxBins) { set_error("%s: %d frequencies (1 .. %d)", what, nFrequencies, kRespMaxBins); return -1; }
+    if (!frequencies) { set_error("%s: no frequencies", what); return -1; }
+    for (int k = 0; k < nFrequencies; ++k)
+        if (!std::isfinite(frequencies[k])) { set_error("%s: frequencies[%d] is not finite", what, k); return -1; }
+    if (!kinds || nKinds <= 0) { set_error("%s: %d kinds", what, nKinds); return -1; }
+    for (int q = 0; q < nKinds; ++q)
+        if (kinds[q] < 0 || kinds[q] >= kRespKinds) { set_error("%s: kinds[%d] = %d (0 .. %d)", what, q, kinds[q], kRespKinds - 1); return -1; }
+    return 0;
+}
+
+// Host only, touches no device: the definition of include/speechPlayer_batch.h on plain frames, out[frame][kind][bin], through the
+// functions the kernel is compiled from (klatt_response.h).
+long long speechPlayer_frameResponse(const speechPlayer_frame_t* frames, long long nFrames, int sampleRate, const double* frequencies,
+                                     int nFrequencies, const int* kinds, int nKinds, int gain, double* out)
+{
+    begin_call();
+    if (nFrames < 0 || sampleRate <= 0 || (nFrames > 0 && (!frames || !out))) { set_error("frameResponse: bad arguments"); return -1; }
+    if (response_request("frameResponse", frequencies, nFrequencies, kinds, nKinds)) return -1;
+    try {
+        std::vector<double> tw((size_t)nFrequencies * 4);
+        for (int k = 0; k < nFrequencies; ++k) response_twiddles(frequencies[k], sampleRate, tw.data() + (size_t)k * 4);
+        bool needC = false, needP = false;
+        for (int q = 0; q < nKinds; ++q) { needC = needC || kinds[q] < 4; needP = needP || kinds[q] >= 4; }
+        const KernelArgs a = base_args(sampleRate);
+        const double* f = reinterpret_cast<const double*>(frames);
+        double V[kRespVals];
+        for (long long i = 0; i < nFrames; ++i) {
+            response_values_host(f + i * kNumParams, a.negPiOverSr, a.twoPiOverSr, V);
+            double* o = out + (size_t)i * nKinds * nFrequencies;
+            for (int k = 0; k < nFrequencies; ++k) {
+                Cx C, P;
+                const double* w = tw.data() + (size_t)k * 4;
+                response_bin(V, w[0], w[1], w[2], w[3], gain != 0, needC, needP, C, P);
+                for (int q = 0; q < nKinds; ++q) o[(size_t)q * nFrequencies + k] = response_kind(kinds[q], C, P);
+            }
+        }
+    } catch (const std::exception& e) { set_error("frameResponse: %s", e.what()); return -1; }
+    return nFrames * nKinds * nFrequencies;
+}
+
+// The response of chosen utterances into the caller's device memory on the caller's stream: rows, steps, packing, refusals and event
+// order are speechPlayer_batch_exportTracks' (one piece: no table).  Rows that speak one frame list form a group, computed once and
+// stored to each of its rows (klatt_response.h).  The twiddles are made here, by the functions speechPlayer_frameResponse uses, and
+// travel in the export's staging block: twiddles | kinds | groups | the rows' first steps, group after group.
+static long long export_response(Batch* b, const long long* utterances, long long nUtterances, const double* frequencies, int nFrequencies,
+                                 const int* kinds, int nKinds, int gain, long long hop, long long phase, void* deviceOut, int format,
+                                 long long rowStride, void* stream)
+{
+    if (format != 0 && format != 1) { set_error("exportResponse: format %d (0 float64, 1 float32)", format); return -1; }
+    if (response_request("exportResponse", frequencies, nFrequencies, kinds, nKinds)) return -1;
+    if (hop <= 0 || phase < 0) { set_error("exportResponse: hop %lld, phase %lld", hop, phase); return -1; }
+    if (rowStride < 0) { set_error("exportResponse: rowStride %lld", rowStride); return -1; }
+    const long long n = utterances ? nUtterances : b->nUtt;
+    if (n < 0) { set_error("exportResponse: %lld utterances", n); return -1; }
+    if (b->nFrames >= 0xFFFFFFFFll) { set_error("exportResponse: too many frames"); return -1; }
+    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
+    const bool packed = rowStride == 0;
+    const long long perStep = (long long)nKinds * nFrequencies;
+    std::vector<ResponseGroup> groups;
+    std::vector<long long> groupOf((size_t)b->nLists, -1), rowGroup((size_t)n), rowFirst((size_t)n);
+    long long maxSteps = 0, totalSteps = 0;
+    for (long long i = 0; i < n; ++i) {
+        const long long u = utterances ? utterances[i] : i;
+        if (u < 0 || u >= b->nUtt) { set_error("exportResponse: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, u, b->nUtt); return -1; }
+        const uint32_t l = b->uttList[(size_t)u];
+        if (groupOf[l] < 0) {
+            const long long L = b->lens[(size_t)u];
+            ResponseGroup g;
+            g.frame0 = b->uttFrameStart[(size_t)u]; g.nFrames = b->uttFrames[(size_t)u]; g.nRows = 0;
+            g.steps = L > phase ? (L - phase + hop - 1) / hop : 0;
+            g.span = 0; g.chunk0 = 0; g.rowAt = 0;
+            groupOf[l] = (long long)groups.size();
+            groups.push_back(g);
+        }
+        ResponseGroup& g = groups[(size_t)groupOf[l]];
+        if (g.nRows == 0xFFFFFFFFu) { set_error("exportResponse: too many rows of one frame list"); return -1; }
+        ++g.nRows;
+        rowGroup[(size_t)i] = groupOf[l];
+        rowFirst[(size_t)i] = packed ? totalSteps : i * rowStride;
+        maxSteps = std::max(maxSteps, g.steps);
+        totalSteps += g.steps;
+    }
+    if (!packed && rowStride < maxSteps) { set_error("exportResponse: rowStride %lld is below the largest step count (%lld)", rowStride, maxSteps); return -1; }
+    if (!packed && n > 0 && n > (1ll << 50) / rowStride / perStep) { set_error("exportResponse: %lld rows of %lld steps of %lld values", n, rowStride, perStep); return -1; }
+    if (packed && totalSteps > (1ll << 50) / perStep) { set_error("exportResponse: %lld steps of %lld values", totalSteps, perStep); return -1; }
+    const long long outSteps = packed ? totalSteps : n * rowStride;
+    const long long elements = outSteps * perStep;
+    if (elements == 0) return 0;
+    const size_t elSize = format ? sizeof(float) : sizeof(double);
+    HIP_TRY(hipSetDevice(b->device));
+    if (!deviceOut) { set_error("exportResponse: no output buffer"); return -1; }
+    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportResponse")) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    // the groups that write anything, their chunks one after the other, and their rows' first steps side by side
+    std::vector<ResponseGroup> live;
+    std::vector<long long> liveOf(groups.size(), -1);
+    long long nChunks = 0, rowAt = 0;
+    for (size_t g = 0; g < groups.size(); ++g) {
+        ResponseGroup G = groups[g];
+        G.span = packed ? G.steps : rowStride;
+        if (G.span == 0) continue;
+        G.chunk0 = nChunks; G.rowAt = rowAt;
+        nChunks += (G.span + kRespSteps - 1) / kRespSteps;
+        rowAt += G.nRows;
+        liveOf[g] = (long long)live.size();
+        live.push_back(G);
+    }
+    std::vector<long long> rowBase((size_t)rowAt), fill(live.size(), 0);
+    for (long long i = 0; i < n; ++i) {
+        const long long g = liveOf[(size_t)rowGroup[(size_t)i]];
+        if (g < 0) continue;
+        rowBase[(size_t)(live[(size_t)g].rowAt + fill[(size_t)g]++)] = rowFirst[(size_t)i];
+    }
+    const size_t twBytes = (size_t)nFrequencies * 4 * sizeof(double), kindBytes = ((size_t)nKinds * sizeof(int) + 15) / 16 * 16;
+    const size_t groupBytes = live.size() * sizeof(ResponseGroup), baseBytes = rowBase.size() * sizeof(long long);
+    const size_t kindsAt = twBytes, groupsAt = kindsAt + kindBytes, basesAt = groupsAt + groupBytes, bytes = basesAt + baseBytes;
+
+    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
+    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
+    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
+    if (timeline_on_stream(b, st)) return -1;
+    char* h = static_cast<char*>(slot.host.ptr);
+    double* tw = reinterpret_cast<double*>(h);
+    for (int k = 0; k < nFrequencies; ++k) response_twiddles(frequencies[k], b->sampleRate, tw + (size_t)k * 4);
+    memcpy(h + kindsAt, kinds, (size_t)nKinds * sizeof(int));
+    memcpy(h + groupsAt, live.data(), groupBytes);
+    memcpy(h + basesAt, rowBase.data(), baseBytes);
+    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
+    const KernelArgs ka = base_args(b->sampleRate);
+    ResponseArgs A;
+    A.frames = b->dFrames.ptr; A.req = b->dTimeline.ptr;
+    A.groups = reinterpret_cast<const ResponseGroup*>(slot.dev.ptr + groupsAt); A.nGroups = (long long)live.size(); A.nChunks = nChunks;
+    A.rowBase = reinterpret_cast<const long long*>(slot.dev.ptr + basesAt);
+    A.hop = hop; A.phase = phase;
+    A.kinds = reinterpret_cast<const int*>(slot.dev.ptr + kindsAt); A.nKinds = nKinds;
+    A.tw = reinterpret_cast<const double*>(slot.dev.ptr); A.K = nFrequencies;
+    A.gain = gain != 0; A.needC = 0; A.needP = 0;
+    for (int q = 0; q < nKinds; ++q) { if (kinds[q] < 4) A.needC = 1; else A.needP = 1; }
+    A.negPiOverSr = ka.negPiOverSr; A.twoPiOverSr = ka.twoPiOverSr;
+    A.out = deviceOut;
+    const unsigned grid = (unsigned)std::min<long long>(nChunks, 16ll * b->cus);
+    if (format) hipLaunchKernelGGL(klatt_response<true>, dim3(grid), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(klatt_response<false>, dim3(grid), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(slot.done, st));
+    slot.used = true;
+    return elements;
+}
+
+long long speechPlayer_batch_exportResponse(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
+                                            const double* frequencies, int nFrequencies, const int* kinds, int nKinds, int gain, long long hop,
+                                            long long phase, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("exportResponse: no batch"); return -1; }
+    try {
+        return export_response(b, utterances, nUtterances, frequencies, nFrequencies, kinds, nKinds, gain, hop, phase, deviceOut, format, rowStride, stream);
+    } catch (const std::exception& e) { set_error("exportResponse: %s", e.what()); return -1; }
 }
 
 }  // extern "C"

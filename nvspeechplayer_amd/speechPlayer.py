@@ -483,6 +483,68 @@ def check_source_request(columns, hop, phase, dtype):
     return np.asarray(cols, dtype=np.int32), hop, phase, 1 if dtype == torch.float32 else 0
 
 
+RESPONSE_KINDS = ["cascade_re", "cascade_im", "cascade_mag", "cascade_db",
+                  "parallel_re", "parallel_im", "parallel_mag", "parallel_db"]      # SPEECHPLAYER_RESPONSE_*
+RESPONSE_MAX_BINS = 4096
+
+
+def check_response_request(frequencies, kinds, sampleRate, what="responseTensor"):
+    """The argument checks of BatchPlayer.responseTensor and frameResponse that need no GPU: `frequencies` an int K (the K bins of
+    linspace(0, sampleRate / 2, K)) or an array of 1 .. 4096 finite values in Hz; `kinds` a non-empty sequence of kind numbers 0 .. 7 or
+    names (RESPONSE_KINDS; a single one stands for one kind).  Raises KeyError (unknown name) or ValueError.  Returns (frequencies as a
+    float64 array, kinds as an int32 array)."""
+    if isinstance(frequencies, (int, np.integer)) and not isinstance(frequencies, bool):
+        if not 1 <= int(frequencies) <= RESPONSE_MAX_BINS:
+            raise ValueError("%s: %d frequencies (1 .. %d)" % (what, int(frequencies), RESPONSE_MAX_BINS))
+        freqs = np.linspace(0.0, sampleRate / 2.0, int(frequencies))
+    else:
+        freqs = np.ascontiguousarray(np.asarray(frequencies, dtype=np.float64).reshape(-1))
+    if not 1 <= len(freqs) <= RESPONSE_MAX_BINS:
+        raise ValueError("%s: %d frequencies (1 .. %d)" % (what, len(freqs), RESPONSE_MAX_BINS))
+    if not np.all(np.isfinite(freqs)):
+        raise ValueError("%s: every frequency must be finite" % what)
+    if isinstance(kinds, (str, int, np.integer)):
+        kinds = [kinds]
+    ks = []
+    for k in kinds:
+        if isinstance(k, str):
+            if k not in RESPONSE_KINDS:
+                raise KeyError("%s: no kind named %r (%s)" % (what, k, ", ".join(RESPONSE_KINDS)))
+            k = RESPONSE_KINDS.index(k)
+        k = int(k)
+        if not 0 <= k < len(RESPONSE_KINDS):
+            raise ValueError("%s: kind %d is not in 0 .. %d" % (what, k, len(RESPONSE_KINDS) - 1))
+        ks.append(k)
+    if not ks:
+        raise ValueError("%s: no kinds" % what)
+    return freqs, np.asarray(ks, dtype=np.int32)
+
+
+def frameResponse(frames, sampleRate, frequencies, kinds=("cascade_db", "parallel_db"), gain=False):
+    """The vocal-tract frequency response of plain frames on the host (speechPlayer_frameResponse; no GPU): frames [n, 47] (or one frame,
+    or a Frame) -> float64 [n, len(kinds), K], by the definition in include/speechPlayer_batch.h -- the cascade and the parallel branch
+    of the filter network each frame configures, at `frequencies` (an int K: linspace(0, sampleRate / 2, K); or Hz values).  kinds by
+    number or name (RESPONSE_KINDS); gain: times preFormantGain * outputGain."""
+    if isinstance(frames, Frame):
+        frames = frames.as_array()
+    fr = np.ascontiguousarray(np.asarray(frames, dtype=np.float64))
+    if fr.ndim == 1:
+        fr = fr.reshape(1, -1)
+    if fr.ndim != 2 or fr.shape[1] != len(FRAME_FIELDS):
+        raise ValueError("frameResponse: frames must be [n, %d], not %s" % (len(FRAME_FIELDS), list(fr.shape)))
+    if int(sampleRate) <= 0:
+        raise ValueError("frameResponse: sampleRate must be positive")
+    freqs, ks = check_response_request(frequencies, kinds, int(sampleRate), "frameResponse")
+    out = np.zeros((fr.shape[0], len(ks), len(freqs)), np.float64)
+    dll = _native.load()
+    got = dll.speechPlayer_frameResponse(fr.ctypes.data, fr.shape[0], int(sampleRate), freqs.ctypes.data, len(freqs), ks.ctypes.data, len(ks),
+                                         1 if gain else 0, out.ctypes.data)
+    if got < 0:
+        raise RuntimeError(_native.last_error())
+    assert got == out.size, (got, out.size)
+    return out
+
+
 def check_option_value(name, value):
     """speechPlayer_batch_setOption takes a C int: a value outside its range would wrap without a word (2 ** 40 arrives as 0).  Returns
     int(value), or raises ValueError."""
@@ -778,6 +840,47 @@ class BatchPlayer(object):
             stream = torch.cuda.current_stream(dev).cuda_stream
             got = self._check(self._dll.speechPlayer_batch_exportSource(self._h, None if sel is None else sel.ctypes.data, n, cols.ctypes.data, len(cols),
                                                                         hop, phase, out.data_ptr(), fmt, stride, stream))
+            assert got == out.numel(), (got, out.numel())
+        return out, torch.from_numpy(steps if padded else offsets)
+
+    def responseTensor(self, frequencies, kinds=("cascade_db", "parallel_db"), hop=1, phase=0, utterances=None, dtype=None, padded=True, gain=False):
+        """The vocal-tract frequency response (the spectral envelope) as a torch tensor on the batch's device
+        (speechPlayer_batch_exportResponse), filled on torch's current stream without a host wait and without a synthesis launch:
+        -> (response, steps).  Step j of an utterance is its sample phase + j * hop; element [.., j, q, k] is kind kinds[q] (by number or
+        name, RESPONSE_KINDS: real part, imaginary part, magnitude or dB of the cascade or the parallel branch) of the filter network
+        the synthesiser configured on that sample, at frequency k of `frequencies`: an int K (linspace(0, sampleRate / 2, K)) or Hz
+        values (at most 4096).  gain: times preFormantGain * outputGain of the sample.  utterances, dtype and padded as trackTensor's:
+        response is [n, most steps, len(kinds), K], zero past each utterance's end, and steps the n step counts; or
+        [total steps, len(kinds), K] and the n + 1 offsets (int64 CPU tensors)."""
+        import torch
+        freqs, ks = check_response_request(frequencies, kinds, self.sampleRate)
+        hop, phase = int(hop), int(phase)
+        if hop < 1:
+            raise ValueError("responseTensor: hop must be at least 1, not %d" % hop)
+        if phase < 0:
+            raise ValueError("responseTensor: phase must not be negative (%d)" % phase)
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError("responseTensor: dtype must be torch.float32 or torch.float64, not %s" % dtype)
+        fmt = 1 if dtype == torch.float32 else 0
+        sel, n, idx = self._selection("responseTensor", utterances)
+        lens = self._lengths()[idx]
+        steps = np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
+        dev = self.device
+        tdtype = torch.float32 if fmt else torch.float64
+        if padded:
+            width = int(steps.max()) if n else 0
+            out = torch.empty((n, width, len(ks), len(freqs)), dtype=tdtype, device="cuda:%d" % dev)
+            stride = width
+        else:
+            offsets = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
+            out = torch.empty((int(offsets[-1]), len(ks), len(freqs)), dtype=tdtype, device="cuda:%d" % dev)
+            stride = 0
+        if out.numel():
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            got = self._check(self._dll.speechPlayer_batch_exportResponse(self._h, None if sel is None else sel.ctypes.data, n, freqs.ctypes.data,
+                                                                          len(freqs), ks.ctypes.data, len(ks), 1 if gain else 0, hop, phase,
+                                                                          out.data_ptr(), fmt, stride, stream))
             assert got == out.numel(), (got, out.numel())
         return out, torch.from_numpy(steps if padded else offsets)
 
