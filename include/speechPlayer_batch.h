@@ -296,6 +296,74 @@ long long speechPlayer_frameResponse(const speechPlayer_frame_t* frames, long lo
 long long speechPlayer_batch_exportResponse(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
 	const double* frequencies, int nFrequencies, const int* kinds, int nKinds, int gain, long long hop, long long phase,
 	void* deviceOut, int format, long long rowStride, void* stream);
+/*
+ * The signal stems of a batch: what the synthesiser computes on every sample between the frame and the PCM -- the excitation that
+ * enters the cascade and its periodic and aperiodic parts, the frication that enters the parallel bank, the outputs of the two filter
+ * branches and the mixed sample before it is clipped and truncated to int16.  For utterance u of a set batch, of length L, with noise
+ * seed s, at sample rate sr:
+ *   cur(t)   the frame speechPlayer_batch_exportTracks defines for sample t, its quirks included
+ *   P(t)     the glottal phase speechPlayer_batch_exportSource defines
+ *   n(k)     value k of the utterance's noise stream (seed s): a 32-bit linear congruential generator whose start and increment come
+ *            from the seed, value k = state k + 1 shifted right by one, 0 .. 2^31 - 1; u(k) = n(k) / 2147483647, correctly rounded
+ *   fourteen resonators in the order N0, NP, c6 .. c1, p1 .. p6, each with memories z1 = z2 = 0 at t = -1 and, on sample t, the
+ *            coefficients (a, b, c)_r(t) = coefficient_finish(coefficient_parts(cf_r(t), cb_r(t)), r == N0, cf_r(t)) of cur(t): the
+ *            functions the synthesis kernels call and speechPlayer_batch_exportResponse names (speechPlayer_resonatorCoefficients
+ *            states them on the host)
+ *   A(-1) = F(-1) = 0
+ * and, every operation a separately rounded binary64 operation, in this order (reference src/speechWaveGenerator.cpp:72-86, :147-180,
+ * :203-208):
+ *   A(t)       = u(2t) + 0.75 A(t-1);                      asp = A(t) 0.2
+ *   turb       = asp voiceTurbulenceAmplitude;             turb = turb 0.01 unless P(t) >= glottalOpenQuotient
+ *   VOICE      = ((P(t) 2 - 1) + turb) voiceAmplitude
+ *   ASPIRATION = asp aspirationAmplitude
+ *   SOURCE     = ASPIRATION + VOICE                        (what VoiceGenerator::getNext returns)
+ *   x          = (SOURCE preFormantGain) 0.5
+ *   n0 = res_N0(x) [its memory takes the input];  np = res_NP(n0);  o = hold_lerp(x, np, caNP)
+ *   o          = res_c6(o) ... res_c1(o)                   res(in) = (a in + b z1) + c z2;  z2 = z1;  z1 = the output
+ *   CASCADE    = o
+ *   F(t)       = u(2t+1) + 0.75 F(t-1)
+ *   FRICATION  = F(t) 0.3 fricationAmplitude
+ *   y          = (FRICATION preFormantGain) 0.5
+ *   par        = sum_{k = 1 .. 6} (res_pk(y) - y) pa_k, from zero, left to right;   PARALLEL = hold_lerp(par, y, parallelBypass)
+ *   OUTPUT     = ((CASCADE + PARALLEL) outputGain) 4000    (before clipping and truncation)
+ * hold_lerp(from, to, r) is `from` when `to` is NaN, else from + (to - from) r (reference src/utils.h:20-23).  The sample the reference
+ * writes is (int)max(min(OUTPUT, 32000), -32000) with windows.h's min / max, so NaN becomes 32000: in MODE_EXACT that is the batch's
+ * PCM, bit for bit.  The stems are ALWAYS this MODE_EXACT arithmetic: a function of the utterance's frames and seed alone, not of the
+ * batch's mode, layout, planner choices or of whether it has been synthesised.  In MODE_FAST the PCM may differ from the truncated OUTPUT
+ * by that mode's stated tolerance.  Non-finite parameters propagate by IEEE arithmetic, never a fault.
+ * Columns, in any order, repeats allowed:
+ */
+#define SPEECHPLAYER_STEM_VOICE      0
+#define SPEECHPLAYER_STEM_ASPIRATION 1
+#define SPEECHPLAYER_STEM_SOURCE     2
+#define SPEECHPLAYER_STEM_FRICATION  3
+#define SPEECHPLAYER_STEM_CASCADE    4
+#define SPEECHPLAYER_STEM_PARALLEL   5
+#define SPEECHPLAYER_STEM_OUTPUT     6
+#define SPEECHPLAYER_STEM_COLUMNS    7
+/* The stems of chosen utterances into caller-owned device memory on the caller's stream, PLANAR: [row][column][sample] of float64
+ * (format 0: the value itself) or float32 (format 1: rounded to nearest).  utterances, nUtterances, deviceOut and stream as
+ * speechPlayer_batch_exportPcm's (any order, repeats allowed -- a repeated utterance is computed again; NULL: all).
+ *   rowStride   > 0: column q of row i starts at element (i * nColumns + q) * rowStride, and elements past the utterance's end are 0; a
+ *               stride below the longest chosen utterance is refused;
+ *               0: the rows back to back, row i taking nColumns * L_i elements, column after column
+ * Returns the number of elements written (0 writes nothing and needs no buffer), -1 on error.  Event ordering, the sixteen-in-flight
+ * rule and the device-memory checks are exactly those of speechPlayer_batch_exportTracks: valid as soon as the set call has returned
+ * (whichever set call it was), no synthesis launch, no host wait; the next set call waits for the exports in flight.  One lane computes
+ * each row, the rows sorted by length; a 16-byte aligned buffer is written with 16-byte stores wherever a row's segment is aligned.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: no batch, a column outside 0 .. 6, nColumns <= 0, an unknown format, a
+ * negative rowStride or one below the longest chosen utterance, an utterance number outside the batch, an output that is not device
+ * memory of the batch's device, misaligned to the element or too small. */
+long long speechPlayer_batch_exportStems(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
+	const int* columns, int nColumns, void* deviceOut, int format, long long rowStride, void* stream);
+/* Host only, touches no device: the resonator coefficients abc[n][3] = (a, b, c) of n (frequency, bandwidth) pairs at sampleRate, the
+ * product's CPU statement of coefficient_finish(coefficient_parts(frequency, bandwidth), anti, frequency) -- the functions
+ * speechPlayer_frameResponse uses.  anti != 0: the anti-resonator's coefficients (inverted unless the frequency is 0; reference
+ * src/speechWaveGenerator.cpp:112-127).  With |pi bandwidth / sampleRate| <= 700 and |2 pi frequency / sampleRate| <= 1e4 these are
+ * the device's bits (exp and cos of klatt_math.h); outside that range the C library's exp and cos are used, as the device uses its
+ * library's, and the bits may differ.  Returns n, -1 on bad arguments (n < 0, sampleRate <= 0, a NULL array with n > 0). */
+long long speechPlayer_resonatorCoefficients(const double* frequency, const double* bandwidth, long long n, int anti, int sampleRate,
+	double* abc);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

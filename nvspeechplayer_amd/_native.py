@@ -59,6 +59,7 @@ EXPORTS = [
     "speechPlayer_batch_exportAlignment", "speechPlayer_batch_exportUnits", "speechPlayer_batch_unitCounts",
     "speechPlayer_batch_exportSource", "speechPlayer_batch_epochCounts", "speechPlayer_batch_exportEpochs",
     "speechPlayer_frameResponse", "speechPlayer_batch_exportResponse",
+    "speechPlayer_batch_exportStems", "speechPlayer_resonatorCoefficients",
 ]
 
 
@@ -367,6 +368,10 @@ def load():
     L.speechPlayer_frameResponse.argtypes = [vp, i64, i32, vp, i32, vp, i32, i32, vp]
     L.speechPlayer_batch_exportResponse.restype = i64
     L.speechPlayer_batch_exportResponse.argtypes = [vp, vp, i64, vp, i32, vp, i32, i32, i64, i64, vp, i32, i64, vp]
+    L.speechPlayer_batch_exportStems.restype = i64
+    L.speechPlayer_batch_exportStems.argtypes = [vp, vp, i64, vp, i32, vp, i32, i64, vp]
+    L.speechPlayer_resonatorCoefficients.restype = i64
+    L.speechPlayer_resonatorCoefficients.argtypes = [vp, vp, i64, i32, i32, vp]
     _lib = L
     return L
 

@@ -19,6 +19,7 @@
 #include "klatt_align.h"
 #include "klatt_source.h"
 #include "klatt_response.h"
+#include "klatt_stems.h"
 
 #include <algorithm>
 #include <cmath>
@@ -583,6 +584,7 @@ struct Batch {
     long long nNoNasalUtt = 0;             // the utterances among them (the rest: replicas that complete a sparse last wavefront)
     long long totalSamples = 0, poolSamples = 0;
     std::vector<uint32_t> lens;
+    std::vector<uint32_t> uttSeed;     // [nUtt] the utterances' noise seeds (speechPlayer_batch_exportStems)
     std::vector<long long> outStart;   // padded offsets in the device pool
     std::vector<UttResult> results;
     bool resultsFresh = false;
@@ -2583,7 +2585,7 @@ static void batch_clear(Batch* b)
     b->nUtt = 0; b->nFrames = 0; b->nFramesSpoken = 0; b->nLists = 0; b->nSlots = 0; b->nQuiet = 0; b->nNoNasal = 0; b->nNoNasalUtt = 0; b->totalSamples = 0; b->poolSamples = 0;
     b->nTracked = 0; b->nTrackedUtt = 0; b->nJobs = 0; b->trackEntries = 0; b->nDirect = 0; b->nDirectUtt = 0; b->nDirectFrames = 0;
     b->lens.clear(); b->outStart.assign(1, 0); b->results.clear(); b->resultsFresh = false; b->floatFresh = false;
-    b->uttFrameStart.clear(); b->uttFrames.clear(); b->uttList.clear(); b->timelineFresh = false; b->epochFresh = false;
+    b->uttFrameStart.clear(); b->uttFrames.clear(); b->uttList.clear(); b->uttSeed.clear(); b->timelineFresh = false; b->epochFresh = false;
     b->hasLabels = false; b->listUnits.clear();
 }
 
@@ -3403,6 +3405,8 @@ static int batch_set(Batch* b, const SetInput& in)
     b->uttFrameStart.swap(uttFrameStart); b->uttFrames.swap(uttFrames);
     b->uttList.resize((size_t)nU);
     for (long long u = 0; u < nU; ++u) b->uttList[(size_t)u] = (uint32_t)list_of(u);
+    b->uttSeed.resize((size_t)nU);
+    for (long long u = 0; u < nU; ++u) b->uttSeed[(size_t)u] = utt[(size_t)u].seed;
     b->timelineFresh = false; b->epochFresh = false;
     // (what this call left queued on its two streams, if anything: the track exports wait for it on the device)
     HIP_TRY(hipEventRecord(b->setDone, b->stream));
@@ -5259,6 +5263,107 @@ long long speechPlayer_batch_exportResponse(speechPlayer_batch_t batch, const lo
     try {
         return export_response(b, utterances, nUtterances, frequencies, nFrequencies, kinds, nKinds, gain, hop, phase, deviceOut, format, rowStride, stream);
     } catch (const std::exception& e) { set_error("exportResponse: %s", e.what()); return -1; }
+}
+
+// ---- signal stems (klatt_stems.h) -------------------------------------------------------------------------------------------------------
+// Host only, touches no device: (a, b, c) of n resonators as the synthesis kernels compute them from (frequency, bandwidth) --
+// coefficient_finish(coefficient_parts(..)) through the host's fast_exp / fast_cos (klatt_response.h), abc[n][3].
+long long speechPlayer_resonatorCoefficients(const double* frequency, const double* bandwidth, long long n, int anti, int sampleRate, double* abc)
+{
+    begin_call();
+    if (n < 0 || sampleRate <= 0 || (n > 0 && (!frequency || !bandwidth || !abc))) { set_error("resonatorCoefficients: bad arguments"); return -1; }
+    const KernelArgs a = base_args(sampleRate);
+    for (long long i = 0; i < n; ++i) {
+        const Coef k = resonator_coefficients_host(frequency[i], bandwidth[i], anti != 0, a.negPiOverSr, a.twoPiOverSr);
+        abc[3 * i] = k.a; abc[3 * i + 1] = k.b; abc[3 * i + 2] = k.c;
+    }
+    return n;
+}
+
+// The stems of chosen utterances into the caller's device memory on the caller's stream: rows, packing, refusals and event order are
+// speechPlayer_batch_exportTracks' (no hop; the output is planar).  One lane per row, the rows sorted by length (klatt_stems.h); the
+// staging block holds the columns and the rows.
+static long long export_stems(Batch* b, const long long* utterances, long long nUtterances, const int* columns, int nColumns, void* deviceOut,
+                              int format, long long rowStride, void* stream)
+{
+    if (format != 0 && format != 1) { set_error("exportStems: format %d (0 float64, 1 float32)", format); return -1; }
+    if (!columns || nColumns <= 0) { set_error("exportStems: %d columns", nColumns); return -1; }
+    if (rowStride < 0) { set_error("exportStems: rowStride %lld", rowStride); return -1; }
+    StemArgs A;
+    memset(&A, 0, sizeof A);
+    for (int c = 0; c < kStemColumns; ++c) A.slotOf[c] = -1;
+    for (int q = 0; q < nColumns; ++q) {
+        if (columns[q] < 0 || columns[q] >= kStemColumns) { set_error("exportStems: columns[%d] = %d (0 .. %d)", q, columns[q], kStemColumns - 1); return -1; }
+        if (A.slotOf[columns[q]] < 0) A.slotOf[columns[q]] = A.nSlots++;
+    }
+    const long long n = utterances ? nUtterances : b->nUtt;
+    if (n < 0) { set_error("exportStems: %lld utterances", n); return -1; }
+    if (b->nFrames >= 0xFFFFFFFFll) { set_error("exportStems: too many frames"); return -1; }
+    const bool packed = rowStride == 0;
+    std::vector<StemRow> rows((size_t)n);
+    long long maxLen = 0, total = 0;
+    for (long long i = 0; i < n; ++i) {
+        const long long u = utterances ? utterances[i] : i;
+        if (u < 0 || u >= b->nUtt) { set_error("exportStems: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, u, b->nUtt); return -1; }
+        StemRow& r = rows[(size_t)i];
+        r.frame0 = b->uttFrameStart[(size_t)u]; r.nFrames = b->uttFrames[(size_t)u]; r.seed = b->uttSeed[(size_t)u];
+        r.length = b->lens[(size_t)u]; r.pad = 0;
+        r.out = total;      // (samples before the row; elements below)
+        maxLen = std::max<long long>(maxLen, r.length);
+        total += r.length;
+    }
+    if (!packed && rowStride < maxLen) { set_error("exportStems: rowStride %lld is below the longest utterance (%lld)", rowStride, maxLen); return -1; }
+    if (!packed && n > 0 && n > (1ll << 50) / rowStride / nColumns) { set_error("exportStems: %lld rows of %lld samples of %d columns", n, rowStride, nColumns); return -1; }
+    if (packed && total > (1ll << 50) / nColumns) { set_error("exportStems: %lld samples of %d columns", total, nColumns); return -1; }
+    if (n > 0x7FFFFFFFll * kLanes) { set_error("exportStems: %lld rows", n); return -1; }
+    const long long elements = (packed ? total : n * rowStride) * nColumns;
+    if (elements == 0) return 0;
+    const size_t elSize = format ? sizeof(float) : sizeof(double);
+    HIP_TRY(hipSetDevice(b->device));
+    if (!deviceOut) { set_error("exportStems: no output buffer"); return -1; }
+    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportStems")) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (long long i = 0; i < n; ++i) rows[(size_t)i].out = (packed ? rows[(size_t)i].out : i * rowStride) * nColumns;
+    // a wavefront runs as long as its longest lane: the rows longest first (each knows its place in the output)
+    std::stable_sort(rows.begin(), rows.end(), [](const StemRow& x, const StemRow& y) { return x.length > y.length; });
+
+    const size_t colBytes = ((size_t)nColumns * sizeof(int) + 15) / 16 * 16, rowBytes = (size_t)n * sizeof(StemRow), bytes = colBytes + rowBytes;
+    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
+    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
+    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
+    const int el = (int)elSize, T = stem_tile(A.nSlots, el), ldsBytes = stem_lds_bytes(A.nSlots, el);
+    const void* kernel = format ? reinterpret_cast<const void*>(klatt_stems<true, 16>)
+                                : (T == 16 ? reinterpret_cast<const void*>(klatt_stems<false, 16>) : reinterpret_cast<const void*>(klatt_stems<false, 8>));
+    if (ensure_lds_limit(kernel, kStemLdsBudget)) return -1;
+    if (timeline_on_stream(b, st)) return -1;
+    char* h = static_cast<char*>(slot.host.ptr);
+    memcpy(h, columns, (size_t)nColumns * sizeof(int));
+    memcpy(h + colBytes, rows.data(), rowBytes);
+    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
+    A.K = base_args(b->sampleRate);
+    A.K.frames = b->dFrames.ptr; A.K.meta = b->dMeta.ptr;
+    A.rows = reinterpret_cast<const StemRow*>(slot.dev.ptr + colBytes); A.nRows = n;
+    A.columns = reinterpret_cast<const int*>(slot.dev.ptr); A.nColumns = nColumns;
+    A.rowStride = rowStride; A.out = deviceOut;
+    const dim3 grid((unsigned)((n + kLanes - 1) / kLanes));
+    if (format) hipLaunchKernelGGL((klatt_stems<true, 16>), grid, dim3(kLanes), ldsBytes, st, A);
+    else if (T == 16) hipLaunchKernelGGL((klatt_stems<false, 16>), grid, dim3(kLanes), ldsBytes, st, A);
+    else hipLaunchKernelGGL((klatt_stems<false, 8>), grid, dim3(kLanes), ldsBytes, st, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(slot.done, st));
+    slot.used = true;
+    return elements;
+}
+
+long long speechPlayer_batch_exportStems(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const int* columns,
+                                         int nColumns, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("exportStems: no batch"); return -1; }
+    try {
+        return export_stems(b, utterances, nUtterances, columns, nColumns, deviceOut, format, rowStride, stream);
+    } catch (const std::exception& e) { set_error("exportStems: %s", e.what()); return -1; }
 }
 
 }  // extern "C"

@@ -148,13 +148,20 @@ inline RadCos coefficient_parts_host(double f, double bw, double negPiOverSr, do
     return o;
 }
 
+// (a, b, c) of one resonator on the host: coefficient_finish(coefficient_parts(f, bw), anti, f), what speechPlayer_frameResponse and
+// speechPlayer_resonatorCoefficients state
+inline Coef resonator_coefficients_host(double f, double bw, bool anti, double negPiOverSr, double twoPiOverSr)
+{
+    const RadCos p = coefficient_parts_host(f, bw, negPiOverSr, twoPiOverSr);
+    return coefficient_finish(p.rad, p.cs, anti, f);
+}
+
 // the kRespVals values of one frame (47 doubles)
 inline void response_values_host(const double* frame, double negPiOverSr, double twoPiOverSr, double* V)
 {
     for (int r = 0; r < kNumRes; ++r) {
         const double f = frame[kRespResF[r]], bw = frame[kRespResB[r]];
-        const RadCos p = coefficient_parts_host(f, bw, negPiOverSr, twoPiOverSr);
-        const Coef k = coefficient_finish(p.rad, p.cs, r == 0, f);
+        const Coef k = resonator_coefficients_host(f, bw, r == 0, negPiOverSr, twoPiOverSr);
         V[3 * r] = k.a; V[3 * r + 1] = k.b; V[3 * r + 2] = k.c;
     }
     for (int g = 0; g < kRespGains; ++g) V[kRespCaNP + g] = frame[kRespGainParamHost[g]];

@@ -545,6 +545,52 @@ def frameResponse(frames, sampleRate, frequencies, kinds=("cascade_db", "paralle
     return out
 
 
+STEM_COLUMNS = ["voice", "aspiration", "source", "frication", "cascade", "parallel", "output"]      # SPEECHPLAYER_STEM_*
+
+
+def check_stem_request(columns, dtype):
+    """The argument checks of BatchPlayer.stemTensor that need no GPU: `columns` a non-empty sequence of column numbers 0 .. 6 or names
+    (STEM_COLUMNS; a single one stands for one column), dtype None / torch.float32 / torch.float64.  Raises KeyError, ValueError or
+    TypeError as check_source_request does.  Returns (columns as an int32 array, the export format: 0 float64, 1 float32)."""
+    import torch
+    if isinstance(columns, (str, int, np.integer)):
+        columns = [columns]
+    cols = []
+    for c in columns:
+        if isinstance(c, str):
+            if c not in STEM_COLUMNS:
+                raise KeyError("stemTensor: no column named %r (%s)" % (c, ", ".join(STEM_COLUMNS)))
+            c = STEM_COLUMNS.index(c)
+        c = int(c)
+        if not 0 <= c < len(STEM_COLUMNS):
+            raise ValueError("stemTensor: column %d is not in 0 .. %d" % (c, len(STEM_COLUMNS) - 1))
+        cols.append(c)
+    if not cols:
+        raise ValueError("stemTensor: no columns")
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError("stemTensor: dtype must be torch.float32 or torch.float64, not %s" % dtype)
+    return np.asarray(cols, dtype=np.int32), 1 if dtype == torch.float32 else 0
+
+
+def resonatorCoefficients(f, bw, sampleRate, anti=False):
+    """The resonator coefficients (a, b, c) the synthesiser computes from frequencies `f` and bandwidths `bw` (Hz; scalars or arrays of
+    one length) at sampleRate, on the host (speechPlayer_resonatorCoefficients; no GPU): -> float64 [n, 3].  anti: the anti-resonator's
+    (inverted unless the frequency is 0).  Inside the range the header documents these are the device's bits."""
+    fr = np.ascontiguousarray(np.atleast_1d(np.asarray(f, dtype=np.float64)).reshape(-1))
+    bws = np.ascontiguousarray(np.atleast_1d(np.asarray(bw, dtype=np.float64)).reshape(-1))
+    if len(fr) != len(bws):
+        raise ValueError("resonatorCoefficients: %d frequencies and %d bandwidths" % (len(fr), len(bws)))
+    if int(sampleRate) <= 0:
+        raise ValueError("resonatorCoefficients: sampleRate must be positive")
+    out = np.zeros((len(fr), 3), np.float64)
+    got = _native.load().speechPlayer_resonatorCoefficients(fr.ctypes.data, bws.ctypes.data, len(fr), 1 if anti else 0, int(sampleRate), out.ctypes.data)
+    if got < 0:
+        raise RuntimeError(_native.last_error())
+    assert got == len(fr), (got, len(fr))
+    return out
+
+
 def check_option_value(name, value):
     """speechPlayer_batch_setOption takes a C int: a value outside its range would wrap without a word (2 ** 40 arrives as 0).  Returns
     int(value), or raises ValueError."""
@@ -883,6 +929,37 @@ class BatchPlayer(object):
                                                                           out.data_ptr(), fmt, stride, stream))
             assert got == out.numel(), (got, out.numel())
         return out, torch.from_numpy(steps if padded else offsets)
+
+    def stemTensor(self, columns, utterances=None, dtype=None, padded=True):
+        """The signal stems as a torch tensor on the batch's device (speechPlayer_batch_exportStems), filled on torch's current stream
+        without a host wait and without a synthesis launch: -> (stems, lengths).  columns by number or by name (STEM_COLUMNS): "voice"
+        (the glottal wave with its turbulence), "aspiration", "source" (their sum: the excitation of the cascade), "frication" (the
+        excitation of the parallel bank), "cascade" and "parallel" (the outputs of the two filter branches) and "output" (the mixed sample
+        before it is clipped and truncated: int16 PCM is trunc(clip(output))) -- the values behind the MODE_EXACT PCM, whatever the batch's
+        mode.  utterances: indices in any order, repeats allowed (None: all, in order); dtype torch.float32 (default) or torch.float64
+        (the values themselves).  padded: stems is [n, len(columns), longest], zero past each utterance's end, and lengths the n
+        lengths; else stems is flat, row i holding its columns one after the other, each of its utterance's length, and lengths the
+        n + 1 element offsets (int64 CPU tensors)."""
+        import torch
+        cols, fmt = check_stem_request(columns, dtype)
+        sel, n, idx = self._selection("stemTensor", utterances)
+        lens = self._lengths()[idx].astype(np.int64)
+        dev = self.device
+        tdtype = torch.float32 if fmt else torch.float64
+        if padded:
+            width = int(lens.max()) if n else 0
+            out = torch.empty((n, len(cols), width), dtype=tdtype, device="cuda:%d" % dev)
+            stride = width
+        else:
+            offsets = np.concatenate([[0], np.cumsum(lens * len(cols))]).astype(np.int64)
+            out = torch.empty(int(offsets[-1]), dtype=tdtype, device="cuda:%d" % dev)
+            stride = 0
+        if out.numel():
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            got = self._check(self._dll.speechPlayer_batch_exportStems(self._h, None if sel is None else sel.ctypes.data, n, cols.ctypes.data, len(cols),
+                                                                       out.data_ptr(), fmt, stride, stream))
+            assert got == out.numel(), (got, out.numel())
+        return out, torch.from_numpy(lens if padded else offsets)
 
     def epochCounts(self, utterances=None):
         """Glottal cycles begun (pitch marks) in each of the chosen utterances (speechPlayer_batch_epochCounts): an int64 array.  The first
