@@ -72,19 +72,7 @@ __global__ void __launch_bounds__(256) klatt_align_dense(const TimelineReq* __re
         const long long e0 = t * EL;
         long long g, r, j;
         int q;
-        if (nCols == 1) { g = e0; q = 0; }
-        else if ((unsigned long long)e0 >> 32) { g = e0 / nCols; q = (int)(e0 - g * nCols); }
-        else { const uint32_t g32 = (uint32_t)e0 / (uint32_t)nCols; g = g32; q = (int)((uint32_t)e0 - g32 * (uint32_t)nCols); }
-        if (rowStride > 0) {
-            if (((unsigned long long)g | (unsigned long long)rowStride) >> 32) r = g / rowStride;
-            else r = (uint32_t)g / (uint32_t)rowStride;
-            j = g - r * rowStride;
-        } else {
-            const long long c = g >> kTimelineChunkLog2;
-            long long lo = chunkRow[c], hi = chunkRow[c + 1] + 1;      // the last row whose start is <= g
-            while (hi - lo > 1) { const long long mid = (lo + hi) >> 1; if (stepStart[mid] <= g) lo = mid; else hi = mid; }
-            r = lo; j = g - stepStart[r];
-        }
+        dense_locate(e0, nCols, rowStride, stepStart, chunkRow, g, q, r, j);
         AlignRow row = rows[r];
         // the request of the step in hand, kept while the following elements stay inside it
         long long k = -1, kFirst = 0, kNext = 0, uFirst = 0, uNext = 0;
@@ -130,15 +118,7 @@ __global__ void __launch_bounds__(256) klatt_align_dense(const TimelineReq* __re
             }
             v[i] = x;
         }
-        if (I32) {
-            int* o = static_cast<int*>(outp) + e0;
-            if (vecStore && e0 + EL <= total) *reinterpret_cast<int4*>(o) = make_int4((int)v[0], (int)v[1], (int)v[EL - 2], (int)v[EL - 1]);
-            else for (int i = 0; i < EL && e0 + i < total; ++i) o[i] = (int)v[i];
-        } else {
-            long long* o = static_cast<long long*>(outp) + e0;
-            if (vecStore && e0 + EL <= total) *reinterpret_cast<longlong2*>(o) = make_longlong2(v[0], v[1]);
-            else for (int i = 0; i < EL && e0 + i < total; ++i) o[i] = v[i];
-        }
+        store16<typename std::conditional<I32, int, long long>::type>(outp, e0, total, vecStore, v);
     }
 }
 
@@ -154,11 +134,7 @@ __global__ void __launch_bounds__(256) klatt_align_units(const TimelineReq* __re
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
         long long r, i;
         if (rowStride > 0) { r = t / rowStride; i = t - r * rowStride; }
-        else {
-            long long lo = 0, hi = nRows;                               // the last row whose start is <= t
-            while (hi - lo > 1) { const long long mid = (lo + hi) >> 1; if (entryStart[mid] <= t) lo = mid; else hi = mid; }
-            r = lo; i = t - entryStart[r];
-        }
+        else packed_locate(t, entryStart, nRows, r, i);
         const AlignRow row = rows[r];
         long long* __restrict__ o = out + t * kUnitColumns;
         if (i >= row.count) {

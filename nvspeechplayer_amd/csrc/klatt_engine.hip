@@ -20,6 +20,7 @@
 #include "klatt_source.h"
 #include "klatt_response.h"
 #include "klatt_stems.h"
+#include "klatt_export.h"
 
 #include <algorithm>
 #include <cmath>
@@ -633,36 +634,38 @@ struct Batch {
     static constexpr int kExportSlots = 16;
     ExportSlot exportSlot[kExportSlots];
     unsigned exportNext = 0;
-    // speechPlayer_batch_exportTracks (klatt_timeline.h) reads the frames, the meta words and the list table of the batch AS SET, on the
-    // caller's stream: behind setDone / setCopied (recorded by the set call on its two streams), and ahead of the NEXT set call, which
-    // waits for the slots' last exports before it overwrites what they read (settle_track_exports).  The per-request records are built
-    // once per set call, by the first export (timelineReady: recorded behind klatt_timeline_requests on that export's stream); the
-    // voicePitch table is shared by the exports that ask for column 0, which follow one another on the device (pitchDone).
+    // The exports of the batch AS SET (tracks, alignment and units, source and epochs, response, stems) share one path: "the export
+    // path" below settle_track_exports says what they read, how they are ordered and what each of these members is for.
+    struct SharedTable {                       // the order among the exports that share a table: each follows the one before on the device
+        hipEvent_t done = nullptr;
+        bool used = false;
+        int wait(hipStream_t st) { if (used) HIP_TRY(hipStreamWaitEvent(st, done, 0)); return 0; }      // (whichever stream it ran on)
+        int mark(hipStream_t st) { HIP_TRY(hipEventRecord(done, st)); used = true; return 0; }
+    };
     std::vector<uint32_t> uttList;             // [nUtt] the list an utterance speaks
     DeviceBuffer<long long> dListStart;        // [nLists + 1]
-    DeviceBuffer<TimelineReq> dTimeline;       // [nFrames]
-    DeviceBuffer<double> dPitch;
-    hipEvent_t setDone = nullptr, setCopied = nullptr, timelineReady = nullptr, pitchDone = nullptr;
-    bool timelineFresh = false, pitchUsed = false;
-    long long pitchBudgetMB = 256;             // option "pitch_table_mb": an export whose voicePitch table would be larger proceeds in pieces
+    DeviceBuffer<TimelineReq> dTimeline;       // [nFrames] the per-request records, built once per set call by the first export
+    hipEvent_t setDone = nullptr, setCopied = nullptr, timelineReady = nullptr;
+    bool timelineFresh = false;
     ExportSlot trackSlot[kExportSlots];
     unsigned trackNext = 0;
-    // speechPlayer_batch_exportAlignment / _exportUnits (klatt_align.h): the labels of a batch set with labels (one per list frame) and
-    // unitFirst[] (list l's entries from listStart[l] + l), uploaded on the copy stream by the set call -- ahead of setCopied; their
-    // exports share the track exports' slots and order.
+    DeviceBuffer<double> dPitch;               // [slot][step] voicePitch of the lists a track export with column 0 speaks
+    SharedTable pitchOrder;
+    long long pitchBudgetMB = 256;             // option "pitch_table_mb": an export whose voicePitch table would be larger proceeds in pieces
+    // klatt_align.h: the labels of a batch set with labels (one per list frame) and unitFirst[] (list l's entries from
+    // listStart[l] + l), uploaded on the copy stream by the set call -- ahead of setCopied
     DeviceBuffer<FrameLabel> dLabels;
     DeviceBuffer<uint32_t> dUnitFirst;
     std::vector<uint32_t> listUnits;           // [nLists] units of a list
     bool hasLabels = false;
-    // speechPlayer_batch_exportSource / _epochCounts / _exportEpochs (klatt_source.h): the walks read what the track exports read and share
-    // their slots and order.  The step table and the epoch table are shared by the exports that use them, which follow one another on the
-    // device (sourceDone); the per-list epoch counts are those of the batch as set, kept until the next set call.
+    // klatt_source.h: the step table and the epoch table follow one order; the per-list epoch counts are those of the batch as set,
+    // kept until the next set call
     DeviceBuffer<double> dSource;              // [slot][step][6]
     DeviceBuffer<double> dEpochs;              // [epoch][4], list after list
+    SharedTable sourceOrder;
     DeviceBuffer<long long> dEpochCount;       // [nLists] what the counting walk leaves
     std::vector<long long> epochCount;         // [nLists]
-    hipEvent_t sourceDone = nullptr;
-    bool sourceUsed = false, epochFresh = false;
+    bool epochFresh = false;
     long long sourceBudgetMB = 256;            // option "source_table_mb": an export whose step table would be larger proceeds in pieces
     long long sourceLaneLists = 12288;         // option "source_lane_lists": a walk over this many lists or more runs one lane per list
 };
@@ -693,6 +696,137 @@ int settle_track_exports(Batch* b, bool onHost)
     }
     return 0;
 }
+
+// ---- the export path ------------------------------------------------------------------------------------------------------------------
+// Every export of the batch AS SET -- tracks, alignment and units, source and epochs, response, stems -- fills the caller's device
+// memory on the CALLER's stream from what a set call leaves resident: the frames, the meta words, the list table and (a batch with
+// labels) the labels.  It is ordered by events only: behind the set call's own device work (setDone, setCopied: recorded by the set
+// call on its two streams), behind the per-request records (built once per set call, by the first export: timelineReady, recorded
+// behind klatt_timeline_requests on that export's stream) and ahead of the NEXT set call, which waits for the slots' last exports
+// before it overwrites what they read (settle_track_exports).  What its kernels need beside the batch -- columns, rows, row tables,
+// list descriptors -- crosses the link as one staging block (klatt_export.h) through one of kExportSlots page-locked / device buffer
+// pairs; nothing waits on the host unless all slots hold exports in flight or a buffer of the batch must grow.  An entry point is
+//     batch_entry        the C-ABI shell: begin_call, the "no batch" refusal, no exception leaves
+//     (its own argument refusals)
+//     export_selection   the chosen utterances: the range refusal and one row per choice
+//     export_elements    the extent refusals; zero elements return 0 here, before the output is looked at
+//     export_output      the batch's device and the caller's output on it
+//     ExportStage        begin() ... the launches ... finish()
+// in this order, which is the order of its refusals: those of the arguments come before anything touches the device.
+
+// A table the exports share grows: the exports in flight may read it, so the host waits for them first.
+template <typename T>
+int grow_table(Batch* b, DeviceBuffer<T>& buf, size_t n)
+{
+    if (n > buf.cap && settle_track_exports(b, true)) return -1;
+    return buf.reserve(std::max<size_t>(n, 1));
+}
+
+// The per-request records behind the set call on stream `st`: built by the first export after a set call, waited for by the others.
+int timeline_on_stream(Batch* b, hipStream_t st)
+{
+    if (b->timelineFresh) { HIP_TRY(hipStreamWaitEvent(st, b->timelineReady, 0)); return 0; }
+    if (grow_table(b, b->dTimeline, (size_t)b->nFrames)) return -1;
+    HIP_TRY(hipStreamWaitEvent(st, b->setDone, 0));
+    HIP_TRY(hipStreamWaitEvent(st, b->setCopied, 0));
+    const unsigned grid = (unsigned)std::min<long long>((b->nLists + 255) / 256, 4ll * b->cus);
+    hipLaunchKernelGGL(klatt_timeline_requests, dim3(std::max(grid, 1u)), dim3(256), 0, st, b->dMeta.ptr, b->dListStart.ptr, b->nLists, b->dTimeline.ptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(b->timelineReady, st));
+    b->timelineFresh = true;
+    return 0;
+}
+
+template <class Fn>
+long long batch_entry(const char* what, speechPlayer_batch_t batch, Fn fn)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("%s: no batch", what); return -1; }
+    try {
+        return fn(b);
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
+// The choice of an export: utterances[0 .. nUtterances) (null: every utterance, in order), each an utterance of the batch.  Its
+// number, or -1 with the message set.  frameLimit: the export's kernels index the frames by 32 bits.
+long long check_selection(Batch* b, const char* what, const long long* utterances, long long nUtterances, bool frameLimit)
+{
+    const long long n = utterances ? nUtterances : b->nUtt;
+    if (n < 0) { set_error("%s: %lld utterances", what, n); return -1; }
+    if (frameLimit && b->nFrames >= 0xFFFFFFFFll) { set_error("%s: too many frames", what); return -1; }
+    for (long long i = 0; utterances && i < n; ++i)
+        if (utterances[i] < 0 || utterances[i] >= b->nUtt) { set_error("%s: utterances[%lld] = %lld is not an utterance of the batch (%lld)", what, i, utterances[i], b->nUtt); return -1; }
+    return n;
+}
+
+// The rows of an export, one per chosen utterance in the order chosen: perRow(i, u, before) makes row i from utterance u and answers
+// its count of entries (negative: it has set the message); `before` is the sum of the counts of rows 0 .. i - 1.
+struct ExportSelection {
+    long long n = 0, most = 0, total = 0;
+    std::vector<long long> counts;
+};
+template <class PerRow>
+int export_selection(Batch* b, const char* what, const long long* utterances, long long nUtterances, bool frameLimit, ExportSelection& s, PerRow perRow)
+{
+    s.n = check_selection(b, what, utterances, nUtterances, frameLimit);
+    if (s.n < 0) return -1;
+    s.counts.resize((size_t)s.n);
+    for (long long i = 0; i < s.n; ++i) {
+        const long long count = perRow(i, utterances ? utterances[i] : i, s.total);
+        if (count < 0) return -1;
+        s.counts[(size_t)i] = count;
+        s.most = std::max(s.most, count);
+        s.total += count;
+    }
+    return 0;
+}
+
+// The elements of the export (klatt_export.h: export_extent), or -1 with the message set.
+long long export_elements(const char* what, const ExportNouns& nouns, const ExportSelection& s, long long rowStride, long long perEntry,
+                          long long capacity = kNoCapacity)
+{
+    std::string why;
+    const long long elements = export_extent(nouns, s.most, s.total, s.n, rowStride, perEntry, capacity, why);
+    if (elements < 0) set_error("%s: %s", what, why.c_str());
+    return elements;
+}
+
+// One export's passage through a slot.  begin(): the slot (the host waits only if its last export is still in flight), the caller's
+// tables (`grow`) -- every allocation first: once a kernel is queued the slot's event must come to stand behind it -- then the
+// per-request records, the shared table's previous export, and the block's upload on the stream.  finish(): behind the launches.
+struct ExportStage {
+    Batch* b;
+    hipStream_t st;
+    const StageBlock& block;
+    Batch::SharedTable* table;      // the order the export's shared table keeps (null: it uses none)
+    Batch::ExportSlot* slot = nullptr;
+    ExportStage(Batch* b, hipStream_t st, const StageBlock& block, Batch::SharedTable* table = nullptr) : b(b), st(st), block(block), table(table) {}
+    template <class Grow>
+    int begin(Grow grow)
+    {
+        slot = &b->trackSlot[b->trackNext++ % Batch::kExportSlots];
+        if (slot->used) { HIP_TRY(hipEventSynchronize(slot->done)); slot->used = false; }
+        if (slot->host.ensure(block.bytes()) || slot->dev.reserve(block.bytes())) return -1;
+        if (grow()) return -1;
+        if (timeline_on_stream(b, st)) return -1;
+        if (table && table->wait(st)) return -1;
+        block.copy_to(slot->host.ptr);
+        HIP_TRY(hipMemcpyAsync(slot->dev.ptr, slot->host.ptr, block.bytes(), hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    int begin() { return begin([] { return 0; }); }
+    template <class T> const T* device(int section) const { return block.device<T>(section, slot->dev.ptr); }
+    int finish()
+    {
+        HIP_TRY(hipEventRecord(slot->done, st));
+        slot->used = true;
+        return table ? table->mark(st) : 0;
+    }
+};
+// (the staging block's sections start on 16-byte boundaries: no kernel takes two of them for one array)
+static_assert(sizeof(TimelineRow) % 8 == 0 && sizeof(AlignRow) % 8 == 0 && sizeof(EpochRow) % 8 == 0 && sizeof(SourceList) % 8 == 0 &&
+              sizeof(TimelineList) % 8 == 0 && sizeof(StemRow) % 8 == 0 && sizeof(ResponseGroup) % 8 == 0, "rows are arrays of 8-byte words");
 
 // How many of the quiet, nasal-free utterances (the head of `order`) the lane-pipelined kernel takes.
 // layout 2 forces it; "auto" takes it where it measured faster than the stage-parallel kernel.
@@ -2468,7 +2602,7 @@ speechPlayer_batch_t speechPlayer_batch_create(int sampleRate, int device)
               hipEventCreateWithFlags(&b->pcmReady, hipEventDisableTiming) == hipSuccess;
     for (auto& s : b->exportSlot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
     for (auto& s : b->trackSlot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
-    for (hipEvent_t* e : {&b->setDone, &b->setCopied, &b->timelineReady, &b->pitchDone, &b->sourceDone}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    for (hipEvent_t* e : {&b->setDone, &b->setCopied, &b->timelineReady, &b->pitchOrder.done, &b->sourceOrder.done}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     { const char* e = getenv("SPEECHPLAYER_TRACKS"); if (e) b->tracks = atoi(e) ? 1 : 0; }
     { const char* e = getenv("SPEECHPLAYER_DIRECT"); if (e) b->direct = std::min(2, std::max(0, atoi(e))); }
     { const char* e = getenv("SPEECHPLAYER_DIRECT_LEAN"); if (e) b->directLean = std::min(1, std::max(-1, atoi(e))); }
@@ -2499,7 +2633,7 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch)
         if (s.done) (void)hipEventDestroy(s.done);
         s.host.release(); s.dev.release();
     }
-    for (hipEvent_t e : {b->setDone, b->setCopied, b->timelineReady, b->pitchDone, b->sourceDone}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {b->setDone, b->setCopied, b->timelineReady, b->pitchOrder.done, b->sourceOrder.done}) if (e) (void)hipEventDestroy(e);
     b->dListStart.release(); b->dTimeline.release(); b->dPitch.release(); b->dLabels.release(); b->dUnitFirst.release();
     b->dSource.release(); b->dEpochs.release(); b->dEpochCount.release();
     if (b->inputReady) (void)hipEventDestroy(b->inputReady);
@@ -3749,70 +3883,51 @@ long long speechPlayer_batch_exportPcm(speechPlayer_batch_t batch, const long lo
 {
     begin_call();
     if (refuse_timing_only("speechPlayer_batch_exportPcm")) return -1;
-    Batch* b = static_cast<Batch*>(batch);
-    if (!b) { set_error("exportPcm: no batch"); return -1; }
-    if (format != 0 && format != 1) { set_error("exportPcm: format %d (0 int16, 1 float32)", format); return -1; }
-    if (rowStride < 0) { set_error("exportPcm: rowStride %lld", rowStride); return -1; }
-    const long long n = utterances ? nUtterances : b->nUtt;
-    if (n < 0) { set_error("exportPcm: %lld utterances", n); return -1; }
-    const bool packed = rowStride == 0;
-    std::vector<ExportRow> rows((size_t)n);
-    std::vector<long long> dst(packed ? (size_t)n + 1 : 0), chunkRow;
-    long long maxLen = 0, total = 0;
-    for (long long i = 0; i < n; ++i) {
-        const long long u = utterances ? utterances[i] : i;
-        if (u < 0 || u >= b->nUtt) { set_error("exportPcm: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, u, b->nUtt); return -1; }
-        rows[(size_t)i] = ExportRow{b->outStart[(size_t)u], (long long)b->lens[(size_t)u]};
-        if (packed) dst[(size_t)i] = total;
-        total += b->lens[(size_t)u];
-        maxLen = std::max<long long>(maxLen, b->lens[(size_t)u]);
-    }
-    if (packed) {
-        dst[(size_t)n] = total;
-        const long long nChunks = (total >> kExportChunkLog2) + 1;
-        chunkRow.resize((size_t)nChunks + 1);
-        long long r = 0;
-        for (long long c = 0; c < nChunks; ++c) {
-            while (r + 1 < n && dst[(size_t)r + 1] <= (c << kExportChunkLog2)) ++r;
-            chunkRow[(size_t)c] = r;
-        }
-        chunkRow[(size_t)nChunks] = std::max<long long>(n - 1, 0);
-    }
-    if (!packed && rowStride < maxLen) { set_error("exportPcm: rowStride %lld is below the longest chosen utterance (%lld samples)", rowStride, maxLen); return -1; }
-    if (!packed && n > (1ll << 50) / rowStride) { set_error("exportPcm: %lld rows of %lld elements", n, rowStride); return -1; }
-    const long long elements = packed ? total : n * rowStride;
-    if (elements == 0) return 0;
-    if (!b->launched) { set_error("exportPcm: the batch has not been synthesised since it was set"); return -1; }
-    const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
-    HIP_TRY(hipSetDevice(b->device));
-    if (!deviceOut) { set_error("exportPcm: no output buffer"); return -1; }
-    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportPcm")) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Batch::ExportSlot& slot = b->exportSlot[b->exportNext++ % Batch::kExportSlots];
-    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
-    const size_t rowBytes = (size_t)n * sizeof(ExportRow), dstBytes = dst.size() * sizeof(long long);
-    const size_t bytes = rowBytes + dstBytes + chunkRow.size() * sizeof(long long);
-    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
-    memcpy(slot.host.ptr, rows.data(), rowBytes);
-    if (packed) {
-        memcpy(static_cast<char*>(slot.host.ptr) + rowBytes, dst.data(), dstBytes);
-        memcpy(static_cast<char*>(slot.host.ptr) + rowBytes + dstBytes, chunkRow.data(), chunkRow.size() * sizeof(long long));
-    }
-    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(b->pcmReady, b->stream));
-    HIP_TRY(hipStreamWaitEvent(st, b->pcmReady, 0));
-    const ExportRow* dRows = reinterpret_cast<const ExportRow*>(slot.dev.ptr);
-    const long long* dDst = packed ? reinterpret_cast<const long long*>(slot.dev.ptr + rowBytes) : nullptr;
-    const long long* dChunk = packed ? reinterpret_cast<const long long*>(slot.dev.ptr + rowBytes + dstBytes) : nullptr;
-    const long long n8 = (elements + 7) / 8;
-    const unsigned grid = (unsigned)std::min<long long>((n8 + 255) / 256, 8ll * b->cus);
-    const int vec = reinterpret_cast<uintptr_t>(deviceOut) % 16 == 0;
-    if (format) hipLaunchKernelGGL(pcm_export<true>, dim3(grid), dim3(256), 0, st, b->dPcm.ptr, deviceOut, dRows, dDst, dChunk, n, rowStride, elements, vec);
-    else hipLaunchKernelGGL(pcm_export<false>, dim3(grid), dim3(256), 0, st, b->dPcm.ptr, deviceOut, dRows, dDst, dChunk, n, rowStride, elements, vec);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(slot.done, st));
-    slot.used = true;
-    return elements;
+    return batch_entry("exportPcm", batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("exportPcm: format %d (0 int16, 1 float32)", format); return -1; }
+        if (rowStride < 0) { set_error("exportPcm: rowStride %lld", rowStride); return -1; }
+        const bool packed = rowStride == 0;
+        std::vector<ExportRow> rows;
+        ExportSelection s;
+        if (export_selection(b, "exportPcm", utterances, nUtterances, false, s, [&](long long, long long u, long long) {
+                rows.push_back(ExportRow{b->outStart[(size_t)u], (long long)b->lens[(size_t)u]});
+                return rows.back().len;
+            })) return -1;
+        const long long n = s.n, maxLen = s.most, total = s.total;
+        std::vector<long long> words;      // the rows' starts in the output and the chunks' first rows (packed)
+        const RowTable table = packed ? packed_row_table(s.counts.data(), 0, n, kExportChunkLog2, words) : RowTable{0, 0};
+        if (!packed && rowStride < maxLen) { set_error("exportPcm: rowStride %lld is below the longest chosen utterance (%lld samples)", rowStride, maxLen); return -1; }
+        if (!packed && n > (1ll << 50) / rowStride) { set_error("exportPcm: %lld rows of %lld elements", n, rowStride); return -1; }
+        const long long elements = packed ? total : n * rowStride;
+        if (elements == 0) return 0;
+        if (!b->launched) { set_error("exportPcm: the batch has not been synthesised since it was set"); return -1; }
+        const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
+        HIP_TRY(hipSetDevice(b->device));
+        if (!deviceOut) { set_error("exportPcm: no output buffer"); return -1; }
+        if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportPcm")) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        Batch::ExportSlot& slot = b->exportSlot[b->exportNext++ % Batch::kExportSlots];
+        if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words);
+        if (slot.host.ensure(block.bytes()) || slot.dev.reserve(block.bytes())) return -1;
+        block.copy_to(slot.host.ptr);
+        HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, block.bytes(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(b->pcmReady, b->stream));
+        HIP_TRY(hipStreamWaitEvent(st, b->pcmReady, 0));
+        const ExportRow* dRows = block.device<ExportRow>(rowsAt, slot.dev.ptr);
+        const long long* dDst = packed ? block.device<long long>(wordsAt, slot.dev.ptr) + table.startOff : nullptr;
+        const long long* dChunk = packed ? block.device<long long>(wordsAt, slot.dev.ptr) + table.chunkOff : nullptr;
+        const long long n8 = (elements + 7) / 8;
+        const unsigned grid = (unsigned)std::min<long long>((n8 + 255) / 256, 8ll * b->cus);
+        const int vec = reinterpret_cast<uintptr_t>(deviceOut) % 16 == 0;
+        if (format) hipLaunchKernelGGL(pcm_export<true>, dim3(grid), dim3(256), 0, st, b->dPcm.ptr, deviceOut, dRows, dDst, dChunk, n, rowStride, elements, vec);
+        else hipLaunchKernelGGL(pcm_export<false>, dim3(grid), dim3(256), 0, st, b->dPcm.ptr, deviceOut, dRows, dDst, dChunk, n, rowStride, elements, vec);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(slot.done, st));
+        slot.used = true;
+        return elements;
+    });
 }
 
 int speechPlayer_batch_time(speechPlayer_batch_t batch, int launches, float* msPerLaunch)
@@ -4436,369 +4551,226 @@ long long speechPlayer_batch_timeline(speechPlayer_batch_t batch, long long u, l
     return n;
 }
 
-// The per-request records behind the set call on stream `st`: built by the first export after a set call, waited for by the others.
-static int timeline_on_stream(Batch* b, hipStream_t st)
+// ---- the exports of a batch as set ("the export path", above) ----------------------------------------------------------------------
+// The batch's device, and the caller's output on it (zero elements have been answered before).
+static int export_output(Batch* b, const char* what, void* deviceOut, long long elements, size_t elSize)
 {
-    if (b->timelineFresh) { HIP_TRY(hipStreamWaitEvent(st, b->timelineReady, 0)); return 0; }
-    if ((size_t)b->nFrames > b->dTimeline.cap && settle_track_exports(b, true)) return -1;
-    if (b->dTimeline.reserve(std::max<size_t>((size_t)b->nFrames, 1))) return -1;
-    HIP_TRY(hipStreamWaitEvent(st, b->setDone, 0));
-    HIP_TRY(hipStreamWaitEvent(st, b->setCopied, 0));
-    const unsigned grid = (unsigned)std::min<long long>((b->nLists + 255) / 256, 4ll * b->cus);
-    hipLaunchKernelGGL(klatt_timeline_requests, dim3(std::max(grid, 1u)), dim3(256), 0, st, b->dMeta.ptr, b->dListStart.ptr, b->nLists, b->dTimeline.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(b->timelineReady, st));
-    b->timelineFresh = true;
+    HIP_TRY(hipSetDevice(b->device));
+    if (!deviceOut) { set_error("%s: no output buffer", what); return -1; }
+    return device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, what) ? 0 : -1;
+}
+
+// The arguments of the exports by step: hop and phase, and no utterance is longer than 2^32 samples: a larger hop or phase means the same.
+static int step_request(const char* what, long long& hop, long long& phase, long long rowStride)
+{
+    if (hop <= 0 || phase < 0) { set_error("%s: hop %lld, phase %lld", what, hop, phase); return -1; }
+    if (rowStride < 0) { set_error("%s: rowStride %lld", what, rowStride); return -1; }
+    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
     return 0;
 }
 
-// The tracks of chosen utterances into the caller's device memory on the caller's stream (klatt_timeline.h), ordered by events only:
-// behind the set call's own device work (setDone, setCopied), behind the per-request records (built by the first export after a set call)
-// and ahead of the next set call (settle_track_exports).  Rows, columns and list descriptors of all pieces are staged through one
-// page-locked slot; nothing waits on the host unless all slots hold exports in flight or a buffer of the batch must grow.
+static int column_range(const char* what, const int* columns, int nColumns, int known)
+{
+    for (int q = 0; q < nColumns; ++q)
+        if (columns[q] < 0 || columns[q] >= known) { set_error("%s: columns[%d] = %d (0 .. %d)", what, q, columns[q], known - 1); return -1; }
+    return 0;
+}
+
+// One row per chosen utterance for klatt_timeline_dense / klatt_source_dense, its steps counted.
+static int step_rows(Batch* b, const char* what, const long long* utterances, long long nUtterances, long long hop, long long phase,
+                     ExportSelection& s, std::vector<TimelineRow>& rows)
+{
+    return export_selection(b, what, utterances, nUtterances, true, s, [&](long long, long long u, long long) {
+        rows.push_back(TimelineRow{b->uttFrameStart[(size_t)u], b->uttFrames[(size_t)u], 0, align_steps_below(b->lens[(size_t)u], hop, phase)});
+        return rows.back().steps;
+    });
+}
+
+// A dense kernel's launch over `elements` elements of elSize bytes from element `at` of the output: a lane per 16 bytes; the row table
+// `t` of the packed form (null: padded) within the staged words.
+struct DenseLaunch {
+    char* out;
+    unsigned grid;
+    int vec;
+    const long long *start, *chunk;
+};
+static DenseLaunch dense_launch(const Batch* b, void* deviceOut, long long at, long long elements, size_t elSize, const long long* dWords, const RowTable* t)
+{
+    DenseLaunch d;
+    d.out = static_cast<char*>(deviceOut) + (size_t)at * elSize;
+    const long long nLane = (elements * (long long)elSize + 15) / 16;
+    d.grid = (unsigned)std::min<long long>((nLane + 255) / 256, 8ll * b->cus);
+    d.vec = reinterpret_cast<uintptr_t>(d.out) % 16 == 0;
+    d.start = t ? dWords + t->startOff : nullptr;
+    d.chunk = t ? dWords + t->chunkOff : nullptr;
+    return d;
+}
+
+// The tracks of chosen utterances (klatt_timeline.h).  An export that asks for column 0 walks the distinct lists its rows speak
+// (klatt_timeline_pitch) into the voicePitch table, in pieces of rows whose lists fit option "pitch_table_mb"; one piece otherwise.
+// The staging block: columns | rows | per piece: step starts and chunk rows (packed) | lists.
 long long speechPlayer_batch_exportTracks(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const int* columns,
                                           int nColumns, long long hop, long long phase, void* deviceOut, int format, long long rowStride, void* stream)
 {
-    begin_call();
-    Batch* b = static_cast<Batch*>(batch);
-    if (!b) { set_error("exportTracks: no batch"); return -1; }
-    if (format != 0 && format != 1) { set_error("exportTracks: format %d (0 float64, 1 float32)", format); return -1; }
-    if (!columns || nColumns <= 0) { set_error("exportTracks: %d columns", nColumns); return -1; }
-    if (hop <= 0 || phase < 0) { set_error("exportTracks: hop %lld, phase %lld", hop, phase); return -1; }
-    if (rowStride < 0) { set_error("exportTracks: rowStride %lld", rowStride); return -1; }
-    bool needPitch = false;
-    for (int q = 0; q < nColumns; ++q) {
-        if (columns[q] < 0 || columns[q] >= kTrackColumns) { set_error("exportTracks: columns[%d] = %d (0 .. %d)", q, columns[q], kTrackColumns - 1); return -1; }
-        needPitch = needPitch || columns[q] == 0;
-    }
-    const long long n = utterances ? nUtterances : b->nUtt;
-    if (n < 0) { set_error("exportTracks: %lld utterances", n); return -1; }
-    if (b->nFrames >= 0xFFFFFFFFll) { set_error("exportTracks: too many frames"); return -1; }
-    // no utterance is longer than 2^32 samples: a larger hop or phase means the same
-    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
-    const bool packed = rowStride == 0;
-    std::vector<TimelineRow> rows((size_t)n);
-    long long maxSteps = 0, totalSteps = 0;
-    for (long long i = 0; i < n; ++i) {
-        const long long u = utterances ? utterances[i] : i;
-        if (u < 0 || u >= b->nUtt) { set_error("exportTracks: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, u, b->nUtt); return -1; }
-        const long long L = b->lens[(size_t)u];
-        TimelineRow& r = rows[(size_t)i];
-        r.frame0 = b->uttFrameStart[(size_t)u]; r.nFrames = b->uttFrames[(size_t)u]; r.slot = 0;
-        r.steps = L > phase ? (L - phase + hop - 1) / hop : 0;
-        maxSteps = std::max(maxSteps, r.steps);
-        totalSteps += r.steps;
-    }
-    if (!packed && rowStride < maxSteps) { set_error("exportTracks: rowStride %lld is below the largest step count (%lld)", rowStride, maxSteps); return -1; }
-    if (!packed && n > 0 && n > (1ll << 50) / rowStride / nColumns) { set_error("exportTracks: %lld rows of %lld steps of %d columns", n, rowStride, nColumns); return -1; }
-    if (packed && totalSteps > (1ll << 50) / nColumns) { set_error("exportTracks: %lld steps of %d columns", totalSteps, nColumns); return -1; }
-    const long long elements = (packed ? totalSteps : n * rowStride) * nColumns;
-    if (elements == 0) return 0;
-    const size_t elSize = format ? sizeof(float) : sizeof(double);
-    HIP_TRY(hipSetDevice(b->device));
-    if (!deviceOut) { set_error("exportTracks: no output buffer"); return -1; }
-    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportTracks")) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    const char* what = "exportTracks";
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("exportTracks: format %d (0 float64, 1 float32)", format); return -1; }
+        if (!columns || nColumns <= 0) { set_error("exportTracks: %d columns", nColumns); return -1; }
+        if (step_request(what, hop, phase, rowStride) || column_range(what, columns, nColumns, kTrackColumns)) return -1;
+        ExportSelection s;
+        std::vector<TimelineRow> rows;
+        if (step_rows(b, what, utterances, nUtterances, hop, phase, s, rows)) return -1;
+        const long long elements = export_elements(what, kStepNouns, s, rowStride, nColumns);
+        if (elements <= 0) return elements;
+        const size_t elSize = format ? sizeof(float) : sizeof(double);
+        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
 
-    // the pieces: runs of rows whose distinct lists fit the voicePitch table (one piece when column 0 is not asked for)
-    struct Piece { long long r0, r1, nLists, rowsOff, startOff, chunkOff, listOff, nChunks; };
-    std::vector<Piece> pieces;
-    std::vector<TimelineList> lists;      // of all pieces, one after the other
-    long long slotsPerPiece = 0;
-    if (needPitch && maxSteps > 0) {
-        slotsPerPiece = std::max<long long>(1, (b->pitchBudgetMB << 20) / (maxSteps * (long long)sizeof(double)));
-        std::vector<long long> stamp((size_t)b->nLists, -1);     // the piece that last gave the list a slot
-        std::vector<uint32_t> slotOf((size_t)b->nLists, 0);
-        Piece pc{0, 0, 0, 0, 0, 0, 0, 0};
-        for (long long i = 0; i < n; ++i) {
-            const long long u = utterances ? utterances[i] : i;
-            const uint32_t l = b->uttList[(size_t)u];
-            const long long id = (long long)pieces.size();
-            if (stamp[l] != id) {
-                if (pc.nLists == slotsPerPiece) {
-                    pc.r1 = i; pieces.push_back(pc);
-                    pc = Piece{i, i, 0, 0, 0, 0, 0, 0};
-                }
-                stamp[l] = (long long)pieces.size();
-                slotOf[l] = (uint32_t)pc.nLists++;
-                lists.push_back(TimelineList{rows[(size_t)i].frame0, (long long)rows[(size_t)i].nFrames});
+        const bool packed = rowStride == 0, needPitch = std::find(columns, columns + nColumns, 0) != columns + nColumns && s.most > 0;
+        const long long pitchStride = needPitch ? s.most : 0;
+        std::vector<TimelineList> lists;      // of all pieces, one after the other
+        std::vector<ExportPiece> pieces{ExportPiece{0, s.n, 0, {0, 0}}};
+        if (needPitch)
+            pieces = list_pieces(s.n, [&](long long i) { return b->uttList[(size_t)(utterances ? utterances[i] : i)]; }, [](long long) { return false; }, b->nLists,
+                                 std::max<long long>(1, (b->pitchBudgetMB << 20) / (s.most * (long long)sizeof(double))), [&](long long i, uint32_t slot, bool fresh) {
+                                     rows[(size_t)i].slot = slot;
+                                     if (fresh) lists.push_back(TimelineList{rows[(size_t)i].frame0, (long long)rows[(size_t)i].nFrames});
+                                 });
+        std::vector<long long> words;      // step starts and chunk rows of all pieces
+        long long mostLists = 0;
+        for (ExportPiece& pc : pieces) {
+            if (packed) pc.table = packed_row_table(s.counts.data(), pc.r0, pc.r1, kTimelineChunkLog2, words);
+            mostLists = std::max(mostLists, pc.nLists);
+        }
+        StageBlock block;
+        const int colsAt = block.add(columns, (size_t)nColumns * sizeof(int)), rowsAt = block.add(rows), wordsAt = block.add(words), listsAt = block.add(lists);
+        ExportStage stage(b, st, block, needPitch ? &b->pitchOrder : nullptr);
+        if (stage.begin([&] { return needPitch ? grow_table(b, b->dPitch, (size_t)(mostLists * pitchStride)) : 0; })) return -1;
+        const TimelineRow* dRows = stage.device<TimelineRow>(rowsAt);
+        const TimelineList* dLists = stage.device<TimelineList>(listsAt);
+        const auto dense = format ? klatt_timeline_dense<true> : klatt_timeline_dense<false>;
+        long long elementAt = 0;
+        for (const ExportPiece& pc : pieces) {
+            const long long nr = pc.r1 - pc.r0;
+            const long long pieceElements = (packed ? words[(size_t)(pc.table.startOff + nr)] : nr * rowStride) * nColumns;
+            if (pc.nLists > 0) {
+                hipLaunchKernelGGL(klatt_timeline_pitch, dim3((unsigned)((pc.nLists + 63) / 64)), dim3(64), 0, st, b->dFrames.ptr, b->dMeta.ptr,
+                                   dLists, pc.nLists, hop, phase, pitchStride, b->dPitch.ptr);
+                HIP_TRY(hipGetLastError());
+                dLists += pc.nLists;
             }
-            rows[(size_t)i].slot = slotOf[l];
+            if (pieceElements > 0) {
+                const DenseLaunch d = dense_launch(b, deviceOut, elementAt, pieceElements, elSize, stage.device<long long>(wordsAt), packed ? &pc.table : nullptr);
+                hipLaunchKernelGGL(dense, dim3(d.grid), dim3(256), 0, st, b->dFrames.ptr, b->dTimeline.ptr, dRows + pc.r0, d.start, d.chunk, nr, rowStride,
+                                   stage.device<int>(colsAt), nColumns, hop, phase, b->dPitch.ptr, pitchStride, (void*)d.out, pieceElements, d.vec);
+                HIP_TRY(hipGetLastError());
+                elementAt += pieceElements;
+            }
         }
-        pc.r1 = n; pieces.push_back(pc);
-    } else {
-        pieces.push_back(Piece{0, n, 0, 0, 0, 0, 0, 0});
-    }
-    // the staging block: columns | rows | per piece: step starts and chunk rows (packed), lists
-    std::vector<long long> words;      // step starts and chunk rows of all pieces
-    for (Piece& pc : pieces) {
-        if (!packed) continue;
-        pc.startOff = (long long)words.size();
-        long long acc = 0;
-        for (long long i = pc.r0; i < pc.r1; ++i) { words.push_back(acc); acc += rows[(size_t)i].steps; }
-        words.push_back(acc);
-        const long long nr = pc.r1 - pc.r0;
-        pc.nChunks = (acc >> kTimelineChunkLog2) + 1;
-        pc.chunkOff = (long long)words.size();
-        long long r = 0;
-        for (long long c = 0; c < pc.nChunks; ++c) {
-            while (r + 1 < nr && words[(size_t)(pc.startOff + r + 1)] <= (c << kTimelineChunkLog2)) ++r;
-            words.push_back(r);
-        }
-        words.push_back(std::max<long long>(nr - 1, 0));
-    }
-    const size_t colBytes = ((size_t)nColumns * sizeof(int) + 15) / 16 * 16, rowBytes = (size_t)n * sizeof(TimelineRow);
-    const size_t wordBytes = words.size() * sizeof(long long), listBytes = lists.size() * sizeof(TimelineList);
-    const size_t rowsAt = colBytes, wordsAt = (rowsAt + rowBytes + 15) / 16 * 16, listsAt = wordsAt + wordBytes, bytes = listsAt + listBytes;
-
-    // (every allocation first: once a kernel is queued the slot's event must come to stand behind it)
-    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
-    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
-    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
-    long long pitchStride = 0;
-    if (needPitch && maxSteps > 0) {
-        long long most = 0;
-        for (const Piece& pc : pieces) most = std::max(most, pc.nLists);
-        pitchStride = maxSteps;
-        if ((size_t)(most * pitchStride) > b->dPitch.cap && settle_track_exports(b, true)) return -1;
-        if (b->dPitch.reserve((size_t)(most * pitchStride))) return -1;
-    }
-    if (timeline_on_stream(b, st)) return -1;
-    if (pitchStride > 0 && b->pitchUsed) HIP_TRY(hipStreamWaitEvent(st, b->pitchDone, 0));      // (the table's previous export, whichever stream it ran on)
-    char* h = static_cast<char*>(slot.host.ptr);
-    memcpy(h, columns, (size_t)nColumns * sizeof(int));
-    memcpy(h + rowsAt, rows.data(), rowBytes);
-    if (wordBytes) memcpy(h + wordsAt, words.data(), wordBytes);
-    if (listBytes) memcpy(h + listsAt, lists.data(), listBytes);
-    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
-    const int* dCols = reinterpret_cast<const int*>(slot.dev.ptr);
-    const TimelineRow* dRows = reinterpret_cast<const TimelineRow*>(slot.dev.ptr + rowsAt);
-    const long long* dWords = reinterpret_cast<const long long*>(slot.dev.ptr + wordsAt);
-    const TimelineList* dLists = reinterpret_cast<const TimelineList*>(slot.dev.ptr + listsAt);
-    long long listAt = 0, elementAt = 0;
-    for (const Piece& pc : pieces) {
-        const long long nr = pc.r1 - pc.r0;
-        const long long pieceElements = (packed ? words[(size_t)(pc.startOff + nr)] : nr * rowStride) * nColumns;
-        if (pc.nLists > 0) {
-            hipLaunchKernelGGL(klatt_timeline_pitch, dim3((unsigned)((pc.nLists + 63) / 64)), dim3(64), 0, st, b->dFrames.ptr, b->dMeta.ptr,
-                               dLists + listAt, pc.nLists, hop, phase, pitchStride, b->dPitch.ptr);
-            HIP_TRY(hipGetLastError());
-            listAt += pc.nLists;
-        }
-        if (pieceElements > 0) {
-            char* out = static_cast<char*>(deviceOut) + (size_t)elementAt * elSize;
-            const long long nLane = (pieceElements * (long long)elSize + 15) / 16;
-            const unsigned grid = (unsigned)std::min<long long>((nLane + 255) / 256, 8ll * b->cus);
-            const int vec = reinterpret_cast<uintptr_t>(out) % 16 == 0;
-            const long long* dStart = packed ? dWords + pc.startOff : nullptr;
-            const long long* dChunk = packed ? dWords + pc.chunkOff : nullptr;
-            if (format) hipLaunchKernelGGL(klatt_timeline_dense<true>, dim3(grid), dim3(256), 0, st, b->dFrames.ptr, b->dTimeline.ptr, dRows + pc.r0, dStart, dChunk,
-                                           nr, rowStride, dCols, nColumns, hop, phase, b->dPitch.ptr, pitchStride, (void*)out, pieceElements, vec);
-            else hipLaunchKernelGGL(klatt_timeline_dense<false>, dim3(grid), dim3(256), 0, st, b->dFrames.ptr, b->dTimeline.ptr, dRows + pc.r0, dStart, dChunk,
-                                    nr, rowStride, dCols, nColumns, hop, phase, b->dPitch.ptr, pitchStride, (void*)out, pieceElements, vec);
-            HIP_TRY(hipGetLastError());
-            elementAt += pieceElements;
-        }
-    }
-    HIP_TRY(hipEventRecord(slot.done, st));
-    slot.used = true;
-    if (needPitch && maxSteps > 0) { HIP_TRY(hipEventRecord(b->pitchDone, st)); b->pitchUsed = true; }
-    return elements;
+        if (stage.finish()) return -1;
+        return elements;
+    });
 }
-
 
 // ---- phoneme alignment (klatt_align.h) ----------------------------------------------------------------------------------------------
 // The rows of an alignment export: count = steps (kind 0), units (1) or frames (2) of every chosen utterance.  0, or -1 with the message set.
-static int align_rows(Batch* b, const char* what, const long long* utterances, long long n, int kind, long long hop, long long phase,
-                      std::vector<AlignRow>& rows, long long* most, long long* total)
+static int align_rows(Batch* b, const char* what, const long long* utterances, long long nUtterances, int kind, long long hop, long long phase,
+                      ExportSelection& s, std::vector<AlignRow>& rows)
 {
     if (!b->hasLabels) { set_error("%s: the batch has no labels (set it with setIpa, setIpaVoices, setText or setRecordsLabelled)", what); return -1; }
-    if (n < 0) { set_error("%s: %lld utterances", what, n); return -1; }
-    if (b->nFrames >= 0xFFFFFFFFll) { set_error("%s: too many frames", what); return -1; }
-    rows.resize((size_t)n);
-    *most = 0; *total = 0;
-    for (long long i = 0; i < n; ++i) {
-        const long long u = utterances ? utterances[i] : i;
-        if (u < 0 || u >= b->nUtt) { set_error("%s: utterances[%lld] = %lld is not an utterance of the batch (%lld)", what, i, u, b->nUtt); return -1; }
+    return export_selection(b, what, utterances, nUtterances, true, s, [&](long long, long long u, long long) {
         const long long L = b->lens[(size_t)u];
         const uint32_t l = b->uttList[(size_t)u];
-        AlignRow& r = rows[(size_t)i];
+        AlignRow r;
         r.frame0 = b->uttFrameStart[(size_t)u]; r.unit0 = r.frame0 + (long long)l;
         r.nFrames = b->uttFrames[(size_t)u]; r.nUnits = b->listUnits[l]; r.length = (uint32_t)L; r.pad = 0;
         r.count = kind == 0 ? align_steps_below(L, hop, phase) : kind == 1 ? (long long)r.nUnits : (long long)r.nFrames;
-        *most = std::max(*most, r.count);
-        *total += r.count;
-    }
-    return 0;
+        rows.push_back(r);
+        return r.count;
+    });
 }
 
 long long speechPlayer_batch_unitCounts(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int byFrame, long long* counts)
 {
-    begin_call();
-    Batch* b = static_cast<Batch*>(batch);
-    if (!b) { set_error("unitCounts: no batch"); return -1; }
-    const long long n = utterances ? nUtterances : b->nUtt;
-    std::vector<AlignRow> rows;
-    long long most, total;
-    try {
-        if (align_rows(b, "unitCounts", utterances, n, byFrame ? 2 : 1, 1, 0, rows, &most, &total)) return -1;
-    } catch (const std::exception& e) { set_error("unitCounts: %s", e.what()); return -1; }
-    for (long long i = 0; counts && i < n; ++i) counts[i] = rows[(size_t)i].count;
-    return n;
+    return batch_entry("unitCounts", batch, [&](Batch* b) -> long long {
+        ExportSelection s;
+        std::vector<AlignRow> rows;
+        if (align_rows(b, "unitCounts", utterances, nUtterances, byFrame ? 2 : 1, 1, 0, s, rows)) return -1;
+        if (counts) std::copy(s.counts.begin(), s.counts.end(), counts);
+        return s.n;
+    });
 }
 
-static long long export_alignment(Batch* b, const long long* utterances, long long nUtterances, const int* columns, int nColumns, long long hop,
-                                  long long phase, void* deviceOut, int format, long long rowStride, long long pad, long long capacity, void* stream)
-{
-    if (format != 0 && format != 1) { set_error("exportAlignment: format %d (0 int64, 1 int32)", format); return -1; }
-    if (!columns || nColumns <= 0) { set_error("exportAlignment: %d columns", nColumns); return -1; }
-    if (hop <= 0 || phase < 0) { set_error("exportAlignment: hop %lld, phase %lld", hop, phase); return -1; }
-    if (rowStride < 0) { set_error("exportAlignment: rowStride %lld", rowStride); return -1; }
-    int needSpan = 0;
-    for (int q = 0; q < nColumns; ++q) {
-        if (columns[q] < 0 || columns[q] >= kAlignColumns) { set_error("exportAlignment: columns[%d] = %d (0 .. %d)", q, columns[q], kAlignColumns - 1); return -1; }
-        needSpan |= columns[q] == kAlignPosition || columns[q] == kAlignRemaining;
-    }
-    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);      // (no utterance is longer than 2^32 samples)
-    const long long n = utterances ? nUtterances : b->nUtt;
-    const bool packed = rowStride == 0;
-    std::vector<AlignRow> rows;
-    long long maxSteps = 0, totalSteps = 0;
-    if (align_rows(b, "exportAlignment", utterances, n, 0, hop, phase, rows, &maxSteps, &totalSteps)) return -1;
-    if (!packed && rowStride < maxSteps) { set_error("exportAlignment: rowStride %lld is below the largest step count (%lld)", rowStride, maxSteps); return -1; }
-    if (!packed && n > 0 && n > (1ll << 50) / rowStride / nColumns) { set_error("exportAlignment: %lld rows of %lld steps of %d columns", n, rowStride, nColumns); return -1; }
-    if (packed && totalSteps > (1ll << 50) / nColumns) { set_error("exportAlignment: %lld steps of %d columns", totalSteps, nColumns); return -1; }
-    const long long elements = (packed ? totalSteps : n * rowStride) * nColumns;
-    if (elements > capacity) { set_error("exportAlignment: the output takes %lld elements, capacity is %lld", elements, capacity); return -1; }
-    if (elements == 0) return 0;
-    const size_t elSize = format ? sizeof(int) : sizeof(long long);
-    HIP_TRY(hipSetDevice(b->device));
-    if (!deviceOut) { set_error("exportAlignment: no output buffer"); return -1; }
-    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportAlignment")) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // the staging block: columns | rows | step starts and chunk rows (packed)
-    std::vector<long long> words;
-    long long chunkOff = 0;
-    if (packed) {
-        long long acc = 0;
-        for (long long i = 0; i < n; ++i) { words.push_back(acc); acc += rows[(size_t)i].count; }
-        words.push_back(acc);
-        const long long nChunks = (acc >> kTimelineChunkLog2) + 1;
-        chunkOff = (long long)words.size();
-        long long r = 0;
-        for (long long c = 0; c < nChunks; ++c) {
-            while (r + 1 < n && words[(size_t)(r + 1)] <= (c << kTimelineChunkLog2)) ++r;
-            words.push_back(r);
-        }
-        words.push_back(std::max<long long>(n - 1, 0));
-    }
-    const size_t colBytes = ((size_t)nColumns * sizeof(int) + 15) / 16 * 16, rowBytes = (size_t)n * sizeof(AlignRow);
-    const size_t wordBytes = words.size() * sizeof(long long);
-    const size_t rowsAt = colBytes, wordsAt = (rowsAt + rowBytes + 15) / 16 * 16, bytes = wordsAt + wordBytes;
-    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
-    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
-    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
-    if (timeline_on_stream(b, st)) return -1;
-    char* h = static_cast<char*>(slot.host.ptr);
-    memcpy(h, columns, (size_t)nColumns * sizeof(int));
-    memcpy(h + rowsAt, rows.data(), rowBytes);
-    if (wordBytes) memcpy(h + wordsAt, words.data(), wordBytes);
-    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
-    const int* dCols = reinterpret_cast<const int*>(slot.dev.ptr);
-    const AlignRow* dRows = reinterpret_cast<const AlignRow*>(slot.dev.ptr + rowsAt);
-    const long long* dWords = reinterpret_cast<const long long*>(slot.dev.ptr + wordsAt);
-    const long long nLane = (elements * (long long)elSize + 15) / 16;
-    const unsigned grid = (unsigned)std::min<long long>((nLane + 255) / 256, 8ll * b->cus);
-    const int vec = reinterpret_cast<uintptr_t>(deviceOut) % 16 == 0;
-    const long long* dStart = packed ? dWords : nullptr;
-    const long long* dChunk = packed ? dWords + chunkOff : nullptr;
-    if (format) hipLaunchKernelGGL(klatt_align_dense<true>, dim3(grid), dim3(256), 0, st, b->dTimeline.ptr, b->dLabels.ptr, b->dUnitFirst.ptr, dRows, dStart, dChunk,
-                                   n, rowStride, dCols, nColumns, hop, phase, pad, needSpan, deviceOut, elements, vec);
-    else hipLaunchKernelGGL(klatt_align_dense<false>, dim3(grid), dim3(256), 0, st, b->dTimeline.ptr, b->dLabels.ptr, b->dUnitFirst.ptr, dRows, dStart, dChunk,
-                            n, rowStride, dCols, nColumns, hop, phase, pad, needSpan, deviceOut, elements, vec);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(slot.done, st));
-    slot.used = true;
-    return elements;
-}
-
-// Framewise labels of chosen utterances into the caller's device memory on the caller's stream: ordered as speechPlayer_batch_exportTracks
-// is (behind the set call and the per-request records, ahead of the next set call), staged through the same page-locked slots.
+// Framewise labels of chosen utterances.  The staging block: columns | rows | step starts and chunk rows (packed).
 long long speechPlayer_batch_exportAlignment(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const int* columns,
                                              int nColumns, long long hop, long long phase, void* deviceOut, int format, long long rowStride,
                                              long long pad, long long capacity, void* stream)
 {
-    begin_call();
-    Batch* b = static_cast<Batch*>(batch);
-    if (!b) { set_error("exportAlignment: no batch"); return -1; }
-    try {
-        return export_alignment(b, utterances, nUtterances, columns, nColumns, hop, phase, deviceOut, format, rowStride, pad, capacity, stream);
-    } catch (const std::exception& e) { set_error("exportAlignment: %s", e.what()); return -1; }
+    const char* what = "exportAlignment";
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("exportAlignment: format %d (0 int64, 1 int32)", format); return -1; }
+        if (!columns || nColumns <= 0) { set_error("exportAlignment: %d columns", nColumns); return -1; }
+        if (step_request(what, hop, phase, rowStride) || column_range(what, columns, nColumns, kAlignColumns)) return -1;
+        int needSpan = 0;
+        for (int q = 0; q < nColumns; ++q) needSpan |= columns[q] == kAlignPosition || columns[q] == kAlignRemaining;
+        ExportSelection s;
+        std::vector<AlignRow> rows;
+        if (align_rows(b, what, utterances, nUtterances, 0, hop, phase, s, rows)) return -1;
+        const long long elements = export_elements(what, kStepNouns, s, rowStride, nColumns, capacity);
+        if (elements <= 0) return elements;
+        const size_t elSize = format ? sizeof(int) : sizeof(long long);
+        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const bool packed = rowStride == 0;
+        std::vector<long long> words;
+        const RowTable table = packed ? packed_row_table(s.counts.data(), 0, s.n, kTimelineChunkLog2, words) : RowTable{0, 0};
+        StageBlock block;
+        const int colsAt = block.add(columns, (size_t)nColumns * sizeof(int)), rowsAt = block.add(rows), wordsAt = block.add(words);
+        ExportStage stage(b, st, block);
+        if (stage.begin()) return -1;
+        const DenseLaunch d = dense_launch(b, deviceOut, 0, elements, elSize, stage.device<long long>(wordsAt), packed ? &table : nullptr);
+        hipLaunchKernelGGL(format ? klatt_align_dense<true> : klatt_align_dense<false>, dim3(d.grid), dim3(256), 0, st, b->dTimeline.ptr, b->dLabels.ptr,
+                           b->dUnitFirst.ptr, stage.device<AlignRow>(rowsAt), d.start, d.chunk, s.n, rowStride, stage.device<int>(colsAt), nColumns, hop, phase,
+                           pad, needSpan, deviceOut, elements, d.vec);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
 }
 
-static long long export_units(Batch* b, const long long* utterances, long long nUtterances, long long hop, long long phase, int byFrame,
-                              void* deviceOut, long long rowStride, long long pad, long long capacity, void* stream)
-{
-    if (hop <= 0 || phase < 0) { set_error("exportUnits: hop %lld, phase %lld", hop, phase); return -1; }
-    if (rowStride < 0) { set_error("exportUnits: rowStride %lld", rowStride); return -1; }
-    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
-    const long long n = utterances ? nUtterances : b->nUtt;
-    const bool packed = rowStride == 0;
-    std::vector<AlignRow> rows;
-    long long most = 0, totalEntries = 0;
-    if (align_rows(b, "exportUnits", utterances, n, byFrame ? 2 : 1, hop, phase, rows, &most, &totalEntries)) return -1;
-    if (!packed && rowStride < most) { set_error("exportUnits: rowStride %lld is below the largest count (%lld)", rowStride, most); return -1; }
-    if (!packed && n > 0 && n > (1ll << 50) / rowStride) { set_error("exportUnits: %lld rows of %lld entries", n, rowStride); return -1; }
-    const long long entries = packed ? totalEntries : n * rowStride;
-    const long long elements = entries * kUnitColumns;
-    if (elements > capacity) { set_error("exportUnits: the output takes %lld elements, capacity is %lld", elements, capacity); return -1; }
-    if (elements == 0) return 0;
-    HIP_TRY(hipSetDevice(b->device));
-    if (!deviceOut) { set_error("exportUnits: no output buffer"); return -1; }
-    if (!device_range(deviceOut, (size_t)elements * sizeof(long long), b->device, sizeof(long long), "exportUnits")) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    std::vector<long long> words;
-    if (packed) {
-        long long acc = 0;
-        for (long long i = 0; i < n; ++i) { words.push_back(acc); acc += rows[(size_t)i].count; }
-        words.push_back(acc);
-    }
-    const size_t rowBytes = (size_t)n * sizeof(AlignRow), wordBytes = words.size() * sizeof(long long);
-    const size_t wordsAt = (rowBytes + 15) / 16 * 16, bytes = wordsAt + wordBytes;
-    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
-    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
-    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
-    if (timeline_on_stream(b, st)) return -1;
-    char* h = static_cast<char*>(slot.host.ptr);
-    memcpy(h, rows.data(), rowBytes);
-    if (wordBytes) memcpy(h + wordsAt, words.data(), wordBytes);
-    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
-    const AlignRow* dRows = reinterpret_cast<const AlignRow*>(slot.dev.ptr);
-    const long long* dStart = packed ? reinterpret_cast<const long long*>(slot.dev.ptr + wordsAt) : nullptr;
-    const unsigned grid = (unsigned)std::min<long long>((entries + 255) / 256, 8ll * b->cus);
-    hipLaunchKernelGGL(klatt_align_units, dim3(grid), dim3(256), 0, st, b->dTimeline.ptr, b->dLabels.ptr, b->dUnitFirst.ptr, dRows, dStart, n, rowStride,
-                       hop, phase, byFrame ? 1 : 0, pad, static_cast<long long*>(deviceOut), entries);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(slot.done, st));
-    slot.used = true;
-    return elements;
-}
-
+// The segment table of chosen utterances.  The staging block: rows | entry starts (packed).
 long long speechPlayer_batch_exportUnits(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, long long hop, long long phase,
                                          int byFrame, void* deviceOut, long long rowStride, long long pad, long long capacity, void* stream)
 {
-    begin_call();
-    Batch* b = static_cast<Batch*>(batch);
-    if (!b) { set_error("exportUnits: no batch"); return -1; }
-    try {
-        return export_units(b, utterances, nUtterances, hop, phase, byFrame, deviceOut, rowStride, pad, capacity, stream);
-    } catch (const std::exception& e) { set_error("exportUnits: %s", e.what()); return -1; }
+    const char* what = "exportUnits";
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (step_request(what, hop, phase, rowStride)) return -1;
+        ExportSelection s;
+        std::vector<AlignRow> rows;
+        if (align_rows(b, what, utterances, nUtterances, byFrame ? 2 : 1, hop, phase, s, rows)) return -1;
+        const long long elements = export_elements(what, kEntryNouns, s, rowStride, kUnitColumns, capacity);
+        if (elements <= 0) return elements;
+        if (export_output(b, what, deviceOut, elements, sizeof(long long))) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const bool packed = rowStride == 0;
+        std::vector<long long> words;
+        if (packed) packed_row_table(s.counts.data(), 0, s.n, -1, words);
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words);
+        ExportStage stage(b, st, block);
+        if (stage.begin()) return -1;
+        const long long entries = elements / kUnitColumns;
+        const unsigned grid = (unsigned)std::min<long long>((entries + 255) / 256, 8ll * b->cus);
+        hipLaunchKernelGGL(klatt_align_units, dim3(grid), dim3(256), 0, st, b->dTimeline.ptr, b->dLabels.ptr, b->dUnitFirst.ptr, stage.device<AlignRow>(rowsAt),
+                           packed ? stage.device<long long>(wordsAt) : nullptr, s.n, rowStride, hop, phase, byFrame ? 1 : 0, pad,
+                           static_cast<long long*>(deviceOut), entries);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
 }
 
 // ---- the glottal source (klatt_source.h) ----------------------------------------------------------------------------------------------
-// The source columns of chosen utterances into the caller's device memory on the caller's stream: arguments, packing, refusals and event
-// order are speechPlayer_batch_exportTracks'.  Every export walks the distinct lists its rows speak (klatt_source_walk) into the step
-// table, in pieces of rows whose lists fit option "source_table_mb", and klatt_source_dense deals the table out to the rows.
 // One walk over nLists lists (klatt_source.h): a wavefront per list, or a lane per list where there are enough of them to fill the
 // device that way (option "source_lane_lists"; profiles/source_export.txt).
 static void launch_source_walk(Batch* b, int what, hipStream_t st, const SourceList* dLists, long long nLists, long long hop, long long phase,
@@ -4816,153 +4788,74 @@ static void launch_source_walk(Batch* b, int what, hipStream_t st, const SourceL
     }
 }
 
-static long long export_source(Batch* b, const long long* utterances, long long nUtterances, const int* columns, int nColumns, long long hop,
-                               long long phase, void* deviceOut, int format, long long rowStride, void* stream)
+static SourceList source_list(const Batch* b, long long u, long long out, long long cap)
 {
-    if (format != 0 && format != 1) { set_error("exportSource: format %d (0 float64, 1 float32)", format); return -1; }
-    if (!columns || nColumns <= 0) { set_error("exportSource: %d columns", nColumns); return -1; }
-    if (hop <= 0 || phase < 0) { set_error("exportSource: hop %lld, phase %lld", hop, phase); return -1; }
-    if (rowStride < 0) { set_error("exportSource: rowStride %lld", rowStride); return -1; }
-    for (int q = 0; q < nColumns; ++q)
-        if (columns[q] < 0 || columns[q] >= kSourceCols) { set_error("exportSource: columns[%d] = %d (0 .. %d)", q, columns[q], kSourceCols - 1); return -1; }
-    const long long n = utterances ? nUtterances : b->nUtt;
-    if (n < 0) { set_error("exportSource: %lld utterances", n); return -1; }
-    if (b->nFrames >= 0xFFFFFFFFll) { set_error("exportSource: too many frames"); return -1; }
-    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);      // (no utterance is longer than 2^32 samples)
-    const bool packed = rowStride == 0;
-    std::vector<TimelineRow> rows((size_t)n);
-    long long maxSteps = 0, totalSteps = 0;
-    for (long long i = 0; i < n; ++i) {
-        const long long u = utterances ? utterances[i] : i;
-        if (u < 0 || u >= b->nUtt) { set_error("exportSource: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, u, b->nUtt); return -1; }
-        const long long L = b->lens[(size_t)u];
-        TimelineRow& r = rows[(size_t)i];
-        r.frame0 = b->uttFrameStart[(size_t)u]; r.nFrames = b->uttFrames[(size_t)u]; r.slot = 0;
-        r.steps = L > phase ? (L - phase + hop - 1) / hop : 0;
-        maxSteps = std::max(maxSteps, r.steps);
-        totalSteps += r.steps;
-    }
-    if (!packed && rowStride < maxSteps) { set_error("exportSource: rowStride %lld is below the largest step count (%lld)", rowStride, maxSteps); return -1; }
-    if (!packed && n > 0 && n > (1ll << 50) / rowStride / nColumns) { set_error("exportSource: %lld rows of %lld steps of %d columns", n, rowStride, nColumns); return -1; }
-    if (packed && totalSteps > (1ll << 50) / nColumns) { set_error("exportSource: %lld steps of %d columns", totalSteps, nColumns); return -1; }
-    const long long elements = (packed ? totalSteps : n * rowStride) * nColumns;
-    if (elements == 0) return 0;
-    const size_t elSize = format ? sizeof(float) : sizeof(double);
-    HIP_TRY(hipSetDevice(b->device));
-    if (!deviceOut) { set_error("exportSource: no output buffer"); return -1; }
-    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportSource")) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-
-    // the pieces: runs of rows whose distinct lists (those with steps) fit the step table
-    struct Piece { long long r0, r1, nLists, startOff, chunkOff, nChunks; };
-    std::vector<Piece> pieces;
-    std::vector<SourceList> lists;      // of all pieces, one after the other
-    const long long tableStride = std::max<long long>(maxSteps, 1);
-    const long long slotsPerPiece = std::max<long long>(1, (b->sourceBudgetMB << 20) / (tableStride * kSourceCols * (long long)sizeof(double)));
-    {
-        std::vector<long long> stamp((size_t)b->nLists, -1);     // the piece that last gave the list a slot
-        std::vector<uint32_t> slotOf((size_t)b->nLists, 0);
-        Piece pc{0, 0, 0, 0, 0, 0};
-        for (long long i = 0; i < n; ++i) {
-            if (rows[(size_t)i].steps == 0) continue;
-            const long long u = utterances ? utterances[i] : i;
-            const uint32_t l = b->uttList[(size_t)u];
-            if (stamp[l] != (long long)pieces.size()) {
-                if (pc.nLists == slotsPerPiece) {
-                    pc.r1 = i; pieces.push_back(pc);
-                    pc = Piece{i, i, 0, 0, 0, 0};
-                }
-                stamp[l] = (long long)pieces.size();
-                slotOf[l] = (uint32_t)pc.nLists++;
-                lists.push_back(SourceList{rows[(size_t)i].frame0, (long long)rows[(size_t)i].nFrames, (long long)b->lens[(size_t)u], 0, 0});
-            }
-            rows[(size_t)i].slot = slotOf[l];
-        }
-        pc.r1 = n; pieces.push_back(pc);
-    }
-    // the staging block: columns | rows | per piece: step starts and chunk rows (packed) | lists
-    std::vector<long long> words;
-    for (Piece& pc : pieces) {
-        if (!packed) continue;
-        pc.startOff = (long long)words.size();
-        long long acc = 0;
-        for (long long i = pc.r0; i < pc.r1; ++i) { words.push_back(acc); acc += rows[(size_t)i].steps; }
-        words.push_back(acc);
-        const long long nr = pc.r1 - pc.r0;
-        pc.nChunks = (acc >> kTimelineChunkLog2) + 1;
-        pc.chunkOff = (long long)words.size();
-        long long r = 0;
-        for (long long c = 0; c < pc.nChunks; ++c) {
-            while (r + 1 < nr && words[(size_t)(pc.startOff + r + 1)] <= (c << kTimelineChunkLog2)) ++r;
-            words.push_back(r);
-        }
-        words.push_back(std::max<long long>(nr - 1, 0));
-    }
-    const size_t colBytes = ((size_t)nColumns * sizeof(int) + 15) / 16 * 16, rowBytes = (size_t)n * sizeof(TimelineRow);
-    const size_t wordBytes = words.size() * sizeof(long long), listBytes = lists.size() * sizeof(SourceList);
-    const size_t rowsAt = colBytes, wordsAt = (rowsAt + rowBytes + 15) / 16 * 16, listsAt = wordsAt + wordBytes, bytes = listsAt + listBytes;
-
-    // (every allocation first: once a kernel is queued the slot's event must come to stand behind it)
-    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
-    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
-    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
-    long long most = 0;
-    for (const Piece& pc : pieces) most = std::max(most, pc.nLists);
-    const size_t tableDoubles = (size_t)(most * tableStride) * kSourceCols;
-    if (tableDoubles > b->dSource.cap && settle_track_exports(b, true)) return -1;
-    if (b->dSource.reserve(std::max<size_t>(tableDoubles, 1))) return -1;
-    if (timeline_on_stream(b, st)) return -1;
-    if (b->sourceUsed) HIP_TRY(hipStreamWaitEvent(st, b->sourceDone, 0));      // (the table's previous export, whichever stream it ran on)
-    char* h = static_cast<char*>(slot.host.ptr);
-    memcpy(h, columns, (size_t)nColumns * sizeof(int));
-    memcpy(h + rowsAt, rows.data(), rowBytes);
-    if (wordBytes) memcpy(h + wordsAt, words.data(), wordBytes);
-    if (listBytes) memcpy(h + listsAt, lists.data(), listBytes);
-    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
-    const int* dCols = reinterpret_cast<const int*>(slot.dev.ptr);
-    const TimelineRow* dRows = reinterpret_cast<const TimelineRow*>(slot.dev.ptr + rowsAt);
-    const long long* dWords = reinterpret_cast<const long long*>(slot.dev.ptr + wordsAt);
-    const SourceList* dLists = reinterpret_cast<const SourceList*>(slot.dev.ptr + listsAt);
-    long long listAt = 0, elementAt = 0;
-    for (const Piece& pc : pieces) {
-        const long long nr = pc.r1 - pc.r0;
-        const long long pieceElements = (packed ? words[(size_t)(pc.startOff + nr)] : nr * rowStride) * nColumns;
-        if (pc.nLists > 0) {
-            launch_source_walk(b, kSourceColumns, st, dLists + listAt, pc.nLists, hop, phase, tableStride, b->dSource.ptr, nullptr, nullptr);
-            HIP_TRY(hipGetLastError());
-            listAt += pc.nLists;
-        }
-        if (pieceElements > 0) {
-            char* out = static_cast<char*>(deviceOut) + (size_t)elementAt * elSize;
-            const long long nLane = (pieceElements * (long long)elSize + 15) / 16;
-            const unsigned grid = (unsigned)std::min<long long>((nLane + 255) / 256, 8ll * b->cus);
-            const int vec = reinterpret_cast<uintptr_t>(out) % 16 == 0;
-            const long long* dStart = packed ? dWords + pc.startOff : nullptr;
-            const long long* dChunk = packed ? dWords + pc.chunkOff : nullptr;
-            if (format) hipLaunchKernelGGL(klatt_source_dense<true>, dim3(grid), dim3(256), 0, st, b->dSource.ptr, tableStride, dRows + pc.r0, dStart, dChunk,
-                                           nr, rowStride, dCols, nColumns, (void*)out, pieceElements, vec);
-            else hipLaunchKernelGGL(klatt_source_dense<false>, dim3(grid), dim3(256), 0, st, b->dSource.ptr, tableStride, dRows + pc.r0, dStart, dChunk,
-                                    nr, rowStride, dCols, nColumns, (void*)out, pieceElements, vec);
-            HIP_TRY(hipGetLastError());
-            elementAt += pieceElements;
-        }
-    }
-    HIP_TRY(hipEventRecord(slot.done, st));
-    slot.used = true;
-    HIP_TRY(hipEventRecord(b->sourceDone, st));
-    b->sourceUsed = true;
-    return elements;
+    return SourceList{b->uttFrameStart[(size_t)u], (long long)b->uttFrames[(size_t)u], (long long)b->lens[(size_t)u], out, cap};
 }
 
+// The source columns of chosen utterances.  Every export walks the distinct lists its rows speak (those with steps) into the step table,
+// in pieces of rows whose lists fit option "source_table_mb", and klatt_source_dense deals the table out to the rows.  The staging
+// block: columns | rows | per piece: step starts and chunk rows (packed) | lists.
 long long speechPlayer_batch_exportSource(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const int* columns,
                                           int nColumns, long long hop, long long phase, void* deviceOut, int format, long long rowStride, void* stream)
 {
-    begin_call();
-    Batch* b = static_cast<Batch*>(batch);
-    if (!b) { set_error("exportSource: no batch"); return -1; }
-    try {
-        return export_source(b, utterances, nUtterances, columns, nColumns, hop, phase, deviceOut, format, rowStride, stream);
-    } catch (const std::exception& e) { set_error("exportSource: %s", e.what()); return -1; }
+    const char* what = "exportSource";
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("exportSource: format %d (0 float64, 1 float32)", format); return -1; }
+        if (!columns || nColumns <= 0) { set_error("exportSource: %d columns", nColumns); return -1; }
+        if (step_request(what, hop, phase, rowStride) || column_range(what, columns, nColumns, kSourceCols)) return -1;
+        ExportSelection s;
+        std::vector<TimelineRow> rows;
+        if (step_rows(b, what, utterances, nUtterances, hop, phase, s, rows)) return -1;
+        const long long elements = export_elements(what, kStepNouns, s, rowStride, nColumns);
+        if (elements <= 0) return elements;
+        const size_t elSize = format ? sizeof(float) : sizeof(double);
+        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+
+        const bool packed = rowStride == 0;
+        const long long tableStride = std::max<long long>(s.most, 1);
+        std::vector<SourceList> lists;      // of all pieces, one after the other
+        std::vector<ExportPiece> pieces =
+            list_pieces(s.n, [&](long long i) { return b->uttList[(size_t)(utterances ? utterances[i] : i)]; }, [&](long long i) { return rows[(size_t)i].steps == 0; },
+                        b->nLists, std::max<long long>(1, (b->sourceBudgetMB << 20) / (tableStride * kSourceCols * (long long)sizeof(double))),
+                        [&](long long i, uint32_t slot, bool fresh) {
+                            rows[(size_t)i].slot = slot;
+                            if (fresh) lists.push_back(source_list(b, utterances ? utterances[i] : i, 0, 0));
+                        });
+        std::vector<long long> words;
+        long long mostLists = 0;
+        for (ExportPiece& pc : pieces) {
+            if (packed) pc.table = packed_row_table(s.counts.data(), pc.r0, pc.r1, kTimelineChunkLog2, words);
+            mostLists = std::max(mostLists, pc.nLists);
+        }
+        StageBlock block;
+        const int colsAt = block.add(columns, (size_t)nColumns * sizeof(int)), rowsAt = block.add(rows), wordsAt = block.add(words), listsAt = block.add(lists);
+        ExportStage stage(b, st, block, &b->sourceOrder);
+        if (stage.begin([&] { return grow_table(b, b->dSource, (size_t)(mostLists * tableStride) * kSourceCols); })) return -1;
+        const TimelineRow* dRows = stage.device<TimelineRow>(rowsAt);
+        const SourceList* dLists = stage.device<SourceList>(listsAt);
+        const auto dense = format ? klatt_source_dense<true> : klatt_source_dense<false>;
+        long long elementAt = 0;
+        for (const ExportPiece& pc : pieces) {
+            const long long nr = pc.r1 - pc.r0;
+            const long long pieceElements = (packed ? words[(size_t)(pc.table.startOff + nr)] : nr * rowStride) * nColumns;
+            if (pc.nLists > 0) {
+                launch_source_walk(b, kSourceColumns, st, dLists, pc.nLists, hop, phase, tableStride, b->dSource.ptr, nullptr, nullptr);
+                HIP_TRY(hipGetLastError());
+                dLists += pc.nLists;
+            }
+            if (pieceElements > 0) {
+                const DenseLaunch d = dense_launch(b, deviceOut, elementAt, pieceElements, elSize, stage.device<long long>(wordsAt), packed ? &pc.table : nullptr);
+                hipLaunchKernelGGL(dense, dim3(d.grid), dim3(256), 0, st, b->dSource.ptr, tableStride, dRows + pc.r0, d.start, d.chunk, nr, rowStride,
+                                   stage.device<int>(colsAt), nColumns, (void*)d.out, pieceElements, d.vec);
+                HIP_TRY(hipGetLastError());
+                elementAt += pieceElements;
+            }
+        }
+        if (stage.finish()) return -1;
+        return elements;
+    });
 }
 
 // The epochs of every list of the batch as set: one counting walk on the batch's own stream, downloaded, kept until the next set call.
@@ -4974,129 +4867,79 @@ static int epoch_counts(Batch* b)
     if (b->nLists == 0) { b->epochFresh = true; return 0; }
     HIP_TRY(hipSetDevice(b->device));
     std::vector<SourceList> lists((size_t)b->nLists, SourceList{0, 0, 0, 0, 0});      // (a list no utterance speaks has no samples)
-    for (long long u = 0; u < b->nUtt; ++u)
-        lists[b->uttList[(size_t)u]] = SourceList{b->uttFrameStart[(size_t)u], (long long)b->uttFrames[(size_t)u], (long long)b->lens[(size_t)u], 0, 0};
-    const size_t bytes = lists.size() * sizeof(SourceList);
-    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
-    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
-    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
-    if ((size_t)b->nLists > b->dEpochCount.cap && settle_track_exports(b, true)) return -1;
-    if (b->dEpochCount.reserve((size_t)b->nLists)) return -1;
-    if (timeline_on_stream(b, b->stream)) return -1;
-    memcpy(slot.host.ptr, lists.data(), bytes);
-    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, b->stream));
-    launch_source_walk(b, kSourceCount, b->stream, reinterpret_cast<const SourceList*>(slot.dev.ptr), b->nLists, 1, 0, 0, nullptr, b->dEpochCount.ptr, nullptr);
+    for (long long u = 0; u < b->nUtt; ++u) lists[b->uttList[(size_t)u]] = source_list(b, u, 0, 0);
+    StageBlock block;
+    const int listsAt = block.add(lists);
+    ExportStage stage(b, b->stream, block);
+    if (stage.begin([&] { return grow_table(b, b->dEpochCount, (size_t)b->nLists); })) return -1;
+    launch_source_walk(b, kSourceCount, b->stream, stage.device<SourceList>(listsAt), b->nLists, 1, 0, 0, nullptr, b->dEpochCount.ptr, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(b->epochCount.data(), b->dEpochCount.ptr, (size_t)b->nLists * sizeof(long long), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));      // (the host has waited: the slot is free again without an event)
     b->epochFresh = true;
     return 0;
 }
 
 long long speechPlayer_batch_epochCounts(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, long long* counts)
 {
-    begin_call();
-    Batch* b = static_cast<Batch*>(batch);
-    if (!b) { set_error("epochCounts: no batch"); return -1; }
-    const long long n = utterances ? nUtterances : b->nUtt;
-    if (n < 0) { set_error("epochCounts: %lld utterances", n); return -1; }
-    for (long long i = 0; utterances && i < n; ++i)
-        if (utterances[i] < 0 || utterances[i] >= b->nUtt) { set_error("epochCounts: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, utterances[i], b->nUtt); return -1; }
-    try {
-        if (epoch_counts(b)) return -1;
-    } catch (const std::exception& e) { set_error("epochCounts: %s", e.what()); return -1; }
-    for (long long i = 0; counts && i < n; ++i) counts[i] = b->epochCount[b->uttList[(size_t)(utterances ? utterances[i] : i)]];
-    return n;
+    return batch_entry("epochCounts", batch, [&](Batch* b) -> long long {
+        const long long n = check_selection(b, "epochCounts", utterances, nUtterances, false);
+        if (n < 0 || epoch_counts(b)) return -1;
+        for (long long i = 0; counts && i < n; ++i) counts[i] = b->epochCount[b->uttList[(size_t)(utterances ? utterances[i] : i)]];
+        return n;
+    });
 }
 
-// The epoch table of chosen utterances into the caller's device memory on the caller's stream, ordered as the other exports are.  The
-// counts come from epoch_counts (the first call after a set call waits for the counting walk); the writing walk takes the distinct
-// lists with epochs that the rows speak, and klatt_source_deal copies their tables to the rows.
-static long long export_epochs(Batch* b, const long long* utterances, long long nUtterances, void* deviceOut, long long rowStride, double pad,
-                               long long capacity, void* stream)
-{
-    if (rowStride < 0) { set_error("exportEpochs: rowStride %lld", rowStride); return -1; }
-    const long long n = utterances ? nUtterances : b->nUtt;
-    if (n < 0) { set_error("exportEpochs: %lld utterances", n); return -1; }
-    for (long long i = 0; utterances && i < n; ++i)
-        if (utterances[i] < 0 || utterances[i] >= b->nUtt) { set_error("exportEpochs: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, utterances[i], b->nUtt); return -1; }
-    if (epoch_counts(b)) return -1;
-    const bool packed = rowStride == 0;
-    std::vector<EpochRow> rows((size_t)n);
-    std::vector<SourceList> lists;
-    std::vector<long long> slotOf((size_t)b->nLists, -1);
-    long long most = 0, total = 0, tableEntries = 0;
-    for (long long i = 0; i < n; ++i) {
-        const long long u = utterances ? utterances[i] : i;
-        const uint32_t l = b->uttList[(size_t)u];
-        const long long count = b->epochCount[l];
-        if (count > 0 && slotOf[l] < 0) {
-            slotOf[l] = (long long)lists.size();
-            lists.push_back(SourceList{b->uttFrameStart[(size_t)u], (long long)b->uttFrames[(size_t)u], (long long)b->lens[(size_t)u], tableEntries, count});
-            tableEntries += count;
-        }
-        rows[(size_t)i] = EpochRow{count > 0 ? lists[(size_t)slotOf[l]].out : 0, count};
-        most = std::max(most, count);
-        total += count;
-    }
-    if (!packed && rowStride < most) { set_error("exportEpochs: rowStride %lld is below the largest count (%lld)", rowStride, most); return -1; }
-    if (!packed && n > 0 && n > (1ll << 50) / rowStride) { set_error("exportEpochs: %lld rows of %lld entries", n, rowStride); return -1; }
-    const long long entries = packed ? total : n * rowStride;
-    const long long elements = entries * kEpochCols;
-    if (elements > capacity) { set_error("exportEpochs: the output takes %lld elements, capacity is %lld", elements, capacity); return -1; }
-    if (elements == 0) return 0;
-    HIP_TRY(hipSetDevice(b->device));
-    if (!deviceOut) { set_error("exportEpochs: no output buffer"); return -1; }
-    if (!device_range(deviceOut, (size_t)elements * sizeof(double), b->device, sizeof(double), "exportEpochs")) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    std::vector<long long> words;
-    if (packed) {
-        long long acc = 0;
-        for (long long i = 0; i < n; ++i) { words.push_back(acc); acc += rows[(size_t)i].count; }
-        words.push_back(acc);
-    }
-    const size_t rowBytes = (size_t)n * sizeof(EpochRow), wordBytes = words.size() * sizeof(long long), listBytes = lists.size() * sizeof(SourceList);
-    const size_t wordsAt = rowBytes, listsAt = wordsAt + wordBytes, bytes = listsAt + listBytes;
-    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
-    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
-    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
-    const size_t tableDoubles = (size_t)tableEntries * kEpochCols;
-    if (tableDoubles > b->dEpochs.cap && settle_track_exports(b, true)) return -1;
-    if (b->dEpochs.reserve(std::max<size_t>(tableDoubles, 1))) return -1;
-    if (timeline_on_stream(b, st)) return -1;
-    if (b->sourceUsed) HIP_TRY(hipStreamWaitEvent(st, b->sourceDone, 0));
-    char* h = static_cast<char*>(slot.host.ptr);
-    memcpy(h, rows.data(), rowBytes);
-    if (wordBytes) memcpy(h + wordsAt, words.data(), wordBytes);
-    if (listBytes) memcpy(h + listsAt, lists.data(), listBytes);
-    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
-    const EpochRow* dRows = reinterpret_cast<const EpochRow*>(slot.dev.ptr);
-    const long long* dStart = packed ? reinterpret_cast<const long long*>(slot.dev.ptr + wordsAt) : nullptr;
-    if (!lists.empty()) {
-        launch_source_walk(b, kSourceEpochs, st, reinterpret_cast<const SourceList*>(slot.dev.ptr + listsAt), (long long)lists.size(), 1, 0, 0, nullptr, nullptr,
-                                          b->dEpochs.ptr);
-        HIP_TRY(hipGetLastError());
-    }
-    const unsigned grid = (unsigned)std::min<long long>((entries + 255) / 256, 8ll * b->cus);
-    hipLaunchKernelGGL(klatt_source_deal, dim3(grid), dim3(256), 0, st, b->dEpochs.ptr, dRows, dStart, n, rowStride, pad, static_cast<double*>(deviceOut), entries,
-                       reinterpret_cast<uintptr_t>(deviceOut) % 16 == 0 ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(slot.done, st));
-    slot.used = true;
-    HIP_TRY(hipEventRecord(b->sourceDone, st));
-    b->sourceUsed = true;
-    return elements;
-}
-
+// The epoch table of chosen utterances.  The counts come from epoch_counts (the first call after a set call waits for the counting walk);
+// the writing walk takes the distinct lists with epochs that the rows speak, and klatt_source_deal copies their tables to the rows.
+// The staging block: rows | entry starts (packed) | lists.
 long long speechPlayer_batch_exportEpochs(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, void* deviceOut,
                                           long long rowStride, double pad, long long capacity, void* stream)
 {
-    begin_call();
-    Batch* b = static_cast<Batch*>(batch);
-    if (!b) { set_error("exportEpochs: no batch"); return -1; }
-    try {
-        return export_epochs(b, utterances, nUtterances, deviceOut, rowStride, pad, capacity, stream);
-    } catch (const std::exception& e) { set_error("exportEpochs: %s", e.what()); return -1; }
+    const char* what = "exportEpochs";
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (rowStride < 0) { set_error("exportEpochs: rowStride %lld", rowStride); return -1; }
+        if (check_selection(b, what, utterances, nUtterances, false) < 0 || epoch_counts(b)) return -1;      // (refusals before the device)
+        std::vector<EpochRow> rows;
+        std::vector<SourceList> lists;
+        std::vector<long long> slotOf((size_t)b->nLists, -1);
+        long long tableEntries = 0;
+        ExportSelection s;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long, long long u, long long) {
+                const uint32_t l = b->uttList[(size_t)u];
+                const long long count = b->epochCount[l];
+                if (count > 0 && slotOf[l] < 0) {
+                    slotOf[l] = (long long)lists.size();
+                    lists.push_back(source_list(b, u, tableEntries, count));
+                    tableEntries += count;
+                }
+                rows.push_back(EpochRow{count > 0 ? lists[(size_t)slotOf[l]].out : 0, count});
+                return count;
+            })) return -1;
+        const long long elements = export_elements(what, kEntryNouns, s, rowStride, kEpochCols, capacity);
+        if (elements <= 0) return elements;
+        if (export_output(b, what, deviceOut, elements, sizeof(double))) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const bool packed = rowStride == 0;
+        std::vector<long long> words;
+        if (packed) packed_row_table(s.counts.data(), 0, s.n, -1, words);
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words), listsAt = block.add(lists);
+        ExportStage stage(b, st, block, &b->sourceOrder);
+        if (stage.begin([&] { return grow_table(b, b->dEpochs, (size_t)tableEntries * kEpochCols); })) return -1;
+        if (!lists.empty()) {
+            launch_source_walk(b, kSourceEpochs, st, stage.device<SourceList>(listsAt), (long long)lists.size(), 1, 0, 0, nullptr, nullptr, b->dEpochs.ptr);
+            HIP_TRY(hipGetLastError());
+        }
+        const long long entries = elements / kEpochCols;
+        const unsigned grid = (unsigned)std::min<long long>((entries + 255) / 256, 8ll * b->cus);
+        hipLaunchKernelGGL(klatt_source_deal, dim3(grid), dim3(256), 0, st, b->dEpochs.ptr, stage.device<EpochRow>(rowsAt),
+                           packed ? stage.device<long long>(wordsAt) : nullptr, s.n, rowStride, pad, static_cast<double*>(deviceOut), entries,
+                           reinterpret_cast<uintptr_t>(deviceOut) % 16 == 0 ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
 }
 
 // ---- vocal-tract frequency response (klatt_response.h) ---------------------------------------------------------------------------------
@@ -5143,126 +4986,90 @@ long long speechPlayer_frameResponse(const speechPlayer_frame_t* frames, long lo
     return nFrames * nKinds * nFrequencies;
 }
 
-// The response of chosen utterances into the caller's device memory on the caller's stream: rows, steps, packing, refusals and event
-// order are speechPlayer_batch_exportTracks' (one piece: no table).  Rows that speak one frame list form a group, computed once and
-// stored to each of its rows (klatt_response.h).  The twiddles are made here, by the functions speechPlayer_frameResponse uses, and
-// travel in the export's staging block: twiddles | kinds | groups | the rows' first steps, group after group.
-static long long export_response(Batch* b, const long long* utterances, long long nUtterances, const double* frequencies, int nFrequencies,
-                                 const int* kinds, int nKinds, int gain, long long hop, long long phase, void* deviceOut, int format,
-                                 long long rowStride, void* stream)
-{
-    if (format != 0 && format != 1) { set_error("exportResponse: format %d (0 float64, 1 float32)", format); return -1; }
-    if (response_request("exportResponse", frequencies, nFrequencies, kinds, nKinds)) return -1;
-    if (hop <= 0 || phase < 0) { set_error("exportResponse: hop %lld, phase %lld", hop, phase); return -1; }
-    if (rowStride < 0) { set_error("exportResponse: rowStride %lld", rowStride); return -1; }
-    const long long n = utterances ? nUtterances : b->nUtt;
-    if (n < 0) { set_error("exportResponse: %lld utterances", n); return -1; }
-    if (b->nFrames >= 0xFFFFFFFFll) { set_error("exportResponse: too many frames"); return -1; }
-    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
-    const bool packed = rowStride == 0;
-    const long long perStep = (long long)nKinds * nFrequencies;
-    std::vector<ResponseGroup> groups;
-    std::vector<long long> groupOf((size_t)b->nLists, -1), rowGroup((size_t)n), rowFirst((size_t)n);
-    long long maxSteps = 0, totalSteps = 0;
-    for (long long i = 0; i < n; ++i) {
-        const long long u = utterances ? utterances[i] : i;
-        if (u < 0 || u >= b->nUtt) { set_error("exportResponse: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, u, b->nUtt); return -1; }
-        const uint32_t l = b->uttList[(size_t)u];
-        if (groupOf[l] < 0) {
-            const long long L = b->lens[(size_t)u];
-            ResponseGroup g;
-            g.frame0 = b->uttFrameStart[(size_t)u]; g.nFrames = b->uttFrames[(size_t)u]; g.nRows = 0;
-            g.steps = L > phase ? (L - phase + hop - 1) / hop : 0;
-            g.span = 0; g.chunk0 = 0; g.rowAt = 0;
-            groupOf[l] = (long long)groups.size();
-            groups.push_back(g);
-        }
-        ResponseGroup& g = groups[(size_t)groupOf[l]];
-        if (g.nRows == 0xFFFFFFFFu) { set_error("exportResponse: too many rows of one frame list"); return -1; }
-        ++g.nRows;
-        rowGroup[(size_t)i] = groupOf[l];
-        rowFirst[(size_t)i] = packed ? totalSteps : i * rowStride;
-        maxSteps = std::max(maxSteps, g.steps);
-        totalSteps += g.steps;
-    }
-    if (!packed && rowStride < maxSteps) { set_error("exportResponse: rowStride %lld is below the largest step count (%lld)", rowStride, maxSteps); return -1; }
-    if (!packed && n > 0 && n > (1ll << 50) / rowStride / perStep) { set_error("exportResponse: %lld rows of %lld steps of %lld values", n, rowStride, perStep); return -1; }
-    if (packed && totalSteps > (1ll << 50) / perStep) { set_error("exportResponse: %lld steps of %lld values", totalSteps, perStep); return -1; }
-    const long long outSteps = packed ? totalSteps : n * rowStride;
-    const long long elements = outSteps * perStep;
-    if (elements == 0) return 0;
-    const size_t elSize = format ? sizeof(float) : sizeof(double);
-    HIP_TRY(hipSetDevice(b->device));
-    if (!deviceOut) { set_error("exportResponse: no output buffer"); return -1; }
-    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportResponse")) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-
-    // the groups that write anything, their chunks one after the other, and their rows' first steps side by side
-    std::vector<ResponseGroup> live;
-    std::vector<long long> liveOf(groups.size(), -1);
-    long long nChunks = 0, rowAt = 0;
-    for (size_t g = 0; g < groups.size(); ++g) {
-        ResponseGroup G = groups[g];
-        G.span = packed ? G.steps : rowStride;
-        if (G.span == 0) continue;
-        G.chunk0 = nChunks; G.rowAt = rowAt;
-        nChunks += (G.span + kRespSteps - 1) / kRespSteps;
-        rowAt += G.nRows;
-        liveOf[g] = (long long)live.size();
-        live.push_back(G);
-    }
-    std::vector<long long> rowBase((size_t)rowAt), fill(live.size(), 0);
-    for (long long i = 0; i < n; ++i) {
-        const long long g = liveOf[(size_t)rowGroup[(size_t)i]];
-        if (g < 0) continue;
-        rowBase[(size_t)(live[(size_t)g].rowAt + fill[(size_t)g]++)] = rowFirst[(size_t)i];
-    }
-    const size_t twBytes = (size_t)nFrequencies * 4 * sizeof(double), kindBytes = ((size_t)nKinds * sizeof(int) + 15) / 16 * 16;
-    const size_t groupBytes = live.size() * sizeof(ResponseGroup), baseBytes = rowBase.size() * sizeof(long long);
-    const size_t kindsAt = twBytes, groupsAt = kindsAt + kindBytes, basesAt = groupsAt + groupBytes, bytes = basesAt + baseBytes;
-
-    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
-    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
-    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
-    if (timeline_on_stream(b, st)) return -1;
-    char* h = static_cast<char*>(slot.host.ptr);
-    double* tw = reinterpret_cast<double*>(h);
-    for (int k = 0; k < nFrequencies; ++k) response_twiddles(frequencies[k], b->sampleRate, tw + (size_t)k * 4);
-    memcpy(h + kindsAt, kinds, (size_t)nKinds * sizeof(int));
-    memcpy(h + groupsAt, live.data(), groupBytes);
-    memcpy(h + basesAt, rowBase.data(), baseBytes);
-    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
-    const KernelArgs ka = base_args(b->sampleRate);
-    ResponseArgs A;
-    A.frames = b->dFrames.ptr; A.req = b->dTimeline.ptr;
-    A.groups = reinterpret_cast<const ResponseGroup*>(slot.dev.ptr + groupsAt); A.nGroups = (long long)live.size(); A.nChunks = nChunks;
-    A.rowBase = reinterpret_cast<const long long*>(slot.dev.ptr + basesAt);
-    A.hop = hop; A.phase = phase;
-    A.kinds = reinterpret_cast<const int*>(slot.dev.ptr + kindsAt); A.nKinds = nKinds;
-    A.tw = reinterpret_cast<const double*>(slot.dev.ptr); A.K = nFrequencies;
-    A.gain = gain != 0; A.needC = 0; A.needP = 0;
-    for (int q = 0; q < nKinds; ++q) { if (kinds[q] < 4) A.needC = 1; else A.needP = 1; }
-    A.negPiOverSr = ka.negPiOverSr; A.twoPiOverSr = ka.twoPiOverSr;
-    A.out = deviceOut;
-    const unsigned grid = (unsigned)std::min<long long>(nChunks, 16ll * b->cus);
-    if (format) hipLaunchKernelGGL(klatt_response<true>, dim3(grid), dim3(256), 0, st, A);
-    else hipLaunchKernelGGL(klatt_response<false>, dim3(grid), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(slot.done, st));
-    slot.used = true;
-    return elements;
-}
-
+// The response of chosen utterances (one piece: no table).  Rows that speak one frame list form a group, computed once and stored to each
+// of its rows (klatt_response.h).  The twiddles are made here, by the functions speechPlayer_frameResponse uses.  The staging block:
+// twiddles | kinds | groups | the rows' first steps, group after group.
 long long speechPlayer_batch_exportResponse(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
                                             const double* frequencies, int nFrequencies, const int* kinds, int nKinds, int gain, long long hop,
                                             long long phase, void* deviceOut, int format, long long rowStride, void* stream)
 {
-    begin_call();
-    Batch* b = static_cast<Batch*>(batch);
-    if (!b) { set_error("exportResponse: no batch"); return -1; }
-    try {
-        return export_response(b, utterances, nUtterances, frequencies, nFrequencies, kinds, nKinds, gain, hop, phase, deviceOut, format, rowStride, stream);
-    } catch (const std::exception& e) { set_error("exportResponse: %s", e.what()); return -1; }
+    const char* what = "exportResponse";
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("exportResponse: format %d (0 float64, 1 float32)", format); return -1; }
+        if (response_request(what, frequencies, nFrequencies, kinds, nKinds) || step_request(what, hop, phase, rowStride)) return -1;
+        const bool packed = rowStride == 0;
+        const long long perStep = (long long)nKinds * nFrequencies;
+        std::vector<ResponseGroup> groups;
+        std::vector<long long> groupOf((size_t)b->nLists, -1), rowGroup, rowFirst;
+        ExportSelection s;
+        if (export_selection(b, what, utterances, nUtterances, true, s, [&](long long i, long long u, long long before) {
+                const uint32_t l = b->uttList[(size_t)u];
+                if (groupOf[l] < 0) {
+                    ResponseGroup g;
+                    g.frame0 = b->uttFrameStart[(size_t)u]; g.nFrames = b->uttFrames[(size_t)u]; g.nRows = 0;
+                    g.steps = align_steps_below(b->lens[(size_t)u], hop, phase);
+                    g.span = 0; g.chunk0 = 0; g.rowAt = 0;
+                    groupOf[l] = (long long)groups.size();
+                    groups.push_back(g);
+                }
+                ResponseGroup& g = groups[(size_t)groupOf[l]];
+                if (g.nRows == 0xFFFFFFFFu) { set_error("exportResponse: too many rows of one frame list"); return -1ll; }
+                ++g.nRows;
+                rowGroup.push_back(groupOf[l]);
+                rowFirst.push_back(packed ? before : i * rowStride);
+                return (long long)g.steps;
+            })) return -1;
+        static constexpr ExportNouns kValueNouns{"largest step count", "steps", "values"};
+        const long long elements = export_elements(what, kValueNouns, s, rowStride, perStep);
+        if (elements <= 0) return elements;
+        const size_t elSize = format ? sizeof(float) : sizeof(double);
+        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+
+        // the groups that write anything, their chunks one after the other, and their rows' first steps side by side
+        std::vector<ResponseGroup> live;
+        std::vector<long long> liveOf(groups.size(), -1);
+        long long nChunks = 0, rowAt = 0;
+        for (size_t g = 0; g < groups.size(); ++g) {
+            ResponseGroup G = groups[g];
+            G.span = packed ? G.steps : rowStride;
+            if (G.span == 0) continue;
+            G.chunk0 = nChunks; G.rowAt = rowAt;
+            nChunks += (G.span + kRespSteps - 1) / kRespSteps;
+            rowAt += G.nRows;
+            liveOf[g] = (long long)live.size();
+            live.push_back(G);
+        }
+        std::vector<long long> rowBase((size_t)rowAt), fill(live.size(), 0);
+        for (long long i = 0; i < s.n; ++i) {
+            const long long g = liveOf[(size_t)rowGroup[(size_t)i]];
+            if (g < 0) continue;
+            rowBase[(size_t)(live[(size_t)g].rowAt + fill[(size_t)g]++)] = rowFirst[(size_t)i];
+        }
+        std::vector<double> tw((size_t)nFrequencies * 4);
+        for (int k = 0; k < nFrequencies; ++k) response_twiddles(frequencies[k], b->sampleRate, tw.data() + (size_t)k * 4);
+        StageBlock block;
+        const int twAt = block.add(tw), kindsAt = block.add(kinds, (size_t)nKinds * sizeof(int)), groupsAt = block.add(live), basesAt = block.add(rowBase);
+        ExportStage stage(b, st, block);
+        if (stage.begin()) return -1;
+        const KernelArgs ka = base_args(b->sampleRate);
+        ResponseArgs A;
+        A.frames = b->dFrames.ptr; A.req = b->dTimeline.ptr;
+        A.groups = stage.device<ResponseGroup>(groupsAt); A.nGroups = (long long)live.size(); A.nChunks = nChunks;
+        A.rowBase = stage.device<long long>(basesAt);
+        A.hop = hop; A.phase = phase;
+        A.kinds = stage.device<int>(kindsAt); A.nKinds = nKinds;
+        A.tw = stage.device<double>(twAt); A.K = nFrequencies;
+        A.gain = gain != 0; A.needC = 0; A.needP = 0;
+        for (int q = 0; q < nKinds; ++q) { if (kinds[q] < 4) A.needC = 1; else A.needP = 1; }
+        A.negPiOverSr = ka.negPiOverSr; A.twoPiOverSr = ka.twoPiOverSr;
+        A.out = deviceOut;
+        const unsigned grid = (unsigned)std::min<long long>(nChunks, 16ll * b->cus);
+        hipLaunchKernelGGL(format ? klatt_response<true> : klatt_response<false>, dim3(grid), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
 }
 
 // ---- signal stems (klatt_stems.h) -------------------------------------------------------------------------------------------------------
@@ -5280,90 +5087,60 @@ long long speechPlayer_resonatorCoefficients(const double* frequency, const doub
     return n;
 }
 
-// The stems of chosen utterances into the caller's device memory on the caller's stream: rows, packing, refusals and event order are
-// speechPlayer_batch_exportTracks' (no hop; the output is planar).  One lane per row, the rows sorted by length (klatt_stems.h); the
-// staging block holds the columns and the rows.
-static long long export_stems(Batch* b, const long long* utterances, long long nUtterances, const int* columns, int nColumns, void* deviceOut,
-                              int format, long long rowStride, void* stream)
-{
-    if (format != 0 && format != 1) { set_error("exportStems: format %d (0 float64, 1 float32)", format); return -1; }
-    if (!columns || nColumns <= 0) { set_error("exportStems: %d columns", nColumns); return -1; }
-    if (rowStride < 0) { set_error("exportStems: rowStride %lld", rowStride); return -1; }
-    StemArgs A;
-    memset(&A, 0, sizeof A);
-    for (int c = 0; c < kStemColumns; ++c) A.slotOf[c] = -1;
-    for (int q = 0; q < nColumns; ++q) {
-        if (columns[q] < 0 || columns[q] >= kStemColumns) { set_error("exportStems: columns[%d] = %d (0 .. %d)", q, columns[q], kStemColumns - 1); return -1; }
-        if (A.slotOf[columns[q]] < 0) A.slotOf[columns[q]] = A.nSlots++;
-    }
-    const long long n = utterances ? nUtterances : b->nUtt;
-    if (n < 0) { set_error("exportStems: %lld utterances", n); return -1; }
-    if (b->nFrames >= 0xFFFFFFFFll) { set_error("exportStems: too many frames"); return -1; }
-    const bool packed = rowStride == 0;
-    std::vector<StemRow> rows((size_t)n);
-    long long maxLen = 0, total = 0;
-    for (long long i = 0; i < n; ++i) {
-        const long long u = utterances ? utterances[i] : i;
-        if (u < 0 || u >= b->nUtt) { set_error("exportStems: utterances[%lld] = %lld is not an utterance of the batch (%lld)", i, u, b->nUtt); return -1; }
-        StemRow& r = rows[(size_t)i];
-        r.frame0 = b->uttFrameStart[(size_t)u]; r.nFrames = b->uttFrames[(size_t)u]; r.seed = b->uttSeed[(size_t)u];
-        r.length = b->lens[(size_t)u]; r.pad = 0;
-        r.out = total;      // (samples before the row; elements below)
-        maxLen = std::max<long long>(maxLen, r.length);
-        total += r.length;
-    }
-    if (!packed && rowStride < maxLen) { set_error("exportStems: rowStride %lld is below the longest utterance (%lld)", rowStride, maxLen); return -1; }
-    if (!packed && n > 0 && n > (1ll << 50) / rowStride / nColumns) { set_error("exportStems: %lld rows of %lld samples of %d columns", n, rowStride, nColumns); return -1; }
-    if (packed && total > (1ll << 50) / nColumns) { set_error("exportStems: %lld samples of %d columns", total, nColumns); return -1; }
-    if (n > 0x7FFFFFFFll * kLanes) { set_error("exportStems: %lld rows", n); return -1; }
-    const long long elements = (packed ? total : n * rowStride) * nColumns;
-    if (elements == 0) return 0;
-    const size_t elSize = format ? sizeof(float) : sizeof(double);
-    HIP_TRY(hipSetDevice(b->device));
-    if (!deviceOut) { set_error("exportStems: no output buffer"); return -1; }
-    if (!device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, "exportStems")) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    for (long long i = 0; i < n; ++i) rows[(size_t)i].out = (packed ? rows[(size_t)i].out : i * rowStride) * nColumns;
-    // a wavefront runs as long as its longest lane: the rows longest first (each knows its place in the output)
-    std::stable_sort(rows.begin(), rows.end(), [](const StemRow& x, const StemRow& y) { return x.length > y.length; });
-
-    const size_t colBytes = ((size_t)nColumns * sizeof(int) + 15) / 16 * 16, rowBytes = (size_t)n * sizeof(StemRow), bytes = colBytes + rowBytes;
-    Batch::ExportSlot& slot = b->trackSlot[b->trackNext++ % Batch::kExportSlots];
-    if (slot.used) { HIP_TRY(hipEventSynchronize(slot.done)); slot.used = false; }
-    if (slot.host.ensure(bytes) || slot.dev.reserve(bytes)) return -1;
-    const int el = (int)elSize, T = stem_tile(A.nSlots, el), ldsBytes = stem_lds_bytes(A.nSlots, el);
-    const void* kernel = format ? reinterpret_cast<const void*>(klatt_stems<true, 16>)
-                                : (T == 16 ? reinterpret_cast<const void*>(klatt_stems<false, 16>) : reinterpret_cast<const void*>(klatt_stems<false, 8>));
-    if (ensure_lds_limit(kernel, kStemLdsBudget)) return -1;
-    if (timeline_on_stream(b, st)) return -1;
-    char* h = static_cast<char*>(slot.host.ptr);
-    memcpy(h, columns, (size_t)nColumns * sizeof(int));
-    memcpy(h + colBytes, rows.data(), rowBytes);
-    HIP_TRY(hipMemcpyAsync(slot.dev.ptr, slot.host.ptr, bytes, hipMemcpyHostToDevice, st));
-    A.K = base_args(b->sampleRate);
-    A.K.frames = b->dFrames.ptr; A.K.meta = b->dMeta.ptr;
-    A.rows = reinterpret_cast<const StemRow*>(slot.dev.ptr + colBytes); A.nRows = n;
-    A.columns = reinterpret_cast<const int*>(slot.dev.ptr); A.nColumns = nColumns;
-    A.rowStride = rowStride; A.out = deviceOut;
-    const dim3 grid((unsigned)((n + kLanes - 1) / kLanes));
-    if (format) hipLaunchKernelGGL((klatt_stems<true, 16>), grid, dim3(kLanes), ldsBytes, st, A);
-    else if (T == 16) hipLaunchKernelGGL((klatt_stems<false, 16>), grid, dim3(kLanes), ldsBytes, st, A);
-    else hipLaunchKernelGGL((klatt_stems<false, 8>), grid, dim3(kLanes), ldsBytes, st, A);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(slot.done, st));
-    slot.used = true;
-    return elements;
-}
-
+// The stems of chosen utterances (no hop; the output is planar).  One lane per row, the rows sorted by length (klatt_stems.h).  The
+// staging block: columns | rows.
 long long speechPlayer_batch_exportStems(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const int* columns,
                                          int nColumns, void* deviceOut, int format, long long rowStride, void* stream)
 {
-    begin_call();
-    Batch* b = static_cast<Batch*>(batch);
-    if (!b) { set_error("exportStems: no batch"); return -1; }
-    try {
-        return export_stems(b, utterances, nUtterances, columns, nColumns, deviceOut, format, rowStride, stream);
-    } catch (const std::exception& e) { set_error("exportStems: %s", e.what()); return -1; }
+    const char* what = "exportStems";
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("exportStems: format %d (0 float64, 1 float32)", format); return -1; }
+        if (!columns || nColumns <= 0) { set_error("exportStems: %d columns", nColumns); return -1; }
+        if (rowStride < 0) { set_error("exportStems: rowStride %lld", rowStride); return -1; }
+        if (column_range(what, columns, nColumns, kStemColumns)) return -1;
+        StemArgs A;
+        memset(&A, 0, sizeof A);
+        for (int c = 0; c < kStemColumns; ++c) A.slotOf[c] = -1;
+        for (int q = 0; q < nColumns; ++q)
+            if (A.slotOf[columns[q]] < 0) A.slotOf[columns[q]] = A.nSlots++;
+        const bool packed = rowStride == 0;
+        ExportSelection s;
+        std::vector<StemRow> rows;
+        if (export_selection(b, what, utterances, nUtterances, true, s, [&](long long i, long long u, long long before) {
+                StemRow r;
+                r.frame0 = b->uttFrameStart[(size_t)u]; r.nFrames = b->uttFrames[(size_t)u]; r.seed = b->uttSeed[(size_t)u];
+                r.length = b->lens[(size_t)u]; r.pad = 0;
+                r.out = packed ? before : i;      // (the samples or rows before the row; elements below)
+                rows.push_back(r);
+                return (long long)r.length;
+            })) return -1;
+        static constexpr ExportNouns kSampleNouns{"longest utterance", "samples", "columns"};
+        const long long elements = export_elements(what, kSampleNouns, s, rowStride, nColumns);
+        if (elements < 0) return -1;
+        if (s.n > 0x7FFFFFFFll * kLanes) { set_error("exportStems: %lld rows", s.n); return -1; }
+        if (elements == 0) return 0;
+        const size_t elSize = format ? sizeof(float) : sizeof(double);
+        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        for (StemRow& r : rows) r.out = (packed ? r.out : r.out * rowStride) * nColumns;
+        // a wavefront runs as long as its longest lane: the rows longest first (each knows its place in the output)
+        std::stable_sort(rows.begin(), rows.end(), [](const StemRow& x, const StemRow& y) { return x.length > y.length; });
+        StageBlock block;
+        const int colsAt = block.add(columns, (size_t)nColumns * sizeof(int)), rowsAt = block.add(rows);
+        const int el = (int)elSize, T = stem_tile(A.nSlots, el), ldsBytes = stem_lds_bytes(A.nSlots, el);
+        const auto kernel = format ? klatt_stems<true, 16> : T == 16 ? klatt_stems<false, 16> : klatt_stems<false, 8>;
+        ExportStage stage(b, st, block);
+        if (stage.begin([&] { return ensure_lds_limit(reinterpret_cast<const void*>(kernel), kStemLdsBudget); })) return -1;
+        A.K = base_args(b->sampleRate);
+        A.K.frames = b->dFrames.ptr; A.K.meta = b->dMeta.ptr;
+        A.rows = stage.device<StemRow>(rowsAt); A.nRows = s.n;
+        A.columns = stage.device<int>(colsAt); A.nColumns = nColumns;
+        A.rowStride = rowStride; A.out = deviceOut;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((s.n + kLanes - 1) / kLanes)), dim3(kLanes), ldsBytes, st, A);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
 }
 
 }  // extern "C"

@@ -266,19 +266,7 @@ __global__ void __launch_bounds__(256) klatt_source_dense(const double* __restri
         const long long e0 = t * EL;
         long long g, r, j;
         int q;
-        if (nCols == 1) { g = e0; q = 0; }
-        else if ((unsigned long long)e0 >> 32) { g = e0 / nCols; q = (int)(e0 - g * nCols); }
-        else { const uint32_t g32 = (uint32_t)e0 / (uint32_t)nCols; g = g32; q = (int)((uint32_t)e0 - g32 * (uint32_t)nCols); }
-        if (rowStride > 0) {
-            if (((unsigned long long)g | (unsigned long long)rowStride) >> 32) r = g / rowStride;
-            else r = (uint32_t)g / (uint32_t)rowStride;
-            j = g - r * rowStride;
-        } else {
-            const long long c = g >> kTimelineChunkLog2;
-            long long lo = chunkRow[c], hi = chunkRow[c + 1] + 1;      // the last row whose start is <= g
-            while (hi - lo > 1) { const long long mid = (lo + hi) >> 1; if (stepStart[mid] <= g) lo = mid; else hi = mid; }
-            r = lo; j = g - stepStart[r];
-        }
+        dense_locate(e0, nCols, rowStride, stepStart, chunkRow, g, q, r, j);
         TimelineRow row = rows[r];
         double v[EL];
 #pragma unroll
@@ -294,15 +282,7 @@ __global__ void __launch_bounds__(256) klatt_source_dense(const double* __restri
             }
             v[i] = x;
         }
-        if (F32) {
-            float* o = static_cast<float*>(outp) + e0;
-            if (vecStore && e0 + EL <= total) *reinterpret_cast<float4*>(o) = make_float4((float)v[0], (float)v[1], (float)v[EL - 2], (float)v[EL - 1]);
-            else for (int i = 0; i < EL && e0 + i < total; ++i) o[i] = (float)v[i];
-        } else {
-            double* o = static_cast<double*>(outp) + e0;
-            if (vecStore && e0 + EL <= total) *reinterpret_cast<double2*>(o) = make_double2(v[0], v[1]);
-            else for (int i = 0; i < EL && e0 + i < total; ++i) o[i] = v[i];
-        }
+        store16<typename std::conditional<F32, float, double>::type>(outp, e0, total, vecStore, v);
     }
 }
 
@@ -315,11 +295,7 @@ __global__ void __launch_bounds__(256) klatt_source_deal(const double* __restric
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < entries; g += stride) {
         long long r, j;
         if (rowStride > 0) { r = g / rowStride; j = g - r * rowStride; }
-        else {
-            long long lo = 0, hi = nRows;                              // the last row whose start is <= g
-            while (hi - lo > 1) { const long long mid = (lo + hi) >> 1; if (start[mid] <= g) lo = mid; else hi = mid; }
-            r = lo; j = g - start[r];
-        }
+        else packed_locate(g, start, nRows, r, j);
         const EpochRow row = rows[r];
         double* __restrict__ o = out + g * kEpochCols;
         double2 a = make_double2(pad, pad), b = a;

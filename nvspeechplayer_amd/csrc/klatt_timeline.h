@@ -27,6 +27,8 @@
 
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "klatt_device.h"
 
 namespace klatt {
@@ -149,8 +151,51 @@ __device__ __forceinline__ double timeline_side(const double* __restrict__ frame
 
 constexpr int kTimelineChunkLog2 = 15;      // steps per chunk of the packed form's row table
 
-// Element e of the output is (row, step, column) = (g / rowStride or by bisection, g - start of the row, e - g * nCols) with
-// g = e / nCols the step's number in the output.  A lane owns 16 bytes: 4 float32 or 2 float64 elements.
+// The row of entry g of a packed output and the entry's place in it: the last row among [lo, hi) whose start is <= g.
+__device__ __forceinline__ void packed_locate(long long g, const long long* __restrict__ start, long long lo, long long hi, long long& r, long long& j)
+{
+    while (hi - lo > 1) { const long long mid = (lo + hi) >> 1; if (start[mid] <= g) lo = mid; else hi = mid; }
+    r = lo; j = g - start[r];
+}
+__device__ __forceinline__ void packed_locate(long long g, const long long* __restrict__ start, long long nRows, long long& r, long long& j)
+{
+    packed_locate(g, start, 0, nRows, r, j);
+}
+
+// Element e0 of a [row][step][column] output is (r, j, q): g = e0 / nCols is the step's number in the output, the row g / rowStride
+// (padded) or by bisection over stepStart within the chunk table's bounds (packed: rowStride 0).  32-bit divisions where they do.
+__device__ __forceinline__ void dense_locate(long long e0, int nCols, long long rowStride, const long long* __restrict__ stepStart,
+                                             const long long* __restrict__ chunkRow, long long& g, int& q, long long& r, long long& j)
+{
+    if (nCols == 1) { g = e0; q = 0; }
+    else if ((unsigned long long)e0 >> 32) { g = e0 / nCols; q = (int)(e0 - g * nCols); }
+    else { const uint32_t g32 = (uint32_t)e0 / (uint32_t)nCols; g = g32; q = (int)((uint32_t)e0 - g32 * (uint32_t)nCols); }
+    if (rowStride > 0) {
+        if (((unsigned long long)g | (unsigned long long)rowStride) >> 32) r = g / rowStride;
+        else r = (uint32_t)g / (uint32_t)rowStride;
+        j = g - r * rowStride;
+    } else {
+        const long long c = g >> kTimelineChunkLog2;
+        packed_locate(g, stepStart, chunkRow[c], chunkRow[c + 1] + 1, r, j);
+    }
+}
+
+// A lane's 16 bytes: EL elements of T from element e0 of the output, one store where the output is aligned and the lane is whole.
+template <typename T, typename V, int EL>
+__device__ __forceinline__ void store16(void* __restrict__ outp, long long e0, long long total, int vecStore, const V (&v)[EL])
+{
+    static_assert(sizeof(T) * EL == 16, "a lane owns 16 bytes");
+    struct alignas(16) Lane { T x[EL]; };
+    T* o = static_cast<T*>(outp) + e0;
+    if (vecStore && e0 + EL <= total) {
+        Lane l;
+#pragma unroll
+        for (int i = 0; i < EL; ++i) l.x[i] = (T)v[i];
+        *reinterpret_cast<Lane*>(o) = l;
+    } else for (int i = 0; i < EL && e0 + i < total; ++i) o[i] = (T)v[i];
+}
+
+// A lane owns 16 bytes: 4 float32 or 2 float64 elements (dense_locate).
 template <bool F32>
 __global__ void __launch_bounds__(256) klatt_timeline_dense(const double* __restrict__ frames, const TimelineReq* __restrict__ req,
                                                             const TimelineRow* __restrict__ rows, const long long* __restrict__ stepStart,
@@ -166,19 +211,7 @@ __global__ void __launch_bounds__(256) klatt_timeline_dense(const double* __rest
         const long long e0 = t * EL;
         long long g, r, j;
         int q;
-        if (nCols == 1) { g = e0; q = 0; }
-        else if ((unsigned long long)e0 >> 32) { g = e0 / nCols; q = (int)(e0 - g * nCols); }
-        else { const uint32_t g32 = (uint32_t)e0 / (uint32_t)nCols; g = g32; q = (int)((uint32_t)e0 - g32 * (uint32_t)nCols); }
-        if (rowStride > 0) {
-            if (((unsigned long long)g | (unsigned long long)rowStride) >> 32) r = g / rowStride;
-            else r = (uint32_t)g / (uint32_t)rowStride;
-            j = g - r * rowStride;
-        } else {
-            const long long c = g >> kTimelineChunkLog2;
-            long long lo = chunkRow[c], hi = chunkRow[c + 1] + 1;      // the last row whose start is <= g
-            while (hi - lo > 1) { const long long mid = (lo + hi) >> 1; if (stepStart[mid] <= g) lo = mid; else hi = mid; }
-            r = lo; j = g - stepStart[r];
-        }
+        dense_locate(e0, nCols, rowStride, stepStart, chunkRow, g, q, r, j);
         TimelineRow row = rows[r];
         // the request of the step in hand, kept while the following elements stay inside it
         long long k = -1, kFirst = 0, kNext = 0;
@@ -223,15 +256,7 @@ __global__ void __launch_bounds__(256) klatt_timeline_dense(const double* __rest
             }
             v[i] = x;
         }
-        if (F32) {
-            float* o = static_cast<float*>(outp) + e0;
-            if (vecStore && e0 + EL <= total) *reinterpret_cast<float4*>(o) = make_float4((float)v[0], (float)v[1], (float)v[EL - 2], (float)v[EL - 1]);
-            else for (int i = 0; i < EL && e0 + i < total; ++i) o[i] = (float)v[i];
-        } else {
-            double* o = static_cast<double*>(outp) + e0;
-            if (vecStore && e0 + EL <= total) *reinterpret_cast<double2*>(o) = make_double2(v[0], v[1]);
-            else for (int i = 0; i < EL && e0 + i < total; ++i) o[i] = v[i];
-        }
+        store16<typename std::conditional<F32, float, double>::type>(outp, e0, total, vecStore, v);
     }
 }
 

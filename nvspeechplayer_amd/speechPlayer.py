@@ -383,35 +383,57 @@ TRACK_MARK, TRACK_FRAME = 47, 48      # SPEECHPLAYER_TRACK_MARK / _FRAME: the co
 TRACK_COLUMNS = FRAME_FIELDS + ["mark", "frame"]
 
 
-def check_track_request(columns, hop, phase, dtype):
-    """The argument checks of BatchPlayer.trackTensor that need no GPU, before any library call: `columns` a non-empty sequence of
-    column numbers 0 .. 48 or names (FRAME_FIELDS, "mark", "frame"; a single number or name stands for one column), hop >= 1,
-    phase >= 0, dtype None / torch.float32 / torch.float64.  Raises KeyError (unknown name), ValueError (number, hop, phase, no columns)
-    or TypeError (dtype).  Returns (columns as an int32 array, hop, phase, the export format: 0 float64, 1 float32)."""
-    import torch
+def _check_columns(what, columns, names, hint, noun="column"):
+    """`columns` (a sequence of numbers or of names among `names`; a single one stands for one column) as an int32 array.  Raises KeyError
+    (unknown name; `hint` lists the known ones) or ValueError (number out of range, no columns)."""
     if isinstance(columns, (str, int, np.integer)):
         columns = [columns]
     cols = []
     for c in columns:
         if isinstance(c, str):
-            if c not in TRACK_COLUMNS:
-                raise KeyError("trackTensor: no column named %r (FRAME_FIELDS, 'mark', 'frame')" % c)
-            c = TRACK_COLUMNS.index(c)
+            if c not in names:
+                raise KeyError("%s: no %s named %r (%s)" % (what, noun, c, hint))
+            c = names.index(c)
         c = int(c)
-        if not 0 <= c < len(TRACK_COLUMNS):
-            raise ValueError("trackTensor: column %d is not in 0 .. %d" % (c, len(TRACK_COLUMNS) - 1))
+        if not 0 <= c < len(names):
+            raise ValueError("%s: %s %d is not in 0 .. %d" % (what, noun, c, len(names) - 1))
         cols.append(c)
     if not cols:
-        raise ValueError("trackTensor: no columns")
+        raise ValueError("%s: no %ss" % (what, noun))
+    return np.asarray(cols, dtype=np.int32)
+
+
+def _check_dtype(what, dtype, allowed, default):
+    """dtype (None: `default`) one of the two `allowed` (TypeError): -> the export format, 1 for the 4-byte type, 0 for the 8-byte one."""
+    import torch
+    dtype = default if dtype is None else dtype
+    if dtype not in allowed:
+        raise TypeError("%s: dtype must be %s or %s, not %s" % (what, allowed[0], allowed[1], dtype))
+    return 1 if dtype in (torch.float32, torch.int32) else 0
+
+
+def _check_hop_phase_dtype(what, hop, phase, dtype, allowed, default):
+    """hop >= 1 and phase >= 0 as ints (ValueError) and the dtype (_check_dtype): -> (hop, phase, the export format)."""
     hop, phase = int(hop), int(phase)
     if hop < 1:
-        raise ValueError("trackTensor: hop must be at least 1, not %d" % hop)
+        raise ValueError("%s: hop must be at least 1, not %d" % (what, hop))
     if phase < 0:
-        raise ValueError("trackTensor: phase must not be negative (%d)" % phase)
-    dtype = torch.float32 if dtype is None else dtype
-    if dtype not in (torch.float32, torch.float64):
-        raise TypeError("trackTensor: dtype must be torch.float32 or torch.float64, not %s" % dtype)
-    return np.asarray(cols, dtype=np.int32), hop, phase, 1 if dtype == torch.float32 else 0
+        raise ValueError("%s: phase must not be negative (%d)" % (what, phase))
+    return hop, phase, _check_dtype(what, dtype, allowed, default)
+
+
+def _float_types():
+    import torch
+    return (torch.float32, torch.float64), torch.float32
+
+
+def check_track_request(columns, hop, phase, dtype):
+    """The argument checks of BatchPlayer.trackTensor that need no GPU, before any library call: `columns` a non-empty sequence of
+    column numbers 0 .. 48 or names (FRAME_FIELDS, "mark", "frame"; a single number or name stands for one column), hop >= 1,
+    phase >= 0, dtype None / torch.float32 / torch.float64.  Raises KeyError (unknown name), ValueError (number, hop, phase, no columns)
+    or TypeError (dtype).  Returns (columns as an int32 array, hop, phase, the export format: 0 float64, 1 float32)."""
+    cols = _check_columns("trackTensor", columns, TRACK_COLUMNS, "FRAME_FIELDS, 'mark', 'frame'")
+    return (cols,) + _check_hop_phase_dtype("trackTensor", hop, phase, dtype, *_float_types())
 
 
 ALIGN_COLUMNS = ["phoneme", "stress", "flags", "unit", "textOffset", "frame", "position", "remaining"]      # SPEECHPLAYER_ALIGN_*
@@ -423,29 +445,8 @@ def check_alignment_request(columns, hop, phase, dtype):
     names (ALIGN_COLUMNS; a single one stands for one column), hop >= 1, phase >= 0, dtype torch.int64 / torch.int32.  Raises KeyError,
     ValueError or TypeError as check_track_request does.  Returns (columns as an int32 array, hop, phase, the export format: 0 int64, 1 int32)."""
     import torch
-    if isinstance(columns, (str, int, np.integer)):
-        columns = [columns]
-    cols = []
-    for c in columns:
-        if isinstance(c, str):
-            if c not in ALIGN_COLUMNS:
-                raise KeyError("alignmentTensor: no column named %r (%s)" % (c, ", ".join(ALIGN_COLUMNS)))
-            c = ALIGN_COLUMNS.index(c)
-        c = int(c)
-        if not 0 <= c < len(ALIGN_COLUMNS):
-            raise ValueError("alignmentTensor: column %d is not in 0 .. %d" % (c, len(ALIGN_COLUMNS) - 1))
-        cols.append(c)
-    if not cols:
-        raise ValueError("alignmentTensor: no columns")
-    hop, phase = int(hop), int(phase)
-    if hop < 1:
-        raise ValueError("alignmentTensor: hop must be at least 1, not %d" % hop)
-    if phase < 0:
-        raise ValueError("alignmentTensor: phase must not be negative (%d)" % phase)
-    dtype = torch.int64 if dtype is None else dtype
-    if dtype not in (torch.int64, torch.int32):
-        raise TypeError("alignmentTensor: dtype must be torch.int64 or torch.int32, not %s" % dtype)
-    return np.asarray(cols, dtype=np.int32), hop, phase, 1 if dtype == torch.int32 else 0
+    cols = _check_columns("alignmentTensor", columns, ALIGN_COLUMNS, ", ".join(ALIGN_COLUMNS))
+    return (cols,) + _check_hop_phase_dtype("alignmentTensor", hop, phase, dtype, (torch.int64, torch.int32), torch.int64)
 
 
 SOURCE_COLUMNS = ["f0", "phase", "vibratoPhase", "cycle", "open", "wave"]      # SPEECHPLAYER_SOURCE_*
@@ -457,30 +458,8 @@ def check_source_request(columns, hop, phase, dtype):
     names (SOURCE_COLUMNS; a single one stands for one column), hop >= 1, phase >= 0, dtype None / torch.float32 / torch.float64.  Raises
     KeyError, ValueError or TypeError as check_track_request does.  Returns (columns as an int32 array, hop, phase, the export format:
     0 float64, 1 float32)."""
-    import torch
-    if isinstance(columns, (str, int, np.integer)):
-        columns = [columns]
-    cols = []
-    for c in columns:
-        if isinstance(c, str):
-            if c not in SOURCE_COLUMNS:
-                raise KeyError("sourceTensor: no column named %r (%s)" % (c, ", ".join(SOURCE_COLUMNS)))
-            c = SOURCE_COLUMNS.index(c)
-        c = int(c)
-        if not 0 <= c < len(SOURCE_COLUMNS):
-            raise ValueError("sourceTensor: column %d is not in 0 .. %d" % (c, len(SOURCE_COLUMNS) - 1))
-        cols.append(c)
-    if not cols:
-        raise ValueError("sourceTensor: no columns")
-    hop, phase = int(hop), int(phase)
-    if hop < 1:
-        raise ValueError("sourceTensor: hop must be at least 1, not %d" % hop)
-    if phase < 0:
-        raise ValueError("sourceTensor: phase must not be negative (%d)" % phase)
-    dtype = torch.float32 if dtype is None else dtype
-    if dtype not in (torch.float32, torch.float64):
-        raise TypeError("sourceTensor: dtype must be torch.float32 or torch.float64, not %s" % dtype)
-    return np.asarray(cols, dtype=np.int32), hop, phase, 1 if dtype == torch.float32 else 0
+    cols = _check_columns("sourceTensor", columns, SOURCE_COLUMNS, ", ".join(SOURCE_COLUMNS))
+    return (cols,) + _check_hop_phase_dtype("sourceTensor", hop, phase, dtype, *_float_types())
 
 
 RESPONSE_KINDS = ["cascade_re", "cascade_im", "cascade_mag", "cascade_db",
@@ -503,21 +482,7 @@ def check_response_request(frequencies, kinds, sampleRate, what="responseTensor"
         raise ValueError("%s: %d frequencies (1 .. %d)" % (what, len(freqs), RESPONSE_MAX_BINS))
     if not np.all(np.isfinite(freqs)):
         raise ValueError("%s: every frequency must be finite" % what)
-    if isinstance(kinds, (str, int, np.integer)):
-        kinds = [kinds]
-    ks = []
-    for k in kinds:
-        if isinstance(k, str):
-            if k not in RESPONSE_KINDS:
-                raise KeyError("%s: no kind named %r (%s)" % (what, k, ", ".join(RESPONSE_KINDS)))
-            k = RESPONSE_KINDS.index(k)
-        k = int(k)
-        if not 0 <= k < len(RESPONSE_KINDS):
-            raise ValueError("%s: kind %d is not in 0 .. %d" % (what, k, len(RESPONSE_KINDS) - 1))
-        ks.append(k)
-    if not ks:
-        raise ValueError("%s: no kinds" % what)
-    return freqs, np.asarray(ks, dtype=np.int32)
+    return freqs, _check_columns(what, kinds, RESPONSE_KINDS, ", ".join(RESPONSE_KINDS), "kind")
 
 
 def frameResponse(frames, sampleRate, frequencies, kinds=("cascade_db", "parallel_db"), gain=False):
@@ -552,25 +517,8 @@ def check_stem_request(columns, dtype):
     """The argument checks of BatchPlayer.stemTensor that need no GPU: `columns` a non-empty sequence of column numbers 0 .. 6 or names
     (STEM_COLUMNS; a single one stands for one column), dtype None / torch.float32 / torch.float64.  Raises KeyError, ValueError or
     TypeError as check_source_request does.  Returns (columns as an int32 array, the export format: 0 float64, 1 float32)."""
-    import torch
-    if isinstance(columns, (str, int, np.integer)):
-        columns = [columns]
-    cols = []
-    for c in columns:
-        if isinstance(c, str):
-            if c not in STEM_COLUMNS:
-                raise KeyError("stemTensor: no column named %r (%s)" % (c, ", ".join(STEM_COLUMNS)))
-            c = STEM_COLUMNS.index(c)
-        c = int(c)
-        if not 0 <= c < len(STEM_COLUMNS):
-            raise ValueError("stemTensor: column %d is not in 0 .. %d" % (c, len(STEM_COLUMNS) - 1))
-        cols.append(c)
-    if not cols:
-        raise ValueError("stemTensor: no columns")
-    dtype = torch.float32 if dtype is None else dtype
-    if dtype not in (torch.float32, torch.float64):
-        raise TypeError("stemTensor: dtype must be torch.float32 or torch.float64, not %s" % dtype)
-    return np.asarray(cols, dtype=np.int32), 1 if dtype == torch.float32 else 0
+    cols = _check_columns("stemTensor", columns, STEM_COLUMNS, ", ".join(STEM_COLUMNS))
+    return cols, _check_dtype("stemTensor", dtype, *_float_types())
 
 
 def resonatorCoefficients(f, bw, sampleRate, anti=False):
@@ -598,6 +546,10 @@ def check_option_value(name, value):
     if not -2 ** 31 <= value < 2 ** 31:
         raise ValueError("setOption(%r): %d does not fit the option's C int (-2**31 .. 2**31 - 1)" % (name, value))
     return value
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
 
 
 def _ready_stream(owner, dev):
@@ -705,27 +657,11 @@ class BatchPlayer(object):
         dtype = torch.float32 if dtype is None else dtype
         if dtype not in (torch.float32, torch.int16):
             raise TypeError("pcmTensor: dtype must be torch.float32 or torch.int16, not %s" % dtype)
-        sel = None if utterances is None else _host_array(utterances, np.int64).reshape(-1)
-        n = self.nUtterances if sel is None else len(sel)
-        idx = np.arange(n) if sel is None else sel
-        if n and (idx.min() < 0 or idx.max() >= self.nUtterances):
-            raise ValueError("pcmTensor: utterance numbers must lie in [0, %d)" % self.nUtterances)
-        lens = self._lengths()[idx]
-        dev = self.device
-        if padded:
-            width = int(lens.max()) if n else 0
-            out = torch.empty((n, width), dtype=dtype, device="cuda:%d" % dev)
-            stride = width
-        else:
-            offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-            out = torch.empty(int(offsets[-1]), dtype=dtype, device="cuda:%d" % dev)
-            stride = 0
-        if out.numel():
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            got = self._check(self._dll.speechPlayer_batch_exportPcm(self._h, None if sel is None else sel.ctypes.data, n, out.data_ptr(),
-                                                                     1 if dtype == torch.float32 else 0, stride, stream))
-            assert got == out.numel(), (got, out.numel())
-        return out, torch.from_numpy(lens if padded else offsets)
+        sel, n, idx = self._selection("pcmTensor", utterances)
+
+        def call(out, stride, numel, stream):
+            return self._dll.speechPlayer_batch_exportPcm(self._h, _ptr(sel), n, out, 1 if dtype == torch.float32 else 0, stride, stream)
+        return self._export_rows(self._lengths()[idx], (), dtype, padded, call)
 
     def timeline(self, u):
         """When utterance u's requests are dequeued (speechPlayer_batch_timeline): -> (firstSample int64 [n + 1], userIndex int32 [n]);
@@ -752,29 +688,11 @@ class BatchPlayer(object):
         else tracks is [total steps, len(columns)] and steps the n + 1 offsets (int64 CPU tensors)."""
         import torch
         cols, hop, phase, fmt = check_track_request(columns, hop, phase, dtype)
-        sel = None if utterances is None else _host_array(utterances, np.int64).reshape(-1)
-        n = self.nUtterances if sel is None else len(sel)
-        idx = np.arange(n) if sel is None else sel
-        if n and (idx.min() < 0 or idx.max() >= self.nUtterances):
-            raise ValueError("trackTensor: utterance numbers must lie in [0, %d)" % self.nUtterances)
-        lens = self._lengths()[idx]
-        steps = np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
-        dev = self.device
-        tdtype = torch.float32 if fmt else torch.float64
-        if padded:
-            width = int(steps.max()) if n else 0
-            out = torch.empty((n, width, len(cols)), dtype=tdtype, device="cuda:%d" % dev)
-            stride = width
-        else:
-            offsets = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
-            out = torch.empty((int(offsets[-1]), len(cols)), dtype=tdtype, device="cuda:%d" % dev)
-            stride = 0
-        if out.numel():
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            got = self._check(self._dll.speechPlayer_batch_exportTracks(self._h, None if sel is None else sel.ctypes.data, n, cols.ctypes.data, len(cols),
-                                                                        hop, phase, out.data_ptr(), fmt, stride, stream))
-            assert got == out.numel(), (got, out.numel())
-        return out, torch.from_numpy(steps if padded else offsets)
+        sel, n, steps = self._steps("trackTensor", utterances, hop, phase)
+
+        def call(out, stride, numel, stream):
+            return self._dll.speechPlayer_batch_exportTracks(self._h, _ptr(sel), n, cols.ctypes.data, len(cols), hop, phase, out, fmt, stride, stream)
+        return self._export_rows(steps, (len(cols),), torch.float32 if fmt else torch.float64, padded, call)
 
     @property
     def hasLabels(self):
@@ -789,6 +707,30 @@ class BatchPlayer(object):
             raise ValueError("%s: utterance numbers must lie in [0, %d)" % (what, self.nUtterances))
         return sel, n, idx
 
+    def _steps(self, what, utterances, hop, phase):
+        """The selection and its rows' step counts: the samples phase + j * hop below each utterance's length."""
+        sel, n, idx = self._selection(what, utterances)
+        lens = self._lengths()[idx]
+        return sel, n, np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
+
+    def _export_rows(self, counts, tail_shape, dtype, padded, call, always=False):
+        """The output of an export of len(counts) rows of counts[i] entries of shape tail_shape: [n, most, ...] (padded) or [total, ...],
+        filled by call(pointer, rowStride, elements, stream) on torch's current stream -- not made for an empty tensor unless `always`
+        (then with a null pointer) -- which answers the elements written.  -> (out, counts or, packed, the n + 1 offsets: int64 CPU tensors)."""
+        import torch
+        dev = self.device
+        if padded:
+            stride = int(counts.max()) if len(counts) else 0
+            lead, second = (len(counts), stride), counts
+        else:
+            stride, second = 0, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            lead = (int(second[-1]),)
+        out = torch.empty(lead + tuple(tail_shape), dtype=dtype, device="cuda:%d" % dev)
+        if out.numel() or always:
+            got = self._check(call(out.data_ptr() if out.numel() else None, stride, out.numel(), torch.cuda.current_stream(dev).cuda_stream))
+            assert got == out.numel(), (got, out.numel())
+        return out, torch.from_numpy(second)
+
     def alignmentTensor(self, columns, hop=1, phase=0, utterances=None, dtype=None, padded=True, pad=-1):
         """Framewise phoneme labels of a batch set from IPA text, as a torch tensor on the batch's device
         (speechPlayer_batch_exportAlignment), filled on torch's current stream without a host wait and without a synthesis launch:
@@ -800,26 +742,12 @@ class BatchPlayer(object):
         [total steps, len(columns)] and steps the n + 1 offsets (int64 CPU tensors).  RuntimeError when the batch has no labels."""
         import torch
         cols, hop, phase, fmt = check_alignment_request(columns, hop, phase, dtype)
-        sel, n, idx = self._selection("alignmentTensor", utterances)
-        lens = self._lengths()[idx]
-        steps = np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
-        dev = self.device
-        tdtype = torch.int32 if fmt else torch.int64
-        if padded:
-            width = int(steps.max()) if n else 0
-            out = torch.empty((n, width, len(cols)), dtype=tdtype, device="cuda:%d" % dev)
-            stride = width
-        else:
-            offsets = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
-            out = torch.empty((int(offsets[-1]), len(cols)), dtype=tdtype, device="cuda:%d" % dev)
-            stride = 0
-        if out.numel() or not self.hasLabels:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            got = self._check(self._dll.speechPlayer_batch_exportAlignment(self._h, None if sel is None else sel.ctypes.data, n, cols.ctypes.data, len(cols),
-                                                                           hop, phase, out.data_ptr() if out.numel() else None, fmt, stride, int(pad),
-                                                                           out.numel(), stream))
-            assert got == out.numel(), (got, out.numel())
-        return out, torch.from_numpy(steps if padded else offsets)
+        sel, n, steps = self._steps("alignmentTensor", utterances, hop, phase)
+
+        def call(out, stride, numel, stream):
+            return self._dll.speechPlayer_batch_exportAlignment(self._h, _ptr(sel), n, cols.ctypes.data, len(cols), hop, phase, out, fmt, stride,
+                                                                int(pad), numel, stream)
+        return self._export_rows(steps, (len(cols),), torch.int32 if fmt else torch.int64, padded, call, always=not self.hasLabels)
 
     def unitCounts(self, utterances=None, by="unit"):
         """Units (by="frame": frames) of the chosen utterances (speechPlayer_batch_unitCounts): an int64 array."""
@@ -827,7 +755,7 @@ class BatchPlayer(object):
             raise ValueError("by must be 'unit' or 'frame', not %r" % (by,))
         sel, n, _ = self._selection("unitCounts", utterances)
         counts = np.zeros(max(n, 1), np.int64)
-        self._check(self._dll.speechPlayer_batch_unitCounts(self._h, None if sel is None else sel.ctypes.data, n, int(by == "frame"), counts.ctypes.data))
+        self._check(self._dll.speechPlayer_batch_unitCounts(self._h, _ptr(sel), n, int(by == "frame"), counts.ctypes.data))
         return counts[:n]
 
     def unitTensor(self, hop=1, phase=0, utterances=None, by="unit", padded=True, pad=-1):
@@ -842,22 +770,10 @@ class BatchPlayer(object):
         if hop < 1 or phase < 0:
             raise ValueError("unitTensor: hop must be at least 1 and phase not negative (%d, %d)" % (hop, phase))
         sel, n, _ = self._selection("unitTensor", utterances)
-        counts = self.unitCounts(utterances, by)
-        dev = self.device
-        if padded:
-            width = int(counts.max()) if n else 0
-            out = torch.empty((n, width, len(UNIT_COLUMNS)), dtype=torch.int64, device="cuda:%d" % dev)
-            stride = width
-        else:
-            offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-            out = torch.empty((int(offsets[-1]), len(UNIT_COLUMNS)), dtype=torch.int64, device="cuda:%d" % dev)
-            stride = 0
-        if out.numel():
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            got = self._check(self._dll.speechPlayer_batch_exportUnits(self._h, None if sel is None else sel.ctypes.data, n, hop, phase, int(by == "frame"),
-                                                                       out.data_ptr(), stride, int(pad), out.numel(), stream))
-            assert got == out.numel(), (got, out.numel())
-        return out, torch.from_numpy(counts if padded else offsets)
+
+        def call(out, stride, numel, stream):
+            return self._dll.speechPlayer_batch_exportUnits(self._h, _ptr(sel), n, hop, phase, int(by == "frame"), out, stride, int(pad), numel, stream)
+        return self._export_rows(self.unitCounts(utterances, by), (len(UNIT_COLUMNS),), torch.int64, padded, call)
 
     def sourceTensor(self, columns, hop=1, phase=0, utterances=None, dtype=None, padded=True):
         """The glottal source as a torch tensor on the batch's device (speechPlayer_batch_exportSource), filled on torch's current stream
@@ -869,25 +785,11 @@ class BatchPlayer(object):
         counts; or [total steps, len(columns)] and the n + 1 offsets (int64 CPU tensors)."""
         import torch
         cols, hop, phase, fmt = check_source_request(columns, hop, phase, dtype)
-        sel, n, idx = self._selection("sourceTensor", utterances)
-        lens = self._lengths()[idx]
-        steps = np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
-        dev = self.device
-        tdtype = torch.float32 if fmt else torch.float64
-        if padded:
-            width = int(steps.max()) if n else 0
-            out = torch.empty((n, width, len(cols)), dtype=tdtype, device="cuda:%d" % dev)
-            stride = width
-        else:
-            offsets = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
-            out = torch.empty((int(offsets[-1]), len(cols)), dtype=tdtype, device="cuda:%d" % dev)
-            stride = 0
-        if out.numel():
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            got = self._check(self._dll.speechPlayer_batch_exportSource(self._h, None if sel is None else sel.ctypes.data, n, cols.ctypes.data, len(cols),
-                                                                        hop, phase, out.data_ptr(), fmt, stride, stream))
-            assert got == out.numel(), (got, out.numel())
-        return out, torch.from_numpy(steps if padded else offsets)
+        sel, n, steps = self._steps("sourceTensor", utterances, hop, phase)
+
+        def call(out, stride, numel, stream):
+            return self._dll.speechPlayer_batch_exportSource(self._h, _ptr(sel), n, cols.ctypes.data, len(cols), hop, phase, out, fmt, stride, stream)
+        return self._export_rows(steps, (len(cols),), torch.float32 if fmt else torch.float64, padded, call)
 
     def responseTensor(self, frequencies, kinds=("cascade_db", "parallel_db"), hop=1, phase=0, utterances=None, dtype=None, padded=True, gain=False):
         """The vocal-tract frequency response (the spectral envelope) as a torch tensor on the batch's device
@@ -900,35 +802,13 @@ class BatchPlayer(object):
         [total steps, len(kinds), K] and the n + 1 offsets (int64 CPU tensors)."""
         import torch
         freqs, ks = check_response_request(frequencies, kinds, self.sampleRate)
-        hop, phase = int(hop), int(phase)
-        if hop < 1:
-            raise ValueError("responseTensor: hop must be at least 1, not %d" % hop)
-        if phase < 0:
-            raise ValueError("responseTensor: phase must not be negative (%d)" % phase)
-        dtype = torch.float32 if dtype is None else dtype
-        if dtype not in (torch.float32, torch.float64):
-            raise TypeError("responseTensor: dtype must be torch.float32 or torch.float64, not %s" % dtype)
-        fmt = 1 if dtype == torch.float32 else 0
-        sel, n, idx = self._selection("responseTensor", utterances)
-        lens = self._lengths()[idx]
-        steps = np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
-        dev = self.device
-        tdtype = torch.float32 if fmt else torch.float64
-        if padded:
-            width = int(steps.max()) if n else 0
-            out = torch.empty((n, width, len(ks), len(freqs)), dtype=tdtype, device="cuda:%d" % dev)
-            stride = width
-        else:
-            offsets = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
-            out = torch.empty((int(offsets[-1]), len(ks), len(freqs)), dtype=tdtype, device="cuda:%d" % dev)
-            stride = 0
-        if out.numel():
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            got = self._check(self._dll.speechPlayer_batch_exportResponse(self._h, None if sel is None else sel.ctypes.data, n, freqs.ctypes.data,
-                                                                          len(freqs), ks.ctypes.data, len(ks), 1 if gain else 0, hop, phase,
-                                                                          out.data_ptr(), fmt, stride, stream))
-            assert got == out.numel(), (got, out.numel())
-        return out, torch.from_numpy(steps if padded else offsets)
+        hop, phase, fmt = _check_hop_phase_dtype("responseTensor", hop, phase, dtype, *_float_types())
+        sel, n, steps = self._steps("responseTensor", utterances, hop, phase)
+
+        def call(out, stride, numel, stream):
+            return self._dll.speechPlayer_batch_exportResponse(self._h, _ptr(sel), n, freqs.ctypes.data, len(freqs), ks.ctypes.data, len(ks),
+                                                               1 if gain else 0, hop, phase, out, fmt, stride, stream)
+        return self._export_rows(steps, (len(ks), len(freqs)), torch.float32 if fmt else torch.float64, padded, call)
 
     def stemTensor(self, columns, utterances=None, dtype=None, padded=True):
         """The signal stems as a torch tensor on the batch's device (speechPlayer_batch_exportStems), filled on torch's current stream
@@ -968,7 +848,7 @@ class BatchPlayer(object):
         if n == 0:
             return np.zeros(0, np.int64)
         counts = np.zeros(n, np.int64)
-        self._check(self._dll.speechPlayer_batch_epochCounts(self._h, None if sel is None else sel.ctypes.data, n, counts.ctypes.data))
+        self._check(self._dll.speechPlayer_batch_epochCounts(self._h, _ptr(sel), n, counts.ctypes.data))
         return counts[:n]
 
     def epochTensor(self, utterances=None, padded=True, pad=-1.0):
@@ -981,22 +861,10 @@ class BatchPlayer(object):
         queues behind a synthesize(wait=False) in flight and is waited for on the host; later calls are ordered by events alone."""
         import torch
         sel, n, _ = self._selection("epochTensor", utterances)
-        counts = self.epochCounts(utterances)
-        dev = self.device
-        if padded:
-            width = int(counts.max()) if n else 0
-            out = torch.empty((n, width, len(EPOCH_COLUMNS)), dtype=torch.float64, device="cuda:%d" % dev)
-            stride = width
-        else:
-            offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-            out = torch.empty((int(offsets[-1]), len(EPOCH_COLUMNS)), dtype=torch.float64, device="cuda:%d" % dev)
-            stride = 0
-        if out.numel():
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            got = self._check(self._dll.speechPlayer_batch_exportEpochs(self._h, None if sel is None else sel.ctypes.data, n, out.data_ptr(), stride,
-                                                                        float(pad), out.numel(), stream))
-            assert got == out.numel(), (got, out.numel())
-        return out, torch.from_numpy(counts if padded else offsets)
+
+        def call(out, stride, numel, stream):
+            return self._dll.speechPlayer_batch_exportEpochs(self._h, _ptr(sel), n, out, stride, float(pad), numel, stream)
+        return self._export_rows(self.epochCounts(utterances), (len(EPOCH_COLUMNS),), torch.float64, padded, call)
 
     def setUtterancesShared(self, listStart, frames, minSamples, fadeSamples, listOf, userIndex=None, isNull=None, noiseSeed=None):
         """Frame lists that utterances share (speechPlayer_batch_setUtterancesShared): `listStart`/frames/... describe the lists as

@@ -399,3 +399,62 @@ def test_refusals_write_nothing_and_leave_the_batch_usable(small):
     bp.synthesize()
     assert bp.getLastIndex(0) == w.table(0)[-1, 47]
     bp.close()
+
+
+def test_export_kinds_share_the_slot_ring_across_streams_and_a_set_call():
+    """Every kind of export of the batch as set takes its staging slot from one ring of 16 (csrc/klatt_engine.hip: the export path), and
+    each test file drives one kind.  Here 2 * 16 + 1 = 33 exports cycle through tracks (with column 0: the voicePitch table), alignment,
+    units, source, epochs, response and stems on two streams that are never synchronised with the host, so the ring wraps twice with
+    exports in flight; a set call with a longer batch follows at once (the per-request records grow), then the same 33.  After one final
+    synchronise every tensor holds the bits the same call gives when made alone on a fresh BatchPlayer.  The batch: three utterances
+    from IPA text, one of an empty text, two of one list."""
+    import torch
+    import nvspeechplayer_amd as eng
+    kinds = [
+        lambda bp: bp.trackTensor([0, 5, "mark"], hop=16, dtype=torch.float64, padded=False)[0],
+        lambda bp: bp.alignmentTensor(["phoneme", "position"], hop=16)[0],
+        lambda bp: bp.unitTensor(hop=16, padded=False)[0],
+        lambda bp: bp.sourceTensor(["f0", "wave"], hop=16, phase=3400, padded=False)[0],
+        lambda bp: bp.epochTensor(padded=False)[0],
+        lambda bp: bp.responseTensor(8, hop=16, padded=False)[0],
+        lambda bp: bp.stemTensor(["voice", "output"])[0],
+    ]
+    # utterances 0 and 2 speak one list; utterance 1 is the 150 ms of silence behind an empty text: 3307 samples, no epochs, and no
+    # step at phase 3400 (a row without entries in the epoch table and in the source export)
+    specs = [dict(texts=[text, ""], textOf=[0, 1, 0], speed=4, noiseSeed=[5, 6, 7]) for text in ("ha", "hælou wɜːld")]
+
+    def bits(t):
+        return t.contiguous().view({8: torch.int64, 4: torch.int32}[t.element_size()])
+
+    want = []       # [batch][kind]: the call alone on a fresh player
+    for spec in specs:
+        row = []
+        for kind in kinds:
+            fresh = eng.BatchPlayer(22050)
+            fresh.setIpa(**spec)
+            row.append(kind(fresh))
+            torch.cuda.synchronize()
+            fresh.close()
+        want.append(row)
+    assert all(t.numel() > 0 for row in want for t in row)
+    assert want[1][0].shape[0] > want[0][0].shape[0]       # (the second batch is the longer one)
+
+    bp = eng.BatchPlayer(22050)
+    dev = "cuda:%d" % bp.device
+    streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+    got = []
+    for spec in specs:
+        bp.setIpa(**spec)       # (the second: straight behind 33 exports in flight)
+        row = []
+        for k in range(33):
+            with torch.cuda.stream(streams[k % 2]):
+                if k < 2:
+                    busy(20_000_000)       # the stream's exports queue up behind this
+                row.append(kinds[k % len(kinds)](bp))
+        got.append(row)
+    torch.cuda.synchronize()
+    for b, row in enumerate(got):
+        for k, t in enumerate(row):
+            w = want[b][k % len(kinds)]
+            assert t.shape == w.shape and t.dtype == w.dtype and torch.equal(bits(t), bits(w)), "batch %d export %d" % (b, k)
+    bp.close()

@@ -215,3 +215,13 @@ def test_global_options_are_checked():
     finally:
         eng.setGlobalOption("live_mode", 0)
         eng.setGlobalOption("live_alone", 1536)
+
+
+def test_export_planning_under_sanitizers(tmp_path):
+    """The host half of the export path (csrc/klatt_export.h: extents, packed row tables, list pieces, the staging block) against the
+    brute-force restatement in tests/native/check_export_plan.cpp, under AddressSanitizer + UBSan."""
+    exe = str(tmp_path / "check_export_plan")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "native", "check_export_plan.cpp"), "-o", exe])
+    out = subprocess.check_output([exe], stderr=subprocess.STDOUT).decode()
+    assert out.startswith("ok ") and "runtime error" not in out and "AddressSanitizer" not in out, out
