@@ -364,6 +364,51 @@ long long speechPlayer_batch_exportStems(speechPlayer_batch_t batch, const long 
  * library's, and the bits may differ.  Returns n, -1 on bad arguments (n < 0, sampleRate <= 0, a NULL array with n > 0). */
 long long speechPlayer_resonatorCoefficients(const double* frequency, const double* bandwidth, long long n, int anti, int sampleRate,
 	double* abc);
+/*
+ * The STFT and band (mel) spectrogram of a batch's PCM, on the step grid of the other exports.  For utterance u of a batch that has been
+ * synthesised since it was set, of length L and int16 PCM s(t):
+ *   steps     step j is centred on sample c = phase + j * hop; an utterance has ceil((L - phase) / hop) steps (0 when L <= phase): the
+ *             grid of speechPlayer_batch_exportTracks, row for row
+ *   frame     x[i] = (float)s(c - nFft/2 + i) / 32767.0f for i = 0 .. nFft-1 (the bits of speechPlayer_batch_exportPcm's format 1); a
+ *             sample outside 0 .. L-1 is +0 (torch.stft's center=True, pad_mode="constant"); the pool's padding and the neighbouring
+ *             utterance are never read as signal
+ *   window    window[nFft], a HOST array of doubles, each rounded to float32 once; NULL: the periodic Hann 0.5 - 0.5 cos(2 pi i / nFft),
+ *             evaluated in binary64 on the host.  xw[i] = x[i] * w[i], one float32 multiplication
+ *   transform X[k] = sum_i xw[i] exp(-2 pi i k / nFft) for k = 0 .. nFft/2, computed in float32 by the functions of csrc/klatt_spectrum.h,
+ *             which the host and the device compile from one source: a half-length complex radix-2 transform of the even / odd samples
+ *             and an unpacking pass, every operation rounded separately (no fused multiply-add), twiddles made once on the host in
+ *             binary64, rounded to float32 and uploaded in the export's stream order.  The definition is those function bodies;
+ *             speechPlayer_pcmSpectrogram executes them in a plain loop.  nFft is a power of two in 64 .. 4096
+ *   bin       p = re * re + im * im in float32 (two products, one sum); power 2: v = p; power 1: v = (float)sqrt((double)p), the binary64
+ *             square root correctly rounded on both sides
+ *   bands     bank[nBands][nFft/2 + 1], a HOST array of doubles, each rounded to float32; NULL: the bands are the bins.  Of every band the
+ *             first and last non-zero column are found on the host; band_b = sum of w[b][k] * v[k] over that column range in ascending k,
+ *             each term one product and one sum in float32, from +0; a band without a non-zero weight is +0
+ *   log       logScale == 0: the linear value.  Otherwise logScale * log10(max((double)value, floor)) in binary64, floor > 0 required:
+ *             10 gives power dB, 20 magnitude dB, 2.302585092994046 the natural logarithm
+ *   output    element (i, j, b) of [row][step][band]; format 0 float64 (widens linear values exactly), 1 float32 rounded to nearest
+ * Unlike the exports of the batch "as set" above, the result is a function of the batch's PCM: it depends on the mode and, in MODE_FAST,
+ * on whatever that mode's tolerance allows; it needs a synthesis launch.
+ *
+ * Host only, touches no device (like speechPlayer_frameResponse): the definition above on `length` samples of plain PCM,
+ * out[step][band] float64 -- the product's own CPU statement, which the device path is held to bit for bit on linear values (log10 is
+ * each side's library call).  Returns steps * bands (bands = nBands with a bank, nFft/2 + 1 without), -1 on bad arguments: those of the
+ * refusal list below that concern the request, length < 0, a NULL pcm with length > 0, a NULL out with steps > 0. */
+long long speechPlayer_pcmSpectrogram(const sample* pcm, long long length, int nFft, long long hop, long long phase, const double* window,
+	const double* bank, int nBands, int power, double logScale, double floor, double* out);
+/* The spectrogram of chosen utterances into caller-owned device memory on the caller's stream.  utterances (any order, repeats allowed,
+ * NULL: all), rowStride (in steps, +0 past the utterance's end; 0: the rows back to back), the return value (elements written; 0 writes
+ * nothing and needs no buffer), the device-memory and alignment checks (16-byte alignment takes the vector stores) and the
+ * sixteen-in-flight rule are those of speechPlayer_batch_exportTracks.  Ordering is that of speechPlayer_batch_exportPcm, by events and
+ * without a host wait: the export runs on `stream` behind the batch's last synthesis launch on all its streams, and the batch's next
+ * launch waits on the device for the export before it overwrites the pool.  One wavefront computes each step (csrc/klatt_spectrum.h).
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: no batch, a batch that has not been synthesised since it was set, nFft not a
+ * power of two in 64 .. 4096, hop <= 0, phase < 0, power outside {1, 2}, nBands <= 0 with a bank, a non-finite window or bank value,
+ * logScale != 0 with floor <= 0, a non-finite logScale or floor, an unknown format, an utterance number outside the batch, a rowStride
+ * below the largest step count, an output that is not device memory of the batch's device, misaligned to the element or too small. */
+long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int nFft,
+	long long hop, long long phase, const double* window, const double* bank, int nBands, int power, double logScale, double floor,
+	void* deviceOut, int format, long long rowStride, void* stream);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

@@ -60,6 +60,7 @@ EXPORTS = [
     "speechPlayer_batch_exportSource", "speechPlayer_batch_epochCounts", "speechPlayer_batch_exportEpochs",
     "speechPlayer_frameResponse", "speechPlayer_batch_exportResponse",
     "speechPlayer_batch_exportStems", "speechPlayer_resonatorCoefficients",
+    "speechPlayer_pcmSpectrogram", "speechPlayer_batch_exportSpectrogram",
 ]
 
 
@@ -372,6 +373,10 @@ def load():
     L.speechPlayer_batch_exportStems.argtypes = [vp, vp, i64, vp, i32, vp, i32, i64, vp]
     L.speechPlayer_resonatorCoefficients.restype = i64
     L.speechPlayer_resonatorCoefficients.argtypes = [vp, vp, i64, i32, i32, vp]
+    L.speechPlayer_pcmSpectrogram.restype = i64
+    L.speechPlayer_pcmSpectrogram.argtypes = [vp, i64, i32, i64, i64, vp, vp, i32, i32, f64, f64, vp]
+    L.speechPlayer_batch_exportSpectrogram.restype = i64
+    L.speechPlayer_batch_exportSpectrogram.argtypes = [vp, vp, i64, i32, i64, i64, vp, vp, i32, i32, f64, f64, vp, i32, i64, vp]
     _lib = L
     return L
 

@@ -20,6 +20,7 @@
 #include "klatt_source.h"
 #include "klatt_response.h"
 #include "klatt_stems.h"
+#include "klatt_spectrum.h"
 #include "klatt_export.h"
 
 #include <algorithm>
@@ -795,21 +796,28 @@ long long export_elements(const char* what, const ExportNouns& nouns, const Expo
 // One export's passage through a slot.  begin(): the slot (the host waits only if its last export is still in flight), the caller's
 // tables (`grow`) -- every allocation first: once a kernel is queued the slot's event must come to stand behind it -- then the
 // per-request records, the shared table's previous export, and the block's upload on the stream.  finish(): behind the launches.
+// An export of the batch's PCM (ofPcm: the spectrogram) reads the pool instead: it takes one of speechPlayer_batch_exportPcm's slots, which
+// the next launch waits for (wait_exports), and stands behind the batch's last launch (pcmReady) in place of the per-request records.
 struct ExportStage {
     Batch* b;
     hipStream_t st;
     const StageBlock& block;
     Batch::SharedTable* table;      // the order the export's shared table keeps (null: it uses none)
+    bool ofPcm;
     Batch::ExportSlot* slot = nullptr;
-    ExportStage(Batch* b, hipStream_t st, const StageBlock& block, Batch::SharedTable* table = nullptr) : b(b), st(st), block(block), table(table) {}
+    ExportStage(Batch* b, hipStream_t st, const StageBlock& block, Batch::SharedTable* table = nullptr, bool ofPcm = false)
+        : b(b), st(st), block(block), table(table), ofPcm(ofPcm) {}
     template <class Grow>
     int begin(Grow grow)
     {
-        slot = &b->trackSlot[b->trackNext++ % Batch::kExportSlots];
+        slot = ofPcm ? &b->exportSlot[b->exportNext++ % Batch::kExportSlots] : &b->trackSlot[b->trackNext++ % Batch::kExportSlots];
         if (slot->used) { HIP_TRY(hipEventSynchronize(slot->done)); slot->used = false; }
         if (slot->host.ensure(block.bytes()) || slot->dev.reserve(block.bytes())) return -1;
         if (grow()) return -1;
-        if (timeline_on_stream(b, st)) return -1;
+        if (ofPcm) {
+            HIP_TRY(hipEventRecord(b->pcmReady, b->stream));
+            HIP_TRY(hipStreamWaitEvent(st, b->pcmReady, 0));
+        } else if (timeline_on_stream(b, st)) return -1;
         if (table && table->wait(st)) return -1;
         block.copy_to(slot->host.ptr);
         HIP_TRY(hipMemcpyAsync(slot->dev.ptr, slot->host.ptr, block.bytes(), hipMemcpyHostToDevice, st));
@@ -5137,6 +5145,84 @@ long long speechPlayer_batch_exportStems(speechPlayer_batch_t batch, const long 
         A.columns = stage.device<int>(colsAt); A.nColumns = nColumns;
         A.rowStride = rowStride; A.out = deviceOut;
         hipLaunchKernelGGL(kernel, dim3((unsigned)((s.n + kLanes - 1) / kLanes)), dim3(kLanes), ldsBytes, st, A);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
+}
+
+// ---- STFT and band spectrogram of the PCM (klatt_spectrum.h) -----------------------------------------------------------------------------
+// Host only, touches no device: the definition of include/speechPlayer_batch.h on plain PCM, out[step][band], through the functions the
+// kernel is compiled from (klatt_spectrum.h).
+long long speechPlayer_pcmSpectrogram(const sample* pcm, long long length, int nFft, long long hop, long long phase, const double* window,
+                                      const double* bank, int nBands, int power, double logScale, double floor, double* out)
+{
+    begin_call();
+    if (length < 0 || hop <= 0 || phase < 0 || (length > 0 && !pcm)) { set_error("pcmSpectrogram: length %lld, hop %lld, phase %lld", length, hop, phase); return -1; }
+    try {
+        SpecPlan P;
+        std::string why;
+        if (!spec_plan(P, nFft, window, bank, nBands, power, logScale, floor, why)) { set_error("pcmSpectrogram: %s", why.c_str()); return -1; }
+        hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
+        if (align_steps_below(length, hop, phase) > 0 && !out) { set_error("pcmSpectrogram: no output"); return -1; }
+        static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
+        return spectrogram_host(reinterpret_cast<const int16_t*>(pcm), length, P, hop, phase, out);
+    } catch (const std::exception& e) { set_error("pcmSpectrogram: %s", e.what()); return -1; }
+}
+
+// The spectrogram of chosen utterances' PCM, one wavefront per step (klatt_spectrum.h).  It reads the pool, so it is ordered as
+// speechPlayer_batch_exportPcm is (ExportStage, ofPcm).  The staging block: rows | step starts and chunk rows (packed) | window |
+// twiddles | band weights | band ranges.
+long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int nFft,
+                                               long long hop, long long phase, const double* window, const double* bank, int nBands, int power,
+                                               double logScale, double floor, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    const char* what = "exportSpectrogram";
+    if (refuse_timing_only("speechPlayer_batch_exportSpectrogram")) return -1;
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("exportSpectrogram: format %d (0 float64, 1 float32)", format); return -1; }
+        if (step_request(what, hop, phase, rowStride)) return -1;
+        SpecPlan P;
+        std::string why;
+        if (!spec_plan(P, nFft, window, bank, nBands, power, logScale, floor, why)) { set_error("exportSpectrogram: %s", why.c_str()); return -1; }
+        ExportSelection s;
+        std::vector<SpecRow> rows;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long, long long u, long long) {
+                const long long L = (long long)b->lens[(size_t)u];
+                rows.push_back(SpecRow{b->outStart[(size_t)u], L, align_steps_below(L, hop, phase)});
+                return rows.back().steps;
+            })) return -1;
+        static constexpr ExportNouns kBandNouns{"largest step count", "steps", "bands"};
+        const long long elements = export_elements(what, kBandNouns, s, rowStride, P.nOut);
+        if (elements <= 0) return elements;
+        if (!b->launched) { set_error("exportSpectrogram: the batch has not been synthesised since it was set"); return -1; }
+        const size_t elSize = format ? sizeof(float) : sizeof(double);
+        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+
+        const bool packed = rowStride == 0;
+        std::vector<long long> words;
+        const RowTable table = packed ? packed_row_table(s.counts.data(), 0, s.n, kTimelineChunkLog2, words) : RowTable{0, 0};
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words), windowAt = block.add(P.window), twAt = block.add(P.tw),
+                  weightsAt = block.add(P.weights), rangeAt = block.add(P.range);
+        const auto kernel = format ? klatt_spectrogram<true> : klatt_spectrogram<false>;
+        ExportStage stage(b, st, block, nullptr, true);
+        if (stage.begin([&] { return ensure_lds_limit(reinterpret_cast<const void*>(kernel), kSpecLdsBudget); })) return -1;
+        SpecArgs A;
+        A.pool = b->dPcm.ptr; A.rows = stage.device<SpecRow>(rowsAt);
+        A.start = packed ? stage.device<long long>(wordsAt) + table.startOff : nullptr;
+        A.chunk = packed ? stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
+        A.rowStride = rowStride; A.nSteps = elements / P.nOut;
+        A.hop = hop; A.phase = phase;
+        A.window = stage.device<float>(windowAt); A.tw = stage.device<SpecCx>(twAt);
+        A.weights = stage.device<float>(weightsAt); A.range = stage.device<int>(rangeAt);
+        A.logN = P.logN; A.nOut = P.nOut; A.hasBank = P.hasBank; A.power = P.power;
+        A.logScale = P.logScale; A.floor = P.floor;
+        A.out = deviceOut; A.vec = reinterpret_cast<uintptr_t>(deviceOut) % 16 == 0;
+        const long long nGroups = (A.nSteps + kSpecWaves - 1) / kSpecWaves;
+        const unsigned grid = (unsigned)std::min<long long>(nGroups, 16ll * b->cus);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kSpecWaves), (size_t)kSpecWaves * spec_lds_wave(P.M), st, A);
         HIP_TRY(hipGetLastError());
         if (stage.finish()) return -1;
         return elements;

@@ -8,6 +8,7 @@ interface (include/speechPlayer_batch.h): many frame streams, one kernel launch.
 
 Everything here calls the HIP library through its C-ABI; there is no CPU path.
 """
+import math
 from ctypes import POINTER, Structure, byref, c_double, c_int, c_short, c_void_p, cast
 from ctypes import c_longlong as ctypes_longlong
 
@@ -539,6 +540,97 @@ def resonatorCoefficients(f, bw, sampleRate, anti=False):
     return out
 
 
+SPECTROGRAM_FFT = (64, 4096)      # nFft: a power of two in this range
+
+
+def check_spectrogram_request(nFft, hop, phase, window, bank, power, log, floor, dtype, what="spectrogramTensor"):
+    """The argument checks of BatchPlayer.spectrogramTensor and pcmSpectrogram that need no GPU: nFft a power of two in 64 .. 4096,
+    hop >= 1, phase >= 0, `window` None (periodic Hann) or nFft finite values, `bank` None (the bands are the bins) or finite
+    [bands >= 1, nFft / 2 + 1], power 1 or 2, `log` None, "db" (10 log10 of a power, 20 log10 of a magnitude), "ln" or a finite
+    number (the factor of log10; 0 means linear) with floor > 0 wherever there is a logarithm, dtype None / torch.float32 /
+    torch.float64 (pcmSpectrogram passes torch.float64).  Raises ValueError or TypeError.  Returns (nFft, hop, phase, window as a
+    float64 array or None, bank as a float64 [bands, nFft / 2 + 1] array or None, bands, power, logScale, floor, the export format:
+    0 float64, 1 float32)."""
+    if isinstance(nFft, bool) or not isinstance(nFft, (int, np.integer)):
+        raise ValueError("%s: nFft must be an integer, not %r" % (what, nFft))
+    nFft = int(nFft)
+    if not SPECTROGRAM_FFT[0] <= nFft <= SPECTROGRAM_FFT[1] or nFft & (nFft - 1):
+        raise ValueError("%s: nFft must be a power of two in %d .. %d, not %d" % ((what,) + SPECTROGRAM_FFT + (nFft,)))
+    hop, phase, fmt = _check_hop_phase_dtype(what, hop, phase, dtype, *_float_types())
+    if window is not None:
+        window = np.ascontiguousarray(_host_array(window, np.float64).reshape(-1))
+        if len(window) != nFft:
+            raise ValueError("%s: the window needs %d values, not %d" % (what, nFft, len(window)))
+        if not np.all(np.isfinite(window)):
+            raise ValueError("%s: every window value must be finite" % what)
+    bands = nFft // 2 + 1
+    if bank is not None:
+        bank = np.ascontiguousarray(_host_array(bank, np.float64))
+        if bank.ndim != 2 or bank.shape[0] < 1 or bank.shape[1] != nFft // 2 + 1:
+            raise ValueError("%s: the bank must be [bands >= 1, %d], not %s" % (what, nFft // 2 + 1, list(bank.shape)))
+        if not np.all(np.isfinite(bank)):
+            raise ValueError("%s: every bank value must be finite" % what)
+        bands = bank.shape[0]
+    if power not in (1, 2) or isinstance(power, bool):
+        raise ValueError("%s: power must be 1 or 2, not %r" % (what, power))
+    if log is None:
+        scale = 0.0
+    elif isinstance(log, str):
+        if log not in ("db", "ln"):
+            raise ValueError("%s: log must be None, 'db', 'ln' or a number, not %r" % (what, log))
+        scale = math.log(10.0) if log == "ln" else (10.0 if power == 2 else 20.0)
+    else:
+        scale = float(log)
+    floor = float(floor)
+    if not math.isfinite(scale) or not math.isfinite(floor):
+        raise ValueError("%s: log and floor must be finite (%r, %r)" % (what, log, floor))
+    if scale != 0.0 and not floor > 0.0:
+        raise ValueError("%s: a logarithm needs floor > 0, not %r" % (what, floor))
+    return nFft, hop, phase, window, bank, bands, int(power), scale, floor, fmt
+
+
+def pcmSpectrogram(pcm, nFft=1024, hop=256, phase=0, window=None, bank=None, power=2, log=None, floor=1e-10):
+    """The STFT / band spectrogram of int16 PCM on the host (speechPlayer_pcmSpectrogram; no GPU): -> float64 [steps, bands], by the
+    definition in include/speechPlayer_batch.h -- step j centred on sample phase + j * hop, zeros outside the signal, the float32
+    transform the device runs.  Arguments as BatchPlayer.spectrogramTensor's."""
+    import torch
+    s = np.ascontiguousarray(np.asarray(pcm))
+    if s.dtype != np.int16 or s.ndim != 1:
+        raise TypeError("pcmSpectrogram: pcm must be a one-dimensional int16 array, not %s %s" % (s.dtype, list(s.shape)))
+    nFft, hop, phase, window, bank, bands, power, scale, floor, _ = check_spectrogram_request(nFft, hop, phase, window, bank, power, log, floor,
+                                                                                             torch.float64, "pcmSpectrogram")
+    steps = (len(s) - phase + hop - 1) // hop if len(s) > phase else 0
+    out = np.zeros((steps, bands), np.float64)
+    got = _native.load().speechPlayer_pcmSpectrogram(s.ctypes.data if len(s) else None, len(s), nFft, hop, phase, _ptr(window), _ptr(bank),
+                                                     bands if bank is not None else 0, power, scale, floor, out.ctypes.data if out.size else None)
+    if got < 0:
+        raise RuntimeError(_native.last_error())
+    assert got == out.size, (got, out.size)
+    return out
+
+
+def melFilterbank(sampleRate, nFft, nMels, fmin=0.0, fmax=None, norm=None):
+    """A mel filterbank for spectrogramTensor / pcmSpectrogram (numpy, no GPU): float64 [nMels, nFft / 2 + 1].  HTK mel,
+    2595 log10(1 + f / 700); triangles between nMels + 2 points equally spaced in mel from fmin to fmax (None: sampleRate / 2), each
+    rising from 0 at one point to 1 at the next and falling to 0 at the one after, evaluated at the bin frequencies k sampleRate / nFft.
+    norm: None, or "slaney": row m times 2 / (f[m + 2] - f[m]), f in Hz."""
+    fmax = sampleRate / 2.0 if fmax is None else float(fmax)
+    fmin = float(fmin)
+    if int(nMels) < 1 or int(nFft) < 2 or not 0.0 <= fmin < fmax:
+        raise ValueError("melFilterbank: nMels %r, nFft %r, fmin %r, fmax %r" % (nMels, nFft, fmin, fmax))
+    if norm not in (None, "slaney"):
+        raise ValueError("melFilterbank: norm must be None or 'slaney', not %r" % (norm,))
+    mel = np.linspace(2595.0 * np.log10(1.0 + fmin / 700.0), 2595.0 * np.log10(1.0 + fmax / 700.0), int(nMels) + 2)
+    f = 700.0 * (10.0 ** (mel / 2595.0) - 1.0)
+    bins = np.arange(int(nFft) // 2 + 1, dtype=np.float64) * (float(sampleRate) / int(nFft))
+    up = (bins[None, :] - f[:-2, None]) / (f[1:-1] - f[:-2])[:, None]
+    down = (f[2:, None] - bins[None, :]) / (f[2:] - f[1:-1])[:, None]
+    bank = np.maximum(0.0, np.minimum(up, down))
+    if norm == "slaney":
+        bank = bank * (2.0 / (f[2:] - f[:-2]))[:, None]
+    return bank
+
+
 def check_option_value(name, value):
     """speechPlayer_batch_setOption takes a C int: a value outside its range would wrap without a word (2 ** 40 arrives as 0).  Returns
     int(value), or raises ValueError."""
@@ -809,6 +901,26 @@ class BatchPlayer(object):
             return self._dll.speechPlayer_batch_exportResponse(self._h, _ptr(sel), n, freqs.ctypes.data, len(freqs), ks.ctypes.data, len(ks),
                                                                1 if gain else 0, hop, phase, out, fmt, stride, stream)
         return self._export_rows(steps, (len(ks), len(freqs)), torch.float32 if fmt else torch.float64, padded, call)
+
+    def spectrogramTensor(self, nFft=1024, hop=256, phase=0, window=None, bank=None, power=2, log=None, floor=1e-10, utterances=None, dtype=None,
+                          padded=True):
+        """The STFT or band (mel) spectrogram of the batch's PCM as a torch tensor on the batch's device
+        (speechPlayer_batch_exportSpectrogram), filled on torch's current stream behind the synthesis without a host wait:
+        -> (spectrogram, steps).  Step j of an utterance is centred on its sample phase + j * hop -- the grid of trackTensor, row for row
+        -- with zeros outside the utterance; element [.., j, b] is band b of |X|^power: the nFft / 2 + 1 bins, or the rows of `bank`
+        ([bands, nFft / 2 + 1], e.g. melFilterbank).  window: nFft values (None: periodic Hann).  log: None (linear), "db", "ln" or the
+        factor of log10, applied to max(value, floor).  utterances, dtype and padded as trackTensor's: spectrogram is
+        [n, most steps, bands], zero past each utterance's end, and steps the n step counts; or [total steps, bands] and the n + 1
+        offsets (int64 CPU tensors).  The batch must have been synthesised since it was set; pcmSpectrogram is the same definition on
+        the host."""
+        import torch
+        nFft, hop, phase, window, bank, bands, power, scale, floor, fmt = check_spectrogram_request(nFft, hop, phase, window, bank, power, log, floor, dtype)
+        sel, n, steps = self._steps("spectrogramTensor", utterances, hop, phase)
+
+        def call(out, stride, numel, stream):
+            return self._dll.speechPlayer_batch_exportSpectrogram(self._h, _ptr(sel), n, nFft, hop, phase, _ptr(window), _ptr(bank),
+                                                                  bands if bank is not None else 0, power, scale, floor, out, fmt, stride, stream)
+        return self._export_rows(steps, (bands,), torch.float32 if fmt else torch.float64, padded, call)
 
     def stemTensor(self, columns, utterances=None, dtype=None, padded=True):
         """The signal stems as a torch tensor on the batch's device (speechPlayer_batch_exportStems), filled on torch's current stream
