@@ -1,0 +1,25 @@
+// klatt_consts.h -- the few constants that the kernels (klatt_device.h, klatt_lanepipe.h, klatt_plan.h) and the host-only planning of a
+// set call (klatt_batchplan.h) share.  Plain C++: no HIP include, so a native test can hold the planning to account on any machine.
+#pragma once
+
+#include <stdint.h>
+
+namespace klatt {
+
+constexpr int kLanes = 64;
+
+constexpr uint32_t FRAME_NULL = 1u;       // FrameMeta.flags
+constexpr uint32_t UTT_NEEDS_NOISE = 1u;  // UttDesc.flags
+constexpr uint32_t UTT_NO_NASAL = 2u;     // UttDesc.flags: caNP == 0 throughout, N0/NP finite and stable (klatt_lanepipe.h)
+constexpr uint32_t UTT_TRACKED = 4u;      // UttDesc.flags: noisy, every parameter finite, tracks planned
+constexpr uint32_t UTT_DIRECT = 8u;       // UttDesc.flags: noisy, every parameter finite and in the range of klatt_math.h, no tracks: direct stages (klatt_direct.h)
+constexpr int kUttKindShift = 8;          // UttDesc.flags bits 8..31 of a tracked utterance: the entry kinds (klatt_tracks) whose values change after the first sample
+                                          // of its first fade -- a kind outside the mask of every lane of a wavefront is loaded once and never again (flat stages)
+
+// FrameFacts.flags (klatt_plan.h)
+constexpr uint32_t FACT_NOISE = 1u;        // a noise gain is non-zero, or the parallel bank's coefficients may not be finite
+constexpr uint32_t FACT_NONFINITE = 2u;    // some parameter is NaN or infinite
+constexpr uint32_t FACT_NASAL = 4u;        // the nasal pair is coupled in, or could not be skipped safely
+constexpr uint32_t FACT_UNBOUNDED = 8u;    // a frequency or bandwidth outside the range of klatt_math.h, or a negative bandwidth (the direct stages)
+
+}  // namespace klatt

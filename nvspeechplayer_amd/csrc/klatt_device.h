@@ -31,12 +31,12 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "klatt_consts.h"
 #include "klatt_math.h"
 
 namespace klatt {
 
 constexpr int kNumParams = 47;
-constexpr int kLanes = 64;
 constexpr int kTile = 32;                 // samples per lane per output tile (64-byte row segments)
 constexpr int kTileStride = kTile * 2 + 8; // bytes per tile row; the pad keeps ds_write_b16 conflict-free
 constexpr int kSlots = 45;                // parameters 1..45 live in LDS slots 0..44
@@ -46,13 +46,6 @@ constexpr int kStateDoubles = 240;        // per-stream saved state (streaming p
 
 constexpr int MODE_EXACT = 0;
 constexpr int MODE_FAST = 1;
-
-constexpr uint32_t FRAME_NULL = 1u;       // FrameMeta.flags
-constexpr uint32_t UTT_NEEDS_NOISE = 1u;  // UttDesc.flags
-constexpr uint32_t UTT_TRACKED = 4u;      // UttDesc.flags: noisy, every parameter finite, tracks planned (2u: UTT_NO_NASAL, klatt_lanepipe.h)
-constexpr uint32_t UTT_DIRECT = 8u;       // UttDesc.flags: noisy, every parameter finite and in the range of klatt_math.h, no tracks: direct stages (klatt_direct.h)
-constexpr int kUttKindShift = 8;          // UttDesc.flags bits 8..31 of a tracked utterance: the entry kinds (klatt_tracks) whose values change after the first sample
-                                          // of its first fade -- a kind outside the mask of every lane of a wavefront is loaded once and never again (flat stages)
 
 struct FrameMeta {           // 16 B per frame; with the 376-B parameter vector: 392 B/frame read
     uint32_t minSamples;

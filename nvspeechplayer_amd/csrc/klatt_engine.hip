@@ -22,6 +22,7 @@
 #include "klatt_stems.h"
 #include "klatt_spectrum.h"
 #include "klatt_export.h"
+#include "klatt_batchplan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2813,18 +2814,26 @@ int speechPlayer_batch_setUtterancesShared(speechPlayer_batch_t batch, long long
     return batch_set_guarded("setUtterancesShared", batch, in);
 }
 
+// A batch of records over a shape table, with labels or without: `what` is the entry point's name in the messages.
+static int batch_set_records(const char* what, speechPlayer_batch_t batch, long long nShapes, const speechPlayer_frame_t* shapes, long long nLists,
+                             const long long* listStart, const speechPlayer_frameRecord_t* records, const speechPlayer_frameLabel_t* labels,
+                             long long nUtterances, const unsigned int* listOf, const unsigned int* noiseSeed)
+{
+    SetInput in;
+    in.nLists = nLists; in.listStart = listStart; in.records = records; in.nShapes = nShapes; in.shapes = shapes;
+    in.nUtt = nUtterances; in.listOf = listOf; in.seeds = noiseSeed; in.labels = labels;
+    if (nShapes < 0 || (nShapes > 0 && !shapes)) { begin_call(); set_error("%s: bad shape table", what); return -1; }
+    if (!records && nLists > 0 && listStart && listStart[nLists] > 0) { begin_call(); set_error("%s: no records", what); return -1; }
+    static const speechPlayer_frameRecord_t none = {0.0, 0.0, SPEECHPLAYER_RECORD_SILENCE, 0u, 0u, -1};
+    if (!in.records) in.records = &none;      // (an empty batch: the record path all the same)
+    return batch_set_guarded(what, batch, in);
+}
+
 int speechPlayer_batch_setRecords(speechPlayer_batch_t batch, long long nShapes, const speechPlayer_frame_t* shapes,
                                   long long nLists, const long long* listStart, const speechPlayer_frameRecord_t* records,
                                   long long nUtterances, const unsigned int* listOf, const unsigned int* noiseSeed)
 {
-    SetInput in;
-    in.nLists = nLists; in.listStart = listStart; in.records = records; in.nShapes = nShapes; in.shapes = shapes;
-    in.nUtt = nUtterances; in.listOf = listOf; in.seeds = noiseSeed;
-    if (nShapes < 0 || (nShapes > 0 && !shapes)) { begin_call(); set_error("setRecords: bad shape table"); return -1; }
-    if (!records && nLists > 0 && listStart && listStart[nLists] > 0) { begin_call(); set_error("setRecords: no records"); return -1; }
-    static const speechPlayer_frameRecord_t none = {0.0, 0.0, SPEECHPLAYER_RECORD_SILENCE, 0u, 0u, -1};
-    if (!in.records) in.records = &none;      // (an empty batch: the record path all the same)
-    return batch_set_guarded("setRecords", batch, in);
+    return batch_set_records("setRecords", batch, nShapes, shapes, nLists, listStart, records, nullptr, nUtterances, listOf, noiseSeed);
 }
 
 int speechPlayer_batch_setRecordsLabelled(speechPlayer_batch_t batch, long long nShapes, const speechPlayer_frame_t* shapes,
@@ -2832,15 +2841,7 @@ int speechPlayer_batch_setRecordsLabelled(speechPlayer_batch_t batch, long long 
                                           const speechPlayer_frameLabel_t* labels, long long nUtterances, const unsigned int* listOf,
                                           const unsigned int* noiseSeed)
 {
-    if (!labels) return speechPlayer_batch_setRecords(batch, nShapes, shapes, nLists, listStart, records, nUtterances, listOf, noiseSeed);
-    SetInput in;
-    in.nLists = nLists; in.listStart = listStart; in.records = records; in.nShapes = nShapes; in.shapes = shapes;
-    in.nUtt = nUtterances; in.listOf = listOf; in.seeds = noiseSeed; in.labels = labels;
-    if (nShapes < 0 || (nShapes > 0 && !shapes)) { begin_call(); set_error("setRecordsLabelled: bad shape table"); return -1; }
-    if (!records && nLists > 0 && listStart && listStart[nLists] > 0) { begin_call(); set_error("setRecordsLabelled: no records"); return -1; }
-    static const speechPlayer_frameRecord_t none = {0.0, 0.0, SPEECHPLAYER_RECORD_SILENCE, 0u, 0u, -1};
-    if (!in.records) in.records = &none;
-    return batch_set_guarded("setRecordsLabelled", batch, in);
+    return batch_set_records(labels ? "setRecordsLabelled" : "setRecords", batch, nShapes, shapes, nLists, listStart, records, labels, nUtterances, listOf, noiseSeed);
 }
 
 int speechPlayer_batch_hasLabels(speechPlayer_batch_t batch) { return batch ? (static_cast<Batch*>(batch)->hasLabels ? 1 : 0) : -1; }
@@ -2904,94 +2905,160 @@ static int device_shape_table(Batch* b, long long nL, const long long* listStart
     return 0;
 }
 
-static int batch_set(Batch* b, const SetInput& in)
+// The first bad index the threads of a parallel_ranges come across (-1: none).
+struct FirstBad {
+    std::atomic<long long> at{-1};
+    void mark(long long i) { long long none = -1; at.compare_exchange_strong(none, i); }
+    long long get() const { return at.load(); }
+};
+
+// Per-frame work arrays are kept between calls (per calling thread): a fresh 25-50 MB vector costs its page faults on first touch
+// and its unmapping on release -- together ~15 ms of a 65 ms call for BASELINE configs[2].  Every element is written before it
+// is read.  (Released again when a batch was very large: kScratchKeepFrames.)
+// (RawVector: resize() leaves new elements uninitialised, so a fresh array is first touched by the threads that fill it)
+constexpr long long kScratchKeepFrames = 4000000;
+struct SetScratch {
+    RawVector<FrameMeta> meta;
+    RawVector<FlatRef> flatRef;
+    RawVector<DirectJob> directJobs;
+    RawVector<FrameFacts> facts;
+};
+static SetScratch& set_scratch()
 {
-    const long long nL = in.nLists, nU = in.nUtt;
-    const long long* const listStart = in.listStart;
-    const unsigned int* const listOf = in.listOf;
-    const bool byRecords = in.records != nullptr;
-    const bool byDevice = in.deviceFrames != nullptr;
-    if (!b || nL < 0 || nU < 0 || !listStart) { set_error("set: bad arguments"); return -1; }
-    if (nU >= 0xFFFFFFFFll || nL >= 0xFFFFFFFFll) { set_error("set: too many utterances"); return -1; }
-    if (!listOf && nU != nL) { set_error("set: %lld utterances for %lld lists and no listOf", nU, nL); return -1; }
-    static const bool setTrace = getenv("SPEECHPLAYER_SET_TRACE") != nullptr;      // where the call's time goes, on stderr
-    const auto tSet = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (setTrace) fprintf(stderr, "[speechPlayer/set] %s: %.1f ms since the start\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tSet).count());
-    };
-    HIP_TRY(hipSetDevice(b->device));
-    // validate the index arrays before anything reads through them
-    if (listStart[0] != 0) { set_error("set: frameStart[0] must be 0"); return -1; }
-    for (long long l = 0; l < nL; ++l)
-        if (listStart[l + 1] < listStart[l]) { set_error("set: frameStart not monotone at %lld", l); return -1; }
-    const long long nF = listStart[nL];
-    if (nF > 0 && !byRecords && ((!in.frames && !byDevice) || !in.minDur || !in.fadeDur)) { set_error("set: bad frame arrays"); return -1; }
-    if (listOf) {
-        std::atomic<long long> bad{-1};
-        parallel_ranges(nU, 1 << 16, [&](long long a, long long e) {
-            for (long long u = a; u < e; ++u) if ((long long)listOf[u] >= nL) { long long none = -1; bad.compare_exchange_strong(none, u); }
-        });
-        if (bad.load() >= 0) { set_error("set: listOf[%lld] is not a list", bad.load()); return -1; }
-    }
-    if (byRecords) {
-        std::atomic<long long> bad{-1};
-        parallel_ranges(nF, 1 << 16, [&](long long a, long long e) {
-            for (long long k = a; k < e; ++k)
-                if (in.records[k].shape != SPEECHPLAYER_RECORD_SILENCE && (long long)in.records[k].shape >= in.nShapes) { long long none = -1; bad.compare_exchange_strong(none, k); }
-        });
-        if (bad.load() >= 0) { set_error("setRecords: record %lld names shape %u of %lld", bad.load(), in.records[bad.load()].shape, in.nShapes); return -1; }
-    }
-    // labels: the units of a list count from 0 and rise by at most one from frame to frame; unitFirst[] (klatt_align.h) from them
-    std::vector<uint32_t> unitFirst, listUnits;
-    if (in.labels) {
-        if (nF >= 0xFFFFFFFFll) { set_error("setRecordsLabelled: too many frames"); return -1; }
-        unitFirst.resize((size_t)(nF + nL)); listUnits.assign((size_t)nL, 0);
-        std::atomic<long long> bad{-1};
-        parallel_ranges(nL, 256, [&](long long la, long long le) {
-            for (long long l = la; l < le; ++l) {
-                uint32_t* uf = unitFirst.data() + listStart[l] + l;
-                int units = 0;
-                for (long long k = listStart[l]; k < listStart[l + 1]; ++k) {
-                    const int u = in.labels[k].unit;
-                    if (in.labels[k].phoneme < 0 || (u != units && !(units > 0 && u == units - 1))) { long long none = -1; bad.compare_exchange_strong(none, k); break; }
-                    if (u == units) uf[units++] = (uint32_t)(k - listStart[l]);
-                }
-                uf[units] = (uint32_t)(listStart[l + 1] - listStart[l]);
-                listUnits[(size_t)l] = (uint32_t)units;
-            }
-        });
-        if (bad.load() >= 0) {
-            set_error("setRecordsLabelled: label %lld (phoneme %d, unit %d): the units of a list count from 0 and rise by at most one, ids are not negative",
-                      bad.load(), in.labels[bad.load()].phoneme, in.labels[bad.load()].unit);
-            return -1;
-        }
-    }
-    auto list_of = [&](long long u) -> long long { return listOf ? (long long)listOf[u] : u; };
-    // everything below is built in locals and committed to the Batch only after the uploads succeeded: a call that fails
-    // validation leaves the previous batch in place, one that fails while uploading leaves an empty batch
-    // Per-frame work arrays are kept between calls (per calling thread): a fresh 25-50 MB vector costs its page faults on first touch
-    // and its unmapping on release -- together ~15 ms of a 65 ms call for BASELINE configs[2].  Every element is written below before it
-    // is read.  (Released again when a batch was very large: kScratchKeepFrames.)
-    constexpr long long kScratchKeepFrames = 4000000;
-    // (RawVector: resize() leaves new elements uninitialised, so a fresh array is first touched by the threads that fill it)
-    static thread_local RawVector<FrameMeta> metaScratch;
-    static thread_local RawVector<FlatRef> flatRefScratch;
-    static thread_local RawVector<DirectJob> directJobsScratch;
-    static thread_local RawVector<FrameFacts> factsScratch;
+    static thread_local SetScratch scratch;
+    return scratch;
+}
+
+// One set call: what its steps (batch_set) hand each other.  Everything is built here and committed to the Batch only after the
+// uploads succeeded: a call that fails validation leaves the previous batch in place, one that fails while uploading leaves an
+// empty batch.  The members are destroyed last to first: the staging thread is joined and the copy stream drained before anything
+// they may read goes away, the scratch is released last.
+struct SetCall {
+    Batch* const b;
+    const SetInput& in;
+    const long long nL, nU;
+    const long long* const listStart;
+    const bool byRecords, byDevice;
+    long long nF = 0;
+    const std::chrono::steady_clock::time_point tSet = std::chrono::steady_clock::now();
+
+    SetScratch& scratch = set_scratch();      // (a reference: the worker threads must write the CALLER's scratch, not their own thread_local one)
     struct ScratchRelease {
-        long long nF;
+        SetScratch& s;
+        long long nF = 0;
         ~ScratchRelease()
         {
             if (nF > kScratchKeepFrames) {
-                RawVector<FrameMeta>().swap(metaScratch); RawVector<FlatRef>().swap(flatRefScratch); RawVector<FrameFacts>().swap(factsScratch);
-                RawVector<DirectJob>().swap(directJobsScratch);
+                RawVector<FrameMeta>().swap(s.meta); RawVector<FlatRef>().swap(s.flatRef); RawVector<FrameFacts>().swap(s.facts);
+                RawVector<DirectJob>().swap(s.directJobs);
             }
         }
-    } scratchRelease{nF};
-    RawVector<FrameMeta>& meta = metaScratch;
+    } scratchRelease{scratch};
+    // labels: unitFirst[] (klatt_align.h) and the units per list
+    std::vector<uint32_t> unitFirst, listUnits;
+    // the frames on their way
+    bool framesPinned = false, earlyStarted = false;
+    int earlyRc = 0;
+    std::string earlyErr;
+    // while a DMA reads the caller's arrays no exit may leave it running: every return passes this guard
+    struct CopyGuard { Batch* b; bool armed = false; ~CopyGuard() { if (armed) (void)hipStreamSynchronize(b->copyStream); } } copyGuard{b};
+    std::thread early;
+    struct JoinEarly { std::thread& t; ~JoinEarly() { if (t.joinable()) t.join(); } } joinEarly{early};
+    // what the planning knows of every frame
+    const FrameFacts* facts = nullptr;
+    bool factsOnDevice = false;
+    // the plan
+    ListTable lists;
+    RouteOptions route;
+    std::vector<uint32_t> lens;                  // per utterance: its length
+    std::vector<long long> outStart, denseStart; // where its PCM goes in the pool; the utterances back to back: what speechPlayer_batch_readAll hands out
+    long long total = 0, pool = 0, spoken = 0;
+    TrackPlan plan;
+    std::vector<uint32_t> directFirst;
+    long long nDirectUtt = 0;
+    std::vector<UttDesc> utt;
+    std::vector<long long> uttFrameStart;
+    std::vector<uint32_t> uttFrames, uttList, uttSeed;
+    LanePacking lanes;
+    // Frames the planner recognised by their HASH are compared with the frame that first carried it, where the frames are (records
+    // need none of this: a shape number IS the values).  The verdict comes back with the upload's last synchronisation.
+    bool verify = false;
+    unsigned long long mismatchAt = ~0ull;
+
+    SetCall(Batch* b_, const SetInput& in_)
+        : b(b_), in(in_), nL(in_.nLists), nU(in_.nUtt), listStart(in_.listStart), byRecords(in_.records != nullptr), byDevice(in_.deviceFrames != nullptr) {}
+    long long list_of(long long u) const { return in.listOf ? (long long)in.listOf[u] : u; }
+    void lap(const char* what) const      // SPEECHPLAYER_SET_TRACE: where the call's time goes, on stderr
+    {
+        static const bool setTrace = getenv("SPEECHPLAYER_SET_TRACE") != nullptr;
+        if (setTrace) fprintf(stderr, "[speechPlayer/set] %s: %.1f ms since the start\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tSet).count());
+    }
+};
+
+// 1. The index arrays before anything reads through them; records, labels (unitFirst[], listUnits from them).
+static int set_validate(SetCall& c)
+{
+    const SetInput& in = c.in;
+    const long long nL = c.nL, nU = c.nU;
+    const long long* const listStart = c.listStart;
+    if (listStart[0] != 0) { set_error("set: frameStart[0] must be 0"); return -1; }
+    for (long long l = 0; l < nL; ++l)
+        if (listStart[l + 1] < listStart[l]) { set_error("set: frameStart not monotone at %lld", l); return -1; }
+    const long long nF = c.nF = listStart[nL];
+    if (nF > 0 && !c.byRecords && ((!in.frames && !c.byDevice) || !in.minDur || !in.fadeDur)) { set_error("set: bad frame arrays"); return -1; }
+    if (in.listOf) {
+        FirstBad bad;
+        parallel_ranges(nU, 1 << 16, [&](long long a, long long e) {
+            for (long long u = a; u < e; ++u) if ((long long)in.listOf[u] >= nL) bad.mark(u);
+        });
+        if (bad.get() >= 0) { set_error("set: listOf[%lld] is not a list", bad.get()); return -1; }
+    }
+    if (c.byRecords) {
+        FirstBad bad;
+        parallel_ranges(nF, 1 << 16, [&](long long a, long long e) {
+            for (long long k = a; k < e; ++k)
+                if (in.records[k].shape != SPEECHPLAYER_RECORD_SILENCE && (long long)in.records[k].shape >= in.nShapes) bad.mark(k);
+        });
+        if (bad.get() >= 0) { set_error("setRecords: record %lld names shape %u of %lld", bad.get(), in.records[bad.get()].shape, in.nShapes); return -1; }
+    }
+    // labels: the units of a list count from 0 and rise by at most one from frame to frame; unitFirst[] (klatt_align.h) from them
+    if (in.labels) {
+        if (nF >= 0xFFFFFFFFll) { set_error("setRecordsLabelled: too many frames"); return -1; }
+        c.unitFirst.resize((size_t)(nF + nL)); c.listUnits.assign((size_t)nL, 0);
+        FirstBad bad;
+        parallel_ranges(nL, 256, [&](long long la, long long le) {
+            for (long long l = la; l < le; ++l) {
+                uint32_t* uf = c.unitFirst.data() + listStart[l] + l;
+                int units = 0;
+                for (long long k = listStart[l]; k < listStart[l + 1]; ++k) {
+                    const int u = in.labels[k].unit;
+                    if (in.labels[k].phoneme < 0 || (u != units && !(units > 0 && u == units - 1))) { bad.mark(k); break; }
+                    if (u == units) uf[units++] = (uint32_t)(k - listStart[l]);
+                }
+                uf[units] = (uint32_t)(listStart[l + 1] - listStart[l]);
+                c.listUnits[(size_t)l] = (uint32_t)units;
+            }
+        });
+        if (bad.get() >= 0) {
+            set_error("setRecordsLabelled: label %lld (phoneme %d, unit %d): the units of a list count from 0 and rise by at most one, ids are not negative",
+                      bad.get(), in.labels[bad.get()].phoneme, in.labels[bad.get()].unit);
+            return -1;
+        }
+    }
+    return 0;
+}
+
+// 2. The meta word of every frame and, from the durations alone, the length of every list.
+static int set_meta_words(SetCall& c)
+{
+    const SetInput& in = c.in;
+    const long long nL = c.nL, nF = c.nF;
+    const long long* const listStart = c.listStart;
+    c.scratchRelease.nF = nF;
+    RawVector<FrameMeta>& meta = c.scratch.meta;
     meta.resize((size_t)nF);
     parallel_ranges(nF, 1 << 16, [&](long long a, long long e) {
-        if (byRecords)
+        if (c.byRecords)
             for (long long k = a; k < e; ++k) {
                 const speechPlayer_frameRecord_t& r = in.records[k];
                 meta[k].minSamples = r.minFrameDuration;
@@ -3007,44 +3074,38 @@ static int batch_set(Batch* b, const SetInput& in)
                 meta[k].flags = (in.isNull && in.isNull[k]) ? FRAME_NULL : 0u;
             }
     });
-    // per list, from the durations alone: its length (closed form, reference src/frame.cpp:41-80)
-    std::vector<uint32_t> lensL((size_t)nL, 0);
-    std::atomic<long long> tooLong{-1};
+    c.lists.lens.assign((size_t)nL, 0);
+    FirstBad tooLong;
     parallel_ranges(nL, 4096, [&](long long la, long long le) {
-        for (long long l = la; l < le; ++l) {
-            unsigned long long len = 0;
-            for (long long k = listStart[l]; k < listStart[l + 1]; ++k) {
-                const unsigned long long m = meta[k].minSamples, f = meta[k].fadeSamples;
-                len += std::max(m, f + 1) + 1;   // samples one request spans
-            }
-            if (len >= 0xFFFFFFFFull) { long long none = -1; tooLong.compare_exchange_strong(none, l); len = 0; }
-            lensL[l] = (uint32_t)len;
-        }
+        for (long long l = la; l < le; ++l)
+            if (!list_length(meta.data() + listStart[l], listStart[l + 1] - listStart[l], c.lists.lens[(size_t)l])) tooLong.mark(l);
     });
-    if (tooLong.load() >= 0) { set_error("utterance (frame list %lld) too long (4294967295 samples or more)", tooLong.load()); return -1; }
-    // From here on nothing but an allocation or a copy can fail (which leaves an empty batch).  The frames -- by far the largest upload
-    // of a batch of full frames, 0.6 GB for BASELINE configs[2] -- start on their way now: on a thread of their own from pageable memory
-    // (such a copy keeps its caller until it is done), as one asynchronous DMA from page-locked memory (speechPlayer_hostAlloc); records
-    // travel the same way (32 bytes per frame) with their shape table, and klatt_expand_frames builds frames and meta words behind them.
+    if (tooLong.get() >= 0) { set_error("utterance (frame list %lld) too long (4294967295 samples or more)", tooLong.get()); return -1; }
+    return 0;
+}
+
+// 3. From here on nothing but an allocation or a copy can fail (which leaves an empty batch).  The frames -- by far the largest upload
+// of a batch of full frames, 0.6 GB for BASELINE configs[2] -- start on their way now: on a thread of their own from pageable memory
+// (such a copy keeps its caller until it is done), as one asynchronous DMA from page-locked memory (speechPlayer_hostAlloc); records
+// travel the same way (32 bytes per frame) with their shape table, and klatt_expand_frames builds frames and meta words behind them.
+static int set_start_frames(SetCall& c)
+{
+    Batch* const b = c.b;
+    const SetInput& in = c.in;
+    const long long nL = c.nL, nF = c.nF;
     // the track exports in flight read the frames, meta words and list table this call replaces
-    const bool framesPinned = !byRecords && nF > 0 && is_pinned(in.frames);
+    c.framesPinned = !c.byRecords && nF > 0 && is_pinned(in.frames);
     {
         const bool grows = (size_t)nF * kNumParams > b->dFrames.cap || (size_t)nF > b->dMeta.cap || (size_t)nL + 1 > b->dListStart.cap ||
                            (in.labels && ((size_t)nF > b->dLabels.cap || (size_t)(nF + nL) > b->dUnitFirst.cap));
-        const bool unordered = !byRecords && !byDevice && !framesPinned;      // pageable frames: copied by a thread of their own, or staged by the runtime
+        const bool unordered = !c.byRecords && !c.byDevice && !c.framesPinned;      // pageable frames: copied by a thread of their own, or staged by the runtime
         if (settle_track_exports(b, grows || unordered)) return -1;
     }
-    int earlyRc = 0;
-    std::string earlyErr;
-    std::thread early;
-    bool earlyStarted = false;
-    // while a DMA reads the caller's arrays no exit may leave it running: every return below passes this guard
-    struct CopyGuard { Batch* b; bool armed = false; ~CopyGuard() { if (armed) (void)hipStreamSynchronize(b->copyStream); } } copyGuard{b};
-    if (byRecords) {
+    if (c.byRecords) {
         if (b->dFrames.reserve(std::max<size_t>((size_t)nF * kNumParams, 1)) || b->dMeta.reserve(std::max<size_t>((size_t)nF, 1)) ||
             b->dRecords.reserve(std::max<size_t>((size_t)nF, 1)) || b->dShapeTable.reserve(std::max<size_t>((size_t)in.nShapes * kNumParams, 1))) { batch_clear(b); return -1; }
         batch_clear(b);      // the batch on the device is the old frames with the new ones over them from now on: it no longer exists
-        copyGuard.armed = true;
+        c.copyGuard.armed = true;
         if (in.nShapes) HIP_TRY(hipMemcpyAsync(b->dShapeTable.ptr, in.shapes, (size_t)in.nShapes * sizeof(speechPlayer_frame_t), hipMemcpyHostToDevice, b->copyStream));
         if (nF) {
             HIP_TRY(hipMemcpyAsync(b->dRecords.ptr, in.records, (size_t)nF * sizeof(FrameRecord), hipMemcpyHostToDevice, b->copyStream));
@@ -3052,8 +3113,8 @@ static int batch_set(Batch* b, const SetInput& in)
             hipLaunchKernelGGL(klatt_expand_frames, dim3(grid), dim3(256), 0, b->copyStream, b->dRecords.ptr, b->dShapeTable.ptr, b->dFrames.ptr, b->dMeta.ptr, nF);
             HIP_TRY(hipGetLastError());
         }
-        earlyStarted = true;
-    } else if (byDevice && nF > 0) {
+        c.earlyStarted = true;
+    } else if (c.byDevice && nF > 0) {
         // frames in device memory: copied device to device on the copy stream, behind what the caller's stream has queued so far
         if (in.readyStream) {
             HIP_TRY(hipEventRecord(b->inputReady, in.readyStream));
@@ -3061,39 +3122,45 @@ static int batch_set(Batch* b, const SetInput& in)
         }
         if (b->dFrames.reserve((size_t)nF * kNumParams)) { batch_clear(b); return -1; }
         batch_clear(b);
-        copyGuard.armed = true;
+        c.copyGuard.armed = true;
         HIP_TRY(hipMemcpyAsync(b->dFrames.ptr, in.deviceFrames, (size_t)nF * kNumParams * sizeof(double), hipMemcpyDeviceToDevice, b->copyStream));
-        earlyStarted = true;
-    } else if (nF > 0 && (framesPinned || (size_t)nF * kNumParams * sizeof(double) >= (32u << 20))) {
+        c.earlyStarted = true;
+    } else if (nF > 0 && (c.framesPinned || (size_t)nF * kNumParams * sizeof(double) >= (32u << 20))) {
         if (b->dFrames.reserve((size_t)nF * kNumParams)) { batch_clear(b); return -1; }
         batch_clear(b);
-        if (framesPinned) {
-            copyGuard.armed = true;
+        if (c.framesPinned) {
+            c.copyGuard.armed = true;
             HIP_TRY(hipMemcpyAsync(b->dFrames.ptr, in.frames, (size_t)nF * kNumParams * sizeof(double), hipMemcpyHostToDevice, b->copyStream));
-            earlyStarted = true;
+            c.earlyStarted = true;
         } else
         try {
-            early = std::thread([&, dev = b->device, dst = b->dFrames.ptr]() {
+            c.early = std::thread([&c, frames = in.frames, nF, dev = b->device, dst = b->dFrames.ptr]() {
                 hipError_t e = hipSetDevice(dev);
-                if (e == hipSuccess) e = hipMemcpy(dst, in.frames, (size_t)nF * kNumParams * sizeof(double), hipMemcpyHostToDevice);
-                if (e != hipSuccess) { earlyRc = -1; earlyErr = hipGetErrorString(e); }
+                if (e == hipSuccess) e = hipMemcpy(dst, frames, (size_t)nF * kNumParams * sizeof(double), hipMemcpyHostToDevice);
+                if (e != hipSuccess) { c.earlyRc = -1; c.earlyErr = hipGetErrorString(e); }
             });
-            earlyStarted = true;
+            c.earlyStarted = true;
         } catch (const std::system_error&) {}
     }
-    struct JoinEarly { std::thread& t; ~JoinEarly() { if (t.joinable()) t.join(); } } joinEarly{early};
-    // What the planning needs to know of every frame (klatt_plan.h: a word of flags, and something that stands for its 45 shape values),
-    // in ONE pass.  Records: the flags of their shape (evaluated once per row of the table) and of their pitches; the shape's number
-    // stands for the values, exactly.  Frames on their way to the device as a DMA (page-locked memory) are looked at THERE, behind the
-    // copy on the same stream, and 24 bytes per frame come back: the host never reads them.  Pageable frames are read here, by the
-    // host's threads, while the staging thread copies them.
+    return 0;
+}
+
+// 4. What the planning needs to know of every frame (klatt_plan.h: a word of flags, and something that stands for its 45 shape values),
+// in ONE pass.  Records: the flags of their shape (evaluated once per row of the table) and of their pitches; the shape's number
+// stands for the values, exactly.  Frames on their way to the device as a DMA (page-locked memory) are looked at THERE, behind the
+// copy on the same stream, and 24 bytes per frame come back: the host never reads them (set_plan waits for them, as late as it can).
+// Pageable frames are read here, by the host's threads, while the staging thread copies them.
+static int set_frame_facts(SetCall& c)
+{
+    Batch* const b = c.b;
+    const SetInput& in = c.in;
+    const long long nF = c.nF;
     const double maxBwDirect = 690.0 * b->sampleRate / M_PI, maxFDirect = 9900.0 * b->sampleRate / (2.0 * M_PI);
-    const FrameFacts* facts = nullptr;
-    const bool factsOnDevice = (framesPinned || byDevice) && earlyStarted;
-    if (byRecords) {
+    c.factsOnDevice = (c.framesPinned || c.byDevice) && c.earlyStarted;
+    RawVector<FrameFacts>& fv = c.scratch.facts;
+    if (c.byRecords) {
         std::vector<uint32_t> shapeFl((size_t)in.nShapes);
         for (long long s = 0; s < in.nShapes; ++s) shapeFl[(size_t)s] = shape_flags(reinterpret_cast<const double*>(in.shapes + s), maxFDirect, maxBwDirect);
-        RawVector<FrameFacts>& fv = factsScratch;
         fv.resize((size_t)nF);
         parallel_ranges(nF, 1 << 15, [&](long long a, long long e) {
             for (long long k = a; k < e; ++k) {
@@ -3104,119 +3171,88 @@ static int batch_set(Batch* b, const SetInput& in)
                 fv[k] = f;
             }
         });
-        facts = fv.data();
-    } else if (factsOnDevice) {
+        c.facts = fv.data();
+    } else if (c.factsOnDevice) {
         if (b->dFacts.reserve((size_t)nF) || b->hFacts.ensure((size_t)nF * sizeof(FrameFacts))) return -1;
         const unsigned grid = (unsigned)std::min<long long>((nF + 255) / 256, 1 << 16);
         hipLaunchKernelGGL(klatt_frame_facts, dim3(grid), dim3(256), 0, b->copyStream, b->dFrames.ptr, b->dFacts.ptr, nF, maxFDirect, maxBwDirect);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(b->hFacts.ptr, b->dFacts.ptr, (size_t)nF * sizeof(FrameFacts), hipMemcpyDeviceToHost, b->copyStream));
-        facts = static_cast<const FrameFacts*>(b->hFacts.ptr);
+        c.facts = static_cast<const FrameFacts*>(b->hFacts.ptr);
     } else if (nF > 0) {
-        RawVector<FrameFacts>& fv = factsScratch;      // (a reference: the worker threads must write the CALLER's scratch, not their own thread_local one)
         fv.resize((size_t)nF);
         parallel_ranges(nF, 1 << 13, [&](long long a, long long e) {
             for (long long k = a; k < e; ++k) fv[k] = frame_facts(reinterpret_cast<const double*>(in.frames + k), maxFDirect, maxBwDirect);
         });
-        facts = fv.data();
+        c.facts = fv.data();
     }
-    // per utterance: its length, where its PCM goes
-    std::vector<uint32_t> lens((size_t)nU, 0);
-    std::vector<long long> outStart((size_t)nU + 1, 0);
-    std::vector<long long> denseStart((size_t)nU + 1);      // the utterances back to back: what speechPlayer_batch_readAll hands out
-    long long total = 0, pool = 0, spoken = 0;
+    return 0;
+}
+
+// 5. The plan (klatt_batchplan.h): per utterance its length and where its PCM goes; per list its timing, its class and the kernels
+// its utterances go to, with plan_tracks in the middle.
+static int set_plan(SetCall& c)
+{
+    Batch* const b = c.b;
+    const SetInput& in = c.in;
+    const long long nL = c.nL, nU = c.nU, nF = c.nF;
+    const long long* const listStart = c.listStart;
+    const FrameMeta* const meta = c.scratch.meta.data();
+    ListTable& lists = c.lists;
+    c.lens.assign((size_t)nU, 0);
+    c.outStart.assign((size_t)nU + 1, 0);
+    c.denseStart.resize((size_t)nU + 1);
     for (long long u = 0; u < nU; ++u) {
-        const long long l = list_of(u);
-        lens[u] = lensL[l];
-        outStart[u] = pool;
-        denseStart[u] = total;
-        total += (long long)lens[u];
-        pool += ((long long)lens[u] + kTile - 1) / kTile * kTile;
-        spoken += listStart[l + 1] - listStart[l];
+        const long long l = c.list_of(u);
+        c.lens[u] = lists.lens[l];
+        c.outStart[u] = c.pool;
+        c.denseStart[u] = c.total;
+        c.total += (long long)c.lens[u];
+        c.pool += ((long long)c.lens[u] + kTile - 1) / kTile * kTile;
+        c.spoken += listStart[l + 1] - listStart[l];
     }
-    outStart[nU] = pool;
-    denseStart[nU] = total;
+    c.outStart[nU] = c.pool;
+    c.denseStart[nU] = c.total;
     // how many utterances speak each list
-    std::vector<uint32_t> weight((size_t)nL, listOf ? 0u : 1u);
-    if (listOf) for (long long u = 0; u < nU; ++u) ++weight[listOf[u]];
-    lap("meta, lengths, frame facts started");
-    // A list's TIMING: a hash of its sequence of frame durations, fades and silences -- the same text at the same speed, whatever
-    // the pitch, the voice or the noise seed.  Lanes with one timing dequeue and fade on the same samples (lane packing, below).
-    std::vector<unsigned long long> timingL((size_t)nL);
+    lists.weight.assign((size_t)nL, in.listOf ? 0u : 1u);
+    if (in.listOf) for (long long u = 0; u < nU; ++u) ++lists.weight[in.listOf[u]];
+    c.lap("meta, lengths, frame facts started");
+    lists.timing.resize((size_t)nL);
     parallel_ranges(nL, 4096, [&](long long la, long long le) {
-        for (long long l = la; l < le; ++l) {
-            unsigned long long h = 0x9E3779B97F4A7C15ull ^ (unsigned long long)(listStart[l + 1] - listStart[l]);
-            for (long long k = listStart[l]; k < listStart[l + 1]; ++k) {
-                h ^= ((unsigned long long)meta[k].minSamples << 32) ^ meta[k].fadeSamples ^ ((unsigned long long)(meta[k].flags & FRAME_NULL) << 63);
-                h *= 0xFF51AFD7ED558CCDull; h ^= h >> 29;
-            }
-            timingL[l] = h;
-        }
+        for (long long l = la; l < le; ++l) lists.timing[l] = list_timing(meta + listStart[l], listStart[l + 1] - listStart[l]);
     });
-    // the facts are back (device path): per list, whether it needs its noise sources, whether it may skip the nasal pair, and -- for
-    // the tracks and the direct stages below -- whether all its parameters are finite (bit 0 of `shape`) and within the range of
-    // klatt_math.h (bit 1).  NULL frames carry no parameters of their own.
-    if (factsOnDevice) HIP_TRY(hipStreamSynchronize(b->copyStream));
-    std::vector<unsigned char> shapeL((size_t)nL, 0);
-    std::vector<uint32_t> flagsL((size_t)nL, 0);
+    // the facts are back (device path), only now: the timing hashes above needed none of them
+    if (c.factsOnDevice) HIP_TRY(hipStreamSynchronize(b->copyStream));
+    const FrameFacts* const facts = c.facts;
+    lists.shape.assign((size_t)nL, 0);
+    lists.flags.assign((size_t)nL, 0);
     parallel_ranges(nL, 4096, [&](long long la, long long le) {
-        for (long long l = la; l < le; ++l) {
-            uint32_t fl = 0;
-            for (long long k = listStart[l]; k < listStart[l + 1]; ++k)
-                if (!(meta[k].flags & FRAME_NULL)) fl |= facts[k].flags;
-            const bool finite = !(fl & FACT_NONFINITE), needsNoise = (fl & FACT_NOISE) || !finite;
-            flagsL[l] = needsNoise ? UTT_NEEDS_NOISE : (!(fl & FACT_NASAL) ? UTT_NO_NASAL : 0u);
-            shapeL[l] = finite ? (!(fl & FACT_UNBOUNDED) ? 3 : 1) : 0;
-        }
+        for (long long l = la; l < le; ++l)
+            classify_list(meta + listStart[l], facts + listStart[l], listStart[l + 1] - listStart[l], lists.flags[l], lists.shape[l]);
     });
-    lap("classification");
-    // how many utterances have a given (timing, length): lanes of such a run fade together
-    auto run_key = [&](long long l) { return timingL[l] ^ ((unsigned long long)lensL[l] * 0x9E3779B97F4A7C15ull); };
-    // A quiet utterance whose timing too few others share cannot fill a wavefront of the quiet kernels with lanes that fade together:
-    // its wavefront would run every chunk sample by sample, evaluating exp / cos for whichever lane is fading (a few workgroups that
-    // take longer than the whole flat launch: 24 ms for the 8192 quiet utterances of a batch with 65 536 different timings).  Such an
-    // utterance goes with the noisy ones instead -- same PCM (its noise gains are zero: the sources add exactly 0), flat stages.
-    constexpr long long kQuietRunMin = 32;
-    std::vector<std::pair<long long, uint32_t>> rerouted;      // (list, its flags as a quiet one): back to the quiet kernels if it gets no tracks
-    const bool wantTracks = b->tracks && !in.noTracks;
-    const bool wantDirect = b->direct && b->layout != 0 && nF > 0 && nF < 0xFFFFFFFFll;
-    if ((wantTracks || wantDirect) && nF > 0 && b->layout == -1) {      // (an explicit layout is taken at its word)
-        std::unordered_map<unsigned long long, long long> runOf;
-        for (long long l = 0; l < nL; ++l)
-            if (!(flagsL[l] & UTT_NEEDS_NOISE)) runOf[run_key(l)] += weight[l];
-        // (quiet utterances that ALL share one timing fade together however few they are: a single sentence, a handful of copies)
-        for (long long l = 0; l < nL && runOf.size() > 1; ++l)
-            if (!(flagsL[l] & UTT_NEEDS_NOISE) && runOf[run_key(l)] < kQuietRunMin) {
-                rerouted.emplace_back(l, flagsL[l]);
-                flagsL[l] = (flagsL[l] | UTT_NEEDS_NOISE) & ~UTT_NO_NASAL;
-            }
-    }
-    lap("timing hashes, quiet runs");
-    // ---- tracks (klatt_tracks.h) for the noisy lists whose parameters are all finite: plan_tracks ---------
-    // ---- and the direct stages (klatt_direct.h) for those among them that get none ------------------------
-    TrackPlan plan;
-    std::vector<unsigned char> eligible;
-    if ((wantTracks || wantDirect) && nF > 0) {
-        // A NaN anywhere ("hold" targets, reference src/utils.h:21) or an infinite parameter keeps an utterance with the untracked kernel.
-        // Finite parameters whose COEFFICIENTS overflow (a huge bandwidth or frequency) are tracked all the same: klatt_tracks evaluates
-        // the same expressions as the kernels' own coefficient code, so the track holds the same inf / NaN the kernel would have computed.
-        eligible.assign((size_t)nL, 0);
-        for (long long l = 0; l < nL; ++l)
-            if ((flagsL[l] & UTT_NEEDS_NOISE) && weight[l]) eligible[l] = shapeL[l];
-    }
-    lap("eligibility");
+    c.lap("classification");
+    RouteOptions& route = c.route;
+    route.tracks = b->tracks; route.direct = b->direct; route.layout = b->layout;
+    route.fast = b->mode == MODE_FAST; route.sortByLength = b->sortByLength != 0; route.noTracks = in.noTracks;
+    route.cus = b->cus; route.nFrames = nF;
+    const Rerouted rerouted = reroute_lonely_quiet(lists, route);
+    c.lap("timing hashes, quiet runs");
+    const std::vector<unsigned char> eligible = eligible_lists(lists, route);
+    c.lap("eligibility");
+    TrackPlan& plan = c.plan;
     FrameSource source{in.frames, in.records, in.shapes};
     RawVector<uint32_t> rowOf;
     std::vector<long long> shapeRep;
     std::vector<double> shapeRows;
-    if (wantTracks && nF > 0 && byDevice) {
-        if (device_shape_table(b, nL, listStart, meta.data(), facts, eligible.data(), rowOf, shapeRep, shapeRows)) return -1;
+    const bool wantTracks = route.want_tracks() && nF > 0;
+    if (wantTracks && c.byDevice) {
+        if (device_shape_table(b, nL, listStart, meta, facts, eligible.data(), rowOf, shapeRep, shapeRows)) return -1;
         source.shapes = reinterpret_cast<const speechPlayer_frame_t*>(shapeRows.data());
         source.rowOf = rowOf.data();
-        lap("shape table");
+        c.lap("shape table");
     }
-    if (wantTracks && nF > 0) {
-        plan_tracks(nL, listStart, source, facts, meta.data(), eligible.data(), b->trackBudgetMB, plan);
+    if (wantTracks) {
+        plan_tracks(nL, listStart, source, facts, meta, eligible.data(), b->trackBudgetMB, plan);
         if (source.rowOf && !plan.rep.empty()) {
             // every frame the planner took values for stands for the table's row: each is compared with the row's frame (klatt_verify_shared)
             parallel_ranges(nL, 4096, [&](long long la, long long le) {
@@ -3230,72 +3266,39 @@ static int batch_set(Batch* b, const SetInput& in)
                 }
             });
         }
-        lap("tracks planned");
-        // MODE_FAST, lanes that fade at unrelated times, tracks far beyond the caches (every fading lane streams through a track of its
-        // own: the jittered batch's 445 MB): the lean direct stages, whose pole recurrences compute what the tracks would deliver, are
-        // faster than the flat stages waiting for rows -- 18.4 against 21.8 ms (bench.py, jittered_durations) -- so such a batch is
-        // not tracked.  (MODE_EXACT keeps its tracks: the polynomials cost more than the rows' latency, 22 ms against ~35.)
-        bool useTracks = true;
-        if (wantDirect && b->direct == 1 && b->mode == MODE_FAST && plan.entries * sizeof(double2) > (128ull << 20)) {
-            std::unordered_map<unsigned long long, long long> runOf;
-            long long tracked = 0, direct = 0, inRuns = 0;
-            for (long long l = 0; l < nL; ++l)
-                if (plan.tracked[l]) { tracked += weight[l]; direct += (eligible[l] & 2) ? weight[l] : 0; runOf[run_key(l)] += weight[l]; }
-            for (const auto& kv : runOf) if (kv.second >= 32) inRuns += kv.second;
-            const long long groups = (tracked + kLanes - 1) / kLanes;
-            if (b->sortByLength && inRuns * 2 <= tracked && direct == tracked && groups > b->cus) useTracks = false;
-        }
-        if (useTracks)
-            for (long long l = 0; l < nL; ++l)
-                if (plan.tracked[l]) flagsL[l] |= UTT_TRACKED | (plan.kinds[l] << kUttKindShift);
-        if (!useTracks) { plan.jobs.clear(); plan.entries = 0; plan.tracked.assign((size_t)nL, 0); }
+        c.lap("tracks planned");
+        if (tracks_pay(lists, eligible.data(), plan.tracked.data(), plan.entries * sizeof(double2), route)) mark_tracked(lists, plan.tracked.data(), plan.kinds.data());
+        else { plan.jobs.clear(); plan.entries = 0; plan.tracked.assign((size_t)nL, 0); }
     }
-    if (wantDirect) {
-        // The direct stages are for lanes that fade at unrelated times.  A group whose wavefronts hold equally timed utterances (the
-        // BASELINE recipes without their tracks, a batch of few sentences in many voices) runs whole chunks on the uniform paths of the
-        // stages with the frame state machine, two workgroups per CU, and is faster there (cfg2 without tracks 13.9 against 19.1 ms,
-        // DESIGN.md section 4.7): "direct" = 1 decides by the share of the candidates that sit in runs of 32 or more equally long,
-        // equally timed utterances; 2 takes the direct stages whatever the timing.
-        bool take = true;
-        b->directAligned = false;
-        {
-            std::unordered_map<unsigned long long, long long> runOf;
-            long long candidates = 0, inRuns = 0;
-            for (long long l = 0; l < nL; ++l)
-                if ((eligible[l] & 2) && !(flagsL[l] & UTT_TRACKED)) { candidates += weight[l]; runOf[run_key(l)] += weight[l]; }
-            for (const auto& kv : runOf) if (kv.second >= 32) inRuns += kv.second;
-            // (without the sort by length and timing nothing is side by side; in MODE_FAST the direct stages advance coefficients by
-            // recurrences and win on the aligned batches whose fades move everything too -- "distinct" 19.2 -> 15.9 ms -- while a batch
-            // of few moving kinds loses 8 % there: cfg2 without its tracks 12.7 -> 13.7)
-            b->directAligned = b->sortByLength && inRuns * 2 > candidates;
-            if (b->direct == 1) take = !b->directAligned || b->mode == MODE_FAST;
-        }
-        if (take)
-            for (long long l = 0; l < nL; ++l)
-                if ((eligible[l] & 2) && !(flagsL[l] & UTT_TRACKED)) flagsL[l] |= UTT_DIRECT;
-    }
-    // (a re-routed quiet list that got neither tracks nor the direct stages goes back to the quiet kernels)
-    for (const auto& r : rerouted)
-        if (!(flagsL[r.first] & (UTT_TRACKED | UTT_DIRECT))) flagsL[r.first] = r.second;
-    // the direct lists' fades: per frame where its fade starts from and ends on (reference src/frame.cpp:55-72: silence keeps
-    // the previous request's values with the gain gated off; the first frame after silence starts from its own values with the gain
-    // gated off; any other frame fades from the previous request's values) -- klatt_seeds reads the values themselves on the device
-    RawVector<DirectJob>& directJobs = directJobsScratch;
+    if (route.want_direct()) b->directAligned = route_direct(lists, eligible.data(), route);
+    restore_rerouted(lists, rerouted);
+    return 0;
+}
+
+// 6. The direct lists' fades: per frame where its fade starts from and ends on (reference src/frame.cpp:55-72: silence keeps
+// the previous request's values with the gain gated off; the first frame after silence starts from its own values with the gain
+// gated off; any other frame fades from the previous request's values) -- klatt_seeds reads the values themselves on the device.
+// And what a flat stage needs of a frame when its fade starts (FlatRef), where there are tracks.
+static void set_direct_jobs_and_refs(SetCall& c)
+{
+    const long long nL = c.nL, nU = c.nU, nF = c.nF;
+    const long long* const listStart = c.listStart;
+    const RawVector<FrameMeta>& meta = c.scratch.meta;
+    const TrackPlan& plan = c.plan;
+    RawVector<DirectJob>& directJobs = c.scratch.directJobs;
     directJobs.clear();
-    std::vector<uint32_t> directFirstL, directFirst;
-    long long nDirectUtt = 0;
-    if (wantDirect) {
-        directFirstL.assign((size_t)nL, 0u);
+    if (c.route.want_direct()) {
+        std::vector<uint32_t> directFirstL((size_t)nL, 0u);
         for (long long l = 0; l < nL; ++l) {
-            if (!(flagsL[l] & UTT_DIRECT)) continue;
-            nDirectUtt += weight[l];
+            if (!(c.lists.flags[l] & UTT_DIRECT)) continue;
+            c.nDirectUtt += c.lists.weight[l];
             directFirstL[l] = (uint32_t)directJobs.size();
             walk_fade_ends(listStart[l], listStart[l + 1], meta.data(), directJobs);
         }
-        directFirst.resize((size_t)nU);
-        parallel_ranges(nU, 1 << 16, [&](long long a, long long e) { for (long long u = a; u < e; ++u) directFirst[u] = directFirstL[list_of(u)]; });
+        c.directFirst.resize((size_t)nU);
+        parallel_ranges(nU, 1 << 16, [&](long long a, long long e) { for (long long u = a; u < e; ++u) c.directFirst[u] = directFirstL[c.list_of(u)]; });
     }
-    RawVector<FlatRef>& flatRef = flatRefScratch;
+    RawVector<FlatRef>& flatRef = c.scratch.flatRef;
     if (!plan.jobs.empty()) {
         flatRef.resize((size_t)nF);
         parallel_ranges(nF, 1 << 16, [&](long long ka, long long ke) {
@@ -3305,250 +3308,129 @@ static int batch_set(Batch* b, const SetInput& in)
         }
         });
     }
-    lap("direct jobs, flat / source references");
-    // the utterances, each with its list's frames, flags and length
-    std::vector<UttDesc> utt((size_t)nU);
-    std::vector<long long> uttFrameStart((size_t)nU);
-    std::vector<uint32_t> uttFrames((size_t)nU);
+    c.lap("direct jobs, flat / source references");
+}
+
+// 7. The utterances, each with its list's frames, flags and length, in their lanes (klatt_batchplan.h, pack_lanes).
+static void set_lanes(SetCall& c)
+{
+    const SetInput& in = c.in;
+    const long long nU = c.nU;
+    const long long* const listStart = c.listStart;
+    c.utt.resize((size_t)nU); c.uttFrameStart.resize((size_t)nU); c.uttFrames.resize((size_t)nU); c.uttList.resize((size_t)nU); c.uttSeed.resize((size_t)nU);
     parallel_ranges(nU, 1 << 15, [&](long long a, long long e) {
         for (long long u = a; u < e; ++u) {
-            const long long l = list_of(u);
+            const long long l = c.list_of(u);
             UttDesc d;
             d.frameStart = listStart[l];
-            d.outStart = outStart[u];
+            d.outStart = c.outStart[u];
             d.nFrames = (uint32_t)(listStart[l + 1] - listStart[l]);
             d.seed = in.seeds ? in.seeds[u] : (uint32_t)u;
-            d.flags = flagsL[l];
-            d.length = lensL[l];
-            utt[u] = d;
-            uttFrameStart[u] = d.frameStart; uttFrames[u] = d.nFrames;
+            d.flags = c.lists.flags[l];
+            d.length = c.lists.lens[l];
+            c.utt[u] = d;
+            c.uttFrameStart[u] = d.frameStart; c.uttFrames[u] = d.nFrames; c.uttList[u] = (uint32_t)l; c.uttSeed[u] = d.seed;
         }
     });
-    std::vector<TrackJob>& jobs = plan.jobs;
-    const unsigned long long trackEntries = plan.entries;
-    // lane packing: similar lengths share a wavefront (longest first), so lanes finish together
-    // (within the quiet group and within the noisy group, which are launched as separate kernels)
     std::vector<unsigned long long> timing;      // per utterance (its list's)
-    if (listOf) { timing.resize((size_t)nU); for (long long u = 0; u < nU; ++u) timing[u] = timingL[listOf[u]]; }
-    else timing.swap(timingL);
-    std::vector<uint32_t> order((size_t)nU);
-    std::iota(order.begin(), order.end(), 0u);
-    auto quietEnd = std::stable_partition(order.begin(), order.end(), [&](uint32_t x) { return !(utt[x].flags & UTT_NEEDS_NOISE); });
-    const long long nQuiet = quietEnd - order.begin();
-    auto noNasalEnd = std::stable_partition(order.begin(), quietEnd, [&](uint32_t x) { return (utt[x].flags & UTT_NO_NASAL) != 0; });
-    const long long nNoNasal = noNasalEnd - order.begin();
-    auto trackedEnd = std::stable_partition(quietEnd, order.end(), [&](uint32_t x) { return (utt[x].flags & UTT_TRACKED) != 0; });
-    const long long nTrackedUtt = trackedEnd - quietEnd;
-    long long nTracked = nTrackedUtt;      // slots of the tracked group (utterances + padding, below)
-    auto directEnd = std::stable_partition(trackedEnd, order.end(), [&](uint32_t x) { return (utt[x].flags & UTT_DIRECT) != 0; });
-    long long nDirectSlots = directEnd - trackedEnd;      // slots of the direct group (utterances + padding to whole wavefronts, below)
-    if (b->sortByLength) {
-        // Within a group: longest first, and utterances with the same TIMING (the same sequence of frame durations, fades and
-        // silences: the same text at the same speed, whatever the pitch, the voice or the noise seed) side by side.  Lanes
-        // with one timing dequeue and fade on the same samples, so their wavefront runs whole chunks on the uniform paths.
-        auto before = [&](uint32_t x, uint32_t y) { return lens[x] != lens[y] ? lens[x] > lens[y] : timing[x] < timing[y]; };
-        std::stable_sort(order.begin(), noNasalEnd, before);
-        std::stable_sort(noNasalEnd, quietEnd, before);
-        std::stable_sort(quietEnd, trackedEnd, before);
-        std::stable_sort(trackedEnd, directEnd, before);
-        std::stable_sort(directEnd, order.end(), before);
-        // The noisy groups (64 utterances per wavefront): a wavefront that holds two timings runs every chunk on the general
-        // path -- ~2.6 times the time of a pure one for the whole length of its utterances, and it is the last to finish.  So a
-        // run of equally timed utterances that filled at least a quarter of its last wavefront, or that is followed by a run
-        // of 64 or more, ends its wavefront there: the remaining lanes stay empty (order slot 0xFFFFFFFF).  Batches of
-        // utterances that are all different (runs of 1) are packed densely, as before.
-        auto pad_runs = [&](std::vector<uint32_t>::iterator first, std::vector<uint32_t>::iterator last, std::vector<uint32_t>& out) {
-            size_t lanesOfRun = 0;     // lanes the current run occupies in the wavefront being filled
-            for (auto it = first; it != last;) {
-                auto runEnd = it;
-                while (runEnd != last && timing[*runEnd] == timing[*it] && lens[*runEnd] == lens[*it]) ++runEnd;
-                const size_t runSize = (size_t)(runEnd - it), fill = out.size() % kLanes;
-                if (fill != 0 && (lanesOfRun >= (size_t)kLanes / 4 || runSize >= (size_t)kLanes))
-                    out.insert(out.end(), kLanes - fill, 0xFFFFFFFFu);
-                out.insert(out.end(), it, runEnd);
-                const size_t tail = out.size() % kLanes;
-                lanesOfRun = tail == 0 ? 0 : std::min(runSize, tail);
-                it = runEnd;
-            }
-        };
-        std::vector<uint32_t> tracked, direct(trackedEnd, directEnd), untracked;
-        pad_runs(quietEnd, trackedEnd, tracked);
-        if (!tracked.empty() && trackedEnd != order.end()) tracked.insert(tracked.end(), (kLanes - tracked.size() % kLanes) % kLanes, 0xFFFFFFFFu);   // the next group starts its own wavefront
-        // (the direct stages do not care whether their lanes fade together: packed densely, longest first)
-        if (!direct.empty() && directEnd != order.end()) direct.insert(direct.end(), (kLanes - direct.size() % kLanes) % kLanes, 0xFFFFFFFFu);
-        pad_runs(directEnd, order.end(), untracked);
-        nTracked = (long long)tracked.size();
-        nDirectSlots = (long long)direct.size();
-        order.resize((size_t)nQuiet);
-        order.insert(order.end(), tracked.begin(), tracked.end());
-        order.insert(order.end(), direct.begin(), direct.end());
-        order.insert(order.end(), untracked.begin(), untracked.end());
-    } else if (nDirectSlots > 0 && directEnd != order.end()) {
-        // unsorted: the groups still start on wavefront boundaries (each is a launch of its own)
-        std::vector<uint32_t> head(order.begin(), directEnd), tail(directEnd, order.end());
-        const size_t padT = nTrackedUtt > 0 ? (size_t)((kLanes - nTrackedUtt % kLanes) % kLanes) : 0;
-        head.insert(head.begin() + nQuiet + nTrackedUtt, padT, 0xFFFFFFFFu);
-        nTracked = nTrackedUtt + (long long)padT;
-        const size_t padD = (size_t)((kLanes - nDirectSlots % kLanes) % kLanes);
-        head.insert(head.end(), padD, 0xFFFFFFFFu);
-        nDirectSlots += (long long)padD;
-        order.swap(head);
-        order.insert(order.end(), tail.begin(), tail.end());
-    } else if (nDirectSlots > 0 && nTrackedUtt > 0) {
-        const size_t padT = (size_t)((kLanes - nTrackedUtt % kLanes) % kLanes);
-        order.insert(order.begin() + nQuiet + nTrackedUtt, padT, 0xFFFFFFFFu);
-        nTracked = nTrackedUtt + (long long)padT;
-    }
-    // A wavefront with FEW live lanes takes up to 1.7 times as long as a full one for the same instructions (measured:
-    // streams_synthesize, tools/lone_probe2.py: 1 .. 8 live lanes 4.3 / 6.1 / 7.4 ms from launch to launch, 16 or more a steady 4.13).  Its
-    // empty slots are given its own utterances again: those lanes compute the same samples and store the same bytes to the same places.
-    // (What a batch of a handful of sentences -- or the tail of a large one -- costs in latency; nothing for full wavefronts.)
-    constexpr int kSparse = 32;      // (16 live lanes still wavered a little: 4.32 against 4.15 ms)
-    long long nQuietSlots = nQuiet, nNoNasalSlots = nNoNasal;
-    {
-        // the two quiet groups are packed densely: only their LAST wavefront can be sparse (one vowel alone: 46 ns per sample against 31)
-        auto fill_tail = [&](long long begin, long long end) -> long long {
-            const long long n = end - begin, tail = n % kLanes;
-            if (n == 0 || tail == 0 || tail >= kSparse) return 0;
-            const long long ext = kLanes - tail;
-            std::vector<uint32_t> rep((size_t)ext);
-            for (long long j = 0; j < ext; ++j) rep[(size_t)j] = order[(size_t)(end - tail + j % tail)];
-            order.insert(order.begin() + end, rep.begin(), rep.end());
-            return ext;
-        };
-        const long long e1 = fill_tail(0, nNoNasal);
-        nNoNasalSlots += e1; nQuietSlots += e1;
-        nQuietSlots += fill_tail(nNoNasalSlots, nQuietSlots);
-        const long long noisy0 = nQuietSlots;
-        const bool tailNoisy = (long long)order.size() > noisy0;
-        if (tailNoisy && ((long long)order.size() - noisy0) % kLanes != 0) {
-            // the last wavefront's dead lanes become slots of the group that ends there
-            const long long ext = kLanes - ((long long)order.size() - noisy0) % kLanes;
-            const long long legacy = (long long)order.size() - nQuietSlots - nTracked - nDirectSlots;
-            if (legacy <= 0) { if (nDirectSlots > 0) nDirectSlots += ext; else nTracked += ext; }
-            order.insert(order.end(), (size_t)ext, 0xFFFFFFFFu);
-        }
-        for (long long w = noisy0; w + kLanes <= (long long)order.size(); w += kLanes) {
-            uint32_t liveU[kSparse];
-            int nLive = 0;
-            for (int i = 0; i < kLanes && nLive < kSparse; ++i)
-                if (order[(size_t)(w + i)] != 0xFFFFFFFFu) liveU[nLive++] = order[(size_t)(w + i)];
-            if (nLive == 0 || nLive >= kSparse) continue;
-            int next = 0;
-            for (int i = 0; i < kLanes; ++i)
-                if (order[(size_t)(w + i)] == 0xFFFFFFFFu) { order[(size_t)(w + i)] = liveU[next]; next = (next + 1) % nLive; }
-        }
-    }
-    const long long nSlotsAll = (long long)order.size();
-    lap("lane packing");
+    if (in.listOf) { timing.resize((size_t)nU); for (long long u = 0; u < nU; ++u) timing[u] = c.lists.timing[in.listOf[u]]; }
+    else timing.swap(c.lists.timing);
+    c.lanes = pack_lanes(nU, [&](uint32_t u) { return c.utt[u].flags; }, c.lens.data(), timing.data(), c.b->sortByLength != 0);
+    c.lap("lane packing");
+}
 
-    // Frames the planner recognised by their HASH are compared with the frame that first carried it, where the frames are (records
-    // need none of this: a shape number IS the values).  The verdict comes back with the upload's last synchronisation.
-    const bool verify = !byRecords && nTrackedUtt > 0 && !plan.rep.empty();
-    unsigned long long mismatchAt = ~0ull;
-
-    auto upload = [&]() -> int {
-        if ((size_t)pool > b->dPcm.cap && sync_exports(b)) return -1;      // (a new pool: the old one is freed once no export reads it)
-        if (b->dFrames.reserve(std::max<size_t>((size_t)nF * kNumParams, 1)) || b->dMeta.reserve(std::max<size_t>(nF, 1)) ||
-            b->dUtt.reserve(std::max<size_t>(nU, 1)) || b->dOrder.reserve(std::max<size_t>(nSlotsAll, 1)) ||
-            b->dResult.reserve(std::max<size_t>(nU, 1)) || b->dPcm.reserve(std::max<size_t>(pool, 1)) || b->dListStart.reserve((size_t)nL + 1))
-            return -1;
-        HIP_TRY(hipMemcpyAsync(b->dListStart.ptr, listStart, ((size_t)nL + 1) * sizeof(long long), hipMemcpyHostToDevice, b->stream));
-        if (nTrackedUtt > 0) {
-            if (b->dFlatRef.reserve((size_t)nF) || b->dJobs.reserve(jobs.size()) || b->dShapes.reserve(plan.shapes.size()) ||
-                b->dTrack.reserve((size_t)trackEntries + kTrackPad)) return -1;
-            HIP_TRY(hipMemcpyAsync(b->dShapes.ptr, plan.shapes.data(), plan.shapes.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
-            HIP_TRY(hipMemcpyAsync(b->dFlatRef.ptr, flatRef.data(), (size_t)nF * sizeof(FlatRef), hipMemcpyHostToDevice, b->stream));
-            HIP_TRY(hipMemcpyAsync(b->dJobs.ptr, jobs.data(), jobs.size() * sizeof(TrackJob), hipMemcpyHostToDevice, b->stream));
-        }
-        if (nTrackedUtt > 0 || nDirectUtt > 0) {
-            if (b->dSourceRef.reserve((size_t)nF)) return -1;
-        }
-        if (nDirectUtt > 0) {
-            const size_t nD = directJobs.size();
-            if (b->dDirectJobs.reserve(nD) || b->dDirectFirst.reserve((size_t)nU) || b->dDirectHdr.reserve((size_t)kDirectStages * nD) ||
-                b->dDirectRec.reserve((size_t)kDirectEntries * nD)) return -1;
-            HIP_TRY(hipMemcpyAsync(b->dDirectJobs.ptr, directJobs.data(), nD * sizeof(DirectJob), hipMemcpyHostToDevice, b->stream));
-            HIP_TRY(hipMemcpyAsync(b->dDirectFirst.ptr, directFirst.data(), (size_t)nU * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-        }
-        if (nF) {
-            if (!earlyStarted) HIP_TRY(hipMemcpyAsync(b->dFrames.ptr, in.frames, (size_t)nF * kNumParams * sizeof(double), hipMemcpyHostToDevice, b->stream));
-            if (!byRecords) HIP_TRY(hipMemcpyAsync(b->dMeta.ptr, meta.data(), (size_t)nF * sizeof(FrameMeta), hipMemcpyHostToDevice, b->stream));
-        }
-        if (nU) {
-            HIP_TRY(hipMemcpyAsync(b->dUtt.ptr, utt.data(), (size_t)nU * sizeof(UttDesc), hipMemcpyHostToDevice, b->stream));
-            HIP_TRY(hipMemcpyAsync(b->dOrder.ptr, order.data(), (size_t)nSlotsAll * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-            HIP_TRY(hipMemsetAsync(b->dResult.ptr, 0, (size_t)nU * sizeof(UttResult), b->stream));
-            if (b->dDenseStart.reserve((size_t)nU + 1)) return -1;
-            HIP_TRY(hipMemcpyAsync(b->dDenseStart.ptr, denseStart.data(), ((size_t)nU + 1) * sizeof(long long), hipMemcpyHostToDevice, b->stream));
-        }
-        if (verify) {
-            if (b->dRep.reserve((size_t)nF) || b->dMismatch.reserve(1)) return -1;
-            HIP_TRY(hipMemcpyAsync(b->dRep.ptr, plan.rep.data(), (size_t)nF * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-            HIP_TRY(hipMemsetAsync(b->dMismatch.ptr, 0xFF, sizeof(unsigned long long), b->stream));
-        }
-        if (in.labels) {
-            // the labels and unitFirst[] (klatt_align.h) on the copy stream, ahead of setCopied; the wait below covers the arrays they leave
-            if (b->dLabels.reserve(std::max<size_t>((size_t)nF, 1)) || b->dUnitFirst.reserve(std::max<size_t>((size_t)(nF + nL), 1))) return -1;
-            copyGuard.armed = true;
-            if (nF) HIP_TRY(hipMemcpyAsync(b->dLabels.ptr, in.labels, (size_t)nF * sizeof(FrameLabel), hipMemcpyHostToDevice, b->copyStream));
-            if (nF + nL) HIP_TRY(hipMemcpyAsync(b->dUnitFirst.ptr, unitFirst.data(), (size_t)(nF + nL) * sizeof(uint32_t), hipMemcpyHostToDevice, b->copyStream));
-        }
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        if (copyGuard.armed) { HIP_TRY(hipStreamSynchronize(b->copyStream)); copyGuard.armed = false; }
-        if (early.joinable()) early.join();
-        if (earlyRc) { set_error_code(SPEECHPLAYER_ERR_HIP); set_error("set: uploading the frames failed: %s", earlyErr.c_str()); return -1; }
-        const unsigned grid = (unsigned)std::min<long long>((nF + 255) / 256, 1 << 16);
-        if (verify) {
-            hipLaunchKernelGGL(klatt_verify_shared, dim3(grid), dim3(256), 0, b->stream, b->dFrames.ptr, b->dRep.ptr, nF, b->dMismatch.ptr);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&mismatchAt, b->dMismatch.ptr, sizeof mismatchAt, hipMemcpyDeviceToHost, b->stream));
-        }
-        if (nTrackedUtt > 0 || nDirectUtt > 0) {
-            // what the flat and direct source stages read at a dequeue (SourceRef: pitch, pitch increment, 1 / fade, index mark), from the
-            // frames and durations now resident: 32 bytes per frame that no longer cross the link, and no third pass of the host over the frames
-            hipLaunchKernelGGL(klatt_source_refs, dim3(grid), dim3(256), 0, b->stream, b->dFrames.ptr, b->dMeta.ptr, b->dSourceRef.ptr, nF);
-            HIP_TRY(hipGetLastError());
-        }
-        if (verify || nTrackedUtt > 0 || nDirectUtt > 0) HIP_TRY(hipStreamSynchronize(b->stream));
-        return 0;
-    };
-    if (upload()) {
-        // the device buffers may hold a mix of the old and the new batch now: the object becomes an empty batch
-        batch_clear(b);
+// 8. Everything else goes up on the batch's stream, the labels on the copy stream ahead of setCopied; then the frames have arrived,
+// and what is computed from them where they are: the verdict on the hashed shapes, the source references.
+static int set_upload(SetCall& c)
+{
+    Batch* const b = c.b;
+    const SetInput& in = c.in;
+    const long long nL = c.nL, nU = c.nU, nF = c.nF, pool = c.pool, nSlotsAll = (long long)c.lanes.order.size();
+    const long long nTrackedUtt = c.lanes.nTrackedUtt, nDirectUtt = c.nDirectUtt;
+    const TrackPlan& plan = c.plan;
+    const RawVector<DirectJob>& directJobs = c.scratch.directJobs;
+    if ((size_t)pool > b->dPcm.cap && sync_exports(b)) return -1;      // (a new pool: the old one is freed once no export reads it)
+    if (b->dFrames.reserve(std::max<size_t>((size_t)nF * kNumParams, 1)) || b->dMeta.reserve(std::max<size_t>(nF, 1)) ||
+        b->dUtt.reserve(std::max<size_t>(nU, 1)) || b->dOrder.reserve(std::max<size_t>(nSlotsAll, 1)) ||
+        b->dResult.reserve(std::max<size_t>(nU, 1)) || b->dPcm.reserve(std::max<size_t>(pool, 1)) || b->dListStart.reserve((size_t)nL + 1))
         return -1;
+    HIP_TRY(hipMemcpyAsync(b->dListStart.ptr, c.listStart, ((size_t)nL + 1) * sizeof(long long), hipMemcpyHostToDevice, b->stream));
+    if (nTrackedUtt > 0) {
+        if (b->dFlatRef.reserve((size_t)nF) || b->dJobs.reserve(plan.jobs.size()) || b->dShapes.reserve(plan.shapes.size()) ||
+            b->dTrack.reserve((size_t)plan.entries + kTrackPad)) return -1;
+        HIP_TRY(hipMemcpyAsync(b->dShapes.ptr, plan.shapes.data(), plan.shapes.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->dFlatRef.ptr, c.scratch.flatRef.data(), (size_t)nF * sizeof(FlatRef), hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->dJobs.ptr, plan.jobs.data(), plan.jobs.size() * sizeof(TrackJob), hipMemcpyHostToDevice, b->stream));
     }
-    lap("uploads");
-    if (verify && mismatchAt != ~0ull) {
-        // two frames with one hash and different values: the plan built on their equality is void.  The batch is planned again
-        // without tracks (nothing else rests on the hash) and the caller is told -- the call succeeds, the message stays.
-        const unsigned long long k = mismatchAt;
-        if (early.joinable()) early.join();
-        SetInput again = in;
-        again.noTracks = true;
-        const uint32_t first = plan.rep[(size_t)k];
-        const int rc = batch_set(b, again);
-        if (rc == 0) {
-            set_error("set: frames %llu and %u carry one 128-bit shape hash and different values; the batch runs without tracks", k, first);
-            set_error_code(SPEECHPLAYER_OK);
-        }
-        return rc;
+    if (nTrackedUtt > 0 || nDirectUtt > 0) {
+        if (b->dSourceRef.reserve((size_t)nF)) return -1;
     }
-    b->hasLabels = in.labels != nullptr;
-    b->listUnits.swap(listUnits);
-    b->nUtt = nU; b->nFrames = nF; b->nFramesSpoken = spoken; b->nLists = nL; b->nSlots = nSlotsAll;
-    b->nNoNasalUtt = nNoNasal;
-    b->nQuiet = nQuietSlots; b->nNoNasal = nNoNasalSlots;      // (slots: the groups' utterances and the replicas that complete their sparse last wavefronts)
-    b->nTracked = nTrackedUtt > 0 ? nTracked : 0; b->nTrackedUtt = nTrackedUtt;
-    b->nJobs = nTrackedUtt > 0 ? (long long)jobs.size() : 0; b->trackEntries = nTrackedUtt > 0 ? (long long)trackEntries : 0;
-    b->nDirect = nDirectUtt > 0 ? nDirectSlots : 0; b->nDirectUtt = nDirectUtt; b->nDirectFrames = (long long)directJobs.size();
-    b->totalSamples = total; b->poolSamples = pool;
-    b->lens.swap(lens); b->outStart.swap(outStart); b->denseStart.swap(denseStart);
-    b->uttFrameStart.swap(uttFrameStart); b->uttFrames.swap(uttFrames);
-    b->uttList.resize((size_t)nU);
-    for (long long u = 0; u < nU; ++u) b->uttList[(size_t)u] = (uint32_t)list_of(u);
-    b->uttSeed.resize((size_t)nU);
-    for (long long u = 0; u < nU; ++u) b->uttSeed[(size_t)u] = utt[(size_t)u].seed;
+    if (nDirectUtt > 0) {
+        const size_t nD = directJobs.size();
+        if (b->dDirectJobs.reserve(nD) || b->dDirectFirst.reserve((size_t)nU) || b->dDirectHdr.reserve((size_t)kDirectStages * nD) ||
+            b->dDirectRec.reserve((size_t)kDirectEntries * nD)) return -1;
+        HIP_TRY(hipMemcpyAsync(b->dDirectJobs.ptr, directJobs.data(), nD * sizeof(DirectJob), hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->dDirectFirst.ptr, c.directFirst.data(), (size_t)nU * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+    }
+    if (nF) {
+        if (!c.earlyStarted) HIP_TRY(hipMemcpyAsync(b->dFrames.ptr, in.frames, (size_t)nF * kNumParams * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        if (!c.byRecords) HIP_TRY(hipMemcpyAsync(b->dMeta.ptr, c.scratch.meta.data(), (size_t)nF * sizeof(FrameMeta), hipMemcpyHostToDevice, b->stream));
+    }
+    if (nU) {
+        HIP_TRY(hipMemcpyAsync(b->dUtt.ptr, c.utt.data(), (size_t)nU * sizeof(UttDesc), hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->dOrder.ptr, c.lanes.order.data(), (size_t)nSlotsAll * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemsetAsync(b->dResult.ptr, 0, (size_t)nU * sizeof(UttResult), b->stream));
+        if (b->dDenseStart.reserve((size_t)nU + 1)) return -1;
+        HIP_TRY(hipMemcpyAsync(b->dDenseStart.ptr, c.denseStart.data(), ((size_t)nU + 1) * sizeof(long long), hipMemcpyHostToDevice, b->stream));
+    }
+    if (c.verify) {
+        if (b->dRep.reserve((size_t)nF) || b->dMismatch.reserve(1)) return -1;
+        HIP_TRY(hipMemcpyAsync(b->dRep.ptr, plan.rep.data(), (size_t)nF * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemsetAsync(b->dMismatch.ptr, 0xFF, sizeof(unsigned long long), b->stream));
+    }
+    if (in.labels) {
+        // the labels and unitFirst[] (klatt_align.h) on the copy stream, ahead of setCopied; the wait below covers the arrays they leave
+        if (b->dLabels.reserve(std::max<size_t>((size_t)nF, 1)) || b->dUnitFirst.reserve(std::max<size_t>((size_t)(nF + nL), 1))) return -1;
+        c.copyGuard.armed = true;
+        if (nF) HIP_TRY(hipMemcpyAsync(b->dLabels.ptr, in.labels, (size_t)nF * sizeof(FrameLabel), hipMemcpyHostToDevice, b->copyStream));
+        if (nF + nL) HIP_TRY(hipMemcpyAsync(b->dUnitFirst.ptr, c.unitFirst.data(), (size_t)(nF + nL) * sizeof(uint32_t), hipMemcpyHostToDevice, b->copyStream));
+    }
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (c.copyGuard.armed) { HIP_TRY(hipStreamSynchronize(b->copyStream)); c.copyGuard.armed = false; }
+    if (c.early.joinable()) c.early.join();
+    if (c.earlyRc) { set_error_code(SPEECHPLAYER_ERR_HIP); set_error("set: uploading the frames failed: %s", c.earlyErr.c_str()); return -1; }
+    const unsigned grid = (unsigned)std::min<long long>((nF + 255) / 256, 1 << 16);
+    if (c.verify) {
+        hipLaunchKernelGGL(klatt_verify_shared, dim3(grid), dim3(256), 0, b->stream, b->dFrames.ptr, b->dRep.ptr, nF, b->dMismatch.ptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&c.mismatchAt, b->dMismatch.ptr, sizeof c.mismatchAt, hipMemcpyDeviceToHost, b->stream));
+    }
+    if (nTrackedUtt > 0 || nDirectUtt > 0) {
+        // what the flat and direct source stages read at a dequeue (SourceRef: pitch, pitch increment, 1 / fade, index mark), from the
+        // frames and durations now resident: 32 bytes per frame that no longer cross the link, and no third pass of the host over the frames
+        hipLaunchKernelGGL(klatt_source_refs, dim3(grid), dim3(256), 0, b->stream, b->dFrames.ptr, b->dMeta.ptr, b->dSourceRef.ptr, nF);
+        HIP_TRY(hipGetLastError());
+    }
+    if (c.verify || nTrackedUtt > 0 || nDirectUtt > 0) HIP_TRY(hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+// 10. The call has succeeded: the Batch takes what it built.
+static int set_commit(SetCall& c)
+{
+    Batch* const b = c.b;
+    const LanePacking& lanes = c.lanes;
+    b->hasLabels = c.in.labels != nullptr;
+    b->listUnits.swap(c.listUnits);
+    b->nUtt = c.nU; b->nFrames = c.nF; b->nFramesSpoken = c.spoken; b->nLists = c.nL; b->nSlots = (long long)lanes.order.size();
+    b->nNoNasalUtt = lanes.nNoNasal;
+    b->nQuiet = lanes.nQuietSlots; b->nNoNasal = lanes.nNoNasalSlots;      // (slots: the groups' utterances and the replicas that complete their sparse last wavefronts)
+    b->nTracked = lanes.nTrackedUtt > 0 ? lanes.nTracked : 0; b->nTrackedUtt = lanes.nTrackedUtt;
+    b->nJobs = lanes.nTrackedUtt > 0 ? (long long)c.plan.jobs.size() : 0; b->trackEntries = lanes.nTrackedUtt > 0 ? (long long)c.plan.entries : 0;
+    b->nDirect = c.nDirectUtt > 0 ? lanes.nDirectSlots : 0; b->nDirectUtt = c.nDirectUtt; b->nDirectFrames = (long long)c.scratch.directJobs.size();
+    b->totalSamples = c.total; b->poolSamples = c.pool;
+    b->lens.swap(c.lens); b->outStart.swap(c.outStart); b->denseStart.swap(c.denseStart);
+    b->uttFrameStart.swap(c.uttFrameStart); b->uttFrames.swap(c.uttFrames); b->uttList.swap(c.uttList); b->uttSeed.swap(c.uttSeed);
     b->timelineFresh = false; b->epochFresh = false;
     // (what this call left queued on its two streams, if anything: the track exports wait for it on the device)
     HIP_TRY(hipEventRecord(b->setDone, b->stream));
@@ -3558,6 +3440,45 @@ static int batch_set(Batch* b, const SetInput& in)
     b->floatFresh = false;
     b->launched = false;
     return 0;
+}
+
+// Setting a batch, behind all five entry points.  The order of events is where the call's measured time comes from: the frames
+// start on their way (3) before anybody looks at them (4), the facts computed on the device are waited for only after the timing
+// hashes (in 5), and the labels travel on the copy stream ahead of setCopied (8).
+static int batch_set(Batch* b, const SetInput& in)
+{
+    if (!b || in.nLists < 0 || in.nUtt < 0 || !in.listStart) { set_error("set: bad arguments"); return -1; }
+    if (in.nUtt >= 0xFFFFFFFFll || in.nLists >= 0xFFFFFFFFll) { set_error("set: too many utterances"); return -1; }
+    if (!in.listOf && in.nUtt != in.nLists) { set_error("set: %lld utterances for %lld lists and no listOf", in.nUtt, in.nLists); return -1; }
+    SetCall c(b, in);
+    HIP_TRY(hipSetDevice(b->device));
+    if (set_validate(c) || set_meta_words(c)) return -1;      // (the previous batch stays)
+    if (set_start_frames(c) || set_frame_facts(c) || set_plan(c)) return -1;
+    set_direct_jobs_and_refs(c);
+    set_lanes(c);
+    c.verify = !c.byRecords && c.lanes.nTrackedUtt > 0 && !c.plan.rep.empty();
+    if (set_upload(c)) {
+        // the device buffers may hold a mix of the old and the new batch now: the object becomes an empty batch
+        batch_clear(b);
+        return -1;
+    }
+    c.lap("uploads");
+    if (c.verify && c.mismatchAt != ~0ull) {
+        // 9. two frames with one hash and different values: the plan built on their equality is void.  The batch is planned again
+        // without tracks (nothing else rests on the hash) and the caller is told -- the call succeeds, the message stays.
+        const unsigned long long k = c.mismatchAt;
+        if (c.early.joinable()) c.early.join();
+        SetInput again = in;
+        again.noTracks = true;
+        const uint32_t first = c.plan.rep[(size_t)k];
+        const int rc = batch_set(b, again);
+        if (rc == 0) {
+            set_error("set: frames %llu and %u carry one 128-bit shape hash and different values; the batch runs without tracks", k, first);
+            set_error_code(SPEECHPLAYER_OK);
+        }
+        return rc;
+    }
+    return set_commit(c);
 }
 
 long long speechPlayer_batch_frames(speechPlayer_batch_t batch, long long u, speechPlayer_frame_t* frames, unsigned int* minFrameDuration,

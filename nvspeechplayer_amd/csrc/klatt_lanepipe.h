@@ -23,11 +23,10 @@
 // never observed, and both are skipped.
 #pragma once
 
+#include "klatt_consts.h"
 #include "klatt_systolic.h"
 
 namespace klatt {
-
-constexpr uint32_t UTT_NO_NASAL = 2u;     // UttDesc.flags: caNP == 0 throughout, N0/NP finite and stable
 
 constexpr int kLpK = 6;                   // lanes (cascade resonators r6..r1) per utterance
 constexpr int kLpUPR = 2;                 // utterances per 16-lane row, interleaved: row position p = 2 k + (utterance & 1); positions 12..15 idle

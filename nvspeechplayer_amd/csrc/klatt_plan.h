@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "klatt_consts.h"
 #include "klatt_device.h"
 
 namespace klatt {
@@ -28,10 +29,6 @@ struct FrameFacts {          // 24 B per frame
     uint32_t flags;              // FACT_*
     uint32_t pad;
 };
-constexpr uint32_t FACT_NOISE = 1u;        // a noise gain is non-zero, or the parallel bank's coefficients may not be finite
-constexpr uint32_t FACT_NONFINITE = 2u;    // some parameter is NaN or infinite
-constexpr uint32_t FACT_NASAL = 4u;        // the nasal pair is coupled in, or could not be skipped safely
-constexpr uint32_t FACT_UNBOUNDED = 8u;    // a frequency or bandwidth outside the range of klatt_math.h, or a negative bandwidth (the direct stages)
 
 __host__ __device__ inline bool fact_finite(double v)
 {

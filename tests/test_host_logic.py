@@ -225,3 +225,13 @@ def test_export_planning_under_sanitizers(tmp_path):
                            "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "native", "check_export_plan.cpp"), "-o", exe])
     out = subprocess.check_output([exe], stderr=subprocess.STDOUT).decode()
     assert out.startswith("ok ") and "runtime error" not in out and "AddressSanitizer" not in out, out
+
+
+def test_batch_planning_under_sanitizers(tmp_path):
+    """The host planning of a set call (csrc/klatt_batchplan.h: per-list length, timing and class, the routing, lane packing) against
+    the rules restated by brute force and the small cases written out in tests/native/check_batch_plan.cpp, under AddressSanitizer + UBSan."""
+    exe = str(tmp_path / "check_batch_plan")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "native", "check_batch_plan.cpp"), "-o", exe])
+    out = subprocess.check_output([exe], stderr=subprocess.STDOUT).decode()
+    assert out.startswith("ok ") and "runtime error" not in out and "AddressSanitizer" not in out, out
