@@ -491,6 +491,12 @@ long long speechPlayer_planTracks(long long nUtterances, const long long* frameS
 long long speechPlayer_planTracksFacts(long long nUtterances, const long long* frameStart, const speechPlayer_frame_t* frames,
 	const unsigned int* fadeDuration, const unsigned char* isNull, const unsigned char* eligible, long long budgetMB, const void* facts24,
 	unsigned long long* trackOff, unsigned int* trackMask, unsigned char* tracked, unsigned long long* nEntries, long long* collisionAt);
+/* speechPlayer_planTracks, and per utterance the word of entry kinds the flat stages are told to follow (kinds[nUtterances], may be NULL;
+ * the bits of trackMask): every kind some fade of the utterance moves, and every kind whose value the first sample of a later fade
+ * re-sets -- the frame after a silence starts from its own values.  0 for an utterance that is not tracked.  Touches no device. */
+long long speechPlayer_planTrackKinds(long long nUtterances, const long long* frameStart, const speechPlayer_frame_t* frames,
+	const unsigned int* fadeDuration, const unsigned char* isNull, const unsigned char* eligible, long long budgetMB,
+	unsigned long long* trackOff, unsigned int* trackMask, unsigned char* tracked, unsigned long long* nEntries, unsigned int* kinds);
 /* Host-only view of the fade end points speechPlayer_batch_setUtterances derives for the utterances it sends to the direct stages
  * (tests; touches no device; follows reference src/frame.cpp:55-72): per frame the frames its fade starts from and ends on
  * (0xFFFFFFFF: none -- all values zero) and flags (bit 0: the start's preFormantGain is gated off -- silence --, bit 1: the end's).

@@ -61,6 +61,7 @@ EXPORTS = [
     "speechPlayer_frameResponse", "speechPlayer_batch_exportResponse",
     "speechPlayer_batch_exportStems", "speechPlayer_resonatorCoefficients",
     "speechPlayer_pcmSpectrogram", "speechPlayer_batch_exportSpectrogram",
+    "speechPlayer_planTrackKinds",
 ]
 
 
@@ -307,6 +308,8 @@ def load():
     L.speechPlayer_planTracks.argtypes = [i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     L.speechPlayer_frameFacts.restype = i64
     L.speechPlayer_frameFacts.argtypes = [vp, i64, i32, i32, vp]
+    L.speechPlayer_planTrackKinds.restype = i64
+    L.speechPlayer_planTrackKinds.argtypes = [i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     L.speechPlayer_planDirect.restype = i64
     L.speechPlayer_planDirect.argtypes = [i64, vp, vp, vp, vp, vp]
     L.speechPlayer_planTracksFacts.restype = i64

@@ -636,8 +636,9 @@ __device__ __forceinline__ void direct_source_stage(const KernelArgs& A, const U
                 }
             } else {
                 const uint32_t wm = direct_chunk_mask(f, t1);
-                // vibrato can only come alive in this chunk through its kind (the phase only turns NaN while it advances)
-                const bool vibChunk = (wm & (1u << DD::NRES)) != 0u || __any(vib_live());
+                // vibrato comes alive in this chunk through its kind, or with the first values of a fade that starts in it: a frame out
+                // of silence brings its own vibrato without moving it (the phase only turns NaN while it advances)
+                const bool vibChunk = (wm & (1u << DD::NRES)) != 0u || __any(vib_live() || f.startAt <= t1);
 #pragma unroll kMixedUnroll
                 for (int i = 0; i < CH; ++i) {
                     const uint32_t t = t0 + (uint32_t)i;

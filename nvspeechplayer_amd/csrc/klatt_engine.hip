@@ -4311,7 +4311,7 @@ int speechPlayer_batch_kernelInfo(speechPlayer_batch_t batch, int* info, int nIn
 static long long plan_tracks_view(long long nUtterances, const long long* frameStart, const speechPlayer_frame_t* frames,
                                   const unsigned int* fadeDuration, const unsigned char* isNull, const unsigned char* eligible,
                                   long long budgetMB, const void* facts24, unsigned long long* trackOff, unsigned int* trackMask, unsigned char* tracked,
-                                  unsigned long long* nEntries, long long* collisionAt)
+                                  unsigned long long* nEntries, long long* collisionAt, unsigned int* kinds = nullptr)
 {
     begin_call();
     if (nUtterances < 0 || !frameStart || frameStart[0] != 0) { set_error("planTracks: bad arguments"); return -1; }
@@ -4354,6 +4354,7 @@ static long long plan_tracks_view(long long nUtterances, const long long* frameS
     // references of utterances that ended up untracked mean nothing: clear them
     for (long long u = 0; u < nUtterances; ++u) {
         if (tracked) tracked[u] = plan.tracked[u];
+        if (kinds) kinds[u] = plan.tracked[u] ? plan.kinds[u] : 0u;
         if (!plan.tracked[u])
             for (long long k = frameStart[u]; k < frameStart[u + 1]; ++k) { if (trackOff) trackOff[k] = 0; if (trackMask) trackMask[k] = 0; }
     }
@@ -4379,6 +4380,18 @@ long long speechPlayer_planTracksFacts(long long nUtterances, const long long* f
     try {
         return plan_tracks_view(nUtterances, frameStart, frames, fadeDuration, isNull, eligible, budgetMB, facts24, trackOff, trackMask, tracked, nEntries, collisionAt);
     } catch (const std::exception& e) { set_error("planTracksFacts: %s", e.what()); return -1; }
+}
+
+// The same plan, and per utterance the kinds word the flat stages get with it (TrackPlan::kinds, UttDesc.flags >> kUttKindShift):
+// every entry kind whose value changes after the first sample of the utterance's first fade; 0 for an utterance that is not tracked.
+long long speechPlayer_planTrackKinds(long long nUtterances, const long long* frameStart, const speechPlayer_frame_t* frames,
+                                      const unsigned int* fadeDuration, const unsigned char* isNull, const unsigned char* eligible,
+                                      long long budgetMB, unsigned long long* trackOff, unsigned int* trackMask, unsigned char* tracked,
+                                      unsigned long long* nEntries, unsigned int* kinds)
+{
+    try {
+        return plan_tracks_view(nUtterances, frameStart, frames, fadeDuration, isNull, eligible, budgetMB, nullptr, trackOff, trackMask, tracked, nEntries, nullptr, kinds);
+    } catch (const std::exception& e) { set_error("planTrackKinds: %s", e.what()); return -1; }
 }
 
 // the engine's worker threads for the other translation unit (frame_producer.cpp): fn(ctx, a, e) over [0, n) in ranges

@@ -1,7 +1,10 @@
 """Host logic of the tracks (speechPlayer_planTracks: what speechPlayer_batch_setUtterances plans; no GPU needed):
 which resonators a fade moves, which fades share a track, where the tracks lie, and the all-or-nothing budget rule -- against a
 plain Python walk of the reference's frame rules (src/frame.cpp:55-72: silence keeps the last spoken shape, the first frame
-after silence starts from its own shape, any other frame fades from the last spoken frame's values)."""
+after silence starts from its own shape, any other frame fades from the last spoken frame's values).
+The random shapes here differ from one another in everything, or singly in three parameters only (9, 44 and 5): every parameter moving
+ALONE in a fade, or jumping out of a silence, and the per-utterance kinds word are held to the table below (RES_F, RES_B, PAIRS) by
+tests/test_one_at_a_time_host.py."""
 import ctypes
 
 import numpy as np
