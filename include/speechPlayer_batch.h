@@ -409,6 +409,60 @@ long long speechPlayer_pcmSpectrogram(const sample* pcm, long long length, int n
 long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int nFft,
 	long long hop, long long phase, const double* window, const double* bank, int nBands, int power, double logScale, double floor,
 	void* deviceOut, int format, long long rowStride, void* stream);
+/*
+ * A batch's PCM at another sample rate: a polyphase windowed-sinc resampler.  For an utterance of Lin samples of int16 PCM s(t), the
+ * source rate sr (the batch's) and the target rate out:
+ *   ratio     g = gcd(sr, out), up = out / g, down = sr / g.  Lout = ceil(Lin * up / down) in 64-bit integers, 0 when Lin is 0.  Output
+ *             sample m lies at source time m * down / up (in source samples): grids and labels of the other exports are at the SOURCE rate
+ *   filter    c = rolloff * min(1, up / down), the cut-off as a fraction of the source Nyquist frequency; Wd = zeros / c, the half-width
+ *             in source samples; Z = ceil(Wd); taps = 2 Z, with offsets i = -Z+1 .. Z
+ *   table     h[p][k] for p = 0 .. up-1 and k = 0 .. taps-1, with i = k - Z + 1 and t = i - p / up:  h = c * sinc(c t) * w(t), where
+ *             sinc(x) = sin(pi x) / (pi x) and is 1 at 0, and w(t) = 0 when |t| >= Wd.  window 0 (Hann): w(t) = cos^2(pi t / (2 Wd)).
+ *             window 1 (Kaiser): w(t) = I0(beta * sqrt(1 - (t/Wd)^2)) / I0(beta), I0 by its power series.  The table is evaluated in
+ *             binary64 on the host, rounded to float32 once and used by both sides
+ *   input     x[n] = (float)s(n) / 32767.0f (the bits of speechPlayer_batch_exportPcm's format 1); a sample outside 0 .. Lin-1 is +0; the
+ *             pool's padding and the neighbouring utterances are never read as signal
+ *   output    for m = 0 .. Lout-1: n0 = floor(m * down / up) and p = (m * down) mod up, both in 64-bit integers; y[m] is the sum over
+ *             k ascending, starting from +0, of x[n0 + k - Z + 1] * h[p][k], each term one float32 product and one float32 sum, no
+ *             fused multiply-add.  The definition is the function bodies of csrc/klatt_resample.h, which the host and the device
+ *             compile from one source; speechPlayer_pcmResample executes them in a plain loop
+ *   format 1  float32: y[m]
+ *   format 0  int16: q = y * 32767.0f, one float32 product; 32767 when q >= 32767, -32768 when q <= -32768, otherwise rintf(q), rounded
+ *             to nearest even.  Clipping does happen: the filter overshoots on full-scale noise
+ *   equal     out == sr does no filtering: the result is speechPlayer_batch_exportPcm's output exactly
+ * Like the spectrogram, and unlike the exports of the batch "as set", the result is a function of the batch's PCM: it depends on the
+ * mode and, in MODE_FAST, on whatever that mode's tolerance allows; it needs a synthesis launch.
+ * Out of scope: live handles (resampling across pulls needs filter state); NodePlayer, which reaches the export through
+ * speechPlayer_node_part; a spectrogram or a label grid at the target rate (see "ratio" for where output sample m lies).
+ *
+ * Refused by all of the entry points below with SPEECHPLAYER_ERR_ARGUMENT and nothing written: a rate <= 0, zeros < 1, rolloff outside
+ * (0, 1] or not finite, an unknown window, Kaiser with beta not finite or negative, up > 4096, taps > 1024, up * taps > 2^20.
+ *
+ * Host only, touches no device: Lout for `length` samples (-1: length < 0 or a rate <= 0). */
+long long speechPlayer_resampledLength(long long length, int srcRate, int dstRate);
+/* Host only: the float32 table widened to double, table[up][taps]; *up, *down, *taps (each may be NULL).  Returns up * taps; a NULL
+ * table only sizes; -1 on a refused request or a capacity below up * taps.  (With equal rates it is the filter the formulas give, which the
+ * resampler does not apply.) */
+long long speechPlayer_resampleKernel(int srcRate, int dstRate, int zeros, double rolloff, int window, double beta, int* up, int* down, int* taps,
+	double* table, long long capacity);
+/* Host only: the definition above on `length` samples of plain PCM -- the product's own CPU statement, which the device path is held to
+ * bit for bit.  out: float[Lout] (format 1) or int16[Lout] (format 0).  Returns Lout; a NULL out only sizes; -1 on a refused request, an
+ * unknown format, length < 0 or above 2^44, a NULL pcm with length > 0, a capacity below Lout. */
+long long speechPlayer_pcmResample(const sample* pcm, long long length, int srcRate, int dstRate, int zeros, double rolloff, int window, double beta,
+	int format, void* out, long long capacity);
+/* The chosen utterances' PCM at outRate into caller-owned device memory on the caller's stream.  utterances (any order, repeats allowed,
+ * NULL: all), the rows (rowStride > 0: padded rows, +0 past each row's Lout; 0: the rows back to back), the return value (elements
+ * written; 0 writes nothing and needs no buffer), the device-memory checks and the sixteen-in-flight rule are those of
+ * speechPlayer_batch_exportPcm, and so is the ordering, by events and without a host wait: the export runs on `stream` behind the batch's
+ * last synthesis launch on all its streams, and the batch's next launch waits on the device for the export before it overwrites the
+ * pool.  A workgroup takes tiles of kResampleTile = 1024 consecutive outputs of one row (csrc/klatt_resample.h); the table stays on the
+ * batch until the parameters change and is uploaded in the export's stream order.  An output aligned to 16 bytes or only to its element
+ * takes 16-byte stores wherever a run of outputs covers an aligned 16 bytes.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: the list above, no batch, a batch that has not been synthesised since it
+ * was set, an unknown format, an utterance number outside the batch, a rowStride below the longest output row, an output that is not
+ * device memory of the batch's device, misaligned to the element or too small. */
+long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int outRate, int zeros,
+	double rolloff, int window, double beta, void* deviceOut, int format, long long rowStride, void* stream);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

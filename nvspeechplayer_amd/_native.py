@@ -61,6 +61,7 @@ EXPORTS = [
     "speechPlayer_frameResponse", "speechPlayer_batch_exportResponse",
     "speechPlayer_batch_exportStems", "speechPlayer_resonatorCoefficients",
     "speechPlayer_pcmSpectrogram", "speechPlayer_batch_exportSpectrogram",
+    "speechPlayer_resampledLength", "speechPlayer_resampleKernel", "speechPlayer_pcmResample", "speechPlayer_batch_exportResampled",
     "speechPlayer_planTrackKinds",
 ]
 
@@ -380,6 +381,14 @@ def load():
     L.speechPlayer_pcmSpectrogram.argtypes = [vp, i64, i32, i64, i64, vp, vp, i32, i32, f64, f64, vp]
     L.speechPlayer_batch_exportSpectrogram.restype = i64
     L.speechPlayer_batch_exportSpectrogram.argtypes = [vp, vp, i64, i32, i64, i64, vp, vp, i32, i32, f64, f64, vp, i32, i64, vp]
+    L.speechPlayer_resampledLength.restype = i64
+    L.speechPlayer_resampledLength.argtypes = [i64, i32, i32]
+    L.speechPlayer_resampleKernel.restype = i64
+    L.speechPlayer_resampleKernel.argtypes = [i32, i32, i32, f64, i32, f64, vp, vp, vp, vp, i64]
+    L.speechPlayer_pcmResample.restype = i64
+    L.speechPlayer_pcmResample.argtypes = [vp, i64, i32, i32, i32, f64, i32, f64, i32, vp, i64]
+    L.speechPlayer_batch_exportResampled.restype = i64
+    L.speechPlayer_batch_exportResampled.argtypes = [vp, vp, i64, i32, i32, f64, i32, f64, vp, i32, i64, vp]
     _lib = L
     return L
 

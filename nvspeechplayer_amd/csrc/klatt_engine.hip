@@ -21,6 +21,7 @@
 #include "klatt_response.h"
 #include "klatt_stems.h"
 #include "klatt_spectrum.h"
+#include "klatt_resample.h"
 #include "klatt_export.h"
 #include "klatt_batchplan.h"
 
@@ -670,6 +671,12 @@ struct Batch {
     bool epochFresh = false;
     long long sourceBudgetMB = 256;            // option "source_table_mb": an export whose step table would be larger proceeds in pieces
     long long sourceLaneLists = 12288;         // option "source_lane_lists": a walk over this many lists or more runs one lane per list
+    // klatt_resample.h: the last request's plan and its table as the kernel reads it, kept until the parameters change; the exports that
+    // read the table follow one order, so that an upload on one stream stands behind the readers on another
+    ResPlan resPlan;
+    DeviceBuffer<float> dResample;             // [taps][up]
+    bool resOnDevice = false;
+    SharedTable resampleOrder;
 };
 
 // The batch's own streams wait (on the device) for the exports that still read its pool.
@@ -2611,7 +2618,7 @@ speechPlayer_batch_t speechPlayer_batch_create(int sampleRate, int device)
               hipEventCreateWithFlags(&b->pcmReady, hipEventDisableTiming) == hipSuccess;
     for (auto& s : b->exportSlot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
     for (auto& s : b->trackSlot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
-    for (hipEvent_t* e : {&b->setDone, &b->setCopied, &b->timelineReady, &b->pitchOrder.done, &b->sourceOrder.done}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    for (hipEvent_t* e : {&b->setDone, &b->setCopied, &b->timelineReady, &b->pitchOrder.done, &b->sourceOrder.done, &b->resampleOrder.done}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     { const char* e = getenv("SPEECHPLAYER_TRACKS"); if (e) b->tracks = atoi(e) ? 1 : 0; }
     { const char* e = getenv("SPEECHPLAYER_DIRECT"); if (e) b->direct = std::min(2, std::max(0, atoi(e))); }
     { const char* e = getenv("SPEECHPLAYER_DIRECT_LEAN"); if (e) b->directLean = std::min(1, std::max(-1, atoi(e))); }
@@ -2642,9 +2649,9 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch)
         if (s.done) (void)hipEventDestroy(s.done);
         s.host.release(); s.dev.release();
     }
-    for (hipEvent_t e : {b->setDone, b->setCopied, b->timelineReady, b->pitchOrder.done, b->sourceOrder.done}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {b->setDone, b->setCopied, b->timelineReady, b->pitchOrder.done, b->sourceOrder.done, b->resampleOrder.done}) if (e) (void)hipEventDestroy(e);
     b->dListStart.release(); b->dTimeline.release(); b->dPitch.release(); b->dLabels.release(); b->dUnitFirst.release();
-    b->dSource.release(); b->dEpochs.release(); b->dEpochCount.release();
+    b->dSource.release(); b->dEpochs.release(); b->dEpochCount.release(); b->dResample.release();
     if (b->inputReady) (void)hipEventDestroy(b->inputReady);
     if (b->pcmReady) (void)hipEventDestroy(b->pcmReady);
     b->dShapeIdx.release(); b->dShapeRows.release();
@@ -5161,6 +5168,125 @@ long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const
         if (stage.finish()) return -1;
         return elements;
     });
+}
+
+
+// ---- the PCM at another sample rate (klatt_resample.h) -----------------------------------------------------------------------------------
+// Host only, touch no device: the definition of include/speechPlayer_batch.h through the functions the kernel is compiled from.
+long long speechPlayer_resampledLength(long long length, int srcRate, int dstRate)
+{
+    begin_call();
+    if (length < 0 || srcRate <= 0 || dstRate <= 0) { set_error("resampledLength: length %lld, %d to %d Hz", length, srcRate, dstRate); return -1; }
+    const long long g = res_gcd(srcRate, dstRate);
+    return res_length(length, dstRate / g, srcRate / g);
+}
+
+long long speechPlayer_resampleKernel(int srcRate, int dstRate, int zeros, double rolloff, int window, double beta, int* up, int* down, int* taps,
+                                      double* table, long long capacity)
+{
+    begin_call();
+    try {
+        ResPlan P;
+        std::string why;
+        if (!res_plan(P, srcRate, dstRate, zeros, rolloff, window, beta, why)) { set_error("resampleKernel: %s", why.c_str()); return -1; }
+        const long long n = (long long)P.table.size();
+        if (table && capacity < n) { set_error("resampleKernel: the table takes %lld values, capacity is %lld", n, capacity); return -1; }
+        if (up) *up = P.up;
+        if (down) *down = P.down;
+        if (taps) *taps = P.taps;
+        for (long long i = 0; table && i < n; ++i) table[i] = (double)P.table[(size_t)i];
+        return n;
+    } catch (const std::exception& e) { set_error("resampleKernel: %s", e.what()); return -1; }
+}
+
+long long speechPlayer_pcmResample(const sample* pcm, long long length, int srcRate, int dstRate, int zeros, double rolloff, int window, double beta,
+                                   int format, void* out, long long capacity)
+{
+    begin_call();
+    if (length < 0 || length > kResampleMaxLength || (length > 0 && !pcm)) { set_error("pcmResample: length %lld (0 .. 2^44, with its samples)", length); return -1; }
+    if (format != 0 && format != 1) { set_error("pcmResample: format %d (0 int16, 1 float32)", format); return -1; }
+    try {
+        ResPlan P;
+        std::string why;
+        if (!res_plan(P, srcRate, dstRate, zeros, rolloff, window, beta, why)) { set_error("pcmResample: %s", why.c_str()); return -1; }
+        const long long Lout = res_length(length, P.up, P.down);
+        if (!out) return Lout;
+        if (capacity < Lout) { set_error("pcmResample: the output takes %lld elements, capacity is %lld", Lout, capacity); return -1; }
+        static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
+        return resample_host(reinterpret_cast<const int16_t*>(pcm), length, P, format, out);
+    } catch (const std::exception& e) { set_error("pcmResample: %s", e.what()); return -1; }
+}
+
+// The chosen utterances' PCM at `outRate` (klatt_resample.h).  It reads the pool, so it is ordered as speechPlayer_batch_exportPcm is
+// (ExportStage, ofPcm).  A workgroup takes tiles of one row: the packed form's row table counts TILES, the rows carry their first
+// element in the output.  The staging block: rows | tile starts and chunk rows (packed) | the table, when the batch does not hold it.
+// The table stays on the batch until the parameters change; the exports that read it follow one order (resampleOrder).
+long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int outRate, int zeros,
+                                             double rolloff, int window, double beta, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    const char* what = "exportResampled";
+    if (refuse_timing_only("speechPlayer_batch_exportResampled")) return -1;
+    const long long done = batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("exportResampled: format %d (0 int16, 1 float32)", format); return -1; }
+        if (rowStride < 0) { set_error("exportResampled: rowStride %lld", rowStride); return -1; }
+        if (!b->resPlan.same(b->sampleRate, outRate, zeros, rolloff, window, beta)) {
+            ResPlan P;
+            std::string why;
+            if (!res_plan(P, b->sampleRate, outRate, zeros, rolloff, window, beta, why)) { set_error("exportResampled: %s", why.c_str()); return -1; }
+            b->resPlan = std::move(P);
+            b->resOnDevice = false;
+        }
+        ResPlan& P = b->resPlan;
+        if (P.identity) return -2;      // equal rates: speechPlayer_batch_exportPcm's output exactly
+        ExportSelection s;
+        std::vector<ResRow> rows;
+        std::vector<long long> tiles;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) {
+                const long long L = (long long)b->lens[(size_t)u], Lout = res_length(L, P.up, P.down);
+                rows.push_back(ResRow{b->outStart[(size_t)u], L, Lout, rowStride > 0 ? (long long)((unsigned long long)i * (unsigned long long)rowStride) : before});      // (export_elements refuses an extent that wraps)
+                tiles.push_back((Lout + kResampleTile - 1) / kResampleTile);
+                return Lout;
+            })) return -1;
+        static constexpr ExportNouns kSampleNouns{"longest output row", "samples", nullptr};
+        const long long elements = export_elements(what, kSampleNouns, s, rowStride, 1);
+        if (elements <= 0) return elements;
+        if (!b->launched) { set_error("exportResampled: the batch has not been synthesised since it was set"); return -1; }
+        const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
+        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+
+        const bool packed = rowStride == 0;
+        std::vector<long long> words;
+        const RowTable table = packed ? packed_row_table(tiles.data(), 0, s.n, kTimelineChunkLog2, words) : RowTable{0, 0};
+        const bool upload = !b->resOnDevice;
+        if (upload) res_transpose(P);
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words), tableAt = upload ? block.add(P.hT) : -1;
+        const size_t tableSize = (size_t)P.up * P.taps;
+        ExportStage stage(b, st, block, &b->resampleOrder, true);
+        if (stage.begin([&] {
+                if (tableSize <= b->dResample.cap) return 0;
+                if (b->resampleOrder.used) { HIP_TRY(hipEventSynchronize(b->resampleOrder.done)); }      // (the table is freed: its readers first)
+                return b->dResample.reserve(tableSize);
+            })) return -1;
+        if (upload) HIP_TRY(hipMemcpyAsync(b->dResample.ptr, stage.device<float>(tableAt), tableSize * sizeof(float), hipMemcpyDeviceToDevice, st));
+        ResArgs A;
+        A.pool = b->dPcm.ptr; A.rows = stage.device<ResRow>(rowsAt);
+        A.start = packed ? stage.device<long long>(wordsAt) + table.startOff : nullptr;
+        A.chunk = packed ? stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
+        A.rowStride = rowStride; A.tilesPerRow = (rowStride + kResampleTile - 1) / kResampleTile;
+        A.nTiles = packed ? words[(size_t)(table.startOff + s.n)] : s.n * A.tilesPerRow;
+        A.hT = b->dResample.ptr; A.up = P.up; A.down = P.down; A.Z = P.Z; A.span = res_span(P);
+        A.out = deviceOut;
+        const unsigned grid = (unsigned)std::min<long long>(A.nTiles, 8ll * b->cus);
+        if (format) hipLaunchKernelGGL(klatt_resample<true>, dim3(grid), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL(klatt_resample<false>, dim3(grid), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        b->resOnDevice = true;
+        return elements;
+    });
+    return done == -2 ? speechPlayer_batch_exportPcm(batch, utterances, nUtterances, deviceOut, format, rowStride, stream) : done;
 }
 
 }  // extern "C"

@@ -1,0 +1,299 @@
+// klatt_resample.h -- a batch's PCM at another sample rate (speechPlayer_batch_exportResampled) and plain PCM resampled on the host
+// (speechPlayer_pcmResample, speechPlayer_resampleKernel, speechPlayer_resampledLength).
+//
+// The definition is in include/speechPlayer_batch.h; this header is its one statement in code.  The functions marked KLATT_RES_HD are
+// compiled for the host and for the device from the same source, with -ffp-contract=off: the input conversion, every product and
+// every sum of the tap loop and the int16 conversion are separately rounded float32 operations on both sides (there is no fmaf
+// anywhere), and the table is evaluated once, in binary64 on the host, and rounded to float32 for both.
+//
+//   The plan        res_plan: the ratio up / down, the cut-off c, the half-width Wd, Z = ceil(Wd), taps = 2 Z, the refusals and the table
+//                   h[p][k] = c sinc(c t) w(t), t = (k - Z + 1) - p / up.  taps <= 1024 bounds the ratio as well: Z >= Wd >= down / up,
+//                   so down <= 512 up <= 2^21, which is what lets the kernel count in 32 bits inside a tile.
+//   The statement   resample_host: for every output m, res_locate gives n0 = floor(m down / up) and p = (m down) mod up, the taps'
+//                   inputs are res_input of the samples n0 - Z + 1 .. n0 + Z (+0 outside the signal), res_taps sums them against row p
+//                   in ascending k from +0, and res_int16 makes format 0.
+//   klatt_resample  A 256-lane workgroup takes tiles of kResampleTile consecutive outputs of one row, a tile in spans whose inputs fit
+//                   kResampleIn floats of LDS ((span - 1) down / up + 1 + taps <= kResampleIn: the whole tile wherever down / up < 6.9).
+//                   Per span: the inputs n0(first) - Z + 1 .. n0(last) + Z are loaded once, masked by 0 <= n < Lin, and converted by
+//                   res_input into LDS; lane i takes outputs i, i + 256, ... of the span, so consecutive lanes read LDS at stride
+//                   down / up (conflict-free below 2, two-way at 2) and the table at consecutive addresses: it is uploaded reordered
+//                   by use and transposed, hT[k][m mod up] = h[(m down) mod up][k] (phase has period `up` in m), 230 KB in the
+//                   largest tested case and L2-resident.  The reordering moves data, not arithmetic.  The values are staged in LDS in
+//                   the output's type and leave by lanes that own an aligned 16 bytes of the output (aligned by ADDRESS: a buffer
+//                   aligned to the element only still gets 16-byte stores inside a span); a span's edges, which share their 16 bytes
+//                   with the neighbouring span or row, go element by element.  A padded row's tail is stored as +0 by the same path.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <string>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define KLATT_RES_HD __host__ __device__ __forceinline__
+#else
+#define KLATT_RES_HD inline
+#endif
+
+namespace klatt {
+
+constexpr int kResampleTile = 1024;          // consecutive outputs of one row a workgroup takes at a time (a power of two, at most 4096)
+constexpr int kResampleIn = 8192;            // floats of LDS for a span's inputs
+constexpr int kResampleMaxUp = 4096, kResampleMaxTaps = 1024;
+constexpr long long kResampleMaxTable = 1ll << 20;
+constexpr long long kResampleMaxLength = 1ll << 44;      // samples of plain PCM the host statement takes (index products stay in 64 bits)
+
+// x[n]: the sample as speechPlayer_batch_exportPcm's format 1 gives it
+KLATT_RES_HD float res_input(int s) { return (float)s / 32767.0f; }
+
+// Output m reads inputs n0 - Z + 1 .. n0 + Z against row p of the table
+KLATT_RES_HD void res_locate(long long m, int up, int down, long long& n0, int& p)
+{
+    const long long a = m * (long long)down;
+    n0 = a / up;
+    p = (int)(a - n0 * up);
+}
+
+// sum over k ascending, from +0, of x[k] h[k * hStride]: one float32 product and one float32 sum per term
+KLATT_RES_HD float res_taps(const float* x, const float* h, int taps, int hStride)
+{
+    float acc = 0.0f;
+#if defined(__clang__)
+#pragma unroll 4
+#endif
+    for (int k = 0; k < taps; ++k) acc = acc + x[k] * h[(size_t)k * hStride];      // (unrolling hoists the loads; the sums keep their order)
+    return acc;
+}
+
+// format 0: one float32 product, clipped, rounded to nearest even
+KLATT_RES_HD int16_t res_int16(float y)
+{
+    const float q = y * 32767.0f;
+    if (q >= 32767.0f) return (int16_t)32767;
+    if (q <= -32768.0f) return (int16_t)-32768;
+    return (int16_t)rintf(q);
+}
+
+// ---- the request, as every entry point plans it on the host -----------------------------------------------------------------------------
+inline long long res_gcd(long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; }
+
+// ceil(length * up / down), 0 for length 0 (length >= 0, up and down positive)
+inline long long res_length(long long length, long long up, long long down)
+{
+    const unsigned __int128 a = (unsigned __int128)length * (unsigned __int128)up + (unsigned __int128)(down - 1);
+    const unsigned __int128 q = a / (unsigned __int128)down;
+    return q > (unsigned __int128)0x7FFFFFFFFFFFFFFFll ? 0x7FFFFFFFFFFFFFFFll : (long long)q;
+}
+
+// I0 by its power series, sum of ((x / 2)^2)^k / (k!)^2, in binary64
+inline double res_bessel_i0(double x)
+{
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 1000; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-20 * sum) break;
+    }
+    return sum;
+}
+
+struct ResPlan {
+    int srcRate = 0, dstRate = 0, zeros = 0, window = 0;
+    double rolloff = 0.0, beta = 0.0;
+    int up = 0, down = 0, Z = 0, taps = 0;
+    bool identity = false;           // equal rates: no filtering
+    std::vector<float> table;        // [up][taps]
+    std::vector<float> hT;           // [taps][up], column j holding row (j down) mod up: what the kernel reads (made by res_transpose)
+    bool same(int s, int d, int z, double r, int w, double b) const
+    {
+        return up > 0 && s == srcRate && d == dstRate && z == zeros && r == rolloff && w == window && (w == 0 || b == beta);
+    }
+};
+
+// The plan of a request, or false with `why` set (without the entry point's prefix).
+inline bool res_plan(ResPlan& P, int srcRate, int dstRate, int zeros, double rolloff, int window, double beta, std::string& why)
+{
+    char buf[200];
+    if (srcRate <= 0 || dstRate <= 0) { snprintf(buf, sizeof buf, "sample rates %d and %d (both above 0)", srcRate, dstRate); why = buf; return false; }
+    if (zeros < 1) { snprintf(buf, sizeof buf, "zeros %d (at least 1)", zeros); why = buf; return false; }
+    if (!std::isfinite(rolloff) || !(rolloff > 0.0) || rolloff > 1.0) { snprintf(buf, sizeof buf, "rolloff %g (in (0, 1])", rolloff); why = buf; return false; }
+    if (window != 0 && window != 1) { snprintf(buf, sizeof buf, "window %d (0 Hann, 1 Kaiser)", window); why = buf; return false; }
+    if (window == 1 && (!std::isfinite(beta) || beta < 0.0)) { snprintf(buf, sizeof buf, "Kaiser beta %g (finite, not negative)", beta); why = buf; return false; }
+    const long long g = res_gcd(srcRate, dstRate), up = dstRate / g, down = srcRate / g;
+    if (up > kResampleMaxUp) { snprintf(buf, sizeof buf, "%d to %d Hz is the ratio %lld / %lld: up is above %d", srcRate, dstRate, up, down, kResampleMaxUp); why = buf; return false; }
+    const double c = rolloff * (up < down ? (double)up / (double)down : 1.0);
+    const double Wd = (double)zeros / c;
+    if (!(Wd <= (double)(kResampleMaxTaps / 2))) {
+        snprintf(buf, sizeof buf, "zeros %d at the ratio %lld / %lld takes more than %d taps", zeros, up, down, kResampleMaxTaps); why = buf; return false;
+    }
+    const int Z = (int)ceil(Wd), taps = 2 * Z;
+    if (up * taps > kResampleMaxTable) {
+        snprintf(buf, sizeof buf, "a table of %lld phases of %d taps is above %lld values", up, taps, kResampleMaxTable); why = buf; return false;
+    }
+    P.srcRate = srcRate; P.dstRate = dstRate; P.zeros = zeros; P.window = window; P.rolloff = rolloff; P.beta = window == 1 ? beta : 0.0;
+    P.up = (int)up; P.down = (int)down; P.Z = Z; P.taps = taps;
+    P.identity = srcRate == dstRate;
+    P.table.resize((size_t)up * taps);
+    P.hT.clear();
+    const double pi = 3.141592653589793;
+    const double i0b = window == 1 ? res_bessel_i0(beta) : 1.0;
+    for (int p = 0; p < (int)up; ++p)
+        for (int k = 0; k < taps; ++k) {
+            const double t = (double)(k - Z + 1) - (double)p / (double)up;
+            double w = 0.0;
+            if (fabs(t) < Wd) {
+                if (window == 0) { const double cw = cos(pi * t / (2.0 * Wd)); w = cw * cw; }
+                else { const double r = t / Wd; w = res_bessel_i0(beta * sqrt(1.0 - r * r)) / i0b; }
+            }
+            const double x = pi * (c * t);
+            const double sinc = x == 0.0 ? 1.0 : sin(x) / x;
+            P.table[(size_t)p * taps + k] = (float)(c * sinc * w);
+        }
+    return true;
+}
+
+// The table as the kernel reads it: hT[k][j] = h[(j down) mod up][k]
+inline void res_transpose(ResPlan& P)
+{
+    if (!P.hT.empty()) return;
+    P.hT.resize(P.table.size());
+    for (int j = 0; j < P.up; ++j) {
+        const int p = (int)(((long long)j * P.down) % P.up);
+        for (int k = 0; k < P.taps; ++k) P.hT[(size_t)k * P.up + j] = P.table[(size_t)p * P.taps + k];
+    }
+}
+
+// ---- the host's statement (speechPlayer_pcmResample): the shared functions in a plain loop ------------------------------------------------
+// format 1: out is float[Lout]; format 0: int16_t[Lout].  Returns Lout.
+inline long long resample_host(const int16_t* pcm, long long length, const ResPlan& P, int format, void* out)
+{
+    const long long Lout = res_length(length, P.up, P.down);
+    float* of = static_cast<float*>(out);
+    int16_t* oi = static_cast<int16_t*>(out);
+    if (P.identity) {
+        for (long long m = 0; m < Lout; ++m) { if (format) of[m] = res_input(pcm[m]); else oi[m] = pcm[m]; }
+        return Lout;
+    }
+    std::vector<float> x((size_t)P.taps);
+    for (long long m = 0; m < Lout; ++m) {
+        long long n0; int p;
+        res_locate(m, P.up, P.down, n0, p);
+        for (int k = 0; k < P.taps; ++k) {
+            const long long n = n0 + k - P.Z + 1;
+            x[(size_t)k] = res_input(n >= 0 && n < length ? pcm[n] : 0);
+        }
+        const float y = res_taps(x.data(), P.table.data() + (size_t)p * P.taps, P.taps, 1);
+        if (format) of[m] = y; else oi[m] = res_int16(y);
+    }
+    return Lout;
+}
+
+// Outputs of a tile whose inputs fit the kernel's LDS at once: the largest span with (span - 1) down / up + 1 + taps <= kResampleIn
+inline int res_span(const ResPlan& P)
+{
+    const long long s = (long long)(kResampleIn - P.taps - 1) * P.up / P.down + 1;
+    return (int)(s < kResampleTile ? s : kResampleTile);
+}
+
+}  // namespace klatt
+
+// ---- the device ---------------------------------------------------------------------------------------------------------------------
+#if defined(__HIPCC__)
+#include "klatt_timeline.h"
+
+namespace klatt {
+
+struct ResRow { long long src, len, outLen, dst; };      // pool offset and samples of a row's utterance; its outputs; its first element in the output
+
+struct ResArgs {
+    const int16_t* pool;
+    const ResRow* rows;
+    const long long *start, *chunk;      // the packed form's row table over TILES (rowStride 0)
+    long long rowStride, tilesPerRow;    // the padded form: a row's width and its tiles
+    long long nTiles;
+    const float* hT;                     // [taps][up]
+    int up, down, Z, span;
+    void* out;
+};
+
+static_assert((kResampleTile & (kResampleTile - 1)) == 0 && kResampleTile <= 4096, "kResampleTile is a power of two, at most 4096");
+static_assert(kResampleIn >= kResampleMaxTaps + 1 + kResampleMaxTaps / 2, "a span of one output fits at the largest ratio and filter");
+
+template <bool F32>
+__global__ void __launch_bounds__(256) klatt_resample(const ResArgs A)
+{
+    using T = typename std::conditional<F32, float, int16_t>::type;
+    constexpr int EL = 16 / (int)sizeof(T);
+    __shared__ float xin[kResampleIn];
+    __shared__ __attribute__((aligned(16))) T staged[kResampleTile];
+    const int tid = threadIdx.x;
+    const int up = A.up, down = A.down, Z = A.Z, taps = 2 * Z;
+    T* __restrict__ out = static_cast<T*>(A.out);
+    const int mis = (int)((reinterpret_cast<uintptr_t>(A.out) / sizeof(T)) & (EL - 1));      // elements past a 16-byte boundary at out[0]
+    for (long long g = blockIdx.x; g < A.nTiles; g += gridDim.x) {
+        long long r, j;
+        if (A.rowStride > 0) { r = g / A.tilesPerRow; j = g - r * A.tilesPerRow; }
+        else { const long long c = g >> kTimelineChunkLog2; packed_locate(g, A.start, A.chunk[c], A.chunk[c + 1] + 1, r, j); }
+        const ResRow row = A.rows[r];
+        const long long width = A.rowStride > 0 ? A.rowStride : row.outLen;
+        const long long t0 = j * kResampleTile;
+        const int n = (int)min((long long)kResampleTile, width - t0);
+        const int16_t* __restrict__ pcm = A.pool + row.src;
+        for (int c0 = 0; c0 < n; c0 += A.span) {
+            const int cn = min(A.span, n - c0);
+            const long long m0 = t0 + c0;
+            const int live = (int)max(0ll, min((long long)cn, row.outLen - m0));      // outputs of the span inside the row; the rest is padding
+            long long nA = 0; int pA = 0;
+            if (live > 0) {
+                // ---- the span's inputs, once ----
+                long long nB; int pB;
+                res_locate(m0, up, down, nA, pA);
+                res_locate(m0 + live - 1, up, down, nB, pB);
+                const long long lo = nA - Z + 1;
+                const int count = (int)(nB - nA) + taps;
+                for (int i = tid; i < count; i += 256) {
+                    const long long s = lo + i;
+                    xin[i] = res_input(s >= 0 && s < row.len ? (int)pcm[s] : 0);
+                }
+            }
+            __syncthreads();
+            // ---- the outputs: lane i takes i, i + 256, ... ----
+            const uint32_t jA = (uint32_t)(m0 % up);
+            for (int i = tid; i < cn; i += 256) {
+                T v = (T)0;
+                if (i < live) {
+                    const uint32_t a = (uint32_t)pA + (uint32_t)i * (uint32_t)down;      // (below 2^12 + 2^10 2^21)
+                    const uint32_t col = (jA + (uint32_t)i) % (uint32_t)up;
+                    const float y = res_taps(xin + a / (uint32_t)up, A.hT + col, taps, up);
+                    if (F32) v = (T)y; else v = (T)res_int16(y);
+                }
+                staged[i] = v;
+            }
+            __syncthreads();
+            // ---- the stores: a lane owns an aligned 16 bytes of the output ----
+            const long long e0 = row.dst + m0;
+            const long long first = e0 - ((e0 + mis) & (EL - 1));
+            const int lanes = (int)((e0 + cn - first + EL - 1) / EL);
+            for (int i = tid; i < lanes; i += 256) {
+                const long long at = first + (long long)i * EL;
+                const int b0 = (int)(at - e0);                          // (negative in the first lane of a span that starts inside its 16 bytes)
+                if (b0 >= 0 && b0 + EL <= cn) {
+                    struct alignas(16) Lane { T x[EL]; } l;
+#pragma unroll
+                    for (int q = 0; q < EL; ++q) l.x[q] = staged[b0 + q];
+                    *reinterpret_cast<Lane*>(out + at) = l;
+                } else {
+#pragma unroll
+                    for (int q = 0; q < EL; ++q) if (b0 + q >= 0 && b0 + q < cn) out[at + q] = staged[b0 + q];
+                }
+            }
+            // (the next span's loads and values are behind its own barriers: every lane has read `staged` before any lane passes the first)
+        }
+    }
+}
+
+}  // namespace klatt
+#endif

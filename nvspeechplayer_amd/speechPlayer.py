@@ -631,6 +631,106 @@ def melFilterbank(sampleRate, nFft, nMels, fmin=0.0, fmax=None, norm=None):
     return bank
 
 
+RESAMPLE_TILE = 1024             # kResampleTile of csrc/klatt_resample.h: consecutive outputs of one row a workgroup takes at a time
+RESAMPLE_WINDOWS = ["hann", "kaiser"]
+RESAMPLE_LIMITS = (4096, 1024, 1 << 20)      # up, taps, up * taps
+
+
+def check_resample_request(srcRate, dstRate, zeros, rolloff, window, beta, dtype, what="resampledTensor"):
+    """The argument checks of BatchPlayer.resampledTensor, pcmResample and resampleKernel that need no GPU, before any library call:
+    both rates integers above 0, zeros an integer >= 1, rolloff finite in (0, 1], window "hann" / "kaiser" (or 0 / 1), the Kaiser beta
+    (None: 8.6) finite and not negative, up <= 4096, taps <= 1024 and up * taps <= 2^20 for the ratio up / down the rates reduce to, dtype
+    None / torch.float32 / np.float32 (float32) or torch.int16 / np.int16.  Raises ValueError or TypeError.  Returns (srcRate, dstRate,
+    zeros, rolloff, the window's number, beta, the export format: 0 int16, 1 float32, up, down, taps)."""
+    for name, v in (("srcRate", srcRate), ("dstRate", dstRate), ("zeros", zeros)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError("%s: %s must be an integer, not %r" % (what, name, v))
+    srcRate, dstRate, zeros = int(srcRate), int(dstRate), int(zeros)
+    if srcRate <= 0 or dstRate <= 0 or srcRate >= 1 << 31 or dstRate >= 1 << 31:
+        raise ValueError("%s: sample rates must be above 0 (and below 2^31), not %d and %d" % (what, srcRate, dstRate))
+    if zeros < 1 or zeros >= 1 << 31:
+        raise ValueError("%s: zeros must be at least 1, not %d" % (what, zeros))
+    rolloff = float(rolloff)
+    if not math.isfinite(rolloff) or not 0.0 < rolloff <= 1.0:
+        raise ValueError("%s: rolloff must lie in (0, 1], not %r" % (what, rolloff))
+    if isinstance(window, str):
+        if window not in RESAMPLE_WINDOWS:
+            raise ValueError("%s: window must be 'hann' or 'kaiser', not %r" % (what, window))
+        win = RESAMPLE_WINDOWS.index(window)
+    elif window in (0, 1) and not isinstance(window, bool):
+        win = int(window)
+    else:
+        raise ValueError("%s: window must be 'hann' or 'kaiser', not %r" % (what, window))
+    beta = 8.6 if beta is None else float(beta)
+    if win == 1 and (not math.isfinite(beta) or beta < 0.0):
+        raise ValueError("%s: the Kaiser beta must be finite and not negative, not %r" % (what, beta))
+    if win == 0:
+        beta = 0.0
+    g = math.gcd(srcRate, dstRate)
+    up, down = dstRate // g, srcRate // g
+    if up > RESAMPLE_LIMITS[0]:
+        raise ValueError("%s: %d to %d Hz is the ratio %d / %d: up must not be above %d" % (what, srcRate, dstRate, up, down, RESAMPLE_LIMITS[0]))
+    wd = zeros / (rolloff * min(1.0, up / down))
+    if not wd <= RESAMPLE_LIMITS[1] // 2:
+        raise ValueError("%s: zeros %d at the ratio %d / %d takes more than %d taps" % (what, zeros, up, down, RESAMPLE_LIMITS[1]))
+    taps = 2 * int(math.ceil(wd))
+    if up * taps > RESAMPLE_LIMITS[2]:
+        raise ValueError("%s: a table of %d phases of %d taps is above %d values" % (what, up, taps, RESAMPLE_LIMITS[2]))
+    names = {"float32": 1, "int16": 0}
+    key = "float32" if dtype is None else (str(dtype).replace("torch.", "") if type(dtype).__module__.startswith("torch") else None)
+    if key is None:
+        try:
+            key = np.dtype(dtype).name
+        except TypeError:
+            key = repr(dtype)
+    if key not in names:
+        raise TypeError("%s: dtype must be float32 or int16, not %s" % (what, dtype))
+    return srcRate, dstRate, zeros, rolloff, win, beta, names[key], up, down, taps
+
+
+def resampledLength(length, srcRate, dstRate):
+    """ceil(length * up / down) for the ratio the rates reduce to (speechPlayer_resampledLength; no GPU)."""
+    got = _native.load().speechPlayer_resampledLength(int(length), int(srcRate), int(dstRate))
+    if got < 0:
+        raise ValueError(_native.last_error())
+    return got
+
+
+def resampleKernel(srcRate, dstRate, zeros=6, rolloff=0.99, window="hann", beta=None):
+    """The polyphase table of the resampler (speechPlayer_resampleKernel; no GPU): -> (table float64 [up, taps], up, down), the float32
+    values both sides use, widened.  Row p, column k is the weight of input n0 + k - taps / 2 + 1 for an output of phase p, as
+    include/speechPlayer_batch.h defines it.  Arguments as BatchPlayer.resampledTensor's."""
+    srcRate, dstRate, zeros, rolloff, win, beta, _, up, down, taps = check_resample_request(srcRate, dstRate, zeros, rolloff, window, beta, None,
+                                                                                           "resampleKernel")
+    table = np.zeros((up, taps), np.float64)
+    u, d, t = c_int(0), c_int(0), c_int(0)
+    got = _native.load().speechPlayer_resampleKernel(srcRate, dstRate, zeros, rolloff, win, beta, byref(u), byref(d), byref(t), table.ctypes.data,
+                                                     table.size)
+    if got < 0:
+        raise RuntimeError(_native.last_error())
+    assert (got, u.value, d.value, t.value) == (table.size, up, down, taps), (got, u.value, d.value, t.value, up, down, taps)
+    return table, up, down
+
+
+def pcmResample(pcm, srcRate, dstRate, zeros=6, rolloff=0.99, window="hann", beta=None, dtype=np.float32):
+    """int16 PCM at another sample rate on the host (speechPlayer_pcmResample; no GPU): -> float32 (sample / 32767 scale) or int16
+    [ceil(len * up / down)], by the definition in include/speechPlayer_batch.h -- the float32 statement the device runs.  Arguments as
+    BatchPlayer.resampledTensor's; dtype np.float32 or np.int16."""
+    s = np.ascontiguousarray(np.asarray(pcm))
+    if s.dtype != np.int16 or s.ndim != 1:
+        raise TypeError("pcmResample: pcm must be a one-dimensional int16 array, not %s %s" % (s.dtype, list(s.shape)))
+    srcRate, dstRate, zeros, rolloff, win, beta, fmt, up, down, _ = check_resample_request(srcRate, dstRate, zeros, rolloff, window, beta, dtype,
+                                                                                          "pcmResample")
+    n = (len(s) * up + down - 1) // down
+    out = np.zeros(n, np.float32 if fmt else np.int16)
+    got = _native.load().speechPlayer_pcmResample(s.ctypes.data if len(s) else None, len(s), srcRate, dstRate, zeros, rolloff, win, beta, fmt,
+                                                  out.ctypes.data if n else None, n)
+    if got < 0:
+        raise RuntimeError(_native.last_error())
+    assert got == n, (got, n)
+    return out
+
+
 def check_option_value(name, value):
     """speechPlayer_batch_setOption takes a C int: a value outside its range would wrap without a word (2 ** 40 arrives as 0).  Returns
     int(value), or raises ValueError."""
@@ -921,6 +1021,23 @@ class BatchPlayer(object):
             return self._dll.speechPlayer_batch_exportSpectrogram(self._h, _ptr(sel), n, nFft, hop, phase, _ptr(window), _ptr(bank),
                                                                   bands if bank is not None else 0, power, scale, floor, out, fmt, stride, stream)
         return self._export_rows(steps, (bands,), torch.float32 if fmt else torch.float64, padded, call)
+
+    def resampledTensor(self, rate, zeros=6, rolloff=0.99, window="hann", beta=None, utterances=None, dtype=None, padded=True):
+        """The batch's PCM at `rate` Hz as a torch tensor on the batch's device (speechPlayer_batch_exportResampled), filled on torch's
+        current stream behind the synthesis without a host wait: -> (pcm, lengths).  A polyphase windowed-sinc resampler: `zeros` zero
+        crossings of the sinc either side, cut-off `rolloff` times the lower of the two Nyquist frequencies, window "hann" or "kaiser"
+        (beta: None is 8.6).  Output sample m of an utterance lies at its source sample m * down / up; an utterance of L samples gives
+        ceil(L * up / down).  utterances, padded and the (pcm, lengths) pair as pcmTensor's; dtype torch.float32 (default) or
+        torch.int16 (clipped, rounded to nearest even).  rate == sampleRate gives pcmTensor's values.  The batch must have been
+        synthesised since it was set; pcmResample is the same definition on the host."""
+        import torch
+        _, rate, zeros, rolloff, win, beta, fmt, up, down, _ = check_resample_request(self.sampleRate, rate, zeros, rolloff, window, beta, dtype)
+        sel, n, idx = self._selection("resampledTensor", utterances)
+        lens = (self._lengths()[idx].astype(np.int64) * up + down - 1) // down
+
+        def call(out, stride, numel, stream):
+            return self._dll.speechPlayer_batch_exportResampled(self._h, _ptr(sel), n, rate, zeros, rolloff, win, beta, out, fmt, stride, stream)
+        return self._export_rows(lens, (), torch.float32 if fmt else torch.int16, padded, call)
 
     def stemTensor(self, columns, utterances=None, dtype=None, padded=True):
         """The signal stems as a torch tensor on the batch's device (speechPlayer_batch_exportStems), filled on torch's current stream
