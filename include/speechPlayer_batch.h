@@ -46,9 +46,26 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch);
  * which the stages with the frame state machine run faster; 2: the direct stages always; 0: never).
  * "quiet_last" (1, default: a launch queues the quiet groups' kernels behind the noisy groups', whose few long workgroups then start first;
  * 0: in front; read by every launch).
- * "tracks", "track_budget_mb" and "direct" are read by speechPlayer_batch_setUtterances: set them before it.  No option changes the
- * PCM of MODE_EXACT; MODE_FAST stays within its tolerance whichever kernel runs (the direct stages advance the coefficients of a
- * fade by recurrences, re-seeded exactly at every fade's first sample: relative error <= 4 F 2^-53 after F fade samples). */
+ * "direct_lean" (the direct stages' residency: 1 two workgroups per CU, 0 one, -1, default: the engine's choice by mode, size and
+ * whether the resident batch's direct group is time-aligned).
+ * Read by:
+ *   "sort", "track_budget_mb", "direct"   the next set call (any of the speechPlayer_batch_set* entry points): set them before it;
+ *                                          changed afterwards they do nothing until the next one.
+ *   "mode"                                 every launch (the arithmetic) and the next set call (the routing of "direct" = 1 and
+ *                                          whether tracks pay): a launch in the other mode runs the plan as it was made.
+ *   "layout"                               the next set call (whether a direct group is formed, whether lonely quiet utterances
+ *                                          join the noisy ones) and every launch (which kernel runs each group of the plan as it
+ *                                          was made: 0 runs the quiet and the once-tracked groups on the lane kernel, 2 the
+ *                                          quiet nasal-free group on the lane-pipelined one; a direct group stays on its stages).
+ *   "tracks"                               the next set call (whether tracks are planned) and every launch: 0 runs a planned
+ *                                          tracked group on the stages with the frame state machine; 1 after a set call under 0
+ *                                          finds no tracks and changes nothing.
+ *   "direct_lean", "quiet_last"            every launch.
+ *   "pitch_table_mb", "source_table_mb", "source_lane_lists"   every export that builds the table they bound.
+ * No option, whenever it is changed, changes the PCM of MODE_EXACT, the lengths or the index marks; MODE_FAST stays within its
+ * tolerance whichever kernel runs (the direct stages advance the coefficients of a fade by recurrences, re-seeded exactly at every
+ * fade's first sample: relative error <= 4 F 2^-53 after F fade samples).  The exports of the batch as set read no option but the
+ * three of their tables.  tests/test_gpu_player_script.py changes each between a set call and a launch. */
 int speechPlayer_batch_setOption(speechPlayer_batch_t batch, const char* name, int value);
 
 /*

@@ -579,7 +579,7 @@ struct Batch {
     long long nTrackedUtt = 0;             // the utterances among them
     long long nJobs = 0, trackEntries = 0; // distinct tracks of the batch, their entries (16 B each)
     int directLean = -1;                   // the direct stages' residency: 1 two workgroups per CU (the lean stages), 0 one, -1 the engine's choice (direct_lean())
-    bool directAligned = false;            // setUtterances: half or more of the direct candidates sit in runs of 32 or more equally long, equally timed utterances
+    bool directAligned = false;            // of the resident batch's direct group (set_commit; false without one): half or more of the direct candidates sit in runs of 32 or more equally long, equally timed utterances
     int direct = 1;                        // noisy utterances with finite, bounded parameters and no tracks: 1 the direct stages (klatt_direct.h) unless their
                                            // lanes are time-aligned and the mode is MODE_EXACT (setUtterances), 2 the direct stages always, 0 the stages with the frame state machine
     long long nDirect = 0;                 // order[nQuiet + nTracked .. + nDirect) = such utterances (slots)
@@ -2733,7 +2733,7 @@ static_assert(SPEECHPLAYER_LABEL_GAP == kLabelGap && SPEECHPLAYER_LABEL_PUFF == 
 static void batch_clear(Batch* b)
 {
     b->nUtt = 0; b->nFrames = 0; b->nFramesSpoken = 0; b->nLists = 0; b->nSlots = 0; b->nQuiet = 0; b->nNoNasal = 0; b->nNoNasalUtt = 0; b->totalSamples = 0; b->poolSamples = 0;
-    b->nTracked = 0; b->nTrackedUtt = 0; b->nJobs = 0; b->trackEntries = 0; b->nDirect = 0; b->nDirectUtt = 0; b->nDirectFrames = 0;
+    b->nTracked = 0; b->nTrackedUtt = 0; b->nJobs = 0; b->trackEntries = 0; b->nDirect = 0; b->nDirectUtt = 0; b->nDirectFrames = 0; b->directAligned = false;
     b->lens.clear(); b->outStart.assign(1, 0); b->results.clear(); b->resultsFresh = false; b->floatFresh = false;
     b->uttFrameStart.clear(); b->uttFrames.clear(); b->uttList.clear(); b->uttSeed.clear(); b->timelineFresh = false; b->epochFresh = false;
     b->hasLabels = false; b->listUnits.clear();
@@ -2983,6 +2983,7 @@ struct SetCall {
     TrackPlan plan;
     std::vector<uint32_t> directFirst;
     long long nDirectUtt = 0;
+    bool directAligned = false;                  // route_direct's verdict; false when the call forms no direct group (Batch::directAligned)
     std::vector<UttDesc> utt;
     std::vector<long long> uttFrameStart;
     std::vector<uint32_t> uttFrames, uttList, uttSeed;
@@ -3277,7 +3278,7 @@ static int set_plan(SetCall& c)
         if (tracks_pay(lists, eligible.data(), plan.tracked.data(), plan.entries * sizeof(double2), route)) mark_tracked(lists, plan.tracked.data(), plan.kinds.data());
         else { plan.jobs.clear(); plan.entries = 0; plan.tracked.assign((size_t)nL, 0); }
     }
-    if (route.want_direct()) b->directAligned = route_direct(lists, eligible.data(), route);
+    if (route.want_direct()) c.directAligned = route_direct(lists, eligible.data(), route);
     restore_rerouted(lists, rerouted);
     return 0;
 }
@@ -3435,6 +3436,7 @@ static int set_commit(SetCall& c)
     b->nTracked = lanes.nTrackedUtt > 0 ? lanes.nTracked : 0; b->nTrackedUtt = lanes.nTrackedUtt;
     b->nJobs = lanes.nTrackedUtt > 0 ? (long long)c.plan.jobs.size() : 0; b->trackEntries = lanes.nTrackedUtt > 0 ? (long long)c.plan.entries : 0;
     b->nDirect = c.nDirectUtt > 0 ? lanes.nDirectSlots : 0; b->nDirectUtt = c.nDirectUtt; b->nDirectFrames = (long long)c.scratch.directJobs.size();
+    b->directAligned = c.nDirectUtt > 0 && c.directAligned;
     b->totalSamples = c.total; b->poolSamples = c.pool;
     b->lens.swap(c.lens); b->outStart.swap(c.outStart); b->denseStart.swap(c.denseStart);
     b->uttFrameStart.swap(c.uttFrameStart); b->uttFrames.swap(c.uttFrames); b->uttList.swap(c.uttList); b->uttSeed.swap(c.uttSeed);
