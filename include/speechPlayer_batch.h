@@ -480,6 +480,59 @@ long long speechPlayer_pcmResample(const sample* pcm, long long length, int srcR
  * device memory of the batch's device, misaligned to the element or too small. */
 long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int outRate, int zeros,
 	double rolloff, int window, double beta, void* deviceOut, int format, long long rowStride, void* stream);
+/*
+ * A batch's PCM convolved with impulse responses: an FIR filter per row -- a room, a channel, a microphone.  For a row whose utterance
+ * has L samples of int16 PCM s(t), and an impulse response h[0 .. K-1] of float32:
+ *   input     x[n] = (float)s(n) / 32767.0f (the bits of speechPlayer_batch_exportPcm's format 1); a sample outside 0 .. L-1 is +0; the
+ *             pool's padding and the neighbouring utterances are never read as signal
+ *   length    tail = 1: Lout = L + K - 1, the full convolution, reverberant tail included.  tail = 0: Lout = L, the first L outputs, so
+ *             the label grids of the other exports apply unchanged.  Output sample m lies at source sample m: whatever delay the response
+ *             has is the caller's
+ *   output    for m = 0 .. Lout-1: acc = +0; for k = 0 .. K-1 ascending acc = fmaf(x[m - k], h[k], acc), each step ONE correctly rounded
+ *             binary32 fused multiply-add with gradual underflow; y[m] = acc + 0.0f.  The definition is the function bodies of
+ *             csrc/klatt_convolve.h (conv_step, conv_finish), which the host and the device compile from one source;
+ *             speechPlayer_pcmConvolve executes them in a plain loop
+ *   format 1  float32: y[m]
+ *   format 0  int16: the resampler's conversion of y[m] (one float32 product by 32767, clipped to 32767 and -32768, rintf)
+ *   responses every h[k] is finite and |h[k]| <= 2^32, refused otherwise: with K <= kConvolveMaxTaps = 65536 and |x| <= 32768 / 32767 no
+ *             sum overflows, so no NaN appears whose bits would differ between host and device
+ * The resampler forbids fusing; this definition demands it: it halves the instruction count of a loop that is the whole cost at
+ * thousands of taps; fmaf is exact by the C standard on the host, whatever the build flags; the device's v_fma_f32 / v_pk_fma_f32 are
+ * the same operation; and an f32 MFMA on this part is documented as bitwise an fmaf chain, so a later matrix-core kernel could meet the
+ * same bits (it is not part of this export).
+ * Lemma.  For finite operands, inserting or removing terms whose product is +-0 -- samples outside the utterance, zero taps, the zero
+ * padding of a tap block -- does not change y[m].  A +-0 product added to a nonzero acc returns acc; added to a zero acc it returns a
+ * zero; a zero acc of either sign followed by a nonzero product p returns RN(p).  So two such sequences agree at every step except
+ * possibly in the sign of a zero, and the closing + 0.0f makes that +0.  This is what lets the kernel skip tap blocks that lie wholly
+ * outside the signal, pad blocks to a multiple of four taps and stage masked inputs.
+ * Like the resampler, the result is a function of the batch's PCM: it depends on the mode and, in MODE_FAST, on whatever that mode's
+ * tolerance allows; it needs a synthesis launch.
+ * Out of scope: live handles (filter state across pulls); NodePlayer, which reaches the export through speechPlayer_node_part; a
+ * spectrogram or resampling of the convolved signal (those exports read the pool); per-row gains and wet/dry mixes (put them in the
+ * response); FFT or MFMA formulations.
+ *
+ * Host only, touches no device: the definition above on `length` samples of plain PCM and one response of `taps` values -- the statement
+ * the device is held to bit for bit.  out: float[Lout] (format 1) or int16[Lout] (format 0).  Returns Lout; a NULL out only sizes; -1 on
+ * tail not 0 or 1, a NULL ir, taps < 1 or above 65536, a tap that is not finite or above 2^32 in magnitude, an unknown format,
+ * length < 0 or above 2^44, a NULL pcm with length > 0, a capacity below Lout. */
+long long speechPlayer_pcmConvolve(const sample* pcm, long long length, const float* ir, long long taps, int tail, int format, void* out,
+	long long capacity);
+/* The chosen utterances' PCM, row i convolved with response irOf[i], into caller-owned device memory on the caller's stream.  The nIr
+ * responses lie back to back in HOST memory: response j is ir[irStart[j] .. irStart[j+1]-1] (irOf NULL: nIr must be 1).  irOf is per ROW,
+ * not per utterance: with repeats in `utterances`, one utterance goes through several rooms in one call.  utterances (any order,
+ * repeats allowed, NULL: all), the rows (rowStride > 0: padded rows, +0 past each row's Lout; 0: the rows back to back), the return value
+ * (elements written; 0 writes nothing and needs no buffer), the device-memory checks, the sixteen-in-flight rule and the ordering by
+ * events are those of speechPlayer_batch_exportPcm.  The responses cross the link with the call's staging block, like the row table, and
+ * are not kept on the batch (no new ordering state; at most kConvolveMaxTable = 2^20 taps, 4 MB, which the staging path takes as it
+ * is).  A workgroup takes tiles of kConvolveTile = 1024 consecutive outputs of one row, and the taps in blocks of kConvolveBlock = 1024
+ * (csrc/klatt_convolve.h).
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: no batch, a batch that has not been synthesised since it was set, an
+ * unknown format, rowStride < 0 or below the longest output row, an utterance number outside the batch, an output that is not device
+ * memory of the batch's device, misaligned to the element or too small; tail not 0 or 1; nIr < 1; a NULL ir or irStart; irStart not
+ * starting at 0 or not increasing (a response of 0 taps); a response of more than 65536 taps; more than 2^20 taps in all; an irOf[i]
+ * outside 0 .. nIr-1; irOf NULL with nIr != 1; a tap that is not finite or above 2^32 in magnitude (the message gives response and tap). */
+long long speechPlayer_batch_exportConvolved(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const float* ir,
+	const long long* irStart, long long nIr, const long long* irOf, int tail, void* deviceOut, int format, long long rowStride, void* stream);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

@@ -62,6 +62,7 @@ EXPORTS = [
     "speechPlayer_batch_exportStems", "speechPlayer_resonatorCoefficients",
     "speechPlayer_pcmSpectrogram", "speechPlayer_batch_exportSpectrogram",
     "speechPlayer_resampledLength", "speechPlayer_resampleKernel", "speechPlayer_pcmResample", "speechPlayer_batch_exportResampled",
+    "speechPlayer_pcmConvolve", "speechPlayer_batch_exportConvolved",
     "speechPlayer_planTrackKinds",
 ]
 
@@ -389,6 +390,10 @@ def load():
     L.speechPlayer_pcmResample.argtypes = [vp, i64, i32, i32, i32, f64, i32, f64, i32, vp, i64]
     L.speechPlayer_batch_exportResampled.restype = i64
     L.speechPlayer_batch_exportResampled.argtypes = [vp, vp, i64, i32, i32, f64, i32, f64, vp, i32, i64, vp]
+    L.speechPlayer_pcmConvolve.restype = i64
+    L.speechPlayer_pcmConvolve.argtypes = [vp, i64, vp, i64, i32, i32, vp, i64]
+    L.speechPlayer_batch_exportConvolved.restype = i64
+    L.speechPlayer_batch_exportConvolved.argtypes = [vp, vp, i64, vp, vp, i64, vp, i32, vp, i32, i64, vp]
     _lib = L
     return L
 

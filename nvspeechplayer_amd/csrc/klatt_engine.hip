@@ -22,6 +22,7 @@
 #include "klatt_stems.h"
 #include "klatt_spectrum.h"
 #include "klatt_resample.h"
+#include "klatt_convolve.h"
 #include "klatt_export.h"
 #include "klatt_batchplan.h"
 
@@ -5289,6 +5290,89 @@ long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const l
         return elements;
     });
     return done == -2 ? speechPlayer_batch_exportPcm(batch, utterances, nUtterances, deviceOut, format, rowStride, stream) : done;
+}
+
+// ---- the PCM convolved with impulse responses (klatt_convolve.h) -------------------------------------------------------------------------
+// Host only, touches no device: the definition of include/speechPlayer_batch.h through the functions the kernel is compiled from.
+long long speechPlayer_pcmConvolve(const sample* pcm, long long length, const float* ir, long long taps, int tail, int format, void* out,
+                                   long long capacity)
+{
+    begin_call();
+    if (length < 0 || length > kResampleMaxLength || (length > 0 && !pcm)) { set_error("pcmConvolve: length %lld (0 .. 2^44, with its samples)", length); return -1; }
+    if (format != 0 && format != 1) { set_error("pcmConvolve: format %d (0 int16, 1 float32)", format); return -1; }
+    try {
+        ConvPlan P;
+        std::string why;
+        const long long starts[2] = {0, taps};
+        if (!conv_plan(P, ir, starts, 1, tail, why)) { set_error("pcmConvolve: %s", why.c_str()); return -1; }
+        const long long Lout = conv_length(length, taps, tail);
+        if (!out) return Lout;
+        if (capacity < Lout) { set_error("pcmConvolve: the output takes %lld elements, capacity is %lld", Lout, capacity); return -1; }
+        static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
+        return convolve_host(reinterpret_cast<const int16_t*>(pcm), length, P.taps.data(), taps, tail, format, out);
+    } catch (const std::exception& e) { set_error("pcmConvolve: %s", e.what()); return -1; }
+}
+
+// The chosen utterances' PCM, each row through the response irOf names (klatt_convolve.h).  It reads the pool, so it is ordered as
+// speechPlayer_batch_exportPcm is (ExportStage, ofPcm).  A workgroup takes tiles of one row: the packed form's row table counts TILES, the
+// rows carry their first element in the output and their response.  The staging block: rows | tile starts and chunk rows (packed) |
+// the responses.  Nothing is kept on the batch: the kernel reads the responses from the call's own slot.
+long long speechPlayer_batch_exportConvolved(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const float* ir,
+                                             const long long* irStart, long long nIr, const long long* irOf, int tail, void* deviceOut, int format,
+                                             long long rowStride, void* stream)
+{
+    const char* what = "exportConvolved";
+    if (refuse_timing_only("speechPlayer_batch_exportConvolved")) return -1;
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("exportConvolved: format %d (0 int16, 1 float32)", format); return -1; }
+        if (rowStride < 0) { set_error("exportConvolved: rowStride %lld", rowStride); return -1; }
+        ConvPlan P;
+        std::string why;
+        if (!conv_plan(P, ir, irStart, nIr, tail, why)) { set_error("exportConvolved: %s", why.c_str()); return -1; }
+        ExportSelection s;
+        std::vector<ConvRow> rows;
+        std::vector<long long> tiles;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) -> long long {
+                const long long j = conv_row(P, irOf, i, why);
+                if (j < 0) { set_error("exportConvolved: %s", why.c_str()); return -1; }
+                const long long L = (long long)b->lens[(size_t)u], K = P.start[(size_t)j + 1] - P.start[(size_t)j], Lout = conv_length(L, K, tail);
+                rows.push_back(ConvRow{b->outStart[(size_t)u], L, Lout, rowStride > 0 ? (long long)((unsigned long long)i * (unsigned long long)rowStride) : before,
+                                       P.start[(size_t)j], K});      // (export_elements refuses an extent that wraps)
+                tiles.push_back((Lout + kConvolveTile - 1) / kConvolveTile);
+                return Lout;
+            })) return -1;
+        static constexpr ExportNouns kSampleNouns{"longest output row", "samples", nullptr};
+        const long long elements = export_elements(what, kSampleNouns, s, rowStride, 1);
+        if (elements <= 0) return elements;
+        if (!b->launched) { set_error("exportConvolved: the batch has not been synthesised since it was set"); return -1; }
+        const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
+        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+
+        const bool packed = rowStride == 0;
+        std::vector<long long> words;
+        const RowTable table = packed ? packed_row_table(tiles.data(), 0, s.n, kTimelineChunkLog2, words) : RowTable{0, 0};
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words), tapsAt = block.add(P.taps);
+        ExportStage stage(b, st, block, nullptr, true);
+        if (stage.begin()) return -1;
+        ConvArgs A;
+        A.pool = b->dPcm.ptr; A.rows = stage.device<ConvRow>(rowsAt);
+        A.start = packed ? stage.device<long long>(wordsAt) + table.startOff : nullptr;
+        A.chunk = packed ? stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
+        A.rowStride = rowStride; A.tilesPerRow = (rowStride + kConvolveTile - 1) / kConvolveTile;
+        A.nTiles = packed ? words[(size_t)(table.startOff + s.n)] : s.n * A.tilesPerRow;
+        A.taps = stage.device<float>(tapsAt);
+        A.out = deviceOut;
+        // Tiles cost in proportion to their response's taps: many more workgroups than the device holds at once, so that the dispatcher
+        // evens out what a fixed share per workgroup would not.
+        const unsigned grid = (unsigned)std::min<long long>(A.nTiles, 64ll * b->cus);
+        if (format) hipLaunchKernelGGL(klatt_convolve<true>, dim3(grid), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL(klatt_convolve<false>, dim3(grid), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
 }
 
 }  // extern "C"

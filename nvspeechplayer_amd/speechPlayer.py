@@ -731,6 +731,93 @@ def pcmResample(pcm, srcRate, dstRate, zeros=6, rolloff=0.99, window="hann", bet
     return out
 
 
+CONVOLVE_TILE = 1024             # kConvolveTile of csrc/klatt_convolve.h: consecutive outputs of one row a workgroup takes at a time
+CONVOLVE_BLOCK = 1024            # kConvolveBlock: taps staged at a time
+CONVOLVE_MAX_TAPS = 65536        # kConvolveMaxTaps: of one response
+CONVOLVE_MAX_TABLE = 1 << 20     # kConvolveMaxTable: of all responses of a call
+
+
+def check_convolve_request(irs, irOf, nRows, tail, dtype, what="convolvedTensor"):
+    """The argument checks of BatchPlayer.convolvedTensor and pcmConvolve that need no GPU, before any library call: irs one
+    one-dimensional array of real numbers or a list of them, each of 1 .. 65536 taps, at most 2^20 in all, every tap finite and at most
+    2^32 in magnitude once rounded to float32; irOf None (exactly one response) or nRows integers in [0, len(irs)); tail a bool or 0 / 1;
+    dtype None / torch.float32 / np.float32 (float32) or torch.int16 / np.int16.  Raises ValueError or TypeError.  Returns (the
+    responses back to back: float32, their nIr + 1 starts: int64, irOf: int64 or None, tail: 0 or 1, the export format: 0 int16,
+    1 float32)."""
+    if isinstance(irs, np.ndarray) and irs.ndim == 1 and irs.dtype != object:
+        irs = [irs]
+    elif isinstance(irs, (list, tuple)) and len(irs) and all(isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) for v in irs):
+        irs = [irs]
+    if not isinstance(irs, (list, tuple)):
+        raise TypeError("%s: irs must be a one-dimensional array or a list of them, not %s" % (what, type(irs).__name__))
+    if len(irs) < 1:
+        raise ValueError("%s: at least one impulse response" % what)
+    flat, start = [], [0]
+    for j, h in enumerate(irs):
+        try:
+            a = np.asarray(h.detach().cpu().numpy() if hasattr(h, "detach") else h)
+        except Exception:
+            raise TypeError("%s: response %d is not an array" % (what, j))
+        if a.ndim != 1 or a.dtype.kind not in "fiu":
+            raise TypeError("%s: response %d must be a one-dimensional array of real numbers, not %s %s" % (what, j, a.dtype, list(a.shape)))
+        if not 1 <= len(a) <= CONVOLVE_MAX_TAPS:
+            raise ValueError("%s: response %d has %d taps (1 .. %d)" % (what, j, len(a), CONVOLVE_MAX_TAPS))
+        with np.errstate(over="ignore"):
+            a = a.astype(np.float32)
+        bad = np.flatnonzero(~(np.abs(a) <= np.float32(2.0 ** 32)))
+        if len(bad):
+            raise ValueError("%s: tap %d of response %d is %r (finite, at most 2^32 in magnitude)" % (what, bad[0], j, float(a[bad[0]])))
+        flat.append(a)
+        start.append(start[-1] + len(a))
+        if start[-1] > CONVOLVE_MAX_TABLE:
+            raise ValueError("%s: the responses have more than %d taps in all" % (what, CONVOLVE_MAX_TABLE))
+    if irOf is None:
+        if len(irs) != 1:
+            raise ValueError("%s: irOf is needed with %d impulse responses" % (what, len(irs)))
+        of = None
+    else:
+        of = np.asarray(irOf.detach().cpu().numpy() if hasattr(irOf, "detach") else irOf)
+        if of.dtype.kind not in "iu" or of.ndim != 1:
+            raise TypeError("%s: irOf must be a one-dimensional array of integers, not %s %s" % (what, of.dtype, list(of.shape)))
+        if len(of) != nRows:
+            raise ValueError("%s: irOf has %d entries for %d rows" % (what, len(of), nRows))
+        of = np.ascontiguousarray(of.astype(np.int64))
+        if len(of) and (of.min() < 0 or of.max() >= len(irs)):
+            raise ValueError("%s: irOf must lie in [0, %d)" % (what, len(irs)))
+    if isinstance(tail, (bool, np.bool_)):
+        tail = int(tail)
+    elif not isinstance(tail, (int, np.integer)) or tail not in (0, 1):
+        raise ValueError("%s: tail must be True or False (1 or 0), not %r" % (what, tail))
+    names = {"float32": 1, "int16": 0}
+    key = "float32" if dtype is None else (str(dtype).replace("torch.", "") if type(dtype).__module__.startswith("torch") else None)
+    if key is None:
+        try:
+            key = np.dtype(dtype).name
+        except TypeError:
+            key = repr(dtype)
+    if key not in names:
+        raise TypeError("%s: dtype must be float32 or int16, not %s" % (what, dtype))
+    return np.ascontiguousarray(np.concatenate(flat)), np.array(start, np.int64), of, int(tail), names[key]
+
+
+def pcmConvolve(pcm, ir, tail=True, dtype=np.float32):
+    """int16 PCM convolved with one impulse response on the host (speechPlayer_pcmConvolve; no GPU): -> float32 (sample / 32767 scale)
+    or int16, len(pcm) + len(ir) - 1 values (tail) or len(pcm), by the definition in include/speechPlayer_batch.h -- the chain of float32
+    fused multiply-adds the device runs, in ascending tap order."""
+    s = np.ascontiguousarray(np.asarray(pcm))
+    if s.dtype != np.int16 or s.ndim != 1:
+        raise TypeError("pcmConvolve: pcm must be a one-dimensional int16 array, not %s %s" % (s.dtype, list(s.shape)))
+    h, start, _, tail, fmt = check_convolve_request(ir, None, 1, tail, dtype, "pcmConvolve")
+    n = len(s) + len(h) - 1 if tail else len(s)
+    out = np.zeros(n, np.float32 if fmt else np.int16)
+    got = _native.load().speechPlayer_pcmConvolve(s.ctypes.data if len(s) else None, len(s), h.ctypes.data, len(h), tail, fmt,
+                                                  out.ctypes.data if n else None, n)
+    if got < 0:
+        raise RuntimeError(_native.last_error())
+    assert got == n, (got, n)
+    return out
+
+
 def check_option_value(name, value):
     """speechPlayer_batch_setOption takes a C int: a value outside its range would wrap without a word (2 ** 40 arrives as 0).  Returns
     int(value), or raises ValueError."""
@@ -1037,6 +1124,26 @@ class BatchPlayer(object):
 
         def call(out, stride, numel, stream):
             return self._dll.speechPlayer_batch_exportResampled(self._h, _ptr(sel), n, rate, zeros, rolloff, win, beta, out, fmt, stride, stream)
+        return self._export_rows(lens, (), torch.float32 if fmt else torch.int16, padded, call)
+
+    def convolvedTensor(self, irs, irOf=None, tail=True, utterances=None, dtype=None, padded=True):
+        """The batch's PCM convolved with impulse responses as a torch tensor on the batch's device
+        (speechPlayer_batch_exportConvolved), filled on torch's current stream behind the synthesis without a host wait:
+        -> (pcm, lengths).  irs: one 1-D array of float32 taps (a room, a channel, a microphone) or a list of them; irOf: the response of
+        each ROW (None: the one response) -- with repeats in `utterances`, one utterance goes through several rooms in one call.  tail:
+        a row of L samples and K taps gives L + K - 1 values (the full convolution) or, tail=False, the first L, on the grid of the
+        other exports.  utterances, padded and the (pcm, lengths) pair as pcmTensor's; dtype torch.float32 (default) or torch.int16
+        (clipped, rounded to nearest even).  The batch must have been synthesised since it was set; pcmConvolve is the same definition
+        on the host, which the device equals bit for bit."""
+        import torch
+        sel, n, idx = self._selection("convolvedTensor", utterances)
+        h, start, of, tail, fmt = check_convolve_request(irs, irOf, n, tail, dtype)
+        taps = np.diff(start)[of if of is not None else np.zeros(n, np.int64)]
+        lens = self._lengths()[idx].astype(np.int64) + (taps - 1 if tail else 0)
+
+        def call(out, stride, numel, stream):
+            return self._dll.speechPlayer_batch_exportConvolved(self._h, _ptr(sel), n, h.ctypes.data, start.ctypes.data, len(start) - 1, _ptr(of),
+                                                                tail, out, fmt, stride, stream)
         return self._export_rows(lens, (), torch.float32 if fmt else torch.int16, padded, call)
 
     def stemTensor(self, columns, utterances=None, dtype=None, padded=True):
