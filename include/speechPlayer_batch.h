@@ -533,6 +533,91 @@ long long speechPlayer_pcmConvolve(const sample* pcm, long long length, const fl
  * outside 0 .. nIr-1; irOf NULL with nIr != 1; a tap that is not finite or above 2^32 in magnitude (the message gives response and tap). */
 long long speechPlayer_batch_exportConvolved(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const float* ir,
 	const long long* irStart, long long nIr, const long long* irOf, int tail, void* deviceOut, int format, long long rowStride, void* stream);
+/*
+ * A batch's PCM mixed with noise and other utterances at set levels: additive noise at a chosen signal-to-noise ratio, babble, two-talker
+ * mixtures -- the other half of an augmentation recipe beside speechPlayer_batch_exportConvolved.  For a row whose utterance has L samples
+ * of int16 PCM s(t):
+ *   input     x[n] = (float)s(n) / 32767.0f (the bits of speechPlayer_batch_exportPcm's format 1).  The output has L samples, on the grid of
+ *             the other exports; there is no tail
+ *   sources   a CLIP of the batch's noise bank (speechPlayer_batch_setNoiseBank): float32 c[0 .. N-1], 1 <= N < 2^31, every value finite and
+ *             at most 2^16 in magnitude; or an UTTERANCE of the same batch, x_u[n] = (float)s_u(n) / 32767.0f, N = L_u -- it may be the
+ *             row's own
+ *   powers    of an utterance: S_u = sum s_u(n)^2 as an exact unsigned 64-bit integer (order-free: any reduction gives the same bits;
+ *             speechPlayer_batch_exportPower hands it out) and P_u = (double)S_u / (double)L_u / 1073676289.0, 0 for L_u = 0.  Of a clip:
+ *             P_c = (sum over n ascending of (double)c[n] * (double)c[n]) / N, computed once on the host when the bank is set and kept
+ *             with it (speechPlayer_batch_noiseBank).  Both are WHOLE-SIGNAL mean squares, silences included
+ *   placement term j with loop = 1: v_j[m] = src[(offset + m) mod N], 0 <= offset < N.  loop = 0: v_j[m] = src[m - offset] where
+ *             0 <= m - offset < N, else +0; |offset| <= 2^44; a negative offset skips the source's beginning
+ *   level     levelKind = 1: g_j = (float)level, finite, |level| <= 2^32.  levelKind = 0: level is an SNR in dB, finite, |level| <= 200;
+ *             ratio = pow(10.0, level / 10.0) is evaluated on the HOST for both statements, and g_j = mix_gain(Ps, Pv, ratio) =
+ *             (Ps > 0 && Pv * ratio > 0) ? (float)fmin(sqrt(Ps / (Pv * ratio)), 4294967296.0) : 0.0f -- one binary64 product, one
+ *             quotient and one square root, each IEEE on both sides.  Ps is the power of the row's own utterance at gain 1, whatever
+ *             speechGain is; a silent row or a silent source gives gain 0
+ *   output    acc = speechGain * x[m], one binary32 product (speechGain finite, at most 2^32 in magnitude; NULL: 1); for j ascending
+ *             acc = fmaf(v_j[m], g_j, acc); y[m] = acc + 0.0f.  Format 1 is y[m], format 0 the resampler's int16 conversion of it.  With
+ *             at most kMixMaxTerms = 64 terms per row no sum overflows under the bounds above.  The convolution's Lemma holds: a term whose
+ *             product is +-0 may be dropped without changing a bit, so the kernel skips a term that lies wholly outside a tile
+ * The definition is the function bodies of csrc/klatt_mix.h (mix_power, mix_gain, mix_source_index; conv_step and conv_finish of
+ * csrc/klatt_convolve.h), which the host and the device compile from one source; speechPlayer_pcmMix executes them in a plain loop.
+ * The result is a function of the batch's PCM: it needs a synthesis launch, depends on the mode (in MODE_FAST on whatever that mode's
+ * tolerance allows) and is ordered as speechPlayer_batch_exportPcm is.
+ * Out of scope: live handles; NodePlayer, which reaches the export through speechPlayer_node_part; mixing onto a convolved or resampled
+ * signal (use speechGain = 0 for the noise bed and add it); segment or active-speech (VAD-weighted) levels; loudness weighting; random
+ * draws of any kind -- clips, offsets and levels are the caller's.
+ */
+typedef struct {
+	int kind;            /* 0 a clip of the noise bank, 1 an utterance of the batch */
+	int levelKind;       /* 0 `level` is an SNR in dB, 1 a linear gain */
+	long long source;    /* the clip's or the utterance's number */
+	long long offset;
+	double level;
+	int loop;            /* 0 or 1 */
+	int reserved;
+} speechPlayer_mixTerm_t;
+typedef struct {
+	const void* data;
+	long long length;
+	int format;          /* 0 int16 (an utterance), 1 float32 (a clip) */
+} speechPlayer_mixSource_t;
+/* The batch's noise bank: nNoise clips back to back in HOST memory, clip k is noise[noiseStart[k] .. noiseStart[k+1]-1].  It is validated
+ * and its clips' powers are computed on the host; the samples are kept in device memory.  At most 2^20 clips and 2^28 samples; nNoise = 0
+ * frees it.  It survives set calls and synthesis launches and dies with the batch.  Replacing it waits for the exports that read the old
+ * one; an export issued after the call returns reads the new one.  Returns 0, or -1 (SPEECHPLAYER_ERR_ARGUMENT, the bank as it was): no
+ * batch, nNoise outside 0 .. 2^20, a NULL noise or noiseStart, noiseStart not starting at 0 or not increasing (a clip of no samples), more
+ * than 2^28 samples, a value that is not finite or above 2^16 in magnitude (the message gives clip and sample). */
+int speechPlayer_batch_setNoiseBank(speechPlayer_batch_t batch, const float* noise, const long long* noiseStart, long long nNoise);
+/* The bank's clips: returns their number (0: no bank) and fills power[] (P_c) and length[] (each may be NULL) when it is <= capacity. */
+long long speechPlayer_batch_noiseBank(speechPlayer_batch_t batch, double* power, long long* length, long long capacity);
+/* S_u of the chosen utterances, one uint64 per row, into caller-owned device memory on the caller's stream: speechPlayer_batch_exportPcm's
+ * contract (row selection, return value = rows written, device-memory checks, the sixteen-in-flight rule, ordering by events, no host
+ * wait) over one element per row.  Lanes accumulate in 64 bits; one 64-bit atomic add per wavefront (csrc/klatt_mix.h: klatt_power). */
+long long speechPlayer_batch_exportPower(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, void* deviceOut, void* stream);
+/* The chosen utterances' PCM, row i mixed with its terms terms[termStart[i] .. termStart[i+1]-1] (termStart: n + 1 entries, CSR per ROW --
+ * not per utterance: with repeats in `utterances`, one utterance gets several mixtures in one call; equal entries are a row with no terms),
+ * into caller-owned device memory on the caller's stream.  speechGain: one per row (NULL: 1).  deviceGains: NULL, or device memory for
+ * termStart[n] floats that receive the g_j actually applied -- the labels of the mixture.  utterances, the rows (rowStride > 0: padded
+ * rows, +0 past each row's L; 0: the rows back to back), the return value (elements written; 0 writes nothing and needs no buffer), the
+ * device-memory checks, the sixteen-in-flight rule, the ordering by events and the absence of host waits are those of
+ * speechPlayer_batch_exportPcm; a call that names a clip also follows the other readers of the bank.  A workgroup takes tiles of
+ * kMixTile = 1024 consecutive outputs of one row (csrc/klatt_mix.h).
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written (the message names row and term): no batch, a batch that has not been
+ * synthesised since it was set, an unknown format, rowStride < 0 or below the longest row, an utterance number outside the batch, an
+ * output or deviceGains that is not device memory of the batch's device, misaligned to the element or too small; a NULL termStart, or one
+ * that does not start at 0 or decreases; more than 64 terms in a row or 2^22 in a call; terms NULL where there are some; a kind or
+ * levelKind other than 0 or 1, a loop other than 0 or 1; a clip with no bank set, or outside the bank; a source utterance outside the
+ * batch; a looped term on a source of length 0 or with an offset outside 0 .. N-1; an offset above 2^44 in magnitude; a gain or speech
+ * gain that is not finite or above 2^32 in magnitude; an SNR that is not finite or above 200 dB in magnitude. */
+long long speechPlayer_batch_exportMixed(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances,
+	const speechPlayer_mixTerm_t* terms, const long long* termStart, const float* speechGain, void* deviceGains, void* deviceOut, int format,
+	long long rowStride, void* stream);
+/* Host only, touches no device: the definition above on `length` samples of plain PCM (at most 2^33) -- the statement the device is held
+ * to bit for bit.  A term's `source` indexes `sources`, whatever its kind: kind 0 names a float32 source (a clip: 1 .. 2^31 - 1 values,
+ * each finite and at most 2^16 in magnitude), kind 1 an int16 one (an utterance: 0 .. 2^33 samples).  gains: NULL, or nTerms floats that
+ * receive the g_j.  out: float[length] (format 1) or int16[length] (format 0).  Returns length; a NULL out only sizes (and fills gains);
+ * -1 on the refusals above that apply (row 0), nTerms above 64, a source whose format does not fit the term's kind, a capacity below
+ * length. */
+long long speechPlayer_pcmMix(const sample* pcm, long long length, float speechGain, const speechPlayer_mixSource_t* sources, long long nSources,
+	const speechPlayer_mixTerm_t* terms, long long nTerms, float* gains, int format, void* out, long long capacity);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

@@ -63,6 +63,8 @@ EXPORTS = [
     "speechPlayer_pcmSpectrogram", "speechPlayer_batch_exportSpectrogram",
     "speechPlayer_resampledLength", "speechPlayer_resampleKernel", "speechPlayer_pcmResample", "speechPlayer_batch_exportResampled",
     "speechPlayer_pcmConvolve", "speechPlayer_batch_exportConvolved",
+    "speechPlayer_pcmMix", "speechPlayer_batch_setNoiseBank", "speechPlayer_batch_noiseBank", "speechPlayer_batch_exportPower",
+    "speechPlayer_batch_exportMixed",
     "speechPlayer_planTrackKinds",
 ]
 
@@ -394,6 +396,16 @@ def load():
     L.speechPlayer_pcmConvolve.argtypes = [vp, i64, vp, i64, i32, i32, vp, i64]
     L.speechPlayer_batch_exportConvolved.restype = i64
     L.speechPlayer_batch_exportConvolved.argtypes = [vp, vp, i64, vp, vp, i64, vp, i32, vp, i32, i64, vp]
+    L.speechPlayer_pcmMix.restype = i64
+    L.speechPlayer_pcmMix.argtypes = [vp, i64, ctypes.c_float, vp, i64, vp, i64, vp, i32, vp, i64]
+    L.speechPlayer_batch_setNoiseBank.restype = i32
+    L.speechPlayer_batch_setNoiseBank.argtypes = [vp, vp, vp, i64]
+    L.speechPlayer_batch_noiseBank.restype = i64
+    L.speechPlayer_batch_noiseBank.argtypes = [vp, vp, vp, i64]
+    L.speechPlayer_batch_exportPower.restype = i64
+    L.speechPlayer_batch_exportPower.argtypes = [vp, vp, i64, vp, vp]
+    L.speechPlayer_batch_exportMixed.restype = i64
+    L.speechPlayer_batch_exportMixed.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, i32, i64, vp]
     _lib = L
     return L
 

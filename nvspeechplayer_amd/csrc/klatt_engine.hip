@@ -23,6 +23,7 @@
 #include "klatt_spectrum.h"
 #include "klatt_resample.h"
 #include "klatt_convolve.h"
+#include "klatt_mix.h"
 #include "klatt_export.h"
 #include "klatt_batchplan.h"
 
@@ -678,6 +679,12 @@ struct Batch {
     DeviceBuffer<float> dResample;             // [taps][up]
     bool resOnDevice = false;
     SharedTable resampleOrder;
+    // klatt_mix.h: the noise bank (speechPlayer_batch_setNoiseBank) -- the clips' starts and powers on the host, their samples on the
+    // device -- kept across set calls until it is replaced; the exports that read it follow one order, which a replacement waits for
+    MixBank bank;
+    bool hasBank = false;
+    DeviceBuffer<float> dBank;
+    SharedTable bankOrder;
 };
 
 // The batch's own streams wait (on the device) for the exports that still read its pool.
@@ -829,7 +836,7 @@ struct ExportStage {
         } else if (timeline_on_stream(b, st)) return -1;
         if (table && table->wait(st)) return -1;
         block.copy_to(slot->host.ptr);
-        HIP_TRY(hipMemcpyAsync(slot->dev.ptr, slot->host.ptr, block.bytes(), hipMemcpyHostToDevice, st));
+        if (block.upload_bytes()) HIP_TRY(hipMemcpyAsync(slot->dev.ptr, slot->host.ptr, block.upload_bytes(), hipMemcpyHostToDevice, st));
         return 0;
     }
     int begin() { return begin([] { return 0; }); }
@@ -2619,7 +2626,7 @@ speechPlayer_batch_t speechPlayer_batch_create(int sampleRate, int device)
               hipEventCreateWithFlags(&b->pcmReady, hipEventDisableTiming) == hipSuccess;
     for (auto& s : b->exportSlot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
     for (auto& s : b->trackSlot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
-    for (hipEvent_t* e : {&b->setDone, &b->setCopied, &b->timelineReady, &b->pitchOrder.done, &b->sourceOrder.done, &b->resampleOrder.done}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    for (hipEvent_t* e : {&b->setDone, &b->setCopied, &b->timelineReady, &b->pitchOrder.done, &b->sourceOrder.done, &b->resampleOrder.done, &b->bankOrder.done}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     { const char* e = getenv("SPEECHPLAYER_TRACKS"); if (e) b->tracks = atoi(e) ? 1 : 0; }
     { const char* e = getenv("SPEECHPLAYER_DIRECT"); if (e) b->direct = std::min(2, std::max(0, atoi(e))); }
     { const char* e = getenv("SPEECHPLAYER_DIRECT_LEAN"); if (e) b->directLean = std::min(1, std::max(-1, atoi(e))); }
@@ -2650,9 +2657,9 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch)
         if (s.done) (void)hipEventDestroy(s.done);
         s.host.release(); s.dev.release();
     }
-    for (hipEvent_t e : {b->setDone, b->setCopied, b->timelineReady, b->pitchOrder.done, b->sourceOrder.done, b->resampleOrder.done}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {b->setDone, b->setCopied, b->timelineReady, b->pitchOrder.done, b->sourceOrder.done, b->resampleOrder.done, b->bankOrder.done}) if (e) (void)hipEventDestroy(e);
     b->dListStart.release(); b->dTimeline.release(); b->dPitch.release(); b->dLabels.release(); b->dUnitFirst.release();
-    b->dSource.release(); b->dEpochs.release(); b->dEpochCount.release(); b->dResample.release();
+    b->dSource.release(); b->dEpochs.release(); b->dEpochCount.release(); b->dResample.release(); b->dBank.release();
     if (b->inputReady) (void)hipEventDestroy(b->inputReady);
     if (b->pcmReady) (void)hipEventDestroy(b->pcmReady);
     b->dShapeIdx.release(); b->dShapeRows.release();
@@ -5369,6 +5376,268 @@ long long speechPlayer_batch_exportConvolved(speechPlayer_batch_t batch, const l
         const unsigned grid = (unsigned)std::min<long long>(A.nTiles, 64ll * b->cus);
         if (format) hipLaunchKernelGGL(klatt_convolve<true>, dim3(grid), dim3(256), 0, st, A);
         else hipLaunchKernelGGL(klatt_convolve<false>, dim3(grid), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
+}
+
+// ---- the PCM mixed with noise and other utterances (klatt_mix.h) ----------------------------------------------------------------------------
+static_assert(sizeof(speechPlayer_mixTerm_t) == sizeof(MixTermIn) && offsetof(speechPlayer_mixTerm_t, kind) == offsetof(MixTermIn, kind) &&
+              offsetof(speechPlayer_mixTerm_t, levelKind) == offsetof(MixTermIn, levelKind) && offsetof(speechPlayer_mixTerm_t, source) == offsetof(MixTermIn, source) &&
+              offsetof(speechPlayer_mixTerm_t, offset) == offsetof(MixTermIn, offset) && offsetof(speechPlayer_mixTerm_t, level) == offsetof(MixTermIn, level) &&
+              offsetof(speechPlayer_mixTerm_t, loop) == offsetof(MixTermIn, loop), "klatt_mix.h restates speechPlayer_mixTerm_t");
+
+// Host only, touches no device: the definition of klatt_mix.h through the functions the kernels are compiled from.
+long long speechPlayer_pcmMix(const sample* pcm, long long length, float speechGain, const speechPlayer_mixSource_t* sources, long long nSources,
+                              const speechPlayer_mixTerm_t* terms, long long nTerms, float* gains, int format, void* out, long long capacity)
+{
+    begin_call();
+    static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
+    if (length < 0 || length > kMixMaxLength || (length > 0 && !pcm)) { set_error("pcmMix: length %lld (0 .. 2^33, with its samples)", length); return -1; }
+    if (format != 0 && format != 1) { set_error("pcmMix: format %d (0 int16, 1 float32)", format); return -1; }
+    if (nSources < 0 || (nSources > 0 && !sources)) { set_error("pcmMix: %lld sources", nSources); return -1; }
+    if (nTerms < 0 || nTerms > kMixMaxTerms || (nTerms > 0 && !terms)) { set_error("pcmMix: %lld terms (0 .. %d, with their descriptors)", nTerms, kMixMaxTerms); return -1; }
+    try {
+        std::string why;
+        if (!mix_check_speech_gain(speechGain, 0, why)) { set_error("pcmMix: %s", why.c_str()); return -1; }
+        std::vector<MixSource> src((size_t)nSources);
+        std::vector<char> powered((size_t)nSources, 0);
+        for (long long k = 0; k < nSources; ++k) {
+            const speechPlayer_mixSource_t& q = sources[k];
+            if (q.format != 0 && q.format != 1) { set_error("pcmMix: source %lld has format %d (0 int16, 1 float32)", k, q.format); return -1; }
+            if (q.length < 0 || (q.format == 1 ? q.length < 1 || q.length >= (1ll << 31) : q.length > kMixMaxLength) || (q.length > 0 && !q.data)) {
+                set_error("pcmMix: source %lld has %lld samples (a clip 1 .. 2^31 - 1, an utterance 0 .. 2^33, with its samples)", k, q.length); return -1;
+            }
+            if (q.format == 1) {
+                const long long bad = mix_bad_value(static_cast<const float*>(q.data), q.length);
+                if (bad >= 0) { set_error("pcmMix: sample %lld of clip %lld is %g (finite, at most 2^16 in magnitude)", bad, k, (double)static_cast<const float*>(q.data)[bad]); return -1; }
+            }
+            src[(size_t)k] = MixSource{q.data, q.length, q.format, 0.0};
+        }
+        const MixTermIn* in = reinterpret_cast<const MixTermIn*>(terms);
+        std::vector<MixTermHost> host((size_t)nTerms);
+        double Ps = 0.0;
+        bool havePs = false;
+        for (long long j = 0; j < nTerms; ++j) {
+            const MixTermIn& t = in[j];
+            // (one list of sources for both kinds: a clip is a float32 source, an utterance an int16 one)
+            if (!mix_check_term(t, 0, j, t.kind == 0 ? nSources : -1, t.kind == 1 ? nSources : 0, [&](int, long long k) { return src[(size_t)k].length; }, why)) {
+                set_error("pcmMix: %s", why.c_str()); return -1;
+            }
+            MixSource& q = src[(size_t)t.source];
+            if (q.isFloat != (t.kind == 0)) { set_error("pcmMix: row 0, term %lld: kind %d names source %lld, which is %s", j, t.kind, t.source, q.isFloat ? "float32 (a clip)" : "int16 (an utterance)"); return -1; }
+            float g = (float)t.level;
+            if (t.levelKind == 0) {
+                if (!havePs) { Ps = mix_power(mix_square_sum(reinterpret_cast<const int16_t*>(pcm), length), length); havePs = true; }
+                if (!powered[(size_t)t.source]) {
+                    q.power = q.isFloat ? mix_clip_power(static_cast<const float*>(q.data), q.length)
+                                        : mix_power(mix_square_sum(static_cast<const int16_t*>(q.data), q.length), q.length);
+                    powered[(size_t)t.source] = 1;
+                }
+                g = mix_gain(Ps, q.power, mix_ratio(t.level));
+            }
+            host[(size_t)j] = MixTermHost{(int)t.source, t.offset, t.loop, g};
+        }
+        if (capacity < length && out) { set_error("pcmMix: the output takes %lld elements, capacity is %lld", length, capacity); return -1; }
+        for (long long j = 0; gains && j < nTerms; ++j) gains[j] = host[(size_t)j].gain;
+        if (!out) return length;
+        return mix_host(reinterpret_cast<const int16_t*>(pcm), length, speechGain, src.data(), host.data(), nTerms, format, out);
+    } catch (const std::exception& e) { set_error("pcmMix: %s", e.what()); return -1; }
+}
+
+// The batch's noise bank: validated and its clips' powers computed on the host, its samples kept in device memory until the next call
+// (nNoise = 0 frees it) or the batch's end, whatever is set or synthesised meanwhile.  Replacing it waits (on the host) for the exports
+// that read the old one; the copy has completed when the call returns, so every later export finds the new one.
+int speechPlayer_batch_setNoiseBank(speechPlayer_batch_t batch, const float* noise, const long long* noiseStart, long long nNoise)
+{
+    return (int)batch_entry("setNoiseBank", batch, [&](Batch* b) -> long long {
+        MixBank B;
+        std::string why;
+        if (!mix_bank_plan(B, noise, noiseStart, nNoise, why)) { set_error("setNoiseBank: %s", why.c_str()); return -1; }
+        HIP_TRY(hipSetDevice(b->device));
+        if (b->bankOrder.used) { HIP_TRY(hipEventSynchronize(b->bankOrder.done)); b->bankOrder.used = false; }
+        // From here on the old bank is gone whatever happens: a buffer that must grow is freed first, and a copy that fails may have
+        // overwritten a part of one that is reused.  A failure below leaves the batch with no bank rather than with stale starts and powers.
+        b->hasBank = false;
+        b->bank = MixBank();
+        if (nNoise == 0) { b->dBank.release(); return 0; }
+        const size_t total = (size_t)B.start.back();
+        if (b->dBank.reserve(total)) return -1;
+        HIP_TRY(hipMemcpy(b->dBank.ptr, noise, total * sizeof(float), hipMemcpyHostToDevice));
+        b->bank = std::move(B);
+        b->hasBank = true;
+        return 0;
+    });
+}
+
+long long speechPlayer_batch_noiseBank(speechPlayer_batch_t batch, double* power, long long* length, long long capacity)
+{
+    return batch_entry("noiseBank", batch, [&](Batch* b) -> long long {
+        const long long n = b->hasBank ? b->bank.clips() : 0;
+        for (long long k = 0; k < n && n <= capacity; ++k) {
+            if (power) power[k] = b->bank.power[(size_t)k];
+            if (length) length[k] = b->bank.start[(size_t)k + 1] - b->bank.start[(size_t)k];
+        }
+        return n;
+    });
+}
+
+// The distinct utterances whose S_u a call needs: a slot each, and klatt_power's tiles
+struct PowerSlots {
+    std::vector<long long> slotOfUtt;      // [nUtt], -1: none yet
+    std::vector<PowerJob> jobs;
+    std::vector<long long> tileStart{0};
+    long long of(const Batch* b, long long u)
+    {
+        if (slotOfUtt.empty()) slotOfUtt.assign((size_t)b->nUtt, -1);
+        if (slotOfUtt[(size_t)u] >= 0) return slotOfUtt[(size_t)u];
+        const long long slot = (long long)jobs.size(), L = (long long)b->lens[(size_t)u];
+        jobs.push_back(PowerJob{b->outStart[(size_t)u], L});
+        tileStart.push_back(tileStart.back() + (L + kPowerTile - 1) / kPowerTile);
+        slotOfUtt[(size_t)u] = slot;
+        return slot;
+    }
+    long long tiles() const { return tileStart.back(); }
+};
+
+static int launch_power(Batch* b, hipStream_t st, const PowerSlots& P, const PowerJob* dJobs, const long long* dTileStart, unsigned long long* dSlots)
+{
+    if (P.tiles() == 0) return 0;
+    PowerArgs A;
+    A.pool = b->dPcm.ptr; A.jobs = dJobs; A.tileStart = dTileStart; A.nJobs = (long long)P.jobs.size(); A.nTiles = P.tiles(); A.slots = dSlots;
+    const unsigned grid = (unsigned)std::min<long long>(A.nTiles, 8ll * b->cus);
+    hipLaunchKernelGGL(klatt_power, dim3(grid), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The chosen utterances' S_u = sum s(n)^2, one uint64 per row (klatt_mix.h: klatt_power into the zeroed slots of the call's staging block,
+// then the deal-out to the rows).  It reads the pool, so it is ordered as speechPlayer_batch_exportPcm is (ExportStage, ofPcm).
+long long speechPlayer_batch_exportPower(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, void* deviceOut, void* stream)
+{
+    const char* what = "exportPower";
+    if (refuse_timing_only("speechPlayer_batch_exportPower")) return -1;
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        ExportSelection s;
+        PowerSlots P;
+        std::vector<long long> slotOf;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long, long long u, long long) -> long long {
+                slotOf.push_back(P.of(b, u));
+                return 1;
+            })) return -1;
+        if (s.n == 0) return 0;
+        if (!b->launched) { set_error("exportPower: the batch has not been synthesised since it was set"); return -1; }
+        if (export_output(b, what, deviceOut, s.n, sizeof(unsigned long long))) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const std::vector<unsigned long long> zeros(P.jobs.size(), 0ull);
+        StageBlock block;
+        const int jobsAt = block.add(P.jobs), tilesAt = block.add(P.tileStart), slotOfAt = block.add(slotOf), slotsAt = block.add(zeros);
+        ExportStage stage(b, st, block, nullptr, true);
+        if (stage.begin()) return -1;
+        unsigned long long* dSlots = const_cast<unsigned long long*>(stage.device<unsigned long long>(slotsAt));      // (the slot is this call's until its event)
+        if (launch_power(b, st, P, stage.device<PowerJob>(jobsAt), stage.device<long long>(tilesAt), dSlots)) return -1;
+        const unsigned grid = (unsigned)std::min<long long>((s.n + 255) / 256, 8ll * b->cus);
+        hipLaunchKernelGGL(klatt_power_deal, dim3(grid), dim3(256), 0, st, dSlots, stage.device<long long>(slotOfAt), s.n, static_cast<unsigned long long*>(deviceOut));
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return s.n;
+    });
+}
+
+// The chosen utterances' PCM, row i mixed with its terms terms[termStart[i] .. termStart[i+1]) (klatt_mix.h).  It reads the pool, so it is
+// ordered as speechPlayer_batch_exportPcm is (ExportStage, ofPcm); a call that names a clip also takes its place in the bank's order.  The
+// staging block: rows | tile starts and chunk rows (packed) | the terms as the kernel reads them | their level jobs | the power slots'
+// utterances, tiles and zeros | the gains (reserved: nothing is uploaded).  The slots and the gains are the call's device scratch: they
+// live in its staging slot.
+long long speechPlayer_batch_exportMixed(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const speechPlayer_mixTerm_t* terms,
+                                         const long long* termStart, const float* speechGain, void* deviceGains, void* deviceOut, int format,
+                                         long long rowStride, void* stream)
+{
+    const char* what = "exportMixed";
+    if (refuse_timing_only("speechPlayer_batch_exportMixed")) return -1;
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("exportMixed: format %d (0 int16, 1 float32)", format); return -1; }
+        if (rowStride < 0) { set_error("exportMixed: rowStride %lld", rowStride); return -1; }
+        const MixTermIn* in = reinterpret_cast<const MixTermIn*>(terms);
+        std::string why;
+        ExportSelection s;
+        PowerSlots P;
+        std::vector<MixRow> rows;
+        std::vector<long long> tiles;
+        std::vector<MixTermDev> dev;
+        std::vector<MixGainJob> jobs;
+        bool readsBank = false;
+        double lastDb = 0.0, lastRatio = 1.0;      // pow(10.0, 0.0) is 1
+        const long long nClips = b->hasBank ? b->bank.clips() : -1;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) -> long long {
+                if (!mix_check_row(termStart, i, terms, why)) { set_error("exportMixed: %s", why.c_str()); return -1; }
+                const float sg = speechGain ? speechGain[i] : 1.0f;
+                if (!mix_check_speech_gain(sg, i, why)) { set_error("exportMixed: %s", why.c_str()); return -1; }
+                const long long L = (long long)b->lens[(size_t)u], a = termStart[i], nT = termStart[i + 1] - a;
+                for (long long j = 0; j < nT; ++j) {
+                    const MixTermIn& t = in[a + j];
+                    if (!mix_check_term(t, i, j, nClips, b->nUtt, [&](int kind, long long k) {
+                            return kind == 0 ? b->bank.start[(size_t)k + 1] - b->bank.start[(size_t)k] : (long long)b->lens[(size_t)k];
+                        }, why)) { set_error("exportMixed: %s", why.c_str()); return -1; }
+                    MixTermDev d;
+                    if (t.kind == 0) { d.at = b->bank.start[(size_t)t.source]; d.len = b->bank.start[(size_t)t.source + 1] - d.at; readsBank = true; }
+                    else { d.at = b->outStart[(size_t)t.source]; d.len = (long long)b->lens[(size_t)t.source]; }
+                    d.offset = t.offset; d.flags = (t.kind == 0 ? kMixClip : 0) | (t.loop ? kMixLoop : 0); d.pad = 0;
+                    dev.push_back(d);
+                    MixGainJob job{1.0, 0.0, 0, -1, (float)t.level, 1};
+                    if (t.levelKind == 0) {
+                        if (t.level != lastDb) { lastDb = t.level; lastRatio = mix_ratio(t.level); }      // (a batch repeats few levels: one pow each)
+                        job.linear = 0; job.gain = 0.0f; job.ratio = lastRatio;
+                        job.rowSlot = P.of(b, u);
+                        if (t.kind == 0) job.pv = b->bank.power[(size_t)t.source]; else job.srcSlot = P.of(b, t.source);
+                    }
+                    jobs.push_back(job);
+                }
+                rows.push_back(MixRow{b->outStart[(size_t)u], L, rowStride > 0 ? (long long)((unsigned long long)i * (unsigned long long)rowStride) : before,
+                                      a, (int)nT, sg});      // (export_elements refuses an extent that wraps)
+                tiles.push_back(mix_tiles(L));
+                return L;
+            })) return -1;
+        static constexpr ExportNouns kSampleNouns{"longest output row", "samples", nullptr};
+        const long long elements = export_elements(what, kSampleNouns, s, rowStride, 1);
+        if (elements <= 0) return elements;
+        if (!b->launched) { set_error("exportMixed: the batch has not been synthesised since it was set"); return -1; }
+        const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
+        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
+        const long long nTerms = (long long)dev.size();
+        if (deviceGains && nTerms > 0 && !device_range(deviceGains, (size_t)nTerms * sizeof(float), b->device, sizeof(float), what)) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+
+        const bool packed = rowStride == 0;
+        std::vector<long long> words;
+        const RowTable table = packed ? packed_row_table(tiles.data(), 0, s.n, kTimelineChunkLog2, words) : RowTable{0, 0};
+        const std::vector<unsigned long long> zeros(P.jobs.size(), 0ull);
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words), termsAt = block.add(dev), jobsAt = block.add(jobs), slotJobsAt = block.add(P.jobs),
+                  tilesAt = block.add(P.tileStart), slotsAt = block.add(zeros), gainsAt = block.reserve((size_t)nTerms * sizeof(float));      // (klatt_mix_gains fills the gains)
+        ExportStage stage(b, st, block, readsBank ? &b->bankOrder : nullptr, true);
+        if (stage.begin()) return -1;
+        unsigned long long* dSlots = const_cast<unsigned long long*>(stage.device<unsigned long long>(slotsAt));      // (the slot is this call's until its event)
+        float* dGains = const_cast<float*>(stage.device<float>(gainsAt));
+        if (launch_power(b, st, P, stage.device<PowerJob>(slotJobsAt), stage.device<long long>(tilesAt), dSlots)) return -1;
+        if (nTerms > 0) {
+            const unsigned grid = (unsigned)std::min<long long>((nTerms + 255) / 256, 8ll * b->cus);
+            hipLaunchKernelGGL(klatt_mix_gains, dim3(grid), dim3(256), 0, st, stage.device<MixGainJob>(jobsAt), nTerms, dSlots, stage.device<PowerJob>(slotJobsAt),
+                               dGains, static_cast<float*>(deviceGains));
+            HIP_TRY(hipGetLastError());
+        }
+        MixArgs A;
+        A.pool = b->dPcm.ptr; A.bank = b->dBank.ptr; A.rows = stage.device<MixRow>(rowsAt);
+        A.start = packed ? stage.device<long long>(wordsAt) + table.startOff : nullptr;
+        A.chunk = packed ? stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
+        A.rowStride = rowStride; A.tilesPerRow = mix_tiles(rowStride);
+        A.nTiles = packed ? words[(size_t)(table.startOff + s.n)] : s.n * A.tilesPerRow;
+        A.terms = stage.device<MixTermDev>(termsAt); A.gains = dGains;
+        A.out = deviceOut;
+        const unsigned grid = (unsigned)std::min<long long>(A.nTiles, 8ll * b->cus);
+        if (format) hipLaunchKernelGGL(klatt_mix<true>, dim3(grid), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL(klatt_mix<false>, dim3(grid), dim3(256), 0, st, A);
         HIP_TRY(hipGetLastError());
         if (stage.finish()) return -1;
         return elements;

@@ -105,7 +105,9 @@ std::vector<ExportPiece> list_pieces(long long n, ListOfRow listOfRow, SkipRow s
 }
 
 // A staging block: sections of host memory that cross the link in one copy, each on a 16-byte boundary of the block (whatever a
-// kernel reads by vector loads may follow whatever else).  add() does not copy: the memory must live until copy_to().
+// kernel reads by vector loads may follow whatever else).  add() does not copy: the memory must live until copy_to().  reserve() makes a
+// section without contents -- device scratch a kernel fills before another reads it: nothing is copied into it on the host, and the
+// reserved sections at the block's END do not cross the link either (upload_bytes).
 class StageBlock {
     struct Section { const void* from; size_t bytes, at; };
     std::vector<Section> sections;
@@ -118,12 +120,21 @@ public:
         return (int)sections.size() - 1;
     }
     template <class T> int add(const std::vector<T>& v) { return add(v.data(), v.size() * sizeof(T)); }
+    int reserve(size_t bytes) { return add(nullptr, bytes); }
     size_t bytes() const { return total; }
+    // The bytes from the block's start that hold contents: what the upload copies
+    size_t upload_bytes() const
+    {
+        size_t end = 0;
+        for (const Section& s : sections)
+            if (s.from && s.bytes) end = (s.at + s.bytes + 15) / 16 * 16;
+        return end;
+    }
     size_t offset(int section) const { return sections[(size_t)section].at; }
     void copy_to(void* host) const
     {
         for (const Section& s : sections)
-            if (s.bytes) memcpy(static_cast<char*>(host) + s.at, s.from, s.bytes);
+            if (s.bytes && s.from) memcpy(static_cast<char*>(host) + s.at, s.from, s.bytes);
     }
     template <class T> const T* device(int section, const unsigned char* base) const
     {

@@ -818,6 +818,153 @@ def pcmConvolve(pcm, ir, tail=True, dtype=np.float32):
     return out
 
 
+MIX_TILE = 1024                  # kMixTile of csrc/klatt_mix.h: consecutive outputs of one row a workgroup takes at a time
+MIX_MAX_TERMS = 64               # kMixMaxTerms: of one row
+MIX_MAX_CALL_TERMS = 1 << 22     # kMixMaxCallTerms: of one call
+MIX_MAX_CLIPS = 1 << 20          # kMixMaxClips: of a noise bank
+MIX_MAX_BANK = 1 << 28           # kMixMaxBank: samples of a noise bank
+# speechPlayer_mixTerm_t and speechPlayer_mixSource_t (include/speechPlayer_batch.h)
+mixTermDtype = np.dtype([("kind", np.int32), ("levelKind", np.int32), ("source", np.int64), ("offset", np.int64), ("level", np.float64),
+                         ("loop", np.int32), ("reserved", np.int32)], align=True)
+_mixSourceDtype = np.dtype([("data", np.uint64), ("length", np.int64), ("format", np.int32), ("reserved", np.int32)], align=True)
+assert mixTermDtype.itemsize == 40 and _mixSourceDtype.itemsize == 24
+
+
+class MixTerm(object):
+    """One term of a mixture (speechPlayer_mixTerm_t): a clip of the noise bank (noise=k) or an utterance of the batch (utterance=u), at
+    a signal-to-noise ratio in dB against the row's own utterance (snr=) or at a linear gain (gain=), placed at `offset`: looped
+    (src[(offset + m) mod N], 0 <= offset < N) or, loop=False, once (src[m - offset], silence outside; a negative offset skips the
+    source's beginning)."""
+    __slots__ = ("kind", "levelKind", "source", "offset", "level", "loop")
+
+    def __init__(self, noise=None, utterance=None, snr=None, gain=None, offset=0, loop=True):
+        if (noise is None) == (utterance is None):
+            raise ValueError("MixTerm: exactly one of noise= and utterance=")
+        if (snr is None) == (gain is None):
+            raise ValueError("MixTerm: exactly one of snr= and gain=")
+        for name, v in (("noise", noise), ("utterance", utterance), ("offset", offset)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+                raise TypeError("MixTerm: %s must be an integer, not %r" % (name, v))
+        if not isinstance(loop, (bool, np.bool_)) and loop not in (0, 1):
+            raise ValueError("MixTerm: loop must be True or False, not %r" % (loop,))
+        self.kind, self.source = (0, int(noise)) if utterance is None else (1, int(utterance))
+        self.levelKind, self.level = (0, float(snr)) if gain is None else (1, float(gain))
+        self.offset, self.loop = int(offset), int(bool(loop))
+
+    def record(self):
+        return (self.kind, self.levelKind, self.source, self.offset, self.level, self.loop, 0)
+
+    def __repr__(self):
+        return "MixTerm(%s=%d, %s=%r, offset=%d, loop=%r)" % ("utterance" if self.kind else "noise", self.source, "gain" if self.levelKind else "snr",
+                                                              self.level, self.offset, bool(self.loop))
+
+
+def _mix_terms(terms, what):
+    """A list of MixTerm or a structured array of mixTermDtype -> a contiguous array of mixTermDtype."""
+    if isinstance(terms, np.ndarray):
+        if terms.dtype != mixTermDtype or terms.ndim != 1:
+            raise TypeError("%s: an array of terms must be one-dimensional, of mixTermDtype, not %s %s" % (what, terms.dtype, list(terms.shape)))
+        return np.ascontiguousarray(terms)
+    if isinstance(terms, MixTerm):
+        terms = [terms]
+    if not isinstance(terms, (list, tuple)) or not all(isinstance(t, MixTerm) for t in terms):
+        raise TypeError("%s: terms must be MixTerm objects or an array of mixTermDtype" % what)
+    return np.array([t.record() for t in terms], dtype=mixTermDtype).reshape(-1)
+
+
+def _mix_format(dtype, what):
+    names = {"float32": 1, "int16": 0}
+    key = "float32" if dtype is None else (str(dtype).replace("torch.", "") if type(dtype).__module__.startswith("torch") else None)
+    if key is None:
+        try:
+            key = np.dtype(dtype).name
+        except TypeError:
+            key = repr(dtype)
+    if key not in names:
+        raise TypeError("%s: dtype must be float32 or int16, not %s" % (what, dtype))
+    return names[key]
+
+
+def check_mix_request(terms, nRows, speechGain, dtype, what="mixedTensor"):
+    """The argument checks of BatchPlayer.mixedTensor that need no GPU, before any library call: terms a list of nRows lists of MixTerm
+    (a row with no terms: an empty list) or a pair (array of mixTermDtype, termStart: nRows + 1 integers from 0, not decreasing, the last
+    the array's length); at most 64 terms in a row and 2^22 in all; speechGain None, one number or nRows of them; dtype None /
+    torch.float32 / np.float32 (float32) or torch.int16 / np.int16.  The values of the terms are the library's to refuse.  Raises
+    ValueError or TypeError.  Returns (the terms: mixTermDtype, termStart: int64, speechGain: float32 [nRows] or None, the export format:
+    0 int16, 1 float32)."""
+    if isinstance(terms, tuple) and len(terms) == 2 and isinstance(terms[0], np.ndarray):
+        flat = _mix_terms(terms[0], what)
+        start = np.asarray(terms[1].detach().cpu().numpy() if hasattr(terms[1], "detach") else terms[1])
+        if start.dtype.kind not in "iu" or start.ndim != 1:
+            raise TypeError("%s: termStart must be a one-dimensional array of integers, not %s %s" % (what, start.dtype, list(start.shape)))
+        start = np.ascontiguousarray(start.astype(np.int64))
+        if len(start) != nRows + 1:
+            raise ValueError("%s: termStart has %d entries for %d rows (one more than the rows)" % (what, len(start), nRows))
+        if start[0] != 0 or np.any(np.diff(start) < 0) or start[-1] != len(flat):
+            raise ValueError("%s: termStart must start at 0, not decrease and end at the number of terms (%d)" % (what, len(flat)))
+    else:
+        if not isinstance(terms, (list, tuple)):
+            raise TypeError("%s: terms must be a list of one list of MixTerm per row, or (array of mixTermDtype, termStart)" % what)
+        if len(terms) != nRows:
+            raise ValueError("%s: terms has %d entries for %d rows" % (what, len(terms), nRows))
+        rows = [_mix_terms([] if row is None else row, what) for row in terms]
+        start = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        flat = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros(0, mixTermDtype)
+    counts = np.diff(start)
+    if len(counts) and counts.max() > MIX_MAX_TERMS:
+        raise ValueError("%s: row %d has %d terms (at most %d)" % (what, int(counts.argmax()), int(counts.max()), MIX_MAX_TERMS))
+    if len(flat) > MIX_MAX_CALL_TERMS:
+        raise ValueError("%s: %d terms in all (at most %d)" % (what, len(flat), MIX_MAX_CALL_TERMS))
+    sg = None
+    if speechGain is not None:
+        sg = np.asarray(speechGain.detach().cpu().numpy() if hasattr(speechGain, "detach") else speechGain)
+        if sg.dtype.kind not in "fiu" or sg.ndim > 1:
+            raise TypeError("%s: speechGain must be a number or a one-dimensional array of them, not %s %s" % (what, sg.dtype, list(sg.shape)))
+        if sg.ndim == 1 and len(sg) != nRows:
+            raise ValueError("%s: speechGain has %d entries for %d rows" % (what, len(sg), nRows))
+        with np.errstate(over="ignore"):
+            sg = np.ascontiguousarray(np.broadcast_to(sg.astype(np.float32), (nRows,)))
+    return flat, start, sg, _mix_format(dtype, what)
+
+
+def _mix_clip(a, what, name):
+    a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a)
+    if a.ndim != 1 or a.dtype.kind != "f":
+        raise TypeError("%s: %s must be a one-dimensional array of floats, not %s %s" % (what, name, a.dtype, list(a.shape)))
+    with np.errstate(over="ignore"):
+        return np.ascontiguousarray(a.astype(np.float32))
+
+
+def pcmMix(pcm, sources, terms, speechGain=1.0, dtype=np.float32, gains=False):
+    """int16 PCM mixed with other signals on the host (speechPlayer_pcmMix; no GPU): -> float32 (sample / 32767 scale) or int16
+    [len(pcm)], by the definition in include/speechPlayer_batch.h -- the statement the device is held to bit for bit.  sources: a list
+    of one-dimensional arrays, float32 (a noise clip) or int16 (an utterance); terms: MixTerm objects (or an array of mixTermDtype) whose
+    noise= / utterance= index `sources` -- noise= a float32 source, utterance= an int16 one.  An SNR is taken against the whole-signal
+    mean square of `pcm` at gain 1.  gains=True: -> (mixed, the float32 gains applied, one per term)."""
+    s = np.ascontiguousarray(np.asarray(pcm))
+    if s.dtype != np.int16 or s.ndim != 1:
+        raise TypeError("pcmMix: pcm must be a one-dimensional int16 array, not %s %s" % (s.dtype, list(s.shape)))
+    if not isinstance(sources, (list, tuple)):
+        raise TypeError("pcmMix: sources must be a list of one-dimensional arrays")
+    held, table = [], np.zeros(max(len(sources), 1), _mixSourceDtype)
+    for k, a in enumerate(sources):
+        a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a)
+        a = np.ascontiguousarray(a) if a.dtype == np.int16 and a.ndim == 1 else _mix_clip(a, "pcmMix", "source %d" % k)
+        held.append(a)
+        table[k] = (a.ctypes.data if len(a) else 0, len(a), 0 if a.dtype == np.int16 else 1, 0)
+    flat = _mix_terms(terms, "pcmMix")
+    fmt = _mix_format(dtype, "pcmMix")
+    out = np.zeros(len(s), np.float32 if fmt else np.int16)
+    g = np.zeros(max(len(flat), 1), np.float32)
+    got = _native.load().speechPlayer_pcmMix(s.ctypes.data if len(s) else None, len(s), float(np.float32(speechGain)), table.ctypes.data if len(sources) else None,
+                                             len(sources), flat.ctypes.data if len(flat) else None, len(flat), g.ctypes.data,
+                                             fmt, out.ctypes.data if len(s) else None, len(s))
+    if got < 0:
+        raise RuntimeError(_native.last_error())
+    assert got == len(s), (got, len(s))
+    return (out, g[:len(flat)]) if gains else out
+
+
 def check_option_value(name, value):
     """speechPlayer_batch_setOption takes a C int: a value outside its range would wrap without a word (2 ** 40 arrives as 0).  Returns
     int(value), or raises ValueError."""
@@ -1145,6 +1292,64 @@ class BatchPlayer(object):
             return self._dll.speechPlayer_batch_exportConvolved(self._h, _ptr(sel), n, h.ctypes.data, start.ctypes.data, len(start) - 1, _ptr(of),
                                                                 tail, out, fmt, stride, stream)
         return self._export_rows(lens, (), torch.float32 if fmt else torch.int16, padded, call)
+
+    def setNoiseBank(self, clips):
+        """The batch's noise bank (speechPlayer_batch_setNoiseBank): a list of one-dimensional float arrays (kept as float32), every value
+        finite and at most 2^16 in magnitude; None or an empty list frees it.  The bank stays on the device across set calls and
+        synthesis launches until it is replaced; replacing it waits for the exports that still read the old one."""
+        if clips is None:
+            clips = []
+        if isinstance(clips, np.ndarray) and clips.ndim == 1 and clips.dtype != object:
+            clips = [clips]
+        if not isinstance(clips, (list, tuple)):
+            raise TypeError("setNoiseBank: clips must be a list of one-dimensional float arrays, not %s" % type(clips).__name__)
+        held = [_mix_clip(c, "setNoiseBank", "clip %d" % k) for k, c in enumerate(clips)]
+        start = np.concatenate([[0], np.cumsum([len(c) for c in held])]).astype(np.int64)
+        flat = np.ascontiguousarray(np.concatenate(held)) if held else np.zeros(1, np.float32)
+        self._check(self._dll.speechPlayer_batch_setNoiseBank(self._h, flat.ctypes.data if held else None, start.ctypes.data if held else None, len(held)))
+
+    def noiseBankPowers(self):
+        """The whole-clip mean squares P_c of the noise bank's clips (speechPlayer_batch_noiseBank): a float64 array, empty without a bank."""
+        n = self._check(self._dll.speechPlayer_batch_noiseBank(self._h, None, None, 0))
+        power = np.zeros(max(n, 1), np.float64)
+        self._check(self._dll.speechPlayer_batch_noiseBank(self._h, power.ctypes.data, None, n))
+        return power[:n]
+
+    def powerTensor(self, utterances=None):
+        """The exact sums of squares S_u = sum s(n)^2 of the chosen utterances' int16 PCM (speechPlayer_batch_exportPower), filled on torch's
+        current stream behind the synthesis without a host wait: -> (sums, lengths), int64 tensors [n] on the batch's device.  The mean
+        square on the sample / 32767 scale is sums / lengths / 32767^2: the number every SNR starts from."""
+        import torch
+        sel, n, idx = self._selection("powerTensor", utterances)
+        dev = self.device
+        sums = torch.zeros(n, dtype=torch.int64, device="cuda:%d" % dev)
+        if n:
+            got = self._check(self._dll.speechPlayer_batch_exportPower(self._h, _ptr(sel), n, sums.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            assert got == n, (got, n)
+        return sums, torch.from_numpy(self._lengths()[idx].astype(np.int64)).to("cuda:%d" % dev)
+
+    def mixedTensor(self, terms, speechGain=None, utterances=None, dtype=None, padded=True, gains=False):
+        """The batch's PCM mixed with noise clips and other utterances as a torch tensor on the batch's device
+        (speechPlayer_batch_exportMixed), filled on torch's current stream behind the synthesis without a host wait: -> (mixed, lengths).
+        terms: one list of MixTerm per ROW (an empty list: the speech alone) -- with repeats in `utterances`, one utterance gets several
+        mixtures in one call -- or, for large batches, a pair (array of mixTermDtype, termStart).  MixTerm(noise=k) names clip k of the
+        bank (setNoiseBank), MixTerm(utterance=u) an utterance of the batch; snr= is in dB against the row's whole-utterance mean square,
+        gain= linear.  speechGain: None (1), one number or one per row.  A row keeps its length; utterances, padded and the
+        (mixed, lengths) pair as pcmTensor's; dtype torch.float32 (default) or torch.int16 (clipped, rounded to nearest even).
+        gains=True: -> (mixed, lengths, the float32 gains applied: a device tensor, one per term, termStart: an int64 CPU tensor).  The
+        batch must have been synthesised since it was set; pcmMix is the same definition on the host, which the device equals bit for bit."""
+        import torch
+        sel, n, idx = self._selection("mixedTensor", utterances)
+        flat, start, sg, fmt = check_mix_request(terms, n, speechGain, dtype)
+        dev = self.device
+        applied = torch.zeros(len(flat), dtype=torch.float32, device="cuda:%d" % dev) if gains else None
+
+        def call(out, stride, numel, stream):
+            return self._dll.speechPlayer_batch_exportMixed(self._h, _ptr(sel), n, flat.ctypes.data if len(flat) else None, start.ctypes.data, _ptr(sg),
+                                                            applied.data_ptr() if gains and len(flat) else None, out, fmt, stride, stream)
+        # (always: the library refuses a bad term even where the chosen rows have no samples to write)
+        out, second = self._export_rows(self._lengths()[idx].astype(np.int64), (), torch.float32 if fmt else torch.int16, padded, call, always=True)
+        return (out, second, applied, torch.from_numpy(start)) if gains else (out, second)
 
     def stemTensor(self, columns, utterances=None, dtype=None, padded=True):
         """The signal stems as a torch tensor on the batch's device (speechPlayer_batch_exportStems), filled on torch's current stream
