@@ -25,10 +25,9 @@
 //                   16-byte LDS read of the taps at the same address in every lane (a broadcast), one 16-byte read of four new inputs at
 //                   a lane stride of 16 bytes (conflict-free: the 16 lanes of a ds_read_b128 group cover 64 distinct banks), a sliding
 //                   window of seven inputs in registers, and sixteen conv_step (conv_step4), which the compiler pairs into eight
-//                   v_pk_fma_f32.  A block whose inputs lie wholly outside 0 .. L-1 is skipped (the lemma).  The values leave through
-//                   LDS by the resampler's stores: a lane owns an aligned 16 bytes of the output by ADDRESS, the edges go element by
-//                   element, a padded row's remainder is +0 by the same path.  LDS: 4 KB of taps + 8 KB of inputs (reused for the
-//                   staged values) = 12 KB.
+//                   v_pk_fma_f32.  A block whose inputs lie wholly outside 0 .. L-1 is skipped (the lemma).  The tiles are walked and
+//                   the values written as klatt_tiles.h says, a padded row's remainder as +0.  LDS: 4 KB of taps + 8 KB of inputs
+//                   (reused for the staged values) = 12 KB.
 #pragma once
 
 #include "klatt_resample.h"
@@ -62,6 +61,12 @@ KLATT_RES_HD void conv_step4(float (&acc)[4], const float (&v)[7], const float (
 #endif
         for (int j = 0; j < 4; ++j) acc[j] = conv_step(acc[j], v[t + 3 - j], h[t]);
     }
+}
+
+// A lane's four finished sums, outputs o0 .. o0 + 3 of the tile, staged in the output's type: +0 past the `live` outputs
+template <bool F32> KLATT_RES_HD void conv_stage4(TileValue<F32>* staged, const float (&acc)[4], int o0, int live)
+{
+    for (int q = 0; q < 4; ++q) staged[o0 + q] = o0 + q < live ? res_value<F32>(conv_finish(acc[q])) : (TileValue<F32>)0;
 }
 
 // ---- the kernel's index arithmetic ---------------------------------------------------------------------------------------------------------
@@ -137,8 +142,6 @@ inline long long conv_length(long long L, long long K, int tail) { return tail ?
 inline long long convolve_host(const int16_t* pcm, long long length, const float* h, long long K, int tail, int format, void* out)
 {
     const long long Lout = conv_length(length, K, tail);
-    float* of = static_cast<float*>(out);
-    int16_t* oi = static_cast<int16_t*>(out);
     // x[n] for n = -(K-1) .. length-1, +0 outside the signal: xp[n + K - 1]
     std::vector<float> xp((size_t)(length + K - 1) + (size_t)(tail ? K - 1 : 0), 0.0f);
     for (long long n = 0; n < length; ++n) xp[(size_t)(n + K - 1)] = res_input(pcm[n]);
@@ -146,8 +149,7 @@ inline long long convolve_host(const int16_t* pcm, long long length, const float
         const float* x = xp.data() + (m + K - 1);      // x[-k] is x[m - k]
         float acc = 0.0f;
         for (long long k = 0; k < K; ++k) acc = conv_step(acc, x[-k], h[k]);
-        const float y = conv_finish(acc);
-        if (format) of[m] = y; else oi[m] = res_int16(y);
+        res_store(out, format, m, conv_finish(acc));
     }
     return Lout;
 }
@@ -156,7 +158,6 @@ inline long long convolve_host(const int16_t* pcm, long long length, const float
 
 // ---- the device ---------------------------------------------------------------------------------------------------------------------
 #if defined(__HIPCC__)
-#include "klatt_timeline.h"
 
 namespace klatt {
 
@@ -166,34 +167,25 @@ struct ConvRow { long long src, len, outLen, dst, irAt, taps; };
 struct ConvArgs {
     const int16_t* pool;
     const ConvRow* rows;
-    const long long *start, *chunk;      // the packed form's row table over TILES (rowStride 0)
-    long long rowStride, tilesPerRow;    // the padded form: a row's width and its tiles
-    long long nTiles;
+    TileOut tile;
     const float* taps;                   // the responses back to back
-    void* out;
 };
 
 template <bool F32>
 __global__ void __launch_bounds__(256) klatt_convolve(const ConvArgs A)
 {
-    using T = typename std::conditional<F32, float, int16_t>::type;
-    constexpr int EL = 16 / (int)sizeof(T);
+    using T = TileValue<F32>;
     constexpr int TILE = kConvolveTile;
     __shared__ __attribute__((aligned(16))) float hs[kConvolveBlock];
     __shared__ __attribute__((aligned(16))) float xr[kConvolveTile + kConvolveBlock];
     T* staged = reinterpret_cast<T*>(xr);      // (behind a barrier: the last block's reads are done)
     const int tid = threadIdx.x;
-    T* __restrict__ out = static_cast<T*>(A.out);
-    const int mis = (int)((reinterpret_cast<uintptr_t>(A.out) / sizeof(T)) & (EL - 1));      // elements past a 16-byte boundary at out[0]
-    for (long long g = blockIdx.x; g < A.nTiles; g += gridDim.x) {
-        long long r, j;
-        if (A.rowStride > 0) { r = g / A.tilesPerRow; j = g - r * A.tilesPerRow; }
-        else { const long long c = g >> kTimelineChunkLog2; packed_locate(g, A.start, A.chunk[c], A.chunk[c + 1] + 1, r, j); }
+    for (long long g = blockIdx.x; g < A.tile.nTiles; g += gridDim.x) {
+        long long r, t0;
+        tile_locate(A.tile, g, TILE, r, t0);
         const ConvRow row = A.rows[r];
-        const long long width = A.rowStride > 0 ? A.rowStride : row.outLen;
-        const long long t0 = j * TILE;
-        const int n = (int)min((long long)TILE, width - t0);
-        const int live = (int)max(0ll, min((long long)n, row.outLen - t0));      // outputs of the tile inside the row; the rest is padding
+        const int n = tile_n(A.tile.rowStride, row.outLen, t0, TILE);
+        const int live = tile_live(n, row.outLen, t0);      // outputs of the tile inside the row; the rest is padding
         const int16_t* __restrict__ pcm = A.pool + row.src;
         const float* __restrict__ h = A.taps + row.irAt;
         const int K = (int)row.taps;
@@ -224,32 +216,9 @@ __global__ void __launch_bounds__(256) klatt_convolve(const ConvArgs A)
             }
         }
         __syncthreads();
-        // ---- the values, in the output's type ----
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int o = 4 * tid + q;
-            T v = (T)0;
-            if (o < live) { const float y = conv_finish(acc[q]); if (F32) v = (T)y; else v = (T)res_int16(y); }
-            staged[o] = v;
-        }
+        conv_stage4<F32>(staged, acc, 4 * tid, live);
         __syncthreads();
-        // ---- the stores: a lane owns an aligned 16 bytes of the output ----
-        const long long e0 = row.dst + t0;
-        const long long first = e0 - ((e0 + mis) & (EL - 1));
-        const int lanes = (int)((e0 + n - first + EL - 1) / EL);
-        for (int i = tid; i < lanes; i += 256) {
-            const long long at = first + (long long)i * EL;
-            const int b0 = (int)(at - e0);                          // (negative in the first lane of a tile that starts inside its 16 bytes)
-            if (b0 >= 0 && b0 + EL <= n) {
-                struct alignas(16) Lane { T x[EL]; } l;
-#pragma unroll
-                for (int q = 0; q < EL; ++q) l.x[q] = staged[b0 + q];
-                *reinterpret_cast<Lane*>(out + at) = l;
-            } else {
-#pragma unroll
-                for (int q = 0; q < EL; ++q) if (b0 + q >= 0 && b0 + q < n) out[at + q] = staged[b0 + q];
-            }
-        }
+        tile_store<T>(A.tile.out, row.dst + t0, n, staged, tid);
         __syncthreads();      // `staged` is the next tile's xr
     }
 }

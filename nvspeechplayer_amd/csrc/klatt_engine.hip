@@ -850,7 +850,9 @@ struct ExportStage {
 };
 // (the staging block's sections start on 16-byte boundaries: no kernel takes two of them for one array)
 static_assert(sizeof(TimelineRow) % 8 == 0 && sizeof(AlignRow) % 8 == 0 && sizeof(EpochRow) % 8 == 0 && sizeof(SourceList) % 8 == 0 &&
-              sizeof(TimelineList) % 8 == 0 && sizeof(StemRow) % 8 == 0 && sizeof(ResponseGroup) % 8 == 0, "rows are arrays of 8-byte words");
+              sizeof(TimelineList) % 8 == 0 && sizeof(StemRow) % 8 == 0 && sizeof(ResponseGroup) % 8 == 0 && sizeof(SpecRow) % 8 == 0 &&
+              sizeof(ResRow) % 8 == 0 && sizeof(ConvRow) % 8 == 0 && sizeof(MixRow) % 8 == 0 && sizeof(MixTermDev) % 8 == 0 &&
+              sizeof(MixGainJob) % 8 == 0 && sizeof(PowerJob) % 8 == 0, "rows are arrays of 8-byte words");
 
 // How many of the quiet, nasal-free utterances (the head of `order`) the lane-pipelined kernel takes.
 // layout 2 forces it; "auto" takes it where it measured faster than the stage-parallel kernel.
@@ -4519,6 +4521,13 @@ static int export_output(Batch* b, const char* what, void* deviceOut, long long 
     return device_range(deviceOut, (size_t)elements * elSize, b->device, elSize, what) ? 0 : -1;
 }
 
+// An export of the batch's PCM needs a synthesis launch since the set call
+static int export_synthesised(const Batch* b, const char* what)
+{
+    if (!b->launched) set_error("%s: the batch has not been synthesised since it was set", what);
+    return b->launched ? 0 : -1;
+}
+
 // The arguments of the exports by step: hop and phase, and no utterance is longer than 2^32 samples: a larger hop or phase means the same.
 static int step_request(const char* what, long long& hop, long long& phase, long long rowStride)
 {
@@ -5146,7 +5155,7 @@ long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const
         static constexpr ExportNouns kBandNouns{"largest step count", "steps", "bands"};
         const long long elements = export_elements(what, kBandNouns, s, rowStride, P.nOut);
         if (elements <= 0) return elements;
-        if (!b->launched) { set_error("exportSpectrogram: the batch has not been synthesised since it was set"); return -1; }
+        if (export_synthesised(b, what)) return -1;
         const size_t elSize = format ? sizeof(float) : sizeof(double);
         if (export_output(b, what, deviceOut, elements, elSize)) return -1;
         hipStream_t st = static_cast<hipStream_t>(stream);
@@ -5180,6 +5189,40 @@ long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const
     });
 }
 
+// ---- the tile-wise exports of the PCM (klatt_tiles.h): resampled, convolved, mixed ---------------------------------------------------------
+// A workgroup takes tiles of one row: the packed form's row table counts TILES (klatt_export.h: tile_row_table), the rows carry their
+// first element in the output.  An entry point is, in the order of its refusals: tile_request, its own plan, export_selection with
+// tile_row_first, tile_elements, ExportStage with the words of tile_row_table, its own launches, tile_out and launch_tiles (which finishes).
+constexpr ExportNouns kSampleNouns{"longest output row", "samples", nullptr};
+static int tile_request(const char* what, int format, long long rowStride)
+{
+    if (format != 0 && format != 1) { set_error("%s: format %d (0 int16, 1 float32)", what, format); return -1; }
+    if (rowStride < 0) { set_error("%s: rowStride %lld", what, rowStride); return -1; }
+    return 0;
+}
+// Row i's first element in the output: i rows of rowStride (padded: export_elements refuses an extent that wraps) or the outputs before it
+static long long tile_row_first(long long i, long long rowStride, long long before) { return rowStride > 0 ? (long long)((unsigned long long)i * (unsigned long long)rowStride) : before; }
+// The elements of the export (0: nothing to do), or -1 with the message set: the extent, a batch not synthesised, the output, in this order
+static long long tile_elements(Batch* b, const char* what, const ExportSelection& s, long long rowStride, int format, void* deviceOut)
+{
+    const long long elements = export_elements(what, kSampleNouns, s, rowStride, 1);
+    if (elements > 0 && (export_synthesised(b, what) || export_output(b, what, deviceOut, elements, format ? sizeof(float) : sizeof(int16_t)))) return -1;
+    return elements;
+}
+static TileOut tile_out(const ExportStage& stage, int wordsAt, const TileTable& t, long long rowStride, void* deviceOut)
+{
+    const long long* words = rowStride == 0 ? stage.device<long long>(wordsAt) : nullptr;      // (the padded form has no row table)
+    return TileOut{words ? words + t.table.startOff : nullptr, words ? words + t.table.chunkOff : nullptr, rowStride, t.tilesPerRow, t.nTiles, deviceOut};
+}
+// The kernel of the format over the tiles, at most perCu workgroups per CU: the stage's last launch
+extern "C++" template <class Args>
+static int launch_tiles(ExportStage& stage, void (*int16)(Args), void (*float32)(Args), int format, long long perCu, const Args& A)
+{
+    const unsigned grid = (unsigned)std::min<long long>(A.tile.nTiles, perCu * stage.b->cus);
+    hipLaunchKernelGGL(format ? float32 : int16, dim3(grid), dim3(256), 0, stage.st, A);
+    HIP_TRY(hipGetLastError());
+    return stage.finish();
+}
 
 // ---- the PCM at another sample rate (klatt_resample.h) -----------------------------------------------------------------------------------
 // Host only, touch no device: the definition of include/speechPlayer_batch.h through the functions the kernel is compiled from.
@@ -5228,8 +5271,7 @@ long long speechPlayer_pcmResample(const sample* pcm, long long length, int srcR
 }
 
 // The chosen utterances' PCM at `outRate` (klatt_resample.h).  It reads the pool, so it is ordered as speechPlayer_batch_exportPcm is
-// (ExportStage, ofPcm).  A workgroup takes tiles of one row: the packed form's row table counts TILES, the rows carry their first
-// element in the output.  The staging block: rows | tile starts and chunk rows (packed) | the table, when the batch does not hold it.
+// (ExportStage, ofPcm), tile-wise.  The staging block: rows | tile starts and chunk rows (packed) | the table, when the batch does not hold it.
 // The table stays on the batch until the parameters change; the exports that read it follow one order (resampleOrder).
 long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int outRate, int zeros,
                                              double rolloff, int window, double beta, void* deviceOut, int format, long long rowStride, void* stream)
@@ -5237,8 +5279,7 @@ long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const l
     const char* what = "exportResampled";
     if (refuse_timing_only("speechPlayer_batch_exportResampled")) return -1;
     const long long done = batch_entry(what, batch, [&](Batch* b) -> long long {
-        if (format != 0 && format != 1) { set_error("exportResampled: format %d (0 int16, 1 float32)", format); return -1; }
-        if (rowStride < 0) { set_error("exportResampled: rowStride %lld", rowStride); return -1; }
+        if (tile_request(what, format, rowStride)) return -1;
         if (!b->resPlan.same(b->sampleRate, outRate, zeros, rolloff, window, beta)) {
             ResPlan P;
             std::string why;
@@ -5250,24 +5291,17 @@ long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const l
         if (P.identity) return -2;      // equal rates: speechPlayer_batch_exportPcm's output exactly
         ExportSelection s;
         std::vector<ResRow> rows;
-        std::vector<long long> tiles;
         if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) {
                 const long long L = (long long)b->lens[(size_t)u], Lout = res_length(L, P.up, P.down);
-                rows.push_back(ResRow{b->outStart[(size_t)u], L, Lout, rowStride > 0 ? (long long)((unsigned long long)i * (unsigned long long)rowStride) : before});      // (export_elements refuses an extent that wraps)
-                tiles.push_back((Lout + kResampleTile - 1) / kResampleTile);
+                rows.push_back(ResRow{b->outStart[(size_t)u], L, Lout, tile_row_first(i, rowStride, before)});
                 return Lout;
             })) return -1;
-        static constexpr ExportNouns kSampleNouns{"longest output row", "samples", nullptr};
-        const long long elements = export_elements(what, kSampleNouns, s, rowStride, 1);
+        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut);
         if (elements <= 0) return elements;
-        if (!b->launched) { set_error("exportResampled: the batch has not been synthesised since it was set"); return -1; }
-        const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
-        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
         hipStream_t st = static_cast<hipStream_t>(stream);
 
-        const bool packed = rowStride == 0;
         std::vector<long long> words;
-        const RowTable table = packed ? packed_row_table(tiles.data(), 0, s.n, kTimelineChunkLog2, words) : RowTable{0, 0};
+        const TileTable tiles = tile_row_table(s.counts.data(), s.n, kResampleTile, rowStride, kTimelineChunkLog2, words);
         const bool upload = !b->resOnDevice;
         if (upload) res_transpose(P);
         StageBlock block;
@@ -5282,17 +5316,9 @@ long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const l
         if (upload) HIP_TRY(hipMemcpyAsync(b->dResample.ptr, stage.device<float>(tableAt), tableSize * sizeof(float), hipMemcpyDeviceToDevice, st));
         ResArgs A;
         A.pool = b->dPcm.ptr; A.rows = stage.device<ResRow>(rowsAt);
-        A.start = packed ? stage.device<long long>(wordsAt) + table.startOff : nullptr;
-        A.chunk = packed ? stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
-        A.rowStride = rowStride; A.tilesPerRow = (rowStride + kResampleTile - 1) / kResampleTile;
-        A.nTiles = packed ? words[(size_t)(table.startOff + s.n)] : s.n * A.tilesPerRow;
+        A.tile = tile_out(stage, wordsAt, tiles, rowStride, deviceOut);
         A.hT = b->dResample.ptr; A.up = P.up; A.down = P.down; A.Z = P.Z; A.span = res_span(P);
-        A.out = deviceOut;
-        const unsigned grid = (unsigned)std::min<long long>(A.nTiles, 8ll * b->cus);
-        if (format) hipLaunchKernelGGL(klatt_resample<true>, dim3(grid), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL(klatt_resample<false>, dim3(grid), dim3(256), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        if (stage.finish()) return -1;
+        if (launch_tiles(stage, klatt_resample<false>, klatt_resample<true>, format, 8, A)) return -1;
         b->resOnDevice = true;
         return elements;
     });
@@ -5321,9 +5347,8 @@ long long speechPlayer_pcmConvolve(const sample* pcm, long long length, const fl
 }
 
 // The chosen utterances' PCM, each row through the response irOf names (klatt_convolve.h).  It reads the pool, so it is ordered as
-// speechPlayer_batch_exportPcm is (ExportStage, ofPcm).  A workgroup takes tiles of one row: the packed form's row table counts TILES, the
-// rows carry their first element in the output and their response.  The staging block: rows | tile starts and chunk rows (packed) |
-// the responses.  Nothing is kept on the batch: the kernel reads the responses from the call's own slot.
+// speechPlayer_batch_exportPcm is (ExportStage, ofPcm), tile-wise; the rows carry their response as well.  The staging block: rows | tile
+// starts and chunk rows (packed) | the responses.  Nothing is kept on the batch: the kernel reads the responses from the call's own slot.
 long long speechPlayer_batch_exportConvolved(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const float* ir,
                                              const long long* irStart, long long nIr, const long long* irOf, int tail, void* deviceOut, int format,
                                              long long rowStride, void* stream)
@@ -5331,53 +5356,34 @@ long long speechPlayer_batch_exportConvolved(speechPlayer_batch_t batch, const l
     const char* what = "exportConvolved";
     if (refuse_timing_only("speechPlayer_batch_exportConvolved")) return -1;
     return batch_entry(what, batch, [&](Batch* b) -> long long {
-        if (format != 0 && format != 1) { set_error("exportConvolved: format %d (0 int16, 1 float32)", format); return -1; }
-        if (rowStride < 0) { set_error("exportConvolved: rowStride %lld", rowStride); return -1; }
+        if (tile_request(what, format, rowStride)) return -1;
         ConvPlan P;
         std::string why;
         if (!conv_plan(P, ir, irStart, nIr, tail, why)) { set_error("exportConvolved: %s", why.c_str()); return -1; }
         ExportSelection s;
         std::vector<ConvRow> rows;
-        std::vector<long long> tiles;
         if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) -> long long {
                 const long long j = conv_row(P, irOf, i, why);
                 if (j < 0) { set_error("exportConvolved: %s", why.c_str()); return -1; }
                 const long long L = (long long)b->lens[(size_t)u], K = P.start[(size_t)j + 1] - P.start[(size_t)j], Lout = conv_length(L, K, tail);
-                rows.push_back(ConvRow{b->outStart[(size_t)u], L, Lout, rowStride > 0 ? (long long)((unsigned long long)i * (unsigned long long)rowStride) : before,
-                                       P.start[(size_t)j], K});      // (export_elements refuses an extent that wraps)
-                tiles.push_back((Lout + kConvolveTile - 1) / kConvolveTile);
+                rows.push_back(ConvRow{b->outStart[(size_t)u], L, Lout, tile_row_first(i, rowStride, before), P.start[(size_t)j], K});
                 return Lout;
             })) return -1;
-        static constexpr ExportNouns kSampleNouns{"longest output row", "samples", nullptr};
-        const long long elements = export_elements(what, kSampleNouns, s, rowStride, 1);
+        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut);
         if (elements <= 0) return elements;
-        if (!b->launched) { set_error("exportConvolved: the batch has not been synthesised since it was set"); return -1; }
-        const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
-        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
-        hipStream_t st = static_cast<hipStream_t>(stream);
-
-        const bool packed = rowStride == 0;
         std::vector<long long> words;
-        const RowTable table = packed ? packed_row_table(tiles.data(), 0, s.n, kTimelineChunkLog2, words) : RowTable{0, 0};
+        const TileTable tiles = tile_row_table(s.counts.data(), s.n, kConvolveTile, rowStride, kTimelineChunkLog2, words);
         StageBlock block;
         const int rowsAt = block.add(rows), wordsAt = block.add(words), tapsAt = block.add(P.taps);
-        ExportStage stage(b, st, block, nullptr, true);
+        ExportStage stage(b, static_cast<hipStream_t>(stream), block, nullptr, true);
         if (stage.begin()) return -1;
         ConvArgs A;
         A.pool = b->dPcm.ptr; A.rows = stage.device<ConvRow>(rowsAt);
-        A.start = packed ? stage.device<long long>(wordsAt) + table.startOff : nullptr;
-        A.chunk = packed ? stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
-        A.rowStride = rowStride; A.tilesPerRow = (rowStride + kConvolveTile - 1) / kConvolveTile;
-        A.nTiles = packed ? words[(size_t)(table.startOff + s.n)] : s.n * A.tilesPerRow;
+        A.tile = tile_out(stage, wordsAt, tiles, rowStride, deviceOut);
         A.taps = stage.device<float>(tapsAt);
-        A.out = deviceOut;
         // Tiles cost in proportion to their response's taps: many more workgroups than the device holds at once, so that the dispatcher
         // evens out what a fixed share per workgroup would not.
-        const unsigned grid = (unsigned)std::min<long long>(A.nTiles, 64ll * b->cus);
-        if (format) hipLaunchKernelGGL(klatt_convolve<true>, dim3(grid), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL(klatt_convolve<false>, dim3(grid), dim3(256), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        if (stage.finish()) return -1;
+        if (launch_tiles(stage, klatt_convolve<false>, klatt_convolve<true>, format, 64, A)) return -1;
         return elements;
     });
 }
@@ -5527,7 +5533,7 @@ long long speechPlayer_batch_exportPower(speechPlayer_batch_t batch, const long 
                 return 1;
             })) return -1;
         if (s.n == 0) return 0;
-        if (!b->launched) { set_error("exportPower: the batch has not been synthesised since it was set"); return -1; }
+        if (export_synthesised(b, what)) return -1;
         if (export_output(b, what, deviceOut, s.n, sizeof(unsigned long long))) return -1;
         hipStream_t st = static_cast<hipStream_t>(stream);
         const std::vector<unsigned long long> zeros(P.jobs.size(), 0ull);
@@ -5546,7 +5552,7 @@ long long speechPlayer_batch_exportPower(speechPlayer_batch_t batch, const long 
 }
 
 // The chosen utterances' PCM, row i mixed with its terms terms[termStart[i] .. termStart[i+1]) (klatt_mix.h).  It reads the pool, so it is
-// ordered as speechPlayer_batch_exportPcm is (ExportStage, ofPcm); a call that names a clip also takes its place in the bank's order.  The
+// ordered as speechPlayer_batch_exportPcm is (ExportStage, ofPcm), tile-wise; a call that names a clip also takes its place in the bank's order.  The
 // staging block: rows | tile starts and chunk rows (packed) | the terms as the kernel reads them | their level jobs | the power slots'
 // utterances, tiles and zeros | the gains (reserved: nothing is uploaded).  The slots and the gains are the call's device scratch: they
 // live in its staging slot.
@@ -5557,14 +5563,12 @@ long long speechPlayer_batch_exportMixed(speechPlayer_batch_t batch, const long 
     const char* what = "exportMixed";
     if (refuse_timing_only("speechPlayer_batch_exportMixed")) return -1;
     return batch_entry(what, batch, [&](Batch* b) -> long long {
-        if (format != 0 && format != 1) { set_error("exportMixed: format %d (0 int16, 1 float32)", format); return -1; }
-        if (rowStride < 0) { set_error("exportMixed: rowStride %lld", rowStride); return -1; }
+        if (tile_request(what, format, rowStride)) return -1;
         const MixTermIn* in = reinterpret_cast<const MixTermIn*>(terms);
         std::string why;
         ExportSelection s;
         PowerSlots P;
         std::vector<MixRow> rows;
-        std::vector<long long> tiles;
         std::vector<MixTermDev> dev;
         std::vector<MixGainJob> jobs;
         bool readsBank = false;
@@ -5594,24 +5598,17 @@ long long speechPlayer_batch_exportMixed(speechPlayer_batch_t batch, const long 
                     }
                     jobs.push_back(job);
                 }
-                rows.push_back(MixRow{b->outStart[(size_t)u], L, rowStride > 0 ? (long long)((unsigned long long)i * (unsigned long long)rowStride) : before,
-                                      a, (int)nT, sg});      // (export_elements refuses an extent that wraps)
-                tiles.push_back(mix_tiles(L));
+                rows.push_back(MixRow{b->outStart[(size_t)u], L, tile_row_first(i, rowStride, before), a, (int)nT, sg});
                 return L;
             })) return -1;
-        static constexpr ExportNouns kSampleNouns{"longest output row", "samples", nullptr};
-        const long long elements = export_elements(what, kSampleNouns, s, rowStride, 1);
+        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut);
         if (elements <= 0) return elements;
-        if (!b->launched) { set_error("exportMixed: the batch has not been synthesised since it was set"); return -1; }
-        const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
-        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
         const long long nTerms = (long long)dev.size();
         if (deviceGains && nTerms > 0 && !device_range(deviceGains, (size_t)nTerms * sizeof(float), b->device, sizeof(float), what)) return -1;
         hipStream_t st = static_cast<hipStream_t>(stream);
 
-        const bool packed = rowStride == 0;
         std::vector<long long> words;
-        const RowTable table = packed ? packed_row_table(tiles.data(), 0, s.n, kTimelineChunkLog2, words) : RowTable{0, 0};
+        const TileTable tiles = tile_row_table(s.counts.data(), s.n, kMixTile, rowStride, kTimelineChunkLog2, words);
         const std::vector<unsigned long long> zeros(P.jobs.size(), 0ull);
         StageBlock block;
         const int rowsAt = block.add(rows), wordsAt = block.add(words), termsAt = block.add(dev), jobsAt = block.add(jobs), slotJobsAt = block.add(P.jobs),
@@ -5629,17 +5626,9 @@ long long speechPlayer_batch_exportMixed(speechPlayer_batch_t batch, const long 
         }
         MixArgs A;
         A.pool = b->dPcm.ptr; A.bank = b->dBank.ptr; A.rows = stage.device<MixRow>(rowsAt);
-        A.start = packed ? stage.device<long long>(wordsAt) + table.startOff : nullptr;
-        A.chunk = packed ? stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
-        A.rowStride = rowStride; A.tilesPerRow = mix_tiles(rowStride);
-        A.nTiles = packed ? words[(size_t)(table.startOff + s.n)] : s.n * A.tilesPerRow;
+        A.tile = tile_out(stage, wordsAt, tiles, rowStride, deviceOut);
         A.terms = stage.device<MixTermDev>(termsAt); A.gains = dGains;
-        A.out = deviceOut;
-        const unsigned grid = (unsigned)std::min<long long>(A.nTiles, 8ll * b->cus);
-        if (format) hipLaunchKernelGGL(klatt_mix<true>, dim3(grid), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL(klatt_mix<false>, dim3(grid), dim3(256), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        if (stage.finish()) return -1;
+        if (launch_tiles(stage, klatt_mix<false>, klatt_mix<true>, format, 8, A)) return -1;
         return elements;
     });
 }

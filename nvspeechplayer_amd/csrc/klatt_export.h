@@ -4,6 +4,7 @@
 //
 //   export_extent      the extent refusals every export makes, and its element count
 //   packed_row_table   the packed form's row table: step starts, chunk rows, the closing entry
+//   tile_row_table     the same over the TILES of rows of outputs (klatt_tiles.h), with the padded form's tiles per row
 //   list_pieces        runs of rows whose distinct lists fit a table
 //   StageBlock         the sections of a staging block, each on a 16-byte boundary
 #pragma once
@@ -16,6 +17,8 @@
 #include <algorithm>
 #include <string>
 #include <vector>
+
+#include "klatt_tiles.h"
 
 namespace klatt {
 
@@ -71,6 +74,19 @@ inline RowTable packed_row_table(const long long* counts, long long r0, long lon
     }
     words.push_back(std::max<long long>(nr - 1, 0));
     return t;
+}
+
+// The tiles of an export whose n rows have outLen[i] outputs each, in tiles of `tile` (klatt_tiles.h).  Packed (rowStride 0): the row
+// table over the rows' tiles is appended to `words`.  Padded: every row has the tiles of rowStride elements, nothing is appended.
+struct TileTable { RowTable table; long long tilesPerRow, nTiles; };
+inline TileTable tile_row_table(const long long* outLen, long long n, int tile, long long rowStride, int chunkLog2, std::vector<long long>& words)
+{
+    const long long perRow = tile_count(rowStride, tile);
+    if (rowStride > 0) return TileTable{{0, 0}, perRow, n * perRow};
+    std::vector<long long> tiles((size_t)n);
+    for (long long i = 0; i < n; ++i) tiles[(size_t)i] = tile_count(outLen[i], tile);
+    const RowTable table = packed_row_table(tiles.data(), 0, n, chunkLog2, words);
+    return TileTable{table, perRow, words[(size_t)(table.startOff + n)]};
 }
 
 // Rows [r0, r1) whose nLists distinct lists hold slots 0 .. nLists - 1 of a table; `table` is the caller's to fill.

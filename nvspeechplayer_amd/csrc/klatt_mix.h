@@ -33,18 +33,17 @@
 //                   a row's place in termStart; messages without the entry point's prefix).
 //   The statement   mix_host: the definition in a plain loop over the shared functions.
 //   The indices     What the kernel visits, as plain functions a stand-alone program checks against brute force (tests/native/check_mix.cpp):
-//                   mix_tiles, mix_tile_row, mix_term_first, mix_term_last, mix_term_skipped, mix_loop_start, mix_loop_index, mix_lane_start,
-//                   mix_lane_whole, mix_speech_whole.
+//                   mix_term_first, mix_term_last, mix_term_skipped, mix_loop_start, mix_loop_index, mix_lane_start, mix_lane_whole,
+//                   mix_speech_whole; the tiles themselves are klatt_tiles.h's.
 //   klatt_power     S_u of the distinct utterances a call needs into zeroed uint64 slots: a workgroup takes kPowerTile samples of one
 //                   utterance, lanes take 16-byte loads of eight samples where the address allows, accumulate in 64 bits (a square is up
 //                   to 2^30: two of them do not fit a signed 32-bit sum), the wavefront reduces, one 64-bit atomic add per wavefront.
 //   klatt_mix_gains one lane per term: mix_gain from the slots and the bank's powers, into the call's scratch and the caller's deviceGains.
-//   klatt_mix       A 256-lane workgroup takes tiles of kMixTile consecutive outputs of one row (the row table counts tiles, as for the
-//                   resampler and the convolution); lane l owns the FOUR outputs 4 l .. 4 l + 3.  The row's term descriptors are
-//                   wave-uniform.  Per term and tile the start index (offset + t0) mod N is computed once; the lanes wrap by comparison
-//                   when N >= kMixTile and by a 32-bit remainder below that.  A term wholly outside the tile is skipped.  Stores go out
-//                   by the convolution's path: staged in LDS in the output's type, a lane owns an aligned 16 bytes of the output by
-//                   ADDRESS, the edges go element by element, a padded row's remainder is +0 by the same path.
+//   klatt_mix       A 256-lane workgroup takes tiles of kMixTile consecutive outputs of one row (klatt_tiles.h: the walk); lane l owns
+//                   the FOUR outputs 4 l .. 4 l + 3.  The row's term descriptors are wave-uniform.  Per term and tile the start index
+//                   (offset + t0) mod N is computed once; the lanes wrap by comparison when N >= kMixTile and by a 32-bit remainder
+//                   below that.  A term wholly outside the tile is skipped.  The values go out as klatt_tiles.h says (the writer):
+//                   staged in LDS in the output's type, a padded row's remainder as +0.
 #pragma once
 
 #include "klatt_convolve.h"
@@ -90,9 +89,6 @@ KLATT_RES_HD long long mix_source_index(long long m, long long offset, long long
 }
 
 // ---- the kernel's index arithmetic ---------------------------------------------------------------------------------------------------------
-KLATT_RES_HD long long mix_tiles(long long width) { return (width + kMixTile - 1) / kMixTile; }
-// Tile g of the padded form: row r, tile j of the row
-KLATT_RES_HD void mix_tile_row(long long g, long long tilesPerRow, long long& r, long long& j) { r = g / tilesPerRow; j = g - r * tilesPerRow; }
 // A term that does not loop covers the outputs [first, last) of the tile at t0 with `live` outputs inside the row, in the tile's own
 // numbering (first >= last: none); output o reads element t0 - offset + o
 KLATT_RES_HD int mix_term_first(long long t0, long long offset) { return offset > t0 ? (int)(offset - t0 < kMixTile ? offset - t0 : kMixTile) : 0; }
@@ -255,8 +251,6 @@ KLATT_RES_HD float mix_source_value(const void* data, int isFloat, long long i)
 inline long long mix_host(const int16_t* pcm, long long length, float speechGain, const MixSource* sources, const MixTermHost* terms, long long nTerms,
                           int format, void* out)
 {
-    float* of = static_cast<float*>(out);
-    int16_t* oi = static_cast<int16_t*>(out);
     for (long long m = 0; m < length; ++m) {
         float acc = speechGain * res_input((int)pcm[m]);
         for (long long j = 0; j < nTerms; ++j) {
@@ -264,8 +258,7 @@ inline long long mix_host(const int16_t* pcm, long long length, float speechGain
             const long long i = mix_source_index(m, terms[j].offset, s.length, terms[j].loop);
             acc = conv_step(acc, i >= 0 ? mix_source_value(s.data, s.isFloat, i) : 0.0f, terms[j].gain);
         }
-        const float y = conv_finish(acc);
-        if (format) of[m] = y; else oi[m] = res_int16(y);
+        res_store(out, format, m, conv_finish(acc));
     }
     return length;
 }
@@ -368,35 +361,26 @@ struct MixArgs {
     const int16_t* pool;
     const float* bank;
     const MixRow* rows;
-    const long long *start, *chunk;      // the packed form's row table over TILES (rowStride 0)
-    long long rowStride, tilesPerRow;    // the padded form: a row's width and its tiles
-    long long nTiles;
+    TileOut tile;
     const MixTermDev* terms;
     const float* gains;
-    void* out;
 };
 
 template <bool F32>
 __global__ void __launch_bounds__(256) klatt_mix(const MixArgs A)
 {
-    using T = typename std::conditional<F32, float, int16_t>::type;
-    constexpr int EL = 16 / (int)sizeof(T);
+    using T = TileValue<F32>;
     constexpr int TILE = kMixTile;
     __shared__ __attribute__((aligned(16))) T staged[TILE];
     struct __attribute__((packed, aligned(4))) F4 { float x[4]; };      // four floats at any float's address
     struct __attribute__((packed, aligned(2))) S4 { int16_t x[4]; };    // four samples at any sample's address
     const int tid = threadIdx.x;
-    T* __restrict__ out = static_cast<T*>(A.out);
-    const int mis = (int)((reinterpret_cast<uintptr_t>(A.out) / sizeof(T)) & (EL - 1));      // elements past a 16-byte boundary at out[0]
-    for (long long g = blockIdx.x; g < A.nTiles; g += gridDim.x) {
-        long long r, j;
-        if (A.rowStride > 0) mix_tile_row(g, A.tilesPerRow, r, j);
-        else { const long long c = g >> kTimelineChunkLog2; packed_locate(g, A.start, A.chunk[c], A.chunk[c + 1] + 1, r, j); }
+    for (long long g = blockIdx.x; g < A.tile.nTiles; g += gridDim.x) {
+        long long r, t0;
+        tile_locate(A.tile, g, TILE, r, t0);
         const MixRow row = A.rows[r];
-        const long long width = A.rowStride > 0 ? A.rowStride : row.len;
-        const long long t0 = j * TILE;
-        const int n = (int)min((long long)TILE, width - t0);
-        const int live = (int)max(0ll, min((long long)n, row.len - t0));      // outputs of the tile inside the row; the rest is padding
+        const int n = tile_n(A.tile.rowStride, row.len, t0, TILE);
+        const int live = tile_live(n, row.len, t0);      // outputs of the tile inside the row; the rest is padding
         const int o0 = 4 * tid;
         float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (live > 0) {
@@ -444,32 +428,9 @@ __global__ void __launch_bounds__(256) klatt_mix(const MixArgs A)
                 for (int q = 0; q < 4; ++q) acc[q] = conv_step(acc[q], v[q], gain);
             }
         }
-        // ---- the values, in the output's type ----
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int o = o0 + q;
-            T v = (T)0;
-            if (o < live) { const float y = conv_finish(acc[q]); if (F32) v = (T)y; else v = (T)res_int16(y); }
-            staged[o] = v;
-        }
+        conv_stage4<F32>(staged, acc, o0, live);
         __syncthreads();
-        // ---- the stores: a lane owns an aligned 16 bytes of the output ----
-        const long long e0 = row.dst + t0;
-        const long long first = e0 - ((e0 + mis) & (EL - 1));
-        const int lanes = (int)((e0 + n - first + EL - 1) / EL);
-        for (int i = tid; i < lanes; i += 256) {
-            const long long at = first + (long long)i * EL;
-            const int b0 = (int)(at - e0);                          // (negative in the first lane of a tile that starts inside its 16 bytes)
-            if (b0 >= 0 && b0 + EL <= n) {
-                struct alignas(16) Lane { T x[EL]; } l;
-#pragma unroll
-                for (int q = 0; q < EL; ++q) l.x[q] = staged[b0 + q];
-                *reinterpret_cast<Lane*>(out + at) = l;
-            } else {
-#pragma unroll
-                for (int q = 0; q < EL; ++q) if (b0 + q >= 0 && b0 + q < n) out[at + q] = staged[b0 + q];
-            }
-        }
+        tile_store<T>(A.tile.out, row.dst + t0, n, staged, tid);
         __syncthreads();      // `staged` is the next tile's
     }
 }

@@ -18,10 +18,9 @@
 //                   res_input into LDS; lane i takes outputs i, i + 256, ... of the span, so consecutive lanes read LDS at stride
 //                   down / up (conflict-free below 2, two-way at 2) and the table at consecutive addresses: it is uploaded reordered
 //                   by use and transposed, hT[k][m mod up] = h[(m down) mod up][k] (phase has period `up` in m), 230 KB in the
-//                   largest tested case and L2-resident.  The reordering moves data, not arithmetic.  The values are staged in LDS in
-//                   the output's type and leave by lanes that own an aligned 16 bytes of the output (aligned by ADDRESS: a buffer
-//                   aligned to the element only still gets 16-byte stores inside a span); a span's edges, which share their 16 bytes
-//                   with the neighbouring span or row, go element by element.  A padded row's tail is stored as +0 by the same path.
+//                   largest tested case and L2-resident.  The reordering moves data, not arithmetic.  The tiles are walked and the
+//                   values written as klatt_tiles.h says, a span being a run of the writer: staged in LDS in the output's type, a
+//                   padded row's tail as +0.
 #pragma once
 
 #include <math.h>
@@ -31,11 +30,7 @@
 #include <string>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define KLATT_RES_HD __host__ __device__ __forceinline__
-#else
-#define KLATT_RES_HD inline
-#endif
+#include "klatt_tiles.h"
 
 namespace klatt {
 
@@ -75,6 +70,11 @@ KLATT_RES_HD int16_t res_int16(float y)
     if (q <= -32768.0f) return (int16_t)-32768;
     return (int16_t)rintf(q);
 }
+
+// A finished sum in the output's type
+template <bool F32> KLATT_RES_HD TileValue<F32> res_value(float y) { if (F32) return (TileValue<F32>)y; return (TileValue<F32>)res_int16(y); }
+// The same into output m of a host statement: format 1 float[], format 0 int16_t[]
+inline void res_store(void* out, int format, long long m, float y) { if (format) static_cast<float*>(out)[m] = y; else static_cast<int16_t*>(out)[m] = res_int16(y); }
 
 // ---- the request, as every entry point plans it on the host -----------------------------------------------------------------------------
 inline long long res_gcd(long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; }
@@ -171,10 +171,8 @@ inline void res_transpose(ResPlan& P)
 inline long long resample_host(const int16_t* pcm, long long length, const ResPlan& P, int format, void* out)
 {
     const long long Lout = res_length(length, P.up, P.down);
-    float* of = static_cast<float*>(out);
-    int16_t* oi = static_cast<int16_t*>(out);
     if (P.identity) {
-        for (long long m = 0; m < Lout; ++m) { if (format) of[m] = res_input(pcm[m]); else oi[m] = pcm[m]; }
+        for (long long m = 0; m < Lout; ++m) { if (format) static_cast<float*>(out)[m] = res_input(pcm[m]); else static_cast<int16_t*>(out)[m] = pcm[m]; }
         return Lout;
     }
     std::vector<float> x((size_t)P.taps);
@@ -186,7 +184,7 @@ inline long long resample_host(const int16_t* pcm, long long length, const ResPl
             x[(size_t)k] = res_input(n >= 0 && n < length ? pcm[n] : 0);
         }
         const float y = res_taps(x.data(), P.table.data() + (size_t)p * P.taps, P.taps, 1);
-        if (format) of[m] = y; else oi[m] = res_int16(y);
+        res_store(out, format, m, y);
     }
     return Lout;
 }
@@ -202,8 +200,6 @@ inline int res_span(const ResPlan& P)
 
 // ---- the device ---------------------------------------------------------------------------------------------------------------------
 #if defined(__HIPCC__)
-#include "klatt_timeline.h"
-
 namespace klatt {
 
 struct ResRow { long long src, len, outLen, dst; };      // pool offset and samples of a row's utterance; its outputs; its first element in the output
@@ -211,12 +207,9 @@ struct ResRow { long long src, len, outLen, dst; };      // pool offset and samp
 struct ResArgs {
     const int16_t* pool;
     const ResRow* rows;
-    const long long *start, *chunk;      // the packed form's row table over TILES (rowStride 0)
-    long long rowStride, tilesPerRow;    // the padded form: a row's width and its tiles
-    long long nTiles;
+    TileOut tile;
     const float* hT;                     // [taps][up]
     int up, down, Z, span;
-    void* out;
 };
 
 static_assert((kResampleTile & (kResampleTile - 1)) == 0 && kResampleTile <= 4096, "kResampleTile is a power of two, at most 4096");
@@ -225,27 +218,21 @@ static_assert(kResampleIn >= kResampleMaxTaps + 1 + kResampleMaxTaps / 2, "a spa
 template <bool F32>
 __global__ void __launch_bounds__(256) klatt_resample(const ResArgs A)
 {
-    using T = typename std::conditional<F32, float, int16_t>::type;
-    constexpr int EL = 16 / (int)sizeof(T);
+    using T = TileValue<F32>;
     __shared__ float xin[kResampleIn];
     __shared__ __attribute__((aligned(16))) T staged[kResampleTile];
     const int tid = threadIdx.x;
     const int up = A.up, down = A.down, Z = A.Z, taps = 2 * Z;
-    T* __restrict__ out = static_cast<T*>(A.out);
-    const int mis = (int)((reinterpret_cast<uintptr_t>(A.out) / sizeof(T)) & (EL - 1));      // elements past a 16-byte boundary at out[0]
-    for (long long g = blockIdx.x; g < A.nTiles; g += gridDim.x) {
-        long long r, j;
-        if (A.rowStride > 0) { r = g / A.tilesPerRow; j = g - r * A.tilesPerRow; }
-        else { const long long c = g >> kTimelineChunkLog2; packed_locate(g, A.start, A.chunk[c], A.chunk[c + 1] + 1, r, j); }
+    for (long long g = blockIdx.x; g < A.tile.nTiles; g += gridDim.x) {
+        long long r, t0;
+        tile_locate(A.tile, g, kResampleTile, r, t0);
         const ResRow row = A.rows[r];
-        const long long width = A.rowStride > 0 ? A.rowStride : row.outLen;
-        const long long t0 = j * kResampleTile;
-        const int n = (int)min((long long)kResampleTile, width - t0);
+        const int n = tile_n(A.tile.rowStride, row.outLen, t0, kResampleTile);
         const int16_t* __restrict__ pcm = A.pool + row.src;
         for (int c0 = 0; c0 < n; c0 += A.span) {
             const int cn = min(A.span, n - c0);
             const long long m0 = t0 + c0;
-            const int live = (int)max(0ll, min((long long)cn, row.outLen - m0));      // outputs of the span inside the row; the rest is padding
+            const int live = tile_live(cn, row.outLen, m0);      // outputs of the span inside the row; the rest is padding
             long long nA = 0; int pA = 0;
             if (live > 0) {
                 // ---- the span's inputs, once ----
@@ -268,28 +255,12 @@ __global__ void __launch_bounds__(256) klatt_resample(const ResArgs A)
                     const uint32_t a = (uint32_t)pA + (uint32_t)i * (uint32_t)down;      // (below 2^12 + 2^10 2^21)
                     const uint32_t col = (jA + (uint32_t)i) % (uint32_t)up;
                     const float y = res_taps(xin + a / (uint32_t)up, A.hT + col, taps, up);
-                    if (F32) v = (T)y; else v = (T)res_int16(y);
+                    v = res_value<F32>(y);
                 }
                 staged[i] = v;
             }
             __syncthreads();
-            // ---- the stores: a lane owns an aligned 16 bytes of the output ----
-            const long long e0 = row.dst + m0;
-            const long long first = e0 - ((e0 + mis) & (EL - 1));
-            const int lanes = (int)((e0 + cn - first + EL - 1) / EL);
-            for (int i = tid; i < lanes; i += 256) {
-                const long long at = first + (long long)i * EL;
-                const int b0 = (int)(at - e0);                          // (negative in the first lane of a span that starts inside its 16 bytes)
-                if (b0 >= 0 && b0 + EL <= cn) {
-                    struct alignas(16) Lane { T x[EL]; } l;
-#pragma unroll
-                    for (int q = 0; q < EL; ++q) l.x[q] = staged[b0 + q];
-                    *reinterpret_cast<Lane*>(out + at) = l;
-                } else {
-#pragma unroll
-                    for (int q = 0; q < EL; ++q) if (b0 + q >= 0 && b0 + q < cn) out[at + q] = staged[b0 + q];
-                }
-            }
+            tile_store<T>(A.tile.out, row.dst + m0, cn, staged, tid);
             // (the next span's loads and values are behind its own barriers: every lane has read `staged` before any lane passes the first)
         }
     }

@@ -55,17 +55,18 @@ static void model(const std::vector<int16_t>& row, float speechGain, const std::
     CHECK(mix_host(pcm, L, speechGain, sources.data(), host.data(), (long long)host.size(), 0, want16.data()) == L, "length");
     CHECK(want[(size_t)L] == -7.0f && want16[(size_t)L] == -7, "the statement wrote past its output");
     const int T = kMixTile;
-    const long long tilesPerRow = mix_tiles(width);
+    const long long tilesPerRow = tile_count(width, T);
     CHECK(tilesPerRow == (width + T - 1) / T, "tiles");
     long long covered = 0;
     for (long long g = 0; g < tilesPerRow; ++g) {
         long long r, j;
-        mix_tile_row(g + 5 * tilesPerRow, tilesPerRow, r, j);
+        tile_row(g + 5 * tilesPerRow, tilesPerRow, r, j);
         CHECK(r == 5 && j == g, "tile %lld is tile %lld of row %lld", g, j, r);
         const long long t0 = j * T;
         const int n = (int)std::min<long long>(T, width - t0);
         const int live = (int)std::max<long long>(0, std::min<long long>(n, L - t0));
         CHECK(n >= 1 && n <= T && live >= 0 && live <= n, "tile %lld: %d elements, %d live", g, n, live);
+        CHECK(tile_n(width, L, t0, T) == n && tile_live(n, L, t0) == live, "tile %lld: the kernel takes %d elements, %d live", g, tile_n(width, L, t0, T), tile_live(n, L, t0));
         covered += live;
         std::vector<float> acc((size_t)T, 0.0f);
         std::vector<std::vector<std::pair<int, long long>>> visited((size_t)T);

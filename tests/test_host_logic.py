@@ -227,6 +227,17 @@ def test_export_planning_under_sanitizers(tmp_path):
     assert out.startswith("ok ") and "runtime error" not in out and "AddressSanitizer" not in out, out
 
 
+def test_tile_walk_and_row_writer_under_sanitizers(tmp_path):
+    """The tile walk and the row writer of the PCM-derived exports (csrc/klatt_tiles.h, tile_row_table of csrc/klatt_export.h) against
+    brute force in tests/native/check_tiles.cpp, under AddressSanitizer + UBSan: every lane of every run into a guarded buffer at every
+    misalignment, every tile of packed and padded launches.  Nothing loaded into python is run under a sanitizer."""
+    exe = str(tmp_path / "check_tiles")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "native", "check_tiles.cpp"), "-o", exe])
+    out = subprocess.check_output([exe], stderr=subprocess.STDOUT).decode()
+    assert out.startswith("ok ") and "runtime error" not in out and "AddressSanitizer" not in out, out
+
+
 def test_batch_planning_under_sanitizers(tmp_path):
     """The host planning of a set call (csrc/klatt_batchplan.h: per-list length, timing and class, the routing, lane packing) against
     the rules restated by brute force and the small cases written out in tests/native/check_batch_plan.cpp, under AddressSanitizer + UBSan."""
