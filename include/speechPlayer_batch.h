@@ -450,7 +450,8 @@ long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const
  * Like the spectrogram, and unlike the exports of the batch "as set", the result is a function of the batch's PCM: it depends on the
  * mode and, in MODE_FAST, on whatever that mode's tolerance allows; it needs a synthesis launch.
  * Out of scope: live handles (resampling across pulls needs filter state); NodePlayer, which reaches the export through
- * speechPlayer_node_part; a spectrogram or a label grid at the target rate (see "ratio" for where output sample m lies).
+ * speechPlayer_node_part; a label grid at the target rate (see "ratio" for where output sample m lies).  A spectrogram at the target
+ * rate is speechPlayer_batch_exportSpectrogramOf of this export's output ("The exports of a signal", below).
  *
  * Refused by all of the entry points below with SPEECHPLAYER_ERR_ARGUMENT and nothing written: a rate <= 0, zeros < 1, rolloff outside
  * (0, 1] or not finite, an unknown window, Kaiser with beta not finite or negative, up > 4096, taps > 1024, up * taps > 2^20.
@@ -507,9 +508,9 @@ long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const l
  * outside the signal, pad blocks to a multiple of four taps and stage masked inputs.
  * Like the resampler, the result is a function of the batch's PCM: it depends on the mode and, in MODE_FAST, on whatever that mode's
  * tolerance allows; it needs a synthesis launch.
- * Out of scope: live handles (filter state across pulls); NodePlayer, which reaches the export through speechPlayer_node_part; a
- * spectrogram or resampling of the convolved signal (those exports read the pool); per-row gains and wet/dry mixes (put them in the
- * response); FFT or MFMA formulations.
+ * Out of scope: live handles (filter state across pulls); NodePlayer, which reaches the export through speechPlayer_node_part;
+ * per-row gains and wet/dry mixes (put them in the response); FFT or MFMA formulations.  A spectrogram or resampling of the convolved
+ * signal is speechPlayer_batch_exportSpectrogramOf / exportResampledOf of this export's output ("The exports of a signal", below).
  *
  * Host only, touches no device: the definition above on `length` samples of plain PCM and one response of `taps` values -- the statement
  * the device is held to bit for bit.  out: float[Lout] (format 1) or int16[Lout] (format 0).  Returns Lout; a NULL out only sizes; -1 on
@@ -562,7 +563,9 @@ long long speechPlayer_batch_exportConvolved(speechPlayer_batch_t batch, const l
  * The result is a function of the batch's PCM: it needs a synthesis launch, depends on the mode (in MODE_FAST on whatever that mode's
  * tolerance allows) and is ordered as speechPlayer_batch_exportPcm is.
  * Out of scope: live handles; NodePlayer, which reaches the export through speechPlayer_node_part; mixing onto a convolved or resampled
- * signal (use speechGain = 0 for the noise bed and add it); segment or active-speech (VAD-weighted) levels; loudness weighting; random
+ * signal -- an SNR needs the row's power, which for a float32 signal has no order-free exact definition as the pool's integer sum is:
+ * until host and device share a fixed reduction shape the mix heads the chain (its output goes into the exports of a signal, below), or
+ * the noise bed is made with speechGain = 0 and added by the caller; segment or active-speech (VAD-weighted) levels; loudness weighting; random
  * draws of any kind -- clips, offsets and levels are the caller's.
  */
 typedef struct {
@@ -618,6 +621,64 @@ long long speechPlayer_batch_exportMixed(speechPlayer_batch_t batch, const long 
  * length. */
 long long speechPlayer_pcmMix(const sample* pcm, long long length, float speechGain, const speechPlayer_mixSource_t* sources, long long nSources,
 	const speechPlayer_mixTerm_t* terms, long long nTerms, float* gains, int format, void* out, long long capacity);
+/* The exports of a signal: the spectrogram, the resampler and the convolution on rows of samples in the CALLER's device memory, in place
+ * of the batch's pool -- what speechPlayer_batch_exportPcm, exportMixed, exportConvolved and exportResampled return, so that the output of
+ * one goes into the next: the log-mel of noisy, reverberant speech at 16 kHz is exportMixed, exportConvolvedOf, exportResampledOf,
+ * exportSpectrogramOf.
+ * A signal is nRows rows of int16 or float32 samples from `data`.  Padded (rowStride > 0): row r starts at element r * rowStride and has
+ * extent[r] <= rowStride samples.  Packed (rowStride 0): extent holds nRows + 1 ascending offsets from 0, row r is the elements
+ * extent[r] .. extent[r + 1] - 1.  extent is HOST memory, read during the call.
+ * The definitions are those of the three exports above with "the utterance's int16 PCM s(t), L samples" replaced by "the row's samples,
+ * L of them": format 0 converts as the pool's samples are, x = (float)s / 32767.0f; format 1 takes x as it is, and every later operation
+ * is unchanged.  Samples outside 0 .. L-1 are +0: a padded row's remainder and the neighbouring rows are never read as signal, whatever
+ * bits they hold -- they are not loaded at all.  For a signal, equal rates in the resampler mean y[m] = x[m] (format 1) or its int16
+ * conversion (format 0).  `rows` / `nRows` choose rows of the signal in any order, repeats allowed (NULL: all, in order) and play the
+ * part `utterances` plays above: irOf is per OUTPUT row.  exportResampledOf takes the signal's rate, srcRate, since a signal has none of
+ * its own; the batch's table is keyed by it.
+ * Ordering    The export reads `data` on `stream`: ordering whatever produces the signal before it is the caller's job (on one stream
+ *             it is automatic).  It does not read the pool: it does not wait for a synthesis launch, the batch's next launch does not
+ *             wait for it, and it works on a batch that has never been set or is set but not synthesised -- the batch gives the device,
+ *             the staging blocks and the resampler's table.  At most sixteen may be in flight per batch, shared with the exports of the
+ *             batch "as set"; the seventeenth waits on the host for the oldest.  The resampler's table keeps its one order.
+ * Values      The device equals the host statements below bit for bit (through log10: within its few ulp, as above) for finite
+ *             samples of magnitude at most 2^16, the noise bank's bound: with K <= 65536 taps of magnitude at most 2^32 no sum
+ *             overflows, and the convolution's Lemma, which needs finite operands, holds.  The device cannot check this without a pass
+ *             over the data and does not.  Outside the bound the bits are unspecified; no sample's value ever steers an address.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written, beyond each export's own list: a NULL signal or an unknown format;
+ * nRows < 0; rowStride < 0; a NULL extent with nRows > 0; a negative length or one above rowStride; packed offsets that do not start
+ * at 0 or that decrease; a length above 2^44; data that is not device memory of the batch's device, misaligned to its element, or
+ * whose allocation is smaller than the rows need (a signal whose rows are all empty is not read and may have no data); a row number
+ * outside the signal; an output that overlaps the signal; srcRate <= 0.  The message names the row.
+ * Out of scope: a signal as the speech row of exportMixed (see there); live handles; NodePlayer beyond speechPlayer_node_part; a fused
+ * kernel for the chain; float64 or float16 signals; label grids at a resampled rate. */
+typedef struct {
+	const void* data;         /* device memory of the batch's device, aligned to its element */
+	int format;               /* 0 int16: x = (float)s / 32767.0f, as the pool's samples; 1 float32: x as it is */
+	int reserved;
+	long long nRows;
+	long long rowStride;      /* > 0: row r starts at r * rowStride and has extent[r] <= rowStride samples; 0: packed */
+	const long long* extent;  /* HOST: nRows lengths (padded) or nRows + 1 ascending offsets from 0 (packed) */
+} speechPlayer_signal_t;
+/* speechPlayer_batch_exportSpectrogram, exportResampled and exportConvolved of chosen rows of `signal`: the remaining arguments, the
+ * output's forms and the return value are theirs. */
+long long speechPlayer_batch_exportSpectrogramOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	int nFft, long long hop, long long phase, const double* window, const double* bank, int nBands, int power, double logScale, double floor,
+	void* deviceOut, int format, long long rowStride, void* stream);
+long long speechPlayer_batch_exportResampledOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	int srcRate, int outRate, int zeros, double rolloff, int window, double beta, void* deviceOut, int format, long long rowStride, void* stream);
+long long speechPlayer_batch_exportConvolvedOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	const float* ir, const long long* irStart, long long nIr, const long long* irOf, int tail, void* deviceOut, int format, long long rowStride,
+	void* stream);
+/* Host only, touch no device: speechPlayer_pcmSpectrogram, pcmResample and pcmConvolve on `length` samples of a signal's row, int16
+ * (inFormat 0: their bits exactly) or float32 (inFormat 1) -- the same function bodies, and the statements the device is held to.  They
+ * have the data, so beyond the refusals of speechPlayer_pcm* they refuse an unknown inFormat and a float32 sample that is not finite or
+ * is above 2^16 in magnitude; the message gives the sample. */
+long long speechPlayer_signalSpectrogram(const void* x, int inFormat, long long length, int nFft, long long hop, long long phase, const double* window,
+	const double* bank, int nBands, int power, double logScale, double floor, double* out);
+long long speechPlayer_signalResample(const void* x, int inFormat, long long length, int srcRate, int dstRate, int zeros, double rolloff, int window,
+	double beta, int format, void* out, long long capacity);
+long long speechPlayer_signalConvolve(const void* x, int inFormat, long long length, const float* ir, long long taps, int tail, int format, void* out,
+	long long capacity);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

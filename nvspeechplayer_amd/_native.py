@@ -65,6 +65,8 @@ EXPORTS = [
     "speechPlayer_pcmConvolve", "speechPlayer_batch_exportConvolved",
     "speechPlayer_pcmMix", "speechPlayer_batch_setNoiseBank", "speechPlayer_batch_noiseBank", "speechPlayer_batch_exportPower",
     "speechPlayer_batch_exportMixed",
+    "speechPlayer_batch_exportSpectrogramOf", "speechPlayer_batch_exportResampledOf", "speechPlayer_batch_exportConvolvedOf",
+    "speechPlayer_signalSpectrogram", "speechPlayer_signalResample", "speechPlayer_signalConvolve",
     "speechPlayer_planTrackKinds",
 ]
 
@@ -406,6 +408,18 @@ def load():
     L.speechPlayer_batch_exportPower.argtypes = [vp, vp, i64, vp, vp]
     L.speechPlayer_batch_exportMixed.restype = i64
     L.speechPlayer_batch_exportMixed.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, i32, i64, vp]
+    L.speechPlayer_batch_exportSpectrogramOf.restype = i64
+    L.speechPlayer_batch_exportSpectrogramOf.argtypes = [vp, vp, vp, i64, i32, i64, i64, vp, vp, i32, i32, f64, f64, vp, i32, i64, vp]
+    L.speechPlayer_batch_exportResampledOf.restype = i64
+    L.speechPlayer_batch_exportResampledOf.argtypes = [vp, vp, vp, i64, i32, i32, i32, f64, i32, f64, vp, i32, i64, vp]
+    L.speechPlayer_batch_exportConvolvedOf.restype = i64
+    L.speechPlayer_batch_exportConvolvedOf.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, i32, vp, i32, i64, vp]
+    L.speechPlayer_signalSpectrogram.restype = i64
+    L.speechPlayer_signalSpectrogram.argtypes = [vp, i32, i64, i32, i64, i64, vp, vp, i32, i32, f64, f64, vp]
+    L.speechPlayer_signalResample.restype = i64
+    L.speechPlayer_signalResample.argtypes = [vp, i32, i64, i32, i32, i32, f64, i32, f64, i32, vp, i64]
+    L.speechPlayer_signalConvolve.restype = i64
+    L.speechPlayer_signalConvolve.argtypes = [vp, i32, i64, vp, i64, i32, i32, vp, i64]
     _lib = L
     return L
 

@@ -20,7 +20,8 @@
 //                   4 l .. 4 l + 3 of the tile and keeps their sums in registers across the tap blocks, which is what keeps every
 //                   output's terms in ascending k from the first block to the last.  Per block of kConvolveBlock taps the workgroup stages
 //                   the taps in LDS (padded with +0 to a multiple of four) and the tile's inputs for them REVERSED:
-//                   xr[p] = x[t0 + T - kb - p], masked to 0 <= n < L and converted by res_input, each loaded once.  Output o, tap
+//                   xr[p] = x[t0 + T - kb - p], masked to 0 <= n < L and converted by the reader (klatt_tiles.h: tile_read downwards from
+//                   conv_read_first, from int16 or float32), each loaded once.  Output o, tap
 //                   kb + q reads xr[(T - o) + q]: both the taps and the inputs are walked upwards.  A step takes four taps: one
 //                   16-byte LDS read of the taps at the same address in every lane (a broadcast), one 16-byte read of four new inputs at
 //                   a lane stride of 16 bytes (conflict-free: the 16 lanes of a ds_read_b128 group cover 64 distinct banks), a sliding
@@ -83,6 +84,8 @@ KLATT_RES_HD bool conv_block_skipped(long long t0, int live, long long L, int kb
 }
 // xr[p] of the tile at t0 and the block at kb holds input sample conv_staged_sample (p = 0 .. kConvolveTile + padded - 1)
 KLATT_RES_HD long long conv_staged_sample(long long t0, int kb, int p) { return t0 + kConvolveTile - kb - p; }
+// ... which is the reader's run downwards from conv_read_first
+KLATT_RES_HD long long conv_read_first(long long t0, int kb) { return t0 + kConvolveTile - kb; }
 // Lane l reads the aligned four values xr[conv_window(l) + q + 4 .. + 7] for taps q .. q + 3 (and xr[conv_window(l) .. + 3] first)
 KLATT_RES_HD int conv_window(int lane) { return kConvolveTile - 4 - 4 * lane; }
 
@@ -138,13 +141,14 @@ inline long long conv_row(const ConvPlan& P, const long long* irOf, long long i,
 inline long long conv_length(long long L, long long K, int tail) { return tail ? L + K - 1 : L; }
 
 // ---- the host's statement (speechPlayer_pcmConvolve): the shared functions in a plain loop ------------------------------------------------
-// format 1: out is float[Lout]; format 0: int16_t[Lout].  Returns Lout.
-inline long long convolve_host(const int16_t* pcm, long long length, const float* h, long long K, int tail, int format, void* out)
+// format 1: out is float[Lout]; format 0: int16_t[Lout].  Returns Lout.  In: int16_t (PCM) or float (a signal's samples).
+template <typename In>
+inline long long convolve_host(const In* pcm, long long length, const float* h, long long K, int tail, int format, void* out)
 {
     const long long Lout = conv_length(length, K, tail);
     // x[n] for n = -(K-1) .. length-1, +0 outside the signal: xp[n + K - 1]
     std::vector<float> xp((size_t)(length + K - 1) + (size_t)(tail ? K - 1 : 0), 0.0f);
-    for (long long n = 0; n < length; ++n) xp[(size_t)(n + K - 1)] = res_input(pcm[n]);
+    for (long long n = 0; n < length; ++n) xp[(size_t)(n + K - 1)] = tile_x(pcm[n]);
     for (long long m = 0; m < Lout; ++m) {
         const float* x = xp.data() + (m + K - 1);      // x[-k] is x[m - k]
         float acc = 0.0f;
@@ -161,17 +165,17 @@ inline long long convolve_host(const int16_t* pcm, long long length, const float
 
 namespace klatt {
 
-// pool offset and samples of a row's utterance; its outputs; its first element in the output; its response's first tap and its taps
+// first element and samples of a row's input (the pool's utterance, a signal's row); its outputs; its first element in the output; its response's first tap and its taps
 struct ConvRow { long long src, len, outLen, dst, irAt, taps; };
 
 struct ConvArgs {
-    const int16_t* pool;
+    const void* in;                      // the pool, or a signal's data: int16_t or float, as the kernel's In says
     const ConvRow* rows;
     TileOut tile;
     const float* taps;                   // the responses back to back
 };
 
-template <bool F32>
+template <bool F32, typename In = int16_t>
 __global__ void __launch_bounds__(256) klatt_convolve(const ConvArgs A)
 {
     using T = TileValue<F32>;
@@ -186,7 +190,7 @@ __global__ void __launch_bounds__(256) klatt_convolve(const ConvArgs A)
         const ConvRow row = A.rows[r];
         const int n = tile_n(A.tile.rowStride, row.outLen, t0, TILE);
         const int live = tile_live(n, row.outLen, t0);      // outputs of the tile inside the row; the rest is padding
-        const int16_t* __restrict__ pcm = A.pool + row.src;
+        const In* __restrict__ pcm = static_cast<const In*>(A.in) + row.src;
         const float* __restrict__ h = A.taps + row.irAt;
         const int K = (int)row.taps;
         float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -197,10 +201,7 @@ __global__ void __launch_bounds__(256) klatt_convolve(const ConvArgs A)
                 if (conv_block_skipped(t0, live, row.len, kb, taps)) continue;
                 __syncthreads();                                  // the block before has been read
                 for (int i = tid; i < padded; i += 256) hs[i] = i < taps ? h[kb + i] : 0.0f;
-                for (int p = tid; p < TILE + padded; p += 256) {
-                    const long long s = conv_staged_sample(t0, kb, p);
-                    xr[p] = res_input(s >= 0 && s < row.len ? (int)pcm[s] : 0);
-                }
+                tile_read<-1>(xr, pcm, row.len, conv_read_first(t0, kb), TILE + padded, tid);
                 __syncthreads();
                 const float4* __restrict__ xw = reinterpret_cast<const float4*>(xr + conv_window(tid));
                 const float4* __restrict__ hw = reinterpret_cast<const float4*>(hs);

@@ -783,10 +783,20 @@ struct ExportSelection {
     long long n = 0, most = 0, total = 0;
     std::vector<long long> counts;
 };
-template <class PerRow>
-int export_selection(Batch* b, const char* what, const long long* utterances, long long nUtterances, bool frameLimit, ExportSelection& s, PerRow perRow)
+// The same over the rows of a caller's signal: rows[0 .. nRows) (null: every row, in order), each a row of the signal
+long long check_signal_rows(const char* what, const SignalPlan& sig, const long long* rows, long long nRows)
 {
-    s.n = check_selection(b, what, utterances, nUtterances, frameLimit);
+    const long long n = rows ? nRows : sig.nRows;
+    if (n < 0) { set_error("%s: %lld rows", what, n); return -1; }
+    for (long long i = 0; rows && i < n; ++i)
+        if (rows[i] < 0 || rows[i] >= sig.nRows) { set_error("%s: rows[%lld] = %lld is not a row of the signal (%lld)", what, i, rows[i], sig.nRows); return -1; }
+    return n;
+}
+template <class PerRow>
+int export_selection(Batch* b, const char* what, const long long* utterances, long long nUtterances, bool frameLimit, ExportSelection& s, PerRow perRow,
+                     const SignalPlan* sig = nullptr)
+{
+    s.n = sig ? check_signal_rows(what, *sig, utterances, nUtterances) : check_selection(b, what, utterances, nUtterances, frameLimit);
     if (s.n < 0) return -1;
     s.counts.resize((size_t)s.n);
     for (long long i = 0; i < s.n; ++i) {
@@ -814,15 +824,17 @@ long long export_elements(const char* what, const ExportNouns& nouns, const Expo
 // per-request records, the shared table's previous export, and the block's upload on the stream.  finish(): behind the launches.
 // An export of the batch's PCM (ofPcm: the spectrogram) reads the pool instead: it takes one of speechPlayer_batch_exportPcm's slots, which
 // the next launch waits for (wait_exports), and stands behind the batch's last launch (pcmReady) in place of the per-request records.
+// An export of a caller's signal (ofSignal) reads nothing of the batch: it takes a slot of the exports "as set" -- no launch waits for
+// it -- and stands behind nothing; the caller orders whatever produces the signal before it on `st`.  It works on a batch never set.
 struct ExportStage {
     Batch* b;
     hipStream_t st;
     const StageBlock& block;
     Batch::SharedTable* table;      // the order the export's shared table keeps (null: it uses none)
-    bool ofPcm;
+    bool ofPcm, ofSignal;
     Batch::ExportSlot* slot = nullptr;
-    ExportStage(Batch* b, hipStream_t st, const StageBlock& block, Batch::SharedTable* table = nullptr, bool ofPcm = false)
-        : b(b), st(st), block(block), table(table), ofPcm(ofPcm) {}
+    ExportStage(Batch* b, hipStream_t st, const StageBlock& block, Batch::SharedTable* table = nullptr, bool ofPcm = false, bool ofSignal = false)
+        : b(b), st(st), block(block), table(table), ofPcm(ofPcm), ofSignal(ofSignal) {}
     template <class Grow>
     int begin(Grow grow)
     {
@@ -833,7 +845,7 @@ struct ExportStage {
         if (ofPcm) {
             HIP_TRY(hipEventRecord(b->pcmReady, b->stream));
             HIP_TRY(hipStreamWaitEvent(st, b->pcmReady, 0));
-        } else if (timeline_on_stream(b, st)) return -1;
+        } else if (!ofSignal && timeline_on_stream(b, st)) return -1;
         if (table && table->wait(st)) return -1;
         block.copy_to(slot->host.ptr);
         if (block.upload_bytes()) HIP_TRY(hipMemcpyAsync(slot->dev.ptr, slot->host.ptr, block.upload_bytes(), hipMemcpyHostToDevice, st));
@@ -5111,53 +5123,124 @@ long long speechPlayer_batch_exportStems(speechPlayer_batch_t batch, const long 
     });
 }
 
+// ---- what the spectrogram, resampled and convolved exports read ----------------------------------------------------------------------------
+// The batch's pool, a row per utterance (sig null), or a caller's signal (speechPlayer_signal_t; klatt_tiles.h: signal_plan, the reader).
+// An entry point over a signal differs from its sibling over the pool in four places, all here (export_input decides): the rows it may choose
+// (export_selection's `sig`), no synthesis is needed (export_synthesised is skipped), the signal's memory is checked beside the output's
+// (signal_memory) and the stage is ExportStage's ofSignal.
+static_assert(sizeof(speechPlayer_signal_t) == 40 && offsetof(speechPlayer_signal_t, extent) == 32, "speechPlayer_signal_t is five 8-byte words");
+struct ExportInput {
+    Batch* b;
+    const SignalPlan* sig = nullptr;
+    const void* data = nullptr;          // the pool, or the signal's data
+    long long at(long long r) const { return sig ? sig->at(r) : b->outStart[(size_t)r]; }
+    long long len(long long r) const { return sig ? sig->len(r) : (long long)b->lens[(size_t)r]; }
+    int format() const { return sig ? sig->format : 0; }
+};
+// What an entry point reads: the pool (ofSignal false; `signal` is not looked at), or `signal` with the refusals that need no device, in
+// the header's order
+static int export_input(Batch* b, const char* what, bool ofSignal, const speechPlayer_signal_t* signal, SignalPlan& P, ExportInput& in)
+{
+    if (!ofSignal) { in = ExportInput{b, nullptr, b->dPcm.ptr}; return 0; }
+    if (!signal) { set_error("%s: no signal", what); return -1; }
+    std::string why;
+    if (!signal_plan(P, signal->format, signal->nRows, signal->rowStride, signal->extent, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+    in = ExportInput{b, &P, signal->data};
+    return 0;
+}
+// ... and those of its memory, once the output's are past: device memory of the batch's device that holds every row, aligned to its
+// element, apart from the output.  A signal whose rows are all empty is never read and may have no data.
+static int signal_memory(const ExportInput& in, const char* what, const void* deviceOut, size_t outBytes)
+{
+    if (!in.sig || in.sig->need == 0) return 0;
+    const size_t bytes = (size_t)in.sig->need * (size_t)in.sig->elSize;
+    if (!in.data) { set_error("%s: signal without data", what); return -1; }
+    const std::string name = std::string(what) + ": signal";
+    if (!device_range(in.data, bytes, in.b->device, (size_t)in.sig->elSize, name.c_str())) return -1;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in.data), o = reinterpret_cast<uintptr_t>(deviceOut);
+    if (a < o + outBytes && o < a + bytes) { set_error("%s: the output (%zu bytes from %p) overlaps the signal (%zu bytes from %p)", what, outBytes, deviceOut, bytes, in.data); return -1; }
+    return 0;
+}
+
 // ---- STFT and band spectrogram of the PCM (klatt_spectrum.h) -----------------------------------------------------------------------------
 // Host only, touches no device: the definition of include/speechPlayer_batch.h on plain PCM, out[step][band], through the functions the
 // kernel is compiled from (klatt_spectrum.h).
+// The host statements over a signal's samples (speechPlayer_signal*): the input format, first of their refusals, and the values of
+// float32 samples, last of them (once there is something to compute)
+static int signal_host_format(const char* what, int inFormat)
+{
+    if (inFormat != 0 && inFormat != 1) { set_error("%s: input format %d (0 int16, 1 float32)", what, inFormat); return -1; }
+    return 0;
+}
+static int signal_host_values(const char* what, const void* x, int inFormat, long long length)
+{
+    std::string why;
+    if (inFormat == 1 && length > 0 && x && !signal_values(static_cast<const float*>(x), length, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+    return 0;
+}
+
+static long long spectrogram_statement(const char* what, const void* x, int inFormat, long long length, int nFft, long long hop, long long phase, const double* window,
+                                       const double* bank, int nBands, int power, double logScale, double floor, double* out)
+{
+    if (signal_host_format(what, inFormat)) return -1;
+    if (length < 0 || hop <= 0 || phase < 0 || (length > 0 && !x)) { set_error("%s: length %lld, hop %lld, phase %lld", what, length, hop, phase); return -1; }
+    try {
+        SpecPlan P;
+        std::string why;
+        if (!spec_plan(P, nFft, window, bank, nBands, power, logScale, floor, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
+        if (align_steps_below(length, hop, phase) > 0 && !out) { set_error("%s: no output", what); return -1; }
+        if (signal_host_values(what, x, inFormat, length)) return -1;
+        return inFormat ? spectrogram_host(static_cast<const float*>(x), length, P, hop, phase, out)
+                        : spectrogram_host(static_cast<const int16_t*>(x), length, P, hop, phase, out);
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
 long long speechPlayer_pcmSpectrogram(const sample* pcm, long long length, int nFft, long long hop, long long phase, const double* window,
                                       const double* bank, int nBands, int power, double logScale, double floor, double* out)
 {
     begin_call();
-    if (length < 0 || hop <= 0 || phase < 0 || (length > 0 && !pcm)) { set_error("pcmSpectrogram: length %lld, hop %lld, phase %lld", length, hop, phase); return -1; }
-    try {
-        SpecPlan P;
-        std::string why;
-        if (!spec_plan(P, nFft, window, bank, nBands, power, logScale, floor, why)) { set_error("pcmSpectrogram: %s", why.c_str()); return -1; }
-        hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
-        if (align_steps_below(length, hop, phase) > 0 && !out) { set_error("pcmSpectrogram: no output"); return -1; }
-        static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
-        return spectrogram_host(reinterpret_cast<const int16_t*>(pcm), length, P, hop, phase, out);
-    } catch (const std::exception& e) { set_error("pcmSpectrogram: %s", e.what()); return -1; }
+    static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
+    return spectrogram_statement("pcmSpectrogram", pcm, 0, length, nFft, hop, phase, window, bank, nBands, power, logScale, floor, out);
+}
+
+long long speechPlayer_signalSpectrogram(const void* x, int inFormat, long long length, int nFft, long long hop, long long phase, const double* window,
+                                         const double* bank, int nBands, int power, double logScale, double floor, double* out)
+{
+    begin_call();
+    return spectrogram_statement("signalSpectrogram", x, inFormat, length, nFft, hop, phase, window, bank, nBands, power, logScale, floor, out);
 }
 
 // The spectrogram of chosen utterances' PCM, one wavefront per step (klatt_spectrum.h).  It reads the pool, so it is ordered as
 // speechPlayer_batch_exportPcm is (ExportStage, ofPcm).  The staging block: rows | step starts and chunk rows (packed) | window |
 // twiddles | band weights | band ranges.
-long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int nFft,
-                                               long long hop, long long phase, const double* window, const double* bank, int nBands, int power,
-                                               double logScale, double floor, void* deviceOut, int format, long long rowStride, void* stream)
+// ofSignal: the rows are chosen from and read from `signal` in place of the pool (export_input).
+static long long spectrogram_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances, long long nUtterances, int nFft,
+                                    long long hop, long long phase, const double* window, const double* bank, int nBands, int power,
+                                    double logScale, double floor, void* deviceOut, int format, long long rowStride, void* stream)
 {
-    const char* what = "exportSpectrogram";
-    if (refuse_timing_only("speechPlayer_batch_exportSpectrogram")) return -1;
     return batch_entry(what, batch, [&](Batch* b) -> long long {
-        if (format != 0 && format != 1) { set_error("exportSpectrogram: format %d (0 float64, 1 float32)", format); return -1; }
+        if (format != 0 && format != 1) { set_error("%s: format %d (0 float64, 1 float32)", what, format); return -1; }
         if (step_request(what, hop, phase, rowStride)) return -1;
         SpecPlan P;
         std::string why;
-        if (!spec_plan(P, nFft, window, bank, nBands, power, logScale, floor, why)) { set_error("exportSpectrogram: %s", why.c_str()); return -1; }
+        if (!spec_plan(P, nFft, window, bank, nBands, power, logScale, floor, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
         ExportSelection s;
         std::vector<SpecRow> rows;
         if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long, long long u, long long) {
-                const long long L = (long long)b->lens[(size_t)u];
-                rows.push_back(SpecRow{b->outStart[(size_t)u], L, align_steps_below(L, hop, phase)});
+                const long long L = in.len(u);
+                rows.push_back(SpecRow{in.at(u), L, align_steps_below(L, hop, phase)});
                 return rows.back().steps;
-            })) return -1;
+            }, in.sig)) return -1;
         static constexpr ExportNouns kBandNouns{"largest step count", "steps", "bands"};
         const long long elements = export_elements(what, kBandNouns, s, rowStride, P.nOut);
         if (elements <= 0) return elements;
-        if (export_synthesised(b, what)) return -1;
+        if (!in.sig && export_synthesised(b, what)) return -1;
         const size_t elSize = format ? sizeof(float) : sizeof(double);
-        if (export_output(b, what, deviceOut, elements, elSize)) return -1;
+        if (export_output(b, what, deviceOut, elements, elSize) || signal_memory(in, what, deviceOut, (size_t)elements * elSize)) return -1;
         hipStream_t st = static_cast<hipStream_t>(stream);
 
         const bool packed = rowStride == 0;
@@ -5166,11 +5249,13 @@ long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const
         StageBlock block;
         const int rowsAt = block.add(rows), wordsAt = block.add(words), windowAt = block.add(P.window), twAt = block.add(P.tw),
                   weightsAt = block.add(P.weights), rangeAt = block.add(P.range);
-        const auto kernel = format ? klatt_spectrogram<true> : klatt_spectrogram<false>;
-        ExportStage stage(b, st, block, nullptr, true);
+        // the kernel of the input's and the output's type
+        void (*const kernels[2][2])(SpecArgs) = {{klatt_spectrogram<false, int16_t>, klatt_spectrogram<true, int16_t>}, {klatt_spectrogram<false, float>, klatt_spectrogram<true, float>}};
+        const auto kernel = kernels[in.format()][format];
+        ExportStage stage(b, st, block, nullptr, !in.sig, in.sig != nullptr);
         if (stage.begin([&] { return ensure_lds_limit(reinterpret_cast<const void*>(kernel), kSpecLdsBudget); })) return -1;
         SpecArgs A;
-        A.pool = b->dPcm.ptr; A.rows = stage.device<SpecRow>(rowsAt);
+        A.in = in.data; A.rows = stage.device<SpecRow>(rowsAt);
         A.start = packed ? stage.device<long long>(wordsAt) + table.startOff : nullptr;
         A.chunk = packed ? stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
         A.rowStride = rowStride; A.nSteps = elements / P.nOut;
@@ -5189,6 +5274,26 @@ long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const
     });
 }
 
+long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int nFft,
+                                               long long hop, long long phase, const double* window, const double* bank, int nBands, int power,
+                                               double logScale, double floor, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportSpectrogram")) return -1;
+    return spectrogram_export("exportSpectrogram", batch, false, nullptr, utterances, nUtterances,
+                              nFft, hop, phase, window, bank, nBands, power, logScale, floor, deviceOut, format, rowStride, stream);
+}
+
+// The same of chosen rows of a caller's signal: it reads no pool and needs no synthesis (ExportStage, ofSignal).
+long long speechPlayer_batch_exportSpectrogramOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows, int nFft,
+                                                 long long hop, long long phase, const double* window, const double* bank, int nBands, int power,
+                                                 double logScale, double floor, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    const char* what = "exportSpectrogramOf";
+    if (refuse_timing_only("speechPlayer_batch_exportSpectrogramOf")) return -1;
+    return spectrogram_export(what, batch, true, signal, rows, nRows,
+                              nFft, hop, phase, window, bank, nBands, power, logScale, floor, deviceOut, format, rowStride, stream);
+}
+
 // ---- the tile-wise exports of the PCM (klatt_tiles.h): resampled, convolved, mixed ---------------------------------------------------------
 // A workgroup takes tiles of one row: the packed form's row table counts TILES (klatt_export.h: tile_row_table), the rows carry their
 // first element in the output.  An entry point is, in the order of its refusals: tile_request, its own plan, export_selection with
@@ -5203,10 +5308,14 @@ static int tile_request(const char* what, int format, long long rowStride)
 // Row i's first element in the output: i rows of rowStride (padded: export_elements refuses an extent that wraps) or the outputs before it
 static long long tile_row_first(long long i, long long rowStride, long long before) { return rowStride > 0 ? (long long)((unsigned long long)i * (unsigned long long)rowStride) : before; }
 // The elements of the export (0: nothing to do), or -1 with the message set: the extent, a batch not synthesised, the output, in this order
-static long long tile_elements(Batch* b, const char* what, const ExportSelection& s, long long rowStride, int format, void* deviceOut)
+// (an export of a signal needs no synthesis; its memory is checked beside the output's)
+static long long tile_elements(Batch* b, const char* what, const ExportSelection& s, long long rowStride, int format, void* deviceOut, const ExportInput* in = nullptr)
 {
     const long long elements = export_elements(what, kSampleNouns, s, rowStride, 1);
-    if (elements > 0 && (export_synthesised(b, what) || export_output(b, what, deviceOut, elements, format ? sizeof(float) : sizeof(int16_t)))) return -1;
+    if (elements <= 0) return elements;
+    const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
+    if (!(in && in->sig) && export_synthesised(b, what)) return -1;
+    if (export_output(b, what, deviceOut, elements, elSize) || (in && signal_memory(*in, what, deviceOut, (size_t)elements * elSize))) return -1;
     return elements;
 }
 static TileOut tile_out(const ExportStage& stage, int wordsAt, const TileTable& t, long long rowStride, void* deviceOut)
@@ -5222,6 +5331,13 @@ static int launch_tiles(ExportStage& stage, void (*int16)(Args), void (*float32)
     hipLaunchKernelGGL(format ? float32 : int16, dim3(grid), dim3(256), 0, stage.st, A);
     HIP_TRY(hipGetLastError());
     return stage.finish();
+}
+
+// The same with a kernel per input type: kernels[input format][output format]
+extern "C++" template <class Args>
+static int launch_tiles(ExportStage& stage, void (*const (&kernels)[2][2])(Args), int inFormat, int format, long long perCu, const Args& A)
+{
+    return launch_tiles(stage, kernels[inFormat][0], kernels[inFormat][1], format, perCu, A);
 }
 
 // ---- the PCM at another sample rate (klatt_resample.h) -----------------------------------------------------------------------------------
@@ -5252,62 +5368,94 @@ long long speechPlayer_resampleKernel(int srcRate, int dstRate, int zeros, doubl
     } catch (const std::exception& e) { set_error("resampleKernel: %s", e.what()); return -1; }
 }
 
+static long long resample_statement(const char* what, const void* x, int inFormat, long long length, int srcRate, int dstRate, int zeros, double rolloff, int window,
+                                    double beta, int format, void* out, long long capacity)
+{
+    if (signal_host_format(what, inFormat)) return -1;
+    if (length < 0 || length > kResampleMaxLength || (length > 0 && !x)) { set_error("%s: length %lld (0 .. 2^44, with its samples)", what, length); return -1; }
+    if (format != 0 && format != 1) { set_error("%s: format %d (0 int16, 1 float32)", what, format); return -1; }
+    try {
+        ResPlan P;
+        std::string why;
+        if (!res_plan(P, srcRate, dstRate, zeros, rolloff, window, beta, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        const long long Lout = res_length(length, P.up, P.down);
+        if (!out) return Lout;
+        if (capacity < Lout) { set_error("%s: the output takes %lld elements, capacity is %lld", what, Lout, capacity); return -1; }
+        if (signal_host_values(what, x, inFormat, length)) return -1;
+        return inFormat ? resample_host(static_cast<const float*>(x), length, P, format, out) : resample_host(static_cast<const int16_t*>(x), length, P, format, out);
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
 long long speechPlayer_pcmResample(const sample* pcm, long long length, int srcRate, int dstRate, int zeros, double rolloff, int window, double beta,
                                    int format, void* out, long long capacity)
 {
     begin_call();
-    if (length < 0 || length > kResampleMaxLength || (length > 0 && !pcm)) { set_error("pcmResample: length %lld (0 .. 2^44, with its samples)", length); return -1; }
-    if (format != 0 && format != 1) { set_error("pcmResample: format %d (0 int16, 1 float32)", format); return -1; }
-    try {
-        ResPlan P;
-        std::string why;
-        if (!res_plan(P, srcRate, dstRate, zeros, rolloff, window, beta, why)) { set_error("pcmResample: %s", why.c_str()); return -1; }
-        const long long Lout = res_length(length, P.up, P.down);
-        if (!out) return Lout;
-        if (capacity < Lout) { set_error("pcmResample: the output takes %lld elements, capacity is %lld", Lout, capacity); return -1; }
-        static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
-        return resample_host(reinterpret_cast<const int16_t*>(pcm), length, P, format, out);
-    } catch (const std::exception& e) { set_error("pcmResample: %s", e.what()); return -1; }
+    static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
+    return resample_statement("pcmResample", pcm, 0, length, srcRate, dstRate, zeros, rolloff, window, beta, format, out, capacity);
+}
+
+long long speechPlayer_signalResample(const void* x, int inFormat, long long length, int srcRate, int dstRate, int zeros, double rolloff, int window, double beta,
+                                      int format, void* out, long long capacity)
+{
+    begin_call();
+    return resample_statement("signalResample", x, inFormat, length, srcRate, dstRate, zeros, rolloff, window, beta, format, out, capacity);
 }
 
 // The chosen utterances' PCM at `outRate` (klatt_resample.h).  It reads the pool, so it is ordered as speechPlayer_batch_exportPcm is
 // (ExportStage, ofPcm), tile-wise.  The staging block: rows | tile starts and chunk rows (packed) | the table, when the batch does not hold it.
 // The table stays on the batch until the parameters change; the exports that read it follow one order (resampleOrder).
-long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int outRate, int zeros,
-                                             double rolloff, int window, double beta, void* deviceOut, int format, long long rowStride, void* stream)
+// ofSignal and `signal` as spectrogram_export's; over the pool srcRate is the batch's rate.  Equal rates: -2 over the pool (the caller answers with
+// speechPlayer_batch_exportPcm), the copy kernel over a signal.
+static long long resampled_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances, long long nUtterances, int srcRate,
+                                  int outRate, int zeros, double rolloff, int window, double beta, void* deviceOut, int format, long long rowStride, void* stream)
 {
-    const char* what = "exportResampled";
-    if (refuse_timing_only("speechPlayer_batch_exportResampled")) return -1;
-    const long long done = batch_entry(what, batch, [&](Batch* b) -> long long {
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
         if (tile_request(what, format, rowStride)) return -1;
-        if (!b->resPlan.same(b->sampleRate, outRate, zeros, rolloff, window, beta)) {
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
+        if (!in.sig) srcRate = b->sampleRate;
+        if (!b->resPlan.same(srcRate, outRate, zeros, rolloff, window, beta)) {
             ResPlan P;
             std::string why;
-            if (!res_plan(P, b->sampleRate, outRate, zeros, rolloff, window, beta, why)) { set_error("exportResampled: %s", why.c_str()); return -1; }
+            if (!res_plan(P, srcRate, outRate, zeros, rolloff, window, beta, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
             b->resPlan = std::move(P);
             b->resOnDevice = false;
         }
         ResPlan& P = b->resPlan;
-        if (P.identity) return -2;      // equal rates: speechPlayer_batch_exportPcm's output exactly
+        if (P.identity && !in.sig) return -2;      // equal rates: speechPlayer_batch_exportPcm's output exactly
         ExportSelection s;
         std::vector<ResRow> rows;
         if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) {
-                const long long L = (long long)b->lens[(size_t)u], Lout = res_length(L, P.up, P.down);
-                rows.push_back(ResRow{b->outStart[(size_t)u], L, Lout, tile_row_first(i, rowStride, before)});
+                const long long L = in.len(u), Lout = res_length(L, P.up, P.down);
+                rows.push_back(ResRow{in.at(u), L, Lout, tile_row_first(i, rowStride, before)});
                 return Lout;
-            })) return -1;
-        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut);
+            }, in.sig)) return -1;
+        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut, &in);
         if (elements <= 0) return elements;
         hipStream_t st = static_cast<hipStream_t>(stream);
 
         std::vector<long long> words;
         const TileTable tiles = tile_row_table(s.counts.data(), s.n, kResampleTile, rowStride, kTimelineChunkLog2, words);
+        if (P.identity) {      // a signal at its own rate: no table, no filter
+            StageBlock block;
+            const int rowsAt = block.add(rows), wordsAt = block.add(words);
+            ExportStage stage(b, st, block, nullptr, false, true);
+            if (stage.begin()) return -1;
+            ResArgs A;
+            A.in = in.data; A.rows = stage.device<ResRow>(rowsAt);
+            A.tile = tile_out(stage, wordsAt, tiles, rowStride, deviceOut);
+            A.hT = nullptr; A.up = A.down = 1; A.Z = 0; A.span = kResampleTile;
+            void (*const copies[2][2])(ResArgs) = {{klatt_signal_copy<false, int16_t>, klatt_signal_copy<true, int16_t>}, {klatt_signal_copy<false, float>, klatt_signal_copy<true, float>}};
+            if (launch_tiles(stage, copies, in.format(), format, 8, A)) return -1;
+            return elements;
+        }
         const bool upload = !b->resOnDevice;
         if (upload) res_transpose(P);
         StageBlock block;
         const int rowsAt = block.add(rows), wordsAt = block.add(words), tableAt = upload ? block.add(P.hT) : -1;
         const size_t tableSize = (size_t)P.up * P.taps;
-        ExportStage stage(b, st, block, &b->resampleOrder, true);
+        ExportStage stage(b, st, block, &b->resampleOrder, !in.sig, in.sig != nullptr);
         if (stage.begin([&] {
                 if (tableSize <= b->dResample.cap) return 0;
                 if (b->resampleOrder.used) { HIP_TRY(hipEventSynchronize(b->resampleOrder.done)); }      // (the table is freed: its readers first)
@@ -5315,77 +5463,137 @@ long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const l
             })) return -1;
         if (upload) HIP_TRY(hipMemcpyAsync(b->dResample.ptr, stage.device<float>(tableAt), tableSize * sizeof(float), hipMemcpyDeviceToDevice, st));
         ResArgs A;
-        A.pool = b->dPcm.ptr; A.rows = stage.device<ResRow>(rowsAt);
+        A.in = in.data; A.rows = stage.device<ResRow>(rowsAt);
         A.tile = tile_out(stage, wordsAt, tiles, rowStride, deviceOut);
         A.hT = b->dResample.ptr; A.up = P.up; A.down = P.down; A.Z = P.Z; A.span = res_span(P);
-        if (launch_tiles(stage, klatt_resample<false>, klatt_resample<true>, format, 8, A)) return -1;
+        void (*const kernels[2][2])(ResArgs) = {{klatt_resample<false, int16_t>, klatt_resample<true, int16_t>}, {klatt_resample<false, float>, klatt_resample<true, float>}};
+        if (launch_tiles(stage, kernels, in.format(), format, 8, A)) return -1;
         b->resOnDevice = true;
         return elements;
     });
+}
+
+long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int outRate, int zeros,
+                                             double rolloff, int window, double beta, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportResampled")) return -1;
+    const long long done = resampled_export("exportResampled", batch, false, nullptr, utterances, nUtterances,
+                                            0, outRate, zeros, rolloff, window, beta, deviceOut, format, rowStride, stream);
     return done == -2 ? speechPlayer_batch_exportPcm(batch, utterances, nUtterances, deviceOut, format, rowStride, stream) : done;
+}
+
+// The same of chosen rows of a caller's signal at `srcRate`: it reads no pool and needs no synthesis (ExportStage, ofSignal); the table is
+// the batch's, keyed by the source rate as well, in the shared order.
+long long speechPlayer_batch_exportResampledOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows, int srcRate,
+                                               int outRate, int zeros, double rolloff, int window, double beta, void* deviceOut, int format, long long rowStride,
+                                               void* stream)
+{
+    const char* what = "exportResampledOf";
+    if (refuse_timing_only("speechPlayer_batch_exportResampledOf")) return -1;
+    return resampled_export(what, batch, true, signal, rows, nRows,
+                            srcRate, outRate, zeros, rolloff, window, beta, deviceOut, format, rowStride, stream);
 }
 
 // ---- the PCM convolved with impulse responses (klatt_convolve.h) -------------------------------------------------------------------------
 // Host only, touches no device: the definition of include/speechPlayer_batch.h through the functions the kernel is compiled from.
-long long speechPlayer_pcmConvolve(const sample* pcm, long long length, const float* ir, long long taps, int tail, int format, void* out,
-                                   long long capacity)
+static long long convolve_statement(const char* what, const void* x, int inFormat, long long length, const float* ir, long long taps, int tail, int format, void* out,
+                                    long long capacity)
 {
-    begin_call();
-    if (length < 0 || length > kResampleMaxLength || (length > 0 && !pcm)) { set_error("pcmConvolve: length %lld (0 .. 2^44, with its samples)", length); return -1; }
-    if (format != 0 && format != 1) { set_error("pcmConvolve: format %d (0 int16, 1 float32)", format); return -1; }
+    if (signal_host_format(what, inFormat)) return -1;
+    if (length < 0 || length > kResampleMaxLength || (length > 0 && !x)) { set_error("%s: length %lld (0 .. 2^44, with its samples)", what, length); return -1; }
+    if (format != 0 && format != 1) { set_error("%s: format %d (0 int16, 1 float32)", what, format); return -1; }
     try {
         ConvPlan P;
         std::string why;
         const long long starts[2] = {0, taps};
-        if (!conv_plan(P, ir, starts, 1, tail, why)) { set_error("pcmConvolve: %s", why.c_str()); return -1; }
+        if (!conv_plan(P, ir, starts, 1, tail, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
         const long long Lout = conv_length(length, taps, tail);
         if (!out) return Lout;
-        if (capacity < Lout) { set_error("pcmConvolve: the output takes %lld elements, capacity is %lld", Lout, capacity); return -1; }
-        static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
-        return convolve_host(reinterpret_cast<const int16_t*>(pcm), length, P.taps.data(), taps, tail, format, out);
-    } catch (const std::exception& e) { set_error("pcmConvolve: %s", e.what()); return -1; }
+        if (capacity < Lout) { set_error("%s: the output takes %lld elements, capacity is %lld", what, Lout, capacity); return -1; }
+        if (signal_host_values(what, x, inFormat, length)) return -1;
+        return inFormat ? convolve_host(static_cast<const float*>(x), length, P.taps.data(), taps, tail, format, out)
+                        : convolve_host(static_cast<const int16_t*>(x), length, P.taps.data(), taps, tail, format, out);
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
+long long speechPlayer_pcmConvolve(const sample* pcm, long long length, const float* ir, long long taps, int tail, int format, void* out,
+                                   long long capacity)
+{
+    begin_call();
+    static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
+    return convolve_statement("pcmConvolve", pcm, 0, length, ir, taps, tail, format, out, capacity);
+}
+
+long long speechPlayer_signalConvolve(const void* x, int inFormat, long long length, const float* ir, long long taps, int tail, int format, void* out,
+                                      long long capacity)
+{
+    begin_call();
+    return convolve_statement("signalConvolve", x, inFormat, length, ir, taps, tail, format, out, capacity);
 }
 
 // The chosen utterances' PCM, each row through the response irOf names (klatt_convolve.h).  It reads the pool, so it is ordered as
 // speechPlayer_batch_exportPcm is (ExportStage, ofPcm), tile-wise; the rows carry their response as well.  The staging block: rows | tile
 // starts and chunk rows (packed) | the responses.  Nothing is kept on the batch: the kernel reads the responses from the call's own slot.
-long long speechPlayer_batch_exportConvolved(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const float* ir,
-                                             const long long* irStart, long long nIr, const long long* irOf, int tail, void* deviceOut, int format,
-                                             long long rowStride, void* stream)
+// ofSignal and `signal` as spectrogram_export's.
+static long long convolved_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances, long long nUtterances, const float* ir,
+                                  const long long* irStart, long long nIr, const long long* irOf, int tail, void* deviceOut, int format,
+                                  long long rowStride, void* stream)
 {
-    const char* what = "exportConvolved";
-    if (refuse_timing_only("speechPlayer_batch_exportConvolved")) return -1;
     return batch_entry(what, batch, [&](Batch* b) -> long long {
         if (tile_request(what, format, rowStride)) return -1;
         ConvPlan P;
         std::string why;
-        if (!conv_plan(P, ir, irStart, nIr, tail, why)) { set_error("exportConvolved: %s", why.c_str()); return -1; }
+        if (!conv_plan(P, ir, irStart, nIr, tail, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
         ExportSelection s;
         std::vector<ConvRow> rows;
         if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) -> long long {
                 const long long j = conv_row(P, irOf, i, why);
-                if (j < 0) { set_error("exportConvolved: %s", why.c_str()); return -1; }
-                const long long L = (long long)b->lens[(size_t)u], K = P.start[(size_t)j + 1] - P.start[(size_t)j], Lout = conv_length(L, K, tail);
-                rows.push_back(ConvRow{b->outStart[(size_t)u], L, Lout, tile_row_first(i, rowStride, before), P.start[(size_t)j], K});
+                if (j < 0) { set_error("%s: %s", what, why.c_str()); return -1; }
+                const long long L = in.len(u), K = P.start[(size_t)j + 1] - P.start[(size_t)j], Lout = conv_length(L, K, tail);
+                rows.push_back(ConvRow{in.at(u), L, Lout, tile_row_first(i, rowStride, before), P.start[(size_t)j], K});
                 return Lout;
-            })) return -1;
-        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut);
+            }, in.sig)) return -1;
+        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut, &in);
         if (elements <= 0) return elements;
         std::vector<long long> words;
         const TileTable tiles = tile_row_table(s.counts.data(), s.n, kConvolveTile, rowStride, kTimelineChunkLog2, words);
         StageBlock block;
         const int rowsAt = block.add(rows), wordsAt = block.add(words), tapsAt = block.add(P.taps);
-        ExportStage stage(b, static_cast<hipStream_t>(stream), block, nullptr, true);
+        ExportStage stage(b, static_cast<hipStream_t>(stream), block, nullptr, !in.sig, in.sig != nullptr);
         if (stage.begin()) return -1;
         ConvArgs A;
-        A.pool = b->dPcm.ptr; A.rows = stage.device<ConvRow>(rowsAt);
+        A.in = in.data; A.rows = stage.device<ConvRow>(rowsAt);
         A.tile = tile_out(stage, wordsAt, tiles, rowStride, deviceOut);
         A.taps = stage.device<float>(tapsAt);
         // Tiles cost in proportion to their response's taps: many more workgroups than the device holds at once, so that the dispatcher
         // evens out what a fixed share per workgroup would not.
-        if (launch_tiles(stage, klatt_convolve<false>, klatt_convolve<true>, format, 64, A)) return -1;
+        void (*const kernels[2][2])(ConvArgs) = {{klatt_convolve<false, int16_t>, klatt_convolve<true, int16_t>}, {klatt_convolve<false, float>, klatt_convolve<true, float>}};
+        if (launch_tiles(stage, kernels, in.format(), format, 64, A)) return -1;
         return elements;
     });
+}
+
+long long speechPlayer_batch_exportConvolved(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const float* ir,
+                                             const long long* irStart, long long nIr, const long long* irOf, int tail, void* deviceOut, int format,
+                                             long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportConvolved")) return -1;
+    return convolved_export("exportConvolved", batch, false, nullptr, utterances, nUtterances,
+                            ir, irStart, nIr, irOf, tail, deviceOut, format, rowStride, stream);
+}
+
+// The same of chosen rows of a caller's signal, irOf per output row: it reads no pool and needs no synthesis (ExportStage, ofSignal).
+long long speechPlayer_batch_exportConvolvedOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+                                               const float* ir, const long long* irStart, long long nIr, const long long* irOf, int tail, void* deviceOut,
+                                               int format, long long rowStride, void* stream)
+{
+    const char* what = "exportConvolvedOf";
+    if (refuse_timing_only("speechPlayer_batch_exportConvolvedOf")) return -1;
+    return convolved_export(what, batch, true, signal, rows, nRows,
+                            ir, irStart, nIr, irOf, tail, deviceOut, format, rowStride, stream);
 }
 
 // ---- the PCM mixed with noise and other utterances (klatt_mix.h) ----------------------------------------------------------------------------

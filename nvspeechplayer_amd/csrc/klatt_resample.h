@@ -14,8 +14,8 @@
 //                   in ascending k from +0, and res_int16 makes format 0.
 //   klatt_resample  A 256-lane workgroup takes tiles of kResampleTile consecutive outputs of one row, a tile in spans whose inputs fit
 //                   kResampleIn floats of LDS ((span - 1) down / up + 1 + taps <= kResampleIn: the whole tile wherever down / up < 6.9).
-//                   Per span: the inputs n0(first) - Z + 1 .. n0(last) + Z are loaded once, masked by 0 <= n < Lin, and converted by
-//                   res_input into LDS; lane i takes outputs i, i + 256, ... of the span, so consecutive lanes read LDS at stride
+//                   Per span: the inputs n0(first) - Z + 1 .. n0(last) + Z are loaded once, masked by 0 <= n < Lin and converted, by the
+//                   reader (klatt_tiles.h: tile_read, from int16 or float32) into LDS; lane i takes outputs i, i + 256, ... of the span, so consecutive lanes read LDS at stride
 //                   down / up (conflict-free below 2, two-way at 2) and the table at consecutive addresses: it is uploaded reordered
 //                   by use and transposed, hT[k][m mod up] = h[(m down) mod up][k] (phase has period `up` in m), 230 KB in the
 //                   largest tested case and L2-resident.  The reordering moves data, not arithmetic.  The tiles are walked and the
@@ -40,8 +40,8 @@ constexpr int kResampleMaxUp = 4096, kResampleMaxTaps = 1024;
 constexpr long long kResampleMaxTable = 1ll << 20;
 constexpr long long kResampleMaxLength = 1ll << 44;      // samples of plain PCM the host statement takes (index products stay in 64 bits)
 
-// x[n]: the sample as speechPlayer_batch_exportPcm's format 1 gives it
-KLATT_RES_HD float res_input(int s) { return (float)s / 32767.0f; }
+// x[n]: the sample as speechPlayer_batch_exportPcm's format 1 gives it (klatt_tiles.h: the reader's conversion)
+KLATT_RES_HD float res_input(int s) { return tile_x(s); }
 
 // Output m reads inputs n0 - Z + 1 .. n0 + Z against row p of the table
 KLATT_RES_HD void res_locate(long long m, int up, int down, long long& n0, int& p)
@@ -167,12 +167,14 @@ inline void res_transpose(ResPlan& P)
 }
 
 // ---- the host's statement (speechPlayer_pcmResample): the shared functions in a plain loop ------------------------------------------------
-// format 1: out is float[Lout]; format 0: int16_t[Lout].  Returns Lout.
-inline long long resample_host(const int16_t* pcm, long long length, const ResPlan& P, int format, void* out)
+// format 1: out is float[Lout]; format 0: int16_t[Lout].  Returns Lout.  In: int16_t (PCM) or float (a signal's samples).
+// Equal rates: y[m] = x[m], and format 0 of an int16 is the sample itself (res_int16(tile_x(s)) == s for all 65 536 values).
+template <typename In>
+inline long long resample_host(const In* pcm, long long length, const ResPlan& P, int format, void* out)
 {
     const long long Lout = res_length(length, P.up, P.down);
     if (P.identity) {
-        for (long long m = 0; m < Lout; ++m) { if (format) static_cast<float*>(out)[m] = res_input(pcm[m]); else static_cast<int16_t*>(out)[m] = pcm[m]; }
+        for (long long m = 0; m < Lout; ++m) res_store(out, format, m, tile_x(pcm[m]));
         return Lout;
     }
     std::vector<float> x((size_t)P.taps);
@@ -181,7 +183,7 @@ inline long long resample_host(const int16_t* pcm, long long length, const ResPl
         res_locate(m, P.up, P.down, n0, p);
         for (int k = 0; k < P.taps; ++k) {
             const long long n = n0 + k - P.Z + 1;
-            x[(size_t)k] = res_input(n >= 0 && n < length ? pcm[n] : 0);
+            x[(size_t)k] = tile_sample(pcm, n, length);
         }
         const float y = res_taps(x.data(), P.table.data() + (size_t)p * P.taps, P.taps, 1);
         res_store(out, format, m, y);
@@ -202,10 +204,10 @@ inline int res_span(const ResPlan& P)
 #if defined(__HIPCC__)
 namespace klatt {
 
-struct ResRow { long long src, len, outLen, dst; };      // pool offset and samples of a row's utterance; its outputs; its first element in the output
+struct ResRow { long long src, len, outLen, dst; };      // first element and samples of a row's input (the pool's utterance, a signal's row); its outputs; its first element in the output
 
 struct ResArgs {
-    const int16_t* pool;
+    const void* in;                      // the pool, or a signal's data: int16_t or float, as the kernel's In says
     const ResRow* rows;
     TileOut tile;
     const float* hT;                     // [taps][up]
@@ -215,7 +217,7 @@ struct ResArgs {
 static_assert((kResampleTile & (kResampleTile - 1)) == 0 && kResampleTile <= 4096, "kResampleTile is a power of two, at most 4096");
 static_assert(kResampleIn >= kResampleMaxTaps + 1 + kResampleMaxTaps / 2, "a span of one output fits at the largest ratio and filter");
 
-template <bool F32>
+template <bool F32, typename In = int16_t>
 __global__ void __launch_bounds__(256) klatt_resample(const ResArgs A)
 {
     using T = TileValue<F32>;
@@ -228,7 +230,7 @@ __global__ void __launch_bounds__(256) klatt_resample(const ResArgs A)
         tile_locate(A.tile, g, kResampleTile, r, t0);
         const ResRow row = A.rows[r];
         const int n = tile_n(A.tile.rowStride, row.outLen, t0, kResampleTile);
-        const int16_t* __restrict__ pcm = A.pool + row.src;
+        const In* __restrict__ pcm = static_cast<const In*>(A.in) + row.src;
         for (int c0 = 0; c0 < n; c0 += A.span) {
             const int cn = min(A.span, n - c0);
             const long long m0 = t0 + c0;
@@ -239,12 +241,7 @@ __global__ void __launch_bounds__(256) klatt_resample(const ResArgs A)
                 long long nB; int pB;
                 res_locate(m0, up, down, nA, pA);
                 res_locate(m0 + live - 1, up, down, nB, pB);
-                const long long lo = nA - Z + 1;
-                const int count = (int)(nB - nA) + taps;
-                for (int i = tid; i < count; i += 256) {
-                    const long long s = lo + i;
-                    xin[i] = res_input(s >= 0 && s < row.len ? (int)pcm[s] : 0);
-                }
+                tile_read<1>(xin, pcm, row.len, nA - Z + 1, (int)(nB - nA) + taps, tid);
             }
             __syncthreads();
             // ---- the outputs: lane i takes i, i + 256, ... ----
@@ -263,6 +260,26 @@ __global__ void __launch_bounds__(256) klatt_resample(const ResArgs A)
             tile_store<T>(A.tile.out, row.dst + m0, cn, staged, tid);
             // (the next span's loads and values are behind its own barriers: every lane has read `staged` before any lane passes the first)
         }
+    }
+}
+
+// Equal rates of a signal: y[m] = x[m] in the output's type, tile by tile: the reader's sample into the writer's staging
+template <bool F32, typename In>
+__global__ void __launch_bounds__(256) klatt_signal_copy(const ResArgs A)
+{
+    using T = TileValue<F32>;
+    __shared__ __attribute__((aligned(16))) T staged[kResampleTile];
+    const int tid = threadIdx.x;
+    for (long long g = blockIdx.x; g < A.tile.nTiles; g += gridDim.x) {
+        long long r, t0;
+        tile_locate(A.tile, g, kResampleTile, r, t0);
+        const ResRow row = A.rows[r];
+        const int n = tile_n(A.tile.rowStride, row.outLen, t0, kResampleTile);
+        const In* __restrict__ x = static_cast<const In*>(A.in) + row.src;
+        for (int i = tid; i < n; i += 256) staged[i] = res_value<F32>(tile_sample(x, tile_source<1>(t0, i), row.len));      // (past the row: +0, the padding)
+        __syncthreads();
+        tile_store<T>(A.tile.out, row.dst + t0, n, staged, tid);
+        __syncthreads();      // every lane has read `staged` before the next tile's values
     }
 }
 

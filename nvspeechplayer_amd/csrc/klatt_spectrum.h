@@ -21,7 +21,8 @@
 //                   The constant of the full-length radix-2 transform therefore holds:  B = (8 log2 nFft + 8) u sqrt(nFft) ||xw||_2.
 //
 //   klatt_spectrogram   One wavefront per step, four steps (consecutive in the output) per 256-lane workgroup, so that overlapping frames
-//                   come from L1/L2.  A wavefront loads its frame's int16 samples masked by 0 <= t < L, multiplies by the window and
+//                   come from L1/L2.  A wavefront loads its frame's samples, int16 or float32, masked by 0 <= t < L (klatt_tiles.h:
+//                   tile_sample), multiplies by the window and
 //                   stores z bit-reversed into its own LDS region; the passes and the unpacking run there; v[k] goes to a float array
 //                   beside it; one lane per band sums its column range from LDS; the values (after the binary64 log) are staged in LDS
 //                   and stored by 16-byte stores where the output is aligned, element by element otherwise.  LDS addresses of z are
@@ -37,6 +38,8 @@
 #include <string>
 #include <vector>
 
+#include "klatt_tiles.h"
+
 #if defined(__HIPCC__)
 #define KLATT_SPEC_HD __host__ __device__ __forceinline__
 #else
@@ -50,12 +53,9 @@ constexpr int kSpecWaves = 4;              // steps a workgroup takes at a time,
 
 struct SpecCx { float re, im; };
 
-// x[i] w[i]: the sample as speechPlayer_batch_exportPcm's format 1 gives it, times the window
-KLATT_SPEC_HD float spec_input(int s, float w)
-{
-    const float x = (float)s / 32767.0f;
-    return x * w;
-}
+// x[i] w[i]: the sample as the reader gives it (klatt_tiles.h: tile_x, tile_sample), times the window
+KLATT_SPEC_HD float spec_windowed(float x, float w) { return x * w; }
+KLATT_SPEC_HD float spec_input(int s, float w) { return spec_windowed(tile_x(s), w); }
 
 // m's lowest `bits` bits in reverse order (bits >= 1)
 KLATT_SPEC_HD uint32_t spec_reverse(uint32_t m, int bits)
@@ -185,8 +185,9 @@ inline bool spec_plan(SpecPlan& P, int nFft, const double* window, const double*
 }
 
 // ---- the host's statement (speechPlayer_pcmSpectrogram): the shared functions in plain loops --------------------------------------------
-// out[step][value] of `length` samples; returns steps * P.nOut.  z [M], v [M + 1]: the caller's scratch.
-inline long long spectrogram_host(const int16_t* pcm, long long length, const SpecPlan& P, long long hop, long long phase, double* out)
+// out[step][value] of `length` samples; returns steps * P.nOut.  In: int16_t (PCM) or float (a signal's samples).
+template <typename In>
+inline long long spectrogram_host(const In* pcm, long long length, const SpecPlan& P, long long hop, long long phase, double* out)
 {
     const int M = P.M, K = M + 1, logM = P.logN - 1;
     const long long steps = length > phase ? (length - phase + hop - 1) / hop : 0;
@@ -196,8 +197,8 @@ inline long long spectrogram_host(const int16_t* pcm, long long length, const Sp
         const long long t0 = phase + j * hop - M;
         for (int m = 0; m < M; ++m) {
             const long long ta = t0 + 2 * m, tb = ta + 1;
-            const int sa = ta >= 0 && ta < length ? pcm[ta] : 0, sb = tb >= 0 && tb < length ? pcm[tb] : 0;
-            z[spec_reverse((uint32_t)m, logM)] = SpecCx{spec_input(sa, P.window[(size_t)(2 * m)]), spec_input(sb, P.window[(size_t)(2 * m + 1)])};
+            z[spec_reverse((uint32_t)m, logM)] = SpecCx{spec_windowed(tile_sample(pcm, ta, length), P.window[(size_t)(2 * m)]),
+                                                       spec_windowed(tile_sample(pcm, tb, length), P.window[(size_t)(2 * m + 1)])};
         }
         for (int p = 0; p < logM; ++p)
             for (uint32_t b = 0; b < (uint32_t)M / 2; ++b) {
@@ -224,10 +225,10 @@ inline long long spectrogram_host(const int16_t* pcm, long long length, const Sp
 
 namespace klatt {
 
-struct SpecRow { long long src, len, steps; };      // pool offset, samples and steps of a row's utterance
+struct SpecRow { long long src, len, steps; };      // first element, samples and steps of a row's input (the pool's utterance, a signal's row)
 
 struct SpecArgs {
-    const int16_t* pool;
+    const void* in;                      // the pool, or a signal's data: int16_t or float, as the kernel's In says
     const SpecRow* rows;
     const long long *start, *chunk;      // the packed form's row table (rowStride 0)
     long long rowStride, nSteps;         // nSteps: the steps of the output, rows x rowStride or the rows' steps together
@@ -248,7 +249,7 @@ constexpr int kSpecLdsBudget = kSpecWaves * spec_lds_wave(kSpecMaxFft / 2);
 // where element i of z lives: i with its low four bits XORed by its top four (i < M = 1 << logM, logM >= 5)
 __device__ __forceinline__ uint32_t spec_slot(uint32_t i, int logM) { return i ^ (i >> (logM - 4)); }
 
-template <bool F32>
+template <bool F32, typename In = int16_t>
 __global__ void __launch_bounds__(64 * kSpecWaves) klatt_spectrogram(const SpecArgs A)
 {
     using T = typename std::conditional<F32, float, double>::type;
@@ -277,12 +278,11 @@ __global__ void __launch_bounds__(64 * kSpecWaves) klatt_spectrogram(const SpecA
         // ---- the frame, windowed, in bit-reversed order ----
         if (live) {
             const long long t0 = A.phase + j * A.hop - M;
-            const int16_t* __restrict__ pcm = A.pool + row.src;
-            for (int m = lane; m < M; m += 64) {
+            const In* __restrict__ pcm = static_cast<const In*>(A.in) + row.src;
+            for (int m = lane; m < M; m += 64) {      // (a lane takes a PAIR of samples: the reader's sample, not its run)
                 const long long ta = t0 + 2 * m, tb = ta + 1;
-                const int sa = ta >= 0 && ta < row.len ? pcm[ta] : 0, sb = tb >= 0 && tb < row.len ? pcm[tb] : 0;
                 const float2 w = reinterpret_cast<const float2*>(A.window)[m];
-                z[spec_slot(spec_reverse((uint32_t)m, logM), logM)] = SpecCx{spec_input(sa, w.x), spec_input(sb, w.y)};
+                z[spec_slot(spec_reverse((uint32_t)m, logM), logM)] = SpecCx{spec_windowed(tile_sample(pcm, ta, row.len), w.x), spec_windowed(tile_sample(pcm, tb, row.len), w.y)};
             }
         }
         // ---- the passes ----

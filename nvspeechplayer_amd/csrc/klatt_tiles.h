@@ -1,11 +1,19 @@
-// klatt_tiles.h -- the tile walk and the row writer of the exports derived from a batch's PCM (klatt_resample.h, klatt_convolve.h,
-// klatt_mix.h).  The functions marked KLATT_RES_HD are compiled for the host (plain C++17, no HIP) and for the device from the same
-// source; tests/native/check_tiles.cpp holds them to brute force under the sanitizers.
+// klatt_tiles.h -- the tile walk, the row reader and the row writer of the exports derived from a batch's PCM or from a caller's signal
+// (klatt_resample.h, klatt_convolve.h, klatt_mix.h; klatt_spectrum.h takes the reader's sample).  The functions marked KLATT_RES_HD are
+// compiled for the host (plain C++17, no HIP) and for the device from the same source; tests/native/check_tiles.cpp and check_signal.cpp
+// hold them to brute force under the sanitizers.
 //   The walk     One row per chosen utterance; a 256-lane workgroup takes tiles of `tile` consecutive outputs of one row.  Padded
 //                (rowStride > 0): every row has rowStride elements and tile_count(rowStride) tiles, tile g is tile_row's (r, j).  Packed
 //                (rowStride 0): a row has its outputs and their tiles -- none where it has none --, the row table counts TILES
 //                (klatt_export.h: tile_row_table) and tile_locate bisects it within the chunk table's bounds.  The tile at output t0
 //                holds tile_n elements, of which the first tile_live lie inside the row; the rest is padding, stored as +0.
+//   The reader   A row is `len` samples from a pointer, int16 or float32 (the pool's utterances; a signal's rows: signal_plan).  tile_sample
+//                is sample s of it as float32 -- (float)s / 32767.0f of an int16, a float32 as it is -- and +0 for every s outside
+//                0 .. len-1: the mask decides whether the address is formed at all, so what lies either side of a row -- a padded row's
+//                remainder, the next row, a guard -- is never loaded, and no sample's VALUE ever reaches an address.  A run is `count`
+//                staged values, element i standing for sample tile_source<DIR>(s0, i): upwards (the resampler's span) or downwards (the
+//                convolution's reversed inputs).  tile_read holds NO barrier.  Lane i loads element i, i + 256, ...: consecutive lanes
+//                load consecutive elements, 128 or 256 contiguous bytes per wavefront, whatever the row's first element is.
 //   The writer   `count` values staged in LDS in the output's type go to the elements e0 .. e0 + count - 1.  Lane i owns the i-th
 //                ALIGNED 16 bytes the run touches -- by ADDRESS: `mis` is what out[0] lies past a 16-byte boundary, so a buffer aligned
 //                to the element only still gets 16-byte stores -- and stores them at once where the run covers them all; the run's
@@ -43,6 +51,21 @@ KLATT_RES_HD int tile_n(long long rowStride, long long outLen, long long t0, int
 // Of the n elements from output t0, those inside the row; the rest is padding
 KLATT_RES_HD int tile_live(int n, long long outLen, long long t0) { const long long left = outLen - t0; return (int)(left < n ? (left > 0 ? left : 0) : n); }
 
+// ---- the reader ----------------------------------------------------------------------------------------------------------------------------
+// x of a sample: an int16 as speechPlayer_batch_exportPcm's format 1 gives it, a float32 as it is
+KLATT_RES_HD float tile_x(int s) { return (float)s / 32767.0f; }
+KLATT_RES_HD float tile_x(float s) { return s; }
+KLATT_RES_HD bool tile_inside(long long s, long long len) { return s >= 0 && s < len; }
+// Sample s of a row of len samples: +0 outside it, and nothing is loaded there
+template <typename In> KLATT_RES_HD float tile_sample(const In* x, long long s, long long len) { return tile_x(tile_inside(s, len) ? x[s] : (In)0); }
+// The sample that element i of a run from s0 stands for: DIR 1 upwards, -1 downwards
+template <int DIR> KLATT_RES_HD long long tile_source(long long s0, int i) { return s0 + (long long)(DIR * i); }
+// Lane `lane` of `lanes`: elements lane, lane + lanes, ... of the run's `count`
+template <int DIR, typename In> KLATT_RES_HD void tile_read_lane(float* xs, const In* x, long long len, long long s0, int count, int lane, int lanes)
+{
+    for (int i = lane; i < count; i += lanes) xs[i] = tile_sample(x, tile_source<DIR>(s0, i), len);
+}
+
 // ---- the writer ----------------------------------------------------------------------------------------------------------------------------
 // Elements past a 16-byte boundary at out[0]
 template <typename T> KLATT_RES_HD int tile_mis(const void* out) { return (int)((reinterpret_cast<uintptr_t>(out) / sizeof(T)) & (kTileLane<T> - 1)); }
@@ -67,6 +90,74 @@ template <typename T> KLATT_RES_HD void tile_store_lane(T* out, int mis, long lo
 
 }  // namespace klatt
 
+// ---- a caller's signal (speechPlayer_signal_t), as every entry point plans it on the host -----------------------------------------------------
+#include <stdio.h>
+#include <math.h>
+#include <string>
+
+namespace klatt {
+
+constexpr long long kSignalMaxLength = 1ll << 44;      // samples of a row (index products stay in 64 bits)
+constexpr long long kSignalMaxElements = 1ll << 60;    // elements of a signal, padded or packed: its bytes stay in 64 bits (need * elSize <= 2^62)
+constexpr float kSignalMaxValue = 65536.0f;            // |x| <= 2^16: the bound of the bit-for-bit promise (the noise bank's)
+
+// The rows of a signal: row r is len(r) samples from element at(r); `need` elements hold them all
+struct SignalPlan {
+    int format = 0, elSize = 2;
+    long long nRows = 0, rowStride = 0, need = 0;
+    const long long* extent = nullptr;
+    long long at(long long r) const { return rowStride > 0 ? r * rowStride : extent[r]; }
+    long long len(long long r) const { return rowStride > 0 ? extent[r] : extent[r + 1] - extent[r]; }
+};
+
+// The plan of a signal's table, or false with `why` set (without the entry point's prefix): every refusal that needs no device.
+inline bool signal_plan(SignalPlan& P, int format, long long nRows, long long rowStride, const long long* extent, std::string& why)
+{
+    char buf[200];
+    if (format != 0 && format != 1) { snprintf(buf, sizeof buf, "signal format %d (0 int16, 1 float32)", format); why = buf; return false; }
+    if (nRows < 0) { snprintf(buf, sizeof buf, "signal nRows %lld", nRows); why = buf; return false; }
+    if (rowStride < 0) { snprintf(buf, sizeof buf, "signal rowStride %lld", rowStride); why = buf; return false; }
+    if (nRows > 0 && !extent) { why = "signal without extent (the rows' lengths or offsets, on the host)"; return false; }
+    P.format = format; P.elSize = format ? 4 : 2; P.nRows = nRows; P.rowStride = rowStride; P.extent = extent; P.need = 0;
+    if (nRows == 0) return true;
+    if (rowStride > 0) {
+        if ((unsigned __int128)nRows * (unsigned __int128)rowStride > (unsigned __int128)kSignalMaxElements) {
+            snprintf(buf, sizeof buf, "signal of %lld rows of rowStride %lld (at most 2^60 elements)", nRows, rowStride); why = buf; return false;
+        }
+        for (long long r = 0; r < nRows; ++r) {
+            const long long L = extent[r];
+            if (L < 0 || L > rowStride) { snprintf(buf, sizeof buf, "signal extent[%lld] = %lld: row %lld has 0 .. rowStride = %lld samples", r, L, r, rowStride); why = buf; return false; }
+            if (L > kSignalMaxLength) { snprintf(buf, sizeof buf, "signal extent[%lld] = %lld: row %lld has more than 2^44 samples", r, L, r); why = buf; return false; }
+            if (L > 0 && r * rowStride + L > P.need) P.need = r * rowStride + L;
+        }
+        return true;
+    }
+    if (extent[0] != 0) { snprintf(buf, sizeof buf, "signal extent[0] = %lld (row 0 of a packed signal starts at 0)", extent[0]); why = buf; return false; }
+    for (long long r = 0; r < nRows; ++r) {
+        const long long a = extent[r], b = extent[r + 1];
+        if (b < a) { snprintf(buf, sizeof buf, "signal extent[%lld] = %lld is below extent[%lld] = %lld: row %lld ends before it starts", r + 1, b, r, a, r); why = buf; return false; }
+        if (b - a > kSignalMaxLength) { snprintf(buf, sizeof buf, "signal extent[%lld] = %lld: row %lld has more than 2^44 samples", r + 1, b, r); why = buf; return false; }
+        if (b > kSignalMaxElements) {      // (rows of 2^44 samples each may add up to anything: the bytes of `need` must not wrap)
+            snprintf(buf, sizeof buf, "signal extent[%lld] = %lld: row %lld ends past 2^60 elements, the most a signal has", r + 1, b, r); why = buf; return false;
+        }
+    }
+    P.need = extent[nRows];
+    return true;
+}
+
+// The values a host statement takes: finite, at most 2^16 in magnitude; or false with the first other sample in `why`
+inline bool signal_values(const float* x, long long length, std::string& why)
+{
+    for (long long n = 0; n < length; ++n)
+        if (!(fabsf(x[n]) <= kSignalMaxValue)) {      // (a NaN fails the comparison)
+            char buf[160];
+            snprintf(buf, sizeof buf, "sample %lld is %g (finite, at most 2^16 in magnitude)", n, (double)x[n]); why = buf; return false;
+        }
+    return true;
+}
+
+}  // namespace klatt
+
 #if defined(__HIPCC__)      // ---- the device ----
 #include "klatt_timeline.h"
 
@@ -79,6 +170,12 @@ __device__ __forceinline__ void tile_locate(const TileOut& O, long long g, int t
     if (O.rowStride > 0) tile_row(g, O.tilesPerRow, r, j);
     else { const long long c = g >> kTimelineChunkLog2; packed_locate(g, O.start, O.chunk[c], O.chunk[c + 1] + 1, r, j); }
     t0 = j * tile;
+}
+
+// The workgroup's loads of a run
+template <int DIR, typename In> __device__ __forceinline__ void tile_read(float* xs, const In* __restrict__ x, long long len, long long s0, int count, int tid)
+{
+    tile_read_lane<DIR>(xs, x, len, s0, count, tid, 256);
 }
 
 // The workgroup's stores of a run

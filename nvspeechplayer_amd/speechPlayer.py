@@ -818,6 +818,132 @@ def pcmConvolve(pcm, ir, tail=True, dtype=np.float32):
     return out
 
 
+SIGNAL_MAX_LENGTH = 1 << 44      # kSignalMaxLength of csrc/klatt_tiles.h: samples of one row
+# speechPlayer_signal_t (include/speechPlayer_batch.h)
+_signalDtype = np.dtype([("data", np.uint64), ("format", np.int32), ("reserved", np.int32), ("nRows", np.int64), ("rowStride", np.int64),
+                         ("extent", np.uint64)], align=True)
+assert _signalDtype.itemsize == 40
+
+
+def check_signal_request(signal, device=None, what="signal"):
+    """The argument checks of the `signal=` of BatchPlayer.spectrogramTensor, resampledTensor and convolvedTensor that need no GPU:
+    `signal` is the (tensor, second) pair the exports return -- a contiguous torch tensor of dtype torch.int16 or torch.float32, 2-D
+    [n, width] with `second` the n row lengths (0 .. width each), or 1-D with `second` the n + 1 ascending offsets from 0 (the last at
+    most the tensor's length) --, rows of at most 2^44 samples, and (device not None) on CUDA device `device`.  Raises ValueError or
+    TypeError.  Returns (the tensor, its format: 0 int16 / 1 float32, n, rowStride: the width or 0, `second` as an int64 array, the n
+    row lengths)."""
+    import torch
+    if not isinstance(signal, (tuple, list)) or len(signal) != 2:
+        raise TypeError("%s: a signal is the (tensor, lengths or offsets) pair an export returns, not %s" % (what, type(signal).__name__))
+    tensor, second = signal
+    if not isinstance(tensor, torch.Tensor):
+        raise TypeError("%s: the samples must be a torch tensor, not %s" % (what, type(tensor).__name__))
+    if tensor.dtype not in (torch.int16, torch.float32):
+        raise TypeError("%s: the samples must be torch.int16 or torch.float32, not %s" % (what, tensor.dtype))
+    if tensor.dim() not in (1, 2):
+        raise TypeError("%s: the samples must be [n, width] (padded) or one-dimensional (packed), not %s" % (what, list(tensor.shape)))
+    if second is None or isinstance(second, str):
+        raise TypeError("%s: the row lengths (padded) or offsets (packed) are missing" % what)
+    try:
+        ext = np.asarray(second.detach().cpu().numpy() if hasattr(second, "detach") else second)
+    except Exception:
+        raise TypeError("%s: the row lengths or offsets are not an array" % what)
+    if ext.size == 0:
+        ext = ext.astype(np.int64)
+    if ext.dtype.kind not in "iu":
+        raise TypeError("%s: the row lengths or offsets must be integers, not %s" % (what, ext.dtype))
+    if ext.ndim != 1:
+        raise ValueError("%s: the row lengths or offsets must be one-dimensional, not %s" % (what, list(ext.shape)))
+    ext = np.ascontiguousarray(ext.astype(np.int64))
+    if not tensor.is_contiguous():
+        raise ValueError("%s: the samples must be contiguous" % what)
+    if tensor.dim() == 2:
+        n, stride = int(tensor.shape[0]), int(tensor.shape[1])
+        if len(ext) != n:
+            raise ValueError("%s: %d row lengths for %d rows" % (what, len(ext), n))
+        bad = np.flatnonzero((ext < 0) | (ext > stride))
+        if len(bad):
+            raise ValueError("%s: row %d has %d samples (0 .. the width, %d)" % (what, bad[0], ext[bad[0]], stride))
+        lens = ext
+        if stride == 0:      # rows of nothing: rowStride 0 would mean packed
+            ext, stride = np.zeros(n + 1, np.int64), 0
+    else:
+        if len(ext) < 1:
+            raise ValueError("%s: a packed signal comes with its n + 1 offsets" % what)
+        n, stride = len(ext) - 1, 0
+        if ext[0] != 0:
+            raise ValueError("%s: row 0 of a packed signal starts at 0, not %d" % (what, ext[0]))
+        lens = np.diff(ext)
+        bad = np.flatnonzero(lens < 0)
+        if len(bad):
+            raise ValueError("%s: row %d ends (%d) before it starts (%d)" % (what, bad[0], ext[bad[0] + 1], ext[bad[0]]))
+        if ext[-1] > tensor.shape[0]:
+            raise ValueError("%s: the rows take %d samples, the tensor has %d" % (what, ext[-1], tensor.shape[0]))
+    bad = np.flatnonzero(lens > SIGNAL_MAX_LENGTH)
+    if len(bad):
+        raise ValueError("%s: row %d has more than 2^44 samples" % (what, bad[0]))
+    if device is not None and (not tensor.is_cuda or tensor.device.index != int(device)):
+        raise ValueError("%s: the samples must be on the batch's device, cuda:%d, not %s" % (what, int(device), tensor.device))
+    return tensor, 1 if tensor.dtype == torch.float32 else 0, n, stride, ext, np.ascontiguousarray(lens.astype(np.int64))
+
+
+def _signal_samples(x, what):
+    s = x if isinstance(x, np.ndarray) else None
+    if s is None or s.ndim != 1 or s.dtype not in (np.int16, np.float32):
+        raise TypeError("%s: the samples must be a one-dimensional int16 or float32 array, not %s" % (
+            what, "%s %s" % (s.dtype, list(s.shape)) if s is not None else type(x).__name__))
+    return np.ascontiguousarray(s), 1 if s.dtype == np.float32 else 0
+
+
+def signalSpectrogram(x, nFft=1024, hop=256, phase=0, window=None, bank=None, power=2, log=None, floor=1e-10):
+    """pcmSpectrogram on a signal's row (speechPlayer_signalSpectrogram; no GPU): x is a one-dimensional int16 array (pcmSpectrogram's
+    bits) or a float32 one, taken as it is -- every sample finite and at most 2^16 in magnitude.  -> float64 [steps, bands]: the
+    statement BatchPlayer.spectrogramTensor(signal=...) is held to."""
+    import torch
+    s, inFormat = _signal_samples(x, "signalSpectrogram")
+    nFft, hop, phase, window, bank, bands, power, scale, floor, _ = check_spectrogram_request(nFft, hop, phase, window, bank, power, log, floor,
+                                                                                             torch.float64, "signalSpectrogram")
+    steps = (len(s) - phase + hop - 1) // hop if len(s) > phase else 0
+    out = np.zeros((steps, bands), np.float64)
+    got = _native.load().speechPlayer_signalSpectrogram(s.ctypes.data if len(s) else None, inFormat, len(s), nFft, hop, phase, _ptr(window), _ptr(bank),
+                                                        bands if bank is not None else 0, power, scale, floor, out.ctypes.data if out.size else None)
+    if got < 0:
+        raise RuntimeError(_native.last_error())
+    assert got == out.size, (got, out.size)
+    return out
+
+
+def signalResample(x, srcRate, dstRate, zeros=6, rolloff=0.99, window="hann", beta=None, dtype=np.float32):
+    """pcmResample on a signal's row (speechPlayer_signalResample; no GPU): x as signalSpectrogram's.  -> float32 or int16
+    [ceil(len * up / down)]; equal rates give the samples themselves.  The statement BatchPlayer.resampledTensor(signal=...) is held to."""
+    s, inFormat = _signal_samples(x, "signalResample")
+    srcRate, dstRate, zeros, rolloff, win, beta, fmt, up, down, _ = check_resample_request(srcRate, dstRate, zeros, rolloff, window, beta, dtype,
+                                                                                          "signalResample")
+    n = (len(s) * up + down - 1) // down
+    out = np.zeros(n, np.float32 if fmt else np.int16)
+    got = _native.load().speechPlayer_signalResample(s.ctypes.data if len(s) else None, inFormat, len(s), srcRate, dstRate, zeros, rolloff, win, beta, fmt,
+                                                     out.ctypes.data if n else None, n)
+    if got < 0:
+        raise RuntimeError(_native.last_error())
+    assert got == n, (got, n)
+    return out
+
+
+def signalConvolve(x, ir, tail=True, dtype=np.float32):
+    """pcmConvolve on a signal's row (speechPlayer_signalConvolve; no GPU): x as signalSpectrogram's.  -> float32 or int16, len(x) +
+    len(ir) - 1 values (tail) or len(x).  The statement BatchPlayer.convolvedTensor(signal=...) is held to."""
+    s, inFormat = _signal_samples(x, "signalConvolve")
+    h, start, _, tail, fmt = check_convolve_request(ir, None, 1, tail, dtype, "signalConvolve")
+    n = len(s) + len(h) - 1 if tail else len(s)
+    out = np.zeros(n, np.float32 if fmt else np.int16)
+    got = _native.load().speechPlayer_signalConvolve(s.ctypes.data if len(s) else None, inFormat, len(s), h.ctypes.data, len(h), tail, fmt,
+                                                     out.ctypes.data if n else None, n)
+    if got < 0:
+        raise RuntimeError(_native.last_error())
+    assert got == n, (got, n)
+    return out
+
+
 MIX_TILE = 1024                  # kMixTile of csrc/klatt_mix.h: consecutive outputs of one row a workgroup takes at a time
 MIX_MAX_TERMS = 64               # kMixMaxTerms: of one row
 MIX_MAX_CALL_TERMS = 1 << 22     # kMixMaxCallTerms: of one call
@@ -1139,6 +1265,19 @@ class BatchPlayer(object):
         lens = self._lengths()[idx]
         return sel, n, np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
 
+    def _signal(self, what, signal, utterances):
+        """A signal= argument (check_signal_request) and the rows chosen from it: -> (the speechPlayer_signal_t record and what it points
+        to -- keep it until the call has returned --, the chosen rows or None, their number, their lengths)."""
+        tensor, fmt, rows, stride, extent, lens = check_signal_request(signal, self.device, what)
+        sel = None if utterances is None else _host_array(utterances, np.int64).reshape(-1)
+        n = rows if sel is None else len(sel)
+        idx = np.arange(n) if sel is None else sel
+        if n and (idx.min() < 0 or idx.max() >= rows):
+            raise ValueError("%s: row numbers must lie in [0, %d)" % (what, rows))
+        rec = np.zeros(1, _signalDtype)
+        rec["data"], rec["format"], rec["nRows"], rec["rowStride"], rec["extent"] = tensor.data_ptr(), fmt, rows, stride, extent.ctypes.data
+        return (rec, tensor, extent), sel, n, lens[idx]
+
     def _export_rows(self, counts, tail_shape, dtype, padded, call, always=False):
         """The output of an export of len(counts) rows of counts[i] entries of shape tail_shape: [n, most, ...] (padded) or [total, ...],
         filled by call(pointer, rowStride, elements, stream) on torch's current stream -- not made for an empty tensor unless `always`
@@ -1237,7 +1376,7 @@ class BatchPlayer(object):
         return self._export_rows(steps, (len(ks), len(freqs)), torch.float32 if fmt else torch.float64, padded, call)
 
     def spectrogramTensor(self, nFft=1024, hop=256, phase=0, window=None, bank=None, power=2, log=None, floor=1e-10, utterances=None, dtype=None,
-                          padded=True):
+                          padded=True, signal=None):
         """The STFT or band (mel) spectrogram of the batch's PCM as a torch tensor on the batch's device
         (speechPlayer_batch_exportSpectrogram), filled on torch's current stream behind the synthesis without a host wait:
         -> (spectrogram, steps).  Step j of an utterance is centred on its sample phase + j * hop -- the grid of trackTensor, row for row
@@ -1246,9 +1385,20 @@ class BatchPlayer(object):
         factor of log10, applied to max(value, floor).  utterances, dtype and padded as trackTensor's: spectrogram is
         [n, most steps, bands], zero past each utterance's end, and steps the n step counts; or [total steps, bands] and the n + 1
         offsets (int64 CPU tensors).  The batch must have been synthesised since it was set; pcmSpectrogram is the same definition on
-        the host."""
+        the host.
+        signal: the (tensor, lengths or offsets) pair another export returned (check_signal_request), read in place of the batch's PCM
+        (speechPlayer_batch_exportSpectrogramOf): `utterances` then chooses rows of the signal, the steps are those of the signal's
+        lengths, no synthesis is needed and signalSpectrogram is the host's statement.  The signal is read on torch's current stream."""
         import torch
         nFft, hop, phase, window, bank, bands, power, scale, floor, fmt = check_spectrogram_request(nFft, hop, phase, window, bank, power, log, floor, dtype)
+        if signal is not None:
+            sig, sel, n, lens = self._signal("spectrogramTensor", signal, utterances)
+            steps = np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
+
+            def call_of(out, stride, numel, stream):
+                return self._dll.speechPlayer_batch_exportSpectrogramOf(self._h, sig[0].ctypes.data, _ptr(sel), n, nFft, hop, phase, _ptr(window), _ptr(bank),
+                                                                        bands if bank is not None else 0, power, scale, floor, out, fmt, stride, stream)
+            return self._export_rows(steps, (bands,), torch.float32 if fmt else torch.float64, padded, call_of)
         sel, n, steps = self._steps("spectrogramTensor", utterances, hop, phase)
 
         def call(out, stride, numel, stream):
@@ -1256,15 +1406,30 @@ class BatchPlayer(object):
                                                                   bands if bank is not None else 0, power, scale, floor, out, fmt, stride, stream)
         return self._export_rows(steps, (bands,), torch.float32 if fmt else torch.float64, padded, call)
 
-    def resampledTensor(self, rate, zeros=6, rolloff=0.99, window="hann", beta=None, utterances=None, dtype=None, padded=True):
+    def resampledTensor(self, rate, zeros=6, rolloff=0.99, window="hann", beta=None, utterances=None, dtype=None, padded=True, signal=None,
+                        signalRate=None):
         """The batch's PCM at `rate` Hz as a torch tensor on the batch's device (speechPlayer_batch_exportResampled), filled on torch's
         current stream behind the synthesis without a host wait: -> (pcm, lengths).  A polyphase windowed-sinc resampler: `zeros` zero
         crossings of the sinc either side, cut-off `rolloff` times the lower of the two Nyquist frequencies, window "hann" or "kaiser"
         (beta: None is 8.6).  Output sample m of an utterance lies at its source sample m * down / up; an utterance of L samples gives
         ceil(L * up / down).  utterances, padded and the (pcm, lengths) pair as pcmTensor's; dtype torch.float32 (default) or
         torch.int16 (clipped, rounded to nearest even).  rate == sampleRate gives pcmTensor's values.  The batch must have been
-        synthesised since it was set; pcmResample is the same definition on the host."""
+        synthesised since it was set; pcmResample is the same definition on the host.
+        signal: the (tensor, lengths or offsets) pair another export returned (check_signal_request), read in place of the batch's PCM
+        (speechPlayer_batch_exportResampledOf) at signalRate Hz (None: the batch's rate): `utterances` then chooses rows of the signal, no
+        synthesis is needed, equal rates give the signal's samples and signalResample is the host's statement."""
         import torch
+        if signal is not None:
+            src, rate, zeros, rolloff, win, beta, fmt, up, down, _ = check_resample_request(self.sampleRate if signalRate is None else signalRate, rate, zeros,
+                                                                                            rolloff, window, beta, dtype)
+            sig, sel, n, lens = self._signal("resampledTensor", signal, utterances)
+
+            def call_of(out, stride, numel, stream):
+                return self._dll.speechPlayer_batch_exportResampledOf(self._h, sig[0].ctypes.data, _ptr(sel), n, src, rate, zeros, rolloff, win, beta, out, fmt,
+                                                                      stride, stream)
+            return self._export_rows((lens * up + down - 1) // down, (), torch.float32 if fmt else torch.int16, padded, call_of)
+        if signalRate is not None:
+            raise ValueError("resampledTensor: signalRate comes with a signal")
         _, rate, zeros, rolloff, win, beta, fmt, up, down, _ = check_resample_request(self.sampleRate, rate, zeros, rolloff, window, beta, dtype)
         sel, n, idx = self._selection("resampledTensor", utterances)
         lens = (self._lengths()[idx].astype(np.int64) * up + down - 1) // down
@@ -1273,7 +1438,7 @@ class BatchPlayer(object):
             return self._dll.speechPlayer_batch_exportResampled(self._h, _ptr(sel), n, rate, zeros, rolloff, win, beta, out, fmt, stride, stream)
         return self._export_rows(lens, (), torch.float32 if fmt else torch.int16, padded, call)
 
-    def convolvedTensor(self, irs, irOf=None, tail=True, utterances=None, dtype=None, padded=True):
+    def convolvedTensor(self, irs, irOf=None, tail=True, utterances=None, dtype=None, padded=True, signal=None):
         """The batch's PCM convolved with impulse responses as a torch tensor on the batch's device
         (speechPlayer_batch_exportConvolved), filled on torch's current stream behind the synthesis without a host wait:
         -> (pcm, lengths).  irs: one 1-D array of float32 taps (a room, a channel, a microphone) or a list of them; irOf: the response of
@@ -1281,8 +1446,20 @@ class BatchPlayer(object):
         a row of L samples and K taps gives L + K - 1 values (the full convolution) or, tail=False, the first L, on the grid of the
         other exports.  utterances, padded and the (pcm, lengths) pair as pcmTensor's; dtype torch.float32 (default) or torch.int16
         (clipped, rounded to nearest even).  The batch must have been synthesised since it was set; pcmConvolve is the same definition
-        on the host, which the device equals bit for bit."""
+        on the host, which the device equals bit for bit.
+        signal: the (tensor, lengths or offsets) pair another export returned (check_signal_request), read in place of the batch's PCM
+        (speechPlayer_batch_exportConvolvedOf): `utterances` then chooses rows of the signal, irOf stays per output row, no synthesis is
+        needed and signalConvolve is the host's statement."""
         import torch
+        if signal is not None:
+            sig, sel, n, lens = self._signal("convolvedTensor", signal, utterances)
+            h, start, of, tail, fmt = check_convolve_request(irs, irOf, n, tail, dtype)
+            taps = np.diff(start)[of if of is not None else np.zeros(n, np.int64)]
+
+            def call_of(out, stride, numel, stream):
+                return self._dll.speechPlayer_batch_exportConvolvedOf(self._h, sig[0].ctypes.data, _ptr(sel), n, h.ctypes.data, start.ctypes.data, len(start) - 1,
+                                                                      _ptr(of), tail, out, fmt, stride, stream)
+            return self._export_rows(lens + (taps - 1 if tail else 0), (), torch.float32 if fmt else torch.int16, padded, call_of)
         sel, n, idx = self._selection("convolvedTensor", utterances)
         h, start, of, tail, fmt = check_convolve_request(irs, irOf, n, tail, dtype)
         taps = np.diff(start)[of if of is not None else np.zeros(n, np.int64)]
