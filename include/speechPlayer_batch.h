@@ -562,11 +562,12 @@ long long speechPlayer_batch_exportConvolved(speechPlayer_batch_t batch, const l
  * csrc/klatt_convolve.h), which the host and the device compile from one source; speechPlayer_pcmMix executes them in a plain loop.
  * The result is a function of the batch's PCM: it needs a synthesis launch, depends on the mode (in MODE_FAST on whatever that mode's
  * tolerance allows) and is ordered as speechPlayer_batch_exportPcm is.
- * Out of scope: live handles; NodePlayer, which reaches the export through speechPlayer_node_part; mixing onto a convolved or resampled
- * signal -- an SNR needs the row's power, which for a float32 signal has no order-free exact definition as the pool's integer sum is:
- * until host and device share a fixed reduction shape the mix heads the chain (its output goes into the exports of a signal, below), or
- * the noise bed is made with speechGain = 0 and added by the caller; segment or active-speech (VAD-weighted) levels; loudness weighting; random
- * draws of any kind -- clips, offsets and levels are the caller's.
+ * Mixing onto a convolved or resampled signal -- noise at an SNR against the reverberant speech -- is speechPlayer_batch_exportMixedOf,
+ * below: an SNR needs the row's power, which for a float32 signal has no order-free exact definition as the pool's integer sum is, so
+ * host and device share a fixed reduction shape (csrc/klatt_sigpower.h).
+ * Out of scope: a term from a different signal, or from the pool in a mix onto a signal; live handles; NodePlayer, which reaches the
+ * export through speechPlayer_node_part; segment or active-speech (VAD-weighted) levels; loudness weighting; random draws of any kind --
+ * clips, offsets and levels are the caller's.
  */
 typedef struct {
 	int kind;            /* 0 a clip of the noise bank, 1 an utterance of the batch */
@@ -621,10 +622,11 @@ long long speechPlayer_batch_exportMixed(speechPlayer_batch_t batch, const long 
  * length. */
 long long speechPlayer_pcmMix(const sample* pcm, long long length, float speechGain, const speechPlayer_mixSource_t* sources, long long nSources,
 	const speechPlayer_mixTerm_t* terms, long long nTerms, float* gains, int format, void* out, long long capacity);
-/* The exports of a signal: the spectrogram, the resampler and the convolution on rows of samples in the CALLER's device memory, in place
- * of the batch's pool -- what speechPlayer_batch_exportPcm, exportMixed, exportConvolved and exportResampled return, so that the output of
- * one goes into the next: the log-mel of noisy, reverberant speech at 16 kHz is exportMixed, exportConvolvedOf, exportResampledOf,
- * exportSpectrogramOf.
+/* The exports of a signal: the spectrogram, the resampler, the convolution, the mix and the power on rows of samples in the CALLER's
+ * device memory, in place of the batch's pool -- what speechPlayer_batch_exportPcm, exportMixed, exportConvolved and exportResampled
+ * return, so that the output of one goes into the next: the log-mel of reverberant speech in noise at 16 kHz is exportConvolved,
+ * exportMixedOf, exportResampledOf, exportSpectrogramOf -- the speech through a room first, then the noise at an SNR measured against
+ * the reverberant speech.
  * A signal is nRows rows of int16 or float32 samples from `data`.  Padded (rowStride > 0): row r starts at element r * rowStride and has
  * extent[r] <= rowStride samples.  Packed (rowStride 0): extent holds nRows + 1 ascending offsets from 0, row r is the elements
  * extent[r] .. extent[r + 1] - 1.  extent is HOST memory, read during the call.
@@ -649,8 +651,9 @@ long long speechPlayer_pcmMix(const sample* pcm, long long length, float speechG
  * at 0 or that decrease; a length above 2^44; data that is not device memory of the batch's device, misaligned to its element, or
  * whose allocation is smaller than the rows need (a signal whose rows are all empty is not read and may have no data); a row number
  * outside the signal; an output that overlaps the signal; srcRate <= 0.  The message names the row.
- * Out of scope: a signal as the speech row of exportMixed (see there); live handles; NodePlayer beyond speechPlayer_node_part; a fused
- * kernel for the chain; float64 or float16 signals; label grids at a resampled rate. */
+ * Out of scope: in a mix onto a signal, a term from a different signal or from the pool; live handles; NodePlayer beyond
+ * speechPlayer_node_part; active-speech levels and loudness weighting; a fused kernel for the chain; float64 or float16 signals; label
+ * grids at a resampled rate. */
 typedef struct {
 	const void* data;         /* device memory of the batch's device, aligned to its element */
 	int format;               /* 0 int16: x = (float)s / 32767.0f, as the pool's samples; 1 float32: x as it is */
@@ -669,6 +672,47 @@ long long speechPlayer_batch_exportResampledOf(speechPlayer_batch_t batch, const
 long long speechPlayer_batch_exportConvolvedOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
 	const float* ir, const long long* irStart, long long nIr, const long long* irOf, int tail, void* deviceOut, int format, long long rowStride,
 	void* stream);
+/*
+ * The power of a signal's row and the mix onto a signal.  For a row of L samples:
+ *   int16     (format 0) the pool's definition: S = sum s^2 as an exact unsigned 64-bit integer, P = (double)S / (double)L / 1073676289.0.
+ *             The pool handed back as an int16 signal gives the pool's bits
+ *   float32   (format 1) sq(x) = (double)x * (double)x -- exact in binary64, so that fusing it into an FMA changes no bit.  Samples at
+ *             index L or beyond are +0.  A BLOCK is kSigPowerBlock = 2048 consecutive samples, 256 LEAVES of 8 consecutive samples:
+ *             leaf = ((((((sq0 + sq1) + sq2) + ...) + sq7), ascending; the block sum is the balanced binary tree over the 256 leaves in
+ *             natural order, t[i] = t[2i] + t[2i+1], eight levels.  Q is the ascending sum of the block sums from +0.0; P = Q / (double)L,
+ *             and P = 0 for L = 0
+ *   Lemma     every addend is >= +0, and adding +0 to a non-negative binary64 changes no bit: absent samples, absent leaves and a
+ *             short last block may be taken as zeros, and nothing past a row is loaded to fill them
+ *   bound     the signal contract's: finite samples of magnitude at most 2^16; no sum overflows.  Outside it the bits are unspecified
+ * Both are WHOLE-SIGNAL mean squares, silences included.  The definition is the function bodies of csrc/klatt_sigpower.h, which the host
+ * and the device compile from one source; its error against the exact mean square is at most (16 + blocks) * 2^-53 * P.
+ * speechPlayer_batch_exportPowerOf: P of the chosen rows, one binary64 per row, into caller-owned device memory: the contract of the
+ * exports of a signal above over one element per row (the output may not overlap the signal).
+ * speechPlayer_batch_exportMixedOf is speechPlayer_batch_exportMixed with "the utterance's int16 PCM" replaced by "the row's samples":
+ * kind 0 is a clip of the batch's noise bank, as there, and follows the bank's order; kind 1 names A ROW OF THE SAME SIGNAL -- any row,
+ * chosen or not, the row's own included --, whose power is the one above; Ps is the row's own power at gain 1; the output has the row's L
+ * samples.  `rows` / `nRows` play the part `utterances` plays; termStart and speechGain are per OUTPUT row.  Its contract is that of the
+ * exports of a signal: the caller orders the producer, it reads no pool and waits for no launch, works on a batch never set, takes a slot
+ * of the sixteen in flight, and neither the output nor deviceGains may overlap the signal.  Only rows named by an SNR term (or by
+ * exportPowerOf) are powered, each distinct row once per call; the block partials, 8 bytes per 2048 powered samples, live in the call's
+ * staging slot, and a call whose powered rows take more than kSigPowerMaxBlocks = 2^24 blocks is refused.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: what speechPlayer_batch_exportMixed refuses (but a batch not synthesised),
+ * with "source ... is not a row of the signal" for a kind-1 source outside it; what the exports of a signal refuse; the cap above.
+ */
+long long speechPlayer_batch_exportPowerOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	void* deviceOut, void* stream);
+long long speechPlayer_batch_exportMixedOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	const speechPlayer_mixTerm_t* terms, const long long* termStart, const float* speechGain, void* deviceGains, void* deviceOut, int format,
+	long long rowStride, void* stream);
+/* Host only, touch no device: the statements the two are held to bit for bit.  speechPlayer_signalPower: P of `length` samples (at most
+ * 2^33), int16 (inFormat 0) or float32 (inFormat 1), into *power; returns 0, or -1: an unknown inFormat, a bad length, a NULL power, a
+ * float32 sample that is not finite or above 2^16 in magnitude.  speechPlayer_signalMix is speechPlayer_pcmMix on a signal's row: a
+ * kind-1 term names a source of either format, a row, whose power is the one above; a kind-0 term names a float32 source, a clip
+ * (1 .. 2^31 - 1 values, the clip's power).  Beyond speechPlayer_pcmMix's refusals it refuses an unknown inFormat and a float32 sample of
+ * x outside the bound.  With int16 inputs throughout it equals speechPlayer_pcmMix bit for bit. */
+int speechPlayer_signalPower(const void* x, int inFormat, long long length, double* power);
+long long speechPlayer_signalMix(const void* x, int inFormat, long long length, float speechGain, const speechPlayer_mixSource_t* sources, long long nSources,
+	const speechPlayer_mixTerm_t* terms, long long nTerms, float* gains, int format, void* out, long long capacity);
 /* Host only, touch no device: speechPlayer_pcmSpectrogram, pcmResample and pcmConvolve on `length` samples of a signal's row, int16
  * (inFormat 0: their bits exactly) or float32 (inFormat 1) -- the same function bodies, and the statements the device is held to.  They
  * have the data, so beyond the refusals of speechPlayer_pcm* they refuse an unknown inFormat and a float32 sample that is not finite or

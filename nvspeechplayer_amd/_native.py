@@ -67,6 +67,7 @@ EXPORTS = [
     "speechPlayer_batch_exportMixed",
     "speechPlayer_batch_exportSpectrogramOf", "speechPlayer_batch_exportResampledOf", "speechPlayer_batch_exportConvolvedOf",
     "speechPlayer_signalSpectrogram", "speechPlayer_signalResample", "speechPlayer_signalConvolve",
+    "speechPlayer_batch_exportPowerOf", "speechPlayer_batch_exportMixedOf", "speechPlayer_signalPower", "speechPlayer_signalMix",
     "speechPlayer_planTrackKinds",
 ]
 
@@ -420,6 +421,14 @@ def load():
     L.speechPlayer_signalResample.argtypes = [vp, i32, i64, i32, i32, i32, f64, i32, f64, i32, vp, i64]
     L.speechPlayer_signalConvolve.restype = i64
     L.speechPlayer_signalConvolve.argtypes = [vp, i32, i64, vp, i64, i32, i32, vp, i64]
+    L.speechPlayer_batch_exportPowerOf.restype = i64
+    L.speechPlayer_batch_exportPowerOf.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.speechPlayer_batch_exportMixedOf.restype = i64
+    L.speechPlayer_batch_exportMixedOf.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, i64, vp]
+    L.speechPlayer_signalPower.restype = i32
+    L.speechPlayer_signalPower.argtypes = [vp, i32, i64, vp]
+    L.speechPlayer_signalMix.restype = i64
+    L.speechPlayer_signalMix.argtypes = [vp, i32, i64, ctypes.c_float, vp, i64, vp, i64, vp, i32, vp, i64]
     _lib = L
     return L
 

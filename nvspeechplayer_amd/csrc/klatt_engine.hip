@@ -840,7 +840,7 @@ struct ExportStage {
     {
         slot = ofPcm ? &b->exportSlot[b->exportNext++ % Batch::kExportSlots] : &b->trackSlot[b->trackNext++ % Batch::kExportSlots];
         if (slot->used) { HIP_TRY(hipEventSynchronize(slot->done)); slot->used = false; }
-        if (slot->host.ensure(block.bytes()) || slot->dev.reserve(block.bytes())) return -1;
+        if (slot->host.ensure(block.upload_bytes()) || slot->dev.reserve(block.bytes())) return -1;      // (reserved sections at the block's end are device scratch alone)
         if (grow()) return -1;
         if (ofPcm) {
             HIP_TRY(hipEventRecord(b->pcmReady, b->stream));
@@ -5123,7 +5123,7 @@ long long speechPlayer_batch_exportStems(speechPlayer_batch_t batch, const long 
     });
 }
 
-// ---- what the spectrogram, resampled and convolved exports read ----------------------------------------------------------------------------
+// ---- what the spectrogram, resampled, convolved, mixed and power exports read ----------------------------------------------------------------------------
 // The batch's pool, a row per utterance (sig null), or a caller's signal (speechPlayer_signal_t; klatt_tiles.h: signal_plan, the reader).
 // An entry point over a signal differs from its sibling over the pool in four places, all here (export_input decides): the rows it may choose
 // (export_selection's `sig`), no synthesis is needed (export_synthesised is skipped), the signal's memory is checked beside the output's
@@ -5135,6 +5135,7 @@ struct ExportInput {
     const void* data = nullptr;          // the pool, or the signal's data
     long long at(long long r) const { return sig ? sig->at(r) : b->outStart[(size_t)r]; }
     long long len(long long r) const { return sig ? sig->len(r) : (long long)b->lens[(size_t)r]; }
+    long long rows() const { return sig ? sig->nRows : b->nUtt; }
     int format() const { return sig ? sig->format : 0; }
 };
 // What an entry point reads: the pool (ofSignal false; `signal` is not looked at), or `signal` with the refusals that need no device, in
@@ -5603,61 +5604,98 @@ static_assert(sizeof(speechPlayer_mixTerm_t) == sizeof(MixTermIn) && offsetof(sp
               offsetof(speechPlayer_mixTerm_t, loop) == offsetof(MixTermIn, loop), "klatt_mix.h restates speechPlayer_mixTerm_t");
 
 // Host only, touches no device: the definition of klatt_mix.h through the functions the kernels are compiled from.
-long long speechPlayer_pcmMix(const sample* pcm, long long length, float speechGain, const speechPlayer_mixSource_t* sources, long long nSources,
-                              const speechPlayer_mixTerm_t* terms, long long nTerms, float* gains, int format, void* out, long long capacity)
+// ofSignal (speechPlayer_signalMix): x is int16 or float32 (inFormat); a kind-1 term may name a float32 source, a row of the signal,
+// whose power is signal_power's; a float32 source is held to a clip's length only where a kind-0 term names it.
+static long long mix_statement(const char* what, bool ofSignal, const void* pcm, int inFormat, long long length, float speechGain, const speechPlayer_mixSource_t* sources,
+                               long long nSources, const speechPlayer_mixTerm_t* terms, long long nTerms, float* gains, int format, void* out, long long capacity)
 {
-    begin_call();
-    static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
-    if (length < 0 || length > kMixMaxLength || (length > 0 && !pcm)) { set_error("pcmMix: length %lld (0 .. 2^33, with its samples)", length); return -1; }
-    if (format != 0 && format != 1) { set_error("pcmMix: format %d (0 int16, 1 float32)", format); return -1; }
-    if (nSources < 0 || (nSources > 0 && !sources)) { set_error("pcmMix: %lld sources", nSources); return -1; }
-    if (nTerms < 0 || nTerms > kMixMaxTerms || (nTerms > 0 && !terms)) { set_error("pcmMix: %lld terms (0 .. %d, with their descriptors)", nTerms, kMixMaxTerms); return -1; }
+    if (ofSignal && signal_host_format(what, inFormat)) return -1;
+    if (length < 0 || length > kMixMaxLength || (length > 0 && !pcm)) { set_error("%s: length %lld (0 .. 2^33, with its samples)", what, length); return -1; }
+    if (format != 0 && format != 1) { set_error("%s: format %d (0 int16, 1 float32)", what, format); return -1; }
+    if (nSources < 0 || (nSources > 0 && !sources)) { set_error("%s: %lld sources", what, nSources); return -1; }
+    if (nTerms < 0 || nTerms > kMixMaxTerms || (nTerms > 0 && !terms)) { set_error("%s: %lld terms (0 .. %d, with their descriptors)", what, nTerms, kMixMaxTerms); return -1; }
     try {
         std::string why;
-        if (!mix_check_speech_gain(speechGain, 0, why)) { set_error("pcmMix: %s", why.c_str()); return -1; }
+        if (!mix_check_speech_gain(speechGain, 0, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
         std::vector<MixSource> src((size_t)nSources);
-        std::vector<char> powered((size_t)nSources, 0);
+        std::vector<char> powered((size_t)nSources, 0);      // bit `kind`: a float32 source may be named as a clip and as a row, and the two powers differ
         for (long long k = 0; k < nSources; ++k) {
             const speechPlayer_mixSource_t& q = sources[k];
-            if (q.format != 0 && q.format != 1) { set_error("pcmMix: source %lld has format %d (0 int16, 1 float32)", k, q.format); return -1; }
-            if (q.length < 0 || (q.format == 1 ? q.length < 1 || q.length >= (1ll << 31) : q.length > kMixMaxLength) || (q.length > 0 && !q.data)) {
-                set_error("pcmMix: source %lld has %lld samples (a clip 1 .. 2^31 - 1, an utterance 0 .. 2^33, with its samples)", k, q.length); return -1;
+            if (q.format != 0 && q.format != 1) { set_error("%s: source %lld has format %d (0 int16, 1 float32)", what, k, q.format); return -1; }
+            // (a float32 source of a signal's mix may be a row: a clip's length is asked of it where a kind-0 term names it)
+            if (q.length < 0 || (q.format == 1 && !ofSignal ? q.length < 1 || q.length >= (1ll << 31) : q.length > kMixMaxLength) || (q.length > 0 && !q.data)) {
+                set_error("%s: source %lld has %lld samples (a clip 1 .. 2^31 - 1, an utterance 0 .. 2^33, with its samples)", what, k, q.length); return -1;
             }
             if (q.format == 1) {
                 const long long bad = mix_bad_value(static_cast<const float*>(q.data), q.length);
-                if (bad >= 0) { set_error("pcmMix: sample %lld of clip %lld is %g (finite, at most 2^16 in magnitude)", bad, k, (double)static_cast<const float*>(q.data)[bad]); return -1; }
+                if (bad >= 0) { set_error("%s: sample %lld of clip %lld is %g (finite, at most 2^16 in magnitude)", what, bad, k, (double)static_cast<const float*>(q.data)[bad]); return -1; }
             }
             src[(size_t)k] = MixSource{q.data, q.length, q.format, 0.0};
         }
         const MixTermIn* in = reinterpret_cast<const MixTermIn*>(terms);
         std::vector<MixTermHost> host((size_t)nTerms);
+        struct PowerOf { double of[2]; };
+        std::vector<PowerOf> powers((size_t)nSources, PowerOf{{0.0, 0.0}});
         double Ps = 0.0;
         bool havePs = false;
         for (long long j = 0; j < nTerms; ++j) {
             const MixTermIn& t = in[j];
             // (one list of sources for both kinds: a clip is a float32 source, an utterance an int16 one)
-            if (!mix_check_term(t, 0, j, t.kind == 0 ? nSources : -1, t.kind == 1 ? nSources : 0, [&](int, long long k) { return src[(size_t)k].length; }, why)) {
-                set_error("pcmMix: %s", why.c_str()); return -1;
+            if (!mix_check_term(t, 0, j, t.kind == 0 ? nSources : -1, t.kind == 1 ? nSources : 0, [&](int, long long k) { return src[(size_t)k].length; }, why, ofSignal)) {
+                set_error("%s: %s", what, why.c_str()); return -1;
             }
             MixSource& q = src[(size_t)t.source];
-            if (q.isFloat != (t.kind == 0)) { set_error("pcmMix: row 0, term %lld: kind %d names source %lld, which is %s", j, t.kind, t.source, q.isFloat ? "float32 (a clip)" : "int16 (an utterance)"); return -1; }
+            if (ofSignal && t.kind == 0 && q.isFloat && (q.length < 1 || q.length >= (1ll << 31))) {
+                set_error("%s: row 0, term %lld: clip %lld has %lld samples (1 .. 2^31 - 1)", what, j, t.source, q.length); return -1;
+            }
+            if (ofSignal ? (t.kind == 0 && !q.isFloat) : q.isFloat != (t.kind == 0)) { set_error("%s: row 0, term %lld: kind %d names source %lld, which is %s", what, j, t.kind, t.source, q.isFloat ? "float32 (a clip)" : "int16 (an utterance)"); return -1; }
             float g = (float)t.level;
             if (t.levelKind == 0) {
-                if (!havePs) { Ps = mix_power(mix_square_sum(reinterpret_cast<const int16_t*>(pcm), length), length); havePs = true; }
-                if (!powered[(size_t)t.source]) {
-                    q.power = q.isFloat ? mix_clip_power(static_cast<const float*>(q.data), q.length)
-                                        : mix_power(mix_square_sum(static_cast<const int16_t*>(q.data), q.length), q.length);
-                    powered[(size_t)t.source] = 1;
+                if (!havePs) { Ps = signal_power(pcm, inFormat, length); havePs = true; }      // (of values yet to be checked: it steers nothing)
+                double (&known)[2] = powers[(size_t)t.source].of;
+                if (!(powered[(size_t)t.source] & (1 << t.kind))) {
+                    known[t.kind] = t.kind == 0 ? mix_clip_power(static_cast<const float*>(q.data), q.length) : signal_power(q.data, q.isFloat, q.length);
+                    powered[(size_t)t.source] |= (char)(1 << t.kind);
                 }
-                g = mix_gain(Ps, q.power, mix_ratio(t.level));
+                g = mix_gain(Ps, known[t.kind], mix_ratio(t.level));
             }
             host[(size_t)j] = MixTermHost{(int)t.source, t.offset, t.loop, g};
         }
-        if (capacity < length && out) { set_error("pcmMix: the output takes %lld elements, capacity is %lld", length, capacity); return -1; }
+        if (capacity < length && out) { set_error("%s: the output takes %lld elements, capacity is %lld", what, length, capacity); return -1; }
+        if (ofSignal && signal_host_values(what, pcm, inFormat, length)) return -1;
         for (long long j = 0; gains && j < nTerms; ++j) gains[j] = host[(size_t)j].gain;
         if (!out) return length;
-        return mix_host(reinterpret_cast<const int16_t*>(pcm), length, speechGain, src.data(), host.data(), nTerms, format, out);
-    } catch (const std::exception& e) { set_error("pcmMix: %s", e.what()); return -1; }
+        return inFormat ? mix_host(static_cast<const float*>(pcm), length, speechGain, src.data(), host.data(), nTerms, format, out)
+                        : mix_host(static_cast<const int16_t*>(pcm), length, speechGain, src.data(), host.data(), nTerms, format, out);
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
+long long speechPlayer_pcmMix(const sample* pcm, long long length, float speechGain, const speechPlayer_mixSource_t* sources, long long nSources,
+                              const speechPlayer_mixTerm_t* terms, long long nTerms, float* gains, int format, void* out, long long capacity)
+{
+    begin_call();
+    static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
+    return mix_statement("pcmMix", false, pcm, 0, length, speechGain, sources, nSources, terms, nTerms, gains, format, out, capacity);
+}
+
+long long speechPlayer_signalMix(const void* x, int inFormat, long long length, float speechGain, const speechPlayer_mixSource_t* sources, long long nSources,
+                                 const speechPlayer_mixTerm_t* terms, long long nTerms, float* gains, int format, void* out, long long capacity)
+{
+    begin_call();
+    return mix_statement("signalMix", true, x, inFormat, length, speechGain, sources, nSources, terms, nTerms, gains, format, out, capacity);
+}
+
+// Host only: the power of `length` samples of a signal's row (klatt_sigpower.h: the definition), int16 (mix_power of the exact sum) or float32
+int speechPlayer_signalPower(const void* x, int inFormat, long long length, double* power)
+{
+    begin_call();
+    const char* what = "signalPower";
+    if (signal_host_format(what, inFormat)) return -1;
+    if (length < 0 || length > kMixMaxLength || (length > 0 && !x)) { set_error("%s: length %lld (0 .. 2^33, with its samples)", what, length); return -1; }
+    if (!power) { set_error("%s: no output", what); return -1; }
+    if (signal_host_values(what, x, inFormat, length)) return -1;
+    *power = signal_power(x, inFormat, length);
+    return 0;
 }
 
 // The batch's noise bank: validated and its clips' powers computed on the host, its samples kept in device memory until the next call
@@ -5697,66 +5735,145 @@ long long speechPlayer_batch_noiseBank(speechPlayer_batch_t batch, double* power
     });
 }
 
-// The distinct utterances whose S_u a call needs: a slot each, and klatt_power's tiles
+// The distinct rows whose power a call needs -- utterances of the pool, rows of a signal --: a slot each, and the power kernel's walk over
+// them: klatt_power's tiles of kPowerTile int16 samples, klatt_signal_power's blocks of kSigPowerBlock float32 ones
 struct PowerSlots {
-    std::vector<long long> slotOfUtt;      // [nUtt], -1: none yet
+    std::vector<long long> slotOfUtt;      // [rows of the input], -1: none yet
     std::vector<PowerJob> jobs;
     std::vector<long long> tileStart{0};
-    long long of(const Batch* b, long long u)
+    long long of(const ExportInput& in, long long u)
     {
-        if (slotOfUtt.empty()) slotOfUtt.assign((size_t)b->nUtt, -1);
+        if (slotOfUtt.empty()) slotOfUtt.assign((size_t)in.rows(), -1);
         if (slotOfUtt[(size_t)u] >= 0) return slotOfUtt[(size_t)u];
-        const long long slot = (long long)jobs.size(), L = (long long)b->lens[(size_t)u];
-        jobs.push_back(PowerJob{b->outStart[(size_t)u], L});
-        tileStart.push_back(tileStart.back() + (L + kPowerTile - 1) / kPowerTile);
+        const long long slot = (long long)jobs.size(), L = in.len(u), unit = in.format() ? kSigPowerBlock : kPowerTile;
+        jobs.push_back(PowerJob{in.at(u), L});
+        tileStart.push_back(tileStart.back() + (L + unit - 1) / unit);
         slotOfUtt[(size_t)u] = slot;
         return slot;
     }
     long long tiles() const { return tileStart.back(); }
 };
 
-static int launch_power(Batch* b, hipStream_t st, const PowerSlots& P, const PowerJob* dJobs, const long long* dTileStart, unsigned long long* dSlots)
+static int launch_power(Batch* b, hipStream_t st, const int16_t* data, const PowerSlots& P, const PowerJob* dJobs, const long long* dTileStart, unsigned long long* dSlots)
 {
     if (P.tiles() == 0) return 0;
     PowerArgs A;
-    A.pool = b->dPcm.ptr; A.jobs = dJobs; A.tileStart = dTileStart; A.nJobs = (long long)P.jobs.size(); A.nTiles = P.tiles(); A.slots = dSlots;
+    A.pool = data; A.jobs = dJobs; A.tileStart = dTileStart; A.nJobs = (long long)P.jobs.size(); A.nTiles = P.tiles(); A.slots = dSlots;
     const unsigned grid = (unsigned)std::min<long long>(A.nTiles, 8ll * b->cus);
     hipLaunchKernelGGL(klatt_power, dim3(grid), dim3(256), 0, st, A);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
+// The powers of a signal's slots as one binary64 each (klatt_sigpower.h).  The call's scratch, all in its staging slot: int16 rows take
+// zeroed uint64 slots (klatt_power, then klatt_power_doubles), float32 rows one partial per block (klatt_signal_power, then the row pass).
+struct SignalPowerScratch {
+    int slotsAt = -1, partialsAt = -1, powersAt = -1;
+    std::vector<unsigned long long> zeros;
+    // The sections that hold contents: before any reserve()
+    void add(StageBlock& block, const ExportInput& in, const PowerSlots& P) { if (!in.format()) { zeros.assign(P.jobs.size(), 0ull); slotsAt = block.add(zeros); } }
+    void reserve(StageBlock& block, const ExportInput& in, const PowerSlots& P)
+    {
+        powersAt = block.reserve(P.jobs.size() * sizeof(double));
+        if (in.format()) partialsAt = block.reserve((size_t)P.tiles() * sizeof(double));
+    }
+};
+// More block partials than a call's scratch carries
+static int signal_power_cap(const char* what, const ExportInput& in, const PowerSlots& P)
+{
+    if (!in.sig || !in.format() || P.tiles() <= kSigPowerMaxBlocks) return 0;
+    set_error("%s: the rows to be powered take %lld blocks of %d samples (at most 2^24 in one call)", what, P.tiles(), kSigPowerBlock);
+    return -1;
+}
+static int launch_signal_power(const ExportStage& stage, const ExportInput& in, const PowerSlots& P, const SignalPowerScratch& S, int jobsAt, int tilesAt, double*& dPowers)
+{
+    Batch* b = stage.b;
+    const long long n = (long long)P.jobs.size();
+    dPowers = const_cast<double*>(stage.device<double>(S.powersAt));      // (the slot is this call's until its event)
+    if (n == 0) return 0;
+    const PowerJob* dJobs = stage.device<PowerJob>(jobsAt);
+    const long long* dTiles = stage.device<long long>(tilesAt);
+    if (!in.format()) {
+        unsigned long long* dSlots = const_cast<unsigned long long*>(stage.device<unsigned long long>(S.slotsAt));
+        if (launch_power(b, stage.st, static_cast<const int16_t*>(in.data), P, dJobs, dTiles, dSlots)) return -1;
+        const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 8ll * b->cus);
+        hipLaunchKernelGGL(klatt_power_doubles, dim3(grid), dim3(256), 0, stage.st, dSlots, dJobs, n, dPowers);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    double* dPartials = const_cast<double*>(stage.device<double>(S.partialsAt));
+    if (P.tiles() > 0) {
+        SigPowerArgs A;
+        A.data = static_cast<const float*>(in.data); A.jobs = dJobs; A.blockStart = dTiles; A.nJobs = n; A.nBlocks = P.tiles(); A.partials = dPartials;
+        const unsigned grid = (unsigned)std::min<long long>(A.nBlocks, 16ll * b->cus);
+        hipLaunchKernelGGL(klatt_signal_power, dim3(grid), dim3(256), 0, stage.st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    const unsigned grid = (unsigned)std::min<long long>((n + 3) / 4, 16ll * b->cus);
+    hipLaunchKernelGGL(klatt_signal_power_rows, dim3(grid), dim3(256), 0, stage.st, dPartials, dTiles, dJobs, n, dPowers);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // The chosen utterances' S_u = sum s(n)^2, one uint64 per row (klatt_mix.h: klatt_power into the zeroed slots of the call's staging block,
 // then the deal-out to the rows).  It reads the pool, so it is ordered as speechPlayer_batch_exportPcm is (ExportStage, ofPcm).
-long long speechPlayer_batch_exportPower(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, void* deviceOut, void* stream)
+// ofSignal and `signal` as spectrogram_export's: the chosen rows' powers P, one binary64 per row (klatt_sigpower.h), by the same deal-out.
+static long long power_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances, long long nUtterances,
+                              void* deviceOut, void* stream)
 {
-    const char* what = "exportPower";
-    if (refuse_timing_only("speechPlayer_batch_exportPower")) return -1;
     return batch_entry(what, batch, [&](Batch* b) -> long long {
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
         ExportSelection s;
         PowerSlots P;
         std::vector<long long> slotOf;
         if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long, long long u, long long) -> long long {
-                slotOf.push_back(P.of(b, u));
+                slotOf.push_back(P.of(in, u));
                 return 1;
-            })) return -1;
+            }, in.sig)) return -1;
         if (s.n == 0) return 0;
-        if (export_synthesised(b, what)) return -1;
-        if (export_output(b, what, deviceOut, s.n, sizeof(unsigned long long))) return -1;
+        if (signal_power_cap(what, in, P)) return -1;
+        if (!in.sig && export_synthesised(b, what)) return -1;
+        if (export_output(b, what, deviceOut, s.n, sizeof(unsigned long long)) || signal_memory(in, what, deviceOut, (size_t)s.n * sizeof(unsigned long long))) return -1;
         hipStream_t st = static_cast<hipStream_t>(stream);
-        const std::vector<unsigned long long> zeros(P.jobs.size(), 0ull);
+        const std::vector<unsigned long long> zeros(in.sig ? 0 : P.jobs.size(), 0ull);
+        SignalPowerScratch S;
         StageBlock block;
         const int jobsAt = block.add(P.jobs), tilesAt = block.add(P.tileStart), slotOfAt = block.add(slotOf), slotsAt = block.add(zeros);
-        ExportStage stage(b, st, block, nullptr, true);
+        if (in.sig) { S.add(block, in, P); S.reserve(block, in, P); }
+        ExportStage stage(b, st, block, nullptr, !in.sig, in.sig != nullptr);
         if (stage.begin()) return -1;
-        unsigned long long* dSlots = const_cast<unsigned long long*>(stage.device<unsigned long long>(slotsAt));      // (the slot is this call's until its event)
-        if (launch_power(b, st, P, stage.device<PowerJob>(jobsAt), stage.device<long long>(tilesAt), dSlots)) return -1;
+        const unsigned long long* dealt;      // eight bytes per slot: S_u of the pool, P of a signal
+        if (in.sig) {
+            double* dPowers;
+            if (launch_signal_power(stage, in, P, S, jobsAt, tilesAt, dPowers)) return -1;
+            dealt = reinterpret_cast<const unsigned long long*>(dPowers);
+        } else {
+            unsigned long long* dSlots = const_cast<unsigned long long*>(stage.device<unsigned long long>(slotsAt));      // (the slot is this call's until its event)
+            if (launch_power(b, st, b->dPcm.ptr, P, stage.device<PowerJob>(jobsAt), stage.device<long long>(tilesAt), dSlots)) return -1;
+            dealt = dSlots;
+        }
         const unsigned grid = (unsigned)std::min<long long>((s.n + 255) / 256, 8ll * b->cus);
-        hipLaunchKernelGGL(klatt_power_deal, dim3(grid), dim3(256), 0, st, dSlots, stage.device<long long>(slotOfAt), s.n, static_cast<unsigned long long*>(deviceOut));
+        hipLaunchKernelGGL(klatt_power_deal, dim3(grid), dim3(256), 0, st, dealt, stage.device<long long>(slotOfAt), s.n, static_cast<unsigned long long*>(deviceOut));
         HIP_TRY(hipGetLastError());
         if (stage.finish()) return -1;
         return s.n;
     });
+}
+
+long long speechPlayer_batch_exportPower(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, void* deviceOut, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportPower")) return -1;
+    return power_export("exportPower", batch, false, nullptr, utterances, nUtterances, deviceOut, stream);
+}
+
+// The same of chosen rows of a caller's signal, as binary64 powers: it reads no pool and needs no synthesis (ExportStage, ofSignal).
+long long speechPlayer_batch_exportPowerOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows, void* deviceOut,
+                                           void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportPowerOf")) return -1;
+    return power_export("exportPowerOf", batch, true, signal, rows, nRows, deviceOut, stream);
 }
 
 // The chosen utterances' PCM, row i mixed with its terms terms[termStart[i] .. termStart[i+1]) (klatt_mix.h).  It reads the pool, so it is
@@ -5764,15 +5881,18 @@ long long speechPlayer_batch_exportPower(speechPlayer_batch_t batch, const long 
 // staging block: rows | tile starts and chunk rows (packed) | the terms as the kernel reads them | their level jobs | the power slots'
 // utterances, tiles and zeros | the gains (reserved: nothing is uploaded).  The slots and the gains are the call's device scratch: they
 // live in its staging slot.
-long long speechPlayer_batch_exportMixed(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const speechPlayer_mixTerm_t* terms,
-                                         const long long* termStart, const float* speechGain, void* deviceGains, void* deviceOut, int format,
-                                         long long rowStride, void* stream)
+// ofSignal and `signal` as spectrogram_export's: the rows and the kind-1 sources are rows of the signal, the powers are klatt_sigpower.h's
+// (SignalPowerScratch: behind the gains, reserved as they are), and a call that names a clip still follows the bank's order.
+static long long mixed_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances, long long nUtterances,
+                              const speechPlayer_mixTerm_t* terms, const long long* termStart, const float* speechGain, void* deviceGains, void* deviceOut, int format,
+                              long long rowStride, void* stream)
 {
-    const char* what = "exportMixed";
-    if (refuse_timing_only("speechPlayer_batch_exportMixed")) return -1;
     return batch_entry(what, batch, [&](Batch* b) -> long long {
         if (tile_request(what, format, rowStride)) return -1;
-        const MixTermIn* in = reinterpret_cast<const MixTermIn*>(terms);
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
+        const MixTermIn* tin = reinterpret_cast<const MixTermIn*>(terms);
         std::string why;
         ExportSelection s;
         PowerSlots P;
@@ -5783,62 +5903,96 @@ long long speechPlayer_batch_exportMixed(speechPlayer_batch_t batch, const long 
         double lastDb = 0.0, lastRatio = 1.0;      // pow(10.0, 0.0) is 1
         const long long nClips = b->hasBank ? b->bank.clips() : -1;
         if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) -> long long {
-                if (!mix_check_row(termStart, i, terms, why)) { set_error("exportMixed: %s", why.c_str()); return -1; }
+                if (!mix_check_row(termStart, i, terms, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
                 const float sg = speechGain ? speechGain[i] : 1.0f;
-                if (!mix_check_speech_gain(sg, i, why)) { set_error("exportMixed: %s", why.c_str()); return -1; }
-                const long long L = (long long)b->lens[(size_t)u], a = termStart[i], nT = termStart[i + 1] - a;
+                if (!mix_check_speech_gain(sg, i, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+                const long long L = in.len(u), a = termStart[i], nT = termStart[i + 1] - a;
                 for (long long j = 0; j < nT; ++j) {
-                    const MixTermIn& t = in[a + j];
-                    if (!mix_check_term(t, i, j, nClips, b->nUtt, [&](int kind, long long k) {
-                            return kind == 0 ? b->bank.start[(size_t)k + 1] - b->bank.start[(size_t)k] : (long long)b->lens[(size_t)k];
-                        }, why)) { set_error("exportMixed: %s", why.c_str()); return -1; }
+                    const MixTermIn& t = tin[a + j];
+                    if (!mix_check_term(t, i, j, nClips, in.rows(), [&](int kind, long long k) {
+                            return kind == 0 ? b->bank.start[(size_t)k + 1] - b->bank.start[(size_t)k] : in.len(k);
+                        }, why, in.sig != nullptr)) { set_error("%s: %s", what, why.c_str()); return -1; }
                     MixTermDev d;
                     if (t.kind == 0) { d.at = b->bank.start[(size_t)t.source]; d.len = b->bank.start[(size_t)t.source + 1] - d.at; readsBank = true; }
-                    else { d.at = b->outStart[(size_t)t.source]; d.len = (long long)b->lens[(size_t)t.source]; }
+                    else { d.at = in.at(t.source); d.len = in.len(t.source); }
                     d.offset = t.offset; d.flags = (t.kind == 0 ? kMixClip : 0) | (t.loop ? kMixLoop : 0); d.pad = 0;
                     dev.push_back(d);
                     MixGainJob job{1.0, 0.0, 0, -1, (float)t.level, 1};
                     if (t.levelKind == 0) {
                         if (t.level != lastDb) { lastDb = t.level; lastRatio = mix_ratio(t.level); }      // (a batch repeats few levels: one pow each)
                         job.linear = 0; job.gain = 0.0f; job.ratio = lastRatio;
-                        job.rowSlot = P.of(b, u);
-                        if (t.kind == 0) job.pv = b->bank.power[(size_t)t.source]; else job.srcSlot = P.of(b, t.source);
+                        job.rowSlot = P.of(in, u);
+                        if (t.kind == 0) job.pv = b->bank.power[(size_t)t.source]; else job.srcSlot = P.of(in, t.source);
                     }
                     jobs.push_back(job);
                 }
-                rows.push_back(MixRow{b->outStart[(size_t)u], L, tile_row_first(i, rowStride, before), a, (int)nT, sg});
+                rows.push_back(MixRow{in.at(u), L, tile_row_first(i, rowStride, before), a, (int)nT, sg});
                 return L;
-            })) return -1;
-        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut);
+            }, in.sig)) return -1;
+        if (signal_power_cap(what, in, P)) return -1;
+        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut, &in);
         if (elements <= 0) return elements;
         const long long nTerms = (long long)dev.size();
         if (deviceGains && nTerms > 0 && !device_range(deviceGains, (size_t)nTerms * sizeof(float), b->device, sizeof(float), what)) return -1;
+        if (deviceGains && nTerms > 0 && signal_memory(in, what, deviceGains, (size_t)nTerms * sizeof(float))) return -1;
         hipStream_t st = static_cast<hipStream_t>(stream);
 
         std::vector<long long> words;
         const TileTable tiles = tile_row_table(s.counts.data(), s.n, kMixTile, rowStride, kTimelineChunkLog2, words);
-        const std::vector<unsigned long long> zeros(P.jobs.size(), 0ull);
+        const std::vector<unsigned long long> zeros(in.sig ? 0 : P.jobs.size(), 0ull);
+        SignalPowerScratch S;
         StageBlock block;
         const int rowsAt = block.add(rows), wordsAt = block.add(words), termsAt = block.add(dev), jobsAt = block.add(jobs), slotJobsAt = block.add(P.jobs),
-                  tilesAt = block.add(P.tileStart), slotsAt = block.add(zeros), gainsAt = block.reserve((size_t)nTerms * sizeof(float));      // (klatt_mix_gains fills the gains)
-        ExportStage stage(b, st, block, readsBank ? &b->bankOrder : nullptr, true);
+                  tilesAt = block.add(P.tileStart), slotsAt = block.add(zeros);
+        if (in.sig) S.add(block, in, P);
+        const int gainsAt = block.reserve((size_t)nTerms * sizeof(float));      // (klatt_mix_gains fills the gains)
+        if (in.sig) S.reserve(block, in, P);
+        ExportStage stage(b, st, block, readsBank ? &b->bankOrder : nullptr, !in.sig, in.sig != nullptr);
         if (stage.begin()) return -1;
-        unsigned long long* dSlots = const_cast<unsigned long long*>(stage.device<unsigned long long>(slotsAt));      // (the slot is this call's until its event)
         float* dGains = const_cast<float*>(stage.device<float>(gainsAt));
-        if (launch_power(b, st, P, stage.device<PowerJob>(slotJobsAt), stage.device<long long>(tilesAt), dSlots)) return -1;
-        if (nTerms > 0) {
-            const unsigned grid = (unsigned)std::min<long long>((nTerms + 255) / 256, 8ll * b->cus);
-            hipLaunchKernelGGL(klatt_mix_gains, dim3(grid), dim3(256), 0, st, stage.device<MixGainJob>(jobsAt), nTerms, dSlots, stage.device<PowerJob>(slotJobsAt),
-                               dGains, static_cast<float*>(deviceGains));
-            HIP_TRY(hipGetLastError());
+        const unsigned gainGrid = (unsigned)std::min<long long>((nTerms + 255) / 256, 8ll * b->cus);
+        if (in.sig) {
+            double* dPowers;
+            if (launch_signal_power(stage, in, P, S, slotJobsAt, tilesAt, dPowers)) return -1;
+            if (nTerms > 0) {
+                hipLaunchKernelGGL(klatt_mix_gains_of, dim3(gainGrid), dim3(256), 0, st, stage.device<MixGainJob>(jobsAt), nTerms, dPowers, dGains, static_cast<float*>(deviceGains));
+                HIP_TRY(hipGetLastError());
+            }
+        } else {
+            unsigned long long* dSlots = const_cast<unsigned long long*>(stage.device<unsigned long long>(slotsAt));      // (the slot is this call's until its event)
+            if (launch_power(b, st, b->dPcm.ptr, P, stage.device<PowerJob>(slotJobsAt), stage.device<long long>(tilesAt), dSlots)) return -1;
+            if (nTerms > 0) {
+                hipLaunchKernelGGL(klatt_mix_gains, dim3(gainGrid), dim3(256), 0, st, stage.device<MixGainJob>(jobsAt), nTerms, dSlots, stage.device<PowerJob>(slotJobsAt),
+                                   dGains, static_cast<float*>(deviceGains));
+                HIP_TRY(hipGetLastError());
+            }
         }
         MixArgs A;
-        A.pool = b->dPcm.ptr; A.bank = b->dBank.ptr; A.rows = stage.device<MixRow>(rowsAt);
+        A.pool = in.data; A.bank = b->dBank.ptr; A.rows = stage.device<MixRow>(rowsAt);
         A.tile = tile_out(stage, wordsAt, tiles, rowStride, deviceOut);
         A.terms = stage.device<MixTermDev>(termsAt); A.gains = dGains;
-        if (launch_tiles(stage, klatt_mix<false>, klatt_mix<true>, format, 8, A)) return -1;
+        void (*const kernels[2][2])(MixArgs) = {{klatt_mix<false, int16_t>, klatt_mix<true, int16_t>}, {klatt_mix<false, float>, klatt_mix<true, float>}};
+        if (launch_tiles(stage, kernels, in.format(), format, 8, A)) return -1;
         return elements;
     });
+}
+
+long long speechPlayer_batch_exportMixed(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const speechPlayer_mixTerm_t* terms,
+                                         const long long* termStart, const float* speechGain, void* deviceGains, void* deviceOut, int format,
+                                         long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportMixed")) return -1;
+    return mixed_export("exportMixed", batch, false, nullptr, utterances, nUtterances, terms, termStart, speechGain, deviceGains, deviceOut, format, rowStride, stream);
+}
+
+// The same onto chosen rows of a caller's signal, termStart and speechGain per output row: it reads no pool and needs no synthesis
+// (ExportStage, ofSignal).
+long long speechPlayer_batch_exportMixedOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+                                           const speechPlayer_mixTerm_t* terms, const long long* termStart, const float* speechGain, void* deviceGains, void* deviceOut,
+                                           int format, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportMixedOf")) return -1;
+    return mixed_export("exportMixedOf", batch, true, signal, rows, nRows, terms, termStart, speechGain, deviceGains, deviceOut, format, rowStride, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // klatt_mix.h -- a batch's PCM mixed with noise clips and other utterances at set levels (speechPlayer_batch_exportMixed), the exact power
 // of utterances (speechPlayer_batch_exportPower), the batch's noise bank (speechPlayer_batch_setNoiseBank) and the same mixture of plain PCM
-// on the host (speechPlayer_pcmMix).
+// on the host (speechPlayer_pcmMix); the same onto the rows of a caller's signal (speechPlayer_batch_exportMixedOf, exportPowerOf,
+// speechPlayer_signalMix, speechPlayer_signalPower), whose power is klatt_sigpower.h's.
 //
 // The definition.  For a row whose utterance has L samples of int16 PCM s(t):
 //   input      x[n] = res_input(s(n)) (klatt_resample.h: the bits of speechPlayer_batch_exportPcm's format 1).  The output has L samples, on
@@ -25,9 +26,15 @@
 //              convolution's lemma holds: a term whose product is +-0 may be dropped without changing a bit, so a kernel may skip a term
 //              that lies wholly outside a tile.
 // The result is a function of the batch's PCM: it needs a synthesis launch, depends on the mode and is ordered as speechPlayer_batch_exportPcm
-// is.  Out of scope: live handles; NodePlayer, which reaches the export through speechPlayer_node_part; mixing onto a convolved or resampled
-// signal (use speechGain = 0 for the noise bed and add it); segment or active-speech (VAD-weighted) levels; loudness weighting; random draws
-// of any kind -- clips, offsets and levels are the caller's.
+// is.
+// Onto a signal (speechPlayer_batch_exportMixedOf): "the utterance's int16 PCM" becomes "the row's samples", int16 or float32 (tile_x is
+// the conversion); a kind-1 term names a ROW OF THE SAME SIGNAL, chosen or not, the row's own included; the power of a row is
+// signal_power (klatt_sigpower.h: the pool's exact integer sum for int16 rows, the fixed tree for float32 ones), and everything after the
+// powers -- mix_gain, the placement, the fmaf chain -- is unchanged.  The speech stands behind a room, the noise is added at an SNR
+// against the reverberant speech.  With an int16 signal that is the pool, every bit is the pool export's.
+// Out of scope: a term from a different signal or from the pool in a mix onto a signal; live handles; NodePlayer, which reaches the
+// export through speechPlayer_node_part; segment or active-speech (VAD-weighted) levels; loudness weighting; random draws of any kind --
+// clips, offsets and levels are the caller's.
 //
 //   The plan        mix_bank_plan (the bank, its refusals, the clip powers), mix_check_term / mix_check_row (the refusals of a term and of
 //                   a row's place in termStart; messages without the entry point's prefix).
@@ -39,14 +46,19 @@
 //                   utterance, lanes take 16-byte loads of eight samples where the address allows, accumulate in 64 bits (a square is up
 //                   to 2^30: two of them do not fit a signed 32-bit sum), the wavefront reduces, one 64-bit atomic add per wavefront.
 //   klatt_mix_gains one lane per term: mix_gain from the slots and the bank's powers, into the call's scratch and the caller's deviceGains.
+//                   klatt_mix_gains_of is the same from an array of binary64 powers per slot, which a signal's rows have:
+//                   klatt_signal_power and its row pass make it for float32 rows, klatt_power and klatt_power_doubles for int16 ones.
 //   klatt_mix       A 256-lane workgroup takes tiles of kMixTile consecutive outputs of one row (klatt_tiles.h: the walk); lane l owns
 //                   the FOUR outputs 4 l .. 4 l + 3.  The row's term descriptors are wave-uniform.  Per term and tile the start index
 //                   (offset + t0) mod N is computed once; the lanes wrap by comparison when N >= kMixTile and by a 32-bit remainder
 //                   below that.  A term wholly outside the tile is skipped.  The values go out as klatt_tiles.h says (the writer):
-//                   staged in LDS in the output's type, a padded row's remainder as +0.
+//                   staged in LDS in the output's type, a padded row's remainder as +0.  The kernel is a template on the element of the
+//                   speech row and of the kind-1 terms, int16 (the pool; an int16 signal) or float32; four consecutive elements go in
+//                   one load where they are aligned and whole.
 #pragma once
 
 #include "klatt_convolve.h"
+#include "klatt_sigpower.h"
 
 namespace klatt {
 
@@ -121,9 +133,10 @@ KLATT_RES_HD bool mix_lane_whole(int o0, int lo, int hi, long long i0, long long
     return !(loop && N < kMixTile) && o0 >= lo && o0 + 4 <= hi && i0 >= 0 && i0 + 4 <= N;
 }
 
-// The lane's four samples of speech at p = the tile's first sample + o0 are all inside the row and p is 8-byte aligned: one load takes them
-// (an utterance starts on 64 bytes of the pool and a tile on 2048 of the utterance, so this fails only at a row's ragged end)
-KLATT_RES_HD bool mix_speech_whole(const int16_t* p, int o0, int live) { return o0 + 4 <= live && (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+// The lane's four samples of speech at p = the tile's first sample + o0 are all inside the row and p is aligned to the four (8 bytes of
+// int16, 16 of float32): one load takes them (an utterance starts on 64 bytes of the pool and a tile on 2048 of the utterance, so there
+// this fails only at a row's ragged end; a signal's row starts wherever its table says)
+template <typename In> KLATT_RES_HD bool mix_speech_whole(const In* p, int o0, int live) { return o0 + 4 <= live && (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(In) - 1)) == 0; }
 
 // ---- the bank ------------------------------------------------------------------------------------------------------------------------------
 struct MixBank {
@@ -191,9 +204,9 @@ inline bool mix_check_row(const long long* termStart, long long i, const void* t
 
 // A term of row i against its source: nClips (-1: no bank is set) and nUtterances are what `source` may name, N the source's length where
 // it names one (the caller looks it up once this has passed the range checks: lengthOf(kind, source)).  False with `why` set: the
-// message names row and term.
+// message names row and term.  ofSignal: a kind-1 source is a row of the signal the mix is made onto.
 template <class LengthOf>
-bool mix_check_term(const MixTermIn& t, long long i, long long j, long long nClips, long long nUtterances, LengthOf lengthOf, std::string& why)
+bool mix_check_term(const MixTermIn& t, long long i, long long j, long long nClips, long long nUtterances, LengthOf lengthOf, std::string& why, bool ofSignal = false)
 {
     char buf[256], at[64];
     at[0] = 0;
@@ -205,7 +218,7 @@ bool mix_check_term(const MixTermIn& t, long long i, long long j, long long nCli
         if (nClips < 0) { snprintf(buf, sizeof buf, "%s: clip %lld, and no noise bank is set", where(), t.source); why = buf; return false; }
         if (t.source < 0 || t.source >= nClips) { snprintf(buf, sizeof buf, "%s: clip %lld is not in the bank (%lld clips)", where(), t.source, nClips); why = buf; return false; }
     } else if (t.source < 0 || t.source >= nUtterances) {
-        snprintf(buf, sizeof buf, "%s: source %lld is not an utterance of the batch (%lld)", where(), t.source, nUtterances); why = buf; return false;
+        snprintf(buf, sizeof buf, "%s: source %lld is not %s (%lld)", where(), t.source, ofSignal ? "a row of the signal" : "an utterance of the batch", nUtterances); why = buf; return false;
     }
     const long long N = lengthOf(t.kind, t.source);
     if (t.loop) {
@@ -232,7 +245,7 @@ inline bool mix_check_speech_gain(float g, long long i, std::string& why)
 inline double mix_ratio(double db) { return pow(10.0, db / 10.0); }
 
 // ---- the host's statement (speechPlayer_pcmMix): the shared functions in a plain loop --------------------------------------------------------
-struct MixSource { const void* data; long long length; int isFloat; double power; };      // int16 PCM (an utterance) or float32 (a clip)
+struct MixSource { const void* data; long long length; int isFloat; double power; };      // int16 PCM (an utterance) or float32 (a clip; a signal's row)
 struct MixTermHost { int source; long long offset; int loop; float gain; };
 
 inline unsigned long long mix_square_sum(const int16_t* s, long long L)
@@ -242,17 +255,24 @@ inline unsigned long long mix_square_sum(const int16_t* s, long long L)
     return S;
 }
 
+// The power of a signal's row (klatt_sigpower.h: the definition): format 0 int16, 1 float32
+inline double signal_power(const void* x, int format, long long L)
+{
+    return format ? sig_power_host(static_cast<const float*>(x), L) : mix_power(mix_square_sum(static_cast<const int16_t*>(x), L), L);
+}
+
 KLATT_RES_HD float mix_source_value(const void* data, int isFloat, long long i)
 {
     return isFloat ? static_cast<const float*>(data)[i] : res_input((int)static_cast<const int16_t*>(data)[i]);
 }
 
 // format 1: out is float[length]; format 0: int16_t[length].  Returns length.
-inline long long mix_host(const int16_t* pcm, long long length, float speechGain, const MixSource* sources, const MixTermHost* terms, long long nTerms,
+template <typename In>
+inline long long mix_host(const In* pcm, long long length, float speechGain, const MixSource* sources, const MixTermHost* terms, long long nTerms,
                           int format, void* out)
 {
     for (long long m = 0; m < length; ++m) {
-        float acc = speechGain * res_input((int)pcm[m]);
+        float acc = speechGain * tile_x(pcm[m]);
         for (long long j = 0; j < nTerms; ++j) {
             const MixSource& s = sources[terms[j].source];
             const long long i = mix_source_index(m, terms[j].offset, s.length, terms[j].loop);
@@ -271,8 +291,6 @@ inline long long mix_host(const int16_t* pcm, long long length, float speechGain
 namespace klatt {
 
 // ---- klatt_power ----
-struct PowerJob { long long src, len; };      // pool offset and samples of a slot's utterance
-
 struct PowerArgs {
     const int16_t* pool;
     const PowerJob* jobs;
@@ -330,6 +348,13 @@ __global__ void __launch_bounds__(256) klatt_power_deal(const unsigned long long
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll) out[i] = slots[slotOf[i]];
 }
 
+// int16 signals: the exact sums of klatt_power as the binary64 powers everything downstream of a signal's powers reads
+__global__ void __launch_bounds__(256) klatt_power_doubles(const unsigned long long* __restrict__ slots, const PowerJob* __restrict__ jobs, long long n,
+                                                           double* __restrict__ powers)
+{
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll) powers[i] = mix_power(slots[i], jobs[i].len);
+}
+
 // ---- klatt_mix_gains ----
 // A term's level: linear (gain as given) or an SNR (ratio; the row's slot; the source's slot, or -1: a clip of power pv)
 struct MixGainJob { double ratio, pv; long long rowSlot, srcSlot; float gain; int linear; };
@@ -350,15 +375,28 @@ __global__ void __launch_bounds__(256) klatt_mix_gains(const MixGainJob* __restr
     }
 }
 
+// The same over a signal's rows: Ps and Pv from the call's binary64 powers, one per slot, or the bank's P_c
+__global__ void __launch_bounds__(256) klatt_mix_gains_of(const MixGainJob* __restrict__ jobs, long long nTerms, const double* __restrict__ powers,
+                                                          float* __restrict__ gains, float* __restrict__ deviceGains)
+{
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < nTerms; i += gridDim.x * 256ll) {
+        const MixGainJob job = jobs[i];
+        float g = job.gain;
+        if (!job.linear) g = mix_gain(powers[job.rowSlot], job.srcSlot >= 0 ? powers[job.srcSlot] : job.pv, job.ratio);
+        gains[i] = g;
+        if (deviceGains) deviceGains[i] = g;
+    }
+}
+
 // ---- klatt_mix ----
 constexpr int kMixClip = 1, kMixLoop = 2;      // MixTermDev.flags
-// A term as the kernel reads it: the source's first element (in the bank: kMixClip; else in the pool), its samples, the offset
+// A term as the kernel reads it: the source's first element (in the bank: kMixClip; else in the pool or the signal), its samples, the offset
 struct MixTermDev { long long at, len, offset; int flags, pad; };
-// pool offset and samples of a row's utterance; its first element in the output; its first term, its terms; its speech gain
+// first element (of the pool, of the signal's data) and samples of a row; its first element in the output; its first term, its terms; its speech gain
 struct MixRow { long long src, len, dst, term0; int nTerms; float speechGain; };
 
 struct MixArgs {
-    const int16_t* pool;
+    const void* pool;                // the pool, or a signal's data: elements of the kernel's In
     const float* bank;
     const MixRow* rows;
     TileOut tile;
@@ -366,7 +404,7 @@ struct MixArgs {
     const float* gains;
 };
 
-template <bool F32>
+template <bool F32, typename In = int16_t>
 __global__ void __launch_bounds__(256) klatt_mix(const MixArgs A)
 {
     using T = TileValue<F32>;
@@ -374,6 +412,8 @@ __global__ void __launch_bounds__(256) klatt_mix(const MixArgs A)
     __shared__ __attribute__((aligned(16))) T staged[TILE];
     struct __attribute__((packed, aligned(4))) F4 { float x[4]; };      // four floats at any float's address
     struct __attribute__((packed, aligned(2))) S4 { int16_t x[4]; };    // four samples at any sample's address
+    using I4 = typename std::conditional<std::is_same<In, float>::value, F4, S4>::type;
+    const In* __restrict__ const pool = static_cast<const In*>(A.pool);
     const int tid = threadIdx.x;
     for (long long g = blockIdx.x; g < A.tile.nTiles; g += gridDim.x) {
         long long r, t0;
@@ -385,15 +425,15 @@ __global__ void __launch_bounds__(256) klatt_mix(const MixArgs A)
         float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (live > 0) {
             // ---- the speech: acc = speechGain * x ----
-            const int16_t* __restrict__ pcm = A.pool + row.src + t0;
+            const In* __restrict__ pcm = pool + row.src + t0;
             if (mix_speech_whole(pcm + o0, o0, live)) {
-                struct alignas(8) S4A { int16_t x[4]; };
+                struct alignas(4 * sizeof(In)) S4A { In x[4]; };
                 const S4A s = *reinterpret_cast<const S4A*>(pcm + o0);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = row.speechGain * res_input((int)s.x[q]);
+                for (int q = 0; q < 4; ++q) acc[q] = row.speechGain * tile_x(s.x[q]);
             } else {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) if (o0 + q < live) acc[q] = row.speechGain * res_input((int)pcm[o0 + q]);
+                for (int q = 0; q < 4; ++q) if (o0 + q < live) acc[q] = row.speechGain * tile_x(pcm[o0 + q]);
             }
             // ---- the terms, ascending (every condition on the term is uniform over the workgroup) ----
             for (int jt = 0; jt < row.nTerms; ++jt) {
@@ -411,9 +451,9 @@ __global__ void __launch_bounds__(256) klatt_mix(const MixArgs A)
 #pragma unroll
                         for (int q = 0; q < 4; ++q) v[q] = c.x[q];
                     } else {
-                        const S4 s = *reinterpret_cast<const S4*>(A.pool + t.at + i0);
+                        const I4 s = *reinterpret_cast<const I4*>(pool + t.at + i0);
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) v[q] = res_input((int)s.x[q]);
+                        for (int q = 0; q < 4; ++q) v[q] = tile_x(s.x[q]);
                     }
                 } else {
 #pragma unroll
@@ -421,7 +461,7 @@ __global__ void __launch_bounds__(256) klatt_mix(const MixArgs A)
                         const int o = o0 + q;
                         if (o < lo || o >= hi) continue;
                         const long long i = loop ? mix_loop_index(base, o, t.len) : base + o;
-                        v[q] = (t.flags & kMixClip) ? A.bank[t.at + i] : res_input((int)A.pool[t.at + i]);
+                        v[q] = (t.flags & kMixClip) ? A.bank[t.at + i] : tile_x(pool[t.at + i]);
                     }
                 }
 #pragma unroll

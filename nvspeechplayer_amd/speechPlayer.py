@@ -949,6 +949,8 @@ MIX_MAX_TERMS = 64               # kMixMaxTerms: of one row
 MIX_MAX_CALL_TERMS = 1 << 22     # kMixMaxCallTerms: of one call
 MIX_MAX_CLIPS = 1 << 20          # kMixMaxClips: of a noise bank
 MIX_MAX_BANK = 1 << 28           # kMixMaxBank: samples of a noise bank
+SIGNAL_POWER_BLOCK = 2048        # kSigPowerBlock of csrc/klatt_sigpower.h: consecutive samples of one block of a float32 row's power
+SIGNAL_POWER_MAX_BLOCKS = 1 << 24    # kSigPowerMaxBlocks: block partials of one call
 # speechPlayer_mixTerm_t and speechPlayer_mixSource_t (include/speechPlayer_batch.h)
 mixTermDtype = np.dtype([("kind", np.int32), ("levelKind", np.int32), ("source", np.int64), ("offset", np.int64), ("level", np.float64),
                          ("loop", np.int32), ("reserved", np.int32)], align=True)
@@ -1011,12 +1013,13 @@ def _mix_format(dtype, what):
     return names[key]
 
 
-def check_mix_request(terms, nRows, speechGain, dtype, what="mixedTensor"):
+def check_mix_request(terms, nRows, speechGain, dtype, what="mixedTensor", signalRows=None):
     """The argument checks of BatchPlayer.mixedTensor that need no GPU, before any library call: terms a list of nRows lists of MixTerm
     (a row with no terms: an empty list) or a pair (array of mixTermDtype, termStart: nRows + 1 integers from 0, not decreasing, the last
     the array's length); at most 64 terms in a row and 2^22 in all; speechGain None, one number or nRows of them; dtype None /
-    torch.float32 / np.float32 (float32) or torch.int16 / np.int16.  The values of the terms are the library's to refuse.  Raises
-    ValueError or TypeError.  Returns (the terms: mixTermDtype, termStart: int64, speechGain: float32 [nRows] or None, the export format:
+    torch.float32 / np.float32 (float32) or torch.int16 / np.int16.  The values of the terms are the library's to refuse.  signalRows:
+    the mix is made onto a signal of that many rows (mixedTensor(signal=...)): MixTerm(utterance=k) names row k of it, and one outside
+    0 .. signalRows - 1 is refused here, by row and term.  Raises ValueError or TypeError.  Returns (the terms: mixTermDtype, termStart: int64, speechGain: float32 [nRows] or None, the export format:
     0 int16, 1 float32)."""
     if isinstance(terms, tuple) and len(terms) == 2 and isinstance(terms[0], np.ndarray):
         flat = _mix_terms(terms[0], what)
@@ -1041,6 +1044,13 @@ def check_mix_request(terms, nRows, speechGain, dtype, what="mixedTensor"):
         raise ValueError("%s: row %d has %d terms (at most %d)" % (what, int(counts.argmax()), int(counts.max()), MIX_MAX_TERMS))
     if len(flat) > MIX_MAX_CALL_TERMS:
         raise ValueError("%s: %d terms in all (at most %d)" % (what, len(flat), MIX_MAX_CALL_TERMS))
+    if signalRows is not None:
+        if isinstance(signalRows, bool) or not isinstance(signalRows, (int, np.integer)) or signalRows < 0:
+            raise TypeError("%s: signalRows must be a count of rows, not %r" % (what, signalRows))
+        bad = np.flatnonzero((flat["kind"] == 1) & ((flat["source"] < 0) | (flat["source"] >= signalRows)))
+        if len(bad):
+            row = int(np.searchsorted(start, bad[0], side="right")) - 1
+            raise ValueError("%s: row %d, term %d: source %d is not a row of the signal (%d)" % (what, row, bad[0] - start[row], flat["source"][bad[0]], signalRows))
     sg = None
     if speechGain is not None:
         sg = np.asarray(speechGain.detach().cpu().numpy() if hasattr(speechGain, "detach") else speechGain)
@@ -1070,25 +1080,49 @@ def pcmMix(pcm, sources, terms, speechGain=1.0, dtype=np.float32, gains=False):
     s = np.ascontiguousarray(np.asarray(pcm))
     if s.dtype != np.int16 or s.ndim != 1:
         raise TypeError("pcmMix: pcm must be a one-dimensional int16 array, not %s %s" % (s.dtype, list(s.shape)))
+    return _mix_statement("pcmMix", _native.load().speechPlayer_pcmMix, (s.ctypes.data if len(s) else None,), s, sources, terms, speechGain, dtype, gains)
+
+
+def _mix_statement(what, fn, lead, s, sources, terms, speechGain, dtype, gains):
     if not isinstance(sources, (list, tuple)):
-        raise TypeError("pcmMix: sources must be a list of one-dimensional arrays")
+        raise TypeError("%s: sources must be a list of one-dimensional arrays" % what)
     held, table = [], np.zeros(max(len(sources), 1), _mixSourceDtype)
     for k, a in enumerate(sources):
         a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a)
-        a = np.ascontiguousarray(a) if a.dtype == np.int16 and a.ndim == 1 else _mix_clip(a, "pcmMix", "source %d" % k)
+        a = np.ascontiguousarray(a) if a.dtype == np.int16 and a.ndim == 1 else _mix_clip(a, what, "source %d" % k)
         held.append(a)
         table[k] = (a.ctypes.data if len(a) else 0, len(a), 0 if a.dtype == np.int16 else 1, 0)
-    flat = _mix_terms(terms, "pcmMix")
-    fmt = _mix_format(dtype, "pcmMix")
+    flat = _mix_terms(terms, what)
+    fmt = _mix_format(dtype, what)
     out = np.zeros(len(s), np.float32 if fmt else np.int16)
     g = np.zeros(max(len(flat), 1), np.float32)
-    got = _native.load().speechPlayer_pcmMix(s.ctypes.data if len(s) else None, len(s), float(np.float32(speechGain)), table.ctypes.data if len(sources) else None,
-                                             len(sources), flat.ctypes.data if len(flat) else None, len(flat), g.ctypes.data,
-                                             fmt, out.ctypes.data if len(s) else None, len(s))
+    got = fn(*(lead + (len(s), float(np.float32(speechGain)), table.ctypes.data if len(sources) else None, len(sources),
+                       flat.ctypes.data if len(flat) else None, len(flat), g.ctypes.data, fmt, out.ctypes.data if len(s) else None, len(s))))
     if got < 0:
         raise RuntimeError(_native.last_error())
     assert got == len(s), (got, len(s))
     return (out, g[:len(flat)]) if gains else out
+
+
+def signalMix(x, sources, terms, speechGain=1.0, dtype=np.float32, gains=False):
+    """pcmMix on a signal's row (speechPlayer_signalMix; no GPU): x is a one-dimensional int16 array (pcmMix's bits) or a float32 one,
+    taken as it is -- every sample finite and at most 2^16 in magnitude.  sources and terms as pcmMix's, but utterance= names a ROW: a
+    source of either dtype, whose power is signalPower's; noise= names a float32 clip.  An SNR is taken against signalPower(x).  The
+    statement BatchPlayer.mixedTensor(signal=...) is held to."""
+    s, inFormat = _signal_samples(x, "signalMix")
+    return _mix_statement("signalMix", _native.load().speechPlayer_signalMix, (s.ctypes.data if len(s) else None, inFormat), s, sources, terms, speechGain, dtype, gains)
+
+
+def signalPower(x):
+    """The power of a signal's row (speechPlayer_signalPower; no GPU): x as signalMix's.  int16: the exact integer sum of squares over
+    the length over 32767^2; float32: the squares in binary64 through the fixed tree of csrc/klatt_sigpower.h -- leaves of 8 samples in
+    ascending order, a balanced tree over the 256 leaves of a block of 2048, the blocks in ascending order -- over the length.  Whole-signal
+    mean squares, silences included; 0.0 for no samples.  The statement BatchPlayer.powerTensor(signal=...) is held to."""
+    s, inFormat = _signal_samples(x, "signalPower")
+    power = np.zeros(1, np.float64)
+    if _native.load().speechPlayer_signalPower(s.ctypes.data if len(s) else None, inFormat, len(s), power.ctypes.data) < 0:
+        raise RuntimeError(_native.last_error())
+    return float(power[0])
 
 
 def check_option_value(name, value):
@@ -1492,11 +1526,23 @@ class BatchPlayer(object):
         self._check(self._dll.speechPlayer_batch_noiseBank(self._h, power.ctypes.data, None, n))
         return power[:n]
 
-    def powerTensor(self, utterances=None):
+    def powerTensor(self, utterances=None, signal=None):
         """The exact sums of squares S_u = sum s(n)^2 of the chosen utterances' int16 PCM (speechPlayer_batch_exportPower), filled on torch's
         current stream behind the synthesis without a host wait: -> (sums, lengths), int64 tensors [n] on the batch's device.  The mean
-        square on the sample / 32767 scale is sums / lengths / 32767^2: the number every SNR starts from."""
+        square on the sample / 32767 scale is sums / lengths / 32767^2: the number every SNR starts from.
+        signal: the (tensor, lengths or offsets) pair another export returned (check_signal_request), read in place of the batch's PCM
+        (speechPlayer_batch_exportPowerOf): `utterances` then chooses rows of the signal and the result is (powers, lengths), the
+        float64 mean squares themselves -- of a wet signal, say --, which signalPower states on the host; no synthesis is needed."""
         import torch
+        if signal is not None:
+            sig, sel, n, lens = self._signal("powerTensor", signal, utterances)
+            dev = self.device
+            powers = torch.zeros(n, dtype=torch.float64, device="cuda:%d" % dev)
+            if n:
+                got = self._check(self._dll.speechPlayer_batch_exportPowerOf(self._h, sig[0].ctypes.data, _ptr(sel), n, powers.data_ptr(),
+                                                                             torch.cuda.current_stream(dev).cuda_stream))
+                assert got == n, (got, n)
+            return powers, torch.from_numpy(lens.astype(np.int64)).to("cuda:%d" % dev)
         sel, n, idx = self._selection("powerTensor", utterances)
         dev = self.device
         sums = torch.zeros(n, dtype=torch.int64, device="cuda:%d" % dev)
@@ -1505,7 +1551,7 @@ class BatchPlayer(object):
             assert got == n, (got, n)
         return sums, torch.from_numpy(self._lengths()[idx].astype(np.int64)).to("cuda:%d" % dev)
 
-    def mixedTensor(self, terms, speechGain=None, utterances=None, dtype=None, padded=True, gains=False):
+    def mixedTensor(self, terms, speechGain=None, utterances=None, dtype=None, padded=True, gains=False, signal=None):
         """The batch's PCM mixed with noise clips and other utterances as a torch tensor on the batch's device
         (speechPlayer_batch_exportMixed), filled on torch's current stream behind the synthesis without a host wait: -> (mixed, lengths).
         terms: one list of MixTerm per ROW (an empty list: the speech alone) -- with repeats in `utterances`, one utterance gets several
@@ -1514,11 +1560,25 @@ class BatchPlayer(object):
         gain= linear.  speechGain: None (1), one number or one per row.  A row keeps its length; utterances, padded and the
         (mixed, lengths) pair as pcmTensor's; dtype torch.float32 (default) or torch.int16 (clipped, rounded to nearest even).
         gains=True: -> (mixed, lengths, the float32 gains applied: a device tensor, one per term, termStart: an int64 CPU tensor).  The
-        batch must have been synthesised since it was set; pcmMix is the same definition on the host, which the device equals bit for bit."""
+        batch must have been synthesised since it was set; pcmMix is the same definition on the host, which the device equals bit for bit.
+        signal: the (tensor, lengths or offsets) pair another export returned (check_signal_request), mixed onto in place of the batch's
+        PCM (speechPlayer_batch_exportMixedOf) -- the speech after a room, say, so that an SNR is measured against the reverberant
+        speech: `utterances` then chooses rows of the signal, MixTerm(utterance=k) means row k of the signal (any row, the row's own
+        included), an SNR is against the row's signalPower, no synthesis is needed and signalMix is the host's statement."""
         import torch
+        dev = self.device
+        if signal is not None:
+            sig, sel, n, lens = self._signal("mixedTensor", signal, utterances)
+            flat, start, sg, fmt = check_mix_request(terms, n, speechGain, dtype, signalRows=int(sig[0]["nRows"][0]))
+            applied = torch.zeros(len(flat), dtype=torch.float32, device="cuda:%d" % dev) if gains else None
+
+            def call_of(out, stride, numel, stream):
+                return self._dll.speechPlayer_batch_exportMixedOf(self._h, sig[0].ctypes.data, _ptr(sel), n, flat.ctypes.data if len(flat) else None, start.ctypes.data,
+                                                                  _ptr(sg), applied.data_ptr() if gains and len(flat) else None, out, fmt, stride, stream)
+            out, second = self._export_rows(lens.astype(np.int64), (), torch.float32 if fmt else torch.int16, padded, call_of, always=True)
+            return (out, second, applied, torch.from_numpy(start)) if gains else (out, second)
         sel, n, idx = self._selection("mixedTensor", utterances)
         flat, start, sg, fmt = check_mix_request(terms, n, speechGain, dtype)
-        dev = self.device
         applied = torch.zeros(len(flat), dtype=torch.float32, device="cuda:%d" % dev) if gains else None
 
         def call(out, stride, numel, stream):
