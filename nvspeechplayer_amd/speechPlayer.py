@@ -297,11 +297,48 @@ def host_array(shape, dtype):
     return np.frombuffer(raw, dtype=dt, count=n).reshape(shape)
 
 
+def _as_array(a):
+    """A numpy array of `a` (numpy, sequence or torch tensor; a CUDA tensor is copied to the host, which synchronises), of whatever dtype
+    it has."""
+    return np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a)
+
+
 def _host_array(a, dtype):
-    """A numpy array of `a` (numpy, sequence or torch tensor; a CUDA tensor is copied to the host, which synchronises)."""
-    if hasattr(a, "detach") and hasattr(a, "cpu"):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(a, dtype=dtype)
+    """_as_array, contiguous and of `dtype`."""
+    return np.ascontiguousarray(_as_array(a), dtype=dtype)
+
+
+def _answer(got, expected=None, error=RuntimeError):
+    """The answer of a host statement of the library: a negative one raises `error` with the library's message; any other is the count
+    `expected` (None: whatever it is)."""
+    if got < 0:
+        raise error(_native.last_error())
+    assert expected is None or got == expected, (got, expected)
+    return got
+
+
+def _row_statement(what, s, inFormat, args, shape, dtype, counted=True):
+    """The host statement speechPlayer_<what> about one row of samples `s` (inFormat None: int16 PCM, a pcm* statement; else a signal*
+    one, which takes the format after the pointer): -> its output, a zeroed array of `shape` and `dtype` handed over after `args`,
+    followed by its size where the statement takes it (`counted`).  A row or an output of nothing is a null pointer."""
+    out = np.zeros(shape, dtype)
+    lead = (s.ctypes.data if len(s) else None,) + (() if inFormat is None else (inFormat,))
+    fn = getattr(_native.load(), "speechPlayer_" + what)
+    _answer(fn(*lead, len(s), *args, out.ctypes.data if out.size else None, *((out.size,) if counted else ())), out.size)
+    return out
+
+
+def _pcm_samples(pcm, what):
+    s = np.ascontiguousarray(np.asarray(pcm))
+    if s.dtype != np.int16 or s.ndim != 1:
+        raise TypeError("%s: pcm must be a one-dimensional int16 array, not %s %s" % (what, s.dtype, list(s.shape)))
+    return s
+
+
+def _step_counts(lens, hop, phase):
+    """The steps phase + j * hop below each of the lengths `lens` (one length: a number): int64."""
+    lens = np.asarray(lens, dtype=np.int64)
+    return np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
 
 
 def check_frames_tensor(frames, frameStart, device):
@@ -502,12 +539,8 @@ def frameResponse(frames, sampleRate, frequencies, kinds=("cascade_db", "paralle
         raise ValueError("frameResponse: sampleRate must be positive")
     freqs, ks = check_response_request(frequencies, kinds, int(sampleRate), "frameResponse")
     out = np.zeros((fr.shape[0], len(ks), len(freqs)), np.float64)
-    dll = _native.load()
-    got = dll.speechPlayer_frameResponse(fr.ctypes.data, fr.shape[0], int(sampleRate), freqs.ctypes.data, len(freqs), ks.ctypes.data, len(ks),
-                                         1 if gain else 0, out.ctypes.data)
-    if got < 0:
-        raise RuntimeError(_native.last_error())
-    assert got == out.size, (got, out.size)
+    _answer(_native.load().speechPlayer_frameResponse(fr.ctypes.data, fr.shape[0], int(sampleRate), freqs.ctypes.data, len(freqs), ks.ctypes.data, len(ks),
+                                                      1 if gain else 0, out.ctypes.data), out.size)
     return out
 
 
@@ -533,10 +566,8 @@ def resonatorCoefficients(f, bw, sampleRate, anti=False):
     if int(sampleRate) <= 0:
         raise ValueError("resonatorCoefficients: sampleRate must be positive")
     out = np.zeros((len(fr), 3), np.float64)
-    got = _native.load().speechPlayer_resonatorCoefficients(fr.ctypes.data, bws.ctypes.data, len(fr), 1 if anti else 0, int(sampleRate), out.ctypes.data)
-    if got < 0:
-        raise RuntimeError(_native.last_error())
-    assert got == len(fr), (got, len(fr))
+    _answer(_native.load().speechPlayer_resonatorCoefficients(fr.ctypes.data, bws.ctypes.data, len(fr), 1 if anti else 0, int(sampleRate), out.ctypes.data),
+            len(fr))
     return out
 
 
@@ -593,20 +624,15 @@ def pcmSpectrogram(pcm, nFft=1024, hop=256, phase=0, window=None, bank=None, pow
     """The STFT / band spectrogram of int16 PCM on the host (speechPlayer_pcmSpectrogram; no GPU): -> float64 [steps, bands], by the
     definition in include/speechPlayer_batch.h -- step j centred on sample phase + j * hop, zeros outside the signal, the float32
     transform the device runs.  Arguments as BatchPlayer.spectrogramTensor's."""
+    return _spectrogram_statement("pcmSpectrogram", _pcm_samples(pcm, "pcmSpectrogram"), None, nFft, hop, phase, window, bank, power, log, floor)
+
+
+def _spectrogram_statement(what, s, inFormat, nFft, hop, phase, window, bank, power, log, floor):
     import torch
-    s = np.ascontiguousarray(np.asarray(pcm))
-    if s.dtype != np.int16 or s.ndim != 1:
-        raise TypeError("pcmSpectrogram: pcm must be a one-dimensional int16 array, not %s %s" % (s.dtype, list(s.shape)))
     nFft, hop, phase, window, bank, bands, power, scale, floor, _ = check_spectrogram_request(nFft, hop, phase, window, bank, power, log, floor,
-                                                                                             torch.float64, "pcmSpectrogram")
-    steps = (len(s) - phase + hop - 1) // hop if len(s) > phase else 0
-    out = np.zeros((steps, bands), np.float64)
-    got = _native.load().speechPlayer_pcmSpectrogram(s.ctypes.data if len(s) else None, len(s), nFft, hop, phase, _ptr(window), _ptr(bank),
-                                                     bands if bank is not None else 0, power, scale, floor, out.ctypes.data if out.size else None)
-    if got < 0:
-        raise RuntimeError(_native.last_error())
-    assert got == out.size, (got, out.size)
-    return out
+                                                                                             torch.float64, what)
+    return _row_statement(what, s, inFormat, (nFft, hop, phase, _ptr(window), _ptr(bank), bands if bank is not None else 0, power, scale, floor),
+                          (int(_step_counts(len(s), hop, phase)), bands), np.float64, counted=False)
 
 
 def melFilterbank(sampleRate, nFft, nMels, fmin=0.0, fmax=None, norm=None):
@@ -676,24 +702,12 @@ def check_resample_request(srcRate, dstRate, zeros, rolloff, window, beta, dtype
     taps = 2 * int(math.ceil(wd))
     if up * taps > RESAMPLE_LIMITS[2]:
         raise ValueError("%s: a table of %d phases of %d taps is above %d values" % (what, up, taps, RESAMPLE_LIMITS[2]))
-    names = {"float32": 1, "int16": 0}
-    key = "float32" if dtype is None else (str(dtype).replace("torch.", "") if type(dtype).__module__.startswith("torch") else None)
-    if key is None:
-        try:
-            key = np.dtype(dtype).name
-        except TypeError:
-            key = repr(dtype)
-    if key not in names:
-        raise TypeError("%s: dtype must be float32 or int16, not %s" % (what, dtype))
-    return srcRate, dstRate, zeros, rolloff, win, beta, names[key], up, down, taps
+    return srcRate, dstRate, zeros, rolloff, win, beta, _sample_format(dtype, what), up, down, taps
 
 
 def resampledLength(length, srcRate, dstRate):
     """ceil(length * up / down) for the ratio the rates reduce to (speechPlayer_resampledLength; no GPU)."""
-    got = _native.load().speechPlayer_resampledLength(int(length), int(srcRate), int(dstRate))
-    if got < 0:
-        raise ValueError(_native.last_error())
-    return got
+    return _answer(_native.load().speechPlayer_resampledLength(int(length), int(srcRate), int(dstRate)), error=ValueError)
 
 
 def resampleKernel(srcRate, dstRate, zeros=6, rolloff=0.99, window="hann", beta=None):
@@ -704,11 +718,9 @@ def resampleKernel(srcRate, dstRate, zeros=6, rolloff=0.99, window="hann", beta=
                                                                                            "resampleKernel")
     table = np.zeros((up, taps), np.float64)
     u, d, t = c_int(0), c_int(0), c_int(0)
-    got = _native.load().speechPlayer_resampleKernel(srcRate, dstRate, zeros, rolloff, win, beta, byref(u), byref(d), byref(t), table.ctypes.data,
-                                                     table.size)
-    if got < 0:
-        raise RuntimeError(_native.last_error())
-    assert (got, u.value, d.value, t.value) == (table.size, up, down, taps), (got, u.value, d.value, t.value, up, down, taps)
+    _answer(_native.load().speechPlayer_resampleKernel(srcRate, dstRate, zeros, rolloff, win, beta, byref(u), byref(d), byref(t), table.ctypes.data,
+                                                       table.size), table.size)
+    assert (u.value, d.value, t.value) == (up, down, taps), (u.value, d.value, t.value, up, down, taps)
     return table, up, down
 
 
@@ -716,19 +728,13 @@ def pcmResample(pcm, srcRate, dstRate, zeros=6, rolloff=0.99, window="hann", bet
     """int16 PCM at another sample rate on the host (speechPlayer_pcmResample; no GPU): -> float32 (sample / 32767 scale) or int16
     [ceil(len * up / down)], by the definition in include/speechPlayer_batch.h -- the float32 statement the device runs.  Arguments as
     BatchPlayer.resampledTensor's; dtype np.float32 or np.int16."""
-    s = np.ascontiguousarray(np.asarray(pcm))
-    if s.dtype != np.int16 or s.ndim != 1:
-        raise TypeError("pcmResample: pcm must be a one-dimensional int16 array, not %s %s" % (s.dtype, list(s.shape)))
-    srcRate, dstRate, zeros, rolloff, win, beta, fmt, up, down, _ = check_resample_request(srcRate, dstRate, zeros, rolloff, window, beta, dtype,
-                                                                                          "pcmResample")
-    n = (len(s) * up + down - 1) // down
-    out = np.zeros(n, np.float32 if fmt else np.int16)
-    got = _native.load().speechPlayer_pcmResample(s.ctypes.data if len(s) else None, len(s), srcRate, dstRate, zeros, rolloff, win, beta, fmt,
-                                                  out.ctypes.data if n else None, n)
-    if got < 0:
-        raise RuntimeError(_native.last_error())
-    assert got == n, (got, n)
-    return out
+    return _resample_statement("pcmResample", _pcm_samples(pcm, "pcmResample"), None, srcRate, dstRate, zeros, rolloff, window, beta, dtype)
+
+
+def _resample_statement(what, s, inFormat, srcRate, dstRate, zeros, rolloff, window, beta, dtype):
+    srcRate, dstRate, zeros, rolloff, win, beta, fmt, up, down, _ = check_resample_request(srcRate, dstRate, zeros, rolloff, window, beta, dtype, what)
+    return _row_statement(what, s, inFormat, (srcRate, dstRate, zeros, rolloff, win, beta, fmt), (len(s) * up + down - 1) // down,
+                          np.float32 if fmt else np.int16)
 
 
 CONVOLVE_TILE = 1024             # kConvolveTile of csrc/klatt_convolve.h: consecutive outputs of one row a workgroup takes at a time
@@ -755,7 +761,7 @@ def check_convolve_request(irs, irOf, nRows, tail, dtype, what="convolvedTensor"
     flat, start = [], [0]
     for j, h in enumerate(irs):
         try:
-            a = np.asarray(h.detach().cpu().numpy() if hasattr(h, "detach") else h)
+            a = _as_array(h)
         except Exception:
             raise TypeError("%s: response %d is not an array" % (what, j))
         if a.ndim != 1 or a.dtype.kind not in "fiu":
@@ -776,7 +782,7 @@ def check_convolve_request(irs, irOf, nRows, tail, dtype, what="convolvedTensor"
             raise ValueError("%s: irOf is needed with %d impulse responses" % (what, len(irs)))
         of = None
     else:
-        of = np.asarray(irOf.detach().cpu().numpy() if hasattr(irOf, "detach") else irOf)
+        of = _as_array(irOf)
         if of.dtype.kind not in "iu" or of.ndim != 1:
             raise TypeError("%s: irOf must be a one-dimensional array of integers, not %s %s" % (what, of.dtype, list(of.shape)))
         if len(of) != nRows:
@@ -788,34 +794,19 @@ def check_convolve_request(irs, irOf, nRows, tail, dtype, what="convolvedTensor"
         tail = int(tail)
     elif not isinstance(tail, (int, np.integer)) or tail not in (0, 1):
         raise ValueError("%s: tail must be True or False (1 or 0), not %r" % (what, tail))
-    names = {"float32": 1, "int16": 0}
-    key = "float32" if dtype is None else (str(dtype).replace("torch.", "") if type(dtype).__module__.startswith("torch") else None)
-    if key is None:
-        try:
-            key = np.dtype(dtype).name
-        except TypeError:
-            key = repr(dtype)
-    if key not in names:
-        raise TypeError("%s: dtype must be float32 or int16, not %s" % (what, dtype))
-    return np.ascontiguousarray(np.concatenate(flat)), np.array(start, np.int64), of, int(tail), names[key]
+    return np.ascontiguousarray(np.concatenate(flat)), np.array(start, np.int64), of, int(tail), _sample_format(dtype, what)
 
 
 def pcmConvolve(pcm, ir, tail=True, dtype=np.float32):
     """int16 PCM convolved with one impulse response on the host (speechPlayer_pcmConvolve; no GPU): -> float32 (sample / 32767 scale)
     or int16, len(pcm) + len(ir) - 1 values (tail) or len(pcm), by the definition in include/speechPlayer_batch.h -- the chain of float32
     fused multiply-adds the device runs, in ascending tap order."""
-    s = np.ascontiguousarray(np.asarray(pcm))
-    if s.dtype != np.int16 or s.ndim != 1:
-        raise TypeError("pcmConvolve: pcm must be a one-dimensional int16 array, not %s %s" % (s.dtype, list(s.shape)))
-    h, start, _, tail, fmt = check_convolve_request(ir, None, 1, tail, dtype, "pcmConvolve")
-    n = len(s) + len(h) - 1 if tail else len(s)
-    out = np.zeros(n, np.float32 if fmt else np.int16)
-    got = _native.load().speechPlayer_pcmConvolve(s.ctypes.data if len(s) else None, len(s), h.ctypes.data, len(h), tail, fmt,
-                                                  out.ctypes.data if n else None, n)
-    if got < 0:
-        raise RuntimeError(_native.last_error())
-    assert got == n, (got, n)
-    return out
+    return _convolve_statement("pcmConvolve", _pcm_samples(pcm, "pcmConvolve"), None, ir, tail, dtype)
+
+
+def _convolve_statement(what, s, inFormat, ir, tail, dtype):
+    h, start, _, tail, fmt = check_convolve_request(ir, None, 1, tail, dtype, what)
+    return _row_statement(what, s, inFormat, (h.ctypes.data, len(h), tail, fmt), len(s) + len(h) - 1 if tail else len(s), np.float32 if fmt else np.int16)
 
 
 SIGNAL_MAX_LENGTH = 1 << 44      # kSignalMaxLength of csrc/klatt_tiles.h: samples of one row
@@ -845,7 +836,7 @@ def check_signal_request(signal, device=None, what="signal"):
     if second is None or isinstance(second, str):
         raise TypeError("%s: the row lengths (padded) or offsets (packed) are missing" % what)
     try:
-        ext = np.asarray(second.detach().cpu().numpy() if hasattr(second, "detach") else second)
+        ext = _as_array(second)
     except Exception:
         raise TypeError("%s: the row lengths or offsets are not an array" % what)
     if ext.size == 0:
@@ -887,6 +878,42 @@ def check_signal_request(signal, device=None, what="signal"):
     return tensor, 1 if tensor.dtype == torch.float32 else 0, n, stride, ext, np.ascontiguousarray(lens.astype(np.int64))
 
 
+class RowSource(object):
+    """What an export reads and the rows chosen from it, without a GPU: `count` rows called `noun`s ("utterance": the batch's PCM pool;
+    "row": a signal) of `lengths` -- an array, or a function that gives one, called when the lengths are first asked for: the pool's
+    cost a library call -- and `utterances`, indices in any order, repeats allowed (None: all, in order; ValueError for one outside
+    [0, count), in the words of `what`).  sel: the choice as an int64 array, or None; n: the rows chosen; idx: their numbers; lengths:
+    their lengths, int64.  lead and suffix: what an entry point over this source takes between the batch and the selection, and what
+    its name ends in -- nothing over the pool; of_signal: the speechPlayer_signal_t record, and "Of"."""
+    lead, suffix = (), ""
+
+    def __init__(self, what, noun, count, lengths, utterances):
+        self.count, self._lengths = count, lengths
+        self.sel = None if utterances is None else _host_array(utterances, np.int64).reshape(-1)
+        self.n = count if self.sel is None else len(self.sel)
+        self.idx = np.arange(self.n) if self.sel is None else self.sel
+        if self.n and (self.idx.min() < 0 or self.idx.max() >= count):
+            raise ValueError("%s: %s numbers must lie in [0, %d)" % (what, noun, count))
+
+    @property
+    def lengths(self):
+        lens = self._lengths() if callable(self._lengths) else self._lengths
+        return lens[self.idx].astype(np.int64)
+
+    @classmethod
+    def of_signal(cls, what, signal, device, utterances):
+        """The rows chosen from a signal= argument (check_signal_request; device None: wherever it is).  `record` is the
+        speechPlayer_signal_t the entry point reads; it, the tensor and the extents it points to live as long as the source."""
+        tensor, fmt, rows, stride, extent, lens = check_signal_request(signal, device, what)
+        src = cls(what, "row", rows, lens, utterances)
+        src.record = np.zeros(1, _signalDtype)
+        src.record["data"], src.record["format"], src.record["nRows"], src.record["rowStride"], src.record["extent"] = (
+            tensor.data_ptr(), fmt, rows, stride, extent.ctypes.data)
+        src.held = (tensor, extent)
+        src.lead, src.suffix = (src.record.ctypes.data,), "Of"
+        return src
+
+
 def _signal_samples(x, what):
     s = x if isinstance(x, np.ndarray) else None
     if s is None or s.ndim != 1 or s.dtype not in (np.int16, np.float32):
@@ -899,49 +926,19 @@ def signalSpectrogram(x, nFft=1024, hop=256, phase=0, window=None, bank=None, po
     """pcmSpectrogram on a signal's row (speechPlayer_signalSpectrogram; no GPU): x is a one-dimensional int16 array (pcmSpectrogram's
     bits) or a float32 one, taken as it is -- every sample finite and at most 2^16 in magnitude.  -> float64 [steps, bands]: the
     statement BatchPlayer.spectrogramTensor(signal=...) is held to."""
-    import torch
-    s, inFormat = _signal_samples(x, "signalSpectrogram")
-    nFft, hop, phase, window, bank, bands, power, scale, floor, _ = check_spectrogram_request(nFft, hop, phase, window, bank, power, log, floor,
-                                                                                             torch.float64, "signalSpectrogram")
-    steps = (len(s) - phase + hop - 1) // hop if len(s) > phase else 0
-    out = np.zeros((steps, bands), np.float64)
-    got = _native.load().speechPlayer_signalSpectrogram(s.ctypes.data if len(s) else None, inFormat, len(s), nFft, hop, phase, _ptr(window), _ptr(bank),
-                                                        bands if bank is not None else 0, power, scale, floor, out.ctypes.data if out.size else None)
-    if got < 0:
-        raise RuntimeError(_native.last_error())
-    assert got == out.size, (got, out.size)
-    return out
+    return _spectrogram_statement("signalSpectrogram", *_signal_samples(x, "signalSpectrogram"), nFft, hop, phase, window, bank, power, log, floor)
 
 
 def signalResample(x, srcRate, dstRate, zeros=6, rolloff=0.99, window="hann", beta=None, dtype=np.float32):
     """pcmResample on a signal's row (speechPlayer_signalResample; no GPU): x as signalSpectrogram's.  -> float32 or int16
     [ceil(len * up / down)]; equal rates give the samples themselves.  The statement BatchPlayer.resampledTensor(signal=...) is held to."""
-    s, inFormat = _signal_samples(x, "signalResample")
-    srcRate, dstRate, zeros, rolloff, win, beta, fmt, up, down, _ = check_resample_request(srcRate, dstRate, zeros, rolloff, window, beta, dtype,
-                                                                                          "signalResample")
-    n = (len(s) * up + down - 1) // down
-    out = np.zeros(n, np.float32 if fmt else np.int16)
-    got = _native.load().speechPlayer_signalResample(s.ctypes.data if len(s) else None, inFormat, len(s), srcRate, dstRate, zeros, rolloff, win, beta, fmt,
-                                                     out.ctypes.data if n else None, n)
-    if got < 0:
-        raise RuntimeError(_native.last_error())
-    assert got == n, (got, n)
-    return out
+    return _resample_statement("signalResample", *_signal_samples(x, "signalResample"), srcRate, dstRate, zeros, rolloff, window, beta, dtype)
 
 
 def signalConvolve(x, ir, tail=True, dtype=np.float32):
     """pcmConvolve on a signal's row (speechPlayer_signalConvolve; no GPU): x as signalSpectrogram's.  -> float32 or int16, len(x) +
     len(ir) - 1 values (tail) or len(x).  The statement BatchPlayer.convolvedTensor(signal=...) is held to."""
-    s, inFormat = _signal_samples(x, "signalConvolve")
-    h, start, _, tail, fmt = check_convolve_request(ir, None, 1, tail, dtype, "signalConvolve")
-    n = len(s) + len(h) - 1 if tail else len(s)
-    out = np.zeros(n, np.float32 if fmt else np.int16)
-    got = _native.load().speechPlayer_signalConvolve(s.ctypes.data if len(s) else None, inFormat, len(s), h.ctypes.data, len(h), tail, fmt,
-                                                     out.ctypes.data if n else None, n)
-    if got < 0:
-        raise RuntimeError(_native.last_error())
-    assert got == n, (got, n)
-    return out
+    return _convolve_statement("signalConvolve", *_signal_samples(x, "signalConvolve"), ir, tail, dtype)
 
 
 MIX_TILE = 1024                  # kMixTile of csrc/klatt_mix.h: consecutive outputs of one row a workgroup takes at a time
@@ -1000,7 +997,9 @@ def _mix_terms(terms, what):
     return np.array([t.record() for t in terms], dtype=mixTermDtype).reshape(-1)
 
 
-def _mix_format(dtype, what):
+def _sample_format(dtype, what):
+    """dtype None / torch.float32 / np.float32 / "float32" or torch.int16 / np.int16 / "int16" (TypeError): -> the format of exported
+    samples, 1 float32 or 0 int16."""
     names = {"float32": 1, "int16": 0}
     key = "float32" if dtype is None else (str(dtype).replace("torch.", "") if type(dtype).__module__.startswith("torch") else None)
     if key is None:
@@ -1023,7 +1022,7 @@ def check_mix_request(terms, nRows, speechGain, dtype, what="mixedTensor", signa
     0 int16, 1 float32)."""
     if isinstance(terms, tuple) and len(terms) == 2 and isinstance(terms[0], np.ndarray):
         flat = _mix_terms(terms[0], what)
-        start = np.asarray(terms[1].detach().cpu().numpy() if hasattr(terms[1], "detach") else terms[1])
+        start = _as_array(terms[1])
         if start.dtype.kind not in "iu" or start.ndim != 1:
             raise TypeError("%s: termStart must be a one-dimensional array of integers, not %s %s" % (what, start.dtype, list(start.shape)))
         start = np.ascontiguousarray(start.astype(np.int64))
@@ -1053,18 +1052,18 @@ def check_mix_request(terms, nRows, speechGain, dtype, what="mixedTensor", signa
             raise ValueError("%s: row %d, term %d: source %d is not a row of the signal (%d)" % (what, row, bad[0] - start[row], flat["source"][bad[0]], signalRows))
     sg = None
     if speechGain is not None:
-        sg = np.asarray(speechGain.detach().cpu().numpy() if hasattr(speechGain, "detach") else speechGain)
+        sg = _as_array(speechGain)
         if sg.dtype.kind not in "fiu" or sg.ndim > 1:
             raise TypeError("%s: speechGain must be a number or a one-dimensional array of them, not %s %s" % (what, sg.dtype, list(sg.shape)))
         if sg.ndim == 1 and len(sg) != nRows:
             raise ValueError("%s: speechGain has %d entries for %d rows" % (what, len(sg), nRows))
         with np.errstate(over="ignore"):
             sg = np.ascontiguousarray(np.broadcast_to(sg.astype(np.float32), (nRows,)))
-    return flat, start, sg, _mix_format(dtype, what)
+    return flat, start, sg, _sample_format(dtype, what)
 
 
 def _mix_clip(a, what, name):
-    a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a)
+    a = _as_array(a)
     if a.ndim != 1 or a.dtype.kind != "f":
         raise TypeError("%s: %s must be a one-dimensional array of floats, not %s %s" % (what, name, a.dtype, list(a.shape)))
     with np.errstate(over="ignore"):
@@ -1077,30 +1076,23 @@ def pcmMix(pcm, sources, terms, speechGain=1.0, dtype=np.float32, gains=False):
     of one-dimensional arrays, float32 (a noise clip) or int16 (an utterance); terms: MixTerm objects (or an array of mixTermDtype) whose
     noise= / utterance= index `sources` -- noise= a float32 source, utterance= an int16 one.  An SNR is taken against the whole-signal
     mean square of `pcm` at gain 1.  gains=True: -> (mixed, the float32 gains applied, one per term)."""
-    s = np.ascontiguousarray(np.asarray(pcm))
-    if s.dtype != np.int16 or s.ndim != 1:
-        raise TypeError("pcmMix: pcm must be a one-dimensional int16 array, not %s %s" % (s.dtype, list(s.shape)))
-    return _mix_statement("pcmMix", _native.load().speechPlayer_pcmMix, (s.ctypes.data if len(s) else None,), s, sources, terms, speechGain, dtype, gains)
+    return _mix_statement("pcmMix", _pcm_samples(pcm, "pcmMix"), None, sources, terms, speechGain, dtype, gains)
 
 
-def _mix_statement(what, fn, lead, s, sources, terms, speechGain, dtype, gains):
+def _mix_statement(what, s, inFormat, sources, terms, speechGain, dtype, gains):
     if not isinstance(sources, (list, tuple)):
         raise TypeError("%s: sources must be a list of one-dimensional arrays" % what)
     held, table = [], np.zeros(max(len(sources), 1), _mixSourceDtype)
     for k, a in enumerate(sources):
-        a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a)
+        a = _as_array(a)
         a = np.ascontiguousarray(a) if a.dtype == np.int16 and a.ndim == 1 else _mix_clip(a, what, "source %d" % k)
         held.append(a)
         table[k] = (a.ctypes.data if len(a) else 0, len(a), 0 if a.dtype == np.int16 else 1, 0)
     flat = _mix_terms(terms, what)
-    fmt = _mix_format(dtype, what)
-    out = np.zeros(len(s), np.float32 if fmt else np.int16)
+    fmt = _sample_format(dtype, what)
     g = np.zeros(max(len(flat), 1), np.float32)
-    got = fn(*(lead + (len(s), float(np.float32(speechGain)), table.ctypes.data if len(sources) else None, len(sources),
-                       flat.ctypes.data if len(flat) else None, len(flat), g.ctypes.data, fmt, out.ctypes.data if len(s) else None, len(s))))
-    if got < 0:
-        raise RuntimeError(_native.last_error())
-    assert got == len(s), (got, len(s))
+    out = _row_statement(what, s, inFormat, (float(np.float32(speechGain)), table.ctypes.data if len(sources) else None, len(sources),
+                                             flat.ctypes.data if len(flat) else None, len(flat), g.ctypes.data, fmt), len(s), np.float32 if fmt else np.int16)
     return (out, g[:len(flat)]) if gains else out
 
 
@@ -1109,8 +1101,7 @@ def signalMix(x, sources, terms, speechGain=1.0, dtype=np.float32, gains=False):
     taken as it is -- every sample finite and at most 2^16 in magnitude.  sources and terms as pcmMix's, but utterance= names a ROW: a
     source of either dtype, whose power is signalPower's; noise= names a float32 clip.  An SNR is taken against signalPower(x).  The
     statement BatchPlayer.mixedTensor(signal=...) is held to."""
-    s, inFormat = _signal_samples(x, "signalMix")
-    return _mix_statement("signalMix", _native.load().speechPlayer_signalMix, (s.ctypes.data if len(s) else None, inFormat), s, sources, terms, speechGain, dtype, gains)
+    return _mix_statement("signalMix", *_signal_samples(x, "signalMix"), sources, terms, speechGain, dtype, gains)
 
 
 def signalPower(x):
@@ -1120,8 +1111,7 @@ def signalPower(x):
     mean squares, silences included; 0.0 for no samples.  The statement BatchPlayer.powerTensor(signal=...) is held to."""
     s, inFormat = _signal_samples(x, "signalPower")
     power = np.zeros(1, np.float64)
-    if _native.load().speechPlayer_signalPower(s.ctypes.data if len(s) else None, inFormat, len(s), power.ctypes.data) < 0:
-        raise RuntimeError(_native.last_error())
+    _answer(_native.load().speechPlayer_signalPower(s.ctypes.data if len(s) else None, inFormat, len(s), power.ctypes.data))
     return float(power[0])
 
 
@@ -1243,11 +1233,11 @@ class BatchPlayer(object):
         dtype = torch.float32 if dtype is None else dtype
         if dtype not in (torch.float32, torch.int16):
             raise TypeError("pcmTensor: dtype must be torch.float32 or torch.int16, not %s" % dtype)
-        sel, n, idx = self._selection("pcmTensor", utterances)
+        src = self._rows("pcmTensor", None, utterances)
 
         def call(out, stride, numel, stream):
-            return self._dll.speechPlayer_batch_exportPcm(self._h, _ptr(sel), n, out, 1 if dtype == torch.float32 else 0, stride, stream)
-        return self._export_rows(self._lengths()[idx], (), dtype, padded, call)
+            return self._dll.speechPlayer_batch_exportPcm(self._h, _ptr(src.sel), src.n, out, 1 if dtype == torch.float32 else 0, stride, stream)
+        return self._export_rows(src.lengths, (), dtype, padded, call)
 
     def timeline(self, u):
         """When utterance u's requests are dequeued (speechPlayer_batch_timeline): -> (firstSample int64 [n + 1], userIndex int32 [n]);
@@ -1285,32 +1275,21 @@ class BatchPlayer(object):
         """True when the batch carries phoneme labels: set by setIpa, setText or setRecords(..., labels=...); any other set call drops them."""
         return self._check(self._dll.speechPlayer_batch_hasLabels(self._h)) == 1
 
-    def _selection(self, what, utterances):
-        sel = None if utterances is None else _host_array(utterances, np.int64).reshape(-1)
-        n = self.nUtterances if sel is None else len(sel)
-        idx = np.arange(n) if sel is None else sel
-        if n and (idx.min() < 0 or idx.max() >= self.nUtterances):
-            raise ValueError("%s: utterance numbers must lie in [0, %d)" % (what, self.nUtterances))
-        return sel, n, idx
+    def _rows(self, what, signal, utterances):
+        """The RowSource an export reads: `utterances` of the batch's PCM pool, or (signal not None) rows of that signal on the batch's device."""
+        if signal is None:
+            return RowSource(what, "utterance", self.nUtterances, self._lengths, utterances)
+        return RowSource.of_signal(what, signal, self.device, utterances)
+
+    def _entry(self, name, src):
+        """The entry point speechPlayer_batch_export<name> over `src`, the pool's or the signal's (...Of), taking what follows the selection."""
+        fn = getattr(self._dll, "speechPlayer_batch_export" + name + src.suffix)
+        return lambda *args: fn(self._h, *src.lead, _ptr(src.sel), src.n, *args)
 
     def _steps(self, what, utterances, hop, phase):
         """The selection and its rows' step counts: the samples phase + j * hop below each utterance's length."""
-        sel, n, idx = self._selection(what, utterances)
-        lens = self._lengths()[idx]
-        return sel, n, np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
-
-    def _signal(self, what, signal, utterances):
-        """A signal= argument (check_signal_request) and the rows chosen from it: -> (the speechPlayer_signal_t record and what it points
-        to -- keep it until the call has returned --, the chosen rows or None, their number, their lengths)."""
-        tensor, fmt, rows, stride, extent, lens = check_signal_request(signal, self.device, what)
-        sel = None if utterances is None else _host_array(utterances, np.int64).reshape(-1)
-        n = rows if sel is None else len(sel)
-        idx = np.arange(n) if sel is None else sel
-        if n and (idx.min() < 0 or idx.max() >= rows):
-            raise ValueError("%s: row numbers must lie in [0, %d)" % (what, rows))
-        rec = np.zeros(1, _signalDtype)
-        rec["data"], rec["format"], rec["nRows"], rec["rowStride"], rec["extent"] = tensor.data_ptr(), fmt, rows, stride, extent.ctypes.data
-        return (rec, tensor, extent), sel, n, lens[idx]
+        src = self._rows(what, None, utterances)
+        return src.sel, src.n, _step_counts(src.lengths, hop, phase)
 
     def _export_rows(self, counts, tail_shape, dtype, padded, call, always=False):
         """The output of an export of len(counts) rows of counts[i] entries of shape tail_shape: [n, most, ...] (padded) or [total, ...],
@@ -1352,10 +1331,10 @@ class BatchPlayer(object):
         """Units (by="frame": frames) of the chosen utterances (speechPlayer_batch_unitCounts): an int64 array."""
         if by not in ("unit", "frame"):
             raise ValueError("by must be 'unit' or 'frame', not %r" % (by,))
-        sel, n, _ = self._selection("unitCounts", utterances)
-        counts = np.zeros(max(n, 1), np.int64)
-        self._check(self._dll.speechPlayer_batch_unitCounts(self._h, _ptr(sel), n, int(by == "frame"), counts.ctypes.data))
-        return counts[:n]
+        src = self._rows("unitCounts", None, utterances)
+        counts = np.zeros(max(src.n, 1), np.int64)
+        self._check(self._dll.speechPlayer_batch_unitCounts(self._h, _ptr(src.sel), src.n, int(by == "frame"), counts.ctypes.data))
+        return counts[:src.n]
 
     def unitTensor(self, hop=1, phase=0, utterances=None, by="unit", padded=True, pad=-1):
         """The segment table of a batch set from IPA text (speechPlayer_batch_exportUnits), an int64 torch tensor on the batch's device
@@ -1368,10 +1347,10 @@ class BatchPlayer(object):
         hop, phase = int(hop), int(phase)
         if hop < 1 or phase < 0:
             raise ValueError("unitTensor: hop must be at least 1 and phase not negative (%d, %d)" % (hop, phase))
-        sel, n, _ = self._selection("unitTensor", utterances)
+        src = self._rows("unitTensor", None, utterances)
 
         def call(out, stride, numel, stream):
-            return self._dll.speechPlayer_batch_exportUnits(self._h, _ptr(sel), n, hop, phase, int(by == "frame"), out, stride, int(pad), numel, stream)
+            return self._dll.speechPlayer_batch_exportUnits(self._h, _ptr(src.sel), src.n, hop, phase, int(by == "frame"), out, stride, int(pad), numel, stream)
         return self._export_rows(self.unitCounts(utterances, by), (len(UNIT_COLUMNS),), torch.int64, padded, call)
 
     def sourceTensor(self, columns, hop=1, phase=0, utterances=None, dtype=None, padded=True):
@@ -1425,20 +1404,12 @@ class BatchPlayer(object):
         lengths, no synthesis is needed and signalSpectrogram is the host's statement.  The signal is read on torch's current stream."""
         import torch
         nFft, hop, phase, window, bank, bands, power, scale, floor, fmt = check_spectrogram_request(nFft, hop, phase, window, bank, power, log, floor, dtype)
-        if signal is not None:
-            sig, sel, n, lens = self._signal("spectrogramTensor", signal, utterances)
-            steps = np.where(lens > phase, (lens - phase + hop - 1) // hop, 0).astype(np.int64)
-
-            def call_of(out, stride, numel, stream):
-                return self._dll.speechPlayer_batch_exportSpectrogramOf(self._h, sig[0].ctypes.data, _ptr(sel), n, nFft, hop, phase, _ptr(window), _ptr(bank),
-                                                                        bands if bank is not None else 0, power, scale, floor, out, fmt, stride, stream)
-            return self._export_rows(steps, (bands,), torch.float32 if fmt else torch.float64, padded, call_of)
-        sel, n, steps = self._steps("spectrogramTensor", utterances, hop, phase)
+        src = self._rows("spectrogramTensor", signal, utterances)
+        export = self._entry("Spectrogram", src)
 
         def call(out, stride, numel, stream):
-            return self._dll.speechPlayer_batch_exportSpectrogram(self._h, _ptr(sel), n, nFft, hop, phase, _ptr(window), _ptr(bank),
-                                                                  bands if bank is not None else 0, power, scale, floor, out, fmt, stride, stream)
-        return self._export_rows(steps, (bands,), torch.float32 if fmt else torch.float64, padded, call)
+            return export(nFft, hop, phase, _ptr(window), _ptr(bank), bands if bank is not None else 0, power, scale, floor, out, fmt, stride, stream)
+        return self._export_rows(_step_counts(src.lengths, hop, phase), (bands,), torch.float32 if fmt else torch.float64, padded, call)
 
     def resampledTensor(self, rate, zeros=6, rolloff=0.99, window="hann", beta=None, utterances=None, dtype=None, padded=True, signal=None,
                         signalRate=None):
@@ -1453,24 +1424,17 @@ class BatchPlayer(object):
         (speechPlayer_batch_exportResampledOf) at signalRate Hz (None: the batch's rate): `utterances` then chooses rows of the signal, no
         synthesis is needed, equal rates give the signal's samples and signalResample is the host's statement."""
         import torch
-        if signal is not None:
-            src, rate, zeros, rolloff, win, beta, fmt, up, down, _ = check_resample_request(self.sampleRate if signalRate is None else signalRate, rate, zeros,
-                                                                                            rolloff, window, beta, dtype)
-            sig, sel, n, lens = self._signal("resampledTensor", signal, utterances)
-
-            def call_of(out, stride, numel, stream):
-                return self._dll.speechPlayer_batch_exportResampledOf(self._h, sig[0].ctypes.data, _ptr(sel), n, src, rate, zeros, rolloff, win, beta, out, fmt,
-                                                                      stride, stream)
-            return self._export_rows((lens * up + down - 1) // down, (), torch.float32 if fmt else torch.int16, padded, call_of)
-        if signalRate is not None:
+        if signal is None and signalRate is not None:
             raise ValueError("resampledTensor: signalRate comes with a signal")
-        _, rate, zeros, rolloff, win, beta, fmt, up, down, _ = check_resample_request(self.sampleRate, rate, zeros, rolloff, window, beta, dtype)
-        sel, n, idx = self._selection("resampledTensor", utterances)
-        lens = (self._lengths()[idx].astype(np.int64) * up + down - 1) // down
+        srcRate, rate, zeros, rolloff, win, beta, fmt, up, down, _ = check_resample_request(self.sampleRate if signalRate is None else signalRate, rate, zeros,
+                                                                                            rolloff, window, beta, dtype)
+        src = self._rows("resampledTensor", signal, utterances)
+        export = self._entry("Resampled", src)
+        rates = (rate,) if signal is None else (srcRate, rate)      # (the pool's rate is the batch's)
 
         def call(out, stride, numel, stream):
-            return self._dll.speechPlayer_batch_exportResampled(self._h, _ptr(sel), n, rate, zeros, rolloff, win, beta, out, fmt, stride, stream)
-        return self._export_rows(lens, (), torch.float32 if fmt else torch.int16, padded, call)
+            return export(*rates, zeros, rolloff, win, beta, out, fmt, stride, stream)
+        return self._export_rows((src.lengths * up + down - 1) // down, (), torch.float32 if fmt else torch.int16, padded, call)
 
     def convolvedTensor(self, irs, irOf=None, tail=True, utterances=None, dtype=None, padded=True, signal=None):
         """The batch's PCM convolved with impulse responses as a torch tensor on the batch's device
@@ -1485,24 +1449,14 @@ class BatchPlayer(object):
         (speechPlayer_batch_exportConvolvedOf): `utterances` then chooses rows of the signal, irOf stays per output row, no synthesis is
         needed and signalConvolve is the host's statement."""
         import torch
-        if signal is not None:
-            sig, sel, n, lens = self._signal("convolvedTensor", signal, utterances)
-            h, start, of, tail, fmt = check_convolve_request(irs, irOf, n, tail, dtype)
-            taps = np.diff(start)[of if of is not None else np.zeros(n, np.int64)]
-
-            def call_of(out, stride, numel, stream):
-                return self._dll.speechPlayer_batch_exportConvolvedOf(self._h, sig[0].ctypes.data, _ptr(sel), n, h.ctypes.data, start.ctypes.data, len(start) - 1,
-                                                                      _ptr(of), tail, out, fmt, stride, stream)
-            return self._export_rows(lens + (taps - 1 if tail else 0), (), torch.float32 if fmt else torch.int16, padded, call_of)
-        sel, n, idx = self._selection("convolvedTensor", utterances)
-        h, start, of, tail, fmt = check_convolve_request(irs, irOf, n, tail, dtype)
-        taps = np.diff(start)[of if of is not None else np.zeros(n, np.int64)]
-        lens = self._lengths()[idx].astype(np.int64) + (taps - 1 if tail else 0)
+        src = self._rows("convolvedTensor", signal, utterances)
+        export = self._entry("Convolved", src)
+        h, start, of, tail, fmt = check_convolve_request(irs, irOf, src.n, tail, dtype)
+        taps = np.diff(start)[of if of is not None else np.zeros(src.n, np.int64)]
 
         def call(out, stride, numel, stream):
-            return self._dll.speechPlayer_batch_exportConvolved(self._h, _ptr(sel), n, h.ctypes.data, start.ctypes.data, len(start) - 1, _ptr(of),
-                                                                tail, out, fmt, stride, stream)
-        return self._export_rows(lens, (), torch.float32 if fmt else torch.int16, padded, call)
+            return export(h.ctypes.data, start.ctypes.data, len(start) - 1, _ptr(of), tail, out, fmt, stride, stream)
+        return self._export_rows(src.lengths + (taps - 1 if tail else 0), (), torch.float32 if fmt else torch.int16, padded, call)
 
     def setNoiseBank(self, clips):
         """The batch's noise bank (speechPlayer_batch_setNoiseBank): a list of one-dimensional float arrays (kept as float32), every value
@@ -1534,22 +1488,13 @@ class BatchPlayer(object):
         (speechPlayer_batch_exportPowerOf): `utterances` then chooses rows of the signal and the result is (powers, lengths), the
         float64 mean squares themselves -- of a wet signal, say --, which signalPower states on the host; no synthesis is needed."""
         import torch
-        if signal is not None:
-            sig, sel, n, lens = self._signal("powerTensor", signal, utterances)
-            dev = self.device
-            powers = torch.zeros(n, dtype=torch.float64, device="cuda:%d" % dev)
-            if n:
-                got = self._check(self._dll.speechPlayer_batch_exportPowerOf(self._h, sig[0].ctypes.data, _ptr(sel), n, powers.data_ptr(),
-                                                                             torch.cuda.current_stream(dev).cuda_stream))
-                assert got == n, (got, n)
-            return powers, torch.from_numpy(lens.astype(np.int64)).to("cuda:%d" % dev)
-        sel, n, idx = self._selection("powerTensor", utterances)
+        src = self._rows("powerTensor", signal, utterances)
         dev = self.device
-        sums = torch.zeros(n, dtype=torch.int64, device="cuda:%d" % dev)
-        if n:
-            got = self._check(self._dll.speechPlayer_batch_exportPower(self._h, _ptr(sel), n, sums.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-            assert got == n, (got, n)
-        return sums, torch.from_numpy(self._lengths()[idx].astype(np.int64)).to("cuda:%d" % dev)
+        out = torch.zeros(src.n, dtype=torch.int64 if signal is None else torch.float64, device="cuda:%d" % dev)      # (sums, or powers)
+        if src.n:
+            got = self._check(self._entry("Power", src)(out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            assert got == src.n, (got, src.n)
+        return out, torch.from_numpy(src.lengths).to("cuda:%d" % dev)
 
     def mixedTensor(self, terms, speechGain=None, utterances=None, dtype=None, padded=True, gains=False, signal=None):
         """The batch's PCM mixed with noise clips and other utterances as a torch tensor on the batch's device
@@ -1567,25 +1512,16 @@ class BatchPlayer(object):
         included), an SNR is against the row's signalPower, no synthesis is needed and signalMix is the host's statement."""
         import torch
         dev = self.device
-        if signal is not None:
-            sig, sel, n, lens = self._signal("mixedTensor", signal, utterances)
-            flat, start, sg, fmt = check_mix_request(terms, n, speechGain, dtype, signalRows=int(sig[0]["nRows"][0]))
-            applied = torch.zeros(len(flat), dtype=torch.float32, device="cuda:%d" % dev) if gains else None
-
-            def call_of(out, stride, numel, stream):
-                return self._dll.speechPlayer_batch_exportMixedOf(self._h, sig[0].ctypes.data, _ptr(sel), n, flat.ctypes.data if len(flat) else None, start.ctypes.data,
-                                                                  _ptr(sg), applied.data_ptr() if gains and len(flat) else None, out, fmt, stride, stream)
-            out, second = self._export_rows(lens.astype(np.int64), (), torch.float32 if fmt else torch.int16, padded, call_of, always=True)
-            return (out, second, applied, torch.from_numpy(start)) if gains else (out, second)
-        sel, n, idx = self._selection("mixedTensor", utterances)
-        flat, start, sg, fmt = check_mix_request(terms, n, speechGain, dtype)
+        src = self._rows("mixedTensor", signal, utterances)
+        export = self._entry("Mixed", src)
+        flat, start, sg, fmt = check_mix_request(terms, src.n, speechGain, dtype, signalRows=None if signal is None else src.count)
         applied = torch.zeros(len(flat), dtype=torch.float32, device="cuda:%d" % dev) if gains else None
 
         def call(out, stride, numel, stream):
-            return self._dll.speechPlayer_batch_exportMixed(self._h, _ptr(sel), n, flat.ctypes.data if len(flat) else None, start.ctypes.data, _ptr(sg),
-                                                            applied.data_ptr() if gains and len(flat) else None, out, fmt, stride, stream)
+            return export(flat.ctypes.data if len(flat) else None, start.ctypes.data, _ptr(sg), applied.data_ptr() if gains and len(flat) else None, out, fmt,
+                          stride, stream)
         # (always: the library refuses a bad term even where the chosen rows have no samples to write)
-        out, second = self._export_rows(self._lengths()[idx].astype(np.int64), (), torch.float32 if fmt else torch.int16, padded, call, always=True)
+        out, second = self._export_rows(src.lengths, (), torch.float32 if fmt else torch.int16, padded, call, always=True)
         return (out, second, applied, torch.from_numpy(start)) if gains else (out, second)
 
     def stemTensor(self, columns, utterances=None, dtype=None, padded=True):
@@ -1600,8 +1536,8 @@ class BatchPlayer(object):
         n + 1 element offsets (int64 CPU tensors)."""
         import torch
         cols, fmt = check_stem_request(columns, dtype)
-        sel, n, idx = self._selection("stemTensor", utterances)
-        lens = self._lengths()[idx].astype(np.int64)
+        src = self._rows("stemTensor", None, utterances)
+        n, lens = src.n, src.lengths
         dev = self.device
         tdtype = torch.float32 if fmt else torch.float64
         if padded:
@@ -1613,16 +1549,15 @@ class BatchPlayer(object):
             out = torch.empty(int(offsets[-1]), dtype=tdtype, device="cuda:%d" % dev)
             stride = 0
         if out.numel():
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            got = self._check(self._dll.speechPlayer_batch_exportStems(self._h, None if sel is None else sel.ctypes.data, n, cols.ctypes.data, len(cols),
-                                                                       out.data_ptr(), fmt, stride, stream))
+            got = self._check(self._entry("Stems", src)(cols.ctypes.data, len(cols), out.data_ptr(), fmt, stride, torch.cuda.current_stream(dev).cuda_stream))
             assert got == out.numel(), (got, out.numel())
         return out, torch.from_numpy(lens if padded else offsets)
 
     def epochCounts(self, utterances=None):
         """Glottal cycles begun (pitch marks) in each of the chosen utterances (speechPlayer_batch_epochCounts): an int64 array.  The first
         call after a set call waits for a counting walk on the device."""
-        sel, n, _ = self._selection("epochCounts", utterances)
+        src = self._rows("epochCounts", None, utterances)
+        sel, n = src.sel, src.n
         if n == 0:
             return np.zeros(0, np.int64)
         counts = np.zeros(n, np.int64)
@@ -1638,10 +1573,10 @@ class BatchPlayer(object):
         counts come from a walk over EVERY list of the batch on the engine's own stream (however few utterances are chosen), which
         queues behind a synthesize(wait=False) in flight and is waited for on the host; later calls are ordered by events alone."""
         import torch
-        sel, n, _ = self._selection("epochTensor", utterances)
+        src = self._rows("epochTensor", None, utterances)
 
         def call(out, stride, numel, stream):
-            return self._dll.speechPlayer_batch_exportEpochs(self._h, _ptr(sel), n, out, stride, float(pad), numel, stream)
+            return self._dll.speechPlayer_batch_exportEpochs(self._h, _ptr(src.sel), src.n, out, stride, float(pad), numel, stream)
         return self._export_rows(self.epochCounts(utterances), (len(EPOCH_COLUMNS),), torch.float64, padded, call)
 
     def setUtterancesShared(self, listStart, frames, minSamples, fadeSamples, listOf, userIndex=None, isNull=None, noiseSeed=None):
