@@ -723,6 +723,71 @@ long long speechPlayer_signalResample(const void* x, int inFormat, long long len
 	double beta, int format, void* out, long long capacity);
 long long speechPlayer_signalConvolve(const void* x, int inFormat, long long length, const float* ir, long long taps, int tail, int format, void* out,
 	long long capacity);
+/*
+ * A batch's PCM, or a signal's rows, through cascades of second-order recursive (biquad, IIR) sections: pre-emphasis and de-emphasis, a
+ * DC blocker, the telephone band, shelving and peaking EQ, a high-pass -- and the synthesiser's own building block, the resonator
+ * (speechPlayer_resonatorCoefficients: y = a x + b y1 + c y2 is the section b0 = a, b1 = b2 = 0, a1 = -b, a2 = -c).  For a row of L
+ * input samples and a filter of K sections (1 <= K <= kFilterMaxSections = 16), section j being five float32 values b0 b1 b2 a1 a2
+ * (a0 = 1):
+ *   input     x[n] = tile_x(s(n)): (float)s(n) / 32767.0f of an int16 sample (the bits of speechPlayer_batch_exportPcm's format 1), a
+ *             float32 sample as it is; x[n] = +0 for n >= L; nothing outside the row is read as signal
+ *   length    Lout = L + tail: tail >= 0 extra samples of zero input, the same for all rows, at most 2^20.  With tail = 0 the label grids
+ *             of the other exports apply unchanged
+ *   section   transposed direct form II, the states s1 = s2 = +0 at n = 0; na1 = -a1 and na2 = -a2 are exact negations made once.  For
+ *             every sample, in this order, each line ONE correctly rounded binary32 operation with gradual underflow:
+ *                 y  = fmaf(b0,  x, s1)
+ *                 t  = fmaf(b1,  x, s2)
+ *                 s1 = fmaf(na1, y, t)
+ *                 v  = b2 * x
+ *                 s2 = fmaf(na2, y, v)
+ *             The y of section j is the x of section j + 1; after the last section out = y + 0.0f.  The definition is the function bodies
+ *             of csrc/klatt_filter.h (filter_section, filter_finish), which the host and the device compile from one source;
+ *             speechPlayer_pcmFilter executes them in a plain loop
+ *   format 1  float32: out
+ *   format 0  int16: the resampler's conversion of out (one float32 product by 32767, clipped to 32767 and -32768, rintf)
+ *   filters   every coefficient is finite, and every section's poles lie strictly inside the unit circle, tested in binary64 on the
+ *             float32 values: a2 < 1 and |a1| < 1 + a2; refused otherwise, the message naming the filter and the section
+ * The bit-for-bit claim holds while every value stays finite; stable sections and |x| <= 2^16 keep it so for any sane filter.  A row some
+ * value of which overflows is outside the claim: the device and the host may differ in the bits of its NaNs (nothing faults).
+ * Lemma.  Appending or inserting an identity section (1 0 0 0 0) changes no output bit.  Its y = fmaf(1, x, s1) with s1 a zero equals x
+ * except possibly in the sign of a zero; its states stay zeros (0 x, -0 y and their sums are zeros while x is finite); the sign of a zero
+ * never changes a nonzero result downstream (a product with a zero is a zero, a zero added to a nonzero value returns it), so two such
+ * runs agree everywhere except possibly in the signs of zeros; and the closing + 0.0f makes a zero +0.  This is what lets a wavefront pad
+ * rows with fewer sections up to its instantiation's 1, 2, 4, 8 or 16.
+ * Over the pool the result is a function of the batch's PCM: it depends on the mode and needs a synthesis launch.
+ * Out of scope: live handles (the filter state would have to persist across pulls); NodePlayer; zero-phase (forward-backward)
+ * filtering; initial conditions in or out; time-parallel (scan) formulations, which cannot meet the sequential statement's bits.  For
+ * the same reason a row cannot be cut in time: a call of fewer than 64 x 1024 rows underfills the device, and that is accepted.
+ *
+ * Host only, touch no device: the definition above on `length` samples of plain PCM (speechPlayer_pcmFilter) or of a signal's row,
+ * int16 (inFormat 0) or float32 (inFormat 1) (speechPlayer_signalFilter), and one filter of nSections sections, sections being
+ * float[nSections][5] -- the statements the device is held to bit for bit.  out: float[Lout] (format 1) or int16[Lout] (format 0).
+ * Return Lout; a NULL out only sizes; -1 on tail outside 0 .. 2^20, a NULL sections, nSections outside 1 .. 16, a coefficient that is not
+ * finite, a section whose poles are not strictly inside the unit circle, an unknown format or inFormat, length < 0 or above 2^44, a NULL
+ * input with length > 0, a capacity below Lout, and (signalFilter) a float32 sample that is not finite or above 2^16 in magnitude. */
+long long speechPlayer_pcmFilter(const sample* pcm, long long length, const float* sections, long long nSections, long long tail, int format, void* out,
+	long long capacity);
+long long speechPlayer_signalFilter(const void* x, int inFormat, long long length, const float* sections, long long nSections, long long tail, int format,
+	void* out, long long capacity);
+/* The chosen utterances' PCM (exportFiltered) or chosen rows of `signal` (exportFilteredOf), row i through filter filterOf[i], into
+ * caller-owned device memory on the caller's stream.  The nFilters filters lie back to back in HOST memory: filter j is the sections
+ * secStart[j] .. secStart[j+1]-1 of sections[][5] (filterOf NULL: nFilters must be 1).  filterOf is per ROW: with repeats in `utterances`
+ * one utterance goes through several filters in one call.  utterances / rows, the rows' forms (rowStride > 0: padded rows, +0 past each
+ * row's Lout; 0: the rows back to back), the return value, the device-memory checks, the sixteen-in-flight rule and the ordering by events
+ * are those of speechPlayer_batch_exportConvolved / exportConvolvedOf.  The filters cross the link with the call's staging block and are
+ * not kept on the batch (no new ordering state).  A wavefront takes 64 rows, a lane each, in tiles of kFilterTile = 64 samples
+ * (csrc/klatt_filter.h); the rows are packed into wavefronts by instantiation and length, and the output order is the caller's.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: what speechPlayer_batch_exportConvolved / exportConvolvedOf refuse of the
+ * batch, the signal, the selection, the format, rowStride and the output; tail outside 0 .. 2^20; nFilters < 1; a NULL sections or
+ * secStart; secStart not starting at 0; a filter of fewer than 1 or more than 16 sections; more than 2^16 sections in all; a
+ * filterOf[i] outside 0 .. nFilters-1; filterOf NULL with nFilters != 1; a coefficient that is not finite and a section whose poles are
+ * not strictly inside the unit circle (the message gives filter and section). */
+long long speechPlayer_batch_exportFiltered(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const float* sections,
+	const long long* secStart, long long nFilters, const long long* filterOf, long long tail, void* deviceOut, int format, long long rowStride,
+	void* stream);
+long long speechPlayer_batch_exportFilteredOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	const float* sections, const long long* secStart, long long nFilters, const long long* filterOf, long long tail, void* deviceOut, int format,
+	long long rowStride, void* stream);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

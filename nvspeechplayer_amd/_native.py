@@ -68,6 +68,7 @@ EXPORTS = [
     "speechPlayer_batch_exportSpectrogramOf", "speechPlayer_batch_exportResampledOf", "speechPlayer_batch_exportConvolvedOf",
     "speechPlayer_signalSpectrogram", "speechPlayer_signalResample", "speechPlayer_signalConvolve",
     "speechPlayer_batch_exportPowerOf", "speechPlayer_batch_exportMixedOf", "speechPlayer_signalPower", "speechPlayer_signalMix",
+    "speechPlayer_pcmFilter", "speechPlayer_signalFilter", "speechPlayer_batch_exportFiltered", "speechPlayer_batch_exportFilteredOf",
     "speechPlayer_planTrackKinds",
 ]
 
@@ -421,6 +422,14 @@ def load():
     L.speechPlayer_signalResample.argtypes = [vp, i32, i64, i32, i32, i32, f64, i32, f64, i32, vp, i64]
     L.speechPlayer_signalConvolve.restype = i64
     L.speechPlayer_signalConvolve.argtypes = [vp, i32, i64, vp, i64, i32, i32, vp, i64]
+    L.speechPlayer_pcmFilter.restype = i64
+    L.speechPlayer_pcmFilter.argtypes = [vp, i64, vp, i64, i64, i32, vp, i64]
+    L.speechPlayer_signalFilter.restype = i64
+    L.speechPlayer_signalFilter.argtypes = [vp, i32, i64, vp, i64, i64, i32, vp, i64]
+    L.speechPlayer_batch_exportFiltered.restype = i64
+    L.speechPlayer_batch_exportFiltered.argtypes = [vp, vp, i64, vp, vp, i64, vp, i64, vp, i32, i64, vp]
+    L.speechPlayer_batch_exportFilteredOf.restype = i64
+    L.speechPlayer_batch_exportFilteredOf.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, i64, vp, i32, i64, vp]
     L.speechPlayer_batch_exportPowerOf.restype = i64
     L.speechPlayer_batch_exportPowerOf.argtypes = [vp, vp, vp, i64, vp, vp]
     L.speechPlayer_batch_exportMixedOf.restype = i64

@@ -23,6 +23,7 @@
 #include "klatt_spectrum.h"
 #include "klatt_resample.h"
 #include "klatt_convolve.h"
+#include "klatt_filter.h"
 #include "klatt_mix.h"
 #include "klatt_export.h"
 #include "klatt_batchplan.h"
@@ -5595,6 +5596,135 @@ long long speechPlayer_batch_exportConvolvedOf(speechPlayer_batch_t batch, const
     if (refuse_timing_only("speechPlayer_batch_exportConvolvedOf")) return -1;
     return convolved_export(what, batch, true, signal, rows, nRows,
                             ir, irStart, nIr, irOf, tail, deviceOut, format, rowStride, stream);
+}
+
+// ---- the PCM through cascades of biquad sections (klatt_filter.h) ---------------------------------------------------------------------------
+static_assert(sizeof(FilterRow) % 8 == 0 && sizeof(FilterGroup) % 8 == 0 && sizeof(FilterSection) == 20, "rows and groups are arrays of 8-byte words, a section is five floats");
+
+// Host only, touches no device: the definition of include/speechPlayer_batch.h through the functions the kernel is compiled from.
+static long long filter_statement(const char* what, const void* x, int inFormat, long long length, const float* sections, long long nSections, long long tail, int format,
+                                  void* out, long long capacity)
+{
+    if (signal_host_format(what, inFormat)) return -1;
+    if (length < 0 || length > kResampleMaxLength || (length > 0 && !x)) { set_error("%s: length %lld (0 .. 2^44, with its samples)", what, length); return -1; }
+    if (format != 0 && format != 1) { set_error("%s: format %d (0 int16, 1 float32)", what, format); return -1; }
+    try {
+        FilterPlan P;
+        std::string why;
+        const long long starts[2] = {0, nSections};
+        if (!filter_plan(P, sections, starts, 1, tail, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        const long long Lout = filter_length(length, tail);
+        if (!out) return Lout;
+        if (capacity < Lout) { set_error("%s: the output takes %lld elements, capacity is %lld", what, Lout, capacity); return -1; }
+        if (signal_host_values(what, x, inFormat, length)) return -1;
+        return inFormat ? filter_host(static_cast<const float*>(x), length, P.sections.data(), nSections, tail, format, out)
+                        : filter_host(static_cast<const int16_t*>(x), length, P.sections.data(), nSections, tail, format, out);
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
+long long speechPlayer_pcmFilter(const sample* pcm, long long length, const float* sections, long long nSections, long long tail, int format, void* out,
+                                 long long capacity)
+{
+    begin_call();
+    static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
+    return filter_statement("pcmFilter", pcm, 0, length, sections, nSections, tail, format, out, capacity);
+}
+
+long long speechPlayer_signalFilter(const void* x, int inFormat, long long length, const float* sections, long long nSections, long long tail, int format,
+                                    void* out, long long capacity)
+{
+    begin_call();
+    return filter_statement("signalFilter", x, inFormat, length, sections, nSections, tail, format, out, capacity);
+}
+
+// The instantiation of klatt_filter for a bucket, an input format and an output format
+extern "C++" template <int K>
+static void (*filter_kernel(int inFormat, int format))(FilterArgs)
+{
+    void (*const kernels[2][2])(FilterArgs) = {{klatt_filter<K, false, int16_t>, klatt_filter<K, true, int16_t>}, {klatt_filter<K, false, float>, klatt_filter<K, true, float>}};
+    return kernels[inFormat][format];
+}
+
+// The chosen utterances' PCM, each row through the filter filterOf names (klatt_filter.h).  It reads the pool, so it is ordered as
+// speechPlayer_batch_exportPcm is (ExportStage, ofPcm).  A wavefront takes 64 rows, not tiles of one: the rows are packed into groups
+// (filter_pack) and carry their first element in the output, so there is no tile table; one launch per bucket that has groups.  The
+// staging block: packed rows | groups | the sections.  Nothing is kept on the batch.  ofSignal and `signal` as spectrogram_export's.
+static long long filtered_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances, long long nUtterances,
+                                 const float* sections, const long long* secStart, long long nFilters, const long long* filterOf, long long tail, void* deviceOut,
+                                 int format, long long rowStride, void* stream)
+{
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (tile_request(what, format, rowStride)) return -1;
+        FilterPlan P;
+        std::string why;
+        if (!filter_plan(P, sections, secStart, nFilters, tail, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
+        ExportSelection s;
+        std::vector<FilterRow> rows;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) -> long long {
+                const long long j = filter_row(P, filterOf, i, why);
+                if (j < 0) { set_error("%s: %s", what, why.c_str()); return -1; }
+                const long long L = in.len(u), Lout = filter_length(L, tail);
+                rows.push_back(FilterRow{in.at(u), L, Lout, tile_row_first(i, rowStride, before), P.start[(size_t)j], P.start[(size_t)j + 1] - P.start[(size_t)j]});
+                return Lout;
+            }, in.sig)) return -1;
+        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut, &in);
+        if (elements <= 0) return elements;
+        std::vector<FilterRow> packed;
+        std::vector<FilterGroup> groups;
+        filter_pack(rows, packed, groups);
+        StageBlock block;
+        const int rowsAt = block.add(packed), groupsAt = block.add(groups), sectionsAt = block.add(P.sections);
+        ExportStage stage(b, static_cast<hipStream_t>(stream), block, nullptr, !in.sig, in.sig != nullptr);
+        if (stage.begin()) return -1;
+        FilterArgs A;
+        A.in = in.data; A.rows = stage.device<FilterRow>(rowsAt);
+        A.sections = stage.device<FilterSection>(sectionsAt);
+        A.rowStride = rowStride; A.out = deviceOut;
+        for (size_t first = 0; first < groups.size();) {      // the groups of one bucket lie together
+            size_t end = first;
+            while (end < groups.size() && groups[end].bucket == groups[first].bucket) ++end;
+            A.groups = stage.device<FilterGroup>(groupsAt) + first;
+            A.nGroups = (long long)(end - first);
+            void (*kernel)(FilterArgs) = nullptr;
+            switch (groups[first].bucket) {
+                case 1: kernel = filter_kernel<1>(in.format(), format); break;
+                case 2: kernel = filter_kernel<2>(in.format(), format); break;
+                case 4: kernel = filter_kernel<4>(in.format(), format); break;
+                case 8: kernel = filter_kernel<8>(in.format(), format); break;
+                default: kernel = filter_kernel<16>(in.format(), format); break;
+            }
+            // a wavefront per group; no more workgroups than keep every SIMD of the device busy several times over
+            const unsigned grid = (unsigned)std::min<long long>(A.nGroups, 64ll * b->cus);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFilterLanes), 0, stage.st, A);
+            HIP_TRY(hipGetLastError());
+            first = end;
+        }
+        if (stage.finish()) return -1;
+        return elements;
+    });
+}
+
+long long speechPlayer_batch_exportFiltered(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const float* sections,
+                                            const long long* secStart, long long nFilters, const long long* filterOf, long long tail, void* deviceOut, int format,
+                                            long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportFiltered")) return -1;
+    return filtered_export("exportFiltered", batch, false, nullptr, utterances, nUtterances,
+                           sections, secStart, nFilters, filterOf, tail, deviceOut, format, rowStride, stream);
+}
+
+// The same of chosen rows of a caller's signal, filterOf per output row: it reads no pool and needs no synthesis (ExportStage, ofSignal).
+long long speechPlayer_batch_exportFilteredOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+                                              const float* sections, const long long* secStart, long long nFilters, const long long* filterOf, long long tail,
+                                              void* deviceOut, int format, long long rowStride, void* stream)
+{
+    const char* what = "exportFilteredOf";
+    if (refuse_timing_only("speechPlayer_batch_exportFilteredOf")) return -1;
+    return filtered_export(what, batch, true, signal, rows, nRows,
+                           sections, secStart, nFilters, filterOf, tail, deviceOut, format, rowStride, stream);
 }
 
 // ---- the PCM mixed with noise and other utterances (klatt_mix.h) ----------------------------------------------------------------------------

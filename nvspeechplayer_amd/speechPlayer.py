@@ -809,6 +809,136 @@ def _convolve_statement(what, s, inFormat, ir, tail, dtype):
     return _row_statement(what, s, inFormat, (h.ctypes.data, len(h), tail, fmt), len(s) + len(h) - 1 if tail else len(s), np.float32 if fmt else np.int16)
 
 
+FILTER_TILE = 64                 # kFilterTile of csrc/klatt_filter.h: consecutive samples of each of its 64 rows a wavefront takes at a time
+FILTER_MAX_SECTIONS = 16         # kFilterMaxSections: of one filter
+FILTER_MAX_TABLE = 1 << 16       # kFilterMaxTable: sections of all filters of a call
+FILTER_MAX_TAIL = 1 << 20        # kFilterMaxTail: extra outputs of zero input
+BIQUAD_KINDS = ["lowpass", "highpass", "bandpass", "notch", "peaking", "lowshelf", "highshelf"]
+
+
+def _filter_sections(f, what, name):
+    """One filter as float32 [K, 5] = b0 b1 b2 a1 a2: from [K, 5], or from scipy's sos layout [K, 6] = b0 b1 b2 a0 a1 a2, divided by a0
+    in binary64 and rounded to float32 once."""
+    try:
+        a = _as_array(f)
+    except Exception:
+        raise TypeError("%s: %s is not an array" % (what, name))
+    if a.ndim != 2 or a.shape[1] not in (5, 6) or a.dtype.kind not in "fiu":
+        raise TypeError("%s: %s must be [K, 5] (b0 b1 b2 a1 a2) or [K, 6] (sos: b0 b1 b2 a0 a1 a2) real numbers, not %s %s" % (what, name, a.dtype, list(a.shape)))
+    if not 1 <= a.shape[0] <= FILTER_MAX_SECTIONS:
+        raise ValueError("%s: %s has %d sections (1 .. %d)" % (what, name, a.shape[0], FILTER_MAX_SECTIONS))
+    if a.shape[1] == 6:
+        a = a.astype(np.float64)
+        if not np.all(np.isfinite(a[:, 3])) or np.any(a[:, 3] == 0):
+            raise ValueError("%s: %s has a section whose a0 is not finite or is 0" % (what, name))
+        with np.errstate(over="ignore", invalid="ignore"):
+            a = a[:, [0, 1, 2, 4, 5]] / a[:, 3:4]
+    with np.errstate(over="ignore"):
+        return np.ascontiguousarray(a.astype(np.float32))
+
+
+def check_filter_request(filters, filterOf, nRows, tail, dtype, what="filteredTensor"):
+    """The argument checks of BatchPlayer.filteredTensor, pcmFilter and signalFilter that need no GPU, before any library call: filters
+    one array of shape [K, 5] or [K, 6] (_filter_sections) or a list of them, each of 1 .. 16 sections, at most 2^16 in all; filterOf
+    None (exactly one filter) or nRows integers in [0, len(filters)); tail an integer in 0 .. 2^20; dtype as convolvedTensor's.  The
+    values -- finite coefficients, poles strictly inside the unit circle -- are the library's to refuse, with the filter and the section
+    in its message.  Raises ValueError or TypeError.  Returns (the sections back to back: float32 [n, 5], their nFilters + 1 starts:
+    int64, filterOf: int64 or None, tail, the export format: 0 int16, 1 float32)."""
+    if not isinstance(filters, (list, tuple)):
+        filters = [filters]
+    elif len(filters) and all(isinstance(r, (list, tuple)) and len(r) and all(isinstance(v, (int, float, np.integer, np.floating)) for v in r) for r in filters):
+        filters = [filters]      # (one filter given as nested lists of numbers)
+    if len(filters) < 1:
+        raise ValueError("%s: at least one filter" % what)
+    flat, start = [], [0]
+    for j, f in enumerate(filters):
+        flat.append(_filter_sections(f, what, "filter %d" % j))
+        start.append(start[-1] + len(flat[-1]))
+        if start[-1] > FILTER_MAX_TABLE:
+            raise ValueError("%s: the filters have more than %d sections in all" % (what, FILTER_MAX_TABLE))
+    if filterOf is None:
+        if len(filters) != 1:
+            raise ValueError("%s: filterOf is needed with %d filters" % (what, len(filters)))
+        of = None
+    else:
+        of = _as_array(filterOf)
+        if of.dtype.kind not in "iu" or of.ndim != 1:
+            raise TypeError("%s: filterOf must be a one-dimensional array of integers, not %s %s" % (what, of.dtype, list(of.shape)))
+        if len(of) != nRows:
+            raise ValueError("%s: filterOf has %d entries for %d rows" % (what, len(of), nRows))
+        of = np.ascontiguousarray(of.astype(np.int64))
+        if len(of) and (of.min() < 0 or of.max() >= len(filters)):
+            raise ValueError("%s: filterOf must lie in [0, %d)" % (what, len(filters)))
+    if isinstance(tail, (bool, np.bool_)) or not isinstance(tail, (int, np.integer)) or not 0 <= tail <= FILTER_MAX_TAIL:
+        raise ValueError("%s: tail must be an integer in 0 .. %d, not %r" % (what, FILTER_MAX_TAIL, tail))
+    return np.ascontiguousarray(np.concatenate(flat)), np.array(start, np.int64), of, int(tail), _sample_format(dtype, what)
+
+
+def pcmFilter(pcm, sections, tail=0, dtype=np.float32):
+    """int16 PCM through one cascade of biquad sections on the host (speechPlayer_pcmFilter; no GPU): sections [K, 5] = b0 b1 b2 a1 a2
+    or scipy's sos layout [K, 6]; -> float32 (sample / 32767 scale) or int16, len(pcm) + tail values, by the definition in
+    include/speechPlayer_batch.h -- transposed direct form II in float32, five correctly rounded operations per section and sample,
+    the statement the device equals bit for bit."""
+    return _filter_statement("pcmFilter", _pcm_samples(pcm, "pcmFilter"), None, sections, tail, dtype)
+
+
+def _filter_statement(what, s, inFormat, sections, tail, dtype):
+    sec, start, _, tail, fmt = check_filter_request(sections, None, 1, tail, dtype, what)
+    return _row_statement(what, s, inFormat, (sec.ctypes.data, len(sec), tail, fmt), len(s) + tail, np.float32 if fmt else np.int16)
+
+
+def biquad(kind, rate, f0, q=np.sqrt(0.5), gainDb=0.0):
+    """One second-order section by the Audio-EQ-Cookbook (host numpy, binary64): kind one of BIQUAD_KINDS -- "lowpass", "highpass",
+    "bandpass" (0 dB at f0), "notch", "peaking", "lowshelf", "highshelf" --, f0 in Hz below rate / 2, q the quality (shelves: the shelf
+    slope's Q), gainDb for the last three.  -> float64 [1, 6] in scipy's sos layout with a0 = 1; stack sections with np.concatenate."""
+    if kind not in BIQUAD_KINDS:
+        raise KeyError("biquad: kind %r (%s)" % (kind, ", ".join(BIQUAD_KINDS)))
+    rate, f0, q, gainDb = float(rate), float(f0), float(q), float(gainDb)
+    if not (rate > 0 and 0 < f0 < rate / 2 and q > 0 and np.isfinite(gainDb)):
+        raise ValueError("biquad: rate %r, f0 %r (0 .. rate / 2, exclusive), q %r (positive), gainDb %r" % (rate, f0, q, gainDb))
+    w0 = 2.0 * np.pi * f0 / rate
+    cs, alpha, A = np.cos(w0), np.sin(w0) / (2.0 * q), 10.0 ** (gainDb / 40.0)
+    if kind == "lowpass":
+        b, a = [(1 - cs) / 2, 1 - cs, (1 - cs) / 2], [1 + alpha, -2 * cs, 1 - alpha]
+    elif kind == "highpass":
+        b, a = [(1 + cs) / 2, -(1 + cs), (1 + cs) / 2], [1 + alpha, -2 * cs, 1 - alpha]
+    elif kind == "bandpass":
+        b, a = [alpha, 0.0, -alpha], [1 + alpha, -2 * cs, 1 - alpha]
+    elif kind == "notch":
+        b, a = [1.0, -2 * cs, 1.0], [1 + alpha, -2 * cs, 1 - alpha]
+    elif kind == "peaking":
+        b, a = [1 + alpha * A, -2 * cs, 1 - alpha * A], [1 + alpha / A, -2 * cs, 1 - alpha / A]
+    else:
+        sq = 2.0 * np.sqrt(A) * alpha
+        if kind == "lowshelf":
+            b = [A * ((A + 1) - (A - 1) * cs + sq), 2 * A * ((A - 1) - (A + 1) * cs), A * ((A + 1) - (A - 1) * cs - sq)]
+            a = [(A + 1) + (A - 1) * cs + sq, -2 * ((A - 1) + (A + 1) * cs), (A + 1) + (A - 1) * cs - sq]
+        else:
+            b = [A * ((A + 1) + (A - 1) * cs + sq), -2 * A * ((A - 1) + (A + 1) * cs), A * ((A + 1) + (A - 1) * cs - sq)]
+            a = [(A + 1) - (A - 1) * cs + sq, 2 * ((A - 1) - (A + 1) * cs), (A + 1) - (A - 1) * cs - sq]
+    b, a = np.array(b, np.float64), np.array(a, np.float64)
+    return np.concatenate([b / a[0], [1.0], a[1:] / a[0]]).reshape(1, 6)
+
+
+def preEmphasis(c=0.97):
+    """y[n] = x[n] - c x[n-1] as one section: float64 [1, 6] (sos)."""
+    return np.array([[1.0, -float(c), 0.0, 1.0, 0.0, 0.0]], np.float64)
+
+
+def dcBlock(r=0.995):
+    """The DC blocker y[n] = x[n] - x[n-1] + r y[n-1] as one section: float64 [1, 6] (sos)."""
+    return np.array([[1.0, -1.0, 0.0, 1.0, -float(r), 0.0]], np.float64)
+
+
+def resonatorSections(frequency, bandwidth, rate):
+    """The synthesiser's resonators as sections (resonatorCoefficients: y = a x + b y1 + c y2, so b0 = a, a1 = -b, a2 = -c), one per
+    (frequency, bandwidth) pair in Hz: float64 [K, 6] (sos)."""
+    abc = resonatorCoefficients(frequency, bandwidth, rate)
+    out = np.zeros((len(abc), 6), np.float64)
+    out[:, 0], out[:, 3], out[:, 4], out[:, 5] = abc[:, 0], 1.0, -abc[:, 1], -abc[:, 2]
+    return out
+
+
 SIGNAL_MAX_LENGTH = 1 << 44      # kSignalMaxLength of csrc/klatt_tiles.h: samples of one row
 # speechPlayer_signal_t (include/speechPlayer_batch.h)
 _signalDtype = np.dtype([("data", np.uint64), ("format", np.int32), ("reserved", np.int32), ("nRows", np.int64), ("rowStride", np.int64),
@@ -939,6 +1069,12 @@ def signalConvolve(x, ir, tail=True, dtype=np.float32):
     """pcmConvolve on a signal's row (speechPlayer_signalConvolve; no GPU): x as signalSpectrogram's.  -> float32 or int16, len(x) +
     len(ir) - 1 values (tail) or len(x).  The statement BatchPlayer.convolvedTensor(signal=...) is held to."""
     return _convolve_statement("signalConvolve", *_signal_samples(x, "signalConvolve"), ir, tail, dtype)
+
+
+def signalFilter(x, sections, tail=0, dtype=np.float32):
+    """pcmFilter on a signal's row (speechPlayer_signalFilter; no GPU): x as signalSpectrogram's.  -> float32 or int16, len(x) + tail
+    values.  The statement BatchPlayer.filteredTensor(signal=...) is held to."""
+    return _filter_statement("signalFilter", *_signal_samples(x, "signalFilter"), sections, tail, dtype)
 
 
 MIX_TILE = 1024                  # kMixTile of csrc/klatt_mix.h: consecutive outputs of one row a workgroup takes at a time
@@ -1457,6 +1593,28 @@ class BatchPlayer(object):
         def call(out, stride, numel, stream):
             return export(h.ctypes.data, start.ctypes.data, len(start) - 1, _ptr(of), tail, out, fmt, stride, stream)
         return self._export_rows(src.lengths + (taps - 1 if tail else 0), (), torch.float32 if fmt else torch.int16, padded, call)
+
+    def filteredTensor(self, filters, filterOf=None, tail=0, utterances=None, dtype=None, padded=True, signal=None):
+        """The batch's PCM through cascades of biquad (IIR) sections as a torch tensor on the batch's device
+        (speechPlayer_batch_exportFiltered), filled on torch's current stream behind the synthesis without a host wait:
+        -> (pcm, lengths).  filters: one array of shape [K, 5] (b0 b1 b2 a1 a2) or [K, 6] (scipy's sos layout: divided by a0 in binary64,
+        then rounded to float32 once) or a list of them, 1 .. 16 sections each -- biquad, preEmphasis, dcBlock and resonatorSections
+        design them; filterOf: the filter of each ROW (None: the one filter) -- with repeats in `utterances`, one utterance goes through
+        several filters in one call.  tail: extra outputs of zero input, the same for every row (0: the grid of the other exports).
+        utterances, padded and the (pcm, lengths) pair as pcmTensor's; dtype torch.float32 (default) or torch.int16 (clipped, rounded to
+        nearest even).  The batch must have been synthesised since it was set; pcmFilter is the same definition on the host, which the
+        device equals bit for bit.  The result feeds the next stage as its signal=.
+        signal: the (tensor, lengths or offsets) pair another export returned (check_signal_request), read in place of the batch's PCM
+        (speechPlayer_batch_exportFilteredOf): `utterances` then chooses rows of the signal, filterOf stays per output row, no synthesis
+        is needed and signalFilter is the host's statement."""
+        import torch
+        src = self._rows("filteredTensor", signal, utterances)
+        export = self._entry("Filtered", src)
+        sec, start, of, tail, fmt = check_filter_request(filters, filterOf, src.n, tail, dtype)
+
+        def call(out, stride, numel, stream):
+            return export(sec.ctypes.data, start.ctypes.data, len(start) - 1, _ptr(of), tail, out, fmt, stride, stream)
+        return self._export_rows(src.lengths + tail, (), torch.float32 if fmt else torch.int16, padded, call)
 
     def setNoiseBank(self, clips):
         """The batch's noise bank (speechPlayer_batch_setNoiseBank): a list of one-dimensional float arrays (kept as float32), every value
