@@ -788,6 +788,71 @@ long long speechPlayer_batch_exportFiltered(speechPlayer_batch_t batch, const lo
 long long speechPlayer_batch_exportFilteredOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
 	const float* sections, const long long* secStart, long long nFilters, const long long* filterOf, long long tail, void* deviceOut, int format,
 	long long rowStride, void* stream);
+/*
+ * A batch's PCM, or a signal's rows, through a speech codec: G.711 mu-law, G.711 A-law and IMA/DVI ADPCM -- what a telephone trunk or an ADPCM
+ * handset does to a signal beyond band-limiting it, and (the 8-bit mu-law code) the class label per sample that autoregressive vocoders
+ * train on.  codec: 0 "ulaw", 1 "alaw", 2 "adpcm".
+ *   input     every codec takes an int16 sample s: a row's int16 itself; a float32 x through the resampler's conversion (one float32
+ *             product by 32767, clipped to 32767 and -32768, rintf).  That conversion returns s for (float)s / 32767.0f, for all 65 536
+ *             values of s, so an int16 row and its float32 form give the same outputs
+ *   outputs   per sample, from one pass, either or both: the CODE, a uint8, ONE PER SAMPLE (0 .. 255 for G.711, 0 .. 15 for ADPCM: the rows
+ *             stay on the grid of every other export; packing nibbles is the caller's, codes[0::2] << 4 | codes[1::2] being the usual byte
+ *             order), and the DECODED sample d, what a decoder makes of the code: format 0 int16 d, format 1 float32 (float)d / 32767.0f.
+ *             Row lengths are unchanged; there is no tail
+ * All arithmetic is int32, >> is arithmetic, top(v) is the bit index of v's highest set bit.
+ *   mu-law    encode  v = s >> 2; if v < 0 { v = -v; m = 0x7F } else m = 0xFF; if v > 8158: v = 8158; v += 33; seg = top(v) - 5;
+ *                     code = ((seg << 4) | ((v >> (seg + 1)) & 15)) ^ m
+ *                     (v stays below 8192 and seg within 0 .. 7; audioop clips at 8159 and answers the one sum that then reaches 8192
+ *                     with the top code, which is the same code)
+ *             decode  c = ~code & 255; t = (((c & 15) << 3) + 132) << ((c & 0x70) >> 4); d = (c & 0x80) ? 132 - t : t - 132
+ *   A-law     encode  v = s >> 3; if v >= 0 m = 0xD5 else { m = 0x55; v = -v - 1 }; seg = v < 32 ? 0 : top(v) - 4;
+ *                     code = ((seg << 4) | (seg < 2 ? (v >> 1) & 15 : (v >> seg) & 15)) ^ m
+ *             decode  c = code ^ 0x55; t = (c & 15) << 4; seg = (c & 0x70) >> 4; seg 0: t += 8; seg 1: t += 0x108; else
+ *                     t = (t + 0x108) << (seg - 1); d = (c & 0x80) ? t : -t
+ *   ADPCM     the state val = 0, idx = 0 at a row's first sample; for each sample s, ascending:
+ *                 step = STEP[idx]; diff = s - val; sign = diff < 0 ? 8 : 0; if sign: diff = -diff
+ *                 delta = 0; vp = step >> 3
+ *                 if diff >= step      { delta  = 4; diff -= step;      vp += step }
+ *                 if diff >= step >> 1 { delta |= 2; diff -= step >> 1; vp += step >> 1 }
+ *                 if diff >= step >> 2 { delta |= 1;                    vp += step >> 2 }
+ *                 val = clamp(sign ? val - vp : val + vp, -32768, 32767)
+ *                 code = delta | sign; idx = clamp(idx + INDEX[delta], 0, 88); d = val
+ *             INDEX is -1 -1 -1 -1 2 4 6 8 and STEP the 89-entry IMA table (7 8 9 10 11 12 13 14 16 17 ... 27086 29794 32767:
+ *             csrc/klatt_codec.h, kAdpcmTable).  A decoder given the codes rebuilds the same val -- vp is a function of step and code --,
+ *             which is why d needs no second pass
+ * The definition is the function bodies of csrc/klatt_codec.h, which the host and the device compile from one source; the G.711 laws and
+ * the ADPCM recursion are those of CPython's audioop (tests/golden/codec_golden.npz records its answers).
+ * Over the pool the result is a function of the batch's PCM: it depends on the mode and needs a synthesis launch.
+ * Out of scope: G.722, G.726, GSM and anything without an independent statement to hold it to; packed nibbles and WAV block headers or
+ * predictor resets; packet loss; live handles (the ADPCM state would have to persist across pulls); NodePlayer.
+ *
+ * Host only, touch no device: the definition above on `length` samples of plain PCM (speechPlayer_pcmCode) or of a signal's row, int16
+ * (inFormat 0) or float32 (inFormat 1) (speechPlayer_signalCode) -- the statements the device is held to bit for bit.  decodedOut:
+ * float[length] (format 1) or int16[length] (format 0); codesOut: unsigned char[length]; either may be NULL, with length > 0 not both.
+ * capacity: the elements each output given holds.  state (may be NULL): int[2], the ADPCM encoder's val and idx behind the last sample
+ * (0 0 for a G.711 law).  Return length; -1 on an unknown inFormat, length < 0 or above 2^44, a NULL input with length > 0, an unknown
+ * codec or format, no output, a capacity below length, and (signalCode) a float32 sample that is not finite or above 2^16 in magnitude. */
+long long speechPlayer_pcmCode(const sample* pcm, long long length, int codec, int format, void* decodedOut, unsigned char* codesOut, long long capacity,
+	int* state);
+long long speechPlayer_signalCode(const void* x, int inFormat, long long length, int codec, int format, void* decodedOut, unsigned char* codesOut,
+	long long capacity, int* state);
+/* Host only: the decoder alone, `length` codes to `length` samples in `format`; for ADPCM the recursion above driven by the codes (state as
+ * above: the decoder's).  Return length; -1 on length < 0 or above 2^44, NULL codes or a NULL out with length > 0, an unknown codec or
+ * format, a capacity below length, and an ADPCM code above 15 (the message gives the code). */
+long long speechPlayer_codecDecode(const unsigned char* codes, long long length, int codec, int format, void* out, long long capacity, int* state);
+/* The chosen utterances' PCM (exportCoded) or chosen rows of `signal` (exportCodedOf) through `codec`, into caller-owned device memory on the
+ * caller's stream: the decoded samples to decodedOut (format 0 int16, 1 float32), the codes to codesOut (unsigned char), either NULL but
+ * not both; the same rowStride, in elements, lays out both.  utterances / rows, the rows' forms (rowStride > 0: padded rows, +0 and code 0
+ * past each row's end; 0: the rows back to back), the return value (the elements of ONE output), the device-memory checks -- of each output
+ * given --, the sixteen-in-flight rule and the ordering by events are those of speechPlayer_batch_exportFiltered / exportFilteredOf.
+ * Nothing is kept on the batch.  A G.711 law runs tile-wise, a 256-lane workgroup per kCodeTile = 1024 samples of a row; ADPCM a wavefront
+ * per 64 rows, a lane each, in tiles of kFilterTile = 64 samples (csrc/klatt_codec.h), the output order being the caller's.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: an unknown codec; both outputs NULL; what speechPlayer_batch_exportFiltered /
+ * exportFilteredOf refuse of the format, rowStride, the batch, the signal, the selection and each output; outputs that overlap. */
+long long speechPlayer_batch_exportCoded(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int codec, void* decodedOut,
+	int format, unsigned char* codesOut, long long rowStride, void* stream);
+long long speechPlayer_batch_exportCodedOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	int codec, void* decodedOut, int format, unsigned char* codesOut, long long rowStride, void* stream);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

@@ -70,6 +70,7 @@ EXPORTS = [
     "speechPlayer_batch_exportPowerOf", "speechPlayer_batch_exportMixedOf", "speechPlayer_signalPower", "speechPlayer_signalMix",
     "speechPlayer_pcmFilter", "speechPlayer_signalFilter", "speechPlayer_batch_exportFiltered", "speechPlayer_batch_exportFilteredOf",
     "speechPlayer_planTrackKinds",
+    "speechPlayer_pcmCode", "speechPlayer_signalCode", "speechPlayer_codecDecode", "speechPlayer_batch_exportCoded", "speechPlayer_batch_exportCodedOf",
 ]
 
 
@@ -430,6 +431,16 @@ def load():
     L.speechPlayer_batch_exportFiltered.argtypes = [vp, vp, i64, vp, vp, i64, vp, i64, vp, i32, i64, vp]
     L.speechPlayer_batch_exportFilteredOf.restype = i64
     L.speechPlayer_batch_exportFilteredOf.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, i64, vp, i32, i64, vp]
+    L.speechPlayer_pcmCode.restype = i64
+    L.speechPlayer_pcmCode.argtypes = [vp, i64, i32, i32, vp, vp, i64, vp]
+    L.speechPlayer_signalCode.restype = i64
+    L.speechPlayer_signalCode.argtypes = [vp, i32, i64, i32, i32, vp, vp, i64, vp]
+    L.speechPlayer_codecDecode.restype = i64
+    L.speechPlayer_codecDecode.argtypes = [vp, i64, i32, i32, vp, i64, vp]
+    L.speechPlayer_batch_exportCoded.restype = i64
+    L.speechPlayer_batch_exportCoded.argtypes = [vp, vp, i64, i32, vp, i32, vp, i64, vp]
+    L.speechPlayer_batch_exportCodedOf.restype = i64
+    L.speechPlayer_batch_exportCodedOf.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, i64, vp]
     L.speechPlayer_batch_exportPowerOf.restype = i64
     L.speechPlayer_batch_exportPowerOf.argtypes = [vp, vp, vp, i64, vp, vp]
     L.speechPlayer_batch_exportMixedOf.restype = i64

@@ -24,6 +24,7 @@
 #include "klatt_resample.h"
 #include "klatt_convolve.h"
 #include "klatt_filter.h"
+#include "klatt_codec.h"
 #include "klatt_mix.h"
 #include "klatt_export.h"
 #include "klatt_batchplan.h"
@@ -5725,6 +5726,154 @@ long long speechPlayer_batch_exportFilteredOf(speechPlayer_batch_t batch, const 
     if (refuse_timing_only("speechPlayer_batch_exportFilteredOf")) return -1;
     return filtered_export(what, batch, true, signal, rows, nRows,
                            sections, secStart, nFilters, filterOf, tail, deviceOut, format, rowStride, stream);
+}
+
+// ---- the PCM through the G.711 laws and IMA ADPCM (klatt_codec.h) ---------------------------------------------------------------------------
+// Host only, touch no device: the definition of include/speechPlayer_batch.h through the functions the kernels are compiled from.
+static int codec_request(const char* what, int codec, int format)
+{
+    if (codec < 0 || codec >= kCodecCount) { set_error("%s: codec %d (0 ulaw, 1 alaw, 2 adpcm)", what, codec); return -1; }
+    if (format != 0 && format != 1) { set_error("%s: format %d (0 int16, 1 float32)", what, format); return -1; }
+    return 0;
+}
+
+static long long code_statement(const char* what, const void* x, int inFormat, long long length, int codec, int format, void* decodedOut, unsigned char* codesOut,
+                                long long capacity, int* state)
+{
+    if (signal_host_format(what, inFormat)) return -1;
+    if (length < 0 || length > kResampleMaxLength || (length > 0 && !x)) { set_error("%s: length %lld (0 .. 2^44, with its samples)", what, length); return -1; }
+    if (codec_request(what, codec, format)) return -1;
+    if (length > 0 && !decodedOut && !codesOut) { set_error("%s: no output (the decoded samples, the codes or both)", what); return -1; }
+    if (capacity < length) { set_error("%s: the output takes %lld elements, capacity is %lld", what, length, capacity); return -1; }
+    if (signal_host_values(what, x, inFormat, length)) return -1;
+    if (inFormat) code_host(static_cast<const float*>(x), length, codec, format, decodedOut, codesOut, state);
+    else code_host(static_cast<const int16_t*>(x), length, codec, format, decodedOut, codesOut, state);
+    return length;
+}
+
+long long speechPlayer_pcmCode(const sample* pcm, long long length, int codec, int format, void* decodedOut, unsigned char* codesOut, long long capacity, int* state)
+{
+    begin_call();
+    static_assert(sizeof(sample) == sizeof(int16_t), "a sample is an int16");
+    return code_statement("pcmCode", pcm, 0, length, codec, format, decodedOut, codesOut, capacity, state);
+}
+
+long long speechPlayer_signalCode(const void* x, int inFormat, long long length, int codec, int format, void* decodedOut, unsigned char* codesOut, long long capacity,
+                                  int* state)
+{
+    begin_call();
+    return code_statement("signalCode", x, inFormat, length, codec, format, decodedOut, codesOut, capacity, state);
+}
+
+long long speechPlayer_codecDecode(const unsigned char* codes, long long length, int codec, int format, void* out, long long capacity, int* state)
+{
+    begin_call();
+    const char* what = "codecDecode";
+    if (length < 0 || length > kResampleMaxLength || (length > 0 && !codes)) { set_error("%s: length %lld (0 .. 2^44, with its codes)", what, length); return -1; }
+    if (codec_request(what, codec, format)) return -1;
+    if (length > 0 && !out) { set_error("%s: no output", what); return -1; }
+    if (capacity < length) { set_error("%s: the output takes %lld elements, capacity is %lld", what, length, capacity); return -1; }
+    const long long bad = decode_bad_code(codes, length, codec);
+    if (bad >= 0) { set_error("%s: code %lld is %d (an ADPCM code is 0 .. 15)", what, bad, (int)codes[bad]); return -1; }
+    decode_host(codes, length, codec, format, out, state);
+    return length;
+}
+
+// The chosen utterances' PCM coded (klatt_codec.h): the decoded samples, the codes or both, on one grid.  It reads the pool, so it is ordered
+// as speechPlayer_batch_exportPcm is (ExportStage, ofPcm).  A G.711 law goes tile-wise (the staging block: rows | tile starts and chunk rows,
+// packed); ADPCM a wavefront per 64 rows as filtered_export's (packed rows | groups).  Nothing is kept on the batch.  ofSignal and `signal` as
+// spectrogram_export's.
+static long long coded_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances, long long nUtterances,
+                              int codec, void* decodedOut, int format, void* codesOut, long long rowStride, void* stream)
+{
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (codec < 0 || codec >= kCodecCount) { set_error("%s: codec %d (0 ulaw, 1 alaw, 2 adpcm)", what, codec); return -1; }
+        if (!decodedOut && !codesOut) { set_error("%s: no output (the decoded samples, the codes or both)", what); return -1; }
+        if (tile_request(what, format, rowStride)) return -1;
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
+        ExportSelection s;
+        std::vector<FilterRow> rows;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) -> long long {
+                const long long L = in.len(u);
+                rows.push_back(FilterRow{in.at(u), L, L, tile_row_first(i, rowStride, before), 0, 1});
+                return L;
+            }, in.sig)) return -1;
+        const long long elements = export_elements(what, kSampleNouns, s, rowStride, 1);
+        if (elements <= 0) return elements;
+        if (!in.sig && export_synthesised(b, what)) return -1;
+        const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
+        if (decodedOut && (export_output(b, what, decodedOut, elements, elSize) || signal_memory(in, what, decodedOut, (size_t)elements * elSize))) return -1;
+        if (codesOut && (export_output(b, what, codesOut, elements, 1) || signal_memory(in, what, codesOut, (size_t)elements))) return -1;
+        if (decodedOut && codesOut) {
+            const uintptr_t d = reinterpret_cast<uintptr_t>(decodedOut), c = reinterpret_cast<uintptr_t>(codesOut);
+            if (d < c + (size_t)elements && c < d + (size_t)elements * elSize) { set_error("%s: the decoded samples and the codes overlap", what); return -1; }
+        }
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        if (codec != kCodecAdpcm) {
+            std::vector<ResRow> tileRows;
+            tileRows.reserve(rows.size());
+            for (const FilterRow& r : rows) tileRows.push_back(ResRow{r.src, r.len, r.outLen, r.dst});
+            std::vector<long long> words;
+            const TileTable tiles = tile_row_table(s.counts.data(), s.n, kCodeTile, rowStride, kTimelineChunkLog2, words);
+            StageBlock block;
+            const int rowsAt = block.add(tileRows), wordsAt = block.add(words);
+            ExportStage stage(b, st, block, nullptr, !in.sig, in.sig != nullptr);
+            if (stage.begin()) return -1;
+            CodeArgs A;
+            A.in = in.data; A.rows = stage.device<ResRow>(rowsAt);
+            A.tile = tile_out(stage, wordsAt, tiles, rowStride, decodedOut);
+            A.codes = static_cast<uint8_t*>(codesOut);
+            void (*const ulaw[2][2])(CodeArgs) = {{klatt_code_g711<kCodecUlaw, false, int16_t>, klatt_code_g711<kCodecUlaw, true, int16_t>},
+                                                  {klatt_code_g711<kCodecUlaw, false, float>, klatt_code_g711<kCodecUlaw, true, float>}};
+            void (*const alaw[2][2])(CodeArgs) = {{klatt_code_g711<kCodecAlaw, false, int16_t>, klatt_code_g711<kCodecAlaw, true, int16_t>},
+                                                  {klatt_code_g711<kCodecAlaw, false, float>, klatt_code_g711<kCodecAlaw, true, float>}};
+            if (codec == kCodecUlaw ? launch_tiles(stage, ulaw, in.format(), format, 8, A) : launch_tiles(stage, alaw, in.format(), format, 8, A)) return -1;
+            return elements;
+        }
+        std::vector<FilterRow> packed;
+        std::vector<FilterGroup> groups;
+        filter_pack(rows, packed, groups);
+        StageBlock block;
+        const int rowsAt = block.add(packed), groupsAt = block.add(groups);
+        ExportStage stage(b, st, block, nullptr, !in.sig, in.sig != nullptr);
+        if (stage.begin()) return -1;
+        AdpcmArgs A;
+        A.in = in.data; A.rows = stage.device<FilterRow>(rowsAt);
+        A.groups = stage.device<FilterGroup>(groupsAt); A.nGroups = (long long)groups.size();
+        A.rowStride = rowStride; A.decoded = decodedOut; A.codes = static_cast<uint8_t*>(codesOut);
+        // [input format][outputs - 1][output format]; the codes alone have no output format
+        constexpr int D = kCodeDecoded, C = kCodeCodes;
+        void (*const kernels[2][3][2])(AdpcmArgs) = {
+            {{klatt_code_adpcm<D, false, int16_t>, klatt_code_adpcm<D, true, int16_t>}, {klatt_code_adpcm<C, false, int16_t>, klatt_code_adpcm<C, false, int16_t>},
+             {klatt_code_adpcm<D | C, false, int16_t>, klatt_code_adpcm<D | C, true, int16_t>}},
+            {{klatt_code_adpcm<D, false, float>, klatt_code_adpcm<D, true, float>}, {klatt_code_adpcm<C, false, float>, klatt_code_adpcm<C, false, float>},
+             {klatt_code_adpcm<D | C, false, float>, klatt_code_adpcm<D | C, true, float>}}};
+        const int outputs = (decodedOut ? D : 0) | (codesOut ? C : 0);
+        // a wavefront per group; no more workgroups than keep every SIMD of the device busy several times over
+        const unsigned grid = (unsigned)std::min<long long>(A.nGroups, 64ll * b->cus);
+        hipLaunchKernelGGL(kernels[in.format()][outputs - 1][format], dim3(grid), dim3(kFilterLanes), 0, stage.st, A);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
+}
+
+long long speechPlayer_batch_exportCoded(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int codec, void* decodedOut, int format,
+                                         unsigned char* codesOut, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportCoded")) return -1;
+    return coded_export("exportCoded", batch, false, nullptr, utterances, nUtterances, codec, decodedOut, format, codesOut, rowStride, stream);
+}
+
+// The same of chosen rows of a caller's signal: it reads no pool and needs no synthesis (ExportStage, ofSignal).
+long long speechPlayer_batch_exportCodedOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows, int codec,
+                                           void* decodedOut, int format, unsigned char* codesOut, long long rowStride, void* stream)
+{
+    const char* what = "exportCodedOf";
+    if (refuse_timing_only("speechPlayer_batch_exportCodedOf")) return -1;
+    return coded_export(what, batch, true, signal, rows, nRows, codec, decodedOut, format, codesOut, rowStride, stream);
 }
 
 // ---- the PCM mixed with noise and other utterances (klatt_mix.h) ----------------------------------------------------------------------------

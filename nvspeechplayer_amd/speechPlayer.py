@@ -1077,6 +1077,84 @@ def signalFilter(x, sections, tail=0, dtype=np.float32):
     return _filter_statement("signalFilter", *_signal_samples(x, "signalFilter"), sections, tail, dtype)
 
 
+CODECS = ["ulaw", "alaw", "adpcm"]      # the codec ids of include/speechPlayer_batch.h: G.711 mu-law, G.711 A-law, IMA/DVI ADPCM
+CODE_TILE = 1024                 # kCodeTile of csrc/klatt_codec.h: consecutive samples of one row a workgroup of the G.711 kernel takes at a time
+
+
+def _int16_format(dtype, what):
+    """_sample_format with int16 for None: a codec's output is integer."""
+    return _sample_format(np.int16 if dtype is None else dtype, what)
+
+
+def check_codec_request(codec, codes, decoded, dtype, what="codedTensor"):
+    """The argument checks of BatchPlayer.codedTensor, pcmCode and signalCode that need no GPU, before any library call: codec a name of
+    CODECS or its number; codes and decoded bools, not both False; dtype None / torch.int16 / np.int16 (int16) or torch.float32 /
+    np.float32.  Raises KeyError (the codec), ValueError or TypeError.  Returns (the codec's id, codes, decoded, the format of the decoded
+    samples: 0 int16, 1 float32)."""
+    if isinstance(codec, str):
+        if codec not in CODECS:
+            raise KeyError("%s: codec %r (%s)" % (what, codec, ", ".join(CODECS)))
+        codec = CODECS.index(codec)
+    elif isinstance(codec, (bool, np.bool_)) or not isinstance(codec, (int, np.integer)) or not 0 <= codec < len(CODECS):
+        raise KeyError("%s: codec %r (%s, or 0 .. %d)" % (what, codec, ", ".join(CODECS), len(CODECS) - 1))
+    for name, v in (("codes", codes), ("decoded", decoded)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError("%s: %s must be True or False, not %r" % (what, name, v))
+    if not codes and not decoded:
+        raise ValueError("%s: codes, decoded or both" % what)
+    return int(codec), bool(codes), bool(decoded), _int16_format(dtype, what)
+
+
+def _code_statement(what, s, inFormat, codec, codes, decoded, dtype, state):
+    codec, codes, decoded, fmt = check_codec_request(codec, codes, decoded, dtype, what)
+    d = np.zeros(len(s), np.float32 if fmt else np.int16) if decoded else None
+    c = np.zeros(len(s), np.uint8) if codes else None
+    st = np.zeros(2, np.int32)
+    lead = (s.ctypes.data if len(s) else None,) + (() if inFormat is None else (inFormat,))
+    fn = getattr(_native.load(), "speechPlayer_" + what)
+    _answer(fn(*lead, len(s), codec, fmt, _ptr(d) if len(s) else None, _ptr(c) if len(s) else None, len(s), st.ctypes.data), len(s))
+    out = tuple(a for a in (d, c) if a is not None)
+    out = out if len(out) > 1 else out[0]
+    return (out, (int(st[0]), int(st[1]))) if state else out
+
+
+def pcmCode(pcm, codec, codes=False, decoded=True, dtype=None, state=False):
+    """int16 PCM through a codec on the host (speechPlayer_pcmCode; no GPU): codec "ulaw", "alaw" or "adpcm" (CODECS).  -> the decoded
+    samples (int16, or dtype np.float32: sample / 32767), the codes (uint8, one per sample: 0 .. 255 for G.711, 0 .. 15 for ADPCM;
+    codes[0::2] << 4 | codes[1::2] packs ADPCM nibbles in the usual byte order) or the pair (decoded, codes), by the definition in
+    include/speechPlayer_batch.h -- the integer statement the device equals bit for bit.  state: -> (that, (val, idx)), the ADPCM
+    encoder's state behind the last sample."""
+    return _code_statement("pcmCode", _pcm_samples(pcm, "pcmCode"), None, codec, codes, decoded, dtype, state)
+
+
+def signalCode(x, codec, codes=False, decoded=True, dtype=None, state=False):
+    """pcmCode on a signal's row (speechPlayer_signalCode; no GPU): x as signalSpectrogram's, a float32 sample clipped and rounded to
+    nearest even.  The statement BatchPlayer.codedTensor(signal=...) is held to."""
+    return _code_statement("signalCode", *_signal_samples(x, "signalCode"), codec, codes, decoded, dtype, state)
+
+
+def codecDecode(codes, codec, dtype=None, state=False):
+    """The decoder alone on the host (speechPlayer_codecDecode; no GPU): codes a one-dimensional uint8 array, one code per sample -> int16
+    (or dtype np.float32) samples; for "adpcm" the recursion driven by the codes, each 0 .. 15.  state as pcmCode's."""
+    c = codes if isinstance(codes, np.ndarray) else None
+    if c is None or c.ndim != 1 or c.dtype != np.uint8:
+        raise TypeError("codecDecode: the codes must be a one-dimensional uint8 array, not %s" % (
+            "%s %s" % (c.dtype, list(c.shape)) if c is not None else type(codes).__name__))
+    c = np.ascontiguousarray(c)
+    codec, _, _, fmt = check_codec_request(codec, True, True, dtype, "codecDecode")
+    out = np.zeros(len(c), np.float32 if fmt else np.int16)
+    st = np.zeros(2, np.int32)
+    _answer(_native.load().speechPlayer_codecDecode(_ptr(c) if len(c) else None, len(c), codec, fmt, _ptr(out) if len(c) else None, len(c), st.ctypes.data), len(c))
+    return (out, (int(st[0]), int(st[1]))) if state else out
+
+
+def codecTable(codec):
+    """The 256-entry int16 decode table of a G.711 law ("ulaw" or "alaw"): table[codes.long()] decodes on any device."""
+    if check_codec_request(codec, True, True, None, "codecTable")[0] == CODECS.index("adpcm"):
+        raise ValueError("codecTable: adpcm has no table (its decoder is a recursion: codecDecode)")
+    return codecDecode(np.arange(256, dtype=np.uint8), codec)
+
+
 MIX_TILE = 1024                  # kMixTile of csrc/klatt_mix.h: consecutive outputs of one row a workgroup takes at a time
 MIX_MAX_TERMS = 64               # kMixMaxTerms: of one row
 MIX_MAX_CALL_TERMS = 1 << 22     # kMixMaxCallTerms: of one call
@@ -1615,6 +1693,40 @@ class BatchPlayer(object):
         def call(out, stride, numel, stream):
             return export(sec.ctypes.data, start.ctypes.data, len(start) - 1, _ptr(of), tail, out, fmt, stride, stream)
         return self._export_rows(src.lengths + tail, (), torch.float32 if fmt else torch.int16, padded, call)
+
+    def codedTensor(self, codec, codes=False, decoded=True, utterances=None, dtype=None, padded=True, signal=None):
+        """The batch's PCM through a speech codec as torch tensors on the batch's device (speechPlayer_batch_exportCoded), filled on
+        torch's current stream behind the synthesis without a host wait: codec "ulaw" or "alaw" (G.711) or "adpcm" (IMA/DVI, 4 bits a
+        sample; CODECS).  -> (decoded, lengths), (decoded, codes, lengths) or (codes, lengths): decoded is what a decoder makes of the
+        codes, dtype torch.int16 (default: a codec's output is integer) or torch.float32 (sample / 32767); codes a torch.uint8 tensor of
+        the same layout, one code per sample (0 .. 255 for G.711 -- the mu-law code is the class label vocoders train on --, 0 .. 15
+        for ADPCM; nibble packing is the caller's).  Row lengths are unchanged.  utterances, padded and the lengths as pcmTensor's: +0
+        and code 0 past each row's end.  The batch must have been synthesised since it was set; pcmCode is the same definition on the
+        host, which the device equals bit for bit.  (decoded, lengths) feeds the next stage as its signal=.
+        signal: the (tensor, lengths or offsets) pair another export returned (check_signal_request), read in place of the batch's PCM
+        (speechPlayer_batch_exportCodedOf): `utterances` then chooses rows of the signal, no synthesis is needed and signalCode is the
+        host's statement."""
+        import torch
+        codec, codes, decoded, fmt = check_codec_request(codec, codes, decoded, dtype)
+        src = self._rows("codedTensor", signal, utterances)
+        export = self._entry("Coded", src)
+        lengths = src.lengths
+        # two outputs of one layout (_export_rows makes one): [n, most] (padded) or [total]
+        if padded:
+            stride = int(lengths.max()) if len(lengths) else 0
+            shape, second = (len(lengths), stride), lengths
+        else:
+            stride, second = 0, np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+            shape = (int(second[-1]),)
+        dev = "cuda:%d" % self.device
+        d = torch.empty(shape, dtype=torch.float32 if fmt else torch.int16, device=dev) if decoded else None
+        c = torch.empty(shape, dtype=torch.uint8, device=dev) if codes else None
+        numel = int(np.prod(shape))
+        if numel:
+            got = self._check(export(codec, d.data_ptr() if decoded else None, fmt, c.data_ptr() if codes else None, stride,
+                                     torch.cuda.current_stream(self.device).cuda_stream))
+            assert got == numel, (got, numel)
+        return tuple(t for t in (d, c) if t is not None) + (torch.from_numpy(second),)
 
     def setNoiseBank(self, clips):
         """The batch's noise bank (speechPlayer_batch_setNoiseBank): a list of one-dimensional float arrays (kept as float32), every value
