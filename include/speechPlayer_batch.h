@@ -651,6 +651,8 @@ long long speechPlayer_pcmMix(const sample* pcm, long long length, float speechG
  * at 0 or that decrease; a length above 2^44; data that is not device memory of the batch's device, misaligned to its element, or
  * whose allocation is smaller than the rows need (a signal whose rows are all empty is not read and may have no data); a row number
  * outside the signal; an output that overlaps the signal; srcRate <= 0.  The message names the row.
+ * Limits      A row has at most 2^44 samples, a signal 2^60 elements, an output 2^50; tests/test_gpu_far_offsets.py runs every export
+ *             past elements 2^31 and 2^32 of its output and of a signal, and past sample 2^31 of the pool (docs/KERNELS.md 4.22).
  * Out of scope: in a mix onto a signal, a term from a different signal or from the pool; live handles; NodePlayer beyond
  * speechPlayer_node_part; active-speech levels and loudness weighting; a fused kernel for the chain; float64 or float16 signals; label
  * grids at a resampled rate. */

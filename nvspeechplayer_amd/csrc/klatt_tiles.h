@@ -51,6 +51,38 @@ KLATT_RES_HD int tile_n(long long rowStride, long long outLen, long long t0, int
 // Of the n elements from output t0, those inside the row; the rest is padding
 KLATT_RES_HD int tile_live(int n, long long outLen, long long t0) { const long long left = outLen - t0; return (int)(left < n ? (left > 0 ? left : 0) : n); }
 
+// ---- the locators (tests/native/check_locate.cpp) --------------------------------------------------------------------------------------------
+constexpr int kTimelineChunkLog2 = 15;      // steps per chunk of the packed form's row table
+
+// The row of entry g of a packed output and the entry's place in it: the last row among [lo, hi) whose start is <= g.
+KLATT_RES_HD void packed_locate(long long g, const long long* __restrict__ start, long long lo, long long hi, long long& r, long long& j)
+{
+    while (hi - lo > 1) { const long long mid = (lo + hi) >> 1; if (start[mid] <= g) lo = mid; else hi = mid; }
+    r = lo; j = g - start[r];
+}
+KLATT_RES_HD void packed_locate(long long g, const long long* __restrict__ start, long long nRows, long long& r, long long& j)
+{
+    packed_locate(g, start, 0, nRows, r, j);
+}
+
+// Element e0 of a [row][step][column] output is (r, j, q): g = e0 / nCols is the step's number in the output, the row g / rowStride
+// (padded) or by bisection over stepStart within the chunk table's bounds (packed: rowStride 0).  32-bit divisions where they do.
+KLATT_RES_HD void dense_locate(long long e0, int nCols, long long rowStride, const long long* __restrict__ stepStart,
+                               const long long* __restrict__ chunkRow, long long& g, int& q, long long& r, long long& j)
+{
+    if (nCols == 1) { g = e0; q = 0; }
+    else if ((unsigned long long)e0 >> 32) { g = e0 / nCols; q = (int)(e0 - g * nCols); }
+    else { const uint32_t g32 = (uint32_t)e0 / (uint32_t)nCols; g = g32; q = (int)((uint32_t)e0 - g32 * (uint32_t)nCols); }
+    if (rowStride > 0) {
+        if (((unsigned long long)g | (unsigned long long)rowStride) >> 32) r = g / rowStride;
+        else r = (uint32_t)g / (uint32_t)rowStride;
+        j = g - r * rowStride;
+    } else {
+        const long long c = g >> kTimelineChunkLog2;
+        packed_locate(g, stepStart, chunkRow[c], chunkRow[c + 1] + 1, r, j);
+    }
+}
+
 // ---- the reader ----------------------------------------------------------------------------------------------------------------------------
 // x of a sample: an int16 as speechPlayer_batch_exportPcm's format 1 gives it, a float32 as it is
 KLATT_RES_HD float tile_x(int s) { return (float)s / 32767.0f; }
@@ -159,7 +191,6 @@ inline bool signal_values(const float* x, long long length, std::string& why)
 }  // namespace klatt
 
 #if defined(__HIPCC__)      // ---- the device ----
-#include "klatt_timeline.h"
 
 namespace klatt {
 

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "klatt_device.h"
+#include "klatt_tiles.h"
 
 namespace klatt {
 
@@ -149,36 +150,7 @@ __device__ __forceinline__ double timeline_side(const double* __restrict__ frame
     return frames[(long long)src * kNumParams + col];
 }
 
-constexpr int kTimelineChunkLog2 = 15;      // steps per chunk of the packed form's row table
-
-// The row of entry g of a packed output and the entry's place in it: the last row among [lo, hi) whose start is <= g.
-__device__ __forceinline__ void packed_locate(long long g, const long long* __restrict__ start, long long lo, long long hi, long long& r, long long& j)
-{
-    while (hi - lo > 1) { const long long mid = (lo + hi) >> 1; if (start[mid] <= g) lo = mid; else hi = mid; }
-    r = lo; j = g - start[r];
-}
-__device__ __forceinline__ void packed_locate(long long g, const long long* __restrict__ start, long long nRows, long long& r, long long& j)
-{
-    packed_locate(g, start, 0, nRows, r, j);
-}
-
-// Element e0 of a [row][step][column] output is (r, j, q): g = e0 / nCols is the step's number in the output, the row g / rowStride
-// (padded) or by bisection over stepStart within the chunk table's bounds (packed: rowStride 0).  32-bit divisions where they do.
-__device__ __forceinline__ void dense_locate(long long e0, int nCols, long long rowStride, const long long* __restrict__ stepStart,
-                                             const long long* __restrict__ chunkRow, long long& g, int& q, long long& r, long long& j)
-{
-    if (nCols == 1) { g = e0; q = 0; }
-    else if ((unsigned long long)e0 >> 32) { g = e0 / nCols; q = (int)(e0 - g * nCols); }
-    else { const uint32_t g32 = (uint32_t)e0 / (uint32_t)nCols; g = g32; q = (int)((uint32_t)e0 - g32 * (uint32_t)nCols); }
-    if (rowStride > 0) {
-        if (((unsigned long long)g | (unsigned long long)rowStride) >> 32) r = g / rowStride;
-        else r = (uint32_t)g / (uint32_t)rowStride;
-        j = g - r * rowStride;
-    } else {
-        const long long c = g >> kTimelineChunkLog2;
-        packed_locate(g, stepStart, chunkRow[c], chunkRow[c + 1] + 1, r, j);
-    }
-}
+// kTimelineChunkLog2, packed_locate and dense_locate -- the row of an output's entry -- are klatt_tiles.h's: the host compiles them too.
 
 // A lane's 16 bytes: EL elements of T from element e0 of the output, one store where the output is aligned and the lane is whole.
 template <typename T, typename V, int EL>

@@ -1508,7 +1508,9 @@ class BatchPlayer(object):
     def _export_rows(self, counts, tail_shape, dtype, padded, call, always=False):
         """The output of an export of len(counts) rows of counts[i] entries of shape tail_shape: [n, most, ...] (padded) or [total, ...],
         filled by call(pointer, rowStride, elements, stream) on torch's current stream -- not made for an empty tensor unless `always`
-        (then with a null pointer) -- which answers the elements written.  -> (out, counts or, packed, the n + 1 offsets: int64 CPU tensors)."""
+        (then with a null pointer) -- which answers the elements written.  -> (out, counts or, packed, the n + 1 offsets: int64 CPU tensors).
+        tests/test_gpu_far_offsets.py replaces this method on a player (into_guarded) to aim the exports at buffers of its own: a change
+        of the signature is a change there."""
         import torch
         dev = self.device
         if padded:

@@ -227,6 +227,19 @@ def test_export_planning_under_sanitizers(tmp_path):
     assert out.startswith("ok ") and "runtime error" not in out and "AddressSanitizer" not in out, out
 
 
+def test_locators_beyond_32_bits_under_sanitizers(tmp_path):
+    """packed_locate and dense_locate (csrc/klatt_tiles.h), which the dense and the tile-wise kernels address their outputs with, against
+    128-bit division and a linear scan in tests/native/check_locate.cpp, under AddressSanitizer + UBSan: windows around 2^31, 2^32, 2^33
+    and 2^49 elements, random elements below 2^50, packed rows of 2^33 steps; every magnitude branch of dense_locate counted."""
+    exe = str(tmp_path / "check_locate")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "native", "check_locate.cpp"), "-o", exe])
+    out = subprocess.check_output([exe], stderr=subprocess.STDOUT).decode()
+    assert out.startswith("ok ") and "runtime error" not in out and "AddressSanitizer" not in out, out
+    taken = [int(n) for n in re.findall(r": (\d+)", out)]
+    assert len(taken) == 5 and min(taken) > 0, out
+
+
 def test_tile_walk_and_row_writer_under_sanitizers(tmp_path):
     """The tile walk and the row writer of the PCM-derived exports (csrc/klatt_tiles.h, tile_row_table of csrc/klatt_export.h) against
     brute force in tests/native/check_tiles.cpp, under AddressSanitizer + UBSan: every lane of every run into a guarded buffer at every
