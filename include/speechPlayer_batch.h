@@ -651,8 +651,9 @@ long long speechPlayer_pcmMix(const sample* pcm, long long length, float speechG
  * at 0 or that decrease; a length above 2^44; data that is not device memory of the batch's device, misaligned to its element, or
  * whose allocation is smaller than the rows need (a signal whose rows are all empty is not read and may have no data); a row number
  * outside the signal; an output that overlaps the signal; srcRate <= 0.  The message names the row.
- * Limits      A row has at most 2^44 samples, a signal 2^60 elements, an output 2^50; tests/test_gpu_far_offsets.py runs every export
- *             past elements 2^31 and 2^32 of its output and of a signal, and past sample 2^31 of the pool (docs/KERNELS.md 4.22).
+ * Limits      A row has at most 2^44 samples, a signal 2^60 elements, an output 2^50; tests/test_gpu_far_offsets.py (and
+ *             tests/test_gpu_lpc.py for the linear-prediction exports) runs every export past elements 2^31 and 2^32 of its output and
+ *             of a signal, and past sample 2^31 of the pool (docs/KERNELS.md 4.22).
  * Out of scope: in a mix onto a signal, a term from a different signal or from the pool; live handles; NodePlayer beyond
  * speechPlayer_node_part; active-speech levels and loudness weighting; a fused kernel for the chain; float64 or float16 signals; label
  * grids at a resampled rate. */
@@ -855,6 +856,110 @@ long long speechPlayer_batch_exportCoded(speechPlayer_batch_t batch, const long 
 	int format, unsigned char* codesOut, long long rowStride, void* stream);
 long long speechPlayer_batch_exportCodedOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
 	int codec, void* decodedOut, int format, unsigned char* codesOut, long long rowStride, void* stream);
+/*
+ * Linear prediction (LPC) of a batch's PCM, or of a signal's rows, on the step grid of the other exports: per analysis frame the
+ * autocorrelation, the prediction coefficients, the reflection coefficients and the prediction error; and, per sample, the residual or
+ * the prediction by the frames' own coefficients -- what autoregressive vocoders of the LPCNet family and every classical speech front
+ * end take beside the mu-law code, and the classical estimate of the vocal-tract envelope that speechPlayer_batch_exportResponse states
+ * exactly.  A row of L samples is read as the other exports of the PCM read it: an int16 s is (float)s / 32767.0f, a float32 is taken as
+ * it is, a sample outside 0 .. L-1 is +0 and nothing is loaded there.
+ *   steps     the spectrogram's grid, row for row: step j is centred on c = phase + j * hop; a row has ceil((L - phase) / hop) steps, 0 when
+ *             L <= phase
+ *   frame     x[i] is sample c - floor(nWin / 2) + i for i = 0 .. nWin-1.  order lies in 1 .. 32 (kLpcMaxOrder); nWin is any integer with
+ *             order < nWin <= 4096 (kLpcMaxWin), not only a power of two (20 to 25 ms windows are 320, 400, 551 samples)
+ *   window    window[nWin], a HOST array of doubles, each rounded to float32 once; NULL: the periodic Hann 0.5 - 0.5 cos(2 pi i / nWin),
+ *             evaluated in binary64 on the host.  xw[i] = x[i] * w[i], one float32 product
+ *   autocorrelation   for k = 0 .. order: term(i, k) = (double)xw[i] * (double)xw[i - k], exact in binary64 (fusing it into an FMA changes
+ *             no bit); partial[q], q = 0 .. 63, is the sum from +0.0, in ascending i, of term(i, k) over k <= i < nWin with i mod 64 == q;
+ *             r[k] is the balanced binary tree over the 64 partials in natural order, t[i] = t[2i] + t[2i+1], six levels.  A partial that
+ *             starts from +0.0 is never -0.0, and adding +-0 to a value that is not -0.0 changes no bit, so terms with a zero factor
+ *             (samples outside the row, the exact zeros of a silence) may be skipped
+ *   lag window   lagWindow[order + 1], a HOST array of finite doubles: r[k] <- r[k] * lagWindow[k], one binary64 product; NULL: no
+ *             multiplication at all.  White-noise correction is lagWindow[0] = 1 + eps; Gaussian lag windowing the rest
+ *   recursion (Levinson-Durbin), entirely in binary64 with explicit fma:
+ *                 E = r[0]; a[1..order] = k[1..order] = +0.0; stages = 0
+ *                 for i = 1 .. order:
+ *                     if not (E > 0 and E finite): stop
+ *                     acc = r[i];  for j = 1 .. i-1 ascending: acc = fma(a[j], r[i-j], acc)
+ *                     kappa = -acc / E
+ *                     if not (|kappa| < 1): stop          (a NaN stops too: the frame is not positive definite in binary64)
+ *                     for j = 1 .. i-1: a'[j] = fma(kappa, a[i-j], a[j])   (all from the old a)
+ *                     a = a'; a[i] = kappa; k[i] = kappa
+ *                     E = fma(kappa, acc, E); stages = i
+ *             Sign convention: A(z) = 1 + sum a_j z^-j; the prediction of x(t) is -sum a_j x(t-j).  A silent frame (r[0] = +0) gives
+ *             stages = 0 and all values +0
+ *   fields    `what` is a bit set; the fields come in this fixed order whatever the order of the bits: 1 AUTOCORR order + 1 values, r
+ *             after the lag window; 2 LPC order values, a_1 .. a_order; 4 REFLECTION order values, k_1 .. k_order; 8 ERROR one value, E;
+ *             16 STAGES one value, stages as a number.  nCols is their total
+ *   output    element (row, step, col) of [row][step][nCols]; format 0 float64, 1 float32 rounded to nearest
+ * The inverse filter: a row's samples through the time-varying FIR of its own frames' coefficients -- no recursion, no synthesis of its
+ * own.  The coefficients come from a DEVICE tensor [row][step][coeffCols] (format 0 float64, 1 float32 widened exactly), a_1 .. a_order at
+ * columns col0 .. col0 + order - 1: one the analysis wrote for the same rows, hop and phase, or the caller's own (bandwidth-expanded,
+ * quantised, a network's).  coeffStride is in steps: 0 packed, else padded; row i of the tensor belongs to the i-th chosen row.
+ *   frame of a sample   for sample t of a row with steps > 0: j = min(steps - 1, (max(t - phase, 0) + floor(hop / 2)) / hop) in 64-bit
+ *             integers -- the nearest centre, ties upward.  A row without steps uses coefficients +0
+ *   residual  (what 0) s = (double)x(t); for m = 1 .. order ascending: s = fma(a_m, (double)x(t - m), s); e(t) = (float)s
+ *   prediction   (what 1) the same chain from +0.0; p(t) = (float)(-s)
+ *   output    L samples per row; format 1 float32, format 0 int16 by the resampler's conversion of the float32 value; padded or packed as
+ *             the resampled, filtered and coded exports are, so (tensor, lengths) is a signal for the next stage
+ * Bits are unspecified for non-finite coefficients, as for samples outside the signal bound; no value ever steers an address.
+ * The definition is the function bodies of csrc/klatt_lpc.h, which the host and the device compile from one source.  Over the pool the
+ * result is a function of the batch's PCM: it depends on the mode and needs a synthesis launch.
+ * Out of scope: line spectral frequencies; Burg and covariance methods; the recursive synthesis filter 1 / A(z); order above 32;
+ * pre-emphasis inside the export (the chain is exportFiltered with a pre-emphasis section, then the signal form); live handles; NodePlayer
+ * beyond speechPlayer_node_part.
+ *
+ * Host only, touches no device: the recursion alone on r[order + 1].  a and k take order values each (a_1 .., k_1 ..), error E, stages the
+ * stages done; each may be NULL.  Returns order; -1 on order outside 1 .. 32 or a NULL r. */
+long long speechPlayer_lpcFromAutocorrelation(const double* r, int order, double* a, double* k, double* error, int* stages);
+/* Host only, touch no device: the analysis above on `length` samples of plain PCM (speechPlayer_pcmLpc) or of a signal's row, int16
+ * (inFormat 0) or float32 (inFormat 1) (speechPlayer_signalLpc), out[step][nCols] float64 -- the statements the device is held to bit for
+ * bit.  Return steps * nCols; -1 on an unknown inFormat, length < 0 or above 2^44, a NULL input with length > 0, hop <= 0, phase < 0,
+ * order outside 1 .. 32, nWin outside order + 1 .. 4096, a non-finite window or lagWindow value, what 0 or with a bit above 16, a NULL out
+ * with steps > 0, and (signalLpc) a float32 sample that is not finite or above 2^16 in magnitude. */
+long long speechPlayer_pcmLpc(const sample* pcm, long long length, int order, int nWin, long long hop, long long phase, const double* window,
+	const double* lagWindow, int what, double* out);
+long long speechPlayer_signalLpc(const void* x, int inFormat, long long length, int order, int nWin, long long hop, long long phase,
+	const double* window, const double* lagWindow, int what, double* out);
+/* Host only: the inverse filter above on `length` samples with the coefficients a HOST array double[steps][order]; out float[length]
+ * (format 1) or int16[length] (format 0) of `capacity` elements.  Return length; -1 on an unknown inFormat, length < 0 or above 2^44, a
+ * NULL input with length > 0, hop <= 0, phase < 0, order outside 1 .. 32, what outside {0, 1}, an unknown format, NULL coefficients with
+ * steps > 0, a NULL out with length > 0, a capacity below length, and (signalLpcResidual) a float32 sample outside the signal bound. */
+long long speechPlayer_pcmLpcResidual(const sample* pcm, long long length, int order, long long hop, long long phase, const double* coeff, int what,
+	int format, void* out, long long capacity);
+long long speechPlayer_signalLpcResidual(const void* x, int inFormat, long long length, int order, long long hop, long long phase, const double* coeff,
+	int what, int format, void* out, long long capacity);
+/* The analysis of chosen utterances (exportLpc) or of chosen rows of `signal` (exportLpcOf) into caller-owned device memory on the caller's
+ * stream.  utterances / rows (any order, repeats allowed, NULL: all), rowStride (in steps, +0 past a row's end; 0: the rows back to back),
+ * the return value (elements written; 0 writes nothing and needs no buffer), the ordering by events, the sixteen-in-flight rule, the
+ * device-memory, alignment and size checks and the signal contract (not the pool, no synthesis needed, the output may not overlap the
+ * signal) are those of speechPlayer_batch_exportSpectrogram / exportSpectrogramOf.  A 256-lane workgroup takes 64 consecutive steps of the
+ * output (csrc/klatt_lpc.h).
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: what speechPlayer_batch_exportSpectrogram / exportSpectrogramOf refuse of the
+ * batch, the signal, hop, phase, the format, the selection, rowStride and the output; order outside 1 .. 32; nWin outside order + 1 ..
+ * 4096; a non-finite window or lagWindow value; what 0 or with a bit above 16. */
+long long speechPlayer_batch_exportLpc(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int order, int nWin,
+	long long hop, long long phase, const double* window, const double* lagWindow, int what, void* deviceOut, int format, long long rowStride,
+	void* stream);
+long long speechPlayer_batch_exportLpcOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	int order, int nWin, long long hop, long long phase, const double* window, const double* lagWindow, int what, void* deviceOut, int format,
+	long long rowStride, void* stream);
+/* The residual (what 0) or the prediction (what 1) of chosen utterances (exportLpcResidual) or of chosen rows of `signal`
+ * (exportLpcResidualOf), the coefficients read from deviceCoeff as described above.  utterances / rows, the rows' forms (rowStride in
+ * samples), the return value, the device-memory checks, the sixteen-in-flight rule and the ordering by events are those of
+ * speechPlayer_batch_exportFiltered / exportFilteredOf; the caller orders whatever wrote the coefficients before the export on `stream`.
+ * Tile-wise, a 256-lane workgroup per kLpcTile = 1024 samples of a row (csrc/klatt_lpc.h).
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: what speechPlayer_batch_exportFiltered / exportFilteredOf refuse of the
+ * format, rowStride, the batch, the signal, the selection and the output; order outside 1 .. 32; hop <= 0; phase < 0; what outside
+ * {0, 1}; an unknown coeffFormat; col0 < 0 or col0 + order > coeffCols; a coeffStride below the largest step count; a coefficient tensor
+ * that is not device memory of the batch's device, misaligned to its element or too small for the rows' steps; an output that overlaps the
+ * coefficients or the signal. */
+long long speechPlayer_batch_exportLpcResidual(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int order, long long hop,
+	long long phase, const void* deviceCoeff, int coeffFormat, int coeffCols, int col0, long long coeffStride, int what, void* deviceOut, int format,
+	long long rowStride, void* stream);
+long long speechPlayer_batch_exportLpcResidualOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	int order, long long hop, long long phase, const void* deviceCoeff, int coeffFormat, int coeffCols, int col0, long long coeffStride, int what,
+	void* deviceOut, int format, long long rowStride, void* stream);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

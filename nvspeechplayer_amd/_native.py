@@ -71,6 +71,8 @@ EXPORTS = [
     "speechPlayer_pcmFilter", "speechPlayer_signalFilter", "speechPlayer_batch_exportFiltered", "speechPlayer_batch_exportFilteredOf",
     "speechPlayer_planTrackKinds",
     "speechPlayer_pcmCode", "speechPlayer_signalCode", "speechPlayer_codecDecode", "speechPlayer_batch_exportCoded", "speechPlayer_batch_exportCodedOf",
+    "speechPlayer_lpcFromAutocorrelation", "speechPlayer_pcmLpc", "speechPlayer_signalLpc", "speechPlayer_pcmLpcResidual", "speechPlayer_signalLpcResidual",
+    "speechPlayer_batch_exportLpc", "speechPlayer_batch_exportLpcOf", "speechPlayer_batch_exportLpcResidual", "speechPlayer_batch_exportLpcResidualOf",
 ]
 
 
@@ -441,6 +443,24 @@ def load():
     L.speechPlayer_batch_exportCoded.argtypes = [vp, vp, i64, i32, vp, i32, vp, i64, vp]
     L.speechPlayer_batch_exportCodedOf.restype = i64
     L.speechPlayer_batch_exportCodedOf.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, i64, vp]
+    L.speechPlayer_lpcFromAutocorrelation.restype = i64
+    L.speechPlayer_lpcFromAutocorrelation.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.speechPlayer_pcmLpc.restype = i64
+    L.speechPlayer_pcmLpc.argtypes = [vp, i64, i32, i32, i64, i64, vp, vp, i32, vp]
+    L.speechPlayer_signalLpc.restype = i64
+    L.speechPlayer_signalLpc.argtypes = [vp, i32, i64, i32, i32, i64, i64, vp, vp, i32, vp]
+    L.speechPlayer_pcmLpcResidual.restype = i64
+    L.speechPlayer_pcmLpcResidual.argtypes = [vp, i64, i32, i64, i64, vp, i32, i32, vp, i64]
+    L.speechPlayer_signalLpcResidual.restype = i64
+    L.speechPlayer_signalLpcResidual.argtypes = [vp, i32, i64, i32, i64, i64, vp, i32, i32, vp, i64]
+    L.speechPlayer_batch_exportLpc.restype = i64
+    L.speechPlayer_batch_exportLpc.argtypes = [vp, vp, i64, i32, i32, i64, i64, vp, vp, i32, vp, i32, i64, vp]
+    L.speechPlayer_batch_exportLpcOf.restype = i64
+    L.speechPlayer_batch_exportLpcOf.argtypes = [vp, vp, vp, i64, i32, i32, i64, i64, vp, vp, i32, vp, i32, i64, vp]
+    L.speechPlayer_batch_exportLpcResidual.restype = i64
+    L.speechPlayer_batch_exportLpcResidual.argtypes = [vp, vp, i64, i32, i64, i64, vp, i32, i32, i32, i64, i32, vp, i32, i64, vp]
+    L.speechPlayer_batch_exportLpcResidualOf.restype = i64
+    L.speechPlayer_batch_exportLpcResidualOf.argtypes = [vp, vp, vp, i64, i32, i64, i64, vp, i32, i32, i32, i64, i32, vp, i32, i64, vp]
     L.speechPlayer_batch_exportPowerOf.restype = i64
     L.speechPlayer_batch_exportPowerOf.argtypes = [vp, vp, vp, i64, vp, vp]
     L.speechPlayer_batch_exportMixedOf.restype = i64

@@ -25,6 +25,7 @@
 #include "klatt_convolve.h"
 #include "klatt_filter.h"
 #include "klatt_codec.h"
+#include "klatt_lpc.h"
 #include "klatt_mix.h"
 #include "klatt_export.h"
 #include "klatt_batchplan.h"
@@ -5874,6 +5875,265 @@ long long speechPlayer_batch_exportCodedOf(speechPlayer_batch_t batch, const spe
     const char* what = "exportCodedOf";
     if (refuse_timing_only("speechPlayer_batch_exportCodedOf")) return -1;
     return coded_export(what, batch, true, signal, rows, nRows, codec, decodedOut, format, codesOut, rowStride, stream);
+}
+
+// ---- linear prediction of the PCM (klatt_lpc.h) -------------------------------------------------------------------------------------------
+// Host only, touch no device: the definition of include/speechPlayer_batch.h through the functions the kernels are compiled from.
+long long speechPlayer_lpcFromAutocorrelation(const double* r, int order, double* a, double* k, double* error, int* stages)
+{
+    begin_call();
+    const char* what = "lpcFromAutocorrelation";
+    if (order < 1 || order > kLpcMaxOrder) { set_error("%s: order %d (1 .. %d)", what, order, kLpcMaxOrder); return -1; }
+    if (!r) { set_error("%s: no autocorrelation (order + 1 values)", what); return -1; }
+    double rr[kLpcMaxOrder + 1] = {}, aa[kLpcMaxOrder + 1], kk[kLpcMaxOrder + 1], E;
+    int done;
+    for (int i = 0; i <= order; ++i) rr[i] = r[i];
+    lpc_levinson(rr, order, aa, kk, E, done);
+    for (int i = 1; i <= order; ++i) { if (a) a[i - 1] = aa[i]; if (k) k[i - 1] = kk[i]; }
+    if (error) *error = E;
+    if (stages) *stages = done;
+    return order;
+}
+
+static long long lpc_statement(const char* what, const void* x, int inFormat, long long length, int order, int nWin, long long hop, long long phase,
+                               const double* window, const double* lagWindow, int fields, double* out)
+{
+    if (signal_host_format(what, inFormat)) return -1;
+    if (length < 0 || length > kResampleMaxLength || hop <= 0 || phase < 0 || (length > 0 && !x)) {
+        set_error("%s: length %lld (0 .. 2^44, with its samples), hop %lld, phase %lld", what, length, hop, phase); return -1;
+    }
+    try {
+        LpcPlan P;
+        std::string why;
+        if (!lpc_plan(P, order, nWin, window, lagWindow, fields, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
+        if (align_steps_below(length, hop, phase) > 0 && !out) { set_error("%s: no output", what); return -1; }
+        if (signal_host_values(what, x, inFormat, length)) return -1;
+        return inFormat ? lpc_host(static_cast<const float*>(x), length, P, hop, phase, out) : lpc_host(static_cast<const int16_t*>(x), length, P, hop, phase, out);
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
+long long speechPlayer_pcmLpc(const sample* pcm, long long length, int order, int nWin, long long hop, long long phase, const double* window,
+                              const double* lagWindow, int what, double* out)
+{
+    begin_call();
+    return lpc_statement("pcmLpc", pcm, 0, length, order, nWin, hop, phase, window, lagWindow, what, out);
+}
+
+long long speechPlayer_signalLpc(const void* x, int inFormat, long long length, int order, int nWin, long long hop, long long phase, const double* window,
+                                 const double* lagWindow, int what, double* out)
+{
+    begin_call();
+    return lpc_statement("signalLpc", x, inFormat, length, order, nWin, hop, phase, window, lagWindow, what, out);
+}
+
+// What the inverse filter's statements and exports share of their request
+static int lpc_residual_request(const char* what, int order, int which, int format)
+{
+    if (order < 1 || order > kLpcMaxOrder) { set_error("%s: order %d (1 .. %d)", what, order, kLpcMaxOrder); return -1; }
+    if (which != kLpcResidual && which != kLpcPrediction) { set_error("%s: what %d (0 residual, 1 prediction)", what, which); return -1; }
+    if (format != 0 && format != 1) { set_error("%s: format %d (0 int16, 1 float32)", what, format); return -1; }
+    return 0;
+}
+
+static long long lpc_residual_statement(const char* what, const void* x, int inFormat, long long length, int order, long long hop, long long phase,
+                                        const double* coeff, int which, int format, void* out, long long capacity)
+{
+    if (signal_host_format(what, inFormat)) return -1;
+    if (length < 0 || length > kResampleMaxLength || hop <= 0 || phase < 0 || (length > 0 && !x)) {
+        set_error("%s: length %lld (0 .. 2^44, with its samples), hop %lld, phase %lld", what, length, hop, phase); return -1;
+    }
+    if (lpc_residual_request(what, order, which, format)) return -1;
+    hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
+    if (align_steps_below(length, hop, phase) > 0 && !coeff) { set_error("%s: no coefficients ([steps][order] doubles)", what); return -1; }
+    if (length > 0 && !out) { set_error("%s: no output", what); return -1; }
+    if (capacity < length) { set_error("%s: the output takes %lld elements, capacity is %lld", what, length, capacity); return -1; }
+    if (signal_host_values(what, x, inFormat, length)) return -1;
+    if (inFormat) lpc_inverse_host(static_cast<const float*>(x), length, order, hop, phase, coeff, which, format, out);
+    else lpc_inverse_host(static_cast<const int16_t*>(x), length, order, hop, phase, coeff, which, format, out);
+    return length;
+}
+
+long long speechPlayer_pcmLpcResidual(const sample* pcm, long long length, int order, long long hop, long long phase, const double* coeff, int what, int format,
+                                      void* out, long long capacity)
+{
+    begin_call();
+    return lpc_residual_statement("pcmLpcResidual", pcm, 0, length, order, hop, phase, coeff, what, format, out, capacity);
+}
+
+long long speechPlayer_signalLpcResidual(const void* x, int inFormat, long long length, int order, long long hop, long long phase, const double* coeff, int what,
+                                         int format, void* out, long long capacity)
+{
+    begin_call();
+    return lpc_residual_statement("signalLpcResidual", x, inFormat, length, order, hop, phase, coeff, what, format, out, capacity);
+}
+
+// The analysis of chosen utterances' PCM, 64 steps of the output per workgroup (klatt_lpc.h).  The host path is spectrogram_export's, step for
+// step: it reads the pool, so it is ordered as speechPlayer_batch_exportPcm is (ExportStage, ofPcm).  The staging block: rows | step starts
+// and chunk rows (packed) | window | lag window.  ofSignal and `signal` as spectrogram_export's.
+static long long lpc_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances, long long nUtterances,
+                            int order, int nWin, long long hop, long long phase, const double* window, const double* lagWindow, int fields, void* deviceOut, int format,
+                            long long rowStride, void* stream)
+{
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("%s: format %d (0 float64, 1 float32)", what, format); return -1; }
+        if (step_request(what, hop, phase, rowStride)) return -1;
+        LpcPlan P;
+        std::string why;
+        if (!lpc_plan(P, order, nWin, window, lagWindow, fields, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
+        ExportSelection s;
+        std::vector<SpecRow> rows;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long, long long u, long long) {
+                const long long L = in.len(u);
+                rows.push_back(SpecRow{in.at(u), L, align_steps_below(L, hop, phase)});
+                return rows.back().steps;
+            }, in.sig)) return -1;
+        static constexpr ExportNouns kFieldNouns{"largest step count", "steps", "values"};
+        const long long elements = export_elements(what, kFieldNouns, s, rowStride, P.nCols);
+        if (elements <= 0) return elements;
+        if (!in.sig && export_synthesised(b, what)) return -1;
+        const size_t elSize = format ? sizeof(float) : sizeof(double);
+        if (export_output(b, what, deviceOut, elements, elSize) || signal_memory(in, what, deviceOut, (size_t)elements * elSize)) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+
+        const bool packed = rowStride == 0;
+        std::vector<long long> words;
+        const RowTable table = packed ? packed_row_table(s.counts.data(), 0, s.n, kTimelineChunkLog2, words) : RowTable{0, 0};
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words), windowAt = block.add(P.window), lagAt = block.add(P.lag);
+        void (*const kernels[2][2])(LpcArgs) = {{klatt_lpc<false, int16_t>, klatt_lpc<true, int16_t>}, {klatt_lpc<false, float>, klatt_lpc<true, float>}};
+        const auto kernel = kernels[in.format()][format];
+        ExportStage stage(b, st, block, nullptr, !in.sig, in.sig != nullptr);
+        if (stage.begin([&] { return ensure_lds_limit(reinterpret_cast<const void*>(kernel), (int)kLpcLdsBudget); })) return -1;
+        LpcArgs A;
+        A.in = in.data; A.rows = stage.device<SpecRow>(rowsAt);
+        A.start = packed ? stage.device<long long>(wordsAt) + table.startOff : nullptr;
+        A.chunk = packed ? stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
+        A.rowStride = rowStride; A.nSteps = elements / P.nCols;
+        A.hop = hop; A.phase = phase;
+        A.window = stage.device<float>(windowAt); A.lag = P.hasLag ? stage.device<double>(lagAt) : nullptr;
+        A.order = P.order; A.nWin = P.nWin; A.what = P.what; A.nCols = P.nCols;
+        A.out = deviceOut;
+        const long long nGroups = (A.nSteps + kLpcGroup - 1) / kLpcGroup;
+        const unsigned grid = (unsigned)std::min<long long>(nGroups, 8ll * b->cus);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lpc_lds_bytes(P.nWin, P.order, P.nCols, (int)elSize), st, A);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
+}
+
+long long speechPlayer_batch_exportLpc(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int order, int nWin, long long hop,
+                                       long long phase, const double* window, const double* lagWindow, int what, void* deviceOut, int format, long long rowStride,
+                                       void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportLpc")) return -1;
+    return lpc_export("exportLpc", batch, false, nullptr, utterances, nUtterances, order, nWin, hop, phase, window, lagWindow, what, deviceOut, format, rowStride, stream);
+}
+
+// The same of chosen rows of a caller's signal: it reads no pool and needs no synthesis (ExportStage, ofSignal).
+long long speechPlayer_batch_exportLpcOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows, int order, int nWin,
+                                         long long hop, long long phase, const double* window, const double* lagWindow, int what, void* deviceOut, int format,
+                                         long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportLpcOf")) return -1;
+    return lpc_export("exportLpcOf", batch, true, signal, rows, nRows, order, nWin, hop, phase, window, lagWindow, what, deviceOut, format, rowStride, stream);
+}
+
+// The chosen rows through the inverse filter of their own frames' coefficients, tile-wise (klatt_lpc.h): the residual or the prediction.  The
+// host path is the tile-wise exports'; the coefficients are a device tensor [row][step][coeffCols], checked as the signal's memory is.  The
+// staging block: rows | tile starts and chunk rows (packed).  Nothing is kept on the batch.  ofSignal and `signal` as spectrogram_export's.
+static long long lpc_residual_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances,
+                                     long long nUtterances, int order, long long hop, long long phase, const void* coeff, int coeffFormat, int coeffCols, int col0,
+                                     long long coeffStride, int which, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (tile_request(what, format, rowStride)) return -1;
+        if (lpc_residual_request(what, order, which, format)) return -1;
+        if (hop <= 0 || phase < 0) { set_error("%s: hop %lld, phase %lld", what, hop, phase); return -1; }
+        hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
+        if (coeffFormat != 0 && coeffFormat != 1) { set_error("%s: coefficient format %d (0 float64, 1 float32)", what, coeffFormat); return -1; }
+        if (coeffCols < 1 || coeffCols > (1 << 20) || col0 < 0 || col0 > coeffCols - order) {
+            set_error("%s: coefficients a_1 .. a_%d at columns %d .. %d of %d (1 .. 2^20)", what, order, col0, col0 + order - 1, coeffCols); return -1;
+        }
+        if (coeffStride < 0) { set_error("%s: coeffStride %lld", what, coeffStride); return -1; }
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
+        ExportSelection s;
+        std::vector<LpcResRow> rows;
+        long long stepsBefore = 0, mostSteps = 0;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) {
+                const long long L = in.len(u), steps = align_steps_below(L, hop, phase);
+                rows.push_back(LpcResRow{in.at(u), L, steps, tile_row_first(i, rowStride, before), tile_row_first(i, coeffStride, stepsBefore)});      // (the extent below refuses a stride that wraps)
+                stepsBefore += steps; mostSteps = std::max(mostSteps, steps);
+                return L;
+            }, in.sig)) return -1;
+        if (coeffStride > 0 && coeffStride < mostSteps) { set_error("%s: coeffStride %lld is below the largest step count (%lld)", what, coeffStride, mostSteps); return -1; }
+        // the coefficients' extent, by division before any product (as export_extent's): rows without steps read none
+        const long long coeffLimit = kExportLimit / coeffCols;
+        if (coeffStride > 0 && mostSteps > 0 && s.n > coeffLimit / coeffStride) {
+            set_error("%s: %lld rows of coeffStride %lld steps of %d coefficient columns (at most 2^50 elements)", what, s.n, coeffStride, coeffCols); return -1;
+        }
+        const long long coeffSteps = coeffStride > 0 ? (mostSteps > 0 ? s.n * coeffStride : 0) : stepsBefore;
+        if (coeffSteps > coeffLimit) { set_error("%s: %lld steps of %d coefficient columns (at most 2^50 elements)", what, coeffSteps, coeffCols); return -1; }
+        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut, &in);
+        if (elements <= 0) return elements;
+        const size_t elSize = format ? sizeof(float) : sizeof(int16_t), cSize = coeffFormat ? sizeof(float) : sizeof(double);
+        const size_t outBytes = (size_t)elements * elSize, coeffBytes = (size_t)coeffSteps * (size_t)coeffCols * cSize;
+        if (coeffBytes) {
+            if (!coeff) { set_error("%s: no coefficients", what); return -1; }
+            const std::string name = std::string(what) + ": coefficients";
+            if (!device_range(coeff, coeffBytes, b->device, cSize, name.c_str())) return -1;
+            const uintptr_t c = reinterpret_cast<uintptr_t>(coeff), o = reinterpret_cast<uintptr_t>(deviceOut);
+            if (c < o + outBytes && o < c + coeffBytes) {
+                set_error("%s: the output (%zu bytes from %p) overlaps the coefficients (%zu bytes from %p)", what, outBytes, deviceOut, coeffBytes, coeff); return -1;
+            }
+        }
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        std::vector<long long> words;
+        const TileTable tiles = tile_row_table(s.counts.data(), s.n, kLpcTile, rowStride, kTimelineChunkLog2, words);
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words);
+        ExportStage stage(b, st, block, nullptr, !in.sig, in.sig != nullptr);
+        if (stage.begin()) return -1;
+        LpcResArgs A;
+        A.in = in.data; A.rows = stage.device<LpcResRow>(rowsAt);
+        A.tile = tile_out(stage, wordsAt, tiles, rowStride, deviceOut);
+        A.coeff = coeff; A.hop = hop; A.phase = phase;
+        A.order = order; A.coeffCols = coeffCols; A.col0 = col0;
+        constexpr int R = kLpcResidual, Q = kLpcPrediction;
+        // [what][coefficient format][input format][output format]
+        void (*const kernels[2][2][2][2])(LpcResArgs) = {
+            {{{klatt_lpc_residual<R, false, int16_t, false>, klatt_lpc_residual<R, true, int16_t, false>}, {klatt_lpc_residual<R, false, float, false>, klatt_lpc_residual<R, true, float, false>}},
+             {{klatt_lpc_residual<R, false, int16_t, true>, klatt_lpc_residual<R, true, int16_t, true>}, {klatt_lpc_residual<R, false, float, true>, klatt_lpc_residual<R, true, float, true>}}},
+            {{{klatt_lpc_residual<Q, false, int16_t, false>, klatt_lpc_residual<Q, true, int16_t, false>}, {klatt_lpc_residual<Q, false, float, false>, klatt_lpc_residual<Q, true, float, false>}},
+             {{klatt_lpc_residual<Q, false, int16_t, true>, klatt_lpc_residual<Q, true, int16_t, true>}, {klatt_lpc_residual<Q, false, float, true>, klatt_lpc_residual<Q, true, float, true>}}}};
+        if (launch_tiles(stage, kernels[which][coeffFormat], in.format(), format, 8, A)) return -1;
+        return elements;
+    });
+}
+
+long long speechPlayer_batch_exportLpcResidual(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int order, long long hop, long long phase,
+                                               const void* deviceCoeff, int coeffFormat, int coeffCols, int col0, long long coeffStride, int what, void* deviceOut,
+                                               int format, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportLpcResidual")) return -1;
+    return lpc_residual_export("exportLpcResidual", batch, false, nullptr, utterances, nUtterances, order, hop, phase, deviceCoeff, coeffFormat, coeffCols, col0, coeffStride,
+                               what, deviceOut, format, rowStride, stream);
+}
+
+// The same of chosen rows of a caller's signal: it reads no pool and needs no synthesis (ExportStage, ofSignal).
+long long speechPlayer_batch_exportLpcResidualOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows, int order,
+                                                 long long hop, long long phase, const void* deviceCoeff, int coeffFormat, int coeffCols, int col0, long long coeffStride,
+                                                 int what, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportLpcResidualOf")) return -1;
+    return lpc_residual_export("exportLpcResidualOf", batch, true, signal, rows, nRows, order, hop, phase, deviceCoeff, coeffFormat, coeffCols, col0, coeffStride, what,
+                               deviceOut, format, rowStride, stream);
 }
 
 // ---- the PCM mixed with noise and other utterances (klatt_mix.h) ----------------------------------------------------------------------------

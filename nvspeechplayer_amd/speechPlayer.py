@@ -1155,6 +1155,168 @@ def codecTable(codec):
     return codecDecode(np.arange(256, dtype=np.uint8), codec)
 
 
+LPC_FIELDS = ["autocorr", "lpc", "reflection", "error", "stages"]      # bit 1 << i of `what` (include/speechPlayer_batch.h); the fields come in this order
+LPC_MAX_ORDER = 32               # kLpcMaxOrder of csrc/klatt_lpc.h
+LPC_MAX_WIN = 4096               # kLpcMaxWin
+LPC_TILE = 1024                  # kLpcTile: consecutive outputs of one row a workgroup of the residual kernel takes at a time
+LPC_WHAT = ["residual", "prediction"]
+
+
+def lpcColumns(fields, order):
+    """Where each of `fields` (names of LPC_FIELDS, any order) lies in a step's values: -> ({name: (first column, count)}, the total)."""
+    what = check_lpc_fields(fields, "lpcColumns")
+    at, col = {}, 0
+    for i, name in enumerate(LPC_FIELDS):
+        if what >> i & 1:
+            n = order + 1 if name == "autocorr" else order if name in ("lpc", "reflection") else 1
+            at[name] = (col, n)
+            col += n
+    return at, col
+
+
+def check_lpc_fields(fields, what="lpcTensor"):
+    """fields: a name of LPC_FIELDS or a non-empty sequence of them (KeyError for another, ValueError for none), or the bit set itself,
+    1 .. 31: -> the bit set."""
+    if isinstance(fields, (int, np.integer)) and not isinstance(fields, (bool, np.bool_)):
+        if not 1 <= int(fields) < 1 << len(LPC_FIELDS):
+            raise ValueError("%s: fields %d (a set of the bits 1 .. %d)" % (what, fields, 1 << len(LPC_FIELDS) - 1))
+        return int(fields)
+    names = [fields] if isinstance(fields, str) else list(fields)
+    bits = 0
+    for name in names:
+        if name not in LPC_FIELDS:
+            raise KeyError("%s: field %r (%s)" % (what, name, ", ".join(LPC_FIELDS)))
+        bits |= 1 << LPC_FIELDS.index(name)
+    if not bits:
+        raise ValueError("%s: no fields" % what)
+    return bits
+
+
+def _check_lpc_grid(hop, phase, what):
+    """hop an integer >= 1 and phase an integer >= 0 (ValueError; a float is refused, not truncated: 2.5 is no hop): -> (hop, phase)."""
+    for name, v, least in (("hop", hop, 1), ("phase", phase, 0)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < least:
+            raise ValueError("%s: %s must be an integer >= %d, not %r" % (what, name, least, v))
+    return int(hop), int(phase)
+
+
+def _check_order(order, what):
+    if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)) or not 1 <= order <= LPC_MAX_ORDER:
+        raise ValueError("%s: order must be an integer in 1 .. %d, not %r" % (what, LPC_MAX_ORDER, order))
+    return int(order)
+
+
+def check_lpc_request(order, nWin, hop, phase, window, lagWindow, fields, dtype, what="lpcTensor"):
+    """The argument checks of BatchPlayer.lpcTensor, pcmLpc and signalLpc that need no GPU: order in 1 .. 32, nWin an integer in
+    order + 1 .. 4096, hop >= 1, phase >= 0, `window` None (periodic Hann) or nWin finite values, `lagWindow` None or order + 1 finite
+    values, `fields` as check_lpc_fields', dtype None / torch.float32 / torch.float64.  Raises ValueError, KeyError or TypeError.
+    Returns (order, nWin, hop, phase, window as a float64 array or None, lagWindow likewise, the bit set, the values per step, the
+    export format: 0 float64, 1 float32)."""
+    order = _check_order(order, what)
+    if isinstance(nWin, (bool, np.bool_)) or not isinstance(nWin, (int, np.integer)) or not order < nWin <= LPC_MAX_WIN:
+        raise ValueError("%s: nWin must be an integer in order + 1 = %d .. %d, not %r" % (what, order + 1, LPC_MAX_WIN, nWin))
+    nWin = int(nWin)
+    hop, phase = _check_lpc_grid(hop, phase, what)
+    fmt = _check_dtype(what, dtype, *_float_types())
+    arrays = []
+    for name, a, n in (("window", window, nWin), ("lagWindow", lagWindow, order + 1)):
+        if a is not None:
+            a = np.ascontiguousarray(_host_array(a, np.float64).reshape(-1))
+            if len(a) != n:
+                raise ValueError("%s: the %s needs %d values, not %d" % (what, name, n, len(a)))
+            if not np.all(np.isfinite(a)):
+                raise ValueError("%s: every %s value must be finite" % (what, name))
+        arrays.append(a)
+    bits = check_lpc_fields(fields, what)
+    return order, nWin, hop, phase, arrays[0], arrays[1], bits, lpcColumns(bits, order)[1], fmt
+
+
+def _lpc_statement(what, s, inFormat, order, nWin, hop, phase, window, lagWindow, fields):
+    import torch
+    order, nWin, hop, phase, window, lagWindow, bits, cols, _ = check_lpc_request(order, nWin, hop, phase, window, lagWindow, fields, torch.float64, what)
+    return _row_statement(what, s, inFormat, (order, nWin, hop, phase, _ptr(window), _ptr(lagWindow), bits),
+                          (int(_step_counts(len(s), hop, phase)), cols), np.float64, counted=False)
+
+
+def pcmLpc(pcm, order=16, nWin=512, hop=256, phase=0, window=None, lagWindow=None, fields=("lpc", "error")):
+    """The linear-prediction analysis of int16 PCM on the host (speechPlayer_pcmLpc; no GPU): -> float64 [steps, values], by the
+    definition in include/speechPlayer_batch.h -- step j centred on sample phase + j * hop, zeros outside the signal, the
+    autocorrelation by exact binary64 products and one fixed tree, the Levinson-Durbin recursion in binary64.  Arguments as
+    BatchPlayer.lpcTensor's; lpcColumns(fields, order) says where each field lies."""
+    return _lpc_statement("pcmLpc", _pcm_samples(pcm, "pcmLpc"), None, order, nWin, hop, phase, window, lagWindow, fields)
+
+
+def signalLpc(x, order=16, nWin=512, hop=256, phase=0, window=None, lagWindow=None, fields=("lpc", "error")):
+    """pcmLpc on a signal's row (speechPlayer_signalLpc; no GPU): x as signalSpectrogram's.  The statement
+    BatchPlayer.lpcTensor(signal=...) is held to."""
+    return _lpc_statement("signalLpc", *_signal_samples(x, "signalLpc"), order, nWin, hop, phase, window, lagWindow, fields)
+
+
+def lpcFromAutocorrelation(r):
+    """The Levinson-Durbin recursion alone (speechPlayer_lpcFromAutocorrelation; no GPU) on r[0 .. order], order = len(r) - 1 in
+    1 .. 32: -> (a float64 [order]: a_1 .., k float64 [order]: the reflection coefficients, the error E, the stages done).  It stops
+    -- the later values +0 -- as soon as E is not positive and finite or a reflection coefficient is not below 1 in magnitude."""
+    r = np.ascontiguousarray(_host_array(r, np.float64).reshape(-1))
+    order = _check_order(len(r) - 1, "lpcFromAutocorrelation")
+    a, k, e, st = np.zeros(order), np.zeros(order), np.zeros(1), np.zeros(1, np.int32)
+    _answer(_native.load().speechPlayer_lpcFromAutocorrelation(r.ctypes.data, order, a.ctypes.data, k.ctypes.data, e.ctypes.data, st.ctypes.data), order)
+    return a, k, float(e[0]), int(st[0])
+
+
+def lagWindow(order, sampleRate, bandwidth=60.0, whiteNoise=2.0 ** -30):
+    """A lag window for lpcTensor / pcmLpc (numpy, no GPU): float64 [order + 1], the Gaussian exp(-0.5 (2 pi bandwidth k / sampleRate)^2)
+    with element 0 multiplied by 1 + whiteNoise (white-noise correction)."""
+    order = _check_order(order, "lagWindow")
+    if not sampleRate > 0 or not bandwidth >= 0 or not whiteNoise >= 0 or not all(math.isfinite(float(v)) for v in (sampleRate, bandwidth, whiteNoise)):
+        raise ValueError("lagWindow: sampleRate > 0, bandwidth >= 0, whiteNoise >= 0, all finite (%r, %r, %r)" % (sampleRate, bandwidth, whiteNoise))
+    w = np.exp(-0.5 * (2.0 * np.pi * float(bandwidth) * np.arange(order + 1, dtype=np.float64) / float(sampleRate)) ** 2)
+    w[0] *= 1.0 + float(whiteNoise)
+    return w
+
+
+def check_lpc_residual_request(order, hop, phase, column, what_, dtype, what="lpcResidualTensor"):
+    """The argument checks of BatchPlayer.lpcResidualTensor, pcmLpcResidual and signalLpcResidual that need no GPU: order in 1 .. 32,
+    hop >= 1, phase >= 0, column >= 0 (where a_1 lies in a step's values), what_ "residual" / "prediction" or 0 / 1, dtype None /
+    torch.float32 / np.float32 or torch.int16 / np.int16.  Raises ValueError, KeyError or TypeError.  Returns (order, hop, phase,
+    column, 0 residual or 1 prediction, the format of the samples: 0 int16, 1 float32)."""
+    order = _check_order(order, what)
+    hop, phase = _check_lpc_grid(hop, phase, what)
+    if isinstance(column, (bool, np.bool_)) or not isinstance(column, (int, np.integer)) or column < 0:
+        raise ValueError("%s: column must be an integer >= 0, not %r" % (what, column))
+    if isinstance(what_, str):
+        if what_ not in LPC_WHAT:
+            raise KeyError("%s: what %r (%s)" % (what, what_, ", ".join(LPC_WHAT)))
+        what_ = LPC_WHAT.index(what_)
+    elif isinstance(what_, (bool, np.bool_)) or not isinstance(what_, (int, np.integer)) or what_ not in (0, 1):
+        raise KeyError("%s: what %r (%s, or 0 / 1)" % (what, what_, ", ".join(LPC_WHAT)))
+    return order, hop, phase, int(column), int(what_), _sample_format(dtype, what)
+
+
+def _lpc_residual_statement(name, s, inFormat, coeff, hop, phase, what, dtype):
+    c = np.ascontiguousarray(_host_array(coeff, np.float64))
+    if c.ndim != 2:
+        raise ValueError("%s: the coefficients must be [steps, order], not %s" % (name, list(c.shape)))
+    order, hop, phase, _, which, fmt = check_lpc_residual_request(c.shape[1], hop, phase, 0, what, dtype, name)
+    steps = int(_step_counts(len(s), hop, phase))
+    if c.shape[0] != steps:
+        raise ValueError("%s: %d rows of coefficients for %d steps" % (name, c.shape[0], steps))
+    return _row_statement(name, s, inFormat, (order, hop, phase, c.ctypes.data if steps else None, which, fmt), (len(s),), np.float32 if fmt else np.int16)
+
+
+def pcmLpcResidual(pcm, coeff, hop=256, phase=0, what="residual", dtype=np.float32):
+    """int16 PCM through the inverse filter of its frames' coefficients on the host (speechPlayer_pcmLpcResidual; no GPU): coeff float64
+    [steps, order], a_1 .. a_order of every step of pcmLpc's grid for the same hop and phase; sample t takes the row of the nearest
+    centre (ties upward).  -> float32 or int16 [len(pcm)]: the residual e(t) = x(t) + sum a_m x(t - m), or (what "prediction")
+    p(t) = -sum a_m x(t - m), one binary64 fma chain per sample."""
+    return _lpc_residual_statement("pcmLpcResidual", _pcm_samples(pcm, "pcmLpcResidual"), None, coeff, hop, phase, what, dtype)
+
+
+def signalLpcResidual(x, coeff, hop=256, phase=0, what="residual", dtype=np.float32):
+    """pcmLpcResidual on a signal's row (speechPlayer_signalLpcResidual; no GPU): x as signalSpectrogram's.  The statement
+    BatchPlayer.lpcResidualTensor(signal=...) is held to."""
+    return _lpc_residual_statement("signalLpcResidual", *_signal_samples(x, "signalLpcResidual"), coeff, hop, phase, what, dtype)
+
+
 MIX_TILE = 1024                  # kMixTile of csrc/klatt_mix.h: consecutive outputs of one row a workgroup takes at a time
 MIX_MAX_TERMS = 64               # kMixMaxTerms: of one row
 MIX_MAX_CALL_TERMS = 1 << 22     # kMixMaxCallTerms: of one call
@@ -1729,6 +1891,70 @@ class BatchPlayer(object):
                                      torch.cuda.current_stream(self.device).cuda_stream))
             assert got == numel, (got, numel)
         return tuple(t for t in (d, c) if t is not None) + (torch.from_numpy(second),)
+
+    def lpcTensor(self, order=16, nWin=512, hop=256, phase=0, window=None, lagWindow=None, fields=("lpc", "error"), utterances=None, dtype=None,
+                  padded=True, signal=None):
+        """The linear-prediction analysis of the batch's PCM as a torch tensor on the batch's device (speechPlayer_batch_exportLpc), filled
+        on torch's current stream behind the synthesis without a host wait: -> (lpc, steps).  Step j of an utterance is centred on its
+        sample phase + j * hop -- the grid of spectrogramTensor and trackTensor, row for row -- over a frame of nWin samples (any
+        integer in order + 1 .. 4096), zeros outside the utterance.  window: nWin values (None: periodic Hann); lagWindow: order + 1
+        values that multiply the autocorrelation (None: none; lagWindow() designs one).  fields: names of LPC_FIELDS; a step's values
+        come in that list's order whatever the order asked for (lpcColumns): "autocorr" r[0 .. order], "lpc" a_1 .. a_order of
+        A(z) = 1 + sum a_j z^-j, "reflection" k_1 .. k_order, "error" E, "stages" the stages of the recursion that ran (order, unless the
+        frame is silent or not positive definite: the later values are +0).  utterances, dtype and padded as spectrogramTensor's.
+        The batch must have been synthesised since it was set; pcmLpc is the same definition on the host, which the device equals bit
+        for bit.
+        signal: the (tensor, lengths or offsets) pair another export returned (check_signal_request), read in place of the batch's PCM
+        (speechPlayer_batch_exportLpcOf): `utterances` then chooses rows of the signal, no synthesis is needed and signalLpc is the
+        host's statement."""
+        import torch
+        order, nWin, hop, phase, window, lagWindow, bits, cols, fmt = check_lpc_request(order, nWin, hop, phase, window, lagWindow, fields, dtype)
+        src = self._rows("lpcTensor", signal, utterances)
+        export = self._entry("Lpc", src)
+
+        def call(out, stride, numel, stream):
+            return export(order, nWin, hop, phase, _ptr(window), _ptr(lagWindow), bits, out, fmt, stride, stream)
+        return self._export_rows(_step_counts(src.lengths, hop, phase), (cols,), torch.float32 if fmt else torch.float64, padded, call)
+
+    def lpcResidualTensor(self, lpc, order=16, hop=256, phase=0, column=0, what="residual", utterances=None, dtype=None, padded=True, signal=None):
+        """The batch's PCM through the inverse filter of its own frames' prediction coefficients as a torch tensor on the batch's device
+        (speechPlayer_batch_exportLpcResidual): -> (pcm, lengths).  lpc: a torch.float64 or torch.float32 tensor on the batch's device,
+        [n, most steps, values] (padded) or [total steps, values] (packed) for the rows chosen here and the same hop and phase -- what
+        lpcTensor returned, or the caller's own coefficients --, a_1 .. a_order at columns column .. column + order - 1
+        (lpcColumns(fields, order)["lpc"][0]); it is read on torch's current stream.  Sample t takes the coefficients of the nearest
+        step's centre, ties upward.  what: "residual", e(t) = x(t) + sum a_m x(t - m), or "prediction", p(t) = -sum a_m x(t - m).
+        utterances, padded and the (pcm, lengths) pair as pcmTensor's; dtype torch.float32 (default) or torch.int16 (clipped, rounded
+        to nearest even).  pcmLpcResidual is the same definition on the host, which the device equals bit for bit.  The result feeds
+        the next stage as its signal=.
+        signal: as lpcTensor's (speechPlayer_batch_exportLpcResidualOf; signalLpcResidual is the host's statement)."""
+        import torch
+        order, hop, phase, column, which, fmt = check_lpc_residual_request(order, hop, phase, column, what, dtype)
+        src = self._rows("lpcResidualTensor", signal, utterances)
+        export = self._entry("LpcResidual", src)
+        steps = _step_counts(src.lengths, hop, phase)
+        if not isinstance(lpc, torch.Tensor) or lpc.dtype not in (torch.float32, torch.float64) or lpc.dim() not in (2, 3) or not lpc.is_contiguous():
+            raise TypeError("lpcResidualTensor: the coefficients must be a contiguous torch.float32 or torch.float64 tensor, [rows, steps, values] or [steps, values]")
+        if not lpc.is_cuda or lpc.device.index != self.device:
+            raise ValueError("lpcResidualTensor: the coefficients must be on the batch's device, cuda:%d, not %s" % (self.device, lpc.device))
+        cols = int(lpc.shape[-1])
+        if column + order > cols:
+            raise ValueError("lpcResidualTensor: a_1 .. a_%d at columns %d .. %d of %d" % (order, column, column + order - 1, cols))
+        most = int(steps.max()) if len(steps) else 0
+        if lpc.dim() == 3:
+            if lpc.shape[0] != src.n or lpc.shape[1] < most:
+                raise ValueError("lpcResidualTensor: coefficients %s for %d rows of at most %d steps" % (list(lpc.shape), src.n, most))
+            cstride = int(lpc.shape[1])
+            if cstride == 0:      # (no row has a step: nothing is read)
+                cstride = 1
+        else:
+            if lpc.shape[0] < int(steps.sum()):
+                raise ValueError("lpcResidualTensor: coefficients %s for %d steps" % (list(lpc.shape), int(steps.sum())))
+            cstride = 0
+
+        def call(out, stride, numel, stream):
+            return export(order, hop, phase, lpc.data_ptr() if lpc.numel() else None, 1 if lpc.dtype == torch.float32 else 0, cols, column, cstride, which, out, fmt,
+                          stride, stream)
+        return self._export_rows(src.lengths, (), torch.float32 if fmt else torch.int16, padded, call)
 
     def setNoiseBank(self, clips):
         """The batch's noise bank (speechPlayer_batch_setNoiseBank): a list of one-dimensional float arrays (kept as float32), every value
