@@ -652,7 +652,7 @@ long long speechPlayer_pcmMix(const sample* pcm, long long length, float speechG
  * whose allocation is smaller than the rows need (a signal whose rows are all empty is not read and may have no data); a row number
  * outside the signal; an output that overlaps the signal; srcRate <= 0.  The message names the row.
  * Limits      A row has at most 2^44 samples, a signal 2^60 elements, an output 2^50; tests/test_gpu_far_offsets.py (and
- *             tests/test_gpu_lpc.py for the linear-prediction exports) runs every export past elements 2^31 and 2^32 of its output and
+ *             tests/test_gpu_lpc.py and tests/test_gpu_tempo.py for the linear-prediction and tempo exports) runs every export past elements 2^31 and 2^32 of its output and
  *             of a signal, and past sample 2^31 of the pool (docs/KERNELS.md 4.22).
  * Out of scope: in a mix onto a signal, a term from a different signal or from the pool; live handles; NodePlayer beyond
  * speechPlayer_node_part; active-speech levels and loudness weighting; a fused kernel for the chain; float64 or float16 signals; label
@@ -960,6 +960,78 @@ long long speechPlayer_batch_exportLpcResidual(speechPlayer_batch_t batch, const
 long long speechPlayer_batch_exportLpcResidualOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
 	int order, long long hop, long long phase, const void* deviceCoeff, int coeffFormat, int coeffCols, int col0, long long coeffStride, int what,
 	void* deviceOut, int format, long long rowStride, void* stream);
+/*
+ * Tempo perturbation of a batch's PCM, or of a signal's rows, by waveform-similarity overlap-add (WSOLA): the duration changes, the pitch
+ * and the formants stay.  Beside the samples the export gives its time map, the input sample every output frame was taken from.  A row
+ * of L samples is read as the other exports of the PCM read it: an int16 s is (float)s / 32767.0f, a float32 is taken as it is, a sample
+ * outside 0 .. L-1 is +0 and nothing is loaded there.
+ *   per call  nWin = N, even, 64 .. 2048 (kTempoMaxWin); Hs = N / 2.  search = D, 0 .. 1024 (kTempoMaxSearch)
+ *   per OUTPUT row   tempo, a finite double in [0.25, 4]; a tempo above 1 gives a shorter output
+ *   lengths   (host only) Lout = (long long)ceil((double)L / tempo), one binary64 division; Lout = 0 for L = 0.  K = ceil(Lout / Hs) + 1
+ *             frames when Lout > 0, else 0
+ *   window    w[i] is the float32 of 0.5 - 0.5 cos(2 pi i / N), i = 0 .. N-1, evaluated in binary64 on the host
+ *   positions p[k], k = 0 .. K-1, 64-bit integers: p[k] is the input sample placed at output k * Hs; p[0] = 0.  For k >= 1:
+ *             a = (long long)floor((double)(k * Hs) * tempo), one binary64 product; the template is T[i] = x(p[k-1] + i), the natural
+ *             continuation of the previous segment; the candidate at lag d is C_d[i] = x(a - Hs + d + i), i = 0 .. N-1, d = -D .. D
+ *   score     term(i) = (double)T[i] * (double)C_d[i], exact in binary64 (fusing it into an FMA changes no bit); four chains c_j,
+ *             j = 0 .. 3, each the sum from +0.0, in ascending i, of term(i) over i mod 4 == j; score(d) = (c_0 + c_1) + (c_2 + c_3).  A
+ *             chain that starts from +0.0 is never -0.0, so terms with a zero factor may be skipped
+ *   choice    p[k] = a + d*, d* of the greatest score compared as binary64 values, ties to the lowest rank(d) = 2|d| - (d < 0 ? 1 : 0):
+ *             0, -1, +1, -2, +2, ...  A silent or constant stretch therefore takes d = 0.  Inputs inside the signal bound (finite,
+ *             magnitude at most 2^16) give finite scores; outside it the bits are unspecified
+ *   render    for output m = 0 .. Lout-1: q = m / Hs, i = m - q * Hs,
+ *                 y(m) = fmaf(w[Hs + i], x(P[q] + i), w[i] * x(P[q+1] - Hs + i)) + 0.0f
+ *             each operation one correctly rounded binary32 operation; P[k] = min(max(p[k], -2^45), 2^45), so the positions may be the
+ *             caller's own, of any value: a position steers an address only behind the row's mask, nothing outside the row is loaded
+ *   output    Lout samples per row; format 1 float32, format 0 int16 by the resampler's conversion; padded or packed as the resampled
+ *             export is, so (tensor, lengths) is a signal for the next stage
+ * The definition is the function bodies of csrc/klatt_tempo.h, which the host and the device compile from one source.  Over the pool the
+ * result is a function of the batch's PCM: it depends on the mode and needs a synthesis launch.
+ * Limits      as the signal contract's (above); tests/test_gpu_tempo.py runs the render past elements 2^31 and 2^32 of its output.
+ * Out of scope: normalised cross-correlation; custom windows or hops other than N / 2; phase-vocoder and PSOLA methods; pitch shifting (this
+ * export followed by the resampler does it); warping the label grids on the device; live handles; NodePlayer beyond
+ * speechPlayer_node_part; filling the chip with few rows (a row's frames are sequential, as a filter's samples are).
+ *
+ * Host only, touch no device: Lout and K of a row of `length` samples.  -1 on length < 0 or above 2^44, a tempo that is not finite or
+ * outside [0.25, 4], and (tempoFrames) nWin odd or outside 64 .. 2048. */
+long long speechPlayer_tempoLength(long long length, double tempo);
+long long speechPlayer_tempoFrames(long long length, double tempo, int nWin);
+/* Host only: the definition above on `length` samples of plain PCM (speechPlayer_pcmTempo) or of a signal's row, int16 (inFormat 0) or
+ * float32 (inFormat 1) (speechPlayer_signalTempo) -- the statements the device is held to bit for bit.  positionsIn NULL: the search runs
+ * and positionsOut (may be NULL) receives the K positions; else positionsIn[K] is rendered (search is not looked at) and copied to
+ * positionsOut.  out is float[Lout] (format 1) or int16[Lout] (format 0) of `capacity` elements; a NULL out only sizes, and still fills
+ * positionsOut.  Return Lout; -1 on an unknown inFormat, a NULL input with length > 0, the refusals of tempoLength, an unknown format,
+ * nWin odd or outside 64 .. 2048, search outside 0 .. 1024, a capacity below Lout, and (signalTempo) a float32 sample that is not finite
+ * or above 2^16 in magnitude. */
+long long speechPlayer_pcmTempo(const sample* pcm, long long length, double tempo, int nWin, int search, const long long* positionsIn,
+	long long* positionsOut, int format, void* out, long long capacity);
+long long speechPlayer_signalTempo(const void* x, int inFormat, long long length, double tempo, int nWin, int search, const long long* positionsIn,
+	long long* positionsOut, int format, void* out, long long capacity);
+/* The positions of chosen utterances (exportTempoPositions) or of chosen rows of `signal` (exportTempoPositionsOf): int64 [row][K] into
+ * caller-owned device memory on the caller's stream.  tempo is a HOST array, one double per OUTPUT row.  rowStride is in frames (0: the
+ * rows back to back); past a row's K the value is 0.  utterances / rows (any order, repeats allowed -- one utterance at several tempos --,
+ * NULL: all), the return value (elements written; 0 writes nothing and needs no buffer), the device-memory, alignment and overlap checks,
+ * the ordering by events, the sixteen-in-flight rule and the signal contract are those of speechPlayer_batch_exportResampled /
+ * exportResampledOf.  One 256-lane workgroup per row, rows longest first (csrc/klatt_tempo.h).  Nothing is kept on the batch.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: what exportResampled / exportResampledOf refuse of the batch, the signal,
+ * the selection, rowStride and the output; nWin odd or outside 64 .. 2048; search outside 0 .. 1024; a NULL tempo, or one that is not
+ * finite or lies outside [0.25, 4] (the message names the row). */
+long long speechPlayer_batch_exportTempoPositions(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const double* tempo,
+	int nWin, int search, long long* devicePositions, long long rowStride, void* stream);
+long long speechPlayer_batch_exportTempoPositionsOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	const double* tempo, int nWin, int search, long long* devicePositions, long long rowStride, void* stream);
+/* The chosen rows rendered from devicePositions, a DEVICE tensor [row][K] of int64: what exportTempoPositions wrote for the same rows,
+ * tempo and nWin, or the caller's own.  posStride is in frames: 0 packed, otherwise padded; row i of the tensor belongs to the i-th chosen
+ * row.  Formats and rowStride (in samples) are speechPlayer_batch_exportResampled's, and so are the selection, the return value, the
+ * checks of the output and the signal, the ordering by events and the sixteen-in-flight rule; the caller orders whatever wrote the
+ * positions before the export on `stream`.  Tile-wise, a 256-lane workgroup per kTempoTile = 1024 outputs of a row.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: what exportResampled / exportResampledOf refuse; nWin odd or outside
+ * 64 .. 2048; a NULL tempo, or one that is not finite or lies outside [0.25, 4]; a posStride below the largest K; a positions tensor that
+ * is not device memory of the batch's device, misaligned to 8 bytes or too small; an output that overlaps the positions or the signal. */
+long long speechPlayer_batch_exportTempo(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const double* tempo, int nWin,
+	const long long* devicePositions, long long posStride, void* deviceOut, int format, long long rowStride, void* stream);
+long long speechPlayer_batch_exportTempoOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	const double* tempo, int nWin, const long long* devicePositions, long long posStride, void* deviceOut, int format, long long rowStride, void* stream);
 /* The HIP device the batch is bound to (-1: no batch). */
 int speechPlayer_batch_device(speechPlayer_batch_t batch);
 

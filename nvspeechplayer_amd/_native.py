@@ -73,6 +73,8 @@ EXPORTS = [
     "speechPlayer_pcmCode", "speechPlayer_signalCode", "speechPlayer_codecDecode", "speechPlayer_batch_exportCoded", "speechPlayer_batch_exportCodedOf",
     "speechPlayer_lpcFromAutocorrelation", "speechPlayer_pcmLpc", "speechPlayer_signalLpc", "speechPlayer_pcmLpcResidual", "speechPlayer_signalLpcResidual",
     "speechPlayer_batch_exportLpc", "speechPlayer_batch_exportLpcOf", "speechPlayer_batch_exportLpcResidual", "speechPlayer_batch_exportLpcResidualOf",
+    "speechPlayer_tempoLength", "speechPlayer_tempoFrames", "speechPlayer_pcmTempo", "speechPlayer_signalTempo",
+    "speechPlayer_batch_exportTempoPositions", "speechPlayer_batch_exportTempoPositionsOf", "speechPlayer_batch_exportTempo", "speechPlayer_batch_exportTempoOf",
 ]
 
 
@@ -461,6 +463,22 @@ def load():
     L.speechPlayer_batch_exportLpcResidual.argtypes = [vp, vp, i64, i32, i64, i64, vp, i32, i32, i32, i64, i32, vp, i32, i64, vp]
     L.speechPlayer_batch_exportLpcResidualOf.restype = i64
     L.speechPlayer_batch_exportLpcResidualOf.argtypes = [vp, vp, vp, i64, i32, i64, i64, vp, i32, i32, i32, i64, i32, vp, i32, i64, vp]
+    L.speechPlayer_tempoLength.restype = i64
+    L.speechPlayer_tempoLength.argtypes = [i64, f64]
+    L.speechPlayer_tempoFrames.restype = i64
+    L.speechPlayer_tempoFrames.argtypes = [i64, f64, i32]
+    L.speechPlayer_pcmTempo.restype = i64
+    L.speechPlayer_pcmTempo.argtypes = [vp, i64, f64, i32, i32, vp, vp, i32, vp, i64]
+    L.speechPlayer_signalTempo.restype = i64
+    L.speechPlayer_signalTempo.argtypes = [vp, i32, i64, f64, i32, i32, vp, vp, i32, vp, i64]
+    L.speechPlayer_batch_exportTempoPositions.restype = i64
+    L.speechPlayer_batch_exportTempoPositions.argtypes = [vp, vp, i64, vp, i32, i32, vp, i64, vp]
+    L.speechPlayer_batch_exportTempoPositionsOf.restype = i64
+    L.speechPlayer_batch_exportTempoPositionsOf.argtypes = [vp, vp, vp, i64, vp, i32, i32, vp, i64, vp]
+    L.speechPlayer_batch_exportTempo.restype = i64
+    L.speechPlayer_batch_exportTempo.argtypes = [vp, vp, i64, vp, i32, vp, i64, vp, i32, i64, vp]
+    L.speechPlayer_batch_exportTempoOf.restype = i64
+    L.speechPlayer_batch_exportTempoOf.argtypes = [vp, vp, vp, i64, vp, i32, vp, i64, vp, i32, i64, vp]
     L.speechPlayer_batch_exportPowerOf.restype = i64
     L.speechPlayer_batch_exportPowerOf.argtypes = [vp, vp, vp, i64, vp, vp]
     L.speechPlayer_batch_exportMixedOf.restype = i64

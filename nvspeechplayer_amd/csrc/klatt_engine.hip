@@ -26,6 +26,7 @@
 #include "klatt_filter.h"
 #include "klatt_codec.h"
 #include "klatt_lpc.h"
+#include "klatt_tempo.h"
 #include "klatt_mix.h"
 #include "klatt_export.h"
 #include "klatt_batchplan.h"
@@ -6134,6 +6135,219 @@ long long speechPlayer_batch_exportLpcResidualOf(speechPlayer_batch_t batch, con
     if (refuse_timing_only("speechPlayer_batch_exportLpcResidualOf")) return -1;
     return lpc_residual_export("exportLpcResidualOf", batch, true, signal, rows, nRows, order, hop, phase, deviceCoeff, coeffFormat, coeffCols, col0, coeffStride, what,
                                deviceOut, format, rowStride, stream);
+}
+
+// ---- the PCM at another tempo by WSOLA (klatt_tempo.h) ----------------------------------------------------------------------------------------
+// Host only, touch no device: the definition of include/speechPlayer_batch.h through the functions the kernels are compiled from.
+static int tempo_length_request(const char* what, long long length, double tempo)
+{
+    if (length < 0 || length > kResampleMaxLength) { set_error("%s: length %lld (0 .. 2^44)", what, length); return -1; }
+    if (!tempo_valid(tempo)) { set_error("%s: tempo %g (finite, 0.25 .. 4)", what, tempo); return -1; }
+    return 0;
+}
+
+long long speechPlayer_tempoLength(long long length, double tempo)
+{
+    begin_call();
+    if (tempo_length_request("tempoLength", length, tempo)) return -1;
+    return tempo_out_length(length, tempo);
+}
+
+long long speechPlayer_tempoFrames(long long length, double tempo, int nWin)
+{
+    begin_call();
+    if (tempo_length_request("tempoFrames", length, tempo)) return -1;
+    TempoPlan P;
+    std::string why;
+    if (!tempo_plan(P, nWin, 0, false, why)) { set_error("tempoFrames: %s", why.c_str()); return -1; }
+    return tempo_frames(tempo_out_length(length, tempo), P.Hs);
+}
+
+static long long tempo_statement(const char* what, const void* x, int inFormat, long long length, double tempo, int nWin, int search, const long long* positionsIn,
+                                 long long* positionsOut, int format, void* out, long long capacity)
+{
+    if (signal_host_format(what, inFormat)) return -1;
+    if (length > 0 && !x) { set_error("%s: length %lld without samples", what, length); return -1; }
+    if (tempo_length_request(what, length, tempo)) return -1;
+    if (format != 0 && format != 1) { set_error("%s: format %d (0 int16, 1 float32)", what, format); return -1; }
+    try {
+        TempoPlan P;
+        std::string why;
+        if (!tempo_plan(P, nWin, search, positionsIn == nullptr, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        const long long Lout = tempo_out_length(length, tempo), K = tempo_frames(Lout, P.Hs);
+        if (out && capacity < Lout) { set_error("%s: the output takes %lld elements, capacity is %lld", what, Lout, capacity); return -1; }
+        if (signal_host_values(what, x, inFormat, length)) return -1;
+        std::vector<long long> own;
+        const long long* p = positionsIn;
+        if (!p && (out || positionsOut)) {
+            own.resize((size_t)K);
+            if (inFormat) tempo_positions_host(static_cast<const float*>(x), length, P, tempo, K, own.data());
+            else tempo_positions_host(static_cast<const int16_t*>(x), length, P, tempo, K, own.data());
+            p = own.data();
+        }
+        for (long long k = 0; positionsOut && k < K; ++k) positionsOut[k] = p[k];
+        if (out) {
+            if (inFormat) tempo_render_host(static_cast<const float*>(x), length, P, Lout, p, format, out);
+            else tempo_render_host(static_cast<const int16_t*>(x), length, P, Lout, p, format, out);
+        }
+        return Lout;
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
+long long speechPlayer_pcmTempo(const sample* pcm, long long length, double tempo, int nWin, int search, const long long* positionsIn, long long* positionsOut,
+                                int format, void* out, long long capacity)
+{
+    begin_call();
+    return tempo_statement("pcmTempo", pcm, 0, length, tempo, nWin, search, positionsIn, positionsOut, format, out, capacity);
+}
+
+long long speechPlayer_signalTempo(const void* x, int inFormat, long long length, double tempo, int nWin, int search, const long long* positionsIn,
+                                   long long* positionsOut, int format, void* out, long long capacity)
+{
+    begin_call();
+    return tempo_statement("signalTempo", x, inFormat, length, tempo, nWin, search, positionsIn, positionsOut, format, out, capacity);
+}
+
+// A row of either tempo export carries its output length and its frames by its own tempo (TempoRow); the export counts frames (the
+// positions) or outputs (the render)
+static_assert(sizeof(TempoRow) % 8 == 0, "rows are arrays of 8-byte words");
+constexpr ExportNouns kFrameNouns{"largest frame count", "frames", nullptr};
+
+// The positions of chosen rows, one workgroup per row, longest first (klatt_tempo.h).  The host path is the other exports': it reads the pool,
+// so it is ordered as speechPlayer_batch_exportPcm is (ExportStage, ofPcm).  The staging block: rows | the order.  Nothing is kept on the batch.
+static long long tempo_positions_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances,
+                                        long long nUtterances, const double* tempo, int nWin, int search, long long* devicePositions, long long rowStride, void* stream)
+{
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (rowStride < 0) { set_error("%s: rowStride %lld", what, rowStride); return -1; }
+        TempoPlan P;
+        std::string why;
+        if (!tempo_plan(P, nWin, search, true, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
+        ExportSelection s;
+        std::vector<TempoRow> rows;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) -> long long {
+                if (!tempo_of_row(tempo, i, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+                const long long L = in.len(u), Lout = tempo_out_length(L, tempo[i]), K = tempo_frames(Lout, P.Hs);
+                rows.push_back(TempoRow{in.at(u), L, Lout, 0, tile_row_first(i, rowStride, before), K, tempo[i]});
+                return K;
+            }, in.sig)) return -1;
+        const long long elements = export_elements(what, kFrameNouns, s, rowStride, 1);
+        if (elements <= 0) return elements;
+        if (!in.sig && export_synthesised(b, what)) return -1;
+        if (export_output(b, what, devicePositions, elements, sizeof(long long)) || signal_memory(in, what, devicePositions, (size_t)elements * sizeof(long long))) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+
+        std::vector<long long> order((size_t)s.n);
+        for (long long i = 0; i < s.n; ++i) order[(size_t)i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](long long a, long long c) { return rows[(size_t)a].frames > rows[(size_t)c].frames; });
+        StageBlock block;
+        const int rowsAt = block.add(rows), orderAt = block.add(order);
+        ExportStage stage(b, st, block, nullptr, !in.sig, in.sig != nullptr);
+        if (stage.begin()) return -1;
+        TempoSearchArgs A;
+        A.in = in.data; A.rows = stage.device<TempoRow>(rowsAt); A.order = stage.device<long long>(orderAt);
+        A.nRows = s.n; A.rowStride = rowStride; A.nWin = P.nWin; A.search = P.search; A.pos = devicePositions;
+        const unsigned grid = (unsigned)std::min<long long>(s.n, 64ll * b->cus);
+        hipLaunchKernelGGL(in.format() ? klatt_tempo_search<float> : klatt_tempo_search<int16_t>, dim3(grid), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
+}
+
+long long speechPlayer_batch_exportTempoPositions(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const double* tempo, int nWin,
+                                                  int search, long long* devicePositions, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportTempoPositions")) return -1;
+    return tempo_positions_export("exportTempoPositions", batch, false, nullptr, utterances, nUtterances, tempo, nWin, search, devicePositions, rowStride, stream);
+}
+
+// The same of chosen rows of a caller's signal: it reads no pool and needs no synthesis (ExportStage, ofSignal).
+long long speechPlayer_batch_exportTempoPositionsOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+                                                    const double* tempo, int nWin, int search, long long* devicePositions, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportTempoPositionsOf")) return -1;
+    return tempo_positions_export("exportTempoPositionsOf", batch, true, signal, rows, nRows, tempo, nWin, search, devicePositions, rowStride, stream);
+}
+
+// The chosen rows rendered from positions in device memory, tile-wise (klatt_tempo.h).  The host path is the tile-wise exports'; the positions
+// are a device tensor [row][frame] of int64, checked as lpc_residual_export checks its coefficients.  The staging block: rows | tile starts and
+// chunk rows (packed) | the window.  Nothing is kept on the batch.
+static long long tempo_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances,
+                              long long nUtterances, const double* tempo, int nWin, const long long* devicePositions, long long posStride, void* deviceOut, int format,
+                              long long rowStride, void* stream)
+{
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (tile_request(what, format, rowStride)) return -1;
+        TempoPlan P;
+        std::string why;
+        if (!tempo_plan(P, nWin, 0, false, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        if (posStride < 0) { set_error("%s: posStride %lld", what, posStride); return -1; }
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
+        ExportSelection s;
+        std::vector<TempoRow> rows;
+        long long framesBefore = 0, mostFrames = 0;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) -> long long {
+                if (!tempo_of_row(tempo, i, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+                const long long L = in.len(u), Lout = tempo_out_length(L, tempo[i]), K = tempo_frames(Lout, P.Hs);
+                rows.push_back(TempoRow{in.at(u), L, Lout, tile_row_first(i, rowStride, before), tile_row_first(i, posStride, framesBefore), K, tempo[i]});      // (the extent below refuses a stride that wraps)
+                framesBefore += K; mostFrames = std::max(mostFrames, K);
+                return Lout;
+            }, in.sig)) return -1;
+        if (posStride > 0 && posStride < mostFrames) { set_error("%s: posStride %lld is below the largest frame count (%lld)", what, posStride, mostFrames); return -1; }
+        if (posStride > 0 && mostFrames > 0 && s.n > kExportLimit / posStride) {
+            set_error("%s: %lld rows of posStride %lld frames (at most 2^50 elements)", what, s.n, posStride); return -1;
+        }
+        const long long posFrames = posStride > 0 ? (mostFrames > 0 ? s.n * posStride : 0) : framesBefore;
+        if (posFrames > kExportLimit) { set_error("%s: %lld frames of positions (at most 2^50 elements)", what, posFrames); return -1; }
+        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut, &in);
+        if (elements <= 0) return elements;
+        const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
+        const size_t outBytes = (size_t)elements * elSize, posBytes = (size_t)posFrames * sizeof(long long);
+        if (posBytes) {
+            if (!devicePositions) { set_error("%s: no positions", what); return -1; }
+            const std::string name = std::string(what) + ": positions";
+            if (!device_range(devicePositions, posBytes, b->device, sizeof(long long), name.c_str())) return -1;
+            const uintptr_t c = reinterpret_cast<uintptr_t>(devicePositions), o = reinterpret_cast<uintptr_t>(deviceOut);
+            if (c < o + outBytes && o < c + posBytes) {
+                set_error("%s: the output (%zu bytes from %p) overlaps the positions (%zu bytes from %p)", what, outBytes, deviceOut, posBytes, (const void*)devicePositions); return -1;
+            }
+        }
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        std::vector<long long> words;
+        const TileTable tiles = tile_row_table(s.counts.data(), s.n, kTempoTile, rowStride, kTimelineChunkLog2, words);
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words), windowAt = block.add(P.window);
+        ExportStage stage(b, st, block, nullptr, !in.sig, in.sig != nullptr);
+        if (stage.begin()) return -1;
+        TempoArgs A;
+        A.in = in.data; A.rows = stage.device<TempoRow>(rowsAt);
+        A.tile = tile_out(stage, wordsAt, tiles, rowStride, deviceOut);
+        A.pos = devicePositions; A.window = stage.device<float>(windowAt); A.nWin = P.nWin;
+        void (*const kernels[2][2])(TempoArgs) = {{klatt_tempo_render<false, int16_t>, klatt_tempo_render<true, int16_t>}, {klatt_tempo_render<false, float>, klatt_tempo_render<true, float>}};
+        if (launch_tiles(stage, kernels, in.format(), format, 8, A)) return -1;
+        return elements;
+    });
+}
+
+long long speechPlayer_batch_exportTempo(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, const double* tempo, int nWin,
+                                         const long long* devicePositions, long long posStride, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportTempo")) return -1;
+    return tempo_export("exportTempo", batch, false, nullptr, utterances, nUtterances, tempo, nWin, devicePositions, posStride, deviceOut, format, rowStride, stream);
+}
+
+// The same of chosen rows of a caller's signal: it reads no pool and needs no synthesis (ExportStage, ofSignal).
+long long speechPlayer_batch_exportTempoOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows, const double* tempo,
+                                           int nWin, const long long* devicePositions, long long posStride, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportTempoOf")) return -1;
+    return tempo_export("exportTempoOf", batch, true, signal, rows, nRows, tempo, nWin, devicePositions, posStride, deviceOut, format, rowStride, stream);
 }
 
 // ---- the PCM mixed with noise and other utterances (klatt_mix.h) ----------------------------------------------------------------------------

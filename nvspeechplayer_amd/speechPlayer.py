@@ -1317,6 +1317,111 @@ def signalLpcResidual(x, coeff, hop=256, phase=0, what="residual", dtype=np.floa
     return _lpc_residual_statement("signalLpcResidual", *_signal_samples(x, "signalLpcResidual"), coeff, hop, phase, what, dtype)
 
 
+TEMPO_MIN_WIN = 64               # kTempoMinWin of csrc/klatt_tempo.h
+TEMPO_MAX_WIN = 2048             # kTempoMaxWin
+TEMPO_MAX_SEARCH = 1024          # kTempoMaxSearch
+TEMPO_TILE = 1024                # kTempoTile: consecutive outputs of one row a workgroup of the render takes at a time
+TEMPO_RANGE = (0.25, 4.0)
+
+
+def check_tempo_request(tempo, nWin, search, dtype, rows=None, what="tempoTensor"):
+    """The argument checks of BatchPlayer.tempoTensor, tempoPositionsTensor, pcmTempo and signalTempo that need no GPU: tempo a finite number
+    in 0.25 .. 4 -- or, with `rows` given, one per row (a scalar stands for all of them) --, nWin an even integer in 64 .. 2048, search
+    an integer in 0 .. 1024, dtype None / float32 or int16 (torch's or numpy's).  Raises ValueError or TypeError; the message names the
+    row.  Returns (tempo as a float -- with `rows`: a float64 array [rows] --, nWin, search, the format of the samples: 0 int16,
+    1 float32)."""
+    if isinstance(nWin, (bool, np.bool_)) or not isinstance(nWin, (int, np.integer)) or not TEMPO_MIN_WIN <= nWin <= TEMPO_MAX_WIN or nWin % 2:
+        raise ValueError("%s: nWin must be an even integer in %d .. %d, not %r" % (what, TEMPO_MIN_WIN, TEMPO_MAX_WIN, nWin))
+    if isinstance(search, (bool, np.bool_)) or not isinstance(search, (int, np.integer)) or not 0 <= search <= TEMPO_MAX_SEARCH:
+        raise ValueError("%s: search must be an integer in 0 .. %d, not %r" % (what, TEMPO_MAX_SEARCH, search))
+    fmt = _sample_format(dtype, what)
+    try:
+        t = np.array(_as_array(tempo), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("%s: tempo must be a number%s, not %r" % (what, "" if rows is None else " or one per row", tempo))
+    if rows is None:
+        if t.ndim != 0:
+            raise ValueError("%s: tempo must be one number, not %s values" % (what, list(t.shape)))
+        t = t.reshape(1)
+    elif t.ndim == 0:
+        t = np.full(rows, float(t), np.float64)
+    elif t.ndim != 1 or len(t) != rows:
+        raise ValueError("%s: tempo must be a number or one per row (%d), not %s values" % (what, rows, list(t.shape)))
+    bad = np.flatnonzero(~(np.isfinite(t) & (t >= TEMPO_RANGE[0]) & (t <= TEMPO_RANGE[1])))
+    if len(bad):
+        raise ValueError("%s: the tempo of row %d is %r (finite, %g .. %g)" % (what, bad[0], float(t[bad[0]]), TEMPO_RANGE[0], TEMPO_RANGE[1]))
+    return (float(t[0]) if rows is None else np.ascontiguousarray(t)), int(nWin), int(search), fmt
+
+
+def _tempo_lengths(lens, tempo):
+    """Lout = ceil(L / tempo), one binary64 division, of each length (speechPlayer_tempoLength's value): int64."""
+    lens = np.asarray(lens, dtype=np.int64)
+    return np.where(lens > 0, np.ceil(lens.astype(np.float64) / tempo), 0).astype(np.int64)
+
+
+def _tempo_frames(outLens, nWin):
+    """K = ceil(Lout / Hs) + 1, or 0 for Lout = 0 (speechPlayer_tempoFrames' value): int64."""
+    outLens, hs = np.asarray(outLens, dtype=np.int64), nWin // 2
+    return np.where(outLens > 0, (outLens + hs - 1) // hs + 1, 0).astype(np.int64)
+
+
+def tempoLength(length, tempo):
+    """The samples a row of `length` samples has at `tempo` (speechPlayer_tempoLength; no GPU): ceil(length / tempo)."""
+    return int(_answer(_native.load().speechPlayer_tempoLength(int(length), float(tempo)), error=ValueError))
+
+
+def tempoFrames(length, tempo, nWin=512):
+    """The frames -- positions -- of a row of `length` samples at `tempo` (speechPlayer_tempoFrames; no GPU): ceil(Lout / (nWin / 2)) + 1,
+    0 for an empty row."""
+    return int(_answer(_native.load().speechPlayer_tempoFrames(int(length), float(tempo), int(nWin)), error=ValueError))
+
+
+def _tempo_statement(what, s, inFormat, tempo, nWin, search, positions, dtype, returnPositions):
+    tempo, nWin, search, fmt = check_tempo_request(tempo, nWin, search, dtype, None, what)
+    Lout = int(_tempo_lengths(len(s), tempo))
+    K = int(_tempo_frames(Lout, nWin))
+    given = None
+    if positions is not None:
+        given = np.ascontiguousarray(_host_array(positions, np.int64).reshape(-1))
+        if len(given) != K:
+            raise ValueError("%s: %d positions for %d frames" % (what, len(given), K))
+    got = np.zeros(K, np.int64)
+    y = _row_statement(what, s, inFormat, (tempo, nWin, search, given.ctypes.data if given is not None and K else None, got.ctypes.data if K else None, fmt),
+                       (Lout,), np.float32 if fmt else np.int16)
+    return (y, got) if returnPositions else y
+
+
+def pcmTempo(pcm, tempo, nWin=512, search=160, positions=None, dtype=np.float32, returnPositions=False):
+    """int16 PCM at another tempo by WSOLA on the host (speechPlayer_pcmTempo; no GPU), by the definition in include/speechPlayer_batch.h:
+    -> float32 or int16 [ceil(len / tempo)], with returnPositions (y, positions int64 [K]).  A tempo above 1 is faster speech; the pitch
+    stays.  nWin is the (Hann) window, its half the hop of the output; `search` the lags either side of the nominal position among which
+    frame k takes the one whose segment correlates best with the natural continuation of frame k - 1 (0: plain overlap-add).
+    positions: render these (K = tempoFrames(len, tempo, nWin) of them) instead of searching."""
+    return _tempo_statement("pcmTempo", _pcm_samples(pcm, "pcmTempo"), None, tempo, nWin, search, positions, dtype, returnPositions)
+
+
+def signalTempo(x, tempo, nWin=512, search=160, positions=None, dtype=np.float32, returnPositions=False):
+    """pcmTempo on a signal's row (speechPlayer_signalTempo; no GPU): x as signalSpectrogram's.  The statement
+    BatchPlayer.tempoTensor(signal=...) is held to."""
+    return _tempo_statement("signalTempo", *_signal_samples(x, "signalTempo"), tempo, nWin, search, positions, dtype, returnPositions)
+
+
+def tempoMap(positions, nWin, outLength):
+    """The time map of a tempo export (numpy, no GPU): int64 [outLength], per output sample m the input sample of the segment with the
+    larger window weight -- with q = m // Hs and i = m - q * Hs, positions[q] + i for i < Hs / 2, else positions[q + 1] - Hs + i.  It
+    carries the label grids of the other exports across: labels_at_tempo = labels[np.clip(tempoMap(...), 0, L - 1)]."""
+    p = np.ascontiguousarray(_host_array(positions, np.int64).reshape(-1))
+    if isinstance(nWin, (bool, np.bool_)) or not isinstance(nWin, (int, np.integer)) or nWin < 2 or nWin % 2:
+        raise ValueError("tempoMap: nWin must be an even integer, not %r" % (nWin,))
+    hs, outLength = int(nWin) // 2, int(outLength)
+    need = int(_tempo_frames(max(outLength, 0), nWin))
+    if outLength < 0 or len(p) < need:
+        raise ValueError("tempoMap: %d outputs take %d positions, not %d" % (outLength, need, len(p)))
+    m = np.arange(outLength, dtype=np.int64)
+    q, i = m // hs, m % hs
+    return np.where(2 * i < hs, p[q] + i, p[q + 1] - hs + i) if outLength else m
+
+
 MIX_TILE = 1024                  # kMixTile of csrc/klatt_mix.h: consecutive outputs of one row a workgroup takes at a time
 MIX_MAX_TERMS = 64               # kMixMaxTerms: of one row
 MIX_MAX_CALL_TERMS = 1 << 22     # kMixMaxCallTerms: of one call
@@ -1955,6 +2060,70 @@ class BatchPlayer(object):
             return export(order, hop, phase, lpc.data_ptr() if lpc.numel() else None, 1 if lpc.dtype == torch.float32 else 0, cols, column, cstride, which, out, fmt,
                           stride, stream)
         return self._export_rows(src.lengths, (), torch.float32 if fmt else torch.int16, padded, call)
+
+    def _tempo_rows(self, what, tempo, nWin, search, dtype, signal, utterances):
+        """What the tempo exports share: the row source, the rows' tempos, output lengths and frame counts."""
+        src = self._rows(what, signal, utterances)
+        tempo, nWin, search, fmt = check_tempo_request(tempo, nWin, search, dtype, src.n, what)
+        outLens = _tempo_lengths(src.lengths, tempo) if src.n else np.zeros(0, np.int64)
+        return src, tempo, nWin, search, fmt, outLens, _tempo_frames(outLens, nWin)
+
+    def tempoPositionsTensor(self, tempo, nWin=512, search=160, utterances=None, padded=True, signal=None):
+        """The time map of the batch's PCM at another tempo as a torch.int64 tensor on the batch's device
+        (speechPlayer_batch_exportTempoPositions), filled on torch's current stream behind the synthesis without a host wait:
+        -> (positions, counts).  Row i has K = tempoFrames(length, tempo, nWin) positions: positions[k] is the input sample that lies at
+        output sample k * nWin / 2 (pcmTempo says how it is chosen; tempoMap gives the map per sample).  tempo: a number, or one per ROW
+        -- with repeats in `utterances` one utterance comes at several tempos.  padded: [n, most frames], 0 past a row's count, and the
+        n counts; else [total frames] and the n + 1 offsets (int64 CPU tensors).  The batch must have been synthesised since it was set.
+        signal: the (tensor, lengths or offsets) pair another export returned, read in place of the batch's PCM
+        (speechPlayer_batch_exportTempoPositionsOf): `utterances` then chooses rows of the signal and no synthesis is needed."""
+        import torch
+        src, tempo, nWin, search, _, _, frames = self._tempo_rows("tempoPositionsTensor", tempo, nWin, search, None, signal, utterances)
+        export = self._entry("TempoPositions", src)
+
+        def call(out, stride, numel, stream):
+            return export(tempo.ctypes.data, nWin, search, out, stride, stream)
+        return self._export_rows(frames, (), torch.int64, padded, call)
+
+    def tempoTensor(self, tempo, nWin=512, search=160, positions=None, utterances=None, dtype=None, padded=True, signal=None, returnPositions=False):
+        """The batch's PCM at another tempo by WSOLA as a torch tensor on the batch's device (speechPlayer_batch_exportTempo), filled on
+        torch's current stream behind the synthesis without a host wait: -> (pcm, lengths), with returnPositions (pcm, lengths, positions,
+        counts).  A row of L samples gives ceil(L / tempo): a tempo above 1 is faster speech, and the pitch and the formants stay where
+        they are (resampledTensor moves them; this export followed by it shifts the pitch alone).  tempo, nWin, search and the positions
+        as tempoPositionsTensor's, which runs first when `positions` is None; else positions is a contiguous torch.int64 tensor on the
+        batch's device, [n, at least the most frames] or [total frames], of any values: the caller's own time map.  utterances, padded
+        and the (pcm, lengths) pair as pcmTensor's; dtype torch.float32 (default) or torch.int16 (clipped, rounded to nearest even).
+        pcmTempo is the same definition on the host, which the device equals bit for bit.  (pcm, lengths) feeds the next stage as its
+        signal=.
+        signal: as tempoPositionsTensor's (speechPlayer_batch_exportTempoOf; signalTempo is the host's statement)."""
+        import torch
+        src, tempo, nWin, search, fmt, outLens, frames = self._tempo_rows("tempoTensor", tempo, nWin, search, dtype, signal, utterances)
+        counts = None
+        if positions is None:
+            positions, counts = self.tempoPositionsTensor(tempo, nWin, search, utterances, padded, signal)
+        if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int64 or positions.dim() not in (1, 2) or not positions.is_contiguous():
+            raise TypeError("tempoTensor: the positions must be a contiguous torch.int64 tensor, [rows, frames] or [frames]")
+        if not positions.is_cuda or positions.device.index != self.device:
+            raise ValueError("tempoTensor: the positions must be on the batch's device, cuda:%d, not %s" % (self.device, positions.device))
+        most = int(frames.max()) if len(frames) else 0
+        if positions.dim() == 2:
+            if positions.shape[0] != src.n or positions.shape[1] < most:
+                raise ValueError("tempoTensor: positions %s for %d rows of at most %d frames" % (list(positions.shape), src.n, most))
+            pstride = max(int(positions.shape[1]), 1)      # (0: no row has a frame, nothing is read)
+        else:
+            if positions.shape[0] < int(frames.sum()):
+                raise ValueError("tempoTensor: positions %s for %d frames" % (list(positions.shape), int(frames.sum())))
+            pstride = 0
+        export = self._entry("Tempo", src)
+
+        def call(out, stride, numel, stream):
+            return export(tempo.ctypes.data, nWin, positions.data_ptr() if positions.numel() else None, pstride, out, fmt, stride, stream)
+        y, lengths = self._export_rows(outLens, (), torch.float32 if fmt else torch.int16, padded, call)
+        if not returnPositions:
+            return y, lengths
+        if counts is None:
+            counts = torch.from_numpy(frames if positions.dim() == 2 else np.concatenate([[0], np.cumsum(frames)]).astype(np.int64))
+        return y, lengths, positions, counts
 
     def setNoiseBank(self, clips):
         """The batch's noise bank (speechPlayer_batch_setNoiseBank): a list of one-dimensional float arrays (kept as float32), every value
