@@ -6,7 +6,7 @@
 // tracks, half of the candidates in runs).  tests/native/check_batch_plan.cpp restates the rules by brute force.
 //
 // The order of a set call: list_length, list_timing and classify_list per list (the engine runs them on its threads), then
-//   reroute_lonely_quiet -> eligible_lists -> [the engine's plan_tracks] -> tracks_pay / mark_tracked -> route_direct -> restore_rerouted
+//   reroute_lonely_quiet -> eligible_lists -> [plan_tracks, klatt_trackplan.h] -> tracks_pay / mark_tracked -> route_direct -> restore_rerouted
 // and, with the flags of every utterance final, pack_lanes.
 #pragma once
 

@@ -30,6 +30,8 @@
 #include "klatt_mix.h"
 #include "klatt_export.h"
 #include "klatt_batchplan.h"
+#include "klatt_hostpool.h"
+#include "klatt_trackplan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -43,10 +45,7 @@
 #include <system_error>
 #include <thread>
 #include <numeric>
-#include <condition_variable>
-#include <deque>
 #include <exception>
-#include <functional>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -891,458 +890,12 @@ long long lanepipe_count(const Batch* b)
 #ifndef KLATT_FLAT_WPS
 #define KLATT_FLAT_WPS 2
 #endif
-constexpr size_t kTrackPad = 64;   // slack past the last track
-// ---- planning the tracks of a batch (host only; klatt_tracks.h, klatt_device.h for the track layout) --------------------
-// Per frame of an eligible utterance: which entry kinds its fade moves and where the fade's track will be.  The state walked
-// here is the part of the frame state machine that decides a fade's end points (reference src/frame.cpp:55-72, restated by
-// stage_event): silence keeps the last request's values with the gain gated off, the first frame after silence starts from its
-// own values with the gain gated off, any other frame fades from the previous request's values.  A SHAPE is the vector of
-// the 39 parameter values a track depends on (klatt_device.h); fades with bitwise equal shapes at both ends and the same
-// length share one track.
-// Tracks pay when (nearly) the whole noisy group has them: a batch whose fades share nothing may need more memory than the
-// budget, and splitting such a batch into a tracked and an untracked launch measured slower than either kernel alone
-// (tools/track_probe.py +distinct).  So once more than a tenth of the eligible utterances did not fit, nothing is tracked.
-// hash of a shape's 45 values: four independent multiply-xor chains (one chain of 45 dependent steps was half the planning's time)
-inline unsigned long long hash_shape(const double* v)
-{
-    unsigned long long h[4] = {0x9E3779B97F4A7C15ull, 0xC2B2AE3D27D4EB4Full, 0x165667B19E3779F9ull, 0x27D4EB2F165667C5ull};
-    int i = 0;
-    for (; i + 4 <= kShapeValues; i += 4)
-        for (int j = 0; j < 4; ++j) { unsigned long long w; memcpy(&w, &v[i + j], 8); h[j] = (h[j] ^ w) * 0xFF51AFD7ED558CCDull; h[j] ^= h[j] >> 29; }
-    for (; i < kShapeValues; ++i) { unsigned long long w; memcpy(&w, &v[i], 8); h[0] = (h[0] ^ w) * 0xFF51AFD7ED558CCDull; h[0] ^= h[0] >> 29; }
-    unsigned long long x = h[0] ^ (h[1] * 0x9E3779B97F4A7C15ull) ^ (h[2] << 21 | h[2] >> 43) ^ (h[3] * 0xC2B2AE3D27D4EB4Full);
-    x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull; x ^= x >> 32;
-    return x;
-}
 
-// where a frame's parameter values are on the host: in the caller's frames, or -- records -- in the row of the shape table a record names
-// (the planner reads parameters 1..45 only: a record's own pitches are not among them), or -- frames that stay in device memory
-// (speechPlayer_batch_setUtterancesDevice) -- in the row rowOf[k] of a table that holds ONE frame per distinct (masked) shape hash,
-// downloaded for the planner: equal hashes stand for equal values, as the planner assumes anyway, and klatt_verify_shared checks it
-struct FrameSource {
-    const speechPlayer_frame_t* frames;
-    const speechPlayer_frameRecord_t* records;
-    const speechPlayer_frame_t* shapes;
-    const uint32_t* rowOf = nullptr;
-    const double* values(long long k) const
-    {
-        if (rowOf) return reinterpret_cast<const double*>(shapes + rowOf[k]);
-        return reinterpret_cast<const double*>(records ? shapes + records[k].shape : frames + k);
-    }
-};
-unsigned long long g_planHashMask[2] = {~0ull, ~0ull};      // speechPlayer_setGlobalOption("plan_hash_bits")
-struct TrackPlan {
-    std::vector<TrackRef> ref;              // [nFrames]
-    std::vector<uint32_t> rep;              // [nFrames] the frame whose shape values stand for this frame's (the first one seen with its hash); 0xFFFFFFFF: itself / none
-    std::vector<TrackJob> jobs;             // one per distinct track
-    std::vector<double> shapes;             // [nShapes][kShapeStride]
-    std::vector<unsigned char> tracked;     // [nUtterances]
-    std::vector<uint32_t> kinds;            // [nUtterances] the entry kinds whose values change after the first sample of the utterance's first fade (UttDesc.flags)
-    unsigned long long entries = 0;
-    long long eligible = 0, missedSize = 0, missedBudget = 0;   // utterances that may be tracked; that a fade of 2^27 entries or the budget kept out
-};
-// One pass over utterances [0, nUtterances) of the arrays given (frameStart may start anywhere: ref is indexed from frameStart[0]).
-// `whole`: this is the whole batch -- apply the all-or-nothing rule; a part of it (plan_tracks below) leaves that to the merge,
-// and gives up (missedBudget != 0) as soon as the parts' tracks together (`sum`) pass a quarter of the budget: that batch is
-// planned in one pass (its fades are shared by few utterances, if at all: the parts would each make most of the tracks again, or
-// fill the budget with 400 MB of shapes and map nodes only for the one pass to find that nothing fits -- 0.4 s for 65 536
-// utterances with nothing in common, which is what such a batch costs without the parts).
-// `facts`: klatt_plan.h's 128-bit hash of every frame's shape values (indexed like `frames`): a frame seen before is recognised by
-// it, without gathering, hashing or comparing its 45 values again.
-void plan_tracks_pass(long long nUtterances, const long long* frameStart, const FrameSource& frames, const FrameFacts* facts, const FrameMeta* meta,
-                      const unsigned char* eligible, long long budgetMB, bool whole, std::atomic<unsigned long long>* sum, TrackPlan& out)
-{
-    const long long frame0 = frameStart[0], nF = frameStart[nUtterances] - frame0;
-    out.ref.assign((size_t)nF, TrackRef{0, 0, 0});
-    const bool wantRep = frameStart[nUtterances] < 0xFFFFFFFFll;
-    out.rep.assign(wantRep ? (size_t)nF : 0, 0xFFFFFFFFu);
-    out.jobs.clear();
-    out.shapes.clear();
-    out.tracked.assign((size_t)nUtterances, 0);
-    out.kinds.assign((size_t)nUtterances, 0);
-    out.entries = 0;
-    // the entry kinds whose values differ between two shapes (the comparisons stage_event makes on the device)
-    auto diff_kinds = [](const double* a, const double* c) -> uint32_t {
-        uint32_t mask = 0;
-        for (int r = 0; r < kNumRes; ++r)
-            if (!(c[2 * r] == a[2 * r]) || !(c[2 * r + 1] == a[2 * r + 1])) mask |= 1u << r;
-        for (int e = kNumRes; e < kTrackEntries; ++e) {
-            const int x = entry_value(e, 0), y = entry_value(e, 1);
-            if (!(c[x] == a[x]) || (y >= 0 && !(c[y] == a[y]))) mask |= 1u << e;
-        }
-        return mask;
-    };
-    struct Shape { double v[kShapeValues]; bool operator==(const Shape& o) const { return !memcmp(v, o.v, sizeof v); } };
-    struct ShapeHash { size_t operator()(const Shape& k) const { return (size_t)hash_shape(k.v); } };
-    struct Fade { uint32_t from, to, len; bool operator==(const Fade& o) const { return from == o.from && to == o.to && len == o.len; } };
-    struct FadeHash { size_t operator()(const Fade& k) const { unsigned long long h = ((unsigned long long)k.from << 32 | k.to) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; h += k.len; h *= 0xFF51AFD7ED558CCDull; return (size_t)(h ^ (h >> 32)); } };
-    std::unordered_map<Shape, uint32_t, ShapeHash> shapes;          // values -> id (row of out.shapes)
-    std::unordered_map<Fade, TrackRef, FadeHash> fades;             // (from, to, length) -> the fade's track
-    auto shape_id = [&](const Shape& sh) -> uint32_t {
-        auto it = shapes.find(sh);
-        if (it != shapes.end()) return it->second;
-        const uint32_t id = (uint32_t)shapes.size();
-        shapes.emplace(sh, id);
-        out.shapes.resize((size_t)(id + 1) * kShapeStride, 0.0);
-        memcpy(&out.shapes[(size_t)id * kShapeStride], sh.v, sizeof sh.v);
-        return id;
-    };
-    Shape zero; memset(&zero, 0, sizeof zero);
-    shape_id(zero);
-    // frames seen before, by their hash: the id of their shape and (once somebody needed it) of the same values with the gain gated off
-    struct Key128 { unsigned long long a, b; bool operator==(const Key128& o) const { return a == o.a && b == o.b; } };
-    struct Key128Hash { size_t operator()(const Key128& k) const { return (size_t)k.a; } };
-    struct FrameIds { uint32_t plain, gated; long long first; };
-    std::unordered_map<Key128, FrameIds, Key128Hash> seen;
-    std::vector<uint32_t> gatedOf;          // shape id -> the id of its values with the gain gated off (0xFFFFFFFF: not asked for yet)
-    auto gated_id = [&](uint32_t id) -> uint32_t {
-        if (gatedOf.size() <= id) gatedOf.resize((size_t)id + 64, 0xFFFFFFFFu);
-        if (gatedOf[id] == 0xFFFFFFFFu) {
-            Shape g;
-            memcpy(g.v, &out.shapes[(size_t)id * kShapeStride], sizeof g.v);
-            g.v[kShapePreGain] = 0.0;
-            const uint32_t gid = shape_id(g);
-            if (gatedOf.size() <= id) gatedOf.resize((size_t)id + 64, 0xFFFFFFFFu);
-            gatedOf[id] = gid;
-        }
-        return gatedOf[id];
-    };
-    // (the flat stages address the tracks with 32-bit byte offsets: below 4 GB, 2^28 entries)
-    const unsigned long long budget = std::min((unsigned long long)std::max(budgetMB, 0ll) * (1ull << 20) / sizeof(double2), (1ull << 28) - (1ull << 21) - kTrackPad);
-    std::vector<Fade> added;
-    long long nEligible = 0, nMissed = 0;
-    out.missedSize = 0; out.missedBudget = 0;
-    for (long long u = 0; u < nUtterances; ++u) nEligible += eligible[u] ? 1 : 0;
-    out.eligible = nEligible;
-    // Give up early on a batch whose fades are (nearly) all different: its tracks grow in proportion to the utterances walked and
-    // would pass the budget long before the end -- walking on until they do, hashing 45 values per frame and filling the maps,
-    // was 0.6 s for 65 536 such utterances (30 launches' worth) for nothing.  Two look-outs, after 1/32 and 1/16 of the
-    // utterances: tracks that doubled in between (no sharing yet: a batch that shares its fades saturates early) and that at this
-    // rate end beyond the budget.
-    const long long look1 = nUtterances / 32, look2 = nUtterances / 16;
-    unsigned long long entriesAt1 = 0;
-    for (long long u = 0; u < nUtterances && (!whole || nMissed * 10 <= nEligible); ++u) {
-        if (whole && look1 >= 256) {
-            if (u == look1) entriesAt1 = out.entries;
-            if (u == look2 && out.entries - entriesAt1 >= entriesAt1 - entriesAt1 / 8 &&
-                (long double)out.entries * ((long double)nUtterances / (long double)look2) > (long double)budget) {
-                nMissed = nEligible + 1;      // the all-or-nothing rule below: nothing is tracked
-                out.missedBudget = nEligible;
-                break;
-            }
-        }
-        if (!eligible[u]) continue;
-        if (sum && sum->load(std::memory_order_relaxed) > budget / 4) { ++out.missedBudget; return; }
-        added.clear();
-        const unsigned long long before = out.entries;
-        const size_t jobsBefore = out.jobs.size();
-        bool fits = true, prevNull = true;
-        uint32_t prevId = 0;       // the previous request's values (a fresh handle: all zero = shape 0)
-        uint32_t kinds = 0;
-        for (long long k = frameStart[u]; k < frameStart[u + 1] && fits; ++k) {
-            uint32_t fromId = prevId, toId;
-            const uint32_t lastTo = prevId;
-            if (meta[k].flags & FRAME_NULL) {
-                toId = gated_id(prevId);                       // silence: the old values, the gain gated off (:59-63)
-                prevNull = true;
-            } else {
-                // (records: the key is the shape's number, exact -- never masked)
-                const Key128 fk = frames.records ? Key128{facts[k].h0, facts[k].h1} : Key128{facts[k].h0 & g_planHashMask[0], facts[k].h1 & g_planHashMask[1]};
-                auto it = seen.find(fk);
-                if (it == seen.end()) {
-                    Shape to;
-                    const double* p = frames.values(k);
-                    for (int i = 0; i < kShapeValues; ++i) to.v[i] = p[shape_param(i)];
-                    it = seen.emplace(fk, FrameIds{shape_id(to), 0xFFFFFFFFu, k}).first;
-                } else if (wantRep) {
-                    out.rep[k - frame0] = (uint32_t)it->second.first;      // taken on trust here; compared where the frames are (klatt_verify_shared)
-                }
-                toId = it->second.plain;
-                if (prevNull) {                                // out of silence: the new values, from gain 0 (:64-67)
-                    if (it->second.gated == 0xFFFFFFFFu) it->second.gated = gated_id(toId);
-                    fromId = it->second.gated;
-                }
-                prevNull = false;
-            }
-            prevId = toId;
-            const Fade key{fromId, toId, meta[k].fadeSamples};
-            auto f = fades.find(key);
-            if (f == fades.end()) {
-                // a new fade: what moves in it (the comparisons stage_event makes on the device), its size, its place
-                const uint32_t mask = diff_kinds(&out.shapes[(size_t)fromId * kShapeStride], &out.shapes[(size_t)toId * kShapeStride]);
-                const uint32_t nSlots = track_slots(mask);
-                const unsigned long long n = (unsigned long long)kTrackFirst + (unsigned long long)(meta[k].fadeSamples - 1u) * nSlots;
-                if (n >= (1ull << 27)) { fits = false; ++out.missedSize; break; }
-                if (out.entries + n > budget) { fits = false; ++out.missedBudget; break; }
-                if (sum && sum->fetch_add(n, std::memory_order_relaxed) + n > budget / 4) { ++out.missedBudget; return; }
-                f = fades.emplace(key, TrackRef{out.entries, mask, nSlots}).first;
-                added.push_back(key);
-                out.jobs.push_back(TrackJob{out.entries, key.from, key.to, meta[k].fadeSamples, mask});
-                out.entries += n;
-            }
-            out.ref[k - frame0] = f->second;
-            // what changes after the utterance's first fade sample: what a fade moves, and what a later fade's first sample re-sets
-            // to other values than the previous fade ended on (the frame after a silence starts from ITS values, gain gated off)
-            kinds |= f->second.mask;
-            if (k > frameStart[u] && fromId != lastTo)
-                kinds |= diff_kinds(&out.shapes[(size_t)lastTo * kShapeStride], &out.shapes[(size_t)fromId * kShapeStride]);
-        }
-        out.kinds[u] = kinds;
-        if (fits) out.tracked[u] = 1;
-        else {
-            for (const Fade& key : added) fades.erase(key);
-            out.jobs.resize(jobsBefore);
-            out.entries = before;
-            ++nMissed;
-        }
-    }
-    if (whole && nMissed * 10 > nEligible) {
-        out.tracked.assign((size_t)nUtterances, 0);
-        out.jobs.clear();
-        out.entries = 0;
-    }
-}
-
-// The host's worker threads.  Until round 5 every parallel section started and joined its own std::threads: eight sections of a
-// setUtterances call are ~56 thread starts, 2-4 ms of a 22 ms call on the GPU box.  Now a pool that lives as long as the process:
-// workers sleep on a condition variable, a section queues its parts and its caller works on queued parts (its own or anybody's) until
-// its own are done -- so sections of several callers (the setter threads of a pipeline, the device threads of a node) share the workers
-// without waiting for each other, and a section whose parts all queue behind others still finishes on its caller's thread.
-// Parts never start sections of their own.  The pool is never destroyed (its threads sleep at process exit).
-class WorkerPool {
-public:
-    struct Section { std::atomic<unsigned> left{0}; };
-    static WorkerPool& get() { static WorkerPool* p = new WorkerPool(); return *p; }
-    void submit(Section* sec, std::function<void()> fn)
-    {
-        { std::lock_guard<std::mutex> lg(mu_); queue_.emplace_back(sec, std::move(fn)); }
-        cv_.notify_one();
-    }
-    // run queued parts until `sec` has none left
-    void help_until_done(Section* sec)
-    {
-        std::unique_lock<std::mutex> lk(mu_);
-        while (sec->left.load(std::memory_order_acquire) != 0) {
-            if (!queue_.empty()) {
-                auto job = std::move(queue_.front());
-                queue_.pop_front();
-                lk.unlock();
-                job.second();
-                job.first->left.fetch_sub(1, std::memory_order_acq_rel);
-                done_.notify_all();
-                lk.lock();
-            } else {
-                done_.wait_for(lk, std::chrono::microseconds(200));
-            }
-        }
-    }
-    unsigned workers() const { return nWorkers_; }
-private:
-    WorkerPool()
-    {
-        // as many workers as the process may really use: CPU affinity, capped by the cgroup quota (the GPU box shows 256 hardware threads
-        // and grants 16 CPUs) and by 32
-        unsigned n = std::max(1u, std::thread::hardware_concurrency());
-        if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-            char q[64] = {0}; long long period = 0;
-            if (fscanf(f, "%63s %lld", q, &period) == 2 && strcmp(q, "max") != 0 && period > 0) n = std::min<unsigned>(n, (unsigned)std::max<long long>(1, atoll(q) / period));
-            fclose(f);
-        }
-        n = std::min(n, 32u);
-        for (unsigned i = 0; i + 1 < n; ++i) {
-            try { std::thread([this] { loop(); }).detach(); ++nWorkers_; } catch (const std::system_error&) { break; }
-        }
-    }
-    void loop()
-    {
-        std::unique_lock<std::mutex> lk(mu_);
-        for (;;) {
-            cv_.wait(lk, [this] { return !queue_.empty(); });
-            auto job = std::move(queue_.front());
-            queue_.pop_front();
-            lk.unlock();
-            job.second();
-            job.first->left.fetch_sub(1, std::memory_order_acq_rel);
-            done_.notify_all();
-            lk.lock();
-        }
-    }
-    std::mutex mu_;
-    std::condition_variable cv_, done_;
-    std::deque<std::pair<Section*, std::function<void()>>> queue_;
-    unsigned nWorkers_ = 0;
-};
-
-// fn(0) .. fn(n - 1) side by side: n - 1 of them offered to the pool, the last one on the caller's thread, which then helps until all are done.
-template <class F>
-void run_parts(unsigned n, F fn)
-{
-    if (n <= 1) { if (n) fn(0u); return; }
-    WorkerPool& pool = WorkerPool::get();
-    if (pool.workers() == 0) { for (unsigned t = 0; t < n; ++t) fn(t); return; }
-    // A part that throws (std::bad_alloc in a planner's maps) must neither unwind this frame while queued parts still point at it nor
-    // leave the section's count standing: every part runs under a guard that keeps the first exception, the caller helps until all
-    // parts are done, and only then is the exception thrown on -- on the caller's thread.
-    WorkerPool::Section sec;
-    std::mutex emu;
-    std::exception_ptr first;
-    auto guarded = [&](unsigned t) {
-        try { fn(t); } catch (...) { std::lock_guard<std::mutex> g(emu); if (!first) first = std::current_exception(); }
-    };
-    sec.left.store(n - 1, std::memory_order_release);
-    for (unsigned t = 0; t + 1 < n; ++t) pool.submit(&sec, [&guarded, t] { guarded(t); });
-    guarded(n - 1);
-    pool.help_until_done(&sec);
-    if (first) std::rethrow_exception(first);
-}
-
-// Host threads of setUtterances (the planner's setting: SPEECHPLAYER_PLAN_THREADS, else up to 8), and a loop over [0, n) cut into
-// one contiguous range per thread (small loops stay on the caller's thread).
-unsigned host_threads()
-{
-    unsigned n = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-    if (const char* e = getenv("SPEECHPLAYER_PLAN_THREADS")) n = (unsigned)std::max(1, atoi(e));
-    return n;
-}
-template <class F>
-void parallel_ranges(long long n, long long grain, F fn)
-{
-    const unsigned t = (unsigned)std::min<long long>(host_threads(), std::max<long long>(1, n / std::max<long long>(grain, 1)));
-    if (t < 2) { fn(0ll, n); return; }
-    run_parts(t, [&](unsigned k) { fn(n * (long long)k / t, n * (long long)(k + 1) / t); });
-}
-
-// The plan of a batch.  Large batches are planned in parts, one host thread each (the walk is a hash of 45 values and two map
-// look-ups per frame: 0.2 s for BASELINE configs[2] on one thread), and the parts' shapes and fades merged: equal fades of
-// different parts end up with one track.  If the merged tracks fit the budget that is the plan; if not -- or if the parts gave
-// up (plan_tracks_pass) -- the batch is planned again in one pass, whose order decides which utterances stay in.
-void plan_tracks(long long nUtterances, const long long* frameStart, const FrameSource& frames, const FrameFacts* facts, const FrameMeta* meta,
-                 const unsigned char* eligible, long long budgetMB, TrackPlan& out)
-{
-    const long long nF = frameStart[nUtterances];
-    static const bool trace = getenv("SPEECHPLAYER_PLAN_TRACE") != nullptr;      // where the planning's time goes, on stderr
-    const auto tStart = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (trace) fprintf(stderr, "[speechPlayer/plan] %s: %.1f ms since the start\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tStart).count());
-    };
-    const unsigned nThreads = host_threads();
-    if (nThreads < 2 || nF < 200000 || nUtterances < (long long)nThreads * 64) {
-        plan_tracks_pass(nUtterances, frameStart, frames, facts, meta, eligible, budgetMB, true, nullptr, out);
-        return;
-    }
-    // A look at the first 128th of the batch before the threads start (the look-outs of plan_tracks_pass, whole = true): a batch
-    // whose fades are all different is given up after a few milliseconds instead of after the parts have filled a quarter of the budget.
-    {
-        TrackPlan probe;
-        // (never past the batch: the threaded path is entered with as few as 2 x 64 utterances -- ADVICE r3)
-        const long long nProbe = std::min<long long>(nUtterances, std::max<long long>(nUtterances / 128, 256));
-        std::vector<unsigned char> none;
-        plan_tracks_pass(nProbe, frameStart, frames, facts, meta, eligible, budgetMB, false, nullptr, probe);
-        TrackPlan half;
-        plan_tracks_pass(nProbe / 2, frameStart, frames, facts, meta, eligible, budgetMB, false, nullptr, half);
-        const unsigned long long cap = std::min((unsigned long long)std::max(budgetMB, 0ll) * (1ull << 20) / sizeof(double2), (1ull << 28) - (1ull << 21) - kTrackPad);
-        if (trace) fprintf(stderr, "[speechPlayer/plan] look: %llu entries after %lld utterances, %llu after %lld; budget %llu\n", half.entries, nProbe / 2, probe.entries, nProbe, cap);
-        const long double scale = (long double)nUtterances / (long double)nProbe;
-        // (tracks that double with the utterances and at that rate end more than a ninth beyond the budget: then more than a tenth of
-        // the utterances would not fit, and the rule is all or nothing)
-        if (half.entries > 0 && probe.missedBudget == 0 && probe.entries - half.entries >= half.entries - half.entries / 8 &&
-            (long double)probe.entries * scale * 0.9L > (long double)cap) {
-            out.ref.assign((size_t)nF, TrackRef{0, 0, 0});
-            out.rep.clear();
-            out.jobs.clear(); out.shapes.clear(); out.entries = 0;
-            out.tracked.assign((size_t)nUtterances, 0);
-            out.kinds.assign((size_t)nUtterances, 0);
-            out.eligible = 0; out.missedSize = 0; out.missedBudget = 0;
-            for (long long u = 0; u < nUtterances; ++u) out.eligible += eligible[u] ? 1 : 0;
-            out.missedBudget = out.eligible;
-            lap("given up after the look at the first utterances");
-            return;
-        }
-    }
-    lap("looked at the first utterances");
-    // parts of about equal frame counts
-    std::vector<long long> cut(nThreads + 1, nUtterances);
-    cut[0] = 0;
-    for (unsigned t = 1; t < nThreads; ++t)
-        cut[t] = std::lower_bound(frameStart, frameStart + nUtterances, nF * (long long)t / nThreads) - frameStart;
-    std::vector<TrackPlan> part(nThreads);
-    std::atomic<unsigned long long> sum{0};
-    run_parts(nThreads, [&](unsigned t) {
-        plan_tracks_pass(cut[t + 1] - cut[t], frameStart + cut[t], frames, facts, meta, eligible + cut[t], budgetMB, false, &sum, part[t]);
-    });
-    lap("parts planned");
-    // merge: shapes by value, fades by (from, to, length)
-    struct ShapeKey { const double* v; bool operator==(const ShapeKey& o) const { return !memcmp(v, o.v, kShapeValues * sizeof(double)); } };
-    struct ShapeKeyHash { size_t operator()(const ShapeKey& k) const { return (size_t)hash_shape(k.v); } };
-    struct FadeKey { uint32_t from, to, len; bool operator==(const FadeKey& o) const { return from == o.from && to == o.to && len == o.len; } };
-    struct FadeKeyHash { size_t operator()(const FadeKey& k) const { unsigned long long h = ((unsigned long long)k.from << 32 | k.to) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; h += k.len; h *= 0xFF51AFD7ED558CCDull; return (size_t)(h ^ (h >> 32)); } };
-    long long eligibleAll = 0, missedSize = 0, missedBudget = 0;
-    size_t nShapesUpper = 0;
-    for (const TrackPlan& p : part) { eligibleAll += p.eligible; missedSize += p.missedSize; missedBudget += p.missedBudget; nShapesUpper += p.shapes.size() / kShapeStride; }
-    if (missedBudget > 0) {
-        part.clear();
-        plan_tracks_pass(nUtterances, frameStart, frames, facts, meta, eligible, budgetMB, true, nullptr, out);
-        return;
-    }
-    out.shapes.clear();
-    out.shapes.reserve(nShapesUpper * kShapeStride);     // no reallocation below: the keys point into it
-    out.jobs.clear();
-    out.entries = 0;
-    std::unordered_map<ShapeKey, uint32_t, ShapeKeyHash> shapes;
-    std::unordered_map<FadeKey, unsigned long long, FadeKeyHash> fades;
-    std::vector<std::unordered_map<unsigned long long, unsigned long long>> offOf(nThreads);   // part, its track's first entry -> the merged track's
-    for (unsigned t = 0; t < nThreads; ++t) {
-        const TrackPlan& p = part[t];
-        std::vector<uint32_t> gid(p.shapes.size() / kShapeStride);
-        for (size_t i = 0; i < gid.size(); ++i) {
-            const ShapeKey key{&p.shapes[i * kShapeStride]};
-            auto it = shapes.find(key);
-            if (it == shapes.end()) {
-                const uint32_t id = (uint32_t)(out.shapes.size() / kShapeStride);
-                out.shapes.insert(out.shapes.end(), key.v, key.v + kShapeStride);
-                it = shapes.emplace(ShapeKey{&out.shapes[(size_t)id * kShapeStride]}, id).first;
-            }
-            gid[i] = it->second;
-        }
-        for (const TrackJob& j : p.jobs) {
-            const FadeKey key{gid[j.fromShape], gid[j.toShape], j.fadeSamples};
-            auto it = fades.find(key);
-            if (it == fades.end()) {
-                it = fades.emplace(key, out.entries).first;
-                out.jobs.push_back(TrackJob{out.entries, key.from, key.to, j.fadeSamples, j.mask});
-                out.entries += (unsigned long long)kTrackFirst + (unsigned long long)(j.fadeSamples - 1u) * track_slots(j.mask);
-            }
-            offOf[t].emplace(j.off, it->second);
-        }
-    }
-    const unsigned long long budget = std::min((unsigned long long)std::max(budgetMB, 0ll) * (1ull << 20) / sizeof(double2), (1ull << 28) - (1ull << 21) - kTrackPad);
-    if (out.entries > budget) {
-        plan_tracks_pass(nUtterances, frameStart, frames, facts, meta, eligible, budgetMB, true, nullptr, out);
-        return;
-    }
-    out.eligible = eligibleAll; out.missedSize = missedSize; out.missedBudget = 0;
-    out.ref.assign((size_t)nF, TrackRef{0, 0, 0});
-    out.rep.assign(nF < 0xFFFFFFFFll ? (size_t)nF : 0, 0xFFFFFFFFu);
-    out.tracked.assign((size_t)nUtterances, 0);
-    out.kinds.assign((size_t)nUtterances, 0);
-    if (missedSize * 10 > eligibleAll) { out.jobs.clear(); out.entries = 0; return; }   // all or nothing
-    run_parts(nThreads, [&](unsigned t) {
-        const TrackPlan& p = part[t];
-        const long long f0 = frameStart[cut[t]];
-        for (long long u = cut[t]; u < cut[t + 1]; ++u) {
-            if (!p.tracked[u - cut[t]]) continue;
-            out.tracked[u] = 1;
-            out.kinds[u] = p.kinds[u - cut[t]];
-            for (long long k = frameStart[u]; k < frameStart[u + 1]; ++k) {
-                TrackRef r = p.ref[k - f0];
-                r.off = offOf[t].find(r.off)->second;
-                out.ref[k] = r;
-                if (!out.rep.empty() && !p.rep.empty()) out.rep[k] = p.rep[k - f0];
-            }
-        }
-    });
-    lap("merged");
-}
+// The track planner, the shape table and the fades' end points are klatt_trackplan.h; the host's worker threads klatt_hostpool.h.
+// speechPlayer_setGlobalOption("plan_hash_bits"): read once per set call or planning view, on the calling thread (plan_hash_mask),
+// and handed to the planner by value -- no planner thread reads it.
+std::atomic<unsigned long long> g_planHashMask[2] = {{~0ull}, {~0ull}};
+HashMask plan_hash_mask() { return HashMask{g_planHashMask[0].load(std::memory_order_relaxed), g_planHashMask[1].load(std::memory_order_relaxed)}; }
 
 // (Timing-only experiment builds -- wrong PCM, kept as a patch under tools/variants/ since round 5 -- define KLATT_TIMING_ONLY_BUILD: such a
 // library refuses to hand PCM out, it only times.  ADVICE r3.)
@@ -1358,45 +911,6 @@ bool refuse_timing_only(const char* what)
     set_error("%s: this library was built with a timing-only experiment switch; its PCM is not valid", what);
     return true;
 }
-
-// The end points of the fades of one utterance's frames [k0, k1), appended to `out` (reference src/frame.cpp:55-72: a NULL request
-// -- silence -- keeps the previous request's values with the gain gated off; the first frame after silence starts from its own
-// values with the gain gated off; any other frame fades from the previous request's values).  klatt_seeds reads the values
-// themselves on the device.  Host-only view for the tests: speechPlayer_planDirect.
-template <class V>
-void walk_fade_ends(long long k0, long long k1, const FrameMeta* meta, V& out)
-{
-    uint32_t prevReal = kNoFrame;
-    bool prevNull = true;
-    for (long long k = k0; k < k1; ++k) {
-        DirectJob j;
-        j.frame = (uint32_t)k;
-        if (meta[k].flags & FRAME_NULL) {
-            j.from = prevReal; j.to = prevReal;
-            j.flags = (prevNull ? 1u : 0u) | 2u;
-            prevNull = true;
-        } else {
-            j.to = (uint32_t)k;
-            j.from = prevNull ? (uint32_t)k : prevReal;
-            j.flags = prevNull ? 1u : 0u;
-            prevReal = (uint32_t)k;
-            prevNull = false;
-        }
-        out.push_back(j);
-    }
-}
-
-// A vector whose resize() does not value-initialise (trivial element types only): the per-frame work arrays of setUtterances are
-// written in full, in parallel, right after they are sized -- a zero-fill by the calling thread first costs ~1 ms per 6 MB.
-template <class T>
-struct NoInitAlloc : std::allocator<T> {
-    template <class U> struct rebind { using other = NoInitAlloc<U>; };
-    NoInitAlloc() = default;
-    template <class U> NoInitAlloc(const NoInitAlloc<U>&) {}
-    template <class U> void construct(U* p) { ::new (static_cast<void*>(p)) U; }
-    template <class U, class... A> void construct(U* p, A&&... a) { ::new (static_cast<void*>(p)) U(std::forward<A>(a)...); }
-};
-template <class T> using RawVector = std::vector<T, NoInitAlloc<T>>;
 
 long long tracked_count(const Batch* b) { return (b->tracks && b->layout != 0) ? b->nTracked : 0; }
 // (setUtterances only forms the direct group under the stage-parallel layouts)
@@ -2323,8 +1837,8 @@ int speechPlayer_setGlobalOption(const char* name, int value)
     // fall-back behind it; the PCM must not change.
     if (name && !strcmp(name, "plan_hash_bits")) {
         const int bits = value < 0 ? 0 : (value > 128 ? 128 : value);
-        g_planHashMask[0] = bits >= 64 ? ~0ull : (bits == 0 ? 0ull : ((1ull << bits) - 1ull));
-        g_planHashMask[1] = bits >= 128 ? ~0ull : (bits <= 64 ? 0ull : ((1ull << (bits - 64)) - 1ull));
+        g_planHashMask[0].store(bits >= 64 ? ~0ull : (bits == 0 ? 0ull : ((1ull << bits) - 1ull)), std::memory_order_relaxed);
+        g_planHashMask[1].store(bits >= 128 ? ~0ull : (bits <= 64 ? 0ull : ((1ull << (bits - 64)) - 1ull)), std::memory_order_relaxed);
         return 0;
     }
     set_error("unknown global option %s", name ? name : "(null)");
@@ -2879,52 +2393,13 @@ int speechPlayer_batch_setRecordsLabelled(speechPlayer_batch_t batch, long long 
 
 int speechPlayer_batch_hasLabels(speechPlayer_batch_t batch) { return batch ? (static_cast<Batch*>(batch)->hasLabels ? 1 : 0) : -1; }
 
-// Frames in device memory (speechPlayer_batch_setUtterancesDevice) and the track planner, which reads the values of a frame whose
-// (masked) shape hash it has not seen yet (FrameSource::values): one frame per distinct hash among the frames it may read -- the
-// non-silent frames of the lists that may be tracked --, the first in frame order, stands for all frames of that hash; rowOf[k] names
-// frame k's.  Their rows are gathered on the device (klatt_gather_frames) and downloaded: a few hundred rows for speech, instead of
-// the frames.  Host threads over parts of the lists, each with a map of its own; the maps are merged in frame order.
+// Frames in device memory (speechPlayer_batch_setUtterancesDevice) and the track planner: one frame per distinct (masked) shape hash
+// stands for all frames of that hash (shape_table_rows, klatt_trackplan.h).  Their rows are gathered on the device
+// (klatt_gather_frames) and downloaded: a few hundred rows for speech, instead of the frames.
 static int device_shape_table(Batch* b, long long nL, const long long* listStart, const FrameMeta* meta, const FrameFacts* facts,
-                              const unsigned char* eligible, RawVector<uint32_t>& rowOf, std::vector<long long>& rep, std::vector<double>& rows)
+                              const unsigned char* eligible, HashMask mask, RawVector<uint32_t>& rowOf, std::vector<long long>& rep, std::vector<double>& rows)
 {
-    struct Key { unsigned long long a, b; bool operator==(const Key& o) const { return a == o.a && b == o.b; } };
-    struct KeyHash { size_t operator()(const Key& k) const { return (size_t)(k.a ^ (k.b * 0x9E3779B97F4A7C15ull)); } };
-    struct Part { std::unordered_map<Key, uint32_t, KeyHash> id; std::vector<long long> first; std::vector<Key> keys; };
-    const long long nF = listStart[nL];
-    rowOf.resize((size_t)nF);
-    const unsigned nT = (unsigned)std::max<long long>(1, std::min<long long>(host_threads(), nF / 65536 + 1));
-    std::vector<long long> cut(nT + 1, nL);
-    cut[0] = 0;
-    for (unsigned t = 1; t < nT; ++t) cut[t] = std::lower_bound(listStart, listStart + nL, nF * (long long)t / nT) - listStart;
-    std::vector<Part> part(nT);
-    auto each_frame = [&](unsigned t, auto fn) {
-        for (long long l = cut[t]; l < cut[t + 1]; ++l)
-            if (eligible[l])
-                for (long long k = listStart[l]; k < listStart[l + 1]; ++k)
-                    if (!(meta[k].flags & FRAME_NULL)) fn(k);
-    };
-    run_parts(nT, [&](unsigned t) {
-        Part& p = part[t];
-        each_frame(t, [&](long long k) {
-            const Key key{facts[k].h0 & g_planHashMask[0], facts[k].h1 & g_planHashMask[1]};
-            auto it = p.id.find(key);
-            if (it == p.id.end()) { it = p.id.emplace(key, (uint32_t)p.first.size()).first; p.first.push_back(k); p.keys.push_back(key); }
-            rowOf[k] = it->second;
-        });
-    });
-    std::unordered_map<Key, uint32_t, KeyHash> global;
-    std::vector<std::vector<uint32_t>> remap(nT);
-    rep.clear();
-    for (unsigned t = 0; t < nT; ++t) {
-        const Part& p = part[t];
-        remap[t].resize(p.first.size());
-        for (size_t i = 0; i < p.first.size(); ++i) {
-            auto it = global.find(p.keys[i]);
-            if (it == global.end()) { it = global.emplace(p.keys[i], (uint32_t)rep.size()).first; rep.push_back(p.first[i]); }
-            remap[t][i] = it->second;
-        }
-    }
-    run_parts(nT, [&](unsigned t) { each_frame(t, [&](long long k) { rowOf[k] = remap[t][rowOf[k]]; }); });
+    shape_table_rows(nL, listStart, meta, facts, eligible, mask, rowOf, rep);
     const size_t nRows = rep.size();
     rows.assign(nRows * kNumParams, 0.0);
     if (nRows == 0) return 0;
@@ -3279,14 +2754,15 @@ static int set_plan(SetCall& c)
     std::vector<long long> shapeRep;
     std::vector<double> shapeRows;
     const bool wantTracks = route.want_tracks() && nF > 0;
+    const HashMask hashMask = plan_hash_mask();
     if (wantTracks && c.byDevice) {
-        if (device_shape_table(b, nL, listStart, meta, facts, eligible.data(), rowOf, shapeRep, shapeRows)) return -1;
+        if (device_shape_table(b, nL, listStart, meta, facts, eligible.data(), hashMask, rowOf, shapeRep, shapeRows)) return -1;
         source.shapes = reinterpret_cast<const speechPlayer_frame_t*>(shapeRows.data());
         source.rowOf = rowOf.data();
         c.lap("shape table");
     }
     if (wantTracks) {
-        plan_tracks(nL, listStart, source, facts, meta, eligible.data(), b->trackBudgetMB, plan);
+        plan_tracks(nL, listStart, source, facts, meta, eligible.data(), track_budget_entries(b->trackBudgetMB), hashMask, plan);
         if (source.rowOf && !plan.rep.empty()) {
             // every frame the planner took values for stands for the table's row: each is compared with the row's frame (klatt_verify_shared)
             parallel_ranges(nL, 4096, [&](long long la, long long le) {
@@ -4370,7 +3846,7 @@ static long long plan_tracks_view(long long nUtterances, const long long* frameS
         parallel_ranges(nF, 1 << 14, [&](long long a, long long e) { for (long long k = a; k < e; ++k) own[k] = frame_facts(reinterpret_cast<const double*>(frames + k), 1e300, 1e300); });
         facts = own.data();
     }
-    plan_tracks(nUtterances, frameStart, FrameSource{frames, nullptr, nullptr}, facts, meta.data(), eligible, budgetMB, plan);
+    plan_tracks(nUtterances, frameStart, FrameSource{frames, nullptr, nullptr}, facts, meta.data(), eligible, track_budget_entries(budgetMB), plan_hash_mask(), plan);
     // what klatt_verify_shared does on the device, here on the host: every frame recognised by its hash against the frame that stood for it
     if (collisionAt) *collisionAt = -1;
     for (long long k = 0; k < nF && !plan.rep.empty(); ++k) {

@@ -20,7 +20,10 @@
 #include <string.h>
 
 #include "klatt_consts.h"
-#include "klatt_device.h"
+#include "klatt_layout.h"
+#if defined(__HIPCC__)
+#include "klatt_device.h"      // the kernels below
+#endif
 
 namespace klatt {
 
@@ -30,15 +33,15 @@ struct FrameFacts {          // 24 B per frame
     uint32_t pad;
 };
 
-__host__ __device__ inline bool fact_finite(double v)
+KLATT_LAYOUT_HD inline bool fact_finite(double v)
 {
     unsigned long long w;
     memcpy(&w, &v, 8);
     return (w & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
 }
-__host__ __device__ inline double fact_abs(double v) { return v < 0 ? -v : v; }      // (NaN stays NaN: every test below is written to fail on it)
+KLATT_LAYOUT_HD inline double fact_abs(double v) { return v < 0 ? -v : v; }      // (NaN stays NaN: every test below is written to fail on it)
 // key n of the hash (splitmix64 of n: a constant wherever n is one)
-__host__ __device__ constexpr unsigned long long fact_key(int n)
+KLATT_LAYOUT_HD constexpr unsigned long long fact_key(int n)
 {
     unsigned long long z = (unsigned long long)(n + 1) * 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -47,7 +50,7 @@ __host__ __device__ constexpr unsigned long long fact_key(int n)
 }
 // high ^ low half of the 128-bit product, plus both operands: a zero operand (a value whose bit pattern equals its key) annihilates
 // the product, not the word -- the other operand still counts
-__host__ __device__ inline unsigned long long fact_fold(unsigned long long a, unsigned long long c)
+KLATT_LAYOUT_HD inline unsigned long long fact_fold(unsigned long long a, unsigned long long c)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return (__umul64hi(a, c) ^ (a * c)) + a + ((c << 32) | (c >> 32));
@@ -58,7 +61,7 @@ __host__ __device__ inline unsigned long long fact_fold(unsigned long long a, un
 }
 
 // what the two pitches (parameters 0 and 46) contribute to a frame's flags
-__host__ __device__ inline uint32_t pitch_flags(double p0, double p46)
+KLATT_LAYOUT_HD inline uint32_t pitch_flags(double p0, double p46)
 {
     uint32_t fl = 0;
     if (!fact_finite(p0) || !fact_finite(p46)) fl |= 2u;                         // FACT_NONFINITE
@@ -66,7 +69,7 @@ __host__ __device__ inline uint32_t pitch_flags(double p0, double p46)
     return fl;
 }
 // ... and what parameters 1..45 contribute (p: all 47; 0 and 46 are not looked at)
-__host__ __device__ inline uint32_t shape_flags(const double* p, double maxF, double maxBw)
+KLATT_LAYOUT_HD inline uint32_t shape_flags(const double* p, double maxF, double maxBw)
 {
     uint32_t fl = 0;
     // Noise sources and the parallel bank can be skipped for an utterance only if every frame has all three noise gains exactly zero
@@ -98,7 +101,7 @@ __host__ __device__ inline uint32_t shape_flags(const double* p, double maxF, do
     return fl;
 }
 // are the 45 shape values (parameters 1..45) of two frames the same bits?
-__host__ __device__ inline bool shape_values_equal(const double* a, const double* c)
+KLATT_LAYOUT_HD inline bool shape_values_equal(const double* a, const double* c)
 {
     bool same = true;
     for (int i = 1; i < kNumParams - 1; ++i) {
@@ -110,7 +113,7 @@ __host__ __device__ inline bool shape_values_equal(const double* a, const double
 }
 
 // p: the frame's 47 parameters (include/speechPlayer.h); maxF / maxBw: the direct stages' bounds for this sample rate
-__host__ __device__ inline FrameFacts frame_facts(const double* p, double maxF, double maxBw)
+KLATT_LAYOUT_HD inline FrameFacts frame_facts(const double* p, double maxF, double maxBw)
 {
     FrameFacts o;
     const uint32_t fl = shape_flags(p, maxF, maxBw) | pitch_flags(p[0], p[46]);
@@ -118,7 +121,9 @@ __host__ __device__ inline FrameFacts frame_facts(const double* p, double maxF, 
     // keyed multiply-fold sums over them, a pair of values per 64 x 64 -> 128-bit product (every position has keys of its own: the
     // same values in other places are another frame), each then avalanched: ~23 multiplies per word instead of a chain of 45.
     unsigned long long x = 0x9E3779B97F4A7C15ull, y = 0xC2B2AE3D27D4EB4Full;
+#if defined(__HIPCC__)
 #pragma unroll
+#endif
     for (int i = 0; i < 46; i += 2) {      // (unrolled: the keys are literals)
         unsigned long long w0, w1 = 0;
         memcpy(&w0, &p[1 + i], 8);

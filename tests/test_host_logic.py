@@ -259,3 +259,46 @@ def test_batch_planning_under_sanitizers(tmp_path):
                            "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "native", "check_batch_plan.cpp"), "-o", exe])
     out = subprocess.check_output([exe], stderr=subprocess.STDOUT).decode()
     assert out.startswith("ok ") and "runtime error" not in out and "AddressSanitizer" not in out, out
+
+
+TRACK_PLAN_BRANCHES = 14      # the branches tests/native/check_track_plan.cpp counts; one reached zero times fails the program itself
+
+
+def run_check_track_plan(exe):
+    """its whole output, a sanitizer's report included (a report is a non-zero exit, which the callers read from the text)"""
+    return subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT).stdout.decode()
+
+
+def test_track_planning_under_sanitizers(tmp_path):
+    """The track planner, the shape table and the host's worker pool (csrc/klatt_trackplan.h, csrc/klatt_hostpool.h) as a stand-alone
+    program, tests/native/check_track_plan.cpp, under AddressSanitizer + UBSan: one pass against a restatement of the frame rules and
+    the budget rule, planning in parts against one pass (frameStart allocated to its exact length), the shape table against a scan,
+    the pool's sections.  Nothing loaded into python is run under a sanitizer."""
+    exe = str(tmp_path / "check_track_plan")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "native", "check_track_plan.cpp"), "-o", exe])
+    out = run_check_track_plan(exe)
+    assert out.startswith("ok ") and "runtime error" not in out and "AddressSanitizer" not in out and "FAILED" not in out, out
+    taken = [int(n) for n in re.findall(r": (\d+)$", out, flags=re.M)]
+    assert len(taken) == TRACK_PLAN_BRANCHES and min(taken) > 0, out
+
+
+def test_track_planning_and_pool_under_thread_sanitizer(tmp_path):
+    """The same program under ThreadSanitizer: the parts of the planner and of the shape table, sections of four callers at once, a part
+    that throws -- no report.  Built with the clang++ that hipcc compiles with: its ThreadSanitizer follows the timed wait of a
+    condition variable on the steady clock (pthread_cond_clockwait, the pool's help_until_done); the runtime of g++ 11 does not, takes
+    the waiting thread to hold the mutex all along, and reports every other thread's lock as a double lock.
+    Skips only where ThreadSanitizer itself refuses to start (a memory layout it does not know), never on a report."""
+    import shutil
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    clang = os.path.join(subprocess.check_output([os.path.join(os.path.dirname(os.path.realpath(hipcc)), "hipconfig"), "--hipclangpath"]).decode().strip(), "clang++")
+    assert os.path.exists(clang), clang
+    exe = str(tmp_path / "check_track_plan_tsan")
+    subprocess.check_call([clang, "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=thread", "-fno-omit-frame-pointer",
+                           "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "native", "check_track_plan.cpp"), "-o", exe])
+    out = run_check_track_plan(exe)
+    if "unexpected memory mapping" in out and "ThreadSanitizer: data race" not in out and not out.startswith("ok "):
+        pytest.skip("ThreadSanitizer does not start on this kernel's memory layout")
+    assert out.startswith("ok ") and "ThreadSanitizer" not in out and "FAILED" not in out, out
+    taken = [int(n) for n in re.findall(r": (\d+)$", out, flags=re.M)]
+    assert len(taken) == TRACK_PLAN_BRANCHES and min(taken) > 0, out

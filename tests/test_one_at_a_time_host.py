@@ -118,7 +118,7 @@ def plan_kinds(b):
 
 
 def walked_kinds(b, masks, keys):
-    """The kinds word by the rule of plan_tracks, from the fade end points tests/test_track_planning.expected walks: what a fade moves,
+    """The kinds word by the rule of plan_tracks (csrc/klatt_trackplan.h), from the fade end points tests/test_track_planning.expected walks: what a fade moves,
     and what the first sample of a later fade sets to other values than the fade before it ended on."""
     shape = [p for r in range(14) for p in (RES_F[r], RES_B[r])] + [23, 41, 42, 43, 45, 24, 44, 37, 38, 39, 40, 1, 2, 3, 4, 5, 6]
     out = []
