@@ -1265,7 +1265,8 @@ int speechPlayer_lastLiveLaunches(int device);
  * unrelated handles 11.2 ms per 8192-sample pull however few they are -- while 2 .. 256 handles alone in their wavefronts take 1.4-1.7 ms
  * and 1024 take 6.2, 1536 9.3 (the two policies meet near 1850 handles).  Handles that speak IN STEP (same frames from the same sample) are the exception: beyond 256 of them sharing
  * wavefronts is faster (2.5 ms) -- set 1 for those.  Needs "live_replicate" 1 and "live_layout" 1.
- * "plan_hash_bits" (tests): how many bits of a frame's 128-bit shape hash the track planner looks at (default 128). */
+ * "plan_hash_bits" (tests): how many bits of a frame's 128-bit shape hash the track planner looks at (default 128).
+ * Options may be set from any thread; a pull in flight finishes under the values it started with. */
 int speechPlayer_setGlobalOption(const char* name, int value);
 /* Choose a handle's noise stream (default 0); see DESIGN.md "Noise". */
 int speechPlayer_setNoiseSeed(speechPlayer_handle_t playerHandle, unsigned int seed);

@@ -46,22 +46,6 @@ constexpr int kStateDoubles = 240;        // per-stream saved state (streaming p
 constexpr int MODE_EXACT = 0;
 constexpr int MODE_FAST = 1;
 
-struct UttDesc {             // 32 B per utterance
-    long long frameStart;    // first frame (index into frames / meta)
-    long long outStart;      // sample offset in the PCM pool, multiple of kTile
-    uint32_t nFrames;
-    uint32_t seed;
-    uint32_t flags;          // UTT_NEEDS_NOISE: some frame has a non-zero (or non-finite) noise gain
-    uint32_t length;         // samples this utterance produces (closed form, host-computed)
-};
-
-struct UttResult {           // written by the kernel
-    uint32_t produced;       // samples written by this launch
-    uint32_t framesTaken;    // frames dequeued by this launch
-    int32_t lastIndex;
-    uint32_t drained;        // 1: the queue ran dry (short count)
-};
-
 // ---- tracks: their entries and kinds are laid out in klatt_layout.h; here, how the flat stages divide them ----------------------
 constexpr int kTrackStages = 4;
 // the kinds of a stage's part, and their entries (N0 takes two)

@@ -32,6 +32,7 @@
 #include "klatt_batchplan.h"
 #include "klatt_hostpool.h"
 #include "klatt_trackplan.h"
+#include "klatt_live.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1063,10 +1064,10 @@ int batch_launch(Batch* b)
 // (speechPlayer_queueFrame), the log travels in one copy and a scatter kernel drops its entries into the rings; a pull
 // uploads one control block (what to do for each handle of the call) and whatever part of the log has not travelled yet.
 // Nothing a handle queued is staged again on a later pull (reference contract: src/frame.cpp:90-115 queue, :54-75 dequeue).
-constexpr uint32_t kRing = 256;                  // frames of a handle on the device; further ones wait on the host (Stream::overflow)
+// The host's bookkeeping of all this -- a handle's ring and host queue, the log's indices, the options, the plan of a pull -- is
+// klatt_live.h, which has no HIP in it and a native test of its own; here are the memory, the copies and the launches.
 constexpr size_t kLogEntries = 40960;            // 16 MB of pinned log
 constexpr size_t kLogEager = 2560;               // queueFrame sends the log on its way once 1 MB waits (if no pull is running)
-constexpr uint32_t kNoTarget = 0xFFFFFFFFu;
 
 struct LogEntry {            // 400 B
     double p[kNumParams];
@@ -1075,11 +1076,6 @@ struct LogEntry {            // 400 B
     uint32_t pad;
 };
 static_assert(sizeof(LogEntry) == 400, "LogEntry layout");
-
-struct PendingFrame {
-    double p[kNumParams];
-    FrameMeta meta;
-};
 
 __global__ void __launch_bounds__(256) live_scatter(const LogEntry* __restrict__ log, uint32_t n, double* __restrict__ ringFrames,
                                                     FrameMeta* __restrict__ ringMeta)
@@ -1115,12 +1111,6 @@ __global__ void __launch_bounds__(256) live_place(const double* __restrict__ fra
     }
 }
 
-inline uint32_t frame_span(const FrameMeta& m)      // samples from this frame's dequeue to the next one's, the closed form of speechPlayer_batch_setUtterances
-{
-    const unsigned long long v = std::max<unsigned long long>(m.minSamples, (unsigned long long)m.fadeSamples + 1) + 1;
-    return (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull);
-}
-
 struct Stream {
     int sampleRate = 0;
     int device = 0;
@@ -1130,14 +1120,8 @@ struct Stream {
     std::mutex mu;                       // per call, not per sample (reference locks per sample: src/frame.cpp:122)
     struct LiveContext* context = nullptr;   // the device's live-handle context
     uint32_t slot = 0;                   // its place in the device's arena
-    uint32_t ringHead = 0;               // ring position of the oldest frame the kernel has not taken
-    uint32_t ringCount = 0;              // frames in the ring from there on (travelled, or waiting in the log)
-    uint32_t span[kRing];                // frame_span of each ring position; read only while frames wait in `overflow`
-    std::vector<PendingFrame> overflow;  // queued beyond the ring: overflow[overHead ..], in order
-    size_t overHead = 0;
-    uint32_t logEpoch = 0;               // logIdx is valid for this upload epoch of the log only
-    std::vector<uint32_t> logIdx;        // this handle's entries in the part of the log that has not travelled
-    bool purgePending = false;
+    FrameQueue q;                        // its ring, and what waits on the host behind it
+    LogMine logged;                      // its entries in the part of the log that has not travelled
     int lastIndex = -1;
 };
 
@@ -1190,8 +1174,7 @@ struct LiveContext {
     std::mutex logMu;
     PinnedBuffer<LogEntry> hLog;
     DeviceBuffer<LogEntry> dLog;
-    size_t logTail = 0, logSent = 0;     // entries [logSent, logTail) have not travelled
-    uint32_t logEpoch = 1;
+    LogIndex<LogEntry> log;              // over hLog
     // one pull
     PinnedBuffer<unsigned char> hCtl;    // UttDesc[n] | state pointer[n] | control[n], one copy
     DeviceBuffer<unsigned char> dCtl;
@@ -1226,15 +1209,8 @@ struct LiveContext {
 };
 std::mutex g_liveMutex;
 std::vector<LiveContext*> g_live;   // per device
-// Which kernel advances live handles: 1 = the stage-parallel kernel's STREAM instantiation (four wavefronts per 64 handles;
-// default), 0 = the lane kernel's (one wavefront per 64 handles).  Same saved state, same PCM; speechPlayer_setGlobalOption.
-int g_liveLayout = [] { const char* e = getenv("SPEECHPLAYER_LIVE_LAYOUT"); return e ? atoi(e) : 1; }();
-int g_liveCus = 0;
-bool g_liveCusForced = false;
-int g_liveReplicate = [] { const char* e = getenv("SPEECHPLAYER_LIVE_REPLICATE"); return e ? atoi(e) : 1; }();   // a lone handle fills its wavefront (streams_synthesize)
-int g_liveMode = [] { const char* e = getenv("SPEECHPLAYER_LIVE_MODE"); return e && atoi(e) == 1 ? MODE_FAST : MODE_EXACT; }();   // arithmetic mode of handles created from now on
-int g_liveAlone = [] { const char* e = getenv("SPEECHPLAYER_LIVE_ALONE"); return e ? atoi(e) : 1536; }();   // pulls of up to this many handles: a wavefront per handle (streams_synthesize)
-int g_liveTrim = 0;                 // speechPlayer_setGlobalOption("live_trim"): release a device's arena when its last handle is terminated
+LiveOptions g_liveOptions;          // speechPlayer_setGlobalOption's "live_*"; a pull, initialize and terminate read one snapshot() each
+static_assert(MODE_EXACT == 0 && MODE_FAST == 1, "live_mode's values (klatt_live.h)");
 
 // c->mu held.  No handle lives on this device: give its arena (state blocks, rings) and the pull buffers back.  The next
 // speechPlayer_initialize starts a new arena of 64 slots.
@@ -1283,6 +1259,7 @@ LiveContext* live_context(int device)
             delete c;
             return nullptr;
         }
+        c->log.entries = c->hLog.ptr; c->log.cap = c->hLog.cap;
         g_live[device] = c;
     }
     return g_live[device];
@@ -1332,81 +1309,53 @@ int stream_init_device(Stream* s)
 // c->mu and c->logMu held.  What waits in the log goes on its way: one copy, one scatter launch; not waited for.
 int log_send(LiveContext* c)
 {
-    if (c->logSent == c->logTail) return 0;
-    const size_t n = c->logTail - c->logSent;
-    HIP_TRY(hipMemcpyAsync(c->dLog.ptr + c->logSent, c->hLog.ptr + c->logSent, n * sizeof(LogEntry), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(live_scatter, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, c->dLog.ptr + c->logSent, (uint32_t)n,
+    const size_t n = c->log.waiting(), from = c->log.sent;
+    if (n == 0) return 0;
+    HIP_TRY(hipMemcpyAsync(c->dLog.ptr + from, c->hLog.ptr + from, n * sizeof(LogEntry), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(live_scatter, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, c->dLog.ptr + from, (uint32_t)n,
                        c->dRingFrames.ptr, c->dRingMeta.ptr);
     HIP_TRY(hipGetLastError());
-    c->logSent = c->logTail;
-    c->logEpoch++;                       // every Stream::logIdx is stale from here on
+    c->log.mark_sent();
     return 0;
 }
 
-// s->mu held.  The handle's next ring position for a frame (the caller has checked ring_takes): its target in the arena.
-uint32_t ring_claim(Stream* s, const FrameMeta& meta)
-{
-    const uint32_t pos = (s->ringHead + s->ringCount) & (kRing - 1);
-    s->span[pos] = frame_span(meta);
-    s->ringCount++;
-    return s->slot * kRing + pos;
-}
-
-// s->mu held.  One frame into the handle's ring, by way of the log.  The caller has checked ringCount < kRing.
-int log_append(LiveContext* c, Stream* s, const double* p, const FrameMeta& meta, bool holdsContext)
+// s->mu held.  One frame into the handle's ring at the position claimed for it (FrameQueue::claim), by way of the log.
+int log_append(LiveContext* c, Stream* s, const double* p, const FrameMeta& meta, uint32_t pos, bool holdsContext)
 {
     std::unique_lock<std::mutex> lg(c->logMu);
-    if (c->logTail == c->hLog.cap) {     // full: send it, wait until it has arrived, start over (lock order: mu before logMu)
+    LogEntry* e = c->log.append(s->logged);
+    if (!e) {                            // full: send it, wait until it has arrived, start over (lock order: mu before logMu)
         std::unique_lock<std::mutex> g(c->mu, std::defer_lock);
         if (!holdsContext) { lg.unlock(); g.lock(); lg.lock(); }
-        if (c->logTail == c->hLog.cap) {
+        e = c->log.append(s->logged);
+        if (!e) {
             HIP_TRY(hipSetDevice(s->device));
             if (log_send(c)) return -1;
             HIP_TRY(hipStreamSynchronize(c->stream));
-            c->logTail = c->logSent = 0;
+            c->log.arrived();
+            e = c->log.append(s->logged);
         }
     }
-    LogEntry& e = c->hLog.ptr[c->logTail];
-    if (p) memcpy(e.p, p, sizeof e.p); else memset(e.p, 0, sizeof e.p);
-    e.meta = meta;
-    e.target = ring_claim(s, meta);
-    e.pad = 0;
-    if (s->logEpoch != c->logEpoch) { s->logIdx.clear(); s->logEpoch = c->logEpoch; }
-    s->logIdx.push_back((uint32_t)c->logTail);
-    c->logTail++;
+    if (p) memcpy(e->p, p, sizeof e->p); else memset(e->p, 0, sizeof e->p);
+    e->meta = meta;
+    e->target = s->slot * kRing + pos;
+    e->pad = 0;
     return 0;
 }
 
-// s->mu held.  Forget what the handle has in the ring and in the log (purge, close).
+// s->mu held.  Forget what the handle has in the ring and in the log (close; the device half of a purge).
 void ring_drop(LiveContext* c, Stream* s)
 {
     std::lock_guard<std::mutex> lg(c->logMu);
-    if (s->logEpoch == c->logEpoch)
-        for (uint32_t i : s->logIdx) c->hLog.ptr[i].target = kNoTarget;
-    s->logIdx.clear();
-    s->ringHead = (s->ringHead + s->ringCount) & (kRing - 1);
-    s->ringCount = 0;
+    c->log.untarget(s->logged);
+    s->q.drop();
 }
 
-// s->mu held.  A purge request (reference src/frame.cpp:103-112): what the handle queued is forgotten, in the ring and on the host;
-// the state half of the purge runs in the kernel before the next sample.
+// s->mu held.  A purge request: FrameQueue::purge, and the handle's waiting log entries go nowhere.
 void stream_purge(LiveContext* c, Stream* s)
 {
-    ring_drop(c, s);
-    s->overflow.clear(); s->overHead = 0;
-    s->purgePending = true;
-}
-
-// s->mu held.  A queued frame goes into the handle's ring while the ring has room and nothing waits on the host, else into the
-// handle's host queue, from where the next pulls refill the ring (copied: the caller may reuse its frame, reference src/frame.cpp:97).
-bool ring_takes(const Stream* s) { return s->overHead == s->overflow.size() && s->ringCount < kRing; }
-void overflow_push(Stream* s, const double* p, const FrameMeta& meta)
-{
-    PendingFrame f;
-    memset(&f, 0, sizeof f);
-    f.meta = meta;
-    if (p) memcpy(f.p, p, sizeof f.p);
-    s->overflow.push_back(f);
+    { std::lock_guard<std::mutex> lg(c->logMu); c->log.untarget(s->logged); }
+    s->q.purge();
 }
 
 // speechPlayer_synthesizeManyExport: where a pull's rows go (caller-owned device memory the entry point has checked).
@@ -1439,11 +1388,133 @@ int live_export(LiveContext* c, const int16_t* pcm, size_t padded, const int* pr
     return 0;
 }
 
+// One pull of n live handles (streams_synthesize): what its steps share.  c->mu and every handle's mutex are held throughout.
+struct Pull {
+    LiveContext* c;
+    Stream* const* ss;
+    int n;
+    int mode;
+    size_t padded;           // samples from a handle's PCM row to the next
+    PullPlan plan;
+    CtlBlock ctl;
+};
+
+// Room for the pull's control block, its results and its PCM; the order 0, 1, 2, ... long enough.
+int pull_reserve(const Pull& p)
+{
+    LiveContext* c = p.c;
+    const size_t nCtl = p.ctl.nCtl;
+    if (c->hCtl.reserve(p.ctl.bytes()) || c->dCtl.reserve(c->hCtl.cap) || c->hResult.reserve(nCtl) || c->dResult.reserve(c->hResult.cap) ||
+        c->dPcm.reserve(p.padded * p.n))
+        return -1;
+    if (c->orderFilled < nCtl) {
+        const size_t m = std::max<size_t>(nCtl, 1024);
+        std::vector<uint32_t> iota(m);
+        std::iota(iota.begin(), iota.end(), 0u);
+        if (c->dOrder.reserve(m)) return -1;
+        HIP_TRY(hipMemcpy(c->dOrder.ptr, iota.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
+        c->orderFilled = m;
+    }
+    return 0;
+}
+
+// The rings take what waited on the host, by way of the log.  *piece: how far of `want` samples this launch may go without meeting a
+// frame that is not in a ring (FrameQueue::reach).
+int pull_refill(const Pull& p, unsigned int want, unsigned int* piece)
+{
+    *piece = want;
+    for (int i = 0; i < p.n; ++i) {
+        Stream* s = p.ss[i];
+        if (s->q.refill([&](const PendingFrame& f, uint32_t pos) { return log_append(p.c, s, (f.meta.flags & FRAME_NULL) ? nullptr : f.p, f.meta, pos, true); }))
+            return -1;
+        *piece = s->q.reach(*piece);
+    }
+    return 0;
+}
+
+// The control block of a launch of `piece` samples, in page-locked memory.
+void pull_fill(const Pull& p, unsigned int piece)
+{
+    fill_ctl(p.ctl.at(p.c->hCtl.ptr), p.plan, p.n, [&](int i) {
+        const Stream* s = p.ss[i];
+        CtlEntry e;
+        e.utt.frameStart = (long long)s->slot * kRing + s->q.ringHead;
+        e.utt.outStart = (long long)(i * p.padded);
+        e.utt.nFrames = s->q.ringCount;
+        e.utt.seed = s->seed; e.utt.flags = UTT_NEEDS_NOISE;
+        e.utt.length = piece;            // the stage-parallel kernel runs exactly `piece` steps (klatt_systolic.h, STREAM)
+        e.state = p.c->dState.ptr + (size_t)s->slot * kStateDoubles;
+        e.control = s->q.purgePending ? 1u : 0u;
+        return e;
+    });
+}
+
+int pull_launch(const Pull& p, const KernelArgs& a)
+{
+    hipStream_t st = p.c->stream;
+    switch (p.plan.launch) {
+    case LiveLaunch::Lane: return launch<true, true>(a, p.mode, p.plan.groups, st);
+    case LiveLaunch::Lone: return launch_systolic<true, 16, 1, true, true, false, true>(a, p.mode, p.plan.groups, st);
+    case LiveLaunch::StreamOnePerCu: return launch_systolic<true, 16, 1, true, true>(a, p.mode, p.plan.groups, st);
+    case LiveLaunch::StreamTwoPerCu: return launch_systolic<true, KLATT_NOISY_CH, 2, true, true>(a, p.mode, p.plan.groups, st);
+    }
+    return -1;
+}
+
+// What the kernel reports, fetched and waited for, into the handles' queues and into done[].
+int pull_apply(const Pull& p, unsigned int piece)
+{
+    LiveContext* c = p.c;
+    for (int i = 0; i < p.n; ++i) {
+        Stream* s = p.ss[i];
+        const UttResult& r = c->hResult.ptr[(size_t)i * p.plan.rep];
+        if (r.produced > piece || r.framesTaken > s->q.ringCount) { set_error("kernel produced %u > %u (took %u frames of %u)", r.produced, piece, r.framesTaken, s->q.ringCount); return -1; }
+        s->q.took(r.framesTaken);
+        s->lastIndex = r.lastIndex;
+        c->done[i] += r.produced;
+    }
+    return 0;
+}
+
+// Rows 0 .. rows-1 of the pull (done[i] samples at pcm + i * padded) into their callers' buffers: whole rows in pieces of about 16 MB
+// through two pinned buffers; piece k + 1 is in flight while the rows of piece k are handed to their callers.
+int pull_hand_out(LiveContext* c, const int16_t* pcm, size_t padded, size_t rows, sample* const* outs)
+{
+    const size_t rowsPerPiece = std::max<size_t>(1, (8u << 20) / padded);
+    if (c->bounce.ensure(rowsPerPiece * padded * sizeof(int16_t))) return -1;
+    const size_t nPieces = (rows + rowsPerPiece - 1) / rowsPerPiece;
+    auto issue = [&](size_t k) -> int {
+        const size_t r0 = k * rowsPerPiece, r1 = std::min(rows, r0 + rowsPerPiece);
+        HIP_TRY(hipMemcpyAsync(c->bounce.buf[k & 1], pcm + r0 * padded, (r1 - r0) * padded * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(c->bounce.ev[k & 1], c->stream));
+        return 0;
+    };
+    if (issue(0)) return -1;
+    for (size_t k = 0; k < nPieces; ++k) {
+        if (k + 1 < nPieces && issue(k + 1)) return -1;
+        HIP_TRY(hipEventSynchronize(c->bounce.ev[k & 1]));
+        const size_t r0 = k * rowsPerPiece, r1 = std::min(rows, r0 + rowsPerPiece);
+        const int16_t* src = static_cast<const int16_t*>(c->bounce.buf[k & 1]);
+        auto rows_out = [&](size_t b0, size_t b1) {
+            for (size_t i = b0; i < b1; ++i)
+                if (c->done[i]) memcpy(outs[i], src + (i - r0) * padded, (size_t)c->done[i] * sizeof(int16_t));
+        };
+        // a piece of several megabytes is handed out in four shares side by side (the host's worker pool): one thread's memcpy (about 20 GB/s) is slower than the copy over PCIe
+        constexpr unsigned kHands = 4;
+        const size_t share = (r1 - r0 + kHands - 1) / kHands;
+        if ((r1 - r0) * padded * sizeof(int16_t) >= (4u << 20))
+            run_parts(kHands, [&](unsigned t) { const size_t b0 = std::min(r1, r0 + t * share); rows_out(b0, std::min(r1, b0 + share)); });
+        else rows_out(r0, r1);
+    }
+    return 0;
+}
+
 // Advance n live streams by up to `count` samples each (one stream per wavefront lane; one launch, unless some handle has
 // more frames queued than its ring holds AND the ring's frames end before `count` samples: then the call proceeds in pieces,
 // refilling the rings in between -- a pull is the same as several shorter pulls, reference src/speechPlayer.cpp:39-42).
 // The callers hold every stream's mutex.  produced[i] receives speechPlayer_synthesize's return value.
 // outs == nullptr: the PCM stays on the device (row i at devicePcm + i * stride), for consumers on the GPU.
+// The live options are read once, on entry (klatt_live.h: one snapshot, one plan); what is set meanwhile is the next pull's.
 #ifdef KLATT_STAMPS
 unsigned long long g_streamStamps[32];
 extern "C" __attribute__((visibility("default"))) void speechPlayer_debugStreamStamps(unsigned long long* out) { for (int k = 0; k < 32; ++k) { out[k] = g_streamStamps[k]; g_streamStamps[k] = 0; } }
@@ -1458,6 +1529,7 @@ int streams_synthesize(Stream* const* ss, int n, unsigned int count, sample* con
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const auto t0 = now();
+    const LiveSettings options = g_liveOptions.snapshot();
     const int device = ss[0]->device, rate = ss[0]->sampleRate, mode = ss[0]->mode;
     for (int i = 1; i < n; ++i)
         if (ss[i]->device != device || ss[i]->sampleRate != rate || ss[i]->mode != mode) {
@@ -1470,52 +1542,16 @@ int streams_synthesize(Stream* const* ss, int n, unsigned int count, sample* con
     HIP_TRY(hipSetDevice(device));
     const size_t padded = ((size_t)count + kTile - 1) / kTile * kTile;
     if (live_wait_exports(c, padded * n > c->dPcm.cap)) return -1;
-    // A LONE handle -- the reference's own use (one stream pulled 8192 samples at a time, nvdaAddon/synthDrivers/nvSpeechPlayer/__init__.py:62-81)
-    // -- is advanced in ALL 64 lanes of its wavefront: every lane is given the same control entry (same state block, same ring, same PCM
-    // row) and computes the same samples; they store the same values to the same places.  A wavefront with one active lane runs the same
-    // instructions but, measured, takes 1.0 / 1.4 / 1.7 times as long from launch to launch (4.3 / 6.1 / 7.4 ms for one cfg2 utterance
-    // against a steady 4.13 ms with 16 or more lanes active: tools/lone_probe2.py); with all lanes active a pull costs what 64 handles cost:
-    // thirty 8192-sample pulls of one handle 3.05 -> 2.04 ms of kernel time on average (tools/single_stream_ab.sh).  The launch then takes
-    // the kernel's LONE instantiation, whose fade chunks are computed side by side across the identical lanes (klatt_systolic.h,
-    // stage_loop: 2.04 -> 1.84 ms); control bit 1 marks the entries.
-    // The same goes for a pull of SEVERAL handles, up to "live_alone" of them (default 1536: six rounds of 256 workgroups; the two policies meet near 1850 unrelated handles): a workgroup per handle, 64 replicas each.  Handles
-    // that share a wavefront pay for one another -- with unrelated handles every chunk has some lane at an event or in a fade and runs sample
-    // by sample: 11.7 ms per 8192-sample pull however few they are -- while a handle alone in its wavefront costs 1.3-1.7 ms and 256 of them
-    // run side by side, one per CU (the LONE instantiation's LDS allows one workgroup per CU): n handles take ceil(n / CUs) rounds of that.
-    const bool replicate = n >= 1 && n <= std::max(1, g_liveAlone) && g_liveLayout != 0 && g_liveReplicate;
-    const int rep = replicate ? kLanes : 1;              // control entries (lanes) per handle
-    // (a FEW handles pulled together -- fewer than half a wavefront -- get their empty lanes filled with replicas of themselves too, on the
-    // ordinary kernel: the same effect, and the same remedy as for the sparse wavefronts of a batch)
-    const bool fillSparse = !replicate && n > 1 && n < kLanes / 2 && g_liveLayout != 0 && g_liveReplicate;
-    const int nCtl = replicate ? n * kLanes : (fillSparse ? kLanes : n);
-    const size_t ctlBytes = (size_t)nCtl * (sizeof(UttDesc) + sizeof(double*) + sizeof(uint32_t));
-    if (c->hCtl.reserve(ctlBytes) || c->dCtl.reserve(c->hCtl.cap) || c->hResult.reserve(nCtl) || c->dResult.reserve(c->hResult.cap) ||
-        c->dPcm.reserve(padded * n))
-        return -1;
-    if (c->orderFilled < (size_t)nCtl) {
-        const size_t m = std::max<size_t>(nCtl, 1024);
-        std::vector<uint32_t> iota(m);
-        std::iota(iota.begin(), iota.end(), 0u);
-        if (c->dOrder.reserve(m)) return -1;
-        HIP_TRY(hipMemcpy(c->dOrder.ptr, iota.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
-        c->orderFilled = m;
-    }
-    UttDesc* const hUtt = reinterpret_cast<UttDesc*>(c->hCtl.ptr);
-    double** const hState = reinterpret_cast<double**>(c->hCtl.ptr + (size_t)nCtl * sizeof(UttDesc));
-    uint32_t* const hControl = reinterpret_cast<uint32_t*>(c->hCtl.ptr + (size_t)nCtl * (sizeof(UttDesc) + sizeof(double*)));
-    if (g_liveCus == 0 && !g_liveCusForced) {
-        hipDeviceProp_t prop;
-        g_liveCus = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
+    const PullPlan plan = pull_plan(n, options, c->cus);
+    const Pull p{c, ss, n, mode, padded, plan, CtlBlock{(size_t)plan.nCtl}};
+    if (pull_reserve(p)) return -1;
 
     KernelArgs a = base_args(rate);
+    const CtlBlock::View dCtl = p.ctl.at(c->dCtl.ptr);
     a.frames = c->dRingFrames.ptr; a.meta = c->dRingMeta.ptr; a.ringMask = kRing - 1;
-    a.utt = reinterpret_cast<const UttDesc*>(c->dCtl.ptr);
-    a.statePtrs = reinterpret_cast<double* const*>(c->dCtl.ptr + (size_t)nCtl * sizeof(UttDesc));
-    a.control = reinterpret_cast<const uint32_t*>(c->dCtl.ptr + (size_t)nCtl * (sizeof(UttDesc) + sizeof(double*)));
+    a.utt = dCtl.utt; a.statePtrs = dCtl.state; a.control = dCtl.control;
     a.order = c->dOrder.ptr; a.pcm = c->dPcm.ptr; a.result = c->dResult.ptr; a.state = nullptr;
-    a.nSlots = nCtl;
-    const long long groups = (nCtl + kLanes - 1) / kLanes;
+    a.nSlots = plan.nCtl;
 
     c->done.assign(n, 0u);
     c->lastKernelMs = 0.0f; c->lastLaunches = 0;
@@ -1524,69 +1560,25 @@ int streams_synthesize(Stream* const* ss, int n, unsigned int count, sample* con
     bool joined = false;                 // the pieces of a call in pieces are put together in dPcmJoin
     while (at < count) {
         const auto ta = now();
-        // rings take what waited on the host; how far may this launch go without meeting a frame that is not in a ring?
-        unsigned int piece = count - at;
-        for (int i = 0; i < n; ++i) {
-            Stream* s = ss[i];
-            if (s->overHead < s->overflow.size()) {
-                while (s->ringCount < kRing && s->overHead < s->overflow.size()) {
-                    const PendingFrame& f = s->overflow[s->overHead];
-                    if (log_append(c, s, (f.meta.flags & FRAME_NULL) ? nullptr : f.p, f.meta, true)) return -1;
-                    s->overHead++;
-                }
-                if (s->overHead == s->overflow.size()) { s->overflow.clear(); s->overHead = 0; }
-                else {
-                    if (s->overHead >= 64 && s->overHead * 2 >= s->overflow.size()) { s->overflow.erase(s->overflow.begin(), s->overflow.begin() + s->overHead); s->overHead = 0; }
-                    // the ring's last frame may be dequeued only when its successor is there to follow it
-                    unsigned long long safe = 0;
-                    for (uint32_t k = 0; k + 1 < s->ringCount && safe < piece; ++k) safe += s->span[(s->ringHead + k) & (kRing - 1)];
-                    piece = (unsigned int)std::min<unsigned long long>(piece, safe);
-                }
-            }
-        }
-        for (int i = 0; i < n; ++i) {
-            const Stream* s = ss[i];
-            UttDesc& d = hUtt[(size_t)i * rep];
-            d.frameStart = (long long)s->slot * kRing + s->ringHead;
-            d.outStart = (long long)(i * padded);
-            d.nFrames = s->ringCount;
-            d.seed = s->seed; d.flags = UTT_NEEDS_NOISE;
-            d.length = piece;                // the stage-parallel kernel runs exactly `piece` steps (klatt_systolic.h, STREAM)
-            hState[(size_t)i * rep] = c->dState.ptr + (size_t)s->slot * kStateDoubles;
-            hControl[(size_t)i * rep] = s->purgePending ? 1u : 0u;
-        }
-        if (replicate) {
-            for (int i = 0; i < n; ++i) {
-                const size_t j0 = (size_t)i * kLanes;
-                hControl[j0] |= 2u;              // every lane of the wavefront advances THIS handle
-                for (size_t j = j0 + 1; j < j0 + kLanes; ++j) { hUtt[j] = hUtt[j0]; hState[j] = hState[j0]; hControl[j] = hControl[j0]; }
-            }
-        } else if (fillSparse) {
-            for (int i = n; i < nCtl; ++i) { hUtt[i] = hUtt[i % n]; hState[i] = hState[i % n]; hControl[i] = hControl[i % n]; }
-        }
+        unsigned int piece;
+        if (pull_refill(p, count - at, &piece)) return -1;
+        pull_fill(p, piece);
         const auto tb = now();
         tFill += ms(ta, tb);
         {
             std::lock_guard<std::mutex> lg(c->logMu);
             if (log_send(c)) return -1;
         }
-        HIP_TRY(hipMemcpyAsync(c->dCtl.ptr, c->hCtl.ptr, ctlBytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dCtl.ptr, c->hCtl.ptr, p.ctl.bytes(), hipMemcpyHostToDevice, c->stream));
         a.maxSamples = piece;
 #ifdef KLATT_STAMPS
         static unsigned long long* dStamps = nullptr;
         if (!dStamps) HIP_TRY(hipMalloc(&dStamps, 32 * 8));
         HIP_TRY(hipMemsetAsync(dStamps, 0, 32 * 8, c->stream));
-        a.debug = groups == 1 ? dStamps : nullptr;
+        a.debug = plan.groups == 1 ? dStamps : nullptr;
 #endif
         HIP_TRY(hipEventRecord(c->kernelStart, c->stream));
-        if (g_liveLayout == 0) {
-            if (launch<true, true>(a, mode, groups, c->stream)) return -1;
-        } else {
-            // one workgroup per CU while they all fit (16-sample hand-overs), else two per CU (8-sample hand-overs), as for batches
-            if (replicate ? launch_systolic<true, 16, 1, true, true, false, true>(a, mode, groups, c->stream)      // the LONE instantiation: 64 replicas of one handle
-                : (groups <= g_liveCus ? launch_systolic<true, 16, 1, true, true>(a, mode, groups, c->stream)
-                                       : launch_systolic<true, KLATT_NOISY_CH, 2, true, true>(a, mode, groups, c->stream))) return -1;
-        }
+        if (pull_launch(p, a)) return -1;
         HIP_TRY(hipEventRecord(c->kernelStop, c->stream));
 #ifdef KLATT_STAMPS
         if (a.debug) {
@@ -1596,7 +1588,7 @@ int streams_synthesize(Stream* const* ss, int n, unsigned int count, sample* con
             for (int k = 0; k < 32; ++k) g_streamStamps[k] += h[k];
         }
 #endif
-        HIP_TRY(hipMemcpyAsync(c->hResult.ptr, c->dResult.ptr, (size_t)(replicate ? nCtl : n) * sizeof(UttResult), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->hResult.ptr, c->dResult.ptr, (size_t)plan.nResults * sizeof(UttResult), hipMemcpyDeviceToHost, c->stream));
         if (piece < count || joined) {       // a call in pieces: this piece's columns into the joined rows
             if ((padded * n > c->dPcmJoin.cap && live_wait_exports(c, true)) || c->dPcmJoin.reserve(padded * n)) return -1;
             HIP_TRY(hipMemcpy2DAsync(c->dPcmJoin.ptr + at, padded * sizeof(int16_t), c->dPcm.ptr, padded * sizeof(int16_t), (size_t)piece * sizeof(int16_t), n,
@@ -1604,23 +1596,11 @@ int streams_synthesize(Stream* const* ss, int n, unsigned int count, sample* con
             joined = true;
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
-        {
-            std::lock_guard<std::mutex> lg(c->logMu);      // everything sent has arrived: an empty log starts over
-            if (c->logSent == c->logTail) c->logSent = c->logTail = 0;
-        }
+        { std::lock_guard<std::mutex> lg(c->logMu); c->log.arrived(); }
         float kms = 0.0f;
         (void)hipEventElapsedTime(&kms, c->kernelStart, c->kernelStop);
         c->lastKernelMs += kms; c->lastLaunches++;
-        for (int i = 0; i < n; ++i) {
-            Stream* s = ss[i];
-            const UttResult& r = c->hResult.ptr[(size_t)i * rep];
-            if (r.produced > piece || r.framesTaken > s->ringCount) { set_error("kernel produced %u > %u (took %u frames of %u)", r.produced, piece, r.framesTaken, s->ringCount); return -1; }
-            s->purgePending = false;
-            s->ringHead = (s->ringHead + r.framesTaken) & (kRing - 1);
-            s->ringCount -= r.framesTaken;
-            s->lastIndex = r.lastIndex;
-            c->done[i] += r.produced;
-        }
+        if (pull_apply(p, piece)) return -1;
         at += piece;
         tRun += ms(tb, now());
     }
@@ -1638,46 +1618,7 @@ int streams_synthesize(Stream* const* ss, int n, unsigned int count, sample* con
     if (any && outs) {
         if (n == 1) {
             HIP_TRY(hipMemcpy(outs[0], pcm, (size_t)c->done[0] * sizeof(int16_t), hipMemcpyDeviceToHost));
-        } else {
-            // whole rows in pieces of about 16 MB through two pinned buffers; piece k + 1 is in flight while the
-            // rows of piece k are handed to their callers
-            const size_t rowsPerPiece = std::max<size_t>(1, (8u << 20) / padded);
-            if (c->bounce.ensure(rowsPerPiece * padded * sizeof(int16_t))) return -1;
-            const size_t rows = lastWithData + 1, nPieces = (rows + rowsPerPiece - 1) / rowsPerPiece;
-            auto issue = [&](size_t k) -> int {
-                const size_t r0 = k * rowsPerPiece, r1 = std::min(rows, r0 + rowsPerPiece);
-                HIP_TRY(hipMemcpyAsync(c->bounce.buf[k & 1], pcm + r0 * padded, (r1 - r0) * padded * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(hipEventRecord(c->bounce.ev[k & 1], c->stream));
-                return 0;
-            };
-            if (issue(0)) return -1;
-            for (size_t k = 0; k < nPieces; ++k) {
-                if (k + 1 < nPieces && issue(k + 1)) return -1;
-                HIP_TRY(hipEventSynchronize(c->bounce.ev[k & 1]));
-                const size_t r0 = k * rowsPerPiece, r1 = std::min(rows, r0 + rowsPerPiece);
-                const int16_t* src = static_cast<const int16_t*>(c->bounce.buf[k & 1]);
-                auto rows_out = [&](size_t b0, size_t b1) {
-                    for (size_t i = b0; i < b1; ++i)
-                        if (c->done[i]) memcpy(outs[i], src + (i - r0) * padded, (size_t)c->done[i] * sizeof(int16_t));
-                };
-                // a piece of several megabytes is handed out by four threads: one thread's memcpy (about 20 GB/s) is slower than the copy over PCIe
-                constexpr int kHands = 4;
-                const size_t share = (r1 - r0 + kHands - 1) / kHands;
-                std::thread hands[kHands - 1];
-                int started = 0;
-                if ((r1 - r0) * padded * sizeof(int16_t) >= (4u << 20)) {
-                    try {
-                        for (; started < kHands - 1; ++started) {
-                            const size_t b0 = std::min(r1, r0 + (started + 1) * share), b1 = std::min(r1, b0 + share);
-                            hands[started] = std::thread(rows_out, b0, b1);
-                        }
-                    } catch (const std::system_error&) {}
-                }
-                rows_out(r0, started ? std::min(r1, r0 + share) : r1);
-                for (int t = 0; t < started; ++t) hands[t].join();
-                if (started && started < kHands - 1) rows_out(std::min(r1, r0 + (started + 1) * share), r1);     // what the threads that did not start would have done
-            }
-        }
+        } else if (pull_hand_out(c, pcm, padded, lastWithData + 1, outs)) return -1;
     }
     if (trace)
         fprintf(stderr, "[speechPlayer/live] %d handles x %u in %d launch(es): control block + ring refill %.2f ms | log + upload + kernel (%.2f ms) + results %.2f ms | PCM to host %.2f ms | before %.2f ms\n",
@@ -1727,7 +1668,7 @@ speechPlayer_handle_t speechPlayer_initialize(int sampleRate)
     if (dev < 0) return nullptr;
     Stream* s = new Stream;
     s->sampleRate = sampleRate;
-    s->mode = g_liveMode;
+    s->mode = g_liveOptions.snapshot().mode;
     s->device = dev;
     if (stream_init_device(s)) { delete s; return nullptr; }
     std::lock_guard<std::mutex> g(g_tableMutex);
@@ -1789,7 +1730,7 @@ void speechPlayer_terminate(speechPlayer_handle_t playerHandle)
         std::lock_guard<std::mutex> g(c->mu);
         ring_drop(c, s);                        // its entries in the log go nowhere
         c->freeSlots.push_back(s->slot);        // state block and ring are the next handle's (zeroed at its initialize, in stream order)
-        if (g_liveTrim && hipSetDevice(s->device) == hipSuccess) arena_trim(c);
+        if (g_liveOptions.snapshot().trim && hipSetDevice(s->device) == hipSuccess) arena_trim(c);
     }
     delete s;
 }
@@ -1809,22 +1750,11 @@ int speechPlayer_setNoiseSeed(speechPlayer_handle_t playerHandle, unsigned int s
 int speechPlayer_setGlobalOption(const char* name, int value)
 {
     begin_call();
-    if (name && !strcmp(name, "live_layout")) { g_liveLayout = value ? 1 : 0; return 0; }
-    // "live_cus": how many workgroups of live handles count as one per CU (0: the device's CU count).  Beyond it a pull of live handles
-    // takes the two-workgroups-per-CU instantiation of the stream kernel -- on a 256-CU device from 16 385 handles on; a small value
-    // lets a test (or a small device) reach that kernel with a few hundred handles.
-    if (name && !strcmp(name, "live_cus")) { g_liveCus = value < 0 ? 0 : value; g_liveCusForced = value > 0; return 0; }
-    // "live_replicate": 1 (default) a handle pulled alone is advanced in all 64 lanes of its wavefront (streams_synthesize); 0: in one lane
-    // "live_mode": the arithmetic mode of handles created from now on -- 0 (default) MODE_EXACT, 1 MODE_FAST (fused multiply-adds in the filters)
-    if (name && !strcmp(name, "live_mode")) { if (value != MODE_EXACT && value != MODE_FAST) { set_error("live_mode: 0 or 1"); return -1; } g_liveMode = value; return 0; }
-    if (name && !strcmp(name, "live_replicate")) { g_liveReplicate = value ? 1 : 0; return 0; }
-    // "live_alone": pulls of up to this many handles give every handle a wavefront of its own (default 1536; 1: only a handle pulled alone)
-    if (name && !strcmp(name, "live_alone")) { g_liveAlone = value < 1 ? 1 : (value > 65536 ? 65536 : value); return 0; }
-    // "live_trim": 1 = a device's arena of live handles (~100 KB of HBM per slot, grown by doubling) is released when the last handle on
-    // that device is terminated -- and now, on devices where none lives; 0 (default): it stays for the next handles.
-    if (name && !strcmp(name, "live_trim")) {
-        g_liveTrim = value ? 1 : 0;
-        if (g_liveTrim) {
+    // the "live_*" options: klatt_live.h says what each takes and how it is clamped
+    const int live = g_liveOptions.set(name, value);
+    if (live < 0) { set_error("live_mode: 0 or 1"); return -1; }
+    if (live == 0) {
+        if (!strcmp(name, "live_trim") && value) {      // ... and now, on devices where no handle lives
             std::vector<LiveContext*> all;
             { std::lock_guard<std::mutex> g(g_liveMutex); all = g_live; }
             for (size_t dev = 0; dev < all.size(); ++dev)
@@ -1998,7 +1928,7 @@ static FrameMeta queue_meta(const QueueCall& q, long long k)
     return m;
 }
 
-// The handles' mutexes held.  Every frame into its ring by way of the pinned log, or into the host queue (ring_takes).
+// The handles' mutexes held.  Every frame into its ring by way of the pinned log, or into the host queue (FrameQueue::takes_now).
 static int queue_host(const QueueCall& q, Stream* const* ss)
 {
     const double* frames = static_cast<const double*>(q.frames);
@@ -2012,13 +1942,13 @@ static int queue_host(const QueueCall& q, Stream* const* ss)
         for (long long k = k0; k < k1; ++k) {
             const FrameMeta meta = queue_meta(q, k);
             const double* p = (meta.flags & FRAME_NULL) ? nullptr : frames + k * kNumParams;
-            if (!ring_takes(s)) { overflow_push(s, p, meta); continue; }
-            if (log_append(c, s, p, meta, false)) return -1;
+            if (!s->q.takes_now()) { s->q.push_host(p, meta); continue; }
+            if (log_append(c, s, p, meta, s->q.claim(meta), false)) { s->q.unclaim(); return -1; }
             logged = true;
         }
         if (!logged) continue;
         bool eager;
-        { std::lock_guard<std::mutex> lg(c->logMu); eager = c->logTail - c->logSent >= kLogEager; }
+        { std::lock_guard<std::mutex> lg(c->logMu); eager = c->log.waiting() >= kLogEager; }
         if (eager && c->mu.try_lock()) {                 // no pull is running: the log need not wait for the next one
             std::lock_guard<std::mutex> lg(c->logMu);
             if (hipSetDevice(s->device) == hipSuccess) (void)log_send(c);
@@ -2061,13 +1991,13 @@ static int queue_device(const QueueCall& q, Stream* const* ss)
         for (long long k = k0; k < k1; ++k) {
             const FrameMeta meta = queue_meta(q, k);
             const bool null = (meta.flags & FRAME_NULL) != 0;
-            if (ring_takes(s)) {
+            if (s->q.takes_now()) {
                 LivePlace& p = c->hPlace.ptr[nPlace++];
                 p.meta = meta; p.row = null ? -1 : k; p.pad = 0;
-                p.target = ring_claim(s, meta);
+                p.target = s->slot * kRing + s->q.claim(meta);
             } else {
-                overflow_push(s, nullptr, meta);
-                if (!null) { c->hGatherIdx.ptr[nGather++] = k; fill.push_back(Fill{s, s->overflow.size() - 1}); }
+                s->q.push_host(nullptr, meta);
+                if (!null) { c->hGatherIdx.ptr[nGather++] = k; fill.push_back(Fill{s, s->q.overflow.size() - 1}); }
             }
         }
     }
@@ -2086,11 +2016,8 @@ static int queue_device(const QueueCall& q, Stream* const* ss)
         HIP_TRY(hipMemcpyAsync(c->hGatherRows.ptr, c->dGatherRows.ptr, nGather * kNumParams * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));            // the caller's memory has been read
-    {
-        std::lock_guard<std::mutex> lg(c->logMu);        // everything sent has arrived: an empty log starts over
-        if (c->logSent == c->logTail) c->logSent = c->logTail = 0;
-    }
-    for (size_t j = 0; j < nGather; ++j) memcpy(fill[j].s->overflow[fill[j].at].p, c->hGatherRows.ptr + j * kNumParams, kNumParams * sizeof(double));
+    { std::lock_guard<std::mutex> lg(c->logMu); c->log.arrived(); }
+    for (size_t j = 0; j < nGather; ++j) memcpy(fill[j].s->q.overflow[fill[j].at].p, c->hGatherRows.ptr + j * kNumParams, kNumParams * sizeof(double));
     return 0;
 }
 

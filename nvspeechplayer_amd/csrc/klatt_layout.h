@@ -1,6 +1,7 @@
-// klatt_layout.h -- the layouts that the host's track planner (klatt_trackplan.h) and the kernels (klatt_device.h, klatt_tracks.h,
-// klatt_direct.h, klatt_plan.h) share: a frame's meta word, the track block, a direct job.  Plain C++: no HIP include, so a native
-// test can hold the planner to account on any machine.  klatt_device.h includes it; the kernels see what they always saw.
+// klatt_layout.h -- the layouts that the host's track planner (klatt_trackplan.h), the live handles' host half (klatt_live.h) and the
+// kernels (klatt_device.h, klatt_tracks.h, klatt_direct.h, klatt_plan.h) share: a frame's meta word, an utterance's descriptor and
+// result, the track block, a direct job.  Plain C++: no HIP include, so a native test can hold the host code to account on any
+// machine.  klatt_device.h includes it; the kernels see what they always saw.
 #pragma once
 
 #include <stdint.h>
@@ -24,6 +25,22 @@ struct FrameMeta {           // 16 B per frame; with the 376-B parameter vector:
     uint32_t fadeSamples;    // already clamped to >= 1 (reference src/speechPlayer.cpp:36)
     int32_t userIndex;
     uint32_t flags;
+};
+
+struct UttDesc {             // 32 B per utterance
+    long long frameStart;    // first frame (index into frames / meta)
+    long long outStart;      // sample offset in the PCM pool, multiple of kTile
+    uint32_t nFrames;
+    uint32_t seed;
+    uint32_t flags;          // UTT_NEEDS_NOISE: some frame has a non-zero (or non-finite) noise gain
+    uint32_t length;         // samples this utterance produces (closed form, host-computed)
+};
+
+struct UttResult {           // written by the kernel
+    uint32_t produced;       // samples written by this launch
+    uint32_t framesTaken;    // frames dequeued by this launch
+    int32_t lastIndex;
+    uint32_t drained;        // 1: the queue ran dry (short count)
 };
 
 // ---- tracks (klatt_tracks.h) ---------------------------------------------------------------------------------

@@ -362,3 +362,58 @@ def test_export_equals_host_pull(ref):
         L.speechPlayer_setGlobalOption(b"live_trim", 0)
         for s in (R, E, F):
             s.close()
+
+
+def test_options_set_from_another_thread_while_pulls_run(ref):
+    """speechPlayer_setGlobalOption from a second thread while the first pulls: a pull takes one snapshot of the live options on entry
+    and finishes under it (a control block laid out for one kernel is never launched on another).  Six handles, one ref.ipa_case and
+    one seed each; the second thread turns "live_alone" 1 / 1536, "live_replicate" 0 / 1 and "live_layout" 0 / 1 over and over; 1000
+    samples per pull until every handle has run dry.  PCM and index marks against one oracle player each, sample for sample."""
+    import threading
+    import nvspeechplayer_amd as eng
+    n = 6
+    players = [eng.SpeechPlayer(22050, noiseSeed=900 + k) for k in range(n)]
+    oracles = [oracle.OraclePlayer(22050, seed=900 + k) for k in range(n)]
+    for k in range(n):
+        for j, (fr, m, f) in enumerate(ref.ipa_case(3 * k + 1)):
+            players[k].queueFrameSamples(None if fr is None else eng.Frame.from_array(fr), m, f, j)
+            oracles[k].queue(fr, m, f, j)
+    stop = threading.Event()
+
+    def set_options():
+        i = 0
+        while not stop.is_set():
+            eng.setGlobalOption("live_alone", 1536 if i & 1 else 1)
+            eng.setGlobalOption("live_replicate", (i >> 1) & 1)
+            eng.setGlobalOption("live_layout", (i >> 2) & 1)
+            i += 1
+
+    t = threading.Thread(target=set_options)
+    got, exp, dry = [[] for _ in range(n)], [[] for _ in range(n)], [False] * n
+    try:
+        t.start()
+        group = eng.LiveGroup(players)
+        out = np.zeros((n, 1000), np.int16)
+        for pull in range(60):
+            produced = group.pull(1000, out).copy()
+            for k in range(n):
+                got[k].append(out[k, :produced[k]].copy())
+                exp[k].append(oracles[k].synthesize(1000))
+                assert players[k].getLastIndex() == oracles[k].last_index(), (pull, k)
+                dry[k] = dry[k] or produced[k] < 1000
+            if all(dry):
+                break
+    finally:
+        stop.set()
+        t.join()
+        eng.setGlobalOption("live_alone", 1536)
+        eng.setGlobalOption("live_replicate", 1)
+        eng.setGlobalOption("live_layout", 1)
+        for p in players:
+            p.close()
+        for o in oracles:
+            o.close()
+    assert all(dry), dry
+    for k in range(n):
+        g, e = np.concatenate(got[k]), np.concatenate(exp[k])
+        assert len(g) == len(e) and len(g) > 0 and np.array_equal(g, e), (k, len(g), len(e), int(np.count_nonzero(g[:len(e)] != e[:len(g)])))

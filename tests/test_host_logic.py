@@ -302,3 +302,39 @@ def test_track_planning_and_pool_under_thread_sanitizer(tmp_path):
     assert out.startswith("ok ") and "ThreadSanitizer" not in out and "FAILED" not in out, out
     taken = [int(n) for n in re.findall(r": (\d+)$", out, flags=re.M)]
     assert len(taken) == TRACK_PLAN_BRANCHES and min(taken) > 0, out
+
+
+LIVE_BRANCHES = 6             # the branches tests/native/check_live.cpp counts; one reached zero times fails the program itself
+
+
+def test_live_handles_host_half_under_sanitizers(tmp_path):
+    """The host half of the live handles (csrc/klatt_live.h: a handle's ring and host queue, the log's indices, the plan of a pull and
+    its control block, the live options) as a stand-alone program, tests/native/check_live.cpp, under AddressSanitizer + UBSan: the queue
+    against a deque and a consumer driven as the engine's pull loop drives it, the log over 8 entries, the plan as a written-out table,
+    every option's clamps.  Nothing loaded into python is run under a sanitizer."""
+    exe = str(tmp_path / "check_live")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "native", "check_live.cpp"), "-o", exe])
+    out = run_check_track_plan(exe)
+    assert out.startswith("ok ") and "runtime error" not in out and "AddressSanitizer" not in out and "FAILED" not in out, out
+    taken = [int(n) for n in re.findall(r": (\d+)$", out, flags=re.M)]
+    assert len(taken) == LIVE_BRANCHES and min(taken) > 0, out
+
+
+def test_live_options_under_thread_sanitizer(tmp_path):
+    """The same program under ThreadSanitizer: four threads set live options in a loop while two take 10^5 snapshots each -- no report,
+    and every snapshot holds values the setter can produce.  Built with the clang++ that hipcc compiles with, as the track planner's
+    program is.  Skips only where ThreadSanitizer itself refuses to start (a memory layout it does not know), never on a report."""
+    import shutil
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    clang = os.path.join(subprocess.check_output([os.path.join(os.path.dirname(os.path.realpath(hipcc)), "hipconfig"), "--hipclangpath"]).decode().strip(), "clang++")
+    assert os.path.exists(clang), clang
+    exe = str(tmp_path / "check_live_tsan")
+    subprocess.check_call([clang, "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=thread", "-fno-omit-frame-pointer",
+                           "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "native", "check_live.cpp"), "-o", exe])
+    out = run_check_track_plan(exe)
+    if "unexpected memory mapping" in out and "ThreadSanitizer: data race" not in out and not out.startswith("ok "):
+        pytest.skip("ThreadSanitizer does not start on this kernel's memory layout")
+    assert out.startswith("ok ") and "ThreadSanitizer" not in out and "FAILED" not in out, out
+    taken = [int(n) for n in re.findall(r": (\d+)$", out, flags=re.M)]
+    assert len(taken) == LIVE_BRANCHES and min(taken) > 0, out
