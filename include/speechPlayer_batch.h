@@ -46,6 +46,12 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch);
  * which the stages with the frame state machine run faster; 2: the direct stages always; 0: never).
  * "quiet_last" (1, default: a launch queues the quiet groups' kernels behind the noisy groups', whose few long workgroups then start first;
  * 0: in front; read by every launch).
+ * "dead_terms" (1, default: a wavefront of the tracked group none of whose utterances has voice turbulence, aspiration or a first
+ * parallel resonator that contributes -- voiceTurbulenceAmplitude / aspirationAmplitude +0.0 in every frame; pa1 zero with pb1 in
+ * [1, 1e6], |pf1| <= 1e6, |fricationAmplitude| and |preFormantGain| <= 1e30 in every frame: all speech of the built-in producer's
+ * phoneme table has no turbulence and no pa1 -- runs stage bodies without those terms, which add exactly nothing; 0: every wavefront
+ * runs the general bodies.  Same PCM either way.  speechPlayer_batch_kernelInfo reports how many wavefronts of the last launch did, as
+ * the stages counted them -- before a batch's first launch: how many will, by the plan and the option as it stands.)
  * "direct_lean" (the direct stages' residency: 1 two workgroups per CU, 0 one, -1, default: the engine's choice by mode, size and
  * whether the resident batch's direct group is time-aligned).
  * Read by:
@@ -60,7 +66,7 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch);
  *   "tracks"                               the next set call (whether tracks are planned) and every launch: 0 runs a planned
  *                                          tracked group on the stages with the frame state machine; 1 after a set call under 0
  *                                          finds no tracks and changes nothing.
- *   "direct_lean", "quiet_last"            every launch.
+ *   "direct_lean", "quiet_last", "dead_terms"   every launch.
  *   "pitch_table_mb", "source_table_mb", "source_lane_lists"   every export that builds the table they bound.
  * No option, whenever it is changed, changes the PCM of MODE_EXACT, the lengths or the index marks; MODE_FAST stays within its
  * tolerance whichever kernel runs (the direct stages advance the coefficients of a fade by recurrences, re-seeded exactly at every

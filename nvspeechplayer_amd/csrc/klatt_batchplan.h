@@ -61,7 +61,7 @@ inline void classify_list(const Meta* meta, const Facts* facts, long long n, uin
     for (long long k = 0; k < n; ++k)
         if (!(meta[k].flags & FRAME_NULL)) fl |= facts[k].flags;
     const bool finite = !(fl & FACT_NONFINITE), needsNoise = (fl & FACT_NOISE) || !finite;
-    flags = needsNoise ? UTT_NEEDS_NOISE : (!(fl & FACT_NASAL) ? UTT_NO_NASAL : 0u);
+    flags = (needsNoise ? UTT_NEEDS_NOISE : (!(fl & FACT_NASAL) ? UTT_NO_NASAL : 0u)) | (fl & kUttPresent);      // (FACT_* and UTT_* of the present terms are the same bits)
     shape = finite ? (!(fl & FACT_UNBOUNDED) ? 3 : 1) : 0;
 }
 
@@ -332,6 +332,28 @@ inline LanePacking pack_lanes(long long nUtt, FlagsOf flagsOf, const uint32_t* l
     }
     fill_sparse_wavefronts(order, p.nQuietSlots, width);
     return p;
+}
+
+// What the flat stages will decide (klatt_systolic.h), from the plan: of the tracked group's wavefronts -- order[first, first + n) in
+// wavefronts of `width` slots -- how many run without parallel 1 [0], without turbulence [1], without the aspiration generator [2]: a term
+// goes when no utterance of the wavefront (replica lanes name one, empty slots none) has it present.  `built`: the bodies the kernel
+// was compiled with (KLATT_DEAD_TERMS: 1 without parallel 1, 2 without turbulence, 4 without turbulence and the generator).
+template <class FlagsOf>
+inline void dead_wave_counts(const uint32_t* order, long long first, long long n, FlagsOf flagsOf, int built, long long counts[3], int width = kLanes)
+{
+    counts[0] = counts[1] = counts[2] = 0;
+    for (long long w = first; w < first + n; w += width) {
+        uint32_t present = 0;
+        bool any = false;
+        for (long long s = w; s < std::min(w + width, first + n); ++s)
+            if (order[s] != kNoUtt) { present |= flagsOf(order[s]); any = true; }
+        if (!any) continue;
+        const bool noTurb = !(present & UTT_TURBULENCE), noAsp = noTurb && !(present & UTT_ASPIRATION);
+        const int body = ((built & 4) && noAsp) ? 2 : (((built & 2) && noTurb) ? 1 : 0);
+        counts[0] += ((built & 1) && !(present & UTT_PARALLEL1)) ? 1 : 0;
+        counts[1] += body >= 1 ? 1 : 0;
+        counts[2] += body >= 2 ? 1 : 0;
+    }
 }
 
 }  // namespace klatt

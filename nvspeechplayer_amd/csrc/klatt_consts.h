@@ -13,7 +13,13 @@ constexpr uint32_t UTT_NEEDS_NOISE = 1u;  // UttDesc.flags
 constexpr uint32_t UTT_NO_NASAL = 2u;     // UttDesc.flags: caNP == 0 throughout, N0/NP finite and stable (klatt_lanepipe.h)
 constexpr uint32_t UTT_TRACKED = 4u;      // UttDesc.flags: noisy, every parameter finite, tracks planned
 constexpr uint32_t UTT_DIRECT = 8u;       // UttDesc.flags: noisy, every parameter finite and in the range of klatt_math.h, no tracks: direct stages (klatt_direct.h)
-constexpr int kUttKindShift = 8;          // UttDesc.flags bits 8..31 of a tracked utterance: the entry kinds (klatt_tracks) whose values change after the first sample
+// UttDesc.flags bits 4..6: terms that are PRESENT somewhere in the utterance's frame list (FACT_* of the same name, OR-ed over the list).  A flat
+// stage whose wavefront holds no live lane with the bit runs a body without the term (klatt_systolic.h; option "dead_terms").
+constexpr uint32_t UTT_TURBULENCE = 16u;  // voiceTurbulenceAmplitude is not +0.0 in every frame
+constexpr uint32_t UTT_ASPIRATION = 32u;  // aspirationAmplitude is not +0.0 in every frame
+constexpr uint32_t UTT_PARALLEL1 = 64u;   // parallel resonator 1 contributes, or might not stay finite
+constexpr uint32_t kUttPresent = UTT_TURBULENCE | UTT_ASPIRATION | UTT_PARALLEL1;
+constexpr int kUttKindShift = 8;         // UttDesc.flags bits 8..31 of a tracked utterance: the entry kinds (klatt_tracks) whose values change after the first sample
                                           // of its first fade -- a kind outside the mask of every lane of a wavefront is loaded once and never again (flat stages)
 
 // FrameFacts.flags (klatt_plan.h)
@@ -21,5 +27,8 @@ constexpr uint32_t FACT_NOISE = 1u;        // a noise gain is non-zero, or the p
 constexpr uint32_t FACT_NONFINITE = 2u;    // some parameter is NaN or infinite
 constexpr uint32_t FACT_NASAL = 4u;        // the nasal pair is coupled in, or could not be skipped safely
 constexpr uint32_t FACT_UNBOUNDED = 8u;    // a frequency or bandwidth outside the range of klatt_math.h, or a negative bandwidth (the direct stages)
+constexpr uint32_t FACT_TURBULENCE = UTT_TURBULENCE;   // parameter 3 is not bit-for-bit +0.0
+constexpr uint32_t FACT_ASPIRATION = UTT_ASPIRATION;   // parameter 6 is not bit-for-bit +0.0
+constexpr uint32_t FACT_PARALLEL1 = UTT_PARALLEL1;     // pa1 is non-zero, or parallel resonator 1's output may not be finite (klatt_plan.h, shape_flags)
 
 }  // namespace klatt

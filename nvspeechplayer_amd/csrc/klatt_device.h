@@ -148,6 +148,8 @@ struct KernelArgs {
     double negPiOverSr;          // -pi/sr     (reference src/speechWaveGenerator.cpp:116)
     double twoPiOverSr;          // (2*pi)/sr  (reference src/speechWaveGenerator.cpp:118)
     unsigned long long* debug;   // diagnostic builds only (KLATT_STAMPS): per-wave cycle sums; nullptr otherwise
+    uint32_t* deadWaves;         // tracked launches: [3] wavefronts that ran without parallel 1 / without turbulence / without the aspiration generator; nullptr: not counted
+    uint32_t deadTerms;          // tracked launches: the UTT_* present bits a wavefront may act on (option "dead_terms"); 0: every wavefront runs the general bodies
 };
 
 // resonator r reads frequency parameter kResF[r] and bandwidth parameter kResB[r]

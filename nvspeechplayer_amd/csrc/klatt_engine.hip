@@ -575,6 +575,9 @@ struct Batch {
     hipStream_t side[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // the other groups run beside the last one (batch_launch)
     hipEvent_t forkEvent = nullptr, join[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int quietLast = 1;                     // option "quiet_last": the quiet groups are launched after the noisy ones (batch_launch)
+    int deadTerms = 1;                     // option "dead_terms": a flat wavefront none of whose lanes has a term (UTT_TURBULENCE .. UTT_PARALLEL1) runs a body without it; 0: the general bodies
+    DeviceBuffer<uint32_t> dDeadWaves;     // [3] the last tracked launch's wavefronts without parallel 1 / turbulence / the aspiration generator (speechPlayer_batch_kernelInfo)
+    long long planDeadWaves[3] = {0, 0, 0};   // ... and what the plan says they will be (dead_wave_counts, klatt_batchplan.h): reported until the batch has been launched
     long long nUtt = 0, nFrames = 0, nSlots = 0;   // nFrames: frames resident in HBM (the lists')
     long long nLists = 0, nFramesSpoken = 0;       // frame lists of the batch; frames the utterances queue (sum over utterances of their list's)
     std::vector<long long> uttFrameStart;          // [nUtt] first frame of the utterance's list
@@ -1009,17 +1012,21 @@ int batch_launch(Batch* b)
         t.negPiOverSr = a.negPiOverSr; t.twoPiOverSr = a.twoPiOverSr;
         const long long tg = b->nJobs;     // one workgroup per track
         if (tg > 0x7FFFFFFF) { set_error("too many tracks: %lld", b->nJobs); return -1; }
+        if (b->dDeadWaves.reserve(3)) return -1;
+        HIP_TRY(hipMemsetAsync(b->dDeadWaves.ptr, 0, 3 * sizeof(uint32_t), st));
         hipLaunchKernelGGL(klatt_tracks, dim3((unsigned)tg), dim3(kLanes * kTrackWaves), 0, st, t);
         HIP_TRY(hipGetLastError());
         a.order = b->dOrder.ptr + b->nQuiet; a.nSlots = nTr;
         a.flatRef = b->dFlatRef.ptr; a.sourceRef = b->dSourceRef.ptr; a.track = b->dTrack.ptr;
         a.trackBytes = (uint32_t)std::min<unsigned long long>(((unsigned long long)b->trackEntries + kTrackPad) * sizeof(double2), 0xFFFFFFFFull);
+        // the terms a wavefront may drop (read by every launch, like "tracks"), and how many did (counters zeroed ahead of klatt_tracks)
+        a.deadWaves = b->dDeadWaves.ptr; a.deadTerms = b->deadTerms ? kUttPresent : 0u;
         const GroupPlan pl = plan_group(b->layout, true, b->nSlots, nTr + nNoisy, b->cus);
         const long long g = (nTr + kLanes - 1) / kLanes;
         // flat stages keep nothing but the pipes and the PCM tile in LDS: 16-sample hand-overs fit two workgroups per CU (70 KB each)
         if (pl.chunk == 8 ? launch_systolic<true, KLATT_FLAT_CH, KLATT_FLAT_WPS, true, false, true>(a, b->mode, g, st)
                           : launch_systolic<true, 16, 1, true, false, true>(a, b->mode, g, st)) return -1;
-        a.flatRef = nullptr; a.sourceRef = nullptr; a.track = nullptr;
+        a.flatRef = nullptr; a.sourceRef = nullptr; a.track = nullptr; a.deadWaves = nullptr; a.deadTerms = 0u;
     }
     if (nDir > 0) {
         hipStream_t st = next_stream();
@@ -2134,7 +2141,7 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch)
     b->dDense.release(); b->dDenseStart.release(); b->dFacts.release(); b->hFacts.release();
     b->dRecords.release(); b->dShapeTable.release(); b->dRep.release(); b->dMismatch.release();
     b->dFrames.release(); b->dMeta.release(); b->dUtt.release(); b->dOrder.release(); b->dPcm.release(); b->dResult.release();
-    b->dFloat.release(); b->dDebug.release(); b->dDigest.release(); b->bounce.release();
+    b->dFloat.release(); b->dDebug.release(); b->dDigest.release(); b->bounce.release(); b->dDeadWaves.release();
     b->dFlatRef.release(); b->dSourceRef.release(); b->dJobs.release(); b->dShapes.release(); b->dTrack.release();
     b->dDirectJobs.release(); b->dDirectFirst.release(); b->dDirectHdr.release(); b->dDirectRec.release();
     delete b;
@@ -2155,6 +2162,7 @@ int speechPlayer_batch_setOption(speechPlayer_batch_t batch, const char* name, i
     if (!strcmp(name, "layout")) { b->layout = value < 0 ? -1 : (value > 2 ? 1 : value); return 0; }
     // tracks: planned by setUtterances (set the option before it), used by the stage-parallel layouts
     if (!strcmp(name, "tracks")) { b->tracks = value ? 1 : 0; return 0; }
+    if (!strcmp(name, "dead_terms")) { b->deadTerms = value ? 1 : 0; return 0; }
     if (!strcmp(name, "track_budget_mb")) { b->trackBudgetMB = value < 0 ? 0 : value; return 0; }
     // direct: read by setUtterances (set the option before it); 0 never, 1 unless the lanes are time-aligned (default), 2 always
     if (!strcmp(name, "direct")) { b->direct = value < 0 ? 0 : (value > 2 ? 2 : value); return 0; }
@@ -2863,6 +2871,7 @@ static int set_commit(SetCall& c)
     b->nNoNasalUtt = lanes.nNoNasal;
     b->nQuiet = lanes.nQuietSlots; b->nNoNasal = lanes.nNoNasalSlots;      // (slots: the groups' utterances and the replicas that complete their sparse last wavefronts)
     b->nTracked = lanes.nTrackedUtt > 0 ? lanes.nTracked : 0; b->nTrackedUtt = lanes.nTrackedUtt;
+    dead_wave_counts(lanes.order.data(), lanes.nQuietSlots, b->nTracked, [&](uint32_t u) { return c.utt[u].flags; }, KLATT_DEAD_TERMS, b->planDeadWaves);
     b->nJobs = lanes.nTrackedUtt > 0 ? (long long)c.plan.jobs.size() : 0; b->trackEntries = lanes.nTrackedUtt > 0 ? (long long)c.plan.entries : 0;
     b->nDirect = c.nDirectUtt > 0 ? lanes.nDirectSlots : 0; b->nDirectUtt = c.nDirectUtt; b->nDirectFrames = (long long)c.scratch.directJobs.size();
     b->directAligned = c.nDirectUtt > 0 && c.directAligned;
@@ -3738,6 +3747,18 @@ int speechPlayer_batch_kernelInfo(speechPlayer_batch_t batch, int* info, int nIn
         info[18] = (int)std::min<long long>(b->nDirectFrames * (long long)(kDirectEntries * sizeof(double2) + kDirectStages * sizeof(DirectHdr)) >> 20, 0x7FFFFFFF);
         info[19] = 0;
     }
+    if (nInfo >= 23) {
+        // the LAST launch's wavefronts (one per workgroup and stage) that ran without parallel 1 / turbulence / the aspiration generator, counted
+        // by the stages themselves; before the first launch of a batch: what the plan says they will be under the option as it stands
+        uint32_t dead[3] = {0u, 0u, 0u};
+        if (b->launched && nTr > 0 && b->dDeadWaves.ptr) {
+            HIP_TRY(hipStreamSynchronize(b->stream));      // (every launch joins its side streams into this one)
+            HIP_TRY(hipMemcpy(dead, b->dDeadWaves.ptr, sizeof dead, hipMemcpyDeviceToHost));
+        } else if (nTr > 0 && b->deadTerms) {
+            for (int k = 0; k < 3; ++k) dead[k] = (uint32_t)std::min<long long>(b->planDeadWaves[k], 0x7FFFFFFFll);
+        }
+        for (int k = 0; k < 3; ++k) info[20 + k] = (int)std::min<uint32_t>(dead[k], 0x7FFFFFFFu);
+    }
     return 0;
 }
 
@@ -3839,14 +3860,19 @@ void speechPlayer_internal_parallel(long long n, long long grain, void (*fn)(voi
     parallel_ranges(n, grain, [&](long long a, long long e) { fn(ctx, a, e); });
 }
 
+// (This view reports the four facts a set call ROUTES by, FACT_NOISE .. FACT_UNBOUNDED, and the hash.  The "present" facts of the flat stages'
+// dead terms travel in the same word inside the engine (klatt_consts.h); what they led to is reported per launch by speechPlayer_batch_kernelInfo.)
 long long speechPlayer_frameFacts(const speechPlayer_frame_t* frames, long long nFrames, int sampleRate, int onDevice, void* facts24)
 {
     begin_call();
     if (nFrames < 0 || (nFrames > 0 && (!frames || !facts24)) || sampleRate <= 0) { set_error("frameFacts: bad arguments"); return -1; }
     const double maxBw = 690.0 * sampleRate / M_PI, maxF = 9900.0 * sampleRate / (2.0 * M_PI);
     FrameFacts* const out = static_cast<FrameFacts*>(facts24);
+    constexpr uint32_t kRouting = FACT_NOISE | FACT_NONFINITE | FACT_NASAL | FACT_UNBOUNDED;
     if (!onDevice) {
-        parallel_ranges(nFrames, 1 << 13, [&](long long a, long long e) { for (long long k = a; k < e; ++k) out[k] = frame_facts(reinterpret_cast<const double*>(frames + k), maxF, maxBw); });
+        parallel_ranges(nFrames, 1 << 13, [&](long long a, long long e) {
+            for (long long k = a; k < e; ++k) { out[k] = frame_facts(reinterpret_cast<const double*>(frames + k), maxF, maxBw); out[k].flags &= kRouting; }
+        });
         return nFrames;
     }
     if (nFrames == 0) return 0;
@@ -3859,6 +3885,7 @@ long long speechPlayer_frameFacts(const speechPlayer_frame_t* frames, long long 
     hipLaunchKernelGGL(klatt_frame_facts, dim3(grid), dim3(256), 0, nullptr, dF.ptr, dO.ptr, nFrames, maxF, maxBw);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, dO.ptr, (size_t)nFrames * sizeof(FrameFacts), hipMemcpyDeviceToHost));
+    for (long long k = 0; k < nFrames; ++k) out[k].flags &= kRouting;
     return nFrames;
 }
 

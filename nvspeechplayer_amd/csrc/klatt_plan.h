@@ -39,6 +39,12 @@ KLATT_LAYOUT_HD inline bool fact_finite(double v)
     memcpy(&w, &v, 8);
     return (w & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
 }
+KLATT_LAYOUT_HD inline bool fact_plus_zero(double v)      // +0.0, bit for bit
+{
+    unsigned long long w;
+    memcpy(&w, &v, 8);
+    return w == 0ull;
+}
 KLATT_LAYOUT_HD inline double fact_abs(double v) { return v < 0 ? -v : v; }      // (NaN stays NaN: every test below is written to fail on it)
 // key n of the hash (splitmix64 of n: a constant wherever n is one)
 KLATT_LAYOUT_HD constexpr unsigned long long fact_key(int n)
@@ -87,6 +93,15 @@ KLATT_LAYOUT_HD inline uint32_t shape_flags(const double* p, double maxF, double
     if (p[23] != 0.0 || !(p[21] >= 1.0) || !(p[22] >= 0.0) || !(p[21] <= 1e6) || !(p[22] <= 1e6) ||
         !(fact_abs(p[13]) <= 1e6) || !(fact_abs(p[14]) <= 1e6) || !(fact_abs(p[5]) <= 1e30) || !(fact_abs(p[44]) <= 1e30))
         fl |= 4u;
+    // Terms of the flat stages that are nothing in every frame of a list (klatt_systolic.h runs bodies without them).  Turbulence and
+    // aspiration: the gain is +0.0 bit for bit -- the glottal wave 2 * phase - 1 is never -0, so adding a turbulence of +0 changes nothing;
+    // the aspiration generator goes only with both (nothing else reads its state).  Parallel resonator 1 enters the parallel sum FIRST, as
+    // (res(y) - y) * pa1 onto +0: with pa1 == 0 that is +0 + (+-0) == +0 while res(y) stays finite, for which the nasal pair's bounds serve
+    // (a stable pole pair, a bounded frequency, a bounded input y = frication * fricationAmplitude * preFormantGain).
+    if (!fact_plus_zero(p[3])) fl |= FACT_TURBULENCE;
+    if (!fact_plus_zero(p[6])) fl |= FACT_ASPIRATION;
+    if (p[37] != 0.0 || !(p[31] >= 1.0) || !(p[31] <= 1e6) || !(fact_abs(p[25]) <= 1e6) || !(fact_abs(p[24]) <= 1e30) || !(fact_abs(p[44]) <= 1e30))
+        fl |= FACT_PARALLEL1;
     // the direct stages evaluate exp / cos with klatt_math.h alone, whose range is |arg| <= 700 / 1e4: frequencies (parameters 7..14,
     // 25..30) and bandwidths (15..22, 31..36) bounded accordingly
     // -- and no bandwidth negative.  In MODE_FAST the direct stages advance a fading gain by constant increments (klatt_direct.h), so a

@@ -65,6 +65,12 @@ namespace klatt {
                                 // VGPRs instead of 256 and NO scratch instead of 128 bytes per lane (0: the test `stage == 2`, as before)
 #endif
 constexpr int kStages = 4;
+#ifndef KLATT_DEAD_TERMS
+#define KLATT_DEAD_TERMS 3      // flat launches: the bodies without a dead term that are built -- 1 the parallel stage without parallel 1, 2 the source stage without
+                                // turbulence, 4 the source stage without turbulence and the aspiration generator.  4 is not built: with it the kernel takes
+                                // 250 VGPRs (MODE_FAST 252) instead of 248, for cfg2 7.99 -> 7.97 ms, within the spread, and cfg3 6.57 -> 6.44
+                                // (profiles/dead_terms.txt; 256 of cfg2's 896 wavefronts have no aspiration: the producer puts a puff behind voiceless stops)
+#endif
 #ifndef KLATT_FLAT_SOURCE
 #define KLATT_FLAT_SOURCE 1     // flat launches: S0 is a flat stage too (0: the source stage of the noisy launches, with its frame state machine)
 #endif
@@ -899,13 +905,15 @@ __device__ __forceinline__ void stage_loop(int depth, int nIter, int nChunks, in
 // utterance's own sample count.)
 // USUAL: the entry kinds of the stage (bit e of its list) that usually change in speech -- the mixed chunks are compiled for this
 // set and for all kinds.  R: the type the stage keeps its coefficients, memories and gains in.
-template <int STAGE_, int NRES_, int NGAIN_, bool ANTI0_, uint32_t USUAL_ = 0, uint32_t USUAL2_ = 0, class R_ = sig_t>
+// SKIP: entry kinds (bit k: kind k) of the stage's part of a track that a body without a dead term leaves out of its list -- their
+// entries are still in the part, so flat2_switch counts them on its way to the kinds behind them.
+template <int STAGE_, int NRES_, int NGAIN_, bool ANTI0_, uint32_t USUAL_ = 0, uint32_t USUAL2_ = 0, class R_ = sig_t, uint32_t SKIP_ = 0>
 struct FlatDesc {
     using R = R_;
     static constexpr int STAGE = STAGE_;      // which part of a track the stage reads (klatt_device.h)
     static constexpr int NRES = NRES_, NGAIN = NGAIN_, NE = NRES_ + NGAIN_;
     static constexpr bool ANTI0 = ANTI0_;
-    static constexpr uint32_t USUAL = USUAL_, USUAL2 = USUAL2_;
+    static constexpr uint32_t USUAL = USUAL_, USUAL2 = USUAL2_, SKIP = SKIP_;
 };
 
 // ---- hand-overs of the flat stages: one workgroup barrier per chunk ------------------------------------------------------------------
@@ -997,6 +1005,11 @@ __device__ __forceinline__ void flat2_switch(FlatState2<FD>& f, const StageCtx& 
     uint32_t moving = 0, still = 0;            // entries of the stage's kinds before this one, among the moving / among the others
 #pragma unroll
     for (int e = 0; e < FD::NE; ++e) {
+        if constexpr (FD::SKIP != 0u) {      // the kinds left out between the previous kind of the list and this one (none of them is N0)
+#pragma unroll
+            for (int k = 0; k < kTrackEntries; ++k)
+                if (((FD::SKIP >> k) & 1u) && k < GE[e] && (e == 0 || k > GE[e - 1])) { const bool mv = (p.mask >> k) & 1u; moving += mv ? 1u : 0u; still += mv ? 0u : 1u; }
+        }
         const bool moves = (p.mask >> GE[e]) & 1u;
         f.idx[e] = (part + (moves ? hdr + moving : still)) * 16u;
         f.stride[e] = moves ? nMove * 16u : 0u;
@@ -1265,7 +1278,9 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
     int cand = wave;
     if (KLATT_PAIR && WPS == 2 && (NOISE || !NASAL)) {
         const uint32_t hw = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_REG_HW_ID: wave slot [3:0], SIMD [5:4]
-        cand = (int)((((hw >> 4) & 3u) + ((hw & 1u) ? 2u : 0u)) & 3u);
+        // KLATT_PAIR 1: S0 with the final stage, S1 with S3; 2: S0 with S1, the final stage with S3; 3: S0 with S3, S1 with the final stage
+        const uint32_t simd = (hw >> 4) & 3u, odd = hw & 1u;
+        cand = (int)(KLATT_PAIR == 2 ? (simd ^ odd) : KLATT_PAIR == 3 ? (simd ^ (odd ? 3u : 0u)) : ((simd + (odd ? 2u : 0u)) & 3u));
     }
     if (wave == 0) atomicMax(maxLenP, d.length);
     if (lane == 0) atomicOr(stageMaskP, 1u << cand);
@@ -1293,6 +1308,16 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
     auto noFadeAlt = [&](int, bool, bool) __attribute__((always_inline)) { return false; };
     auto nothing = [&](int) __attribute__((always_inline)) {};
     auto noChunk = [&]() __attribute__((always_inline)) {};
+    // Flat launches: the terms that are dead in EVERY live lane of this wavefront (replica lanes of a sparse wavefront carry their utterance's
+    // bits), among those the launch lets the stages act on (option "dead_terms"): wave-uniform, decided once, before the chunk loop --
+    // as the per-wavefront gate on the lanes' kinds (FlatState2::wmask) picks the chunk bodies for the usual kinds.
+    uint32_t deadSet = 0;
+    if (FLAT) {
+        const uint32_t mine = live ? d.flags : 0u;
+#pragma unroll
+        for (uint32_t bit = UTT_TURBULENCE; bit <= UTT_PARALLEL1; bit <<= 1) deadSet |= __any((mine & bit) != 0u) ? 0u : bit;
+        deadSet = (uint32_t)__builtin_amdgcn_readfirstlane((int)(deadSet & A.deadTerms));
+    }
 
     // hand-overs of the flat stages (BarrierSync above): pipe X = S0 -> S1, O = S1 -> final, A and B = S3 -> final
     auto make_sync = [&](auto, auto, auto, int, int, int) __attribute__((always_inline)) { return BarrierSync{}; };
@@ -1306,20 +1331,31 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
         // steady (glide).  What a dequeue reads (durations, index mark, the frame's two pitch values, the FlatRef) was loaded when the
         // previous frame was dequeued.
         if constexpr (FLAT) {
+            // DEAD (chosen once per wavefront from its live lanes' UTT_TURBULENCE / UTT_ASPIRATION): 1 -- no lane has turbulence: its gain and the
+            // open quotient, which gates nothing else, are not read and kind 21 is not in the list; 2 -- nor aspiration: the generator goes
+            // as well (the frication generator of the parallel stage steps a sub-sequence of its own: nothing else reads this state)
+            auto sourceStage = [&](auto deadTag) __attribute__((always_inline)) {
+            constexpr int DEAD = decltype(deadTag)::value;
+            constexpr bool NOTURB = DEAD >= 1;
 #if KLATT_FLAT_LAYOUT == 2
             // the source AND the head of the cascade: N0 (anti), NP mixed in by caNP (reference src/speechWaveGenerator.cpp:149-152)
-            using FD = FlatDesc<0, 2, 5, true, 0, 0, double>;
-            constexpr int GE[7] = {0, 1, 14, 20, 21, 22, 23};     // N0, NP | cur: caNP, - | vibratoPitchOffset, vibratoSpeed, turbulence, openQuotient, voiceAmplitude, aspirationAmplitude, preFormantGain
+            using FD = FlatDesc<0, 2, NOTURB ? 4 : 5, true, 0, 0, double, NOTURB ? (1u << 21) : 0u>;
+            constexpr int GE[7] = {0, 1, 14, 20, NOTURB ? 22 : 21, NOTURB ? 23 : 22, 23};     // N0, NP | cur: caNP, - | vibratoPitchOffset, vibratoSpeed, turbulence, openQuotient, voiceAmplitude, aspirationAmplitude, preFormantGain
             constexpr int CB = 2;                                 // f.cur[CB + k]: the source's parameters
-            constexpr uint32_t kUsualS0 = 0x67u, kAllS0 = 0x7Fu, kVibBit = 8u;      // usually: N0, NP, caNP, the amplitudes and the gain
+            constexpr uint32_t kUsualS0 = NOTURB ? 0x37u : 0x67u, kAllS0 = NOTURB ? 0x3Fu : 0x7Fu, kVibBit = 8u;      // usually: N0, NP, caNP, the amplitudes and the gain
             constexpr bool kHead = true;
 #else
-            using FD = FlatDesc<0, 0, 4, false, 0, 0, double>;
-            constexpr int GE[4] = {20, 21, 22, 23};     // cur: vibratoPitchOffset, vibratoSpeed, turbulence, openQuotient, voiceAmplitude, aspirationAmplitude, preFormantGain
+            using FD = FlatDesc<0, 0, NOTURB ? 3 : 4, false, 0, 0, double, NOTURB ? (1u << 21) : 0u>;
+            constexpr int GE[4] = {20, NOTURB ? 22 : 21, NOTURB ? 23 : 22, 23};     // cur: vibratoPitchOffset, vibratoSpeed, turbulence, openQuotient, voiceAmplitude, aspirationAmplitude, preFormantGain
             constexpr int CB = 0;
-            constexpr uint32_t kUsualS0 = 0xCu, kAllS0 = 0xFu, kVibBit = 1u;
+            constexpr uint32_t kUsualS0 = NOTURB ? 0x6u : 0xCu, kAllS0 = NOTURB ? 0x7u : 0xFu, kVibBit = 1u;
             constexpr bool kHead = false;
 #endif
+            constexpr int CA = CB + (NOTURB ? 2 : 4);             // f.cur[CA + k]: voiceAmplitude, aspirationAmplitude, preFormantGain
+            if (A.deadWaves && lane == 0) {
+                if (DEAD >= 1) atomicAdd(A.deadWaves + 1, 1u);
+                if (DEAD >= 2) atomicAdd(A.deadWaves + 2, 1u);
+            }
             bool staleNP = false;       // NP's `a` in its register predates the last rows (mixed chunks derive it on the fly)
             FlatState2<FD> f;
             flat2_init<FD>(f, live, d, X, GE);
@@ -1341,17 +1377,26 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
                     vibPhase = (vs != 0.0) ? adv : vibPhase;
                     vib = (sin(vibPhase * 6.283185307179586) * 0.06 * f.cur[CB + 0]) + 1.0;
                 }
-                const double turbGain = f.cur[CB + 2], openQ = f.cur[CB + 3], voiceAmp = f.cur[CB + 4], aspAmp = f.cur[CB + 5], preGain = f.cur[CB + 6];
+                const double voiceAmp = f.cur[CA + 0], aspAmp = f.cur[CA + 1], preGain = f.cur[CA + 2];
+                (void)aspAmp; (void)aspNoise; (void)noiseSt;      // (DEAD == 2 reads none of them)
                 pitchPhase = frac_toward_zero(div_by(ps.cur0 * vib, A.sampleRateF, A.invSampleRate) + pitchPhase);
                 double voice = (pitchPhase * 2.0) - 1.0;
-                aspNoise = noise_uniform(noiseSt) + 0.75 * aspNoise;
-                noiseSt = noise_step2(noiseSt, ninc2);
-                double asp = aspNoise * 0.2;
-                double turb = asp * turbGain;
-                turb = (pitchPhase >= openQ) ? turb : turb * 0.01;
-                voice += turb;
+                double asp = 0.0;
+                if constexpr (DEAD < 2) {
+                    aspNoise = noise_uniform(noiseSt) + 0.75 * aspNoise;
+                    noiseSt = noise_step2(noiseSt, ninc2);
+                    asp = aspNoise * 0.2;
+                }
+                if constexpr (!NOTURB) {
+                    const double turbGain = f.cur[CB + 2], openQ = f.cur[CB + 3];
+                    double turb = asp * turbGain;
+                    turb = (pitchPhase >= openQ) ? turb : turb * 0.01;
+                    voice += turb;
+                }
                 voice *= voiceAmp;
-                asp *= aspAmp;
+                // (without the generator: aspNoise * 0.2 * +0 is +-0, and so is the sum unless the voice is non-zero; the add stays, for
+                // voice * voiceAmplitude may be -0 and the reference's +0 + -0 is +0)
+                if constexpr (DEAD < 2) asp *= aspAmp;
                 const double src = asp + voice;
                 const double out = (src * preGain) * 0.5;
                 if constexpr (kHead) {
@@ -1488,6 +1533,10 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
                 res.produced = d.length; res.framesTaken = f.next; res.lastIndex = lastIndex; res.drained = 1u;
                 A.result[u] = res;
             }
+            };
+            if ((KLATT_DEAD_TERMS & 4) && (deadSet & (UTT_TURBULENCE | UTT_ASPIRATION)) == (UTT_TURBULENCE | UTT_ASPIRATION)) sourceStage(std::integral_constant<int, 2>{});
+            else if ((KLATT_DEAD_TERMS & 2) && (deadSet & UTT_TURBULENCE)) sourceStage(std::integral_constant<int, 1>{});
+            else sourceStage(std::integral_constant<int, 0>{});
         }
     } else if (stage == 0) {
         // ================= S0: frame + glottal source (+ aspiration noise) =================
@@ -1684,10 +1733,16 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
     } else if (FLAT && stage == 3) {
         // ================= flat S3: frication noise, parallel r1..r4 partial sum =================
         if constexpr (FLAT) {
-            using FD = FlatDesc<3, 4, 3, false, 0x77u>;                // usually parallel 1..3 and the gains
-            constexpr int GE[7] = {8, 9, 10, 11, 17, 18, 19};     // parallel 1..4 | cur: fricationAmplitude, preFormantGain, pa1..pa4
+            // NOP1: no live lane of the wavefront has parallel resonator 1 present (UTT_PARALLEL1): its term (res(y) - y) * pa1 is +-0 onto
+            // a sum that starts at +0, so the sum starts with parallel 2's term; the resonator, its memories and kind 8 are not there
+            auto parallel = [&](auto noP1Tag) __attribute__((always_inline)) {
+            constexpr bool NOP1 = decltype(noP1Tag)::value;
+            constexpr int NR = NOP1 ? 3 : 4;
+            using FD = FlatDesc<3, NR, 3, false, NOP1 ? 0x3Bu : 0x77u, 0, sig_t, NOP1 ? (1u << 8) : 0u>;      // usually parallel 1..3 and the gains
+            constexpr int GE[7] = {NOP1 ? 9 : 8, NOP1 ? 10 : 9, NOP1 ? 11 : 10, NOP1 ? 17 : 11, NOP1 ? 18 : 17, NOP1 ? 19 : 18, 19};     // parallel 1..4 | cur: fricationAmplitude, preFormantGain, pa1..pa4
             FlatState2<FD> f;
             flat2_init<FD>(f, live, d, X, GE);
+            if (NOP1 && A.deadWaves && lane == 0) atomicAdd(A.deadWaves + 0, 1u);
             sig_t fricNoise = 0;
             uint32_t noiseSt = noise_step(noise_first(nkey, ninc), ninc);     // frication: values 1, 3, 5, ...
             flat2_loop<FD, CH>(1, nIter, nChunks, stage, f, X, GE,
@@ -1696,25 +1751,40 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
                     const ResPre<sig_t> q0 = res_pre<MODE, ((SET >> 0) & 1u) != 0u>(f.ra[0], f.rb[0], f.rc[0], f.z1[0], f.z2[0]);
                     const ResPre<sig_t> q1 = res_pre<MODE, ((SET >> 1) & 1u) != 0u>(f.ra[1], f.rb[1], f.rc[1], f.z1[1], f.z2[1]);
                     const ResPre<sig_t> q2 = res_pre<MODE, ((SET >> 2) & 1u) != 0u>(f.ra[2], f.rb[2], f.rc[2], f.z1[2], f.z2[2]);
-                    const ResPre<sig_t> q3 = res_pre<MODE, ((SET >> 3) & 1u) != 0u>(f.ra[3], f.rb[3], f.rc[3], f.z1[3], f.z2[3]);
+                    constexpr int R3 = NR - 1;      // (the general body's fourth resonator)
+                    ResPre<sig_t> q3{};
+                    if constexpr (!NOP1) q3 = res_pre<MODE, ((SET >> 3) & 1u) != 0u>(f.ra[R3], f.rb[R3], f.rc[R3], f.z1[R3], f.z2[R3]);
                     fricNoise = (sig_t)noise_uniform(noiseSt) + (sig_t)0.75 * fricNoise;
                     noiseSt = noise_step2(noiseSt, ninc2);
                     const sig_t fric = fricNoise * (sig_t)0.3 * f.cur[0];
                     const sig_t y = (fric * f.cur[1]) * (sig_t)0.5;
                     const sig_t pa1 = f.cur[2], pa2 = f.cur[3], pa3 = f.cur[4], pa4 = f.cur[5];
-                    mid(q0, q1, q2, q3, y, pa1, pa2, pa3, pa4);
-                    sig_t par = 0;
-                    sig_t w = res_post<MODE>(q0, y, f.z1[0], f.z2[0]);
-                    par += (w - y) * pa1;
-                    w = res_post<MODE>(q1, y, f.z1[1], f.z2[1]);
-                    par += (w - y) * pa2;
-                    w = res_post<MODE>(q2, y, f.z1[2], f.z2[2]);
-                    par += (w - y) * pa3;
-                    w = res_post<MODE>(q3, y, f.z1[3], f.z2[3]);
-                    par += (w - y) * pa4;
-                    PIPE(pipeA, c, i) = y; PIPE(pipeB, c, i) = par;
+                    if constexpr (NOP1) {
+                        mid(q0, q1, q2, y, pa2, pa3, pa4);
+                        sig_t w = res_post<MODE>(q0, y, f.z1[0], f.z2[0]);
+                        sig_t par = (w - y) * pa2;
+                        w = res_post<MODE>(q1, y, f.z1[1], f.z2[1]);
+                        par += (w - y) * pa3;
+                        w = res_post<MODE>(q2, y, f.z1[2], f.z2[2]);
+                        par += (w - y) * pa4;
+                        PIPE(pipeA, c, i) = y; PIPE(pipeB, c, i) = par;
+                    } else {
+                        mid(q0, q1, q2, q3, y, pa1, pa2, pa3, pa4);
+                        sig_t par = 0;
+                        sig_t w = res_post<MODE>(q0, y, f.z1[0], f.z2[0]);
+                        par += (w - y) * pa1;
+                        w = res_post<MODE>(q1, y, f.z1[1], f.z2[1]);
+                        par += (w - y) * pa2;
+                        w = res_post<MODE>(q2, y, f.z1[2], f.z2[2]);
+                        par += (w - y) * pa3;
+                        w = res_post<MODE>(q3, y, f.z1[R3], f.z2[R3]);
+                        par += (w - y) * pa4;
+                        PIPE(pipeA, c, i) = y; PIPE(pipeB, c, i) = par;
+                    }
                 },
                 noChunk, make_sync(std::integral_constant<int, L::kBufs>{}, I0{}, I1{}, 0, 0, 4));
+            };
+            if ((KLATT_DEAD_TERMS & 1) && (deadSet & UTT_PARALLEL1)) parallel(std::true_type{}); else parallel(std::false_type{});
         }
     } else if (FLAT && (KLATT_FLAT_EXHAUSTIVE || stage == 2)) {
         // ================= flat final stage: r3, r2, r1 | parallel 5, 6, bypass | gain, clip, int16 -> PCM =================
