@@ -967,6 +967,66 @@ long long speechPlayer_batch_exportLpcResidualOf(speechPlayer_batch_t batch, con
 	int order, long long hop, long long phase, const void* deviceCoeff, int coeffFormat, int coeffCols, int col0, long long coeffStride, int what,
 	void* deviceOut, int format, long long rowStride, void* stream);
 /*
+ * Pitch ESTIMATED FROM THE SIGNAL (YIN) of a batch's PCM, or of a signal's rows, on the step grid of the other exports: per analysis frame
+ * the period, the fundamental, a periodicity measure and the voicing decision -- the one feature the LPCNet family and the classical front
+ * ends take that the other exports plus a matrix product cannot give.  speechPlayer_batch_exportSource states the TRUE fundamental of the
+ * clean synthesis; this export estimates it from a row that has been through a room, a noise mix, a codec or a tempo change, which is what a
+ * front end sees.  A row of L samples is read as the other exports of the PCM read it: an int16 s is (float)s / 32767.0f, a float32 is taken
+ * as it is, a sample outside 0 .. L-1 is +0 and nothing is loaded there.
+ *   per call  nWin = W, any integer in 32 .. 2048 (kPitchMaxWin); 2 <= lagMin < lagMax <= 1024 (kPitchMaxLag); threshold a finite double in
+ *             [0, 1]; hop > 0, phase >= 0; sampleRate > 0 serves the F0 field alone: the batch's own (exportPitch) or the argument
+ *             (exportPitchOf and the host statements), as exportResampledOf takes srcRate
+ *   steps     the spectrogram's grid, row for row: step j is centred on c = phase + j * hop; a row has ceil((L - phase) / hop) steps, 0 when
+ *             L <= phase
+ *   frame     N = W + lagMax; x[i] is sample c - floor(N / 2) + i for i = 0 .. N-1
+ *   difference   for tau = 1 .. lagMax: u(i) = x[i] - x[i + tau], ONE binary32 subtraction; term(i) = (double)u * (double)u, exact in
+ *             binary64; four chains c_j, j = i mod 4, each the sum from +0.0, in ascending i over 0 <= i < W, of its terms, one rounding an
+ *             addition (an fma does it); d(tau) = (c_0 + c_1) + (c_2 + c_3).  A chain that starts from +0.0 is never -0.0, so terms with
+ *             u == 0 may be skipped.  Inside the signal bound (finite, |x| <= 2^16) every value is finite
+ *   cumulative mean   s(0) = +0.0; s(tau) = s(tau - 1) + d(tau) in ascending tau; m(tau) = s(tau) > 0 ? (d(tau) * (double)tau) / s(tau) : 1.0,
+ *             one product and one division
+ *   choice    tau* is the lowest tau in lagMin .. lagMax with m(tau) < threshold and (tau == lagMax or !(m(tau + 1) < m(tau))): voiced = 1.
+ *             If there is none, voiced = 0 and tau* is the tau of the least m(tau) in the range, ties to the lowest tau.  Both rules are
+ *             minima under a total order: only the choice crosses lanes
+ *   refinement   if tau* - 1 >= 1 and tau* + 1 <= lagMax: with y0, y1, y2 = m at tau* - 1, tau*, tau* + 1, den = (y0 - y1) + (y2 - y1); if
+ *             den > 0: delta = (0.5 * (y0 - y2)) / den, used only if fabs(delta) <= 0.5.  In every other case delta = +0.0.
+ *             period = (double)tau* + delta
+ *   fields    `what` is a bit set; the fields come in this fixed order whatever the order of the bits: 1 F0 voiced ? (double)sampleRate /
+ *             period : +0.0; 2 PERIOD the period, always; 4 LAG tau* as a number; 8 APERIODICITY m(tau*); 16 VOICED 0 or 1; 32 CMND
+ *             m(lagMin .. lagMax), lagMax - lagMin + 1 values, for a tracker of the caller's own (Viterbi, pYIN).  nCols is their total
+ *   output    element (row, step, col) of [row][step][nCols]; format 0 float64, 1 float32 rounded once; +0 past a row's steps in the padded
+ *             form
+ * The definition is the function bodies of csrc/klatt_pitch.h, which the host and the device compile from one source.  Over the pool the
+ * result is a function of the batch's PCM: it depends on the mode and needs a synthesis launch.
+ * Known behaviour of the method: the first dip below the threshold may be a formant's, not the period's -- vowel i at 220 Hz and 22050 Hz has
+ * m = 0.11 at lag 95 beside the period of 100.2 samples --; the CMND field exists so that a tracker can decide otherwise.
+ * Out of scope: normalised cross-correlation and energies; smoothing or tracking across steps; octave-error correction; FFT or MFMA
+ * evaluation of the difference (their summation order is not the definition's); decimation inside the export (the chain is
+ * exportResampled to 16000 Hz, then the signal form); live handles; NodePlayer beyond speechPlayer_node_part.
+ *
+ * Host only, touch no device: the estimate above on `length` samples of plain PCM (speechPlayer_pcmPitch) or of a signal's row, int16
+ * (inFormat 0) or float32 (inFormat 1) (speechPlayer_signalPitch), out[step][nCols] float64 -- the statements the device is held to bit for
+ * bit.  Return steps * nCols; -1 on an unknown inFormat, length < 0 or above 2^44, a NULL input with length > 0, hop <= 0, phase < 0,
+ * sampleRate <= 0, nWin outside 32 .. 2048, lagMin < 2, lagMin >= lagMax, lagMax > 1024, a threshold outside [0, 1] or not finite, what 0 or
+ * with a bit above 32, a NULL out with steps > 0, and (signalPitch) a float32 sample that is not finite or above 2^16 in magnitude. */
+long long speechPlayer_pcmPitch(const sample* pcm, long long length, int sampleRate, int nWin, int lagMin, int lagMax, double threshold,
+	long long hop, long long phase, int what, double* out);
+long long speechPlayer_signalPitch(const void* x, int inFormat, long long length, int sampleRate, int nWin, int lagMin, int lagMax,
+	double threshold, long long hop, long long phase, int what, double* out);
+/* The estimate of chosen utterances (exportPitch, at the batch's sample rate) or of chosen rows of `signal` (exportPitchOf, at sampleRate)
+ * into caller-owned device memory on the caller's stream.  utterances / rows, rowStride (in steps; 0: packed), the return value, the ordering
+ * by events, the sixteen-in-flight rule, the device-memory, alignment and size checks and the signal contract are those of
+ * speechPlayer_batch_exportLpc / exportLpcOf.  A 256-lane workgroup takes 16 consecutive steps of the output, a wavefront a step at a time
+ * (csrc/klatt_pitch.h).
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written, the batch still usable: what speechPlayer_batch_exportLpc / exportLpcOf refuse
+ * of the batch, the signal, hop, phase, the format, the selection, rowStride and the output; nWin, lagMin, lagMax, threshold or sampleRate
+ * out of the ranges above; what 0 or with a bit above 32. */
+long long speechPlayer_batch_exportPitch(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int nWin, int lagMin,
+	int lagMax, double threshold, long long hop, long long phase, int what, void* deviceOut, int format, long long rowStride, void* stream);
+long long speechPlayer_batch_exportPitchOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	int sampleRate, int nWin, int lagMin, int lagMax, double threshold, long long hop, long long phase, int what, void* deviceOut, int format,
+	long long rowStride, void* stream);
+/*
  * Tempo perturbation of a batch's PCM, or of a signal's rows, by waveform-similarity overlap-add (WSOLA): the duration changes, the pitch
  * and the formants stay.  Beside the samples the export gives its time map, the input sample every output frame was taken from.  A row
  * of L samples is read as the other exports of the PCM read it: an int16 s is (float)s / 32767.0f, a float32 is taken as it is, a sample

@@ -73,6 +73,7 @@ EXPORTS = [
     "speechPlayer_pcmCode", "speechPlayer_signalCode", "speechPlayer_codecDecode", "speechPlayer_batch_exportCoded", "speechPlayer_batch_exportCodedOf",
     "speechPlayer_lpcFromAutocorrelation", "speechPlayer_pcmLpc", "speechPlayer_signalLpc", "speechPlayer_pcmLpcResidual", "speechPlayer_signalLpcResidual",
     "speechPlayer_batch_exportLpc", "speechPlayer_batch_exportLpcOf", "speechPlayer_batch_exportLpcResidual", "speechPlayer_batch_exportLpcResidualOf",
+    "speechPlayer_pcmPitch", "speechPlayer_signalPitch", "speechPlayer_batch_exportPitch", "speechPlayer_batch_exportPitchOf",
     "speechPlayer_tempoLength", "speechPlayer_tempoFrames", "speechPlayer_pcmTempo", "speechPlayer_signalTempo",
     "speechPlayer_batch_exportTempoPositions", "speechPlayer_batch_exportTempoPositionsOf", "speechPlayer_batch_exportTempo", "speechPlayer_batch_exportTempoOf",
 ]
@@ -463,6 +464,15 @@ def load():
     L.speechPlayer_batch_exportLpcResidual.argtypes = [vp, vp, i64, i32, i64, i64, vp, i32, i32, i32, i64, i32, vp, i32, i64, vp]
     L.speechPlayer_batch_exportLpcResidualOf.restype = i64
     L.speechPlayer_batch_exportLpcResidualOf.argtypes = [vp, vp, vp, i64, i32, i64, i64, vp, i32, i32, i32, i64, i32, vp, i32, i64, vp]
+    f64 = ctypes.c_double
+    L.speechPlayer_pcmPitch.restype = i64
+    L.speechPlayer_pcmPitch.argtypes = [vp, i64, i32, i32, i32, i32, f64, i64, i64, i32, vp]
+    L.speechPlayer_signalPitch.restype = i64
+    L.speechPlayer_signalPitch.argtypes = [vp, i32, i64, i32, i32, i32, i32, f64, i64, i64, i32, vp]
+    L.speechPlayer_batch_exportPitch.restype = i64
+    L.speechPlayer_batch_exportPitch.argtypes = [vp, vp, i64, i32, i32, i32, f64, i64, i64, i32, vp, i32, i64, vp]
+    L.speechPlayer_batch_exportPitchOf.restype = i64
+    L.speechPlayer_batch_exportPitchOf.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, f64, i64, i64, i32, vp, i32, i64, vp]
     L.speechPlayer_tempoLength.restype = i64
     L.speechPlayer_tempoLength.argtypes = [i64, f64]
     L.speechPlayer_tempoFrames.restype = i64

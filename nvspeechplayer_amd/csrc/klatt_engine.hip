@@ -26,6 +26,7 @@
 #include "klatt_filter.h"
 #include "klatt_codec.h"
 #include "klatt_lpc.h"
+#include "klatt_pitch.h"
 #include "klatt_tempo.h"
 #include "klatt_mix.h"
 #include "klatt_export.h"
@@ -5472,6 +5473,112 @@ long long speechPlayer_batch_exportLpcOf(speechPlayer_batch_t batch, const speec
 {
     if (refuse_timing_only("speechPlayer_batch_exportLpcOf")) return -1;
     return lpc_export("exportLpcOf", batch, true, signal, rows, nRows, order, nWin, hop, phase, window, lagWindow, what, deviceOut, format, rowStride, stream);
+}
+
+// ---- pitch estimated from the PCM (klatt_pitch.h) ---------------------------------------------------------------------------------------------
+// Host only, touch no device: the definition of include/speechPlayer_batch.h through the functions the kernel is compiled from.
+static long long pitch_statement(const char* what, const void* x, int inFormat, long long length, int sampleRate, int nWin, int lagMin, int lagMax,
+                                 double threshold, long long hop, long long phase, int fields, double* out)
+{
+    if (signal_host_format(what, inFormat)) return -1;
+    if (length < 0 || length > kResampleMaxLength || hop <= 0 || phase < 0 || (length > 0 && !x)) {
+        set_error("%s: length %lld (0 .. 2^44, with its samples), hop %lld, phase %lld", what, length, hop, phase); return -1;
+    }
+    try {
+        PitchPlan P;
+        std::string why;
+        if (!pitch_plan(P, sampleRate, nWin, lagMin, lagMax, threshold, fields, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        hop = std::min(hop, 1ll << 40); phase = std::min(phase, 1ll << 40);
+        if (align_steps_below(length, hop, phase) > 0 && !out) { set_error("%s: no output", what); return -1; }
+        if (signal_host_values(what, x, inFormat, length)) return -1;
+        return inFormat ? pitch_host(static_cast<const float*>(x), length, P, hop, phase, out) : pitch_host(static_cast<const int16_t*>(x), length, P, hop, phase, out);
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
+long long speechPlayer_pcmPitch(const sample* pcm, long long length, int sampleRate, int nWin, int lagMin, int lagMax, double threshold, long long hop,
+                                long long phase, int what, double* out)
+{
+    begin_call();
+    return pitch_statement("pcmPitch", pcm, 0, length, sampleRate, nWin, lagMin, lagMax, threshold, hop, phase, what, out);
+}
+
+long long speechPlayer_signalPitch(const void* x, int inFormat, long long length, int sampleRate, int nWin, int lagMin, int lagMax, double threshold,
+                                   long long hop, long long phase, int what, double* out)
+{
+    begin_call();
+    return pitch_statement("signalPitch", x, inFormat, length, sampleRate, nWin, lagMin, lagMax, threshold, hop, phase, what, out);
+}
+
+// The pitch of chosen utterances' PCM, 16 steps of the output per workgroup, four per wavefront (klatt_pitch.h).  The host path is lpc_export's,
+// step for step.  The staging block: rows | step starts and chunk rows (packed).  ofSignal and `signal` as spectrogram_export's.
+static long long pitch_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances,
+                              long long nUtterances, int sampleRate, int nWin, int lagMin, int lagMax, double threshold, long long hop, long long phase, int fields,
+                              void* deviceOut, int format, long long rowStride, void* stream)
+{
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (format != 0 && format != 1) { set_error("%s: format %d (0 float64, 1 float32)", what, format); return -1; }
+        if (step_request(what, hop, phase, rowStride)) return -1;
+        PitchPlan P;
+        std::string why;
+        if (!pitch_plan(P, ofSignal ? sampleRate : b->sampleRate, nWin, lagMin, lagMax, threshold, fields, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
+        ExportSelection s;
+        std::vector<SpecRow> rows;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long, long long u, long long) {
+                const long long L = in.len(u);
+                rows.push_back(SpecRow{in.at(u), L, align_steps_below(L, hop, phase)});
+                return rows.back().steps;
+            }, in.sig)) return -1;
+        static constexpr ExportNouns kFieldNouns{"largest step count", "steps", "values"};
+        const long long elements = export_elements(what, kFieldNouns, s, rowStride, P.nCols);
+        if (elements <= 0) return elements;
+        if (!in.sig && export_synthesised(b, what)) return -1;
+        const size_t elSize = format ? sizeof(float) : sizeof(double);
+        if (export_output(b, what, deviceOut, elements, elSize) || signal_memory(in, what, deviceOut, (size_t)elements * elSize)) return -1;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+
+        const bool packed = rowStride == 0;
+        std::vector<long long> words;
+        const RowTable table = packed ? packed_row_table(s.counts.data(), 0, s.n, kTimelineChunkLog2, words) : RowTable{0, 0};
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words);
+        void (*const kernels[2][2])(PitchArgs) = {{klatt_pitch<false, int16_t>, klatt_pitch<true, int16_t>}, {klatt_pitch<false, float>, klatt_pitch<true, float>}};
+        const auto kernel = kernels[in.format()][format];
+        ExportStage stage(b, st, block, nullptr, !in.sig, in.sig != nullptr);
+        if (stage.begin([&] { return ensure_lds_limit(reinterpret_cast<const void*>(kernel), (int)kPitchLdsBudget); })) return -1;
+        PitchArgs A;
+        A.in = in.data; A.rows = stage.device<SpecRow>(rowsAt);
+        A.start = packed ? stage.device<long long>(wordsAt) + table.startOff : nullptr;
+        A.chunk = packed ? stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
+        A.rowStride = rowStride; A.nSteps = elements / P.nCols;
+        A.hop = hop; A.phase = phase; A.threshold = P.threshold;
+        A.nWin = P.nWin; A.lagMin = P.lagMin; A.lagMax = P.lagMax; A.what = P.what; A.nCols = P.nCols; A.sampleRate = P.sampleRate;
+        A.out = deviceOut;
+        const long long nGroups = (A.nSteps + kPitchGroup - 1) / kPitchGroup;
+        const unsigned grid = (unsigned)std::min<long long>(nGroups, 8ll * b->cus);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), pitch_lds_bytes(P.nWin, P.lagMax, P.nCols, (int)elSize), st, A);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
+}
+
+long long speechPlayer_batch_exportPitch(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int nWin, int lagMin, int lagMax,
+                                         double threshold, long long hop, long long phase, int what, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportPitch")) return -1;
+    return pitch_export("exportPitch", batch, false, nullptr, utterances, nUtterances, 0, nWin, lagMin, lagMax, threshold, hop, phase, what, deviceOut, format, rowStride, stream);
+}
+
+// The same of chosen rows of a caller's signal at `sampleRate`: it reads no pool and needs no synthesis (ExportStage, ofSignal).
+long long speechPlayer_batch_exportPitchOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows, int sampleRate,
+                                           int nWin, int lagMin, int lagMax, double threshold, long long hop, long long phase, int what, void* deviceOut, int format,
+                                           long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportPitchOf")) return -1;
+    return pitch_export("exportPitchOf", batch, true, signal, rows, nRows, sampleRate, nWin, lagMin, lagMax, threshold, hop, phase, what, deviceOut, format, rowStride, stream);
 }
 
 // The chosen rows through the inverse filter of their own frames' coefficients, tile-wise (klatt_lpc.h): the residual or the prediction.  The

@@ -1252,6 +1252,102 @@ def signalLpc(x, order=16, nWin=512, hop=256, phase=0, window=None, lagWindow=No
     return _lpc_statement("signalLpc", *_signal_samples(x, "signalLpc"), order, nWin, hop, phase, window, lagWindow, fields)
 
 
+PITCH_FIELDS = ["f0", "period", "lag", "aperiodicity", "voiced", "cmnd"]      # bit 1 << i of `what` (include/speechPlayer_batch.h); the fields come in this order
+PITCH_MIN_WIN = 32               # csrc/klatt_pitch.h
+PITCH_MAX_WIN = 2048             # kPitchMaxWin
+PITCH_MAX_LAG = 1024             # kPitchMaxLag
+PITCH_GROUP = 16                 # kPitchGroup: consecutive steps of the output a workgroup of the kernel takes at a time
+
+
+def pitchLags(sampleRate, fmin=60.0, fmax=500.0):
+    """The lags that hold the periods of fmin .. fmax Hz at sampleRate: -> (floor(sampleRate / fmax), ceil(sampleRate / fmin)), clamped to
+    2 <= lagMin < lagMax <= 1024 (22050 Hz, 60 .. 500 Hz: 44 .. 368)."""
+    if not (sampleRate > 0 and 0 < fmin < fmax and math.isfinite(fmax)):
+        raise ValueError("pitchLags: sampleRate %r, fmin %r, fmax %r (sampleRate > 0, 0 < fmin < fmax)" % (sampleRate, fmin, fmax))
+    lagMin = max(2, min(int(math.floor(sampleRate / fmax)), PITCH_MAX_LAG - 1))
+    lagMax = min(PITCH_MAX_LAG, max(int(min(math.ceil(sampleRate / fmin), PITCH_MAX_LAG)), lagMin + 1))
+    return lagMin, lagMax
+
+
+def check_pitch_fields(fields, what="pitchTensor"):
+    """fields: a name of PITCH_FIELDS or a non-empty sequence of them (KeyError for another, ValueError for none), or the bit set itself,
+    1 .. 63: -> the bit set."""
+    if isinstance(fields, (int, np.integer)) and not isinstance(fields, (bool, np.bool_)):
+        if not 1 <= int(fields) < 1 << len(PITCH_FIELDS):
+            raise ValueError("%s: fields %d (a set of the bits 1 .. %d)" % (what, fields, 1 << len(PITCH_FIELDS) - 1))
+        return int(fields)
+    names = [fields] if isinstance(fields, str) else list(fields)
+    bits = 0
+    for name in names:
+        if name not in PITCH_FIELDS:
+            raise KeyError("%s: field %r (%s)" % (what, name, ", ".join(PITCH_FIELDS)))
+        bits |= 1 << PITCH_FIELDS.index(name)
+    if not bits:
+        raise ValueError("%s: no fields" % what)
+    return bits
+
+
+def pitchColumns(fields, lagMin, lagMax):
+    """Where each of `fields` (names of PITCH_FIELDS, any order) lies in a step's values: -> ({name: (first column, count)}, the total)."""
+    what = check_pitch_fields(fields, "pitchColumns")
+    at, col = {}, 0
+    for i, name in enumerate(PITCH_FIELDS):
+        if what >> i & 1:
+            n = lagMax - lagMin + 1 if name == "cmnd" else 1
+            at[name] = (col, n)
+            col += n
+    return at, col
+
+
+def check_pitch_request(sampleRate, fmin, fmax, lagMin, lagMax, nWin, hop, phase, threshold, fields, dtype, what="pitchTensor"):
+    """The argument checks of BatchPlayer.pitchTensor, pcmPitch and signalPitch that need no GPU: sampleRate an integer > 0; the lags from
+    fmin and fmax (pitchLags) unless lagMin and lagMax are both given, integers with 2 <= lagMin < lagMax <= 1024; nWin an integer in
+    32 .. 2048; hop >= 1; phase >= 0; threshold a finite number in [0, 1]; `fields` as check_pitch_fields'; dtype None / torch.float32 /
+    torch.float64.  Raises ValueError, KeyError or TypeError.  Returns (sampleRate, nWin, lagMin, lagMax, threshold, hop, phase, the bit
+    set, the values per step, the export format: 0 float64, 1 float32)."""
+    def whole(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not whole(sampleRate) or not 0 < sampleRate < 1 << 31:
+        raise ValueError("%s: sampleRate must be an integer > 0, not %r" % (what, sampleRate))
+    if (lagMin is None) != (lagMax is None):
+        raise ValueError("%s: lagMin and lagMax come together (or neither: fmin and fmax give them)" % what)
+    if lagMin is None:
+        lagMin, lagMax = pitchLags(sampleRate, fmin, fmax)
+    if not whole(lagMin) or not whole(lagMax) or not 2 <= lagMin < lagMax <= PITCH_MAX_LAG:
+        raise ValueError("%s: lagMin and lagMax must be integers with 2 <= lagMin < lagMax <= %d, not %r and %r" % (what, PITCH_MAX_LAG, lagMin, lagMax))
+    if not whole(nWin) or not PITCH_MIN_WIN <= nWin <= PITCH_MAX_WIN:
+        raise ValueError("%s: nWin must be an integer in %d .. %d, not %r" % (what, PITCH_MIN_WIN, PITCH_MAX_WIN, nWin))
+    hop, phase = _check_lpc_grid(hop, phase, what)
+    if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)) or not 0.0 <= threshold <= 1.0:
+        raise ValueError("%s: threshold must be a number in 0 .. 1, not %r" % (what, threshold))
+    fmt = _check_dtype(what, dtype, *_float_types())
+    bits = check_pitch_fields(fields, what)
+    return (int(sampleRate), int(nWin), int(lagMin), int(lagMax), float(threshold), hop, phase, bits, pitchColumns(bits, int(lagMin), int(lagMax))[1], fmt)
+
+
+def _pitch_statement(what, s, inFormat, sampleRate, fmin, fmax, lagMin, lagMax, nWin, hop, phase, threshold, fields):
+    import torch
+    sampleRate, nWin, lagMin, lagMax, threshold, hop, phase, bits, cols, _ = check_pitch_request(sampleRate, fmin, fmax, lagMin, lagMax, nWin, hop, phase,
+                                                                                                 threshold, fields, torch.float64, what)
+    return _row_statement(what, s, inFormat, (sampleRate, nWin, lagMin, lagMax, threshold, hop, phase, bits),
+                          (int(_step_counts(len(s), hop, phase)), cols), np.float64, counted=False)
+
+
+def pcmPitch(pcm, sampleRate, fmin=60.0, fmax=500.0, nWin=1024, hop=256, phase=0, threshold=0.1, fields=("f0", "aperiodicity"), lagMin=None, lagMax=None):
+    """The pitch of int16 PCM estimated from the signal on the host (speechPlayer_pcmPitch; no GPU): -> float64 [steps, values], by the
+    definition in include/speechPlayer_batch.h -- step j centred on sample phase + j * hop, a frame of nWin + lagMax samples, zeros outside
+    the signal, the YIN difference by exact binary64 squares in four chains, its cumulative mean normalised form, the first dip below the
+    threshold and a parabolic refinement.  Arguments as BatchPlayer.pitchTensor's; pitchColumns(fields, lagMin, lagMax) says where each
+    field lies."""
+    return _pitch_statement("pcmPitch", _pcm_samples(pcm, "pcmPitch"), None, sampleRate, fmin, fmax, lagMin, lagMax, nWin, hop, phase, threshold, fields)
+
+
+def signalPitch(x, sampleRate, fmin=60.0, fmax=500.0, nWin=1024, hop=256, phase=0, threshold=0.1, fields=("f0", "aperiodicity"), lagMin=None, lagMax=None):
+    """pcmPitch on a signal's row (speechPlayer_signalPitch; no GPU): x as signalSpectrogram's.  The statement
+    BatchPlayer.pitchTensor(signal=...) is held to."""
+    return _pitch_statement("signalPitch", *_signal_samples(x, "signalPitch"), sampleRate, fmin, fmax, lagMin, lagMax, nWin, hop, phase, threshold, fields)
+
+
 def lpcFromAutocorrelation(r):
     """The Levinson-Durbin recursion alone (speechPlayer_lpcFromAutocorrelation; no GPU) on r[0 .. order], order = len(r) - 1 in
     1 .. 32: -> (a float64 [order]: a_1 .., k float64 [order]: the reflection coefficients, the error E, the stages done).  It stops
@@ -2019,6 +2115,36 @@ class BatchPlayer(object):
 
         def call(out, stride, numel, stream):
             return export(order, nWin, hop, phase, _ptr(window), _ptr(lagWindow), bits, out, fmt, stride, stream)
+        return self._export_rows(_step_counts(src.lengths, hop, phase), (cols,), torch.float32 if fmt else torch.float64, padded, call)
+
+    def pitchTensor(self, fmin=60.0, fmax=500.0, nWin=1024, hop=256, phase=0, threshold=0.1, fields=("f0", "aperiodicity"), utterances=None, dtype=None,
+                    padded=True, signal=None, sampleRate=None, lagMin=None, lagMax=None):
+        """The pitch of the batch's PCM ESTIMATED FROM THE SIGNAL (YIN) as a torch tensor on the batch's device
+        (speechPlayer_batch_exportPitch), filled on torch's current stream behind the synthesis without a host wait: -> (pitch, steps).
+        Step j of an utterance is centred on its sample phase + j * hop -- the grid of spectrogramTensor and lpcTensor, row for row -- over
+        a frame of nWin + lagMax samples (nWin any integer in 32 .. 2048), zeros outside the utterance.  The lags searched are
+        pitchLags(sampleRate, fmin, fmax), or lagMin= and lagMax= (2 <= lagMin < lagMax <= 1024); threshold in 0 .. 1 is YIN's.  fields:
+        names of PITCH_FIELDS; a step's values come in that list's order whatever the order asked for (pitchColumns): "f0" in Hz, +0 where
+        unvoiced; "period" in samples, refined by a parabola; "lag" the integer lag chosen; "aperiodicity" the normalised difference
+        there; "voiced" 0 or 1; "cmnd" the whole normalised difference over lagMin .. lagMax for a tracker of the caller's own.  sourceTensor
+        gives the TRUE fundamental of the clean synthesis; this is what a front end would estimate from the row.  utterances, dtype and
+        padded as lpcTensor's.  The batch must have been synthesised since it was set; pcmPitch is the same definition on the host,
+        which the device equals bit for bit.
+        signal: the (tensor, lengths or offsets) pair another export returned, read in place of the batch's PCM
+        (speechPlayer_batch_exportPitchOf) at sampleRate=, which is then required (a signal has no rate of its own: resampledTensor's is
+        the rate asked for); signalPitch is the host's statement."""
+        import torch
+        if signal is None and sampleRate is not None:
+            raise ValueError("pitchTensor: sampleRate comes with a signal")
+        if signal is not None and sampleRate is None:
+            raise ValueError("pitchTensor: a signal needs its sampleRate")
+        rate, nWin, lagMin, lagMax, threshold, hop, phase, bits, cols, fmt = check_pitch_request(int(self.sampleRate) if signal is None else sampleRate, fmin, fmax,
+                                                                                                 lagMin, lagMax, nWin, hop, phase, threshold, fields, dtype)
+        src = self._rows("pitchTensor", signal, utterances)
+        export = self._entry("Pitch", src)
+
+        def call(out, stride, numel, stream):
+            return export(*(() if signal is None else (rate,)), nWin, lagMin, lagMax, threshold, hop, phase, bits, out, fmt, stride, stream)
         return self._export_rows(_step_counts(src.lengths, hop, phase), (cols,), torch.float32 if fmt else torch.float64, padded, call)
 
     def lpcResidualTensor(self, lpc, order=16, hop=256, phase=0, column=0, what="residual", utterances=None, dtype=None, padded=True, signal=None):
