@@ -54,18 +54,24 @@ VARIANTS = {
     "quiet": (QUIET_PARAMS, NOISE_GAINS),
     "quiet_nasal_free": (tuple(p for p in QUIET_PARAMS if p not in (13, 14, 21, 22, 23)), NOISE_GAINS + (23,)),
 }
+# variants of other modules, same form (tests/dead_terms.py: the dead variants).  A table of its own: list(VARIANTS) parametrises tests.
+MORE_VARIANTS = {}
 MANNERS = ("move", "jump", "edges")
 EDGE_FADES = (1, 2, 15, 16, 17, 31, 32, 33)
 USUAL = 7       # cf1: the parameter the intruder composition's 63 other lanes move
 
 
+def _spec(variant):
+    return VARIANTS[variant] if variant in VARIANTS else MORE_VARIANTS[variant]
+
+
 def params(variant):
-    return VARIANTS[variant][0]
+    return _spec(variant)[0]
 
 
 def base(variant="noisy"):
     f = BASE.copy()
-    f[list(VARIANTS[variant][1])] = 0.0
+    f[list(_spec(variant)[1])] = 0.0
     return f
 
 
@@ -158,6 +164,16 @@ class Corpus:
 
     def __len__(self):
         return len(self.what)
+
+    def tiled(self, k):
+        """This corpus k times in order (whole wavefronts: under "sort" = 0 every wavefront keeps its composition) -- a batch large enough
+        for the flat launch with two workgroups per CU; .what counts the wavefronts on.  The oracle synthesizes nothing twice."""
+        assert len(self) % LANES == 0
+        c = Corpus(self.variant)
+        for _ in range(k):
+            for (p, manner, composition, _, lane), frames, seed in zip(self.what, self.cases, self.seeds):
+                c.add(frames, seed, p, manner, composition, lane)
+        return c.finish()
 
     def oracle(self, threads=8):
         """(pcm, start, total) of tests/oracle.batch_synthesize; every distinct (frame list, seed) is synthesized once."""

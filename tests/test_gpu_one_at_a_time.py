@@ -94,6 +94,46 @@ def test_noisy_batch_paths(path, mode):
         check("noisy", "%s, sort %d" % (path, sort), mode, got, start)
 
 
+def test_noisy_flat_stages_two_workgroups_per_cu():
+    """The noisy corpus repeated in order until it no longer fits one workgroup per CU (kernelInfo(): wavefronts // 4 + 1 against cus): the
+    flat launch with two workgroups per CU, the instantiation bench.py times (another kernel, whatever its hand-overs and registers), which
+    the corpus as it is -- 168 wavefronts -- never takes.  Lanes in the given order, so every wavefront keeps its composition.
+    MODE_EXACT: the anchor's bytes, tile by tile; MODE_FAST: the bar.  Every term is present in the noisy base: no wavefront drops one
+    (option "dead_terms")."""
+    c0, exp, exp_start = corpus_of("noisy")
+    anchor = anchor_of("noisy")
+    flat = NOISY_PATHS["flat stages"]
+    _, _, info0 = run_batch(c0, 0, sort=0, options=flat)
+    cus = info0["cus"]
+    assert info0["wavefronts"] // 4 + 1 <= cus and info0["tracked_utterances"] == len(c0), info0
+    k = 1
+    while len(c0) * k // oat.LANES + 1 <= cus:
+        k += 1
+    c = c0.tiled(k)
+    n = len(exp)
+    want_start = np.concatenate([[0], np.cumsum(np.tile(np.diff(exp_start), k))]).astype(np.int64)
+    for mode in (0, 1):
+        got, start, info = run_batch(c, mode, sort=0, options=flat)
+        print("noisy x %d, MODE_%s: %d wavefronts on %d CUs, hand-overs of %d samples, %d VGPRs (untiled: %d wavefronts, %d samples, %d VGPRs in MODE_EXACT)" % (
+            k, "FAST" if mode else "EXACT", info["wavefronts"], cus, info["stage_parallel_chunk"], info["vgprs"], info0["wavefronts"],
+            info0["stage_parallel_chunk"], info0["vgprs"]))
+        assert info["wavefronts"] // 4 + 1 > cus, info
+        assert info["tracked_utterances"] == len(c) and info["direct_utterances"] == 0 and info["scratch_bytes"] == 0, info
+        assert not any(v for key, v in info.items() if key.startswith("waves_without_")), info
+        assert np.array_equal(start, want_start)
+        if mode == 0:
+            for t in range(k):
+                diff = c0.first_difference(got[t * n:(t + 1) * n], anchor, exp_start)
+                assert diff is None, "two workgroups per CU, tile %d of %d against the untracked stages: %s" % (t, k, diff)
+        want = np.tile(exp, k)
+        try:
+            flips = compare(got, want, "flat stages, two workgroups per CU, MODE_%s" % ("FAST" if mode else "EXACT"))
+        except AssertionError as e:
+            beyond = int(np.abs(got.astype(np.int32) - want.astype(np.int32)).max()) > 1
+            raise AssertionError("%s -- %s" % (e, c.first_difference(got, want, start, 1 if beyond else 0)))
+        print("%d utterances, %d samples, %d one-LSB differences from the oracle" % (len(c), len(want), flips))
+
+
 @pytest.mark.parametrize("mode", [0, 1])
 @pytest.mark.parametrize("layout", [-1, 2, 1, 0])
 @pytest.mark.parametrize("variant", ["quiet", "quiet_nasal_free"])

@@ -35,6 +35,12 @@ def test_every_case_is_audible_and_nothing_clips(variant):
     -- the edges cases included -- peaks at 16 000 or above (clipping would hide sensitivity and errors alike).
     Measured: noisy pb6 102 (move) / 95 (jump) samples, largest difference 3 / 4 LSB; quiet cb5 247 / 255, up to 15 LSB; quiet
     nasal-free vibratoSpeed 203 (jump); every other case more than 300.  INAUDIBLE: the one pair that cannot meet it."""
+    check_audible(variant, {p for v, p in INAUDIBLE if v == variant})
+
+
+def check_audible(variant, inaudible):
+    """(the body of the test above, for any variant; `inaudible`: the parameters that must differ in NO sample)  Returns per manner the
+    weakest audible parameter with its count, and the peak."""
     weakest, peak = {}, 0
     for manner in ("move", "jump"):
         plain = pcm_of(oat.case(oat.USUAL, manner, variant, unchanged=True))
@@ -43,13 +49,13 @@ def test_every_case_is_audible_and_nothing_clips(variant):
             pcm = pcm_of(oat.case(p, manner, variant))
             assert len(pcm) == len(plain)
             d = np.abs(pcm.astype(np.int32) - plain.astype(np.int32))
-            if (variant, p) in INAUDIBLE:
-                assert not d.any(), (variant, manner, oat.NAMES[p])
+            if p in inaudible:
+                assert not d.any(), (variant, manner, oat.NAMES[p], int(np.count_nonzero(d)))
                 continue
             counts[p] = (int(np.count_nonzero(d > 1)), int(d.max()))
             peak = max(peak, int(np.abs(pcm.astype(np.int32)).max()))
-        weakest[manner] = min(counts, key=lambda p: counts[p])
-        p = weakest[manner]
+        p = min(counts, key=lambda p: counts[p])
+        weakest[manner] = (oat.NAMES[p], counts[p][0])
         print("%s %s: weakest %s, %d samples differ by more than 1 LSB (largest difference %d LSB)" % (
             variant, manner, oat.NAMES[p], counts[p][0], counts[p][1]))
         weak = {oat.NAMES[p]: c for p, c in counts.items() if c[0] < MIN_SAMPLES}
@@ -60,6 +66,7 @@ def test_every_case_is_audible_and_nothing_clips(variant):
                 peak = max(peak, int(np.abs(pcm_of(oat.case(p, "edges", variant, edge)).astype(np.int32)).max()))
     print("%s: peak %d" % (variant, peak))
     assert peak < MAX_PEAK
+    return weakest, peak
 
 
 def test_corpus_holds_every_parameter_in_every_manner():
@@ -70,34 +77,40 @@ def test_corpus_holds_every_parameter_in_every_manner():
     assert oat.params("quiet") == (0, 1, 2, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 44, 45, 46)
     assert oat.params("quiet_nasal_free") == (0, 1, 2, 4, 5, 7, 8, 9, 10, 11, 12, 15, 16, 17, 18, 19, 20, 44, 45, 46)
     for variant in oat.VARIANTS:
-        c = oat.batch_corpus(variant)
-        ps = set(oat.params(variant))
-        have = {(p, m, comp) for p, m, comp, _, _ in c.what}
-        assert {p for p, m, comp in have if (m, comp) == ("move", "pure")} == ps
-        assert {p for p, m, comp in have if (m, comp) == ("move", "intruder")} == ps
-        assert {p for p, m, comp in have if (m, comp) == ("jump", "intruder")} == ps
-        assert {p for p, m, comp in have if (m, comp) == ("edges", "ragged")} == ps
-        kinds = 0
-        for p in {p for p, m, comp in have if (m, comp) == ("jump", "pure")}:
-            kinds |= oat.kind_bits(p)
-        full = 0
-        for p in ps:
-            full |= oat.kind_bits(p)
-        assert kinds == full and {0, 46} <= {p for p, m, comp in have if (m, comp) == ("jump", "pure")}
-        b = c.batch
-        for w in range(len(c) // oat.LANES):
-            lanes = range(w * oat.LANES, (w + 1) * oat.LANES)
-            timing = {(b["min"][b["frame_start"][u]:b["frame_start"][u + 1]].tobytes(), b["fade"][b["frame_start"][u]:b["frame_start"][u + 1]].tobytes()) for u in lanes}
-            comp = c.what[w * oat.LANES][2]
-            assert all(c.what[u][2] == comp and c.what[u][4] == u % oat.LANES for u in lanes)
-            assert len(timing) == (oat.LANES if comp == "ragged" else 1)
-            if comp == "intruder":
-                odd = [u for u in lanes if c.what[u][0] != oat.USUAL]
-                assert len(odd) <= 1 and all(c.what[u][4] == c.what[u][0] % oat.LANES for u in odd)
-        for p in ps:
-            assert np.count_nonzero(oat.changed(p, variant) != oat.base(variant)) == 1
-        fades = {int(f) for u in range(len(c)) if c.what[u][1] == "edges" for f in b["fade"][b["frame_start"][u]:b["frame_start"][u + 1]]}
-        assert fades == set(oat.EDGE_FADES)
+        check_corpus_shape(variant)
+
+
+def check_corpus_shape(variant):
+    """(the body of the test above, for any variant)  Returns the corpus."""
+    c = oat.batch_corpus(variant)
+    ps = set(oat.params(variant))
+    have = {(p, m, comp) for p, m, comp, _, _ in c.what}
+    assert {p for p, m, comp in have if (m, comp) == ("move", "pure")} == ps
+    assert {p for p, m, comp in have if (m, comp) == ("move", "intruder")} == ps
+    assert {p for p, m, comp in have if (m, comp) == ("jump", "intruder")} == ps
+    assert {p for p, m, comp in have if (m, comp) == ("edges", "ragged")} == ps
+    kinds = 0
+    for p in {p for p, m, comp in have if (m, comp) == ("jump", "pure")}:
+        kinds |= oat.kind_bits(p)
+    full = 0
+    for p in ps:
+        full |= oat.kind_bits(p)
+    assert kinds == full and {0, 46} <= {p for p, m, comp in have if (m, comp) == ("jump", "pure")}
+    b = c.batch
+    for w in range(len(c) // oat.LANES):
+        lanes = range(w * oat.LANES, (w + 1) * oat.LANES)
+        timing = {(b["min"][b["frame_start"][u]:b["frame_start"][u + 1]].tobytes(), b["fade"][b["frame_start"][u]:b["frame_start"][u + 1]].tobytes()) for u in lanes}
+        comp = c.what[w * oat.LANES][2]
+        assert all(c.what[u][2] == comp and c.what[u][4] == u % oat.LANES for u in lanes)
+        assert len(timing) == (oat.LANES if comp == "ragged" else 1)
+        if comp == "intruder":
+            odd = [u for u in lanes if c.what[u][0] != oat.USUAL]
+            assert len(odd) <= 1 and all(c.what[u][4] == c.what[u][0] % oat.LANES for u in odd)
+    for p in ps:
+        assert np.count_nonzero(oat.changed(p, variant) != oat.base(variant)) == 1
+    fades = {int(f) for u in range(len(c)) if c.what[u][1] == "edges" for f in b["fade"][b["frame_start"][u]:b["frame_start"][u + 1]]}
+    assert fades == set(oat.EDGE_FADES)
+    return c
 
 
 def plan_kinds(b):
@@ -141,7 +154,18 @@ def test_masks_and_kinds_word_of_every_case(variant):
     move: the fade into B' and the fade back have exactly the kind(s) of p in their mask (none for the pitches).  jump: the fade out
     of silence has the gain kinds alone.  Either way the word holds the kinds of p and the gain kinds the silence fades move, and
     nothing else: in jump only its second term -- what a fade's first row re-sets -- can have put the kind of p there."""
-    c = oat.batch_corpus(variant)
+    check_masks_and_kinds(oat.batch_corpus(variant), variant)
+    # every one of the 24 kinds is some parameter's, and the noisy variant reaches them all
+    if variant == "noisy":
+        every = 0
+        for p in range(1, 46):
+            assert oat.kind_bits(p) != 0
+            every |= oat.kind_bits(p)
+        assert every == (1 << 24) - 1
+
+
+def check_masks_and_kinds(c, variant):
+    """(the body of the test above, for any variant's batch corpus)  Returns (mask per frame, kinds word per utterance)."""
     b = c.batch
     mask, tracked, kinds = plan_kinds(b)
     assert tracked.all()
@@ -163,13 +187,7 @@ def test_masks_and_kinds_word_of_every_case(variant):
         assert int(kinds[u]) == own | gain, c.describe(u)
         seen.add((p, manner))
     assert seen == {(p, manner) for p in oat.params(variant) for manner in oat.MANNERS}
-    # every one of the 24 kinds is some parameter's, and the noisy variant reaches them all
-    if variant == "noisy":
-        every = 0
-        for p in range(1, 46):
-            assert oat.kind_bits(p) != 0
-            every |= oat.kind_bits(p)
-        assert every == (1 << 24) - 1
+    return mask, kinds
 
 
 def test_kinds_word_of_utterances_that_get_no_tracks():
