@@ -51,7 +51,14 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch);
  * [1, 1e6], |pf1| <= 1e6, |fricationAmplitude| and |preFormantGain| <= 1e30 in every frame: all speech of the built-in producer's
  * phoneme table has no turbulence and no pa1 -- runs stage bodies without those terms, which add exactly nothing; 0: every wavefront
  * runs the general bodies.  Same PCM either way.  speechPlayer_batch_kernelInfo reports how many wavefronts of the last launch did, as
- * the stages counted them -- before a batch's first launch: how many will, by the plan and the option as it stands.)
+ * the stages counted them -- before a batch's first launch: how many will, by the plan and the option as it stands.
+ * The same option, by the same rule, drops four more pieces where no utterance of the wavefront has them: the nasal pair N0 / NP from the
+ * source stage (caNP zero of either sign in every frame, cbN0 in [1, 1e6], cbNP in [0, 1e6], |cfN0|, |cfNP| <= 1e6, |voiceAmplitude|,
+ * |aspirationAmplitude|, |preFormantGain| and the pitches <= 1e30; taken together with the turbulence: m, n and ng alone set caNP); parallel resonator 5, or 5 and
+ * 6, from the final stage; parallel resonators 1..4 from the parallel stage (each pa_k zero of either sign with pb_k in [1, 1e6],
+ * |pf_k| <= 1e6, |fricationAmplitude| and |preFormantGain| <= 1e30 in every frame: stops, affricates, sh, zh and the flap alone set
+ * pa2..pa5).  What is dropped is a finite value times zero; where a zero's sign differs from the general bodies' it stays a zero up to the
+ * int16.  kernelInfo: four more counts, of wavefronts whose stage ran without the nasal pair / parallel 5 / parallel 5 and 6 / parallel 1..4.)
  * "direct_lean" (the direct stages' residency: 1 two workgroups per CU, 0 one, -1, default: the engine's choice by mode, size and
  * whether the resident batch's direct group is time-aligned).
  * Read by:

@@ -64,6 +64,17 @@ inline void classify_list(const Meta* meta, const Facts* facts, long long n, uin
     flags = (needsNoise ? UTT_NEEDS_NOISE : (!(fl & FACT_NASAL) ? UTT_NO_NASAL : 0u)) | (fl & kUttPresent);      // (FACT_* and UTT_* of the present terms are the same bits)
     shape = finite ? (!(fl & FACT_UNBOUNDED) ? 3 : 1) : 0;
 }
+// ... and the list's second word of present terms (UTT2_*; Facts: flags, present2): whatever the routing makes of the list -- a noisy
+// one, or a quiet one sent to the flat stages, loses UTT_NO_NASAL -- this word keeps what the frames said.
+template <class Meta, class Facts>
+inline void classify_list(const Meta* meta, const Facts* facts, long long n, uint32_t& flags, unsigned char& shape, uint32_t& present2)
+{
+    classify_list(meta, facts, n, flags, shape);
+    uint32_t p2 = 0;
+    for (long long k = 0; k < n; ++k)
+        if (!(meta[k].flags & FRAME_NULL)) p2 |= facts[k].present2;
+    present2 = p2 & kUtt2Present;
+}
 
 // ---- the routing: which kernels a list's utterances go to --------------------------------------------------------------------------
 
@@ -73,6 +84,7 @@ struct ListTable {      // per frame list
     std::vector<uint32_t> flags;                 // classify_list, then the routing: UTT_*, what every utterance of the list carries
     std::vector<unsigned char> shape;            // classify_list
     std::vector<uint32_t> weight;                // how many utterances speak it
+    std::vector<uint32_t> present2;              // classify_list: UTT2_*, the second word of present terms; no step of the routing touches it
     long long size() const { return (long long)flags.size(); }
     // utterances with one (timing, length) are a RUN: their lanes fade together
     unsigned long long run_key(long long l) const { return timing[(size_t)l] ^ ((unsigned long long)lens[(size_t)l] * 0x9E3779B97F4A7C15ull); }
@@ -353,6 +365,30 @@ inline void dead_wave_counts(const uint32_t* order, long long first, long long n
         counts[0] += ((built & 1) && !(present & UTT_PARALLEL1)) ? 1 : 0;
         counts[1] += body >= 1 ? 1 : 0;
         counts[2] += body >= 2 ? 1 : 0;
+    }
+}
+
+// The same for the second word of present terms (present2Of(u): utterance u's UTT2_* bits), the bodies behind KLATT_DEAD_TERMS bits 8 .. 64:
+// wavefronts whose source stage runs without turbulence and the nasal pair [0] (bit 8; the stage needs turbulence dead too, flagsOf),
+// whose final stage runs without parallel 5 [1] (bit 16 or 32) and without parallel 5 and 6 [2] (bit 32), whose parallel stage runs
+// without parallel 1..4 [3] (bit 64; parallel 1 by flagsOf).
+template <class FlagsOf, class Present2Of>
+inline void dead2_wave_counts(const uint32_t* order, long long first, long long n, FlagsOf flagsOf, Present2Of present2Of, int built, long long counts[kDead2Counts],
+                              int width = kLanes)
+{
+    for (int k = 0; k < kDead2Counts; ++k) counts[k] = 0;
+    for (long long w = first; w < first + n; w += width) {
+        uint32_t present = 0, present2 = 0;
+        bool any = false;
+        for (long long s = w; s < std::min(w + width, first + n); ++s)
+            if (order[s] != kNoUtt) { present |= flagsOf(order[s]); present2 |= present2Of(order[s]); any = true; }
+        if (!any) continue;
+        const bool no5 = !(present2 & UTT2_PARALLEL5), no56 = no5 && !(present2 & UTT2_PARALLEL6);
+        const int fin = ((built & 32) && no56) ? 2 : (((built & 16) && no5) ? 1 : 0);
+        counts[0] += ((built & 8) && !(present & UTT_TURBULENCE) && !(present2 & UTT2_NASAL)) ? 1 : 0;
+        counts[1] += fin >= 1 ? 1 : 0;
+        counts[2] += fin >= 2 ? 1 : 0;
+        counts[3] += ((built & 64) && !(present & UTT_PARALLEL1) && !(present2 & kUtt2Parallel234)) ? 1 : 0;
     }
 }
 

@@ -31,4 +31,17 @@ constexpr uint32_t FACT_TURBULENCE = UTT_TURBULENCE;   // parameter 3 is not bit
 constexpr uint32_t FACT_ASPIRATION = UTT_ASPIRATION;   // parameter 6 is not bit-for-bit +0.0
 constexpr uint32_t FACT_PARALLEL1 = UTT_PARALLEL1;     // pa1 is non-zero, or parallel resonator 1's output may not be finite (klatt_plan.h, shape_flags)
 
+// A second word of PRESENT terms, of its own (UttDesc.flags is full): per frame in FrameFacts.present2 (klatt_plan.h), OR-ed per list
+// (classify_list, ListTable.present2) and handed per utterance to the flat launch alone (KernelArgs.present2).  Same rule as above: a flat
+// stage whose wavefront holds no live lane with the bit runs a body without the term.
+constexpr uint32_t UTT2_PARALLEL2 = 1u;    // parallel resonator k (bit k - 2, k = 2..6) contributes, or might not stay finite
+constexpr uint32_t UTT2_PARALLEL3 = 2u;
+constexpr uint32_t UTT2_PARALLEL4 = 4u;
+constexpr uint32_t UTT2_PARALLEL5 = 8u;
+constexpr uint32_t UTT2_PARALLEL6 = 16u;
+constexpr uint32_t UTT2_NASAL = 32u;       // FACT_NASAL of some frame: the nasal pair is coupled in, or could not be skipped safely
+constexpr uint32_t kUtt2Present = 63u;
+constexpr uint32_t kUtt2Parallel234 = UTT2_PARALLEL2 | UTT2_PARALLEL3 | UTT2_PARALLEL4;
+constexpr int kDead2Counts = 4;            // the flat stages' second set of counters (dead2_wave_counts, klatt_batchplan.h)
+
 }  // namespace klatt

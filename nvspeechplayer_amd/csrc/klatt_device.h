@@ -148,8 +148,11 @@ struct KernelArgs {
     double negPiOverSr;          // -pi/sr     (reference src/speechWaveGenerator.cpp:116)
     double twoPiOverSr;          // (2*pi)/sr  (reference src/speechWaveGenerator.cpp:118)
     unsigned long long* debug;   // diagnostic builds only (KLATT_STAMPS): per-wave cycle sums; nullptr otherwise
-    uint32_t* deadWaves;         // tracked launches: [3] wavefronts that ran without parallel 1 / without turbulence / without the aspiration generator; nullptr: not counted
+    uint32_t* deadWaves;         // tracked launches: [3] wavefronts that ran without parallel 1 / without turbulence / without the aspiration generator, then [kDead2Counts]
+                                 // without turbulence and the nasal pair / parallel 5 / parallel 5 and 6 / parallel 1..4 (dead2_wave_counts); nullptr: not counted
     uint32_t deadTerms;          // tracked launches: the UTT_* present bits a wavefront may act on (option "dead_terms"); 0: every wavefront runs the general bodies
+    uint32_t deadTerms2;         // tracked launches: the UTT2_* bits a wavefront may act on (option "dead_terms"); 0: the general bodies
+    const uint32_t* present2;    // tracked launches: per utterance its second word of present terms (UTT2_*, klatt_consts.h); nullptr: none is looked at
 };
 
 // resonator r reads frequency parameter kResF[r] and bandwidth parameter kResB[r]

@@ -577,8 +577,11 @@ struct Batch {
     hipEvent_t forkEvent = nullptr, join[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int quietLast = 1;                     // option "quiet_last": the quiet groups are launched after the noisy ones (batch_launch)
     int deadTerms = 1;                     // option "dead_terms": a flat wavefront none of whose lanes has a term (UTT_TURBULENCE .. UTT_PARALLEL1) runs a body without it; 0: the general bodies
-    DeviceBuffer<uint32_t> dDeadWaves;     // [3] the last tracked launch's wavefronts without parallel 1 / turbulence / the aspiration generator (speechPlayer_batch_kernelInfo)
+    DeviceBuffer<uint32_t> dDeadWaves;     // [3] the last tracked launch's wavefronts without parallel 1 / turbulence / the aspiration generator (speechPlayer_batch_kernelInfo),
+                                           // then [kDead2Counts] without the nasal pair / parallel 5 / parallel 5 and 6 / parallel 1..4
     long long planDeadWaves[3] = {0, 0, 0};   // ... and what the plan says they will be (dead_wave_counts, klatt_batchplan.h): reported until the batch has been launched
+    long long planDead2Waves[kDead2Counts] = {0, 0, 0, 0};   // (dead2_wave_counts)
+    DeviceBuffer<uint32_t> dPresent2;      // [nUtt] the utterances' second word of present terms (UTT2_*): read by the flat launch alone
     long long nUtt = 0, nFrames = 0, nSlots = 0;   // nFrames: frames resident in HBM (the lists')
     long long nLists = 0, nFramesSpoken = 0;       // frame lists of the batch; frames the utterances queue (sum over utterances of their list's)
     std::vector<long long> uttFrameStart;          // [nUtt] first frame of the utterance's list
@@ -1013,8 +1016,10 @@ int batch_launch(Batch* b)
         t.negPiOverSr = a.negPiOverSr; t.twoPiOverSr = a.twoPiOverSr;
         const long long tg = b->nJobs;     // one workgroup per track
         if (tg > 0x7FFFFFFF) { set_error("too many tracks: %lld", b->nJobs); return -1; }
-        if (b->dDeadWaves.reserve(3)) return -1;
-        HIP_TRY(hipMemsetAsync(b->dDeadWaves.ptr, 0, 3 * sizeof(uint32_t), st));
+        // (eight words, not seven: a fill of 28 bytes goes out as two kernels, one of 32 as one)
+        if (b->dDeadWaves.reserve(8)) return -1;
+        static_assert(3 + kDead2Counts <= 8, "the counters' block");
+        HIP_TRY(hipMemsetAsync(b->dDeadWaves.ptr, 0, 8 * sizeof(uint32_t), st));
         hipLaunchKernelGGL(klatt_tracks, dim3((unsigned)tg), dim3(kLanes * kTrackWaves), 0, st, t);
         HIP_TRY(hipGetLastError());
         a.order = b->dOrder.ptr + b->nQuiet; a.nSlots = nTr;
@@ -1022,12 +1027,13 @@ int batch_launch(Batch* b)
         a.trackBytes = (uint32_t)std::min<unsigned long long>(((unsigned long long)b->trackEntries + kTrackPad) * sizeof(double2), 0xFFFFFFFFull);
         // the terms a wavefront may drop (read by every launch, like "tracks"), and how many did (counters zeroed ahead of klatt_tracks)
         a.deadWaves = b->dDeadWaves.ptr; a.deadTerms = b->deadTerms ? kUttPresent : 0u;
+        a.present2 = b->dPresent2.ptr; a.deadTerms2 = (b->deadTerms && b->dPresent2.ptr) ? kUtt2Present : 0u;
         const GroupPlan pl = plan_group(b->layout, true, b->nSlots, nTr + nNoisy, b->cus);
         const long long g = (nTr + kLanes - 1) / kLanes;
         // flat stages keep nothing but the pipes and the PCM tile in LDS: 16-sample hand-overs fit two workgroups per CU (70 KB each)
         if (pl.chunk == 8 ? launch_systolic<true, KLATT_FLAT_CH, KLATT_FLAT_WPS, true, false, true>(a, b->mode, g, st)
                           : launch_systolic<true, 16, 1, true, false, true>(a, b->mode, g, st)) return -1;
-        a.flatRef = nullptr; a.sourceRef = nullptr; a.track = nullptr; a.deadWaves = nullptr; a.deadTerms = 0u;
+        a.flatRef = nullptr; a.sourceRef = nullptr; a.track = nullptr; a.deadWaves = nullptr; a.deadTerms = 0u; a.present2 = nullptr; a.deadTerms2 = 0u;
     }
     if (nDir > 0) {
         hipStream_t st = next_stream();
@@ -2142,7 +2148,7 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch)
     b->dDense.release(); b->dDenseStart.release(); b->dFacts.release(); b->hFacts.release();
     b->dRecords.release(); b->dShapeTable.release(); b->dRep.release(); b->dMismatch.release();
     b->dFrames.release(); b->dMeta.release(); b->dUtt.release(); b->dOrder.release(); b->dPcm.release(); b->dResult.release();
-    b->dFloat.release(); b->dDebug.release(); b->dDigest.release(); b->bounce.release(); b->dDeadWaves.release();
+    b->dFloat.release(); b->dDebug.release(); b->dDigest.release(); b->bounce.release(); b->dDeadWaves.release(); b->dPresent2.release();
     b->dFlatRef.release(); b->dSourceRef.release(); b->dJobs.release(); b->dShapes.release(); b->dTrack.release();
     b->dDirectJobs.release(); b->dDirectFirst.release(); b->dDirectHdr.release(); b->dDirectRec.release();
     delete b;
@@ -2422,6 +2428,7 @@ struct SetCall {
     long long nDirectUtt = 0;
     bool directAligned = false;                  // route_direct's verdict; false when the call forms no direct group (Batch::directAligned)
     std::vector<UttDesc> utt;
+    std::vector<uint32_t> present2;      // per utterance: its list's second word of present terms (UTT2_*)
     std::vector<long long> uttFrameStart;
     std::vector<uint32_t> uttFrames, uttList, uttSeed;
     LanePacking lanes;
@@ -2604,15 +2611,20 @@ static int set_frame_facts(SetCall& c)
     c.factsOnDevice = (c.framesPinned || c.byDevice) && c.earlyStarted;
     RawVector<FrameFacts>& fv = c.scratch.facts;
     if (c.byRecords) {
-        std::vector<uint32_t> shapeFl((size_t)in.nShapes);
-        for (long long s = 0; s < in.nShapes; ++s) shapeFl[(size_t)s] = shape_flags(reinterpret_cast<const double*>(in.shapes + s), maxFDirect, maxBwDirect);
+        std::vector<uint32_t> shapeFl((size_t)in.nShapes), shapeP2((size_t)in.nShapes);
+        for (long long s = 0; s < in.nShapes; ++s) {
+            shapeFl[(size_t)s] = shape_flags(reinterpret_cast<const double*>(in.shapes + s), maxFDirect, maxBwDirect);
+            shapeP2[(size_t)s] = shape_present2(reinterpret_cast<const double*>(in.shapes + s));
+        }
         fv.resize((size_t)nF);
         parallel_ranges(nF, 1 << 15, [&](long long a, long long e) {
             for (long long k = a; k < e; ++k) {
                 const speechPlayer_frameRecord_t& r = in.records[k];
                 FrameFacts f;
-                f.h0 = r.shape; f.h1 = ~0ull; f.pad = 0;
+                f.h0 = r.shape; f.h1 = ~0ull;
                 f.flags = r.shape == SPEECHPLAYER_RECORD_SILENCE ? 0u : (shapeFl[r.shape] | pitch_flags(r.voicePitch, r.endVoicePitch));
+                // (a silence record sets no bit in either word, where frame_facts on its all-zero frame would set several: it is a NULL frame, which classify_list skips)
+                f.present2 = r.shape == SPEECHPLAYER_RECORD_SILENCE ? 0u : present2_of(f.flags, shapeP2[r.shape]);
                 fv[k] = f;
             }
         });
@@ -2671,9 +2683,10 @@ static int set_plan(SetCall& c)
     const FrameFacts* const facts = c.facts;
     lists.shape.assign((size_t)nL, 0);
     lists.flags.assign((size_t)nL, 0);
+    lists.present2.assign((size_t)nL, 0);
     parallel_ranges(nL, 4096, [&](long long la, long long le) {
         for (long long l = la; l < le; ++l)
-            classify_list(meta + listStart[l], facts + listStart[l], listStart[l + 1] - listStart[l], lists.flags[l], lists.shape[l]);
+            classify_list(meta + listStart[l], facts + listStart[l], listStart[l + 1] - listStart[l], lists.flags[l], lists.shape[l], lists.present2[l]);
     });
     c.lap("classification");
     RouteOptions& route = c.route;
@@ -2763,7 +2776,7 @@ static void set_lanes(SetCall& c)
     const SetInput& in = c.in;
     const long long nU = c.nU;
     const long long* const listStart = c.listStart;
-    c.utt.resize((size_t)nU); c.uttFrameStart.resize((size_t)nU); c.uttFrames.resize((size_t)nU); c.uttList.resize((size_t)nU); c.uttSeed.resize((size_t)nU);
+    c.utt.resize((size_t)nU); c.present2.resize((size_t)nU); c.uttFrameStart.resize((size_t)nU); c.uttFrames.resize((size_t)nU); c.uttList.resize((size_t)nU); c.uttSeed.resize((size_t)nU);
     parallel_ranges(nU, 1 << 15, [&](long long a, long long e) {
         for (long long u = a; u < e; ++u) {
             const long long l = c.list_of(u);
@@ -2775,6 +2788,7 @@ static void set_lanes(SetCall& c)
             d.flags = c.lists.flags[l];
             d.length = c.lists.lens[l];
             c.utt[u] = d;
+            c.present2[u] = c.lists.present2[l];
             c.uttFrameStart[u] = d.frameStart; c.uttFrames[u] = d.nFrames; c.uttList[u] = (uint32_t)l; c.uttSeed[u] = d.seed;
         }
     });
@@ -2810,6 +2824,10 @@ static int set_upload(SetCall& c)
     }
     if (nTrackedUtt > 0 || nDirectUtt > 0) {
         if (b->dSourceRef.reserve((size_t)nF)) return -1;
+    }
+    if (nTrackedUtt > 0) {
+        if (b->dPresent2.reserve((size_t)nU)) return -1;
+        HIP_TRY(hipMemcpyAsync(b->dPresent2.ptr, c.present2.data(), (size_t)nU * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
     }
     if (nDirectUtt > 0) {
         const size_t nD = directJobs.size();
@@ -2873,6 +2891,8 @@ static int set_commit(SetCall& c)
     b->nQuiet = lanes.nQuietSlots; b->nNoNasal = lanes.nNoNasalSlots;      // (slots: the groups' utterances and the replicas that complete their sparse last wavefronts)
     b->nTracked = lanes.nTrackedUtt > 0 ? lanes.nTracked : 0; b->nTrackedUtt = lanes.nTrackedUtt;
     dead_wave_counts(lanes.order.data(), lanes.nQuietSlots, b->nTracked, [&](uint32_t u) { return c.utt[u].flags; }, KLATT_DEAD_TERMS, b->planDeadWaves);
+    dead2_wave_counts(lanes.order.data(), lanes.nQuietSlots, b->nTracked, [&](uint32_t u) { return c.utt[u].flags; }, [&](uint32_t u) { return c.present2[u]; },
+                      KLATT_DEAD_TERMS, b->planDead2Waves);
     b->nJobs = lanes.nTrackedUtt > 0 ? (long long)c.plan.jobs.size() : 0; b->trackEntries = lanes.nTrackedUtt > 0 ? (long long)c.plan.entries : 0;
     b->nDirect = c.nDirectUtt > 0 ? lanes.nDirectSlots : 0; b->nDirectUtt = c.nDirectUtt; b->nDirectFrames = (long long)c.scratch.directJobs.size();
     b->directAligned = c.nDirectUtt > 0 && c.directAligned;
@@ -3750,15 +3770,20 @@ int speechPlayer_batch_kernelInfo(speechPlayer_batch_t batch, int* info, int nIn
     }
     if (nInfo >= 23) {
         // the LAST launch's wavefronts (one per workgroup and stage) that ran without parallel 1 / turbulence / the aspiration generator, counted
-        // by the stages themselves; before the first launch of a batch: what the plan says they will be under the option as it stands
-        uint32_t dead[3] = {0u, 0u, 0u};
+        // by the stages themselves; before the first launch of a batch: what the plan says they will be under the option as it stands.
+        // Behind them (nInfo >= 23 + kDead2Counts), the same way: the wavefronts whose source stage ran without turbulence and the nasal pair,
+        // whose final stage ran without parallel 5 / without parallel 5 and 6, whose parallel stage ran without parallel 1..4 (dead2_wave_counts).
+        constexpr int kAll = 3 + kDead2Counts;
+        uint32_t dead[kAll] = {};
         if (b->launched && nTr > 0 && b->dDeadWaves.ptr) {
             HIP_TRY(hipStreamSynchronize(b->stream));      // (every launch joins its side streams into this one)
-            HIP_TRY(hipMemcpy(dead, b->dDeadWaves.ptr, sizeof dead, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(dead, b->dDeadWaves.ptr, sizeof dead, hipMemcpyDeviceToHost));      // one copy of the counters' block
         } else if (nTr > 0 && b->deadTerms) {
             for (int k = 0; k < 3; ++k) dead[k] = (uint32_t)std::min<long long>(b->planDeadWaves[k], 0x7FFFFFFFll);
+            for (int k = 0; k < kDead2Counts; ++k) dead[3 + k] = (uint32_t)std::min<long long>(b->planDead2Waves[k], 0x7FFFFFFFll);
         }
-        for (int k = 0; k < 3; ++k) info[20 + k] = (int)std::min<uint32_t>(dead[k], 0x7FFFFFFFu);
+        const int n = nInfo >= 20 + kAll ? kAll : 3;
+        for (int k = 0; k < n; ++k) info[20 + k] = (int)std::min<uint32_t>(dead[k], 0x7FFFFFFFu);
     }
     return 0;
 }
@@ -3872,7 +3897,7 @@ long long speechPlayer_frameFacts(const speechPlayer_frame_t* frames, long long 
     constexpr uint32_t kRouting = FACT_NOISE | FACT_NONFINITE | FACT_NASAL | FACT_UNBOUNDED;
     if (!onDevice) {
         parallel_ranges(nFrames, 1 << 13, [&](long long a, long long e) {
-            for (long long k = a; k < e; ++k) { out[k] = frame_facts(reinterpret_cast<const double*>(frames + k), maxF, maxBw); out[k].flags &= kRouting; }
+            for (long long k = a; k < e; ++k) { out[k] = frame_facts(reinterpret_cast<const double*>(frames + k), maxF, maxBw); out[k].flags &= kRouting; out[k].present2 = 0u; }
         });
         return nFrames;
     }
@@ -3886,7 +3911,7 @@ long long speechPlayer_frameFacts(const speechPlayer_frame_t* frames, long long 
     hipLaunchKernelGGL(klatt_frame_facts, dim3(grid), dim3(256), 0, nullptr, dF.ptr, dO.ptr, nFrames, maxF, maxBw);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, dO.ptr, (size_t)nFrames * sizeof(FrameFacts), hipMemcpyDeviceToHost));
-    for (long long k = 0; k < nFrames; ++k) out[k].flags &= kRouting;
+    for (long long k = 0; k < nFrames; ++k) { out[k].flags &= kRouting; out[k].present2 = 0u; }
     return nFrames;
 }
 

@@ -30,7 +30,7 @@ namespace klatt {
 struct FrameFacts {          // 24 B per frame
     unsigned long long h0, h1;   // hash of the 45 shape values (klatt_device.h, shape_param), bit patterns
     uint32_t flags;              // FACT_*
-    uint32_t pad;
+    uint32_t present2;           // UTT2_*: the second word of present terms (klatt_consts.h)
 };
 
 KLATT_LAYOUT_HD inline bool fact_finite(double v)
@@ -115,6 +115,28 @@ KLATT_LAYOUT_HD inline uint32_t shape_flags(const double* p, double maxF, double
     if (!inRange) fl |= 8u;                                                      // FACT_UNBOUNDED
     return fl;
 }
+// The second word of present terms (UTT2_*, klatt_consts.h), parallel resonators 2..6, by parallel 1's rule on their own parameters: term k
+// is (res_k(y) - y) * pa_k.  With pa_k zero of either sign it is a zero as long as res_k(y) stays finite: a stable pole pair (pb_k in
+// [1, 1e6]), a bounded frequency, a bounded input y = frication * fricationAmplitude * preFormantGain.  (Onto what the zero is added, and
+// what its sign may do: klatt_systolic.h, where the bodies without the terms are.)  p: all 47 parameters.
+// The nasal pair's bit is FACT_NASAL of the frame (present2_of below) AND one bound more, set here: FACT_NASAL bounds the SOURCE by
+// |voiceAmplitude|, |preFormantGain| and the pitches, which is all of it in a quiet list (UTT_NO_NASAL: aspirationAmplitude is 0 there).  A noisy
+// list's source is (aspiration * aspirationAmplitude + voice * voiceAmplitude) * preFormantGain * 0.5: with a finite aspirationAmplitude of 1e307
+// N0 overflows, (np - out) * 0 is NaN and the general body clips to +32000 where a body without the pair would hand on a finite sample.  So the
+// pair is present unless |aspirationAmplitude| <= 1e30 as well.
+KLATT_LAYOUT_HD inline uint32_t shape_present2(const double* p)
+{
+    uint32_t fl = !(fact_abs(p[6]) <= 1e30) ? UTT2_NASAL : 0u;
+    const bool bounded = (fact_abs(p[24]) <= 1e30) && (fact_abs(p[44]) <= 1e30);
+    for (int k = 2; k <= 6; ++k) {
+        const double pf = p[24 + k], pb = p[30 + k], pa = p[36 + k];
+        if (pa != 0.0 || !(pb >= 1.0) || !(pb <= 1e6) || !(fact_abs(pf) <= 1e6) || !bounded) fl |= 1u << (k - 2);
+    }
+    return fl;
+}
+// ... and the whole word: the nasal pair's bit is also FACT_NASAL of the frame's flags (shape_flags | pitch_flags), carried where no routing drops it
+KLATT_LAYOUT_HD inline uint32_t present2_of(uint32_t flags, uint32_t shapePresent2) { return shapePresent2 | ((flags & FACT_NASAL) ? UTT2_NASAL : 0u); }
+
 // are the 45 shape values (parameters 1..45) of two frames the same bits?
 KLATT_LAYOUT_HD inline bool shape_values_equal(const double* a, const double* c)
 {
@@ -148,7 +170,7 @@ KLATT_LAYOUT_HD inline FrameFacts frame_facts(const double* p, double maxF, doub
     }
     x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull; x ^= x >> 32;
     y ^= y >> 31; y *= 0xBF58476D1CE4E5B9ull; y ^= y >> 29;
-    o.h0 = x; o.h1 = y; o.flags = fl; o.pad = 0;
+    o.h0 = x; o.h1 = y; o.flags = fl; o.present2 = present2_of(fl, shape_present2(p));
     return o;
 }
 

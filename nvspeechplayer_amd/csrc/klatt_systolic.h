@@ -66,10 +66,15 @@ namespace klatt {
 #endif
 constexpr int kStages = 4;
 #ifndef KLATT_DEAD_TERMS
-#define KLATT_DEAD_TERMS 3      // flat launches: the bodies without a dead term that are built -- 1 the parallel stage without parallel 1, 2 the source stage without
+#define KLATT_DEAD_TERMS 123    // flat launches: the bodies without a dead term that are built -- 1 the parallel stage without parallel 1, 2 the source stage without
                                 // turbulence, 4 the source stage without turbulence and the aspiration generator.  4 is not built: with it the kernel takes
                                 // 250 VGPRs (MODE_FAST 252) instead of 248, for cfg2 7.99 -> 7.97 ms, within the spread, and cfg3 6.57 -> 6.44
                                 // (profiles/dead_terms.txt; 256 of cfg2's 896 wavefronts have no aspiration: the producer puts a puff behind voiceless stops)
+                                // By the utterances' second word of present terms (UTT2_*, klatt_consts.h; profiles/dead_terms2.txt): 8 the source stage without
+                                // turbulence AND the nasal pair, 16 the final stage without parallel 5, 32 the final stage without parallel 5 and 6, 64 the
+                                // parallel stage without parallel 1..4 (the frication generator and y stay).  All four are built: each on its own, against the
+                                // build without it, five alternating rounds on cfg2 -- 8: 7.76 -> 7.55 ms, 16: 7.64 -> 7.55, 32: 7.64 -> 7.55, 64: 7.72 -> 7.55,
+                                // every round apart, no other batch slower; 248 VGPRs and no scratch as before.
 #endif
 #ifndef KLATT_FLAT_SOURCE
 #define KLATT_FLAT_SOURCE 1     // flat launches: S0 is a flat stage too (0: the source stage of the noisy launches, with its frame state machine)
@@ -1005,10 +1010,14 @@ __device__ __forceinline__ void flat2_switch(FlatState2<FD>& f, const StageCtx& 
     uint32_t moving = 0, still = 0;            // entries of the stage's kinds before this one, among the moving / among the others
 #pragma unroll
     for (int e = 0; e < FD::NE; ++e) {
-        if constexpr (FD::SKIP != 0u) {      // the kinds left out between the previous kind of the list and this one (none of them is N0)
+        if constexpr (FD::SKIP != 0u) {      // the kinds left out between the previous kind of the list and this one (N0 takes two entries here too)
 #pragma unroll
             for (int k = 0; k < kTrackEntries; ++k)
-                if (((FD::SKIP >> k) & 1u) && k < GE[e] && (e == 0 || k > GE[e - 1])) { const bool mv = (p.mask >> k) & 1u; moving += mv ? 1u : 0u; still += mv ? 0u : 1u; }
+                if (((FD::SKIP >> k) & 1u) && k < GE[e] && (e == 0 || k > GE[e - 1])) {
+                    const bool mv = (p.mask >> k) & 1u;
+                    const uint32_t ws = k == 0 ? 2u : 1u;
+                    moving += mv ? ws : 0u; still += mv ? 0u : ws;
+                }
         }
         const bool moves = (p.mask >> GE[e]) & 1u;
         f.idx[e] = (part + (moves ? hdr + moving : still)) * 16u;
@@ -1318,6 +1327,15 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
         for (uint32_t bit = UTT_TURBULENCE; bit <= UTT_PARALLEL1; bit <<= 1) deadSet |= __any((mine & bit) != 0u) ? 0u : bit;
         deadSet = (uint32_t)__builtin_amdgcn_readfirstlane((int)(deadSet & A.deadTerms));
     }
+    // ... and the same AND over the lanes' second word (UTT2_*: parallel 2..6, the nasal pair), which only the flat launch is handed
+    uint32_t deadSet2 = 0;
+    if (FLAT && A.deadTerms2 != 0u) {
+        const uint32_t mine2 = live ? A.present2[u] : 0u;
+#pragma unroll
+        for (uint32_t bit = UTT2_PARALLEL2; bit <= UTT2_NASAL; bit <<= 1) deadSet2 |= __any((mine2 & bit) != 0u) ? 0u : bit;
+        deadSet2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(deadSet2 & A.deadTerms2));
+    }
+    (void)deadSet2;
 
     // hand-overs of the flat stages (BarrierSync above): pipe X = S0 -> S1, O = S1 -> final, A and B = S3 -> final
     auto make_sync = [&](auto, auto, auto, int, int, int) __attribute__((always_inline)) { return BarrierSync{}; };
@@ -1334,16 +1352,28 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
             // DEAD (chosen once per wavefront from its live lanes' UTT_TURBULENCE / UTT_ASPIRATION): 1 -- no lane has turbulence: its gain and the
             // open quotient, which gates nothing else, are not read and kind 21 is not in the list; 2 -- nor aspiration: the generator goes
             // as well (the frication generator of the parallel stage steps a sub-sequence of its own: nothing else reads this state)
-            auto sourceStage = [&](auto deadTag) __attribute__((always_inline)) {
+            // NONASAL (UTT2_NASAL dead in every live lane: caNP is zero of either sign in every frame, N0 / NP bounded and stable, the source
+            // bounded -- FACT_NASAL for the voice, the gain and the pitches, and |aspirationAmplitude| <= 1e30, which a noisy list's source needs as
+            // well: klatt_plan.h, shape_present2): the stage hands on the source sample `out` itself.  The general body hands on
+            // out + (np - out) * caNP with np finite: out + (+-0), which is `out` bit for bit unless out is -0 and the product +0, where the
+            // general body holds +0 and this one -0.  A zero of the other sign stays a zero through the cascade (a * (+-0) + b * z1 + c * z2: every
+            // sum is the same number or a zero in both), the mix and the gain, and (int)(+-0) is 0: the int16 cannot differ.  N0, NP, their
+            // memories and kinds 0, 1 and 14 are not there; flat2_switch steps over their entries (N0's two).
+            auto sourceStage = [&](auto deadTag, auto noNasalTag) __attribute__((always_inline)) {
             constexpr int DEAD = decltype(deadTag)::value;
             constexpr bool NOTURB = DEAD >= 1;
+            constexpr bool NONASAL = decltype(noNasalTag)::value;
+            (void)NONASAL;
 #if KLATT_FLAT_LAYOUT == 2
             // the source AND the head of the cascade: N0 (anti), NP mixed in by caNP (reference src/speechWaveGenerator.cpp:149-152)
-            using FD = FlatDesc<0, 2, NOTURB ? 4 : 5, true, 0, 0, double, NOTURB ? (1u << 21) : 0u>;
-            constexpr int GE[7] = {0, 1, 14, 20, NOTURB ? 22 : 21, NOTURB ? 23 : 22, 23};     // N0, NP | cur: caNP, - | vibratoPitchOffset, vibratoSpeed, turbulence, openQuotient, voiceAmplitude, aspirationAmplitude, preFormantGain
-            constexpr int CB = 2;                                 // f.cur[CB + k]: the source's parameters
-            constexpr uint32_t kUsualS0 = NOTURB ? 0x37u : 0x67u, kAllS0 = NOTURB ? 0x3Fu : 0x7Fu, kVibBit = 8u;      // usually: N0, NP, caNP, the amplitudes and the gain
-            constexpr bool kHead = true;
+            constexpr bool kHead = !NONASAL;
+            constexpr uint32_t kSkipS0 = (NOTURB ? (1u << 21) : 0u) | (kHead ? 0u : 0x4003u);
+            using FD = FlatDesc<0, kHead ? 2 : 0, NOTURB ? (kHead ? 4 : 3) : (kHead ? 5 : 4), kHead, 0, 0, double, kSkipS0>;
+            // N0, NP | cur: caNP, - | vibratoPitchOffset, vibratoSpeed, turbulence, openQuotient, voiceAmplitude, aspirationAmplitude, preFormantGain (without the head: from kind 20 on)
+            constexpr int GE[7] = {kHead ? 0 : 20, kHead ? 1 : (NOTURB ? 22 : 21), kHead ? 14 : (NOTURB ? 23 : 22), kHead ? 20 : 23, NOTURB ? 22 : 21, NOTURB ? 23 : 22, 23};
+            constexpr int CB = kHead ? 2 : 0;                     // f.cur[CB + k]: the source's parameters
+            constexpr uint32_t kUsualS0 = kHead ? (NOTURB ? 0x37u : 0x67u) : (NOTURB ? 0x6u : 0xCu), kAllS0 = kHead ? (NOTURB ? 0x3Fu : 0x7Fu) : (NOTURB ? 0x7u : 0xFu);      // usually: N0, NP, caNP, the amplitudes and the gain
+            constexpr uint32_t kVibBit = kHead ? 8u : 1u;
 #else
             using FD = FlatDesc<0, 0, NOTURB ? 3 : 4, false, 0, 0, double, NOTURB ? (1u << 21) : 0u>;
             constexpr int GE[4] = {20, NOTURB ? 22 : 21, NOTURB ? 23 : 22, 23};     // cur: vibratoPitchOffset, vibratoSpeed, turbulence, openQuotient, voiceAmplitude, aspirationAmplitude, preFormantGain
@@ -1355,6 +1385,7 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
             if (A.deadWaves && lane == 0) {
                 if (DEAD >= 1) atomicAdd(A.deadWaves + 1, 1u);
                 if (DEAD >= 2) atomicAdd(A.deadWaves + 2, 1u);
+                if (NONASAL) atomicAdd(A.deadWaves + 3, 1u);
             }
             bool staleNP = false;       // NP's `a` in its register predates the last rows (mixed chunks derive it on the fly)
             FlatState2<FD> f;
@@ -1442,7 +1473,7 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
                         run = run < room ? run : room;
                         run = run < 1u ? 1u : run;
                         int cc = c;
-                        if (kHead && staleNP) { f.ra[1] = 1.0 - f.rb[1] - f.rc[1]; staleNP = false; }
+                        if constexpr (kHead) { if (staleNP) { f.ra[1] = 1.0 - f.rb[1] - f.rc[1]; staleNP = false; } }
                         for (uint32_t q = 0; q < run; ++q) {
                             if (f.live) {
 #pragma unroll
@@ -1534,9 +1565,11 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
                 A.result[u] = res;
             }
             };
-            if ((KLATT_DEAD_TERMS & 4) && (deadSet & (UTT_TURBULENCE | UTT_ASPIRATION)) == (UTT_TURBULENCE | UTT_ASPIRATION)) sourceStage(std::integral_constant<int, 2>{});
-            else if ((KLATT_DEAD_TERMS & 2) && (deadSet & UTT_TURBULENCE)) sourceStage(std::integral_constant<int, 1>{});
-            else sourceStage(std::integral_constant<int, 0>{});
+            // (the body without the nasal pair is built without turbulence only: one more body, taken when both are dead)
+            if ((KLATT_DEAD_TERMS & 8) && KLATT_FLAT_LAYOUT == 2 && (deadSet & UTT_TURBULENCE) && (deadSet2 & UTT2_NASAL)) sourceStage(std::integral_constant<int, 1>{}, std::true_type{});
+            else if ((KLATT_DEAD_TERMS & 4) && (deadSet & (UTT_TURBULENCE | UTT_ASPIRATION)) == (UTT_TURBULENCE | UTT_ASPIRATION)) sourceStage(std::integral_constant<int, 2>{}, std::false_type{});
+            else if ((KLATT_DEAD_TERMS & 2) && (deadSet & UTT_TURBULENCE)) sourceStage(std::integral_constant<int, 1>{}, std::false_type{});
+            else sourceStage(std::integral_constant<int, 0>{}, std::false_type{});
         }
     } else if (stage == 0) {
         // ================= S0: frame + glottal source (+ aspiration noise) =================
@@ -1735,23 +1768,40 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
         if constexpr (FLAT) {
             // NOP1: no live lane of the wavefront has parallel resonator 1 present (UTT_PARALLEL1): its term (res(y) - y) * pa1 is +-0 onto
             // a sum that starts at +0, so the sum starts with parallel 2's term; the resonator, its memories and kind 8 are not there
-            auto parallel = [&](auto noP1Tag) __attribute__((always_inline)) {
-            constexpr bool NOP1 = decltype(noP1Tag)::value;
-            constexpr int NR = NOP1 ? 3 : 4;
-            using FD = FlatDesc<3, NR, 3, false, NOP1 ? 0x3Bu : 0x77u, 0, sig_t, NOP1 ? (1u << 8) : 0u>;      // usually parallel 1..3 and the gains
-            constexpr int GE[7] = {NOP1 ? 9 : 8, NOP1 ? 10 : 9, NOP1 ? 11 : 10, NOP1 ? 17 : 11, NOP1 ? 18 : 17, NOP1 ? 19 : 18, 19};     // parallel 1..4 | cur: fricationAmplitude, preFormantGain, pa1..pa4
+            // NONE: nor parallel 2, 3, 4 (UTT2_PARALLEL2..4): every term is (res(y) - y) * (+-0) with res(y) finite, and the general body's sum is
+            // +0 + (+-0) four times over: +0 bit for bit, which this body hands on as it is.  The frication generator and y stay (the final stage
+            // reads y); the four resonators, their memories, kinds 8..11 and the gains' kinds 18 and 19 are not there.
+            auto parallel = [&](auto noP1Tag, auto noneTag) __attribute__((always_inline)) {
+            constexpr bool NONE = decltype(noneTag)::value;
+            constexpr bool NOP1 = decltype(noP1Tag)::value || NONE;
+            constexpr int NR = NONE ? 0 : (NOP1 ? 3 : 4);
+            using FD = FlatDesc<3, NR, NONE ? 1 : 3, false, NONE ? 0u : (NOP1 ? 0x3Bu : 0x77u), 0, sig_t, NONE ? 0xC0F00u : (NOP1 ? (1u << 8) : 0u)>;      // usually parallel 1..3 and the gains
+            // parallel 1..4 | cur: fricationAmplitude, preFormantGain, pa1..pa4 (NONE: kind 17 alone)
+            constexpr int GE[7] = {NONE ? 17 : (NOP1 ? 9 : 8), NOP1 ? 10 : 9, NOP1 ? 11 : 10, NOP1 ? 17 : 11, NOP1 ? 18 : 17, NOP1 ? 19 : 18, 19};
             FlatState2<FD> f;
             flat2_init<FD>(f, live, d, X, GE);
-            if (NOP1 && A.deadWaves && lane == 0) atomicAdd(A.deadWaves + 0, 1u);
+            if (A.deadWaves && lane == 0) {
+                if (NOP1) atomicAdd(A.deadWaves + 0, 1u);
+                if (NONE) atomicAdd(A.deadWaves + 6, 1u);
+            }
             sig_t fricNoise = 0;
             uint32_t noiseSt = noise_step(noise_first(nkey, ninc), ninc);     // frication: values 1, 3, 5, ...
             flat2_loop<FD, CH>(1, nIter, nChunks, stage, f, X, GE,
                 [&](int c, int i, auto setTag, const auto& mid) __attribute__((always_inline)) {
                     constexpr uint32_t SET = decltype(setTag)::value;      // the kinds this chunk loads (0: a steady chunk)
+                    if constexpr (NONE) {
+                        fricNoise = (sig_t)noise_uniform(noiseSt) + (sig_t)0.75 * fricNoise;
+                        noiseSt = noise_step2(noiseSt, ninc2);
+                        const sig_t fric = fricNoise * (sig_t)0.3 * f.cur[0];
+                        const sig_t y = (fric * f.cur[1]) * (sig_t)0.5;
+                        mid(y);
+                        PIPE(pipeA, c, i) = y; PIPE(pipeB, c, i) = (sig_t)0;
+                    } else {
+                    constexpr int R1 = NR > 1 ? 1 : 0, R2 = NR > 2 ? 2 : 0;
                     const ResPre<sig_t> q0 = res_pre<MODE, ((SET >> 0) & 1u) != 0u>(f.ra[0], f.rb[0], f.rc[0], f.z1[0], f.z2[0]);
-                    const ResPre<sig_t> q1 = res_pre<MODE, ((SET >> 1) & 1u) != 0u>(f.ra[1], f.rb[1], f.rc[1], f.z1[1], f.z2[1]);
-                    const ResPre<sig_t> q2 = res_pre<MODE, ((SET >> 2) & 1u) != 0u>(f.ra[2], f.rb[2], f.rc[2], f.z1[2], f.z2[2]);
-                    constexpr int R3 = NR - 1;      // (the general body's fourth resonator)
+                    const ResPre<sig_t> q1 = res_pre<MODE, ((SET >> 1) & 1u) != 0u>(f.ra[R1], f.rb[R1], f.rc[R1], f.z1[R1], f.z2[R1]);
+                    const ResPre<sig_t> q2 = res_pre<MODE, ((SET >> 2) & 1u) != 0u>(f.ra[R2], f.rb[R2], f.rc[R2], f.z1[R2], f.z2[R2]);
+                    constexpr int R3 = NR > 0 ? NR - 1 : 0;      // (the general body's fourth resonator)
                     ResPre<sig_t> q3{};
                     if constexpr (!NOP1) q3 = res_pre<MODE, ((SET >> 3) & 1u) != 0u>(f.ra[R3], f.rb[R3], f.rc[R3], f.z1[R3], f.z2[R3]);
                     fricNoise = (sig_t)noise_uniform(noiseSt) + (sig_t)0.75 * fricNoise;
@@ -1763,9 +1813,9 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
                         mid(q0, q1, q2, y, pa2, pa3, pa4);
                         sig_t w = res_post<MODE>(q0, y, f.z1[0], f.z2[0]);
                         sig_t par = (w - y) * pa2;
-                        w = res_post<MODE>(q1, y, f.z1[1], f.z2[1]);
+                        w = res_post<MODE>(q1, y, f.z1[R1], f.z2[R1]);
                         par += (w - y) * pa3;
-                        w = res_post<MODE>(q2, y, f.z1[2], f.z2[2]);
+                        w = res_post<MODE>(q2, y, f.z1[R2], f.z2[R2]);
                         par += (w - y) * pa4;
                         PIPE(pipeA, c, i) = y; PIPE(pipeB, c, i) = par;
                     } else {
@@ -1773,33 +1823,52 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
                         sig_t par = 0;
                         sig_t w = res_post<MODE>(q0, y, f.z1[0], f.z2[0]);
                         par += (w - y) * pa1;
-                        w = res_post<MODE>(q1, y, f.z1[1], f.z2[1]);
+                        w = res_post<MODE>(q1, y, f.z1[R1], f.z2[R1]);
                         par += (w - y) * pa2;
-                        w = res_post<MODE>(q2, y, f.z1[2], f.z2[2]);
+                        w = res_post<MODE>(q2, y, f.z1[R2], f.z2[R2]);
                         par += (w - y) * pa3;
                         w = res_post<MODE>(q3, y, f.z1[R3], f.z2[R3]);
                         par += (w - y) * pa4;
                         PIPE(pipeA, c, i) = y; PIPE(pipeB, c, i) = par;
                     }
+                    }
                 },
                 noChunk, make_sync(std::integral_constant<int, L::kBufs>{}, I0{}, I1{}, 0, 0, 4));
             };
-            if ((KLATT_DEAD_TERMS & 1) && (deadSet & UTT_PARALLEL1)) parallel(std::true_type{}); else parallel(std::false_type{});
+            if ((KLATT_DEAD_TERMS & 64) && (deadSet & UTT_PARALLEL1) && (deadSet2 & kUtt2Parallel234) == kUtt2Parallel234) parallel(std::true_type{}, std::true_type{});
+            else if ((KLATT_DEAD_TERMS & 1) && (deadSet & UTT_PARALLEL1)) parallel(std::true_type{}, std::false_type{});
+            else parallel(std::false_type{}, std::false_type{});
         }
     } else if (FLAT && (KLATT_FLAT_EXHAUSTIVE || stage == 2)) {
         // ================= flat final stage: r3, r2, r1 | parallel 5, 6, bypass | gain, clip, int16 -> PCM =================
         if constexpr (FLAT) {
+            // GONE (UTT2_PARALLEL5, UTT2_PARALLEL6 dead in every live lane): 1 -- without parallel 5: its term (res(y) - y) * pa5 is +-0 (res(y) finite:
+            // klatt_plan.h, parallel_present) onto the partial sum `par` of the parallel stage, which stays what it is unless it is -0 and the
+            // term +0, where the general body holds +0 and this one -0; 2 -- nor parallel 6, by the same rule on the same sum: kind 15 (pa5, pa6)
+            // goes with it.  A zero of the other sign stays a zero through parallel 6's term, the bypass mix par + (y - par) * bypass, the add
+            // to the cascade's sample, the gain and the clip (all finite: a tracked utterance has no non-finite parameter), and (int)(+-0)
+            // is 0: the int16 cannot differ.  flat2_switch steps over kinds 12 (13, 15); bypass mix, gain, clip and PCM stay.
+            auto finalStage = [&](auto goneTag) __attribute__((always_inline)) {
+            constexpr int GONE = decltype(goneTag)::value;
 #if KLATT_FLAT_LAYOUT == 2
-            constexpr int GE[4] = {12, 13, 15, 16};               // parallel 5, 6 | cur: pa5, pa6, parallelBypass, outputGain
-            using FD = FlatDesc<2, 2, 2, false, 0xEu>;                 // usually parallel 6 and the gains
+            // parallel 5, 6 | cur: pa5, pa6, parallelBypass, outputGain
+            constexpr int GE[4] = {GONE == 2 ? 16 : (GONE == 1 ? 13 : 12), GONE == 1 ? 15 : 13, GONE == 1 ? 16 : 15, 16};
+            using FD = FlatDesc<2, 2 - GONE, GONE == 2 ? 1 : 2, false, GONE == 0 ? 0xEu : 0u, 0, sig_t,
+                                GONE == 2 ? ((1u << 12) | (1u << 13) | (1u << 15)) : (GONE == 1 ? (1u << 12) : 0u)>;      // usually parallel 6 and the gains
+            // (GONE 1: the list IS the general body's usual set -- parallel 6 and the gains -- so its usual and all-kinds chunks are one and USUAL says 0)
             constexpr int RS = 0;                                      // cascade resonators in this stage
 #else
+            static_assert(GONE == 0, "the final stage's lightened bodies: layout 2");
             constexpr int GE[6] = {6, 7, 12, 13, 15, 16};         // r2, r1, parallel 5, 6 | cur: pa5, pa6, parallelBypass, outputGain
             using FD = FlatDesc<2, 4, 2, false, 0x3Bu>;                // usually c2, c1, parallel 6 and the gains
             constexpr int RS = 2;
 #endif
             FlatState2<FD> f;
             flat2_init<FD>(f, live, d, X, GE);
+            if (A.deadWaves && lane == 0) {
+                if (GONE >= 1) atomicAdd(A.deadWaves + 4, 1u);
+                if (GONE >= 2) atomicAdd(A.deadWaves + 5, 1u);
+            }
             int16_t* const myRow = reinterpret_cast<int16_t*>(tile + lane * kTileStride);
             uint32_t it = 0;
             auto flush_tile = [&](uint32_t tileStart, uint32_t validTo) __attribute__((always_inline)) {
@@ -1834,23 +1903,32 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
                 [&](int c, int i, auto setTag, const auto& mid) __attribute__((always_inline)) {
                     constexpr uint32_t SET = decltype(setTag)::value;      // the kinds this chunk loads (0: a steady chunk)
                     // resonators of the stage: RS of the cascade's last ones, then parallel 5 and 6
-                    constexpr int NR = 2 + RS;
+                    constexpr int NR = 2 - GONE + RS;
+                    constexpr int G0 = GONE == 2 ? 0 : 2;      // f.cur[G0 ..]: parallelBypass, outputGain
                     ResPre<sig_t> q[4];
 #pragma unroll
                     for (int r = 0; r < NR; ++r) q[r] = ((SET >> r) & 1u) ? res_pre<MODE, true>(f.ra[r], f.rb[r], f.rc[r], f.z1[r], f.z2[r])
                                                                           : res_pre<MODE, false>(f.ra[r], f.rb[r], f.rc[r], f.z1[r], f.z2[r]);
-                    const sig_t pa5 = f.cur[0], pa6 = f.cur[1], bypass = f.cur[2], outGain = f.cur[3];
-                    if constexpr (RS == 2) mid(q[0], q[1], q[2], q[3], pa5, pa6, bypass, outGain);
+                    const sig_t pa5 = f.cur[0], pa6 = f.cur[GONE == 2 ? 0 : 1], bypass = f.cur[G0], outGain = f.cur[G0 + 1];
+                    (void)pa5; (void)pa6;
+                    if constexpr (GONE == 2) mid(bypass, outGain);
+                    else if constexpr (GONE == 1) mid(q[0], pa6, bypass, outGain);
+                    else if constexpr (RS == 2) mid(q[0], q[1], q[2], q[3], pa5, pa6, bypass, outGain);
                     else mid(q[0], q[1], pa5, pa6, bypass, outGain);
                     sig_t o = PIPE(pipeO, c, i);
                     const sig_t y = PIPE(pipeA, c, i);
 #pragma unroll
                     for (int r = 0; r < RS; ++r) o = res_post<MODE>(q[r], o, f.z1[r], f.z2[r]);
                     sig_t par = PIPE(pipeB, c, i);
-                    sig_t w = res_post<MODE>(q[RS], y, f.z1[RS], f.z2[RS]);
-                    par += (w - y) * pa5;
-                    w = res_post<MODE>(q[RS + 1], y, f.z1[RS + 1], f.z2[RS + 1]);
-                    par += (w - y) * pa6;
+                    if constexpr (GONE == 0) {
+                        const sig_t w = res_post<MODE>(q[RS], y, f.z1[RS], f.z2[RS]);
+                        par += (w - y) * pa5;
+                    }
+                    if constexpr (GONE <= 1) {
+                        constexpr int R6 = RS + 1 - GONE;
+                        const sig_t w = res_post<MODE>(q[R6], y, f.z1[R6], f.z2[R6]);
+                        par += (w - y) * pa6;
+                    }
                     par = fade_value(par, y, bypass);
                     const sig_t mix = o + par;
                     const sig_t v = (mix * outGain) * (sig_t)4000.0;
@@ -1861,6 +1939,11 @@ __global__ void __launch_bounds__(kLanes * kStages, WPS) klatt_systolic(const Ke
                 [&]() __attribute__((always_inline)) { it += kChunk; if ((it % kTile) == 0) flush_tile(it - kTile, it); },
                 make_sync(std::integral_constant<int, L::kBufs>{}, I2{}, I0{}, 2, 4, 0));
             if ((it % kTile) != 0) flush_tile(it - (it % kTile), it);
+            };
+            constexpr bool kLight = KLATT_FLAT_LAYOUT == 2;
+            if (kLight && (KLATT_DEAD_TERMS & 32) && (deadSet2 & (UTT2_PARALLEL5 | UTT2_PARALLEL6)) == (UTT2_PARALLEL5 | UTT2_PARALLEL6)) finalStage(std::integral_constant<int, kLight ? 2 : 0>{});
+            else if (kLight && (KLATT_DEAD_TERMS & 16) && (deadSet2 & UTT2_PARALLEL5)) finalStage(std::integral_constant<int, kLight ? 1 : 0>{});
+            else finalStage(std::integral_constant<int, 0>{});
         }
     } else if (!NOISE && !NASAL && (stage == 1 || stage == 2)) {
         // ================= quiet, nasal-free S1: r6, r5, r4 and S2: r3, r2, r1 =================

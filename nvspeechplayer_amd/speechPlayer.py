@@ -2545,10 +2545,14 @@ class BatchPlayer(object):
         return ms
 
     def kernelInfo(self):
-        info = np.zeros(23, dtype=np.int32)
+        info = np.zeros(27, dtype=np.int32)
         self._check(self._dll.speechPlayer_batch_kernelInfo(self._h, info.ctypes.data, len(info)))
         # (the last launch's wavefronts -- one per workgroup and stage of the tracked group -- that ran without a dead term, option "dead_terms")
         dead = dict(waves_without_parallel1=int(info[20]), waves_without_turbulence=int(info[21]), waves_without_aspiration=int(info[22]))
+        # (... and by the utterances' second word of present terms: the source stage without turbulence and the nasal pair, the final stage without
+        # parallel 5 / without parallel 5 and 6, the parallel stage without parallel 1..4)
+        dead.update(stages_without_nasal=int(info[23]), stages_without_parallel5=int(info[24]), stages_without_parallel56=int(info[25]),
+                    stages_without_parallel1to4=int(info[26]))
         return dict(vgprs=int(info[0]), lds_bytes=int(info[1]), wavefronts=int(info[2]), cus=int(info[3]),
                     workgroups_per_cu_by_lds=int(info[4]), scratch_bytes=int(info[5]),
                     stage_parallel_chunk=int(info[6]), noisy_group=bool(info[7]),
