@@ -462,7 +462,8 @@ long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const
  *   equal     out == sr does no filtering: the result is speechPlayer_batch_exportPcm's output exactly
  * Like the spectrogram, and unlike the exports of the batch "as set", the result is a function of the batch's PCM: it depends on the
  * mode and, in MODE_FAST, on whatever that mode's tolerance allows; it needs a synthesis launch.
- * Out of scope: live handles (resampling across pulls needs filter state); NodePlayer, which reaches the export through
+ * Out of scope: live handles through this export (resampling across pulls needs filter state: "Signal stages", below, keep it --
+ * speechPlayer_batch_stageResample); NodePlayer, which reaches the export through
  * speechPlayer_node_part; a label grid at the target rate (see "ratio" for where output sample m lies).  A spectrogram at the target
  * rate is speechPlayer_batch_exportSpectrogramOf of this export's output ("The exports of a signal", below).
  *
@@ -771,8 +772,8 @@ long long speechPlayer_signalConvolve(const void* x, int inFormat, long long len
  * runs agree everywhere except possibly in the signs of zeros; and the closing + 0.0f makes a zero +0.  This is what lets a wavefront pad
  * rows with fewer sections up to its instantiation's 1, 2, 4, 8 or 16.
  * Over the pool the result is a function of the batch's PCM: it depends on the mode and needs a synthesis launch.
- * Out of scope: live handles (the filter state would have to persist across pulls); NodePlayer; zero-phase (forward-backward)
- * filtering; initial conditions in or out; time-parallel (scan) formulations, which cannot meet the sequential statement's bits.  For
+ * Out of scope: live handles and initial conditions in or out through this export (the filter state would have to persist across pulls:
+ * "Signal stages", below, keep it -- speechPlayer_batch_stageFilter); NodePlayer; zero-phase (forward-backward) filtering; time-parallel (scan) formulations, which cannot meet the sequential statement's bits.  For
  * the same reason a row cannot be cut in time: a call of fewer than 64 x 1024 rows underfills the device, and that is accepted.
  *
  * Host only, touch no device: the definition above on `length` samples of plain PCM (speechPlayer_pcmFilter) or of a signal's row,
@@ -840,7 +841,8 @@ long long speechPlayer_batch_exportFilteredOf(speechPlayer_batch_t batch, const 
  * the ADPCM recursion are those of CPython's audioop (tests/golden/codec_golden.npz records its answers).
  * Over the pool the result is a function of the batch's PCM: it depends on the mode and needs a synthesis launch.
  * Out of scope: G.722, G.726, GSM and anything without an independent statement to hold it to; packed nibbles and WAV block headers or
- * predictor resets; packet loss; live handles (the ADPCM state would have to persist across pulls); NodePlayer.
+ * predictor resets; packet loss; live handles through this export (the ADPCM state would have to persist across pulls: "Signal stages",
+ * below, keep it -- speechPlayer_batch_stageCode); NodePlayer.
  *
  * Host only, touch no device: the definition above on `length` samples of plain PCM (speechPlayer_pcmCode) or of a signal's row, int16
  * (inFormat 0) or float32 (inFormat 1) (speechPlayer_signalCode) -- the statements the device is held to bit for bit.  decodedOut:
@@ -869,6 +871,67 @@ long long speechPlayer_batch_exportCoded(speechPlayer_batch_t batch, const long 
 	int format, unsigned char* codesOut, long long rowStride, void* stream);
 long long speechPlayer_batch_exportCodedOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
 	int codec, void* decodedOut, int format, unsigned char* codesOut, long long rowStride, void* stream);
+/*
+ * Signal stages: the resampler, the biquad filter and the codecs fed chunk by chunk -- what a live handle's pulls need.  The whole-row
+ * exports above start every call from a fresh state, so calling them per pull clicks at every chunk edge and starts the ADPCM predictor
+ * anew.  A STAGE is a device-resident object of a fixed number of rows that holds the per-row state of ONE sequential export between
+ * calls.  It belongs to a batch, which gives it the device, the staging blocks and the sixteen-in-flight slots, as it does to the exports
+ * of a signal: a batch that was never set is enough.  (The resampler's table is the stage's own, uploaded once when it is made: the
+ * batch's table follows the last whole-row request.)  It is freed by speechPlayer_stage_free or with its batch.
+ *   resample  (srcRate, outRate, zeros, rolloff, window, beta: the resampler's arguments and refusals.)  Per row: N, the samples
+ *             consumed; M, the outputs emitted; and the last taps - 1 = 2 Z - 1 consumed samples as float32 -- x of what came in, +0
+ *             before the start.  Equal rates pass the samples through and keep no state (Z = 0 below).
+ *   filter    (sections, secStart, nFilters, filterOf, tail: the filter's arguments and refusals; filterOf is per row of the STAGE.)
+ *             Per row: s1, s2 of each of its K sections.
+ *   code      (codec 0 ulaw, 1 alaw, 2 adpcm.)  Per row: ADPCM's val and idx.  The G.711 laws carry none and take the same interface.
+ * A PUSH takes a speechPlayer_signal_t of exactly nRows rows; row i of the signal is row i of the stage.  The rows are int16 or float32,
+ * padded or packed, and the format may differ from push to push.  A row of length 0 is untouched.  end (may be NULL: none): per row,
+ * nonzero ends the row with this push.  With c the row's length in this push and N' = N + c:
+ *   resample, open   emits the outputs m = M .. M' - 1, M' = ceil(max(N' - Z, 0) up / down): exactly the outputs whose taps
+ *                    n0 - Z + 1 .. n0 + Z, n0 = floor(m down / up), all lie at or before sample N' - 1 (n0 + Z <= N' - 1 <=> m down <
+ *                    (N' - Z) up).  Inputs before sample 0 are +0, as in the definition.
+ *   resample, ended  emits up to M' = ceil(N' up / down), the definition's count; inputs past N' - 1 are +0.  Afterwards the row is
+ *                    fresh: N = M = 0, the history zeros.
+ *   filter           open: c outputs, and the states as they are after exactly c samples.  Ended: c + tail outputs (tail samples of zero
+ *                    input), then the states are +0.
+ *   code             c outputs -- codes, decoded samples or both, as speechPlayer_batch_exportCoded --; ended: val = idx = 0 afterwards.
+ * Lemma (the history's length).  With N consumed, output M is the first not emitted: n0(M) + Z > N - 1, so its oldest tap
+ * n0(M) - Z + 1 >= N - 2 Z + 1, and n0 does not decrease with m: no later output reaches further back.  The samples N - 2 Z + 1 .. N - 1
+ * are 2 Z - 1 values, which is what a row keeps.
+ * The claim.  For every row, the outputs of its pushes up to and including the one that ends it, concatenated, are bit for bit what
+ * speechPlayer_signalResample / speechPlayer_signalFilter (with tail) / speechPlayer_signalCode give on the concatenation of its chunks --
+ * a chunk of int16 and a chunk of float32 count alike, each through x --, under those exports' bounds: finite samples of magnitude at
+ * most 2^16, finite values in the filter.  A row pushed again after its end is a fresh row.
+ * The outputs come as the exports' pair: deviceOut (format 0 int16, 1 float32; for a code stage the decoded samples) and, a code stage
+ * only, deviceCodes (unsigned char), rowStride > 0 padded rows (+0 and code 0 past a row's outputs) or 0 the rows back to back;
+ * outLengths (may be NULL): the nRows output counts.  They feed the next stage as its chunk.  Returns the elements of ONE output.
+ * A push reads the chunk on `stream`, as the exports of a signal do; the pushes of one stage follow one another by events, whatever streams
+ * they are issued on.  There are no repeats and no selection: a repeated row would race on its state.  A row's N may not pass 2^44.
+ * speechPlayer_stage_plan is host only and changes nothing: what a push of rows of these lengths with these end flags would emit per row
+ * (outLengths may be NULL); it returns their sum.  speechPlayer_stage_reset makes the chosen rows (rows[i] nonzero; NULL: all) fresh behind
+ * the stage's last push; speechPlayer_stage_counts copies out N and M (either may be NULL).  speechPlayer_resampleEmitted is host only and
+ * needs no stage: the outputs a resampler row has emitted after `consumed` samples, open or ended; the difference of two is a push's count.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT (the makers return NULL, the others -1), nothing written AND THE STATE UNCHANGED: what the
+ * resampler, the filter and the codecs refuse of their arguments (when the stage is made); nRows outside 1 .. 2^20; a chunk whose row
+ * count is not the stage's; what the exports of a signal refuse of the signal, the output, rowStride and the format; an output or
+ * deviceCodes that overlaps the chunk, or the two each other; a row that would pass 2^44; a stage that was freed, alone or with its
+ * batch (the handle names nothing any more); for a code stage, neither output given; deviceCodes on a stage that is not a code stage.
+ * Out of scope: the convolution, spectrogram, LPC, pitch and tempo exports chunk by chunk; saving a stage's state to the host; NodePlayer;
+ * a fused kernel for a chain of stages.  The kernels are csrc/klatt_stage.h.
+ */
+typedef void* speechPlayer_stage_t;
+speechPlayer_stage_t speechPlayer_batch_stageResample(speechPlayer_batch_t batch, long long nRows, int srcRate, int outRate, int zeros, double rolloff,
+	int window, double beta);
+speechPlayer_stage_t speechPlayer_batch_stageFilter(speechPlayer_batch_t batch, long long nRows, const float* sections, const long long* secStart,
+	long long nFilters, const long long* filterOf, long long tail);
+speechPlayer_stage_t speechPlayer_batch_stageCode(speechPlayer_batch_t batch, long long nRows, int codec);
+long long speechPlayer_stage_plan(speechPlayer_stage_t stage, const long long* lengths, const unsigned char* end, long long* outLengths);
+long long speechPlayer_stage_push(speechPlayer_stage_t stage, const speechPlayer_signal_t* chunk, const unsigned char* end, void* deviceOut, int format,
+	void* deviceCodes, long long rowStride, long long* outLengths, void* stream);
+int speechPlayer_stage_reset(speechPlayer_stage_t stage, const unsigned char* rows, void* stream);
+int speechPlayer_stage_counts(speechPlayer_stage_t stage, long long* consumed, long long* emitted);
+void speechPlayer_stage_free(speechPlayer_stage_t stage);
+long long speechPlayer_resampleEmitted(long long consumed, int srcRate, int outRate, int zeros, double rolloff, int ended);
 /*
  * Linear prediction (LPC) of a batch's PCM, or of a signal's rows, on the step grid of the other exports: per analysis frame the
  * autocorrelation, the prediction coefficients, the reflection coefficients and the prediction error; and, per sample, the residual or

@@ -76,6 +76,8 @@ EXPORTS = [
     "speechPlayer_pcmPitch", "speechPlayer_signalPitch", "speechPlayer_batch_exportPitch", "speechPlayer_batch_exportPitchOf",
     "speechPlayer_tempoLength", "speechPlayer_tempoFrames", "speechPlayer_pcmTempo", "speechPlayer_signalTempo",
     "speechPlayer_batch_exportTempoPositions", "speechPlayer_batch_exportTempoPositionsOf", "speechPlayer_batch_exportTempo", "speechPlayer_batch_exportTempoOf",
+    "speechPlayer_batch_stageResample", "speechPlayer_batch_stageFilter", "speechPlayer_batch_stageCode", "speechPlayer_stage_plan", "speechPlayer_stage_push",
+    "speechPlayer_stage_reset", "speechPlayer_stage_counts", "speechPlayer_stage_free", "speechPlayer_resampleEmitted",
 ]
 
 
@@ -497,6 +499,24 @@ def load():
     L.speechPlayer_signalPower.argtypes = [vp, i32, i64, vp]
     L.speechPlayer_signalMix.restype = i64
     L.speechPlayer_signalMix.argtypes = [vp, i32, i64, ctypes.c_float, vp, i64, vp, i64, vp, i32, vp, i64]
+    L.speechPlayer_batch_stageResample.restype = vp
+    L.speechPlayer_batch_stageResample.argtypes = [vp, i64, i32, i32, i32, f64, i32, f64]
+    L.speechPlayer_batch_stageFilter.restype = vp
+    L.speechPlayer_batch_stageFilter.argtypes = [vp, i64, vp, vp, i64, vp, i64]
+    L.speechPlayer_batch_stageCode.restype = vp
+    L.speechPlayer_batch_stageCode.argtypes = [vp, i64, i32]
+    L.speechPlayer_stage_plan.restype = i64
+    L.speechPlayer_stage_plan.argtypes = [vp, vp, vp, vp]
+    L.speechPlayer_stage_push.restype = i64
+    L.speechPlayer_stage_push.argtypes = [vp, vp, vp, vp, i32, vp, i64, vp, vp]
+    L.speechPlayer_stage_reset.restype = i32
+    L.speechPlayer_stage_reset.argtypes = [vp, vp, vp]
+    L.speechPlayer_stage_counts.restype = i32
+    L.speechPlayer_stage_counts.argtypes = [vp, vp, vp]
+    L.speechPlayer_stage_free.restype = None
+    L.speechPlayer_stage_free.argtypes = [vp]
+    L.speechPlayer_resampleEmitted.restype = i64
+    L.speechPlayer_resampleEmitted.argtypes = [i64, i32, i32, i32, f64, i32]
     _lib = L
     return L
 

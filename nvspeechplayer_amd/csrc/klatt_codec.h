@@ -31,8 +31,8 @@
 //                   (float32), 16 (int16) or 8 (uint8: 64 codes touch at most 5 aligned 16 bytes) lanes a row.  The step table is 89
 //                   dwords of LDS read per lane by idx -- a lane-indexed register array would become scratch.
 //   Out of scope    G.722, G.726, GSM and anything without an independent statement to hold it to; packed nibbles (codes[0::2] << 4 |
-//                   codes[1::2] is the usual byte order) and WAV block headers or predictor resets; packet loss; live handles (the ADPCM
-//                   state would have to persist across pulls); NodePlayer.
+//                   codes[1::2] is the usual byte order) and WAV block headers or predictor resets; packet loss; live handles through these
+//                   kernels (the ADPCM state would have to persist across pulls: klatt_stage.h keeps it); NodePlayer.
 #pragma once
 
 #include "klatt_filter.h"

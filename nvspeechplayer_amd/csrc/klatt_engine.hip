@@ -25,6 +25,7 @@
 #include "klatt_convolve.h"
 #include "klatt_filter.h"
 #include "klatt_codec.h"
+#include "klatt_stage.h"
 #include "klatt_lpc.h"
 #include "klatt_pitch.h"
 #include "klatt_tempo.h"
@@ -563,6 +564,7 @@ int pick_device(int device)
 // ------------------------------------------------------------------------------------------
 // Batch
 // ------------------------------------------------------------------------------------------
+struct Stage;
 struct Batch {
     int sampleRate = 0;
     int device = 0;
@@ -696,7 +698,55 @@ struct Batch {
     bool hasBank = false;
     DeviceBuffer<float> dBank;
     SharedTable bankOrder;
+    // klatt_stage.h: the signal stages made on this batch; freed with it
+    std::vector<Stage*> stages;
 };
+
+// ---- a signal stage (klatt_stage.h): the per-row state of one sequential export, fed chunk by chunk ---------------------------------------
+// It belongs to a batch, which gives it the device, the staging blocks and the sixteen-in-flight slots.  The resampler's table is the
+// stage's own, uploaded once when it is made: the batch's table follows the last whole-row request, and two stages at different rates on
+// one batch would upload theirs again at every push.  Its pushes follow one another by `done`, whichever streams they are issued on.
+struct Stage {
+    Batch* b = nullptr;
+    StageGeometry g;
+    long long nRows = 0;
+    std::vector<long long> N, M;               // [nRows] consumed and emitted since the row's start
+    ResPlan res;                               // resample
+    DeviceBuffer<float> dTable;                // [taps][up]
+    DeviceBuffer<float> dHist[2];              // [nRows][2 Z - 1] each; dHist[cur] is what the next push reads
+    int cur = 0;
+    FilterPlan fil;                            // filter
+    std::vector<long long> secAt, secN;        // [nRows] the row's filter: its first section and its sections
+    DeviceBuffer<float> dFilterState;          // [nRows][kStageFilterState]
+    int codec = 0;                             // code
+    DeviceBuffer<int> dCodeState;              // [nRows][2]
+    hipEvent_t done = nullptr;
+    bool used = false;
+};
+std::mutex g_stageMutex;
+std::vector<Stage*> g_stages;                  // every live stage: a handle that is not here was freed (or never made)
+
+bool stage_known(Stage* s)
+{
+    std::lock_guard<std::mutex> lock(g_stageMutex);
+    return std::find(g_stages.begin(), g_stages.end(), s) != g_stages.end();
+}
+// Frees a live stage: its last push first
+void stage_release(Stage* s)
+{
+    {
+        std::lock_guard<std::mutex> lock(g_stageMutex);
+        g_stages.erase(std::remove(g_stages.begin(), g_stages.end(), s), g_stages.end());
+    }
+    if (s->b) {
+        (void)hipSetDevice(s->b->device);
+        auto& all = s->b->stages;
+        all.erase(std::remove(all.begin(), all.end(), s), all.end());
+    }
+    if (s->done) { if (s->used) (void)hipEventSynchronize(s->done); (void)hipEventDestroy(s->done); }
+    s->dTable.release(); s->dHist[0].release(); s->dHist[1].release(); s->dFilterState.release(); s->dCodeState.release();
+    delete s;
+}
 
 // The batch's own streams wait (on the device) for the exports that still read its pool.
 int wait_exports(Batch* b)
@@ -2120,6 +2170,7 @@ void speechPlayer_batch_destroy(speechPlayer_batch_t batch)
     Batch* b = static_cast<Batch*>(batch);
     if (!b) return;
     (void)hipSetDevice(b->device);
+    while (!b->stages.empty()) stage_release(b->stages.back());      // (its signal stages go with it)
     (void)sync_exports(b);      // (exports on the callers' streams may still read the pool)
     for (auto& s : b->exportSlot) {
         if (s.done) (void)hipEventDestroy(s.done);
@@ -5332,6 +5383,452 @@ long long speechPlayer_batch_exportCodedOf(speechPlayer_batch_t batch, const spe
     const char* what = "exportCodedOf";
     if (refuse_timing_only("speechPlayer_batch_exportCodedOf")) return -1;
     return coded_export(what, batch, true, signal, rows, nRows, codec, decodedOut, format, codesOut, rowStride, stream);
+}
+
+// ---- signal stages (klatt_stage.h): the resampler, the filter and the codecs chunk by chunk ---------------------------------------------------
+static_assert(sizeof(StageResRow) % 8 == 0 && sizeof(StageLaneRow) % 8 == 0, "rows are arrays of 8-byte words");
+
+// Host only, touches no device: the outputs a resampler stage has emitted after `consumed` samples of a row, open or ended
+long long speechPlayer_resampleEmitted(long long consumed, int srcRate, int outRate, int zeros, double rolloff, int ended)
+{
+    begin_call();
+    const char* what = "resampleEmitted";
+    if (consumed < 0 || consumed > kResampleMaxLength) { set_error("%s: %lld samples consumed (0 .. 2^44)", what, consumed); return -1; }
+    try {
+        ResPlan P;
+        std::string why;
+        if (!res_plan(P, srcRate, outRate, zeros, rolloff, 0, 0.0, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        return stage_res_emitted(consumed, P.identity ? 0 : P.Z, P.up, P.down, ended != 0);
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
+// A stage of nRows rows on `batch`: fill(b, s) plans it and makes its state (+0) on the device; then it is the batch's and a live handle
+extern "C++" template <class Fill>
+static speechPlayer_stage_t stage_create(const char* what, speechPlayer_batch_t batch, long long nRows, Fill fill)
+{
+    begin_call();
+    Batch* b = static_cast<Batch*>(batch);
+    if (!b) { set_error("%s: no batch", what); return nullptr; }
+    if (nRows < 1 || nRows > kStageMaxRows) { set_error("%s: nRows %lld (1 .. 2^20)", what, nRows); return nullptr; }
+    Stage* s = nullptr;
+    try {
+        s = new Stage;
+        s->nRows = nRows;
+        s->N.assign((size_t)nRows, 0); s->M.assign((size_t)nRows, 0);
+        const auto made = [&]() -> int {
+            if (fill(b, s)) return -1;
+            HIP_TRY(hipSetDevice(b->device));
+            HIP_TRY(hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
+            HIP_TRY(hipStreamSynchronize(b->stream));      // (the state's zeros are there)
+            return 0;
+        };
+        if (made()) { stage_release(s); return nullptr; }
+        s->b = b;
+        b->stages.push_back(s);
+        std::lock_guard<std::mutex> lock(g_stageMutex);
+        g_stages.push_back(s);
+        return s;
+    } catch (const std::exception& e) {
+        set_error("%s: %s", what, e.what());
+        if (s) stage_release(s);
+        return nullptr;
+    }
+}
+// n dwords of +0 on the batch's device, behind the batch's stream
+extern "C++" template <class T>
+static int stage_zeros(Batch* b, DeviceBuffer<T>& buf, size_t n)
+{
+    static_assert(sizeof(T) == 4, "a state is dwords");
+    HIP_TRY(hipSetDevice(b->device));
+    if (buf.reserve(n)) return -1;
+    HIP_TRY(hipMemsetAsync(buf.ptr, 0, n * sizeof(T), b->stream));
+    return 0;
+}
+
+speechPlayer_stage_t speechPlayer_batch_stageResample(speechPlayer_batch_t batch, long long nRows, int srcRate, int outRate, int zeros, double rolloff, int window, double beta)
+{
+    const char* what = "stageResample";
+    return stage_create(what, batch, nRows, [&](Batch* b, Stage* s) -> int {
+        std::string why;
+        if (!res_plan(s->res, srcRate, outRate, zeros, rolloff, window, beta, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        ResPlan& P = s->res;
+        s->g.kind = kStageResample; s->g.up = P.up; s->g.down = P.down; s->g.Z = P.identity ? 0 : P.Z;
+        if (P.identity) return 0;      // equal rates: no table, no state
+        res_transpose(P);
+        HIP_TRY(hipSetDevice(b->device));
+        if (s->dTable.reserve(P.hT.size())) return -1;
+        HIP_TRY(hipMemcpy(s->dTable.ptr, P.hT.data(), P.hT.size() * sizeof(float), hipMemcpyHostToDevice));
+        std::vector<float>().swap(P.table); std::vector<float>().swap(P.hT);      // (the device holds what the pushes read)
+        const size_t n = (size_t)s->nRows * (size_t)stage_history(P.Z);
+        return stage_zeros(b, s->dHist[0], n) || stage_zeros(b, s->dHist[1], n) ? -1 : 0;
+    });
+}
+
+speechPlayer_stage_t speechPlayer_batch_stageFilter(speechPlayer_batch_t batch, long long nRows, const float* sections, const long long* secStart, long long nFilters,
+                                                    const long long* filterOf, long long tail)
+{
+    const char* what = "stageFilter";
+    return stage_create(what, batch, nRows, [&](Batch* b, Stage* s) -> int {
+        std::string why;
+        if (!filter_plan(s->fil, sections, secStart, nFilters, tail, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        s->g.kind = kStageFilter; s->g.tail = tail;
+        s->secAt.resize((size_t)s->nRows); s->secN.resize((size_t)s->nRows);
+        for (long long i = 0; i < s->nRows; ++i) {
+            const long long j = filter_row(s->fil, filterOf, i, why);
+            if (j < 0) { set_error("%s: %s", what, why.c_str()); return -1; }
+            s->secAt[(size_t)i] = s->fil.start[(size_t)j];
+            s->secN[(size_t)i] = s->fil.start[(size_t)j + 1] - s->fil.start[(size_t)j];
+        }
+        return stage_zeros(b, s->dFilterState, (size_t)s->nRows * kStageFilterState);
+    });
+}
+
+speechPlayer_stage_t speechPlayer_batch_stageCode(speechPlayer_batch_t batch, long long nRows, int codec)
+{
+    const char* what = "stageCode";
+    return stage_create(what, batch, nRows, [&](Batch* b, Stage* s) -> int {
+        if (codec < 0 || codec >= kCodecCount) { set_error("%s: codec %d (0 ulaw, 1 alaw, 2 adpcm)", what, codec); return -1; }
+        s->g.kind = kStageCode; s->codec = codec;
+        return codec == kCodecAdpcm ? stage_zeros(b, s->dCodeState, (size_t)s->nRows * 2) : 0;      // (the G.711 laws carry no state)
+    });
+}
+
+// The stage a handle names, or null with the message set: a handle that was freed -- alone or with its batch -- names none
+static Stage* stage_of(const char* what, speechPlayer_stage_t stage)
+{
+    Stage* s = static_cast<Stage*>(stage);
+    if (!s) { set_error("%s: no stage", what); return nullptr; }
+    if (!stage_known(s)) { set_error("%s: %p is not a stage (freed, alone or with its batch?)", what, stage); return nullptr; }
+    return s;
+}
+
+// What a push of rows of len(i) samples with these end flags emits per row (stage_row_plan), as an export's selection; -1 with the message set
+extern "C++" template <class Len>
+static int stage_selection(const char* what, const Stage* s, Len len, const unsigned char* end, ExportSelection& sel)
+{
+    sel.n = s->nRows;
+    sel.counts.resize((size_t)s->nRows);
+    for (long long i = 0; i < s->nRows; ++i) {
+        const long long c = len(i);
+        long long out;
+        if (!stage_row_plan(s->g, s->N[(size_t)i], s->M[(size_t)i], c, end && end[i], out)) {
+            set_error("%s: row %lld has consumed %lld samples and would take %lld more (0 or more, at most 2^44 in all)", what, i, s->N[(size_t)i], c);
+            return -1;
+        }
+        sel.counts[(size_t)i] = out;
+        sel.most = std::max(sel.most, out);
+        sel.total += out;
+    }
+    return 0;
+}
+
+long long speechPlayer_stage_plan(speechPlayer_stage_t stage, const long long* lengths, const unsigned char* end, long long* outLengths)
+{
+    begin_call();
+    const char* what = "stage_plan";
+    Stage* s = stage_of(what, stage);
+    if (!s) return -1;
+    if (!lengths) { set_error("%s: no lengths", what); return -1; }
+    try {
+        ExportSelection sel;
+        if (stage_selection(what, s, [&](long long i) { return lengths[i]; }, end, sel)) return -1;
+        for (long long i = 0; outLengths && i < s->nRows; ++i) outLengths[i] = sel.counts[(size_t)i];
+        return sel.total;
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
+// One push's passage through a slot: ExportStage over a signal, behind the stage's last push whichever stream that was on
+struct StagePass {
+    Stage* s;
+    ExportStage stage;
+    StagePass(Stage* s, hipStream_t st, const StageBlock& block) : s(s), stage(s->b, st, block, nullptr, false, true) {}
+    int begin()
+    {
+        if (stage.begin()) return -1;
+        if (s->used) HIP_TRY(hipStreamWaitEvent(stage.st, s->done, 0));
+        return 0;
+    }
+    int finish()
+    {
+        HIP_TRY(hipEventRecord(s->done, stage.st));
+        s->used = true;
+        return stage.finish();
+    }
+};
+
+extern "C++" template <int K>
+static void (*stage_filter_kernel(int inFormat, int format))(StageFilterArgs)
+{
+    void (*const kernels[2][2])(StageFilterArgs) = {{klatt_stage_filter<K, false, int16_t>, klatt_stage_filter<K, true, int16_t>},
+                                                    {klatt_stage_filter<K, false, float>, klatt_stage_filter<K, true, float>}};
+    return kernels[inFormat][format];
+}
+
+// The rows of a filter or ADPCM stage's push, packed into wavefronts (filter_pack)
+static void stage_lane_rows(const Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long rowStride,
+                            std::vector<StageLaneRow>& packed, std::vector<FilterGroup>& groups)
+{
+    std::vector<StageLaneRow> rows((size_t)s->nRows);
+    long long before = 0;
+    for (long long i = 0; i < s->nRows; ++i) {
+        StageLaneRow& r = rows[(size_t)i];
+        r.src = in.at(i); r.len = in.len(i); r.outLen = sel.counts[(size_t)i]; r.dst = tile_row_first(i, rowStride, before);
+        r.secAt = s->g.kind == kStageFilter ? s->secAt[(size_t)i] : 0;
+        r.sections = s->g.kind == kStageFilter ? s->secN[(size_t)i] : 1;
+        r.state = i; r.ended = end && end[i];
+        before += r.outLen;
+    }
+    filter_pack(rows, packed, groups);
+}
+
+static int stage_push_resample(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long elements, void* deviceOut, int format,
+                               long long rowStride, hipStream_t st)
+{
+    Batch* b = s->b;
+    const bool identity = s->g.Z == 0;
+    if (identity && elements == 0) return 0;
+    std::vector<StageResRow> rows((size_t)s->nRows);
+    std::vector<ResRow> plain;
+    long long before = 0;
+    for (long long i = 0; i < s->nRows; ++i) {
+        rows[(size_t)i] = StageResRow{in.at(i), in.len(i), s->N[(size_t)i], s->M[(size_t)i], sel.counts[(size_t)i], tile_row_first(i, rowStride, before), end && end[i]};
+        if (identity) plain.push_back(ResRow{in.at(i), in.len(i), sel.counts[(size_t)i], rows[(size_t)i].dst});
+        before += sel.counts[(size_t)i];
+    }
+    std::vector<long long> words;
+    const TileTable tiles = tile_row_table(sel.counts.data(), sel.n, kResampleTile, rowStride, kTimelineChunkLog2, words);
+    StageBlock block;
+    const int rowsAt = identity ? block.add(plain) : block.add(rows), wordsAt = block.add(words);
+    StagePass pass(s, st, block);
+    if (pass.begin()) return -1;
+    const unsigned grid = (unsigned)std::min<long long>(tiles.nTiles, 8ll * b->cus);
+    if (identity) {      // equal rates: the copy kernel of the whole-row export
+        ResArgs A;
+        A.in = in.data; A.rows = pass.stage.device<ResRow>(rowsAt);
+        A.tile = tile_out(pass.stage, wordsAt, tiles, rowStride, deviceOut);
+        A.hT = nullptr; A.up = A.down = 1; A.Z = 0; A.span = kResampleTile;
+        void (*const copies[2][2])(ResArgs) = {{klatt_signal_copy<false, int16_t>, klatt_signal_copy<true, int16_t>}, {klatt_signal_copy<false, float>, klatt_signal_copy<true, float>}};
+        hipLaunchKernelGGL(copies[in.format()][format], dim3(grid), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        return pass.finish();
+    }
+    const int H = stage_history(s->g.Z);
+    const float* from = s->dHist[s->cur].ptr;
+    float* to = s->dHist[s->cur ^ 1].ptr;
+    if (tiles.nTiles > 0) {
+        StageResArgs A;
+        A.in = in.data; A.rows = pass.stage.device<StageResRow>(rowsAt);
+        A.tile = tile_out(pass.stage, wordsAt, tiles, rowStride, deviceOut);
+        A.hT = s->dTable.ptr; A.hist = from;
+        A.up = s->g.up; A.down = s->g.down; A.Z = s->g.Z; A.span = res_span(s->res);
+        void (*const kernels[2][2])(StageResArgs) = {{klatt_stage_resample<false, int16_t>, klatt_stage_resample<true, int16_t>},
+                                                     {klatt_stage_resample<false, float>, klatt_stage_resample<true, float>}};
+        hipLaunchKernelGGL(kernels[in.format()][format], dim3(grid), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    // the next history, into the buffer nothing of this push reads
+    const long long cells = s->nRows * H;
+    const unsigned hgrid = (unsigned)std::min<long long>((cells + 255) / 256, 4ll * b->cus);
+    hipLaunchKernelGGL(in.format() ? klatt_stage_history<float> : klatt_stage_history<int16_t>, dim3(hgrid), dim3(256), 0, st, in.data,
+                       pass.stage.device<StageResRow>(rowsAt), s->nRows, H, from, to);
+    HIP_TRY(hipGetLastError());
+    if (pass.finish()) return -1;
+    s->cur ^= 1;
+    return 0;
+}
+
+static int stage_push_filter(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, void* deviceOut, int format, long long rowStride,
+                             hipStream_t st)
+{
+    Batch* b = s->b;
+    std::vector<StageLaneRow> packed;
+    std::vector<FilterGroup> groups;
+    stage_lane_rows(s, in, end, sel, rowStride, packed, groups);
+    StageBlock block;
+    const int rowsAt = block.add(packed), groupsAt = block.add(groups), sectionsAt = block.add(s->fil.sections);
+    StagePass pass(s, st, block);
+    if (pass.begin()) return -1;
+    StageFilterArgs A;
+    A.in = in.data; A.rows = pass.stage.device<StageLaneRow>(rowsAt);
+    A.sections = pass.stage.device<FilterSection>(sectionsAt);
+    A.rowStride = rowStride; A.out = deviceOut; A.state = s->dFilterState.ptr;
+    for (size_t first = 0; first < groups.size();) {      // the groups of one bucket lie together
+        size_t last = first;
+        while (last < groups.size() && groups[last].bucket == groups[first].bucket) ++last;
+        A.groups = pass.stage.device<FilterGroup>(groupsAt) + first;
+        A.nGroups = (long long)(last - first);
+        void (*kernel)(StageFilterArgs) = nullptr;
+        switch (groups[first].bucket) {
+            case 1: kernel = stage_filter_kernel<1>(in.format(), format); break;
+            case 2: kernel = stage_filter_kernel<2>(in.format(), format); break;
+            case 4: kernel = stage_filter_kernel<4>(in.format(), format); break;
+            case 8: kernel = stage_filter_kernel<8>(in.format(), format); break;
+            default: kernel = stage_filter_kernel<16>(in.format(), format); break;
+        }
+        const unsigned grid = (unsigned)std::min<long long>(A.nGroups, 64ll * b->cus);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFilterLanes), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        first = last;
+    }
+    return pass.finish();
+}
+
+static int stage_push_code(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long elements, void* decodedOut, int format,
+                           void* codesOut, long long rowStride, hipStream_t st)
+{
+    Batch* b = s->b;
+    if (s->codec != kCodecAdpcm) {      // no state: the tile kernel of the whole-row export
+        if (elements == 0) return 0;
+        std::vector<ResRow> rows((size_t)s->nRows);
+        long long before = 0;
+        for (long long i = 0; i < s->nRows; ++i) {
+            rows[(size_t)i] = ResRow{in.at(i), in.len(i), sel.counts[(size_t)i], tile_row_first(i, rowStride, before)};
+            before += sel.counts[(size_t)i];
+        }
+        std::vector<long long> words;
+        const TileTable tiles = tile_row_table(sel.counts.data(), sel.n, kCodeTile, rowStride, kTimelineChunkLog2, words);
+        StageBlock block;
+        const int rowsAt = block.add(rows), wordsAt = block.add(words);
+        StagePass pass(s, st, block);
+        if (pass.begin()) return -1;
+        CodeArgs A;
+        A.in = in.data; A.rows = pass.stage.device<ResRow>(rowsAt);
+        A.tile = tile_out(pass.stage, wordsAt, tiles, rowStride, decodedOut);
+        A.codes = static_cast<uint8_t*>(codesOut);
+        void (*const ulaw[2][2])(CodeArgs) = {{klatt_code_g711<kCodecUlaw, false, int16_t>, klatt_code_g711<kCodecUlaw, true, int16_t>},
+                                              {klatt_code_g711<kCodecUlaw, false, float>, klatt_code_g711<kCodecUlaw, true, float>}};
+        void (*const alaw[2][2])(CodeArgs) = {{klatt_code_g711<kCodecAlaw, false, int16_t>, klatt_code_g711<kCodecAlaw, true, int16_t>},
+                                              {klatt_code_g711<kCodecAlaw, false, float>, klatt_code_g711<kCodecAlaw, true, float>}};
+        const unsigned grid = (unsigned)std::min<long long>(tiles.nTiles, 8ll * b->cus);
+        hipLaunchKernelGGL((s->codec == kCodecUlaw ? ulaw : alaw)[in.format()][format], dim3(grid), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        return pass.finish();
+    }
+    std::vector<StageLaneRow> packed;
+    std::vector<FilterGroup> groups;
+    stage_lane_rows(s, in, end, sel, rowStride, packed, groups);
+    StageBlock block;
+    const int rowsAt = block.add(packed), groupsAt = block.add(groups);
+    StagePass pass(s, st, block);
+    if (pass.begin()) return -1;
+    StageAdpcmArgs A;
+    A.in = in.data; A.rows = pass.stage.device<StageLaneRow>(rowsAt);
+    A.groups = pass.stage.device<FilterGroup>(groupsAt); A.nGroups = (long long)groups.size();
+    A.rowStride = rowStride; A.decoded = decodedOut; A.codes = static_cast<uint8_t*>(codesOut); A.state = s->dCodeState.ptr;
+    // [input format][outputs - 1][output format]; the codes alone have no output format.  Nothing to write: the codes' kernel, which then
+    // only moves the states
+    constexpr int D = kCodeDecoded, C = kCodeCodes;
+    void (*const kernels[2][3][2])(StageAdpcmArgs) = {
+        {{klatt_stage_adpcm<D, false, int16_t>, klatt_stage_adpcm<D, true, int16_t>}, {klatt_stage_adpcm<C, false, int16_t>, klatt_stage_adpcm<C, false, int16_t>},
+         {klatt_stage_adpcm<D | C, false, int16_t>, klatt_stage_adpcm<D | C, true, int16_t>}},
+        {{klatt_stage_adpcm<D, false, float>, klatt_stage_adpcm<D, true, float>}, {klatt_stage_adpcm<C, false, float>, klatt_stage_adpcm<C, false, float>},
+         {klatt_stage_adpcm<D | C, false, float>, klatt_stage_adpcm<D | C, true, float>}}};
+    const int outputs = elements == 0 ? C : (decodedOut ? D : 0) | (codesOut ? C : 0);
+    const unsigned grid = (unsigned)std::min<long long>(A.nGroups, 64ll * b->cus);
+    hipLaunchKernelGGL(kernels[in.format()][outputs - 1][format], dim3(grid), dim3(kFilterLanes), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    return pass.finish();
+}
+
+long long speechPlayer_stage_push(speechPlayer_stage_t stage, const speechPlayer_signal_t* chunk, const unsigned char* end, void* deviceOut, int format,
+                                  void* deviceCodes, long long rowStride, long long* outLengths, void* stream)
+{
+    const char* what = "stage_push";
+    if (refuse_timing_only("speechPlayer_stage_push")) return -1;
+    begin_call();
+    Stage* s = stage_of(what, stage);
+    if (!s) return -1;
+    Batch* b = s->b;
+    try {
+        const bool code = s->g.kind == kStageCode;
+        if (tile_request(what, format, rowStride)) return -1;
+        if (!code && deviceCodes) { set_error("%s: deviceCodes on a stage that is not a code stage", what); return -1; }
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, true, chunk, sig, in)) return -1;
+        if (sig.nRows != s->nRows) { set_error("%s: a chunk of %lld rows for a stage of %lld", what, sig.nRows, s->nRows); return -1; }
+        ExportSelection sel;
+        if (stage_selection(what, s, [&](long long i) { return sig.len(i); }, end, sel)) return -1;
+        bool active = false;      // a row that is neither fed nor ended is untouched
+        for (long long i = 0; i < s->nRows && !active; ++i) active = sig.len(i) > 0 || (end && end[i]);
+        const long long elements = export_elements(what, kSampleNouns, sel, rowStride, 1);
+        if (elements < 0) return -1;
+        if (code && elements > 0 && !deviceOut && !deviceCodes) { set_error("%s: no output (the decoded samples, the codes or both)", what); return -1; }
+        if (elements > 0 || active) {
+            HIP_TRY(hipSetDevice(b->device));
+            const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
+            if (elements > 0) {
+                if ((!code || deviceOut) && export_output(b, what, deviceOut, elements, elSize)) return -1;
+                if (deviceCodes && export_output(b, what, deviceCodes, elements, 1)) return -1;
+                if (deviceOut && deviceCodes) {
+                    const uintptr_t d = reinterpret_cast<uintptr_t>(deviceOut), c = reinterpret_cast<uintptr_t>(deviceCodes);
+                    if (d < c + (size_t)elements && c < d + (size_t)elements * elSize) { set_error("%s: the decoded samples and the codes overlap", what); return -1; }
+                }
+            }
+            if (signal_memory(in, what, deviceOut, deviceOut ? (size_t)elements * elSize : 0) || (deviceCodes && signal_memory(in, what, deviceCodes, (size_t)elements))) return -1;
+            hipStream_t st = static_cast<hipStream_t>(stream);
+            const int rc = s->g.kind == kStageResample ? stage_push_resample(s, in, end, sel, elements, deviceOut, format, rowStride, st)
+                         : s->g.kind == kStageFilter   ? stage_push_filter(s, in, end, sel, deviceOut, format, rowStride, st)
+                                                       : stage_push_code(s, in, end, sel, elements, deviceOut, format, deviceCodes, rowStride, st);
+            if (rc) return -1;
+        }
+        for (long long i = 0; i < s->nRows; ++i) {
+            stage_row_advance(s->N[(size_t)i], s->M[(size_t)i], sig.len(i), end && end[i], sel.counts[(size_t)i]);
+            if (outLengths) outLengths[i] = sel.counts[(size_t)i];
+        }
+        return elements;
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
+// The chosen rows (NULL: all) are fresh again: N = M = 0 and their state +0, behind the stage's last push
+int speechPlayer_stage_reset(speechPlayer_stage_t stage, const unsigned char* rows, void* stream)
+{
+    begin_call();
+    const char* what = "stage_reset";
+    Stage* s = stage_of(what, stage);
+    if (!s) return -1;
+    try {
+        uint32_t* state = nullptr;
+        int perRow = 0;
+        if (s->g.kind == kStageResample && s->g.Z > 0) { state = reinterpret_cast<uint32_t*>(s->dHist[s->cur].ptr); perRow = stage_history(s->g.Z); }
+        else if (s->g.kind == kStageFilter) { state = reinterpret_cast<uint32_t*>(s->dFilterState.ptr); perRow = kStageFilterState; }
+        else if (s->g.kind == kStageCode && s->codec == kCodecAdpcm) { state = reinterpret_cast<uint32_t*>(s->dCodeState.ptr); perRow = 2; }
+        if (state) {
+            HIP_TRY(hipSetDevice(s->b->device));
+            StageBlock block;
+            const int rowsAt = rows ? block.add(rows, (size_t)s->nRows) : -1;
+            StagePass pass(s, static_cast<hipStream_t>(stream), block);
+            if (pass.begin()) return -1;
+            const long long cells = s->nRows * perRow;
+            const unsigned grid = (unsigned)std::min<long long>((cells + 255) / 256, 4ll * s->b->cus);
+            hipLaunchKernelGGL(klatt_stage_clear, dim3(grid), dim3(256), 0, pass.stage.st, rows ? pass.stage.device<unsigned char>(rowsAt) : nullptr, s->nRows, perRow, state);
+            HIP_TRY(hipGetLastError());
+            if (pass.finish()) return -1;
+        }
+        for (long long i = 0; i < s->nRows; ++i)
+            if (!rows || rows[i]) { s->N[(size_t)i] = 0; s->M[(size_t)i] = 0; }
+        return 0;
+    } catch (const std::exception& e) { set_error("%s: %s", what, e.what()); return -1; }
+}
+
+// Host only: the samples every row has consumed and the outputs it has emitted since its start; either may be NULL
+int speechPlayer_stage_counts(speechPlayer_stage_t stage, long long* consumed, long long* emitted)
+{
+    begin_call();
+    Stage* s = stage_of("stage_counts", stage);
+    if (!s) return -1;
+    for (long long i = 0; i < s->nRows; ++i) {
+        if (consumed) consumed[i] = s->N[(size_t)i];
+        if (emitted) emitted[i] = s->M[(size_t)i];
+    }
+    return 0;
+}
+
+void speechPlayer_stage_free(speechPlayer_stage_t stage)
+{
+    begin_call();
+    Stage* s = static_cast<Stage*>(stage);
+    if (s && stage_known(s)) stage_release(s);
 }
 
 // ---- linear prediction of the PCM (klatt_lpc.h) -------------------------------------------------------------------------------------------

@@ -38,8 +38,8 @@
 //                   The workgroup is one wavefront, so __syncthreads() is a wavefront barrier and no wavefront waits for another.
 //                   LDS: 64 x 65 x 4 = 16 640 bytes of samples + 1 024 of the rows' places in the output = 17 664 per wavefront;
 //                   a CU's 160 KB hold nine.  Instantiated for K = 1, 2, 4, 8, 16 (filter_bucket) with the section loop unrolled.
-//   Out of scope    Live handles (the state would have to persist across pulls), NodePlayer, zero-phase (forward-backward) filtering,
-//                   initial conditions in or out, time-parallel (scan) formulations -- they cannot meet the sequential statement's
+//   Out of scope    Live handles and initial conditions in or out through this kernel (the state would have to persist across pulls:
+//                   klatt_stage.h keeps it), NodePlayer, zero-phase (forward-backward) filtering, time-parallel (scan) formulations -- they cannot meet the sequential statement's
 //                   bits --, and filling the chip with fewer than 64 x 1024 rows: a recursion cannot be cut in time bit-exactly.
 //                   A row some value of which overflows is outside the bit-for-bit claim (it faults nothing).
 #pragma once
@@ -167,7 +167,9 @@ struct FilterGroup { long long first, bucket, outMost, inMost; };
 
 // The rows in the order the wavefronts take them: by bucket ascending, then by outLen descending (ties in the caller's order), cut
 // into groups of kFilterLanes that hold one bucket each; `packed` holds kFilterLanes rows per group, fillers behind the last.
-inline void filter_pack(const std::vector<FilterRow>& rows, std::vector<FilterRow>& packed, std::vector<FilterGroup>& groups)
+// (Row: FilterRow, or a row that carries more beside it -- klatt_stage.h; a filler is all zeros)
+template <class Row>
+inline void filter_pack(const std::vector<Row>& rows, std::vector<Row>& packed, std::vector<FilterGroup>& groups)
 {
     std::vector<long long> order(rows.size());
     for (size_t i = 0; i < rows.size(); ++i) order[i] = (long long)i;
@@ -181,12 +183,12 @@ inline void filter_pack(const std::vector<FilterRow>& rows, std::vector<FilterRo
         FilterGroup g{(long long)packed.size(), bucket, 0, 0};
         int n = 0;
         for (; n < kFilterLanes && at < order.size() && filter_bucket(rows[(size_t)order[at]].sections) == bucket; ++n, ++at) {
-            const FilterRow& r = rows[(size_t)order[at]];
+            const Row& r = rows[(size_t)order[at]];
             packed.push_back(r);
             g.outMost = std::max(g.outMost, r.outLen);
             g.inMost = std::max(g.inMost, r.len);
         }
-        for (; n < kFilterLanes; ++n) packed.push_back(FilterRow{0, 0, 0, 0, 0, 0});
+        for (; n < kFilterLanes; ++n) packed.push_back(Row{});
         groups.push_back(g);
     }
 }

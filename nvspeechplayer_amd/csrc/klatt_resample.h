@@ -21,6 +21,7 @@
 //                   largest tested case and L2-resident.  The reordering moves data, not arithmetic.  The tiles are walked and the
 //                   values written as klatt_tiles.h says, a span being a run of the writer: staged in LDS in the output's type, a
 //                   padded row's tail as +0.
+//   Live handles    A row fed chunk by chunk keeps 2 Z - 1 samples of history between calls: klatt_stage.h (klatt_stage_resample).
 #pragma once
 
 #include <math.h>

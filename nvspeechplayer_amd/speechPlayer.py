@@ -1718,6 +1718,207 @@ def _ready_stream(owner, dev):
     return owner._ready.cuda_stream
 
 
+STAGE_KINDS = ["resample", "filter", "code"]      # kStageResample, kStageFilter, kStageCode of csrc/klatt_stage.h
+STAGE_MAX_ROWS = 1 << 20                          # kStageMaxRows
+
+
+def check_stage_request(kind, nRows, *args, **kw):
+    """The argument checks of BatchPlayer.resampleStage, filterStage and codeStage that need no GPU, before any library call: kind a name
+    of STAGE_KINDS; nRows an integer in 1 .. 2^20; then, by kind, the arguments of the whole-row export and its checks --
+    "resample": (srcRate, rate, zeros=6, rolloff=0.99, window="hann", beta=None) through check_resample_request; "filter": (filters,
+    filterOf=None, tail=0) through check_filter_request, filterOf per row of the stage; "code": (codec) through check_codec_request.
+    Raises KeyError (the kind, the codec), ValueError or TypeError.  Returns (kind's number, nRows, what the kind's check returns)."""
+    what = "%sStage" % kind if kind in STAGE_KINDS else "stage"
+    if kind not in STAGE_KINDS:
+        raise KeyError("%s: kind %r (%s)" % (what, kind, ", ".join(STAGE_KINDS)))
+    if isinstance(nRows, (bool, np.bool_)) or not isinstance(nRows, (int, np.integer)):
+        raise TypeError("%s: nRows must be an integer, not %r" % (what, nRows))
+    if not 1 <= nRows <= STAGE_MAX_ROWS:
+        raise ValueError("%s: nRows must lie in 1 .. 2^20, not %d" % (what, nRows))
+    nRows = int(nRows)
+    if kind == "resample":
+        def plan(srcRate, rate, zeros=6, rolloff=0.99, window="hann", beta=None):
+            return check_resample_request(srcRate, rate, zeros, rolloff, window, beta, None, what)
+    elif kind == "filter":
+        def plan(filters, filterOf=None, tail=0):
+            return check_filter_request(filters, filterOf, nRows, tail, None, what)
+    else:
+        def plan(codec):
+            return check_codec_request(codec, True, True, None, what)
+    return STAGE_KINDS.index(kind), nRows, plan(*args, **kw)
+
+
+def check_stage_push(kind, nRows, signal, end=None, dtype=None, codes=False, decoded=True, device=None, what="SignalStage.push"):
+    """The argument checks of SignalStage.push that need no GPU: signal as check_signal_request's, of exactly nRows rows; end None, a bool
+    or nRows bools; dtype as the kind's export takes it (None: float32, a code stage's int16); codes and decoded bools that only a code
+    stage takes otherwise than (False, True), not both False.  Raises ValueError or TypeError.  Returns (check_signal_request's answer,
+    end: uint8 [nRows] or None, the output format: 0 int16, 1 float32, codes, decoded)."""
+    if kind not in STAGE_KINDS:
+        raise KeyError("%s: kind %r (%s)" % (what, kind, ", ".join(STAGE_KINDS)))
+    sig = check_signal_request(signal, device, what)
+    if sig[2] != nRows:
+        raise ValueError("%s: a chunk of %d rows for a stage of %d" % (what, sig[2], nRows))
+    if end is None:
+        flags = None
+    elif isinstance(end, (bool, np.bool_)):
+        flags = np.full(nRows, 1 if end else 0, np.uint8)
+    else:
+        a = _as_array(end)
+        if a.dtype.kind != "b" or a.ndim != 1:
+            raise TypeError("%s: end must be None, True, False or a one-dimensional array of bools, not %s %s" % (what, a.dtype, list(a.shape)))
+        if len(a) != nRows:
+            raise ValueError("%s: end has %d entries for %d rows" % (what, len(a), nRows))
+        flags = np.ascontiguousarray(a.astype(np.uint8))
+    for name, v in (("codes", codes), ("decoded", decoded)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError("%s: %s must be True or False, not %r" % (what, name, v))
+    if kind != "code":
+        if codes or not decoded:
+            raise ValueError("%s: codes and decoded belong to a code stage" % what)
+        fmt = _sample_format(dtype, what)
+    else:
+        if not codes and not decoded:
+            raise ValueError("%s: codes, decoded or both" % what)
+        fmt = _int16_format(dtype, what)
+    return sig, flags, fmt, bool(codes), bool(decoded)
+
+
+def resampleEmitted(consumed, srcRate, dstRate, zeros=6, rolloff=0.99, ended=False):
+    """The outputs a resampler stage has emitted for a row after `consumed` samples, open or ended (speechPlayer_resampleEmitted; no GPU):
+    open, ceil(max(consumed - Z, 0) * up / down) -- the outputs whose taps all lie at or before the last sample consumed --; ended,
+    ceil(consumed * up / down), pcmResample's length.  Equal rates: consumed.  The difference of two is what a push emits."""
+    srcRate, dstRate, zeros, rolloff = check_resample_request(srcRate, dstRate, zeros, rolloff, "hann", None, None, "resampleEmitted")[:4]
+    return _answer(_native.load().speechPlayer_resampleEmitted(int(consumed), srcRate, dstRate, zeros, rolloff, 1 if ended else 0), error=ValueError)
+
+
+class SignalStage(object):
+    """The per-row state of one sequential export -- the resampler, the biquad filter or a codec -- on a BatchPlayer's device, fed chunk by
+    chunk (include/speechPlayer_batch.h, "Signal stages"): what a live handle's pulls go through.  Made by BatchPlayer.resampleStage,
+    filterStage and codeStage; freed by close() or with the player."""
+
+    def __init__(self, player, kind, nRows, handle):
+        self._bp, self.kind, self.nRows, self._h = player, kind, nRows, handle
+        self._dll = player._dll
+
+    def _handle(self):
+        if not getattr(self, "_h", None) or not getattr(self._bp, "_h", None):
+            raise RuntimeError("SignalStage: the stage was closed, or its player was")
+        return self._h
+
+    def plan(self, lengths, end=None):
+        """What a push of rows of these lengths with these end flags would emit per row (speechPlayer_stage_plan; host only, changes
+        nothing): -> int64 [nRows]."""
+        lens = _host_array(lengths, np.int64).reshape(-1)
+        if len(lens) != self.nRows:
+            raise ValueError("SignalStage.plan: %d lengths for %d rows" % (len(lens), self.nRows))
+        flags = None if end is None else np.ascontiguousarray(np.broadcast_to(_as_array(end), (self.nRows,)).astype(np.uint8))
+        out = np.zeros(self.nRows, np.int64)
+        _answer(self._dll.speechPlayer_stage_plan(self._handle(), lens.ctypes.data, _ptr(flags), out.ctypes.data), error=ValueError)
+        return out
+
+    def push(self, signal, end=None, dtype=None, padded=True, codes=False, decoded=True):
+        """Feed every row its next chunk (speechPlayer_stage_push), on torch's current stream without a host wait: signal the (tensor,
+        lengths or offsets) pair an export, a pull or another stage returns, of exactly nRows rows -- a row of length 0 is untouched --;
+        end None, a bool or nRows bools: the rows this push ends (a resampler then emits its last outputs, a filter its tail, and the
+        row is fresh afterwards).  -> (tensor, lengths), as the whole-row export returns them -- dtype torch.float32 (default) or
+        torch.int16; padded [nRows, most] with +0 past each row's outputs, or packed with the nRows + 1 offsets --; a code stage
+        -> (decoded, lengths), (decoded, codes, lengths) or (codes, lengths) as codedTensor, dtype torch.int16 by default.  The outputs
+        of a row's pushes, concatenated, are bit for bit signalResample / signalFilter / signalCode of its chunks concatenated."""
+        import torch
+        h, dev = self._handle(), self._bp.device
+        sig, flags, fmt, codes, decoded = check_stage_push(self.kind, self.nRows, signal, end, dtype, codes, decoded, dev)
+        tensor, inFormat, rows, stride, extent, lens = sig
+        counts = np.zeros(self.nRows, np.int64)
+        _answer(self._dll.speechPlayer_stage_plan(h, lens.ctypes.data, _ptr(flags), counts.ctypes.data), error=ValueError)
+        if padded:
+            outStride = max(int(counts.max()), 1)      # (rowStride 0 would mean packed)
+            shape, second = (self.nRows, outStride), counts
+        else:
+            outStride, second = 0, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            shape = (int(second[-1]),)
+        record = np.zeros(1, _signalDtype)
+        record["data"], record["format"], record["nRows"], record["rowStride"], record["extent"] = tensor.data_ptr(), inFormat, rows, stride, extent.ctypes.data
+        name = "cuda:%d" % dev
+        d = torch.empty(shape, dtype=torch.float32 if fmt else torch.int16, device=name) if decoded else None
+        c = torch.empty(shape, dtype=torch.uint8, device=name) if codes else None
+        numel = int(np.prod(shape))
+        got = self._dll.speechPlayer_stage_push(h, record.ctypes.data, _ptr(flags), d.data_ptr() if decoded and numel else None, fmt,
+                                                c.data_ptr() if codes and numel else None, outStride, None, torch.cuda.current_stream(dev).cuda_stream)
+        if got < 0:
+            raise RuntimeError("SignalStage.push failed: %s" % _native.last_error())
+        assert got == numel, (got, numel)
+        if padded and not counts.max():      # (rows of nothing: the width the whole-row exports give)
+            d, c = (None if t is None else t[:, :0] for t in (d, c))
+        return tuple(t for t in (d, c) if t is not None) + (torch.from_numpy(second),)
+
+    def reset(self, rows=None):
+        """Make rows fresh again -- nothing consumed, nothing emitted, the state +0 -- behind the stage's last push: rows None (all) or
+        nRows bools."""
+        import torch
+        flags = None
+        if rows is not None:
+            a = _as_array(rows)
+            if a.dtype.kind != "b" or a.shape != (self.nRows,):
+                raise TypeError("SignalStage.reset: rows must be None or %d bools" % self.nRows)
+            flags = np.ascontiguousarray(a.astype(np.uint8))
+        dev = self._bp.device
+        if self._dll.speechPlayer_stage_reset(self._handle(), _ptr(flags), torch.cuda.current_stream(dev).cuda_stream) < 0:
+            raise RuntimeError("SignalStage.reset failed: %s" % _native.last_error())
+
+    def _counts(self, which):
+        out = np.zeros(self.nRows, np.int64)
+        if self._dll.speechPlayer_stage_counts(self._handle(), *((out.ctypes.data, None) if which == 0 else (None, out.ctypes.data))) < 0:
+            raise RuntimeError("SignalStage: %s" % _native.last_error())
+        return out
+
+    @property
+    def consumed(self):
+        """The samples every row has consumed since its start (its creation, its last end or its last reset): int64 [nRows]."""
+        return self._counts(0)
+
+    @property
+    def emitted(self):
+        """The outputs every row has emitted since its start: int64 [nRows]."""
+        return self._counts(1)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._bp, "_h", None):      # (a stage goes with its player)
+                self._dll.speechPlayer_stage_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SignalChain(object):
+    """Stages one behind the other: push feeds each stage's (tensor, lengths) pair to the next as its chunk, and `end` travels with it --
+    pcm, produced = group.pullTensor(8192); y = chain.push((pcm, produced)).  Only the last stage may be a code stage."""
+
+    def __init__(self, stages):
+        self.stages = list(stages)
+        if not self.stages or not all(isinstance(s, SignalStage) for s in self.stages):
+            raise TypeError("SignalChain: a list of SignalStage objects, at least one")
+        if any(s.kind == "code" for s in self.stages[:-1]):
+            raise ValueError("SignalChain: a code stage comes last")
+        if len({s.nRows for s in self.stages}) != 1:
+            raise ValueError("SignalChain: the stages have %s rows" % sorted({s.nRows for s in self.stages}))
+
+    def push(self, signal, end=None, **last):
+        """The chunk through every stage; the keywords (dtype, padded, codes, decoded) are the last stage's push's, the stages between
+        hand on float32 padded rows."""
+        for s in self.stages[:-1]:
+            signal = s.push(signal, end)
+        return self.stages[-1].push(signal, end, **last)
+
+    def reset(self, rows=None):
+        for s in self.stages:
+            s.reset(rows)
+
+
 class BatchPlayer(object):
     """N independent utterances per launch (include/speechPlayer_batch.h)."""
 
@@ -2566,6 +2767,31 @@ class BatchPlayer(object):
 
     def deviceOffset(self, u):
         return self._dll.speechPlayer_batch_deviceOffset(self._h, u)
+
+    def _stage(self, kind, nRows, handle):
+        if not handle:
+            raise RuntimeError("%sStage failed: %s" % (kind, _native.last_error()))
+        return SignalStage(self, kind, nRows, handle)
+
+    def resampleStage(self, nRows, srcRate, rate, zeros=6, rolloff=0.99, window="hann", beta=None):
+        """A SignalStage of nRows rows that resamples from srcRate to rate Hz chunk by chunk (speechPlayer_batch_stageResample):
+        resampledTensor's resampler with the last 2 Z - 1 samples of every row kept between pushes.  The player need never be set."""
+        _, nRows, plan = check_stage_request("resample", nRows, srcRate, rate, zeros, rolloff, window, beta)
+        srcRate, rate, zeros, rolloff, win, beta = plan[:6]
+        return self._stage("resample", nRows, self._dll.speechPlayer_batch_stageResample(self._h, nRows, srcRate, rate, zeros, rolloff, win, beta))
+
+    def filterStage(self, nRows, filters, filterOf=None, tail=0):
+        """A SignalStage of nRows rows through cascades of biquad sections chunk by chunk (speechPlayer_batch_stageFilter):
+        filteredTensor's filters -- filterOf the filter of each row of the stage -- with every section's state kept between pushes; the
+        push that ends a row emits `tail` more outputs of zero input."""
+        _, nRows, (sec, start, of, tail, _) = check_stage_request("filter", nRows, filters, filterOf, tail)
+        return self._stage("filter", nRows, self._dll.speechPlayer_batch_stageFilter(self._h, nRows, sec.ctypes.data, start.ctypes.data, len(start) - 1, _ptr(of), tail))
+
+    def codeStage(self, nRows, codec):
+        """A SignalStage of nRows rows through a codec chunk by chunk (speechPlayer_batch_stageCode): codedTensor's codecs, the ADPCM
+        predictor and step index of every row kept between pushes."""
+        _, nRows, (codec, _, _, _) = check_stage_request("code", nRows, codec)
+        return self._stage("code", nRows, self._dll.speechPlayer_batch_stageCode(self._h, nRows, codec))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1,0 +1,81 @@
+"""Times the signal stages (BatchPlayer.resampleStage / filterStage / codeStage; csrc/klatt_stage.h) beside the whole-row exports of a
+signal on the same tensor in the same run, alternating the two: one push of 1024 rows x 8192 float32 samples at 22050 -> 16000 against
+resampledTensor(signal=), the same through the four-section telephone band against filteredTensor(signal=), and the single-row 8192-sample
+push a one-stream caller pays, per kind.  Two figures per call: `queued`, device events around REPS calls issued back to back, per call --
+what the kernels and the staging copy take once the host runs ahead --, and `alone`, a host clock around one call and a synchronise.
+Prints one JSON object; --out writes it to a file as well.  Needs a GPU."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+# scipy.signal.butter(4, [300, 3400], "bandpass", fs=22050, output="sos"): the telephone band, four sections
+TELEPHONE = np.array([
+    [0.015031869558932728, 0.030063739117865456, 0.015031869558932728, 1.0, -0.790740694160057, 0.1990626472143866],
+    [1.0, 2.0, 1.0, 1.0, -0.9114585623463567, 0.5756179539149701],
+    [1.0, -2.0, 1.0, 1.0, -1.829051960405075, 0.8381042282374366],
+    [1.0, -2.0, 1.0, 1.0, -1.9368246537081515, 0.9441864241806792]])
+REPS, ROUNDS, SAMPLES = 20, 5, 8192
+
+
+def measure(calls, dev):
+    """calls: name -> function.  ROUNDS rounds, the functions alternating within a round: -> name -> (queued ms per call: the median and the
+    range over the rounds, alone ms per call: the same)."""
+    import torch
+    for fn in calls.values():      # warm up: code objects, staging slots, the allocator
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize(dev)
+    queued, alone = {k: [] for k in calls}, {k: [] for k in calls}
+    for _ in range(ROUNDS):
+        for name, fn in calls.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(REPS):
+                fn()
+            b.record()
+            torch.cuda.synchronize(dev)
+            queued[name].append(a.elapsed_time(b) / REPS)
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            alone[name].append((time.perf_counter() - t) * 1e3)
+    spread = lambda v: dict(median=round(float(np.median(v)), 4), low=round(min(v), 4), high=round(max(v), 4))
+    return {k: dict(queued_ms=spread(queued[k]), alone_ms=spread(alone[k])) for k in calls}
+
+
+def main():
+    import torch
+    import nvspeechplayer_amd as eng
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    bp = eng.BatchPlayer(22050)
+    dev = bp.device
+    rng = np.random.default_rng(1)
+    result = {}
+    for rows in (1024, 1):
+        x = torch.from_numpy(rng.uniform(-1.0, 1.0, (rows, SAMPLES)).astype(np.float32)).to("cuda:%d" % dev)
+        signal = (x, np.full(rows, SAMPLES, np.int64))
+        res, fil, cod = bp.resampleStage(rows, 22050, 16000), bp.filterStage(rows, TELEPHONE), bp.codeStage(rows, "adpcm")
+        calls = {"resample stage push": lambda: res.push(signal), "resampledTensor(signal=)": lambda: bp.resampledTensor(16000, signal=signal),
+                 "filter stage push": lambda: fil.push(signal), "filteredTensor(signal=)": lambda: bp.filteredTensor(TELEPHONE, signal=signal),
+                 "adpcm stage push": lambda: cod.push(signal), "codedTensor(adpcm, signal=)": lambda: bp.codedTensor("adpcm", signal=signal)}
+        result["%d rows x %d float32" % (rows, SAMPLES)] = measure(calls, dev)
+        for s in (res, fil, cod):
+            s.close()
+    bp.close()
+    text = json.dumps(result, indent=1)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
