@@ -4913,6 +4913,19 @@ long long speechPlayer_signalResample(const void* x, int inFormat, long long len
     return resample_statement("signalResample", x, inFormat, length, srcRate, dstRate, zeros, rolloff, window, beta, format, out, capacity);
 }
 
+// Equal rates of a signal: klatt_signal_copy (input format, output format) over the tiles, on the stage's stream -- no table, no filter
+static int launch_signal_copy(const ExportStage& stage, const ExportInput& in, int format, const ResRow* rows, const TileOut& tile)
+{
+    ResArgs A;
+    A.in = in.data; A.rows = rows; A.tile = tile;
+    A.hT = nullptr; A.up = A.down = 1; A.Z = 0; A.span = kResampleTile;
+    void (*const copies[2][2])(ResArgs) = {{klatt_signal_copy<false, int16_t>, klatt_signal_copy<true, int16_t>}, {klatt_signal_copy<false, float>, klatt_signal_copy<true, float>}};
+    const unsigned grid = (unsigned)std::min<long long>(tile.nTiles, 8ll * stage.b->cus);
+    hipLaunchKernelGGL(copies[in.format()][format], dim3(grid), dim3(256), 0, stage.st, A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // The chosen utterances' PCM at `outRate` (klatt_resample.h).  It reads the pool, so it is ordered as speechPlayer_batch_exportPcm is
 // (ExportStage, ofPcm), tile-wise.  The staging block: rows | tile starts and chunk rows (packed) | the table, when the batch does not hold it.
 // The table stays on the batch until the parameters change; the exports that read it follow one order (resampleOrder).
@@ -4954,12 +4967,7 @@ static long long resampled_export(const char* what, speechPlayer_batch_t batch, 
             const int rowsAt = block.add(rows), wordsAt = block.add(words);
             ExportStage stage(b, st, block, nullptr, false, true);
             if (stage.begin()) return -1;
-            ResArgs A;
-            A.in = in.data; A.rows = stage.device<ResRow>(rowsAt);
-            A.tile = tile_out(stage, wordsAt, tiles, rowStride, deviceOut);
-            A.hT = nullptr; A.up = A.down = 1; A.Z = 0; A.span = kResampleTile;
-            void (*const copies[2][2])(ResArgs) = {{klatt_signal_copy<false, int16_t>, klatt_signal_copy<true, int16_t>}, {klatt_signal_copy<false, float>, klatt_signal_copy<true, float>}};
-            if (launch_tiles(stage, copies, in.format(), format, 8, A)) return -1;
+            if (launch_signal_copy(stage, in, format, stage.device<ResRow>(rowsAt), tile_out(stage, wordsAt, tiles, rowStride, deviceOut)) || stage.finish()) return -1;
             return elements;
         }
         const bool upload = !b->resOnDevice;
@@ -5147,12 +5155,43 @@ long long speechPlayer_signalFilter(const void* x, int inFormat, long long lengt
     return filter_statement("signalFilter", x, inFormat, length, sections, nSections, tail, format, out, capacity);
 }
 
-// The instantiation of klatt_filter for a bucket, an input format and an output format
-extern "C++" template <int K>
-static void (*filter_kernel(int inFormat, int format))(FilterArgs)
+// The entry point on filter_rows that takes these arguments: the whole-row export's, or the stage's that keeps state (klatt_stage.h)
+extern "C++" template <int K, bool F32, typename In> static void (*filter_entry(const FilterArgs&))(FilterArgs) { return klatt_filter<K, F32, In>; }
+extern "C++" template <int K, bool F32, typename In> static void (*filter_entry(const StageFilterArgs&))(StageFilterArgs) { return klatt_stage_filter<K, F32, In>; }
+
+// ... its instantiation for a bucket, an input format and an output format
+extern "C++" template <int K, class Args>
+static void (*filter_kernel(int inFormat, int format, const Args& A))(Args)
 {
-    void (*const kernels[2][2])(FilterArgs) = {{klatt_filter<K, false, int16_t>, klatt_filter<K, true, int16_t>}, {klatt_filter<K, false, float>, klatt_filter<K, true, float>}};
+    void (*const kernels[2][2])(Args) = {{filter_entry<K, false, int16_t>(A), filter_entry<K, true, int16_t>(A)}, {filter_entry<K, false, float>(A), filter_entry<K, true, float>(A)}};
     return kernels[inFormat][format];
+}
+
+// The launches of a packed table's groups on the stage's stream, one per bucket that has groups (those of one bucket lie together); A holds
+// everything but the groups, which are the block's section groupsAt.  A wavefront per group; no more workgroups than keep every SIMD of the
+// device busy several times over.
+extern "C++" template <class Args>
+static int launch_filter_groups(const ExportStage& stage, const std::vector<FilterGroup>& groups, int groupsAt, int inFormat, int format, Args& A)
+{
+    for (size_t first = 0; first < groups.size();) {
+        size_t end = first;
+        while (end < groups.size() && groups[end].bucket == groups[first].bucket) ++end;
+        A.groups = stage.device<FilterGroup>(groupsAt) + first;
+        A.nGroups = (long long)(end - first);
+        void (*kernel)(Args) = nullptr;
+        switch (groups[first].bucket) {
+            case 1: kernel = filter_kernel<1>(inFormat, format, A); break;
+            case 2: kernel = filter_kernel<2>(inFormat, format, A); break;
+            case 4: kernel = filter_kernel<4>(inFormat, format, A); break;
+            case 8: kernel = filter_kernel<8>(inFormat, format, A); break;
+            default: kernel = filter_kernel<16>(inFormat, format, A); break;
+        }
+        const unsigned grid = (unsigned)std::min<long long>(A.nGroups, 64ll * stage.b->cus);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFilterLanes), 0, stage.st, A);
+        HIP_TRY(hipGetLastError());
+        first = end;
+    }
+    return 0;
 }
 
 // The chosen utterances' PCM, each row through the filter filterOf names (klatt_filter.h).  It reads the pool, so it is ordered as
@@ -5193,26 +5232,7 @@ static long long filtered_export(const char* what, speechPlayer_batch_t batch, b
         A.in = in.data; A.rows = stage.device<FilterRow>(rowsAt);
         A.sections = stage.device<FilterSection>(sectionsAt);
         A.rowStride = rowStride; A.out = deviceOut;
-        for (size_t first = 0; first < groups.size();) {      // the groups of one bucket lie together
-            size_t end = first;
-            while (end < groups.size() && groups[end].bucket == groups[first].bucket) ++end;
-            A.groups = stage.device<FilterGroup>(groupsAt) + first;
-            A.nGroups = (long long)(end - first);
-            void (*kernel)(FilterArgs) = nullptr;
-            switch (groups[first].bucket) {
-                case 1: kernel = filter_kernel<1>(in.format(), format); break;
-                case 2: kernel = filter_kernel<2>(in.format(), format); break;
-                case 4: kernel = filter_kernel<4>(in.format(), format); break;
-                case 8: kernel = filter_kernel<8>(in.format(), format); break;
-                default: kernel = filter_kernel<16>(in.format(), format); break;
-            }
-            // a wavefront per group; no more workgroups than keep every SIMD of the device busy several times over
-            const unsigned grid = (unsigned)std::min<long long>(A.nGroups, 64ll * b->cus);
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFilterLanes), 0, stage.st, A);
-            HIP_TRY(hipGetLastError());
-            first = end;
-        }
-        if (stage.finish()) return -1;
+        if (launch_filter_groups(stage, groups, groupsAt, in.format(), format, A) || stage.finish()) return -1;
         return elements;
     });
 }
@@ -5288,6 +5308,41 @@ long long speechPlayer_codecDecode(const unsigned char* codes, long long length,
     return length;
 }
 
+// klatt_code_g711 of a law (input format, output format) over the tiles, on the stage's stream, at most 8 workgroups per CU
+static int launch_g711(const ExportStage& stage, int codec, int inFormat, int format, const CodeArgs& A)
+{
+    void (*const ulaw[2][2])(CodeArgs) = {{klatt_code_g711<kCodecUlaw, false, int16_t>, klatt_code_g711<kCodecUlaw, true, int16_t>},
+                                          {klatt_code_g711<kCodecUlaw, false, float>, klatt_code_g711<kCodecUlaw, true, float>}};
+    void (*const alaw[2][2])(CodeArgs) = {{klatt_code_g711<kCodecAlaw, false, int16_t>, klatt_code_g711<kCodecAlaw, true, int16_t>},
+                                          {klatt_code_g711<kCodecAlaw, false, float>, klatt_code_g711<kCodecAlaw, true, float>}};
+    const unsigned grid = (unsigned)std::min<long long>(A.tile.nTiles, 8ll * stage.b->cus);
+    hipLaunchKernelGGL((codec == kCodecUlaw ? ulaw : alaw)[inFormat][format], dim3(grid), dim3(256), 0, stage.st, A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The entry point on adpcm_rows that takes these arguments: the whole-row export's, or the stage's that keeps state (klatt_stage.h)
+extern "C++" template <int OUT, bool F32, typename In> static void (*adpcm_entry(const AdpcmArgs&))(AdpcmArgs) { return klatt_code_adpcm<OUT, F32, In>; }
+extern "C++" template <int OUT, bool F32, typename In> static void (*adpcm_entry(const StageAdpcmArgs&))(StageAdpcmArgs) { return klatt_stage_adpcm<OUT, F32, In>; }
+
+// ... its instantiation for (input format, outputs, output format) over A's groups, on the stage's stream: a wavefront per group; no more
+// workgroups than keep every SIMD of the device busy several times over
+extern "C++" template <class Args>
+static int launch_adpcm(const ExportStage& stage, int inFormat, int outputs, int format, const Args& A)
+{
+    // [input format][outputs - 1][output format]; the codes alone have no output format
+    constexpr int D = kCodeDecoded, C = kCodeCodes;
+    void (*const kernels[2][3][2])(Args) = {
+        {{adpcm_entry<D, false, int16_t>(A), adpcm_entry<D, true, int16_t>(A)}, {adpcm_entry<C, false, int16_t>(A), adpcm_entry<C, false, int16_t>(A)},
+         {adpcm_entry<D | C, false, int16_t>(A), adpcm_entry<D | C, true, int16_t>(A)}},
+        {{adpcm_entry<D, false, float>(A), adpcm_entry<D, true, float>(A)}, {adpcm_entry<C, false, float>(A), adpcm_entry<C, false, float>(A)},
+         {adpcm_entry<D | C, false, float>(A), adpcm_entry<D | C, true, float>(A)}}};
+    const unsigned grid = (unsigned)std::min<long long>(A.nGroups, 64ll * stage.b->cus);
+    hipLaunchKernelGGL(kernels[inFormat][outputs - 1][format], dim3(grid), dim3(kFilterLanes), 0, stage.st, A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // The chosen utterances' PCM coded (klatt_codec.h): the decoded samples, the codes or both, on one grid.  It reads the pool, so it is ordered
 // as speechPlayer_batch_exportPcm is (ExportStage, ofPcm).  A G.711 law goes tile-wise (the staging block: rows | tile starts and chunk rows,
 // packed); ADPCM a wavefront per 64 rows as filtered_export's (packed rows | groups).  Nothing is kept on the batch.  ofSignal and `signal` as
@@ -5334,11 +5389,7 @@ static long long coded_export(const char* what, speechPlayer_batch_t batch, bool
             A.in = in.data; A.rows = stage.device<ResRow>(rowsAt);
             A.tile = tile_out(stage, wordsAt, tiles, rowStride, decodedOut);
             A.codes = static_cast<uint8_t*>(codesOut);
-            void (*const ulaw[2][2])(CodeArgs) = {{klatt_code_g711<kCodecUlaw, false, int16_t>, klatt_code_g711<kCodecUlaw, true, int16_t>},
-                                                  {klatt_code_g711<kCodecUlaw, false, float>, klatt_code_g711<kCodecUlaw, true, float>}};
-            void (*const alaw[2][2])(CodeArgs) = {{klatt_code_g711<kCodecAlaw, false, int16_t>, klatt_code_g711<kCodecAlaw, true, int16_t>},
-                                                  {klatt_code_g711<kCodecAlaw, false, float>, klatt_code_g711<kCodecAlaw, true, float>}};
-            if (codec == kCodecUlaw ? launch_tiles(stage, ulaw, in.format(), format, 8, A) : launch_tiles(stage, alaw, in.format(), format, 8, A)) return -1;
+            if (launch_g711(stage, codec, in.format(), format, A) || stage.finish()) return -1;
             return elements;
         }
         std::vector<FilterRow> packed;
@@ -5352,19 +5403,8 @@ static long long coded_export(const char* what, speechPlayer_batch_t batch, bool
         A.in = in.data; A.rows = stage.device<FilterRow>(rowsAt);
         A.groups = stage.device<FilterGroup>(groupsAt); A.nGroups = (long long)groups.size();
         A.rowStride = rowStride; A.decoded = decodedOut; A.codes = static_cast<uint8_t*>(codesOut);
-        // [input format][outputs - 1][output format]; the codes alone have no output format
-        constexpr int D = kCodeDecoded, C = kCodeCodes;
-        void (*const kernels[2][3][2])(AdpcmArgs) = {
-            {{klatt_code_adpcm<D, false, int16_t>, klatt_code_adpcm<D, true, int16_t>}, {klatt_code_adpcm<C, false, int16_t>, klatt_code_adpcm<C, false, int16_t>},
-             {klatt_code_adpcm<D | C, false, int16_t>, klatt_code_adpcm<D | C, true, int16_t>}},
-            {{klatt_code_adpcm<D, false, float>, klatt_code_adpcm<D, true, float>}, {klatt_code_adpcm<C, false, float>, klatt_code_adpcm<C, false, float>},
-             {klatt_code_adpcm<D | C, false, float>, klatt_code_adpcm<D | C, true, float>}}};
-        const int outputs = (decodedOut ? D : 0) | (codesOut ? C : 0);
-        // a wavefront per group; no more workgroups than keep every SIMD of the device busy several times over
-        const unsigned grid = (unsigned)std::min<long long>(A.nGroups, 64ll * b->cus);
-        hipLaunchKernelGGL(kernels[in.format()][outputs - 1][format], dim3(grid), dim3(kFilterLanes), 0, stage.st, A);
-        HIP_TRY(hipGetLastError());
-        if (stage.finish()) return -1;
+        const int outputs = (decodedOut ? kCodeDecoded : 0) | (codesOut ? kCodeCodes : 0);
+        if (launch_adpcm(stage, in.format(), outputs, format, A) || stage.finish()) return -1;
         return elements;
     });
 }
@@ -5556,14 +5596,6 @@ struct StagePass {
     }
 };
 
-extern "C++" template <int K>
-static void (*stage_filter_kernel(int inFormat, int format))(StageFilterArgs)
-{
-    void (*const kernels[2][2])(StageFilterArgs) = {{klatt_stage_filter<K, false, int16_t>, klatt_stage_filter<K, true, int16_t>},
-                                                    {klatt_stage_filter<K, false, float>, klatt_stage_filter<K, true, float>}};
-    return kernels[inFormat][format];
-}
-
 // The rows of a filter or ADPCM stage's push, packed into wavefronts (filter_pack)
 static void stage_lane_rows(const Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long rowStride,
                             std::vector<StageLaneRow>& packed, std::vector<FilterGroup>& groups)
@@ -5602,16 +5634,8 @@ static int stage_push_resample(Stage* s, const ExportInput& in, const unsigned c
     StagePass pass(s, st, block);
     if (pass.begin()) return -1;
     const unsigned grid = (unsigned)std::min<long long>(tiles.nTiles, 8ll * b->cus);
-    if (identity) {      // equal rates: the copy kernel of the whole-row export
-        ResArgs A;
-        A.in = in.data; A.rows = pass.stage.device<ResRow>(rowsAt);
-        A.tile = tile_out(pass.stage, wordsAt, tiles, rowStride, deviceOut);
-        A.hT = nullptr; A.up = A.down = 1; A.Z = 0; A.span = kResampleTile;
-        void (*const copies[2][2])(ResArgs) = {{klatt_signal_copy<false, int16_t>, klatt_signal_copy<true, int16_t>}, {klatt_signal_copy<false, float>, klatt_signal_copy<true, float>}};
-        hipLaunchKernelGGL(copies[in.format()][format], dim3(grid), dim3(256), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        return pass.finish();
-    }
+    if (identity)      // equal rates: the copy kernel of the whole-row export
+        return launch_signal_copy(pass.stage, in, format, pass.stage.device<ResRow>(rowsAt), tile_out(pass.stage, wordsAt, tiles, rowStride, deviceOut)) || pass.finish() ? -1 : 0;
     const int H = stage_history(s->g.Z);
     const float* from = s->dHist[s->cur].ptr;
     float* to = s->dHist[s->cur ^ 1].ptr;
@@ -5640,7 +5664,6 @@ static int stage_push_resample(Stage* s, const ExportInput& in, const unsigned c
 static int stage_push_filter(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, void* deviceOut, int format, long long rowStride,
                              hipStream_t st)
 {
-    Batch* b = s->b;
     std::vector<StageLaneRow> packed;
     std::vector<FilterGroup> groups;
     stage_lane_rows(s, in, end, sel, rowStride, packed, groups);
@@ -5652,31 +5675,12 @@ static int stage_push_filter(Stage* s, const ExportInput& in, const unsigned cha
     A.in = in.data; A.rows = pass.stage.device<StageLaneRow>(rowsAt);
     A.sections = pass.stage.device<FilterSection>(sectionsAt);
     A.rowStride = rowStride; A.out = deviceOut; A.state = s->dFilterState.ptr;
-    for (size_t first = 0; first < groups.size();) {      // the groups of one bucket lie together
-        size_t last = first;
-        while (last < groups.size() && groups[last].bucket == groups[first].bucket) ++last;
-        A.groups = pass.stage.device<FilterGroup>(groupsAt) + first;
-        A.nGroups = (long long)(last - first);
-        void (*kernel)(StageFilterArgs) = nullptr;
-        switch (groups[first].bucket) {
-            case 1: kernel = stage_filter_kernel<1>(in.format(), format); break;
-            case 2: kernel = stage_filter_kernel<2>(in.format(), format); break;
-            case 4: kernel = stage_filter_kernel<4>(in.format(), format); break;
-            case 8: kernel = stage_filter_kernel<8>(in.format(), format); break;
-            default: kernel = stage_filter_kernel<16>(in.format(), format); break;
-        }
-        const unsigned grid = (unsigned)std::min<long long>(A.nGroups, 64ll * b->cus);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFilterLanes), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        first = last;
-    }
-    return pass.finish();
+    return launch_filter_groups(pass.stage, groups, groupsAt, in.format(), format, A) || pass.finish() ? -1 : 0;
 }
 
 static int stage_push_code(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long elements, void* decodedOut, int format,
                            void* codesOut, long long rowStride, hipStream_t st)
 {
-    Batch* b = s->b;
     if (s->codec != kCodecAdpcm) {      // no state: the tile kernel of the whole-row export
         if (elements == 0) return 0;
         std::vector<ResRow> rows((size_t)s->nRows);
@@ -5695,14 +5699,7 @@ static int stage_push_code(Stage* s, const ExportInput& in, const unsigned char*
         A.in = in.data; A.rows = pass.stage.device<ResRow>(rowsAt);
         A.tile = tile_out(pass.stage, wordsAt, tiles, rowStride, decodedOut);
         A.codes = static_cast<uint8_t*>(codesOut);
-        void (*const ulaw[2][2])(CodeArgs) = {{klatt_code_g711<kCodecUlaw, false, int16_t>, klatt_code_g711<kCodecUlaw, true, int16_t>},
-                                              {klatt_code_g711<kCodecUlaw, false, float>, klatt_code_g711<kCodecUlaw, true, float>}};
-        void (*const alaw[2][2])(CodeArgs) = {{klatt_code_g711<kCodecAlaw, false, int16_t>, klatt_code_g711<kCodecAlaw, true, int16_t>},
-                                              {klatt_code_g711<kCodecAlaw, false, float>, klatt_code_g711<kCodecAlaw, true, float>}};
-        const unsigned grid = (unsigned)std::min<long long>(tiles.nTiles, 8ll * b->cus);
-        hipLaunchKernelGGL((s->codec == kCodecUlaw ? ulaw : alaw)[in.format()][format], dim3(grid), dim3(256), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        return pass.finish();
+        return launch_g711(pass.stage, s->codec, in.format(), format, A) || pass.finish() ? -1 : 0;
     }
     std::vector<StageLaneRow> packed;
     std::vector<FilterGroup> groups;
@@ -5715,19 +5712,9 @@ static int stage_push_code(Stage* s, const ExportInput& in, const unsigned char*
     A.in = in.data; A.rows = pass.stage.device<StageLaneRow>(rowsAt);
     A.groups = pass.stage.device<FilterGroup>(groupsAt); A.nGroups = (long long)groups.size();
     A.rowStride = rowStride; A.decoded = decodedOut; A.codes = static_cast<uint8_t*>(codesOut); A.state = s->dCodeState.ptr;
-    // [input format][outputs - 1][output format]; the codes alone have no output format.  Nothing to write: the codes' kernel, which then
-    // only moves the states
-    constexpr int D = kCodeDecoded, C = kCodeCodes;
-    void (*const kernels[2][3][2])(StageAdpcmArgs) = {
-        {{klatt_stage_adpcm<D, false, int16_t>, klatt_stage_adpcm<D, true, int16_t>}, {klatt_stage_adpcm<C, false, int16_t>, klatt_stage_adpcm<C, false, int16_t>},
-         {klatt_stage_adpcm<D | C, false, int16_t>, klatt_stage_adpcm<D | C, true, int16_t>}},
-        {{klatt_stage_adpcm<D, false, float>, klatt_stage_adpcm<D, true, float>}, {klatt_stage_adpcm<C, false, float>, klatt_stage_adpcm<C, false, float>},
-         {klatt_stage_adpcm<D | C, false, float>, klatt_stage_adpcm<D | C, true, float>}}};
-    const int outputs = elements == 0 ? C : (decodedOut ? D : 0) | (codesOut ? C : 0);
-    const unsigned grid = (unsigned)std::min<long long>(A.nGroups, 64ll * b->cus);
-    hipLaunchKernelGGL(kernels[in.format()][outputs - 1][format], dim3(grid), dim3(kFilterLanes), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    return pass.finish();
+    // Nothing to write: the codes' kernel, which then only moves the states
+    const int outputs = elements == 0 ? kCodeCodes : (decodedOut ? kCodeDecoded : 0) | (codesOut ? kCodeCodes : 0);
+    return launch_adpcm(pass.stage, in.format(), outputs, format, A) || pass.finish() ? -1 : 0;
 }
 
 long long speechPlayer_stage_push(speechPlayer_stage_t stage, const speechPlayer_signal_t* chunk, const unsigned char* end, void* deviceOut, int format,

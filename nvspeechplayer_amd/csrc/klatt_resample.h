@@ -21,7 +21,11 @@
 //                   largest tested case and L2-resident.  The reordering moves data, not arithmetic.  The tiles are walked and the
 //                   values written as klatt_tiles.h says, a span being a run of the writer: staged in LDS in the output's type, a
 //                   padded row's tail as +0.
-//   Live handles    A row fed chunk by chunk keeps 2 Z - 1 samples of history between calls: klatt_stage.h (klatt_stage_resample).
+//   One body        The kernel is resample_rows<KEPT = false>: the loop is written once, and klatt_resample is the entry point that hands it
+//                   the reader above.  A row fed chunk by chunk keeps 2 Z - 1 samples of history between calls (klatt_stage.h):
+//                   klatt_stage_resample is the other entry point, resample_rows<KEPT = true> with the reader of the virtual row
+//                   [history | chunk | +0] and a span's first output counted from the row's start.  Behind `if constexpr (KEPT)` is that
+//                   one addition; with KEPT false nothing of a stage exists in the code.
 #pragma once
 
 #include <math.h>
@@ -218,8 +222,12 @@ struct ResArgs {
 static_assert((kResampleTile & (kResampleTile - 1)) == 0 && kResampleTile <= 4096, "kResampleTile is a power of two, at most 4096");
 static_assert(kResampleIn >= kResampleMaxTaps + 1 + kResampleMaxTaps / 2, "a span of one output fits at the largest ratio and filter");
 
-template <bool F32, typename In = int16_t>
-__global__ void __launch_bounds__(256) klatt_resample(const ResArgs A)
+// The one body of klatt_resample and of klatt_stage_resample (klatt_stage.h).  KEPT: the launch carries a row's state from push to push --
+// A.rows are StageResRow, a span's first output is output row.M + e0 of the row's stream, and `read` fills LDS from the virtual row.
+// read(xin, x, r, row, first, count, tid): samples first .. first + count - 1 of row r's stream into xin, +0 where the stream has none; x is
+// the first of the row's samples in this call (the whole row's, or the chunk's).
+template <bool KEPT, bool F32, typename In, class Args, class Read>
+__device__ __forceinline__ void resample_rows(const Args& A, Read read)
 {
     using T = TileValue<F32>;
     __shared__ float xin[kResampleIn];
@@ -229,20 +237,22 @@ __global__ void __launch_bounds__(256) klatt_resample(const ResArgs A)
     for (long long g = blockIdx.x; g < A.tile.nTiles; g += gridDim.x) {
         long long r, t0;
         tile_locate(A.tile, g, kResampleTile, r, t0);
-        const ResRow row = A.rows[r];
+        const auto row = A.rows[r];
         const int n = tile_n(A.tile.rowStride, row.outLen, t0, kResampleTile);
-        const In* __restrict__ pcm = static_cast<const In*>(A.in) + row.src;
+        const In* __restrict__ x = static_cast<const In*>(A.in) + row.src;
         for (int c0 = 0; c0 < n; c0 += A.span) {
             const int cn = min(A.span, n - c0);
-            const long long m0 = t0 + c0;
-            const int live = tile_live(cn, row.outLen, m0);      // outputs of the span inside the row; the rest is padding
+            const long long e0 = t0 + c0;                        // the span's first output: of this call ...
+            long long m0 = e0;                                   // ... and of the row
+            if constexpr (KEPT) m0 += row.M;
+            const int live = tile_live(cn, row.outLen, e0);      // outputs of the span inside the row's; the rest is padding
             long long nA = 0; int pA = 0;
             if (live > 0) {
                 // ---- the span's inputs, once ----
                 long long nB; int pB;
                 res_locate(m0, up, down, nA, pA);
                 res_locate(m0 + live - 1, up, down, nB, pB);
-                tile_read<1>(xin, pcm, row.len, nA - Z + 1, (int)(nB - nA) + taps, tid);
+                read(xin, x, r, row, nA - Z + 1, (int)(nB - nA) + taps, tid);
             }
             __syncthreads();
             // ---- the outputs: lane i takes i, i + 256, ... ----
@@ -258,10 +268,18 @@ __global__ void __launch_bounds__(256) klatt_resample(const ResArgs A)
                 staged[i] = v;
             }
             __syncthreads();
-            tile_store<T>(A.tile.out, row.dst + m0, cn, staged, tid);
+            tile_store<T>(A.tile.out, row.dst + e0, cn, staged, tid);
             // (the next span's loads and values are behind its own barriers: every lane has read `staged` before any lane passes the first)
         }
     }
+}
+
+template <bool F32, typename In = int16_t>
+__global__ void __launch_bounds__(256) klatt_resample(const ResArgs A)
+{
+    resample_rows<false, F32, In>(A, [](float* xin, const In* __restrict__ pcm, long long, const ResRow& row, long long first, int count, int tid) {
+        tile_read<1>(xin, pcm, row.len, first, count, tid);
+    });
 }
 
 // Equal rates of a signal: y[m] = x[m] in the output's type, tile by tile: the reader's sample into the writer's staging

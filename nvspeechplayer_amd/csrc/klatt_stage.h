@@ -23,11 +23,14 @@
 //                   (stage_history_from_chunk), all zeros for an ended row.  It is written to the OTHER of two buffers by a kernel of its own
 //                   (klatt_stage_history), so no workgroup writes what another reads; the next push swaps the buffers.
 //   klatt_stage_resample
-//                   klatt_resample's tiling -- kResampleTile outputs a workgroup, spans whose inputs fit kResampleIn floats of LDS, the
-//                   transposed table, the writer of klatt_tiles.h -- with two differences: the reader fills LDS from the virtual row, and a
-//                   tile's first output is the row's global index M + t0, located in 64 bits (the phase column as well); addresses are
-//                   relative to the chunk and to the row's place in the output.
+//                   resample_rows<KEPT = true> of klatt_resample.h, the one body it shares with klatt_resample: that kernel's tiling --
+//                   kResampleTile outputs a workgroup, spans whose inputs fit kResampleIn floats of LDS, the transposed table, the writer
+//                   of klatt_tiles.h.  The entry point here hands it the reader of the virtual row (stage_sample) in place of tile_read,
+//                   and KEPT makes a span's first output the row's global index M + t0, located in 64 bits (the phase column as well);
+//                   addresses are relative to the chunk and to the row's place in the output.
 //   klatt_stage_filter, klatt_stage_adpcm
+//                   Siblings of klatt_filter and klatt_code_adpcm, not entry points on one body: merged, three rows of the timing probes
+//                   lay above the parent's maximum (profiles/stage_kernels_one_body.txt), so the loops stay written twice.
 //                   klatt_filter's and klatt_code_adpcm's scheme whole -- a lane per row, tiles transposed through LDS, coefficients and
 //                   states in registers, the buckets with identity padding -- with the states loaded from the stage before the first sample
 //                   and stored behind the last.  Those kernels keep stepping on zeros past a row's own samples while the group's longest
@@ -125,49 +128,11 @@ struct StageResArgs {
 template <bool F32, typename In>
 __global__ void __launch_bounds__(256) klatt_stage_resample(const StageResArgs A)
 {
-    using T = TileValue<F32>;
-    __shared__ float xin[kResampleIn];
-    __shared__ __attribute__((aligned(16))) T staged[kResampleTile];
-    const int tid = threadIdx.x;
-    const int up = A.up, down = A.down, Z = A.Z, taps = 2 * Z, H = stage_history(Z);
-    for (long long g = blockIdx.x; g < A.tile.nTiles; g += gridDim.x) {
-        long long r, t0;
-        tile_locate(A.tile, g, kResampleTile, r, t0);
-        const StageResRow row = A.rows[r];
-        const int n = tile_n(A.tile.rowStride, row.outLen, t0, kResampleTile);
-        const In* __restrict__ chunk = static_cast<const In*>(A.in) + row.src;
+    const int H = stage_history(A.Z);
+    resample_rows<true, F32, In>(A, [&](float* xin, const In* __restrict__ chunk, long long r, const StageResRow& row, long long first, int count, int tid) {
         const float* __restrict__ hist = A.hist + r * H;
-        for (int c0 = 0; c0 < n; c0 += A.span) {
-            const int cn = min(A.span, n - c0);
-            const long long e0 = t0 + c0, m0 = row.M + e0;       // the span's first output: of this push, of the row
-            const int live = tile_live(cn, row.outLen, e0);      // outputs of the span inside the push's; the rest is padding
-            long long nA = 0; int pA = 0;
-            if (live > 0) {
-                // ---- the span's inputs, once, from the virtual row ----
-                long long nB; int pB;
-                res_locate(m0, up, down, nA, pA);
-                res_locate(m0 + live - 1, up, down, nB, pB);
-                const int count = (int)(nB - nA) + taps;
-                for (int i = tid; i < count; i += 256) xin[i] = stage_sample(hist, chunk, nA - Z + 1 + i, row.N, H, row.len);
-            }
-            __syncthreads();
-            // ---- the outputs: lane i takes i, i + 256, ... ----
-            const uint32_t jA = (uint32_t)(m0 % up);
-            for (int i = tid; i < cn; i += 256) {
-                T v = (T)0;
-                if (i < live) {
-                    const uint32_t a = (uint32_t)pA + (uint32_t)i * (uint32_t)down;      // (below 2^12 + 2^10 2^21)
-                    const uint32_t col = (jA + (uint32_t)i) % (uint32_t)up;
-                    const float y = res_taps(xin + a / (uint32_t)up, A.hT + col, taps, up);
-                    v = res_value<F32>(y);
-                }
-                staged[i] = v;
-            }
-            __syncthreads();
-            tile_store<T>(A.tile.out, row.dst + e0, cn, staged, tid);
-            // (the next span's loads and values are behind its own barriers: every lane has read `staged` before any lane passes the first)
-        }
-    }
+        for (int i = tid; i < count; i += 256) xin[i] = stage_sample(hist, chunk, first + i, row.N, H, row.len);
+    });
 }
 
 // The next history of every row, into the buffer this push does not read: the last H of [history | chunk], zeros for an ended row

@@ -448,3 +448,67 @@ def test_refusals_write_nothing_and_leave_the_state_as_it_was(kind):
         assert same(again[0][i], want[len(want) - len(again[0][i]):]), i
     L.speechPlayer_stage_free(h)
     bp.close()
+
+
+# ---- 7. the stage kernel against the whole-row kernel -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("form", ["packed", "padded"])
+@pytest.mark.parametrize("kind", ["resample 22050 -> 16000", "resample 48000 -> 4000", "filter", "adpcm"])
+def test_one_push_that_ends_every_row_is_the_whole_row_export(bare, kind, form):
+    """The stage kernels against the whole-row kernels on the device -- two entry points on one body for the resampler (resample_rows of
+    csrc/klatt_resample.h), siblings for the filter and for ADPCM (csrc/klatt_stage.h beside klatt_filter.h and klatt_codec.h):
+    on 65 float32 rows of lengths drawn unsorted from {0, 1, T - 1, T, T + 1, 2 T + 3} (T the kind's tile), a single push that ends every
+    row of a fresh stage writes, between its guards, exactly the bytes exportResampledOf / exportFilteredOf (the same tail) / exportCodedOf
+    write for the same signal -- rows, padding and guards, float32 and int16, the codes as well."""
+    import torch
+    from nvspeechplayer_amd import _native, speechPlayer as sp
+    L = _native.load()
+    n, dev = 65, "cuda:%d" % bare.device
+    p = lambda a: None if a is None else a.ctypes.data
+    T = sp.RESAMPLE_TILE if kind.startswith("resample") else sp.FILTER_TILE
+    pool = [0, 1, T - 1, T, T + 1, 2 * T + 3]
+    rng = np.random.default_rng(len(kind) + len(form))
+    lens = [pool[rng.integers(0, len(pool))] for _ in range(n)]
+    assert set(lens) == set(pool) and sorted(lens) != lens and sorted(lens, reverse=True) != lens
+    rows = edge_rows(lens, F32, 70 + len(kind))
+    host, first, extent = lay_out(rows, F32, 0 if form == "packed" else max(lens) + 5, poison, 1)
+    data = torch.from_numpy(host.view(np.int32)).to(dev)
+    rec = record(sp, data.data_ptr() + 4 * first, 1, n, 0 if form == "packed" else max(lens) + 5, extent)
+    filters = seven()
+    flat, start = np.concatenate(filters), np.concatenate([[0], np.cumsum([len(f) for f in filters])]).astype(np.int64)
+    of = ((np.arange(n) * 3) % 7).astype(np.int64)
+    if kind.startswith("resample"):
+        src, dst = (int(w) for w in kind.split()[1::2])
+        h = L.speechPlayer_batch_stageResample(bare._h, n, src, dst, 6, 0.99, 0, 0.0)
+        export = lambda d, fmt, c, stride: L.speechPlayer_batch_exportResampledOf(bare._h, p(rec), None, 0, src, dst, 6, 0.99, 0, 0.0, d, fmt, stride, None)
+    elif kind == "filter":
+        h = L.speechPlayer_batch_stageFilter(bare._h, n, p(flat), p(start), 7, p(of), T + 3)
+        export = lambda d, fmt, c, stride: L.speechPlayer_batch_exportFilteredOf(bare._h, p(rec), None, 0, p(flat), p(start), 7, p(of), T + 3, d, fmt, stride, None)
+    else:
+        h = L.speechPlayer_batch_stageCode(bare._h, n, sp.CODECS.index("adpcm"))
+        export = lambda d, fmt, c, stride: L.speechPlayer_batch_exportCodedOf(bare._h, p(rec), None, 0, sp.CODECS.index("adpcm"), d, fmt, c, stride, None)
+    assert h, _native.last_error()
+    end, counts, lengths = np.ones(n, np.uint8), np.zeros(n, np.int64), np.zeros(n, np.int64)
+    shift = 3
+    for fmt in (1, 0):      # (the push ends every row, so the stage is fresh again for the second format)
+        assert L.speechPlayer_stage_plan(h, p(np.array(lens, np.int64)), p(end), p(counts)) == counts.sum() > 0
+        stride = 0 if form == "packed" else int(counts.max()) + 3
+        elements = int(counts.sum()) if stride == 0 else n * stride
+        bufs = {}
+        for who in ("push", "export"):
+            d = torch.full((elements + 2 * GUARD + shift,), -7, dtype=torch.float32 if fmt else torch.int16, device=dev)
+            c = torch.full((elements + 2 * GUARD + shift,), 0x55, dtype=torch.uint8, device=dev) if kind == "adpcm" else None
+            bufs[who] = (d, c)
+            dptr, cptr = d.data_ptr() + (GUARD + shift) * d.element_size(), None if c is None else c.data_ptr() + GUARD + shift
+            got = L.speechPlayer_stage_push(h, p(rec), p(end), dptr, fmt, cptr, stride, p(lengths), None) if who == "push" else export(dptr, fmt, cptr, stride)
+            assert got == elements, (kind, form, fmt, who, got, elements, _native.last_error())
+        assert list(lengths) == list(counts)
+        torch.cuda.synchronize()
+        for a, b in zip(bufs["push"], bufs["export"]):
+            if a is not None:
+                a, b = a.cpu().numpy(), b.cpu().numpy()
+                assert a.tobytes() == b.tobytes(), (kind, form, fmt, a.dtype)
+                assert np.all(a[:GUARD + shift] == a[0]) and np.all(a[GUARD + shift + elements:] == a[0]) and a[0] in (-7, 0x55), (kind, form, fmt, "guards")
+                assert np.any(a[GUARD + shift:GUARD + shift + elements] != a[0])
+    consumed = np.full(n, -1, np.int64)
+    assert L.speechPlayer_stage_counts(h, p(consumed), None) == 0 and not consumed.any()
+    L.speechPlayer_stage_free(h)
