@@ -435,7 +435,9 @@ long long speechPlayer_pcmSpectrogram(const sample* pcm, long long length, int n
  * Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: no batch, a batch that has not been synthesised since it was set, nFft not a
  * power of two in 64 .. 4096, hop <= 0, phase < 0, power outside {1, 2}, nBands <= 0 with a bank, a non-finite window or bank value,
  * logScale != 0 with floor <= 0, a non-finite logScale or floor, an unknown format, an utterance number outside the batch, a rowStride
- * below the largest step count, an output that is not device memory of the batch's device, misaligned to the element or too small. */
+ * below the largest step count, an output that is not device memory of the batch's device, misaligned to the element or too small.
+ * Out of scope: live handles through this export (the last nFft - 1 samples would have to persist across pulls: "Signal stages that keep
+ * a window", below, keep them -- speechPlayer_batch_stageSpectrogram). */
 long long speechPlayer_batch_exportSpectrogram(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int nFft,
 	long long hop, long long phase, const double* window, const double* bank, int nBands, int power, double logScale, double floor,
 	void* deviceOut, int format, long long rowStride, void* stream);
@@ -522,7 +524,8 @@ long long speechPlayer_batch_exportResampled(speechPlayer_batch_t batch, const l
  * outside the signal, pad blocks to a multiple of four taps and stage masked inputs.
  * Like the resampler, the result is a function of the batch's PCM: it depends on the mode and, in MODE_FAST, on whatever that mode's
  * tolerance allows; it needs a synthesis launch.
- * Out of scope: live handles (filter state across pulls); NodePlayer, which reaches the export through speechPlayer_node_part;
+ * Out of scope: live handles through this export (the last K - 1 samples would have to persist across pulls: "Signal stages that keep a
+ * window", below, keep them -- speechPlayer_batch_stageConvolve); NodePlayer, which reaches the export through speechPlayer_node_part;
  * per-row gains and wet/dry mixes (put them in the response); FFT or MFMA formulations.  A spectrogram or resampling of the convolved
  * signal is speechPlayer_batch_exportSpectrogramOf / exportResampledOf of this export's output ("The exports of a signal", below).
  *
@@ -917,7 +920,8 @@ long long speechPlayer_batch_exportCodedOf(speechPlayer_batch_t batch, const spe
  * deviceCodes that overlaps the chunk, or the two each other; a row that would pass 2^44; a stage that was freed, alone or with its
  * batch (the handle names nothing any more); for a code stage, neither output given; deviceCodes on a stage that is not a code stage.
  * Out of scope: the convolution, spectrogram, LPC, pitch and tempo exports chunk by chunk; saving a stage's state to the host; NodePlayer;
- * a fused kernel for a chain of stages.  The kernels are csrc/klatt_stage.h.
+ * a fused kernel for a chain of stages ("Signal stages that keep a window", below, adds the convolution and the spectrogram:
+ * speechPlayer_batch_stageConvolve, speechPlayer_batch_stageSpectrogram).  The kernels are csrc/klatt_stage.h.
  */
 typedef void* speechPlayer_stage_t;
 speechPlayer_stage_t speechPlayer_batch_stageResample(speechPlayer_batch_t batch, long long nRows, int srcRate, int outRate, int zeros, double rolloff,
@@ -932,6 +936,57 @@ int speechPlayer_stage_reset(speechPlayer_stage_t stage, const unsigned char* ro
 int speechPlayer_stage_counts(speechPlayer_stage_t stage, long long* consumed, long long* emitted);
 void speechPlayer_stage_free(speechPlayer_stage_t stage);
 long long speechPlayer_resampleEmitted(long long consumed, int srcRate, int outRate, int zeros, double rolloff, int ended);
+/*
+ * Signal stages that keep a window: the convolution and the spectrogram fed chunk by chunk -- the two ends of a live chain, the speech
+ * through a room, a channel or a microphone first and the log-mel of what comes out last.  Both are stages as above (made on a batch, pushed
+ * with speechPlayer_stage_push, planned, reset, counted and freed by the same entry points) whose per-row state is a window of the row's
+ * most recent samples, float32 as x gave them and +0 before sample 0: the resampler stage's history with a length per row.
+ * As above, a row has consumed N samples and emitted M outputs since its start; a push of c samples makes N' = N + c; an ended row is
+ * fresh afterwards (N = M = 0, the history +0), and so is a row that speechPlayer_stage_reset names.
+ *   convolution  (ir, irStart, nIr, irOf, tail: speechPlayer_batch_exportConvolved's arguments and refusals; irOf is per row of the
+ *                STAGE.)  Row r has K_r taps and keeps H_r = K_r - 1 samples.  Open, a push emits c outputs, y[N .. N' - 1] of the row's
+ *                stream.  Ended with tail 1: c + K_r - 1 outputs; ended with tail 0: c.
+ *   spectrogram  (nFft, hop, phase, window, bank, nBands, power, logScale, floor: speechPlayer_batch_exportSpectrogram's arguments and
+ *                refusals.)  Step j is centred on c_j = phase + j hop and reads the samples c_j - nFft / 2 .. c_j + nFft / 2 - 1: a frame
+ *                (before, after) = (nFft / 2, nFft / 2 - 1).  Open, the steps emitted after N samples are those whose whole frame lies at
+ *                or before sample N - 1: E_open(N) = 0 if N - after - 1 - phase < 0, else floor((N - after - 1 - phase) / hop) + 1.
+ *                Ended: the definition's ceil((N - phase) / hop), 0 when N <= phase; samples past the end are +0, as the definition has
+ *                them.  A push emits E(N', ended) - M steps.  A row keeps H = before + after = nFft - 1 samples.
+ * Lemma (the convolution's bits).  speechPlayer_batch_exportConvolved's lemma applies: inserting or removing products that are +-0 changes
+ * nothing behind the closing + 0.0f.  So the outputs H .. H + c - 1 (and the tail's) of the convolution of the virtual row
+ * [history | chunk | +0] are the definition's, whether the history holds real samples or the +0 of a fresh row, and tap blocks whose
+ * inputs all lie before the stream's first sample or past its last are skipped as the export skips them.
+ * Lemma (the spectrogram's history).  Step M, the first not yet emitted with N consumed, has c_M > N - 1 - after, so its oldest sample
+ * c_M - before >= N - (before + after); later steps reach no further back.  H = before + after = nFft - 1 samples therefore suffice
+ * whatever hop and phase are, a hop above nFft (which skips samples) included.  Everything is in 64-bit integers; N <= 2^44, and a
+ * hop or a phase above 2^45 means 2^45 (no row has that many samples).
+ * The claim.  For every row, the outputs of its pushes up to and including the one that ends it, concatenated, are
+ * speechPlayer_signalConvolve (with tail) / speechPlayer_signalSpectrogram of the concatenation of its chunks -- a chunk of int16 and a
+ * chunk of float32 count alike, each through x --, under those exports' bounds: BIT FOR BIT for the convolution and for the spectrogram's
+ * linear values; through the logarithm each side calls its own log10, and the device lies within 4 ulp of the host in float64, within one
+ * float32 ulp of the rounded host value in float32.
+ * The convolution's output is the other stages': deviceOut in format 0 int16 or 1 float32, rowStride > 0 padded rows (+0 past a row's
+ * outputs) or 0 the rows back to back, outLengths the counts, so it feeds the next stage as its chunk.  The spectrogram's is
+ * [row][step][bands] -- the bins nFft / 2 + 1 without a bank --: format 0 is float64 and 1 float32 (the spectrogram export's meanings, not
+ * int16 / float32), rowStride is in STEPS (0: packed), outLengths are steps per row and the return value is the element count, steps times
+ * bands; padding is +0.  It is not a signal, so a spectrogram stage ends a chain.  Window, twiddles, bank weights and ranges, and the
+ * responses, are the stage's own, uploaded once when it is made.
+ * speechPlayer_spectrogramEmitted is host only and needs no stage: the steps a spectrogram row has emitted after `consumed` samples, open
+ * or ended; the difference of two is a push's count.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT (the makers return NULL, the others -1), nothing written AND THE STATE UNCHANGED: what the
+ * whole-row exports refuse of the same arguments; nRows outside 1 .. 2^20; a stage whose histories -- the sum over its rows of H_r --
+ * exceed 2^27 float32 per buffer (512 MiB; there are two), before anything is allocated; and of a push what the stages above refuse,
+ * deviceCodes included.  speechPlayer_spectrogramEmitted refuses consumed outside 0 .. 2^44, an nFft that is no power of two in
+ * 64 .. 4096, hop <= 0 and phase < 0.
+ * Out of scope: LPC, pitch and tempo chunk by chunk (the frame bookkeeping here is written for a general (before, after) and serves the
+ * first two); a mix stage (an SNR needs the whole row's power); FFT or MFMA convolution; saving a stage's state to the host; NodePlayer;
+ * a fused kernel for a chain.  The kernels are csrc/klatt_stage_window.h.
+ */
+speechPlayer_stage_t speechPlayer_batch_stageConvolve(speechPlayer_batch_t batch, long long nRows, const float* ir, const long long* irStart, long long nIr,
+	const long long* irOf, int tail);
+speechPlayer_stage_t speechPlayer_batch_stageSpectrogram(speechPlayer_batch_t batch, long long nRows, int nFft, long long hop, long long phase,
+	const double* window, const double* bank, int nBands, int power, double logScale, double floor);
+long long speechPlayer_spectrogramEmitted(long long consumed, int nFft, long long hop, long long phase, int ended);
 /*
  * Linear prediction (LPC) of a batch's PCM, or of a signal's rows, on the step grid of the other exports: per analysis frame the
  * autocorrelation, the prediction coefficients, the reflection coefficients and the prediction error; and, per sample, the residual or

@@ -78,6 +78,7 @@ EXPORTS = [
     "speechPlayer_batch_exportTempoPositions", "speechPlayer_batch_exportTempoPositionsOf", "speechPlayer_batch_exportTempo", "speechPlayer_batch_exportTempoOf",
     "speechPlayer_batch_stageResample", "speechPlayer_batch_stageFilter", "speechPlayer_batch_stageCode", "speechPlayer_stage_plan", "speechPlayer_stage_push",
     "speechPlayer_stage_reset", "speechPlayer_stage_counts", "speechPlayer_stage_free", "speechPlayer_resampleEmitted",
+    "speechPlayer_batch_stageConvolve", "speechPlayer_batch_stageSpectrogram", "speechPlayer_spectrogramEmitted",
 ]
 
 
@@ -517,6 +518,12 @@ def load():
     L.speechPlayer_stage_free.argtypes = [vp]
     L.speechPlayer_resampleEmitted.restype = i64
     L.speechPlayer_resampleEmitted.argtypes = [i64, i32, i32, i32, f64, i32]
+    L.speechPlayer_batch_stageConvolve.restype = vp
+    L.speechPlayer_batch_stageConvolve.argtypes = [vp, i64, vp, vp, i64, vp, i32]
+    L.speechPlayer_batch_stageSpectrogram.restype = vp
+    L.speechPlayer_batch_stageSpectrogram.argtypes = [vp, i64, i32, i64, i64, vp, vp, i32, i32, f64, f64]
+    L.speechPlayer_spectrogramEmitted.restype = i64
+    L.speechPlayer_spectrogramEmitted.argtypes = [i64, i32, i64, i64, i32]
     _lib = L
     return L
 

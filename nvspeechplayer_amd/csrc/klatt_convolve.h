@@ -16,6 +16,8 @@
 //   The indices     What the kernel visits, as plain functions a stand-alone program checks against brute force
 //                   (tests/native/check_convolve.cpp): conv_blocks, conv_block_taps, conv_block_padded, conv_block_skipped, conv_block_last,
 //                   conv_staged_sample, conv_window.
+//   conv_rows       The one body of klatt_convolve and of klatt_stage_convolve (klatt_stage_window.h: the convolution fed chunk by chunk), its
+//                   two entry points; KEPT is the compile-time switch for "this launch carries state", and the entry point hands in the reader.
 //   klatt_convolve  A 256-lane workgroup takes tiles of kConvolveTile consecutive outputs of one row; lane l owns the FOUR outputs
 //                   4 l .. 4 l + 3 of the tile and keeps their sums in registers across the tap blocks, which is what keeps every
 //                   output's terms in ascending k from the first block to the last.  Per block of kConvolveBlock taps the workgroup stages
@@ -175,8 +177,11 @@ struct ConvArgs {
     const float* taps;                   // the responses back to back
 };
 
-template <bool F32, typename In = int16_t>
-__global__ void __launch_bounds__(256) klatt_convolve(const ConvArgs A)
+// The one body of klatt_convolve and of klatt_stage_convolve (klatt_stage_window.h), its two entry points.  KEPT: the launch carries state --
+// output t of a row is y[N + t] of the row's stream, whose samples 0 .. N + len - 1 exist (the block tests run at that index), its taps
+// are the row's history + 1, and `read` fills the reversed inputs from the virtual row; otherwise from the row itself (tile_read).
+template <bool KEPT, bool F32, typename In, class Args, class Read>
+__device__ __forceinline__ void conv_rows(const Args& A, Read read)
 {
     using T = TileValue<F32>;
     constexpr int TILE = kConvolveTile;
@@ -187,21 +192,24 @@ __global__ void __launch_bounds__(256) klatt_convolve(const ConvArgs A)
     for (long long g = blockIdx.x; g < A.tile.nTiles; g += gridDim.x) {
         long long r, t0;
         tile_locate(A.tile, g, TILE, r, t0);
-        const ConvRow row = A.rows[r];
+        const auto row = A.rows[r];
         const int n = tile_n(A.tile.rowStride, row.outLen, t0, TILE);
         const int live = tile_live(n, row.outLen, t0);      // outputs of the tile inside the row; the rest is padding
         const In* __restrict__ pcm = static_cast<const In*>(A.in) + row.src;
         const float* __restrict__ h = A.taps + row.irAt;
-        const int K = (int)row.taps;
+        long long first = t0, L = row.len;                   // the tile's first output and the samples there are, in the coordinates of the block tests
+        int K;
+        if constexpr (KEPT) { first = row.N + t0; L = row.N + row.len; K = (int)row.H + 1; }
+        else K = (int)row.taps;
         float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (live > 0) {
             for (int kb = 0; kb < K; kb += kConvolveBlock) {      // (every condition here is uniform over the workgroup)
-                if (conv_block_last(t0, live, kb)) break;
+                if (conv_block_last(first, live, kb)) break;
                 const int taps = conv_block_taps(K, kb), padded = conv_block_padded(taps);
-                if (conv_block_skipped(t0, live, row.len, kb, taps)) continue;
+                if (conv_block_skipped(first, live, L, kb, taps)) continue;
                 __syncthreads();                                  // the block before has been read
                 for (int i = tid; i < padded; i += 256) hs[i] = i < taps ? h[kb + i] : 0.0f;
-                tile_read<-1>(xr, pcm, row.len, conv_read_first(t0, kb), TILE + padded, tid);
+                read(xr, pcm, row, conv_read_first(first, kb), TILE + padded, tid);
                 __syncthreads();
                 const float4* __restrict__ xw = reinterpret_cast<const float4*>(xr + conv_window(tid));
                 const float4* __restrict__ hw = reinterpret_cast<const float4*>(hs);
@@ -222,6 +230,14 @@ __global__ void __launch_bounds__(256) klatt_convolve(const ConvArgs A)
         tile_store<T>(A.tile.out, row.dst + t0, n, staged, tid);
         __syncthreads();      // `staged` is the next tile's xr
     }
+}
+
+template <bool F32, typename In = int16_t>
+__global__ void __launch_bounds__(256) klatt_convolve(const ConvArgs A)
+{
+    conv_rows<false, F32, In>(A, [](float* xr, const In* __restrict__ pcm, const ConvRow& row, long long s0, int count, int tid) {
+        tile_read<-1>(xr, pcm, row.len, s0, count, tid);
+    });
 }
 
 }  // namespace klatt

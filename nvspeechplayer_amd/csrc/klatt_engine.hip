@@ -26,6 +26,7 @@
 #include "klatt_filter.h"
 #include "klatt_codec.h"
 #include "klatt_stage.h"
+#include "klatt_stage_window.h"
 #include "klatt_lpc.h"
 #include "klatt_pitch.h"
 #include "klatt_tempo.h"
@@ -720,6 +721,14 @@ struct Stage {
     DeviceBuffer<float> dFilterState;          // [nRows][kStageFilterState]
     int codec = 0;                             // code
     DeviceBuffer<int> dCodeState;              // [nRows][2]
+    StageWindowGeometry win;                   // convolution, spectrogram (klatt_stage_window.h): their histories are dHist, row r's from histAt[r]
+    std::vector<long long> histAt;             // [nRows + 1]
+    std::vector<long long> irAt;               // convolution: [nRows] the row's response, its first tap (its taps: the row's history + 1)
+    DeviceBuffer<float> dTaps;                 // the responses back to back
+    SpecPlan spec;                             // spectrogram: the plan without its arrays, which the device holds
+    DeviceBuffer<float> dWindow, dWeights;
+    DeviceBuffer<SpecCx> dTw;
+    DeviceBuffer<int> dRange;
     hipEvent_t done = nullptr;
     bool used = false;
 };
@@ -745,6 +754,7 @@ void stage_release(Stage* s)
     }
     if (s->done) { if (s->used) (void)hipEventSynchronize(s->done); (void)hipEventDestroy(s->done); }
     s->dTable.release(); s->dHist[0].release(); s->dHist[1].release(); s->dFilterState.release(); s->dCodeState.release();
+    s->dTaps.release(); s->dWindow.release(); s->dWeights.release(); s->dTw.release(); s->dRange.release();
     delete s;
 }
 
@@ -4723,6 +4733,32 @@ long long speechPlayer_signalSpectrogram(const void* x, int inFormat, long long 
     return spectrogram_statement("signalSpectrogram", x, inFormat, length, nFft, hop, phase, window, bank, nBands, power, logScale, floor, out);
 }
 
+// What a spectrogram kernel takes of the plan, the step grid, the packed form's row table (null: padded) and the output: everything but
+// the input, the rows and the plan's arrays on the device (the whole-row export's and the stage's: klatt_stage_window.h)
+static SpecArgs spec_args(const ExportStage& stage, const SpecPlan& P, const RowTable* table, int wordsAt, long long rowStride, long long elements, long long hop,
+                          long long phase, void* deviceOut)
+{
+    SpecArgs A{};
+    A.start = table ? stage.device<long long>(wordsAt) + table->startOff : nullptr;
+    A.chunk = table ? stage.device<long long>(wordsAt) + table->chunkOff : nullptr;
+    A.rowStride = rowStride; A.nSteps = elements / P.nOut;
+    A.hop = hop; A.phase = phase;
+    A.logN = P.logN; A.nOut = P.nOut; A.hasBank = P.hasBank; A.power = P.power;
+    A.logScale = P.logScale; A.floor = P.floor;
+    A.out = deviceOut; A.vec = reinterpret_cast<uintptr_t>(deviceOut) % 16 == 0;
+    return A;
+}
+// A spectrogram kernel over the steps of `S`, four a workgroup, queued on the stage's stream
+extern "C++" template <class Args>
+static int queue_spectrogram(const ExportStage& stage, void (*kernel)(Args), const Args& A, const SpecArgs& S)
+{
+    const long long nGroups = (S.nSteps + kSpecWaves - 1) / kSpecWaves;
+    const unsigned grid = (unsigned)std::min<long long>(nGroups, 16ll * stage.b->cus);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kSpecWaves), (size_t)kSpecWaves * spec_lds_wave(1 << (S.logN - 1)), stage.st, A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // The spectrogram of chosen utterances' PCM, one wavefront per step (klatt_spectrum.h).  It reads the pool, so it is ordered as
 // speechPlayer_batch_exportPcm is (ExportStage, ofPcm).  The staging block: rows | step starts and chunk rows (packed) | window |
 // twiddles | band weights | band ranges.
@@ -4766,22 +4802,11 @@ static long long spectrogram_export(const char* what, speechPlayer_batch_t batch
         const auto kernel = kernels[in.format()][format];
         ExportStage stage(b, st, block, nullptr, !in.sig, in.sig != nullptr);
         if (stage.begin([&] { return ensure_lds_limit(reinterpret_cast<const void*>(kernel), kSpecLdsBudget); })) return -1;
-        SpecArgs A;
+        SpecArgs A = spec_args(stage, P, packed ? &table : nullptr, wordsAt, rowStride, elements, hop, phase, deviceOut);
         A.in = in.data; A.rows = stage.device<SpecRow>(rowsAt);
-        A.start = packed ? stage.device<long long>(wordsAt) + table.startOff : nullptr;
-        A.chunk = packed ? stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
-        A.rowStride = rowStride; A.nSteps = elements / P.nOut;
-        A.hop = hop; A.phase = phase;
         A.window = stage.device<float>(windowAt); A.tw = stage.device<SpecCx>(twAt);
         A.weights = stage.device<float>(weightsAt); A.range = stage.device<int>(rangeAt);
-        A.logN = P.logN; A.nOut = P.nOut; A.hasBank = P.hasBank; A.power = P.power;
-        A.logScale = P.logScale; A.floor = P.floor;
-        A.out = deviceOut; A.vec = reinterpret_cast<uintptr_t>(deviceOut) % 16 == 0;
-        const long long nGroups = (A.nSteps + kSpecWaves - 1) / kSpecWaves;
-        const unsigned grid = (unsigned)std::min<long long>(nGroups, 16ll * b->cus);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kSpecWaves), (size_t)kSpecWaves * spec_lds_wave(P.M), st, A);
-        HIP_TRY(hipGetLastError());
-        if (stage.finish()) return -1;
+        if (queue_spectrogram(stage, kernel, A, A) || stage.finish()) return -1;
         return elements;
     });
 }
@@ -4835,14 +4860,20 @@ static TileOut tile_out(const ExportStage& stage, int wordsAt, const TileTable& 
     const long long* words = rowStride == 0 ? stage.device<long long>(wordsAt) : nullptr;      // (the padded form has no row table)
     return TileOut{words ? words + t.table.startOff : nullptr, words ? words + t.table.chunkOff : nullptr, rowStride, t.tilesPerRow, t.nTiles, deviceOut};
 }
-// The kernel of the format over the tiles, at most perCu workgroups per CU: the stage's last launch
+// The kernel of the format over the tiles, at most perCu workgroups per CU, queued on the stage's stream
 extern "C++" template <class Args>
-static int launch_tiles(ExportStage& stage, void (*int16)(Args), void (*float32)(Args), int format, long long perCu, const Args& A)
+static int queue_tiles(const ExportStage& stage, void (*int16)(Args), void (*float32)(Args), int format, long long perCu, const Args& A)
 {
     const unsigned grid = (unsigned)std::min<long long>(A.tile.nTiles, perCu * stage.b->cus);
     hipLaunchKernelGGL(format ? float32 : int16, dim3(grid), dim3(256), 0, stage.st, A);
     HIP_TRY(hipGetLastError());
-    return stage.finish();
+    return 0;
+}
+// ... as the stage's last launch
+extern "C++" template <class Args>
+static int launch_tiles(ExportStage& stage, void (*int16)(Args), void (*float32)(Args), int format, long long perCu, const Args& A)
+{
+    return queue_tiles(stage, int16, float32, format, perCu, A) || stage.finish() ? -1 : 0;
 }
 
 // The same with a kernel per input type: kernels[input format][output format]
@@ -5051,6 +5082,10 @@ long long speechPlayer_signalConvolve(const void* x, int inFormat, long long len
     return convolve_statement("signalConvolve", x, inFormat, length, ir, taps, tail, format, out, capacity);
 }
 
+// Tiles cost in proportion to their response's taps: many more workgroups than the device holds at once, so that the dispatcher evens out
+// what a fixed share per workgroup would not (the whole-row export and the stage alike).
+constexpr long long kConvolveGroupsPerCu = 64;
+
 // The chosen utterances' PCM, each row through the response irOf names (klatt_convolve.h).  It reads the pool, so it is ordered as
 // speechPlayer_batch_exportPcm is (ExportStage, ofPcm), tile-wise; the rows carry their response as well.  The staging block: rows | tile
 // starts and chunk rows (packed) | the responses.  Nothing is kept on the batch: the kernel reads the responses from the call's own slot.
@@ -5088,10 +5123,8 @@ static long long convolved_export(const char* what, speechPlayer_batch_t batch, 
         A.in = in.data; A.rows = stage.device<ConvRow>(rowsAt);
         A.tile = tile_out(stage, wordsAt, tiles, rowStride, deviceOut);
         A.taps = stage.device<float>(tapsAt);
-        // Tiles cost in proportion to their response's taps: many more workgroups than the device holds at once, so that the dispatcher
-        // evens out what a fixed share per workgroup would not.
         void (*const kernels[2][2])(ConvArgs) = {{klatt_convolve<false, int16_t>, klatt_convolve<true, int16_t>}, {klatt_convolve<false, float>, klatt_convolve<true, float>}};
-        if (launch_tiles(stage, kernels, in.format(), format, 64, A)) return -1;
+        if (launch_tiles(stage, kernels, in.format(), format, kConvolveGroupsPerCu, A)) return -1;
         return elements;
     });
 }
@@ -5426,7 +5459,7 @@ long long speechPlayer_batch_exportCodedOf(speechPlayer_batch_t batch, const spe
 }
 
 // ---- signal stages (klatt_stage.h): the resampler, the filter and the codecs chunk by chunk ---------------------------------------------------
-static_assert(sizeof(StageResRow) % 8 == 0 && sizeof(StageLaneRow) % 8 == 0, "rows are arrays of 8-byte words");
+static_assert(sizeof(StageResRow) % 8 == 0 && sizeof(StageLaneRow) % 8 == 0 && sizeof(StageWinRow) % 8 == 0, "rows are arrays of 8-byte words");
 
 // Host only, touches no device: the outputs a resampler stage has emitted after `consumed` samples of a row, open or ended
 long long speechPlayer_resampleEmitted(long long consumed, int srcRate, int outRate, int zeros, double rolloff, int ended)
@@ -5533,6 +5566,94 @@ speechPlayer_stage_t speechPlayer_batch_stageCode(speechPlayer_batch_t batch, lo
     });
 }
 
+// The histories of a window stage (klatt_stage_window.h), row r's H(r) float32 from histAt[r] of either buffer: refused beyond
+// kStageMaxHistory before anything is allocated
+extern "C++" template <class Len>
+static int stage_window_histories(const char* what, Batch* b, Stage* s, Len H)
+{
+    s->histAt.assign((size_t)s->nRows + 1, 0);
+    for (long long i = 0; i < s->nRows; ++i) {
+        s->histAt[(size_t)i + 1] = s->histAt[(size_t)i] + H(i);
+        if (s->histAt[(size_t)i + 1] > kStageMaxHistory) {
+            set_error("%s: the rows' histories take more than 2^27 samples in all (row %lld keeps %lld)", what, i, (long long)H(i));
+            return -1;
+        }
+    }
+    const size_t n = (size_t)s->histAt[(size_t)s->nRows];
+    return n == 0 ? 0 : stage_zeros(b, s->dHist[0], n) || stage_zeros(b, s->dHist[1], n) ? -1 : 0;
+}
+extern "C++" template <class T>
+static int stage_upload(Batch* b, DeviceBuffer<T>& buf, const std::vector<T>& v)
+{
+    if (v.empty()) return 0;
+    HIP_TRY(hipSetDevice(b->device));
+    if (buf.reserve(v.size())) return -1;
+    HIP_TRY(hipMemcpy(buf.ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+speechPlayer_stage_t speechPlayer_batch_stageConvolve(speechPlayer_batch_t batch, long long nRows, const float* ir, const long long* irStart, long long nIr,
+                                                      const long long* irOf, int tail)
+{
+    const char* what = "stageConvolve";
+    return stage_create(what, batch, nRows, [&](Batch* b, Stage* s) -> int {
+        ConvPlan P;
+        std::string why;
+        if (!conv_plan(P, ir, irStart, nIr, tail, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        s->g.kind = kStageConvolve; s->win.kind = kStageConvolve; s->win.tail = tail;
+        s->irAt.resize((size_t)s->nRows);
+        std::vector<long long> taps((size_t)s->nRows);
+        for (long long i = 0; i < s->nRows; ++i) {
+            const long long j = conv_row(P, irOf, i, why);
+            if (j < 0) { set_error("%s: %s", what, why.c_str()); return -1; }
+            s->irAt[(size_t)i] = P.start[(size_t)j];
+            taps[(size_t)i] = P.start[(size_t)j + 1] - P.start[(size_t)j];
+        }
+        if (stage_window_histories(what, b, s, [&](long long i) { return (long long)stage_conv_history(taps[(size_t)i]); })) return -1;
+        return stage_upload(b, s->dTaps, P.taps);
+    });
+}
+
+// hop and phase of a stage's step grid: a row may consume 2^44 samples, so a larger hop or phase means the same as kStageMaxStep = 2^45
+// (the whole-row exports, whose rows are shorter, stop at 2^40)
+static int stage_step_request(const char* what, long long& hop, long long& phase)
+{
+    if (hop <= 0 || phase < 0) { set_error("%s: hop %lld, phase %lld", what, hop, phase); return -1; }
+    hop = std::min(hop, kStageMaxStep); phase = std::min(phase, kStageMaxStep);
+    return 0;
+}
+
+speechPlayer_stage_t speechPlayer_batch_stageSpectrogram(speechPlayer_batch_t batch, long long nRows, int nFft, long long hop, long long phase, const double* window,
+                                                         const double* bank, int nBands, int power, double logScale, double floor)
+{
+    const char* what = "stageSpectrogram";
+    return stage_create(what, batch, nRows, [&](Batch* b, Stage* s) -> int {
+        if (stage_step_request(what, hop, phase)) return -1;
+        SpecPlan& P = s->spec;
+        std::string why;
+        if (!spec_plan(P, nFft, window, bank, nBands, power, logScale, floor, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        s->g.kind = kStageSpectrogram; s->win.kind = kStageSpectrogram; s->win.frames = stage_spec_frames(nFft, hop, phase);
+        const long long H = stage_frame_history(s->win.frames);
+        if (stage_window_histories(what, b, s, [&](long long) { return H; })) return -1;
+        if (stage_upload(b, s->dWindow, P.window) || stage_upload(b, s->dTw, P.tw) || stage_upload(b, s->dWeights, P.weights) || stage_upload(b, s->dRange, P.range)) return -1;
+        std::vector<float>().swap(P.window); std::vector<SpecCx>().swap(P.tw); std::vector<float>().swap(P.weights); std::vector<int>().swap(P.range);      // (the device holds what the pushes read)
+        return 0;
+    });
+}
+
+// Host only, touches no device: the steps a spectrogram stage has emitted after `consumed` samples of a row, open or ended
+long long speechPlayer_spectrogramEmitted(long long consumed, int nFft, long long hop, long long phase, int ended)
+{
+    begin_call();
+    const char* what = "spectrogramEmitted";
+    if (consumed < 0 || consumed > kResampleMaxLength) { set_error("%s: %lld samples consumed (0 .. 2^44)", what, consumed); return -1; }
+    if (nFft < kSpecMinFft || nFft > kSpecMaxFft || (nFft & (nFft - 1))) { set_error("%s: nFft %d (a power of two in %d .. %d)", what, nFft, kSpecMinFft, kSpecMaxFft); return -1; }
+    if (stage_step_request(what, hop, phase)) return -1;
+    return stage_frames_emitted(stage_spec_frames(nFft, hop, phase), consumed, ended != 0);
+}
+
+static bool stage_window(const Stage* s) { return s->g.kind == kStageConvolve || s->g.kind == kStageSpectrogram; }
+
 // The stage a handle names, or null with the message set: a handle that was freed -- alone or with its batch -- names none
 static Stage* stage_of(const char* what, speechPlayer_stage_t stage)
 {
@@ -5551,7 +5672,9 @@ static int stage_selection(const char* what, const Stage* s, Len len, const unsi
     for (long long i = 0; i < s->nRows; ++i) {
         const long long c = len(i);
         long long out;
-        if (!stage_row_plan(s->g, s->N[(size_t)i], s->M[(size_t)i], c, end && end[i], out)) {
+        const bool fits = stage_window(s) ? stage_window_row_plan(s->win, s->histAt[(size_t)i + 1] - s->histAt[(size_t)i] + 1, s->N[(size_t)i], s->M[(size_t)i], c, end && end[i], out)
+                                          : stage_row_plan(s->g, s->N[(size_t)i], s->M[(size_t)i], c, end && end[i], out);
+        if (!fits) {
             set_error("%s: row %lld has consumed %lld samples and would take %lld more (0 or more, at most 2^44 in all)", what, i, s->N[(size_t)i], c);
             return -1;
         }
@@ -5578,16 +5701,18 @@ long long speechPlayer_stage_plan(speechPlayer_stage_t stage, const long long* l
 }
 
 // One push's passage through a slot: ExportStage over a signal, behind the stage's last push whichever stream that was on
-struct StagePass {
+extern "C++" struct StagePass {
     Stage* s;
     ExportStage stage;
     StagePass(Stage* s, hipStream_t st, const StageBlock& block) : s(s), stage(s->b, st, block, nullptr, false, true) {}
-    int begin()
+    template <class Grow>
+    int begin(Grow grow)
     {
-        if (stage.begin()) return -1;
+        if (stage.begin(grow)) return -1;
         if (s->used) HIP_TRY(hipStreamWaitEvent(stage.st, s->done, 0));
         return 0;
     }
+    int begin() { return begin([] { return 0; }); }
     int finish()
     {
         HIP_TRY(hipEventRecord(s->done, stage.st));
@@ -5717,6 +5842,86 @@ static int stage_push_code(Stage* s, const ExportInput& in, const unsigned char*
     return launch_adpcm(pass.stage, in.format(), outputs, format, A) || pass.finish() ? -1 : 0;
 }
 
+// The rows of a window stage's push (klatt_stage_window.h)
+static std::vector<StageWinRow> stage_window_rows(const Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long rowStride)
+{
+    std::vector<StageWinRow> rows((size_t)s->nRows);
+    long long before = 0;
+    for (long long i = 0; i < s->nRows; ++i) {
+        rows[(size_t)i] = StageWinRow{in.at(i), in.len(i), s->N[(size_t)i], s->M[(size_t)i], sel.counts[(size_t)i], tile_row_first(i, rowStride, before), end && end[i],
+                                      s->histAt[(size_t)i], s->histAt[(size_t)i + 1] - s->histAt[(size_t)i], s->g.kind == kStageConvolve ? s->irAt[(size_t)i] : 0};
+        before += sel.counts[(size_t)i];
+    }
+    return rows;
+}
+// The next history of every row of a window stage, into the buffer nothing of this push reads, behind the push's kernel; then the buffers
+// change places
+static int stage_window_finish(Stage* s, StagePass& pass, const ExportInput& in, const StageWinRow* dRows, long long mostHistory)
+{
+    if (mostHistory > 0) {
+        const dim3 hgrid((unsigned)std::min<long long>((mostHistory + 255) / 256, 64), (unsigned)std::min<long long>(s->nRows, 16ll * s->b->cus));
+        hipLaunchKernelGGL(in.format() ? klatt_stage_history_rows<float> : klatt_stage_history_rows<int16_t>, hgrid, dim3(256), 0, pass.stage.st, in.data, dRows, s->nRows,
+                           s->dHist[s->cur].ptr, s->dHist[s->cur ^ 1].ptr);
+        HIP_TRY(hipGetLastError());
+    }
+    if (pass.finish()) return -1;
+    if (mostHistory > 0) s->cur ^= 1;
+    return 0;
+}
+static long long stage_most_history(const Stage* s)
+{
+    long long most = 0;
+    for (long long i = 0; i < s->nRows; ++i) most = std::max(most, s->histAt[(size_t)i + 1] - s->histAt[(size_t)i]);
+    return most;
+}
+
+static int stage_push_convolve(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, void* deviceOut, int format, long long rowStride,
+                               hipStream_t st)
+{
+    const std::vector<StageWinRow> rows = stage_window_rows(s, in, end, sel, rowStride);
+    std::vector<long long> words;
+    const TileTable tiles = tile_row_table(sel.counts.data(), sel.n, kConvolveTile, rowStride, kTimelineChunkLog2, words);
+    StageBlock block;
+    const int rowsAt = block.add(rows), wordsAt = block.add(words);
+    StagePass pass(s, st, block);
+    if (pass.begin()) return -1;
+    if (tiles.nTiles > 0) {
+        StageConvArgs A;
+        A.in = in.data; A.rows = pass.stage.device<StageWinRow>(rowsAt);
+        A.tile = tile_out(pass.stage, wordsAt, tiles, rowStride, deviceOut);
+        A.taps = s->dTaps.ptr; A.hist = s->dHist[s->cur].ptr;
+        void (*const kernels[2][2])(StageConvArgs) = {{klatt_stage_convolve<false, int16_t>, klatt_stage_convolve<true, int16_t>},
+                                                      {klatt_stage_convolve<false, float>, klatt_stage_convolve<true, float>}};
+        if (queue_tiles(pass.stage, kernels[in.format()][0], kernels[in.format()][1], format, kConvolveGroupsPerCu, A)) return -1;
+    }
+    return stage_window_finish(s, pass, in, pass.stage.device<StageWinRow>(rowsAt), stage_most_history(s));
+}
+
+static int stage_push_spectrogram(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long elements, void* deviceOut, int format,
+                                  long long rowStride, hipStream_t st)
+{
+    const std::vector<StageWinRow> rows = stage_window_rows(s, in, end, sel, rowStride);
+    const bool packed = rowStride == 0;
+    std::vector<long long> words;
+    const RowTable table = packed ? packed_row_table(sel.counts.data(), 0, sel.n, kTimelineChunkLog2, words) : RowTable{0, 0};
+    StageBlock block;
+    const int rowsAt = block.add(rows), wordsAt = block.add(words);
+    void (*const kernels[2][2])(StageSpecArgs) = {{klatt_stage_spectrogram<false, int16_t>, klatt_stage_spectrogram<true, int16_t>},
+                                                  {klatt_stage_spectrogram<false, float>, klatt_stage_spectrogram<true, float>}};
+    const auto kernel = kernels[in.format()][format];
+    StagePass pass(s, st, block);
+    if (pass.begin([&] { return ensure_lds_limit(reinterpret_cast<const void*>(kernel), kSpecLdsBudget); })) return -1;
+    if (elements > 0) {
+        StageSpecArgs A;
+        A.s = spec_args(pass.stage, s->spec, packed ? &table : nullptr, wordsAt, rowStride, elements, s->win.frames.hop, s->win.frames.phase, deviceOut);
+        A.s.in = in.data; A.s.rows = nullptr;
+        A.s.window = s->dWindow.ptr; A.s.tw = s->dTw.ptr; A.s.weights = s->dWeights.ptr; A.s.range = s->dRange.ptr;
+        A.rows = pass.stage.device<StageWinRow>(rowsAt); A.hist = s->dHist[s->cur].ptr;
+        if (queue_spectrogram(pass.stage, kernel, A, A.s)) return -1;
+    }
+    return stage_window_finish(s, pass, in, pass.stage.device<StageWinRow>(rowsAt), stage_most_history(s));
+}
+
 long long speechPlayer_stage_push(speechPlayer_stage_t stage, const speechPlayer_signal_t* chunk, const unsigned char* end, void* deviceOut, int format,
                                   void* deviceCodes, long long rowStride, long long* outLengths, void* stream)
 {
@@ -5727,8 +5932,11 @@ long long speechPlayer_stage_push(speechPlayer_stage_t stage, const speechPlayer
     if (!s) return -1;
     Batch* b = s->b;
     try {
-        const bool code = s->g.kind == kStageCode;
-        if (tile_request(what, format, rowStride)) return -1;
+        const bool code = s->g.kind == kStageCode, spec = s->g.kind == kStageSpectrogram;
+        if (spec) {      // (the spectrogram export's formats, rowStride in steps)
+            if (format != 0 && format != 1) { set_error("%s: format %d (0 float64, 1 float32)", what, format); return -1; }
+            if (rowStride < 0) { set_error("%s: rowStride %lld", what, rowStride); return -1; }
+        } else if (tile_request(what, format, rowStride)) return -1;
         if (!code && deviceCodes) { set_error("%s: deviceCodes on a stage that is not a code stage", what); return -1; }
         SignalPlan sig;
         ExportInput in{b};
@@ -5738,12 +5946,13 @@ long long speechPlayer_stage_push(speechPlayer_stage_t stage, const speechPlayer
         if (stage_selection(what, s, [&](long long i) { return sig.len(i); }, end, sel)) return -1;
         bool active = false;      // a row that is neither fed nor ended is untouched
         for (long long i = 0; i < s->nRows && !active; ++i) active = sig.len(i) > 0 || (end && end[i]);
-        const long long elements = export_elements(what, kSampleNouns, sel, rowStride, 1);
+        static constexpr ExportNouns kBandNouns{"largest step count", "steps", "bands"};
+        const long long elements = spec ? export_elements(what, kBandNouns, sel, rowStride, s->spec.nOut) : export_elements(what, kSampleNouns, sel, rowStride, 1);
         if (elements < 0) return -1;
         if (code && elements > 0 && !deviceOut && !deviceCodes) { set_error("%s: no output (the decoded samples, the codes or both)", what); return -1; }
         if (elements > 0 || active) {
             HIP_TRY(hipSetDevice(b->device));
-            const size_t elSize = format ? sizeof(float) : sizeof(int16_t);
+            const size_t elSize = format ? sizeof(float) : spec ? sizeof(double) : sizeof(int16_t);
             if (elements > 0) {
                 if ((!code || deviceOut) && export_output(b, what, deviceOut, elements, elSize)) return -1;
                 if (deviceCodes && export_output(b, what, deviceCodes, elements, 1)) return -1;
@@ -5756,6 +5965,8 @@ long long speechPlayer_stage_push(speechPlayer_stage_t stage, const speechPlayer
             hipStream_t st = static_cast<hipStream_t>(stream);
             const int rc = s->g.kind == kStageResample ? stage_push_resample(s, in, end, sel, elements, deviceOut, format, rowStride, st)
                          : s->g.kind == kStageFilter   ? stage_push_filter(s, in, end, sel, deviceOut, format, rowStride, st)
+                         : s->g.kind == kStageConvolve ? stage_push_convolve(s, in, end, sel, deviceOut, format, rowStride, st)
+                         : spec                        ? stage_push_spectrogram(s, in, end, sel, elements, deviceOut, format, rowStride, st)
                                                        : stage_push_code(s, in, end, sel, elements, deviceOut, format, deviceCodes, rowStride, st);
             if (rc) return -1;
         }
@@ -5780,6 +5991,18 @@ int speechPlayer_stage_reset(speechPlayer_stage_t stage, const unsigned char* ro
         if (s->g.kind == kStageResample && s->g.Z > 0) { state = reinterpret_cast<uint32_t*>(s->dHist[s->cur].ptr); perRow = stage_history(s->g.Z); }
         else if (s->g.kind == kStageFilter) { state = reinterpret_cast<uint32_t*>(s->dFilterState.ptr); perRow = kStageFilterState; }
         else if (s->g.kind == kStageCode && s->codec == kCodecAdpcm) { state = reinterpret_cast<uint32_t*>(s->dCodeState.ptr); perRow = 2; }
+        if (stage_window(s) && s->histAt[(size_t)s->nRows] > 0) {      // a history per row, each from its own first element
+            HIP_TRY(hipSetDevice(s->b->device));
+            StageBlock block;
+            const int rowsAt = rows ? block.add(rows, (size_t)s->nRows) : -1, atAt = block.add(s->histAt);
+            StagePass pass(s, static_cast<hipStream_t>(stream), block);
+            if (pass.begin()) return -1;
+            const dim3 grid((unsigned)std::min<long long>((stage_most_history(s) + 255) / 256, 64), (unsigned)std::min<long long>(s->nRows, 16ll * s->b->cus));
+            hipLaunchKernelGGL(klatt_stage_clear_rows, grid, dim3(256), 0, pass.stage.st, rows ? pass.stage.device<unsigned char>(rowsAt) : nullptr,
+                               pass.stage.device<long long>(atAt), s->nRows, s->dHist[s->cur].ptr);
+            HIP_TRY(hipGetLastError());
+            if (pass.finish()) return -1;
+        }
         if (state) {
             HIP_TRY(hipSetDevice(s->b->device));
             StageBlock block;

@@ -20,6 +20,8 @@
 //                   keeps for them.  ||Z||_2 <= sqrt(nFft) ||xw||_2 as for the full-length transform (Parseval on the even and odd halves).
 //                   The constant of the full-length radix-2 transform therefore holds:  B = (8 log2 nFft + 8) u sqrt(nFft) ||xw||_2.
 //
+//   spec_rows       The one body of klatt_spectrogram and of klatt_stage_spectrogram (klatt_stage_window.h: the spectrogram fed chunk by chunk),
+//                   its two entry points: a row's steps, a step's first sample and the sample reader are the entry point's, inlined.
 //   klatt_spectrogram   One wavefront per step, four steps (consecutive in the output) per 256-lane workgroup, so that overlapping frames
 //                   come from L1/L2.  A wavefront loads its frame's samples, int16 or float32, masked by 0 <= t < L (klatt_tiles.h:
 //                   tile_sample), multiplies by the window and
@@ -249,8 +251,11 @@ constexpr int kSpecLdsBudget = kSpecWaves * spec_lds_wave(kSpecMaxFft / 2);
 // where element i of z lives: i with its low four bits XORed by its top four (i < M = 1 << logM, logM >= 5)
 __device__ __forceinline__ uint32_t spec_slot(uint32_t i, int logM) { return i ^ (i >> (logM - 4)); }
 
-template <bool F32, typename In = int16_t>
-__global__ void __launch_bounds__(64 * kSpecWaves) klatt_spectrogram(const SpecArgs A)
+// The one body of klatt_spectrogram and of klatt_stage_spectrogram (klatt_stage_window.h), its two entry points: `rows` is the launch's row
+// table, steps(row) the steps of a row in this output, first(row, j) the first sample of its step j's frame, and sample(row, t) sample t
+// as the reader gives it -- of the row itself, or of a stage's virtual row.
+template <bool F32, class Row, class Steps, class First, class Sample>
+__device__ __forceinline__ void spec_rows(const SpecArgs& A, const Row* __restrict__ rows, Steps steps, First first, Sample sample)
 {
     using T = typename std::conditional<F32, float, double>::type;
     constexpr int EL = 16 / (int)sizeof(T);
@@ -266,23 +271,22 @@ __global__ void __launch_bounds__(64 * kSpecWaves) klatt_spectrogram(const SpecA
     for (long long grp = blockIdx.x; grp < nGroups; grp += gridDim.x) {
         const long long g = grp * kSpecWaves + wave;                         // the step's number in the output
         bool inside = g < A.nSteps, live = false;
-        SpecRow row{0, 0, 0};
+        Row row{};
         long long j = 0;
         if (inside) {
             long long r;
             if (A.rowStride > 0) { r = g / A.rowStride; j = g - r * A.rowStride; }
             else { const long long c = g >> kTimelineChunkLog2; packed_locate(g, A.start, A.chunk[c], A.chunk[c + 1] + 1, r, j); }
-            row = A.rows[r];
-            live = j < row.steps;
+            row = rows[r];
+            live = j < steps(row);
         }
         // ---- the frame, windowed, in bit-reversed order ----
         if (live) {
-            const long long t0 = A.phase + j * A.hop - M;
-            const In* __restrict__ pcm = static_cast<const In*>(A.in) + row.src;
+            const long long t0 = first(row, j);
             for (int m = lane; m < M; m += 64) {      // (a lane takes a PAIR of samples: the reader's sample, not its run)
                 const long long ta = t0 + 2 * m, tb = ta + 1;
                 const float2 w = reinterpret_cast<const float2*>(A.window)[m];
-                z[spec_slot(spec_reverse((uint32_t)m, logM), logM)] = SpecCx{spec_windowed(tile_sample(pcm, ta, row.len), w.x), spec_windowed(tile_sample(pcm, tb, row.len), w.y)};
+                z[spec_slot(spec_reverse((uint32_t)m, logM), logM)] = SpecCx{spec_windowed(sample(row, ta), w.x), spec_windowed(sample(row, tb), w.y)};
             }
         }
         // ---- the passes ----
@@ -340,6 +344,15 @@ __global__ void __launch_bounds__(64 * kSpecWaves) klatt_spectrogram(const SpecA
             __syncthreads();
         }
     }
+}
+
+template <bool F32, typename In = int16_t>
+__global__ void __launch_bounds__(64 * kSpecWaves) klatt_spectrogram(const SpecArgs A)
+{
+    const int M = 1 << (A.logN - 1);
+    spec_rows<F32>(A, A.rows, [](const SpecRow& row) { return row.steps; },
+                   [&](const SpecRow&, long long j) { return A.phase + j * A.hop - M; },
+                   [&](const SpecRow& row, long long t) { return tile_sample(static_cast<const In*>(A.in) + row.src, t, row.len); });
 }
 
 }  // namespace klatt

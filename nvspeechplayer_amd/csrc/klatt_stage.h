@@ -39,7 +39,8 @@
 //                   the state after exactly c samples (c + tail for an ended filter row, which is then stored as +0; val = idx = 0).
 //                   Identity padding sits behind the real sections, so the real sections' states are exact; the padding's are never stored.
 //   Out of scope    The convolution, spectrogram, LPC, pitch and tempo exports chunk by chunk; saving a stage's state to the host;
-//                   NodePlayer; a fused kernel for a chain of stages.
+//                   NodePlayer; a fused kernel for a chain of stages.  (klatt_stage_window.h puts the convolution and the spectrogram on
+//                   this header's virtual row, with a history length per row.)
 #pragma once
 
 #include "klatt_codec.h"

@@ -1718,17 +1718,23 @@ def _ready_stream(owner, dev):
     return owner._ready.cuda_stream
 
 
-STAGE_KINDS = ["resample", "filter", "code"]      # kStageResample, kStageFilter, kStageCode of csrc/klatt_stage.h
+# kStageResample, kStageFilter, kStageCode of csrc/klatt_stage.h; kStageConvolve, kStageSpectrogram of csrc/klatt_stage_window.h
+STAGE_KINDS = ["resample", "filter", "code", "convolution", "spectrogram"]
+STAGE_MAKERS = {"convolution": "convolveStage", "spectrogram": "spectrogramStage"}      # (the others: kind + "Stage")
 STAGE_MAX_ROWS = 1 << 20                          # kStageMaxRows
+STAGE_MAX_HISTORY = 1 << 27                       # kStageMaxHistory: float32 of history per buffer, all rows of a stage together
 
 
 def check_stage_request(kind, nRows, *args, **kw):
-    """The argument checks of BatchPlayer.resampleStage, filterStage and codeStage that need no GPU, before any library call: kind a name
-    of STAGE_KINDS; nRows an integer in 1 .. 2^20; then, by kind, the arguments of the whole-row export and its checks --
-    "resample": (srcRate, rate, zeros=6, rolloff=0.99, window="hann", beta=None) through check_resample_request; "filter": (filters,
-    filterOf=None, tail=0) through check_filter_request, filterOf per row of the stage; "code": (codec) through check_codec_request.
+    """The argument checks of BatchPlayer.resampleStage, filterStage, codeStage, convolveStage and spectrogramStage that need no GPU,
+    before any library call: kind a name of STAGE_KINDS; nRows an integer in 1 .. 2^20; then, by kind, the arguments of the whole-row
+    export and its checks -- "resample": (srcRate, rate, zeros=6, rolloff=0.99, window="hann", beta=None) through
+    check_resample_request; "filter": (filters, filterOf=None, tail=0) through check_filter_request, filterOf per row of the stage;
+    "code": (codec) through check_codec_request; "convolution": (irs, irOf=None, tail=True) through check_convolve_request, irOf per
+    row of the stage; "spectrogram": (nFft=1024, hop=256, phase=0, window=None, bank=None, power=2, log=None, floor=1e-10) through
+    check_spectrogram_request -- and, for the last two, the rows' histories (taps - 1 each; nFft - 1 each) within 2^27 samples in all.
     Raises KeyError (the kind, the codec), ValueError or TypeError.  Returns (kind's number, nRows, what the kind's check returns)."""
-    what = "%sStage" % kind if kind in STAGE_KINDS else "stage"
+    what = STAGE_MAKERS.get(kind, "%sStage" % kind) if kind in STAGE_KINDS else "stage"
     if kind not in STAGE_KINDS:
         raise KeyError("%s: kind %r (%s)" % (what, kind, ", ".join(STAGE_KINDS)))
     if isinstance(nRows, (bool, np.bool_)) or not isinstance(nRows, (int, np.integer)):
@@ -1742,6 +1748,20 @@ def check_stage_request(kind, nRows, *args, **kw):
     elif kind == "filter":
         def plan(filters, filterOf=None, tail=0):
             return check_filter_request(filters, filterOf, nRows, tail, None, what)
+    elif kind == "convolution":
+        def plan(irs, irOf=None, tail=True):
+            got = check_convolve_request(irs, irOf, nRows, tail, None, what)
+            taps = np.diff(got[1])
+            history = int((taps[got[2]] - 1).sum()) if got[2] is not None else int(taps[0] - 1) * nRows
+            if history > STAGE_MAX_HISTORY:
+                raise ValueError("%s: the rows' histories take %d samples in all (at most 2^27)" % (what, history))
+            return got
+    elif kind == "spectrogram":
+        def plan(nFft=1024, hop=256, phase=0, window=None, bank=None, power=2, log=None, floor=1e-10):
+            got = check_spectrogram_request(nFft, hop, phase, window, bank, power, log, floor, None, what)
+            if (got[0] - 1) * nRows > STAGE_MAX_HISTORY:
+                raise ValueError("%s: the rows' histories take %d samples in all (at most 2^27)" % (what, (got[0] - 1) * nRows))
+            return got
     else:
         def plan(codec):
             return check_codec_request(codec, True, True, None, what)
@@ -1750,9 +1770,10 @@ def check_stage_request(kind, nRows, *args, **kw):
 
 def check_stage_push(kind, nRows, signal, end=None, dtype=None, codes=False, decoded=True, device=None, what="SignalStage.push"):
     """The argument checks of SignalStage.push that need no GPU: signal as check_signal_request's, of exactly nRows rows; end None, a bool
-    or nRows bools; dtype as the kind's export takes it (None: float32, a code stage's int16); codes and decoded bools that only a code
-    stage takes otherwise than (False, True), not both False.  Raises ValueError or TypeError.  Returns (check_signal_request's answer,
-    end: uint8 [nRows] or None, the output format: 0 int16, 1 float32, codes, decoded)."""
+    or nRows bools; dtype as the kind's export takes it (None: float32, a code stage's int16; a spectrogram stage takes torch.float32 or
+    torch.float64); codes and decoded bools that only a code stage takes otherwise than (False, True), not both False.  Raises ValueError
+    or TypeError.  Returns (check_signal_request's answer, end: uint8 [nRows] or None, the output format: 0 int16, 1 float32 -- a
+    spectrogram stage's: 0 float64, 1 float32 --, codes, decoded)."""
     if kind not in STAGE_KINDS:
         raise KeyError("%s: kind %r (%s)" % (what, kind, ", ".join(STAGE_KINDS)))
     sig = check_signal_request(signal, device, what)
@@ -1775,7 +1796,7 @@ def check_stage_push(kind, nRows, signal, end=None, dtype=None, codes=False, dec
     if kind != "code":
         if codes or not decoded:
             raise ValueError("%s: codes and decoded belong to a code stage" % what)
-        fmt = _sample_format(dtype, what)
+        fmt = _check_dtype(what, dtype, *_float_types()) if kind == "spectrogram" else _sample_format(dtype, what)
     else:
         if not codes and not decoded:
             raise ValueError("%s: codes, decoded or both" % what)
@@ -1791,13 +1812,22 @@ def resampleEmitted(consumed, srcRate, dstRate, zeros=6, rolloff=0.99, ended=Fal
     return _answer(_native.load().speechPlayer_resampleEmitted(int(consumed), srcRate, dstRate, zeros, rolloff, 1 if ended else 0), error=ValueError)
 
 
-class SignalStage(object):
-    """The per-row state of one sequential export -- the resampler, the biquad filter or a codec -- on a BatchPlayer's device, fed chunk by
-    chunk (include/speechPlayer_batch.h, "Signal stages"): what a live handle's pulls go through.  Made by BatchPlayer.resampleStage,
-    filterStage and codeStage; freed by close() or with the player."""
+def spectrogramEmitted(consumed, nFft=1024, hop=256, phase=0, ended=False):
+    """The steps a spectrogram stage has emitted for a row after `consumed` samples, open or ended (speechPlayer_spectrogramEmitted; no
+    GPU): open, the steps j whose whole frame lies at or before the last sample consumed, phase + j * hop + nFft / 2 - 1 <= consumed - 1;
+    ended, ceil((consumed - phase) / hop), pcmSpectrogram's count.  The difference of two is what a push emits."""
+    return _answer(_native.load().speechPlayer_spectrogramEmitted(int(consumed), int(nFft), int(hop), int(phase), 1 if ended else 0), error=ValueError)
 
-    def __init__(self, player, kind, nRows, handle):
+
+class SignalStage(object):
+    """The per-row state of one sequential export -- the resampler, the biquad filter, a codec, the convolution or the spectrogram -- on a
+    BatchPlayer's device, fed chunk by chunk (include/speechPlayer_batch.h, "Signal stages" and "Signal stages that keep a window"): what a
+    live handle's pulls go through.  Made by BatchPlayer.resampleStage, filterStage, codeStage, convolveStage and spectrogramStage; freed
+    by close() or with the player."""
+
+    def __init__(self, player, kind, nRows, handle, bands=None):
         self._bp, self.kind, self.nRows, self._h = player, kind, nRows, handle
+        self.bands = bands      # a spectrogram stage's values per step
         self._dll = player._dll
 
     def _handle(self):
@@ -1822,8 +1852,11 @@ class SignalStage(object):
         end None, a bool or nRows bools: the rows this push ends (a resampler then emits its last outputs, a filter its tail, and the
         row is fresh afterwards).  -> (tensor, lengths), as the whole-row export returns them -- dtype torch.float32 (default) or
         torch.int16; padded [nRows, most] with +0 past each row's outputs, or packed with the nRows + 1 offsets --; a code stage
-        -> (decoded, lengths), (decoded, codes, lengths) or (codes, lengths) as codedTensor, dtype torch.int16 by default.  The outputs
-        of a row's pushes, concatenated, are bit for bit signalResample / signalFilter / signalCode of its chunks concatenated."""
+        -> (decoded, lengths), (decoded, codes, lengths) or (codes, lengths) as codedTensor, dtype torch.int16 by default; a
+        spectrogram stage -> (tensor [nRows, most steps, bands], steps) or, packed, ([total steps, bands], the nRows + 1 offsets), dtype
+        torch.float32 (default) or torch.float64, and takes neither codes nor decoded.  The outputs of a row's pushes, concatenated, are
+        bit for bit signalResample / signalFilter / signalCode / signalConvolve of its chunks concatenated, and signalSpectrogram's (its
+        linear values bit for bit, a logarithm's within the spectrogram export's bar)."""
         import torch
         h, dev = self._handle(), self._bp.device
         sig, flags, fmt, codes, decoded = check_stage_push(self.kind, self.nRows, signal, end, dtype, codes, decoded, dev)
@@ -1839,7 +1872,11 @@ class SignalStage(object):
         record = np.zeros(1, _signalDtype)
         record["data"], record["format"], record["nRows"], record["rowStride"], record["extent"] = tensor.data_ptr(), inFormat, rows, stride, extent.ctypes.data
         name = "cuda:%d" % dev
-        d = torch.empty(shape, dtype=torch.float32 if fmt else torch.int16, device=name) if decoded else None
+        if self.kind == "spectrogram":
+            shape, low = shape + (self.bands,), torch.float64
+        else:
+            low = torch.int16
+        d = torch.empty(shape, dtype=torch.float32 if fmt else low, device=name) if decoded else None
         c = torch.empty(shape, dtype=torch.uint8, device=name) if codes else None
         numel = int(np.prod(shape))
         got = self._dll.speechPlayer_stage_push(h, record.ctypes.data, _ptr(flags), d.data_ptr() if decoded and numel else None, fmt,
@@ -1896,7 +1933,8 @@ class SignalStage(object):
 
 class SignalChain(object):
     """Stages one behind the other: push feeds each stage's (tensor, lengths) pair to the next as its chunk, and `end` travels with it --
-    pcm, produced = group.pullTensor(8192); y = chain.push((pcm, produced)).  Only the last stage may be a code stage."""
+    pcm, produced = group.pullTensor(8192); y = chain.push((pcm, produced)).  A code stage or a spectrogram stage comes last: what it
+    gives is not a signal."""
 
     def __init__(self, stages):
         self.stages = list(stages)
@@ -1904,6 +1942,8 @@ class SignalChain(object):
             raise TypeError("SignalChain: a list of SignalStage objects, at least one")
         if any(s.kind == "code" for s in self.stages[:-1]):
             raise ValueError("SignalChain: a code stage comes last")
+        if any(s.kind == "spectrogram" for s in self.stages[:-1]):
+            raise ValueError("SignalChain: a spectrogram stage comes last")
         if len({s.nRows for s in self.stages}) != 1:
             raise ValueError("SignalChain: the stages have %s rows" % sorted({s.nRows for s in self.stages}))
 
@@ -2768,10 +2808,10 @@ class BatchPlayer(object):
     def deviceOffset(self, u):
         return self._dll.speechPlayer_batch_deviceOffset(self._h, u)
 
-    def _stage(self, kind, nRows, handle):
+    def _stage(self, kind, nRows, handle, bands=None):
         if not handle:
-            raise RuntimeError("%sStage failed: %s" % (kind, _native.last_error()))
-        return SignalStage(self, kind, nRows, handle)
+            raise RuntimeError("%s failed: %s" % (STAGE_MAKERS.get(kind, "%sStage" % kind), _native.last_error()))
+        return SignalStage(self, kind, nRows, handle, bands)
 
     def resampleStage(self, nRows, srcRate, rate, zeros=6, rolloff=0.99, window="hann", beta=None):
         """A SignalStage of nRows rows that resamples from srcRate to rate Hz chunk by chunk (speechPlayer_batch_stageResample):
@@ -2786,6 +2826,22 @@ class BatchPlayer(object):
         push that ends a row emits `tail` more outputs of zero input."""
         _, nRows, (sec, start, of, tail, _) = check_stage_request("filter", nRows, filters, filterOf, tail)
         return self._stage("filter", nRows, self._dll.speechPlayer_batch_stageFilter(self._h, nRows, sec.ctypes.data, start.ctypes.data, len(start) - 1, _ptr(of), tail))
+
+    def convolveStage(self, nRows, irs, irOf=None, tail=True):
+        """A SignalStage of nRows rows through impulse responses chunk by chunk (speechPlayer_batch_stageConvolve): convolvedTensor's
+        irs -- irOf the response of each row of the stage -- with the last taps - 1 samples of every row kept between pushes; a push
+        emits as many samples as it takes, an ended row's its tail of taps - 1 more (tail=True)."""
+        _, nRows, (h, start, of, tail, _) = check_stage_request("convolution", nRows, irs, irOf, tail)
+        return self._stage("convolution", nRows, self._dll.speechPlayer_batch_stageConvolve(self._h, nRows, h.ctypes.data, start.ctypes.data, len(start) - 1, _ptr(of), tail))
+
+    def spectrogramStage(self, nRows, nFft=1024, hop=256, phase=0, window=None, bank=None, power=2, log=None, floor=1e-10):
+        """A SignalStage of nRows rows that takes the STFT or band (mel) spectrogram chunk by chunk
+        (speechPlayer_batch_stageSpectrogram): spectrogramTensor's arguments, with the last nFft - 1 samples of every row kept between
+        pushes; a push emits the steps whose whole frame has come in (spectrogramEmitted), an ended row's the rest of the definition's.
+        Its output is not a signal: it ends a SignalChain."""
+        _, nRows, (nFft, hop, phase, window, bank, bands, power, scale, floor, _) = check_stage_request("spectrogram", nRows, nFft, hop, phase, window, bank, power, log, floor)
+        return self._stage("spectrogram", nRows, self._dll.speechPlayer_batch_stageSpectrogram(self._h, nRows, nFft, hop, phase, _ptr(window), _ptr(bank),
+                                                                                             bands if bank is not None else 0, power, scale, floor), bands)
 
     def codeStage(self, nRows, codec):
         """A SignalStage of nRows rows through a codec chunk by chunk (speechPlayer_batch_stageCode): codedTensor's codecs, the ADPCM

@@ -1,7 +1,9 @@
-"""Times the signal stages (BatchPlayer.resampleStage / filterStage / codeStage; csrc/klatt_stage.h) beside the whole-row exports of a
-signal on the same tensor in the same run, alternating the two: one push of 1024 rows x 8192 float32 samples at 22050 -> 16000 against
-resampledTensor(signal=), the same through the four-section telephone band against filteredTensor(signal=), and the single-row 8192-sample
-push a one-stream caller pays, per kind.  Two figures per call: `queued`, device events around REPS calls issued back to back, per call --
+"""Times the signal stages (BatchPlayer.resampleStage / filterStage / codeStage; csrc/klatt_stage.h; convolveStage / spectrogramStage;
+csrc/klatt_stage_window.h) beside the whole-row exports of a signal on the same tensor in the same run, alternating the two: one push of
+1024 rows x 8192 float32 samples at 22050 -> 16000 against resampledTensor(signal=), the same through the four-section telephone band
+against filteredTensor(signal=), through a 4096-tap response against convolvedTensor(signal=) and into a 1024-point, 80-band mel
+spectrogram against spectrogramTensor(signal=), and the single-row 8192-sample push a one-stream caller pays, per kind; then, --long, 64
+rows through a 65536-tap response, where a push copies 65535 float32 of history per row.  Two figures per call: `queued`, device events around REPS calls issued back to back, per call --
 what the kernels and the staging copy take once the host runs ahead --, and `alone`, a host clock around one call and a synchronise.
 Prints one JSON object; --out writes it to a file as well.  Needs a GPU."""
 import argparse
@@ -23,7 +25,7 @@ TELEPHONE = np.array([
 REPS, ROUNDS, SAMPLES = 20, 5, 8192
 
 
-def measure(calls, dev):
+def measure(calls, dev, reps=None):
     """calls: name -> function.  ROUNDS rounds, the functions alternating within a round: -> name -> (queued ms per call: the median and the
     range over the rounds, alone ms per call: the same)."""
     import torch
@@ -36,11 +38,11 @@ def measure(calls, dev):
         for name, fn in calls.items():
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            for _ in range(REPS):
+            for _ in range(reps or REPS):
                 fn()
             b.record()
             torch.cuda.synchronize(dev)
-            queued[name].append(a.elapsed_time(b) / REPS)
+            queued[name].append(a.elapsed_time(b) / (reps or REPS))
             t = time.perf_counter()
             fn()
             torch.cuda.synchronize(dev)
@@ -49,12 +51,21 @@ def measure(calls, dev):
     return {k: dict(queued_ms=spread(queued[k]), alone_ms=spread(alone[k])) for k in calls}
 
 
+def room_response(taps):
+    rng = np.random.default_rng(taps)
+    return (rng.normal(0.0, 1.0, taps) * np.exp(-np.arange(taps) / (0.2 * taps))).astype(np.float32)
+
+
 def main():
     import torch
     import nvspeechplayer_amd as eng
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
+    ap.add_argument("--families", default="resample,filter,adpcm,convolution,spectrogram", help="comma-separated: which rows to time")
+    ap.add_argument("--long", action="store_true", help="also 64 rows through a 65536-tap response")
+    ap.add_argument("--exports-only", action="store_true", help="the whole-row exports alone: an A/B of two builds of the library (SPEECHPLAYER_LIB)")
     args = ap.parse_args()
+    families = args.families.split(",")
     bp = eng.BatchPlayer(22050)
     dev = bp.device
     rng = np.random.default_rng(1)
@@ -62,13 +73,30 @@ def main():
     for rows in (1024, 1):
         x = torch.from_numpy(rng.uniform(-1.0, 1.0, (rows, SAMPLES)).astype(np.float32)).to("cuda:%d" % dev)
         signal = (x, np.full(rows, SAMPLES, np.int64))
+        room, mel = room_response(4096), eng.melFilterbank(22050, 1024, 80)
         res, fil, cod = bp.resampleStage(rows, 22050, 16000), bp.filterStage(rows, TELEPHONE), bp.codeStage(rows, "adpcm")
-        calls = {"resample stage push": lambda: res.push(signal), "resampledTensor(signal=)": lambda: bp.resampledTensor(16000, signal=signal),
-                 "filter stage push": lambda: fil.push(signal), "filteredTensor(signal=)": lambda: bp.filteredTensor(TELEPHONE, signal=signal),
-                 "adpcm stage push": lambda: cod.push(signal), "codedTensor(adpcm, signal=)": lambda: bp.codedTensor("adpcm", signal=signal)}
+        con, spe = bp.convolveStage(rows, room, tail=False), bp.spectrogramStage(rows, 1024, 256, bank=mel, log="db")
+        every = {"resample": {"resample stage push": lambda: res.push(signal), "resampledTensor(signal=)": lambda: bp.resampledTensor(16000, signal=signal)},
+                 "filter": {"filter stage push": lambda: fil.push(signal), "filteredTensor(signal=)": lambda: bp.filteredTensor(TELEPHONE, signal=signal)},
+                 "adpcm": {"adpcm stage push": lambda: cod.push(signal), "codedTensor(adpcm, signal=)": lambda: bp.codedTensor("adpcm", signal=signal)},
+                 "convolution": {"convolution stage push, 4096 taps": lambda: con.push(signal),
+                                 "convolvedTensor(4096 taps, tail=False, signal=)": lambda: bp.convolvedTensor(room, tail=False, signal=signal)},
+                 "spectrogram": {"spectrogram stage push, 1024 / 256, 80 mel, db": lambda: spe.push(signal),
+                                 "spectrogramTensor(1024 / 256, 80 mel, db, signal=)": lambda: bp.spectrogramTensor(1024, 256, bank=mel, log="db", signal=signal)}}
+        calls = {name: fn for family in families for name, fn in every[family].items() if not (args.exports_only and "stage push" in name)}
         result["%d rows x %d float32" % (rows, SAMPLES)] = measure(calls, dev)
-        for s in (res, fil, cod):
+        for s in (res, fil, cod, con, spe):
             s.close()
+    if args.long:      # the history copy at its largest: 65535 float32 per row and push beside 8192 x 65536 taps of arithmetic per row
+        rows = 64
+        x = torch.from_numpy(rng.uniform(-1.0, 1.0, (rows, SAMPLES)).astype(np.float32)).to("cuda:%d" % dev)
+        signal = (x, np.full(rows, SAMPLES, np.int64))
+        room = room_response(65536)
+        con = bp.convolveStage(rows, room, tail=False)
+        calls = {"convolution stage push, 65536 taps": lambda: con.push(signal),
+                 "convolvedTensor(65536 taps, tail=False, signal=)": lambda: bp.convolvedTensor(room, tail=False, signal=signal)}
+        result["%d rows x %d float32, 65536 taps" % (rows, SAMPLES)] = measure(calls, dev, reps=4)
+        con.close()
     bp.close()
     text = json.dumps(result, indent=1)
     print(text)
