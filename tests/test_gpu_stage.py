@@ -2,7 +2,8 @@
 speechPlayer_stage_push; BatchPlayer.resampleStage / filterStage / codeStage, SignalStage, SignalChain; csrc/klatt_stage.h): for every row,
 the outputs of its pushes up to the one that ends it, concatenated, against the host's whole-signal statement -- signalResample,
 signalFilter, signalCode -- on the concatenation of its chunks, bit for bit.  Chunks are int16 or float32, padded or packed, with poison
-around and between the rows; outputs float32 or int16, padded or packed, between guards.  Needs a GPU."""
+around and between the rows; outputs float32 or int16, padded or packed, between guards.  Every stream here is short: streams past 2^31
+and 2^32 samples, and chunks and outputs past those elements, are tests/test_gpu_stage_far.py.  Needs a GPU."""
 import numpy as np
 import pytest
 

@@ -3,7 +3,8 @@ speechPlayer_batch_stageConvolve / stageSpectrogram, speechPlayer_stage_push; Ba
 SignalChain; csrc/klatt_stage_window.h): for every row, the outputs of its pushes up to the one that ends it, concatenated, against the
 host's whole-signal statement -- signalConvolve, signalSpectrogram -- on the concatenation of its chunks: bit for bit for the convolution
 and for the spectrogram's linear values, at tests/test_gpu_spectrogram.py's bar through the logarithm.  Chunks are int16 or float32, padded
-or packed, with poison around and between the rows; outputs padded or packed, between guards.  Needs a GPU."""
+or packed, with poison around and between the rows; outputs padded or packed, between guards.  Every stream here is short: streams past
+2^31 and 2^32 samples, and chunks and outputs past those elements, are tests/test_gpu_stage_far.py.  Needs a GPU."""
 import numpy as np
 import pytest
 
