@@ -714,15 +714,15 @@ struct Stage {
     std::vector<long long> N, M;               // [nRows] consumed and emitted since the row's start
     ResPlan res;                               // resample
     DeviceBuffer<float> dTable;                // [taps][up]
-    DeviceBuffer<float> dHist[2];              // [nRows][2 Z - 1] each; dHist[cur] is what the next push reads
+    DeviceBuffer<float> dHist[2];              // resample, convolution, spectrogram: the rows' histories, row r's from histAt[r] of either; dHist[cur] is what the next push reads
     int cur = 0;
+    std::vector<long long> histAt;             // [nRows + 1] (all 0 where the kind keeps none)
+    long long mostHistory = 0;                 // the longest row's
     FilterPlan fil;                            // filter
     std::vector<long long> secAt, secN;        // [nRows] the row's filter: its first section and its sections
     DeviceBuffer<float> dFilterState;          // [nRows][kStageFilterState]
     int codec = 0;                             // code
     DeviceBuffer<int> dCodeState;              // [nRows][2]
-    StageWindowGeometry win;                   // convolution, spectrogram (klatt_stage_window.h): their histories are dHist, row r's from histAt[r]
-    std::vector<long long> histAt;             // [nRows + 1]
     std::vector<long long> irAt;               // convolution: [nRows] the row's response, its first tap (its taps: the row's history + 1)
     DeviceBuffer<float> dTaps;                 // the responses back to back
     SpecPlan spec;                             // spectrogram: the plan without its arrays, which the device holds
@@ -5458,8 +5458,8 @@ long long speechPlayer_batch_exportCodedOf(speechPlayer_batch_t batch, const spe
     return coded_export(what, batch, true, signal, rows, nRows, codec, decodedOut, format, codesOut, rowStride, stream);
 }
 
-// ---- signal stages (klatt_stage.h): the resampler, the filter and the codecs chunk by chunk ---------------------------------------------------
-static_assert(sizeof(StageResRow) % 8 == 0 && sizeof(StageLaneRow) % 8 == 0 && sizeof(StageWinRow) % 8 == 0, "rows are arrays of 8-byte words");
+// ---- signal stages (klatt_stage.h, klatt_stage_window.h): the resampler, the filter, the codecs, the convolution and the spectrogram chunk by chunk ----
+static_assert(sizeof(StageHistRow) % 8 == 0 && sizeof(StageResRow) % 8 == 0 && sizeof(StageLaneRow) % 8 == 0, "rows are arrays of 8-byte words");
 
 // Host only, touches no device: the outputs a resampler stage has emitted after `consumed` samples of a row, open or ended
 long long speechPlayer_resampleEmitted(long long consumed, int srcRate, int outRate, int zeros, double rolloff, int ended)
@@ -5487,7 +5487,7 @@ static speechPlayer_stage_t stage_create(const char* what, speechPlayer_batch_t 
     try {
         s = new Stage;
         s->nRows = nRows;
-        s->N.assign((size_t)nRows, 0); s->M.assign((size_t)nRows, 0);
+        s->N.assign((size_t)nRows, 0); s->M.assign((size_t)nRows, 0); s->histAt.assign((size_t)nRows + 1, 0);
         const auto made = [&]() -> int {
             if (fill(b, s)) return -1;
             HIP_TRY(hipSetDevice(b->device));
@@ -5517,6 +5517,26 @@ static int stage_zeros(Batch* b, DeviceBuffer<T>& buf, size_t n)
     HIP_TRY(hipMemsetAsync(buf.ptr, 0, n * sizeof(T), b->stream));
     return 0;
 }
+// The histories of a stage whose kind keeps one, row r's H(r) float32 from histAt[r] of either buffer: refused beyond `cap` samples in all
+// (kStageMaxHistory, the convolution's and the spectrogram's) before anything is allocated
+constexpr long long kStageNoCap = 0x7FFFFFFFFFFFFFFFll;      // the resampler's cap: its histories are 2^20 rows of 1023 samples at the most and are not refused
+extern "C++" template <class Len>
+static int stage_histories(const char* what, Batch* b, Stage* s, Len H, long long cap)
+{
+    for (long long i = 0; i < s->nRows; ++i) {
+        const long long h = H(i);
+        if (h > cap - s->histAt[(size_t)i]) {
+            int bits = 0;      // (a cap is a power of two)
+            while ((1ll << bits) < cap) ++bits;
+            set_error("%s: the rows' histories take more than 2^%d samples in all (row %lld keeps %lld)", what, bits, i, h);
+            return -1;
+        }
+        s->histAt[(size_t)i + 1] = s->histAt[(size_t)i] + h;
+        s->mostHistory = std::max(s->mostHistory, h);
+    }
+    const size_t n = (size_t)s->histAt[(size_t)s->nRows];
+    return n == 0 ? 0 : stage_zeros(b, s->dHist[0], n) || stage_zeros(b, s->dHist[1], n) ? -1 : 0;
+}
 
 speechPlayer_stage_t speechPlayer_batch_stageResample(speechPlayer_batch_t batch, long long nRows, int srcRate, int outRate, int zeros, double rolloff, int window, double beta)
 {
@@ -5526,14 +5546,15 @@ speechPlayer_stage_t speechPlayer_batch_stageResample(speechPlayer_batch_t batch
         if (!res_plan(s->res, srcRate, outRate, zeros, rolloff, window, beta, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
         ResPlan& P = s->res;
         s->g.kind = kStageResample; s->g.up = P.up; s->g.down = P.down; s->g.Z = P.identity ? 0 : P.Z;
-        if (P.identity) return 0;      // equal rates: no table, no state
+        const long long H = stage_history(s->g.Z);
+        if (stage_histories(what, b, s, [&](long long) { return H; }, kStageNoCap)) return -1;
+        if (P.identity) return 0;      // equal rates: no table, and histories of no samples
         res_transpose(P);
         HIP_TRY(hipSetDevice(b->device));
         if (s->dTable.reserve(P.hT.size())) return -1;
         HIP_TRY(hipMemcpy(s->dTable.ptr, P.hT.data(), P.hT.size() * sizeof(float), hipMemcpyHostToDevice));
         std::vector<float>().swap(P.table); std::vector<float>().swap(P.hT);      // (the device holds what the pushes read)
-        const size_t n = (size_t)s->nRows * (size_t)stage_history(P.Z);
-        return stage_zeros(b, s->dHist[0], n) || stage_zeros(b, s->dHist[1], n) ? -1 : 0;
+        return 0;
     });
 }
 
@@ -5566,22 +5587,6 @@ speechPlayer_stage_t speechPlayer_batch_stageCode(speechPlayer_batch_t batch, lo
     });
 }
 
-// The histories of a window stage (klatt_stage_window.h), row r's H(r) float32 from histAt[r] of either buffer: refused beyond
-// kStageMaxHistory before anything is allocated
-extern "C++" template <class Len>
-static int stage_window_histories(const char* what, Batch* b, Stage* s, Len H)
-{
-    s->histAt.assign((size_t)s->nRows + 1, 0);
-    for (long long i = 0; i < s->nRows; ++i) {
-        s->histAt[(size_t)i + 1] = s->histAt[(size_t)i] + H(i);
-        if (s->histAt[(size_t)i + 1] > kStageMaxHistory) {
-            set_error("%s: the rows' histories take more than 2^27 samples in all (row %lld keeps %lld)", what, i, (long long)H(i));
-            return -1;
-        }
-    }
-    const size_t n = (size_t)s->histAt[(size_t)s->nRows];
-    return n == 0 ? 0 : stage_zeros(b, s->dHist[0], n) || stage_zeros(b, s->dHist[1], n) ? -1 : 0;
-}
 extern "C++" template <class T>
 static int stage_upload(Batch* b, DeviceBuffer<T>& buf, const std::vector<T>& v)
 {
@@ -5600,7 +5605,7 @@ speechPlayer_stage_t speechPlayer_batch_stageConvolve(speechPlayer_batch_t batch
         ConvPlan P;
         std::string why;
         if (!conv_plan(P, ir, irStart, nIr, tail, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
-        s->g.kind = kStageConvolve; s->win.kind = kStageConvolve; s->win.tail = tail;
+        s->g.kind = kStageConvolve; s->g.tail = tail;
         s->irAt.resize((size_t)s->nRows);
         std::vector<long long> taps((size_t)s->nRows);
         for (long long i = 0; i < s->nRows; ++i) {
@@ -5609,7 +5614,7 @@ speechPlayer_stage_t speechPlayer_batch_stageConvolve(speechPlayer_batch_t batch
             s->irAt[(size_t)i] = P.start[(size_t)j];
             taps[(size_t)i] = P.start[(size_t)j + 1] - P.start[(size_t)j];
         }
-        if (stage_window_histories(what, b, s, [&](long long i) { return (long long)stage_conv_history(taps[(size_t)i]); })) return -1;
+        if (stage_histories(what, b, s, [&](long long i) { return (long long)stage_conv_history(taps[(size_t)i]); }, kStageMaxHistory)) return -1;
         return stage_upload(b, s->dTaps, P.taps);
     });
 }
@@ -5632,9 +5637,9 @@ speechPlayer_stage_t speechPlayer_batch_stageSpectrogram(speechPlayer_batch_t ba
         SpecPlan& P = s->spec;
         std::string why;
         if (!spec_plan(P, nFft, window, bank, nBands, power, logScale, floor, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
-        s->g.kind = kStageSpectrogram; s->win.kind = kStageSpectrogram; s->win.frames = stage_spec_frames(nFft, hop, phase);
-        const long long H = stage_frame_history(s->win.frames);
-        if (stage_window_histories(what, b, s, [&](long long) { return H; })) return -1;
+        s->g.kind = kStageSpectrogram; s->g.frames = stage_spec_frames(nFft, hop, phase);
+        const long long H = stage_frame_history(s->g.frames);
+        if (stage_histories(what, b, s, [&](long long) { return H; }, kStageMaxHistory)) return -1;
         if (stage_upload(b, s->dWindow, P.window) || stage_upload(b, s->dTw, P.tw) || stage_upload(b, s->dWeights, P.weights) || stage_upload(b, s->dRange, P.range)) return -1;
         std::vector<float>().swap(P.window); std::vector<SpecCx>().swap(P.tw); std::vector<float>().swap(P.weights); std::vector<int>().swap(P.range);      // (the device holds what the pushes read)
         return 0;
@@ -5651,8 +5656,6 @@ long long speechPlayer_spectrogramEmitted(long long consumed, int nFft, long lon
     if (stage_step_request(what, hop, phase)) return -1;
     return stage_frames_emitted(stage_spec_frames(nFft, hop, phase), consumed, ended != 0);
 }
-
-static bool stage_window(const Stage* s) { return s->g.kind == kStageConvolve || s->g.kind == kStageSpectrogram; }
 
 // The stage a handle names, or null with the message set: a handle that was freed -- alone or with its batch -- names none
 static Stage* stage_of(const char* what, speechPlayer_stage_t stage)
@@ -5672,9 +5675,7 @@ static int stage_selection(const char* what, const Stage* s, Len len, const unsi
     for (long long i = 0; i < s->nRows; ++i) {
         const long long c = len(i);
         long long out;
-        const bool fits = stage_window(s) ? stage_window_row_plan(s->win, s->histAt[(size_t)i + 1] - s->histAt[(size_t)i] + 1, s->N[(size_t)i], s->M[(size_t)i], c, end && end[i], out)
-                                          : stage_row_plan(s->g, s->N[(size_t)i], s->M[(size_t)i], c, end && end[i], out);
-        if (!fits) {
+        if (!stage_row_plan(s->g, s->histAt[(size_t)i + 1] - s->histAt[(size_t)i], s->N[(size_t)i], s->M[(size_t)i], c, end && end[i], out)) {
             set_error("%s: row %lld has consumed %lld samples and would take %lld more (0 or more, at most 2^44 in all)", what, i, s->N[(size_t)i], c);
             return -1;
         }
@@ -5737,49 +5738,84 @@ static void stage_lane_rows(const Stage* s, const ExportInput& in, const unsigne
     }
     filter_pack(rows, packed, groups);
 }
+// The rows of a push that carries no state, for the whole-row kernels: the resampler's at equal rates, the G.711 laws'
+static std::vector<ResRow> stage_plain_rows(const Stage* s, const ExportInput& in, const ExportSelection& sel, long long rowStride)
+{
+    std::vector<ResRow> rows((size_t)s->nRows);
+    long long before = 0;
+    for (long long i = 0; i < s->nRows; ++i) {
+        rows[(size_t)i] = ResRow{in.at(i), in.len(i), sel.counts[(size_t)i], tile_row_first(i, rowStride, before)};
+        before += sel.counts[(size_t)i];
+    }
+    return rows;
+}
+// The rows of a push onto a stage whose rows carry their history's place (the convolution, the spectrogram)
+static std::vector<StageHistRow> stage_history_rows(const Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long rowStride)
+{
+    std::vector<StageHistRow> rows((size_t)s->nRows);
+    long long before = 0;
+    for (long long i = 0; i < s->nRows; ++i) {
+        rows[(size_t)i] = StageHistRow{in.at(i), in.len(i), s->N[(size_t)i], s->M[(size_t)i], sel.counts[(size_t)i], tile_row_first(i, rowStride, before), end && end[i],
+                                       s->histAt[(size_t)i], s->histAt[(size_t)i + 1] - s->histAt[(size_t)i], s->g.kind == kStageConvolve ? s->irAt[(size_t)i] : 0};
+        before += sel.counts[(size_t)i];
+    }
+    return rows;
+}
+// The next history of every row, into the buffer nothing of this push reads, behind the push's kernel; then the buffers change places
+static int stage_history_finish(Stage* s, StagePass& pass, const ExportInput& in, const StageHistRow* dRows)
+{
+    if (s->mostHistory > 0) {
+        const dim3 hgrid((unsigned)std::min<long long>((s->mostHistory + 255) / 256, 64), (unsigned)std::min<long long>(s->nRows, 16ll * s->b->cus));
+        hipLaunchKernelGGL(in.format() ? klatt_stage_history_rows<float> : klatt_stage_history_rows<int16_t>, hgrid, dim3(256), 0, pass.stage.st, in.data, dRows, s->nRows,
+                           s->dHist[s->cur].ptr, s->dHist[s->cur ^ 1].ptr);
+        HIP_TRY(hipGetLastError());
+    }
+    if (pass.finish()) return -1;
+    if (s->mostHistory > 0) s->cur ^= 1;
+    return 0;
+}
 
 static int stage_push_resample(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long elements, void* deviceOut, int format,
                                long long rowStride, hipStream_t st)
 {
-    Batch* b = s->b;
-    const bool identity = s->g.Z == 0;
-    if (identity && elements == 0) return 0;
-    std::vector<StageResRow> rows((size_t)s->nRows);
-    std::vector<ResRow> plain;
-    long long before = 0;
-    for (long long i = 0; i < s->nRows; ++i) {
-        rows[(size_t)i] = StageResRow{in.at(i), in.len(i), s->N[(size_t)i], s->M[(size_t)i], sel.counts[(size_t)i], tile_row_first(i, rowStride, before), end && end[i]};
-        if (identity) plain.push_back(ResRow{in.at(i), in.len(i), sel.counts[(size_t)i], rows[(size_t)i].dst});
-        before += sel.counts[(size_t)i];
-    }
     std::vector<long long> words;
     const TileTable tiles = tile_row_table(sel.counts.data(), sel.n, kResampleTile, rowStride, kTimelineChunkLog2, words);
     StageBlock block;
-    const int rowsAt = identity ? block.add(plain) : block.add(rows), wordsAt = block.add(words);
+    if (s->g.Z == 0) {      // equal rates: no state, the copy kernel of the whole-row export
+        if (elements == 0) return 0;
+        const std::vector<ResRow> rows = stage_plain_rows(s, in, sel, rowStride);
+        const int rowsAt = block.add(rows), wordsAt = block.add(words);
+        StagePass pass(s, st, block);
+        if (pass.begin()) return -1;
+        return launch_signal_copy(pass.stage, in, format, pass.stage.device<ResRow>(rowsAt), tile_out(pass.stage, wordsAt, tiles, rowStride, deviceOut)) || pass.finish() ? -1 : 0;
+    }
+    // The resampler's own 56-byte rows (klatt_stage.h, StageResRow): its histories' places follow from the row's number
+    std::vector<StageResRow> rows((size_t)s->nRows);
+    long long before = 0;
+    for (long long i = 0; i < s->nRows; ++i) {
+        rows[(size_t)i] = StageResRow{in.at(i), in.len(i), s->N[(size_t)i], s->M[(size_t)i], sel.counts[(size_t)i], tile_row_first(i, rowStride, before), end && end[i]};
+        before += sel.counts[(size_t)i];
+    }
+    const int rowsAt = block.add(rows), wordsAt = block.add(words);
     StagePass pass(s, st, block);
     if (pass.begin()) return -1;
-    const unsigned grid = (unsigned)std::min<long long>(tiles.nTiles, 8ll * b->cus);
-    if (identity)      // equal rates: the copy kernel of the whole-row export
-        return launch_signal_copy(pass.stage, in, format, pass.stage.device<ResRow>(rowsAt), tile_out(pass.stage, wordsAt, tiles, rowStride, deviceOut)) || pass.finish() ? -1 : 0;
     const int H = stage_history(s->g.Z);
-    const float* from = s->dHist[s->cur].ptr;
-    float* to = s->dHist[s->cur ^ 1].ptr;
     if (tiles.nTiles > 0) {
         StageResArgs A;
         A.in = in.data; A.rows = pass.stage.device<StageResRow>(rowsAt);
         A.tile = tile_out(pass.stage, wordsAt, tiles, rowStride, deviceOut);
-        A.hT = s->dTable.ptr; A.hist = from;
+        A.hT = s->dTable.ptr; A.hist = s->dHist[s->cur].ptr;
         A.up = s->g.up; A.down = s->g.down; A.Z = s->g.Z; A.span = res_span(s->res);
         void (*const kernels[2][2])(StageResArgs) = {{klatt_stage_resample<false, int16_t>, klatt_stage_resample<true, int16_t>},
                                                      {klatt_stage_resample<false, float>, klatt_stage_resample<true, float>}};
+        const unsigned grid = (unsigned)std::min<long long>(tiles.nTiles, 8ll * s->b->cus);
         hipLaunchKernelGGL(kernels[in.format()][format], dim3(grid), dim3(256), 0, st, A);
         HIP_TRY(hipGetLastError());
     }
     // the next history, into the buffer nothing of this push reads
-    const long long cells = s->nRows * H;
-    const unsigned hgrid = (unsigned)std::min<long long>((cells + 255) / 256, 4ll * b->cus);
+    const unsigned hgrid = (unsigned)std::min<long long>((s->nRows * H + 255) / 256, 4ll * s->b->cus);
     hipLaunchKernelGGL(in.format() ? klatt_stage_history<float> : klatt_stage_history<int16_t>, dim3(hgrid), dim3(256), 0, st, in.data,
-                       pass.stage.device<StageResRow>(rowsAt), s->nRows, H, from, to);
+                       pass.stage.device<StageResRow>(rowsAt), s->nRows, H, s->dHist[s->cur].ptr, s->dHist[s->cur ^ 1].ptr);
     HIP_TRY(hipGetLastError());
     if (pass.finish()) return -1;
     s->cur ^= 1;
@@ -5808,12 +5844,7 @@ static int stage_push_code(Stage* s, const ExportInput& in, const unsigned char*
 {
     if (s->codec != kCodecAdpcm) {      // no state: the tile kernel of the whole-row export
         if (elements == 0) return 0;
-        std::vector<ResRow> rows((size_t)s->nRows);
-        long long before = 0;
-        for (long long i = 0; i < s->nRows; ++i) {
-            rows[(size_t)i] = ResRow{in.at(i), in.len(i), sel.counts[(size_t)i], tile_row_first(i, rowStride, before)};
-            before += sel.counts[(size_t)i];
-        }
+        const std::vector<ResRow> rows = stage_plain_rows(s, in, sel, rowStride);
         std::vector<long long> words;
         const TileTable tiles = tile_row_table(sel.counts.data(), sel.n, kCodeTile, rowStride, kTimelineChunkLog2, words);
         StageBlock block;
@@ -5842,43 +5873,10 @@ static int stage_push_code(Stage* s, const ExportInput& in, const unsigned char*
     return launch_adpcm(pass.stage, in.format(), outputs, format, A) || pass.finish() ? -1 : 0;
 }
 
-// The rows of a window stage's push (klatt_stage_window.h)
-static std::vector<StageWinRow> stage_window_rows(const Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long rowStride)
-{
-    std::vector<StageWinRow> rows((size_t)s->nRows);
-    long long before = 0;
-    for (long long i = 0; i < s->nRows; ++i) {
-        rows[(size_t)i] = StageWinRow{in.at(i), in.len(i), s->N[(size_t)i], s->M[(size_t)i], sel.counts[(size_t)i], tile_row_first(i, rowStride, before), end && end[i],
-                                      s->histAt[(size_t)i], s->histAt[(size_t)i + 1] - s->histAt[(size_t)i], s->g.kind == kStageConvolve ? s->irAt[(size_t)i] : 0};
-        before += sel.counts[(size_t)i];
-    }
-    return rows;
-}
-// The next history of every row of a window stage, into the buffer nothing of this push reads, behind the push's kernel; then the buffers
-// change places
-static int stage_window_finish(Stage* s, StagePass& pass, const ExportInput& in, const StageWinRow* dRows, long long mostHistory)
-{
-    if (mostHistory > 0) {
-        const dim3 hgrid((unsigned)std::min<long long>((mostHistory + 255) / 256, 64), (unsigned)std::min<long long>(s->nRows, 16ll * s->b->cus));
-        hipLaunchKernelGGL(in.format() ? klatt_stage_history_rows<float> : klatt_stage_history_rows<int16_t>, hgrid, dim3(256), 0, pass.stage.st, in.data, dRows, s->nRows,
-                           s->dHist[s->cur].ptr, s->dHist[s->cur ^ 1].ptr);
-        HIP_TRY(hipGetLastError());
-    }
-    if (pass.finish()) return -1;
-    if (mostHistory > 0) s->cur ^= 1;
-    return 0;
-}
-static long long stage_most_history(const Stage* s)
-{
-    long long most = 0;
-    for (long long i = 0; i < s->nRows; ++i) most = std::max(most, s->histAt[(size_t)i + 1] - s->histAt[(size_t)i]);
-    return most;
-}
-
 static int stage_push_convolve(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, void* deviceOut, int format, long long rowStride,
                                hipStream_t st)
 {
-    const std::vector<StageWinRow> rows = stage_window_rows(s, in, end, sel, rowStride);
+    const std::vector<StageHistRow> rows = stage_history_rows(s, in, end, sel, rowStride);
     std::vector<long long> words;
     const TileTable tiles = tile_row_table(sel.counts.data(), sel.n, kConvolveTile, rowStride, kTimelineChunkLog2, words);
     StageBlock block;
@@ -5887,20 +5885,20 @@ static int stage_push_convolve(Stage* s, const ExportInput& in, const unsigned c
     if (pass.begin()) return -1;
     if (tiles.nTiles > 0) {
         StageConvArgs A;
-        A.in = in.data; A.rows = pass.stage.device<StageWinRow>(rowsAt);
+        A.in = in.data; A.rows = pass.stage.device<StageHistRow>(rowsAt);
         A.tile = tile_out(pass.stage, wordsAt, tiles, rowStride, deviceOut);
         A.taps = s->dTaps.ptr; A.hist = s->dHist[s->cur].ptr;
         void (*const kernels[2][2])(StageConvArgs) = {{klatt_stage_convolve<false, int16_t>, klatt_stage_convolve<true, int16_t>},
                                                       {klatt_stage_convolve<false, float>, klatt_stage_convolve<true, float>}};
         if (queue_tiles(pass.stage, kernels[in.format()][0], kernels[in.format()][1], format, kConvolveGroupsPerCu, A)) return -1;
     }
-    return stage_window_finish(s, pass, in, pass.stage.device<StageWinRow>(rowsAt), stage_most_history(s));
+    return stage_history_finish(s, pass, in, pass.stage.device<StageHistRow>(rowsAt));
 }
 
 static int stage_push_spectrogram(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long elements, void* deviceOut, int format,
                                   long long rowStride, hipStream_t st)
 {
-    const std::vector<StageWinRow> rows = stage_window_rows(s, in, end, sel, rowStride);
+    const std::vector<StageHistRow> rows = stage_history_rows(s, in, end, sel, rowStride);
     const bool packed = rowStride == 0;
     std::vector<long long> words;
     const RowTable table = packed ? packed_row_table(sel.counts.data(), 0, sel.n, kTimelineChunkLog2, words) : RowTable{0, 0};
@@ -5913,13 +5911,13 @@ static int stage_push_spectrogram(Stage* s, const ExportInput& in, const unsigne
     if (pass.begin([&] { return ensure_lds_limit(reinterpret_cast<const void*>(kernel), kSpecLdsBudget); })) return -1;
     if (elements > 0) {
         StageSpecArgs A;
-        A.s = spec_args(pass.stage, s->spec, packed ? &table : nullptr, wordsAt, rowStride, elements, s->win.frames.hop, s->win.frames.phase, deviceOut);
+        A.s = spec_args(pass.stage, s->spec, packed ? &table : nullptr, wordsAt, rowStride, elements, s->g.frames.hop, s->g.frames.phase, deviceOut);
         A.s.in = in.data; A.s.rows = nullptr;
         A.s.window = s->dWindow.ptr; A.s.tw = s->dTw.ptr; A.s.weights = s->dWeights.ptr; A.s.range = s->dRange.ptr;
-        A.rows = pass.stage.device<StageWinRow>(rowsAt); A.hist = s->dHist[s->cur].ptr;
+        A.rows = pass.stage.device<StageHistRow>(rowsAt); A.hist = s->dHist[s->cur].ptr;
         if (queue_spectrogram(pass.stage, kernel, A, A.s)) return -1;
     }
-    return stage_window_finish(s, pass, in, pass.stage.device<StageWinRow>(rowsAt), stage_most_history(s));
+    return stage_history_finish(s, pass, in, pass.stage.device<StageHistRow>(rowsAt));
 }
 
 long long speechPlayer_stage_push(speechPlayer_stage_t stage, const speechPlayer_signal_t* chunk, const unsigned char* end, void* deviceOut, int format,
@@ -5986,18 +5984,17 @@ int speechPlayer_stage_reset(speechPlayer_stage_t stage, const unsigned char* ro
     Stage* s = stage_of(what, stage);
     if (!s) return -1;
     try {
-        uint32_t* state = nullptr;
+        uint32_t* state = nullptr;      // the lane state of a filter or an ADPCM stage
         int perRow = 0;
-        if (s->g.kind == kStageResample && s->g.Z > 0) { state = reinterpret_cast<uint32_t*>(s->dHist[s->cur].ptr); perRow = stage_history(s->g.Z); }
-        else if (s->g.kind == kStageFilter) { state = reinterpret_cast<uint32_t*>(s->dFilterState.ptr); perRow = kStageFilterState; }
+        if (s->g.kind == kStageFilter) { state = reinterpret_cast<uint32_t*>(s->dFilterState.ptr); perRow = kStageFilterState; }
         else if (s->g.kind == kStageCode && s->codec == kCodecAdpcm) { state = reinterpret_cast<uint32_t*>(s->dCodeState.ptr); perRow = 2; }
-        if (stage_window(s) && s->histAt[(size_t)s->nRows] > 0) {      // a history per row, each from its own first element
+        if (stage_keeps_history(s->g.kind) && s->mostHistory > 0) {      // a history per row, each from its own first element
             HIP_TRY(hipSetDevice(s->b->device));
             StageBlock block;
             const int rowsAt = rows ? block.add(rows, (size_t)s->nRows) : -1, atAt = block.add(s->histAt);
             StagePass pass(s, static_cast<hipStream_t>(stream), block);
             if (pass.begin()) return -1;
-            const dim3 grid((unsigned)std::min<long long>((stage_most_history(s) + 255) / 256, 64), (unsigned)std::min<long long>(s->nRows, 16ll * s->b->cus));
+            const dim3 grid((unsigned)std::min<long long>((s->mostHistory + 255) / 256, 64), (unsigned)std::min<long long>(s->nRows, 16ll * s->b->cus));
             hipLaunchKernelGGL(klatt_stage_clear_rows, grid, dim3(256), 0, pass.stage.st, rows ? pass.stage.device<unsigned char>(rowsAt) : nullptr,
                                pass.stage.device<long long>(atAt), s->nRows, s->dHist[s->cur].ptr);
             HIP_TRY(hipGetLastError());

@@ -1,12 +1,17 @@
 // klatt_stage.h -- signal stages: the resampler, the biquad filter and the codecs fed chunk by chunk, with the state that survives a call
-// (speechPlayer_batch_stageResample / stageFilter / stageCode, speechPlayer_stage_push; speechPlayer_resampleEmitted).
+// (speechPlayer_batch_stageResample / stageFilter / stageCode, speechPlayer_stage_push; speechPlayer_resampleEmitted), and what all kinds share.
 //
 // The definition is in include/speechPlayer_batch.h ("Signal stages").  Nothing per sample is restated here: the resampler's res_locate /
 // res_taps / res_value, the filter's filter_section / filter_finish, the codecs' adpcm_encode and G.711 laws and the reader's tile_x are the
-// functions of klatt_resample.h, klatt_filter.h, klatt_codec.h and klatt_tiles.h, called.  What this header adds is the bookkeeping, compiled
-// for the host and for the device from one source (KLATT_RES_HD) and driven by the kernels, by the entry points and by the host model of
-// tests/native/check_stage.cpp alike, and the three kernels that keep state.
+// functions of klatt_resample.h, klatt_filter.h, klatt_codec.h and klatt_tiles.h, called.  What this header adds is the bookkeeping of ALL
+// five kinds, compiled for the host and for the device from one source (KLATT_RES_HD) and driven by the kernels, by the entry points and by
+// the host models of tests/native/check_stage.cpp and check_stage_window.cpp alike, and the kernels of the resampler, the filter and ADPCM.
 //
+//   Who owns what   here: the kind constants, StageGeometry and stage_row_plan (what a push emits, every kind); the step grid (StageFrames);
+//                   the virtual row (stage_where, stage_sample, stage_history_from_chunk); the histories' layout with StageHistRow,
+//                   klatt_stage_history_rows and klatt_stage_clear_rows; the resampler's StageResRow, klatt_stage_resample and
+//                   klatt_stage_history; the filter's and ADPCM's lane state, klatt_stage_filter, klatt_stage_adpcm, klatt_stage_clear.
+//                   klatt_stage_window.h: the convolution's block arithmetic, stage_read_lane / stage_read, the two kinds' kernels.
 //   The counts      A row has consumed N samples and emitted M outputs since its start (its creation, its last end or its last reset).  A
 //                   push of c samples makes N' = N + c.  The resampler, open, emits the outputs m whose taps n0(m) - Z + 1 .. n0(m) + Z,
 //                   n0(m) = floor(m down / up), all lie at or before sample N' - 1:  n0(m) + Z <= N' - 1  <=>  m down < (N' - Z) up  <=>
@@ -16,12 +21,26 @@
 //   The lemma       2 Z - 1 samples of history suffice.  Output M, the first not yet emitted with N consumed, has n0(M) + Z > N - 1, so
 //                   its oldest tap n0(M) - Z + 1 >= N - 2 Z + 1; n0 does not decrease with m, so no later output reaches further back.  The
 //                   samples N - 2 Z + 1 .. N - 1 are 2 Z - 1 = stage_history(Z) values, float32 as tile_x gave them, +0 before sample 0.
-//   The virtual row [history | chunk | +0]: sample n of the row's stream is element v = n - (N - H) of it, H = 2 Z - 1 (stage_where): below 0
+//   The frames      A frame (before, after) of step j is the samples c_j - before .. c_j + after around its centre c_j = phase + j hop
+//                   (stage_frame_centre).  The spectrogram's frame is (nFft / 2, nFft / 2 - 1); LPC's (floor(nWin / 2), nWin - 1 -
+//                   floor(nWin / 2)) and YIN's fit the same bookkeeping.  Open, the steps emitted after N samples are those whose whole
+//                   frame lies at or before sample N - 1:  c_j + after <= N - 1  <=>  j <= (N - after - 1 - phase) / hop, so
+//                   E_open(N) = 0 where N - after - 1 - phase < 0 and floor((N - after - 1 - phase) / hop) + 1 otherwise.  Ended, the
+//                   statement's count ceil((N - phase) / hop) (0 where N <= phase), the samples past N - 1 being +0 as the statement has
+//                   them.  A push emits E(N', ended) - M (stage_frames_emitted).  N <= 2^44, hop and phase <= 2^45: 64 bits hold it all.
+//                   before + after samples of history suffice, whatever hop and phase are: step M, the first not emitted with N
+//                   consumed, has c_M + after > N - 1, so its oldest sample c_M - before >= N - (before + after); c_j does not decrease
+//                   with j, so no later step reaches further back.  (A hop above the frame's length skips samples that the history holds.)
+//   The virtual row [history | chunk | +0]: sample n of the row's stream is element v = n - (N - H) of it, H the samples of history the
+//                   row keeps -- 2 Z - 1, a convolution row's K_r - 1, a frame's before + after; 0 at equal rates -- (stage_where): below 0
 //                   it is +0 (a sample before the start that the history no longer holds: by the lemma no output of the push needs it),
 //                   below H the history's, below H + c the chunk's, beyond it +0 -- needed by an ended row's last outputs alone.
 //   The window      The next history is the last H elements of [history | chunk]: element j is element c + j of it
 //                   (stage_history_from_chunk), all zeros for an ended row.  It is written to the OTHER of two buffers by a kernel of its own
-//                   (klatt_stage_history), so no workgroup writes what another reads; the next push swaps the buffers.
+//                   (klatt_stage_history_rows; the resampler's klatt_stage_history), so no workgroup writes what another reads; the host
+//                   swaps the buffers once the push is queued.  Row r's history lies at histAt[r] of either buffer.  StageHistRow carries
+//                   that place and the length, since a convolution's rows differ; the resampler's are uniform, r H, and its pushes leave
+//                   them out of the row (StageResRow).  klatt_stage_clear_rows puts +0 into the chosen rows' histories (a reset), all kinds'.
 //   klatt_stage_resample
 //                   resample_rows<KEPT = true> of klatt_resample.h, the one body it shares with klatt_resample: that kernel's tiling --
 //                   kResampleTile outputs a workgroup, spans whose inputs fit kResampleIn floats of LDS, the transposed table, the writer
@@ -38,9 +57,9 @@
 //                   ends in (a wave-uniform test) runs steps that commit the state only while t < the row's own count, so what is stored is
 //                   the state after exactly c samples (c + tail for an ended filter row, which is then stored as +0; val = idx = 0).
 //                   Identity padding sits behind the real sections, so the real sections' states are exact; the padding's are never stored.
-//   Out of scope    The convolution, spectrogram, LPC, pitch and tempo exports chunk by chunk; saving a stage's state to the host;
-//                   NodePlayer; a fused kernel for a chain of stages.  (klatt_stage_window.h puts the convolution and the spectrogram on
-//                   this header's virtual row, with a history length per row.)
+//                   (Their state is uniform, 16 and 2 dwords a row, and updated in place: the flat klatt_stage_clear resets it.)
+//   Out of scope    The LPC, pitch and tempo exports chunk by chunk (a kind is a plan, a line of stage_row_plan and a kernel entry point
+//                   on the history above); saving a stage's state to the host; NodePlayer; a fused kernel for a chain of stages.
 #pragma once
 
 #include "klatt_codec.h"
@@ -48,7 +67,7 @@
 namespace klatt {
 
 constexpr long long kStageMaxRows = 1ll << 20;
-constexpr int kStageResample = 0, kStageFilter = 1, kStageCode = 2;
+constexpr int kStageResample = 0, kStageFilter = 1, kStageCode = 2, kStageConvolve = 3, kStageSpectrogram = 4;
 constexpr int kStageFilterState = 2 * kFilterMaxSections;      // floats of a filter stage's row: s1, s2 of section j at 2 j, 2 j + 1
 
 // ---- the bookkeeping, for the host and the device ---------------------------------------------------------------------------------------
@@ -88,15 +107,34 @@ KLATT_RES_HD bool stage_history_from_chunk(int j, int H, long long c, long long&
     return true;
 }
 
-// What a stage is, as far as the counts go.  Z 0: a resampler at equal rates.
-struct StageGeometry { int kind = 0, up = 1, down = 1, Z = 0; long long tail = 0; };
-// The outputs of a push of c samples, ended or not, onto a row at (N, M); false: c is negative or the row would pass 2^44 samples
-KLATT_RES_HD bool stage_row_plan(const StageGeometry& g, long long N, long long M, long long c, bool ended, long long& out)
+// A step grid with a frame around every centre
+struct StageFrames { long long before = 0, after = 0, hop = 1, phase = 0; };
+KLATT_RES_HD StageFrames stage_spec_frames(int nFft, long long hop, long long phase) { StageFrames f; f.before = nFft / 2; f.after = nFft / 2 - 1; f.hop = hop; f.phase = phase; return f; }
+KLATT_RES_HD int stage_frame_history(const StageFrames& f) { return (int)(f.before + f.after); }
+KLATT_RES_HD long long stage_frame_centre(const StageFrames& f, long long j) { return f.phase + j * f.hop; }
+// Steps emitted once N samples are consumed, open (the whole frame at or before sample N - 1) or ended (the statement's count)
+KLATT_RES_HD long long stage_frames_emitted(const StageFrames& f, long long N, bool ended)
+{
+    if (ended) return N > f.phase ? (N - f.phase + f.hop - 1) / f.hop : 0;
+    const long long a = N - f.after - 1 - f.phase;
+    return a < 0 ? 0 : a / f.hop + 1;
+}
+
+// What a stage is, as far as the counts go.  Z 0: a resampler at equal rates.  tail: the filter's samples, the convolution's 0 or 1.
+// frames: the spectrogram's.  A convolution row's taps come with the row, as its history + 1.
+struct StageGeometry { int kind = 0, up = 1, down = 1, Z = 0; long long tail = 0; StageFrames frames; };
+// The kinds whose rows keep a history of their most recent samples (a resampler's at equal rates has length 0); the others keep lane state
+KLATT_RES_HD bool stage_keeps_history(int kind) { return kind == kStageResample || kind == kStageConvolve || kind == kStageSpectrogram; }
+// The outputs of a push of c samples, ended or not, onto a row at (N, M) that keeps H samples of history (read for the convolution, whose
+// H is K - 1, alone); false: c is negative or the row would pass 2^44 samples
+KLATT_RES_HD bool stage_row_plan(const StageGeometry& g, long long H, long long N, long long M, long long c, bool ended, long long& out)
 {
     out = 0;
     if (c < 0 || c > kResampleMaxLength - N) return false;
     if (g.kind == kStageResample) out = stage_res_emitted(N + c, g.Z, g.up, g.down, ended) - M;
     else if (g.kind == kStageFilter) out = c + (ended ? g.tail : 0);
+    else if (g.kind == kStageConvolve) out = c + (ended && g.tail ? H : 0);
+    else if (g.kind == kStageSpectrogram) out = stage_frames_emitted(g.frames, N + c, ended) - M;
     else out = c;
     return true;
 }
@@ -113,8 +151,45 @@ KLATT_RES_HD void stage_row_advance(long long& N, long long& M, long long c, boo
 #if defined(__HIPCC__)
 namespace klatt {
 
-// A resampler row of a push: first element and samples of its chunk; the samples it has consumed and the outputs it has emitted before;
-// the outputs of this push; their first element in the output; whether the push ends it
+// A row of a push onto a stage that keeps a history: first element and samples of its chunk; the samples it has consumed and the outputs
+// it has emitted before; the outputs of this push; their first element in the output (the spectrogram's are located by its own table);
+// whether the push ends it; its history's first element in either buffer and its length; its response's first tap (a convolution's, of
+// H + 1 taps; 0 otherwise)
+struct StageHistRow { long long src, len, N, M, outLen, dst, ended, hist, H, irAt; };
+
+// The next history of every row, into the buffer this push does not read: the last H of [history | chunk], zeros for an ended row.
+// Workgroups (x, y): the rows y, y + gridDim.y, ..; of a row the elements x 256 + lane, + gridDim.x 256, ..
+template <typename In>
+__global__ void __launch_bounds__(256) klatt_stage_history_rows(const void* in, const StageHistRow* __restrict__ rows, long long nRows, const float* __restrict__ from,
+                                                                float* __restrict__ to)
+{
+    for (long long r = blockIdx.y; r < nRows; r += gridDim.y) {
+        const StageHistRow row = rows[r];
+        const int H = (int)row.H;
+        for (int j = blockIdx.x * 256 + threadIdx.x; j < H; j += gridDim.x * 256) {
+            float v = 0.0f;
+            if (!row.ended) {
+                long long at;
+                if (stage_history_from_chunk(j, H, row.len, at)) v = tile_x(static_cast<const In*>(in)[row.src + at]);
+                else v = from[row.hist + at];
+            }
+            to[row.hist + j] = v;
+        }
+    }
+}
+
+// +0 into the history of the chosen rows (rows null: all): row r's is at[r] .. at[r + 1] - 1
+__global__ void __launch_bounds__(256) klatt_stage_clear_rows(const unsigned char* __restrict__ rows, const long long* __restrict__ at, long long nRows, float* __restrict__ state)
+{
+    for (long long r = blockIdx.y; r < nRows; r += gridDim.y) {
+        if (rows && !rows[r]) continue;
+        const long long a = at[r], b = at[r + 1];
+        for (long long e = a + blockIdx.x * 256 + threadIdx.x; e < b; e += gridDim.x * 256) state[e] = 0.0f;
+    }
+}
+
+// A resampler row of a push: StageHistRow's first seven fields; row r's history is the 2 Z - 1 samples at r (2 Z - 1).  A row table is
+// staged and uploaded at every push: with 80 bytes a row for these 56, 16384 rows x 256 samples took 17 % longer (profiles/stage_one_history.txt)
 struct StageResRow { long long src, len, N, M, outLen, dst, ended; };
 
 struct StageResArgs {
@@ -136,7 +211,7 @@ __global__ void __launch_bounds__(256) klatt_stage_resample(const StageResArgs A
     });
 }
 
-// The next history of every row, into the buffer this push does not read: the last H of [history | chunk], zeros for an ended row
+// klatt_stage_history_rows for the resampler's uniform histories and 56-byte rows: one lane per history element, flat over all rows
 template <typename In>
 __global__ void __launch_bounds__(256) klatt_stage_history(const void* in, const StageResRow* __restrict__ rows, long long nRows, int H,
                                                            const float* __restrict__ from, float* __restrict__ to)
@@ -156,7 +231,7 @@ __global__ void __launch_bounds__(256) klatt_stage_history(const void* in, const
     }
 }
 
-// +0 into the state of the chosen rows (rows null: all): perRow dwords each
+// +0 into the lane state of the chosen rows (rows null: all) of a filter or ADPCM stage: perRow dwords each, uniform and updated in place, so a flat clear suits it
 __global__ void __launch_bounds__(256) klatt_stage_clear(const unsigned char* __restrict__ rows, long long nRows, int perRow, uint32_t* __restrict__ state)
 {
     const long long total = nRows * perRow, stride = (long long)gridDim.x * blockDim.x;

@@ -1718,7 +1718,7 @@ def _ready_stream(owner, dev):
     return owner._ready.cuda_stream
 
 
-# kStageResample, kStageFilter, kStageCode of csrc/klatt_stage.h; kStageConvolve, kStageSpectrogram of csrc/klatt_stage_window.h
+# kStageResample, kStageFilter, kStageCode, kStageConvolve, kStageSpectrogram of csrc/klatt_stage.h
 STAGE_KINDS = ["resample", "filter", "code", "convolution", "spectrogram"]
 STAGE_MAKERS = {"convolution": "convolveStage", "spectrogram": "spectrogramStage"}      # (the others: kind + "Stage")
 STAGE_MAX_ROWS = 1 << 20                          # kStageMaxRows

@@ -56,8 +56,8 @@ template <typename In>
 static void res_push(const ResPlan& P, const StageGeometry& g, ResRowModel& r, const In* chunk, long long c, bool ended, std::vector<float>& out)
 {
     long long n;
-    CHECK(stage_row_plan(g, r.N, r.M, c, ended, n) && n >= 0);
     const int H = stage_history(g.Z);
+    CHECK(stage_keeps_history(g.kind) && stage_row_plan(g, H, r.N, r.M, c, ended, n) && n >= 0);
     CHECK((int)r.hist.size() == H);
     if (g.Z == 0) {      // equal rates: the samples themselves
         CHECK(n == c);
@@ -147,7 +147,7 @@ static void filter_push(const StageGeometry& g, const FilterSection* sec, int K,
                         std::vector<float>& out)
 {
     long long n;
-    CHECK(stage_row_plan(g, r.N, r.M, c, ended, n) && n == c + (ended ? g.tail : 0));
+    CHECK(!stage_keeps_history(g.kind) && stage_row_plan(g, 0, r.N, r.M, c, ended, n) && n == c + (ended ? g.tail : 0));
     const int bucket = filter_bucket(K);
     FilterSection cs[kFilterMaxSections];
     float s1[kFilterMaxSections], s2[kFilterMaxSections];
@@ -202,7 +202,7 @@ static void code_push(const StageGeometry& g, int codec, CodeRowModel& r, const 
                       std::vector<int16_t>& decoded)
 {
     long long n;
-    CHECK(stage_row_plan(g, r.N, r.M, c, ended, n) && n == c);
+    CHECK(!stage_keeps_history(g.kind) && stage_row_plan(g, 0, r.N, r.M, c, ended, n) && n == c);
     int val = r.val, idx = r.idx;
     const long long steps = codec == kCodecAdpcm ? (std::max(groupMost, n) + kFilterTile - 1) / kFilterTile * kFilterTile : n;
     for (long long t = 0; t < steps; ++t) {
@@ -259,7 +259,7 @@ int main()
     // a row may not pass 2^44 samples, and a negative length is no length
     StageGeometry g;
     long long n;
-    CHECK(stage_row_plan(g, kResampleMaxLength - 5, 0, 5, false, n) && !stage_row_plan(g, kResampleMaxLength - 5, 0, 6, false, n) && !stage_row_plan(g, 0, 0, -1, false, n));
+    CHECK(stage_row_plan(g, 0, kResampleMaxLength - 5, 0, 5, false, n) && !stage_row_plan(g, 0, kResampleMaxLength - 5, 0, 6, false, n) && !stage_row_plan(g, 0, 0, 0, -1, false, n));
     printf("ok %lld checks\n", g_checks);
     return 0;
 }

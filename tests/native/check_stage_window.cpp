@@ -1,5 +1,5 @@
 // check_stage_window.cpp -- a host model of the signal stages that keep a window (csrc/klatt_stage_window.h) in a program of its own, built
-// by tests/test_stage_window_host.py with AddressSanitizer + UBSan.  Each model drives the header's bookkeeping (stage_window_row_plan,
+// by tests/test_stage_window_host.py with AddressSanitizer + UBSan.  Each model drives the headers' bookkeeping (klatt_stage.h's stage_row_plan,
 // stage_frames_emitted, stage_conv_block_last / _skipped, stage_read_lane, stage_sample, stage_history_from_chunk, stage_row_advance) and
 // the shared statements (conv_step / conv_finish and the block arithmetic; the spec_* functions) chunk by chunk, as the kernels do, and must
 // give, bit for bit, what convolve_host / spectrogram_host give on the concatenation of the chunks.  Every chunk lives in an allocation of
@@ -69,11 +69,11 @@ static void next_history(RowModel& r, const In* chunk, long long c, bool ended)
 
 // ---- the convolution: the kernel's tiles and tap blocks ------------------------------------------------------------------------------------
 template <typename In>
-static void conv_push(const StageWindowGeometry& g, const float* h, int K, RowModel& r, const In* chunk, long long c, bool ended, std::vector<float>& out)
+static void conv_push(const StageGeometry& g, const float* h, int K, RowModel& r, const In* chunk, long long c, bool ended, std::vector<float>& out)
 {
     long long n;
-    CHECK(stage_window_row_plan(g, K, r.N, r.M, c, ended, n) && n == c + (ended && g.tail ? K - 1 : 0));
     const int H = stage_conv_history(K);
+    CHECK(stage_keeps_history(g.kind) && stage_row_plan(g, H, r.N, r.M, c, ended, n) && n == c + (ended && g.tail ? K - 1 : 0));
     CHECK((int)r.hist.size() == H);
     std::vector<float> xr, acc;
     for (long long t0 = 0; t0 < n; t0 += kConvolveTile) {
@@ -105,7 +105,7 @@ static void conv_push(const StageWindowGeometry& g, const float* h, int K, RowMo
     stage_row_advance(r.N, r.M, c, ended, n);
 }
 
-static void conv_stream(const StageWindowGeometry& g, const std::vector<float>& h, RowModel& r, const std::vector<long long>& lens)
+static void conv_stream(const StageGeometry& g, const std::vector<float>& h, RowModel& r, const std::vector<long long>& lens)
 {
     const int K = (int)h.size();
     std::vector<float> whole, got;
@@ -127,7 +127,7 @@ static void check_convolve(int K, int tail)
 {
     std::vector<float> h((size_t)K);
     for (int k = 0; k < K; ++k) h[(size_t)k] = k % 7 == 3 ? 0.0f : (float)((double)(long long)(rnd() % 2001) / 1000.0 - 1.0);      // (zero taps among them)
-    StageWindowGeometry g;
+    StageGeometry g;
     g.kind = kStageConvolve; g.tail = tail;
     RowModel r;
     r.hist.assign((size_t)stage_conv_history(K), 0.0f);
@@ -150,10 +150,10 @@ static void check_convolve(int K, int tail)
 
 // ---- the spectrogram: a frame from the virtual row through the shared functions ---------------------------------------------------------------
 template <typename In>
-static void spec_push(const SpecPlan& P, const StageWindowGeometry& g, RowModel& r, const In* chunk, long long c, bool ended, std::vector<double>& out)
+static void spec_push(const SpecPlan& P, const StageGeometry& g, RowModel& r, const In* chunk, long long c, bool ended, std::vector<double>& out)
 {
     long long n;
-    CHECK(stage_window_row_plan(g, 0, r.N, r.M, c, ended, n) && n >= 0);
+    CHECK(stage_keeps_history(g.kind) && stage_row_plan(g, stage_frame_history(g.frames), r.N, r.M, c, ended, n) && n >= 0);
     CHECK(n == stage_frames_emitted(g.frames, r.N + c, ended) - r.M);
     const int H = stage_frame_history(g.frames), M = P.M, K = M + 1, logM = P.logN - 1;
     CHECK(H == P.nFft - 1 && (int)r.hist.size() == H);
@@ -187,7 +187,7 @@ static void spec_push(const SpecPlan& P, const StageWindowGeometry& g, RowModel&
     stage_row_advance(r.N, r.M, c, ended, n);
 }
 
-static void spec_stream(const SpecPlan& P, const StageWindowGeometry& g, RowModel& r, const std::vector<long long>& lens)
+static void spec_stream(const SpecPlan& P, const StageGeometry& g, RowModel& r, const std::vector<long long>& lens)
 {
     std::vector<float> whole;
     std::vector<double> got;
@@ -219,7 +219,7 @@ static void check_spectrogram(int nFft, long long hop, long long phase, int band
             }
     }
     CHECK(spec_plan(P, nFft, nullptr, bands ? bank.data() : nullptr, bands, power, logScale, 1e-10, why));
-    StageWindowGeometry g;
+    StageGeometry g;
     g.kind = kStageSpectrogram; g.frames = stage_spec_frames(nFft, hop, phase);
     // the counts against brute force
     for (long long N = 0; N <= 3 * nFft + hop; ++N) {
@@ -256,10 +256,11 @@ int main()
     check_spectrogram(128, 1, 3, 5, 2, 0.0);
     check_spectrogram(256, 300, 259, 0, 1, 0.0);
     // the refusals of the plan: a negative chunk, a row that would pass 2^44 samples
-    StageWindowGeometry g;
+    StageGeometry g;
+    g.kind = kStageConvolve;
     long long n;
-    CHECK(stage_window_row_plan(g, 3, kResampleMaxLength - 5, 0, 5, false, n) && !stage_window_row_plan(g, 3, kResampleMaxLength - 5, 0, 6, false, n) &&
-          !stage_window_row_plan(g, 3, 0, 0, -1, false, n));
+    CHECK(stage_row_plan(g, 2, kResampleMaxLength - 5, 0, 5, false, n) && !stage_row_plan(g, 2, kResampleMaxLength - 5, 0, 6, false, n) &&
+          !stage_row_plan(g, 2, 0, 0, -1, false, n));
     printf("ok %lld\n", g_checks);
     return 0;
 }

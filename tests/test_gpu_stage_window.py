@@ -105,6 +105,35 @@ def test_convolution_pushes_concatenate_to_the_statement(bare, n, tail):
     raw.free()
 
 
+def test_histories_of_unequal_lengths_at_unequal_offsets(bare):
+    """Five rows whose irOf names responses of 1, 2, 5, 1025 and 2 taps: histories of 0, 1, 4, 1024 and 1 samples, at the offsets 0, 0, 1,
+    5 and 1029 of either buffer, one row with none.  Two pushes of 7 and 3 float32 samples a row, both shorter than the longest history, so
+    its next history mixes old history and chunk; a reset of rows [0, 1, 0, 1, 1]; a push of 9 that ends every row.  Rows 0 and 2 are
+    signalConvolve of their 19 samples, rows 1, 3 and 4 of the last 9 alone, bit for bit."""
+    import torch
+    import nvspeechplayer_amd as eng
+    irs = [response(K, 80 + K) for K in (1, 2, 5, 1025)]
+    of = [0, 1, 2, 3, 1]
+    stage = bare.convolveStage(5, irs, irOf=of, tail=False)
+    rng = np.random.default_rng(27)
+    chunks = [rng.uniform(-1.0, 1.0, (5, c)).astype(F32) for c in (7, 3, 9)]
+    outs = []
+    for k, x in enumerate(chunks):
+        if k == 2:
+            stage.reset(np.array([False, True, False, True, True]))
+            assert list(stage.consumed) == [10, 0, 10, 0, 0]
+        out, counts = stage.push((torch.from_numpy(x).to("cuda:%d" % bare.device), np.full(5, x.shape[1])), end=k == 2)
+        assert out.dtype == torch.float32 and list(counts) == [x.shape[1]] * 5
+        outs.append(out.cpu().numpy())
+    for i in range(5):
+        kept = i in (0, 2)
+        got = np.concatenate([o[i] for o in outs]) if kept else outs[2][i]
+        x = np.concatenate([c[i] for c in chunks]) if kept else chunks[2][i]
+        assert len(got) == (19 if kept else 9) and same(got, eng.signalConvolve(x, irs[of[i]], tail=False)), i
+    assert not stage.consumed.any()
+    stage.close()
+
+
 # ---- 2. the spectrogram ----------------------------------------------------------------------------------------------------------------------
 def spectrogram_stream(bare, n, geometry, bank, power, scale, floor, seed):
     import nvspeechplayer_amd as eng

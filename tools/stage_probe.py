@@ -3,7 +3,8 @@ csrc/klatt_stage_window.h) beside the whole-row exports of a signal on the same 
 1024 rows x 8192 float32 samples at 22050 -> 16000 against resampledTensor(signal=), the same through the four-section telephone band
 against filteredTensor(signal=), through a 4096-tap response against convolvedTensor(signal=) and into a 1024-point, 80-band mel
 spectrogram against spectrogramTensor(signal=), and the single-row 8192-sample push a one-stream caller pays, per kind; then, --long, 64
-rows through a 65536-tap response, where a push copies 65535 float32 of history per row.  Two figures per call: `queued`, device events around REPS calls issued back to back, per call --
+rows through a 65536-tap response, where a push copies 65535 float32 of history per row, and, --short, 16384 rows x 256 samples through the
+resampler, where the history copy's share of a push is largest.  Two figures per call: `queued`, device events around REPS calls issued back to back, per call --
 what the kernels and the staging copy take once the host runs ahead --, and `alone`, a host clock around one call and a synchronise.
 Prints one JSON object; --out writes it to a file as well.  Needs a GPU."""
 import argparse
@@ -63,6 +64,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--families", default="resample,filter,adpcm,convolution,spectrogram", help="comma-separated: which rows to time")
     ap.add_argument("--long", action="store_true", help="also 64 rows through a 65536-tap response")
+    ap.add_argument("--short", action="store_true", help="also 16384 rows x 256 samples through the resampler, 22050 -> 16000")
     ap.add_argument("--exports-only", action="store_true", help="the whole-row exports alone: an A/B of two builds of the library (SPEECHPLAYER_LIB)")
     args = ap.parse_args()
     families = args.families.split(",")
@@ -97,6 +99,14 @@ def main():
                  "convolvedTensor(65536 taps, tail=False, signal=)": lambda: bp.convolvedTensor(room, tail=False, signal=signal)}
         result["%d rows x %d float32, 65536 taps" % (rows, SAMPLES)] = measure(calls, dev, reps=4)
         con.close()
+    if args.short:      # the resampler's history copy at its largest share: 2 Z - 1 = 17 float32 of history a row beside 256 samples of chunk
+        rows, samples = 16384, 256
+        x = torch.from_numpy(rng.uniform(-1.0, 1.0, (rows, samples)).astype(np.float32)).to("cuda:%d" % dev)
+        signal = (x, np.full(rows, samples, np.int64))
+        res = bp.resampleStage(rows, 22050, 16000)
+        calls = {"resample stage push": lambda: res.push(signal), "resampledTensor(signal=)": lambda: bp.resampledTensor(16000, signal=signal)}
+        result["%d rows x %d float32" % (rows, samples)] = measure(calls, dev)
+        res.close()
     bp.close()
     text = json.dumps(result, indent=1)
     print(text)
