@@ -919,9 +919,10 @@ long long speechPlayer_batch_exportCodedOf(speechPlayer_batch_t batch, const spe
  * count is not the stage's; what the exports of a signal refuse of the signal, the output, rowStride and the format; an output or
  * deviceCodes that overlaps the chunk, or the two each other; a row that would pass 2^44; a stage that was freed, alone or with its
  * batch (the handle names nothing any more); for a code stage, neither output given; deviceCodes on a stage that is not a code stage.
- * Out of scope: the convolution, spectrogram, LPC, pitch and tempo exports chunk by chunk; saving a stage's state to the host; NodePlayer;
- * a fused kernel for a chain of stages ("Signal stages that keep a window", below, adds the convolution and the spectrogram:
- * speechPlayer_batch_stageConvolve, speechPlayer_batch_stageSpectrogram).  The kernels are csrc/klatt_stage.h.
+ * Out of scope in this section: the convolution, spectrogram, LPC, pitch and tempo exports chunk by chunk; saving a stage's state to the
+ * host; NodePlayer; a fused kernel for a chain of stages ("Signal stages that keep a window", below, adds the convolution and the
+ * spectrogram: speechPlayer_batch_stageConvolve, speechPlayer_batch_stageSpectrogram; "Signal stages on the step grid", behind it, adds LPC
+ * and the pitch: speechPlayer_batch_stageLpc, speechPlayer_batch_stagePitch; tempo has no stage).  The kernels are csrc/klatt_stage.h.
  */
 typedef void* speechPlayer_stage_t;
 speechPlayer_stage_t speechPlayer_batch_stageResample(speechPlayer_batch_t batch, long long nRows, int srcRate, int outRate, int zeros, double rolloff,
@@ -978,15 +979,58 @@ long long speechPlayer_resampleEmitted(long long consumed, int srcRate, int outR
  * exceed 2^27 float32 per buffer (512 MiB; there are two), before anything is allocated; and of a push what the stages above refuse,
  * deviceCodes included.  speechPlayer_spectrogramEmitted refuses consumed outside 0 .. 2^44, an nFft that is no power of two in
  * 64 .. 4096, hop <= 0 and phase < 0.
- * Out of scope: LPC, pitch and tempo chunk by chunk (the frame bookkeeping here is written for a general (before, after) and serves the
- * first two); a mix stage (an SNR needs the whole row's power); FFT or MFMA convolution; saving a stage's state to the host; NodePlayer;
- * a fused kernel for a chain.  The kernels are csrc/klatt_stage_window.h.
+ * Out of scope: LPC, pitch and tempo chunk by chunk are not in this section (the frame bookkeeping here is written for a general
+ * (before, after) and serves the first two, which follow in "Signal stages on the step grid", below; tempo has no stage); a mix stage (an
+ * SNR needs the whole row's power); FFT or MFMA convolution; saving a stage's state to the host; NodePlayer; a fused kernel for a chain.
+ * The kernels are csrc/klatt_stage_window.h.
  */
 speechPlayer_stage_t speechPlayer_batch_stageConvolve(speechPlayer_batch_t batch, long long nRows, const float* ir, const long long* irStart, long long nIr,
 	const long long* irOf, int tail);
 speechPlayer_stage_t speechPlayer_batch_stageSpectrogram(speechPlayer_batch_t batch, long long nRows, int nFft, long long hop, long long phase,
 	const double* window, const double* bank, int nBands, int power, double logScale, double floor);
 long long speechPlayer_spectrogramEmitted(long long consumed, int nFft, long long hop, long long phase, int ended);
+/*
+ * Signal stages on the step grid: the linear-prediction analysis and the pitch (YIN) fed chunk by chunk -- the frame features a live stream
+ * needs beside its mu-law code (LPCNet-style vocoders), and the pitch a streaming front end tracks.  Both are stages as above (made on a
+ * batch, pushed with speechPlayer_stage_push, planned, reset, counted and freed by the same entry points) whose per-row state is the
+ * spectrogram stage's: a window of the row's most recent samples, float32 as x gave them and +0 before sample 0, H = before + after
+ * samples of the frame (before, after) around a step's centre c_j = phase + j hop.
+ *   LPC     (order, nWin, hop, phase, window, lagWindow, what: speechPlayer_batch_exportLpc's arguments and refusals.)  Step j reads the
+ *           samples c_j - floor(nWin / 2) .. c_j - floor(nWin / 2) + nWin - 1, as the definition below has them: a frame (before, after)
+ *           = (floor(nWin / 2), nWin - 1 - floor(nWin / 2)).  A row keeps H = nWin - 1 samples.  nCols = the values per step of `what`.
+ *   pitch   (sampleRate, nWin = W, lagMin, lagMax, threshold, hop, phase, what: speechPlayer_batch_exportPitchOf's arguments and
+ *           refusals.)  The frame has Nf = W + lagMax samples from c_j - floor(Nf / 2): (before, after) = (floor(Nf / 2), Nf - 1 -
+ *           floor(Nf / 2)).  A row keeps H = Nf - 1 samples.  nCols = the values per step of `what`, lagMax - lagMin + 1 of them the CMND's.
+ * The counts are the spectrogram stage's, with these (before, after): open, a row has emitted the steps whose whole frame lies at or before
+ * sample N - 1, E_open(N) = 0 if N - after - 1 - phase < 0, else floor((N - after - 1 - phase) / hop) + 1; ended, the definition's
+ * ceil((N - phase) / hop), 0 when N <= phase, samples past the end being +0.  A push emits E(N', ended) - M steps.  That H = before + after
+ * samples suffice whatever hop and phase are is the lemma on the spectrogram's history above, which is stated for a general
+ * (before, after).  A hop or a phase above 2^45 means 2^45; the sum of H over the rows is held to 2^27 float32 per buffer before anything
+ * is allocated.
+ * The output is laid out as the spectrogram stage's, [row][step][nCols]: format 0 is float64 and 1 float32, rowStride is in STEPS (0:
+ * packed), outLengths are steps per row, the return value is steps times nCols, padding is +0, deviceCodes is refused.  Neither output is
+ * a signal, so either stage ends a chain.  The window (float32) and the lag window (binary64) are the stage's own, uploaded once when it
+ * is made.
+ * The claim.  For every row, the outputs of its pushes up to and including the one that ends it, concatenated, are BIT FOR BIT
+ * speechPlayer_signalLpc / speechPlayer_signalPitch of the concatenation of its chunks -- a chunk of int16 and a chunk of float32 count
+ * alike, each through x --, under those exports' bounds.  There is no logarithm here and so no ulp bar: every field is bit-equal.  A row
+ * pushed after its end or its reset is a fresh row.
+ * speechPlayer_lpcEmitted and speechPlayer_pitchEmitted are host only and need no stage: the steps a row has emitted after `consumed`
+ * samples, open or ended; the difference of two is a push's count.
+ * Refused with SPEECHPLAYER_ERR_ARGUMENT (the makers return NULL, the others -1), nothing written AND THE STATE UNCHANGED: what the
+ * whole-row exports refuse of the same arguments; nRows outside 1 .. 2^20; histories beyond 2^27 samples in all; and of a push what the
+ * spectrogram stage refuses.  The two *Emitted functions refuse consumed outside 0 .. 2^44, hop <= 0, phase < 0, an nWin outside 2 .. 4096
+ * (LPC) or 32 .. 2048 (pitch) and a lagMax outside 3 .. 1024.
+ * Out of scope: the residual or the prediction (speechPlayer_batch_exportLpcResidual) chunk by chunk -- a sample's frame is the nearest
+ * centre, so it needs frames still to come --; tempo; a mix stage; saving a stage's state to the host; NodePlayer; a fused kernel for a
+ * chain.  The kernels are csrc/klatt_stage_frames.h.
+ */
+speechPlayer_stage_t speechPlayer_batch_stageLpc(speechPlayer_batch_t batch, long long nRows, int order, int nWin, long long hop, long long phase,
+	const double* window, const double* lagWindow, int what);
+speechPlayer_stage_t speechPlayer_batch_stagePitch(speechPlayer_batch_t batch, long long nRows, int sampleRate, int nWin, int lagMin, int lagMax,
+	double threshold, long long hop, long long phase, int what);
+long long speechPlayer_lpcEmitted(long long consumed, int nWin, long long hop, long long phase, int ended);
+long long speechPlayer_pitchEmitted(long long consumed, int nWin, int lagMax, long long hop, long long phase, int ended);
 /*
  * Linear prediction (LPC) of a batch's PCM, or of a signal's rows, on the step grid of the other exports: per analysis frame the
  * autocorrelation, the prediction coefficients, the reflection coefficients and the prediction error; and, per sample, the residual or
@@ -1037,8 +1081,9 @@ long long speechPlayer_spectrogramEmitted(long long consumed, int nFft, long lon
  * The definition is the function bodies of csrc/klatt_lpc.h, which the host and the device compile from one source.  Over the pool the
  * result is a function of the batch's PCM: it depends on the mode and needs a synthesis launch.
  * Out of scope: line spectral frequencies; Burg and covariance methods; the recursive synthesis filter 1 / A(z); order above 32;
- * pre-emphasis inside the export (the chain is exportFiltered with a pre-emphasis section, then the signal form); live handles; NodePlayer
- * beyond speechPlayer_node_part.
+ * pre-emphasis inside the export (the chain is exportFiltered with a pre-emphasis section, then the signal form); live handles through
+ * this export (the last nWin - 1 samples would have to persist across pulls: "Signal stages on the step grid", above, keep them for the
+ * analysis -- speechPlayer_batch_stageLpc; the residual has no stage); NodePlayer beyond speechPlayer_node_part.
  *
  * Host only, touches no device: the recursion alone on r[order + 1].  a and k take order values each (a_1 .., k_1 ..), error E, stages the
  * stages done; each may be NULL.  Returns order; -1 on order outside 1 .. 32 or a NULL r. */
@@ -1127,7 +1172,8 @@ long long speechPlayer_batch_exportLpcResidualOf(speechPlayer_batch_t batch, con
  * m = 0.11 at lag 95 beside the period of 100.2 samples --; the CMND field exists so that a tracker can decide otherwise.
  * Out of scope: normalised cross-correlation and energies; smoothing or tracking across steps; octave-error correction; FFT or MFMA
  * evaluation of the difference (their summation order is not the definition's); decimation inside the export (the chain is
- * exportResampled to 16000 Hz, then the signal form); live handles; NodePlayer beyond speechPlayer_node_part.
+ * exportResampled to 16000 Hz, then the signal form); live handles through this export ("Signal stages on the step grid", above, keep the
+ * last nWin + lagMax - 1 samples across pulls -- speechPlayer_batch_stagePitch); NodePlayer beyond speechPlayer_node_part.
  *
  * Host only, touch no device: the estimate above on `length` samples of plain PCM (speechPlayer_pcmPitch) or of a signal's row, int16
  * (inFormat 0) or float32 (inFormat 1) (speechPlayer_signalPitch), out[step][nCols] float64 -- the statements the device is held to bit for

@@ -79,6 +79,7 @@ EXPORTS = [
     "speechPlayer_batch_stageResample", "speechPlayer_batch_stageFilter", "speechPlayer_batch_stageCode", "speechPlayer_stage_plan", "speechPlayer_stage_push",
     "speechPlayer_stage_reset", "speechPlayer_stage_counts", "speechPlayer_stage_free", "speechPlayer_resampleEmitted",
     "speechPlayer_batch_stageConvolve", "speechPlayer_batch_stageSpectrogram", "speechPlayer_spectrogramEmitted",
+    "speechPlayer_batch_stageLpc", "speechPlayer_batch_stagePitch", "speechPlayer_lpcEmitted", "speechPlayer_pitchEmitted",
 ]
 
 
@@ -524,6 +525,14 @@ def load():
     L.speechPlayer_batch_stageSpectrogram.argtypes = [vp, i64, i32, i64, i64, vp, vp, i32, i32, f64, f64]
     L.speechPlayer_spectrogramEmitted.restype = i64
     L.speechPlayer_spectrogramEmitted.argtypes = [i64, i32, i64, i64, i32]
+    L.speechPlayer_batch_stageLpc.restype = vp
+    L.speechPlayer_batch_stageLpc.argtypes = [vp, i64, i32, i32, i64, i64, vp, vp, i32]
+    L.speechPlayer_batch_stagePitch.restype = vp
+    L.speechPlayer_batch_stagePitch.argtypes = [vp, i64, i32, i32, i32, i32, f64, i64, i64, i32]
+    L.speechPlayer_lpcEmitted.restype = i64
+    L.speechPlayer_lpcEmitted.argtypes = [i64, i32, i64, i64, i32]
+    L.speechPlayer_pitchEmitted.restype = i64
+    L.speechPlayer_pitchEmitted.argtypes = [i64, i32, i32, i64, i64, i32]
     _lib = L
     return L
 

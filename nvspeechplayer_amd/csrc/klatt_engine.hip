@@ -29,6 +29,7 @@
 #include "klatt_stage_window.h"
 #include "klatt_lpc.h"
 #include "klatt_pitch.h"
+#include "klatt_stage_frames.h"
 #include "klatt_tempo.h"
 #include "klatt_mix.h"
 #include "klatt_export.h"
@@ -729,6 +730,9 @@ struct Stage {
     DeviceBuffer<float> dWindow, dWeights;
     DeviceBuffer<SpecCx> dTw;
     DeviceBuffer<int> dRange;
+    LpcPlan lpc;                               // LPC: the plan without its arrays, which the device holds (dWindow, dLag)
+    DeviceBuffer<double> dLag;
+    PitchPlan pitch;                           // pitch
     hipEvent_t done = nullptr;
     bool used = false;
 };
@@ -754,7 +758,7 @@ void stage_release(Stage* s)
     }
     if (s->done) { if (s->used) (void)hipEventSynchronize(s->done); (void)hipEventDestroy(s->done); }
     s->dTable.release(); s->dHist[0].release(); s->dHist[1].release(); s->dFilterState.release(); s->dCodeState.release();
-    s->dTaps.release(); s->dWindow.release(); s->dWeights.release(); s->dTw.release(); s->dRange.release();
+    s->dTaps.release(); s->dWindow.release(); s->dWeights.release(); s->dTw.release(); s->dRange.release(); s->dLag.release();
     delete s;
 }
 
@@ -5657,6 +5661,65 @@ long long speechPlayer_spectrogramEmitted(long long consumed, int nFft, long lon
     return stage_frames_emitted(stage_spec_frames(nFft, hop, phase), consumed, ended != 0);
 }
 
+// The stages on the step grid (klatt_stage_frames.h): the whole-row exports' plans, a history of the frame's before + after samples a row
+speechPlayer_stage_t speechPlayer_batch_stageLpc(speechPlayer_batch_t batch, long long nRows, int order, int nWin, long long hop, long long phase, const double* window,
+                                                 const double* lagWindow, int fields)
+{
+    const char* what = "stageLpc";
+    return stage_create(what, batch, nRows, [&](Batch* b, Stage* s) -> int {
+        if (stage_step_request(what, hop, phase)) return -1;
+        LpcPlan& P = s->lpc;
+        std::string why;
+        if (!lpc_plan(P, order, nWin, window, lagWindow, fields, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        s->g.kind = kStageLpc; s->g.frames = stage_lpc_frames(nWin, hop, phase);
+        const long long H = stage_frame_history(s->g.frames);
+        if (stage_histories(what, b, s, [&](long long) { return H; }, kStageMaxHistory)) return -1;
+        if (stage_upload(b, s->dWindow, P.window) || stage_upload(b, s->dLag, P.lag)) return -1;
+        std::vector<float>().swap(P.window); std::vector<double>().swap(P.lag);      // (the device holds what the pushes read)
+        return 0;
+    });
+}
+
+speechPlayer_stage_t speechPlayer_batch_stagePitch(speechPlayer_batch_t batch, long long nRows, int sampleRate, int nWin, int lagMin, int lagMax, double threshold,
+                                                   long long hop, long long phase, int fields)
+{
+    const char* what = "stagePitch";
+    return stage_create(what, batch, nRows, [&](Batch* b, Stage* s) -> int {
+        if (stage_step_request(what, hop, phase)) return -1;
+        std::string why;
+        if (!pitch_plan(s->pitch, sampleRate, nWin, lagMin, lagMax, threshold, fields, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        s->g.kind = kStagePitch; s->g.frames = stage_pitch_frames(nWin, lagMax, hop, phase);
+        const long long H = stage_frame_history(s->g.frames);
+        return stage_histories(what, b, s, [&](long long) { return H; }, kStageMaxHistory);
+    });
+}
+
+// Host only, touch no device: the steps an LPC or a pitch stage has emitted after `consumed` samples of a row, open or ended
+static long long stage_emitted_request(const char* what, long long consumed, long long& hop, long long& phase)
+{
+    if (consumed < 0 || consumed > kResampleMaxLength) { set_error("%s: %lld samples consumed (0 .. 2^44)", what, consumed); return -1; }
+    return stage_step_request(what, hop, phase);
+}
+
+long long speechPlayer_lpcEmitted(long long consumed, int nWin, long long hop, long long phase, int ended)
+{
+    begin_call();
+    const char* what = "lpcEmitted";
+    if (stage_emitted_request(what, consumed, hop, phase)) return -1;
+    if (nWin < 2 || nWin > kLpcMaxWin) { set_error("%s: nWin %d (2 .. %d)", what, nWin, kLpcMaxWin); return -1; }
+    return stage_frames_emitted(stage_lpc_frames(nWin, hop, phase), consumed, ended != 0);
+}
+
+long long speechPlayer_pitchEmitted(long long consumed, int nWin, int lagMax, long long hop, long long phase, int ended)
+{
+    begin_call();
+    const char* what = "pitchEmitted";
+    if (stage_emitted_request(what, consumed, hop, phase)) return -1;
+    if (nWin < kPitchMinWin || nWin > kPitchMaxWin) { set_error("%s: nWin %d (%d .. %d)", what, nWin, kPitchMinWin, kPitchMaxWin); return -1; }
+    if (lagMax < 3 || lagMax > kPitchMaxLag) { set_error("%s: lagMax %d (3 .. %d)", what, lagMax, kPitchMaxLag); return -1; }
+    return stage_frames_emitted(stage_pitch_frames(nWin, lagMax, hop, phase), consumed, ended != 0);
+}
+
 // The stage a handle names, or null with the message set: a handle that was freed -- alone or with its batch -- names none
 static Stage* stage_of(const char* what, speechPlayer_stage_t stage)
 {
@@ -5895,8 +5958,10 @@ static int stage_push_convolve(Stage* s, const ExportInput& in, const unsigned c
     return stage_history_finish(s, pass, in, pass.stage.device<StageHistRow>(rowsAt));
 }
 
-static int stage_push_spectrogram(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long elements, void* deviceOut, int format,
-                                  long long rowStride, hipStream_t st)
+// A push onto a stage on the step grid -- the spectrogram, LPC, the pitch --: one staging of the rows and of the push's step table, the
+// kind's kernel over the steps (its whole-row kernel's grid and dynamic LDS), then the next history
+static int stage_push_frames(Stage* s, const ExportInput& in, const unsigned char* end, const ExportSelection& sel, long long elements, void* deviceOut, int format,
+                             long long rowStride, hipStream_t st)
 {
     const std::vector<StageHistRow> rows = stage_history_rows(s, in, end, sel, rowStride);
     const bool packed = rowStride == 0;
@@ -5904,18 +5969,61 @@ static int stage_push_spectrogram(Stage* s, const ExportInput& in, const unsigne
     const RowTable table = packed ? packed_row_table(sel.counts.data(), 0, sel.n, kTimelineChunkLog2, words) : RowTable{0, 0};
     StageBlock block;
     const int rowsAt = block.add(rows), wordsAt = block.add(words);
-    void (*const kernels[2][2])(StageSpecArgs) = {{klatt_stage_spectrogram<false, int16_t>, klatt_stage_spectrogram<true, int16_t>},
-                                                  {klatt_stage_spectrogram<false, float>, klatt_stage_spectrogram<true, float>}};
-    const auto kernel = kernels[in.format()][format];
+    void (*const specKernels[2][2])(StageSpecArgs) = {{klatt_stage_spectrogram<false, int16_t>, klatt_stage_spectrogram<true, int16_t>},
+                                                      {klatt_stage_spectrogram<false, float>, klatt_stage_spectrogram<true, float>}};
+    void (*const lpcKernels[2][2])(StageLpcArgs) = {{klatt_stage_lpc<false, int16_t>, klatt_stage_lpc<true, int16_t>}, {klatt_stage_lpc<false, float>, klatt_stage_lpc<true, float>}};
+    void (*const pitchKernels[2][2])(StagePitchArgs) = {{klatt_stage_pitch<false, int16_t>, klatt_stage_pitch<true, int16_t>},
+                                                        {klatt_stage_pitch<false, float>, klatt_stage_pitch<true, float>}};
+    const auto specKernel = specKernels[in.format()][format];
+    const auto lpcKernel = lpcKernels[in.format()][format];
+    const auto pitchKernel = pitchKernels[in.format()][format];
+    const int kind = s->g.kind;
+    const void* const kernel = kind == kStageSpectrogram ? reinterpret_cast<const void*>(specKernel)
+                               : kind == kStageLpc       ? reinterpret_cast<const void*>(lpcKernel)
+                                                         : reinterpret_cast<const void*>(pitchKernel);
+    const int budget = kind == kStageSpectrogram ? (int)kSpecLdsBudget : kind == kStageLpc ? (int)kLpcLdsBudget : (int)kPitchLdsBudget;
     StagePass pass(s, st, block);
-    if (pass.begin([&] { return ensure_lds_limit(reinterpret_cast<const void*>(kernel), kSpecLdsBudget); })) return -1;
+    if (pass.begin([&] { return ensure_lds_limit(kernel, budget); })) return -1;
     if (elements > 0) {
-        StageSpecArgs A;
-        A.s = spec_args(pass.stage, s->spec, packed ? &table : nullptr, wordsAt, rowStride, elements, s->g.frames.hop, s->g.frames.phase, deviceOut);
-        A.s.in = in.data; A.s.rows = nullptr;
-        A.s.window = s->dWindow.ptr; A.s.tw = s->dTw.ptr; A.s.weights = s->dWeights.ptr; A.s.range = s->dRange.ptr;
-        A.rows = pass.stage.device<StageHistRow>(rowsAt); A.hist = s->dHist[s->cur].ptr;
-        if (queue_spectrogram(pass.stage, kernel, A, A.s)) return -1;
+        const StageHistRow* dRows = pass.stage.device<StageHistRow>(rowsAt);
+        const long long* start = packed ? pass.stage.device<long long>(wordsAt) + table.startOff : nullptr;
+        const long long* chunk = packed ? pass.stage.device<long long>(wordsAt) + table.chunkOff : nullptr;
+        const size_t elSize = format ? sizeof(float) : sizeof(double);
+        if (kind == kStageSpectrogram) {
+            StageSpecArgs A;
+            A.s = spec_args(pass.stage, s->spec, packed ? &table : nullptr, wordsAt, rowStride, elements, s->g.frames.hop, s->g.frames.phase, deviceOut);
+            A.s.in = in.data; A.s.rows = nullptr;
+            A.s.window = s->dWindow.ptr; A.s.tw = s->dTw.ptr; A.s.weights = s->dWeights.ptr; A.s.range = s->dRange.ptr;
+            A.rows = dRows; A.hist = s->dHist[s->cur].ptr;
+            if (queue_spectrogram(pass.stage, specKernel, A, A.s)) return -1;
+        } else if (kind == kStageLpc) {
+            const LpcPlan& P = s->lpc;
+            StageLpcArgs A;
+            A.s.in = in.data; A.s.rows = nullptr; A.s.start = start; A.s.chunk = chunk;
+            A.s.rowStride = rowStride; A.s.nSteps = elements / P.nCols;
+            A.s.hop = s->g.frames.hop; A.s.phase = s->g.frames.phase;
+            A.s.window = s->dWindow.ptr; A.s.lag = P.hasLag ? s->dLag.ptr : nullptr;
+            A.s.order = P.order; A.s.nWin = P.nWin; A.s.what = P.what; A.s.nCols = P.nCols;
+            A.s.out = deviceOut;
+            A.rows = dRows; A.hist = s->dHist[s->cur].ptr;
+            const long long nGroups = (A.s.nSteps + kLpcGroup - 1) / kLpcGroup;
+            const unsigned grid = (unsigned)std::min<long long>(nGroups, 8ll * s->b->cus);
+            hipLaunchKernelGGL(lpcKernel, dim3(grid), dim3(256), lpc_lds_bytes(P.nWin, P.order, P.nCols, (int)elSize), pass.stage.st, A);
+            HIP_TRY(hipGetLastError());
+        } else {
+            const PitchPlan& P = s->pitch;
+            StagePitchArgs A;
+            A.s.in = in.data; A.s.rows = nullptr; A.s.start = start; A.s.chunk = chunk;
+            A.s.rowStride = rowStride; A.s.nSteps = elements / P.nCols;
+            A.s.hop = s->g.frames.hop; A.s.phase = s->g.frames.phase; A.s.threshold = P.threshold;
+            A.s.nWin = P.nWin; A.s.lagMin = P.lagMin; A.s.lagMax = P.lagMax; A.s.what = P.what; A.s.nCols = P.nCols; A.s.sampleRate = P.sampleRate;
+            A.s.out = deviceOut;
+            A.rows = dRows; A.hist = s->dHist[s->cur].ptr;
+            const long long nGroups = (A.s.nSteps + kPitchGroup - 1) / kPitchGroup;
+            const unsigned grid = (unsigned)std::min<long long>(nGroups, 8ll * s->b->cus);
+            hipLaunchKernelGGL(pitchKernel, dim3(grid), dim3(256), pitch_lds_bytes(P.nWin, P.lagMax, P.nCols, (int)elSize), pass.stage.st, A);
+            HIP_TRY(hipGetLastError());
+        }
     }
     return stage_history_finish(s, pass, in, pass.stage.device<StageHistRow>(rowsAt));
 }
@@ -5930,7 +6038,8 @@ long long speechPlayer_stage_push(speechPlayer_stage_t stage, const speechPlayer
     if (!s) return -1;
     Batch* b = s->b;
     try {
-        const bool code = s->g.kind == kStageCode, spec = s->g.kind == kStageSpectrogram;
+        const bool code = s->g.kind == kStageCode, spec = stage_has_frames(s->g.kind);      // spec: the output is [step][nCols]
+        const int nCols = s->g.kind == kStageSpectrogram ? s->spec.nOut : s->g.kind == kStageLpc ? s->lpc.nCols : s->g.kind == kStagePitch ? s->pitch.nCols : 1;
         if (spec) {      // (the spectrogram export's formats, rowStride in steps)
             if (format != 0 && format != 1) { set_error("%s: format %d (0 float64, 1 float32)", what, format); return -1; }
             if (rowStride < 0) { set_error("%s: rowStride %lld", what, rowStride); return -1; }
@@ -5945,7 +6054,9 @@ long long speechPlayer_stage_push(speechPlayer_stage_t stage, const speechPlayer
         bool active = false;      // a row that is neither fed nor ended is untouched
         for (long long i = 0; i < s->nRows && !active; ++i) active = sig.len(i) > 0 || (end && end[i]);
         static constexpr ExportNouns kBandNouns{"largest step count", "steps", "bands"};
-        const long long elements = spec ? export_elements(what, kBandNouns, sel, rowStride, s->spec.nOut) : export_elements(what, kSampleNouns, sel, rowStride, 1);
+        static constexpr ExportNouns kFieldNouns{"largest step count", "steps", "values"};
+        const long long elements = spec ? export_elements(what, s->g.kind == kStageSpectrogram ? kBandNouns : kFieldNouns, sel, rowStride, nCols)
+                                        : export_elements(what, kSampleNouns, sel, rowStride, 1);
         if (elements < 0) return -1;
         if (code && elements > 0 && !deviceOut && !deviceCodes) { set_error("%s: no output (the decoded samples, the codes or both)", what); return -1; }
         if (elements > 0 || active) {
@@ -5964,7 +6075,7 @@ long long speechPlayer_stage_push(speechPlayer_stage_t stage, const speechPlayer
             const int rc = s->g.kind == kStageResample ? stage_push_resample(s, in, end, sel, elements, deviceOut, format, rowStride, st)
                          : s->g.kind == kStageFilter   ? stage_push_filter(s, in, end, sel, deviceOut, format, rowStride, st)
                          : s->g.kind == kStageConvolve ? stage_push_convolve(s, in, end, sel, deviceOut, format, rowStride, st)
-                         : spec                        ? stage_push_spectrogram(s, in, end, sel, elements, deviceOut, format, rowStride, st)
+                         : spec                        ? stage_push_frames(s, in, end, sel, elements, deviceOut, format, rowStride, st)
                                                        : stage_push_code(s, in, end, sel, elements, deviceOut, format, deviceCodes, rowStride, st);
             if (rc) return -1;
         }

@@ -24,7 +24,8 @@
 //   The inverse     lpc_frame_of: the nearest centre, ties upward; lpc_inverse: the fma chain in ascending m from x(t) (residual) or
 //   filter          +0.0 (prediction, negated), rounded to float32 once.
 //
-//   klatt_lpc<F32, In>   A 256-lane workgroup takes kLpcGroup = 64 consecutive steps of the OUTPUT (located by dense_locate: a group may
+//   klatt_lpc<F32, In>   lpc_rows<F32>, the one body it shares with klatt_stage_lpc (klatt_stage_frames.h), handed the row's own steps, the
+//                   frame's first sample phase + j hop - nWin / 2 and the reader tile_sample.  A 256-lane workgroup takes kLpcGroup = 64 consecutive steps of the OUTPUT (located by dense_locate: a group may
 //                   end one row and begin the next).  Phase A: each wavefront takes 16 of them, one at a time and at its own pace (its LDS region is its own: lpc_wave_sync): coalesced masked loads
 //                   of the frame, the window product, xw into its own LDS region; lane q then accumulates partial[q] of kLpcLagBlock
 //                   lags at a time (xw[i] is read once per block; consecutive lanes read consecutive words: no bank conflict), the tree
@@ -40,7 +41,8 @@
 //                   (hop 1: every sample has a row of its own, staging would share nothing), one output per lane per pass, stored by
 //                   tile_store.
 // Out of scope: line spectral frequencies, Burg and covariance methods, the recursive synthesis filter 1 / A(z), order above 32,
-// pre-emphasis inside the export, live handles, NodePlayer.
+// pre-emphasis inside the export, live handles (their pulls go through the LPC stage of klatt_stage_frames.h; the inverse filter has no
+// stage: a sample's frame is the nearest centre, which may be a frame still to come), NodePlayer.
 #pragma once
 
 #include <math.h>
@@ -293,8 +295,11 @@ __device__ __forceinline__ void lpc_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <bool F32, typename In = int16_t>
-__global__ void __launch_bounds__(256) klatt_lpc(const LpcArgs A)
+// The one body of klatt_lpc and of klatt_stage_lpc (klatt_stage_frames.h: the analysis fed chunk by chunk), its two entry points: `rows` is
+// the launch's row table, steps(row) the steps of a row in this output, first(row, j) the first sample of its step j's frame, and
+// sample(row, t) sample t as the reader gives it -- of the row itself, or of a stage's virtual row.
+template <bool F32, class Row, class Steps, class First, class Sample>
+__device__ __forceinline__ void lpc_rows(const LpcArgs& A, const Row* __restrict__ rows, Steps steps, First first, Sample sample)
 {
     using T = typename std::conditional<F32, float, double>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char lpc_lds[];
@@ -312,19 +317,18 @@ __global__ void __launch_bounds__(256) klatt_lpc(const LpcArgs A)
         for (int s = 0; s < kLpcGroup / 4; ++s) {
             const int step = wave * (kLpcGroup / 4) + s;
             bool live = false;
-            SpecRow row{0, 0, 0};
+            Row row{};
             long long j = 0;
             if (step < nInside) {
                 long long g, r;
                 int q;
                 dense_locate(g0 + step, 1, A.rowStride, A.start, A.chunk, g, q, r, j);
-                row = A.rows[r];
-                live = j < row.steps;
+                row = rows[r];
+                live = j < steps(row);
             }
             if (live) {
-                const long long t0 = A.phase + j * A.hop - nWin / 2;
-                const In* __restrict__ x = static_cast<const In*>(A.in) + row.src;
-                for (int i = lane; i < nWin; i += 64) xw[i] = spec_windowed(tile_sample(x, t0 + i, row.len), A.window[i]);
+                const long long t0 = first(row, j);
+                for (int i = lane; i < nWin; i += 64) xw[i] = spec_windowed(sample(row, t0 + i), A.window[i]);
             }
             lpc_wave_sync();
             if (live) {
@@ -355,7 +359,7 @@ KLATT_LPC_UNROLL
             long long g, rr, j;
             int q;
             dense_locate(g0 + lane, 1, A.rowStride, A.start, A.chunk, g, q, rr, j);
-            const bool live = j < A.rows[rr].steps;
+            const bool live = j < steps(rows[rr]);
             double r[kLpcMaxOrder + 1], a[kLpcMaxOrder + 1], k[kLpcMaxOrder + 1], E = 0.0;
             int stages = 0;
 KLATT_LPC_UNROLL
@@ -367,6 +371,14 @@ KLATT_LPC_UNROLL
         tile_store<T>(A.out, g0 * nCols, nInside * nCols, staged, tid);
         __syncthreads();      // every lane has read the staged values before the next group's frames
     }
+}
+
+template <bool F32, typename In = int16_t>
+__global__ void __launch_bounds__(256) klatt_lpc(const LpcArgs A)
+{
+    lpc_rows<F32>(A, A.rows, [](const SpecRow& row) { return row.steps; },
+                  [&](const SpecRow&, long long j) { return A.phase + j * A.hop - A.nWin / 2; },
+                  [&](const SpecRow& row, long long t) { return tile_sample(static_cast<const In*>(A.in) + row.src, t, row.len); });
 }
 
 struct LpcResRow { long long src, len, steps, dst, coeff; };      // a row's input, its steps, its first element in the output, its first STEP in the coefficients

@@ -23,7 +23,8 @@
 //   Refinement      pitch_refine: the parabola through m(tau* - 1 .. tau* + 1), +0.0 at the range's edge (tau* - 1 < 1 or tau* + 1 >
 //                   lagMax), for den <= 0 and for |delta| > 0.5.
 //
-//   klatt_pitch<F32, In>   A 256-lane workgroup takes kPitchGroup = 16 consecutive steps of the OUTPUT (located by dense_locate: a group
+//   klatt_pitch<F32, In>   pitch_rows<F32>, the one body it shares with klatt_stage_pitch (klatt_stage_frames.h), handed the row's own steps,
+//                   the frame's first sample phase + j hop - N / 2 and the reader tile_sample.  A 256-lane workgroup takes kPitchGroup = 16 consecutive steps of the OUTPUT (located by dense_locate: a group
 //                   may end one row and begin the next), each wavefront four of them, one at a time, in its own LDS region and at its own
 //                   pace (lpc_wave_sync: there is no workgroup barrier in the kernel).  Per step:
 //                     1  the frame into LDS by masked coalesced loads, zeros from N to the region's end;
@@ -47,8 +48,8 @@
 //                   and 171 (float64), no scratch: three and two wavefronts a SIMD (docs/KERNELS.md 4.25).
 // Out of scope: normalised cross-correlation and energies; smoothing or tracking across steps (the CMND field serves a tracker of the
 // caller's own); octave-error correction; FFT or MFMA evaluation of the difference (their summation order is not the definition's);
-// decimation inside the export (the chain is exportResampled to 16 kHz, then the signal form); live handles; NodePlayer beyond
-// speechPlayer_node_part.
+// decimation inside the export (the chain is exportResampled to 16 kHz, then the signal form); live handles (their pulls go through the
+// pitch stage of klatt_stage_frames.h); NodePlayer beyond speechPlayer_node_part.
 #pragma once
 
 #include <math.h>
@@ -321,8 +322,10 @@ __device__ __forceinline__ double pitch_lane_value(double v, int k)
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), k), __builtin_amdgcn_readlane(__double2loint(v), k));
 }
 
-template <bool F32, typename In = int16_t>
-__global__ void __launch_bounds__(256) klatt_pitch(const PitchArgs A)
+// The one body of klatt_pitch and of klatt_stage_pitch (klatt_stage_frames.h: the pitch fed chunk by chunk), its two entry points: `rows`,
+// steps(row), first(row, j) and sample(row, t) as lpc_rows' (klatt_lpc.h).
+template <bool F32, class Row, class Steps, class First, class Sample>
+__device__ __forceinline__ void pitch_rows(const PitchArgs& A, const Row* __restrict__ rows, Steps steps, First first, Sample sample)
 {
     using T = typename std::conditional<F32, float, double>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char pitch_lds[];
@@ -342,12 +345,11 @@ __global__ void __launch_bounds__(256) klatt_pitch(const PitchArgs A)
             long long g, r, j;
             int q;
             dense_locate(gs, 1, A.rowStride, A.start, A.chunk, g, q, r, j);
-            const SpecRow row = A.rows[r];
-            if (j < row.steps) {
+            const Row row = rows[r];
+            if (j < steps(row)) {
                 // ---- 1: the frame ----
-                const long long t0 = A.phase + j * A.hop - N / 2;
-                const In* __restrict__ x = static_cast<const In*>(A.in) + row.src;
-                for (int i = lane; i < frameWords; i += 64) xs[i] = i < N ? tile_sample(x, t0 + i, row.len) : 0.0f;
+                const long long t0 = first(row, j);
+                for (int i = lane; i < frameWords; i += 64) xs[i] = i < N ? sample(row, t0 + i) : 0.0f;
                 lpc_wave_sync();
                 // ---- 2: d(1 .. lagMax), four or six lags a lane ----
                 if (pitch_lane_lags(lagMax) == 6) pitch_lane_diff<6>(xs, dm, W, lagMax, lane);
@@ -397,6 +399,14 @@ KLATT_PITCH_UNROLL
             lpc_wave_sync();      // the staged values are read before the next step's
         }
     }
+}
+
+template <bool F32, typename In = int16_t>
+__global__ void __launch_bounds__(256) klatt_pitch(const PitchArgs A)
+{
+    pitch_rows<F32>(A, A.rows, [](const SpecRow& row) { return row.steps; },
+                    [&](const SpecRow&, long long j) { return A.phase + j * A.hop - (A.nWin + A.lagMax) / 2; },
+                    [&](const SpecRow& row, long long t) { return tile_sample(static_cast<const In*>(A.in) + row.src, t, row.len); });
 }
 
 }  // namespace klatt

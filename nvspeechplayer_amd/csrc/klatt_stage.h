@@ -4,7 +4,7 @@
 // The definition is in include/speechPlayer_batch.h ("Signal stages").  Nothing per sample is restated here: the resampler's res_locate /
 // res_taps / res_value, the filter's filter_section / filter_finish, the codecs' adpcm_encode and G.711 laws and the reader's tile_x are the
 // functions of klatt_resample.h, klatt_filter.h, klatt_codec.h and klatt_tiles.h, called.  What this header adds is the bookkeeping of ALL
-// five kinds, compiled for the host and for the device from one source (KLATT_RES_HD) and driven by the kernels, by the entry points and by
+// seven kinds, compiled for the host and for the device from one source (KLATT_RES_HD) and driven by the kernels, by the entry points and by
 // the host models of tests/native/check_stage.cpp and check_stage_window.cpp alike, and the kernels of the resampler, the filter and ADPCM.
 //
 //   Who owns what   here: the kind constants, StageGeometry and stage_row_plan (what a push emits, every kind); the step grid (StageFrames);
@@ -12,6 +12,7 @@
 //                   klatt_stage_history_rows and klatt_stage_clear_rows; the resampler's StageResRow, klatt_stage_resample and
 //                   klatt_stage_history; the filter's and ADPCM's lane state, klatt_stage_filter, klatt_stage_adpcm, klatt_stage_clear.
 //                   klatt_stage_window.h: the convolution's block arithmetic, stage_read_lane / stage_read, the two kinds' kernels.
+//                   klatt_stage_frames.h: the LPC and the pitch stage's kernels, entry points on lpc_rows and pitch_rows.
 //   The counts      A row has consumed N samples and emitted M outputs since its start (its creation, its last end or its last reset).  A
 //                   push of c samples makes N' = N + c.  The resampler, open, emits the outputs m whose taps n0(m) - Z + 1 .. n0(m) + Z,
 //                   n0(m) = floor(m down / up), all lie at or before sample N' - 1:  n0(m) + Z <= N' - 1  <=>  m down < (N' - Z) up  <=>
@@ -22,8 +23,9 @@
 //                   its oldest tap n0(M) - Z + 1 >= N - 2 Z + 1; n0 does not decrease with m, so no later output reaches further back.  The
 //                   samples N - 2 Z + 1 .. N - 1 are 2 Z - 1 = stage_history(Z) values, float32 as tile_x gave them, +0 before sample 0.
 //   The frames      A frame (before, after) of step j is the samples c_j - before .. c_j + after around its centre c_j = phase + j hop
-//                   (stage_frame_centre).  The spectrogram's frame is (nFft / 2, nFft / 2 - 1); LPC's (floor(nWin / 2), nWin - 1 -
-//                   floor(nWin / 2)) and YIN's fit the same bookkeeping.  Open, the steps emitted after N samples are those whose whole
+//                   (stage_frame_centre).  The spectrogram's frame is (nFft / 2, nFft / 2 - 1) (stage_spec_frames); LPC's is
+//                   (floor(nWin / 2), nWin - 1 - floor(nWin / 2)) (stage_lpc_frames) and YIN's the same of its nWin + lagMax samples
+//                   (stage_pitch_frames), as lpc_host and pitch_host place a frame's first sample at c_j - floor(n / 2).  Open, the steps emitted after N samples are those whose whole
 //                   frame lies at or before sample N - 1:  c_j + after <= N - 1  <=>  j <= (N - after - 1 - phase) / hop, so
 //                   E_open(N) = 0 where N - after - 1 - phase < 0 and floor((N - after - 1 - phase) / hop) + 1 otherwise.  Ended, the
 //                   statement's count ceil((N - phase) / hop) (0 where N <= phase), the samples past N - 1 being +0 as the statement has
@@ -58,8 +60,9 @@
 //                   the state after exactly c samples (c + tail for an ended filter row, which is then stored as +0; val = idx = 0).
 //                   Identity padding sits behind the real sections, so the real sections' states are exact; the padding's are never stored.
 //                   (Their state is uniform, 16 and 2 dwords a row, and updated in place: the flat klatt_stage_clear resets it.)
-//   Out of scope    The LPC, pitch and tempo exports chunk by chunk (a kind is a plan, a line of stage_row_plan and a kernel entry point
-//                   on the history above); saving a stage's state to the host; NodePlayer; a fused kernel for a chain of stages.
+//   Out of scope    The tempo export and the LPC residual chunk by chunk (a sample's frame is the nearest centre: it needs frames still to
+//                   come); a mix stage; saving a stage's state to the host; NodePlayer; a fused kernel for a chain of stages.  (A kind on
+//                   the step grid is a plan, stage_has_frames and a kernel entry point on the history above: klatt_stage_frames.h.)
 #pragma once
 
 #include "klatt_codec.h"
@@ -67,7 +70,7 @@
 namespace klatt {
 
 constexpr long long kStageMaxRows = 1ll << 20;
-constexpr int kStageResample = 0, kStageFilter = 1, kStageCode = 2, kStageConvolve = 3, kStageSpectrogram = 4;
+constexpr int kStageResample = 0, kStageFilter = 1, kStageCode = 2, kStageConvolve = 3, kStageSpectrogram = 4, kStageLpc = 5, kStagePitch = 6;
 constexpr int kStageFilterState = 2 * kFilterMaxSections;      // floats of a filter stage's row: s1, s2 of section j at 2 j, 2 j + 1
 
 // ---- the bookkeeping, for the host and the device ---------------------------------------------------------------------------------------
@@ -110,6 +113,10 @@ KLATT_RES_HD bool stage_history_from_chunk(int j, int H, long long c, long long&
 // A step grid with a frame around every centre
 struct StageFrames { long long before = 0, after = 0, hop = 1, phase = 0; };
 KLATT_RES_HD StageFrames stage_spec_frames(int nFft, long long hop, long long phase) { StageFrames f; f.before = nFft / 2; f.after = nFft / 2 - 1; f.hop = hop; f.phase = phase; return f; }
+// LPC's frame of nWin samples and YIN's of nWin + lagMax around the centre, as lpc_host and pitch_host place them: t0 = c - n / 2
+KLATT_RES_HD StageFrames stage_frames_of(int n, long long hop, long long phase) { StageFrames f; f.before = n / 2; f.after = n - 1 - n / 2; f.hop = hop; f.phase = phase; return f; }
+KLATT_RES_HD StageFrames stage_lpc_frames(int nWin, long long hop, long long phase) { return stage_frames_of(nWin, hop, phase); }
+KLATT_RES_HD StageFrames stage_pitch_frames(int nWin, int lagMax, long long hop, long long phase) { return stage_frames_of(nWin + lagMax, hop, phase); }
 KLATT_RES_HD int stage_frame_history(const StageFrames& f) { return (int)(f.before + f.after); }
 KLATT_RES_HD long long stage_frame_centre(const StageFrames& f, long long j) { return f.phase + j * f.hop; }
 // Steps emitted once N samples are consumed, open (the whole frame at or before sample N - 1) or ended (the statement's count)
@@ -121,10 +128,12 @@ KLATT_RES_HD long long stage_frames_emitted(const StageFrames& f, long long N, b
 }
 
 // What a stage is, as far as the counts go.  Z 0: a resampler at equal rates.  tail: the filter's samples, the convolution's 0 or 1.
-// frames: the spectrogram's.  A convolution row's taps come with the row, as its history + 1.
+// frames: the spectrogram's, LPC's, the pitch's.  A convolution row's taps come with the row, as its history + 1.
 struct StageGeometry { int kind = 0, up = 1, down = 1, Z = 0; long long tail = 0; StageFrames frames; };
+// The kinds on the step grid: their outputs are steps, [step][columns], and a row keeps its frame's before + after samples
+KLATT_RES_HD bool stage_has_frames(int kind) { return kind == kStageSpectrogram || kind == kStageLpc || kind == kStagePitch; }
 // The kinds whose rows keep a history of their most recent samples (a resampler's at equal rates has length 0); the others keep lane state
-KLATT_RES_HD bool stage_keeps_history(int kind) { return kind == kStageResample || kind == kStageConvolve || kind == kStageSpectrogram; }
+KLATT_RES_HD bool stage_keeps_history(int kind) { return kind == kStageResample || kind == kStageConvolve || stage_has_frames(kind); }
 // The outputs of a push of c samples, ended or not, onto a row at (N, M) that keeps H samples of history (read for the convolution, whose
 // H is K - 1, alone); false: c is negative or the row would pass 2^44 samples
 KLATT_RES_HD bool stage_row_plan(const StageGeometry& g, long long H, long long N, long long M, long long c, bool ended, long long& out)
@@ -134,7 +143,7 @@ KLATT_RES_HD bool stage_row_plan(const StageGeometry& g, long long H, long long 
     if (g.kind == kStageResample) out = stage_res_emitted(N + c, g.Z, g.up, g.down, ended) - M;
     else if (g.kind == kStageFilter) out = c + (ended ? g.tail : 0);
     else if (g.kind == kStageConvolve) out = c + (ended && g.tail ? H : 0);
-    else if (g.kind == kStageSpectrogram) out = stage_frames_emitted(g.frames, N + c, ended) - M;
+    else if (stage_has_frames(g.kind)) out = stage_frames_emitted(g.frames, N + c, ended) - M;
     else out = c;
     return true;
 }

@@ -1720,6 +1720,8 @@ def _ready_stream(owner, dev):
 
 # kStageResample, kStageFilter, kStageCode, kStageConvolve, kStageSpectrogram of csrc/klatt_stage.h
 STAGE_KINDS = ["resample", "filter", "code", "convolution", "spectrogram"]
+# kStageLpc, kStagePitch: the kinds on the step grid beside the spectrogram (csrc/klatt_stage_frames.h); kind number len(STAGE_KINDS) + index
+STAGE_FRAME_KINDS = ["lpc", "pitch"]
 STAGE_MAKERS = {"convolution": "convolveStage", "spectrogram": "spectrogramStage"}      # (the others: kind + "Stage")
 STAGE_MAX_ROWS = 1 << 20                          # kStageMaxRows
 STAGE_MAX_HISTORY = 1 << 27                       # kStageMaxHistory: float32 of history per buffer, all rows of a stage together
@@ -1733,10 +1735,15 @@ def check_stage_request(kind, nRows, *args, **kw):
     "code": (codec) through check_codec_request; "convolution": (irs, irOf=None, tail=True) through check_convolve_request, irOf per
     row of the stage; "spectrogram": (nFft=1024, hop=256, phase=0, window=None, bank=None, power=2, log=None, floor=1e-10) through
     check_spectrogram_request -- and, for the last two, the rows' histories (taps - 1 each; nFft - 1 each) within 2^27 samples in all.
-    Raises KeyError (the kind, the codec), ValueError or TypeError.  Returns (kind's number, nRows, what the kind's check returns)."""
-    what = STAGE_MAKERS.get(kind, "%sStage" % kind) if kind in STAGE_KINDS else "stage"
-    if kind not in STAGE_KINDS:
-        raise KeyError("%s: kind %r (%s)" % (what, kind, ", ".join(STAGE_KINDS)))
+    A name of STAGE_FRAME_KINDS likewise -- "lpc": (order=16, nWin=512, hop=256, phase=0, window=None, lagWindow=None,
+    fields=("lpc", "error")) through check_lpc_request; "pitch": (sampleRate, fmin=60.0, fmax=500.0, nWin=1024, hop=256, phase=0,
+    threshold=0.1, fields=("f0", "aperiodicity"), lagMin=None, lagMax=None) through check_pitch_request --, the histories nWin - 1 and
+    nWin + lagMax - 1 a row.  Raises KeyError (the kind, the codec, a field), ValueError or TypeError.  Returns (kind's number, nRows, what
+    the kind's check returns)."""
+    kinds = STAGE_KINDS + STAGE_FRAME_KINDS
+    what = STAGE_MAKERS.get(kind, "%sStage" % kind) if kind in kinds else "stage"
+    if kind not in kinds:
+        raise KeyError("%s: kind %r (%s)" % (what, kind, ", ".join(kinds)))
     if isinstance(nRows, (bool, np.bool_)) or not isinstance(nRows, (int, np.integer)):
         raise TypeError("%s: nRows must be an integer, not %r" % (what, nRows))
     if not 1 <= nRows <= STAGE_MAX_ROWS:
@@ -1762,20 +1769,32 @@ def check_stage_request(kind, nRows, *args, **kw):
             if (got[0] - 1) * nRows > STAGE_MAX_HISTORY:
                 raise ValueError("%s: the rows' histories take %d samples in all (at most 2^27)" % (what, (got[0] - 1) * nRows))
             return got
+    elif kind == "lpc":
+        def plan(order=16, nWin=512, hop=256, phase=0, window=None, lagWindow=None, fields=("lpc", "error")):
+            got = check_lpc_request(order, nWin, hop, phase, window, lagWindow, fields, None, what)
+            if (got[1] - 1) * nRows > STAGE_MAX_HISTORY:
+                raise ValueError("%s: the rows' histories take %d samples in all (at most 2^27)" % (what, (got[1] - 1) * nRows))
+            return got
+    elif kind == "pitch":
+        def plan(sampleRate, fmin=60.0, fmax=500.0, nWin=1024, hop=256, phase=0, threshold=0.1, fields=("f0", "aperiodicity"), lagMin=None, lagMax=None):
+            got = check_pitch_request(sampleRate, fmin, fmax, lagMin, lagMax, nWin, hop, phase, threshold, fields, None, what)
+            if (got[1] + got[3] - 1) * nRows > STAGE_MAX_HISTORY:
+                raise ValueError("%s: the rows' histories take %d samples in all (at most 2^27)" % (what, (got[1] + got[3] - 1) * nRows))
+            return got
     else:
         def plan(codec):
             return check_codec_request(codec, True, True, None, what)
-    return STAGE_KINDS.index(kind), nRows, plan(*args, **kw)
+    return kinds.index(kind), nRows, plan(*args, **kw)
 
 
 def check_stage_push(kind, nRows, signal, end=None, dtype=None, codes=False, decoded=True, device=None, what="SignalStage.push"):
     """The argument checks of SignalStage.push that need no GPU: signal as check_signal_request's, of exactly nRows rows; end None, a bool
-    or nRows bools; dtype as the kind's export takes it (None: float32, a code stage's int16; a spectrogram stage takes torch.float32 or
-    torch.float64); codes and decoded bools that only a code stage takes otherwise than (False, True), not both False.  Raises ValueError
+    or nRows bools; dtype as the kind's export takes it (None: float32, a code stage's int16; a spectrogram, lpc or pitch stage takes
+    torch.float32 or torch.float64); codes and decoded bools that only a code stage takes otherwise than (False, True), not both False.  Raises ValueError
     or TypeError.  Returns (check_signal_request's answer, end: uint8 [nRows] or None, the output format: 0 int16, 1 float32 -- a
     spectrogram stage's: 0 float64, 1 float32 --, codes, decoded)."""
-    if kind not in STAGE_KINDS:
-        raise KeyError("%s: kind %r (%s)" % (what, kind, ", ".join(STAGE_KINDS)))
+    if kind not in STAGE_KINDS + STAGE_FRAME_KINDS:
+        raise KeyError("%s: kind %r (%s)" % (what, kind, ", ".join(STAGE_KINDS + STAGE_FRAME_KINDS)))
     sig = check_signal_request(signal, device, what)
     if sig[2] != nRows:
         raise ValueError("%s: a chunk of %d rows for a stage of %d" % (what, sig[2], nRows))
@@ -1796,7 +1815,7 @@ def check_stage_push(kind, nRows, signal, end=None, dtype=None, codes=False, dec
     if kind != "code":
         if codes or not decoded:
             raise ValueError("%s: codes and decoded belong to a code stage" % what)
-        fmt = _check_dtype(what, dtype, *_float_types()) if kind == "spectrogram" else _sample_format(dtype, what)
+        fmt = _check_dtype(what, dtype, *_float_types()) if kind == "spectrogram" or kind in STAGE_FRAME_KINDS else _sample_format(dtype, what)
     else:
         if not codes and not decoded:
             raise ValueError("%s: codes, decoded or both" % what)
@@ -1819,15 +1838,29 @@ def spectrogramEmitted(consumed, nFft=1024, hop=256, phase=0, ended=False):
     return _answer(_native.load().speechPlayer_spectrogramEmitted(int(consumed), int(nFft), int(hop), int(phase), 1 if ended else 0), error=ValueError)
 
 
-class SignalStage(object):
-    """The per-row state of one sequential export -- the resampler, the biquad filter, a codec, the convolution or the spectrogram -- on a
-    BatchPlayer's device, fed chunk by chunk (include/speechPlayer_batch.h, "Signal stages" and "Signal stages that keep a window"): what a
-    live handle's pulls go through.  Made by BatchPlayer.resampleStage, filterStage, codeStage, convolveStage and spectrogramStage; freed
-    by close() or with the player."""
+def lpcEmitted(consumed, nWin=512, hop=256, phase=0, ended=False):
+    """The steps an LPC stage has emitted for a row after `consumed` samples, open or ended (speechPlayer_lpcEmitted; no GPU): open, the
+    steps j whose whole frame lies at or before the last sample consumed, phase + j * hop - nWin // 2 + nWin - 1 <= consumed - 1; ended,
+    ceil((consumed - phase) / hop), pcmLpc's count.  The difference of two is what a push emits."""
+    return _answer(_native.load().speechPlayer_lpcEmitted(int(consumed), int(nWin), int(hop), int(phase), 1 if ended else 0), error=ValueError)
 
-    def __init__(self, player, kind, nRows, handle, bands=None):
+
+def pitchEmitted(consumed, nWin=1024, lagMax=368, hop=256, phase=0, ended=False):
+    """The steps a pitch stage has emitted for a row after `consumed` samples, open or ended (speechPlayer_pitchEmitted; no GPU): as
+    lpcEmitted with the frame of nWin + lagMax samples (lagMax 368: 60 Hz at 22050 Hz, pitchLags); ended, pcmPitch's count."""
+    return _answer(_native.load().speechPlayer_pitchEmitted(int(consumed), int(nWin), int(lagMax), int(hop), int(phase), 1 if ended else 0), error=ValueError)
+
+
+class SignalStage(object):
+    """The per-row state of one sequential export -- the resampler, the biquad filter, a codec, the convolution, the spectrogram, the LPC
+    analysis or the pitch -- on a BatchPlayer's device, fed chunk by chunk (include/speechPlayer_batch.h, "Signal stages", "Signal stages
+    that keep a window" and "Signal stages on the step grid"): what a live handle's pulls go through.  Made by BatchPlayer.resampleStage,
+    filterStage, codeStage, convolveStage, spectrogramStage, lpcStage and pitchStage; freed by close() or with the player."""
+
+    def __init__(self, player, kind, nRows, handle, bands=None, columns=None):
         self._bp, self.kind, self.nRows, self._h = player, kind, nRows, handle
         self.bands = bands      # a spectrogram stage's values per step
+        self.columns = bands if columns is None else columns      # the values per step of any kind on the step grid
         self._dll = player._dll
 
     def _handle(self):
@@ -1854,8 +1887,9 @@ class SignalStage(object):
         torch.int16; padded [nRows, most] with +0 past each row's outputs, or packed with the nRows + 1 offsets --; a code stage
         -> (decoded, lengths), (decoded, codes, lengths) or (codes, lengths) as codedTensor, dtype torch.int16 by default; a
         spectrogram stage -> (tensor [nRows, most steps, bands], steps) or, packed, ([total steps, bands], the nRows + 1 offsets), dtype
-        torch.float32 (default) or torch.float64, and takes neither codes nor decoded.  The outputs of a row's pushes, concatenated, are
-        bit for bit signalResample / signalFilter / signalCode / signalConvolve of its chunks concatenated, and signalSpectrogram's (its
+        torch.float32 (default) or torch.float64, and takes neither codes nor decoded; an lpc or pitch stage likewise, -> (tensor [nRows,
+        most steps, columns], steps) or the packed form.  The outputs of a row's pushes, concatenated, are bit for bit signalResample /
+        signalFilter / signalCode / signalConvolve / signalLpc / signalPitch of its chunks concatenated, and signalSpectrogram's (its
         linear values bit for bit, a logarithm's within the spectrogram export's bar)."""
         import torch
         h, dev = self._handle(), self._bp.device
@@ -1872,8 +1906,8 @@ class SignalStage(object):
         record = np.zeros(1, _signalDtype)
         record["data"], record["format"], record["nRows"], record["rowStride"], record["extent"] = tensor.data_ptr(), inFormat, rows, stride, extent.ctypes.data
         name = "cuda:%d" % dev
-        if self.kind == "spectrogram":
-            shape, low = shape + (self.bands,), torch.float64
+        if self.kind == "spectrogram" or self.kind in STAGE_FRAME_KINDS:
+            shape, low = shape + (self.columns,), torch.float64
         else:
             low = torch.int16
         d = torch.empty(shape, dtype=torch.float32 if fmt else low, device=name) if decoded else None
@@ -1934,22 +1968,37 @@ class SignalStage(object):
 class SignalChain(object):
     """Stages one behind the other: push feeds each stage's (tensor, lengths) pair to the next as its chunk, and `end` travels with it --
     pcm, produced = group.pullTensor(8192); y = chain.push((pcm, produced)).  A code stage or a spectrogram stage comes last: what it
-    gives is not a signal."""
+    gives is not a signal, and so does an lpc or a pitch stage.  The last element may be a tuple or a list of such terminal stages, a fan:
+    SignalChain([filterStage, resampleStage, (lpcStage, pitchStage, codeStage)]) feeds the chunk that arrives there to each of them."""
 
     def __init__(self, stages):
-        self.stages = list(stages)
+        stages = list(stages)
+        if any(isinstance(s, (tuple, list)) for s in stages[:-1]):
+            raise ValueError("SignalChain: a fan of stages comes last")
+        self.fan = None
+        if stages and isinstance(stages[-1], (tuple, list)):
+            self.fan = list(stages.pop())
+            if not self.fan:
+                raise TypeError("SignalChain: a fan holds one stage at least")
+        self.stages = stages + (self.fan or [])
         if not self.stages or not all(isinstance(s, SignalStage) for s in self.stages):
             raise TypeError("SignalChain: a list of SignalStage objects, at least one")
-        if any(s.kind == "code" for s in self.stages[:-1]):
-            raise ValueError("SignalChain: a code stage comes last")
-        if any(s.kind == "spectrogram" for s in self.stages[:-1]):
-            raise ValueError("SignalChain: a spectrogram stage comes last")
+        for kind in ("code", "spectrogram") + tuple(STAGE_FRAME_KINDS):
+            if any(s.kind == kind for s in stages[:-1 if self.fan is None else len(stages)]):
+                raise ValueError("SignalChain: %s stage comes last" % ("an lpc" if kind == "lpc" else "a " + kind))
         if len({s.nRows for s in self.stages}) != 1:
             raise ValueError("SignalChain: the stages have %s rows" % sorted({s.nRows for s in self.stages}))
 
     def push(self, signal, end=None, **last):
         """The chunk through every stage; the keywords (dtype, padded, codes, decoded) are the last stage's push's, the stages between
-        hand on float32 padded rows."""
+        hand on float32 padded rows.  With a fan at the end: -> a tuple of its stages' results, in order, each with its defaults (no
+        keywords)."""
+        if self.fan is not None:
+            if last:
+                raise TypeError("SignalChain.push: a fan's stages take their defaults, not %s" % ", ".join(sorted(last)))
+            for s in self.stages[:len(self.stages) - len(self.fan)]:
+                signal = s.push(signal, end)
+            return tuple(s.push(signal, end) for s in self.fan)
         for s in self.stages[:-1]:
             signal = s.push(signal, end)
         return self.stages[-1].push(signal, end, **last)
@@ -2808,10 +2857,25 @@ class BatchPlayer(object):
     def deviceOffset(self, u):
         return self._dll.speechPlayer_batch_deviceOffset(self._h, u)
 
-    def _stage(self, kind, nRows, handle, bands=None):
+    def _stage(self, kind, nRows, handle, bands=None, columns=None):
         if not handle:
             raise RuntimeError("%s failed: %s" % (STAGE_MAKERS.get(kind, "%sStage" % kind), _native.last_error()))
-        return SignalStage(self, kind, nRows, handle, bands)
+        return SignalStage(self, kind, nRows, handle, bands, columns)
+
+    def lpcStage(self, nRows, order=16, nWin=512, hop=256, phase=0, window=None, lagWindow=None, fields=("lpc", "error")):
+        """A SignalStage of nRows rows that takes the linear-prediction analysis chunk by chunk (speechPlayer_batch_stageLpc): lpcTensor's
+        arguments, with the last nWin - 1 samples of every row kept between pushes; a push emits the steps whose whole frame has come in
+        (lpcEmitted), an ended row's the rest of the definition's.  Its output is not a signal: it ends a SignalChain."""
+        _, nRows, (order, nWin, hop, phase, window, lagWindow, bits, cols, _) = check_stage_request("lpc", nRows, order, nWin, hop, phase, window, lagWindow, fields)
+        return self._stage("lpc", nRows, self._dll.speechPlayer_batch_stageLpc(self._h, nRows, order, nWin, hop, phase, _ptr(window), _ptr(lagWindow), bits), columns=cols)
+
+    def pitchStage(self, nRows, sampleRate, fmin=60.0, fmax=500.0, nWin=1024, hop=256, phase=0, threshold=0.1, fields=("f0", "aperiodicity"), lagMin=None, lagMax=None):
+        """A SignalStage of nRows rows that estimates the pitch (YIN) chunk by chunk (speechPlayer_batch_stagePitch): pitchTensor's
+        arguments for a signal at sampleRate, with the last nWin + lagMax - 1 samples of every row kept between pushes; a push emits the
+        steps whose whole frame has come in (pitchEmitted), an ended row's the rest of the definition's.  It ends a SignalChain."""
+        _, nRows, (sampleRate, nWin, lagMin, lagMax, threshold, hop, phase, bits, cols, _) = check_stage_request(
+            "pitch", nRows, sampleRate, fmin, fmax, nWin, hop, phase, threshold, fields, lagMin, lagMax)
+        return self._stage("pitch", nRows, self._dll.speechPlayer_batch_stagePitch(self._h, nRows, sampleRate, nWin, lagMin, lagMax, threshold, hop, phase, bits), columns=cols)
 
     def resampleStage(self, nRows, srcRate, rate, zeros=6, rolloff=0.99, window="hann", beta=None):
         """A SignalStage of nRows rows that resamples from srcRate to rate Hz chunk by chunk (speechPlayer_batch_stageResample):

@@ -2,7 +2,9 @@
 csrc/klatt_stage_window.h) beside the whole-row exports of a signal on the same tensor in the same run, alternating the two: one push of
 1024 rows x 8192 float32 samples at 22050 -> 16000 against resampledTensor(signal=), the same through the four-section telephone band
 against filteredTensor(signal=), through a 4096-tap response against convolvedTensor(signal=) and into a 1024-point, 80-band mel
-spectrogram against spectrogramTensor(signal=), and the single-row 8192-sample push a one-stream caller pays, per kind; then, --long, 64
+spectrogram against spectrogramTensor(signal=), and -- --families lpc,pitch; csrc/klatt_stage_frames.h -- into the LPC analysis (order 16,
+512 / 256) against lpcTensor(signal=) and the pitch (1024 / 256, lags 44 .. 368) against pitchTensor(signal=), and the single-row
+8192-sample push a one-stream caller pays, per kind; then, --long, 64
 rows through a 65536-tap response, where a push copies 65535 float32 of history per row, and, --short, 16384 rows x 256 samples through the
 resampler, where the history copy's share of a push is largest.  Two figures per call: `queued`, device events around REPS calls issued back to back, per call --
 what the kernels and the staging copy take once the host runs ahead --, and `alone`, a host clock around one call and a synchronise.
@@ -76,18 +78,28 @@ def main():
         x = torch.from_numpy(rng.uniform(-1.0, 1.0, (rows, SAMPLES)).astype(np.float32)).to("cuda:%d" % dev)
         signal = (x, np.full(rows, SAMPLES, np.int64))
         room, mel = room_response(4096), eng.melFilterbank(22050, 1024, 80)
-        res, fil, cod = bp.resampleStage(rows, 22050, 16000), bp.filterStage(rows, TELEPHONE), bp.codeStage(rows, "adpcm")
-        con, spe = bp.convolveStage(rows, room, tail=False), bp.spectrogramStage(rows, 1024, 256, bank=mel, log="db")
-        every = {"resample": {"resample stage push": lambda: res.push(signal), "resampledTensor(signal=)": lambda: bp.resampledTensor(16000, signal=signal)},
-                 "filter": {"filter stage push": lambda: fil.push(signal), "filteredTensor(signal=)": lambda: bp.filteredTensor(TELEPHONE, signal=signal)},
-                 "adpcm": {"adpcm stage push": lambda: cod.push(signal), "codedTensor(adpcm, signal=)": lambda: bp.codedTensor("adpcm", signal=signal)},
-                 "convolution": {"convolution stage push, 4096 taps": lambda: con.push(signal),
-                                 "convolvedTensor(4096 taps, tail=False, signal=)": lambda: bp.convolvedTensor(room, tail=False, signal=signal)},
-                 "spectrogram": {"spectrogram stage push, 1024 / 256, 80 mel, db": lambda: spe.push(signal),
-                                 "spectrogramTensor(1024 / 256, 80 mel, db, signal=)": lambda: bp.spectrogramTensor(1024, 256, bank=mel, log="db", signal=signal)}}
-        calls = {name: fn for family in families for name, fn in every[family].items() if not (args.exports_only and "stage push" in name)}
+        # family -> (its stage's maker, its push's name, the whole-row export's name and call); a stage is made for the families asked for alone.
+        # lpc: order 16, 512 / 256, lpc + error -- a row's 32 steps are one workgroup of 64; pitch: 1024 + 368 lags / 256 at 22050 Hz, f0 +
+        # aperiodicity -- two workgroups of 16 steps
+        every = {"resample": (lambda: bp.resampleStage(rows, 22050, 16000), "resample stage push", "resampledTensor(signal=)", lambda: bp.resampledTensor(16000, signal=signal)),
+                 "filter": (lambda: bp.filterStage(rows, TELEPHONE), "filter stage push", "filteredTensor(signal=)", lambda: bp.filteredTensor(TELEPHONE, signal=signal)),
+                 "adpcm": (lambda: bp.codeStage(rows, "adpcm"), "adpcm stage push", "codedTensor(adpcm, signal=)", lambda: bp.codedTensor("adpcm", signal=signal)),
+                 "convolution": (lambda: bp.convolveStage(rows, room, tail=False), "convolution stage push, 4096 taps", "convolvedTensor(4096 taps, tail=False, signal=)",
+                                 lambda: bp.convolvedTensor(room, tail=False, signal=signal)),
+                 "spectrogram": (lambda: bp.spectrogramStage(rows, 1024, 256, bank=mel, log="db"), "spectrogram stage push, 1024 / 256, 80 mel, db",
+                                 "spectrogramTensor(1024 / 256, 80 mel, db, signal=)", lambda: bp.spectrogramTensor(1024, 256, bank=mel, log="db", signal=signal)),
+                 "lpc": (lambda: bp.lpcStage(rows), "lpc stage push, order 16, 512 / 256", "lpcTensor(order 16, 512 / 256, signal=)", lambda: bp.lpcTensor(signal=signal)),
+                 "pitch": (lambda: bp.pitchStage(rows, 22050), "pitch stage push, 1024 / 256, lags 44 .. 368", "pitchTensor(1024 / 256, lags 44 .. 368, signal=)",
+                           lambda: bp.pitchTensor(signal=signal, sampleRate=22050))}
+        stages, calls = [], {}
+        for family in families:
+            make, push_name, export_name, export = every[family]
+            if not args.exports_only:
+                stages.append(make())
+                calls[push_name] = (lambda s: lambda: s.push(signal))(stages[-1])
+            calls[export_name] = export
         result["%d rows x %d float32" % (rows, SAMPLES)] = measure(calls, dev)
-        for s in (res, fil, cod, con, spe):
+        for s in stages:
             s.close()
     if args.long:      # the history copy at its largest: 65535 float32 per row and push beside 8192 x 65536 taps of arithmetic per row
         rows = 64
