@@ -11,6 +11,20 @@
  *
  * Plain C: host pointers and sizes only.  All functions return 0 on success and a
  * negative value on failure unless stated; speechPlayer_lastError() describes it.
+ *
+ * Threads.  DISTINCT batch objects, node objects, signal stages and live handles may be used from distinct threads at the
+ * same time, in any mix of calls: each batch has streams, scratch and cached tables of its own, and what the process shares
+ * -- the host worker pool the set calls plan on, the registries of stages and live handles -- is locked inside.  ONE batch
+ * object (and one node object) is used by one thread at a time; it may be handed from thread to thread -- a set call on a
+ * worker thread, the launch and the reads on another, as bench.py's `pipeline` extra does -- with the order kept by the
+ * caller (the hand-over must synchronise the two threads: a semaphore, an event, a join).  A signal stage belongs to the
+ * batch object it was made on and is used under the same rule, together with it; a stage handle that was freed is refused
+ * by whichever thread presents it, and so long as the caller makes no new stage in between it names no other stage.
+ * speechPlayer_lastError() and speechPlayer_lastErrorCode() are per calling thread: the code is 0 after that thread's
+ * last call succeeded, the message is that of the thread's last failure (empty for a thread that never had one) -- no
+ * thread sees another's.  The global option "plan_hash_bits" is read once per set call (and once per planning view):
+ * changing it beside a set call in flight changes nothing of that call.
+ * tests/test_concurrent_players_host.py and tests/test_gpu_concurrent_players.py hold exactly this.
  */
 #ifndef NVSP_AMD_SPEECHPLAYER_BATCH_H
 #define NVSP_AMD_SPEECHPLAYER_BATCH_H
