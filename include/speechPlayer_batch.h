@@ -1094,7 +1094,8 @@ long long speechPlayer_pitchEmitted(long long consumed, int nWin, int lagMax, lo
  * Bits are unspecified for non-finite coefficients, as for samples outside the signal bound; no value ever steers an address.
  * The definition is the function bodies of csrc/klatt_lpc.h, which the host and the device compile from one source.  Over the pool the
  * result is a function of the batch's PCM: it depends on the mode and needs a synthesis launch.
- * Out of scope: line spectral frequencies; Burg and covariance methods; the recursive synthesis filter 1 / A(z); order above 32;
+ * Out of scope: line spectral frequencies; Burg and covariance methods; the recursive synthesis filter 1 / A(z) inside these exports (it is
+ * an export of its own: "LPC synthesis", below); order above 32;
  * pre-emphasis inside the export (the chain is exportFiltered with a pre-emphasis section, then the signal form); live handles through
  * this export (the last nWin - 1 samples would have to persist across pulls: "Signal stages on the step grid", above, keep them for the
  * analysis -- speechPlayer_batch_stageLpc; the residual has no stage); NodePlayer beyond speechPlayer_node_part.
@@ -1149,6 +1150,55 @@ long long speechPlayer_batch_exportLpcResidual(speechPlayer_batch_t batch, const
 	long long rowStride, void* stream);
 long long speechPlayer_batch_exportLpcResidualOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
 	int order, long long hop, long long phase, const void* deviceCoeff, int coeffFormat, int coeffCols, int col0, long long coeffStride, int what,
+	void* deviceOut, int format, long long rowStride, void* stream);
+/*
+ * LPC synthesis: a row of excitation samples through the recursive all-pole filter 1 / A(z) of its frames' prediction coefficients -- the
+ * inverse of the inverse filter above, and the decoder half of what the other two exports give: analysis-synthesis with changed
+ * coefficients (bandwidth expansion, quantised reflection coefficients, another speaker's envelope), cross-synthesis, x = e + p where e is
+ * not the exact residual.  A row of L excitation samples e(0 .. L-1) is read as the other exports read a row: an int16 s is
+ * (float)s / 32767.0f, a float32 is taken as it is; the row is the pool's utterance or a signal's row.  The coefficients come from a
+ * DEVICE tensor [row][step][coeffCols] (format 0 float64, 1 float32 widened exactly), a_1 .. a_order at columns col0 .. col0 + order - 1,
+ * coeffStride in steps (0 packed, else padded), row i of the tensor belonging to the i-th chosen row: exactly as
+ * speechPlayer_batch_exportLpcResidual reads them, for the same hop and phase.  order lies in 1 .. 32, one per call.
+ *   frame of a sample   lpc_frame_of(t, hop, phase, steps): j = min(steps - 1, (max(t - phase, 0) + floor(hop / 2)) / hop), the nearest
+ *             centre, ties upward.  A row without steps uses coefficients +0
+ *   recursion y(t) = +0 for t < 0.  For t = 0 .. L-1 ascending: s = (double)e(t); for m = 1 .. order ascending:
+ *             s = fma(-a_m, (double)y(t - m), s) -- the negation is exact, the fma explicit --; y(t) = (float)s
+ *   history   the history is the float32 y, never the int16 of the output
+ *   bounds    the loops run behind m <= order tests: no row is padded with zero coefficients, because fma(-0.0, y, s) can change the sign
+ *             of a zero
+ *   output    L samples per row; format 1 float32 y(t), format 0 int16 by the resampler's conversion of y(t); padded (rowStride, +0 past
+ *             a row's end) or packed, so (tensor, lengths) is a signal for the next stage
+ * Unstable coefficients cannot be refused, since they live on the device: once a value of a row is not finite, that row's later bits are
+ * unspecified.  It faults nothing and no value steers an address.
+ * The definition is the function bodies of csrc/klatt_lpcsynth.h, which the host and the device compile from one source: one wavefront per
+ * 64 rows, a lane per row, the history a register ring of 8, 16 or 32 slots (the smallest >= order).
+ * Out of scope: initial conditions in or out; a pole-zero or weighting filter A(z/g1)/A(z/g2); order above 32; a live stage (a stage takes
+ * one input; this takes two); NodePlayer; time-parallel formulations (they cannot meet the sequential statement's bits).
+ *
+ * Host only, touch no device: the recursion above on `length` samples with the coefficients a HOST array double[steps][order]; out
+ * float[length] (format 1) or int16[length] (format 0) of `capacity` elements.  Return length; -1 on an unknown inFormat, length < 0 or
+ * above 2^44, a NULL input with length > 0, hop <= 0, phase < 0, order outside 1 .. 32, an unknown format, NULL coefficients with steps > 0,
+ * a NULL out with length > 0, a capacity below length, and (signalLpcSynthesis) a float32 sample outside the signal bound. */
+long long speechPlayer_pcmLpcSynthesis(const sample* pcm, long long length, int order, long long hop, long long phase, const double* coeff, int format,
+	void* out, long long capacity);
+long long speechPlayer_signalLpcSynthesis(const void* x, int inFormat, long long length, int order, long long hop, long long phase, const double* coeff,
+	int format, void* out, long long capacity);
+/* Host only, touches no device: a_1 .. a_order from the reflection coefficients k_1 .. k_order by the step-up recursion, which is exactly
+ * the Levinson-Durbin recursion's update: for i = 1 .. order: a'[j] = fma(k_i, a[i-j], a[j]) for j = 1 .. i-1, all from the old a, then
+ * a[i] = k_i.  |k_i| < 1 for every i gives a stable 1 / A(z): this is how a caller gets stable coefficients out of modified or quantised
+ * reflection coefficients.  Returns order; -1 on order outside 1 .. 32 or a NULL argument. */
+long long speechPlayer_lpcFromReflection(const double* k, int order, double* a);
+/* The synthesis of chosen utterances (exportLpcSynthesis) or of chosen rows of `signal` (exportLpcSynthesisOf), the coefficients read from
+ * deviceCoeff as described above.  The arguments are speechPlayer_batch_exportLpcResidual / exportLpcResidualOf's without `what`;
+ * utterances / rows, the rows' forms (rowStride in samples), the return value, the device-memory, alignment and overlap checks, the
+ * sixteen-in-flight rule and the ordering by events are theirs; the caller orders whatever wrote the coefficients before the export on
+ * `stream`.  Refused with SPEECHPLAYER_ERR_ARGUMENT and nothing written: what they refuse, `what` apart. */
+long long speechPlayer_batch_exportLpcSynthesis(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int order, long long hop,
+	long long phase, const void* deviceCoeff, int coeffFormat, int coeffCols, int col0, long long coeffStride, void* deviceOut, int format,
+	long long rowStride, void* stream);
+long long speechPlayer_batch_exportLpcSynthesisOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows,
+	int order, long long hop, long long phase, const void* deviceCoeff, int coeffFormat, int coeffCols, int col0, long long coeffStride,
 	void* deviceOut, int format, long long rowStride, void* stream);
 /*
  * Pitch ESTIMATED FROM THE SIGNAL (YIN) of a batch's PCM, or of a signal's rows, on the step grid of the other exports: per analysis frame

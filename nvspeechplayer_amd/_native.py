@@ -73,6 +73,8 @@ EXPORTS = [
     "speechPlayer_pcmCode", "speechPlayer_signalCode", "speechPlayer_codecDecode", "speechPlayer_batch_exportCoded", "speechPlayer_batch_exportCodedOf",
     "speechPlayer_lpcFromAutocorrelation", "speechPlayer_pcmLpc", "speechPlayer_signalLpc", "speechPlayer_pcmLpcResidual", "speechPlayer_signalLpcResidual",
     "speechPlayer_batch_exportLpc", "speechPlayer_batch_exportLpcOf", "speechPlayer_batch_exportLpcResidual", "speechPlayer_batch_exportLpcResidualOf",
+    "speechPlayer_pcmLpcSynthesis", "speechPlayer_signalLpcSynthesis", "speechPlayer_lpcFromReflection", "speechPlayer_batch_exportLpcSynthesis",
+    "speechPlayer_batch_exportLpcSynthesisOf",
     "speechPlayer_pcmPitch", "speechPlayer_signalPitch", "speechPlayer_batch_exportPitch", "speechPlayer_batch_exportPitchOf",
     "speechPlayer_tempoLength", "speechPlayer_tempoFrames", "speechPlayer_pcmTempo", "speechPlayer_signalTempo",
     "speechPlayer_batch_exportTempoPositions", "speechPlayer_batch_exportTempoPositionsOf", "speechPlayer_batch_exportTempo", "speechPlayer_batch_exportTempoOf",
@@ -468,6 +470,16 @@ def load():
     L.speechPlayer_batch_exportLpcResidual.argtypes = [vp, vp, i64, i32, i64, i64, vp, i32, i32, i32, i64, i32, vp, i32, i64, vp]
     L.speechPlayer_batch_exportLpcResidualOf.restype = i64
     L.speechPlayer_batch_exportLpcResidualOf.argtypes = [vp, vp, vp, i64, i32, i64, i64, vp, i32, i32, i32, i64, i32, vp, i32, i64, vp]
+    L.speechPlayer_pcmLpcSynthesis.restype = i64
+    L.speechPlayer_pcmLpcSynthesis.argtypes = [vp, i64, i32, i64, i64, vp, i32, vp, i64]
+    L.speechPlayer_signalLpcSynthesis.restype = i64
+    L.speechPlayer_signalLpcSynthesis.argtypes = [vp, i32, i64, i32, i64, i64, vp, i32, vp, i64]
+    L.speechPlayer_lpcFromReflection.restype = i64
+    L.speechPlayer_lpcFromReflection.argtypes = [vp, i32, vp]
+    L.speechPlayer_batch_exportLpcSynthesis.restype = i64
+    L.speechPlayer_batch_exportLpcSynthesis.argtypes = [vp, vp, i64, i32, i64, i64, vp, i32, i32, i32, i64, vp, i32, i64, vp]
+    L.speechPlayer_batch_exportLpcSynthesisOf.restype = i64
+    L.speechPlayer_batch_exportLpcSynthesisOf.argtypes = [vp, vp, vp, i64, i32, i64, i64, vp, i32, i32, i32, i64, vp, i32, i64, vp]
     f64 = ctypes.c_double
     L.speechPlayer_pcmPitch.restype = i64
     L.speechPlayer_pcmPitch.argtypes = [vp, i64, i32, i32, i32, i32, f64, i64, i64, i32, vp]

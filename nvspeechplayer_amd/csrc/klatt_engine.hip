@@ -28,6 +28,7 @@
 #include "klatt_stage.h"
 #include "klatt_stage_window.h"
 #include "klatt_lpc.h"
+#include "klatt_lpcsynth.h"
 #include "klatt_pitch.h"
 #include "klatt_stage_frames.h"
 #include "klatt_tempo.h"
@@ -6512,6 +6513,159 @@ long long speechPlayer_batch_exportLpcResidualOf(speechPlayer_batch_t batch, con
     if (refuse_timing_only("speechPlayer_batch_exportLpcResidualOf")) return -1;
     return lpc_residual_export("exportLpcResidualOf", batch, true, signal, rows, nRows, order, hop, phase, deviceCoeff, coeffFormat, coeffCols, col0, coeffStride, what,
                                deviceOut, format, rowStride, stream);
+}
+
+// ---- LPC synthesis: an excitation through 1 / A(z) (klatt_lpcsynth.h) ---------------------------------------------------------------------------
+static_assert(sizeof(LpcSynthRow) == sizeof(FilterRow) + 16 && sizeof(LpcSynthRow) % 8 == 0, "a row is an array of 8-byte words: a FilterRow, its first coefficient step, its steps");
+
+// Host only, touches no device: the step-up recursion, lpc_levinson's update of a[] with the reflection coefficients given.
+long long speechPlayer_lpcFromReflection(const double* k, int order, double* a)
+{
+    begin_call();
+    const char* what = "lpcFromReflection";
+    if (order < 1 || order > kLpcMaxOrder) { set_error("%s: order %d (1 .. %d)", what, order, kLpcMaxOrder); return -1; }
+    if (!k || !a) { set_error("%s: no %s (order values)", what, k ? "output" : "reflection coefficients"); return -1; }
+    double kk[kLpcMaxOrder + 1] = {}, aa[kLpcMaxOrder + 1];
+    for (int i = 1; i <= order; ++i) kk[i] = k[i - 1];
+    lpc_step_up(kk, order, aa);
+    for (int i = 1; i <= order; ++i) a[i - 1] = aa[i];
+    return order;
+}
+
+// Host only, touch no device: the definition of include/speechPlayer_batch.h through the functions the kernel is compiled from.
+static long long lpc_synth_statement(const char* what, const void* x, int inFormat, long long length, int order, long long hop, long long phase,
+                                     const double* coeff, int format, void* out, long long capacity)
+{
+    if (signal_host_format(what, inFormat)) return -1;
+    if (length < 0 || length > kResampleMaxLength || hop <= 0 || phase < 0 || (length > 0 && !x)) {
+        set_error("%s: length %lld (0 .. 2^44, with its samples), hop %lld, phase %lld", what, length, hop, phase); return -1;
+    }
+    LpcSynthPlan P;
+    std::string why;
+    if (!lpc_synth_plan(P, order, hop, phase, format, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+    if (align_steps_below(length, P.hop, P.phase) > 0 && !coeff) { set_error("%s: no coefficients ([steps][order] doubles)", what); return -1; }
+    if (length > 0 && !out) { set_error("%s: no output", what); return -1; }
+    if (capacity < length) { set_error("%s: the output takes %lld elements, capacity is %lld", what, length, capacity); return -1; }
+    if (signal_host_values(what, x, inFormat, length)) return -1;
+    if (inFormat) lpc_synth_host(static_cast<const float*>(x), length, order, P.hop, P.phase, coeff, format, out);
+    else lpc_synth_host(static_cast<const int16_t*>(x), length, order, P.hop, P.phase, coeff, format, out);
+    return length;
+}
+
+long long speechPlayer_pcmLpcSynthesis(const sample* pcm, long long length, int order, long long hop, long long phase, const double* coeff, int format, void* out,
+                                       long long capacity)
+{
+    begin_call();
+    return lpc_synth_statement("pcmLpcSynthesis", pcm, 0, length, order, hop, phase, coeff, format, out, capacity);
+}
+
+long long speechPlayer_signalLpcSynthesis(const void* x, int inFormat, long long length, int order, long long hop, long long phase, const double* coeff, int format,
+                                          void* out, long long capacity)
+{
+    begin_call();
+    return lpc_synth_statement("signalLpcSynthesis", x, inFormat, length, order, hop, phase, coeff, format, out, capacity);
+}
+
+// klatt_lpc_synth of a ring, a coefficient format, an input format and an output format
+extern "C++" template <int B>
+static void (*lpc_synth_kernel(int coeffFormat, int inFormat, int format))(LpcSynthArgs)
+{
+    void (*const kernels[2][2][2])(LpcSynthArgs) = {
+        {{klatt_lpc_synth<B, false, int16_t, false>, klatt_lpc_synth<B, true, int16_t, false>}, {klatt_lpc_synth<B, false, float, false>, klatt_lpc_synth<B, true, float, false>}},
+        {{klatt_lpc_synth<B, false, int16_t, true>, klatt_lpc_synth<B, true, int16_t, true>}, {klatt_lpc_synth<B, false, float, true>, klatt_lpc_synth<B, true, float, true>}}};
+    return kernels[coeffFormat][inFormat][format];
+}
+
+// The chosen rows through the recursive filter of their own frames' coefficients (klatt_lpcsynth.h).  The request, the coefficient tensor and
+// its checks are lpc_residual_export's without `what`; the rows go a wavefront per 64 as filtered_export's (the staging block: packed rows |
+// groups), all in one launch.  Nothing is kept on the batch.  ofSignal and `signal` as spectrogram_export's.
+static long long lpc_synth_export(const char* what, speechPlayer_batch_t batch, bool ofSignal, const speechPlayer_signal_t* signal, const long long* utterances,
+                                  long long nUtterances, int order, long long hop, long long phase, const void* coeff, int coeffFormat, int coeffCols, int col0,
+                                  long long coeffStride, void* deviceOut, int format, long long rowStride, void* stream)
+{
+    return batch_entry(what, batch, [&](Batch* b) -> long long {
+        if (tile_request(what, format, rowStride)) return -1;
+        LpcSynthPlan P;
+        std::string why;
+        if (!lpc_synth_plan(P, order, hop, phase, format, why)) { set_error("%s: %s", what, why.c_str()); return -1; }
+        if (coeffFormat != 0 && coeffFormat != 1) { set_error("%s: coefficient format %d (0 float64, 1 float32)", what, coeffFormat); return -1; }
+        if (coeffCols < 1 || coeffCols > (1 << 20) || col0 < 0 || col0 > coeffCols - order) {
+            set_error("%s: coefficients a_1 .. a_%d at columns %d .. %d of %d (1 .. 2^20)", what, order, col0, col0 + order - 1, coeffCols); return -1;
+        }
+        if (coeffStride < 0) { set_error("%s: coeffStride %lld", what, coeffStride); return -1; }
+        SignalPlan sig;
+        ExportInput in{b};
+        if (export_input(b, what, ofSignal, signal, sig, in)) return -1;
+        ExportSelection s;
+        std::vector<LpcSynthRow> rows;
+        long long stepsBefore = 0, mostSteps = 0;
+        if (export_selection(b, what, utterances, nUtterances, false, s, [&](long long i, long long u, long long before) {
+                const long long L = in.len(u), steps = align_steps_below(L, P.hop, P.phase);
+                rows.push_back(lpc_synth_row(in.at(u), L, tile_row_first(i, rowStride, before), tile_row_first(i, coeffStride, stepsBefore), steps));      // (the extent below refuses a stride that wraps)
+                stepsBefore += steps; mostSteps = std::max(mostSteps, steps);
+                return L;
+            }, in.sig)) return -1;
+        if (coeffStride > 0 && coeffStride < mostSteps) { set_error("%s: coeffStride %lld is below the largest step count (%lld)", what, coeffStride, mostSteps); return -1; }
+        // the coefficients' extent, by division before any product (as export_extent's): rows without steps read none
+        const long long coeffLimit = kExportLimit / coeffCols;
+        if (coeffStride > 0 && mostSteps > 0 && s.n > coeffLimit / coeffStride) {
+            set_error("%s: %lld rows of coeffStride %lld steps of %d coefficient columns (at most 2^50 elements)", what, s.n, coeffStride, coeffCols); return -1;
+        }
+        const long long coeffSteps = coeffStride > 0 ? (mostSteps > 0 ? s.n * coeffStride : 0) : stepsBefore;
+        if (coeffSteps > coeffLimit) { set_error("%s: %lld steps of %d coefficient columns (at most 2^50 elements)", what, coeffSteps, coeffCols); return -1; }
+        const long long elements = tile_elements(b, what, s, rowStride, format, deviceOut, &in);
+        if (elements <= 0) return elements;
+        const size_t elSize = format ? sizeof(float) : sizeof(int16_t), cSize = coeffFormat ? sizeof(float) : sizeof(double);
+        const size_t outBytes = (size_t)elements * elSize, coeffBytes = (size_t)coeffSteps * (size_t)coeffCols * cSize;
+        if (coeffBytes) {
+            if (!coeff) { set_error("%s: no coefficients", what); return -1; }
+            const std::string name = std::string(what) + ": coefficients";
+            if (!device_range(coeff, coeffBytes, b->device, cSize, name.c_str())) return -1;
+            const uintptr_t c = reinterpret_cast<uintptr_t>(coeff), o = reinterpret_cast<uintptr_t>(deviceOut);
+            if (c < o + outBytes && o < c + coeffBytes) {
+                set_error("%s: the output (%zu bytes from %p) overlaps the coefficients (%zu bytes from %p)", what, outBytes, deviceOut, coeffBytes, coeff); return -1;
+            }
+        }
+        std::vector<LpcSynthRow> packed;
+        std::vector<FilterGroup> groups;
+        lpc_synth_pack(rows, packed, groups);
+        StageBlock block;
+        const int rowsAt = block.add(packed), groupsAt = block.add(groups);
+        ExportStage stage(b, static_cast<hipStream_t>(stream), block, nullptr, !in.sig, in.sig != nullptr);
+        if (stage.begin()) return -1;
+        LpcSynthArgs A;
+        A.in = in.data; A.rows = stage.device<LpcSynthRow>(rowsAt);
+        A.groups = stage.device<FilterGroup>(groupsAt); A.nGroups = (long long)groups.size();
+        A.rowStride = rowStride; A.out = deviceOut;
+        A.coeff = coeff; A.hop = P.hop; A.phase = P.phase;
+        A.order = order; A.coeffCols = coeffCols; A.col0 = col0;
+        const auto kernel = P.history == 8 ? lpc_synth_kernel<8>(coeffFormat, in.format(), format)
+                          : P.history == 16 ? lpc_synth_kernel<16>(coeffFormat, in.format(), format) : lpc_synth_kernel<32>(coeffFormat, in.format(), format);
+        const unsigned grid = (unsigned)std::min<long long>(A.nGroups, 64ll * b->cus);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFilterLanes), 0, stage.st, A);
+        HIP_TRY(hipGetLastError());
+        if (stage.finish()) return -1;
+        return elements;
+    });
+}
+
+long long speechPlayer_batch_exportLpcSynthesis(speechPlayer_batch_t batch, const long long* utterances, long long nUtterances, int order, long long hop, long long phase,
+                                                const void* deviceCoeff, int coeffFormat, int coeffCols, int col0, long long coeffStride, void* deviceOut, int format,
+                                                long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportLpcSynthesis")) return -1;
+    return lpc_synth_export("exportLpcSynthesis", batch, false, nullptr, utterances, nUtterances, order, hop, phase, deviceCoeff, coeffFormat, coeffCols, col0, coeffStride,
+                            deviceOut, format, rowStride, stream);
+}
+
+// The same of chosen rows of a caller's signal: it reads no pool and needs no synthesis (ExportStage, ofSignal).
+long long speechPlayer_batch_exportLpcSynthesisOf(speechPlayer_batch_t batch, const speechPlayer_signal_t* signal, const long long* rows, long long nRows, int order,
+                                                  long long hop, long long phase, const void* deviceCoeff, int coeffFormat, int coeffCols, int col0, long long coeffStride,
+                                                  void* deviceOut, int format, long long rowStride, void* stream)
+{
+    if (refuse_timing_only("speechPlayer_batch_exportLpcSynthesisOf")) return -1;
+    return lpc_synth_export("exportLpcSynthesisOf", batch, true, signal, rows, nRows, order, hop, phase, deviceCoeff, coeffFormat, coeffCols, col0, coeffStride,
+                            deviceOut, format, rowStride, stream);
 }
 
 // ---- the PCM at another tempo by WSOLA (klatt_tempo.h) ----------------------------------------------------------------------------------------

@@ -40,7 +40,7 @@
 //                   at most kLpcStageRows = 64 (hop >= 17 or so; a row serves hop samples) and read from memory by each lane otherwise
 //                   (hop 1: every sample has a row of its own, staging would share nothing), one output per lane per pass, stored by
 //                   tile_store.
-// Out of scope: line spectral frequencies, Burg and covariance methods, the recursive synthesis filter 1 / A(z), order above 32,
+// Out of scope: line spectral frequencies, Burg and covariance methods, the recursive synthesis filter 1 / A(z) (klatt_lpcsynth.h), order above 32,
 // pre-emphasis inside the export, live handles (their pulls go through the LPC stage of klatt_stage_frames.h; the inverse filter has no
 // stage: a sample's frame is the nearest centre, which may be a frame still to come), NodePlayer.
 #pragma once

@@ -1413,6 +1413,70 @@ def signalLpcResidual(x, coeff, hop=256, phase=0, what="residual", dtype=np.floa
     return _lpc_residual_statement("signalLpcResidual", *_signal_samples(x, "signalLpcResidual"), coeff, hop, phase, what, dtype)
 
 
+LPC_SYNTH_HISTORIES = (8, 16, 32)      # the register rings of csrc/klatt_lpcsynth.h: a request runs in the smallest that holds its order
+
+
+def check_lpc_synthesis_request(order, hop, phase, column, dtype, what="lpcSynthesisTensor"):
+    """The argument checks of BatchPlayer.lpcSynthesisTensor, pcmLpcSynthesis and signalLpcSynthesis that need no GPU: order in 1 .. 32,
+    hop >= 1, phase >= 0, column >= 0 (where a_1 lies in a step's values), dtype None / torch.float32 / np.float32 or torch.int16 /
+    np.int16.  Raises ValueError or TypeError.  Returns (order, hop, phase, column, the format of the samples: 0 int16, 1 float32)."""
+    order = _check_order(order, what)
+    hop, phase = _check_lpc_grid(hop, phase, what)
+    if isinstance(column, (bool, np.bool_)) or not isinstance(column, (int, np.integer)) or column < 0:
+        raise ValueError("%s: column must be an integer >= 0, not %r" % (what, column))
+    return order, hop, phase, int(column), _sample_format(dtype, what)
+
+
+def _lpc_synthesis_statement(name, s, inFormat, coeff, hop, phase, dtype):
+    c = np.ascontiguousarray(_host_array(coeff, np.float64))
+    if c.ndim != 2:
+        raise ValueError("%s: the coefficients must be [steps, order], not %s" % (name, list(c.shape)))
+    order, hop, phase, _, fmt = check_lpc_synthesis_request(c.shape[1], hop, phase, 0, dtype, name)
+    steps = int(_step_counts(len(s), hop, phase))
+    if c.shape[0] != steps:
+        raise ValueError("%s: %d rows of coefficients for %d steps" % (name, c.shape[0], steps))
+    return _row_statement(name, s, inFormat, (order, hop, phase, c.ctypes.data if steps else None, fmt), (len(s),), np.float32 if fmt else np.int16)
+
+
+def pcmLpcSynthesis(pcm, coeff, hop=256, phase=0, dtype=np.float32):
+    """int16 PCM, taken as an excitation, through the recursive filter 1 / A(z) of its frames' coefficients on the host
+    (speechPlayer_pcmLpcSynthesis; no GPU): coeff float64 [steps, order] as pcmLpcResidual's; sample t takes the row of the nearest
+    centre (ties upward).  -> float32 or int16 [len(pcm)]: y(t) = e(t) - sum a_m y(t - m), one binary64 fma chain per sample from
+    y(t) = +0 for t < 0, the history the float32 y."""
+    return _lpc_synthesis_statement("pcmLpcSynthesis", _pcm_samples(pcm, "pcmLpcSynthesis"), None, coeff, hop, phase, dtype)
+
+
+def signalLpcSynthesis(x, coeff, hop=256, phase=0, dtype=np.float32):
+    """pcmLpcSynthesis on a signal's row (speechPlayer_signalLpcSynthesis; no GPU): x as signalSpectrogram's.  The statement
+    BatchPlayer.lpcSynthesisTensor(signal=...) is held to."""
+    return _lpc_synthesis_statement("signalLpcSynthesis", *_signal_samples(x, "signalLpcSynthesis"), coeff, hop, phase, dtype)
+
+
+def lpcFromReflection(k):
+    """The step-up recursion (speechPlayer_lpcFromReflection; no GPU): the reflection coefficients k_1 .. k_order, order = len(k) in
+    1 .. 32 -> a float64 [order]: a_1 .. a_order, bit for bit the `a` lpcFromAutocorrelation gives beside these k.  |k_i| < 1 for every i
+    gives a stable 1 / A(z): quantise or modify the k, not the a."""
+    k = np.ascontiguousarray(_host_array(k, np.float64).reshape(-1))
+    order = _check_order(len(k), "lpcFromReflection")
+    a = np.zeros(order)
+    _answer(_native.load().speechPlayer_lpcFromReflection(k.ctypes.data, order, a.ctypes.data), order)
+    return a
+
+
+def lpcBandwidthExpand(a, gamma):
+    """Bandwidth expansion of prediction coefficients (numpy, no GPU): a float64 [..., order] -> a_j * g_j with g_0 = 1 and
+    g_j = g_(j-1) * gamma in binary64, the poles of 1 / A(z) drawn towards the origin by the factor gamma."""
+    a = _host_array(a, np.float64)
+    gamma = float(gamma)
+    if a.ndim < 1 or not math.isfinite(gamma):
+        raise ValueError("lpcBandwidthExpand: a [..., order] and a finite gamma (%s, %r)" % (list(a.shape), gamma))
+    g, w = 1.0, np.zeros(a.shape[-1])
+    for j in range(a.shape[-1]):
+        g = g * gamma
+        w[j] = g
+    return a * w
+
+
 TEMPO_MIN_WIN = 64               # kTempoMinWin of csrc/klatt_tempo.h
 TEMPO_MAX_WIN = 2048             # kTempoMaxWin
 TEMPO_MAX_SEARCH = 1024          # kTempoMaxSearch
@@ -2474,6 +2538,45 @@ class BatchPlayer(object):
 
         def call(out, stride, numel, stream):
             return export(order, hop, phase, lpc.data_ptr() if lpc.numel() else None, 1 if lpc.dtype == torch.float32 else 0, cols, column, cstride, which, out, fmt,
+                          stride, stream)
+        return self._export_rows(src.lengths, (), torch.float32 if fmt else torch.int16, padded, call)
+
+    def lpcSynthesisTensor(self, lpc, order=16, hop=256, phase=0, column=0, utterances=None, dtype=None, padded=True, signal=None):
+        """The batch's PCM, taken as an excitation, through the recursive filter 1 / A(z) of its frames' prediction coefficients as a
+        torch tensor on the batch's device (speechPlayer_batch_exportLpcSynthesis): -> (pcm, lengths).  lpc, order, hop, phase and column
+        as lpcResidualTensor's: the coefficients lpcTensor returned for the same rows, or the caller's own (lpcBandwidthExpand,
+        lpcFromReflection of quantised reflection coefficients, another row's).  y(t) = e(t) - sum a_m y(t - m) from y(t) = +0 for
+        t < 0, one binary64 fma chain per sample; the history is the float32 y.  utterances, padded and the (pcm, lengths) pair as
+        pcmTensor's; dtype torch.float32 (default) or torch.int16 (clipped, rounded to nearest even).  pcmLpcSynthesis is the same
+        definition on the host, which the device equals bit for bit while the row's values are finite; unstable coefficients are not
+        refused.  The usual excitation is a signal: lpcResidualTensor's result, changed or not.
+        signal: as lpcTensor's (speechPlayer_batch_exportLpcSynthesisOf; signalLpcSynthesis is the host's statement)."""
+        import torch
+        order, hop, phase, column, fmt = check_lpc_synthesis_request(order, hop, phase, column, dtype)
+        src = self._rows("lpcSynthesisTensor", signal, utterances)
+        export = self._entry("LpcSynthesis", src)
+        steps = _step_counts(src.lengths, hop, phase)
+        if not isinstance(lpc, torch.Tensor) or lpc.dtype not in (torch.float32, torch.float64) or lpc.dim() not in (2, 3) or not lpc.is_contiguous():
+            raise TypeError("lpcSynthesisTensor: the coefficients must be a contiguous torch.float32 or torch.float64 tensor, [rows, steps, values] or [steps, values]")
+        if not lpc.is_cuda or lpc.device.index != self.device:
+            raise ValueError("lpcSynthesisTensor: the coefficients must be on the batch's device, cuda:%d, not %s" % (self.device, lpc.device))
+        cols = int(lpc.shape[-1])
+        if column + order > cols:
+            raise ValueError("lpcSynthesisTensor: a_1 .. a_%d at columns %d .. %d of %d" % (order, column, column + order - 1, cols))
+        most = int(steps.max()) if len(steps) else 0
+        if lpc.dim() == 3:
+            if lpc.shape[0] != src.n or lpc.shape[1] < most:
+                raise ValueError("lpcSynthesisTensor: coefficients %s for %d rows of at most %d steps" % (list(lpc.shape), src.n, most))
+            cstride = int(lpc.shape[1])
+            if cstride == 0:      # (no row has a step: nothing is read)
+                cstride = 1
+        else:
+            if lpc.shape[0] < int(steps.sum()):
+                raise ValueError("lpcSynthesisTensor: coefficients %s for %d steps" % (list(lpc.shape), int(steps.sum())))
+            cstride = 0
+
+        def call(out, stride, numel, stream):
+            return export(order, hop, phase, lpc.data_ptr() if lpc.numel() else None, 1 if lpc.dtype == torch.float32 else 0, cols, column, cstride, out, fmt,
                           stride, stream)
         return self._export_rows(src.lengths, (), torch.float32 if fmt else torch.int16, padded, call)
 

@@ -8,7 +8,12 @@ with events on torch's stream over REPS launches after WARM warm-ups, the export
 (min, max) of each.  Two rows of every case are checked against the host's statement.  The operations counted are the binary64
 multiply-adds the definition needs: nWin (order + 1) for the lags and order^2 for the recursion per step, order per sample for the
 inverse filter.  No target is set in advance.
-Usage: python tools/lpc_probe.py [n_utt]"""
+The synthesis row (speechPlayer_batch_exportLpcSynthesisOf; csrc/klatt_lpcsynth.h) needs no batch content: a float32 signal of `rows` rows
+of 16 000 samples (1 s at 16 kHz) of noise through 1 / A(z) of order 16 at hop 160, float32 coefficients of stable random filters, float32
+out, beside filteredTensor with 8 resonator sections on the same rows -- the other lane-per-row recursion, with a comparable count of
+dependent multiply-adds per sample (16 binary64 against 8 x 5 binary32, two of the five on the critical path of each section).
+Usage: python tools/lpc_probe.py [n_utt]
+       python tools/lpc_probe.py synthesis [rows]"""
 import json
 import os
 import sys
@@ -20,7 +25,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import nvspeechplayer_amd as eng  # noqa: E402
 from nvspeechplayer_amd import workloads  # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
+synthesis_only = len(sys.argv) > 1 and sys.argv[1] == "synthesis"
+n = int(sys.argv[2 if synthesis_only else 1]) if len(sys.argv) > (2 if synthesis_only else 1) else (4096 if synthesis_only else 65536)
 WARM, REPS = 3, 10
 
 
@@ -52,6 +58,34 @@ def same(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
+def synthesis_row(rows, length=16000, order=16, hop=160):
+    bp = eng.BatchPlayer(16000)
+    dev = "cuda:%d" % bp.device
+    rng = np.random.default_rng(1)
+    steps = -(-length // hop)
+    bank = np.array([eng.lpcFromReflection(rng.uniform(-0.9, 0.9, order)) for _ in range(512)], np.float32)
+    lpc = torch.from_numpy(bank[rng.integers(0, 512, (rows, steps))]).to(dev)
+    x = torch.from_numpy((rng.standard_normal((rows, length)) * 0.01).astype(np.float32)).to(dev)
+    signal = (x, torch.full((rows,), length, dtype=torch.int64))
+    centres = np.array([500.0, 900.0, 1500.0, 2100.0, 2500.0, 3300.0, 4200.0, 5000.0])
+    sections = eng.resonatorSections(centres, 80.0 + 0.02 * centres, 16000)
+    kw = dict(order=order, hop=hop)
+    got, lens = bp.lpcSynthesisTensor(lpc[:2].contiguous(), utterances=np.arange(2), signal=signal, **kw)
+    two = x[:2].cpu().numpy()
+    ok = all(same(got[u].cpu().numpy(), eng.signalLpcSynthesis(two[u], lpc[u].cpu().numpy(), hop=hop)) for u in range(2))
+    del got
+    med, ms = pair(bp, lambda: bp.lpcSynthesisTensor(lpc, signal=signal, **kw)[0], "filtered_8_sections", lambda: bp.filteredTensor(sections, signal=signal)[0])
+    samples = rows * length
+    print(json.dumps({"case": "synthesis", "order": order, "hop": hop, "rows": rows, "samples": samples, "in": "float32", "coefficients": "float32", "out": "float32",
+                      "statement_bits": ok, "ms": ms, "export_over_filtered": round(med["export"] / med["filtered_8_sections"], 3),
+                      "samples_per_second": float("%.4g" % (samples / (med["export"] * 1e-3))), "f64_fma_per_second": float("%.4g" % (samples * order / (med["export"] * 1e-3))),
+                      "filtered_samples_per_second": float("%.4g" % (samples / (med["filtered_8_sections"] * 1e-3)))}), flush=True)
+    bp.close()
+
+
+if synthesis_only:
+    synthesis_row(n)
+    sys.exit(0)
 bp = eng.BatchPlayer(22050)
 bp.setIpa(**workloads.cfg2_spec(n))
 bp.synthesize()
@@ -82,3 +116,4 @@ for hop in (256, 8):
                           "f64_fma_per_second": float("%.4g" % (samples * 16 / (med["export"] * 1e-3)))}), flush=True)
         del lpc
 bp.close()
+synthesis_row(4096)
